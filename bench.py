@@ -20,7 +20,13 @@ algorithm issues more Scene::Intersect calls than that: the production path sett
 answer cannot reach the image -- those are NOT in `value`; the rate that counts them is reported beside
 it as `config.reference_queries_mrays_s`, and `config.msamples_per_s` is the rate of finished camera samples.
 
-The printed JSON line carries
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`,
+`image_mean_rgb`).  `--dump-outputs DIR` also writes what the last timed step returned, for comparing two builds output for
+output: DIR/accum.npy, the [H, W, 4] float32 film accumulator agpt_render filled (a seeded sample of its pixels,
+accum_sample.npy + accum_sample_pixels.npy, where the film exceeds 64 MB), and DIR/ray_counts.npy, the step's closest /
+any-hit / answered ray counts (float64, summed over ranks).
+
+`--full` adds the measurements that take runs of their own; with it the printed JSON line also carries
   * `roofline` for the dominant kernels (the persistent trace kernels k_trace_fast<closest / MIS query / any-hit>, timed
     live per launch with HIP events on the launch stream).  Top level: the HBM view -- achieved = the MEASURED memory-side
     rate (bytes per traversed ray from the committed rocprofv3 TCC passes of this exact kernel build and workload,
@@ -33,8 +39,10 @@ The printed JSON line carries
     match the running kernel build / workload;
   * `secondary`: the same measurement on BASELINE configs[4]'s 5 M-triangle scene (1080p / 64 spp), whose 0.46 GB of
     trace-time data exceeds the 256 MiB Infinity Cache;
+  * `all_rays_traversed`: the same workload with every ray query of the reference traversed;
   * `cpu_baseline`: the CPU oracle timed on this host's cores on a bounded sample of the same workload -- a reported
     baseline, not the thing measured.
+`--no-secondary` leaves out `secondary` and `all_rays_traversed`, `--no-cpu-baseline` the CPU baseline.
 """
 import argparse
 import glob
@@ -254,6 +262,23 @@ def roofline_block(sums, cst, rays, steps, workload_key):
     }
 
 
+DUMP_SAMPLE_PIXELS = 2_000_000    # 48 MB of pixels + indices: a film above 64 MB (4K) is dumped as this fixed sample
+
+
+def dump_outputs(out_dir, a, ray_counts):
+    """--dump-outputs: the last timed step's film accumulator (numpy [H, W, 4] float32) and ray counts as .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if a.nbytes <= (64 << 20) - 4096:
+        np.save(os.path.join(out_dir, "accum.npy"), a)
+    else:
+        flat = a.reshape(-1, a.shape[-1])
+        idx = np.sort(np.random.RandomState(0).choice(flat.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "accum_sample.npy"), flat[idx])
+        np.save(os.path.join(out_dir, "accum_sample_pixels.npy"), idx.astype(np.float64))   # row-major index into [H, W]
+    np.save(os.path.join(out_dir, "ray_counts.npy"), np.asarray(ray_counts, np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -267,8 +292,13 @@ def main():
     ap.add_argument("--scene-scale", type=float, default=1.0)
     ap.add_argument("--workload", default="c3", choices=["c3", "c5"],
                     help="c3 = the BASELINE metric's configuration (default); c5 = the 5M-triangle multi-mesh scene")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C5 secondary measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: roofline (counter pass), all-rays-traversed run, C5 "
+                         "secondary, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's film accumulator and ray counts to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the all-rays-traversed and C5 secondary measurements")
     ap.add_argument("--samples-per-batch", type=int, default=0)
     ap.add_argument("--gather", default="agpt", choices=["agpt", "torch"],
                     help="N > 1: agpt = the library's own collective agpt_gather_tiles (RCCL grouped send/recv + de-interleave "
@@ -373,7 +403,7 @@ def main():
         return tiles.gather_to_rank0(local, W, H, rank, world, out_bufs=gather_bufs)
 
     def measure(desc, steps, warmup, spp_, do_gather, trace_all=False):
-        """warmup + `steps` timed passes over one workload; returns (dt, sums, scene, last full accumulator)."""
+        """warmup + `steps` timed passes over one workload; returns (dt, sums, scene, last full accumulator, last step's counts)."""
         scene = desc.instantiate(ag.Scene(ctx))
 
         def step(timing):
@@ -391,8 +421,10 @@ def main():
         t0 = time.perf_counter()
         acc = None
         sums = None
+        last = None
         for _ in range(steps):
             tot, full = step(True)
+            last = dict(tot)
             if sums is None:
                 sums = tot
             else:
@@ -401,7 +433,7 @@ def main():
             acc = full
         barrier()
         dt = time.perf_counter() - t0
-        return dt, sums, scene, acc
+        return dt, sums, scene, acc, last
 
     def rates(sums, dt, steps, samples_per_step):
         """The three rates of one measurement (this process' rays; the headline sums over ranks below)."""
@@ -424,7 +456,7 @@ def main():
         wl_name = "BASELINE configs[2]: Sponza-class closed atrium"
     wl_key = "%s:%dx%d:%dspp:world%d:scale%g" % (args.workload, W, H, spp, world, args.scene_scale)
 
-    dt, sums, scene, acc = measure(desc, args.steps, args.warmup, spp, True)
+    dt, sums, scene, acc, last = measure(desc, args.steps, args.warmup, spp, True)
 
     queries_local = float(sums["closest"] + sums["anyhit"])
     traversed_local = queries_local - float(sums["answered"])
@@ -438,10 +470,19 @@ def main():
     queries_total, answered_total = float(r_all[0].item()), float(r_all[1].item())
     traversed_total = queries_total - answered_total
 
+    if args.dump_outputs:
+        c_all = torch.tensor([float(last["closest"]), float(last["anyhit"]), float(last["answered"])], dtype=torch.float64, device=dev)
+        if world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(c_all, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, acc.cpu().numpy(), c_all.cpu().numpy())
+
     if rank == 0:
-        # counter pass outside the timed region: the production kernels count the records they fetch on a 2-spp sample of
-        # the same film (per-ray work is deterministic per scene + seed)
-        cst = pt.render(scene, W, H, min(spp, 2), local.data_ptr(), accum_pitch=W, counters=2, interleave=interleave)
+        if args.full:
+            # counter pass outside the timed region: the production kernels count the records they fetch on a 2-spp sample of
+            # the same film (per-ray work is deterministic per scene + seed)
+            cst = pt.render(scene, W, H, min(spp, 2), local.data_ptr(), accum_pitch=W, counters=2, interleave=interleave)
         img_mean = acc[..., :3].double().mean(dim=(0, 1)).div(spp).tolist() if acc is not None else None
         out = {
             "metric": "Mrays/sec (primary+secondary) at 1080p/64spp", "value": round(traversed_total / dt_max / 1e6, 2),
@@ -471,24 +512,25 @@ def main():
                 "reference_queries_mrays_s": round(queries_total / dt_max / 1e6, 2),
                 "msamples_per_s": round(W * H * spp * args.steps / dt_max / 1e6, 2),
             },
-            "roofline": roofline_block(sums, cst, traversed_local, args.steps, wl_key),
-            "image_mean_rgb": [round(x, 6) for x in img_mean] if img_mean else None,
         }
+        if args.full:
+            out["roofline"] = roofline_block(sums, cst, traversed_local, args.steps, wl_key)
+        out["image_mean_rgb"] = [round(x, 6) for x in img_mean] if img_mean else None
     scene.close()
 
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         # the same workload with every ray query of the reference sent through the BVH (agpt_render_params::trace_all_rays):
         # the image and the query totals are identical; the queries that cannot reach the image are traversed too
-        dta, sumsa, scenea, _ = measure(desc, args.steps, args.warmup, spp, False, trace_all=True)
+        dta, sumsa, scenea, _, _ = measure(desc, args.steps, args.warmup, spp, False, trace_all=True)
         out["all_rays_traversed"] = dict(rates(sumsa, dta, args.steps, W * H * spp), warmup=args.warmup,
             note="agpt_render_params::trace_all_rays = 1: every Scene::Intersect / IntersectP call of the reference goes through the "
                  "BVH (the headline run settles the ones whose result cannot reach the image without a traversal, DESIGN.md 5.0)")
         scenea.close()
 
-    if world == 1 and args.workload == "c3" and not args.no_secondary:
+    if args.full and world == 1 and args.workload == "c3" and not args.no_secondary:
         # BASELINE configs[4]'s scene on the same film: the configuration whose trace-time data exceeds the Infinity Cache
         desc5 = ag.scenes.scene_c5(aspect=W / float(H))
-        dt5, sums5, scene5, _ = measure(desc5, args.steps, args.warmup, spp, False)
+        dt5, sums5, scene5, _, _ = measure(desc5, args.steps, args.warmup, spp, False)
         cst5 = pt.render(scene5, W, H, min(spp, 2), local.data_ptr(), accum_pitch=W, counters=2)
         trav5 = float(sums5["closest"] + sums5["anyhit"] - sums5["answered"])
         out["secondary"] = dict(rates(sums5, dt5, args.steps, W * H * spp), warmup=args.warmup,
@@ -499,7 +541,7 @@ def main():
         scene5.close()
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(desc, W, H, MAXD)
         print(json.dumps(out))
         sys.stdout.flush()

@@ -42,3 +42,28 @@ def test_kernel_build_id_covers_every_kernel_source():
     assert "csrc" in src and "build.py" in src
     a = bench.kernel_build_id()
     assert len(a) == 16 and a == bench.kernel_build_id()
+
+
+def test_dump_outputs_writes_the_film_and_the_ray_counts(tmp_path):
+    import numpy as np
+    acc = np.arange(6 * 5 * 4, dtype=np.float32).reshape(6, 5, 4)
+    bench.dump_outputs(str(tmp_path / "out"), acc, [7, 5, 3])
+    a = np.load(tmp_path / "out" / "accum.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, acc)
+    c = np.load(tmp_path / "out" / "ray_counts.npy")
+    assert c.dtype == np.float64 and c.tolist() == [7.0, 5.0, 3.0]
+
+
+def test_dump_outputs_samples_a_film_above_64_mb_the_same_way_every_time(tmp_path):
+    import numpy as np
+    H, W = 2160, 3840
+    acc = np.repeat(np.arange(H * W, dtype=np.float32).reshape(H, W, 1), 4, axis=2)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), acc, [1, 2, 3])
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["accum_sample.npy", "accum_sample_pixels.npy", "ray_counts.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+    s, i = np.load(tmp_path / "a" / "accum_sample.npy"), np.load(tmp_path / "a" / "accum_sample_pixels.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and len(s) == len(i) == bench.DUMP_SAMPLE_PIXELS
+    assert np.array_equal(s[:, 0], i.astype(np.float32)) and np.all(np.diff(i) > 0)
+    assert np.array_equal(i, np.load(tmp_path / "b" / "accum_sample_pixels.npy"))

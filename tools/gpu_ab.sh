@@ -1,8 +1,9 @@
 # bench.py once per environment setting (A/B of run-time knobs and AGPT_LIB_VARIANT builds): bash tools/gpu_ab.sh "ENV=.." ...
 # AB_ARGS: extra bench.py arguments (default: the C3 headline workload), AB_STEPS: timed steps (default 3)
 set -e
-cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+cd "$(dirname "$0")/.."
+OUT=${AGPT_OUT:-out}   # where the logs go (relative to the repository root)
+mkdir -p $OUT
 show() { python - "$1" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -14,7 +15,7 @@ PY
 }
 for cfg in "$@"; do
   echo "== $cfg"
-  env $cfg python bench.py --steps ${AB_STEPS:-3} --warmup 1 --no-cpu-baseline --no-secondary $AB_ARGS > gpurun_out/ab.log 2> gpurun_out/ab.err || { tail -20 gpurun_out/ab.err; exit 1; }
-  show gpurun_out/ab.log
-  grep "trace clock\|trace stats\|shade clock" gpurun_out/ab.err | cut -c1-400 || true
+  env $cfg python bench.py --full --steps ${AB_STEPS:-3} --warmup 1 --no-cpu-baseline --no-secondary $AB_ARGS > $OUT/ab.log 2> $OUT/ab.err || { tail -20 $OUT/ab.err; exit 1; }
+  show $OUT/ab.log
+  grep "trace clock\|trace stats\|shade clock" $OUT/ab.err | cut -c1-400 || true
 done
