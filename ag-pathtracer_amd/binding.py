@@ -18,6 +18,9 @@ MAT_DISNEY, MAT_MIRROR, MAT_DIFFUSE_ONLY = 0, 1, 2
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("tmax", np.float32)])
 HIT_DTYPE = np.dtype([("hit", np.int32), ("prim", np.int32), ("tri", np.int32),
                       ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
+# agpt_scene_set_bvh_builder; work tiers of agpt_bvh_build_device (include/agpt.h)
+BVH_BUILDER_HOST, BVH_BUILDER_DEVICE = 0, 1
+BVH_DEVICE_LANE_MAX, BVH_DEVICE_CHUNK = 64, 2048
 NODE_DTYPE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("first", np.int32), ("count", np.int32)])
 
 # every symbol include/agpt.h declares (tests check the library exports all of them)
@@ -26,7 +29,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_li_batch", "agpt_resolve", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -113,6 +116,9 @@ def lib():
     L.agpt_mesh_num_prims.argtypes = [vp, C.c_int]
     L.agpt_mesh_get_bvh.argtypes = [vp, C.c_int, vp, ip]
     L.agpt_bvh_build.argtypes = [fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
+    L.agpt_bvh_build_device.argtypes = [vp, fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int)]
     L.agpt_toplevel_build.argtypes = [fp, C.c_int, fp]
     L.agpt_toplevel_pack16.argtypes = [fp, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_create_backdrop.argtypes = [fp, fp, C.c_float, C.c_int, fp, fp, fp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -228,6 +234,21 @@ def bvh_build(verts, indices, max_prims_in_node=1):
                                 order.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(total), C.byref(depth)),
            "agpt_bvh_build")
     return nodes[:total.value + 1].copy(), order, depth.value
+
+
+def bvh_build_device(ctx, verts, indices, max_prims_in_node=1):
+    """agpt_bvh_build_device: bvh_build on the context's GPU, the same bytes -> (nodes[total+1], prim_index[n_tris], max_depth,
+    on_device); on_device is 0 when non-finite input made the library run the host builder."""
+    v, pv = _f(np.asarray(verts).reshape(-1, 3))
+    ix, pi = _i(np.asarray(indices).reshape(-1, 3))
+    n_tris = ix.shape[0] // 3
+    nodes = np.zeros(2 * n_tris + 2, NODE_DTYPE)
+    order = np.zeros(n_tris, np.int32)
+    total, depth, on_device = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(ctx.L.agpt_bvh_build_device(ctx.h, pv, v.shape[0], pi, ix.shape[0], int(max_prims_in_node), nodes.ctypes.data_as(C.c_void_p),
+                                       order.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(total), C.byref(depth), C.byref(on_device)),
+           "agpt_bvh_build_device")
+    return nodes[:total.value + 1].copy(), order, depth.value, on_device.value
 
 
 def load_obj(path=None, text=None, transform=None, ignore_normals=False):
@@ -423,6 +444,11 @@ class Scene:
         return _check(self.L.agpt_scene_add_mesh(self.h, pv, v.shape[0], pn, n.shape[0], pt, t.shape[0], pi,
                                                  ix.shape[0], int(material), int(max_prims_in_node)),
                       "agpt_scene_add_mesh")
+
+    def set_bvh_builder(self, builder):
+        """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""
+        code = {"host": BVH_BUILDER_HOST, "device": BVH_BUILDER_DEVICE}[builder]
+        _check(self.L.agpt_scene_set_bvh_builder(self.h, code), "agpt_scene_set_bvh_builder")
 
     def add_sphere(self, center, radius, material):
         _, p = _f(center)

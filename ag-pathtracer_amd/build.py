@@ -10,10 +10,10 @@ LIB = os.path.join(HERE, "libagpt_hip.so")
 # path loop and keeps the pairs live for the whole kernel (168 registers + 7-14 spilled against 134 + 0; at the 128 of four waves
 # 2 spilled).  Measured on C3: k_shade -3.5 ms per step; the same flag on the trace kernels costs them 2 ms, hence two units.
 SHADE_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
-SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_bvh_device.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {"agpt_shade_kernels.hip": SHADE_FLAGS}
 HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h",
-           "agpt_host_scene.hpp", os.path.join("..", "..", "include", "agpt.h")]
+           "agpt_host_scene.hpp", "agpt_bvh_device.h", os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);
 # explicit __builtin_fmaf calls (Markstein division in agpt_trace.h) stay fused.
 # -fno-slp-vectorize: the SLP pass packs adjacent f32 adds/muls into v_pk_*_f32, which on gfx950 cost more than the two

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/agpt.h"
+#include "agpt_bvh_device.h"
 #include "agpt_host_scene.hpp"
 #include "agpt_kernels.h"
 
@@ -129,6 +130,7 @@ struct agpt_scene {
     bool has_camera = false;
     bool committed = false;
     int max_depth = 0;
+    int bvh_builder = AGPT_BVH_BUILDER_HOST;  // agpt_scene_set_bvh_builder
     DevBuf<float4> d_nodes, d_tri_verts, d_tri_shade, d_prefilter;
     DevBuf<uint32_t> d_toplevel;
     DevBuf<unsigned long long> d_chunk_mesh_masks;
@@ -413,7 +415,20 @@ int agpt_scene_add_mesh(agpt_scene* s, const float* vertices, int n_vertices, co
     }
     m.indices.assign(indices, indices + (size_t)3 * n_indices);
     m.material = material;
-    agpt::build_bvh(m, max_prims_in_node);
+    if (s->bvh_builder == AGPT_BVH_BUILDER_DEVICE) {
+        // same bytes as build_bvh (agpt_bvh_device.hip)
+        HIP_TRY(hipSetDevice(s->ctx->device));
+        const int n_tris = n_indices / 3;
+        m.nodes.resize((size_t)2 * n_tris + 2);
+        m.prim_index.resize(n_tris);
+        int on_device = 0;
+        const int rc = agpt::build_bvh_device(s->ctx->stream, vertices, n_vertices, indices, n_tris, max_prims_in_node, m.nodes.data(),
+                                              m.prim_index.data(), &m.total_nodes, &m.max_depth, &on_device);
+        if (rc != AGPT_OK) return rc;
+        m.nodes.resize((size_t)m.total_nodes + 1);
+    } else {
+        agpt::build_bvh(m, max_prims_in_node);
+    }
     s->meshes.push_back(std::move(m));
     agpt::HostPrim p;
     p.type = AGPT_PRIM_MESH;
@@ -626,6 +641,34 @@ int agpt_bvh_build(const float* vertices, int n_vertices, const int32_t* indices
     if (prim_index_out) std::memcpy(prim_index_out, m.prim_index.data(), m.prim_index.size() * sizeof(int32_t));
     if (total_nodes_out) *total_nodes_out = m.total_nodes;
     if (max_depth_out) *max_depth_out = m.max_depth;
+    return AGPT_OK;
+}
+
+int agpt_scene_set_bvh_builder(agpt_scene* s, int builder) {
+    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_set_bvh_builder: NULL scene");
+    if (builder != AGPT_BVH_BUILDER_HOST && builder != AGPT_BVH_BUILDER_DEVICE)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_bvh_builder: unknown builder " + std::to_string(builder));
+    s->bvh_builder = builder;
+    return AGPT_OK;
+}
+
+int agpt_bvh_build_device(agpt_ctx* c, const float* vertices, int n_vertices, const int32_t* indices, int n_indices,
+                          int max_prims_in_node, agpt_bvh_node* nodes_out, int32_t* prim_index_out, int* total_nodes_out,
+                          int* max_depth_out, int* on_device_out) {
+    if (!c) return fail(AGPT_ERR_INVALID, "agpt_bvh_build_device: NULL context");
+    if (!vertices || !indices || n_vertices <= 0 || n_indices < 3 || n_indices % 3 != 0)
+        return fail(AGPT_ERR_INVALID, "agpt_bvh_build_device: need at least one triangle");
+    for (int i = 0; i < n_indices; i++)
+        if (indices[3 * i] < 0 || indices[3 * i] >= n_vertices)
+            return fail(AGPT_ERR_INVALID, "agpt_bvh_build_device: vertex index out of range");
+    HIP_TRY(hipSetDevice(c->device));
+    int total = 0, depth = 0, on_device = 0;
+    const int rc = agpt::build_bvh_device(c->stream, vertices, n_vertices, indices, n_indices / 3, max_prims_in_node, nodes_out,
+                                          prim_index_out, &total, &depth, &on_device);
+    if (rc != AGPT_OK) return rc;
+    if (total_nodes_out) *total_nodes_out = total;
+    if (max_depth_out) *max_depth_out = depth;
+    if (on_device_out) *on_device_out = on_device;
     return AGPT_OK;
 }
 

@@ -163,6 +163,19 @@ int agpt_mesh_get_bvh(const agpt_scene*, int prim, agpt_bvh_node* nodes_out, int
  * written, slot 1 unused); prim_index_out n_indices/3 entries.  Either output may be NULL. */
 int agpt_bvh_build(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int max_prims_in_node,
                    agpt_bvh_node* nodes_out, int32_t* prim_index_out, int* total_nodes_out, int* max_depth_out);
+/* Which builder agpt_scene_add_mesh uses for the BVH of later meshes on this scene (default HOST).  Both produce the same
+ * bytes; DEVICE runs agpt_bvh_build_device on the scene's context. */
+enum { AGPT_BVH_BUILDER_HOST = 0, AGPT_BVH_BUILDER_DEVICE = 1 };
+int agpt_scene_set_bvh_builder(agpt_scene*, int builder);
+/* agpt_bvh_build on the context's GPU: same arguments, same outputs byte for byte; synchronises with the context's stream.
+ * *on_device_out (may be NULL) is 0 when a referenced coordinate is non-finite or the mesh's extent overflows: then the host
+ * builder ran (the device folds are exact only on finite input).  HIP errors return AGPT_ERR_DEVICE / AGPT_ERR_NOMEM. */
+int agpt_bvh_build_device(agpt_ctx*, const float* vertices, int n_vertices, const int32_t* indices, int n_indices,
+                          int max_prims_in_node, agpt_bvh_node* nodes_out, int32_t* prim_index_out, int* total_nodes_out,
+                          int* max_depth_out, int* on_device_out);
+/* Work tiers of the device builder: nodes of up to LANE_MAX primitives are built whole by one lane; larger ones level by level,
+ * one 64-lane block per CHUNK primitives. */
+enum { AGPT_BVH_DEVICE_LANE_MAX = 64, AGPT_BVH_DEVICE_CHUNK = 2048 };
 /* The top-level structure the library builds over Scene::primitives (scene.h:5-19) when the list is longer than 64 entries,
  * host-only (no GPU, no context): a binary tree over n boxes (6 floats each: bmin.xyz, bmax.xyz) in depth-first order with
  * skip links.  Writes 2n-1 nodes of 8 floats -- (bmin.xyz, uint32 index of the node after this node's subtree), (bmax.xyz,

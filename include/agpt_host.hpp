@@ -135,6 +135,9 @@ private:
 };
 using CameraDesc = agpt_camera_desc;
 
+// agpt_scene_set_bvh_builder: where the BVH of later primitives_push_back(mesh) calls is built; both give the same bytes
+enum class BvhBuilder { Host = AGPT_BVH_BUILDER_HOST, Device = AGPT_BVH_BUILDER_DEVICE };
+
 class Scene {
 public:
     explicit Scene(Context& ctx) : ctx_(ctx) {
@@ -149,6 +152,7 @@ public:
         const float c[3] = {color.x, color.y, color.z};
         return check(agpt_scene_add_material(h_, type, c, roughness, metallic), "agpt_scene_add_material");
     }
+    void SetBvhBuilder(BvhBuilder b) { check(agpt_scene_set_bvh_builder(h_, (int)b), "agpt_scene_set_bvh_builder"); }
     // scene->primitives.push_back(make_shared<BVHTriMesh>(mesh, material, maxPrimsInNode))
     int primitives_push_back(const TriangleMesh& m, int material, int maxPrimsInNode = 1) {
         return check(agpt_scene_add_mesh(h_, m.vertices.data(), (int)m.vertices.size() / 3, m.normals.data(),

@@ -1,0 +1,215 @@
+"""The device BVH builder (agpt_bvh_build_device, Scene.set_bvh_builder("device")) against the host builder: the same node
+bytes, primitive order, node count and depth for every input, and everything downstream unchanged."""
+import numpy as np
+import pytest
+
+import ag_pathtracer_amd as ag
+from helpers import gpu_context, oracle_scene, random_rays
+from oracle import binding as ob
+
+pytestmark = pytest.mark.gpu
+
+
+def mesh_ops(desc):
+    return [(op[1], op[4]) for op in desc.ops if op[0] == "mesh"]
+
+
+def check_same(verts, idx, mp=1, expect_device=1):
+    hn, ho, hd = ag.bvh_build(verts, idx, mp)
+    dn, do, dd, on_dev = ag.bvh_build_device(gpu_context(), verts, idx, mp)
+    assert on_dev == expect_device
+    assert len(dn) == len(hn), (len(dn), len(hn))
+    assert dn.tobytes() == hn.tobytes()
+    assert np.array_equal(do, ho) and dd == hd
+    return hn
+
+
+def soup(n, rng, kind):
+    if kind == "uniform":
+        c = rng.uniform(-1, 1, (n, 3))
+    elif kind == "clustered":
+        centers = rng.uniform(-10, 10, (8, 3))
+        c = centers[rng.randint(0, 8, n)] + rng.normal(scale=0.05, size=(n, 3))
+    else:  # elongated
+        c = rng.uniform(-1, 1, (n, 3)) * np.array([100.0, 0.01, 1.0])
+    v = (c[:, None, :] + rng.normal(scale=0.02, size=(n, 3, 3))).reshape(-1, 3).astype(np.float32)
+    idx = np.zeros((3 * n, 3), np.int32)
+    idx[:, 0] = np.arange(3 * n)
+    return v, idx
+
+
+@pytest.mark.parametrize("name", ["c1", "c2", "c3", "c5"])
+def test_scene_meshes_all_leaf_sizes(name):
+    desc = getattr(ag.scenes, "scene_" + name)()
+    for verts, idx in mesh_ops(desc):
+        for mp in (1, 2, 4, 8):
+            check_same(verts, idx, mp)
+
+
+def test_five_million_triangle_heightfield():
+    v, _, _, idx = ag.scenes.heightfield(1581)
+    assert idx.shape[0] // 3 == 4999122
+    check_same(v, idx)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 12, 13, 64])
+def test_small_meshes(n):
+    rng = np.random.RandomState(n)
+    check_same(*soup(n, rng, "uniform"))
+
+
+def test_tier_thresholds():
+    rng = np.random.RandomState(7)
+    for t in (ag.BVH_DEVICE_LANE_MAX, ag.BVH_DEVICE_CHUNK, 2 * ag.BVH_DEVICE_CHUNK):
+        for n in (t - 1, t, t + 1):
+            for kind in ("uniform", "clustered"):
+                for mp in (1, 4):
+                    check_same(*soup(n, rng, kind), mp)
+
+
+def test_identical_triangles_one_big_leaf():
+    n = 5000
+    v = np.tile(np.float32([[0, 0, 0], [1, 0, 0], [0, 1, 0]]), (n, 1))
+    idx = np.zeros((3 * n, 3), np.int32)
+    idx[:, 0] = np.arange(3 * n)
+    nodes = check_same(v, idx)
+    assert len(nodes) == 2 and nodes[0]["count"] == n
+
+
+def test_equal_centroids_in_two_triangle_nodes():
+    # pairs of triangles with the same centroid along x, different along the others
+    n = 3000
+    rng = np.random.RandomState(3)
+    base = rng.uniform(-5, 5, (n // 2, 3)).astype(np.float32)
+    tris = []
+    for b in base:
+        for dz in (0.0, 0.25):
+            p = b + np.float32([0, 0, dz])
+            tris.append([p, p + np.float32([0.1, 0, 0]), p + np.float32([0, 0.1, 0.01])])
+    v = np.asarray(tris, np.float32).reshape(-1, 3)
+    idx = np.zeros((v.shape[0], 3), np.int32)
+    idx[:, 0] = np.arange(v.shape[0])
+    for mp in (1, 2):
+        check_same(v, idx, mp)
+
+
+def test_signed_zero_grid():
+    n = 60
+    g = np.linspace(-1, 1, n + 1).astype(np.float32)
+    X, Z = np.meshgrid(g, g, indexing="ij")
+    Y = np.where((np.arange(X.size) % 3).reshape(X.shape) == 0, np.float32(-0.0), np.float32(0.0))
+    X = np.where(X == 0, np.float32(-0.0), X)
+    verts = np.stack([X, Y, Z], -1).reshape(-1, 3).astype(np.float32)
+    tri = []
+    for i in range(n):
+        for j in range(n):
+            a, b, c, d = i * (n + 1) + j, (i + 1) * (n + 1) + j, i * (n + 1) + j + 1, (i + 1) * (n + 1) + j + 1
+            tri += [a, b, c, c, b, d]
+    idx = np.zeros((len(tri), 3), np.int32)
+    idx[:, 0] = tri
+    assert np.signbit(verts).any()
+    for mp in (1, 2):
+        check_same(verts, idx, mp)
+
+
+def test_degenerate_unused_and_out_of_order_vertices():
+    rng = np.random.RandomState(11)
+    n = 4000
+    v = rng.uniform(-3, 3, (3 * n + 500, 3)).astype(np.float32)
+    v[7] = np.float32(np.nan)  # unused vertex: ignored
+    perm = rng.permutation(3 * n + 500)
+    perm = perm[perm != 7][:3 * n]
+    idx = np.zeros((3 * n, 3), np.int32)
+    idx[:, 0] = perm
+    idx[0:300, 0] = idx[0, 0]  # 100 zero-area triangles on one point
+    idx[300:600:3, 0] = idx[301:601:3, 0]  # and 100 with two equal corners
+    check_same(v, idx)
+
+
+def test_random_soups():
+    rng = np.random.RandomState(5)
+    for kind in ("clustered", "uniform", "elongated"):
+        for n in (1000, 50000):
+            check_same(*soup(n, rng, kind), 1)
+            check_same(*soup(n, rng, kind), 4)
+
+
+def test_non_finite_input_runs_host_builder():
+    rng = np.random.RandomState(9)
+    v, idx = soup(3000, rng, "uniform")
+    v1 = v.copy()
+    v1[100, 1] = np.float32(np.nan)
+    check_same(v1, idx, 1, expect_device=0)
+    v2 = v.copy()
+    v2[0] = [-3e38, 0, 0]
+    v2[1] = [3e38, 0, 0]
+    check_same(v2, idx, 1, expect_device=0)
+
+
+def test_repeated_builds_are_identical():
+    desc = ag.scenes.scene_c5()
+    verts, idx = max(mesh_ops(desc), key=lambda m: m[1].shape[0])
+    a = ag.bvh_build_device(gpu_context(), verts, idx, 1)
+    b = ag.bvh_build_device(gpu_context(), verts, idx, 1)
+    assert a[3] == 1 and a[0].tobytes() == b[0].tobytes() and np.array_equal(a[1], b[1]) and a[2] == b[2]
+
+
+def device_scene(desc):
+    s = ag.Scene(gpu_context())
+    s.set_bvh_builder("device")
+    return desc.instantiate(s)
+
+
+@pytest.mark.parametrize("name", ["c3", "c5"])
+def test_scene_bvh_builder_device_same_trees(name):
+    desc = getattr(ag.scenes, "scene_" + name)()
+    h = desc.instantiate(ag.Scene(gpu_context()))
+    d = device_scene(desc)
+    for prim in range(desc.n_prims):
+        if h.L.agpt_mesh_num_nodes(h.h, prim) < 0:  # not a mesh
+            continue
+        hn, ho = h.bvh(prim)
+        dn, do = d.bvh(prim)
+        assert hn.tobytes() == dn.tobytes() and np.array_equal(ho, do)
+    h.close()
+    d.close()
+
+
+def test_c3_render_and_rays_with_device_built_scene():
+    desc = ag.scenes.scene_c3()
+    h = desc.instantiate(ag.Scene(gpu_context()))
+    d = device_scene(desc)
+    pt = ag.PathTracer(5)
+    ha, hs = pt.render_to_host(h, 480, 270, 4)
+    da, ds = pt.render_to_host(d, 480, 270, 4)
+    assert ha.tobytes() == da.tobytes() and hs.rays == ds.rays
+    rays = random_rays(desc, 200000, seed=3)
+    o = oracle_scene(desc)
+    dh, _ = d.Intersect(rays)
+    oh, _ = o.intersect(rays, any_hit=False)
+    assert dh.tobytes() == oh.tobytes()
+    h.close()
+    d.close()
+
+
+def test_c1_device_built_render_matches_oracle():
+    desc = ag.scenes.scene_c1()
+    d = device_scene(desc)
+    acc, st = ag.PathTracer(5).render_to_host(d, 64, 64, 2)
+    o = desc.instantiate(ob.OracleScene())
+    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
+    try:
+        oacc, ost = o.render(64, 64, 2, rng_mode=ob.RNG_PER_SAMPLE, threads=4)
+    finally:
+        ob.set_trig_mode(ob.TRIG_LIBM)
+    assert np.array_equal(acc[..., :3].view(np.uint32), oacc[..., :3].view(np.uint32))
+    assert st.rays == ost.rays
+    d.close()
+
+
+def test_set_bvh_builder_rejects_unknown_values():
+    s = ag.Scene(gpu_context())
+    assert s.L.agpt_scene_set_bvh_builder(s.h, 2) == -1
+    with pytest.raises(KeyError):
+        s.set_bvh_builder("gpu")
+    s.close()

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--pfm", default=None, help="also write the linear float image")
+    ap.add_argument("--bvh-builder", default="host", choices=["host", "device"], help="where the mesh BVHs are built (same trees)")
     a = ap.parse_args()
     W, H = a.width, a.height
     aspect = W / float(H)
@@ -31,7 +32,9 @@ def main():
             "heightfield": lambda: ag.scenes.scene_heightfield(361, True, W, H)}[a.scene]()
     ctx = ag.Context(0)
     t0 = time.time()
-    scene = desc.instantiate(ag.Scene(ctx))
+    scene = ag.Scene(ctx)
+    scene.set_bvh_builder(a.bvh_builder)
+    scene = desc.instantiate(scene)
     print("scene build + BVH + upload: %.2f s" % (time.time() - t0))
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
