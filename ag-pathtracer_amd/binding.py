@@ -20,6 +20,8 @@ HIT_DTYPE = np.dtype([("hit", np.int32), ("prim", np.int32), ("tri", np.int32),
                       ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 # agpt_scene_set_bvh_builder; work tiers of agpt_bvh_build_device (include/agpt.h)
 BVH_BUILDER_HOST, BVH_BUILDER_DEVICE = 0, 1
+# agpt_scene_set_shading_arith (include/agpt.h)
+SHADING_EXACT, SHADING_FAST = 0, 1
 BVH_DEVICE_LANE_MAX, BVH_DEVICE_CHUNK = 64, 2048
 NODE_DTYPE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("first", np.int32), ("count", np.int32)])
 
@@ -29,7 +31,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_li_batch", "agpt_resolve", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -117,6 +119,7 @@ def lib():
     L.agpt_mesh_get_bvh.argtypes = [vp, C.c_int, vp, ip]
     L.agpt_bvh_build.argtypes = [fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
+    L.agpt_scene_set_shading_arith.argtypes = [vp, C.c_int]
     L.agpt_bvh_build_device.argtypes = [vp, fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(C.c_int)]
     L.agpt_toplevel_build.argtypes = [fp, C.c_int, fp]
@@ -449,6 +452,16 @@ class Scene:
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""
         code = {"host": BVH_BUILDER_HOST, "device": BVH_BUILDER_DEVICE}[builder]
         _check(self.L.agpt_scene_set_bvh_builder(self.h, code), "agpt_scene_set_bvh_builder")
+
+    def set_shading_arith(self, mode):
+        """agpt_scene_set_shading_arith: "exact" (default; bit-identical to the oracle) or "fast" (the path weights through the
+        hardware reciprocal / square root; the same rays, include/agpt.h) for the renders, Li and BSDF known-answer calls that
+        follow.  An integer is passed through as the C mode value."""
+        if isinstance(mode, str):
+            if mode not in ("exact", "fast"):
+                raise ValueError("set_shading_arith: unknown mode %r (exact, fast)" % mode)
+            mode = SHADING_EXACT if mode == "exact" else SHADING_FAST
+        _check(self.L.agpt_scene_set_shading_arith(self.h, int(mode)), "agpt_scene_set_shading_arith")
 
     def add_sphere(self, center, radius, material):
         _, p = _f(center)

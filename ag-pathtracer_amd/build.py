@@ -10,9 +10,13 @@ LIB = os.path.join(HERE, "libagpt_hip.so")
 # path loop and keeps the pairs live for the whole kernel (168 registers + 7-14 spilled against 134 + 0; at the 128 of four waves
 # 2 spilled).  Measured on C3: k_shade -3.5 ms per step; the same flag on the trace kernels costs them 2 ms, hence two units.
 SHADE_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
-SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_bvh_device.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
-SOURCE_FLAGS = {"agpt_shade_kernels.hip": SHADE_FLAGS}
-HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h",
+# agpt_shade_kernels_fast.hip -- the same kernels with the fast value arithmetic (k_shade_fast, ...; agpt_shade_arith.h) -- keeps
+# the exact unit's flags: the sampling trigonometry (fp64) is still there, and measured on C3 three waves without spills (133
+# registers) cost 3 ms of non-trace time per step against four waves with 2 spilled.
+SHADE_FAST_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
+SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_shade_kernels_fast.hip", "agpt_bvh_device.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+SOURCE_FLAGS = {"agpt_shade_kernels.hip": SHADE_FLAGS, "agpt_shade_kernels_fast.hip": SHADE_FAST_FLAGS}
+HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h", "agpt_shade_arith.h",
            "agpt_host_scene.hpp", "agpt_bvh_device.h", os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);
 # explicit __builtin_fmaf calls (Markstein division in agpt_trace.h) stay fused.

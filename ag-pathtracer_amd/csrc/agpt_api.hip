@@ -131,6 +131,7 @@ struct agpt_scene {
     bool committed = false;
     int max_depth = 0;
     int bvh_builder = AGPT_BVH_BUILDER_HOST;  // agpt_scene_set_bvh_builder
+    int shading_arith = AGPT_SHADING_EXACT;   // agpt_scene_set_shading_arith
     DevBuf<float4> d_nodes, d_tri_verts, d_tri_shade, d_prefilter;
     DevBuf<uint32_t> d_toplevel;
     DevBuf<unsigned long long> d_chunk_mesh_masks;
@@ -652,6 +653,14 @@ int agpt_scene_set_bvh_builder(agpt_scene* s, int builder) {
     return AGPT_OK;
 }
 
+int agpt_scene_set_shading_arith(agpt_scene* s, int mode) {
+    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_set_shading_arith: NULL scene");
+    if (mode != AGPT_SHADING_EXACT && mode != AGPT_SHADING_FAST)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_shading_arith: unknown mode " + std::to_string(mode));
+    s->shading_arith = mode;
+    return AGPT_OK;
+}
+
 int agpt_bvh_build_device(agpt_ctx* c, const float* vertices, int n_vertices, const int32_t* indices, int n_indices,
                           int max_prims_in_node, agpt_bvh_node* nodes_out, int32_t* prim_index_out, int* total_nodes_out,
                           int* max_depth_out, int* on_device_out) {
@@ -780,6 +789,7 @@ static int ensure_pool(agpt_ctx* c, size_t paths, int n_prims) {
 // round trip, then the loop keeps going while the active or the resolve queue is non-empty.
 struct WavefrontRun {
     bool mis_mode, timing, shade_lds_tables, shade_env;
+    bool shade_fast;        // agpt_scene_set_shading_arith(AGPT_SHADING_FAST): k_shade_fast, k_resolve_pending_fast
     int count;              // enable_counters, normalised
     uint64_t iterations = 0, launches = 0;
 };
@@ -859,10 +869,17 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, co
             trace_mis();
             trace_shadow();
         }
-        agpt::launch_shade(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p,
-                           c->work.p + 3 * AGPT_FRONTIERS * AGPT_QSTRIDE /* k_shade's tile heads, zeroed above */);
-        // (independent of k_shade: different paths)
-        agpt::launch_resolve_pending(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
+        uint32_t* const shade_heads = c->work.p + 3 * AGPT_FRONTIERS * AGPT_QSTRIDE;   // k_shade's tile heads, zeroed above
+        if (run.shade_fast) {
+            agpt::launch_shade_fast(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p,
+                                    shade_heads);
+            agpt::launch_resolve_pending_fast(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
+        } else {
+            agpt::launch_shade(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p,
+                               shade_heads);
+            // (independent of k_shade: different paths)
+            agpt::launch_resolve_pending(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
+        }
         cur = nxt;
         run.iterations++;
         run.launches += 3;
@@ -1066,6 +1083,7 @@ int agpt_render(agpt_scene* s, const agpt_render_params* rp, float* accum_dev, a
     run.timing = rp->enable_timing != 0 && stats != nullptr;
     run.shade_lds_tables = shade_tables_fit_lds(s->dev);
     run.shade_env = !s->envs.empty();   // an InfiniteAreaLight is present
+    run.shade_fast = s->shading_arith == AGPT_SHADING_FAST;
     const bool timing = run.timing;
     c->tev_used = 0;
     c->tev_kind.clear();
@@ -1185,6 +1203,7 @@ int agpt_li_batch(agpt_scene* s, const agpt_ray* rays, const uint32_t* rng_state
     run.timing = false;
     run.shade_lds_tables = shade_tables_fit_lds(s->dev);
     run.shade_env = !s->envs.empty();
+    run.shade_fast = s->shading_arith == AGPT_SHADING_FAST;
     RenderConsts rcn{};
     rcn.max_depth = max_depth;
     rcn.mis_mode = run.mis_mode ? 1 : 0;
@@ -1243,7 +1262,10 @@ int agpt_kat_bsdf_eval(agpt_scene* s, int material, int n, const float* wo3, con
     HIP_TRY(d_p.alloc((size_t)n));
     HIP_TRY(hipMemcpy(d_wo.p, wo3, 12 * (size_t)n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_wi.p, wi3, 12 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_kat_bsdf_eval, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, material, n, d_wo.p, d_wi.p, d_f.p, d_p.p);
+    if (s->shading_arith == AGPT_SHADING_FAST)
+        agpt::launch_kat_bsdf_eval_fast(c->stream, s->dev, material, n, d_wo.p, d_wi.p, d_f.p, d_p.p);
+    else
+        hipLaunchKernelGGL(k_kat_bsdf_eval, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, material, n, d_wo.p, d_wi.p, d_f.p, d_p.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(f3_out, d_f.p, 12 * (size_t)n, hipMemcpyDeviceToHost));
@@ -1268,8 +1290,11 @@ int agpt_kat_bsdf_sample(agpt_scene* s, int material, int n, const float* wo3, c
     HIP_TRY(d_s.alloc((size_t)n));
     HIP_TRY(hipMemcpy(d_wo.p, wo3, 12 * (size_t)n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_u.p, u2, 8 * (size_t)n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_kat_bsdf_sample, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, material, n, d_wo.p, d_u.p, d_wi.p, d_f.p,
-                       d_p.p, d_s.p);
+    if (s->shading_arith == AGPT_SHADING_FAST)
+        agpt::launch_kat_bsdf_sample_fast(c->stream, s->dev, material, n, d_wo.p, d_u.p, d_wi.p, d_f.p, d_p.p, d_s.p);
+    else
+        hipLaunchKernelGGL(k_kat_bsdf_sample, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, material, n, d_wo.p, d_u.p, d_wi.p, d_f.p,
+                           d_p.p, d_s.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(wi3_out, d_wi.p, 12 * (size_t)n, hipMemcpyDeviceToHost));

@@ -1049,41 +1049,14 @@ __global__ void k_resolve(const float4* __restrict__ accum, int n, int samples, 
 
 // ---------------------------------------------------------------------------------------------------------
 // known-answer kernels (one lane per case)
-__device__ __forceinline__ void kat_frame(Bsdf& b, const DevMaterial& m) {
-    // canonical SurfaceInteraction: dpdu = +x, dpdv = +y -> n = ns = +z, ss = +x
-    bsdf_setup(b, m, V3(0, 0, 1), V3(0, 0, 1), V3(1, 0, 0));
-}
 __global__ void k_kat_bsdf_eval(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ wi3,
                                 float* __restrict__ f3o, float* __restrict__ pdfo) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const DevMaterial& m = sc.materials[material];
-    Bsdf b;
-    kat_frame(b, m);
-    v3 wo = V3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]), wi = V3(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]);
-    v3 f;
-    float pdf;
-    bsdf_f_pdf(b, m, bsdf_wo_cache(b, m, wo), wo, wi, true, &f, &pdf);
-    f3o[3 * i] = f.x; f3o[3 * i + 1] = f.y; f3o[3 * i + 2] = f.z;
-    pdfo[i] = pdf;
+    kat_bsdf_eval_lane(sc, material, n, wo3, wi3, f3o, pdfo);
 }
 __global__ void k_kat_bsdf_sample(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ u2,
                                   float* __restrict__ wi3o, float* __restrict__ f3o, float* __restrict__ pdfo,
                                   int32_t* __restrict__ speco) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const DevMaterial& m = sc.materials[material];
-    Bsdf b;
-    kat_frame(b, m);
-    v3 wo = V3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]);
-    v3 wi = V3s(0.f);
-    float pdf = 0;
-    bool spec = false;
-    v3 f = bsdf_sample_f(b, m, bsdf_wo_cache(b, m, wo), wo, &wi, u2[2 * i], u2[2 * i + 1], &pdf, false, &spec);
-    wi3o[3 * i] = wi.x; wi3o[3 * i + 1] = wi.y; wi3o[3 * i + 2] = wi.z;
-    f3o[3 * i] = f.x; f3o[3 * i + 1] = f.y; f3o[3 * i + 2] = f.z;
-    pdfo[i] = pdf;
-    speco[i] = spec ? 1 : 0;
+    kat_bsdf_sample_lane(sc, material, n, wo3, u2, wi3o, f3o, pdfo, speco);
 }
 // known-answer kernel: Distribution1D::SampleContinuous (env_sample_continuous) for k draws, one lane each
 __global__ void k_kat_distribution1d(DevEnv e, const float* __restrict__ u, int k, float* __restrict__ x_out, float* __restrict__ pdf_out) {

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "agpt_scene.h"
+#include "agpt_shade_arith.h"
 
 enum { LOBE_DIFFUSE = 0, LOBE_RETRO = 1, LOBE_MICROFACET = 2, LOBE_SPECULAR = 3 };
 
@@ -78,6 +79,21 @@ __device__ __forceinline__ float SinPhi(v3 w) {
 __device__ __forceinline__ float Cos2Phi(v3 w) { float c = CosPhi(w); return c * c; }
 __device__ __forceinline__ float Sin2Phi(v3 w) { float s = SinPhi(w); return s * s; }
 
+// the same for the value-only code (tr_D, tr_lambda: what f and pdf are, not where a ray goes): through the shading helpers
+__device__ __forceinline__ float ShSinTheta(v3 w) { return sh_sqrt(Sin2Theta(w)); }
+__device__ __forceinline__ float ShTanTheta(v3 w) { return sh_div(ShSinTheta(w), CosTheta(w)); }
+__device__ __forceinline__ float ShTan2Theta(v3 w) { return sh_div(Sin2Theta(w), Cos2Theta(w)); }
+__device__ __forceinline__ float ShCos2Phi(v3 w) {
+    float sinTheta = ShSinTheta(w);
+    float c = (sinTheta == 0) ? 1 : tclampf(sh_div(w.x, sinTheta), -1.f, 1.f);
+    return c * c;
+}
+__device__ __forceinline__ float ShSin2Phi(v3 w) {
+    float sinTheta = ShSinTheta(w);
+    float s = (sinTheta == 0) ? 0 : tclampf(sh_div(w.y, sinTheta), -1.f, 1.f);
+    return s * s;
+}
+
 // microfacet.h:34-73
 __device__ __forceinline__ void tr_sample11(float cosTheta, float U1, float U2, float* slope_x, float* slope_y) {
     if (cosTheta > .9999f) {
@@ -128,24 +144,24 @@ __device__ __forceinline__ v3 tr_sample(v3 wi, float ax, float ay, float U1, flo
 }
 // microfacet.h:124-132
 __device__ __forceinline__ float tr_D(const DevMaterial& m, v3 wh) {
-    float tan2Theta = Tan2Theta(wh);
+    float tan2Theta = ShTan2Theta(wh);
     if (isinf(tan2Theta)) return 0.f;
     float cos4Theta = Cos2Theta(wh) * Cos2Theta(wh);
-    float e = (Cos2Phi(wh) / (m.alphax * m.alphax) + Sin2Phi(wh) / (m.alphay * m.alphay)) * tan2Theta;
-    return 1 / (AGPT_PI * m.alphax * m.alphay * cos4Theta * (1 + e) * (1 + e));
+    float e = (sh_div(ShCos2Phi(wh), m.alphax * m.alphax) + sh_div(ShSin2Phi(wh), m.alphay * m.alphay)) * tan2Theta;
+    return sh_rcp(AGPT_PI * m.alphax * m.alphay * cos4Theta * (1 + e) * (1 + e));
 }
 // microfacet.h:142-149
 __device__ __forceinline__ float tr_lambda(const DevMaterial& m, v3 w) {
-    float absTanTheta = fabsf(TanTheta(w));
+    float absTanTheta = fabsf(ShTanTheta(w));
     if (isinf(absTanTheta)) return 0.f;
-    float alpha = sqrtf(Cos2Phi(w) * m.alphax * m.alphax + Sin2Phi(w) * m.alphay * m.alphay);
+    float alpha = sh_sqrt(ShCos2Phi(w) * m.alphax * m.alphax + ShSin2Phi(w) * m.alphay * m.alphay);
     float a2t2 = (alpha * absTanTheta) * (alpha * absTanTheta);
-    return (-1 + sqrtf(1.f + a2t2)) / 2;
+    return sh_div(-1 + sh_sqrt(1.f + a2t2), 2);
 }
-__device__ __forceinline__ float tr_G1(const DevMaterial& m, v3 w) { return 1 / (1 + tr_lambda(m, w)); }
+__device__ __forceinline__ float tr_G1(const DevMaterial& m, v3 w) { return sh_rcp(1 + tr_lambda(m, w)); }
 // MicrofacetDistribution::Pdf microfacet.h:107-109
 __device__ __forceinline__ float tr_pdf(const DevMaterial& m, v3 wo, v3 wh, float G1o) {  // G1o = tr_G1(m, wo)
-    return tr_D(m, wh) * G1o * absdot(wo, wh) / AbsCosTheta(wo);
+    return sh_div(tr_D(m, wh) * G1o * absdot(wo, wh), AbsCosTheta(wo));
 }
 // microfacet.h:180-201
 __device__ __forceinline__ float fr_dielectric(float cosThetaI, float etaI, float etaT) {
@@ -157,13 +173,13 @@ __device__ __forceinline__ float fr_dielectric(float cosThetaI, float etaI, floa
         etaT = t;
         cosThetaI = fabsf(cosThetaI);
     }
-    float sinThetaI = sqrtf(smaxf(0.f, 1.f - cosThetaI * cosThetaI));
-    float sinThetaT = etaI / etaT * sinThetaI;
+    float sinThetaI = sh_sqrt(smaxf(0.f, 1.f - cosThetaI * cosThetaI));
+    float sinThetaT = sh_div(etaI, etaT) * sinThetaI;
     if (sinThetaT >= 1) return 1;
-    float cosThetaT = sqrtf(smaxf(0.f, 1.f - sinThetaT * sinThetaT));
-    float Rparl = ((etaT * cosThetaI) - (etaI * cosThetaT)) / ((etaT * cosThetaI) + (etaI * cosThetaT));
-    float Rperp = ((etaI * cosThetaI) - (etaT * cosThetaT)) / ((etaI * cosThetaI) + (etaT * cosThetaT));
-    return (Rparl * Rparl + Rperp * Rperp) / 2;
+    float cosThetaT = sh_sqrt(smaxf(0.f, 1.f - sinThetaT * sinThetaT));
+    float Rparl = sh_div((etaT * cosThetaI) - (etaI * cosThetaT), (etaT * cosThetaI) + (etaI * cosThetaT));
+    float Rperp = sh_div((etaI * cosThetaI) - (etaT * cosThetaT), (etaI * cosThetaI) + (etaT * cosThetaT));
+    return sh_div(Rparl * Rparl + Rperp * Rperp, 2);
 }
 
 // ---- disney.h -----------------------------------------------------------------------------------------------
@@ -203,13 +219,13 @@ __device__ __forceinline__ LobeEval lobe_eval(const DevMaterial& m, int lobe, v3
     e.pdf = 0.f;
     if (lobe == LOBE_DIFFUSE) {  // DisneyDiffuse::f disney.h:28-35; BxDF::Pdf reflection.h:16-18
         float Fo = wc.Fo, Fi = schlick_weight(AbsCosTheta(wi));
-        e.f = mat_v3(m.diffuse_R) * AGPT_INVPI * (1 - Fo / 2) * (1 - Fi / 2);
+        e.f = mat_v3(m.diffuse_R) * AGPT_INVPI * (1 - sh_div(Fo, 2)) * (1 - sh_div(Fi, 2));
         e.pdf = same_hemisphere(wo, wi) ? AbsCosTheta(wi) * AGPT_INVPI : 0;
     } else if (lobe == LOBE_RETRO) {  // DisneyRetro::f disney.h:43-55
         e.pdf = same_hemisphere(wo, wi) ? AbsCosTheta(wi) * AGPT_INVPI : 0;
         v3 wh = wi + wo;
         if (!(wh.x == 0 && wh.y == 0 && wh.z == 0)) {
-            wh = normalize(wh);
+            wh = sh_normalize(wh);
             float cosThetaD = dot(wi, wh);
             float Fo = wc.Fo, Fi = schlick_weight(AbsCosTheta(wi));
             float Rr = 2 * m.roughness * cosThetaD * cosThetaD;
@@ -221,15 +237,15 @@ __device__ __forceinline__ LobeEval lobe_eval(const DevMaterial& m, int lobe, v3
         bool f_ok = !(cosThetaI == 0 || cosThetaO == 0) && !(whs.x == 0 && whs.y == 0 && whs.z == 0);
         bool pdf_ok = same_hemisphere(wo, wi);
         if (f_ok || pdf_ok) {
-            v3 wh = normalize(whs);
+            v3 wh = sh_normalize(whs);
             float D = tr_D(m, wh);
             float G1o = wc.G1o;
             if (f_ok) {
                 v3 F = disney_fresnel(m, dot(wi, faceforward(wh, V3(0, 0, 1))));
                 float G = G1o * tr_G1(m, wi);  // DisneyMicrofacetDistribution::G disney.h:78-81
-                e.f = V3s(1.f) * D * G * F / (4 * cosThetaI * cosThetaO);
+                e.f = sh_div3(V3s(1.f) * D * G * F, 4 * cosThetaI * cosThetaO);
             }
-            if (pdf_ok) e.pdf = D * G1o * absdot(wo, wh) / AbsCosTheta(wo) / (4 * dot(wo, wh));
+            if (pdf_ok) e.pdf = sh_div(sh_div(D * G1o * absdot(wo, wh), AbsCosTheta(wo)), 4 * dot(wo, wh));
         }
     }
     // LOBE_SPECULAR: f = 0 (reflection.h:26-28), Pdf = 0 (:30)
@@ -306,7 +322,7 @@ __device__ __forceinline__ void bsdf_f_pdf(const Bsdf& b, const DevMaterial& m, 
     int matching = __popc(mask);
     LobeEval e = bsdf_eval_lobes(&m, mask, wo, wi, -1, 0.f, reflect, wc);
     if (reflect) *f_out = e.f;
-    *pdf_out = matching > 0 ? e.pdf / matching : 0.f;
+    *pdf_out = matching > 0 ? sh_div(e.pdf, matching) : 0.f;
 }
 // the chosen lobe's own Sample_f: returns its f (only used for the specular lobe); *pdf is written only on the paths
 // the reference writes it (quirk 8)
@@ -326,13 +342,13 @@ __device__ __forceinline__ v3 lobe_sample(const DevMaterial& m, int lobe, v3 wo,
         if (dot(wo, wh) < 0) return V3s(0.f);
         *wi = reflect3(wo, wh);
         if (!same_hemisphere(wo, *wi)) return V3s(0.f);
-        *pdf = tr_pdf(m, wo, wh, wc.G1o) / (4 * dot(wo, wh));
+        *pdf = sh_div(tr_pdf(m, wo, wh, wc.G1o), 4 * dot(wo, wh));
         return V3s(1.f);
     }
     // SpecularReflection::Sample_f reflection.cpp:13-18, FresnelNoOp
     *wi = V3(-wo.x, -wo.y, wo.z);
     *pdf = 1;
-    return V3s(1.f) * mat_v3(m.mirror_R) / AbsCosTheta(*wi);
+    return sh_div3(V3s(1.f) * mat_v3(m.mirror_R), AbsCosTheta(*wi));
 }
 // BSDF::Sample_f reflection.h:124-172.  pdf_io: the caller's variable (left untouched on the wo.z==0 early out, quirk 9)
 __device__ __forceinline__ v3 bsdf_sample_f(const Bsdf& b, const DevMaterial& m, const WoCache& wc, v3 woW, v3* wiW, float u0,
@@ -358,13 +374,13 @@ __device__ __forceinline__ v3 bsdf_sample_f(const Bsdf& b, const DevMaterial& m,
     if (*pdf_io == 0) return V3s(0.f);
     *wiW = l2w(b, wi);
     if (lobe == LOBE_SPECULAR) {
-        if (matching > 1) *pdf_io /= matching;
+        if (matching > 1) *pdf_io = sh_div(*pdf_io, matching);
         return f;
     }
     bool reflect = dot(*wiW, b.ng) * dot(woW, b.ng) > 0;
     // *pdf += other lobes' Pdf (in list order), f = sum of all matching lobes' f if reflect
     LobeEval e = bsdf_eval_lobes(&m, mask, wo, wi, matching > 1 ? lobe : -2, *pdf_io, reflect, wc);
-    if (matching > 1) *pdf_io = e.pdf / matching;
+    if (matching > 1) *pdf_io = sh_div(e.pdf, matching);
     return reflect ? e.f : V3s(0.f);
 }
 
@@ -448,13 +464,13 @@ __device__ __forceinline__ void sphere_sample_ref(const DevPrim& P, v3 refp, flo
     if (sqrlen(refp - pCenter) <= P.r2) {
         v3 pObj = pCenter + P.r * random_in_sphere_u(u0, u1);
         v3 n = normalize(pObj);  // quirk 6
-        *pdf = 1 / (4.f * AGPT_PI * P.r2);
+        *pdf = sh_rcp(4.f * AGPT_PI * P.r2);
         v3 wi = pObj - refp;
         if (sqrlen(wi) == 0)
             *pdf = 0;
         else {
-            wi = normalize(wi);
-            *pdf *= sqrlen(refp - pObj) / absdot(n, -wi);
+            wi = sh_normalize(wi);
+            *pdf *= sh_div(sqrlen(refp - pObj), absdot(n, -wi));
         }
         if (isinf(*pdf)) *pdf = 0;
         *p_out = pObj;
@@ -481,15 +497,15 @@ __device__ __forceinline__ void sphere_sample_ref(const DevPrim& P, v3 refp, flo
     float phi = u1 * 2 * AGPT_PI;
     v3 nWorld = spherical_direction(sinAlpha, cosAlpha, phi, -wcX, -wcY, -wc);
     *p_out = pCenter + P.r * V3(nWorld.x, nWorld.y, nWorld.z);
-    *pdf = 1 / (2 * AGPT_PI * (1 - cosThetaMax));
+    *pdf = sh_rcp(2 * AGPT_PI * (1 - cosThetaMax));
 }
 // Sphere::Pdf intersectable.h:306-317
 __device__ __forceinline__ float sphere_pdf(const DevPrim& P, v3 refp) {
     v3 pCenter = V3(P.cx, P.cy, P.cz);
-    if (sqrlen(refp - pCenter) <= P.r2) return 1 / (4 * AGPT_PI);
-    float sinThetaMax2 = P.r2 / sqrlen(refp - pCenter);
-    float cosThetaMax = sqrtf(smaxf(0.f, 1 - sinThetaMax2));
-    return 1 / (2 * AGPT_PI * (1 - cosThetaMax));
+    if (sqrlen(refp - pCenter) <= P.r2) return sh_rcp(4 * AGPT_PI);
+    float sinThetaMax2 = sh_div(P.r2, sqrlen(refp - pCenter));
+    float cosThetaMax = sh_sqrt(smaxf(0.f, 1 - sinThetaMax2));
+    return sh_rcp(2 * AGPT_PI * (1 - cosThetaMax));
 }
 // ---- InfiniteAreaLight (lights.cpp:50-112, #define ILS) ------------------------------------------------------
 __device__ __forceinline__ int env_mod(int a, int b) {  // HDRTexture::Mod texture.h:76-79
@@ -530,7 +546,7 @@ __device__ __forceinline__ float env_sample_continuous(const DevEnv& e, float u,
     float c0 = e.cdf[offset], c1 = e.cdf[offset + 1];
     float du = u - c0;
     if ((c1 - c0) > 0) du /= c1 - c0;
-    *pdf = (e.funcInt > 0) ? e.func[offset] / e.funcInt : 0;
+    *pdf = (e.funcInt > 0) ? sh_div(e.func[offset], e.funcInt) : 0;
     return (offset + du) / e.n;
 }
 // InfiniteAreaLight::Sample_Li lights.cpp:50-90: wi and pdf for one uniform draw u; returns false when mapPdf == 0
@@ -547,7 +563,7 @@ __device__ __noinline__ bool env_sample_li(const DevEnv* ep, float u, v3* wi, fl
     cr_sincosf(theta, &sinTheta, &cosTheta);
     cr_sincosf(phi, &sinPhi, &cosPhi);
     *wi = V3(sinTheta * cosPhi, cosTheta, sinTheta * sinPhi);
-    *pdf = mapPdf / (2 * AGPT_PI * AGPT_PI * sinTheta);
+    *pdf = sh_div(mapPdf, 2 * AGPT_PI * AGPT_PI * sinTheta);
     if (sinTheta == 0) *pdf = 0;
     return true;
 }
@@ -565,12 +581,50 @@ __device__ __noinline__ float env_pdf_li(const DevEnv* ep, v3 wi) {
     int y = (int)(theta * AGPT_INVPI * e.height);
     if (e.height - 1 < y) y = e.height - 1;
     if (y < 0) y = 0;
-    float discrete = e.func[y * e.width + x] / (e.funcInt * e.n);
-    return e.n * discrete / (2 * AGPT_PI * AGPT_PI * sinTheta);
+    float discrete = sh_div(e.func[y * e.width + x], e.funcInt * e.n);
+    return sh_div(e.n * discrete, 2 * AGPT_PI * AGPT_PI * sinTheta);
 }
 
 // integrator.h:33-36
 __device__ __forceinline__ float power_heuristic(int nf, float fPdf, int ng, float gPdf) {
     float f = nf * fPdf, g = ng * gPdf;
-    return (f * f) / (f * f + g * g);
+    return sh_div(f * f, f * f + g * g);
+}
+
+// ---- known-answer kernels (one lane per case): k_kat_bsdf_eval / _sample and their _fast twins ---------------------------
+__device__ __forceinline__ void kat_frame(Bsdf& b, const DevMaterial& m) {
+    // canonical SurfaceInteraction: dpdu = +x, dpdv = +y -> n = ns = +z, ss = +x
+    bsdf_setup(b, m, V3(0, 0, 1), V3(0, 0, 1), V3(1, 0, 0));
+}
+__device__ __forceinline__ void kat_bsdf_eval_lane(const DevScene& sc, int material, int n, const float* __restrict__ wo3,
+                                                   const float* __restrict__ wi3, float* __restrict__ f3o, float* __restrict__ pdfo) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DevMaterial& m = sc.materials[material];
+    Bsdf b;
+    kat_frame(b, m);
+    v3 wo = V3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]), wi = V3(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]);
+    v3 f;
+    float pdf;
+    bsdf_f_pdf(b, m, bsdf_wo_cache(b, m, wo), wo, wi, true, &f, &pdf);
+    f3o[3 * i] = f.x; f3o[3 * i + 1] = f.y; f3o[3 * i + 2] = f.z;
+    pdfo[i] = pdf;
+}
+__device__ __forceinline__ void kat_bsdf_sample_lane(const DevScene& sc, int material, int n, const float* __restrict__ wo3,
+                                                     const float* __restrict__ u2, float* __restrict__ wi3o, float* __restrict__ f3o,
+                                                     float* __restrict__ pdfo, int32_t* __restrict__ speco) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DevMaterial& m = sc.materials[material];
+    Bsdf b;
+    kat_frame(b, m);
+    v3 wo = V3(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]);
+    v3 wi = V3s(0.f);
+    float pdf = 0;
+    bool spec = false;
+    v3 f = bsdf_sample_f(b, m, bsdf_wo_cache(b, m, wo), wo, &wi, u2[2 * i], u2[2 * i + 1], &pdf, false, &spec);
+    wi3o[3 * i] = wi.x; wi3o[3 * i + 1] = wi.y; wi3o[3 * i + 2] = wi.z;
+    f3o[3 * i] = f.x; f3o[3 * i + 1] = f.y; f3o[3 * i + 2] = f.z;
+    pdfo[i] = pdf;
+    speco[i] = spec ? 1 : 0;
 }

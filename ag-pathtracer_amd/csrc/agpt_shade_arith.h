@@ -1,0 +1,42 @@
+// agpt_shade_arith.h -- the value-only arithmetic of the shading code, behind device helpers whose body the translation unit
+// chooses.  Value-only: what a BSDF's f and pdf are (lobe evaluation, Fresnel, the microfacet D and G), the pdfs of the lights,
+// MIS weights and the path's contributions and throughput.
+//
+//   AGPT_SHADE_FAST 0 (default; agpt_api.hip, agpt_shade_kernels.hip): each helper is exactly the expression it replaces --
+//     correctly rounded fp32 divide and square root.  Bit-exact parity with the oracle rests on this; the unit's code is the
+//     code the plain expressions compile to.
+//   AGPT_SHADE_FAST 1 (agpt_shade_kernels_fast.hip, agpt_scene_set_shading_arith(AGPT_SHADING_FAST)): a / b is a * v_rcp_f32(b),
+//     square roots are v_sqrt_f32 and normalize uses v_rsq_f32.
+//
+// What decides where a ray goes or what a path draws stays exact in both modes and does not use these helpers: the sampled
+// directions (BSDF and light sampling, with their fp64 trigonometry), the surface frames they are built in, the environment
+// map's texel choices (sampling, Le and pdf lookups), every ray's origin, direction and tmax, agpt_trace.h (sphere_test_c included), camera rays, the RNG and the queue logic.
+// A 1-ulp change to a direction moves the next hit point; on finely tessellated meshes that flips the hit triangle (its
+// geometric normal) often enough that relaxing the sampling arithmetic left 2-14 % of the pixels of a 1-spp render more than
+// 1e-3 away from the exact one.  With the directions exact a FAST render traces the same rays as the
+// exact one and differs from it only by the rounding of the path weights.
+#pragma once
+
+#include "agpt_math.h"
+
+#ifndef AGPT_SHADE_FAST
+#define AGPT_SHADE_FAST 0
+#endif
+
+#define AGPT_SH __device__ __forceinline__
+
+#if AGPT_SHADE_FAST
+AGPT_SH float sh_rcp(float b) { return __builtin_amdgcn_rcpf(b); }
+AGPT_SH float sh_div(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+AGPT_SH float sh_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
+AGPT_SH v3 sh_div3(v3 a, float b) { return a * __builtin_amdgcn_rcpf(b); }
+AGPT_SH v3 sh_normalize(v3 v) { return v * __builtin_amdgcn_rsqf(dot(v, v)); }
+#else
+AGPT_SH float sh_rcp(float b) { return 1.f / b; }
+// (a macro, not a function: through an always-inlined call the optimiser laid out env_sample_li's blocks differently, and
+// this unit's code must stay the code the expressions themselves compile to)
+#define sh_div(a, b) ((float)(a) / (float)(b))
+AGPT_SH float sh_sqrt(float x) { return sqrtf(x); }
+AGPT_SH v3 sh_div3(v3 a, float b) { return a / b; }
+AGPT_SH v3 sh_normalize(v3 v) { return normalize(v); }
+#endif

@@ -10,6 +10,14 @@
 #include "agpt_trace.h"   // TraceRay + sphere_test_c: MIS queries answered without a traversal
 #include "agpt_wavefront.h"
 
+// The kernels of a unit compiled with AGPT_SHADE_FAST 1 (agpt_shade_kernels_fast.hip, agpt_shade_arith.h) carry the suffix
+// _fast: their host-side stubs would otherwise collide with the exact unit's at link time.
+#if AGPT_SHADE_FAST
+#define AGPT_SHADE_KNAME(n) n##_fast
+#else
+#define AGPT_SHADE_KNAME(n) n
+#endif
+
 // ---------------------------------------------------------------------------------------------------------
 // PathTracer::Li's loop body (integrator.h:132-188) in wavefront form, for one path.  Returns which of the next
 // iteration's queues the path goes to.
@@ -92,8 +100,8 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
     // ---- resolve the previous vertex' UniformSampleOneLight (integrator.h:38-105) ------------------
     if (flags & PF_PENDING) {
         const v3 Ld = pending_light_sample(sc, rc, pb, pid, flags, was_occluded, was_mis_ok, c1_4, c2_4, f4);
-        float lightPdf = 1.f / sc.n_lights;           // integrator.h:100,104
-        L = L + beta * (Ld / lightPdf);               // integrator.h:166
+        float lightPdf = sh_rcp(sc.n_lights);         // integrator.h:100,104
+        L = L + beta * sh_div3(Ld, lightPdf);         // integrator.h:166
         if (!(flags & PF_DEAD)) beta = beta * V3(f4.x, f4.y, f4.z);  // integrator.h:176
         flags &= ~(PF_PENDING | PF_PEND_C1 | PF_PEND_C2);
     }
@@ -260,7 +268,7 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                             if (pdf != 0) {
                                 wi = l2w(bsdf, wi_l);
                                 if (lobe == LOBE_SPECULAR) {
-                                    if (matching > 1) pdf /= matching;
+                                    if (matching > 1) pdf = sh_div(pdf, matching);
                                     f = fs;
                                 } else {
                                     eval = true;   // pdf += the other lobes' Pdf (list order), f = sum of all matching lobes' f
@@ -274,9 +282,9 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                     const bool reflect = dot(wi, bsdf.ng) * woDotNg > 0;
                     const LobeEval e = bsdf_eval_lobes_inl(m, lmask, wo_l, wi_l, skip_lobe, pdf, reflect, wc);
                     if (it == 0)
-                        pdf = matching > 0 ? e.pdf / matching : 0.f;
+                        pdf = matching > 0 ? sh_div(e.pdf, matching) : 0.f;
                     else if (matching > 1)
-                        pdf = e.pdf / matching;
+                        pdf = sh_div(e.pdf, matching);
                     if (reflect) f = e.f;
                 }
                 if (it == 0) {   // integrator.h:46-60
@@ -284,7 +292,7 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                     f = f * absdot(wi, s.ns);
                     if (!isblack(f)) {
                         float weight = power_heuristic(1, nee_lightPdf, 1, scatteringPdf);
-                        v3 c1 = f * nee_Li * weight / nee_lightPdf;
+                        v3 c1 = sh_div3(f * nee_Li * weight, nee_lightPdf);
                         float4 c4;
                         c4.x = c1.x; c4.y = c1.y; c4.z = c1.z; c4.w = 0.f;
                         pb.c1[pid] = c4;
@@ -309,7 +317,7 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                                                                             : mat_v3(light.L);
                             // the reference traces this ray before it looks at Li (integrator.h:77-88); a black Li only
                             // means nothing is added afterwards
-                            v3 c2 = isblack(Li2) ? V3s(0.f) : f * Li2 * weight / pdf;
+                            v3 c2 = isblack(Li2) ? V3s(0.f) : sh_div3(f * Li2 * weight, pdf);
                             v3 mO = s.p + AGPT_EPSILON * wi;
                             v3 mD = normalize(wi);
                             // The query's answer for an area light is "the closest hit is the light's sphere" (integrator.h:82-85):
@@ -348,7 +356,7 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                 } else if (isblack(f) || pdf == 0) {   // integrator.h:175
                     flags |= PF_DEAD;
                 } else {
-                    fac = f * absdot(wi, s.ns) / pdf;
+                    fac = sh_div3(f * absdot(wi, s.ns), pdf);
                     if (!(flags & PF_PENDING)) beta = beta * fac;
                     flags = (flags & ~PF_SPECULAR) | (sampledSpecular ? PF_SPECULAR : 0u);
                     flags = (flags & ~PF_BOUNCE_MASK) | ((bounces + 1) & PF_BOUNCE_MASK);
@@ -425,7 +433,7 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
 #define AGPT_SHADE_LDS_LIGHTS 64
 template <bool LDS_TABLES, bool ENV>
 __global__ void __launch_bounds__(AGPT_BLOCK, AGPT_SHADE_WAVES)
-k_shade(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queues qin, Queues qout, DevCounters* __restrict__ counters,
+AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queues qin, Queues qout, DevCounters* __restrict__ counters,
         uint32_t* __restrict__ tile_heads) {
     __shared__ DevPrim s_tab_prims[LDS_TABLES ? AGPT_SHADE_LDS_PRIMS : 1];
     __shared__ DevMaterial s_tab_materials[LDS_TABLES ? AGPT_SHADE_LDS_MATERIALS : 1];
@@ -570,7 +578,7 @@ k_shade(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queues qin, Queues qout
 // shadow ray / MIS query: add the sample (integrator.h:166) and let the path go.  They used to ride through a whole
 // k_shade pass for this -- after the last bounce that is EVERY path of the batch: 10 records loaded, 3 wave slots per SIMD.
 __global__ void __launch_bounds__(AGPT_BLOCK)
-k_resolve_pending(DevScene sc, RenderConsts rc, PathBuffers pb, Queues qin) {
+AGPT_SHADE_KNAME(k_resolve_pending)(DevScene sc, RenderConsts rc, PathBuffers pb, Queues qin) {
     const uint32_t n = QCOUNT(qin, 4);
     for (uint32_t i = blockIdx.x * AGPT_BLOCK + threadIdx.x; i < n; i += gridDim.x * AGPT_BLOCK) {
         const uint32_t pid = qin.resolve[i];
@@ -581,8 +589,8 @@ k_resolve_pending(DevScene sc, RenderConsts rc, PathBuffers pb, Queues qin) {
         const float4 c1_4 = pb.c1[pid], c2_4 = pb.c2[pid];
         const uint32_t flags = __float_as_uint(b4.w);
         const v3 Ld = pending_light_sample(sc, rc, pb, pid, flags, was_occluded, was_mis_ok, c1_4, c2_4, f4);
-        const float lightPdf = 1.f / sc.n_lights;
-        const v3 L = V3(l4.x, l4.y, l4.z) + V3(b4.x, b4.y, b4.z) * (Ld / lightPdf);
+        const float lightPdf = sh_rcp(sc.n_lights);
+        const v3 L = V3(l4.x, l4.y, l4.z) + V3(b4.x, b4.y, b4.z) * sh_div3(Ld, lightPdf);
         l4.x = L.x; l4.y = L.y; l4.z = L.z;
         pb.L4[pid] = l4;
     }

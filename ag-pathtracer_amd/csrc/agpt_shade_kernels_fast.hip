@@ -1,0 +1,46 @@
+// agpt_shade_kernels_fast.hip -- the shading kernels again, with the path weights in fast arithmetic (AGPT_SHADE_FAST 1,
+// agpt_shade_arith.h): k_shade_fast, k_resolve_pending_fast and the BSDF known-answer kernels k_kat_bsdf_*_fast, with their
+// host-side launchers.  agpt_scene_set_shading_arith(AGPT_SHADING_FAST) selects them.  The unit keeps -ffp-contract=off
+// -fno-fast-math like every other: agpt_trace.h, which it includes for sphere_test_c, must answer a ray as the trace kernels do.
+#define AGPT_SHADE_FAST 1
+#include <hip/hip_runtime.h>
+
+#include "agpt_shade_kernels.h"
+
+__global__ void k_kat_bsdf_eval_fast(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ wi3,
+                                     float* __restrict__ f3o, float* __restrict__ pdfo) {
+    kat_bsdf_eval_lane(sc, material, n, wo3, wi3, f3o, pdfo);
+}
+__global__ void k_kat_bsdf_sample_fast(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ u2,
+                                       float* __restrict__ wi3o, float* __restrict__ f3o, float* __restrict__ pdfo,
+                                       int32_t* __restrict__ speco) {
+    kat_bsdf_sample_lane(sc, material, n, wo3, u2, wi3o, f3o, pdfo, speco);
+}
+
+namespace agpt {
+
+void launch_shade_fast(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
+                       const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
+    const dim3 g(grid), b(AGPT_BLOCK);
+    if (lds_tables && env) hipLaunchKernelGGL((k_shade_fast<true, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+    else if (lds_tables) hipLaunchKernelGGL((k_shade_fast<true, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+    else if (env) hipLaunchKernelGGL((k_shade_fast<false, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+    else hipLaunchKernelGGL((k_shade_fast<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+}
+
+void launch_resolve_pending_fast(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb,
+                                 const Queues& qin) {
+    hipLaunchKernelGGL(k_resolve_pending_fast, dim3(grid), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, qin);
+}
+
+void launch_kat_bsdf_eval_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* wi3, float* f3o,
+                               float* pdfo) {
+    hipLaunchKernelGGL(k_kat_bsdf_eval_fast, dim3((n + 63) / 64), dim3(64), 0, stream, sc, material, n, wo3, wi3, f3o, pdfo);
+}
+
+void launch_kat_bsdf_sample_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* u2, float* wi3o,
+                                 float* f3o, float* pdfo, int32_t* speco) {
+    hipLaunchKernelGGL(k_kat_bsdf_sample_fast, dim3((n + 63) / 64), dim3(64), 0, stream, sc, material, n, wo3, u2, wi3o, f3o, pdfo, speco);
+}
+
+}  // namespace agpt

@@ -136,11 +136,21 @@ __device__ __forceinline__ void queue_push(uint32_t* q, uint32_t* count, bool pr
 
 
 // ---------------------------------------------------------------------------------------------------------
-// host-side launchers of the shading translation unit (agpt_shade_kernels.hip)
+// host-side launchers of the shading translation units (agpt_shade_kernels.hip, agpt_shade_kernels_fast.hip)
 namespace agpt {
 // the scene's Scene::primitives records, materials and lights fit the LDS copies k_shade<LDS_TABLES> works from
 bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights);
 void launch_shade(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb,
                   const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
 void launch_resolve_pending(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin);
+// the same launches of the fast-arithmetic unit (agpt_shade_kernels_fast.hip: k_shade_fast, k_resolve_pending_fast), and its
+// known-answer kernels (k_kat_bsdf_eval_fast, k_kat_bsdf_sample_fast; one lane per case, 64-lane blocks)
+void launch_shade_fast(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
+                       const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
+void launch_resolve_pending_fast(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb,
+                                 const Queues& qin);
+void launch_kat_bsdf_eval_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* wi3, float* f3o,
+                               float* pdfo);
+void launch_kat_bsdf_sample_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* u2, float* wi3o,
+                                 float* f3o, float* pdfo, int32_t* speco);
 }  // namespace agpt

@@ -167,6 +167,21 @@ int agpt_bvh_build(const float* vertices, int n_vertices, const int32_t* indices
  * bytes; DEVICE runs agpt_bvh_build_device on the scene's context. */
 enum { AGPT_BVH_BUILDER_HOST = 0, AGPT_BVH_BUILDER_DEVICE = 1 };
 int agpt_scene_set_bvh_builder(agpt_scene*, int builder);
+/* The arithmetic of the scene's shading kernels (default EXACT).  Scene state, valid before or after agpt_scene_commit; it takes
+ * effect at the next agpt_render, agpt_li_batch, agpt_kat_bsdf_eval or agpt_kat_bsdf_sample call on the scene (no recommit).
+ *   EXACT: correctly rounded fp32 divides and square roots, sin / cos / acos / atan2 correctly rounded through fp64 -- renders
+ *          bit-identical to the oracle.
+ *   FAST:  the path weights -- BSDF f and pdf (lobe evaluation, Fresnel, microfacet D and G), light pdfs, MIS weights, the
+ *          contributions and the throughput -- use the hardware reciprocal (a * rcp(b) for a / b), square root and reciprocal
+ *          square root.  What decides a ray stays exact: sampled directions and their trigonometry, surface frames, the
+ *          environment map's texel choices, ray origins / directions / tmax, traversal and intersection (the MIS pre-test
+ *          included), camera rays, the RNG streams, accumulation and the queue logic.  A FAST render therefore traces the same
+ *          rays as an EXACT one and is deterministic: bit-identical across repeated calls, samples_per_batch splits and rank
+ *          shares.  Tested at BSDF f / pdf within rel 1e-4 (sampled wi within abs 1e-5), >= 99 % of pixels within rel 1e-3 of
+ *          the oracle with the same seeds at 1-2 spp, per-channel image means within rel 1e-3 at 16 spp.
+ * A NULL scene or an unknown mode returns AGPT_ERR_INVALID. */
+enum { AGPT_SHADING_EXACT = 0, AGPT_SHADING_FAST = 1 };
+int agpt_scene_set_shading_arith(agpt_scene*, int mode);
 /* agpt_bvh_build on the context's GPU: same arguments, same outputs byte for byte; synchronises with the context's stream.
  * *on_device_out (may be NULL) is 0 when a referenced coordinate is non-finite or the mesh's extent overflows: then the host
  * builder ran (the device folds are exact only on finite input).  HIP errors return AGPT_ERR_DEVICE / AGPT_ERR_NOMEM. */

@@ -137,6 +137,8 @@ using CameraDesc = agpt_camera_desc;
 
 // agpt_scene_set_bvh_builder: where the BVH of later primitives_push_back(mesh) calls is built; both give the same bytes
 enum class BvhBuilder { Host = AGPT_BVH_BUILDER_HOST, Device = AGPT_BVH_BUILDER_DEVICE };
+// agpt_scene_set_shading_arith: exact (default, bit-identical to the oracle) or fast shading arithmetic for later renders
+enum class ShadingArith { Exact = AGPT_SHADING_EXACT, Fast = AGPT_SHADING_FAST };
 
 class Scene {
 public:
@@ -153,6 +155,7 @@ public:
         return check(agpt_scene_add_material(h_, type, c, roughness, metallic), "agpt_scene_add_material");
     }
     void SetBvhBuilder(BvhBuilder b) { check(agpt_scene_set_bvh_builder(h_, (int)b), "agpt_scene_set_bvh_builder"); }
+    void SetShadingArith(ShadingArith m) { check(agpt_scene_set_shading_arith(h_, (int)m), "agpt_scene_set_shading_arith"); }
     // scene->primitives.push_back(make_shared<BVHTriMesh>(mesh, material, maxPrimsInNode))
     int primitives_push_back(const TriangleMesh& m, int material, int maxPrimsInNode = 1) {
         return check(agpt_scene_add_mesh(h_, m.vertices.data(), (int)m.vertices.size() / 3, m.normals.data(),

@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--out", default="gpurun_out/render.png")
     ap.add_argument("--pfm", default=None, help="also write the linear float image")
     ap.add_argument("--bvh-builder", default="host", choices=["host", "device"], help="where the mesh BVHs are built (same trees)")
+    ap.add_argument("--shading", default="exact", choices=["exact", "fast"],
+                    help="shading arithmetic: exact (bit-identical to the oracle) or fast (agpt_scene_set_shading_arith)")
     a = ap.parse_args()
     W, H = a.width, a.height
     aspect = W / float(H)
@@ -34,6 +36,7 @@ def main():
     t0 = time.time()
     scene = ag.Scene(ctx)
     scene.set_bvh_builder(a.bvh_builder)
+    scene.set_shading_arith(a.shading)
     scene = desc.instantiate(scene)
     print("scene build + BVH + upload: %.2f s" % (time.time() - t0))
     ptr = ctx.alloc(W * H * 16)
