@@ -32,7 +32,8 @@ EXPORTS = [
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
-    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_li_batch", "agpt_resolve", "agpt_device_alloc", "agpt_device_free",
+    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_li_batch", "agpt_resolve",
+    "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
     "agpt_obj_free", "agpt_obj_last_error", "agpt_write_png", "agpt_write_pfm", "agpt_hdr_load", "agpt_hdr_parse", "agpt_hdr_free",
@@ -72,6 +73,20 @@ class RenderParams(C.Structure):
                 ("accum_row0", C.c_int32), ("samples_per_batch", C.c_int32), ("enable_counters", C.c_int32),
                 ("enable_timing", C.c_int32), ("interleave_block", C.c_int32), ("interleave_world", C.c_int32),
                 ("interleave_rank", C.c_int32), ("trace_all_rays", C.c_int32)]
+
+
+class AdaptiveParams(C.Structure):
+    """agpt_adaptive_params (include/agpt.h)."""
+    _fields_ = [("min_spp", C.c_int32), ("max_spp", C.c_int32), ("step_spp", C.c_int32), ("rel_error", C.c_float),
+                ("abs_floor", C.c_float)]
+
+
+class AdaptiveStats(C.Structure):
+    """agpt_adaptive_stats (include/agpt.h)."""
+    _fields_ = [("rounds", C.c_int32), ("active_last", C.c_int32), ("samples", C.c_uint64), ("pixels_stopped", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 def library_path():
@@ -128,6 +143,9 @@ def lib():
     L.agpt_intersect_batch.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(Stats)]
     L.agpt_intersect_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(Stats)]
     L.agpt_render.argtypes = [vp, C.POINTER(RenderParams), vp, C.POINTER(Stats)]
+    L.agpt_render_adaptive.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), vp, vp, C.POINTER(Stats),
+                                       C.POINTER(AdaptiveStats)]
+    L.agpt_resolve_counts.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_li_batch.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), C.POINTER(Stats)]
     L.agpt_resolve.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -354,6 +372,13 @@ class Context:
         out = np.zeros(n_pixels, np.uint32)
         _check(self.L.agpt_resolve(self.h, C.c_void_p(accum_ptr), n_pixels, samples,
                                    out.ctypes.data_as(C.POINTER(C.c_uint32))), "agpt_resolve")
+        return out
+
+    def resolve_counts(self, accum_ptr, n_pixels):
+        """agpt_resolve_counts: CopyToSurface with each pixel's own count in accum.w (0 for a pixel without samples)."""
+        out = np.zeros(n_pixels, np.uint32)
+        _check(self.L.agpt_resolve_counts(self.h, C.c_void_p(int(accum_ptr)), n_pixels, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+               "agpt_resolve_counts")
         return out
 
 
@@ -590,6 +615,46 @@ class PathTracer:
         _check(scene.L.agpt_render(scene.h, C.byref(rp), C.c_void_p(int(accum_ptr)), C.byref(st) if want_stats else None),
                "agpt_render")
         return st
+
+    def render_adaptive(self, scene, W, H, accum_ptr, moment2_ptr, min_spp, max_spp, step_spp, rel_error, abs_floor=0.0, tile=None,
+                        seed_base=0, accum_pitch=None, accum_row0=0, samples_per_batch=0, counters=False, timing=False, want_stats=True,
+                        interleave=None, trace_all_rays=False, spp_begin=0, spp_count=0):
+        """agpt_render_adaptive: rounds of step_spp samples for the pixels of `tile` whose stop test fails, until none is active
+        (include/agpt.h).  accum_ptr / moment2_ptr: DEVICE float4 / float buffers, the count in accum.w; zeroed for a fresh frame,
+        kept between calls to continue one.  Other arguments as in render (spp_begin / spp_count must stay 0).
+        Returns (stats, adaptive stats)."""
+        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
+        il = interleave if interleave is not None else (0, 0, 0)
+        rp = RenderParams(W, H, x0, y0, w, h, spp_begin, spp_count, seed_base & 0xFFFFFFFF, self.MaxDepth,
+                          accum_pitch if accum_pitch is not None else W, accum_row0, samples_per_batch,
+                          int(counters), 1 if timing else 0, il[0], il[1], il[2], 1 if trace_all_rays else 0)
+        ap = AdaptiveParams(int(min_spp), int(max_spp), int(step_spp), float(rel_error), float(abs_floor))
+        st, ast = Stats(), AdaptiveStats()
+        _check(scene.L.agpt_render_adaptive(scene.h, C.byref(rp), C.byref(ap), C.c_void_p(int(accum_ptr)),
+                                            C.c_void_p(int(moment2_ptr)) if moment2_ptr else None, C.byref(st) if want_stats else None,
+                                            C.byref(ast)), "agpt_render_adaptive")
+        return st, ast
+
+    def render_adaptive_to_host(self, scene, W, H, min_spp, max_spp, step_spp, rel_error, accum=None, moment2=None, **kw):
+        """Convenience for tests and tools: uploads accum[H,W,4] / moment2[H,W] (zeros when None: a fresh frame), runs
+        render_adaptive, returns (accum[H,W,4], moment2[H,W], stats, adaptive stats)."""
+        ctx = scene.ctx
+        acc = np.zeros((H, W, 4), np.float32) if accum is None else np.ascontiguousarray(accum, np.float32)
+        m2 = np.zeros((H, W), np.float32) if moment2 is None else np.ascontiguousarray(moment2, np.float32)
+        pa = ctx.alloc(acc.nbytes)
+        try:
+            pm = ctx.alloc(m2.nbytes)
+            try:
+                ctx.upload(pa, acc)
+                ctx.upload(pm, m2)
+                st, ast = self.render_adaptive(scene, W, H, pa, pm, min_spp, max_spp, step_spp, rel_error, **kw)
+                acc = ctx.download(pa, (H, W, 4))
+                m2 = ctx.download(pm, (H, W))
+            finally:
+                ctx.free(pm)
+        finally:
+            ctx.free(pa)
+        return acc, m2, st, ast
 
     def Li(self, scene, rays, rng_states):
         """Integrator::Li (integrator.h:28-31, 120-191) for a batch of rays (RAY_DTYPE) with one xorshift32 state each:

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/agpt.h"
+#include "agpt_adaptive.h"
 #include "agpt_bvh_device.h"
 #include "agpt_host_scene.hpp"
 #include "agpt_kernels.h"
@@ -97,6 +98,9 @@ struct agpt_ctx {
     // primitive lists longer than 64 entries: per-path candidate words written by k_candidates, read by k_trace_fast<LIST>
     DevBuf<unsigned long long> cand_mask;   // [chunk][pool_paths]
     DevBuf<uint32_t> cand_chunks;           // [pool_paths]
+    // agpt_render_adaptive: per-thread decision masks and per-block active counts of the select pass, the active list, the words
+    // the host reads back each round (agpt_adaptive.h)
+    DevBuf<uint32_t> adapt_masks, adapt_blocks, adapt_list, adapt_words;
     int refill = AGPT_REFILL;    // AGPT_REFILL: idle lanes that trigger an in-flight refill (closest-hit launches)
     int refill_any = AGPT_REFILL_ANY;  // AGPT_REFILL_ANY: same for the any-hit / MIS-query launches
     bool mis_closest = false;    // AGPT_MIS_CLOSEST=1: trace MIS rays as full closest-hit queries (A/B, tests)
@@ -338,6 +342,7 @@ void agpt_destroy(agpt_ctx* c) {
     c->spill.release();
     c->work.release();
     c->counters.release();
+    for (DevBuf<uint32_t>* b : {&c->adapt_masks, &c->adapt_blocks, &c->adapt_list, &c->adapt_words}) b->release();
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     for (auto& ev : c->tev) (void)hipEventDestroy(ev);
     for (auto& ev : c->ev)
@@ -1176,6 +1181,181 @@ int agpt_render(agpt_scene* s, const agpt_render_params* rp, float* accum_dev, a
     return AGPT_OK;
 }
 
+// Rounds of: the decision (k_adaptive_select + k_adaptive_compact over the tile, one read-back of the active count), then wavefront
+// batches over the active list (k_generate_list -> run_wavefront -> k_accumulate_list) in chunks of whole pixels.
+int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt_adaptive_params* ap, float* accum_dev,
+                         float* moment2_dev, agpt_stats* stats, agpt_adaptive_stats* astats) {
+    if (!s || !rp || !ap || !accum_dev || !moment2_dev) return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: NULL argument");
+    if (!s->committed || !s->has_camera) return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: scene not committed or camera not set");
+    if (rp->width <= 0 || rp->height <= 0 || rp->w <= 0 || rp->h <= 0 || rp->x0 < 0 || rp->y0 < 0 ||
+        rp->x0 + rp->w > rp->width || rp->y0 + rp->h > rp->height || rp->max_depth < 0 || rp->max_depth > 200 ||
+        rp->accum_pitch < rp->x0 + rp->w)
+        return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: bad tile / film");
+    if (rp->spp_begin != 0 || rp->spp_count != 0)
+        return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: spp_begin and spp_count must be 0 (the counts are in accum.w)");
+    const int step = ap->step_spp, min_spp = ap->min_spp, max_spp = ap->max_spp;
+    if (step < 1 || min_spp < 2 || min_spp > max_spp || max_spp > (1 << 24) || min_spp % step != 0 || max_spp % step != 0 ||
+        !(ap->abs_floor >= 0.f) || ap->rel_error != ap->rel_error)
+        return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: need 1 <= step_spp, 2 <= min_spp <= max_spp <= 2^24, both multiples of "
+                                      "step_spp, abs_floor >= 0, rel_error not NaN");
+    if (astats) std::memset(astats, 0, sizeof(*astats));
+    agpt_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    uint32_t rows = (uint32_t)rp->h;
+    if (rp->interleave_block > 0) {
+        if (rp->interleave_world < 1 || rp->interleave_rank < 0 || rp->interleave_rank >= rp->interleave_world || rp->x0 != 0 ||
+            rp->y0 != 0 || rp->w != rp->width || rp->h != rp->height)
+            return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: row interleave needs the whole film as tile and 0 <= rank < world");
+        rows = 0;
+        for (int k = rp->interleave_rank, y = k * rp->interleave_block; y < rp->height;
+             k += rp->interleave_world, y = k * rp->interleave_block)
+            rows += (uint32_t)std::min(rp->interleave_block, rp->height - y);
+        if (rows == 0) return AGPT_OK;
+    }
+    const uint32_t NP = (uint32_t)rp->w * rows;
+    // paths of one wavefront batch: at most w * rows * samples_per_batch (default: agpt_render's 128 Mi paths), and no more than the
+    // largest batch a call can run (the whole tile at max(step_spp, min_spp) samples); then kept within free memory as agpt_render
+    const uint64_t spb = rp->samples_per_batch > 0 ? (uint64_t)rp->samples_per_batch : std::max<uint64_t>(1, (128ull << 20) / NP);
+    uint64_t cap = std::min<uint64_t>((uint64_t)NP * spb, (uint64_t)NP * (uint64_t)std::max(step, min_spp));
+    if (cap > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, "agpt_render_adaptive: batch too large");
+    if (cap > c->pool_paths) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const size_t per_path = (size_t)AGPT_BYTES_PER_PATH + candidate_bytes_per_path(s->dev.n_prims);
+            const size_t fit = (size_t)((double)(free_b + c->pool_paths * per_path) * 0.9) / per_path;
+            while (cap > 1 && cap > fit) cap = (cap + 1) / 2;
+        }
+    }
+    int rc = ensure_pool(c, (size_t)cap, s->dev.n_prims);
+    while (rc == AGPT_ERR_NOMEM && cap > 1) {
+        release_pool(c);
+        cap = (cap + 1) / 2;
+        rc = ensure_pool(c, (size_t)cap, s->dev.n_prims);
+    }
+    if (rc) return rc;
+    const uint32_t n_blocks = (NP + AGPT_ADAPT_BLOCK_PIXELS - 1) / AGPT_ADAPT_BLOCK_PIXELS;
+    if ((rc = c->adapt_masks.ensure((size_t)n_blocks * AGPT_BLOCK)) || (rc = c->adapt_blocks.ensure(n_blocks)) ||
+        (rc = c->adapt_list.ensure(NP)) || (rc = c->adapt_words.ensure(AGPT_AW_COUNT)))
+        return rc;
+    s->dev.cam = s->cam;
+
+    PathBuffers pb;
+    Queues q[2];
+    bind_pool(c, pb, q);
+    WavefrontRun run;
+    run.count = rp->enable_counters == 2 ? 2 : (rp->enable_counters != 0 ? 1 : 0);
+    run.mis_mode = use_fast_trace(c, s->dev, run.count) && !c->mis_closest;
+    run.timing = rp->enable_timing != 0 && stats != nullptr;
+    run.shade_lds_tables = shade_tables_fit_lds(s->dev);
+    run.shade_env = !s->envs.empty();
+    run.shade_fast = s->shading_arith == AGPT_SHADING_FAST;
+    c->tev_used = 0;
+    c->tev_kind.clear();
+    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+
+    RenderConsts base;
+    base.W = rp->width; base.H = rp->height; base.x0 = rp->x0; base.y0 = rp->y0; base.w = rp->w; base.h = rp->h;
+    base.s0 = 0; base.S = 0;
+    base.seed_base = rp->seed_base; base.max_depth = rp->max_depth;
+    base.accum_pitch = rp->accum_pitch; base.accum_row0 = rp->accum_row0; base.NP = NP;
+    base.mis_mode = run.mis_mode ? 1 : 0;
+    base.answer_rays = (run.mis_mode && !rp->trace_all_rays) ? 1 : 0;
+    base.il_block = rp->interleave_block; base.il_world = rp->interleave_world; base.il_rank = rp->interleave_rank;
+    AdaptiveConsts ac;
+    ac.min_spp = min_spp; ac.max_spp = max_spp; ac.step_spp = step; ac.rel_error = ap->rel_error; ac.abs_floor = ap->abs_floor;
+    float4* const accum = (float4*)accum_dev;
+    uint64_t samples = 0;
+
+    // `spp` more samples for each of the na pixels list[0 .. na) (list NULL: the local pixels 0 .. na): batches of at most cap paths,
+    // split into chunks of whole pixels, and a pixel's samples into several batches only if cap < spp.  Each batch reads the
+    // pixels' counts afresh (k_generate_list), so the samples stay in order.
+    auto add_samples = [&](const uint32_t* list, uint32_t na, uint32_t spp) -> int {
+        const uint32_t S = (uint32_t)std::min<uint64_t>(spp, cap);
+        const uint32_t per_chunk = (uint32_t)std::min<uint64_t>(na, cap / S);
+        for (uint32_t done = 0; done < spp; done += S) {
+            RenderConsts rcg = base;
+            rcg.S = (int32_t)std::min(S, spp - done);
+            for (uint32_t a0 = 0; a0 < na; a0 += per_chunk) {
+                const uint32_t nc = std::min(per_chunk, na - a0);
+                agpt::launch_generate_list(c->stream, s->dev, rcg, list, a0, nc, accum, pb, q[0]);
+                RenderConsts rcw = rcg;
+                rcw.NP = nc;   // (run_wavefront reads NP * S only to pick the small-batch trace kernels: the batch's real path count)
+                const int rc_run = run_wavefront(c, s, rcw, pb, q, run);
+                if (rc_run) return rc_run;
+                agpt::launch_accumulate_list(c->stream, rcg, list, a0, nc, pb, accum, moment2_dev, c->counters.p);
+            }
+        }
+        samples += (uint64_t)na * spp;
+        return AGPT_OK;
+    };
+
+    int rounds = 0;
+    uint32_t active_last = 0, stopped = 0;
+    for (;;) {
+        uint32_t* const words = c->adapt_words.p;
+        HIP_TRY(hipMemsetAsync(words, 0, AGPT_AW_COUNT * sizeof(uint32_t), c->stream));
+        agpt::launch_adaptive_select(c->stream, base, ac, accum, moment2_dev, c->adapt_masks.p, c->adapt_blocks.p, words);
+        agpt::launch_adaptive_compact(c->stream, NP, c->adapt_masks.p, c->adapt_blocks.p, c->adapt_list.p, words);
+        HIP_TRY(hipGetLastError());
+        uint32_t w[AGPT_AW_COUNT];
+        HIP_TRY(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (w[AGPT_AW_INVALID]) {
+            (void)c->take_deferred();
+            return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: " + std::to_string(w[AGPT_AW_INVALID]) +
+                                              " tile pixels hold a count (accum.w) that is not a multiple of step_spp in [0, 2^24]");
+        }
+        const uint32_t na = w[AGPT_AW_ACTIVE];
+        if (na == 0) {
+            stopped = w[AGPT_AW_STOPPED];
+            break;
+        }
+        // every round adds step_spp to each active pixel and a pixel at max_spp is never active: max_spp / step_spp rounds at most
+        if (++rounds > max_spp / step + 1) return fail(AGPT_ERR_LIMIT, "agpt_render_adaptive: rounds did not end");
+        const uint32_t n_min = ~w[AGPT_AW_INV_MIN], n_max = w[AGPT_AW_MAX];
+        // every pixel at the same n < min_spp (a fresh frame): no decision falls before min_spp -- one full-tile warm-up batch
+        const int rc_add = (n_min == n_max && n_min < (uint32_t)min_spp) ? add_samples(nullptr, NP, (uint32_t)min_spp - n_min)
+                                                                          : add_samples(c->adapt_list.p, na, (uint32_t)step);
+        if (rc_add) return rc_add;
+        active_last = na;
+    }
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(c->take_deferred());
+    if (astats) {
+        astats->rounds = rounds;
+        astats->active_last = (int32_t)active_last;
+        astats->samples = samples;
+        astats->pixels_stopped = stopped;
+    }
+    if (stats) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        std::memset(stats, 0, sizeof(*stats));
+        DevCounters dc;
+        HIP_TRY(hipMemcpy(&dc, c->counters.p, sizeof(dc), hipMemcpyDeviceToHost));
+        read_counters(dc, stats);
+        stats->samples = samples;
+        stats->iterations = run.iterations;
+        stats->trace_launches = run.launches;
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        stats->total_ms = ms;
+        if (run.timing) {
+            for (size_t i = 0; i + 1 < c->tev_used; i += 2) {
+                float t = 0;
+                HIP_TRY(hipEventElapsedTime(&t, c->tev[i], c->tev[i + 1]));
+                const int kind = c->tev_kind[i / 2];
+                stats->trace_ms += t;
+                if (kind == 0) stats->ext_ms += t;
+                else if (kind == 1) stats->mis_ms += t;
+                else stats->shadow_ms += t;
+            }
+        }
+    }
+    return AGPT_OK;
+}
+
 int agpt_li_batch(agpt_scene* s, const agpt_ray* rays, const uint32_t* rng_states, int n, int max_depth, float* radiance3_out,
                   uint32_t* rng_states_out, agpt_stats* stats) {
     if (!s || !rays || !rng_states || !radiance3_out || n < 0 || max_depth < 0 || max_depth > 200)
@@ -1243,6 +1423,18 @@ int agpt_resolve(agpt_ctx* c, const float* accum_dev, int n_pixels, int samples,
     TempBuf<uint32_t> d;
     HIP_TRY(d.alloc((size_t)n_pixels));
     hipLaunchKernelGGL(k_resolve, dim3((n_pixels + 255) / 256), dim3(256), 0, c->stream, (const float4*)accum_dev, n_pixels, samples, d.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_rgb, d.p, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AGPT_OK;
+}
+
+int agpt_resolve_counts(agpt_ctx* c, const float* accum_dev, int n_pixels, uint32_t* out_rgb) {
+    if (!c || !accum_dev || !out_rgb || n_pixels <= 0) return fail(AGPT_ERR_INVALID, "agpt_resolve_counts: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    TempBuf<uint32_t> d;
+    HIP_TRY(d.alloc((size_t)n_pixels));
+    agpt::launch_resolve_counts(c->stream, (const float4*)accum_dev, n_pixels, d.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_rgb, d.p, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

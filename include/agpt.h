@@ -235,6 +235,40 @@ int agpt_intersect_device(agpt_scene*, const agpt_ray* rays_dev, int n, agpt_hit
  * has been enqueued and, if stats != NULL, synchronised. */
 int agpt_render(agpt_scene*, const agpt_render_params*, float* accum_dev, agpt_stats* stats);
 
+/* ---- adaptive sampling -------------------------------------------------------------------------------------
+ * agpt_render_adaptive works in rounds.  A tile pixel holding n samples (samples [0, n) of its agpt_render streams, already in
+ * accum.rgb; n = accum.w) is ACTIVE when n < max_spp and either n < min_spp or the stop test fails:
+ *     mu = luminance(accum.rgb) / n,  var = max(0, moment2 / n - mu*mu) * n / (n - 1)
+ *     stop <=> sqrt(var / n) <= rel_error * max(mu, abs_floor)          (rel_error <= 0: never -- every pixel to max_spp)
+ * An active pixel takes samples [n, n + step_spp) in sample order: accum.rgb += clr exactly as agpt_render, moment2 += Y*Y
+ * (Y = luminance(clr) after the NaN / inf reject, fp32), accum.w = n + step_spp.  Rounds repeat until no pixel is active.  The
+ * decision reads only the pixel's own buffers, so the result is independent of batching, tiles, rank shares and how calls are
+ * split, and every pixel is bit-identical to agpt_render's pixel at spp = its own count. */
+typedef struct {
+    int32_t min_spp;    /* every pixel reaches at least this; multiple of step_spp, >= 2 */
+    int32_t max_spp;    /* no pixel goes beyond; multiple of step_spp, <= 1 << 24 (w holds the count exactly) */
+    int32_t step_spp;   /* samples an active pixel gets per round, >= 1 */
+    float   rel_error;  /* stop test threshold; <= 0: off, every pixel to max_spp */
+    float   abs_floor;  /* luminance floor of the test's denominator (dark pixels), >= 0 */
+} agpt_adaptive_params;
+
+typedef struct {
+    int32_t  rounds;            /* rounds this call ran (a full-tile warm-up to min_spp counts as one) */
+    int32_t  active_last;       /* pixels that took samples in the last round */
+    uint64_t samples;           /* samples this call added */
+    uint64_t pixels_stopped;    /* tile pixels left with min_spp <= n < max_spp (stopped by the test) */
+} agpt_adaptive_stats;
+
+/* rp as for agpt_render (film, tile, seed_base, max_depth, accum_pitch / accum_row0, interleave, samples_per_batch as a batch cap,
+ * trace_all_rays, counters, timing) except that spp_begin and spp_count must be 0: the counts come from accum.w.  moment2_dev:
+ * DEVICE, one float per pixel indexed like accum (same pitch, row flip and compact interleave layout), not NULL; the caller keeps
+ * it with accum between calls -- a later call with a larger max_spp or a smaller rel_error continues the frame.  A fresh frame
+ * starts with accum and moment2 zeroed.  A tile pixel whose count is not an integer multiple of step_spp in [0, 2^24] returns
+ * AGPT_ERR_INVALID before any sample is added.  stats (may be NULL) covers the whole call; astats may be NULL.  Synchronises
+ * with the context's stream (one read-back per round). */
+int agpt_render_adaptive(agpt_scene*, const agpt_render_params* rp, const agpt_adaptive_params* ap, float* accum_dev,
+                         float* moment2_dev, agpt_stats* stats, agpt_adaptive_stats* astats);
+
 /* Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) of PathTracer (integrator.h:120-191) for n rays of the caller --
  * the single-ray entry the reference's split-screen compare (myapp.cpp:168) and mouse picking (myapp.cpp:197-201) use, batched.
  * rays / rng_states / radiance3_out are HOST arrays.  rng_states[i] is the xorshift32 state the path's RandomFloat() calls start
@@ -273,6 +307,8 @@ int agpt_deinterleave_tiles(agpt_ctx*, const float* compact_dev, int width, int 
 /* Accumulator::CopyToSurface (myapp.h:34-41): lin2rgb(sum/samples) -> 0x00RRGGBB.  accum_dev DEVICE float4,
  * out_rgb HOST uint32[w*h] */
 int agpt_resolve(agpt_ctx*, const float* accum_dev, int n_pixels, int samples, uint32_t* out_rgb);
+/* CopyToSurface with the per-pixel count in accum.w (agpt_render_adaptive's buffers); a pixel with w == 0 resolves to 0 */
+int agpt_resolve_counts(agpt_ctx*, const float* accum_dev, int n_pixels, uint32_t* out_rgb);
 
 /* Host-only image writers (no GPU work) for headless use; the reference only blits to an OpenGL window
  * (myapp.cpp:177).  agpt_write_png: rgb = width*height 0x00RRGGBB words as agpt_resolve returns them, top row first

@@ -294,6 +294,51 @@ private:
     int samples_ = 0;
 };
 
+// The buffers of an adaptive render (agpt_render_adaptive): the float4 sums with each pixel's own sample count in w, and the
+// per-pixel luminance second moment the stop test reads.  Keep both between RenderAdaptive calls to continue a frame.
+class AdaptiveAccumulator {
+public:
+    AdaptiveAccumulator(Context& ctx, int w, int h) : width(w), height(h), ctx_(ctx) {
+        check(agpt_device_alloc(ctx.handle(), (size_t)w * h * 16, &pixels_), "agpt_device_alloc");
+        check(agpt_device_alloc(ctx.handle(), (size_t)w * h * 4, &moment2_), "agpt_device_alloc");
+        Clear();
+    }
+    ~AdaptiveAccumulator() {
+        agpt_device_free(ctx_.handle(), moment2_);
+        agpt_device_free(ctx_.handle(), pixels_);
+    }
+    AdaptiveAccumulator(const AdaptiveAccumulator&) = delete;
+    AdaptiveAccumulator& operator=(const AdaptiveAccumulator&) = delete;
+    void Clear() {
+        check(agpt_device_memset(ctx_.handle(), pixels_, 0, (size_t)width * height * 16), "agpt_device_memset");
+        check(agpt_device_memset(ctx_.handle(), moment2_, 0, (size_t)width * height * 4), "agpt_device_memset");
+    }
+    float* device_pixels() const { return static_cast<float*>(pixels_); }
+    float* device_moment2() const { return static_cast<float*>(moment2_); }
+    // CopyToSurface with each pixel's own count (agpt_resolve_counts)
+    std::vector<uint32_t> CopyToSurface() const {
+        std::vector<uint32_t> out((size_t)width * height);
+        check(agpt_resolve_counts(ctx_.handle(), device_pixels(), width * height, out.data()), "agpt_resolve_counts");
+        return out;
+    }
+    std::vector<float> Download() const {
+        std::vector<float> out((size_t)width * height * 4);
+        check(agpt_device_download(ctx_.handle(), out.data(), pixels_, out.size() * 4), "agpt_device_download");
+        return out;
+    }
+    std::vector<float> DownloadMoment2() const {
+        std::vector<float> out((size_t)width * height);
+        check(agpt_device_download(ctx_.handle(), out.data(), moment2_, out.size() * 4), "agpt_device_download");
+        return out;
+    }
+    const int width, height;
+
+private:
+    Context& ctx_;
+    void* pixels_ = nullptr;
+    void* moment2_ = nullptr;
+};
+
 // Integrator / PathTracer (integrator.h:28-31,120-196).  Li is evaluated for whole frames: one Render() call is
 // `spp` iterations of MyApp::Tick's per-pixel loop (myapp.cpp:161-175).
 // One rank's share of a film split over `world` GPUs: the 8-row blocks k with k % world == rank.
@@ -331,6 +376,11 @@ public:
         check(agpt_gather_tiles(h_, local.device_pixels(), local.width, film_height, share.block_rows, full ? full->device_pixels() : nullptr),
               "agpt_gather_tiles");
         if (full) full->SetSamples(local.NumSamples());
+    }
+    // adaptive renders: the counts travel in w, so the full film resolves with its CopyToSurface as it is
+    void GatherTiles(const AdaptiveAccumulator& local, int film_height, const RankShare& share, AdaptiveAccumulator* full) {
+        check(agpt_gather_tiles(h_, local.device_pixels(), local.width, film_height, share.block_rows, full ? full->device_pixels() : nullptr),
+              "agpt_gather_tiles");
     }
 
 private:
@@ -377,6 +427,41 @@ public:
         agpt_stats st{};
         check(agpt_render(scene.handle(), &p, acc.device_pixels(), &st), "agpt_render");
         acc.AddSamples(spp);
+        return st;
+    }
+    // agpt_render_adaptive over the whole film (or, with `share`, this rank's rows of a film_height-row film into its compact
+    // accumulator): rounds of params.step_spp samples for the pixels whose stop test fails, from the counts in acc
+    agpt_stats RenderAdaptive(Scene& scene, AdaptiveAccumulator& acc, int film_height, const RankShare& share, const agpt_adaptive_params& params,
+                              uint32_t seed_base = 0, agpt_adaptive_stats* astats = nullptr) const {
+        agpt_render_params p{};
+        p.width = acc.width;
+        p.height = film_height;
+        p.w = acc.width;
+        p.h = film_height;
+        p.seed_base = seed_base;
+        p.max_depth = MaxDepth;
+        p.accum_pitch = acc.width;
+        p.interleave_block = share.block_rows;
+        p.interleave_world = share.world;
+        p.interleave_rank = share.rank;
+        agpt_stats st{};
+        check(agpt_render_adaptive(scene.handle(), &p, &params, acc.device_pixels(), acc.device_moment2(), &st, astats),
+              "agpt_render_adaptive");
+        return st;
+    }
+    agpt_stats RenderAdaptive(Scene& scene, AdaptiveAccumulator& acc, const agpt_adaptive_params& params, uint32_t seed_base = 0,
+                              agpt_adaptive_stats* astats = nullptr) const {
+        agpt_render_params p{};
+        p.width = acc.width;
+        p.height = acc.height;
+        p.w = acc.width;
+        p.h = acc.height;
+        p.seed_base = seed_base;
+        p.max_depth = MaxDepth;
+        p.accum_pitch = acc.width;
+        agpt_stats st{};
+        check(agpt_render_adaptive(scene.handle(), &p, &params, acc.device_pixels(), acc.device_moment2(), &st, astats),
+              "agpt_render_adaptive");
         return st;
     }
     // Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) for n rays -- what MyApp::Tick calls per pixel (myapp.cpp:168)

@@ -25,6 +25,13 @@ def main():
     ap.add_argument("--bvh-builder", default="host", choices=["host", "device"], help="where the mesh BVHs are built (same trees)")
     ap.add_argument("--shading", default="exact", choices=["exact", "fast"],
                     help="shading arithmetic: exact (bit-identical to the oracle) or fast (agpt_scene_set_shading_arith)")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="REL_ERROR",
+                    help="adaptive sampling (agpt_render_adaptive) with this stop-test threshold instead of --spp uniform samples")
+    ap.add_argument("--min-spp", type=int, default=16)
+    ap.add_argument("--max-spp", type=int, default=256)
+    ap.add_argument("--step-spp", type=int, default=16)
+    ap.add_argument("--abs-floor", type=float, default=0.01, help="adaptive: luminance floor of the stop test")
+    ap.add_argument("--counts-png", default=None, help="adaptive: also write a heat map of the per-pixel sample counts")
     a = ap.parse_args()
     W, H = a.width, a.height
     aspect = W / float(H)
@@ -41,14 +48,36 @@ def main():
     print("scene build + BVH + upload: %.2f s" % (time.time() - t0))
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
-    t0 = time.time()
-    st = ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
-    dt = time.time() - t0
-    packed = ctx.resolve(ptr, W * H, a.spp)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    ag.binding.write_png(a.out, packed, W, H)
-    if a.pfm:
-        ag.binding.write_pfm(a.pfm, ctx.download(ptr, (H, W, 4)), a.spp)
+    if a.adaptive is not None:
+        mptr = ctx.alloc(W * H * 4)
+        ctx.memset(mptr, 0, W * H * 4)
+        t0 = time.time()
+        st, ast = ag.PathTracer(5).render_adaptive(scene, W, H, ptr, mptr, a.min_spp, a.max_spp, a.step_spp, a.adaptive, a.abs_floor)
+        dt = time.time() - t0
+        ctx.free(mptr)
+        ag.binding.write_png(a.out, ctx.resolve_counts(ptr, W * H), W, H)
+        acc = ctx.download(ptr, (H, W, 4))
+        counts = acc[..., 3]
+        print("adaptive: %d rounds, %.1f spp on average (%d..%d), %d pixels stopped by the test" %
+              (ast.rounds, counts.mean(), counts.min(), counts.max(), ast.pixels_stopped))
+        if a.pfm:   # the PFM writer divides by one count: normalise here
+            img = acc.copy()
+            img[..., :3] /= np.maximum(counts, 1)[..., None]
+            ag.binding.write_pfm(a.pfm, img, 1)
+        if a.counts_png:   # black (min_spp) .. red .. yellow .. white (max_spp), in the order of the resolved image
+            t = np.clip((counts - a.min_spp) / float(max(1, a.max_spp - a.min_spp)), 0, 1)
+            rgb = (np.stack([np.clip(3 * t, 0, 1), np.clip(3 * t - 1, 0, 1), np.clip(3 * t - 2, 0, 1)], -1) * 255).astype(np.uint32)
+            ag.binding.write_png(a.counts_png, ((rgb[..., 0] << 16) | (rgb[..., 1] << 8) | rgb[..., 2]).reshape(-1), W, H)
+        a.spp = int(round(float(counts.mean())))
+    else:
+        t0 = time.time()
+        st = ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
+        dt = time.time() - t0
+        packed = ctx.resolve(ptr, W * H, a.spp)
+        ag.binding.write_png(a.out, packed, W, H)
+        if a.pfm:
+            ag.binding.write_pfm(a.pfm, ctx.download(ptr, (H, W, 4)), a.spp)
     print("%s: %dx%d @%d spp, %d tris, %.2f s, %.1f Mrays/s -> %s" % (desc.name, W, H, a.spp, desc.n_tris, dt, st.rays / dt / 1e6, a.out))
 
 
