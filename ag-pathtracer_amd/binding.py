@@ -32,7 +32,7 @@ EXPORTS = [
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
-    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_li_batch", "agpt_resolve",
+    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -87,6 +87,15 @@ class AdaptiveStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DenoiseParams(C.Structure):
+    """agpt_denoise_params (include/agpt.h); the sigma defaults are AGPT_DENOISE_SIGMA_*."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_z", C.c_float), ("sigma_n", C.c_float), ("sigma_l", C.c_float)]
+
+
+DENOISE_SIGMA_Z, DENOISE_SIGMA_N, DENOISE_SIGMA_L = 1.0, 0.25, 4.0
 
 
 def library_path():
@@ -146,6 +155,8 @@ def lib():
     L.agpt_render_adaptive.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), vp, vp, C.POINTER(Stats),
                                        C.POINTER(AdaptiveStats)]
     L.agpt_resolve_counts.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_uint32)]
+    L.agpt_render_features.argtypes = [vp, C.POINTER(RenderParams), vp, vp]
+    L.agpt_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
     L.agpt_li_batch.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), C.POINTER(Stats)]
     L.agpt_resolve.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -380,6 +391,32 @@ class Context:
         _check(self.L.agpt_resolve_counts(self.h, C.c_void_p(int(accum_ptr)), n_pixels, out.ctypes.data_as(C.POINTER(C.c_uint32))),
                "agpt_resolve_counts")
         return out
+
+
+    def denoise(self, params, accum_ptr, moment2_ptr, albedo_ptr, normal_depth_ptr, out_ptr):
+        """agpt_denoise: the a-trous filter over an adaptive render's buffers (accum with the count in w, moment2) guided by
+        render_features' buffers; out_ptr receives float4 (mean radiance, 1).  All DEVICE pointers, full film."""
+        _check(self.L.agpt_denoise(self.h, C.byref(params), *[C.c_void_p(int(p)) if p else None for p in
+                                                             (accum_ptr, moment2_ptr, albedo_ptr, normal_depth_ptr, out_ptr)]),
+               "agpt_denoise")
+
+    def denoise_to_host(self, accum, moment2, albedo, normal_depth, iterations=5, demodulate=True, sigma_z=DENOISE_SIGMA_Z,
+                        sigma_n=DENOISE_SIGMA_N, sigma_l=DENOISE_SIGMA_L):
+        """Convenience for tests and tools: uploads the four host buffers ([H,W,4], [H,W], [H,W,4], [H,W,4]), runs denoise,
+        returns out[H,W,4]."""
+        H, W = np.shape(moment2)
+        host = [np.ascontiguousarray(a, np.float32) for a in (accum, moment2, albedo, normal_depth)]
+        ptrs = []
+        try:
+            for a in host:
+                ptrs.append(self.alloc(a.nbytes))
+                self.upload(ptrs[-1], a)
+            ptrs.append(self.alloc(W * H * 16))
+            self.denoise(DenoiseParams(W, H, int(iterations), int(bool(demodulate)), sigma_z, sigma_n, sigma_l), *ptrs)
+            return self.download(ptrs[-1], (H, W, 4))
+        finally:
+            for p in ptrs:
+                self.free(p)
 
 
 def comm_unique_id():
@@ -655,6 +692,35 @@ class PathTracer:
         finally:
             ctx.free(pa)
         return acc, m2, st, ast
+
+    def render_features(self, scene, W, H, albedo_ptr, normal_depth_ptr, tile=None, accum_pitch=None, accum_row0=0, seed_base=0,
+                        spp_begin=0, spp_count=0, interleave=None):
+        """agpt_render_features: one unjittered closest-hit query per pixel of `tile`; albedo_ptr / normal_depth_ptr are DEVICE
+        float4 buffers indexed like render's accum: (material colour, flag 0 miss / 1 surface / 2 emitter) and (shading normal, t).
+        seed_base is ignored; spp_begin, spp_count and interleave must stay at their defaults."""
+        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
+        il = interleave if interleave is not None else (0, 0, 0)
+        rp = RenderParams(W, H, x0, y0, w, h, spp_begin, spp_count, seed_base & 0xFFFFFFFF, self.MaxDepth,
+                          accum_pitch if accum_pitch is not None else W, accum_row0, 0, 0, 0, il[0], il[1], il[2], 0)
+        _check(scene.L.agpt_render_features(scene.h, C.byref(rp), C.c_void_p(int(albedo_ptr)) if albedo_ptr else None,
+                                            C.c_void_p(int(normal_depth_ptr)) if normal_depth_ptr else None), "agpt_render_features")
+
+    def render_features_to_host(self, scene, W, H, **kw):
+        """Convenience for tests and tools: render_features into zeroed full-film buffers, returns (albedo[H,W,4],
+        normal_depth[H,W,4])."""
+        ctx = scene.ctx
+        pa = ctx.alloc(W * H * 16)
+        try:
+            pn = ctx.alloc(W * H * 16)
+            try:
+                ctx.memset(pa, 0, W * H * 16)
+                ctx.memset(pn, 0, W * H * 16)
+                self.render_features(scene, W, H, pa, pn, **kw)
+                return ctx.download(pa, (H, W, 4)), ctx.download(pn, (H, W, 4))
+            finally:
+                ctx.free(pn)
+        finally:
+            ctx.free(pa)
 
     def Li(self, scene, rays, rng_states):
         """Integrator::Li (integrator.h:28-31, 120-191) for a batch of rays (RAY_DTYPE) with one xorshift32 state each:

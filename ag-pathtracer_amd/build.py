@@ -14,10 +14,10 @@ SHADE_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
 # the exact unit's flags: the sampling trigonometry (fp64) is still there, and measured on C3 three waves without spills (133
 # registers) cost 3 ms of non-trace time per step against four waves with 2 spilled.
 SHADE_FAST_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
-SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_shade_kernels_fast.hip", "agpt_bvh_device.hip", "agpt_adaptive.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_shade_kernels_fast.hip", "agpt_bvh_device.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {"agpt_shade_kernels.hip": SHADE_FLAGS, "agpt_shade_kernels_fast.hip": SHADE_FAST_FLAGS}
 HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h", "agpt_shade_arith.h",
-           "agpt_host_scene.hpp", "agpt_bvh_device.h", "agpt_adaptive.h", os.path.join("..", "..", "include", "agpt.h")]
+           "agpt_host_scene.hpp", "agpt_bvh_device.h", "agpt_adaptive.h", "agpt_denoise.h", os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);
 # explicit __builtin_fmaf calls (Markstein division in agpt_trace.h) stay fused.
 # -fno-slp-vectorize: the SLP pass packs adjacent f32 adds/muls into v_pk_*_f32, which on gfx950 cost more than the two

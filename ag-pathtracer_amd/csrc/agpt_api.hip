@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +13,7 @@
 #include "../../include/agpt.h"
 #include "agpt_adaptive.h"
 #include "agpt_bvh_device.h"
+#include "agpt_denoise.h"
 #include "agpt_host_scene.hpp"
 #include "agpt_kernels.h"
 
@@ -101,6 +103,7 @@ struct agpt_ctx {
     // agpt_render_adaptive: per-thread decision masks and per-block active counts of the select pass, the active list, the words
     // the host reads back each round (agpt_adaptive.h)
     DevBuf<uint32_t> adapt_masks, adapt_blocks, adapt_list, adapt_words;
+    DevBuf<float4> denoise_state;   // agpt_denoise: the ping-pong partner of the caller's output buffer
     int refill = AGPT_REFILL;    // AGPT_REFILL: idle lanes that trigger an in-flight refill (closest-hit launches)
     int refill_any = AGPT_REFILL_ANY;  // AGPT_REFILL_ANY: same for the any-hit / MIS-query launches
     bool mis_closest = false;    // AGPT_MIS_CLOSEST=1: trace MIS rays as full closest-hit queries (A/B, tests)
@@ -130,13 +133,14 @@ struct agpt_scene {
     std::vector<agpt::HostLight> lights;
     std::vector<agpt::HostEnv> envs;
     std::vector<DevMaterial> materials;
+    std::vector<float4> colors;   // per material: the colour as given (agpt_render_features' albedo)
     DevCamera cam{};
     bool has_camera = false;
     bool committed = false;
     int max_depth = 0;
     int bvh_builder = AGPT_BVH_BUILDER_HOST;  // agpt_scene_set_bvh_builder
     int shading_arith = AGPT_SHADING_EXACT;   // agpt_scene_set_shading_arith
-    DevBuf<float4> d_nodes, d_tri_verts, d_tri_shade, d_prefilter;
+    DevBuf<float4> d_nodes, d_tri_verts, d_tri_shade, d_prefilter, d_colors;
     DevBuf<uint32_t> d_toplevel;
     DevBuf<unsigned long long> d_chunk_mesh_masks;
     DevBuf<uint32_t> d_bigleaves;
@@ -343,6 +347,7 @@ void agpt_destroy(agpt_ctx* c) {
     c->work.release();
     c->counters.release();
     for (DevBuf<uint32_t>* b : {&c->adapt_masks, &c->adapt_blocks, &c->adapt_list, &c->adapt_words}) b->release();
+    c->denoise_state.release();
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     for (auto& ev : c->tev) (void)hipEventDestroy(ev);
     for (auto& ev : c->ev)
@@ -376,6 +381,7 @@ void agpt_scene_destroy(agpt_scene* s) {
     s->d_chunk_mesh_masks.release();
     s->d_prims.release();
     s->d_materials.release();
+    s->d_colors.release();
     s->d_lights.release();
     s->d_envs.release();
     for (auto& b : s->d_env_pixels) b.release();
@@ -388,6 +394,7 @@ int agpt_scene_add_material(agpt_scene* s, int type, const float color[3], float
     if (!s || !color) return fail(AGPT_ERR_INVALID, "agpt_scene_add_material: NULL argument");
     if (type < AGPT_MAT_DISNEY || type > AGPT_MAT_DIFFUSE_ONLY) return fail(AGPT_ERR_INVALID, "unknown material type");
     s->materials.push_back(agpt::make_material(type, color, roughness, metallic));
+    s->colors.push_back(make_float4(color[0], color[1], color[2], 0.f));
     s->committed = false;
     return (int)s->materials.size() - 1;
 }
@@ -563,6 +570,7 @@ int agpt_scene_commit(agpt_scene* s) {
     }
     if ((rc = upload(s->d_prims, flat.prims, st))) return rc;
     if ((rc = upload(s->d_materials, s->materials, st))) return rc;
+    if ((rc = upload(s->d_colors, s->colors, st))) return rc;
     if ((rc = upload(s->d_lights, lights, st))) return rc;
     std::vector<DevEnv> envs(s->envs.size());
     s->d_env_pixels.resize(envs.size());
@@ -1353,6 +1361,80 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
             }
         }
     }
+    return AGPT_OK;
+}
+
+// One closest-hit query per tile pixel through the pixel centre (k_feature_rays -> the trace launch of agpt_intersect_device), then
+// k_features: material colour + flag and shading normal + t.
+int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev) {
+    if (!rp) return fail(AGPT_ERR_INVALID, "agpt_render_features: NULL argument");
+    if (rp->spp_begin != 0 || rp->spp_count != 0)
+        return fail(AGPT_ERR_INVALID, "agpt_render_features: spp_begin and spp_count must be 0 (one unjittered ray per pixel)");
+    if (rp->interleave_block != 0 || rp->interleave_world != 0 || rp->interleave_rank != 0)
+        return fail(AGPT_ERR_INVALID, "agpt_render_features: the interleave fields must be 0");
+    if (!s || !albedo_dev || !normal_depth_dev) return fail(AGPT_ERR_INVALID, "agpt_render_features: NULL argument");
+    if (!s->committed || !s->has_camera) return fail(AGPT_ERR_INVALID, "agpt_render_features: scene not committed or camera not set");
+    if (rp->width <= 0 || rp->height <= 0 || rp->w <= 0 || rp->h <= 0 || rp->x0 < 0 || rp->y0 < 0 ||
+        rp->x0 + rp->w > rp->width || rp->y0 + rp->h > rp->height || rp->accum_pitch < rp->x0 + rp->w)
+        return fail(AGPT_ERR_INVALID, "agpt_render_features: bad tile / film");
+    if (albedo_dev == normal_depth_dev) return fail(AGPT_ERR_INVALID, "agpt_render_features: the two outputs are one buffer");
+    agpt_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t np64 = (uint64_t)rp->w * (uint64_t)rp->h;
+    if (np64 > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, "agpt_render_features: tile too large");
+    const uint32_t NP = (uint32_t)np64;
+    int rc = ensure_pool(c, (size_t)NP, s->dev.n_prims);
+    if (rc) return rc;
+    s->dev.cam = s->cam;
+    RenderConsts rcn{};
+    rcn.W = rp->width; rcn.H = rp->height; rcn.x0 = rp->x0; rcn.y0 = rp->y0; rcn.w = rp->w; rcn.h = rp->h;
+    rcn.accum_pitch = rp->accum_pitch; rcn.accum_row0 = rp->accum_row0; rcn.NP = NP;
+    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
+    HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
+    agpt::launch_feature_rays(c->stream, s->dev, rcn, c->ext_o.p, c->ext_d.p);
+    c->trace_small_batch = (unsigned long long)NP < AGPT_SMALL_BATCH;
+    launch_trace<0>(c, s->dev, nullptr, nullptr, NP, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p, 0);
+    agpt::launch_features(c->stream, s->dev, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
+                          (float4*)normal_depth_dev);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(c->take_deferred());
+    return AGPT_OK;
+}
+
+// k_denoise_prepare, then `iterations` passes that ping-pong between out_dev and the context's scratch buffer so that the last one,
+// which also re-modulates and sets w = 1, lands in out_dev.
+int agpt_denoise(agpt_ctx* c, const agpt_denoise_params* p, const float* accum_dev, const float* moment2_dev, const float* albedo_dev,
+                 const float* normal_depth_dev, float* out_dev) {
+    if (!p) return fail(AGPT_ERR_INVALID, "agpt_denoise: NULL argument");
+    if (p->width <= 0 || p->height <= 0 || (uint64_t)p->width * (uint64_t)p->height > 0x7FFFFFFFull)
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: bad film size");
+    if (p->iterations < 1 || p->iterations > 8) return fail(AGPT_ERR_INVALID, "agpt_denoise: iterations must be in 1..8");
+    if (p->demodulate != 0 && p->demodulate != 1) return fail(AGPT_ERR_INVALID, "agpt_denoise: demodulate must be 0 or 1");
+    if (!(p->sigma_z > 0.f) || !(p->sigma_n > 0.f) || !(p->sigma_l > 0.f) || std::isinf(p->sigma_z) || std::isinf(p->sigma_n) ||
+        std::isinf(p->sigma_l))
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: sigma_z, sigma_n and sigma_l must be positive and finite");
+    if (!c || !accum_dev || !moment2_dev || !albedo_dev || !normal_depth_dev || !out_dev)
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: NULL argument");
+    if (out_dev == accum_dev || out_dev == moment2_dev || out_dev == albedo_dev || out_dev == normal_depth_dev)
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: out_dev aliases an input");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    const int rc = c->denoise_state.ensure(n);
+    if (rc) return rc;
+    DenoiseConsts dc{};
+    dc.W = p->width; dc.H = p->height; dc.demodulate = p->demodulate;
+    dc.sigma_z = p->sigma_z; dc.sigma_n = p->sigma_n; dc.sigma_l = p->sigma_l;
+    float4* buf[2] = {(float4*)out_dev, c->denoise_state.p};
+    int cur = p->iterations & 1;   // pass i reads buf[cur] and writes the other: an even number of passes starts in out_dev
+    agpt::launch_denoise_prepare(c->stream, dc, (const float4*)accum_dev, moment2_dev, (const float4*)albedo_dev, buf[cur]);
+    for (int i = 0; i < p->iterations; ++i, cur ^= 1) {
+        dc.step = 1 << i;
+        dc.last = i == p->iterations - 1;
+        agpt::launch_denoise_pass(c->stream, dc, buf[cur], (const float4*)albedo_dev, (const float4*)normal_depth_dev, buf[cur ^ 1]);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return AGPT_OK;
 }
 

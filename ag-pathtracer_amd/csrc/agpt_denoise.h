@@ -1,0 +1,30 @@
+// agpt_denoise.h -- host-side launchers of the feature-buffer / denoiser unit (agpt_denoise.hip), used by agpt_render_features and
+// agpt_denoise in agpt_api.hip.
+#pragma once
+
+#include "agpt_wavefront.h"
+
+// a pass works on tiles of AGPT_DN_TX x AGPT_DN_TY pixels, one thread each: a wave is one 64-pixel row segment (1 KiB per float4 tap)
+#define AGPT_DN_TX 64
+#define AGPT_DN_TY 4
+
+struct DenoiseConsts {
+    int32_t W, H;
+    int32_t step;          // tap spacing of this pass
+    int32_t demodulate;
+    int32_t last;          // 1: this pass writes the final image (re-modulated, w = 1)
+    float sigma_z, sigma_n, sigma_l;
+};
+
+namespace agpt {
+// the pixel-centre camera rays of the tile (rc.NP pixels in pixel_of order), ready for a closest-hit trace launch
+void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d);
+// colors: one float4 per material, rgb = the colour agpt_scene_add_material was given
+void launch_features(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const float4* colors, const DevHit* hits,
+                     const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth);
+// state = (c.rgb, v); v = -1 marks a pixel without samples
+void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,
+                            float4* state);
+void launch_denoise_pass(hipStream_t stream, const DenoiseConsts& dc, const float4* state_in, const float4* albedo,
+                         const float4* normal_depth, float4* state_out);
+}  // namespace agpt

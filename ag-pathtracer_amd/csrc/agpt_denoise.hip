@@ -1,0 +1,224 @@
+// agpt_denoise.hip -- the kernels of agpt_render_features and agpt_denoise (include/agpt.h).
+//
+// Features: k_feature_rays writes one camera ray per tile pixel through the pixel centre (Camera::GetRay with a zero lens offset, no
+// RNG), the library's closest-hit trace launch follows (agpt_api.hip, the path of agpt_intersect_device), and k_features turns each
+// hit record into (material colour, flag) and (shading normal, t) with the surface reconstruction k_shade uses (agpt_shade.h;
+// spheres: (p - c) / r, see k_features).
+//
+// Denoiser: k_denoise_prepare turns the adaptive buffers into the per-pixel state (mean radiance -- demodulated by the albedo on
+// request --, variance of the mean luminance), k_denoise_pass is one a-trous pass of 25 taps at a given spacing.  Every pixel is
+// computed by one thread from the previous pass' buffer in a fixed tap order: no atomics, no cross-lane sums, so tests/denoise_model.py
+// reproduces it operation by operation.  Compiled with the library's common flags (-ffp-contract=off, IEEE divide / sqrt).
+#include <hip/hip_runtime.h>
+
+#include "agpt_denoise.h"
+#include "agpt_shade.h"
+
+#define AGPT_DN_ALBEDO_FLOOR 1e-3f
+#define AGPT_DN_DEPTH_FLOOR 1e-3f
+#define AGPT_DN_LUM_EPS 1e-6f
+
+namespace {
+
+// exp of an fp32 argument as the correctly rounded fp32 value, through fp64 (the convention of cr_acosf / cr_atan2f, agpt_math.h)
+__device__ __forceinline__ float cr_expf(float x) { return (float)exp((double)x); }
+
+__device__ __forceinline__ v3 albedo_floor(float4 a) {
+    return V3(fmaxf(a.x, AGPT_DN_ALBEDO_FLOOR), fmaxf(a.y, AGPT_DN_ALBEDO_FLOOR), fmaxf(a.z, AGPT_DN_ALBEDO_FLOOR));
+}
+
+}  // namespace
+
+// myapp.cpp:165-167 for the pixel centre: film position ((x + .5) / W, (y + .5) / H) -> Camera::GetRay (camera.h:58-64) with rd = 0
+// whatever the aperture; the Ray that Scene::Intersect then receives normalises the direction once more (camera.h:6), as the rays
+// of agpt_intersect_device do (k_prepare_rays).
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_feature_rays(DevCamera c, RenderConsts rc, float4* __restrict__ ray_o, float4* __restrict__ ray_d) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rc.NP) return;
+    int x, y;
+    size_t unused_index;
+    pixel_of(rc, i, x, y, unused_index);
+    const float px = x + 0.5f, py = y + 0.5f;
+    const float s = px / rc.W, t = py / rc.H;
+    const v3 rd = V3s(0.f);
+    const v3 offset = c.u * rd.x + c.v * rd.y;
+    const v3 pixel = c.lower_left_corner + s * c.horizontal + t * c.vertical;
+    const v3 O = c.origin + offset;
+    const v3 D = normalize(normalize(pixel - c.origin - offset));
+    float4 o4, d4;
+    o4.x = O.x; o4.y = O.y; o4.z = O.z; o4.w = AGPT_FLT_MAX;
+    d4.x = D.x; d4.y = D.y; d4.z = D.z; d4.w = 0.f;
+    ray_o[i] = o4;
+    ray_d[i] = d4;
+}
+
+// albedo = (colour, flag): flag 1 a primitive with a material, 2 an emitter (null material), 0 a miss (colour 1 for both);
+// normal_depth = (Surface::ns -- spheres: (p - c) / r --, t), zero on a miss
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_features(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
+           const float4* __restrict__ ray_d, float4* __restrict__ albedo, float4* __restrict__ normal_depth) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rc.NP) return;
+    int x, y;
+    size_t ai;
+    pixel_of(rc, i, x, y, ai);
+    const DevHit h = hits[i];
+    float4 a, nd;
+    a.x = 1.f; a.y = 1.f; a.z = 1.f; a.w = 0.f;
+    nd.x = 0.f; nd.y = 0.f; nd.z = 0.f; nd.w = 0.f;
+    if (h.id != AGPT_HIT_MISS) {
+        const float4 o4 = ray_o[i], d4 = ray_d[i];
+        const v3 O = V3(o4.x, o4.y, o4.z), D = V3(d4.x, d4.y, d4.z);
+        Surface s;
+        if (h.id & AGPT_HIT_SPHERE) {
+            const int prim = (int)(h.id & 0x7FFFFFFFu);
+            const DevPrim& P = sc.prims[prim];
+            if (P.type == AGPT_PRIM_SPHERE) {
+                // (p - c) / r, the value Sphere::Intersect's normalize(cross(dpdv, dpdu)) (surface_from_sphere) has for a p exactly
+                // on the sphere.  That expression takes x and y from r sin(acos(z / r)) and z from sqrt(x^2 + y^2): near the poles
+                // of the sphere's z axis it amplifies the distance of the fp32 hit point from the sphere by r^2 / (r^2 - z^2)
+                // (measured: up to 1.8e-4 off (p - c) / r), which a path's shading tolerates and a guide buffer need not carry.
+                s.prim = prim;
+                s.ns = (O + h.t * D - V3(P.cx, P.cy, P.cz)) / P.r;
+            } else {
+                surface_from_sphere(sc, prim, O, D, h.t, s);   // (a plane: ns = +y)
+            }
+        } else {
+            surface_from_triangle(sc, h.id, h.b1, h.b2, O, D, h.t, s);
+        }
+        const int mat = sc.prims[s.prim].material;
+        a.w = 2.f;
+        if (mat >= 0) {
+            a = colors[mat];
+            a.w = 1.f;
+        }
+        nd.x = s.ns.x; nd.y = s.ns.y; nd.z = s.ns.z; nd.w = h.t;
+    }
+    albedo[ai] = a;
+    normal_depth[ai] = nd;
+}
+
+// state = (c.rgb, v): c = accum.rgb / n, v = the variance of the mean luminance from agpt_render_adaptive's estimate
+// (max(0, moment2 / n - mu * mu) * n / (n - 1) / n; 0 for n < 2); with demodulate both in units of the floored albedo.
+// v = -1 marks a pixel without samples.
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_denoise_prepare(DenoiseConsts dc, const float4* __restrict__ accum, const float* __restrict__ moment2, const float4* __restrict__ albedo,
+                  float4* __restrict__ state) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)dc.W * (uint32_t)dc.H) return;
+    const float4 a = accum[i];
+    const float n = a.w;
+    float4 st;
+    st.x = 0.f; st.y = 0.f; st.z = 0.f; st.w = -1.f;
+    if (n > 0.f) {
+        v3 c = V3(a.x / n, a.y / n, a.z / n);
+        float v = 0.f;
+        if (n >= 2.f) {
+            const float mu = luminance(V3(a.x, a.y, a.z)) / n;
+            const float var = fmaxf(0.f, moment2[i] / n - mu * mu) * n / (n - 1.f);
+            v = var / n;
+        }
+        if (dc.demodulate) {
+            const v3 al = albedo_floor(albedo[i]);
+            c = V3(c.x / al.x, c.y / al.y, c.z / al.z);
+            const float la = luminance(al);
+            v = v / (la * la);
+        }
+        st.x = c.x; st.y = c.y; st.z = c.z; st.w = v;
+    }
+    state[i] = st;
+}
+
+// One a-trous pass: the 25 taps q = p + step * (dx, dy), dx, dy in -2..2, inside the film, dy outermost.  A tap with another flag or
+// without samples is skipped; the others weigh h * exp(-(ez + en + el)) (include/agpt.h) and the sums run in tap order.
+// A wave is 64 consecutive pixels of one row: every tap is one contiguous 1 KiB (state, normal_depth) or 256 B (flag) read, at every
+// spacing, and a pass re-reads each line 25 times from L1 / L2.
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_denoise_pass(DenoiseConsts dc, const float4* __restrict__ state_in, const float4* __restrict__ albedo, const float4* __restrict__ normal_depth,
+               float4* __restrict__ state_out) {
+    const int x = (int)(blockIdx.x * AGPT_DN_TX + (threadIdx.x & (AGPT_DN_TX - 1)));
+    const int y = (int)(blockIdx.y * AGPT_DN_TY + threadIdx.x / AGPT_DN_TX);
+    if (x >= dc.W || y >= dc.H) return;
+    const size_t p = (size_t)y * (size_t)dc.W + (size_t)x;
+    const float4 sp = state_in[p];
+    float4 out;
+    out.x = 0.f; out.y = 0.f; out.z = 0.f; out.w = dc.last ? 1.f : -1.f;
+    if (sp.w < 0.f) {
+        state_out[p] = out;
+        return;
+    }
+    const float4 ap = albedo[p];
+    const float4 gp = normal_depth[p];
+    const float flag_p = ap.w;
+    const float Yp = luminance(V3(sp.x, sp.y, sp.z));
+    const float lden = dc.sigma_l * sqrtf(sp.w) + AGPT_DN_LUM_EPS;
+    const float zden = dc.sigma_z * (float)dc.step * fmaxf(gp.w, AGPT_DN_DEPTH_FLOOR);
+    const float nden = dc.sigma_n * dc.sigma_n;
+    const bool geometry = flag_p != 0.f;
+    const float k[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sv = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * dc.step;
+        if (qy < 0 || qy >= dc.H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * dc.step;
+            if (qx < 0 || qx >= dc.W) continue;
+            const size_t q = (size_t)qy * (size_t)dc.W + (size_t)qx;
+            const float flag_q = albedo[q].w;
+            const float4 sq = state_in[q];
+            if (flag_q != flag_p || sq.w < 0.f) continue;
+            float ez = 0.f, en = 0.f;
+            if (geometry) {
+                const float4 gq = normal_depth[q];
+                ez = fabsf(gp.w - gq.w) / zden;
+                const float nx = gp.x - gq.x, ny = gp.y - gq.y, nz = gp.z - gq.z;
+                en = (nx * nx + ny * ny + nz * nz) / nden;
+            }
+            const float Yq = luminance(V3(sq.x, sq.y, sq.z));
+            const float el = fabsf(Yp - Yq) / lden;
+            const float w = (k[dx + 2] * k[dy + 2]) * cr_expf(-((ez + en) + el));
+            sw += w;
+            sr += w * sq.x;
+            sg += w * sq.y;
+            sb += w * sq.z;
+            sv += (w * w) * sq.w;
+        }
+    }
+    v3 c = V3(sr / sw, sg / sw, sb / sw);
+    if (dc.last) {
+        if (dc.demodulate) c = c * albedo_floor(ap);
+        out.w = 1.f;
+    } else {
+        out.w = sv / (sw * sw);
+    }
+    out.x = c.x; out.y = c.y; out.z = c.z;
+    state_out[p] = out;
+}
+
+namespace agpt {
+
+static inline dim3 blocks_for(uint64_t n) { return dim3((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)); }
+
+void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d) {
+    hipLaunchKernelGGL(k_feature_rays, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc.cam, rc, ray_o, ray_d);
+}
+void launch_features(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const float4* colors, const DevHit* hits,
+                     const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth) {
+    hipLaunchKernelGGL(k_features, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+}
+void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,
+                            float4* state) {
+    hipLaunchKernelGGL(k_denoise_prepare, blocks_for((uint64_t)dc.W * (uint64_t)dc.H), dim3(AGPT_BLOCK), 0, stream, dc, accum, moment2, albedo,
+                       state);
+}
+void launch_denoise_pass(hipStream_t stream, const DenoiseConsts& dc, const float4* state_in, const float4* albedo,
+                         const float4* normal_depth, float4* state_out) {
+    static_assert(AGPT_DN_TX * AGPT_DN_TY == AGPT_BLOCK, "one thread per tile pixel");
+    const dim3 g((unsigned)((dc.W + AGPT_DN_TX - 1) / AGPT_DN_TX), (unsigned)((dc.H + AGPT_DN_TY - 1) / AGPT_DN_TY));
+    hipLaunchKernelGGL(k_denoise_pass, g, dim3(AGPT_BLOCK), 0, stream, dc, state_in, albedo, normal_depth, state_out);
+}
+
+}  // namespace agpt

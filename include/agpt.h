@@ -269,6 +269,60 @@ typedef struct {
 int agpt_render_adaptive(agpt_scene*, const agpt_render_params* rp, const agpt_adaptive_params* ap, float* accum_dev,
                          float* moment2_dev, agpt_stats* stats, agpt_adaptive_stats* astats);
 
+/* ---- first-hit feature buffers and the denoiser -----------------------------------------------------------------
+ * agpt_render_features casts ONE ray per tile pixel through the pixel centre -- film position ((x + 0.5) / W, (y + 0.5) / H) through
+ * Camera::GetRay's arithmetic (camera.h:58-64) with the lens offset zero whatever the aperture; no RNG is drawn, so the buffers do
+ * not depend on a seed -- and runs one Scene::Intersect (scene.h:5-13) on it (the launch path of agpt_intersect_device).  Per pixel:
+ *     albedo       = (color.rgb, flag)   flag 1: a primitive with a material (Disney, mirror or diffuse-only), color = what
+ *                                                agpt_scene_add_material was given, bit for bit
+ *                                        flag 2: an emitter (a primitive with the null material), color = (1, 1, 1)
+ *                                        flag 0: a miss, color = (1, 1, 1)
+ *     normal_depth = (ns.xyz, t)         ns = the shading normal the path tracer shades that hit with (shading.n: the interpolated
+ *                                        normal of a mesh with normals, else the geometric one; +y for a plane), except that a
+ *                                        sphere's is written as (p - c) / r, p = o + t d: the value Sphere::Intersect's dpdu x dpdv
+ *                                        expression has for a p exactly on the sphere, without that expression's loss of accuracy
+ *                                        near the poles (up to 2e-4 in fp32).  t = the hit distance; 0 on a miss
+ * rp: film, tile, accum_pitch and accum_row0 as for agpt_render -- both outputs are DEVICE float4 buffers indexed like accum (same
+ * pitch and row flip); spp_begin, spp_count and the interleave_* fields must be 0 (AGPT_ERR_INVALID otherwise); seed_base, max_depth
+ * and the remaining fields are ignored.  Synchronises with the context's stream. */
+int agpt_render_features(agpt_scene*, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev);
+
+/* agpt_denoise: a variance-guided edge-avoiding a-trous filter over an adaptive render's buffers and its feature buffers.
+ * accum_dev / moment2_dev are agpt_render_adaptive's (the count in accum.w); a UNIFORM render for denoising is agpt_render_adaptive
+ * with rel_error <= 0 and min_spp = max_spp.  All buffers cover the full film, pitch = width, Accumulator::pixels order.
+ * Everything is fp32, every operation rounded on its own, divisions and square roots IEEE; luminance(c) = 0.212671 r + 0.715160 g +
+ * 0.072169 b summed left to right; expc(x) = (float)exp((double)x), the correctly rounded value through fp64.
+ *   Prepare, per pixel:  n = accum.w.  n == 0: the pixel is EXCLUDED (weight 0 as a tap, output rgb 0).  Otherwise
+ *       c = accum.rgb / n;   v = 0 for n < 2, else with mu = luminance(accum.rgb) / n:
+ *       v = max(0, moment2 / n - mu * mu) * n / (n - 1) / n        (the variance of the mean luminance, agpt_render_adaptive's estimate)
+ *       with demodulate:  a = max(albedo.rgb, 1e-3) per channel,  c = c / a,  v = v / (luminance(a) * luminance(a))
+ *   Pass i = 0 .. iterations - 1 (spacing s = 1 << i), for pixel p, from the state (c, v) the previous pass left:
+ *       over the taps q = p + s * (dx, dy), dy = -2 .. 2 outermost, dx = -2 .. 2, that lie inside the film:
+ *           h = k[dx] * k[dy],  k = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *           a tap with flag_q != flag_p or an excluded q is skipped (w = 0); otherwise
+ *           ez = |t_p - t_q| / (sigma_z * s * max(t_p, 1e-3))                        (0 when flag_p == 0: sky)
+ *           en = ((ns_p - ns_q) . (ns_p - ns_q)) / (sigma_n * sigma_n)               (0 when flag_p == 0)
+ *           el = |Y_p - Y_q| / (sigma_l * sqrt(v_p) + 1e-6),  Y = luminance(c)
+ *           w = h * expc(-((ez + en) + el))
+ *           sw += w;  sc += w * c_q (per channel);  sv += (w * w) * v_q             (in tap order; the centre tap has w = h)
+ *       c' = sc / sw,  v' = sv / (sw * sw)
+ *   Finish (in the last pass): rgb = c' * a with demodulate, else c';  out.w = 1.
+ * out_dev: DEVICE float4, rgb = the denoised MEAN radiance, w = 1 -- agpt_resolve(out, n, 1) and agpt_resolve_counts(out, n) both
+ * display it.  It must not alias an input; the inputs are not written.  The one ping-pong scratch buffer is the context's
+ * (allocated on first use, released by agpt_destroy).  No atomics and a fixed order: repeated calls are bit-identical.  Enqueued
+ * on the context's stream and synchronised before returning. */
+typedef struct {
+    int32_t width, height;   /* all buffers: full film, pitch = width, Accumulator::pixels order */
+    int32_t iterations;      /* passes with tap spacing 1, 2, 4, ...; 1..8 */
+    int32_t demodulate;      /* 1: filter radiance / albedo, multiply back at the end; 0: filter radiance */
+    float sigma_z, sigma_n, sigma_l;   /* > 0; AGPT_DENOISE_SIGMA_* are the defaults the tools use */
+} agpt_denoise_params;
+#define AGPT_DENOISE_SIGMA_Z 1.0f
+#define AGPT_DENOISE_SIGMA_N 0.25f
+#define AGPT_DENOISE_SIGMA_L 4.0f
+int agpt_denoise(agpt_ctx*, const agpt_denoise_params*, const float* accum_dev, const float* moment2_dev, const float* albedo_dev,
+                 const float* normal_depth_dev, float* out_dev);
+
 /* Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) of PathTracer (integrator.h:120-191) for n rays of the caller --
  * the single-ray entry the reference's split-screen compare (myapp.cpp:168) and mouse picking (myapp.cpp:197-201) use, batched.
  * rays / rng_states / radiance3_out are HOST arrays.  rng_states[i] is the xorshift32 state the path's RandomFloat() calls start

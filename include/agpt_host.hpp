@@ -294,6 +294,37 @@ private:
     int samples_ = 0;
 };
 
+// First-hit feature buffers (agpt_render_features): albedo = (material colour, flag 0 miss / 1 surface / 2 emitter) and
+// normal_depth = (shading normal, hit distance), float4 per pixel in Accumulator::pixels order.  They guide AdaptiveAccumulator::Denoise.
+class FeatureBuffers {
+public:
+    FeatureBuffers(Context& ctx, int w, int h) : width(w), height(h), ctx_(ctx) {
+        check(agpt_device_alloc(ctx.handle(), (size_t)w * h * 16, &albedo_), "agpt_device_alloc");
+        check(agpt_device_alloc(ctx.handle(), (size_t)w * h * 16, &normal_depth_), "agpt_device_alloc");
+    }
+    ~FeatureBuffers() {
+        agpt_device_free(ctx_.handle(), normal_depth_);
+        agpt_device_free(ctx_.handle(), albedo_);
+    }
+    FeatureBuffers(const FeatureBuffers&) = delete;
+    FeatureBuffers& operator=(const FeatureBuffers&) = delete;
+    float* device_albedo() const { return static_cast<float*>(albedo_); }
+    float* device_normal_depth() const { return static_cast<float*>(normal_depth_); }
+    std::vector<float> DownloadAlbedo() const { return download(albedo_); }
+    std::vector<float> DownloadNormalDepth() const { return download(normal_depth_); }
+    const int width, height;
+
+private:
+    std::vector<float> download(const void* src) const {
+        std::vector<float> out((size_t)width * height * 4);
+        check(agpt_device_download(ctx_.handle(), out.data(), src, out.size() * 4), "agpt_device_download");
+        return out;
+    }
+    Context& ctx_;
+    void* albedo_ = nullptr;
+    void* normal_depth_ = nullptr;
+};
+
 // The buffers of an adaptive render (agpt_render_adaptive): the float4 sums with each pixel's own sample count in w, and the
 // per-pixel luminance second moment the stop test reads.  Keep both between RenderAdaptive calls to continue a frame.
 class AdaptiveAccumulator {
@@ -325,6 +356,23 @@ public:
         std::vector<float> out((size_t)width * height * 4);
         check(agpt_device_download(ctx_.handle(), out.data(), pixels_, out.size() * 4), "agpt_device_download");
         return out;
+    }
+    // agpt_denoise: the a-trous filter over this frame, guided by `features`, into `out` as the mean radiance of ONE sample (its
+    // CopyToSurface then displays it).  A uniform render for denoising is RenderAdaptive with rel_error <= 0 and min_spp = max_spp.
+    void Denoise(const FeatureBuffers& features, Accumulator& out, int iterations = 5, bool demodulate = true,
+                 float sigma_z = AGPT_DENOISE_SIGMA_Z, float sigma_n = AGPT_DENOISE_SIGMA_N, float sigma_l = AGPT_DENOISE_SIGMA_L) const {
+        agpt_denoise_params p{};
+        p.width = width;
+        p.height = height;
+        p.iterations = iterations;
+        p.demodulate = demodulate ? 1 : 0;
+        p.sigma_z = sigma_z;
+        p.sigma_n = sigma_n;
+        p.sigma_l = sigma_l;
+        check(agpt_denoise(ctx_.handle(), &p, device_pixels(), device_moment2(), features.device_albedo(), features.device_normal_depth(),
+                           out.device_pixels()),
+              "agpt_denoise");
+        out.SetSamples(1);
     }
     std::vector<float> DownloadMoment2() const {
         std::vector<float> out((size_t)width * height);
@@ -463,6 +511,16 @@ public:
         check(agpt_render_adaptive(scene.handle(), &p, &params, acc.device_pixels(), acc.device_moment2(), &st, astats),
               "agpt_render_adaptive");
         return st;
+    }
+    // agpt_render_features over the whole film: one unjittered closest-hit query per pixel (no RNG, lens offset zero)
+    void RenderFeatures(Scene& scene, FeatureBuffers& features) const {
+        agpt_render_params p{};
+        p.width = features.width;
+        p.height = features.height;
+        p.w = features.width;
+        p.h = features.height;
+        p.accum_pitch = features.width;
+        check(agpt_render_features(scene.handle(), &p, features.device_albedo(), features.device_normal_depth()), "agpt_render_features");
     }
     // Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) for n rays -- what MyApp::Tick calls per pixel (myapp.cpp:168)
     // and the mouse-pick overlay per click (myapp.cpp:197-201).  rng[i] is the RandomFloat() state path i starts from and receives

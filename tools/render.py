@@ -32,6 +32,10 @@ def main():
     ap.add_argument("--step-spp", type=int, default=16)
     ap.add_argument("--abs-floor", type=float, default=0.01, help="adaptive: luminance floor of the stop test")
     ap.add_argument("--counts-png", default=None, help="adaptive: also write a heat map of the per-pixel sample counts")
+    ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="ITER",
+                    help="denoise the render (agpt_render_features + agpt_denoise, ITER a-trous passes, default 5) before the resolve; "
+                         "implies the adaptive entry point -- uniform at --spp when --adaptive is not given")
+    ap.add_argument("--features-png", default=None, metavar="PREFIX", help="write PREFIX_albedo.png and PREFIX_normal.png (first-hit features)")
     a = ap.parse_args()
     W, H = a.width, a.height
     aspect = W / float(H)
@@ -49,14 +53,44 @@ def main():
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    if a.adaptive is not None:
+    features = None
+    if a.denoise is not None or a.features_png:
+        features = (ctx.alloc(W * H * 16), ctx.alloc(W * H * 16))
+        ag.PathTracer(5).render_features(scene, W, H, *features)
+        if a.features_png:   # albedo as it is, the normal as n / 2 + 1/2 (black where nothing was hit), both through the display resolve
+            for suffix, p in (("albedo", features[0]), ("normal", features[1])):
+                img = ctx.download(p, (H, W, 4)).copy()
+                if suffix == "normal":
+                    img[..., :3] = np.where(img[..., 3:4] > 0, img[..., :3] * 0.5 + 0.5, 0.0) ** 2.2   # (the resolve applies 1 / 2.2)
+                img[..., 3] = 1.0
+                tmp = ctx.alloc(img.nbytes)
+                ctx.upload(tmp, img)
+                ag.binding.write_png("%s_%s.png" % (a.features_png, suffix), ctx.resolve_counts(tmp, W * H), W, H)
+                ctx.free(tmp)
+    if a.adaptive is not None or a.denoise is not None:
         mptr = ctx.alloc(W * H * 4)
         ctx.memset(mptr, 0, W * H * 4)
         t0 = time.time()
-        st, ast = ag.PathTracer(5).render_adaptive(scene, W, H, ptr, mptr, a.min_spp, a.max_spp, a.step_spp, a.adaptive, a.abs_floor)
+        if a.adaptive is not None:
+            st, ast = ag.PathTracer(5).render_adaptive(scene, W, H, ptr, mptr, a.min_spp, a.max_spp, a.step_spp, a.adaptive, a.abs_floor)
+        else:   # uniform through the adaptive entry point: it keeps the luminance second moment the denoiser reads
+            a.min_spp = a.max_spp = spp = max(2, a.spp)
+            st, ast = ag.PathTracer(5).render_adaptive(scene, W, H, ptr, mptr, spp, spp, spp, 0.0)
         dt = time.time() - t0
+        if a.denoise is not None:
+            out = ctx.alloc(W * H * 16)
+            t1 = time.time()
+            ctx.denoise(ag.DenoiseParams(W, H, a.denoise, 1, ag.DENOISE_SIGMA_Z, ag.DENOISE_SIGMA_N, ag.DENOISE_SIGMA_L), ptr, mptr,
+                        features[0], features[1], out)
+            print("denoise: %d passes, %.2f ms" % (a.denoise, (time.time() - t1) * 1e3))
+            ag.binding.write_png(a.out, ctx.resolve_counts(out, W * H), W, H)
+            if a.pfm:
+                ag.binding.write_pfm(a.pfm, ctx.download(out, (H, W, 4)), 1)
+                a.pfm = None
+            ctx.free(out)
+        else:
+            ag.binding.write_png(a.out, ctx.resolve_counts(ptr, W * H), W, H)
         ctx.free(mptr)
-        ag.binding.write_png(a.out, ctx.resolve_counts(ptr, W * H), W, H)
         acc = ctx.download(ptr, (H, W, 4))
         counts = acc[..., 3]
         print("adaptive: %d rounds, %.1f spp on average (%d..%d), %d pixels stopped by the test" %
