@@ -30,7 +30,7 @@ EXPORTS = [
     "agpt_last_error", "agpt_version", "agpt_init", "agpt_set_stream", "agpt_destroy", "agpt_scene_create",
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
-    "agpt_scene_set_camera",
+    "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
@@ -136,6 +136,8 @@ def lib():
     L.agpt_scene_add_area_light.argtypes = [vp, fp, C.c_float, fp]
     L.agpt_scene_add_uniform_infinite_light.argtypes = [vp, fp]
     L.agpt_scene_add_infinite_area_light.argtypes = [vp, fp, C.c_int, C.c_int]
+    L.agpt_scene_add_texture.argtypes = [vp, fp, C.c_int, C.c_int]
+    L.agpt_scene_set_material_texture.argtypes = [vp, C.c_int, C.c_int]
     L.agpt_scene_set_camera.argtypes = [vp, C.POINTER(CameraDesc)]
     L.agpt_scene_commit.argtypes = [vp]
     L.agpt_mesh_num_nodes.argtypes = [vp, C.c_int]
@@ -556,6 +558,19 @@ class Scene:
         return _check(self.L.agpt_scene_add_infinite_area_light(self.h, img.ctypes.data_as(C.POINTER(C.c_float)),
                                                                 img.shape[1], img.shape[0]),
                       "agpt_scene_add_infinite_area_light")
+
+    def add_texture(self, rgb):
+        """agpt_scene_add_texture: an image texture from rgb[H, W, 3] float32, row 0 = top, LINEAR values; returns its id."""
+        img = np.ascontiguousarray(rgb, np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("add_texture: expected an array of shape [H, W, 3], got %r" % (img.shape,))
+        return _check(self.L.agpt_scene_add_texture(self.h, img.ctypes.data_as(C.POINTER(C.c_float)), img.shape[1], img.shape[0]),
+                      "agpt_scene_add_texture")
+
+    def set_material_texture(self, material, texture):
+        """agpt_scene_set_material_texture: the material's colour at a mesh hit becomes the texture's nearest texel at the hit's uv
+        (texture = -1: the constant colour again)."""
+        _check(self.L.agpt_scene_set_material_texture(self.h, int(material), int(texture)), "agpt_scene_set_material_texture")
 
     def set_camera(self, lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
         d = CameraDesc()

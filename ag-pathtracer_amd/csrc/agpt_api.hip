@@ -134,6 +134,18 @@ struct agpt_scene {
     std::vector<agpt::HostEnv> envs;
     std::vector<DevMaterial> materials;
     std::vector<float4> colors;   // per material: the colour as given (agpt_render_features' albedo)
+    // image textures (agpt_scene_add_texture / agpt_scene_set_material_texture): texels as float4, per material the texture id or -1
+    struct HostTexture {
+        int width = 0, height = 0;
+        std::vector<float4> texels;
+    };
+    std::vector<HostTexture> textures;
+    std::vector<int32_t> material_texture;
+    bool textured = false;   // set by agpt_scene_commit: a material has a texture -> the TEXTURED shading / feature kernels
+    DevBuf<float4> d_tri_uv;
+    DevBuf<DevTexture> d_textures;
+    DevBuf<int32_t> d_material_texture;
+    std::vector<DevBuf<float4>> d_texels;
     DevCamera cam{};
     bool has_camera = false;
     bool committed = false;
@@ -384,6 +396,10 @@ void agpt_scene_destroy(agpt_scene* s) {
     s->d_colors.release();
     s->d_lights.release();
     s->d_envs.release();
+    s->d_tri_uv.release();
+    s->d_textures.release();
+    s->d_material_texture.release();
+    for (auto& b : s->d_texels) b.release();
     for (auto& b : s->d_env_pixels) b.release();
     for (auto& b : s->d_env_func) b.release();
     for (auto& b : s->d_env_cdf) b.release();
@@ -395,6 +411,7 @@ int agpt_scene_add_material(agpt_scene* s, int type, const float color[3], float
     if (type < AGPT_MAT_DISNEY || type > AGPT_MAT_DIFFUSE_ONLY) return fail(AGPT_ERR_INVALID, "unknown material type");
     s->materials.push_back(agpt::make_material(type, color, roughness, metallic));
     s->colors.push_back(make_float4(color[0], color[1], color[2], 0.f));
+    s->material_texture.push_back(-1);
     s->committed = false;
     return (int)s->materials.size() - 1;
 }
@@ -527,6 +544,29 @@ int agpt_scene_add_infinite_area_light(agpt_scene* s, const float* rgb, int widt
     return (int)s->lights.size() - 1;
 }
 
+int agpt_scene_add_texture(agpt_scene* s, const float* rgb, int width, int height) {
+    if (!s || !rgb) return fail(AGPT_ERR_INVALID, "agpt_scene_add_texture: NULL argument");
+    if (width <= 0 || height <= 0 || (long long)width * height > (1ll << 28))
+        return fail(AGPT_ERR_INVALID, "agpt_scene_add_texture: width and height must be positive (at most 2^28 texels)");
+    if (s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_add_texture: the scene is already committed");
+    agpt_scene::HostTexture t;
+    t.width = width;
+    t.height = height;
+    t.texels.resize((size_t)width * height);
+    for (size_t i = 0; i < t.texels.size(); i++) t.texels[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.f);
+    s->textures.push_back(std::move(t));
+    return (int)s->textures.size() - 1;
+}
+
+int agpt_scene_set_material_texture(agpt_scene* s, int material, int texture) {
+    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_texture: scene is NULL");
+    if (material < 0 || material >= (int)s->materials.size()) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_texture: bad material id");
+    if (texture < -1 || texture >= (int)s->textures.size()) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_texture: bad texture id");
+    if (s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_texture: the scene is already committed");
+    s->material_texture[material] = texture;
+    return AGPT_OK;
+}
+
 int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
     if (!s || !d) return fail(AGPT_ERR_INVALID, "agpt_scene_set_camera: NULL argument");
     s->cam = agpt::make_camera(*d);
@@ -537,8 +577,15 @@ int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
 
 int agpt_scene_commit(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_commit: scene is NULL");
+    bool textured = false;
+    for (int32_t t : s->material_texture) textured = textured || t >= 0;
+    if (textured)
+        for (const agpt::HostPrim& hp : s->prims)
+            if (hp.type != AGPT_PRIM_MESH && hp.material >= 0 && s->material_texture[hp.material] >= 0)
+                return fail(AGPT_ERR_INVALID, "agpt_scene_commit: a sphere or a plane has a textured material (textures apply to triangle meshes only)");
     HIP_TRY(hipSetDevice(s->ctx->device));
     agpt::FlatScene flat;
+    flat.want_tri_uv = textured;
     agpt::flatten_scene(s->meshes, s->spheres, s->prims, flat);
     s->max_depth = flat.max_depth;
     if (flat.max_depth > AGPT_STACK_DEPTH_MAX)
@@ -590,7 +637,25 @@ int agpt_scene_commit(agpt_scene* s) {
         envs[i].funcInt = he.funcInt;
     }
     if ((rc = upload(s->d_envs, envs, st))) return rc;
+    // texture coordinates, texels and the tables are uploaded only for a scene that has a textured material
+    std::vector<DevTexture> textures(textured ? s->textures.size() : 0);
+    if (textured) {
+        s->d_texels.resize(textures.size());
+        for (size_t i = 0; i < textures.size(); i++) {
+            if ((rc = upload(s->d_texels[i], s->textures[i].texels, st))) return rc;
+            textures[i].texels = s->d_texels[i].p;
+            textures[i].width = s->textures[i].width;
+            textures[i].height = s->textures[i].height;
+        }
+        if ((rc = upload(s->d_tri_uv, flat.tri_uv, st))) return rc;
+        if ((rc = upload(s->d_textures, textures, st))) return rc;
+        if ((rc = upload(s->d_material_texture, s->material_texture, st))) return rc;
+    }
     HIP_TRY(hipStreamSynchronize(st));
+    s->textured = textured;
+    s->dev.tri_uv = textured ? s->d_tri_uv.p : nullptr;
+    s->dev.textures = textured ? s->d_textures.p : nullptr;
+    s->dev.material_texture = textured ? s->d_material_texture.p : nullptr;
     s->dev.envs = s->d_envs.p;
     s->dev.nodes = s->d_nodes.p;
     s->dev.bigleaves = s->d_bigleaves.p;
@@ -883,7 +948,16 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, co
             trace_shadow();
         }
         uint32_t* const shade_heads = c->work.p + 3 * AGPT_FRONTIERS * AGPT_QSTRIDE;   // k_shade's tile heads, zeroed above
-        if (run.shade_fast) {
+        if (s->textured) {   // a material of the scene has a texture: the TEXTURED variants (agpt_shade_kernels_textured.hip)
+            if (run.shade_fast)
+                agpt::launch_shade_textured_fast(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt],
+                                                 c->counters.p, shade_heads);
+            else
+                agpt::launch_shade_textured(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt],
+                                            c->counters.p, shade_heads);
+            if (run.shade_fast) agpt::launch_resolve_pending_fast(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
+            else agpt::launch_resolve_pending(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
+        } else if (run.shade_fast) {
             agpt::launch_shade_fast(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p,
                                     shade_heads);
             agpt::launch_resolve_pending_fast(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);

@@ -55,9 +55,13 @@ k_feature_rays(DevCamera c, RenderConsts rc, float4* __restrict__ ray_o, float4*
 
 // albedo = (colour, flag): flag 1 a primitive with a material, 2 an emitter (null material), 0 a miss (colour 1 for both);
 // normal_depth = (Surface::ns -- spheres: (p - c) / r --, t), zero on a miss
-__global__ void __launch_bounds__(AGPT_BLOCK)
-k_features(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
-           const float4* __restrict__ ray_d, float4* __restrict__ albedo, float4* __restrict__ normal_depth) {
+// TEXTURED (scenes with a textured material): on a mesh hit the colour of a textured material is the texel k_shade_textured shades
+// that hit with (triangle_uv + texture_value, agpt_shade.h)
+template <bool TEXTURED>
+__device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderConsts& rc, const float4* __restrict__ colors,
+                                               const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
+                                               const float4* __restrict__ ray_d, float4* __restrict__ albedo,
+                                               float4* __restrict__ normal_depth) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rc.NP) return;
     int x, y;
@@ -91,12 +95,32 @@ k_features(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, cons
         a.w = 2.f;
         if (mat >= 0) {
             a = colors[mat];
+            if constexpr (TEXTURED) {
+                const int tex = sc.material_texture[mat];
+                if (tex >= 0 && !(h.id & AGPT_HIT_SPHERE)) {
+                    float tu, tv;
+                    triangle_uv(sc.tri_uv[2 * (size_t)h.id], sc.tri_uv[2 * (size_t)h.id + 1], h.b1, h.b2, &tu, &tv);
+                    const v3 c = texture_value(sc.textures[tex], tu, tv);
+                    a.x = c.x; a.y = c.y; a.z = c.z;
+                }
+            }
             a.w = 1.f;
         }
         nd.x = s.ns.x; nd.y = s.ns.y; nd.z = s.ns.z; nd.w = h.t;
     }
     albedo[ai] = a;
     normal_depth[ai] = nd;
+}
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_features(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
+           const float4* __restrict__ ray_d, float4* __restrict__ albedo, float4* __restrict__ normal_depth) {
+    features_pixel<false>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+}
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_features_textured(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits,
+                    const float4* __restrict__ ray_o, const float4* __restrict__ ray_d, float4* __restrict__ albedo,
+                    float4* __restrict__ normal_depth) {
+    features_pixel<true>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
 
 // state = (c.rgb, v): c = accum.rgb / n, v = the variance of the mean luminance from agpt_render_adaptive's estimate
@@ -207,7 +231,11 @@ void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderCon
 }
 void launch_features(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const float4* colors, const DevHit* hits,
                      const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth) {
-    hipLaunchKernelGGL(k_features, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+    if (sc.tri_uv)   // the scene has a textured material
+        hipLaunchKernelGGL(k_features_textured, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
+                           normal_depth);
+    else
+        hipLaunchKernelGGL(k_features, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
 void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,
                             float4* state) {

@@ -267,10 +267,6 @@ DevMaterial make_material(int type, const float color[3], float roughness, float
         if (diffuse_weight > 0) {
             m.has_diffuse = 1;
             m.has_retro = 1;
-            v3 d = diffuse_weight * c;
-            m.diffuse_R[0] = d.x;
-            m.diffuse_R[1] = d.y;
-            m.diffuse_R[2] = d.z;
         }
         m.roughness = roughness;
         const float aspect = 1.f;
@@ -278,27 +274,15 @@ DevMaterial make_material(int type, const float color[3], float roughness, float
         float ay = smaxf(.001f, (roughness * roughness) * aspect);
         m.alphax = smaxf(0.001f, ax);  // TrowbridgeReitzDistribution ctor, microfacet.h:120-122
         m.alphay = smaxf(0.001f, ay);
-        const float spec_tint = 0.f;
-        const v3 ctint = V3s(1.f);
-        const float r0 = ((eta - 1) * (eta - 1)) / ((eta + 1) * (eta + 1));  // SchlickR0FromEta, disney.h:23
-        v3 cspec0 = lerp3(metallic, r0 * lerp3(spec_tint, V3s(1.f), ctint), c);
-        m.R0[0] = cspec0.x;
-        m.R0[1] = cspec0.y;
-        m.R0[2] = cspec0.z;
         m.metallic = metallic;
         m.eta = eta;
         m.has_microfacet = 1;
     } else if (type == AGPT_MAT_MIRROR) {
         m.has_specular = 1;
-        m.mirror_R[0] = c.x;
-        m.mirror_R[1] = c.y;
-        m.mirror_R[2] = c.z;
     } else {
         m.has_diffuse = 1;
-        m.diffuse_R[0] = c.x;
-        m.diffuse_R[1] = c.y;
-        m.diffuse_R[2] = c.z;
     }
+    material_set_color(m, c);   // diffuse_R / R0 / mirror_R (agpt_scene.h: shared with the textured shading kernels)
     return m;
 }
 
@@ -501,6 +485,8 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
     out.nodes.assign(2 * (node_base + 2 * n_rootpairs), F4(0, 0, 0, 0));   // + the root-pair records (agpt_scene.h)
     out.tri_verts.resize(3 * tri_base);
     out.tri_shade.resize(4 * tri_base);
+    out.tri_uv.clear();
+    if (out.want_tri_uv) out.tri_uv.resize(2 * tri_base);
 
     int mesh_ordinal = 0;
     for (size_t pi = 0; pi < prims.size(); pi++) {
@@ -634,6 +620,10 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
             q[1] = F4(ss.y, ss.z, n0.x, n0.y);
             q[2] = F4(n0.z, n1.x, n1.y, n1.z);
             q[3] = F4(n2.x, n2.y, n2.z, bits((uint32_t)pi));
+            if (out.want_tri_uv) {
+                out.tri_uv[2 * (tb + t)] = F4(uv0.x, uv0.y, uv1.x, uv1.y);
+                out.tri_uv[2 * (tb + t) + 1] = F4(uv2.x, uv2.y, 0.f, 0.f);
+            }
         }
         for (int s = 0; s < n_tris; s++) {
             const int t = mesh.prim_index[s] / 3;

@@ -65,6 +65,8 @@ DevCamera make_camera(const agpt_camera_desc& d);
 
 struct FlatScene {
     std::vector<float4> nodes, tri_verts, tri_shade;
+    bool want_tri_uv = false;        // set by the caller: also fill tri_uv (scenes with a textured material)
+    std::vector<float4> tri_uv;      // two float4 per global triangle id (agpt_scene.h)
     std::vector<DevPrim> prims;
     std::vector<uint32_t> bigleaves;  // (first slot, count) pairs of leaves too big for the inline encoding
     int max_depth = 0;

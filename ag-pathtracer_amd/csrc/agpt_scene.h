@@ -15,6 +15,11 @@
 //   tri_shade  float4[4*T]  per global triangle id, ray-independent parts of the SurfaceInteraction the reference
 //                           rebuilds on every accepted hit (trianglemesh.cpp:46-111): geometric normal ng,
 //                           ss = normalize(dpdu), the three vertex normals, owning primitive
+//   tri_uv     float4[2*T]  per global triangle id, ONLY in scenes with a textured material: (u0, v0, u1, v1), (u2, v2, -, -) --
+//                           the triangle's texture coordinates (trianglemesh.cpp:46-56; (0,0), (1,0), (1,1) for a mesh without),
+//                           two aligned 16-B loads per shaded hit
+//   textures   DevTexture[X], material_texture int32[M] (texture id of a material, -1 = none): kept beside DevMaterial so that the
+//                           material table the untextured kernels stage in LDS stays what it was
 //   prims      DevPrim[P]   Scene::primitives in insertion order (scene.h:5-19 walks them linearly)
 //   materials  DevMaterial[M], lights DevLight[L]
 #pragma once
@@ -68,6 +73,45 @@ struct DevMaterial {
     float R0[3];         // Cspec0
     float metallic, eta;
     float mirror_R[3];
+};
+
+// The colour-dependent part of a material (DisneyMaterial / MirrorMaterial ctor, material.h:14-49,72-77), for a material whose
+// colour-independent fields are set: make_material runs it once with the material's constant colour, the textured shading
+// kernels once per hit with the texel -- the same fp32 operations in the same order.
+AGPT_HD void material_set_color(DevMaterial& m, v3 c) {
+    if (m.has_microfacet) {   // Disney
+        const float eta = 1.5f;
+        const float strans = 0.f;
+        const float diffuse_weight = (1 - m.metallic) * (1 - strans);
+        if (diffuse_weight > 0) {
+            v3 d = diffuse_weight * c;
+            m.diffuse_R[0] = d.x;
+            m.diffuse_R[1] = d.y;
+            m.diffuse_R[2] = d.z;
+        }
+        const float spec_tint = 0.f;
+        const v3 ctint = V3s(1.f);
+        const float r0 = ((eta - 1) * (eta - 1)) / ((eta + 1) * (eta + 1));  // SchlickR0FromEta, disney.h:23
+        v3 cspec0 = lerp3(m.metallic, r0 * lerp3(spec_tint, V3s(1.f), ctint), c);
+        m.R0[0] = cspec0.x;
+        m.R0[1] = cspec0.y;
+        m.R0[2] = cspec0.z;
+    } else if (m.has_specular) {   // mirror
+        m.mirror_R[0] = c.x;
+        m.mirror_R[1] = c.y;
+        m.mirror_R[2] = c.z;
+    } else {   // diffuse only
+        m.diffuse_R[0] = c.x;
+        m.diffuse_R[1] = c.y;
+        m.diffuse_R[2] = c.z;
+    }
+}
+
+// An image texture (HDRTexture, texture.h:41-84): texels row-major, row 0 = top, one float4 (rgb, -) each so that a lookup is
+// one 16-byte gather
+struct DevTexture {
+    const float4* texels;
+    int32_t width, height;
 };
 
 struct DevLight {
@@ -128,6 +172,10 @@ struct DevScene {
     int32_t n_toplevel;
     const unsigned long long* chunk_mesh_masks;   // mesh_masks[] again, in global memory (per-lane chunk index)
     DevCamera cam;
+    // image textures: all three NULL unless a material of the scene has one (only the TEXTURED kernel variants read them)
+    const float4* tri_uv;
+    const DevTexture* textures;
+    const int32_t* material_texture;   // [n_materials]
 };
 
 // 16-B hit record written by the trace kernel

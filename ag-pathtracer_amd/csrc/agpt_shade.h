@@ -518,6 +518,25 @@ __device__ __forceinline__ v3 env_value(const DevEnv& e, float u, float v) {  //
     float4 p = e.pixels[env_mod(ti, e.height) * e.width + env_mod(si, e.width)];
     return V3(p.x, p.y, p.z);
 }
+// ---- image textures (agpt_scene.h: tri_uv, DevTexture) -------------------------------------------------------------
+// TriangleIntersect's texture coordinates (trianglemesh.cpp:46-57): tc = uv[0] * b0 + uv[1] * b1 + uv[2] * b2 from the triangle's two
+// uv records (u0, v0, u1, v1), (u2, v2, -, -)
+__device__ __forceinline__ void triangle_uv(float4 uv01, float4 uv2, float b1, float b2, float* u, float* v) {
+    const float b0 = 1.f - b1 - b2;
+    *u = uv01.x * b0 + uv01.z * b1 + uv2.x * b2;
+    *v = uv01.y * b0 + uv01.w * b1 + uv2.y * b2;
+}
+// HDRTexture::value (texture.h:59-67): nearest texel with wrap.  A non-finite coordinate (finite input cannot produce one) reads
+// texel (0, 0); the float -> int conversion saturates for a huge finite one and env_mod brings it back inside the image.
+__device__ __forceinline__ v3 texture_value(const DevTexture& t, float u, float v) {
+    int x = 0, y = 0;
+    if (isfinite(u) && isfinite(v)) {
+        x = env_mod((int)floorf(u * t.width - .5f), t.width);
+        y = env_mod((int)floorf(v * t.height - .5f), t.height);
+    }
+    const float4 p = t.texels[(size_t)y * t.width + x];
+    return V3(p.x, p.y, p.z);
+}
 __device__ __forceinline__ float spherical_theta(v3 v) { return cr_acosf(tclampf(v.z, -1.f, 1.f)); }  // common.h:158-160
 __device__ __forceinline__ float spherical_phi(v3 v) {                                                // common.h:162-165
     float p = cr_atan2f(v.y, v.x);

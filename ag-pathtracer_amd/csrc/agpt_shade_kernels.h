@@ -12,7 +12,18 @@
 
 // The kernels of a unit compiled with AGPT_SHADE_FAST 1 (agpt_shade_kernels_fast.hip, agpt_shade_arith.h) carry the suffix
 // _fast: their host-side stubs would otherwise collide with the exact unit's at link time.
-#if AGPT_SHADE_FAST
+// A unit compiled with AGPT_SHADE_TEXTURED 1 (agpt_shade_kernels_textured.hip, agpt_shade_kernels_textured_fast.hip) holds the
+// TEXTURED variant of k_shade -- a material's colour at a mesh hit comes from its image texture (agpt_scene.h: tri_uv, textures,
+// material_texture) -- as k_shade_textured / k_shade_textured_fast; the launchers pick it for scenes that have a textured
+// material, every other scene runs the kernels of the two plain units, whose code the flag does not touch.
+#ifndef AGPT_SHADE_TEXTURED
+#define AGPT_SHADE_TEXTURED 0
+#endif
+#if AGPT_SHADE_TEXTURED && AGPT_SHADE_FAST
+#define AGPT_SHADE_KNAME(n) n##_textured_fast
+#elif AGPT_SHADE_TEXTURED
+#define AGPT_SHADE_KNAME(n) n##_textured
+#elif AGPT_SHADE_FAST
 #define AGPT_SHADE_KNAME(n) n##_fast
 #else
 #define AGPT_SHADE_KNAME(n) n
@@ -73,7 +84,11 @@ __device__ __forceinline__ v3 pending_light_sample(const DevScene& sc, const Ren
 // ENV: the scene has an InfiniteAreaLight (lights.cpp:31-112).  Its sampling / pdf / Le helpers are out-of-line calls whose mere
 // presence costs the register allocation of every path (values live across a call site go to callee-saved registers); scenes
 // without an environment map -- every BASELINE configuration -- run the instantiation that does not contain them.
-template <bool ENV>
+// TEXTURED: see AGPT_SHADE_TEXTURED above.  The hit triangle's two uv records are fetched beside its tri_shade record (one more
+// pair of 16-B loads in the same round trip); the texel gather follows the material lookup, and material_set_color puts what
+// make_material derives from a colour -- diffuse_R, R0, mirror_R -- into a register copy of the material, which is what
+// bsdf_setup, lobe_eval, disney_fresnel and lobe_sample then read.
+template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0)>
 __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t pid SCK_PARAMS) {
     uint32_t bits = 0;
     // Every per-path record is fetched up front, unconditionally: the loads then overlap in one memory round trip instead
@@ -112,11 +127,17 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
         v3 O = V3(o4.x, o4.y, o4.z), D = V3(d4.x, d4.y, d4.z);
         const bool found = h.id != AGPT_HIT_MISS;
         Surface s;
+        float4 uv01 = {0.f, 0.f, 0.f, 0.f}, uv2 = {0.f, 0.f, 0.f, 0.f};   // (TEXTURED only)
         if (found) {
             if (h.id & AGPT_HIT_SPHERE)
                 surface_from_sphere(sc, (int)(h.id & 0x7FFFFFFFu), O, D, h.t, s);
-            else
+            else {
+                if constexpr (TEXTURED) {
+                    uv01 = sc.tri_uv[2 * (size_t)h.id];
+                    uv2 = sc.tri_uv[2 * (size_t)h.id + 1];
+                }
                 surface_from_triangle(sc, h.id, h.b1, h.b2, O, D, h.t, s);
+            }
         }
         SCK(2);   // surface record (tri_shade fetch + interpolation)
         // integrator.h:139-147
@@ -150,7 +171,18 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
         } else {
             SCK(3);   // emission, termination
             bits |= SB_SHADED;
-            const DevMaterial& m = sc.materials[sc.prims[s.prim].material];
+            const DevMaterial& mc = sc.materials[sc.prims[s.prim].material];
+            DevMaterial mt;   // TEXTURED: the material with the colour of the texel at the hit
+            if constexpr (TEXTURED) {
+                mt = mc;
+                const int tex = sc.material_texture[sc.prims[s.prim].material];
+                if (tex >= 0 && !(h.id & AGPT_HIT_SPHERE)) {
+                    float tu, tv;
+                    triangle_uv(uv01, uv2, h.b1, h.b2, &tu, &tv);
+                    material_set_color(mt, texture_value(sc.textures[tex], tu, tv));
+                }
+            }
+            const DevMaterial& m = TEXTURED ? mt : mc;
             Bsdf bsdf;
             bsdf_setup(bsdf, m, s.n, s.ns, s.ss_bsdf);
             const WoCache wc = bsdf_wo_cache(bsdf, m, s.wo);
@@ -438,6 +470,9 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
     __shared__ DevPrim s_tab_prims[LDS_TABLES ? AGPT_SHADE_LDS_PRIMS : 1];
     __shared__ DevMaterial s_tab_materials[LDS_TABLES ? AGPT_SHADE_LDS_MATERIALS : 1];
     __shared__ DevLight s_tab_lights[LDS_TABLES ? AGPT_SHADE_LDS_LIGHTS : 1];
+#if AGPT_SHADE_TEXTURED
+    __shared__ int32_t s_tab_material_texture[LDS_TABLES ? AGPT_SHADE_LDS_MATERIALS : 1];   // 512 B beside the 9.5 KB of materials
+#endif
     // (a launch over a short queue: one wave per 256-path tile is all it can use -- the rest of the grid leaves before setting up)
     if (blockIdx.x * (AGPT_BLOCK / 64) * 64u * SHADE_U >= QCOUNT(qin, 0) && blockIdx.x > 0) return;
     DevScene sc = sc_in;
@@ -453,6 +488,10 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
         sc.prims = s_tab_prims;
         sc.materials = s_tab_materials;
         sc.lights = s_tab_lights;
+#if AGPT_SHADE_TEXTURED
+        copy_words(s_tab_material_texture, sc_in.material_texture, sc_in.n_materials * (int)sizeof(int32_t));
+        sc.material_texture = s_tab_material_texture;
+#endif
         __syncthreads();
     }
     __shared__ uint32_t s_pid[SHADE_U][AGPT_BLOCK];
@@ -577,6 +616,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
 // Paths that have ended (MaxDepth reached, miss, black sample) while their last vertex' light sample was still waiting for its
 // shadow ray / MIS query: add the sample (integrator.h:166) and let the path go.  They used to ride through a whole
 // k_shade pass for this -- after the last bounce that is EVERY path of the batch: 10 records loaded, 3 wave slots per SIMD.
+#if !AGPT_SHADE_TEXTURED   // (no BSDF, no material: the TEXTURED units launch the plain units' kernel)
 __global__ void __launch_bounds__(AGPT_BLOCK)
 AGPT_SHADE_KNAME(k_resolve_pending)(DevScene sc, RenderConsts rc, PathBuffers pb, Queues qin) {
     const uint32_t n = QCOUNT(qin, 4);
@@ -595,4 +635,4 @@ AGPT_SHADE_KNAME(k_resolve_pending)(DevScene sc, RenderConsts rc, PathBuffers pb
         pb.L4[pid] = l4;
     }
 }
-
+#endif

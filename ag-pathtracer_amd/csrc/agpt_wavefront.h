@@ -136,7 +136,7 @@ __device__ __forceinline__ void queue_push(uint32_t* q, uint32_t* count, bool pr
 
 
 // ---------------------------------------------------------------------------------------------------------
-// host-side launchers of the shading translation units (agpt_shade_kernels.hip, agpt_shade_kernels_fast.hip)
+// host-side launchers of the shading translation units (agpt_shade_kernels.hip, agpt_shade_kernels_fast.hip and their _textured twins)
 namespace agpt {
 // the scene's Scene::primitives records, materials and lights fit the LDS copies k_shade<LDS_TABLES> works from
 bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights);
@@ -153,4 +153,10 @@ void launch_kat_bsdf_eval_fast(hipStream_t stream, const DevScene& sc, int mater
                                float* pdfo);
 void launch_kat_bsdf_sample_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* u2, float* wi3o,
                                  float* f3o, float* pdfo, int32_t* speco);
+// k_shade of the TEXTURED units (agpt_shade_kernels_textured.hip, agpt_shade_kernels_textured_fast.hip) for scenes with a textured
+// material; their ended paths go through launch_resolve_pending / launch_resolve_pending_fast
+void launch_shade_textured(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
+                           const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
+void launch_shade_textured_fast(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
+                                const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
 }  // namespace agpt

@@ -39,6 +39,7 @@ class SceneDesc:
         self.n_prims = 0
         self.n_lights = 0
         self.n_tris = 0
+        self.n_textures = 0
         self.camera = None
 
     def add_material(self, mtype, color, roughness=0.5, metallic=0.0):
@@ -82,6 +83,15 @@ class SceneDesc:
         self.n_lights += 1
         return self.n_lights - 1
 
+    def add_texture(self, rgb):
+        """An image texture rgb[H, W, 3] (float32, linear, row 0 = top); returns its id."""
+        self.ops.append(("texture", np.ascontiguousarray(rgb, F).copy()))
+        self.n_textures += 1
+        return self.n_textures - 1
+
+    def set_material_texture(self, material, texture):
+        self.ops.append(("material_texture", int(material), int(texture)))
+
     def set_camera(self, lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
         self.camera = (np.asarray(lookfrom, F).copy(), np.asarray(lookat, F).copy(), np.asarray(vup, F).copy(),
                        F(aspect_ratio), float(vfov), float(aperture))
@@ -104,6 +114,10 @@ class SceneDesc:
                 target.add_uniform_infinite_light(op[1])
             elif k == "env_light":
                 target.add_infinite_area_light(op[1])
+            elif k == "texture":
+                target.add_texture(op[1])
+            elif k == "material_texture":
+                target.set_material_texture(op[1], op[2])
         if self.camera is not None:
             target.set_camera(*self.camera)
         if hasattr(target, "commit"):
@@ -219,6 +233,31 @@ def scene_c1(backdrop=None):
     d.add_area_light([0, 25, -20], 1.0, KEY_LIGHT * F(200))
     d.add_uniform_infinite_light([.4, .45, .5])
     d.set_camera([-1.46, 1.16, -4.64], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
+    return d
+
+
+def checker_texture(width=64, height=64, cells=8, a=(0.80, 0.78, 0.70), b=(0.10, 0.22, 0.42)):
+    """Procedural texture rgb[height, width, 3] (linear): a `cells` x `cells` checker of colours a and b, each cell shaded by a
+    gradient along v so that no two rows of texels are alike."""
+    y, x = np.mgrid[0:height, 0:width]
+    odd = ((x * cells // width) + (y * cells // height)) % 2 == 1
+    base = np.where(odd[..., None], np.asarray(b, np.float64), np.asarray(a, np.float64))
+    shade = 0.55 + 0.45 * (y[..., None] + 0.5) / height
+    return (base * shade).astype(F)
+
+
+def scene_textured(texture=None, backdrop=None):
+    """C1 with images on its surfaces: the backdrop's floor material takes a texture (default: checker_texture()) -- the backdrop's
+    own texture coordinates run 0..1 across and 0..36 along the sweep, so the image repeats along it (HDRTexture::value wraps) --
+    and a half-metallic blob beside the gold sphere takes a second, finer checker through its (phi, theta) coordinates.  The gold
+    sphere keeps its constant colour (textures apply to meshes)."""
+    d = scene_c1(backdrop)
+    d.name = "C1-textured"
+    d.set_material_texture(0, d.add_texture(checker_texture() if texture is None else texture))
+    metal = d.add_material(MAT_DISNEY, [0.8, 0.5, 0.3], 0.4, 0.6)
+    v, n, t, idx = blob_mesh(24, 16, center=(2.2, 0.2, 0.6), radius=0.9, seed=3)
+    d.add_mesh(v, n, t, idx, metal, 1)
+    d.set_material_texture(metal, d.add_texture(checker_texture(32, 16, 8, a=(0.9, 0.6, 0.3), b=(0.6, 0.7, 0.8))))
     return d
 
 

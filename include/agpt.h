@@ -148,6 +148,29 @@ int agpt_scene_add_uniform_infinite_light(agpt_scene*, const float L[3]);
  * passed as width*height RGB floats (row-major, row 0 = top), i.e. what stbi_loadf returns in the reference (texture.h:43-53);
  * builds the max(rgb)*sin(theta) Distribution1D (sampling.h:19-69) on the host.  returns light index */
 int agpt_scene_add_infinite_area_light(agpt_scene*, const float* rgb, int width, int height);
+/* ---- image textures for the base colour of materials --------------------------------------------------------
+ * An RGB image for materials: width*height RGB floats, row-major, row 0 = top, LINEAR values -- the same form
+ * agpt_scene_add_infinite_area_light takes (an sRGB image is linearised by the host first).  Copied.  Returns the texture
+ * id >= 0.  Before agpt_scene_commit. */
+int agpt_scene_add_texture(agpt_scene*, const float* rgb, int width, int height);
+/* From now on `material`'s colour at a mesh hit is value(u, v) of `texture` instead of the constant it was created with;
+ * texture = -1 restores the constant.  Before agpt_scene_commit.  All fp32, every operation rounded on its own:
+ *   uv of the hit   TriangleIntersect's (trianglemesh.cpp:46-57): uv = uv0 * b0 + uv1 * b1 + uv2 * b2, summed left to right, with
+ *                   b0 = 1 - b1 - b2; a mesh without texture coordinates has (0,0), (1,0), (1,1) at every triangle.
+ *   value(u, v)     HDRTexture::value (texture.h:59-79): s = (int)floorf(u * width - .5f), t = (int)floorf(v * height - .5f), both
+ *                   wrapped with Mod (a - (a / b) * b, + b if negative), the nearest texel (s, t), no filtering.  A non-finite u
+ *                   or v reads texel (0, 0).
+ *   what it feeds   exactly what agpt_scene_add_material derives from `color`, recomputed per hit with the same operations in
+ *                   the same order (Disney: diffuseWeight * c and Cspec0 = lerp(metallic, R0(eta), c); mirror: R = c; diffuse-only:
+ *                   R = c).  The lobe set, roughness and metallic stay per material.  A texture whose texels all equal the
+ *                   material's colour therefore renders bit-identical to the untextured scene.
+ * Every path that shades sees the texture -- agpt_render, agpt_render_adaptive, agpt_li_batch, in both shading arithmetics (the
+ * uv interpolation and the texel choice decide what is read and stay exact under AGPT_SHADING_FAST) -- and agpt_render_features
+ * writes the texel as the albedo.  Triangle meshes only: agpt_scene_commit returns AGPT_ERR_INVALID if a sphere or a plane carries a
+ * textured material.  Scenes without a textured material run the kernels they ran before textures existed.
+ * Both calls return AGPT_ERR_INVALID (+ agpt_last_error) for a NULL argument, a non-positive size, an unknown material or texture
+ * id, or a scene that is already committed. */
+int agpt_scene_set_material_texture(agpt_scene*, int material, int texture);
 /* scene->camera = desc; Camera(desc) (camera.h:29-56,77-90) */
 int agpt_scene_set_camera(agpt_scene*, const agpt_camera_desc*);
 /* flatten + upload to HBM; must be called after the last add_* and before render/intersect */
@@ -274,7 +297,8 @@ int agpt_render_adaptive(agpt_scene*, const agpt_render_params* rp, const agpt_a
  * Camera::GetRay's arithmetic (camera.h:58-64) with the lens offset zero whatever the aperture; no RNG is drawn, so the buffers do
  * not depend on a seed -- and runs one Scene::Intersect (scene.h:5-13) on it (the launch path of agpt_intersect_device).  Per pixel:
  *     albedo       = (color.rgb, flag)   flag 1: a primitive with a material (Disney, mirror or diffuse-only), color = what
- *                                                agpt_scene_add_material was given, bit for bit
+ *                                                agpt_scene_add_material was given, bit for bit -- or, for a material with a
+ *                                                texture (agpt_scene_set_material_texture) on a mesh, the texel at the hit
  *                                        flag 2: an emitter (a primitive with the null material), color = (1, 1, 1)
  *                                        flag 0: a miss, color = (1, 1, 1)
  *     normal_depth = (ns.xyz, t)         ns = the shading normal the path tracer shades that hit with (shading.n: the interpolated
@@ -387,7 +411,8 @@ int agpt_device_download(agpt_ctx*, void* host_dst, const void* dev_src, size_t 
 int agpt_device_upload(agpt_ctx*, void* dev_dst, const void* host_src, size_t bytes);
 
 /* known-answer entry points (each runs the device implementation of one hot-path function on one lane) */
-/* BSDF::f + BSDF::Pdf (reflection.h:114-123,174-188) on the canonical frame ng = ns = +z, ss = +x */
+/* BSDF::f + BSDF::Pdf (reflection.h:114-123,174-188) on the canonical frame ng = ns = +z, ss = +x.  There is no hit here: both
+ * known-answer calls use the material's constant colour, whether or not it has a texture. */
 int agpt_kat_bsdf_eval(agpt_scene*, int material, int n, const float* wo3, const float* wi3, float* f3_out, float* pdf_out);
 /* BSDF::Sample_f (reflection.h:124-172) */
 int agpt_kat_bsdf_sample(agpt_scene*, int material, int n, const float* wo3, const float* u2, float* wi3_out,

@@ -183,6 +183,15 @@ public:
     int lights_push_back(const InfiniteAreaLight& l) {
         return check(agpt_scene_add_infinite_area_light(h_, l.rgb, l.width, l.height), "agpt_scene_add_infinite_area_light");
     }
+    // An image for materials (agpt_scene_add_texture): width * height linear RGB floats, row 0 = top -- HDRTexture's pixels
+    // (texture.h:41-84) handed over in memory; returns the texture id
+    int textures_push_back(const float* rgb, int width, int height) {
+        return check(agpt_scene_add_texture(h_, rgb, width, height), "agpt_scene_add_texture");
+    }
+    // the material's colour at a mesh hit becomes Texture::value(u, v) of `texture` (-1: its constant colour again)
+    void SetMaterialTexture(int material, int texture) {
+        check(agpt_scene_set_material_texture(h_, material, texture), "agpt_scene_set_material_texture");
+    }
     // upload to HBM; call once after the scene is built (and again after changing `camera`)
     void commit() {
         check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera");

@@ -1,0 +1,91 @@
+"""Developer measurement: what image textures cost.  C3 at 1080p / 64 spp untextured (k_shade) against the same scene with every
+material pointed at a 256x256 texture (k_shade_textured), two scenes in one process, each rendered --reps times, alternating,
+after a warm-up.  Per variant: step ms, trace ms, non-trace ms, the agpt_stats totals and non-trace ns per shaded vertex (medians).
+    python tools/textures_cost.py [--out profiles/textures_c3.json] [--reps 3] [--shading exact|fast] [--kernel-trace CSV]
+(--reps 1 --no-warmup: exactly one render per variant, the run for rocprofv3 --kernel-trace --stats; --kernel-trace adds that
+run's per-kernel times to the JSON)"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import ag_pathtracer_amd as ag  # noqa: E402
+
+
+def textured_c3(desc, size=256, seed=7):
+    """every material of the scene takes its own window of one size x size noise image scaled around the material's colour"""
+    rng = np.random.RandomState(seed)
+    noise = rng.uniform(0.6, 1.0, (size, size, 1)).astype(np.float32)
+    colors = [op[2] for op in desc.ops if op[0] == "material"]
+    for m, c in enumerate(colors):
+        desc.set_material_texture(m, desc.add_texture(np.clip(noise * np.asarray(c, np.float32), 0, 1)))
+    return desc
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--shading", default="exact", choices=["exact", "fast"])
+    ap.add_argument("--no-warmup", action="store_true")
+    ap.add_argument("--kernel-trace", default=None, metavar="CSV", help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of this tool")
+    a = ap.parse_args()
+    W, H, spp = 1920, 1080, 64
+    ctx = ag.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    scenes = {}
+    for name in ("untextured", "textured"):
+        d = ag.scenes.scene_c3(aspect=W / float(H))
+        if name == "textured":
+            d = textured_c3(d)
+        scenes[name] = d.instantiate(ag.Scene(ctx))
+        scenes[name].set_shading_arith(a.shading)
+    film = torch.zeros((H, W, 4), device="cuda")
+    pt = ag.PathTracer(5)
+
+    def step(name):
+        film.zero_()
+        return pt.render(scenes[name], W, H, spp, film.data_ptr(), accum_pitch=W, timing=True)
+
+    if not a.no_warmup:
+        for name in scenes:
+            step(name)
+    runs = {name: [] for name in scenes}
+    for _ in range(a.reps):
+        for name in scenes:
+            st = step(name)
+            runs[name].append(dict(step_ms=st.total_ms, trace_ms=st.trace_ms, non_trace_ms=st.total_ms - st.trace_ms,
+                                   shaded_vertices=int(st.shaded_vertices), rays=int(st.rays), closest_rays=int(st.closest_rays),
+                                   anyhit_rays=int(st.anyhit_rays), answered_rays=int(st.answered_rays), iterations=int(st.iterations)))
+    res = {"device": torch.cuda.get_device_name(0), "command": "python " + " ".join(sys.argv),
+           "config": dict(W=W, H=H, spp=spp, shading=a.shading, texture="256x256 per material, 35 materials", reps=a.reps)}
+    for name, rs in runs.items():
+        med = {k: statistics.median(r[k] for r in rs) for k in ("step_ms", "trace_ms", "non_trace_ms")}
+        med["non_trace_ns_per_shaded_vertex"] = med["non_trace_ms"] * 1e6 / max(1, rs[0]["shaded_vertices"])
+        med["stats"] = {k: rs[0][k] for k in ("shaded_vertices", "rays", "closest_rays", "anyhit_rays", "answered_rays", "iterations")}
+        med["runs"] = rs
+        res[name] = med
+        print("%-10s step %7.1f ms  trace %7.1f  non-trace %6.1f  shaded %6.1f M  %.3f ns/vertex" % (
+            name, med["step_ms"], med["trace_ms"], med["non_trace_ms"], rs[0]["shaded_vertices"] / 1e6,
+            med["non_trace_ns_per_shaded_vertex"]), flush=True)
+    res["non_trace_ratio"] = res["textured"]["non_trace_ms"] / res["untextured"]["non_trace_ms"]
+    res["step_ratio"] = res["textured"]["step_ms"] / res["untextured"]["step_ms"]
+    if a.kernel_trace:
+        rows = list(csv.DictReader(open(a.kernel_trace)))
+        res["kernel_trace"] = {r["Name"].split("(")[0]: dict(calls=int(r["Calls"]), total_ms=float(r["TotalDurationNs"]) / 1e6)
+                               for r in rows if "k_shade" in r["Name"] or "k_resolve_pending" in r["Name"]}
+    for s in scenes.values():
+        s.close()
+    ctx.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+        print("->", a.out)
+
+
+if __name__ == "__main__":
+    main()
