@@ -50,18 +50,36 @@ namespace {
             return fail(AGPT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));           \
     } while (0)
 
+// A device allocation that belongs to its holder: freed when the holder goes (a context, a scene, a local of an entry point on
+// every return path).  Move-only: std::vector<DevBuf<...>> is resized.
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) {
+        o.p = nullptr;
+        o.n = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    // exactly `count` elements (at least one), whatever was held before
+    hipError_t alloc(size_t count) {
+        release();
+        const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        else p = nullptr;
+        return e;
+    }
+    // at least `count` elements: grows, never shrinks
     int ensure(size_t count) {
         if (count <= n) return AGPT_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        const hipError_t e = alloc(count);
         if (e != hipSuccess) return fail(AGPT_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        n = count;
         return AGPT_OK;
     }
     void release() {
@@ -73,6 +91,13 @@ struct DevBuf {
 
 }  // namespace
 
+// The per-path pool, listed once: X(element type, name), the names being PathBuffers' members.  The context's buffers, their
+// allocation and release, the binding into PathBuffers and the bytes-per-path figure of the batch-size policy all come from here.
+#define AGPT_POOL_BUFFERS(X)                                                                                                  \
+    X(float4, ext_o) X(float4, ext_d) X(float4, sh_o) X(float4, sh_d) X(float4, mis_o) X(float4, mis_d) X(float4, beta4)      \
+    X(float4, L4) X(float4, fac4) X(float4, c1) X(float4, c2) X(DevHit, hit) X(DevHit, mis_hit) X(uint32_t, occluded)          \
+    X(uint32_t, mis_ok)
+
 struct agpt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -81,19 +106,17 @@ struct agpt_ctx {
     hipStream_t aux_stream[2] = {nullptr, nullptr};   // small batches: the MIS and shadow launches of an iteration run beside the closest-hit one
     hipEvent_t aux_ev[3] = {nullptr, nullptr, nullptr};
     int multi_stream = 0;
-    // path-state pool (sized for the largest batch seen)
+    // path-state pool (sized for the largest batch seen): AGPT_POOL_BUFFERS and the path-id queues, one element per path each
     size_t pool_paths = 0;
-    DevBuf<float4> ext_o, ext_d, sh_o, sh_d, mis_o, mis_d, beta4, L4, fac4, c1, c2;
-    DevBuf<DevHit> hit, mis_hit;
-    DevBuf<uint32_t> occluded, mis_ok;
+#define X(T, name) DevBuf<T> name;
+    AGPT_POOL_BUFFERS(X)
+#undef X
     DevBuf<uint32_t> q[2][AGPT_NQUEUES];
     DevBuf<uint32_t> qcounts;   // 2 x AGPT_NQUEUES queue lengths
     DevBuf<uint32_t> work;      // work-queue heads of the persistent trace launches
     DevBuf<DevCounters> counters;
     uint32_t* host_pinned = nullptr;
     int blocks_per_cu = 4;       // generic trace kernel (32-entry LDS stacks)
-    bool trace_recast = false;        // the closest-hit launch in flight is the wavefront loop's own (its rays carry d.w, see k_trace_fast)
-    bool trace_small_batch = false;   // the rays of the current batch number fewer than AGPT_SMALL_BATCH: k_trace_fast<PEEK>
     int shade_blocks_per_cu = 8;   // AGPT_SHADE_BLOCKS_PER_CU: k_shade's grid (its waves take wave tiles from work heads)
     int fast_blocks_per_cu = AGPT_FAST_BLOCKS_PER_CU;  // AGPT_BLOCKS_PER_CU: production trace kernel (AGPT_FAST_STACK-entry LDS stacks)
     DevBuf<uint32_t> spill;      // traversal-stack entries beyond the LDS part (BVHs deeper than AGPT_FAST_STACK)
@@ -165,16 +188,6 @@ struct agpt_scene {
     DevScene dev{};
 };
 
-// scoped device allocation for the entry points that need a temporary: freed on every return path
-template <class T>
-struct TempBuf {
-    T* p = nullptr;
-    ~TempBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t count) { return hipMalloc((void**)&p, (count ? count : 1) * sizeof(T)); }
-};
-
 template <class T>
 static int upload(DevBuf<T>& buf, const std::vector<T>& host, hipStream_t st) {
     int rc = buf.ensure(host.empty() ? 1 : host.size());
@@ -192,19 +205,33 @@ static bool use_fast_trace(const agpt_ctx* c, const DevScene& sc, int count) {
     return count != 1 && sc.n_prims <= 64 * AGPT_MAX_CHUNKS && !c->force_generic;
 }
 
-// LDS stack entries of the production kernel (23 KiB of stack + 8 KiB = 31 KiB per block -> five blocks per CU) and the
-// blocks per CU that go with it; deeper BVHs spill the entries beyond into c->spill (HBM)
 #define AGPT_SMALL_BATCH (48ull << 20)   // paths: below this the trace launches run the PEEK instantiation (see k_trace_fast)
+
+// One trace launch, said in full: where it is enqueued, what it reads and writes, and what picks its kernel instantiation.
+struct TraceLaunch {
+    hipStream_t stream;
+    const uint32_t* queue;       // path ids and their number on the device, or (nullptr, nullptr, n): the rays 0 .. n
+    const uint32_t* count_ptr;
+    uint32_t count_imm;
+    uint32_t* work_head;         // the launch's work-queue frontiers in agpt_ctx::work, zeroed by the caller
+    const float4 *ro, *rd;
+    DevHit* hits;
+    uint32_t* occ;
+    int count;                   // see use_fast_trace
+    bool small_batch;            // the rays of the batch number fewer than AGPT_SMALL_BATCH: k_trace_fast<PEEK>
+    bool recast;                 // the wavefront loop's own closest-hit launch (its rays carry d.w): may re-cast a ray in place, see
+                                 // the retire branch of k_trace_fast
+};
+
 template <int MODE, bool COUNT, bool SPILL, bool PEEK>
-static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm,
-                              uint32_t* work_head, const float4* ro, const float4* rd, DevHit* hits, uint32_t* occ, int refill) {
+static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch& t) {
     const dim3 block(AGPT_BLOCK), g(fast_grid(c));
+    const int refill = MODE == 0 ? c->refill : c->refill_any;
     if (sc.n_prims <= 64) {
-        // (closest-hit launches of the wavefront loop may re-cast a ray in place: see the retire branch of k_trace_fast)
-        float4* ro_w = MODE == 0 && c->trace_recast ? const_cast<float4*>(ro) : nullptr;
-        float4* rd_w = MODE == 0 && c->trace_recast ? const_cast<float4*>(rd) : nullptr;
-        hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, false, COUNT, SPILL, PEEK>), g, block, 0, c->stream, sc, queue, count_ptr,
-                           count_imm, work_head, ro, rd, hits, occ, c->counters.p, refill, 0u, c->spill.p,
+        float4* ro_w = MODE == 0 && t.recast ? const_cast<float4*>(t.ro) : nullptr;
+        float4* rd_w = MODE == 0 && t.recast ? const_cast<float4*>(t.rd) : nullptr;
+        hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, false, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
+                           t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, refill, 0u, c->spill.p,
                            (const unsigned long long*)nullptr, (const uint32_t*)nullptr, ro_w, rd_w, (const float4*)c->beta4.p, c->L4.p);
         return;
     }
@@ -215,72 +242,58 @@ static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const uint32_t* q
         c->note(hipErrorOutOfMemory);   // (ensure_pool sizes both for the scene: not reached)
         return;
     }
-    hipLaunchKernelGGL((k_candidates<MODE>), dim3(c->num_cus * 8), block, 0, c->stream, sc, queue, count_ptr, count_imm, ro, rd,
+    hipLaunchKernelGGL((k_candidates<MODE>), dim3(c->num_cus * 8), block, 0, t.stream, sc, t.queue, t.count_ptr, t.count_imm, t.ro, t.rd,
                        c->cand_mask.p, c->cand_chunks.p, stride);
-    hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, true, COUNT, SPILL, PEEK>), g, block, 0, c->stream, sc, queue, count_ptr,
-                       count_imm, work_head, ro, rd, hits, occ, c->counters.p, refill, stride, c->spill.p,
+    hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, true, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
+                       t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, refill, stride, c->spill.p,
                        (const unsigned long long*)c->cand_mask.p, (const uint32_t*)c->cand_chunks.p, (float4*)nullptr, (float4*)nullptr,
                        (const float4*)nullptr, (float4*)nullptr);
 }
 
-template <int MODE>
-static void launch_trace_fast_c(agpt_ctx* c, int count, const DevScene& sc, const uint32_t* queue, const uint32_t* count_ptr,
-                                uint32_t count_imm, uint32_t* work_head, const float4* ro, const float4* rd, DevHit* hits,
-                                uint32_t* occ, int refill) {
-    const bool spill = sc.max_depth > AGPT_FAST_STACK;
-    if (spill) {
-        // one column of (max_depth - AGPT_FAST_STACK) entries per thread of the grid
-        const size_t need = (size_t)(sc.max_depth - AGPT_FAST_STACK) * (size_t)fast_grid(c) * AGPT_BLOCK;
-        if (c->spill.ensure(need) != AGPT_OK) {
-            c->note(hipErrorOutOfMemory);
-            return;
-        }
-    }
-    if (count) {
-        if (spill) launch_trace_fast<MODE, true, true, false>(c, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, refill);
-        else launch_trace_fast<MODE, true, false, false>(c, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, refill);
-    } else if (c->trace_small_batch) {   // (see PEEK in k_trace_fast)
-        if (spill) launch_trace_fast<MODE, false, true, true>(c, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, refill);
-        else launch_trace_fast<MODE, false, false, true>(c, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, refill);
-    } else {
-        if (spill) launch_trace_fast<MODE, false, true, false>(c, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, refill);
-        else launch_trace_fast<MODE, false, false, false>(c, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, refill);
-    }
+template <bool ANY, bool COUNT, int DEPTH>
+static void launch_trace_generic(agpt_ctx* c, int grid, const DevScene& sc, const TraceLaunch& t) {
+    hipLaunchKernelGGL((k_trace<ANY, COUNT, DEPTH>), dim3(grid), dim3(AGPT_BLOCK), 0, t.stream, sc, t.queue, t.count_ptr, t.count_imm,
+                       t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p);
 }
 
 // MODE 0 closest, 1 any-hit, 2 MIS query (production kernel only; the generic kernel traces MIS rays as closest hits)
 template <int MODE>
-static void launch_trace(agpt_ctx* c, const DevScene& sc, const uint32_t* queue, const uint32_t* count_ptr, uint32_t count_imm,
-                         uint32_t* work_head, const float4* ro, const float4* rd, DevHit* hits, uint32_t* occ, int count) {
+static void launch_trace(agpt_ctx* c, const DevScene& sc, const TraceLaunch& t) {
     constexpr bool ANY = MODE == 1;
-    dim3 grid(trace_grid(c)), block(AGPT_BLOCK);
-    if (use_fast_trace(c, sc, count)) {
-        const int refill = MODE == 0 ? c->refill : c->refill_any;
-        launch_trace_fast_c<MODE>(c, count, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, refill);
+    if (use_fast_trace(c, sc, t.count)) {
+        const bool spill = sc.max_depth > AGPT_FAST_STACK;
+        if (spill) {
+            // one column of (max_depth - AGPT_FAST_STACK) entries per thread of the grid
+            const size_t need = (size_t)(sc.max_depth - AGPT_FAST_STACK) * (size_t)fast_grid(c) * AGPT_BLOCK;
+            if (c->spill.ensure(need) != AGPT_OK) {
+                c->note(hipErrorOutOfMemory);
+                return;
+            }
+        }
+        // <COUNT, SPILL, PEEK>: a counting launch never peeks, so six of the eight combinations exist
+        if (t.count) {
+            if (spill) launch_trace_fast<MODE, true, true, false>(c, sc, t);
+            else launch_trace_fast<MODE, true, false, false>(c, sc, t);
+        } else if (t.small_batch) {   // (see PEEK in k_trace_fast)
+            if (spill) launch_trace_fast<MODE, false, true, true>(c, sc, t);
+            else launch_trace_fast<MODE, false, false, true>(c, sc, t);
+        } else {
+            if (spill) launch_trace_fast<MODE, false, true, false>(c, sc, t);
+            else launch_trace_fast<MODE, false, false, false>(c, sc, t);
+        }
     } else if (sc.max_depth > AGPT_STACK_DEPTH) {
-        dim3 grid_deep(c->num_cus * 2);
-        if (count)
-            hipLaunchKernelGGL((k_trace<ANY, true, AGPT_STACK_DEPTH_MAX>), grid_deep, block, 0, c->stream, sc, queue, count_ptr,
-                               count_imm, work_head, ro, rd, hits, occ, c->counters.p);
-        else
-            hipLaunchKernelGGL((k_trace<ANY, false, AGPT_STACK_DEPTH_MAX>), grid_deep, block, 0, c->stream, sc, queue, count_ptr,
-                               count_imm, work_head, ro, rd, hits, occ, c->counters.p);
-    } else if (count)
-        hipLaunchKernelGGL((k_trace<ANY, true, AGPT_STACK_DEPTH>), grid, block, 0, c->stream, sc, queue, count_ptr, count_imm,
-                           work_head, ro, rd, hits, occ, c->counters.p);
+        if (t.count) launch_trace_generic<ANY, true, AGPT_STACK_DEPTH_MAX>(c, c->num_cus * 2, sc, t);
+        else launch_trace_generic<ANY, false, AGPT_STACK_DEPTH_MAX>(c, c->num_cus * 2, sc, t);
+    } else if (t.count)
+        launch_trace_generic<ANY, true, AGPT_STACK_DEPTH>(c, trace_grid(c), sc, t);
     else
-        hipLaunchKernelGGL((k_trace<ANY, false, AGPT_STACK_DEPTH>), grid, block, 0, c->stream, sc, queue, count_ptr, count_imm,
-                           work_head, ro, rd, hits, occ, c->counters.p);
+        launch_trace_generic<ANY, false, AGPT_STACK_DEPTH>(c, trace_grid(c), sc, t);
 }
 
 static void release_pool(agpt_ctx* c) {
-    for (DevBuf<float4>* b : {&c->ext_o, &c->ext_d, &c->sh_o, &c->sh_d, &c->mis_o, &c->mis_d, &c->beta4, &c->L4, &c->fac4, &c->c1,
-                              &c->c2})
-        b->release();
-    c->hit.release();
-    c->mis_hit.release();
-    c->occluded.release();
-    c->mis_ok.release();
+#define X(T, name) c->name.release();
+    AGPT_POOL_BUFFERS(X)
+#undef X
     for (int i = 0; i < 2; i++)
         for (int j = 0; j < AGPT_NQUEUES; j++) c->q[i][j].release();
     c->cand_mask.release();
@@ -296,17 +309,16 @@ static hipEvent_t next_event(agpt_ctx* c) {
     return c->tev[c->tev_used++];
 }
 
+// a trace launch of the wavefront loop: its asynchronous errors are noted, and with `timing` it sits between two events of `kind`
 template <int MODE>
-static void launch_trace_timed(agpt_ctx* c, bool timing, int kind, const DevScene& sc, const uint32_t* queue,
-                               const uint32_t* count_ptr, uint32_t count_imm, uint32_t* work_head, const float4* ro,
-                               const float4* rd, DevHit* hits, uint32_t* occ, int count) {
+static void launch_trace_timed(agpt_ctx* c, bool timing, int kind, const DevScene& sc, const TraceLaunch& t) {
     if (timing) {
-        c->note(hipEventRecord(next_event(c), c->stream));
+        c->note(hipEventRecord(next_event(c), t.stream));
         c->tev_kind.push_back(kind);
     }
-    launch_trace<MODE>(c, sc, queue, count_ptr, count_imm, work_head, ro, rd, hits, occ, count);
+    launch_trace<MODE>(c, sc, t);
     c->note(hipGetLastError());
-    if (timing) c->note(hipEventRecord(next_event(c), c->stream));
+    if (timing) c->note(hipEventRecord(next_event(c), t.stream));
 }
 
 extern "C" {
@@ -353,13 +365,6 @@ void agpt_destroy(agpt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    release_pool(c);   // every per-path buffer (one list, shared with the batch-halving path of agpt_render)
-    c->qcounts.release();
-    c->spill.release();
-    c->work.release();
-    c->counters.release();
-    for (DevBuf<uint32_t>* b : {&c->adapt_masks, &c->adapt_blocks, &c->adapt_list, &c->adapt_words}) b->release();
-    c->denoise_state.release();
     if (c->host_pinned) (void)hipHostFree(c->host_pinned);
     for (auto& ev : c->tev) (void)hipEventDestroy(ev);
     for (auto& ev : c->ev)
@@ -368,7 +373,7 @@ void agpt_destroy(agpt_ctx* c) {
         if (ev) (void)hipEventDestroy(ev);
     for (auto& st : c->aux_stream)
         if (st) (void)hipStreamDestroy(st);
-    delete c;
+    delete c;   // (and with it every device buffer the context holds)
 }
 
 // ---- scene building -----------------------------------------------------------------------------------------
@@ -384,25 +389,6 @@ void agpt_scene_destroy(agpt_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipDeviceSynchronize();
-    s->d_nodes.release();
-    s->d_bigleaves.release();
-    s->d_tri_verts.release();
-    s->d_tri_shade.release();
-    s->d_prefilter.release();
-    s->d_toplevel.release();
-    s->d_chunk_mesh_masks.release();
-    s->d_prims.release();
-    s->d_materials.release();
-    s->d_colors.release();
-    s->d_lights.release();
-    s->d_envs.release();
-    s->d_tri_uv.release();
-    s->d_textures.release();
-    s->d_material_texture.release();
-    for (auto& b : s->d_texels) b.release();
-    for (auto& b : s->d_env_pixels) b.release();
-    for (auto& b : s->d_env_func) b.release();
-    for (auto& b : s->d_env_cdf) b.release();
     delete s;
 }
 
@@ -414,6 +400,18 @@ int agpt_scene_add_material(agpt_scene* s, int type, const float color[3], float
     s->material_texture.push_back(-1);
     s->committed = false;
     return (int)s->materials.size() - 1;
+}
+
+// the Scene::primitives record of a mesh / sphere / plane just added; returns its primitive id
+static int add_prim(agpt_scene* s, int type, int index, int material) {
+    agpt::HostPrim p;
+    p.type = type;
+    p.index = index;
+    p.material = material;
+    p.arealight = -1;
+    s->prims.push_back(p);
+    s->committed = false;
+    return (int)s->prims.size() - 1;
 }
 
 int agpt_scene_add_mesh(agpt_scene* s, const float* vertices, int n_vertices, const float* normals, int n_normals,
@@ -460,14 +458,7 @@ int agpt_scene_add_mesh(agpt_scene* s, const float* vertices, int n_vertices, co
         agpt::build_bvh(m, max_prims_in_node);
     }
     s->meshes.push_back(std::move(m));
-    agpt::HostPrim p;
-    p.type = AGPT_PRIM_MESH;
-    p.index = (int)s->meshes.size() - 1;
-    p.material = material;
-    p.arealight = -1;
-    s->prims.push_back(p);
-    s->committed = false;
-    return (int)s->prims.size() - 1;
+    return add_prim(s, AGPT_PRIM_MESH, (int)s->meshes.size() - 1, material);
 }
 
 int agpt_scene_add_sphere(agpt_scene* s, const float center[3], float radius, int material) {
@@ -478,14 +469,7 @@ int agpt_scene_add_sphere(agpt_scene* s, const float center[3], float radius, in
     sp.r = radius;
     sp.r2 = radius * radius;
     s->spheres.push_back(sp);
-    agpt::HostPrim p;
-    p.type = AGPT_PRIM_SPHERE;
-    p.index = (int)s->spheres.size() - 1;
-    p.material = material;
-    p.arealight = -1;
-    s->prims.push_back(p);
-    s->committed = false;
-    return (int)s->prims.size() - 1;
+    return add_prim(s, AGPT_PRIM_SPHERE, (int)s->spheres.size() - 1, material);
 }
 
 int agpt_scene_add_plane(agpt_scene* s, const float o[3], const float size[2], int material) {
@@ -496,14 +480,7 @@ int agpt_scene_add_plane(agpt_scene* s, const float o[3], const float size[2], i
     sp.r = size[0] / 2;
     sp.r2 = size[1] / 2;
     s->spheres.push_back(sp);
-    agpt::HostPrim p;
-    p.type = AGPT_PRIM_PLANE;
-    p.index = (int)s->spheres.size() - 1;
-    p.material = material;
-    p.arealight = -1;
-    s->prims.push_back(p);
-    s->committed = false;
-    return (int)s->prims.size() - 1;
+    return add_prim(s, AGPT_PRIM_PLANE, (int)s->spheres.size() - 1, material);
 }
 
 int agpt_scene_add_area_light(agpt_scene* s, const float center[3], float radius, const float L[3]) {
@@ -705,12 +682,18 @@ int agpt_mesh_get_bvh(const agpt_scene* s, int prim, agpt_bvh_node* nodes_out, i
     return AGPT_OK;
 }
 
+// the mesh arguments of agpt_bvh_build / agpt_bvh_build_device (n_indices index triplets, as agpt_scene_add_mesh)
+static int check_bvh_input(const char* fn, const float* vertices, int n_vertices, const int32_t* indices, int n_indices) {
+    if (!vertices || !indices || n_vertices <= 0 || n_indices < 3 || n_indices % 3 != 0)
+        return fail(AGPT_ERR_INVALID, std::string(fn) + ": need at least one triangle");
+    for (int i = 0; i < n_indices; i++)
+        if (indices[3 * i] < 0 || indices[3 * i] >= n_vertices) return fail(AGPT_ERR_INVALID, std::string(fn) + ": vertex index out of range");
+    return AGPT_OK;
+}
+
 int agpt_bvh_build(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int max_prims_in_node,
                    agpt_bvh_node* nodes_out, int32_t* prim_index_out, int* total_nodes_out, int* max_depth_out) {
-    if (!vertices || !indices || n_vertices <= 0 || n_indices < 3 || n_indices % 3 != 0)
-        return fail(AGPT_ERR_INVALID, "agpt_bvh_build: need at least one triangle");
-    for (int i = 0; i < n_indices; i++)
-        if (indices[3 * i] < 0 || indices[3 * i] >= n_vertices) return fail(AGPT_ERR_INVALID, "agpt_bvh_build: vertex index out of range");
+    if (const int rc = check_bvh_input("agpt_bvh_build", vertices, n_vertices, indices, n_indices)) return rc;
     agpt::HostMesh m;
     m.vertices.resize(n_vertices);
     for (int i = 0; i < n_vertices; i++) m.vertices[i] = V3(vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);
@@ -743,11 +726,7 @@ int agpt_bvh_build_device(agpt_ctx* c, const float* vertices, int n_vertices, co
                           int max_prims_in_node, agpt_bvh_node* nodes_out, int32_t* prim_index_out, int* total_nodes_out,
                           int* max_depth_out, int* on_device_out) {
     if (!c) return fail(AGPT_ERR_INVALID, "agpt_bvh_build_device: NULL context");
-    if (!vertices || !indices || n_vertices <= 0 || n_indices < 3 || n_indices % 3 != 0)
-        return fail(AGPT_ERR_INVALID, "agpt_bvh_build_device: need at least one triangle");
-    for (int i = 0; i < n_indices; i++)
-        if (indices[3 * i] < 0 || indices[3 * i] >= n_vertices)
-            return fail(AGPT_ERR_INVALID, "agpt_bvh_build_device: vertex index out of range");
+    if (const int rc = check_bvh_input("agpt_bvh_build_device", vertices, n_vertices, indices, n_indices)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     int total = 0, depth = 0, on_device = 0;
     const int rc = agpt::build_bvh_device(c->stream, vertices, n_vertices, indices, n_indices / 3, max_prims_in_node, nodes_out,
@@ -831,8 +810,11 @@ int agpt_device_upload(agpt_ctx* c, void* dst, const void* src, size_t bytes) {
 }
 
 // ---- hot path -----------------------------------------------------------------------------------------------
-// bytes of pool state per path: 11 float4 arrays + 2 hit arrays (16 B) + 2 flag words + 2 x AGPT_NQUEUES queue words
-#define AGPT_BYTES_PER_PATH (11 * 16 + 2 * 16 + 2 * 4 + 2 * AGPT_NQUEUES * 4)
+// bytes of pool state per path: the AGPT_POOL_BUFFERS elements + 2 x AGPT_NQUEUES queue words
+#define X(T, name) +sizeof(T)
+constexpr size_t AGPT_BYTES_PER_PATH = (0 AGPT_POOL_BUFFERS(X)) + 2 * AGPT_NQUEUES * sizeof(uint32_t);
+#undef X
+static_assert(AGPT_BYTES_PER_PATH == 256, "11 float4 arrays + 2 hit arrays (16 B) + 2 flag words + 10 queue words");
 // extra pool bytes per path for a scene: the candidate words of lists longer than 64 primitives (k_candidates)
 static size_t candidate_bytes_per_path(int n_prims) { return n_prims > 64 ? 4 + 8 * (size_t)((n_prims + 63) / 64) : 0; }
 static int ensure_pool(agpt_ctx* c, size_t paths, int n_prims) {
@@ -844,13 +826,10 @@ static int ensure_pool(agpt_ctx* c, size_t paths, int n_prims) {
         if ((rc = c->cand_chunks.ensure(paths))) return rc;
         if ((rc = c->cand_mask.ensure(paths * (size_t)((n_prims + 63) / 64)))) return rc;
     }
-    for (DevBuf<float4>* b : {&c->ext_o, &c->ext_d, &c->sh_o, &c->sh_d, &c->mis_o, &c->mis_d, &c->beta4, &c->L4, &c->fac4,
-                              &c->c1, &c->c2})
-        if ((rc = b->ensure(paths))) return rc;
-    if ((rc = c->hit.ensure(paths))) return rc;
-    if ((rc = c->mis_hit.ensure(paths))) return rc;
-    if ((rc = c->occluded.ensure(paths))) return rc;
-    if ((rc = c->mis_ok.ensure(paths))) return rc;
+#define X(T, name) \
+    if ((rc = c->name.ensure(paths))) return rc;
+    AGPT_POOL_BUFFERS(X)
+#undef X
     for (int i = 0; i < 2; i++)
         for (int j = 0; j < AGPT_NQUEUES; j++)
             if ((rc = c->q[i][j].ensure(paths))) return rc;
@@ -861,26 +840,93 @@ static int ensure_pool(agpt_ctx* c, size_t paths, int n_prims) {
     return AGPT_OK;
 }
 
+// The batch-size policy of the renderers: a pool for unit * count paths, `count` halved until it fits.  The batch is a
+// performance choice, not a semantic one (the image is batch-split invariant): when the pool has to grow, keep it within the
+// memory that is actually free (other ranks or applications may share the GPU), and halve the batch if an allocation still fails.
+static int fit_pool(agpt_ctx* c, const agpt_scene* s, size_t unit, uint64_t& count) {
+    if (unit * (size_t)count > c->pool_paths) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            const size_t per_path = AGPT_BYTES_PER_PATH + candidate_bytes_per_path(s->dev.n_prims);
+            const size_t avail = free_b + c->pool_paths * per_path;
+            const size_t fit = (size_t)((double)avail * 0.9) / per_path;
+            while (count > 1 && unit * (size_t)count > fit) count = (count + 1) / 2;
+        }
+    }
+    int rc = ensure_pool(c, unit * (size_t)count, s->dev.n_prims);
+    while (rc == AGPT_ERR_NOMEM && count > 1) {
+        release_pool(c);
+        count = (count + 1) / 2;
+        rc = ensure_pool(c, unit * (size_t)count, s->dev.n_prims);
+    }
+    return rc;
+}
+
+static bool shade_tables_fit_lds(const DevScene& d) {
+    return agpt::shade_tables_fit_lds(d.n_prims, d.n_materials, d.n_lights) && !getenv("AGPT_SHADE_GLOBAL_TABLES");
+}
+
+// What a call that runs the wavefront loop sets up once (begin_wavefront): the pool as the kernels see it, how rays are traced and
+// counted, which shading kernels run; and what the loop adds up for the call's statistics (fill_stats).
+struct WavefrontRun {
+    PathBuffers pb;
+    Queues q[2];
+    bool mis_mode, timing;
+    int count;              // enable_counters, normalised (see use_fast_trace)
+    agpt::ShadeVariant shade;
+    uint64_t iterations = 0, launches = 0;
+};
+
+static int begin_wavefront(agpt_ctx* c, const agpt_scene* s, int enable_counters, bool timing, WavefrontRun& run) {
+#define X(T, name) run.pb.name = c->name.p;
+    AGPT_POOL_BUFFERS(X)
+#undef X
+    for (int i = 0; i < 2; i++) {
+        Queues& q = run.q[i];
+        q.active = c->q[i][0].p; q.ext = c->q[i][1].p; q.mis = c->q[i][2].p; q.shadow = c->q[i][3].p;
+        q.resolve = c->q[i][4].p;
+        q.counts = c->qcounts.p + AGPT_NQUEUES * AGPT_QSTRIDE * i;
+    }
+    run.count = enable_counters == 2 ? 2 : (enable_counters != 0 ? 1 : 0);
+    run.mis_mode = use_fast_trace(c, s->dev, run.count) && !c->mis_closest;
+    run.timing = timing;
+    run.shade.fast = s->shading_arith == AGPT_SHADING_FAST;   // agpt_scene_set_shading_arith
+    run.shade.textured = s->textured;                         // a material of the scene has a texture
+    run.shade.lds_tables = shade_tables_fit_lds(s->dev);
+    run.shade.env = !s->envs.empty();                         // an InfiniteAreaLight is present
+    c->tev_used = 0;
+    c->tev_kind.clear();
+    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
+    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    return AGPT_OK;
+}
+
+// the part of RenderConsts that the wavefront loop's kernels read
+static void set_wavefront_consts(RenderConsts& rc, const WavefrontRun& run, int max_depth, bool trace_all_rays) {
+    rc.max_depth = max_depth;
+    rc.mis_mode = run.mis_mode ? 1 : 0;
+    rc.answer_rays = (run.mis_mode && !trace_all_rays) ? 1 : 0;
+}
+
 // The wavefront loop of PathTracer::Li (integrator.h:124-191) over the paths k_generate / k_generate_li have set up in q[0]:
 // per iteration the three trace launches, k_shade and k_resolve_pending.  A path needs at most max_depth + 2 iterations unless it
 // crosses emitter spheres (pass-through re-casts do not count as bounces, integrator.h:152-161): that many run without a host
 // round trip, then the loop keeps going while the active or the resolve queue is non-empty.
-struct WavefrontRun {
-    bool mis_mode, timing, shade_lds_tables, shade_env;
-    bool shade_fast;        // agpt_scene_set_shading_arith(AGPT_SHADING_FAST): k_shade_fast, k_resolve_pending_fast
-    int count;              // enable_counters, normalised
-    uint64_t iterations = 0, launches = 0;
-};
-static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, const PathBuffers& pb, Queues q[2], WavefrontRun& run) {
+static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, WavefrontRun& run) {
     const int count = run.count;
-    const bool mis_mode = run.mis_mode, timing = run.timing;
+    const PathBuffers& pb = run.pb;
+    Queues* const q = run.q;
     const int shade_grid = c->num_cus * c->shade_blocks_per_cu;
-    c->trace_small_batch = (unsigned long long)rcn.NP * (unsigned long long)rcn.S < AGPT_SMALL_BATCH;
+    const bool small_batch = (unsigned long long)rcn.NP * (unsigned long long)rcn.S < AGPT_SMALL_BATCH;
     const bool recast = !getenv("AGPT_NO_RECAST");   // (developer knob: emitter pass-throughs through k_shade, an iteration each)
     // side streams: not where the launches share scratch buffers (the HBM stack spill of deep BVHs, the candidate words of long
     // lists), nor with the reference-order kernels
-    const bool side = (c->multi_stream == 2 || (c->multi_stream == 1 && c->trace_small_batch)) && use_fast_trace(c, s->dev, count) &&
+    const bool side = (c->multi_stream == 2 || (c->multi_stream == 1 && small_batch)) && use_fast_trace(c, s->dev, count) &&
                       s->dev.max_depth <= AGPT_FAST_STACK && s->dev.n_prims <= 64;
+    // AGPT_MULTI_STREAM: the three trace launches of an iteration are independent -- MIS and shadow rays on streams of their own,
+    // beside the closest-hit launch
+    const hipStream_t main_stream = c->stream, mis_stream = side ? c->aux_stream[0] : main_stream,
+                      shadow_stream = side ? c->aux_stream[1] : main_stream;
     int cur = 0;
     const int planned = rcn.max_depth + 2;
     for (int it = 0;; it++) {
@@ -891,8 +937,8 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, co
             // and the iterations out here are a few hundred microseconds long).  The price is one iteration of launches over
             // empty queues at the very end (the kernels return at once on those).
             uint32_t* slot = c->host_pinned + (it & 1) * (AGPT_NQUEUES * AGPT_QSTRIDE);
-            HIP_TRY(hipMemcpyAsync(slot, q[cur].counts, (4 * AGPT_QSTRIDE + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipEventRecord(c->ev[2 + (it & 1)], c->stream));
+            HIP_TRY(hipMemcpyAsync(slot, q[cur].counts, (4 * AGPT_QSTRIDE + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream));
+            HIP_TRY(hipEventRecord(c->ev[2 + (it & 1)], main_stream));
             if (it > planned) {
                 const uint32_t* seen = c->host_pinned + ((it - 1) & 1) * (AGPT_NQUEUES * AGPT_QSTRIDE);
                 HIP_TRY(hipEventSynchronize(c->ev[2 + ((it - 1) & 1)]));
@@ -901,44 +947,32 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, co
             if (it > 4096) return fail(AGPT_ERR_LIMIT, "agpt: path did not terminate");
         }
         const int nxt = cur ^ 1;
-        HIP_TRY(hipMemsetAsync(q[nxt].counts, 0, AGPT_NQUEUES * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
-        HIP_TRY(hipMemsetAsync(c->work.p, 0, 4 * AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
-        auto trace_ext = [&]() {
-            c->trace_recast = recast;   // (the closest-hit launch over the continuation rays may re-cast in place, see k_trace_fast)
-            launch_trace_timed<0>(c, timing, 0, s->dev, q[cur].ext, &QCOUNT(q[cur], 1), 0, c->work.p + 0, pb.ext_o, pb.ext_d, pb.hit, nullptr, count);
-            c->trace_recast = false;
-        };
+        HIP_TRY(hipMemsetAsync(q[nxt].counts, 0, AGPT_NQUEUES * AGPT_QSTRIDE * sizeof(uint32_t), main_stream));
+        HIP_TRY(hipMemsetAsync(c->work.p, 0, 4 * AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), main_stream));
+        // the launches' work heads and k_shade's tile heads, zeroed above
+        uint32_t* const heads[4] = {c->work.p, c->work.p + AGPT_FRONTIERS * AGPT_QSTRIDE, c->work.p + 2 * AGPT_FRONTIERS * AGPT_QSTRIDE,
+                                    c->work.p + 3 * AGPT_FRONTIERS * AGPT_QSTRIDE};
+        // (the closest-hit launch over the continuation rays may re-cast in place, see k_trace_fast)
+        const TraceLaunch ext{main_stream, q[cur].ext, &QCOUNT(q[cur], 1), 0, heads[0], pb.ext_o, pb.ext_d, pb.hit, nullptr,
+                              count, small_batch, recast};
+        const TraceLaunch mis{mis_stream, q[cur].mis, &QCOUNT(q[cur], 2), 0, heads[1], pb.mis_o, pb.mis_d,
+                              run.mis_mode ? nullptr : pb.mis_hit, run.mis_mode ? pb.mis_ok : nullptr, count, small_batch, false};
+        const TraceLaunch shadow{shadow_stream, q[cur].shadow, &QCOUNT(q[cur], 3), 0, heads[2], pb.sh_o, pb.sh_d, nullptr, pb.occluded,
+                                 count, small_batch, false};
+        auto trace_ext = [&]() { launch_trace_timed<0>(c, run.timing, 0, s->dev, ext); };
         auto trace_mis = [&]() {
-            if (mis_mode)
-                launch_trace_timed<2>(c, timing, 1, s->dev, q[cur].mis, &QCOUNT(q[cur], 2), 0, c->work.p + AGPT_FRONTIERS * AGPT_QSTRIDE, pb.mis_o,
-                                      pb.mis_d, nullptr, pb.mis_ok, count);
-            else
-                launch_trace_timed<0>(c, timing, 1, s->dev, q[cur].mis, &QCOUNT(q[cur], 2), 0, c->work.p + AGPT_FRONTIERS * AGPT_QSTRIDE, pb.mis_o,
-                                      pb.mis_d, pb.mis_hit, nullptr, count);
+            if (run.mis_mode) launch_trace_timed<2>(c, run.timing, 1, s->dev, mis);
+            else launch_trace_timed<0>(c, run.timing, 1, s->dev, mis);
         };
-        auto trace_shadow = [&]() {
-            launch_trace_timed<1>(c, timing, 2, s->dev, q[cur].shadow, &QCOUNT(q[cur], 3), 0, c->work.p + 2 * AGPT_FRONTIERS * AGPT_QSTRIDE, pb.sh_o,
-                                  pb.sh_d, nullptr, pb.occluded, count);
-        };
+        auto trace_shadow = [&]() { launch_trace_timed<1>(c, run.timing, 2, s->dev, shadow); };
         if (side) {
-            // AGPT_MULTI_STREAM: the three trace launches of an iteration are independent -- MIS and shadow rays on streams of their
-            // own, beside the closest-hit launch (c->stream is what the launch helpers enqueue on; restored whatever happens)
-            struct Restore {
-                agpt_ctx* c;
-                hipStream_t s;
-                ~Restore() { c->stream = s; }
-            } restore{c, c->stream};
-            hipStream_t main_stream = c->stream;
             HIP_TRY(hipEventRecord(c->aux_ev[0], main_stream));
-            HIP_TRY(hipStreamWaitEvent(c->aux_stream[0], c->aux_ev[0], 0));
-            HIP_TRY(hipStreamWaitEvent(c->aux_stream[1], c->aux_ev[0], 0));
-            c->stream = c->aux_stream[0];
+            HIP_TRY(hipStreamWaitEvent(mis_stream, c->aux_ev[0], 0));
+            HIP_TRY(hipStreamWaitEvent(shadow_stream, c->aux_ev[0], 0));
             trace_mis();
-            HIP_TRY(hipEventRecord(c->aux_ev[1], c->stream));
-            c->stream = c->aux_stream[1];
+            HIP_TRY(hipEventRecord(c->aux_ev[1], mis_stream));
             trace_shadow();
-            HIP_TRY(hipEventRecord(c->aux_ev[2], c->stream));
-            c->stream = main_stream;
+            HIP_TRY(hipEventRecord(c->aux_ev[2], shadow_stream));
             trace_ext();
             HIP_TRY(hipStreamWaitEvent(main_stream, c->aux_ev[1], 0));
             HIP_TRY(hipStreamWaitEvent(main_stream, c->aux_ev[2], 0));
@@ -947,46 +981,12 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, co
             trace_mis();
             trace_shadow();
         }
-        uint32_t* const shade_heads = c->work.p + 3 * AGPT_FRONTIERS * AGPT_QSTRIDE;   // k_shade's tile heads, zeroed above
-        if (s->textured) {   // a material of the scene has a texture: the TEXTURED variants (agpt_shade_kernels_textured.hip)
-            if (run.shade_fast)
-                agpt::launch_shade_textured_fast(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt],
-                                                 c->counters.p, shade_heads);
-            else
-                agpt::launch_shade_textured(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt],
-                                            c->counters.p, shade_heads);
-            if (run.shade_fast) agpt::launch_resolve_pending_fast(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
-            else agpt::launch_resolve_pending(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
-        } else if (run.shade_fast) {
-            agpt::launch_shade_fast(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p,
-                                    shade_heads);
-            agpt::launch_resolve_pending_fast(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
-        } else {
-            agpt::launch_shade(c->stream, shade_grid, run.shade_lds_tables, run.shade_env, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p,
-                               shade_heads);
-            // (independent of k_shade: different paths)
-            agpt::launch_resolve_pending(c->stream, c->num_cus * 8, s->dev, rcn, pb, q[cur]);
-        }
+        agpt::launch_shading(main_stream, run.shade, shade_grid, c->num_cus * 8, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p, heads[3]);
         cur = nxt;
         run.iterations++;
         run.launches += 3;
     }
     return AGPT_OK;
-}
-
-static void bind_pool(agpt_ctx* c, PathBuffers& pb, Queues q[2]) {
-    pb.ext_o = c->ext_o.p; pb.ext_d = c->ext_d.p; pb.sh_o = c->sh_o.p; pb.sh_d = c->sh_d.p;
-    pb.mis_o = c->mis_o.p; pb.mis_d = c->mis_d.p; pb.hit = c->hit.p; pb.mis_hit = c->mis_hit.p;
-    pb.occluded = c->occluded.p; pb.mis_ok = c->mis_ok.p; pb.beta4 = c->beta4.p; pb.L4 = c->L4.p; pb.fac4 = c->fac4.p;
-    pb.c1 = c->c1.p; pb.c2 = c->c2.p;
-    for (int i = 0; i < 2; i++) {
-        q[i].active = c->q[i][0].p; q[i].ext = c->q[i][1].p; q[i].mis = c->q[i][2].p; q[i].shadow = c->q[i][3].p;
-        q[i].resolve = c->q[i][4].p;
-        q[i].counts = c->qcounts.p + AGPT_NQUEUES * AGPT_QSTRIDE * i;
-    }
-}
-static bool shade_tables_fit_lds(const DevScene& d) {
-    return agpt::shade_tables_fit_lds(d.n_prims, d.n_materials, d.n_lights) && !getenv("AGPT_SHADE_GLOBAL_TABLES");
 }
 
 static void read_counters(const DevCounters& d, agpt_stats* st) {
@@ -999,6 +999,133 @@ static void read_counters(const DevCounters& d, agpt_stats* st) {
     st->outliers = d.outliers;
     st->samples = d.samples;
     st->answered_rays = d.answered;
+}
+
+// Closes what begin_wavefront opened: the asynchronous errors of the work the call enqueued are reported here.
+static int end_wavefront(agpt_ctx* c) {
+    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(c->take_deferred());
+    return AGPT_OK;
+}
+
+// DevCounters, the run and the events -> agpt_stats, after end_wavefront (waits for the stream; nothing to do without `stats`)
+static int fill_stats(agpt_ctx* c, const WavefrontRun& run, uint64_t samples, agpt_stats* stats) {
+    if (!stats) return AGPT_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::memset(stats, 0, sizeof(*stats));
+    DevCounters dc;
+    HIP_TRY(hipMemcpy(&dc, c->counters.p, sizeof(dc), hipMemcpyDeviceToHost));
+    read_counters(dc, stats);
+#ifdef AGPT_SHADE_CLOCK
+    {
+        const double tot = (double)dc.dbg[55];
+        static const char* names[8] = {"record loads", "resolve pending", "surface", "emission/termination", "BSDF set-up + light sampling",
+                                       "evaluations + ray stores", "final stores", "queue appends + barriers"};
+        std::fprintf(stderr, "[shade clock] wave-cycles %.4g:", tot);
+        for (int k = 0; k < 8; ++k) std::fprintf(stderr, "  %s %.1f%%", names[k], 100. * dc.dbg[56 + k] / tot);
+        std::fprintf(stderr, "\n");
+    }
+#endif
+#ifdef AGPT_TRACE_STATS
+    for (int mode = 0; mode < 3; ++mode) {
+        const unsigned long long* d = dc.dbg + 16 * mode;
+        const double steps = (double)(d[0] + d[1] + d[2]);
+        if (steps == 0) continue;
+        std::fprintf(stderr,
+                     "[trace stats mode %d] steps A/B/C %.3g/%.3g/%.3g (%.1f%%/%.1f%%/%.1f%%)  lanes per step A %.1f B %.1f C %.1f  "
+                     "active lanes per step %.1f  refills %.3g (%.1f lanes each)  prefilter batches %.3g\n", mode,
+                     (double)d[0], (double)d[1], (double)d[2], 100 * d[0] / steps, 100 * d[1] / steps, 100 * d[2] / steps,
+                     d[0] ? (double)d[3] / d[0] : 0., d[1] ? (double)d[4] / d[1] : 0., d[2] ? (double)d[5] / d[2] : 0.,
+                     (double)d[6] / steps, (double)d[7], d[7] ? (double)d[8] / d[7] : 0., (double)d[9]);
+#ifndef AGPT_TRACE_CLOCK
+        std::fprintf(stderr, "[trace stats mode %d] stack pushes %.3g: to depth > 4 %.2f%%  > 6 %.3f%%  > 8 %.4f%%  > 12 %.5f%%\n", mode, (double)d[10],
+                     d[10] ? 100. * d[11] / d[10] : 0., d[10] ? 100. * d[12] / d[10] : 0., d[10] ? 100. * d[13] / d[10] : 0.,
+                     d[10] ? 100. * d[14] / d[10] : 0.);
+#endif
+#ifdef AGPT_TRACE_CLOCK
+        const double tot = (double)dc.dbg[48 + mode];
+        std::fprintf(stderr,
+                     "[trace clock mode %d] wave-cycles %.4g: refill %.1f%%  vote %.1f%%  B %.1f%% (of which load wait %.1f%%)  C %.1f%%  A %.1f%%;"
+                     "  cycles per step: B %.0f (wait %.0f)  C %.0f  A %.0f  vote %.0f; per refill %.0f\n", mode, tot,
+                     100 * d[10] / tot, 100 * d[11] / tot, 100 * d[13] / tot, 100 * d[12] / tot, 100 * d[14] / tot, 100 * d[15] / tot,
+                     d[1] ? (double)d[13] / d[1] : 0., d[1] ? (double)d[12] / d[1] : 0., d[2] ? (double)d[14] / d[2] : 0.,
+                     d[0] ? (double)d[15] / d[0] : 0., (double)d[11] / steps, d[7] ? (double)d[10] / d[7] : 0.);
+#endif
+    }
+#endif
+    stats->samples = samples;
+    stats->iterations = run.iterations;
+    stats->trace_launches = run.launches;
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    stats->total_ms = ms;
+    if (run.timing) {
+        for (size_t i = 0; i + 1 < c->tev_used; i += 2) {
+            float t = 0;
+            HIP_TRY(hipEventElapsedTime(&t, c->tev[i], c->tev[i + 1]));
+            const int kind = c->tev_kind[i / 2];
+            stats->trace_ms += t;
+            if (kind == 0) stats->ext_ms += t;
+            else if (kind == 1) stats->mis_ms += t;
+            else stats->shadow_ms += t;
+        }
+    }
+    return AGPT_OK;
+}
+
+// ---- what the tile-based entry points (agpt_render, agpt_render_adaptive, agpt_render_features) share ----------------------------
+// (`fn` is the entry point that was called: its name opens the message)
+static int check_depth(const char* fn, int max_depth) {
+    if (max_depth < 0 || max_depth > 200) return fail(AGPT_ERR_INVALID, std::string(fn) + ": max_depth must be in 0 .. 200");
+    return AGPT_OK;
+}
+// film and tile of `rp`
+static int check_tile(const char* fn, const agpt_render_params* rp) {
+    if (rp->width <= 0 || rp->height <= 0 || rp->w <= 0 || rp->h <= 0 || rp->x0 < 0 || rp->y0 < 0 || rp->x0 + rp->w > rp->width ||
+        rp->y0 + rp->h > rp->height || rp->accum_pitch < rp->x0 + rp->w)
+        return fail(AGPT_ERR_INVALID, std::string(fn) + ": bad tile / film");
+    return AGPT_OK;
+}
+
+// film rows of the row blocks k with k % world == rank (blocks of `block` rows, the last one of a film may be shorter)
+static int interleave_rows(int H, int block, int world, int rank) {
+    int rows = 0;
+    for (int k = rank, y = k * block; y < H; k += world, y = k * block) rows += std::min(block, H - y);
+    return rows;
+}
+
+// rows of the tile this call renders: rp->h, or with the row interleave on this rank's share of the film (which may be empty)
+static int tile_rows(const char* fn, const agpt_render_params* rp, uint32_t& rows) {
+    rows = (uint32_t)rp->h;
+    if (rp->interleave_block <= 0) return AGPT_OK;
+    if (rp->interleave_world < 1 || rp->interleave_rank < 0 || rp->interleave_rank >= rp->interleave_world || rp->x0 != 0 ||
+        rp->y0 != 0 || rp->w != rp->width || rp->h != rp->height)
+        return fail(AGPT_ERR_INVALID, std::string(fn) + ": row interleave needs the whole film as tile and 0 <= rank < world");
+    rows = (uint32_t)interleave_rows(rp->height, rp->interleave_block, rp->interleave_world, rp->interleave_rank);
+    return AGPT_OK;
+}
+
+// the part of RenderConsts that says where the NP pixels of the tile lie on the film and in the accumulator; the rest is zero
+static RenderConsts tile_consts(const agpt_render_params* rp, uint32_t NP) {
+    RenderConsts rc{};
+    rc.W = rp->width; rc.H = rp->height; rc.x0 = rp->x0; rc.y0 = rp->y0; rc.w = rp->w; rc.h = rp->h;
+    rc.accum_pitch = rp->accum_pitch; rc.accum_row0 = rp->accum_row0; rc.NP = NP;
+    rc.il_block = rp->interleave_block; rc.il_world = rp->interleave_world; rc.il_rank = rp->interleave_rank;
+    return rc;
+}
+
+// paths of a renderer's default batch: up to 128 Mi (27 GB of path state -- MI355X has 288 GB); fewer, larger wavefront launches
+static uint64_t samples_per_batch(const agpt_render_params* rp, uint32_t NP) {
+    return rp->samples_per_batch > 0 ? (uint64_t)rp->samples_per_batch : std::max<uint64_t>(1, (128ull << 20) / NP);
+}
+
+// n rays in ext_o / ext_d -> hit / occluded, one launch outside the wavefront loop (agpt_intersect_device, agpt_render_features)
+static void trace_rays(agpt_ctx* c, const DevScene& sc, uint32_t n, bool any_hit, int count) {
+    const TraceLaunch t{c->stream, nullptr, nullptr, n, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p,
+                        count, (unsigned long long)n < AGPT_SMALL_BATCH, false};
+    if (any_hit) launch_trace<1>(c, sc, t);
+    else launch_trace<0>(c, sc, t);
 }
 
 int agpt_intersect_device(agpt_scene* s, const agpt_ray* d_rays, int n, agpt_hit* d_out, int any_hit, agpt_stats* stats) {
@@ -1017,13 +1144,7 @@ int agpt_intersect_device(agpt_scene* s, const agpt_ray* d_rays, int n, agpt_hit
     // stats requested -> the instrumented reference-order kernel (work counters); AGPT_INTERSECT_TIMING=1 (developer knob)
     // keeps the production kernel so that stats->trace_ms times it
     const int instrumented = (stats != nullptr && !getenv("AGPT_INTERSECT_TIMING")) ? 1 : 0;
-    c->trace_small_batch = (unsigned long long)n < AGPT_SMALL_BATCH;
-    if (any_hit)
-        launch_trace<1>(c, s->dev, nullptr, nullptr, (uint32_t)n, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p,
-                        instrumented);
-    else
-        launch_trace<0>(c, s->dev, nullptr, nullptr, (uint32_t)n, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p,
-                        instrumented);
+    trace_rays(c, s->dev, (uint32_t)n, any_hit != 0, instrumented);
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     hipLaunchKernelGGL(k_export_hits, dim3(blocks), dim3(AGPT_BLOCK), 0, c->stream, s->dev, c->hit.p, c->occluded.p, n, any_hit,
                        d_out);
@@ -1050,8 +1171,8 @@ int agpt_intersect_batch(agpt_scene* s, const agpt_ray* rays, int n, agpt_hit* o
     if (n == 0) return AGPT_OK;
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    TempBuf<agpt_ray> d_rays;
-    TempBuf<agpt_hit> d_out;
+    DevBuf<agpt_ray> d_rays;
+    DevBuf<agpt_hit> d_out;
     if (d_rays.alloc((size_t)n) != hipSuccess || d_out.alloc((size_t)n) != hipSuccess)
         return fail(AGPT_ERR_NOMEM, "agpt_intersect_batch: out of device memory");
     HIP_TRY(hipMemcpyAsync(d_rays.p, rays, (size_t)n * sizeof(agpt_ray), hipMemcpyHostToDevice, c->stream));
@@ -1118,149 +1239,38 @@ int agpt_dbg_li_batch(agpt_scene* s, const agpt_ray* rays, int n, float* radianc
 int agpt_render(agpt_scene* s, const agpt_render_params* rp, float* accum_dev, agpt_stats* stats) {
     if (!s || !rp || !accum_dev) return fail(AGPT_ERR_INVALID, "agpt_render: NULL argument");
     if (!s->committed || !s->has_camera) return fail(AGPT_ERR_INVALID, "agpt_render: scene not committed or camera not set");
-    if (rp->width <= 0 || rp->height <= 0 || rp->w <= 0 || rp->h <= 0 || rp->x0 < 0 || rp->y0 < 0 ||
-        rp->x0 + rp->w > rp->width || rp->y0 + rp->h > rp->height || rp->spp_count < 0 || rp->max_depth < 0 ||
-        rp->max_depth > 200 || rp->accum_pitch < rp->x0 + rp->w)
-        return fail(AGPT_ERR_INVALID, "agpt_render: bad tile / film / sample range");
+    int rc;
+    if ((rc = check_tile("agpt_render", rp)) || (rc = check_depth("agpt_render", rp->max_depth))) return rc;
+    if (rp->spp_count < 0) return fail(AGPT_ERR_INVALID, "agpt_render: bad sample range");
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t rows = (uint32_t)rp->h;
-    if (rp->interleave_block > 0) {
-        if (rp->interleave_world < 1 || rp->interleave_rank < 0 || rp->interleave_rank >= rp->interleave_world || rp->x0 != 0 ||
-            rp->y0 != 0 || rp->w != rp->width || rp->h != rp->height)
-            return fail(AGPT_ERR_INVALID, "agpt_render: row interleave needs the whole film as tile and 0 <= rank < world");
-        rows = 0;
-        for (int k = rp->interleave_rank, y = k * rp->interleave_block; y < rp->height;
-             k += rp->interleave_world, y = k * rp->interleave_block)
-            rows += (uint32_t)std::min(rp->interleave_block, rp->height - y);
-        if (rows == 0) return AGPT_OK;
-    }
+    uint32_t rows;
+    if ((rc = tile_rows("agpt_render", rp, rows))) return rc;
+    if (rows == 0) return AGPT_OK;   // (a rank that owns no rows)
     const uint32_t NP = (uint32_t)rp->w * rows;
-    // default batch: up to 128 Mi paths (27 GB of path state -- MI355X has 288 GB); fewer, larger wavefront launches
-    int S = rp->samples_per_batch > 0 ? rp->samples_per_batch : (int)std::max<uint64_t>(1, (128ull << 20) / NP);
-    S = std::min(S, std::max(1, rp->spp_count));
-    if ((uint64_t)NP * (uint64_t)S > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, "agpt_render: batch too large");
-    // The batch is a performance choice, not a semantic one (the image is batch-split invariant): when the pool has to
-    // grow, keep it within the memory that is actually free (other ranks or applications may share the GPU), and halve
-    // the batch if an allocation still fails.
-    if ((size_t)NP * (size_t)S > c->pool_paths) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t per_path = (size_t)AGPT_BYTES_PER_PATH + candidate_bytes_per_path(s->dev.n_prims);
-            const size_t avail = free_b + c->pool_paths * per_path;
-            const size_t fit = (size_t)((double)avail * 0.9) / per_path;
-            while (S > 1 && (size_t)NP * (size_t)S > fit) S = (S + 1) / 2;
-        }
-    }
-    int rc = ensure_pool(c, (size_t)NP * S, s->dev.n_prims);
-    while (rc == AGPT_ERR_NOMEM && S > 1) {
-        release_pool(c);
-        S = (S + 1) / 2;
-        rc = ensure_pool(c, (size_t)NP * S, s->dev.n_prims);
-    }
-    if (rc) return rc;
+    uint64_t batch = std::min<uint64_t>(samples_per_batch(rp, NP), (uint64_t)std::max(1, rp->spp_count));
+    if ((uint64_t)NP * batch > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, "agpt_render: batch too large");
+    if ((rc = fit_pool(c, s, NP, batch))) return rc;
+    const int S = (int)batch;
     s->dev.cam = s->cam;
 
-    PathBuffers pb;
-    Queues q[2];
-    bind_pool(c, pb, q);
     WavefrontRun run;
-    run.count = rp->enable_counters == 2 ? 2 : (rp->enable_counters != 0 ? 1 : 0);
-    run.mis_mode = use_fast_trace(c, s->dev, run.count) && !c->mis_closest;
-    run.timing = rp->enable_timing != 0 && stats != nullptr;
-    run.shade_lds_tables = shade_tables_fit_lds(s->dev);
-    run.shade_env = !s->envs.empty();   // an InfiniteAreaLight is present
-    run.shade_fast = s->shading_arith == AGPT_SHADING_FAST;
-    const bool timing = run.timing;
-    c->tev_used = 0;
-    c->tev_kind.clear();
-    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-
+    if ((rc = begin_wavefront(c, s, rp->enable_counters, rp->enable_timing != 0 && stats != nullptr, run))) return rc;
+    RenderConsts rcn = tile_consts(rp, NP);
+    rcn.seed_base = rp->seed_base;
+    set_wavefront_consts(rcn, run, rp->max_depth, rp->trace_all_rays != 0);
     for (int s0 = rp->spp_begin; s0 < rp->spp_begin + rp->spp_count; s0 += S) {
-        RenderConsts rcn;
-        rcn.W = rp->width; rcn.H = rp->height; rcn.x0 = rp->x0; rcn.y0 = rp->y0; rcn.w = rp->w; rcn.h = rp->h;
-        rcn.s0 = s0; rcn.S = std::min(S, rp->spp_begin + rp->spp_count - s0);
-        rcn.seed_base = rp->seed_base; rcn.max_depth = rp->max_depth;
-        rcn.accum_pitch = rp->accum_pitch; rcn.accum_row0 = rp->accum_row0; rcn.NP = NP;
-        rcn.mis_mode = run.mis_mode ? 1 : 0;
-        rcn.answer_rays = (run.mis_mode && !rp->trace_all_rays) ? 1 : 0;
-        rcn.il_block = rp->interleave_block; rcn.il_world = rp->interleave_world; rcn.il_rank = rp->interleave_rank;
+        rcn.s0 = s0;
+        rcn.S = std::min(S, rp->spp_begin + rp->spp_count - s0);
         const uint32_t total = NP * (uint32_t)rcn.S;
-        hipLaunchKernelGGL(k_generate, dim3((total + AGPT_BLOCK - 1) / AGPT_BLOCK), dim3(AGPT_BLOCK), 0, c->stream, s->dev, rcn, pb,
-                           q[0]);
-        {
-            const int rc_run = run_wavefront(c, s, rcn, pb, q, run);
-            if (rc_run) return rc_run;
-        }
-        hipLaunchKernelGGL(k_accumulate, dim3((NP + AGPT_BLOCK - 1) / AGPT_BLOCK), dim3(AGPT_BLOCK), 0, c->stream, rcn, pb,
+        hipLaunchKernelGGL(k_generate, dim3((total + AGPT_BLOCK - 1) / AGPT_BLOCK), dim3(AGPT_BLOCK), 0, c->stream, s->dev, rcn, run.pb,
+                           run.q[0]);
+        if ((rc = run_wavefront(c, s, rcn, run))) return rc;
+        hipLaunchKernelGGL(k_accumulate, dim3((NP + AGPT_BLOCK - 1) / AGPT_BLOCK), dim3(AGPT_BLOCK), 0, c->stream, rcn, run.pb,
                            (float4*)accum_dev, c->counters.p);
     }
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(c->take_deferred());
-    if (stats) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::memset(stats, 0, sizeof(*stats));
-        DevCounters dc;
-        HIP_TRY(hipMemcpy(&dc, c->counters.p, sizeof(dc), hipMemcpyDeviceToHost));
-        read_counters(dc, stats);
-#ifdef AGPT_SHADE_CLOCK
-        {
-            const double tot = (double)dc.dbg[55];
-            static const char* names[8] = {"record loads", "resolve pending", "surface", "emission/termination", "BSDF set-up + light sampling",
-                                           "evaluations + ray stores", "final stores", "queue appends + barriers"};
-            std::fprintf(stderr, "[shade clock] wave-cycles %.4g:", tot);
-            for (int k = 0; k < 8; ++k) std::fprintf(stderr, "  %s %.1f%%", names[k], 100. * dc.dbg[56 + k] / tot);
-            std::fprintf(stderr, "\n");
-        }
-#endif
-#ifdef AGPT_TRACE_STATS
-        for (int mode = 0; mode < 3; ++mode) {
-            const unsigned long long* d = dc.dbg + 16 * mode;
-            const double steps = (double)(d[0] + d[1] + d[2]);
-            if (steps == 0) continue;
-            std::fprintf(stderr,
-                         "[trace stats mode %d] steps A/B/C %.3g/%.3g/%.3g (%.1f%%/%.1f%%/%.1f%%)  lanes per step A %.1f B %.1f C %.1f  "
-                         "active lanes per step %.1f  refills %.3g (%.1f lanes each)  prefilter batches %.3g\n", mode,
-                         (double)d[0], (double)d[1], (double)d[2], 100 * d[0] / steps, 100 * d[1] / steps, 100 * d[2] / steps,
-                         d[0] ? (double)d[3] / d[0] : 0., d[1] ? (double)d[4] / d[1] : 0., d[2] ? (double)d[5] / d[2] : 0.,
-                         (double)d[6] / steps, (double)d[7], d[7] ? (double)d[8] / d[7] : 0., (double)d[9]);
-#ifndef AGPT_TRACE_CLOCK
-            std::fprintf(stderr, "[trace stats mode %d] stack pushes %.3g: to depth > 4 %.2f%%  > 6 %.3f%%  > 8 %.4f%%  > 12 %.5f%%\n", mode, (double)d[10],
-                         d[10] ? 100. * d[11] / d[10] : 0., d[10] ? 100. * d[12] / d[10] : 0., d[10] ? 100. * d[13] / d[10] : 0.,
-                         d[10] ? 100. * d[14] / d[10] : 0.);
-#endif
-#ifdef AGPT_TRACE_CLOCK
-            const double tot = (double)dc.dbg[48 + mode];
-            std::fprintf(stderr,
-                         "[trace clock mode %d] wave-cycles %.4g: refill %.1f%%  vote %.1f%%  B %.1f%% (of which load wait %.1f%%)  C %.1f%%  A %.1f%%;"
-                         "  cycles per step: B %.0f (wait %.0f)  C %.0f  A %.0f  vote %.0f; per refill %.0f\n", mode, tot,
-                         100 * d[10] / tot, 100 * d[11] / tot, 100 * d[13] / tot, 100 * d[12] / tot, 100 * d[14] / tot, 100 * d[15] / tot,
-                         d[1] ? (double)d[13] / d[1] : 0., d[1] ? (double)d[12] / d[1] : 0., d[2] ? (double)d[14] / d[2] : 0.,
-                         d[0] ? (double)d[15] / d[0] : 0., (double)d[11] / steps, d[7] ? (double)d[10] / d[7] : 0.);
-#endif
-        }
-#endif
-        stats->samples = (uint64_t)NP * (uint64_t)rp->spp_count;
-        stats->iterations = run.iterations;
-        stats->trace_launches = run.launches;
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        stats->total_ms = ms;
-        if (timing) {
-            for (size_t i = 0; i + 1 < c->tev_used; i += 2) {
-                float t = 0;
-                HIP_TRY(hipEventElapsedTime(&t, c->tev[i], c->tev[i + 1]));
-                int kind = c->tev_kind[i / 2];
-                stats->trace_ms += t;
-                if (kind == 0) stats->ext_ms += t;
-                else if (kind == 1) stats->mis_ms += t;
-                else stats->shadow_ms += t;
-            }
-        }
-    }
-    return AGPT_OK;
+    if ((rc = end_wavefront(c))) return rc;
+    return fill_stats(c, run, (uint64_t)NP * (uint64_t)rp->spp_count, stats);
 }
 
 // Rounds of: the decision (k_adaptive_select + k_adaptive_compact over the tile, one read-back of the active count), then wavefront
@@ -1269,10 +1279,8 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
                          float* moment2_dev, agpt_stats* stats, agpt_adaptive_stats* astats) {
     if (!s || !rp || !ap || !accum_dev || !moment2_dev) return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: NULL argument");
     if (!s->committed || !s->has_camera) return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: scene not committed or camera not set");
-    if (rp->width <= 0 || rp->height <= 0 || rp->w <= 0 || rp->h <= 0 || rp->x0 < 0 || rp->y0 < 0 ||
-        rp->x0 + rp->w > rp->width || rp->y0 + rp->h > rp->height || rp->max_depth < 0 || rp->max_depth > 200 ||
-        rp->accum_pitch < rp->x0 + rp->w)
-        return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: bad tile / film");
+    int rc;
+    if ((rc = check_tile("agpt_render_adaptive", rp)) || (rc = check_depth("agpt_render_adaptive", rp->max_depth))) return rc;
     if (rp->spp_begin != 0 || rp->spp_count != 0)
         return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: spp_begin and spp_count must be 0 (the counts are in accum.w)");
     const int step = ap->step_spp, min_spp = ap->min_spp, max_spp = ap->max_spp;
@@ -1283,67 +1291,26 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
     if (astats) std::memset(astats, 0, sizeof(*astats));
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t rows = (uint32_t)rp->h;
-    if (rp->interleave_block > 0) {
-        if (rp->interleave_world < 1 || rp->interleave_rank < 0 || rp->interleave_rank >= rp->interleave_world || rp->x0 != 0 ||
-            rp->y0 != 0 || rp->w != rp->width || rp->h != rp->height)
-            return fail(AGPT_ERR_INVALID, "agpt_render_adaptive: row interleave needs the whole film as tile and 0 <= rank < world");
-        rows = 0;
-        for (int k = rp->interleave_rank, y = k * rp->interleave_block; y < rp->height;
-             k += rp->interleave_world, y = k * rp->interleave_block)
-            rows += (uint32_t)std::min(rp->interleave_block, rp->height - y);
-        if (rows == 0) return AGPT_OK;
-    }
+    uint32_t rows;
+    if ((rc = tile_rows("agpt_render_adaptive", rp, rows))) return rc;
+    if (rows == 0) return AGPT_OK;
     const uint32_t NP = (uint32_t)rp->w * rows;
-    // paths of one wavefront batch: at most w * rows * samples_per_batch (default: agpt_render's 128 Mi paths), and no more than the
-    // largest batch a call can run (the whole tile at max(step_spp, min_spp) samples); then kept within free memory as agpt_render
-    const uint64_t spb = rp->samples_per_batch > 0 ? (uint64_t)rp->samples_per_batch : std::max<uint64_t>(1, (128ull << 20) / NP);
-    uint64_t cap = std::min<uint64_t>((uint64_t)NP * spb, (uint64_t)NP * (uint64_t)std::max(step, min_spp));
+    // paths of one wavefront batch: at most w * rows * samples_per_batch (agpt_render's default), and no more than the largest batch a
+    // call can run (the whole tile at max(step_spp, min_spp) samples); then kept within free memory as agpt_render
+    uint64_t cap = std::min<uint64_t>((uint64_t)NP * samples_per_batch(rp, NP), (uint64_t)NP * (uint64_t)std::max(step, min_spp));
     if (cap > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, "agpt_render_adaptive: batch too large");
-    if (cap > c->pool_paths) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t per_path = (size_t)AGPT_BYTES_PER_PATH + candidate_bytes_per_path(s->dev.n_prims);
-            const size_t fit = (size_t)((double)(free_b + c->pool_paths * per_path) * 0.9) / per_path;
-            while (cap > 1 && cap > fit) cap = (cap + 1) / 2;
-        }
-    }
-    int rc = ensure_pool(c, (size_t)cap, s->dev.n_prims);
-    while (rc == AGPT_ERR_NOMEM && cap > 1) {
-        release_pool(c);
-        cap = (cap + 1) / 2;
-        rc = ensure_pool(c, (size_t)cap, s->dev.n_prims);
-    }
-    if (rc) return rc;
+    if ((rc = fit_pool(c, s, 1, cap))) return rc;
     const uint32_t n_blocks = (NP + AGPT_ADAPT_BLOCK_PIXELS - 1) / AGPT_ADAPT_BLOCK_PIXELS;
     if ((rc = c->adapt_masks.ensure((size_t)n_blocks * AGPT_BLOCK)) || (rc = c->adapt_blocks.ensure(n_blocks)) ||
         (rc = c->adapt_list.ensure(NP)) || (rc = c->adapt_words.ensure(AGPT_AW_COUNT)))
         return rc;
     s->dev.cam = s->cam;
 
-    PathBuffers pb;
-    Queues q[2];
-    bind_pool(c, pb, q);
     WavefrontRun run;
-    run.count = rp->enable_counters == 2 ? 2 : (rp->enable_counters != 0 ? 1 : 0);
-    run.mis_mode = use_fast_trace(c, s->dev, run.count) && !c->mis_closest;
-    run.timing = rp->enable_timing != 0 && stats != nullptr;
-    run.shade_lds_tables = shade_tables_fit_lds(s->dev);
-    run.shade_env = !s->envs.empty();
-    run.shade_fast = s->shading_arith == AGPT_SHADING_FAST;
-    c->tev_used = 0;
-    c->tev_kind.clear();
-    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
-
-    RenderConsts base;
-    base.W = rp->width; base.H = rp->height; base.x0 = rp->x0; base.y0 = rp->y0; base.w = rp->w; base.h = rp->h;
-    base.s0 = 0; base.S = 0;
-    base.seed_base = rp->seed_base; base.max_depth = rp->max_depth;
-    base.accum_pitch = rp->accum_pitch; base.accum_row0 = rp->accum_row0; base.NP = NP;
-    base.mis_mode = run.mis_mode ? 1 : 0;
-    base.answer_rays = (run.mis_mode && !rp->trace_all_rays) ? 1 : 0;
-    base.il_block = rp->interleave_block; base.il_world = rp->interleave_world; base.il_rank = rp->interleave_rank;
+    if ((rc = begin_wavefront(c, s, rp->enable_counters, rp->enable_timing != 0 && stats != nullptr, run))) return rc;
+    RenderConsts base = tile_consts(rp, NP);
+    base.seed_base = rp->seed_base;
+    set_wavefront_consts(base, run, rp->max_depth, rp->trace_all_rays != 0);
     AdaptiveConsts ac;
     ac.min_spp = min_spp; ac.max_spp = max_spp; ac.step_spp = step; ac.rel_error = ap->rel_error; ac.abs_floor = ap->abs_floor;
     float4* const accum = (float4*)accum_dev;
@@ -1360,12 +1327,11 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
             rcg.S = (int32_t)std::min(S, spp - done);
             for (uint32_t a0 = 0; a0 < na; a0 += per_chunk) {
                 const uint32_t nc = std::min(per_chunk, na - a0);
-                agpt::launch_generate_list(c->stream, s->dev, rcg, list, a0, nc, accum, pb, q[0]);
+                agpt::launch_generate_list(c->stream, s->dev, rcg, list, a0, nc, accum, run.pb, run.q[0]);
                 RenderConsts rcw = rcg;
                 rcw.NP = nc;   // (run_wavefront reads NP * S only to pick the small-batch trace kernels: the batch's real path count)
-                const int rc_run = run_wavefront(c, s, rcw, pb, q, run);
-                if (rc_run) return rc_run;
-                agpt::launch_accumulate_list(c->stream, rcg, list, a0, nc, pb, accum, moment2_dev, c->counters.p);
+                if (const int rc_run = run_wavefront(c, s, rcw, run)) return rc_run;
+                agpt::launch_accumulate_list(c->stream, rcg, list, a0, nc, run.pb, accum, moment2_dev, c->counters.p);
             }
         }
         samples += (uint64_t)na * spp;
@@ -1402,40 +1368,14 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
         if (rc_add) return rc_add;
         active_last = na;
     }
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(c->take_deferred());
+    if ((rc = end_wavefront(c))) return rc;
     if (astats) {
         astats->rounds = rounds;
         astats->active_last = (int32_t)active_last;
         astats->samples = samples;
         astats->pixels_stopped = stopped;
     }
-    if (stats) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::memset(stats, 0, sizeof(*stats));
-        DevCounters dc;
-        HIP_TRY(hipMemcpy(&dc, c->counters.p, sizeof(dc), hipMemcpyDeviceToHost));
-        read_counters(dc, stats);
-        stats->samples = samples;
-        stats->iterations = run.iterations;
-        stats->trace_launches = run.launches;
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        stats->total_ms = ms;
-        if (run.timing) {
-            for (size_t i = 0; i + 1 < c->tev_used; i += 2) {
-                float t = 0;
-                HIP_TRY(hipEventElapsedTime(&t, c->tev[i], c->tev[i + 1]));
-                const int kind = c->tev_kind[i / 2];
-                stats->trace_ms += t;
-                if (kind == 0) stats->ext_ms += t;
-                else if (kind == 1) stats->mis_ms += t;
-                else stats->shadow_ms += t;
-            }
-        }
-    }
-    return AGPT_OK;
+    return fill_stats(c, run, samples, stats);
 }
 
 // One closest-hit query per tile pixel through the pixel centre (k_feature_rays -> the trace launch of agpt_intersect_device), then
@@ -1448,26 +1388,21 @@ int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* alb
         return fail(AGPT_ERR_INVALID, "agpt_render_features: the interleave fields must be 0");
     if (!s || !albedo_dev || !normal_depth_dev) return fail(AGPT_ERR_INVALID, "agpt_render_features: NULL argument");
     if (!s->committed || !s->has_camera) return fail(AGPT_ERR_INVALID, "agpt_render_features: scene not committed or camera not set");
-    if (rp->width <= 0 || rp->height <= 0 || rp->w <= 0 || rp->h <= 0 || rp->x0 < 0 || rp->y0 < 0 ||
-        rp->x0 + rp->w > rp->width || rp->y0 + rp->h > rp->height || rp->accum_pitch < rp->x0 + rp->w)
-        return fail(AGPT_ERR_INVALID, "agpt_render_features: bad tile / film");
+    int rc;
+    if ((rc = check_tile("agpt_render_features", rp))) return rc;
     if (albedo_dev == normal_depth_dev) return fail(AGPT_ERR_INVALID, "agpt_render_features: the two outputs are one buffer");
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint64_t np64 = (uint64_t)rp->w * (uint64_t)rp->h;
     if (np64 > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, "agpt_render_features: tile too large");
     const uint32_t NP = (uint32_t)np64;
-    int rc = ensure_pool(c, (size_t)NP, s->dev.n_prims);
-    if (rc) return rc;
+    if ((rc = ensure_pool(c, (size_t)NP, s->dev.n_prims))) return rc;
     s->dev.cam = s->cam;
-    RenderConsts rcn{};
-    rcn.W = rp->width; rcn.H = rp->height; rcn.x0 = rp->x0; rcn.y0 = rp->y0; rcn.w = rp->w; rcn.h = rp->h;
-    rcn.accum_pitch = rp->accum_pitch; rcn.accum_row0 = rp->accum_row0; rcn.NP = NP;
+    const RenderConsts rcn = tile_consts(rp, NP);   // (the interleave fields are 0)
     HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
     HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
     agpt::launch_feature_rays(c->stream, s->dev, rcn, c->ext_o.p, c->ext_d.p);
-    c->trace_small_batch = (unsigned long long)NP < AGPT_SMALL_BATCH;
-    launch_trace<0>(c, s->dev, nullptr, nullptr, NP, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p, 0);
+    trace_rays(c, s->dev, NP, false, 0);
     agpt::launch_features(c->stream, s->dev, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
                           (float4*)normal_depth_dev);
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1521,62 +1456,37 @@ int agpt_li_batch(agpt_scene* s, const agpt_ray* rays, const uint32_t* rng_state
     if (n == 0) return AGPT_OK;
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    TempBuf<agpt_ray> d_rays;
-    TempBuf<uint32_t> d_rng;
-    TempBuf<float> d_out;
+    DevBuf<agpt_ray> d_rays;
+    DevBuf<uint32_t> d_rng;
+    DevBuf<float> d_out;
     if (d_rays.alloc((size_t)n) != hipSuccess || d_rng.alloc((size_t)n) != hipSuccess || d_out.alloc(3 * (size_t)n) != hipSuccess)
         return fail(AGPT_ERR_NOMEM, "agpt_li_batch: out of device memory");
     HIP_TRY(hipMemcpyAsync(d_rays.p, rays, (size_t)n * sizeof(agpt_ray), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_rng.p, rng_states, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     int rc = ensure_pool(c, (size_t)n, s->dev.n_prims);
     if (rc) return rc;
-    PathBuffers pb;
-    Queues q[2];
-    bind_pool(c, pb, q);
+    // counters off, no timing; every answerable ray query is answered (no trace_all_rays here); NP = S = 0 in the constants, so the
+    // trace launches are the small-batch ones whatever n is
     WavefrontRun run;
-    run.count = 0;
-    run.mis_mode = use_fast_trace(c, s->dev, 0) && !c->mis_closest;
-    run.timing = false;
-    run.shade_lds_tables = shade_tables_fit_lds(s->dev);
-    run.shade_env = !s->envs.empty();
-    run.shade_fast = s->shading_arith == AGPT_SHADING_FAST;
+    if ((rc = begin_wavefront(c, s, 0, false, run))) return rc;
     RenderConsts rcn{};
-    rcn.max_depth = max_depth;
-    rcn.mis_mode = run.mis_mode ? 1 : 0;
-    rcn.answer_rays = run.mis_mode ? 1 : 0;
-    c->tev_used = 0;
-    c->tev_kind.clear();
-    HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    set_wavefront_consts(rcn, run, max_depth, false);
     const dim3 grid((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)), block(AGPT_BLOCK);
-    hipLaunchKernelGGL(k_generate_li, grid, block, 0, c->stream, (const agpt_ray*)d_rays.p, (const uint32_t*)d_rng.p, (uint32_t)n, pb, q[0], max_depth);
-    rc = run_wavefront(c, s, rcn, pb, q, run);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_export_li, grid, block, 0, c->stream, pb, (uint32_t)n, d_out.p, rng_states_out ? d_rng.p : (uint32_t*)nullptr);
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(c->take_deferred());
+    hipLaunchKernelGGL(k_generate_li, grid, block, 0, c->stream, (const agpt_ray*)d_rays.p, (const uint32_t*)d_rng.p, (uint32_t)n, run.pb,
+                       run.q[0], max_depth);
+    if ((rc = run_wavefront(c, s, rcn, run))) return rc;
+    hipLaunchKernelGGL(k_export_li, grid, block, 0, c->stream, run.pb, (uint32_t)n, d_out.p, rng_states_out ? d_rng.p : (uint32_t*)nullptr);
+    if ((rc = end_wavefront(c))) return rc;
     HIP_TRY(hipMemcpyAsync(radiance3_out, d_out.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (rng_states_out) HIP_TRY(hipMemcpyAsync(rng_states_out, d_rng.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (stats) {
-        DevCounters dc;
-        HIP_TRY(hipMemcpy(&dc, c->counters.p, sizeof(dc), hipMemcpyDeviceToHost));
-        read_counters(dc, stats);
-        stats->samples = (uint64_t)n;
-        stats->iterations = run.iterations;
-        stats->trace_launches = run.launches;
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-        stats->total_ms = ms;
-    }
-    return AGPT_OK;
+    return fill_stats(c, run, (uint64_t)n, stats);
 }
 
 int agpt_resolve(agpt_ctx* c, const float* accum_dev, int n_pixels, int samples, uint32_t* out_rgb) {
     if (!c || !accum_dev || !out_rgb || n_pixels <= 0 || samples <= 0) return fail(AGPT_ERR_INVALID, "agpt_resolve: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    TempBuf<uint32_t> d;
+    DevBuf<uint32_t> d;
     HIP_TRY(d.alloc((size_t)n_pixels));
     hipLaunchKernelGGL(k_resolve, dim3((n_pixels + 255) / 256), dim3(256), 0, c->stream, (const float4*)accum_dev, n_pixels, samples, d.p);
     HIP_TRY(hipGetLastError());
@@ -1588,7 +1498,7 @@ int agpt_resolve(agpt_ctx* c, const float* accum_dev, int n_pixels, int samples,
 int agpt_resolve_counts(agpt_ctx* c, const float* accum_dev, int n_pixels, uint32_t* out_rgb) {
     if (!c || !accum_dev || !out_rgb || n_pixels <= 0) return fail(AGPT_ERR_INVALID, "agpt_resolve_counts: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    TempBuf<uint32_t> d;
+    DevBuf<uint32_t> d;
     HIP_TRY(d.alloc((size_t)n_pixels));
     agpt::launch_resolve_counts(c->stream, (const float4*)accum_dev, n_pixels, d.p);
     HIP_TRY(hipGetLastError());
@@ -1603,7 +1513,7 @@ int agpt_kat_bsdf_eval(agpt_scene* s, int material, int n, const float* wo3, con
         return fail(AGPT_ERR_INVALID, "agpt_kat_bsdf_eval: bad argument");
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    TempBuf<float> d_wo, d_wi, d_f, d_p;
+    DevBuf<float> d_wo, d_wi, d_f, d_p;
     HIP_TRY(d_wo.alloc(3 * (size_t)n));
     HIP_TRY(d_wi.alloc(3 * (size_t)n));
     HIP_TRY(d_f.alloc(3 * (size_t)n));
@@ -1628,8 +1538,8 @@ int agpt_kat_bsdf_sample(agpt_scene* s, int material, int n, const float* wo3, c
         return fail(AGPT_ERR_INVALID, "agpt_kat_bsdf_sample: bad argument");
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    TempBuf<float> d_wo, d_u, d_wi, d_f, d_p;
-    TempBuf<int32_t> d_s;
+    DevBuf<float> d_wo, d_u, d_wi, d_f, d_p;
+    DevBuf<int32_t> d_s;
     HIP_TRY(d_wo.alloc(3 * (size_t)n));
     HIP_TRY(d_u.alloc(2 * (size_t)n));
     HIP_TRY(d_wi.alloc(3 * (size_t)n));
@@ -1656,8 +1566,8 @@ int agpt_kat_rng(agpt_ctx* c, uint32_t pixel, uint32_t wh, uint32_t sample, uint
                  uint32_t* seed_out) {
     if (!c || n <= 0 || !out || !seed_out) return fail(AGPT_ERR_INVALID, "agpt_kat_rng: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    TempBuf<float> d_o;
-    TempBuf<uint32_t> d_s;
+    DevBuf<float> d_o;
+    DevBuf<uint32_t> d_s;
     HIP_TRY(d_o.alloc((size_t)n));
     HIP_TRY(d_s.alloc(1));
     hipLaunchKernelGGL(k_kat_rng, dim3(1), dim3(64), 0, c->stream, pixel, wh, sample, seed_base, n, d_o.p, d_s.p);
@@ -1678,7 +1588,7 @@ int agpt_kat_distribution1d(agpt_ctx* c, const float* func, int n, const float* 
     if (cdf_out) memcpy(cdf_out, cdf.data(), 4 * cdf.size());
     if (func_int_out) *func_int_out = func_int;
     if (k == 0) return AGPT_OK;
-    TempBuf<float> d_f, d_c, d_u, d_x, d_p;
+    DevBuf<float> d_f, d_c, d_u, d_x, d_p;
     HIP_TRY(d_f.alloc((size_t)n));
     HIP_TRY(d_c.alloc((size_t)n + 1));
     HIP_TRY(d_u.alloc((size_t)k));
@@ -1771,12 +1681,6 @@ __global__ void k_deinterleave(const float4* __restrict__ compact, float4* __res
     full[(size_t)(H - 1 - y) * (size_t)W + (size_t)x] = compact[i];
 }
 
-int rows_of_rank(int H, int block, int world, int rank) {
-    int rows = 0;
-    for (int k = rank, y = k * block; y < H; k += world, y = k * block) rows += std::min(block, H - y);
-    return rows;
-}
-
 }  // namespace
 
 struct agpt_comm {
@@ -1823,7 +1727,6 @@ void agpt_comm_destroy(agpt_comm* m) {
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
     if (m->comm) (void)rccl()->CommDestroy(m->comm);
-    m->staging.release();
     delete m;
 }
 
@@ -1832,7 +1735,7 @@ int agpt_deinterleave_tiles(agpt_ctx* c, const float* compact_dev, int width, in
     if (!c || !compact_dev || !full_accum_dev || width <= 0 || height <= 0 || block_rows <= 0 || world < 1 || rank < 0 || rank >= world)
         return fail(AGPT_ERR_INVALID, "agpt_deinterleave_tiles: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    const int rows = rows_of_rank(height, block_rows, world, rank);
+    const int rows = interleave_rows(height, block_rows, world, rank);
     if (!rows) return AGPT_OK;
     const size_t n = (size_t)rows * (size_t)width;
     hipLaunchKernelGGL(k_deinterleave, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)compact_dev,
@@ -1848,7 +1751,7 @@ int agpt_gather_tiles(agpt_comm* m, const float* local_accum_dev, int width, int
     HIP_TRY(hipSetDevice(c->device));
     const int world = m->world;
     int max_rows = 0;
-    for (int r = 0; r < world; r++) max_rows = std::max(max_rows, rows_of_rank(height, block_rows, world, r));
+    for (int r = 0; r < world; r++) max_rows = std::max(max_rows, interleave_rows(height, block_rows, world, r));
     const size_t slot = (size_t)max_rows * (size_t)width;   // float4 per rank buffer
     if (world > 1) {
         RcclApi* R = rccl();
@@ -1861,14 +1764,14 @@ int agpt_gather_tiles(agpt_comm* m, const float* local_accum_dev, int width, int
             e = R->GroupStart();
             if (e == ncclSuccess) {
                 for (int r = 1; r < world && e == ncclSuccess; r++) {
-                    const size_t n = (size_t)rows_of_rank(height, block_rows, world, r) * (size_t)width * 4;
+                    const size_t n = (size_t)interleave_rows(height, block_rows, world, r) * (size_t)width * 4;
                     if (n) e = R->Recv(m->staging.p + slot * (size_t)(r - 1), n, ncclFloat, r, m->comm, c->stream);
                 }
                 const ncclResult_t e_end = R->GroupEnd();
                 if (e == ncclSuccess) e = e_end;
             }
         } else {
-            const size_t n = (size_t)rows_of_rank(height, block_rows, world, m->rank) * (size_t)width * 4;
+            const size_t n = (size_t)interleave_rows(height, block_rows, world, m->rank) * (size_t)width * 4;
             e = R->GroupStart();
             if (e == ncclSuccess) {
                 if (n) e = R->Send(local_accum_dev, n, ncclFloat, 0, m->comm, c->stream);

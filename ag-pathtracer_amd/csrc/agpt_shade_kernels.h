@@ -636,3 +636,34 @@ AGPT_SHADE_KNAME(k_resolve_pending)(DevScene sc, RenderConsts rc, PathBuffers pb
     }
 }
 #endif
+
+// ---------------------------------------------------------------------------------------------------------
+// The host-side launchers of a unit, named like its kernels (launch_shade_fast, ...).  agpt::launch_shading (agpt_shade_kernels.hip)
+// picks among the units.
+namespace agpt {
+using ShadeLaunch = void(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
+                         const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
+using ResolveLaunch = void(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin);
+ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast;
+ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED units have none, see k_resolve_pending)
+
+void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
+                                    const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters,
+                                    uint32_t* tile_heads) {
+    const dim3 g(grid), b(AGPT_BLOCK);
+    if (lds_tables && env)
+        hipLaunchKernelGGL((AGPT_SHADE_KNAME(k_shade)<true, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+    else if (lds_tables)
+        hipLaunchKernelGGL((AGPT_SHADE_KNAME(k_shade)<true, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+    else if (env)
+        hipLaunchKernelGGL((AGPT_SHADE_KNAME(k_shade)<false, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+    else
+        hipLaunchKernelGGL((AGPT_SHADE_KNAME(k_shade)<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
+}
+#if !AGPT_SHADE_TEXTURED
+void AGPT_SHADE_KNAME(launch_resolve_pending)(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc,
+                                              const PathBuffers& pb, const Queues& qin) {
+    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_resolve_pending), dim3(grid), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, qin);
+}
+#endif
+}  // namespace agpt

@@ -1,4 +1,4 @@
-// agpt_shade_kernels.hip -- translation unit of the shading kernels (agpt_shade_kernels.h) and their host-side launchers.
+// agpt_shade_kernels.hip -- translation unit of the shading kernels (agpt_shade_kernels.h) and their host-side launchers (the unit's own come with the header; launch_shading picks the unit).
 // build.py compiles it with -mllvm -disable-machine-licm (see the header for why); everything else of the library is in
 // agpt_api.hip.
 #include <hip/hip_runtime.h>
@@ -11,17 +11,15 @@ bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights) {
     return n_prims <= AGPT_SHADE_LDS_PRIMS && n_materials <= AGPT_SHADE_LDS_MATERIALS && n_lights <= AGPT_SHADE_LDS_LIGHTS;
 }
 
-void launch_shade(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb,
-                  const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
-    const dim3 g(grid), b(AGPT_BLOCK);
-    if (lds_tables && env) hipLaunchKernelGGL((k_shade<true, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else if (lds_tables) hipLaunchKernelGGL((k_shade<true, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else if (env) hipLaunchKernelGGL((k_shade<false, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else hipLaunchKernelGGL((k_shade<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-}
-
-void launch_resolve_pending(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin) {
-    hipLaunchKernelGGL(k_resolve_pending, dim3(grid), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, qin);
+void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, int resolve_grid, const DevScene& sc, const RenderConsts& rc,
+                    const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
+    ShadeLaunch* const shade = v.textured ? (v.fast ? launch_shade_textured_fast : launch_shade_textured)
+                                          : (v.fast ? launch_shade_fast : launch_shade);
+    shade(stream, shade_grid, v.lds_tables, v.env, sc, rc, pb, qin, qout, counters, tile_heads);
+    // The TEXTURED units have no k_resolve_pending (no BSDF and no material in it): their ended paths use the plain unit's of the same
+    // arithmetic.  (Independent of k_shade: different paths.)
+    ResolveLaunch* const resolve = v.fast ? launch_resolve_pending_fast : launch_resolve_pending;
+    resolve(stream, resolve_grid, sc, rc, pb, qin);
 }
 
 }  // namespace agpt

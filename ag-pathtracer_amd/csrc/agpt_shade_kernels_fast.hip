@@ -19,20 +19,6 @@ __global__ void k_kat_bsdf_sample_fast(DevScene sc, int material, int n, const f
 
 namespace agpt {
 
-void launch_shade_fast(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
-                       const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
-    const dim3 g(grid), b(AGPT_BLOCK);
-    if (lds_tables && env) hipLaunchKernelGGL((k_shade_fast<true, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else if (lds_tables) hipLaunchKernelGGL((k_shade_fast<true, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else if (env) hipLaunchKernelGGL((k_shade_fast<false, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else hipLaunchKernelGGL((k_shade_fast<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-}
-
-void launch_resolve_pending_fast(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb,
-                                 const Queues& qin) {
-    hipLaunchKernelGGL(k_resolve_pending_fast, dim3(grid), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, qin);
-}
-
 void launch_kat_bsdf_eval_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* wi3, float* f3o,
                                float* pdfo) {
     hipLaunchKernelGGL(k_kat_bsdf_eval_fast, dim3((n + 63) / 64), dim3(64), 0, stream, sc, material, n, wo3, wi3, f3o, pdfo);

@@ -5,16 +5,3 @@
 #include <hip/hip_runtime.h>
 
 #include "agpt_shade_kernels.h"
-
-namespace agpt {
-
-void launch_shade_textured(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
-                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
-    const dim3 g(grid), b(AGPT_BLOCK);
-    if (lds_tables && env) hipLaunchKernelGGL((k_shade_textured<true, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else if (lds_tables) hipLaunchKernelGGL((k_shade_textured<true, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else if (env) hipLaunchKernelGGL((k_shade_textured<false, true>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-    else hipLaunchKernelGGL((k_shade_textured<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
-}
-
-}  // namespace agpt

@@ -136,27 +136,21 @@ __device__ __forceinline__ void queue_push(uint32_t* q, uint32_t* count, bool pr
 
 
 // ---------------------------------------------------------------------------------------------------------
-// host-side launchers of the shading translation units (agpt_shade_kernels.hip, agpt_shade_kernels_fast.hip and their _textured twins)
+// host side of the shading translation units (agpt_shade_kernels.hip, agpt_shade_kernels_fast.hip and their _textured twins)
 namespace agpt {
 // the scene's Scene::primitives records, materials and lights fit the LDS copies k_shade<LDS_TABLES> works from
 bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights);
-void launch_shade(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb,
-                  const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
-void launch_resolve_pending(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin);
-// the same launches of the fast-arithmetic unit (agpt_shade_kernels_fast.hip: k_shade_fast, k_resolve_pending_fast), and its
-// known-answer kernels (k_kat_bsdf_eval_fast, k_kat_bsdf_sample_fast; one lane per case, 64-lane blocks)
-void launch_shade_fast(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
-                       const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
-void launch_resolve_pending_fast(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb,
-                                 const Queues& qin);
+// Which shading kernels an iteration runs: the unit (fast: agpt_scene_set_shading_arith(AGPT_SHADING_FAST); textured: a material of
+// the scene has a texture) and k_shade's <LDS_TABLES, ENV> instantiation in it.
+struct ShadeVariant {
+    bool fast, textured, lds_tables, env;
+};
+// the shading of one wavefront iteration: k_shade over qin's active paths, k_resolve_pending over its ended ones
+void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, int resolve_grid, const DevScene& sc, const RenderConsts& rc,
+                    const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
+// the known-answer kernels of the fast-arithmetic unit (k_kat_bsdf_eval_fast, k_kat_bsdf_sample_fast; one lane per case, 64-lane blocks)
 void launch_kat_bsdf_eval_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* wi3, float* f3o,
                                float* pdfo);
 void launch_kat_bsdf_sample_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* u2, float* wi3o,
                                  float* f3o, float* pdfo, int32_t* speco);
-// k_shade of the TEXTURED units (agpt_shade_kernels_textured.hip, agpt_shade_kernels_textured_fast.hip) for scenes with a textured
-// material; their ended paths go through launch_resolve_pending / launch_resolve_pending_fast
-void launch_shade_textured(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
-                           const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
-void launch_shade_textured_fast(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
-                                const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
 }  // namespace agpt
