@@ -164,7 +164,9 @@ struct agpt_scene {
     };
     std::vector<HostTexture> textures;
     std::vector<int32_t> material_texture;
-    bool textured = false;   // set by agpt_scene_commit: a material has a texture -> the TEXTURED shading / feature kernels
+    std::vector<uint32_t> material_param_slots;   // agpt_scene_set_material_param_texture: per material, param_slots_pack (0 = no map)
+    bool textured = false;   // set by agpt_scene_commit: a material has a texture or a map -> the TEXTURED shading / feature kernels
+    bool mapped = false;     // set by agpt_scene_commit: a material has a roughness / metallic map -> the MAPPED shading kernels
     DevBuf<float4> d_tri_uv;
     DevBuf<DevTexture> d_textures;
     DevBuf<int32_t> d_material_texture;
@@ -398,6 +400,7 @@ int agpt_scene_add_material(agpt_scene* s, int type, const float color[3], float
     s->materials.push_back(agpt::make_material(type, color, roughness, metallic));
     s->colors.push_back(make_float4(color[0], color[1], color[2], 0.f));
     s->material_texture.push_back(-1);
+    s->material_param_slots.push_back(0u);
     s->committed = false;
     return (int)s->materials.size() - 1;
 }
@@ -544,6 +547,32 @@ int agpt_scene_set_material_texture(agpt_scene* s, int material, int texture) {
     return AGPT_OK;
 }
 
+static_assert(AGPT_PARAM_ROUGHNESS == 0 && AGPT_PARAM_METALLIC == 1, "param_slots_pack (agpt_scene.h) numbers the parameters like agpt.h");
+
+int agpt_scene_set_material_param_texture(agpt_scene* s, int material, int param, int texture, int channel) {
+    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_param_texture: scene is NULL");
+    if (material < 0 || material >= (int)s->materials.size())
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_param_texture: bad material id");
+    if (param != AGPT_PARAM_ROUGHNESS && param != AGPT_PARAM_METALLIC)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_param_texture: param is neither AGPT_PARAM_ROUGHNESS nor AGPT_PARAM_METALLIC");
+    if (texture < -1 || texture >= (int)s->textures.size()) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_param_texture: bad texture id");
+    if (texture >= 0 && (channel < 0 || channel > 2))
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_param_texture: channel must be 0 (r), 1 (g) or 2 (b)");
+    if (s->materials[material].type != AGPT_MAT_DISNEY)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_param_texture: only AGPT_MAT_DISNEY materials have a roughness and a metallic weight");
+    if (s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_param_texture: the scene is already committed");
+    if (texture > AGPT_PARAM_MAX_TEXTURE)
+        return fail(AGPT_ERR_LIMIT, "agpt_scene_set_material_param_texture: a parameter map must be one of the scene's first " +
+                                        std::to_string(AGPT_PARAM_MAX_TEXTURE + 1) + " textures");
+    const uint32_t old = s->material_param_slots[material];
+    int tex[2] = {param_slot_texture(old, 0), param_slot_texture(old, 1)};
+    int ch[2] = {param_slot_channel(old, 0), param_slot_channel(old, 1)};
+    tex[param] = texture;
+    ch[param] = texture >= 0 ? channel : 0;
+    s->material_param_slots[material] = param_slots_pack(tex[0], ch[0], tex[1], ch[1]);
+    return AGPT_OK;
+}
+
 int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
     if (!s || !d) return fail(AGPT_ERR_INVALID, "agpt_scene_set_camera: NULL argument");
     s->cam = agpt::make_camera(*d);
@@ -554,12 +583,15 @@ int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
 
 int agpt_scene_commit(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_commit: scene is NULL");
-    bool textured = false;
+    bool textured = false, mapped = false;
     for (int32_t t : s->material_texture) textured = textured || t >= 0;
+    for (uint32_t slots : s->material_param_slots) mapped = mapped || slots != 0;
+    textured = textured || mapped;   // (the MAPPED kernels are TEXTURED ones: same uv records, same texture table)
     if (textured)
         for (const agpt::HostPrim& hp : s->prims)
-            if (hp.type != AGPT_PRIM_MESH && hp.material >= 0 && s->material_texture[hp.material] >= 0)
-                return fail(AGPT_ERR_INVALID, "agpt_scene_commit: a sphere or a plane has a textured material (textures apply to triangle meshes only)");
+            if (hp.type != AGPT_PRIM_MESH && hp.material >= 0 && (s->material_texture[hp.material] >= 0 || s->material_param_slots[hp.material] != 0))
+                return fail(AGPT_ERR_INVALID, "agpt_scene_commit: a sphere or a plane has a material with a colour texture or a roughness / metallic map "
+                                              "(textures apply to triangle meshes only)");
     HIP_TRY(hipSetDevice(s->ctx->device));
     agpt::FlatScene flat;
     flat.want_tri_uv = textured;
@@ -616,20 +648,34 @@ int agpt_scene_commit(agpt_scene* s) {
     if ((rc = upload(s->d_envs, envs, st))) return rc;
     // texture coordinates, texels and the tables are uploaded only for a scene that has a textured material
     std::vector<DevTexture> textures(textured ? s->textures.size() : 0);
+    std::vector<std::vector<float4>> own_texels;   // (kept until the copies below have completed)
     if (textured) {
+        // The device's material_texture table.  A material with a roughness / metallic map and no colour texture gets a 1x1 texture of
+        // its constant colour here (any uv reads that texel, and the texel has the constant's bits), so the MAPPED kernels have
+        // one source for the colour; with maps the table's second half holds the packed slots (agpt_scene.h).
+        std::vector<int32_t> table = s->material_texture;
+        for (size_t m = 0; m < table.size(); m++)
+            if (s->material_param_slots[m] != 0 && table[m] < 0) {
+                table[m] = (int32_t)(s->textures.size() + own_texels.size());
+                own_texels.push_back(std::vector<float4>(1, s->colors[m]));
+            }
+        if (mapped) table.insert(table.end(), s->material_param_slots.begin(), s->material_param_slots.end());
+        textures.resize(s->textures.size() + own_texels.size());
         s->d_texels.resize(textures.size());
         for (size_t i = 0; i < textures.size(); i++) {
-            if ((rc = upload(s->d_texels[i], s->textures[i].texels, st))) return rc;
+            const bool own = i >= s->textures.size();
+            if ((rc = upload(s->d_texels[i], own ? own_texels[i - s->textures.size()] : s->textures[i].texels, st))) return rc;
             textures[i].texels = s->d_texels[i].p;
-            textures[i].width = s->textures[i].width;
-            textures[i].height = s->textures[i].height;
+            textures[i].width = own ? 1 : s->textures[i].width;
+            textures[i].height = own ? 1 : s->textures[i].height;
         }
         if ((rc = upload(s->d_tri_uv, flat.tri_uv, st))) return rc;
         if ((rc = upload(s->d_textures, textures, st))) return rc;
-        if ((rc = upload(s->d_material_texture, s->material_texture, st))) return rc;
+        if ((rc = upload(s->d_material_texture, table, st))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
     s->textured = textured;
+    s->mapped = mapped;
     s->dev.tri_uv = textured ? s->d_tri_uv.p : nullptr;
     s->dev.textures = textured ? s->d_textures.p : nullptr;
     s->dev.material_texture = textured ? s->d_material_texture.p : nullptr;
@@ -892,6 +938,7 @@ static int begin_wavefront(agpt_ctx* c, const agpt_scene* s, int enable_counters
     run.timing = timing;
     run.shade.fast = s->shading_arith == AGPT_SHADING_FAST;   // agpt_scene_set_shading_arith
     run.shade.textured = s->textured;                         // a material of the scene has a texture
+    run.shade.mapped = s->mapped;                             // ... a roughness / metallic map
     run.shade.lds_tables = shade_tables_fit_lds(s->dev);
     run.shade.env = !s->envs.empty();                         // an InfiniteAreaLight is present
     c->tev_used = 0;

@@ -260,29 +260,14 @@ DevMaterial make_material(int type, const float color[3], float roughness, float
     m.type = type;
     const v3 c = V3(color[0], color[1], color[2]);
     if (type == AGPT_MAT_DISNEY) {
-        // material.h:14-49
-        const float eta = 1.5f;
-        const float strans = 0.f;
-        const float diffuse_weight = (1 - metallic) * (1 - strans);
-        if (diffuse_weight > 0) {
-            m.has_diffuse = 1;
-            m.has_retro = 1;
-        }
-        m.roughness = roughness;
-        const float aspect = 1.f;
-        float ax = smaxf(.001f, (roughness * roughness) / aspect);
-        float ay = smaxf(.001f, (roughness * roughness) * aspect);
-        m.alphax = smaxf(0.001f, ax);  // TrowbridgeReitzDistribution ctor, microfacet.h:120-122
-        m.alphay = smaxf(0.001f, ay);
-        m.metallic = metallic;
-        m.eta = eta;
-        m.has_microfacet = 1;
-    } else if (type == AGPT_MAT_MIRROR) {
-        m.has_specular = 1;
+        material_set_disney(m, c, roughness, metallic);   // material.h:14-49 (agpt_scene.h: shared with the mapped shading kernels)
     } else {
-        m.has_diffuse = 1;
+        if (type == AGPT_MAT_MIRROR)
+            m.has_specular = 1;
+        else
+            m.has_diffuse = 1;
+        material_set_color(m, c);   // mirror_R / diffuse_R (agpt_scene.h: shared with the textured shading kernels)
     }
-    material_set_color(m, c);   // diffuse_R / R0 / mirror_R (agpt_scene.h: shared with the textured shading kernels)
     return m;
 }
 

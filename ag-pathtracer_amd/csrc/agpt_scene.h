@@ -19,7 +19,9 @@
 //                           the triangle's texture coordinates (trianglemesh.cpp:46-56; (0,0), (1,0), (1,1) for a mesh without),
 //                           two aligned 16-B loads per shaded hit
 //   textures   DevTexture[X], material_texture int32[M] (texture id of a material, -1 = none): kept beside DevMaterial so that the
-//                           material table the untextured kernels stage in LDS stays what it was
+//                           material table the untextured kernels stage in LDS stays what it was.  In a scene with roughness /
+//                           metallic maps the table has a second half, material_texture[M + m] = the packed parameter slots of
+//                           material m (param_slots_pack below), which only the MAPPED kernel variants read
 //   prims      DevPrim[P]   Scene::primitives in insertion order (scene.h:5-19 walks them linearly)
 //   materials  DevMaterial[M], lights DevLight[L]
 #pragma once
@@ -107,6 +109,40 @@ AGPT_HD void material_set_color(DevMaterial& m, v3 c) {
     }
 }
 
+// The whole DisneyMaterial constructor (material.h:14-49) on a material whose type is set: every field that depends on the colour,
+// the roughness or the metallic weight -- the lobe set (has_diffuse / has_retro: diffuseWeight > 0), roughness (DisneyRetro),
+// alphax / alphay with both .001 clamps, metallic, eta, diffuse_R (zero without a diffuse lobe), R0.  make_material runs it once with
+// the material's constants, the MAPPED shading kernels once per hit with the texels -- the same fp32 operations in the same order.
+AGPT_HD void material_set_disney(DevMaterial& m, v3 c, float roughness, float metallic) {
+    const float strans = 0.f;
+    const float diffuse_weight = (1 - metallic) * (1 - strans);
+    m.has_diffuse = m.has_retro = diffuse_weight > 0 ? 1 : 0;
+    m.roughness = roughness;
+    const float aspect = 1.f;
+    float ax = smaxf(.001f, (roughness * roughness) / aspect);
+    float ay = smaxf(.001f, (roughness * roughness) * aspect);
+    m.alphax = smaxf(0.001f, ax);  // TrowbridgeReitzDistribution ctor, microfacet.h:120-122
+    m.alphay = smaxf(0.001f, ay);
+    m.metallic = metallic;
+    m.eta = 1.5f;
+    m.has_microfacet = 1;
+    m.diffuse_R[0] = m.diffuse_R[1] = m.diffuse_R[2] = 0.f;
+    material_set_color(m, c);   // diffuse_R (with a diffuse lobe), R0
+}
+
+// Roughness / metallic maps (agpt_scene_set_material_param_texture): a slot is 0 = the material's constant, or
+// (texture id + 1) << 2 | channel in 16 bits; a material's two slots share one word -- parameter p (agpt.h: AGPT_PARAM_ROUGHNESS 0,
+// AGPT_PARAM_METALLIC 1) in bits 16p .. 16p + 15 -- so that the table costs the MAPPED kernels one word per material of LDS.  A
+// texture with an id above AGPT_PARAM_MAX_TEXTURE cannot be named.
+#define AGPT_PARAM_MAX_TEXTURE 16382
+AGPT_HD uint32_t param_slots_pack(int rough_texture, int rough_channel, int metal_texture, int metal_channel) {
+    const uint32_t r = rough_texture < 0 ? 0u : ((uint32_t)(rough_texture + 1) << 2 | (uint32_t)rough_channel);
+    const uint32_t m = metal_texture < 0 ? 0u : ((uint32_t)(metal_texture + 1) << 2 | (uint32_t)metal_channel);
+    return r | m << 16;
+}
+AGPT_HD int param_slot_texture(uint32_t slots, int param) { return (int)((slots >> (16 * param) & 0xFFFFu) >> 2) - 1; }   // -1 = none
+AGPT_HD int param_slot_channel(uint32_t slots, int param) { return (int)(slots >> (16 * param) & 3u); }
+
 // An image texture (HDRTexture, texture.h:41-84): texels row-major, row 0 = top, one float4 (rgb, -) each so that a lookup is
 // one 16-byte gather
 struct DevTexture {
@@ -175,7 +211,7 @@ struct DevScene {
     // image textures: all three NULL unless a material of the scene has one (only the TEXTURED kernel variants read them)
     const float4* tri_uv;
     const DevTexture* textures;
-    const int32_t* material_texture;   // [n_materials]
+    const int32_t* material_texture;   // [n_materials], or [2 * n_materials] in a scene with roughness / metallic maps (see above)
 };
 
 // 16-B hit record written by the trace kernel

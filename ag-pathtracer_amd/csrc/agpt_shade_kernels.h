@@ -16,10 +16,18 @@
 // TEXTURED variant of k_shade -- a material's colour at a mesh hit comes from its image texture (agpt_scene.h: tri_uv, textures,
 // material_texture) -- as k_shade_textured / k_shade_textured_fast; the launchers pick it for scenes that have a textured
 // material, every other scene runs the kernels of the two plain units, whose code the flag does not touch.
+// AGPT_SHADE_TEXTURED 2 (agpt_shade_kernels_mapped.hip, agpt_shade_kernels_mapped_fast.hip) is the MAPPED variant on top of it -- roughness
+// and metallic at a mesh hit come from image textures too (agpt_scene.h: param_slots_pack), so the whole Disney constructor runs per
+// hit -- as k_shade_mapped / k_shade_mapped_fast, for scenes in which a material has such a map; it leaves the code of the other four
+// units alone in the same way.
 #ifndef AGPT_SHADE_TEXTURED
 #define AGPT_SHADE_TEXTURED 0
 #endif
-#if AGPT_SHADE_TEXTURED && AGPT_SHADE_FAST
+#if AGPT_SHADE_TEXTURED == 2 && AGPT_SHADE_FAST
+#define AGPT_SHADE_KNAME(n) n##_mapped_fast
+#elif AGPT_SHADE_TEXTURED == 2
+#define AGPT_SHADE_KNAME(n) n##_mapped
+#elif AGPT_SHADE_TEXTURED && AGPT_SHADE_FAST
 #define AGPT_SHADE_KNAME(n) n##_textured_fast
 #elif AGPT_SHADE_TEXTURED
 #define AGPT_SHADE_KNAME(n) n##_textured
@@ -88,7 +96,10 @@ __device__ __forceinline__ v3 pending_light_sample(const DevScene& sc, const Ren
 // pair of 16-B loads in the same round trip); the texel gather follows the material lookup, and material_set_color puts what
 // make_material derives from a colour -- diffuse_R, R0, mirror_R -- into a register copy of the material, which is what
 // bsdf_setup, lobe_eval, disney_fresnel and lobe_sample then read.
-template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0)>
+// MAPPED: see AGPT_SHADE_TEXTURED 2 above.  Up to three texels per vertex (colour, roughness, metallic), one gather per DISTINCT
+// texture -- slots that name the same image, as glTF's metallic-roughness image does, share its texel -- all issued before
+// material_set_disney rebuilds the register copy, lobe set included.
+template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0), bool MAPPED = (AGPT_SHADE_TEXTURED == 2)>
 __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t pid SCK_PARAMS) {
     uint32_t bits = 0;
     // Every per-path record is fetched up front, unconditionally: the loads then overlap in one memory round trip instead
@@ -172,8 +183,31 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
             SCK(3);   // emission, termination
             bits |= SB_SHADED;
             const DevMaterial& mc = sc.materials[sc.prims[s.prim].material];
-            DevMaterial mt;   // TEXTURED: the material with the colour of the texel at the hit
-            if constexpr (TEXTURED) {
+            DevMaterial mt;   // TEXTURED: the material with the colour of the texel at the hit (MAPPED: and its roughness / metallic)
+            if constexpr (MAPPED) {
+                mt = mc;
+                const int mat = sc.prims[s.prim].material;
+                // (a material with a parameter map always has a colour texture: agpt_scene_commit gives it a 1x1 one of its constant
+                // colour if the host set none, so the constructor's third input needs no table of its own)
+                const int tex = sc.material_texture[mat];
+                const uint32_t slots = (uint32_t)sc.material_texture[sc.n_materials + mat];
+                if (tex >= 0 && !(h.id & AGPT_HIT_SPHERE)) {
+                    const int rtex = param_slot_texture(slots, 0), mtex = param_slot_texture(slots, 1);   // (0 = roughness, 1 = metallic)
+                    // the texture records first (valid for any slot: record 0 stands in for "none"), then the gathers, then their uses
+                    const DevTexture ct = sc.textures[tex], rt = sc.textures[rtex >= 0 ? rtex : 0], mx = sc.textures[mtex >= 0 ? mtex : 0];
+                    float tu, tv;
+                    triangle_uv(uv01, uv2, h.b1, h.b2, &tu, &tv);
+                    const v3 c = texture_value(ct, tu, tv);
+                    v3 rv = c, mv = c;
+                    if (rtex >= 0 && rtex != tex) rv = texture_value(rt, tu, tv);
+                    if (mtex >= 0 && mtex != tex) mv = mtex == rtex ? rv : texture_value(mx, tu, tv);
+                    if (slots)   // (Disney: the only type agpt_scene_set_material_param_texture accepts)
+                        material_set_disney(mt, c, rtex >= 0 ? comp(rv, param_slot_channel(slots, 0)) : mc.roughness,
+                                            mtex >= 0 ? comp(mv, param_slot_channel(slots, 1)) : mc.metallic);
+                    else
+                        material_set_color(mt, c);
+                }
+            } else if constexpr (TEXTURED) {
                 mt = mc;
                 const int tex = sc.material_texture[sc.prims[s.prim].material];
                 if (tex >= 0 && !(h.id & AGPT_HIT_SPHERE)) {
@@ -471,7 +505,9 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
     __shared__ DevMaterial s_tab_materials[LDS_TABLES ? AGPT_SHADE_LDS_MATERIALS : 1];
     __shared__ DevLight s_tab_lights[LDS_TABLES ? AGPT_SHADE_LDS_LIGHTS : 1];
 #if AGPT_SHADE_TEXTURED
-    __shared__ int32_t s_tab_material_texture[LDS_TABLES ? AGPT_SHADE_LDS_MATERIALS : 1];   // 512 B beside the 9.5 KB of materials
+    // 512 B beside the 9.5 KB of materials; MAPPED: both halves of the table, 1 KB (40,960 B per block in all: still four blocks per CU)
+    constexpr int n_tab_halves = AGPT_SHADE_TEXTURED == 2 ? 2 : 1;
+    __shared__ int32_t s_tab_material_texture[LDS_TABLES ? n_tab_halves * AGPT_SHADE_LDS_MATERIALS : 1];
 #endif
     // (a launch over a short queue: one wave per 256-path tile is all it can use -- the rest of the grid leaves before setting up)
     if (blockIdx.x * (AGPT_BLOCK / 64) * 64u * SHADE_U >= QCOUNT(qin, 0) && blockIdx.x > 0) return;
@@ -489,7 +525,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
         sc.materials = s_tab_materials;
         sc.lights = s_tab_lights;
 #if AGPT_SHADE_TEXTURED
-        copy_words(s_tab_material_texture, sc_in.material_texture, sc_in.n_materials * (int)sizeof(int32_t));
+        copy_words(s_tab_material_texture, sc_in.material_texture, n_tab_halves * sc_in.n_materials * (int)sizeof(int32_t));
         sc.material_texture = s_tab_material_texture;
 #endif
         __syncthreads();
@@ -644,8 +680,8 @@ namespace agpt {
 using ShadeLaunch = void(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
                          const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
 using ResolveLaunch = void(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin);
-ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast;
-ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED units have none, see k_resolve_pending)
+ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast, launch_shade_mapped, launch_shade_mapped_fast;
+ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED and MAPPED units have none, see k_resolve_pending)
 
 void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
                                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters,

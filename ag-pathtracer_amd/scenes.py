@@ -92,6 +92,9 @@ class SceneDesc:
     def set_material_texture(self, material, texture):
         self.ops.append(("material_texture", int(material), int(texture)))
 
+    def set_material_param_texture(self, material, param, texture, channel=0):
+        self.ops.append(("material_param_texture", int(material), int(param), int(texture), int(channel)))
+
     def set_camera(self, lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
         self.camera = (np.asarray(lookfrom, F).copy(), np.asarray(lookat, F).copy(), np.asarray(vup, F).copy(),
                        F(aspect_ratio), float(vfov), float(aperture))
@@ -118,6 +121,8 @@ class SceneDesc:
                 target.add_texture(op[1])
             elif k == "material_texture":
                 target.set_material_texture(op[1], op[2])
+            elif k == "material_param_texture":
+                target.set_material_param_texture(op[1], op[2], op[3], op[4])
         if self.camera is not None:
             target.set_camera(*self.camera)
         if hasattr(target, "commit"):
@@ -258,6 +263,23 @@ def scene_textured(texture=None, backdrop=None):
     v, n, t, idx = blob_mesh(24, 16, center=(2.2, 0.2, 0.6), radius=0.9, seed=3)
     d.add_mesh(v, n, t, idx, metal, 1)
     d.set_material_texture(metal, d.add_texture(checker_texture(32, 16, 8, a=(0.9, 0.6, 0.3), b=(0.6, 0.7, 0.8))))
+    return d
+
+
+def scene_mapped(backdrop=None):
+    """scene_textured() with a metallic-roughness image on both of its mesh materials, laid out as glTF does: roughness in g, metallic in
+    b of ONE image -- a checker whose cells alternate between a rough dielectric and a polished metal (the lobe set changes from cell to
+    cell: metallic is exactly 0 or 1), each cell's roughness graded along v."""
+    from .binding import PARAM_METALLIC, PARAM_ROUGHNESS
+    d = scene_textured(backdrop=backdrop)
+    d.name = "C1-mapped"
+    y, x = np.mgrid[0:32, 0:32]
+    metal = (x // 4 + y // 4) % 2 == 1
+    rough = np.where(metal, 0.15, 0.55) + 0.4 * (y + 0.5) / 32
+    mr = d.add_texture(np.stack([np.zeros_like(rough), rough, metal.astype(np.float64)], -1).astype(F))
+    for m in (0, 2):   # the floor and the blob (the gold sphere is analytic: no maps)
+        d.set_material_param_texture(m, PARAM_ROUGHNESS, mr, 1)
+        d.set_material_param_texture(m, PARAM_METALLIC, mr, 2)
     return d
 
 

@@ -171,6 +171,31 @@ int agpt_scene_add_texture(agpt_scene*, const float* rgb, int width, int height)
  * Both calls return AGPT_ERR_INVALID (+ agpt_last_error) for a NULL argument, a non-positive size, an unknown material or texture
  * id, or a scene that is already committed. */
 int agpt_scene_set_material_texture(agpt_scene*, int material, int texture);
+/* ---- image textures for the roughness and the metallic weight of Disney materials ------------------------------
+ * From now on `material`'s roughness / metallic at a mesh hit is channel `channel` (0 = r, 1 = g, 2 = b) of value(u, v) of
+ * `texture` instead of the constant it was created with; texture = -1 restores the constant (channel is then ignored).  Before
+ * agpt_scene_commit.  Textures are those of agpt_scene_add_texture: one image may serve several slots of several materials (glTF
+ * keeps roughness in g and metallic in b of one image), and the colour slot (agpt_scene_set_material_texture) is independent of
+ * these two.
+ *   uv, value(u, v)  exactly the colour texture's, above: nearest texel, Mod wrap, texel (0, 0) for a non-finite uv; exact under
+ *                    AGPT_SHADING_FAST.
+ *   the value        the channel as stored, no clamp: it is treated exactly as if it had been passed to agpt_scene_add_material
+ *                    (the host owns the range).
+ *   what it feeds    at the hit the material is what agpt_scene_add_material(AGPT_MAT_DISNEY, c, r, m) would have built, with c, r
+ *                    and m each the texel or the constant -- the DisneyMaterial constructor (material.h:14-49) per hit, same fp32
+ *                    operations in the same order: diffuseWeight = (1 - m) * (1 - 0); the diffuse and the retro lobe exist iff
+ *                    diffuseWeight > 0 (metallic 1 drops both); roughness; alphax = alphay = max(.001, max(.001, r * r)); metallic;
+ *                    diffuseWeight * c; Cspec0.  A map whose texels equal the constant therefore renders bit-identical to no map, and
+ *                    a texel per mesh bit-identical to a material per mesh.
+ * Every path that shades sees the maps -- agpt_render, agpt_render_adaptive, agpt_li_batch, in both shading arithmetics.
+ * agpt_render_features does not: its albedo stays the colour (or the colour texel), whatever the maps say.  agpt_kat_bsdf_eval /
+ * _sample have no hit and keep the constants.  Triangle meshes only: agpt_scene_commit returns AGPT_ERR_INVALID if a sphere or a
+ * plane carries a material with a map.  Scenes without a map run the kernels they ran before maps existed.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error) for a NULL scene, an unknown material, param, texture or channel, a material that is
+ * not AGPT_MAT_DISNEY (mirror and diffuse-only materials ignore both parameters) or a scene that is already committed, and
+ * AGPT_ERR_LIMIT for a texture id above 16382 (a material's two slots are packed into one 32-bit word). */
+enum { AGPT_PARAM_ROUGHNESS = 0, AGPT_PARAM_METALLIC = 1 };
+int agpt_scene_set_material_param_texture(agpt_scene*, int material, int param, int texture, int channel);
 /* scene->camera = desc; Camera(desc) (camera.h:29-56,77-90) */
 int agpt_scene_set_camera(agpt_scene*, const agpt_camera_desc*);
 /* flatten + upload to HBM; must be called after the last add_* and before render/intersect */

@@ -192,6 +192,12 @@ public:
     void SetMaterialTexture(int material, int texture) {
         check(agpt_scene_set_material_texture(h_, material, texture), "agpt_scene_set_material_texture");
     }
+    // a Disney material's roughness (AGPT_PARAM_ROUGHNESS) / metallic (AGPT_PARAM_METALLIC) at a mesh hit becomes channel `channel`
+    // (0 = r, 1 = g, 2 = b) of Texture::value(u, v) of `texture` (-1: its constant again), and the material what DisneyMaterial::Make
+    // builds from it
+    void SetMaterialParamTexture(int material, int param, int texture, int channel) {
+        check(agpt_scene_set_material_param_texture(h_, material, param, texture, channel), "agpt_scene_set_material_param_texture");
+    }
     // upload to HBM; call once after the scene is built (and again after changing `camera`)
     void commit() {
         check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera");

@@ -16,7 +16,7 @@ import ag_pathtracer_amd as ag  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scene", default="c3", choices=["c1", "c2", "c3", "c5", "simple", "heightfield", "textured"])
+    ap.add_argument("--scene", default="c3", choices=["c1", "c2", "c3", "c5", "simple", "heightfield", "textured", "mapped"])
     ap.add_argument("--width", type=int, default=960)
     ap.add_argument("--height", type=int, default=540)
     ap.add_argument("--spp", type=int, default=64)
@@ -41,7 +41,7 @@ def main():
     aspect = W / float(H)
     desc = {"c1": lambda: ag.scenes.scene_c1(), "c2": lambda: ag.scenes.scene_c2(aspect=aspect),
             "c3": lambda: ag.scenes.scene_c3(aspect=aspect), "c5": lambda: ag.scenes.scene_c5(aspect=aspect),
-            "simple": lambda: ag.scenes.scene_simple_test(), "textured": lambda: ag.scenes.scene_textured(),
+            "simple": lambda: ag.scenes.scene_simple_test(), "textured": lambda: ag.scenes.scene_textured(), "mapped": lambda: ag.scenes.scene_mapped(),
             "heightfield": lambda: ag.scenes.scene_heightfield(361, True, W, H)}[a.scene]()
     ctx = ag.Context(0)
     t0 = time.time()

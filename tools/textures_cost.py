@@ -1,7 +1,8 @@
 """Developer measurement: what image textures cost.  C3 at 1080p / 64 spp untextured (k_shade) against the same scene with every
-material pointed at a 256x256 texture (k_shade_textured), two scenes in one process, each rendered --reps times, alternating,
-after a warm-up.  Per variant: step ms, trace ms, non-trace ms, the agpt_stats totals and non-trace ns per shaded vertex (medians).
-    python tools/textures_cost.py [--out profiles/textures_c3.json] [--reps 3] [--shading exact|fast] [--kernel-trace CSV]
+material pointed at a 256x256 texture (k_shade_textured) and, with --mapped, against that scene with every Disney material also
+pointed at one 256x256 image for its roughness (g) and its metallic weight (b) (k_shade_mapped); the scenes live in one process, each
+rendered --reps times, alternating, after a warm-up.  Per variant: step ms, trace ms, non-trace ms, the agpt_stats totals and non-trace ns per shaded vertex (medians).
+    python tools/textures_cost.py [--out profiles/textures_c3.json] [--mapped] [--reps 3] [--shading exact|fast] [--kernel-trace CSV]
 (--reps 1 --no-warmup: exactly one render per variant, the run for rocprofv3 --kernel-trace --stats; --kernel-trace adds that
 run's per-kernel times to the JSON)"""
 import argparse
@@ -27,8 +28,34 @@ def textured_c3(desc, size=256, seed=7):
     return desc
 
 
+def mapped_c3(desc, size=256, seed=9):
+    """textured_c3, then every Disney material takes one size x size noise image for both parameters: roughness from g, metallic
+    from b, each scattered around the material's own value (so that the scene stays the kind of scene it was)"""
+    desc = textured_c3(desc, size)
+    rng = np.random.RandomState(seed)
+    noise = rng.uniform(-0.2, 0.2, (size, size, 2))
+    mats = [op for op in desc.ops if op[0] == "material"]
+    for m, op in enumerate(mats):
+        if op[1] != ag.MAT_DISNEY:
+            continue
+        image = np.zeros((size, size, 3), np.float32)
+        image[..., 1] = np.clip(op[3] + noise[..., 0], 0, 1)
+        image[..., 2] = np.clip(op[4] + noise[..., 1], 0, 1)
+        tex = desc.add_texture(image)
+        desc.set_material_param_texture(m, ag.PARAM_ROUGHNESS, tex, 1)
+        desc.set_material_param_texture(m, ag.PARAM_METALLIC, tex, 2)
+    return desc
+
+
+def library_build_id():
+    """sha256 of the loaded library file: which kernel build the numbers belong to"""
+    import hashlib
+    return hashlib.sha256(open(ag.library_path(), "rb").read()).hexdigest()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mapped", action="store_true", help="add the leg with roughness / metallic maps (k_shade_mapped)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--shading", default="exact", choices=["exact", "fast"])
@@ -38,10 +65,12 @@ def main():
     W, H, spp = 1920, 1080, 64
     ctx = ag.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     scenes = {}
-    for name in ("untextured", "textured"):
+    for name in ("untextured", "textured") + (("mapped",) if a.mapped else ()):
         d = ag.scenes.scene_c3(aspect=W / float(H))
         if name == "textured":
             d = textured_c3(d)
+        elif name == "mapped":
+            d = mapped_c3(d)
         scenes[name] = d.instantiate(ag.Scene(ctx))
         scenes[name].set_shading_arith(a.shading)
     film = torch.zeros((H, W, 4), device="cuda")
@@ -61,7 +90,7 @@ def main():
             runs[name].append(dict(step_ms=st.total_ms, trace_ms=st.trace_ms, non_trace_ms=st.total_ms - st.trace_ms,
                                    shaded_vertices=int(st.shaded_vertices), rays=int(st.rays), closest_rays=int(st.closest_rays),
                                    anyhit_rays=int(st.anyhit_rays), answered_rays=int(st.answered_rays), iterations=int(st.iterations)))
-    res = {"device": torch.cuda.get_device_name(0), "command": "python " + " ".join(sys.argv),
+    res = {"device": torch.cuda.get_device_name(0), "command": "python " + " ".join(sys.argv), "library_sha256": library_build_id(),
            "config": dict(W=W, H=H, spp=spp, shading=a.shading, texture="256x256 per material, 35 materials", reps=a.reps)}
     for name, rs in runs.items():
         med = {k: statistics.median(r[k] for r in rs) for k in ("step_ms", "trace_ms", "non_trace_ms")}
@@ -74,6 +103,9 @@ def main():
             med["non_trace_ns_per_shaded_vertex"]), flush=True)
     res["non_trace_ratio"] = res["textured"]["non_trace_ms"] / res["untextured"]["non_trace_ms"]
     res["step_ratio"] = res["textured"]["step_ms"] / res["untextured"]["step_ms"]
+    if a.mapped:
+        for base in ("textured", "untextured"):
+            res["mapped_over_%s" % base] = {k: res["mapped"][k] / res[base][k] for k in ("step_ms", "non_trace_ms")}
     if a.kernel_trace:
         rows = list(csv.DictReader(open(a.kernel_trace)))
         res["kernel_trace"] = {r["Name"].split("(")[0]: dict(calls=int(r["Calls"]), total_ms=float(r["TotalDurationNs"]) / 1e6)
