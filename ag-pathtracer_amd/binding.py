@@ -24,6 +24,9 @@ BVH_BUILDER_HOST, BVH_BUILDER_DEVICE = 0, 1
 SHADING_EXACT, SHADING_FAST = 0, 1
 # agpt_scene_set_material_param_texture (include/agpt.h)
 PARAM_ROUGHNESS, PARAM_METALLIC = 0, 1
+# agpt_scene_set_texture_sampler (include/agpt.h)
+FILTER_NEAREST, FILTER_BILINEAR = 0, 1
+WRAP_REPEAT, WRAP_CLAMP, WRAP_MIRROR = 0, 1, 2
 BVH_DEVICE_LANE_MAX, BVH_DEVICE_CHUNK = 64, 2048
 NODE_DTYPE = np.dtype([("bmin", np.float32, 3), ("bmax", np.float32, 3), ("first", np.int32), ("count", np.int32)])
 
@@ -32,7 +35,7 @@ EXPORTS = [
     "agpt_last_error", "agpt_version", "agpt_init", "agpt_set_stream", "agpt_destroy", "agpt_scene_create",
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
-    "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_camera",
+    "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
@@ -141,6 +144,7 @@ def lib():
     L.agpt_scene_add_texture.argtypes = [vp, fp, C.c_int, C.c_int]
     L.agpt_scene_set_material_texture.argtypes = [vp, C.c_int, C.c_int]
     L.agpt_scene_set_material_param_texture.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.agpt_scene_set_texture_sampler.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.agpt_scene_set_camera.argtypes = [vp, C.POINTER(CameraDesc)]
     L.agpt_scene_commit.argtypes = [vp]
     L.agpt_mesh_num_nodes.argtypes = [vp, C.c_int]
@@ -581,6 +585,13 @@ class Scene:
         rebuilt from it as add_material would have built it (texture = -1: the constant again)."""
         _check(self.L.agpt_scene_set_material_param_texture(self.h, int(material), int(param), int(texture), int(channel)),
                "agpt_scene_set_material_param_texture")
+
+    def set_texture_sampler(self, texture, filter=FILTER_NEAREST, wrap_u=WRAP_REPEAT, wrap_v=WRAP_REPEAT):
+        """agpt_scene_set_texture_sampler: how the texture is read in every slot that names it -- filter FILTER_NEAREST (one texel) or
+        FILTER_BILINEAR (the fp32 lerp of the four texels around the position), each axis wrapped WRAP_REPEAT, WRAP_CLAMP or WRAP_MIRROR.
+        The default is nearest / repeat / repeat."""
+        _check(self.L.agpt_scene_set_texture_sampler(self.h, int(texture), int(filter), int(wrap_u), int(wrap_v)),
+               "agpt_scene_set_texture_sampler")
 
     def set_camera(self, lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
         d = CameraDesc()

@@ -160,13 +160,16 @@ struct agpt_scene {
     // image textures (agpt_scene_add_texture / agpt_scene_set_material_texture): texels as float4, per material the texture id or -1
     struct HostTexture {
         int width = 0, height = 0;
+        int filter = AGPT_FILTER_NEAREST, wrap_u = AGPT_WRAP_REPEAT, wrap_v = AGPT_WRAP_REPEAT;   // agpt_scene_set_texture_sampler
         std::vector<float4> texels;
+        bool default_sampler() const { return filter == AGPT_FILTER_NEAREST && wrap_u == AGPT_WRAP_REPEAT && wrap_v == AGPT_WRAP_REPEAT; }
     };
     std::vector<HostTexture> textures;
     std::vector<int32_t> material_texture;
     std::vector<uint32_t> material_param_slots;   // agpt_scene_set_material_param_texture: per material, param_slots_pack (0 = no map)
     bool textured = false;   // set by agpt_scene_commit: a material has a texture or a map -> the TEXTURED shading / feature kernels
     bool mapped = false;     // set by agpt_scene_commit: a material has a roughness / metallic map -> the MAPPED shading kernels
+    bool sampled = false;    // set by agpt_scene_commit: a material names a texture with a non-default sampler -> the SAMPLED kernels
     DevBuf<float4> d_tri_uv;
     DevBuf<DevTexture> d_textures;
     DevBuf<int32_t> d_material_texture;
@@ -573,6 +576,26 @@ int agpt_scene_set_material_param_texture(agpt_scene* s, int material, int param
     return AGPT_OK;
 }
 
+static_assert(AGPT_WRAP_REPEAT == (int)AGPT_TEXTURE_WRAP_REPEAT && AGPT_WRAP_CLAMP == (int)AGPT_TEXTURE_WRAP_CLAMP &&
+                  AGPT_WRAP_MIRROR == (int)AGPT_TEXTURE_WRAP_MIRROR && AGPT_FILTER_NEAREST == 0 && AGPT_FILTER_BILINEAR == 1,
+              "texture_size_pack (agpt_scene.h) numbers filters and wrap modes like agpt.h");
+
+int agpt_scene_set_texture_sampler(agpt_scene* s, int texture, int filter, int wrap_u, int wrap_v) {
+    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_set_texture_sampler: scene is NULL");
+    if (texture < 0 || texture >= (int)s->textures.size()) return fail(AGPT_ERR_INVALID, "agpt_scene_set_texture_sampler: bad texture id");
+    if (filter != AGPT_FILTER_NEAREST && filter != AGPT_FILTER_BILINEAR)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_texture_sampler: filter is neither AGPT_FILTER_NEAREST nor AGPT_FILTER_BILINEAR");
+    for (int wrap : {wrap_u, wrap_v})
+        if (wrap != AGPT_WRAP_REPEAT && wrap != AGPT_WRAP_CLAMP && wrap != AGPT_WRAP_MIRROR)
+            return fail(AGPT_ERR_INVALID, "agpt_scene_set_texture_sampler: a wrap mode is none of AGPT_WRAP_REPEAT, AGPT_WRAP_CLAMP, AGPT_WRAP_MIRROR");
+    if (s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_set_texture_sampler: the scene is already committed");
+    agpt_scene::HostTexture& t = s->textures[texture];
+    t.filter = filter;
+    t.wrap_u = wrap_u;
+    t.wrap_v = wrap_v;
+    return AGPT_OK;
+}
+
 int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
     if (!s || !d) return fail(AGPT_ERR_INVALID, "agpt_scene_set_camera: NULL argument");
     s->cam = agpt::make_camera(*d);
@@ -587,6 +610,11 @@ int agpt_scene_commit(agpt_scene* s) {
     for (int32_t t : s->material_texture) textured = textured || t >= 0;
     for (uint32_t slots : s->material_param_slots) mapped = mapped || slots != 0;
     textured = textured || mapped;   // (the MAPPED kernels are TEXTURED ones: same uv records, same texture table)
+    // SAMPLED: a texture that a material names -- in its colour slot or in a parameter slot -- has a sampler of its own
+    bool sampled = false;
+    for (size_t m = 0; m < s->material_texture.size(); m++)
+        for (int t : {(int)s->material_texture[m], param_slot_texture(s->material_param_slots[m], 0), param_slot_texture(s->material_param_slots[m], 1)})
+            sampled = sampled || (t >= 0 && !s->textures[t].default_sampler());
     if (textured)
         for (const agpt::HostPrim& hp : s->prims)
             if (hp.type != AGPT_PRIM_MESH && hp.material >= 0 && (s->material_texture[hp.material] >= 0 || s->material_param_slots[hp.material] != 0))
@@ -659,7 +687,8 @@ int agpt_scene_commit(agpt_scene* s) {
                 table[m] = (int32_t)(s->textures.size() + own_texels.size());
                 own_texels.push_back(std::vector<float4>(1, s->colors[m]));
             }
-        if (mapped) table.insert(table.end(), s->material_param_slots.begin(), s->material_param_slots.end());
+        if (mapped || sampled)   // (the SAMPLED kernels are MAPPED ones: they read the slots, all 0 in a scene without maps)
+            table.insert(table.end(), s->material_param_slots.begin(), s->material_param_slots.end());
         textures.resize(s->textures.size() + own_texels.size());
         s->d_texels.resize(textures.size());
         for (size_t i = 0; i < textures.size(); i++) {
@@ -668,6 +697,10 @@ int agpt_scene_commit(agpt_scene* s) {
             textures[i].texels = s->d_texels[i].p;
             textures[i].width = own ? 1 : s->textures[i].width;
             textures[i].height = own ? 1 : s->textures[i].height;
+            if (sampled && !own) {   // (only the SAMPLED kernels decode the size words, agpt_scene.h: DevTexture)
+                textures[i].width = texture_size_pack(s->textures[i].width, s->textures[i].wrap_u, s->textures[i].filter);
+                textures[i].height = texture_size_pack(s->textures[i].height, s->textures[i].wrap_v, 0);
+            }
         }
         if ((rc = upload(s->d_tri_uv, flat.tri_uv, st))) return rc;
         if ((rc = upload(s->d_textures, textures, st))) return rc;
@@ -676,6 +709,7 @@ int agpt_scene_commit(agpt_scene* s) {
     HIP_TRY(hipStreamSynchronize(st));
     s->textured = textured;
     s->mapped = mapped;
+    s->sampled = sampled;
     s->dev.tri_uv = textured ? s->d_tri_uv.p : nullptr;
     s->dev.textures = textured ? s->d_textures.p : nullptr;
     s->dev.material_texture = textured ? s->d_material_texture.p : nullptr;
@@ -939,6 +973,7 @@ static int begin_wavefront(agpt_ctx* c, const agpt_scene* s, int enable_counters
     run.shade.fast = s->shading_arith == AGPT_SHADING_FAST;   // agpt_scene_set_shading_arith
     run.shade.textured = s->textured;                         // a material of the scene has a texture
     run.shade.mapped = s->mapped;                             // ... a roughness / metallic map
+    run.shade.sampled = s->sampled;                           // ... a texture with a sampler of its own
     run.shade.lds_tables = shade_tables_fit_lds(s->dev);
     run.shade.env = !s->envs.empty();                         // an InfiniteAreaLight is present
     c->tev_used = 0;
@@ -1450,7 +1485,7 @@ int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* alb
     HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
     agpt::launch_feature_rays(c->stream, s->dev, rcn, c->ext_o.p, c->ext_d.p);
     trace_rays(c, s->dev, NP, false, 0);
-    agpt::launch_features(c->stream, s->dev, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
+    agpt::launch_features(c->stream, s->dev, s->sampled, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
                           (float4*)normal_depth_dev);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());

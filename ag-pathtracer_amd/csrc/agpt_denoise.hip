@@ -56,8 +56,9 @@ k_feature_rays(DevCamera c, RenderConsts rc, float4* __restrict__ ray_o, float4*
 // albedo = (colour, flag): flag 1 a primitive with a material, 2 an emitter (null material), 0 a miss (colour 1 for both);
 // normal_depth = (Surface::ns -- spheres: (p - c) / r --, t), zero on a miss
 // TEXTURED (scenes with a textured material): on a mesh hit the colour of a textured material is the texel k_shade_textured shades
-// that hit with (triangle_uv + texture_value, agpt_shade.h)
-template <bool TEXTURED>
+// that hit with (triangle_uv + texture_value, agpt_shade.h); SAMPLED (scenes in which a material names a texture with a non-default
+// sampler): the filtered colour k_shade_sampled shades it with (texture_address / texture_load / texture_blend)
+template <bool TEXTURED, bool SAMPLED = false>
 __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderConsts& rc, const float4* __restrict__ colors,
                                                const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
                                                const float4* __restrict__ ray_d, float4* __restrict__ albedo,
@@ -100,7 +101,16 @@ __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderC
                 if (tex >= 0 && !(h.id & AGPT_HIT_SPHERE)) {
                     float tu, tv;
                     triangle_uv(sc.tri_uv[2 * (size_t)h.id], sc.tri_uv[2 * (size_t)h.id + 1], h.b1, h.b2, &tu, &tv);
-                    const v3 c = texture_value(sc.textures[tex], tu, tv);
+                    v3 c;
+                    if constexpr (SAMPLED) {
+                        TextureAddress ta;
+                        TextureTaps k;
+                        texture_address(sc.textures[tex], tu, tv, ta);
+                        texture_load(ta, k);
+                        c = texture_blend(ta, k);
+                    } else {
+                        c = texture_value(sc.textures[tex], tu, tv);
+                    }
                     a.x = c.x; a.y = c.y; a.z = c.z;
                 }
             }
@@ -121,6 +131,12 @@ k_features_textured(DevScene sc, RenderConsts rc, const float4* __restrict__ col
                     const float4* __restrict__ ray_o, const float4* __restrict__ ray_d, float4* __restrict__ albedo,
                     float4* __restrict__ normal_depth) {
     features_pixel<true>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+}
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_features_sampled(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits,
+                   const float4* __restrict__ ray_o, const float4* __restrict__ ray_d, float4* __restrict__ albedo,
+                   float4* __restrict__ normal_depth) {
+    features_pixel<true, true>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
 
 // state = (c.rgb, v): c = accum.rgb / n, v = the variance of the mean luminance from agpt_render_adaptive's estimate
@@ -229,9 +245,12 @@ static inline dim3 blocks_for(uint64_t n) { return dim3((unsigned)((n + AGPT_BLO
 void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d) {
     hipLaunchKernelGGL(k_feature_rays, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc.cam, rc, ray_o, ray_d);
 }
-void launch_features(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const float4* colors, const DevHit* hits,
+void launch_features(hipStream_t stream, const DevScene& sc, bool sampled, const RenderConsts& rc, const float4* colors, const DevHit* hits,
                      const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth) {
-    if (sc.tri_uv)   // the scene has a textured material
+    if (sampled)     // a material names a texture with a sampler of its own (which implies the next case)
+        hipLaunchKernelGGL(k_features_sampled, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
+                           normal_depth);
+    else if (sc.tri_uv)   // the scene has a textured material
         hipLaunchKernelGGL(k_features_textured, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
                            normal_depth);
     else

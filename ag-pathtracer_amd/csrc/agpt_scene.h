@@ -21,7 +21,8 @@
 //   textures   DevTexture[X], material_texture int32[M] (texture id of a material, -1 = none): kept beside DevMaterial so that the
 //                           material table the untextured kernels stage in LDS stays what it was.  In a scene with roughness /
 //                           metallic maps the table has a second half, material_texture[M + m] = the packed parameter slots of
-//                           material m (param_slots_pack below), which only the MAPPED kernel variants read
+//                           material m (param_slots_pack below), which only the MAPPED kernel variants read (a SAMPLED scene
+//                           -- see DevTexture -- always has it: its kernels are the MAPPED ones with a filtering lookup)
 //   prims      DevPrim[P]   Scene::primitives in insertion order (scene.h:5-19 walks them linearly)
 //   materials  DevMaterial[M], lights DevLight[L]
 #pragma once
@@ -144,11 +145,24 @@ AGPT_HD int param_slot_texture(uint32_t slots, int param) { return (int)((slots 
 AGPT_HD int param_slot_channel(uint32_t slots, int param) { return (int)(slots >> (16 * param) & 3u); }
 
 // An image texture (HDRTexture, texture.h:41-84): texels row-major, row 0 = top, one float4 (rgb, -) each so that a lookup is
-// one 16-byte gather
+// one 16-byte gather.  In a SAMPLED scene (a texture that a material names has a sampler other than nearest / repeat / repeat,
+// agpt_scene_set_texture_sampler) the two size words also carry the sampler: width * height <= 2^28 leaves bits 29..31 of both
+// free, so the record stays one 16-B load and costs the shading kernels no LDS -- width: bit 31 filter, bits 29..30 wrap_u;
+// height: bits 29..30 wrap_v.  Every other scene has the plain sizes there, which is what the TEXTURED and MAPPED kernels read.
 struct DevTexture {
     const float4* texels;
     int32_t width, height;
 };
+#define AGPT_TEXTURE_SIZE_MASK 0x1FFFFFFFu
+#define AGPT_TEXTURE_WRAP_REPEAT 0u   // (agpt.h: AGPT_WRAP_*, AGPT_FILTER_*)
+#define AGPT_TEXTURE_WRAP_CLAMP 1u
+#define AGPT_TEXTURE_WRAP_MIRROR 2u
+AGPT_HD int32_t texture_size_pack(int size, int wrap, int filter) {
+    return (int32_t)((uint32_t)size | (uint32_t)wrap << 29 | (uint32_t)filter << 31);
+}
+AGPT_HD int texture_size(int32_t word) { return (int)((uint32_t)word & AGPT_TEXTURE_SIZE_MASK); }
+AGPT_HD uint32_t texture_wrap_mode(int32_t word) { return (uint32_t)word >> 29 & 3u; }
+AGPT_HD bool texture_bilinear(const DevTexture& t) { return t.width < 0; }
 
 struct DevLight {
     int32_t type;

@@ -537,6 +537,83 @@ __device__ __forceinline__ v3 texture_value(const DevTexture& t, float u, float 
     const float4 p = t.texels[(size_t)y * t.width + x];
     return V3(p.x, p.y, p.z);
 }
+// ---- sampled lookups (agpt.h: agpt_scene_set_texture_sampler; only the SAMPLED kernel variants) ------------------------------
+// One axis of a lookup at position s = u * n - .5f: the wrapped coordinates of the two taps floor(s), floor(s) + 1 and the weight of
+// the second.  One Mod per axis: the second tap is the first one's wrapped coordinate stepped inside the period (n, MIRROR: 2n),
+// which is Mod(x0 + 1, period) without forming x0 + 1 -- x0 may be INT_MAX, where the conversion saturated (s beyond the int range
+// or infinite: the weight is 0 there, s - floorf(s) being 0 or NaN).  CLAMP forms x0 + 1 only below n - 1.
+__device__ __forceinline__ void texture_axis(float s, int n, uint32_t mode, bool bilinear, int* i0, int* i1, float* f) {
+    const float fl = floorf(s);
+    const int x0 = (int)fl;
+    *f = (bilinear && fabsf(fl) < 2147483648.f) ? s - fl : 0.f;
+    const int period = mode == AGPT_TEXTURE_WRAP_MIRROR ? 2 * n : n;
+    int m0 = env_mod(x0, period);
+    int m1 = m0 + 1 == period ? 0 : m0 + 1;
+    if (mode == AGPT_TEXTURE_WRAP_MIRROR) {
+        m0 = m0 < n ? m0 : 2 * n - 1 - m0;
+        m1 = m1 < n ? m1 : 2 * n - 1 - m1;
+    }
+    if (mode == AGPT_TEXTURE_WRAP_CLAMP) {
+        m0 = min(max(x0, 0), n - 1);
+        m1 = x0 < n - 1 ? max(x0 + 1, 0) : n - 1;
+    }
+    *i0 = m0;
+    *i1 = m1;
+}
+// A lookup in three steps, so that a vertex can do the arithmetic of ALL its textures first, then issue ALL their gathers back to
+// back, and only then wait: texture_address (the wrap / weight arithmetic, two integer divisions per texture: no memory access),
+// texture_load (one tap of a NEAREST texture, four of a BILINEAR one), texture_blend.  The texel pointer comes out of a loaded
+// record, which makes it a generic pointer and its loads flat_load: those count against both memory counters, and the compiler then
+// drains every outstanding load (s_waitcnt vmcnt(0)) before the next thing it waits for.  Texels live in global memory, so the
+// pointer is given that address space: the taps are global_load, counted in order, and nothing waits before the first blend.
+// (a built-in vector, not float4: a class type cannot be read through an address-space pointer in the host pass of this header.  Three
+// lanes in a 16-byte slot: a tap is one global_load_dwordx3 -- a fourth register that nothing reads would be handed out again as a
+// temporary of the next address computation, and that write would have to wait for the load.)
+typedef float Texel __attribute__((ext_vector_type(3)));
+static_assert(sizeof(Texel) == sizeof(float4), "a texel slot is 16 bytes (agpt_scene.h: DevTexture)");
+typedef const __attribute__((address_space(1))) Texel* TexelPtr;
+struct TextureAddress {
+    TexelPtr texels;
+    uint32_t i00, i10, i01, i11;   // texel indices of (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1)
+    float fx, fy;
+    bool bilinear;
+};
+struct TextureTaps {
+    Texel c00, c10, c01, c11;
+};
+__device__ __forceinline__ void texture_address(const DevTexture& t, float u, float v, TextureAddress& a) {
+    const int w = texture_size(t.width), h = texture_size(t.height);
+    a.texels = (TexelPtr)t.texels;
+    a.bilinear = texture_bilinear(t);
+    int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+    a.fx = a.fy = 0.f;
+    if (isfinite(u) && isfinite(v)) {
+        texture_axis(u * w - .5f, w, texture_wrap_mode(t.width), a.bilinear, &x0, &x1, &a.fx);
+        texture_axis(v * h - .5f, h, texture_wrap_mode(t.height), a.bilinear, &y0, &y1, &a.fy);
+    }
+    a.i00 = (uint32_t)(y0 * w + x0);   // (width * height <= 2^28)
+    a.i10 = (uint32_t)(y0 * w + x1);
+    a.i01 = (uint32_t)(y1 * w + x0);
+    a.i11 = (uint32_t)(y1 * w + x1);
+}
+__device__ __forceinline__ void texture_load(const TextureAddress& a, TextureTaps& o) {
+    o.c00 = a.texels[a.i00];
+    if (a.bilinear) {
+        o.c10 = a.texels[a.i10];
+        o.c01 = a.texels[a.i01];
+        o.c11 = a.texels[a.i11];
+    }
+}
+// c = top + fy * (bot - top) of top = c00 + fx * (c10 - c00), bot = c01 + fx * (c11 - c01), per channel, every operation rounded on
+// its own (the unit is compiled without contraction): equal taps give the tap, whatever the weights.  NEAREST: the tap itself.
+__device__ __forceinline__ v3 texture_blend(const TextureAddress& a, const TextureTaps& k) {
+    const v3 c00 = V3(k.c00.x, k.c00.y, k.c00.z);
+    if (!a.bilinear) return c00;
+    const v3 c10 = V3(k.c10.x, k.c10.y, k.c10.z), c01 = V3(k.c01.x, k.c01.y, k.c01.z), c11 = V3(k.c11.x, k.c11.y, k.c11.z);
+    const v3 top = c00 + a.fx * (c10 - c00);
+    const v3 bot = c01 + a.fx * (c11 - c01);
+    return top + a.fy * (bot - top);
+}
 __device__ __forceinline__ float spherical_theta(v3 v) { return cr_acosf(tclampf(v.z, -1.f, 1.f)); }  // common.h:158-160
 __device__ __forceinline__ float spherical_phi(v3 v) {                                                // common.h:162-165
     float p = cr_atan2f(v.y, v.x);

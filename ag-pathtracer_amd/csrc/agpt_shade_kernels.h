@@ -20,10 +20,18 @@
 // and metallic at a mesh hit come from image textures too (agpt_scene.h: param_slots_pack), so the whole Disney constructor runs per
 // hit -- as k_shade_mapped / k_shade_mapped_fast, for scenes in which a material has such a map; it leaves the code of the other four
 // units alone in the same way.
+// AGPT_SHADE_TEXTURED 3 (agpt_shade_kernels_sampled.hip, agpt_shade_kernels_sampled_fast.hip) is the SAMPLED variant on top of that -- the MAPPED
+// kernel whose lookups honour each texture's sampler (agpt_scene.h: DevTexture; bilinear filtering, clamp and mirror wrap) -- as
+// k_shade_sampled / k_shade_sampled_fast, for scenes in which a material names a texture with a non-default sampler.  One level covers
+// the colour slot and both maps; the other six units are left alone in the same way.
 #ifndef AGPT_SHADE_TEXTURED
 #define AGPT_SHADE_TEXTURED 0
 #endif
-#if AGPT_SHADE_TEXTURED == 2 && AGPT_SHADE_FAST
+#if AGPT_SHADE_TEXTURED == 3 && AGPT_SHADE_FAST
+#define AGPT_SHADE_KNAME(n) n##_sampled_fast
+#elif AGPT_SHADE_TEXTURED == 3
+#define AGPT_SHADE_KNAME(n) n##_sampled
+#elif AGPT_SHADE_TEXTURED == 2 && AGPT_SHADE_FAST
 #define AGPT_SHADE_KNAME(n) n##_mapped_fast
 #elif AGPT_SHADE_TEXTURED == 2
 #define AGPT_SHADE_KNAME(n) n##_mapped
@@ -99,7 +107,10 @@ __device__ __forceinline__ v3 pending_light_sample(const DevScene& sc, const Ren
 // MAPPED: see AGPT_SHADE_TEXTURED 2 above.  Up to three texels per vertex (colour, roughness, metallic), one gather per DISTINCT
 // texture -- slots that name the same image, as glTF's metallic-roughness image does, share its texel -- all issued before
 // material_set_disney rebuilds the register copy, lobe set included.
-template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0), bool MAPPED = (AGPT_SHADE_TEXTURED == 2)>
+// SAMPLED: see AGPT_SHADE_TEXTURED 3 above.  MAPPED with texture_address / texture_load / texture_blend (agpt_shade.h) in texture_value's place: one tap of a NEAREST
+// texture, four of a BILINEAR one, the taps of every distinct texture issued before the first blend (up to twelve 16-B gathers in
+// flight behind the material lookup instead of three round trips of four).
+template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0), bool MAPPED = (AGPT_SHADE_TEXTURED >= 2), bool SAMPLED = (AGPT_SHADE_TEXTURED == 3)>
 __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t pid SCK_PARAMS) {
     uint32_t bits = 0;
     // Every per-path record is fetched up front, unconditionally: the loads then overlap in one memory round trip instead
@@ -197,10 +208,28 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                     const DevTexture ct = sc.textures[tex], rt = sc.textures[rtex >= 0 ? rtex : 0], mx = sc.textures[mtex >= 0 ? mtex : 0];
                     float tu, tv;
                     triangle_uv(uv01, uv2, h.b1, h.b2, &tu, &tv);
-                    const v3 c = texture_value(ct, tu, tv);
-                    v3 rv = c, mv = c;
-                    if (rtex >= 0 && rtex != tex) rv = texture_value(rt, tu, tv);
-                    if (mtex >= 0 && mtex != tex) mv = mtex == rtex ? rv : texture_value(mx, tu, tv);
+                    v3 c, rv, mv;
+                    if constexpr (SAMPLED) {
+                        const bool r_own = rtex >= 0 && rtex != tex, m_own = mtex >= 0 && mtex != tex && mtex != rtex;
+                        // all the arithmetic (a texture that is not fetched gets the colour's record: no branch around a division), then
+                        // all the gathers, then the blends
+                        TextureAddress ca, ra, ma;
+                        TextureTaps ck, rk, mk;
+                        texture_address(ct, tu, tv, ca);
+                        texture_address(r_own ? rt : ct, tu, tv, ra);
+                        texture_address(m_own ? mx : ct, tu, tv, ma);
+                        texture_load(ca, ck);
+                        if (r_own) texture_load(ra, rk);
+                        if (m_own) texture_load(ma, mk);
+                        c = texture_blend(ca, ck);
+                        rv = r_own ? texture_blend(ra, rk) : c;
+                        mv = m_own ? texture_blend(ma, mk) : (mtex == rtex ? rv : c);
+                    } else {
+                        c = texture_value(ct, tu, tv);
+                        rv = c, mv = c;
+                        if (rtex >= 0 && rtex != tex) rv = texture_value(rt, tu, tv);
+                        if (mtex >= 0 && mtex != tex) mv = mtex == rtex ? rv : texture_value(mx, tu, tv);
+                    }
                     if (slots)   // (Disney: the only type agpt_scene_set_material_param_texture accepts)
                         material_set_disney(mt, c, rtex >= 0 ? comp(rv, param_slot_channel(slots, 0)) : mc.roughness,
                                             mtex >= 0 ? comp(mv, param_slot_channel(slots, 1)) : mc.metallic);
@@ -505,8 +534,9 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
     __shared__ DevMaterial s_tab_materials[LDS_TABLES ? AGPT_SHADE_LDS_MATERIALS : 1];
     __shared__ DevLight s_tab_lights[LDS_TABLES ? AGPT_SHADE_LDS_LIGHTS : 1];
 #if AGPT_SHADE_TEXTURED
-    // 512 B beside the 9.5 KB of materials; MAPPED: both halves of the table, 1 KB (40,960 B per block in all: still four blocks per CU)
-    constexpr int n_tab_halves = AGPT_SHADE_TEXTURED == 2 ? 2 : 1;
+    // 512 B beside the 9.5 KB of materials; MAPPED, SAMPLED: both halves of the table, 1 KB (40,960 B per block in all: still four blocks
+    // per CU; the sampler state rides in the texture records, agpt_scene.h)
+    constexpr int n_tab_halves = AGPT_SHADE_TEXTURED >= 2 ? 2 : 1;
     __shared__ int32_t s_tab_material_texture[LDS_TABLES ? n_tab_halves * AGPT_SHADE_LDS_MATERIALS : 1];
 #endif
     // (a launch over a short queue: one wave per 256-path tile is all it can use -- the rest of the grid leaves before setting up)
@@ -680,8 +710,9 @@ namespace agpt {
 using ShadeLaunch = void(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
                          const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
 using ResolveLaunch = void(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin);
-ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast, launch_shade_mapped, launch_shade_mapped_fast;
-ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED and MAPPED units have none, see k_resolve_pending)
+ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast, launch_shade_mapped, launch_shade_mapped_fast,
+    launch_shade_sampled, launch_shade_sampled_fast;
+ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED, MAPPED and SAMPLED units have none, see k_resolve_pending)
 
 void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
                                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters,

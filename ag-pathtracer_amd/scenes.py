@@ -95,6 +95,10 @@ class SceneDesc:
     def set_material_param_texture(self, material, param, texture, channel=0):
         self.ops.append(("material_param_texture", int(material), int(param), int(texture), int(channel)))
 
+    def set_texture_sampler(self, texture, filter=0, wrap_u=0, wrap_v=0):
+        """binding.FILTER_* / WRAP_* of a texture, for every slot that names it (default: nearest, repeat, repeat)"""
+        self.ops.append(("texture_sampler", int(texture), int(filter), int(wrap_u), int(wrap_v)))
+
     def set_camera(self, lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
         self.camera = (np.asarray(lookfrom, F).copy(), np.asarray(lookat, F).copy(), np.asarray(vup, F).copy(),
                        F(aspect_ratio), float(vfov), float(aperture))
@@ -123,6 +127,8 @@ class SceneDesc:
                 target.set_material_texture(op[1], op[2])
             elif k == "material_param_texture":
                 target.set_material_param_texture(op[1], op[2], op[3], op[4])
+            elif k == "texture_sampler":
+                target.set_texture_sampler(op[1], op[2], op[3], op[4])
         if self.camera is not None:
             target.set_camera(*self.camera)
         if hasattr(target, "commit"):

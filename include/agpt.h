@@ -196,6 +196,32 @@ int agpt_scene_set_material_texture(agpt_scene*, int material, int texture);
  * AGPT_ERR_LIMIT for a texture id above 16382 (a material's two slots are packed into one 32-bit word). */
 enum { AGPT_PARAM_ROUGHNESS = 0, AGPT_PARAM_METALLIC = 1 };
 int agpt_scene_set_material_param_texture(agpt_scene*, int material, int param, int texture, int channel);
+/* ---- filtering and wrap modes of image textures ------------------------------------------------------------------
+ * The sampler of `texture`: how value(u, v) above is formed from its texels.  It belongs to the texture (as in glTF) and holds for
+ * every slot that names it -- the colour slot, AGPT_PARAM_ROUGHNESS and AGPT_PARAM_METALLIC.  The default, (AGPT_FILTER_NEAREST,
+ * AGPT_WRAP_REPEAT, AGPT_WRAP_REPEAT), is value(u, v) as described above.  Before agpt_scene_commit.  All fp32, every operation rounded
+ * on its own, nothing contracted into an fma:
+ *   position        s = u * width - .5f, t = v * height - .5f (the expressions above).
+ *   wrap(x, n)      of an integer coordinate x on an axis of n texels -- REPEAT: Mod(x, n); CLAMP: min(max(x, 0), n - 1); MIRROR:
+ *                   m = Mod(x, 2n), then m < n ? m : 2n - 1 - m.  wrap_u holds for x, wrap_v for y.
+ *   NEAREST         the texel (wrap_u((int)floorf(s)), wrap_v((int)floorf(t))).
+ *   BILINEAR        x0 = (int)floorf(s), fx = s - floorf(s) (exact); y0, fy likewise.  The four taps are c00 = (wrap_u(x0), wrap_v(y0)),
+ *                   c10 = (wrap_u(x0 + 1), wrap_v(y0)), c01 = (wrap_u(x0), wrap_v(y0 + 1)), c11 = (wrap_u(x0 + 1), wrap_v(y0 + 1)); x0 + 1
+ *                   is formed without integer overflow, and where the float-to-int conversion saturated (|floorf(s)| >= 2^31 or s not
+ *                   finite) fx is 0.  Per channel top = c00 + fx * (c10 - c00), bot = c01 + fx * (c11 - c01), c = top + fy * (bot - top)
+ *                   -- this form, not (1 - f) * a + f * b: equal taps return the tap exactly, whatever the weights.
+ *   non-finite uv   a non-finite u or v reads texel (0, 0), as above.
+ *   what it feeds   exactly what the nearest texel feeds above: the colour goes through what agpt_scene_add_material derives from
+ *                   `color`; with a map, colour, roughness and metallic go through the DisneyMaterial constructor.  A map's channel is
+ *                   taken after the blend.
+ * The texel choice and the blend decide what is read and stay exact under AGPT_SHADING_FAST, like the uv interpolation.
+ * agpt_render_features writes the filtered colour as the albedo; agpt_kat_bsdf_eval / _sample keep the constants.  Scenes in which no
+ * material names a texture with a non-default sampler run the kernels they ran before samplers existed.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error) for a NULL scene, an unknown texture id, an unknown filter or wrap value, or a scene
+ * that is already committed. */
+enum { AGPT_FILTER_NEAREST = 0, AGPT_FILTER_BILINEAR = 1 };
+enum { AGPT_WRAP_REPEAT = 0, AGPT_WRAP_CLAMP = 1, AGPT_WRAP_MIRROR = 2 };
+int agpt_scene_set_texture_sampler(agpt_scene*, int texture, int filter, int wrap_u, int wrap_v);
 /* scene->camera = desc; Camera(desc) (camera.h:29-56,77-90) */
 int agpt_scene_set_camera(agpt_scene*, const agpt_camera_desc*);
 /* flatten + upload to HBM; must be called after the last add_* and before render/intersect */

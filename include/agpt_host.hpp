@@ -192,6 +192,11 @@ public:
     void SetMaterialTexture(int material, int texture) {
         check(agpt_scene_set_material_texture(h_, material, texture), "agpt_scene_set_material_texture");
     }
+    // how `texture` is read in every slot that names it: AGPT_FILTER_NEAREST / _BILINEAR, each axis AGPT_WRAP_REPEAT / _CLAMP / _MIRROR
+    // (the default: nearest, repeat, repeat = Texture::value)
+    void SetTextureSampler(int texture, int filter, int wrap_u, int wrap_v) {
+        check(agpt_scene_set_texture_sampler(h_, texture, filter, wrap_u, wrap_v), "agpt_scene_set_texture_sampler");
+    }
     // a Disney material's roughness (AGPT_PARAM_ROUGHNESS) / metallic (AGPT_PARAM_METALLIC) at a mesh hit becomes channel `channel`
     // (0 = r, 1 = g, 2 = b) of Texture::value(u, v) of `texture` (-1: its constant again), and the material what DisneyMaterial::Make
     // builds from it

@@ -36,6 +36,9 @@ def main():
                     help="denoise the render (agpt_render_features + agpt_denoise, ITER a-trous passes, default 5) before the resolve; "
                          "implies the adaptive entry point -- uniform at --spp when --adaptive is not given")
     ap.add_argument("--features-png", default=None, metavar="PREFIX", help="write PREFIX_albedo.png and PREFIX_normal.png (first-hit features)")
+    ap.add_argument("--filter", default="nearest", choices=["nearest", "bilinear"],
+                    help="scenes textured / mapped: how every texture is read (agpt_scene_set_texture_sampler)")
+    ap.add_argument("--wrap", default="repeat", choices=["repeat", "clamp", "mirror"], help="scenes textured / mapped: wrap mode of both axes")
     a = ap.parse_args()
     W, H = a.width, a.height
     aspect = W / float(H)
@@ -43,6 +46,12 @@ def main():
             "c3": lambda: ag.scenes.scene_c3(aspect=aspect), "c5": lambda: ag.scenes.scene_c5(aspect=aspect),
             "simple": lambda: ag.scenes.scene_simple_test(), "textured": lambda: ag.scenes.scene_textured(), "mapped": lambda: ag.scenes.scene_mapped(),
             "heightfield": lambda: ag.scenes.scene_heightfield(361, True, W, H)}[a.scene]()
+    if (a.filter, a.wrap) != ("nearest", "repeat"):
+        if a.scene not in ("textured", "mapped"):
+            ap.error("--filter / --wrap apply to the scenes textured and mapped")
+        wrap = {"repeat": ag.WRAP_REPEAT, "clamp": ag.WRAP_CLAMP, "mirror": ag.WRAP_MIRROR}[a.wrap]
+        for t in range(desc.n_textures):
+            desc.set_texture_sampler(t, ag.FILTER_BILINEAR if a.filter == "bilinear" else ag.FILTER_NEAREST, wrap, wrap)
     ctx = ag.Context(0)
     t0 = time.time()
     scene = ag.Scene(ctx)

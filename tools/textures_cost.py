@@ -1,10 +1,12 @@
 """Developer measurement: what image textures cost.  C3 at 1080p / 64 spp untextured (k_shade) against the same scene with every
 material pointed at a 256x256 texture (k_shade_textured) and, with --mapped, against that scene with every Disney material also
-pointed at one 256x256 image for its roughness (g) and its metallic weight (b) (k_shade_mapped); the scenes live in one process, each
+pointed at one 256x256 image for its roughness (g) and its metallic weight (b) (k_shade_mapped); with --sampled the mapped scene
+with every texture read BILINEAR (k_shade_sampled) against the same scene with the default NEAREST samplers (k_shade_mapped), into
+profiles/texture_filter_c3.json by default; the scenes live in one process, each
 rendered --reps times, alternating, after a warm-up.  Per variant: step ms, trace ms, non-trace ms, the agpt_stats totals and non-trace ns per shaded vertex (medians).
-    python tools/textures_cost.py [--out profiles/textures_c3.json] [--mapped] [--reps 3] [--shading exact|fast] [--kernel-trace CSV]
+    python tools/textures_cost.py [--out profiles/textures_c3.json] [--mapped | --sampled] [--reps 3] [--shading exact|fast] [--kernel-trace CSV]
 (--reps 1 --no-warmup: exactly one render per variant, the run for rocprofv3 --kernel-trace --stats; --kernel-trace adds that
-run's per-kernel times to the JSON)"""
+run's per-kernel times to the JSON, --kernel-trace-run JSON -- what that run wrote with --out -- its command and library hash)"""
 import argparse
 import csv
 import json
@@ -47,6 +49,14 @@ def mapped_c3(desc, size=256, seed=9):
     return desc
 
 
+def sampled_c3(desc, size=256):
+    """mapped_c3 with every texture BILINEAR (repeat on both axes: the same texels are in reach, four of them per lookup)"""
+    desc = mapped_c3(desc, size)
+    for t in range(desc.n_textures):
+        desc.set_texture_sampler(t, ag.FILTER_BILINEAR, ag.WRAP_REPEAT, ag.WRAP_REPEAT)
+    return desc
+
+
 def library_build_id():
     """sha256 of the loaded library file: which kernel build the numbers belong to"""
     import hashlib
@@ -56,21 +66,29 @@ def library_build_id():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mapped", action="store_true", help="add the leg with roughness / metallic maps (k_shade_mapped)")
+    ap.add_argument("--sampled", action="store_true", help="mapped with NEAREST (k_shade_mapped) against mapped with BILINEAR (k_shade_sampled)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--shading", default="exact", choices=["exact", "fast"])
     ap.add_argument("--no-warmup", action="store_true")
     ap.add_argument("--kernel-trace", default=None, metavar="CSV", help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run of this tool")
+    ap.add_argument("--kernel-trace-run", default=None, metavar="JSON",
+                    help="the JSON that the traced run itself wrote (--reps 1 --no-warmup --out JSON under rocprofv3): its command and its "
+                         "library sha256 go into this run's JSON beside the kernel times, and the two libraries must be the same build")
     a = ap.parse_args()
+    if a.sampled and a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "texture_filter_c3.json")
     W, H, spp = 1920, 1080, 64
     ctx = ag.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     scenes = {}
-    for name in ("untextured", "textured") + (("mapped",) if a.mapped else ()):
+    for name in ("mapped", "sampled") if a.sampled else ("untextured", "textured") + (("mapped",) if a.mapped else ()):
         d = ag.scenes.scene_c3(aspect=W / float(H))
         if name == "textured":
             d = textured_c3(d)
         elif name == "mapped":
             d = mapped_c3(d)
+        elif name == "sampled":
+            d = sampled_c3(d)
         scenes[name] = d.instantiate(ag.Scene(ctx))
         scenes[name].set_shading_arith(a.shading)
     film = torch.zeros((H, W, 4), device="cuda")
@@ -101,15 +119,24 @@ def main():
         print("%-10s step %7.1f ms  trace %7.1f  non-trace %6.1f  shaded %6.1f M  %.3f ns/vertex" % (
             name, med["step_ms"], med["trace_ms"], med["non_trace_ms"], rs[0]["shaded_vertices"] / 1e6,
             med["non_trace_ns_per_shaded_vertex"]), flush=True)
-    res["non_trace_ratio"] = res["textured"]["non_trace_ms"] / res["untextured"]["non_trace_ms"]
-    res["step_ratio"] = res["textured"]["step_ms"] / res["untextured"]["step_ms"]
-    if a.mapped:
+    if a.sampled:
+        res["sampled_over_mapped"] = {k: res["sampled"][k] / res["mapped"][k] for k in ("step_ms", "non_trace_ms")}
+    else:
+        res["non_trace_ratio"] = res["textured"]["non_trace_ms"] / res["untextured"]["non_trace_ms"]
+        res["step_ratio"] = res["textured"]["step_ms"] / res["untextured"]["step_ms"]
+    if a.mapped and not a.sampled:
         for base in ("textured", "untextured"):
             res["mapped_over_%s" % base] = {k: res["mapped"][k] / res[base][k] for k in ("step_ms", "non_trace_ms")}
     if a.kernel_trace:
         rows = list(csv.DictReader(open(a.kernel_trace)))
         res["kernel_trace"] = {r["Name"].split("(")[0]: dict(calls=int(r["Calls"]), total_ms=float(r["TotalDurationNs"]) / 1e6)
                                for r in rows if "k_shade" in r["Name"] or "k_resolve_pending" in r["Name"]}
+        if a.kernel_trace_run:   # where the kernel times come from: another run of this tool, under the profiler
+            run = json.load(open(a.kernel_trace_run))
+            if run["library_sha256"] != res["library_sha256"]:
+                sys.exit("--kernel-trace-run: the traced run used another build of the library")
+            res["kernel_trace_run"] = {"command": "rocprofv3 --kernel-trace --stats --output-format csv -- " + run["command"],
+                                       "library_sha256": run["library_sha256"], "stats_csv": a.kernel_trace}
     for s in scenes.values():
         s.close()
     ctx.close()
