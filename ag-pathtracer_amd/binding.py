@@ -35,12 +35,12 @@ EXPORTS = [
     "agpt_last_error", "agpt_version", "agpt_init", "agpt_set_stream", "agpt_destroy", "agpt_scene_create",
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
-    "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
+    "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
-    "agpt_kat_bsdf_sample", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
+    "agpt_kat_bsdf_sample", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
     "agpt_obj_free", "agpt_obj_last_error", "agpt_write_png", "agpt_write_pfm", "agpt_hdr_load", "agpt_hdr_parse", "agpt_hdr_free",
     "agpt_comm_unique_id", "agpt_comm_init", "agpt_comm_destroy", "agpt_gather_tiles", "agpt_deinterleave_tiles",
 ]
@@ -145,6 +145,7 @@ def lib():
     L.agpt_scene_set_material_texture.argtypes = [vp, C.c_int, C.c_int]
     L.agpt_scene_set_material_param_texture.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
     L.agpt_scene_set_texture_sampler.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.agpt_scene_set_material_normal_texture.argtypes = [vp, C.c_int, C.c_int, C.c_float]
     L.agpt_scene_set_camera.argtypes = [vp, C.POINTER(CameraDesc)]
     L.agpt_scene_commit.argtypes = [vp]
     L.agpt_mesh_num_nodes.argtypes = [vp, C.c_int]
@@ -176,6 +177,7 @@ def lib():
     L.agpt_kat_bsdf_eval.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
     L.agpt_kat_bsdf_sample.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp, ip]
     L.agpt_kat_rng.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, fp, C.POINTER(C.c_uint32)]
+    L.agpt_kat_normal_map.argtypes = [vp, C.c_int, fp, fp, fp, C.c_float, fp]
     L.agpt_dbg_li_batch.argtypes = [vp, vp, C.c_int, fp]
     L.agpt_kat_distribution1d.argtypes = [vp, fp, C.c_int, fp, C.c_int, fp, fp, fp, fp]
     L.agpt_obj_load.argtypes = [C.c_char_p, fp, C.c_int, C.POINTER(vp)]
@@ -370,6 +372,19 @@ class Context:
         _check(self.L.agpt_kat_rng(self.h, pixel, wh, sample, seed_base, n, out.ctypes.data_as(C.POINTER(C.c_float)),
                                    C.byref(seed)), "agpt_kat_rng")
         return out, seed.value
+
+    def kat_normal_map(self, ns, ss, rgb, scale=1.0):
+        """agpt_kat_normal_map: the normal-map perturbation alone (agpt_scene_set_material_normal_texture's definition) on n items --
+        shading normals ns[n, 3], tangents ss[n, 3], texels rgb[n, 3] -> the perturbed normals [n, 3]."""
+        ns, pns = _f(np.asarray(ns).reshape(-1, 3))
+        ss, pss = _f(np.asarray(ss).reshape(-1, 3))
+        rgb, prgb = _f(np.asarray(rgb).reshape(-1, 3))
+        if not ns.shape == ss.shape == rgb.shape:
+            raise ValueError("kat_normal_map: ns, ss and rgb must have the same number of items")
+        out = np.zeros_like(ns)
+        _check(self.L.agpt_kat_normal_map(self.h, ns.shape[0], pns, pss, prgb, float(scale), out.ctypes.data_as(C.POINTER(C.c_float))),
+               "agpt_kat_normal_map")
+        return out
 
     def distribution1d(self, func, u):
         """Distribution1D(func) and SampleContinuous(u[i]) (sampling.h:19-52): (cdf[n + 1], funcInt, x[k], pdf[k])."""
@@ -585,6 +600,13 @@ class Scene:
         rebuilt from it as add_material would have built it (texture = -1: the constant again)."""
         _check(self.L.agpt_scene_set_material_param_texture(self.h, int(material), int(param), int(texture), int(channel)),
                "agpt_scene_set_material_param_texture")
+
+    def set_material_normal_texture(self, material, texture, scale=1.0):
+        """agpt_scene_set_material_normal_texture: the material's shading normal at a mesh hit is perturbed by the texture read as a
+        tangent-space normal map -- (2r - 1) * scale along the tangent, (2g - 1) * scale along cross(ns, tangent), 2b - 1 along the
+        normal (texture = -1: no normal map)."""
+        _check(self.L.agpt_scene_set_material_normal_texture(self.h, int(material), int(texture), float(scale)),
+               "agpt_scene_set_material_normal_texture")
 
     def set_texture_sampler(self, texture, filter=FILTER_NEAREST, wrap_u=WRAP_REPEAT, wrap_v=WRAP_REPEAT):
         """agpt_scene_set_texture_sampler: how the texture is read in every slot that names it -- filter FILTER_NEAREST (one texel) or

@@ -17,14 +17,20 @@ SHADE_FAST_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
 # agpt_shade_kernels_textured.hip / _textured_fast.hip -- k_shade for scenes with an image-textured material (AGPT_SHADE_TEXTURED) -- are
 # the same header compiled once more per arithmetic, with the flags of the unit they vary; agpt_shade_kernels_mapped.hip / _mapped_fast.hip
 # -- k_shade for scenes with a roughness / metallic map (AGPT_SHADE_TEXTURED 2) -- likewise, and agpt_shade_kernels_sampled.hip /
-# _sampled_fast.hip -- k_shade for scenes with a filtered, clamped or mirrored texture (AGPT_SHADE_TEXTURED 3).
+# _sampled_fast.hip -- k_shade for scenes with a filtered, clamped or mirrored texture (AGPT_SHADE_TEXTURED 3), and agpt_shade_kernels_normal.hip /
+# _normal_fast.hip -- k_shade for scenes with a normal map (AGPT_SHADE_TEXTURED 4) -- are the same header again, but held to THREE waves per
+# SIMD: the fourth lookup's addresses and taps are live beside the other three's, and at the 128 registers of four waves the kernel spills
+# 10-19 of them; at three waves it needs 143-151 and spills none.  Measured on the all-bilinear mapped C3 with a normal map on every
+# material, interleaved processes on one GPU: non-trace time 114.9 ms at three waves against 118.1 ms at four (FAST: 111.1 against 112.8 ms; profiles/normal_map_c3.json).
+SHADE_NORMAL_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=3"]
 SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_shade_kernels_fast.hip", "agpt_shade_kernels_textured.hip", "agpt_shade_kernels_textured_fast.hip",
            "agpt_shade_kernels_mapped.hip", "agpt_shade_kernels_mapped_fast.hip", "agpt_shade_kernels_sampled.hip", "agpt_shade_kernels_sampled_fast.hip",
-           "agpt_bvh_device.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+           "agpt_shade_kernels_normal.hip", "agpt_shade_kernels_normal_fast.hip", "agpt_bvh_device.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {"agpt_shade_kernels.hip": SHADE_FLAGS, "agpt_shade_kernels_fast.hip": SHADE_FAST_FLAGS,
                 "agpt_shade_kernels_textured.hip": SHADE_FLAGS, "agpt_shade_kernels_textured_fast.hip": SHADE_FAST_FLAGS,
                 "agpt_shade_kernels_mapped.hip": SHADE_FLAGS, "agpt_shade_kernels_mapped_fast.hip": SHADE_FAST_FLAGS,
-                "agpt_shade_kernels_sampled.hip": SHADE_FLAGS, "agpt_shade_kernels_sampled_fast.hip": SHADE_FAST_FLAGS}
+                "agpt_shade_kernels_sampled.hip": SHADE_FLAGS, "agpt_shade_kernels_sampled_fast.hip": SHADE_FAST_FLAGS,
+                "agpt_shade_kernels_normal.hip": SHADE_NORMAL_FLAGS, "agpt_shade_kernels_normal_fast.hip": SHADE_NORMAL_FLAGS}
 HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h", "agpt_shade_arith.h",
            "agpt_host_scene.hpp", "agpt_bvh_device.h", "agpt_adaptive.h", "agpt_denoise.h", os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);

@@ -170,6 +170,10 @@ struct agpt_scene {
     bool textured = false;   // set by agpt_scene_commit: a material has a texture or a map -> the TEXTURED shading / feature kernels
     bool mapped = false;     // set by agpt_scene_commit: a material has a roughness / metallic map -> the MAPPED shading kernels
     bool sampled = false;    // set by agpt_scene_commit: a material names a texture with a non-default sampler -> the SAMPLED kernels
+    // agpt_scene_set_material_normal_texture: per material the texture id (-1 = no normal map) and the scale
+    std::vector<int32_t> material_normal_texture;
+    std::vector<float> material_normal_scale;
+    bool normal = false;     // set by agpt_scene_commit: a material has a normal map -> the NORMAL kernels
     DevBuf<float4> d_tri_uv;
     DevBuf<DevTexture> d_textures;
     DevBuf<int32_t> d_material_texture;
@@ -404,6 +408,8 @@ int agpt_scene_add_material(agpt_scene* s, int type, const float color[3], float
     s->colors.push_back(make_float4(color[0], color[1], color[2], 0.f));
     s->material_texture.push_back(-1);
     s->material_param_slots.push_back(0u);
+    s->material_normal_texture.push_back(-1);
+    s->material_normal_scale.push_back(0.f);
     s->committed = false;
     return (int)s->materials.size() - 1;
 }
@@ -576,6 +582,18 @@ int agpt_scene_set_material_param_texture(agpt_scene* s, int material, int param
     return AGPT_OK;
 }
 
+int agpt_scene_set_material_normal_texture(agpt_scene* s, int material, int texture, float scale) {
+    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_normal_texture: scene is NULL");
+    if (material < 0 || material >= (int)s->materials.size())
+        return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_normal_texture: bad material id");
+    if (texture < -1 || texture >= (int)s->textures.size()) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_normal_texture: bad texture id");
+    if (texture >= 0 && !std::isfinite(scale)) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_normal_texture: scale is not finite");
+    if (s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_set_material_normal_texture: the scene is already committed");
+    s->material_normal_texture[material] = texture;
+    s->material_normal_scale[material] = texture >= 0 ? scale : 0.f;
+    return AGPT_OK;
+}
+
 static_assert(AGPT_WRAP_REPEAT == (int)AGPT_TEXTURE_WRAP_REPEAT && AGPT_WRAP_CLAMP == (int)AGPT_TEXTURE_WRAP_CLAMP &&
                   AGPT_WRAP_MIRROR == (int)AGPT_TEXTURE_WRAP_MIRROR && AGPT_FILTER_NEAREST == 0 && AGPT_FILTER_BILINEAR == 1,
               "texture_size_pack (agpt_scene.h) numbers filters and wrap modes like agpt.h");
@@ -606,10 +624,11 @@ int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
 
 int agpt_scene_commit(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_commit: scene is NULL");
-    bool textured = false, mapped = false;
+    bool textured = false, mapped = false, normal = false;
     for (int32_t t : s->material_texture) textured = textured || t >= 0;
     for (uint32_t slots : s->material_param_slots) mapped = mapped || slots != 0;
-    textured = textured || mapped;   // (the MAPPED kernels are TEXTURED ones: same uv records, same texture table)
+    for (int32_t t : s->material_normal_texture) normal = normal || t >= 0;
+    textured = textured || mapped || normal;   // (the MAPPED and NORMAL kernels are TEXTURED ones: same uv records, same texture table)
     // SAMPLED: a texture that a material names -- in its colour slot or in a parameter slot -- has a sampler of its own
     bool sampled = false;
     for (size_t m = 0; m < s->material_texture.size(); m++)
@@ -617,8 +636,9 @@ int agpt_scene_commit(agpt_scene* s) {
             sampled = sampled || (t >= 0 && !s->textures[t].default_sampler());
     if (textured)
         for (const agpt::HostPrim& hp : s->prims)
-            if (hp.type != AGPT_PRIM_MESH && hp.material >= 0 && (s->material_texture[hp.material] >= 0 || s->material_param_slots[hp.material] != 0))
-                return fail(AGPT_ERR_INVALID, "agpt_scene_commit: a sphere or a plane has a material with a colour texture or a roughness / metallic map "
+            if (hp.type != AGPT_PRIM_MESH && hp.material >= 0 &&
+                (s->material_texture[hp.material] >= 0 || s->material_param_slots[hp.material] != 0 || s->material_normal_texture[hp.material] >= 0))
+                return fail(AGPT_ERR_INVALID, "agpt_scene_commit: a sphere or a plane has a material with a colour texture, a roughness / metallic map or a normal map "
                                               "(textures apply to triangle meshes only)");
     HIP_TRY(hipSetDevice(s->ctx->device));
     agpt::FlatScene flat;
@@ -678,16 +698,16 @@ int agpt_scene_commit(agpt_scene* s) {
     std::vector<DevTexture> textures(textured ? s->textures.size() : 0);
     std::vector<std::vector<float4>> own_texels;   // (kept until the copies below have completed)
     if (textured) {
-        // The device's material_texture table.  A material with a roughness / metallic map and no colour texture gets a 1x1 texture of
+        // The device's material_texture table.  A material with a roughness / metallic map or a normal map and no colour texture gets a 1x1 texture of
         // its constant colour here (any uv reads that texel, and the texel has the constant's bits), so the MAPPED kernels have
         // one source for the colour; with maps the table's second half holds the packed slots (agpt_scene.h).
         std::vector<int32_t> table = s->material_texture;
         for (size_t m = 0; m < table.size(); m++)
-            if (s->material_param_slots[m] != 0 && table[m] < 0) {
+            if ((s->material_param_slots[m] != 0 || s->material_normal_texture[m] >= 0) && table[m] < 0) {
                 table[m] = (int32_t)(s->textures.size() + own_texels.size());
                 own_texels.push_back(std::vector<float4>(1, s->colors[m]));
             }
-        if (mapped || sampled)   // (the SAMPLED kernels are MAPPED ones: they read the slots, all 0 in a scene without maps)
+        if (mapped || sampled || normal)   // (the SAMPLED and NORMAL kernels are MAPPED ones: they read the slots, all 0 in a scene without maps)
             table.insert(table.end(), s->material_param_slots.begin(), s->material_param_slots.end());
         textures.resize(s->textures.size() + own_texels.size());
         s->d_texels.resize(textures.size());
@@ -697,9 +717,22 @@ int agpt_scene_commit(agpt_scene* s) {
             textures[i].texels = s->d_texels[i].p;
             textures[i].width = own ? 1 : s->textures[i].width;
             textures[i].height = own ? 1 : s->textures[i].height;
-            if (sampled && !own) {   // (only the SAMPLED kernels decode the size words, agpt_scene.h: DevTexture)
+            if ((sampled || normal) && !own) {   // (only the SAMPLED and NORMAL kernels decode the size words, agpt_scene.h: DevTexture)
                 textures[i].width = texture_size_pack(s->textures[i].width, s->textures[i].wrap_u, s->textures[i].filter);
                 textures[i].height = texture_size_pack(s->textures[i].height, s->textures[i].wrap_v, 0);
+            }
+        }
+        if (normal) {   // one DevNormalSlot per material behind the two halves (agpt_scene.h)
+            static_assert(sizeof(DevNormalSlot) == 8 * sizeof(int32_t), "a normal slot is two 16-byte loads");
+            const size_t off = (size_t)normal_slots_offset((int)s->materials.size());
+            table.resize(off + 8 * s->materials.size(), 0);
+            for (size_t m = 0; m < s->materials.size(); m++) {
+                const int t = s->material_normal_texture[m];
+                DevNormalSlot slot{};
+                slot.tex = textures[t >= 0 ? t : 0];
+                slot.scale = s->material_normal_scale[m];
+                slot.texture = t;
+                memcpy(&table[off + 8 * m], &slot, sizeof(slot));
             }
         }
         if ((rc = upload(s->d_tri_uv, flat.tri_uv, st))) return rc;
@@ -710,6 +743,7 @@ int agpt_scene_commit(agpt_scene* s) {
     s->textured = textured;
     s->mapped = mapped;
     s->sampled = sampled;
+    s->normal = normal;
     s->dev.tri_uv = textured ? s->d_tri_uv.p : nullptr;
     s->dev.textures = textured ? s->d_textures.p : nullptr;
     s->dev.material_texture = textured ? s->d_material_texture.p : nullptr;
@@ -974,6 +1008,7 @@ static int begin_wavefront(agpt_ctx* c, const agpt_scene* s, int enable_counters
     run.shade.textured = s->textured;                         // a material of the scene has a texture
     run.shade.mapped = s->mapped;                             // ... a roughness / metallic map
     run.shade.sampled = s->sampled;                           // ... a texture with a sampler of its own
+    run.shade.normal = s->normal;                             // ... a normal map
     run.shade.lds_tables = shade_tables_fit_lds(s->dev);
     run.shade.env = !s->envs.empty();                         // an InfiniteAreaLight is present
     c->tev_used = 0;
@@ -1485,7 +1520,7 @@ int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* alb
     HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
     agpt::launch_feature_rays(c->stream, s->dev, rcn, c->ext_o.p, c->ext_d.p);
     trace_rays(c, s->dev, NP, false, 0);
-    agpt::launch_features(c->stream, s->dev, s->sampled, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
+    agpt::launch_features(c->stream, s->dev, s->sampled, s->normal, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
                           (float4*)normal_depth_dev);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());
@@ -1641,6 +1676,24 @@ int agpt_kat_bsdf_sample(agpt_scene* s, int material, int n, const float* wo3, c
     HIP_TRY(hipMemcpy(f3_out, d_f.p, 12 * (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(pdf_out, d_p.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(specular_out, d_s.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return AGPT_OK;
+}
+
+int agpt_kat_normal_map(agpt_ctx* c, int n, const float* ns3, const float* ss3, const float* rgb3, float scale, float* ns_out3) {
+    if (!c || n <= 0 || !ns3 || !ss3 || !rgb3 || !ns_out3) return fail(AGPT_ERR_INVALID, "agpt_kat_normal_map: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> d_ns, d_ss, d_rgb, d_o;
+    HIP_TRY(d_ns.alloc(3 * (size_t)n));
+    HIP_TRY(d_ss.alloc(3 * (size_t)n));
+    HIP_TRY(d_rgb.alloc(3 * (size_t)n));
+    HIP_TRY(d_o.alloc(3 * (size_t)n));
+    HIP_TRY(hipMemcpy(d_ns.p, ns3, 12 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ss.p, ss3, 12 * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_rgb.p, rgb3, 12 * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_kat_normal_map, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_ns.p, d_ss.p, d_rgb.p, scale, d_o.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(ns_out3, d_o.p, 12 * (size_t)n, hipMemcpyDeviceToHost));
     return AGPT_OK;
 }
 

@@ -57,8 +57,10 @@ k_feature_rays(DevCamera c, RenderConsts rc, float4* __restrict__ ray_o, float4*
 // normal_depth = (Surface::ns -- spheres: (p - c) / r --, t), zero on a miss
 // TEXTURED (scenes with a textured material): on a mesh hit the colour of a textured material is the texel k_shade_textured shades
 // that hit with (triangle_uv + texture_value, agpt_shade.h); SAMPLED (scenes in which a material names a texture with a non-default
-// sampler): the filtered colour k_shade_sampled shades it with (texture_address / texture_load / texture_blend)
-template <bool TEXTURED, bool SAMPLED = false>
+// sampler): the filtered colour k_shade_sampled shades it with (texture_address / texture_load / texture_blend); NORMAL (scenes in which
+// a material has a normal map): SAMPLED, and normal_depth.xyz is the shading normal k_shade_normal perturbs at that hit
+// (surface_apply_normal_map, agpt_shade.h) -- the albedo stays the colour
+template <bool TEXTURED, bool SAMPLED = false, bool NORMAL = false>
 __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderConsts& rc, const float4* __restrict__ colors,
                                                const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
                                                const float4* __restrict__ ray_d, float4* __restrict__ albedo,
@@ -102,7 +104,21 @@ __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderC
                     float tu, tv;
                     triangle_uv(sc.tri_uv[2 * (size_t)h.id], sc.tri_uv[2 * (size_t)h.id + 1], h.b1, h.b2, &tu, &tv);
                     v3 c;
-                    if constexpr (SAMPLED) {
+                    if constexpr (NORMAL) {   // (a material with a normal map always has a colour texture, agpt_scene_commit)
+                        // both records, both addresses, all the taps, then the blends -- one round trip, as in k_shade_normal; a normal map
+                        // that is the colour image reuses its blend
+                        const DevNormalSlot slot = normal_slot(sc.material_texture, sc.n_materials, mat);
+                        const DevTexture ct = sc.textures[tex];
+                        const bool n_own = slot.texture >= 0 && slot.texture != tex;
+                        TextureAddress ta, na;
+                        TextureTaps k, nk;
+                        texture_address(ct, tu, tv, ta);
+                        texture_address(n_own ? slot.tex : ct, tu, tv, na);
+                        texture_load(ta, k);
+                        if (n_own) texture_load(na, nk);
+                        c = texture_blend(ta, k);
+                        if (slot.texture >= 0) surface_apply_normal_map(s, n_own ? texture_blend(na, nk) : c, slot.scale);
+                    } else if constexpr (SAMPLED) {
                         TextureAddress ta;
                         TextureTaps k;
                         texture_address(sc.textures[tex], tu, tv, ta);
@@ -137,6 +153,13 @@ k_features_sampled(DevScene sc, RenderConsts rc, const float4* __restrict__ colo
                    const float4* __restrict__ ray_o, const float4* __restrict__ ray_d, float4* __restrict__ albedo,
                    float4* __restrict__ normal_depth) {
     features_pixel<true, true>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+}
+
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_features_normal(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits,
+                  const float4* __restrict__ ray_o, const float4* __restrict__ ray_d, float4* __restrict__ albedo,
+                  float4* __restrict__ normal_depth) {
+    features_pixel<true, true, true>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
 
 // state = (c.rgb, v): c = accum.rgb / n, v = the variance of the mean luminance from agpt_render_adaptive's estimate
@@ -245,9 +268,12 @@ static inline dim3 blocks_for(uint64_t n) { return dim3((unsigned)((n + AGPT_BLO
 void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d) {
     hipLaunchKernelGGL(k_feature_rays, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc.cam, rc, ray_o, ray_d);
 }
-void launch_features(hipStream_t stream, const DevScene& sc, bool sampled, const RenderConsts& rc, const float4* colors, const DevHit* hits,
-                     const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth) {
-    if (sampled)     // a material names a texture with a sampler of its own (which implies the next case)
+void launch_features(hipStream_t stream, const DevScene& sc, bool sampled, bool normal, const RenderConsts& rc, const float4* colors,
+                     const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth) {
+    if (normal)      // a material has a normal map (the lookups are the next case's)
+        hipLaunchKernelGGL(k_features_normal, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
+                           normal_depth);
+    else if (sampled)     // a material names a texture with a sampler of its own (which implies the next case)
         hipLaunchKernelGGL(k_features_sampled, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
                            normal_depth);
     else if (sc.tri_uv)   // the scene has a textured material

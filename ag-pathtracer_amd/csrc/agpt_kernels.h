@@ -1059,6 +1059,11 @@ __global__ void k_kat_bsdf_sample(DevScene sc, int material, int n, const float*
     kat_bsdf_sample_lane(sc, material, n, wo3, u2, wi3o, f3o, pdfo, speco);
 }
 // known-answer kernel: Distribution1D::SampleContinuous (env_sample_continuous) for k draws, one lane each
+// agpt_kat_normal_map: surface_apply_normal_map (agpt_shade.h) alone, one lane per item
+__global__ void k_kat_normal_map(int n, const float* __restrict__ ns3, const float* __restrict__ ss3, const float* __restrict__ rgb3, float scale,
+                                 float* __restrict__ out3) {
+    kat_normal_map_lane(n, ns3, ss3, rgb3, scale, out3);
+}
 __global__ void k_kat_distribution1d(DevEnv e, const float* __restrict__ u, int k, float* __restrict__ x_out, float* __restrict__ pdf_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k) return;

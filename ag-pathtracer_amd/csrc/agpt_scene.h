@@ -23,6 +23,9 @@
 //                           metallic maps the table has a second half, material_texture[M + m] = the packed parameter slots of
 //                           material m (param_slots_pack below), which only the MAPPED kernel variants read (a SAMPLED scene
 //                           -- see DevTexture -- always has it: its kernels are the MAPPED ones with a filtering lookup)
+//                           In a scene with a normal map (agpt_scene_set_material_normal_texture) the table is followed, at the next
+//                           16-byte boundary, by one DevNormalSlot per material, which only the NORMAL kernel variants read -- straight
+//                           from global memory: the halves above are all the LDS a block of k_shade has left
 //   prims      DevPrim[P]   Scene::primitives in insertion order (scene.h:5-19 walks them linearly)
 //   materials  DevMaterial[M], lights DevLight[L]
 #pragma once
@@ -164,6 +167,19 @@ AGPT_HD int texture_size(int32_t word) { return (int)((uint32_t)word & AGPT_TEXT
 AGPT_HD uint32_t texture_wrap_mode(int32_t word) { return (uint32_t)word >> 29 & 3u; }
 AGPT_HD bool texture_bilinear(const DevTexture& t) { return t.width < 0; }
 
+// The normal-map slot of a material (agpt_scene_set_material_normal_texture), in a scene that has one: a copy of the texture's
+// record, so that the lookup costs no load behind the table's (its address depends on the material alone, like the records of the
+// other slots), the scale, and the texture's id (-1: the material has no normal map; `tex` is then some valid record), by which a slot
+// that names the same image shares its taps.  Two 16-byte loads.
+struct DevNormalSlot {
+    DevTexture tex;
+    float scale;
+    int32_t texture;
+    int32_t pad[2];
+};
+// where the slots begin in a material_texture table of n_materials materials (in int32 words; a NORMAL scene's table has both halves)
+AGPT_HD int normal_slots_offset(int n_materials) { return (2 * n_materials + 3) & ~3; }
+
 struct DevLight {
     int32_t type;
     int32_t shape;  // primitive index of the emitting sphere
@@ -226,6 +242,7 @@ struct DevScene {
     const float4* tri_uv;
     const DevTexture* textures;
     const int32_t* material_texture;   // [n_materials], or [2 * n_materials] in a scene with roughness / metallic maps (see above)
+                                       // (+ DevNormalSlot[n_materials] at normal_slots_offset in a scene with a normal map)
 };
 
 // 16-B hit record written by the trace kernel

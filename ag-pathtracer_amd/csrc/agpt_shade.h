@@ -614,6 +614,43 @@ __device__ __forceinline__ v3 texture_blend(const TextureAddress& a, const Textu
     const v3 bot = c01 + a.fx * (c11 - c01);
     return top + a.fy * (bot - top);
 }
+// ---- tangent-space normal maps (agpt.h: agpt_scene_set_material_normal_texture; only the NORMAL kernel variants) -----------------
+// The whole definition: the texel decoded to (tx, ty, tz), taken from the frame bsdf_setup is about to build -- ss = ss_bsdf, ts =
+// cross(ns, ss), ns; not orthogonal for an interpolated normal -- to the world, l2w's sums left to right, and normalized into the new
+// shading normal.  n (face-forwarded against the unperturbed ns) and ss_bsdf stay.  A texel along the normal, a non-finite m and a
+// zero-length m leave the hit untouched.  Ray directions depend on it: no sh_ helper, exact in both arithmetics.
+__device__ __forceinline__ void surface_apply_normal_map(Surface& s, v3 rgb, float scale) {
+    const float tx = (2.f * rgb.x - 1.f) * scale, ty = (2.f * rgb.y - 1.f) * scale, tz = 2.f * rgb.z - 1.f;
+    if (tx == 0.f && ty == 0.f && tz > 0.f) return;
+    const v3 ns = s.ns, ss = s.ss_bsdf, ts = cross(ns, ss);
+    const v3 m = V3(ss.x * tx + ts.x * ty + ns.x * tz, ss.y * tx + ts.y * ty + ns.y * tz, ss.z * tx + ts.z * ty + ns.z * tz);
+    if (!(isfinite(m.x) && isfinite(m.y) && isfinite(m.z))) return;
+    if (sqrlen(m) == 0.f) return;
+    s.ns = normalize(m);
+}
+// the slot of material `mat` (agpt_scene.h: DevNormalSlot) in the GLOBAL-memory material_texture table
+__device__ __forceinline__ DevNormalSlot normal_slot(const int32_t* material_texture, int n_materials, int mat) {
+    const int4* q = (const int4*)(material_texture + normal_slots_offset(n_materials)) + 2 * (size_t)mat;
+    const int4 a = q[0], b = q[1];
+    DevNormalSlot o;
+    o.tex.texels = (const float4*)(((unsigned long long)(uint32_t)a.y << 32) | (uint32_t)a.x);
+    o.tex.width = a.z;
+    o.tex.height = a.w;
+    o.scale = __int_as_float(b.x);
+    o.texture = b.y;
+    return o;
+}
+// known-answer kernel body (agpt_kat_normal_map): the perturbation alone, one lane per item
+__device__ __forceinline__ void kat_normal_map_lane(int n, const float* __restrict__ ns3, const float* __restrict__ ss3,
+                                                    const float* __restrict__ rgb3, float scale, float* __restrict__ out3) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Surface s{};   // (a hit with nothing but a shading normal and a tangent)
+    s.ns = V3(ns3[3 * i], ns3[3 * i + 1], ns3[3 * i + 2]);
+    s.ss_bsdf = V3(ss3[3 * i], ss3[3 * i + 1], ss3[3 * i + 2]);
+    surface_apply_normal_map(s, V3(rgb3[3 * i], rgb3[3 * i + 1], rgb3[3 * i + 2]), scale);
+    out3[3 * i] = s.ns.x; out3[3 * i + 1] = s.ns.y; out3[3 * i + 2] = s.ns.z;
+}
 __device__ __forceinline__ float spherical_theta(v3 v) { return cr_acosf(tclampf(v.z, -1.f, 1.f)); }  // common.h:158-160
 __device__ __forceinline__ float spherical_phi(v3 v) {                                                // common.h:162-165
     float p = cr_atan2f(v.y, v.x);

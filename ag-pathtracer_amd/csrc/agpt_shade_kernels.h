@@ -24,10 +24,18 @@
 // kernel whose lookups honour each texture's sampler (agpt_scene.h: DevTexture; bilinear filtering, clamp and mirror wrap) -- as
 // k_shade_sampled / k_shade_sampled_fast, for scenes in which a material names a texture with a non-default sampler.  One level covers
 // the colour slot and both maps; the other six units are left alone in the same way.
+// AGPT_SHADE_TEXTURED 4 (agpt_shade_kernels_normal.hip, agpt_shade_kernels_normal_fast.hip) is the NORMAL variant on top of that -- the SAMPLED
+// kernel plus the normal-map slot (agpt_scene.h: DevNormalSlot; agpt_shade.h: surface_apply_normal_map), whose taps ride in the same round
+// trip as the other slots' -- as k_shade_normal / k_shade_normal_fast, for scenes in which a material has a normal map; the other eight
+// units are left alone in the same way.
 #ifndef AGPT_SHADE_TEXTURED
 #define AGPT_SHADE_TEXTURED 0
 #endif
-#if AGPT_SHADE_TEXTURED == 3 && AGPT_SHADE_FAST
+#if AGPT_SHADE_TEXTURED == 4 && AGPT_SHADE_FAST
+#define AGPT_SHADE_KNAME(n) n##_normal_fast
+#elif AGPT_SHADE_TEXTURED == 4
+#define AGPT_SHADE_KNAME(n) n##_normal
+#elif AGPT_SHADE_TEXTURED == 3 && AGPT_SHADE_FAST
 #define AGPT_SHADE_KNAME(n) n##_sampled_fast
 #elif AGPT_SHADE_TEXTURED == 3
 #define AGPT_SHADE_KNAME(n) n##_sampled
@@ -110,8 +118,14 @@ __device__ __forceinline__ v3 pending_light_sample(const DevScene& sc, const Ren
 // SAMPLED: see AGPT_SHADE_TEXTURED 3 above.  MAPPED with texture_address / texture_load / texture_blend (agpt_shade.h) in texture_value's place: one tap of a NEAREST
 // texture, four of a BILINEAR one, the taps of every distinct texture issued before the first blend (up to twelve 16-B gathers in
 // flight behind the material lookup instead of three round trips of four).
-template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0), bool MAPPED = (AGPT_SHADE_TEXTURED >= 2), bool SAMPLED = (AGPT_SHADE_TEXTURED == 3)>
-__device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t pid SCK_PARAMS) {
+// NORMAL: see AGPT_SHADE_TEXTURED 4 above.  SAMPLED with a fourth lookup: the material's DevNormalSlot is read from the global-memory table
+// (`normal_table`: sc.material_texture before the LDS copy took its place; nullptr in every other variant) beside the other slots' texture
+// records, its address and its taps are formed and issued with theirs -- up to sixteen gathers in one round trip; an image that another
+// slot names shares that slot's taps -- and surface_apply_normal_map perturbs the shading normal before bsdf_setup.
+template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0), bool MAPPED = (AGPT_SHADE_TEXTURED >= 2), bool SAMPLED = (AGPT_SHADE_TEXTURED >= 3),
+          bool NORMAL = (AGPT_SHADE_TEXTURED == 4)>
+__device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t pid,
+                                               const int32_t* normal_table SCK_PARAMS) {
     uint32_t bits = 0;
     // Every per-path record is fetched up front, unconditionally: the loads then overlap in one memory round trip instead
     // of forming a chain of dependent ones behind the flag tests (a record that turns out not to be needed is a coalesced
@@ -206,6 +220,8 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                     const int rtex = param_slot_texture(slots, 0), mtex = param_slot_texture(slots, 1);   // (0 = roughness, 1 = metallic)
                     // the texture records first (valid for any slot: record 0 stands in for "none"), then the gathers, then their uses
                     const DevTexture ct = sc.textures[tex], rt = sc.textures[rtex >= 0 ? rtex : 0], mx = sc.textures[mtex >= 0 ? mtex : 0];
+                    DevNormalSlot nslot;
+                    if constexpr (NORMAL) nslot = normal_slot(normal_table, sc.n_materials, mat);
                     float tu, tv;
                     triangle_uv(uv01, uv2, h.b1, h.b2, &tu, &tv);
                     v3 c, rv, mv;
@@ -218,12 +234,26 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                         texture_address(ct, tu, tv, ca);
                         texture_address(r_own ? rt : ct, tu, tv, ra);
                         texture_address(m_own ? mx : ct, tu, tv, ma);
+                        int ntex = -1;
+                        bool n_own = false;
+                        TextureAddress na;
+                        TextureTaps nk;
+                        if constexpr (NORMAL) {
+                            ntex = nslot.texture;
+                            n_own = ntex >= 0 && ntex != tex && ntex != rtex && ntex != mtex;
+                            texture_address(n_own ? nslot.tex : ct, tu, tv, na);
+                        }
                         texture_load(ca, ck);
                         if (r_own) texture_load(ra, rk);
                         if (m_own) texture_load(ma, mk);
+                        if constexpr (NORMAL)
+                            if (n_own) texture_load(na, nk);
                         c = texture_blend(ca, ck);
                         rv = r_own ? texture_blend(ra, rk) : c;
                         mv = m_own ? texture_blend(ma, mk) : (mtex == rtex ? rv : c);
+                        if constexpr (NORMAL)
+                            if (ntex >= 0)
+                                surface_apply_normal_map(s, n_own ? texture_blend(na, nk) : (ntex == tex ? c : (ntex == rtex ? rv : mv)), nslot.scale);
                     } else {
                         c = texture_value(ct, tu, tv);
                         rv = c, mv = c;
@@ -535,7 +565,8 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
     __shared__ DevLight s_tab_lights[LDS_TABLES ? AGPT_SHADE_LDS_LIGHTS : 1];
 #if AGPT_SHADE_TEXTURED
     // 512 B beside the 9.5 KB of materials; MAPPED, SAMPLED: both halves of the table, 1 KB (40,960 B per block in all: still four blocks
-    // per CU; the sampler state rides in the texture records, agpt_scene.h)
+    // per CU; the sampler state rides in the texture records, agpt_scene.h).  NORMAL: the same 1 KB -- a fifth block-wide kilobyte would
+    // cost the fourth block of the CU, so the normal slots stay in global memory
     constexpr int n_tab_halves = AGPT_SHADE_TEXTURED >= 2 ? 2 : 1;
     __shared__ int32_t s_tab_material_texture[LDS_TABLES ? n_tab_halves * AGPT_SHADE_LDS_MATERIALS : 1];
 #endif
@@ -632,7 +663,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
             uint32_t pid = 0, bits = 0;
             if (qi < n_active) {
                 pid = qin.active[qi];
-                bits = shade_path<ENV>(sc, rc, pb, pid SCK_ARGS);
+                bits = shade_path<ENV>(sc, rc, pb, pid, AGPT_SHADE_TEXTURED == 4 ? sc_in.material_texture : nullptr SCK_ARGS);
             }
             s_pid[u][tid] = pid;     // (slots private to the thread: no synchronisation)
             s_bits[u][tid] = bits;
@@ -711,8 +742,8 @@ using ShadeLaunch = void(hipStream_t stream, int grid, bool lds_tables, bool env
                          const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
 using ResolveLaunch = void(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin);
 ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast, launch_shade_mapped, launch_shade_mapped_fast,
-    launch_shade_sampled, launch_shade_sampled_fast;
-ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED, MAPPED and SAMPLED units have none, see k_resolve_pending)
+    launch_shade_sampled, launch_shade_sampled_fast, launch_shade_normal, launch_shade_normal_fast;
+ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED, MAPPED, SAMPLED and NORMAL units have none, see k_resolve_pending)
 
 void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
                                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters,

@@ -13,12 +13,13 @@ bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights) {
 
 void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, int resolve_grid, const DevScene& sc, const RenderConsts& rc,
                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
-    ShadeLaunch* const shade = v.sampled    ? (v.fast ? launch_shade_sampled_fast : launch_shade_sampled)
+    ShadeLaunch* const shade = v.normal     ? (v.fast ? launch_shade_normal_fast : launch_shade_normal)
+                               : v.sampled  ? (v.fast ? launch_shade_sampled_fast : launch_shade_sampled)
                                : v.mapped   ? (v.fast ? launch_shade_mapped_fast : launch_shade_mapped)
                                : v.textured ? (v.fast ? launch_shade_textured_fast : launch_shade_textured)
                                             : (v.fast ? launch_shade_fast : launch_shade);
     shade(stream, shade_grid, v.lds_tables, v.env, sc, rc, pb, qin, qout, counters, tile_heads);
-    // The TEXTURED, MAPPED and SAMPLED units have no k_resolve_pending (no BSDF and no material in it): their ended paths use the plain unit's of the same
+    // The TEXTURED, MAPPED, SAMPLED and NORMAL units have no k_resolve_pending (no BSDF and no material in it): their ended paths use the plain unit's of the same
     // arithmetic.  (Independent of k_shade: different paths.)
     ResolveLaunch* const resolve = v.fast ? launch_resolve_pending_fast : launch_resolve_pending;
     resolve(stream, resolve_grid, sc, rc, pb, qin);

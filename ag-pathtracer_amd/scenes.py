@@ -95,6 +95,10 @@ class SceneDesc:
     def set_material_param_texture(self, material, param, texture, channel=0):
         self.ops.append(("material_param_texture", int(material), int(param), int(texture), int(channel)))
 
+    def set_material_normal_texture(self, material, texture, scale=1.0):
+        """the material's tangent-space normal map (agpt_scene_set_material_normal_texture; texture = -1: none)"""
+        self.ops.append(("material_normal_texture", int(material), int(texture), float(scale)))
+
     def set_texture_sampler(self, texture, filter=0, wrap_u=0, wrap_v=0):
         """binding.FILTER_* / WRAP_* of a texture, for every slot that names it (default: nearest, repeat, repeat)"""
         self.ops.append(("texture_sampler", int(texture), int(filter), int(wrap_u), int(wrap_v)))
@@ -127,6 +131,8 @@ class SceneDesc:
                 target.set_material_texture(op[1], op[2])
             elif k == "material_param_texture":
                 target.set_material_param_texture(op[1], op[2], op[3], op[4])
+            elif k == "material_normal_texture":
+                target.set_material_normal_texture(op[1], op[2], op[3])
             elif k == "texture_sampler":
                 target.set_texture_sampler(op[1], op[2], op[3], op[4])
         if self.camera is not None:

@@ -222,6 +222,34 @@ int agpt_scene_set_material_param_texture(agpt_scene*, int material, int param, 
 enum { AGPT_FILTER_NEAREST = 0, AGPT_FILTER_BILINEAR = 1 };
 enum { AGPT_WRAP_REPEAT = 0, AGPT_WRAP_CLAMP = 1, AGPT_WRAP_MIRROR = 2 };
 int agpt_scene_set_texture_sampler(agpt_scene*, int texture, int filter, int wrap_u, int wrap_v);
+/* ---- tangent-space normal maps ------------------------------------------------------------------------------------
+ * From now on `material`'s shading normal at a mesh hit is perturbed by `texture`; texture = -1 removes it (scale ignored).  Before
+ * agpt_scene_commit.  Any material type (Disney, mirror, diffuse-only); the texture is one of agpt_scene_add_texture's, read through its
+ * own sampler (agpt_scene_set_texture_sampler) like every other slot, and the slot is independent of the colour, roughness and
+ * metallic slots.  All fp32, every operation rounded on its own, nothing contracted into an fma:
+ *   uv, texel       the hit's uv as above; (r, g, b) = value(u, v) through the texture's sampler, exactly as for the colour slot; a
+ *                   non-finite uv reads texel (0, 0).
+ *   decode          tx = (2 * r - 1) * scale, ty = (2 * g - 1) * scale, tz = 2 * b - 1.
+ *   no-op rule      the hit is left exactly as it was, with no arithmetic on it, if tx == 0 && ty == 0 && tz > 0 (a texel along the
+ *                   normal), if m below has a non-finite component, or if sqrlen(m) == 0.  A map of (.5, .5, 1) texels therefore
+ *                   renders bit-identical to no map, whatever the scale and the filter.
+ *   frame           the one the BSDF uses at that hit, non-orthogonal for an interpolated normal: ns = the shading normal, ss =
+ *                   normalize(dpdu) of the triangle (the tangent the BSDF's frame is built on), ts = cross(ns, ss).
+ *   perturbed ns    m = (ss.c * tx + ts.c * ty + ns.c * tz per component c, summed left to right); ns' = m * (1 / sqrtf(dot(m, m))).
+ *   what stays      the geometric normal (already face-forwarded against the unperturbed ns) and ss; the BSDF then forms its
+ *                   ts = cross(ns', ss) as it always does.  A mesh without vertex normals has ns = ng and is perturbed the same way.
+ *   conventions     +x of the texel is along normalize(dpdu), +y along cross(ns, ss), rows top-first as everywhere in this ABI; a host
+ *                   whose images use the other green convention flips g itself.  A perturbed normal that ends up below the geometric
+ *                   surface is not corrected: the host owns the map.
+ * Every path that shades sees it -- agpt_render, agpt_render_adaptive, agpt_li_batch.  The perturbation decides ray directions and
+ * stays exact under AGPT_SHADING_FAST, like the uv interpolation and the texel blend.  agpt_render_features writes the perturbed
+ * normal into normal_depth.xyz (the denoiser's normal edge-stop sees the detail); its albedo is unaffected.  agpt_kat_bsdf_eval /
+ * _sample have no hit and are unaffected.  Triangle meshes only: agpt_scene_commit returns AGPT_ERR_INVALID if a sphere or a plane
+ * carries such a material.  Scenes without a normal map run the kernels they ran before normal maps existed.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error) for a NULL scene, an unknown material or texture id, a non-finite scale, or a scene
+ * that is already committed -- checked in this order, the first that applies is the one reported; the scale is looked at only for
+ * texture >= 0. */
+int agpt_scene_set_material_normal_texture(agpt_scene*, int material, int texture, float scale);
 /* scene->camera = desc; Camera(desc) (camera.h:29-56,77-90) */
 int agpt_scene_set_camera(agpt_scene*, const agpt_camera_desc*);
 /* flatten + upload to HBM; must be called after the last add_* and before render/intersect */
@@ -468,6 +496,9 @@ int agpt_kat_bsdf_eval(agpt_scene*, int material, int n, const float* wo3, const
 /* BSDF::Sample_f (reflection.h:124-172) */
 int agpt_kat_bsdf_sample(agpt_scene*, int material, int n, const float* wo3, const float* u2, float* wi3_out,
                          float* f3_out, float* pdf_out, int32_t* specular_out);
+/* known-answer: the perturbation of agpt_scene_set_material_normal_texture alone, one lane per item (n items: ns3, ss3, rgb3 in,
+ * ns_out3 out; HOST arrays) */
+int agpt_kat_normal_map(agpt_ctx*, int n, const float* ns3, const float* ss3, const float* rgb3, float scale, float* ns_out3);
 /* RNG stream of a (pixel, sample): first n floats (template.cpp:667-675 + cl/tools.cl:1-2) */
 int agpt_kat_rng(agpt_ctx*, uint32_t pixel, uint32_t wh, uint32_t sample, uint32_t seed_base, int n, float* out,
                  uint32_t* seed_out);

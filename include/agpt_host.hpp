@@ -203,6 +203,11 @@ public:
     void SetMaterialParamTexture(int material, int param, int texture, int channel) {
         check(agpt_scene_set_material_param_texture(h_, material, param, texture, channel), "agpt_scene_set_material_param_texture");
     }
+    // the material's shading normal at a mesh hit is perturbed by `texture` read as a tangent-space normal map: x = (2r - 1) * scale along
+    // the tangent, y = (2g - 1) * scale along cross(normal, tangent), z = 2b - 1 along the normal (-1: no normal map)
+    void SetMaterialNormalTexture(int material, int texture, float scale = 1.f) {
+        check(agpt_scene_set_material_normal_texture(h_, material, texture, scale), "agpt_scene_set_material_normal_texture");
+    }
     // upload to HBM; call once after the scene is built (and again after changing `camera`)
     void commit() {
         check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera");

@@ -14,6 +14,20 @@ import numpy as np  # noqa: E402
 import ag_pathtracer_amd as ag  # noqa: E402
 
 
+def stud_normal_map(studs_x=4, studs_y=4, cell=16, height=0.35):
+    """rgb[studs_y * cell, studs_x * cell, 3]: the normals of studs_x x studs_y round bumps (a raised cosine each, cell x cell texels)
+    over a flat ground, as n / 2 + 1 / 2"""
+    y, x = np.mgrid[0:studs_y * cell, 0:studs_x * cell]
+    cx, cy = ((x + .5) % cell) / cell - .5, ((y + .5) % cell) / cell - .5
+    r = np.sqrt(cx * cx + cy * cy)
+    slope = np.where(r < .4, height * np.pi / .4 * np.sin(np.pi * r / .4) * .5, 0.0)        # -d/dr of height / 2 * (1 + cos(pi r / .4))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        gx, gy = np.where(r > 0, slope * cx / r, 0.0), np.where(r > 0, slope * cy / r, 0.0)
+    n = np.stack([gx, gy, np.ones_like(gx)], -1)
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    return (0.5 * n + 0.5).astype(np.float32)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="c3", choices=["c1", "c2", "c3", "c5", "simple", "heightfield", "textured", "mapped"])
@@ -39,6 +53,9 @@ def main():
     ap.add_argument("--filter", default="nearest", choices=["nearest", "bilinear"],
                     help="scenes textured / mapped: how every texture is read (agpt_scene_set_texture_sampler)")
     ap.add_argument("--wrap", default="repeat", choices=["repeat", "clamp", "mirror"], help="scenes textured / mapped: wrap mode of both axes")
+    ap.add_argument("--normal-map", type=float, nargs="?", const=1.0, default=None, metavar="SCALE",
+                    help="scenes textured / mapped: a procedural bump image (a field of round studs) as tangent-space normal map on both mesh "
+                         "materials, read like the other textures (agpt_scene_set_material_normal_texture)")
     a = ap.parse_args()
     W, H = a.width, a.height
     aspect = W / float(H)
@@ -46,6 +63,14 @@ def main():
             "c3": lambda: ag.scenes.scene_c3(aspect=aspect), "c5": lambda: ag.scenes.scene_c5(aspect=aspect),
             "simple": lambda: ag.scenes.scene_simple_test(), "textured": lambda: ag.scenes.scene_textured(), "mapped": lambda: ag.scenes.scene_mapped(),
             "heightfield": lambda: ag.scenes.scene_heightfield(361, True, W, H)}[a.scene]()
+    if a.normal_map is not None:
+        if a.scene not in ("textured", "mapped"):
+            ap.error("--normal-map applies to the scenes textured and mapped")
+        # the floor and the blob (scenes.scene_textured).  The backdrop's u runs 0..36 along the sweep, the last unit of it over the ~32
+        # units of flat floor, and v 0..1 across its 40 units: 48 x 60 studs per image are round and two thirds of a unit wide on the
+        # floor (and far below a pixel on the wall behind, where the image repeats 35 times: no mip-mapping)
+        desc.set_material_normal_texture(0, desc.add_texture(stud_normal_map(48, 60, 8)), a.normal_map)
+        desc.set_material_normal_texture(2, desc.add_texture(stud_normal_map(8, 4)), a.normal_map)
     if (a.filter, a.wrap) != ("nearest", "repeat"):
         if a.scene not in ("textured", "mapped"):
             ap.error("--filter / --wrap apply to the scenes textured and mapped")

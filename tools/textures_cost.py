@@ -4,7 +4,7 @@ pointed at one 256x256 image for its roughness (g) and its metallic weight (b) (
 with every texture read BILINEAR (k_shade_sampled) against the same scene with the default NEAREST samplers (k_shade_mapped), into
 profiles/texture_filter_c3.json by default; the scenes live in one process, each
 rendered --reps times, alternating, after a warm-up.  Per variant: step ms, trace ms, non-trace ms, the agpt_stats totals and non-trace ns per shaded vertex (medians).
-    python tools/textures_cost.py [--out profiles/textures_c3.json] [--mapped | --sampled] [--reps 3] [--shading exact|fast] [--kernel-trace CSV]
+    python tools/textures_cost.py [--out profiles/textures_c3.json] [--mapped | --sampled | --normal] [--reps 3] [--shading exact|fast] [--kernel-trace CSV]
 (--reps 1 --no-warmup: exactly one render per variant, the run for rocprofv3 --kernel-trace --stats; --kernel-trace adds that
 run's per-kernel times to the JSON, --kernel-trace-run JSON -- what that run wrote with --out -- its command and library hash)"""
 import argparse
@@ -57,6 +57,20 @@ def sampled_c3(desc, size=256):
     return desc
 
 
+def normal_c3(desc, size=256, seed=13):
+    """sampled_c3 with one more size x size image, a random bump field read as a tangent-space normal map (tilts up to ~25 degrees),
+    on every material (k_shade_normal)"""
+    desc = sampled_c3(desc, size)
+    g = np.random.RandomState(seed).uniform(-0.45, 0.45, (size, size, 2))
+    n = np.concatenate([g, np.ones((size, size, 1))], -1)
+    n /= np.linalg.norm(n, axis=-1, keepdims=True)
+    tex = desc.add_texture((0.5 * n + 0.5).astype(np.float32))
+    desc.set_texture_sampler(tex, ag.FILTER_BILINEAR, ag.WRAP_REPEAT, ag.WRAP_REPEAT)
+    for m in range(desc.n_materials):
+        desc.set_material_normal_texture(m, tex, 1.0)
+    return desc
+
+
 def library_build_id():
     """sha256 of the loaded library file: which kernel build the numbers belong to"""
     import hashlib
@@ -67,6 +81,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mapped", action="store_true", help="add the leg with roughness / metallic maps (k_shade_mapped)")
     ap.add_argument("--sampled", action="store_true", help="mapped with NEAREST (k_shade_mapped) against mapped with BILINEAR (k_shade_sampled)")
+    ap.add_argument("--normal", action="store_true", help="the all-BILINEAR mapped scene (k_shade_sampled) against the same scene with a normal map on every material (k_shade_normal)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--shading", default="exact", choices=["exact", "fast"])
@@ -78,10 +93,12 @@ def main():
     a = ap.parse_args()
     if a.sampled and a.out is None:
         a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "texture_filter_c3.json")
+    if a.normal and a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "normal_map_c3.json")
     W, H, spp = 1920, 1080, 64
     ctx = ag.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     scenes = {}
-    for name in ("mapped", "sampled") if a.sampled else ("untextured", "textured") + (("mapped",) if a.mapped else ()):
+    for name in ("sampled", "normal") if a.normal else ("mapped", "sampled") if a.sampled else ("untextured", "textured") + (("mapped",) if a.mapped else ()):
         d = ag.scenes.scene_c3(aspect=W / float(H))
         if name == "textured":
             d = textured_c3(d)
@@ -89,6 +106,8 @@ def main():
             d = mapped_c3(d)
         elif name == "sampled":
             d = sampled_c3(d)
+        elif name == "normal":
+            d = normal_c3(d)
         scenes[name] = d.instantiate(ag.Scene(ctx))
         scenes[name].set_shading_arith(a.shading)
     film = torch.zeros((H, W, 4), device="cuda")
@@ -114,12 +133,16 @@ def main():
         med = {k: statistics.median(r[k] for r in rs) for k in ("step_ms", "trace_ms", "non_trace_ms")}
         med["non_trace_ns_per_shaded_vertex"] = med["non_trace_ms"] * 1e6 / max(1, rs[0]["shaded_vertices"])
         med["stats"] = {k: rs[0][k] for k in ("shaded_vertices", "rays", "closest_rays", "anyhit_rays", "answered_rays", "iterations")}
+        med["spread"] = {k: [min(r[k] for r in rs), max(r[k] for r in rs)] for k in ("step_ms", "trace_ms", "non_trace_ms")}
         med["runs"] = rs
         res[name] = med
         print("%-10s step %7.1f ms  trace %7.1f  non-trace %6.1f  shaded %6.1f M  %.3f ns/vertex" % (
             name, med["step_ms"], med["trace_ms"], med["non_trace_ms"], rs[0]["shaded_vertices"] / 1e6,
             med["non_trace_ns_per_shaded_vertex"]), flush=True)
-    if a.sampled:
+    if a.normal:
+        # (the like-for-like figure is the one per shaded vertex: tilted normals end more paths, the two legs shade other vertex counts)
+        res["normal_over_sampled"] = {k: res["normal"][k] / res["sampled"][k] for k in ("non_trace_ns_per_shaded_vertex", "non_trace_ms", "step_ms")}
+    elif a.sampled:
         res["sampled_over_mapped"] = {k: res["sampled"][k] / res["mapped"][k] for k in ("step_ms", "non_trace_ms")}
     else:
         res["non_trace_ratio"] = res["textured"]["non_trace_ms"] / res["untextured"]["non_trace_ms"]
