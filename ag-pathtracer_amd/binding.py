@@ -20,6 +20,8 @@ HIT_DTYPE = np.dtype([("hit", np.int32), ("prim", np.int32), ("tri", np.int32),
                       ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
 # agpt_scene_set_bvh_builder; work tiers of agpt_bvh_build_device (include/agpt.h)
 BVH_BUILDER_HOST, BVH_BUILDER_DEVICE = 0, 1
+# agpt_scene_update_mesh (include/agpt.h)
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 # agpt_scene_set_shading_arith (include/agpt.h)
 SHADING_EXACT, SHADING_FAST = 0, 1
 # agpt_scene_set_material_param_texture (include/agpt.h)
@@ -36,7 +38,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
@@ -152,6 +154,8 @@ def lib():
     L.agpt_mesh_num_prims.argtypes = [vp, C.c_int]
     L.agpt_mesh_get_bvh.argtypes = [vp, C.c_int, vp, ip]
     L.agpt_bvh_build.argtypes = [fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.agpt_bvh_refit.argtypes = [fp, C.c_int, ip, C.c_int, ip, vp, C.c_int]
+    L.agpt_scene_update_mesh.argtypes = [vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int]
     L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
     L.agpt_scene_set_shading_arith.argtypes = [vp, C.c_int]
     L.agpt_bvh_build_device.argtypes = [vp, fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -277,6 +281,17 @@ def bvh_build(verts, indices, max_prims_in_node=1):
                                 order.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(total), C.byref(depth)),
            "agpt_bvh_build")
     return nodes[:total.value + 1].copy(), order, depth.value
+
+
+def bvh_refit(verts, indices, prim_index, nodes):
+    """agpt_bvh_refit on the host (no GPU needed): the tree `nodes` (bvh_build's, with its prim_index) with the bounds recomputed
+    for `verts`, topology kept -> a new nodes array."""
+    v, pv = _f(np.asarray(verts).reshape(-1, 3))
+    ix, pi = _i(np.asarray(indices).reshape(-1, 3))
+    order, po = _i(np.asarray(prim_index).reshape(-1))
+    out = np.array(nodes, NODE_DTYPE, copy=True)
+    _check(lib().agpt_bvh_refit(pv, v.shape[0], pi, ix.shape[0], po, out.ctypes.data_as(C.c_void_p), out.shape[0] - 1), "agpt_bvh_refit")
+    return out
 
 
 def bvh_build_device(ctx, verts, indices, max_prims_in_node=1):
@@ -533,6 +548,19 @@ class Scene:
         return _check(self.L.agpt_scene_add_mesh(self.h, pv, v.shape[0], pn, n.shape[0], pt, t.shape[0], pi,
                                                  ix.shape[0], int(material), int(max_prims_in_node)),
                       "agpt_scene_add_mesh")
+
+    def update_mesh(self, prim, verts, normals=None, mode=UPDATE_REFIT):
+        """agpt_scene_update_mesh: new positions (and vertex normals, if the mesh has any) for mesh primitive `prim` of the committed
+        scene.  mode: UPDATE_REFIT / "refit" (the tree keeps its topology, the mesh's records are rewritten on the GPU) or
+        UPDATE_REBUILD / "rebuild" (a new BVH and the full upload)."""
+        if isinstance(mode, str):
+            if mode not in ("refit", "rebuild"):
+                raise ValueError("update_mesh: unknown mode %r (refit, rebuild)" % mode)
+            mode = UPDATE_REFIT if mode == "refit" else UPDATE_REBUILD
+        v, pv = _f(np.asarray(verts).reshape(-1, 3))
+        n, pn = (None, None) if normals is None else _f(np.asarray(normals).reshape(-1, 3))
+        _check(self.L.agpt_scene_update_mesh(self.h, int(prim), pv, v.shape[0], pn, 0 if n is None else n.shape[0], int(mode)),
+               "agpt_scene_update_mesh")
 
     def set_bvh_builder(self, builder):
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""

@@ -16,6 +16,7 @@
 #include "agpt_denoise.h"
 #include "agpt_host_scene.hpp"
 #include "agpt_kernels.h"
+#include "agpt_update.h"
 
 // LDS stack entries of the production trace kernel (23 KiB of stack + 8 KiB = 31 KiB per block -> five blocks per CU) and the
 // blocks per CU that go with it; deeper BVHs spill the entries beyond into agpt_ctx::spill (HBM)
@@ -195,6 +196,13 @@ struct agpt_scene {
     std::vector<DevBuf<float4>> d_env_pixels;
     std::vector<DevBuf<float>> d_env_func, d_env_cdf;
     DevScene dev{};
+    // agpt_scene_update_mesh: per mesh the device path's cache (created by the mesh's first REFIT, agpt_update.h) and whether the
+    // bounds of HostMesh::nodes are behind the device's (root box excepted; brought up to date by sync_mirror)
+    std::vector<agpt::MeshUpdater*> updaters;
+    std::vector<char> bounds_stale;
+    ~agpt_scene() {
+        for (agpt::MeshUpdater* u : updaters) agpt::mesh_updater_destroy(u);
+    }
 };
 
 template <class T>
@@ -466,6 +474,7 @@ int agpt_scene_add_mesh(agpt_scene* s, const float* vertices, int n_vertices, co
                                               m.prim_index.data(), &m.total_nodes, &m.max_depth, &on_device);
         if (rc != AGPT_OK) return rc;
         m.nodes.resize((size_t)m.total_nodes + 1);
+        m.max_prims_in_node = max_prims_in_node;
     } else {
         agpt::build_bvh(m, max_prims_in_node);
     }
@@ -622,8 +631,20 @@ int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
     return AGPT_OK;
 }
 
+// the bounds of the host copies of meshes that were refitted on the device (agpt_scene_update_mesh)
+static int sync_mirror(agpt_scene* s) {
+    for (size_t m = 0; m < s->bounds_stale.size(); m++)
+        if (s->bounds_stale[m]) {
+            HIP_TRY(hipSetDevice(s->ctx->device));
+            if (const int rc = agpt::download_bounds(s->ctx->stream, s->updaters[m], s->meshes[m])) return rc;
+            s->bounds_stale[m] = 0;
+        }
+    return AGPT_OK;
+}
+
 int agpt_scene_commit(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_commit: scene is NULL");
+    if (const int rc = sync_mirror(s)) return rc;
     bool textured = false, mapped = false, normal = false;
     for (int32_t t : s->material_texture) textured = textured || t >= 0;
     for (uint32_t slots : s->material_param_slots) mapped = mapped || slots != 0;
@@ -791,6 +812,7 @@ int agpt_mesh_num_prims(const agpt_scene* s, int prim) {
 int agpt_mesh_get_bvh(const agpt_scene* s, int prim, agpt_bvh_node* nodes_out, int32_t* prim_index_out) {
     const agpt::HostMesh* m = mesh_of(s, prim);
     if (!m) return fail(AGPT_ERR_INVALID, "agpt_mesh_get_bvh: not a mesh primitive");
+    if (const int rc = sync_mirror(const_cast<agpt_scene*>(s))) return rc;
     if (nodes_out) std::memcpy(nodes_out, m->nodes.data(), m->nodes.size() * sizeof(agpt_bvh_node));
     if (prim_index_out) std::memcpy(prim_index_out, m->prim_index.data(), m->prim_index.size() * sizeof(int32_t));
     return AGPT_OK;
@@ -817,6 +839,126 @@ int agpt_bvh_build(const float* vertices, int n_vertices, const int32_t* indices
     if (prim_index_out) std::memcpy(prim_index_out, m.prim_index.data(), m.prim_index.size() * sizeof(int32_t));
     if (total_nodes_out) *total_nodes_out = m.total_nodes;
     if (max_depth_out) *max_depth_out = m.max_depth;
+    return AGPT_OK;
+}
+
+int agpt_bvh_refit(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, const int32_t* prim_index,
+                   agpt_bvh_node* nodes_inout, int total_nodes) {
+    if (const int rc = check_bvh_input("agpt_bvh_refit", vertices, n_vertices, indices, n_indices)) return rc;
+    const int n_tris = n_indices / 3;
+    if (!prim_index || !nodes_inout || total_nodes < 1 || total_nodes > 2 * n_tris)
+        return fail(AGPT_ERR_INVALID, "agpt_bvh_refit: NULL tree or a node count outside [1, 2 * triangles]");
+    for (int t = 0; t < n_tris; t++)
+        if (prim_index[t] < 0 || prim_index[t] % 3 != 0 || prim_index[t] / 3 >= n_tris) return fail(AGPT_ERR_INVALID, "agpt_bvh_refit: bad prim_index");
+    std::vector<v3> v((size_t)n_vertices);
+    for (int i = 0; i < n_vertices; i++) v[i] = V3(vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);
+    const std::vector<int32_t> ix(indices, indices + (size_t)3 * n_indices), order(prim_index, prim_index + n_tris);
+    std::vector<agpt_bvh_node> nodes(nodes_inout, nodes_inout + total_nodes + 1);   // (a refused call changes nothing)
+    if (!agpt::refit_bvh(v, ix, order, nodes.data(), total_nodes)) return fail(AGPT_ERR_INVALID, "agpt_bvh_refit: not a tree of agpt_bvh_build's");
+    std::memcpy(nodes_inout, nodes.data(), nodes.size() * sizeof(agpt_bvh_node));
+    return AGPT_OK;
+}
+
+// the top-level tree again (lists longer than 64 primitives): its topology depends on the root boxes (flatten_scene)
+static int upload_toplevel(agpt_scene* s) {
+    std::vector<float> boxes;
+    std::vector<uint32_t> index;
+    for (size_t pi = 0; pi < std::min<size_t>(s->prims.size(), 64 * (size_t)AGPT_MAX_CHUNKS); pi++)
+        if (s->prims[pi].type == AGPT_PRIM_MESH) {
+            const agpt_bvh_node& r = s->meshes[s->prims[pi].index].nodes[0];
+            boxes.insert(boxes.end(), {r.bmin[0], r.bmin[1], r.bmin[2], r.bmax[0], r.bmax[1], r.bmax[2]});
+            index.push_back((uint32_t)pi);
+        }
+    std::vector<float4> tree;
+    std::vector<uint32_t> packed;
+    agpt::build_skip_tree(boxes.data(), index.data(), (int)index.size(), tree);
+    agpt::pack_skip_tree16(tree, packed);
+    if (packed.size() > s->d_toplevel.n || (int32_t)(tree.size() / 2) != s->dev.n_toplevel)
+        return fail(AGPT_ERR_DEVICE, "agpt_scene_update_mesh: the top-level tree changed size");
+    HIP_TRY(hipMemcpyAsync(s->d_toplevel.p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    return AGPT_OK;
+}
+
+int agpt_scene_update_mesh(agpt_scene* s, int prim, const float* vertices, int n_vertices, const float* normals, int n_normals, int mode) {
+    if (!s || !vertices) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: NULL scene or vertices");
+    if (!s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: the scene is not committed");
+    if (prim < 0 || prim >= (int)s->prims.size() || s->prims[prim].type != AGPT_PRIM_MESH)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: primitive " + std::to_string(prim) + " is not a mesh of this scene");
+    const size_t mi = (size_t)s->prims[prim].index;
+    agpt::HostMesh& mesh = s->meshes[mi];
+    if (n_vertices != (int)mesh.vertices.size() || n_normals != (int)mesh.normals.size() || (!normals && !mesh.normals.empty()))
+        return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: the mesh has " + std::to_string(mesh.vertices.size()) + " vertices and " +
+                                          std::to_string(mesh.normals.size()) + " normals; both counts stay (normals may be NULL only without any)");
+    if (mode != AGPT_UPDATE_REFIT && mode != AGPT_UPDATE_REBUILD)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: unknown mode " + std::to_string(mode));
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (s->updaters.size() < s->meshes.size()) {
+        s->updaters.resize(s->meshes.size(), nullptr);
+        s->bounds_stale.resize(s->meshes.size(), 0);
+    }
+    bool finite = true;
+    for (int i = 0; i < 3 * n_vertices && finite; i++) finite = std::isfinite(vertices[i]);
+    auto set_arrays = [&]() {
+        for (int i = 0; i < n_vertices; i++) mesh.vertices[i] = V3(vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);
+        for (int i = 0; i < n_normals; i++) mesh.normals[i] = V3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+    };
+    if (mode == AGPT_UPDATE_REBUILD || !finite) {
+        // host orchestration of what exists: a new tree (REBUILD) or the host refit (a non-finite position), then the full commit
+        if (mode == AGPT_UPDATE_REBUILD && s->bvh_builder == AGPT_BVH_BUILDER_DEVICE) {
+            const int n_tris = (int)mesh.prim_index.size();
+            std::vector<agpt_bvh_node> nodes((size_t)2 * n_tris + 2);
+            std::vector<int32_t> order(n_tris);
+            int total = 0, depth = 0, on_device = 0;
+            const int rc = agpt::build_bvh_device(s->ctx->stream, vertices, n_vertices, mesh.indices.data(), n_tris, mesh.max_prims_in_node,
+                                                  nodes.data(), order.data(), &total, &depth, &on_device);
+            if (rc != AGPT_OK) return rc;
+            nodes.resize((size_t)total + 1);
+            set_arrays();
+            mesh.nodes.swap(nodes);
+            mesh.prim_index.swap(order);
+            mesh.total_nodes = total;
+            mesh.max_depth = depth;
+        } else if (mode == AGPT_UPDATE_REBUILD) {
+            set_arrays();
+            agpt::build_bvh(mesh, mesh.max_prims_in_node);
+        } else {
+            set_arrays();
+            agpt::refit_bvh(mesh.vertices, mesh.indices, mesh.prim_index, mesh.nodes.data(), mesh.total_nodes);
+        }
+        s->bounds_stale[mi] = 0;   // every box of this mesh has just been computed on the host
+        if (mode == AGPT_UPDATE_REBUILD) {   // the cache holds the old topology
+            agpt::mesh_updater_destroy(s->updaters[mi]);
+            s->updaters[mi] = nullptr;
+        }
+        return agpt_scene_commit(s);
+    }
+    // REFIT on the device: where flatten_scene put this mesh
+    size_t node_base = 0, tri_base = 0;
+    for (size_t m = 0; m < mi; m++) {
+        node_base += (s->meshes[m].nodes.size() + 1) & ~size_t(1);
+        tri_base += s->meshes[m].prim_index.size();
+    }
+    int ordinal = 0;   // its prefilter record: non-empty meshes before it in the list (every mesh has a triangle)
+    for (int pi = 0; pi < prim; pi++) ordinal += s->prims[pi].type == AGPT_PRIM_MESH;
+    const bool listed = prim < 64 * AGPT_MAX_CHUNKS;   // root pairs and prefilter records exist for these only
+    agpt::UpdateTarget tg;
+    tg.nodes = s->d_nodes.p;
+    tg.tri_verts = s->d_tri_verts.p;
+    tg.tri_shade = s->d_tri_shade.p;
+    tg.prim = s->d_prims.p + prim;
+    tg.rootpair = listed ? s->d_nodes.p + 4 * (((size_t)s->dev.rootpair_base + 2 * (size_t)prim) >> 1) : nullptr;
+    tg.prefilter = listed ? s->d_prefilter.p + 2 * (size_t)ordinal : nullptr;
+    tg.node_base = (uint32_t)node_base;
+    tg.tri_base = (uint32_t)tri_base;
+    tg.prim_id = (uint32_t)prim;
+    float root[6];
+    if (const int rc = agpt::update_mesh_device(s->ctx->stream, &s->updaters[mi], mesh, vertices, normals, tg, root)) return rc;
+    set_arrays();
+    std::memcpy(mesh.nodes[0].bmin, root, 12);
+    std::memcpy(mesh.nodes[0].bmax, root + 3, 12);
+    s->bounds_stale[mi] = 1;
+    if (s->prims.size() > 64) return upload_toplevel(s);
     return AGPT_OK;
 }
 

@@ -1,6 +1,7 @@
 // agpt_host_scene.cpp -- host-side scene preparation (runs once per scene; the reference does the same work in
 // BVHTriMesh's constructor, DisneyMaterial's constructor and Camera's constructor).
 #include "agpt_host_scene.hpp"
+#include "agpt_update.h"
 
 #include <algorithm>
 #include <array>
@@ -249,8 +250,38 @@ void build_bvh(HostMesh& mesh, int max_prims_in_node) {
     mesh.nodes.swap(tree.nodes);
     mesh.total_nodes = tree.total;
     mesh.max_depth = tree.max_depth;
+    mesh.max_prims_in_node = max_prims_in_node;
     mesh.prim_index.resize(n_tris);
     for (int t = 0; t < n_tris; t++) mesh.prim_index[t] = prims[t].index;
+}
+
+// The bounds of build_bvh's tree for the mesh's current vertices, topology kept: what Builder::leaf and Builder::build store, in
+// their order.  Child pairs have higher slots than their parent (pre-order allocation), so one pass from the last slot down.
+bool refit_bvh(const std::vector<v3>& vertices, const std::vector<int32_t>& indices, const std::vector<int32_t>& prim_index,
+               agpt_bvh_node* nodes, int total_nodes) {
+    const int n_tris = (int)prim_index.size();
+    for (int i = total_nodes; i >= 0; i--) {
+        if (i == 1) continue;  // unused slot
+        agpt_bvh_node& nd = nodes[i];
+        if (nd.count > 0) {
+            if (nd.first < 0 || nd.count > n_tris - nd.first) return false;
+            Box bounds;
+            for (int s = nd.first; s < nd.first + nd.count; s++) {
+                Box box;
+                for (int k = 0; k < 3; k++) box.grow(vertices[indices[3 * (size_t)prim_index[s] + 3 * k]]);
+                bounds.grow(box);
+            }
+            std::memcpy(nd.bmin, bounds.lo, 12);
+            std::memcpy(nd.bmax, bounds.hi, 12);
+        } else {
+            if (nd.count < 0 || nd.first <= i || nd.first < 2 || nd.first >= total_nodes) return false;
+            for (int a = 0; a < 3; a++) {
+                nd.bmin[a] = tminf(nodes[nd.first].bmin[a], nodes[nd.first + 1].bmin[a]);
+                nd.bmax[a] = tmaxf(nodes[nd.first].bmax[a], nodes[nd.first + 1].bmax[a]);
+            }
+        }
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -560,7 +591,6 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
         for (int t = 0; t < n_tris; t++) {
             const int32_t* ix = &mesh.indices[9 * t];
             const v3 v0 = mesh.vertices[ix[0]], v1 = mesh.vertices[ix[3]], v2 = mesh.vertices[ix[6]];
-            // trianglemesh.cpp:46-80 -- ray-independent: uv deltas, dpdu/dpdv, degenerate handling
             uv_t uv0, uv1, uv2;
             if (has_uv) {
                 uv0 = mesh.texcoords[ix[2]];
@@ -571,29 +601,9 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
                 uv1.x = 1; uv1.y = 0;
                 uv2.x = 1; uv2.y = 1;
             }
-            const float du02x = uv0.x - uv2.x, du02y = uv0.y - uv2.y;
-            const float du12x = uv1.x - uv2.x, du12y = uv1.y - uv2.y;
-            const v3 dp02 = v0 - v2, dp12 = v1 - v2;
-            const float determinant = du02x * du12y - du02y * du12x;
-            const bool degenerate_uv = (double)fabsf(determinant) < 1e-8;
-            v3 dpdu = V3s(0), dpdv = V3s(0);
-            if (!degenerate_uv) {
-                const float invdet = 1 / determinant;
-                dpdu = (du12y * dp02 - du02y * dp12) * invdet;
-                dpdv = (-du12x * dp02 + du02x * dp12) * invdet;
-            }
-            if (degenerate_uv || sqrlen(cross(dpdu, dpdv)) == 0) {
-                v3 ng = cross(v2 - v0, v1 - v0);
-                if (sqrlen(ng) == 0) {
-                    reject[t] = AGPT_TRI_FLAG_REJECT;
-                    dpdu = V3(1, 0, 0);
-                    dpdv = V3(0, 1, 0);
-                } else {
-                    coordinate_system(normalize(ng), &dpdu, &dpdv);
-                }
-            }
-            const v3 ng = normalize(cross(dpdu, dpdv));  // SurfaceInteraction ctor, intersectable.h:69
-            const v3 ss = normalize(dpdu);                // BSDF::ss (reflection.cpp:10) and trianglemesh.cpp:100
+            const TriFrame f = triangle_frame(v0, v1, v2, uv0, uv1, uv2);   // (agpt_update.h: shared with the device update)
+            reject[t] = f.reject;
+            const v3 ng = f.ng, ss = f.ss;
             v3 n0 = V3s(0), n1 = V3s(0), n2 = V3s(0);
             if (dp.has_normals) {
                 n0 = mesh.normals[ix[1]];

@@ -23,6 +23,7 @@ struct HostMesh {
     int total_nodes = 0;
     std::vector<int32_t> prim_index;  // reordered Primitive::index (= 3 * triangle)
     int max_depth = 0;
+    int max_prims_in_node = 1;  // as built (agpt_scene_update_mesh's REBUILD builds with it again)
 };
 
 struct HostSphere {
@@ -56,6 +57,11 @@ HostEnv make_env(const float* rgb, int width, int height);
 
 // BVHTriMesh ctor: Primitive list + BuildRecursive + FlattenBVHTree (bvhtrimesh.h:154-178,213-330)
 void build_bvh(HostMesh& mesh, int max_prims_in_node);
+
+// The tree's bounds recomputed for new vertices, topology kept (agpt_bvh_refit): nodes has total_nodes + 1 entries; false for a
+// tree that is not one of build_bvh's (a range outside the primitives, a child pair not behind its parent)
+bool refit_bvh(const std::vector<v3>& vertices, const std::vector<int32_t>& indices, const std::vector<int32_t>& prim_index,
+               agpt_bvh_node* nodes, int total_nodes);
 
 // DisneyMaterial / MirrorMaterial ctor parameterisation (material.h:14-49,72-77)
 DevMaterial make_material(int type, const float color[3], float roughness, float metallic);

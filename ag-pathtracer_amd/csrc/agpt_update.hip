@@ -1,0 +1,304 @@
+// agpt_update.hip -- agpt_scene_update_mesh's device path (agpt_update.h).  Compiled with the flags of the exact units: the
+// triangle records decide rays, so every operation rounds on its own and divides / square roots are correctly rounded.
+//
+//   k_update_tris    one lane per triangle SLOT (BVH leaf order): the three float4 of tri_verts at the slot, the four float4 of
+//                    tri_shade at the triangle's global id -- flatten_scene's two per-triangle loops, fused.
+//   k_refit_nodes    one lane per node of a list: a leaf grows the +-1e34 box over its slots' vertices (read back from tri_verts,
+//                    which k_update_tris has just written), an interior node takes (left, right) of its child pair.  Launched
+//                    once for all leaves, then once per level of interior nodes from the deepest up, on one stream: a launch sees
+//                    what the launches before it wrote, and the output does not depend on the launch shape.
+// Both are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair); 64-lane blocks, 16-byte
+// accesses of the float4 records, no LDS.
+#include "agpt_update.h"
+
+#include <string>
+#include <vector>
+
+namespace agpt {
+
+int report_error(int code, const std::string& msg);   // agpt_api.hip
+
+namespace {
+
+#define UPD_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess)                                                                             \
+            return report_error(e_ == hipErrorOutOfMemory ? AGPT_ERR_NOMEM : AGPT_ERR_DEVICE,             \
+                                std::string(#expr) + ": " + hipGetErrorString(e_));                       \
+    } while (0)
+
+constexpr int kBlock = 64;
+
+struct TriArgs {
+    const float* verts;        // xyz per vertex
+    const float* normals;      // xyz per normal, NULL: the mesh has none
+    const v2* uv;              // NULL: the mesh has none ((0,0), (1,0), (1,1), trianglemesh.cpp:52-56)
+    const int32_t* indices;    // (v, n, t) triplets, 9 per triangle
+    const int32_t* prim_index; // 3 * triangle per slot
+    float4* tri_verts;
+    float4* tri_shade;
+    uint32_t tri_base, prim_id;
+    int n_tris;
+};
+
+__device__ __forceinline__ v3 load3(const float* p, int i) { return V3(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]); }
+
+__global__ __launch_bounds__(kBlock) void k_update_tris(TriArgs a) {
+    const int s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= a.n_tris) return;
+    const int t = a.prim_index[s] / 3;
+    const int32_t* ix = a.indices + 9 * (size_t)t;
+    const v3 v0 = load3(a.verts, ix[0]), v1 = load3(a.verts, ix[3]), v2_ = load3(a.verts, ix[6]);
+    v2 uv0, uv1, uv2;
+    if (a.uv) {
+        uv0 = a.uv[ix[2]];
+        uv1 = a.uv[ix[5]];
+        uv2 = a.uv[ix[8]];
+    } else {
+        uv0.x = 0; uv0.y = 0;
+        uv1.x = 1; uv1.y = 0;
+        uv2.x = 1; uv2.y = 1;
+    }
+    const TriFrame f = triangle_frame(v0, v1, v2_, uv0, uv1, uv2);
+    v3 n0 = V3s(0), n1 = V3s(0), n2 = V3s(0);
+    if (a.normals) {
+        n0 = load3(a.normals, ix[1]);
+        n1 = load3(a.normals, ix[4]);
+        n2 = load3(a.normals, ix[7]);
+    }
+    const uint32_t gid = a.tri_base + (uint32_t)t;
+    float4* q = a.tri_shade + 4 * (size_t)gid;
+    q[0] = make_float4(f.ng.x, f.ng.y, f.ng.z, f.ss.x);
+    q[1] = make_float4(f.ss.y, f.ss.z, n0.x, n0.y);
+    q[2] = make_float4(n0.z, n1.x, n1.y, n1.z);
+    q[3] = make_float4(n2.x, n2.y, n2.z, __uint_as_float(a.prim_id));
+    float4* p = a.tri_verts + 3 * (size_t)(a.tri_base + (uint32_t)s);
+    p[0] = make_float4(v0.x, v0.y, v0.z, __uint_as_float(gid));
+    p[1] = make_float4(v1.x, v1.y, v1.z, __uint_as_float(f.reject));
+    p[2] = make_float4(v2_.x, v2_.y, v2_.z, 0.f);
+}
+
+struct RefitArgs {
+    const int2* topo;          // (first, count) per node, mesh-local
+    const int32_t* list;       // the nodes of this launch
+    int n;
+    const float4* tri_verts;
+    float4* bounds;            // reference layout: (bmin, -), (bmax, -) per node, mesh-local
+    float* nodes;              // the scene's pair records, as floats
+    uint32_t node_base, tri_base;
+    // the copies of the root box (node 0)
+    DevPrim* prim;
+    float* rootpair;
+    float* prefilter;
+};
+
+__global__ __launch_bounds__(kBlock) void k_refit_nodes(RefitArgs a) {
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= a.n) return;
+    const int i = a.list[k];
+    const int2 fc = a.topo[i];
+    float lo[3], hi[3];
+    if (fc.y > 0) {
+        // Builder::choose_split's `bounds`: Box() grown over the primitives' boxes, each Box() grown over its three vertices
+        for (int c = 0; c < 3; c++) {
+            lo[c] = 1e34f;
+            hi[c] = -1e34f;
+        }
+        const float4* tv = a.tri_verts + 3 * (size_t)(a.tri_base + (uint32_t)fc.x);
+        for (int s = 0; s < fc.y; s++) {
+            float plo[3] = {1e34f, 1e34f, 1e34f}, phi[3] = {-1e34f, -1e34f, -1e34f};
+            for (int v = 0; v < 3; v++) {
+                const float4 q = tv[3 * (size_t)s + v];
+                plo[0] = tminf(plo[0], q.x);
+                plo[1] = tminf(plo[1], q.y);
+                plo[2] = tminf(plo[2], q.z);
+                phi[0] = tmaxf(phi[0], q.x);
+                phi[1] = tmaxf(phi[1], q.y);
+                phi[2] = tmaxf(phi[2], q.z);
+            }
+            for (int c = 0; c < 3; c++) {
+                lo[c] = tminf(lo[c], plo[c]);
+                hi[c] = tmaxf(hi[c], phi[c]);
+            }
+        }
+    } else {
+        const float4 llo = a.bounds[2 * (size_t)fc.x], lhi = a.bounds[2 * (size_t)fc.x + 1];
+        const float4 rlo = a.bounds[2 * (size_t)fc.x + 2], rhi = a.bounds[2 * (size_t)fc.x + 3];
+        lo[0] = tminf(llo.x, rlo.x);
+        lo[1] = tminf(llo.y, rlo.y);
+        lo[2] = tminf(llo.z, rlo.z);
+        hi[0] = tmaxf(lhi.x, rhi.x);
+        hi[1] = tmaxf(lhi.y, rhi.y);
+        hi[2] = tmaxf(lhi.z, rhi.z);
+    }
+    a.bounds[2 * (size_t)i] = make_float4(lo[0], lo[1], lo[2], 0.f);
+    a.bounds[2 * (size_t)i + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
+    // the pair record of agpt_scene.h: [0] lx0 rx0 ly0 ry0  [1] lz0 rz0 lx1 rx1  [2] ly1 ry1 lz1 rz1  [3] untouched
+    const size_t g = (size_t)a.node_base + (size_t)i;
+    float* rec = a.nodes + 16 * (g >> 1);
+    const size_t side = g & 1;
+    for (int c = 0; c < 3; c++) {
+        rec[2 * c + side] = lo[c];
+        rec[6 + 2 * c + side] = hi[c];
+    }
+    if (i == 0) {
+        for (int c = 0; c < 3; c++) {
+            a.prim->root_bmin[c] = lo[c];
+            a.prim->root_bmax[c] = hi[c];
+            if (a.rootpair) {
+                a.rootpair[2 * c] = a.rootpair[2 * c + 1] = lo[c];
+                a.rootpair[6 + 2 * c] = a.rootpair[6 + 2 * c + 1] = hi[c];
+            }
+            if (a.prefilter) {
+                a.prefilter[c] = lo[c];
+                a.prefilter[4 + c] = hi[c];
+            }
+        }
+    }
+}
+
+template <class T>
+struct Buf {
+    T* p = nullptr;
+    ~Buf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t upload(const T* host, size_t count, hipStream_t st) {
+        if (!p) {
+            const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
+            if (e != hipSuccess) {
+                p = nullptr;
+                return e;
+            }
+        }
+        return count ? hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
+    }
+};
+
+}  // namespace
+
+struct MeshUpdater {
+    Buf<float> verts, normals;
+    Buf<v2> uv;
+    Buf<int32_t> indices, prim_index, lists;
+    Buf<int2> topo;
+    Buf<float4> bounds;
+    // lists: all leaves first, then the interior nodes level by level from the deepest up; launch l covers [begin[l], begin[l + 1])
+    std::vector<int> begin;
+    int total_nodes = 0;
+};
+
+void mesh_updater_destroy(MeshUpdater* u) { delete u; }
+
+// the topology and the per-level node lists of a tree of build_bvh's, checked against the sizes the kernels index with
+static int prepare(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh) {
+    const int total = mesh.total_nodes, n_tris = (int)mesh.prim_index.size();
+    std::vector<int2> topo((size_t)total + 1, make_int2(0, 0));
+    std::vector<int> depth((size_t)total + 1, -1);
+    std::vector<std::vector<int32_t>> interior;
+    std::vector<int32_t> lists;
+    depth[0] = 0;
+    for (int i = 0; i <= total; i++) {   // a parent has a lower slot than its children: its depth is known when it is reached
+        if (i == 1) continue;
+        const agpt_bvh_node& nd = mesh.nodes[i];
+        topo[i] = make_int2(nd.first, nd.count);
+        if (depth[i] < 0) return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: the mesh's BVH has an unreachable node");
+        if (nd.count > 0) {
+            if (nd.first < 0 || nd.count > n_tris - nd.first) return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: leaf range outside the mesh");
+            lists.push_back(i);
+        } else {
+            if (nd.count < 0 || nd.first <= i || nd.first < 2 || nd.first >= total)
+                return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: child pair outside the tree");
+            depth[nd.first] = depth[nd.first + 1] = depth[i] + 1;
+            if ((int)interior.size() <= depth[i]) interior.resize((size_t)depth[i] + 1);
+            interior[depth[i]].push_back(i);
+        }
+    }
+    u.begin.assign(1, 0);
+    u.begin.push_back((int)lists.size());
+    for (int d = (int)interior.size() - 1; d >= 0; d--) {
+        lists.insert(lists.end(), interior[d].begin(), interior[d].end());
+        u.begin.push_back((int)lists.size());
+    }
+    for (int32_t p : mesh.prim_index)
+        if (p < 0 || p % 3 != 0 || p / 3 >= n_tris) return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: bad prim_index");
+    u.total_nodes = total;
+    UPD_TRY(u.topo.upload(topo.data(), topo.size(), stream));
+    UPD_TRY(u.lists.upload(lists.data(), lists.size(), stream));
+    UPD_TRY(u.indices.upload(mesh.indices.data(), mesh.indices.size(), stream));
+    UPD_TRY(u.prim_index.upload(mesh.prim_index.data(), mesh.prim_index.size(), stream));
+    if (!mesh.texcoords.empty()) UPD_TRY(u.uv.upload(mesh.texcoords.data(), mesh.texcoords.size(), stream));
+    UPD_TRY(hipMalloc((void**)&u.bounds.p, 2 * ((size_t)total + 1) * sizeof(float4)));
+    UPD_TRY(hipMemsetAsync(u.bounds.p, 0, 2 * ((size_t)total + 1) * sizeof(float4), stream));
+    UPD_TRY(hipStreamSynchronize(stream));   // the staging vectors above go out of scope
+    return AGPT_OK;
+}
+
+int update_mesh_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices, const float* normals,
+                       const UpdateTarget& tg, float root6[6]) {
+    if (!*cache) {
+        MeshUpdater* u = new MeshUpdater();
+        const int rc = prepare(stream, *u, mesh);
+        if (rc != AGPT_OK) {
+            delete u;
+            return rc;
+        }
+        *cache = u;
+    }
+    MeshUpdater& u = **cache;
+    const int n_tris = (int)mesh.prim_index.size();
+    UPD_TRY(u.verts.upload(vertices, 3 * mesh.vertices.size(), stream));
+    if (!mesh.normals.empty()) UPD_TRY(u.normals.upload(normals, 3 * mesh.normals.size(), stream));
+
+    TriArgs ta;
+    ta.verts = u.verts.p;
+    ta.normals = mesh.normals.empty() ? nullptr : u.normals.p;
+    ta.uv = mesh.texcoords.empty() ? nullptr : u.uv.p;
+    ta.indices = u.indices.p;
+    ta.prim_index = u.prim_index.p;
+    ta.tri_verts = tg.tri_verts;
+    ta.tri_shade = tg.tri_shade;
+    ta.tri_base = tg.tri_base;
+    ta.prim_id = tg.prim_id;
+    ta.n_tris = n_tris;
+    hipLaunchKernelGGL(k_update_tris, dim3((n_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, ta);
+
+    RefitArgs ra;
+    ra.topo = u.topo.p;
+    ra.tri_verts = tg.tri_verts;
+    ra.bounds = u.bounds.p;
+    ra.nodes = reinterpret_cast<float*>(tg.nodes);
+    ra.node_base = tg.node_base;
+    ra.tri_base = tg.tri_base;
+    ra.prim = tg.prim;
+    ra.rootpair = reinterpret_cast<float*>(tg.rootpair);
+    ra.prefilter = reinterpret_cast<float*>(tg.prefilter);
+    for (size_t l = 0; l + 1 < u.begin.size(); l++) {
+        ra.list = u.lists.p + u.begin[l];
+        ra.n = u.begin[l + 1] - u.begin[l];
+        if (ra.n > 0) hipLaunchKernelGGL(k_refit_nodes, dim3((ra.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, ra);
+    }
+    UPD_TRY(hipGetLastError());
+    float4 root[2];
+    UPD_TRY(hipMemcpyAsync(root, u.bounds.p, sizeof(root), hipMemcpyDeviceToHost, stream));
+    UPD_TRY(hipStreamSynchronize(stream));
+    root6[0] = root[0].x; root6[1] = root[0].y; root6[2] = root[0].z;
+    root6[3] = root[1].x; root6[4] = root[1].y; root6[5] = root[1].z;
+    return AGPT_OK;
+}
+
+int download_bounds(hipStream_t stream, const MeshUpdater* u, HostMesh& mesh) {
+    std::vector<float4> b(2 * ((size_t)u->total_nodes + 1));
+    UPD_TRY(hipMemcpyAsync(b.data(), u->bounds.p, b.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    UPD_TRY(hipStreamSynchronize(stream));
+    for (int i = 0; i <= u->total_nodes; i++) {
+        if (i == 1) continue;
+        agpt_bvh_node& nd = mesh.nodes[i];
+        nd.bmin[0] = b[2 * (size_t)i].x; nd.bmin[1] = b[2 * (size_t)i].y; nd.bmin[2] = b[2 * (size_t)i].z;
+        nd.bmax[0] = b[2 * (size_t)i + 1].x; nd.bmax[1] = b[2 * (size_t)i + 1].y; nd.bmax[2] = b[2 * (size_t)i + 1].z;
+    }
+    return AGPT_OK;
+}
+
+}  // namespace agpt

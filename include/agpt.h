@@ -265,6 +265,28 @@ int agpt_mesh_get_bvh(const agpt_scene*, int prim, agpt_bvh_node* nodes_out, int
  * written, slot 1 unused); prim_index_out n_indices/3 entries.  Either output may be NULL. */
 int agpt_bvh_build(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int max_prims_in_node,
                    agpt_bvh_node* nodes_out, int32_t* prim_index_out, int* total_nodes_out, int* max_depth_out);
+/* The bounds of an existing tree recomputed for new vertex positions, host-only like agpt_bvh_build: the topology (first and count
+ * of every node, prim_index) stays, every box is rebuilt bottom-up with the builder's own comparisons in the builder's order -- a
+ * leaf is the +-1e34 box grown over its primitives' vertices in slot order, an interior node (left, right) of its child pair.  With
+ * the vertices the tree was built from it returns the builder's bytes.  nodes_inout has total_nodes + 1 entries (slot 1 unused).
+ * AGPT_ERR_INVALID for a NULL argument, an index out of range or a tree that is not one of agpt_bvh_build's. */
+int agpt_bvh_refit(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, const int32_t* prim_index,
+                   agpt_bvh_node* nodes_inout, int total_nodes);
+/* New vertex positions (and vertex normals, if the mesh has any) for mesh primitive `prim` of a COMMITTED scene; indices, texture
+ * coordinates, material and max_prims_in_node stay.  vertices / normals are host arrays of the mesh's own counts.  Synchronises
+ * with the context's stream and leaves the scene committed: every call that reads the scene -- agpt_render*, agpt_intersect_*,
+ * agpt_li_batch, agpt_render_features, agpt_dbg_li_batch, agpt_mesh_get_bvh -- sees the new geometry from then on.
+ *   REBUILD: a new BVH from the scene's builder (agpt_scene_set_bvh_builder), then the full flatten and upload of agpt_scene_commit:
+ *            the scene is what creating it from scratch with the new arrays gives.
+ *   REFIT:   the tree keeps its topology and gets agpt_bvh_refit's bounds; the triangle records and the bounds are rewritten on the
+ *            GPU (the same bytes as the host flatten's), so the cost is that of the one mesh.  A non-finite position takes the host
+ *            refit and the full upload instead.  A tree refitted far from the pose it was built for is still correct but slower to
+ *            traverse (its boxes overlap more): the host decides when to REBUILD.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order, for a NULL scene or NULL vertices; a scene that is not
+ * committed; a prim that is out of range or not a mesh; an n_vertices or n_normals that differs from the mesh's own count (normals
+ * may be NULL only if the mesh has none); an unknown mode.  A refused call changes nothing. */
+enum { AGPT_UPDATE_REFIT = 0, AGPT_UPDATE_REBUILD = 1 };
+int agpt_scene_update_mesh(agpt_scene*, int prim, const float* vertices, int n_vertices, const float* normals, int n_normals, int mode);
 /* Which builder agpt_scene_add_mesh uses for the BVH of later meshes on this scene (default HOST).  Both produce the same
  * bytes; DEVICE runs agpt_bvh_build_device on the scene's context. */
 enum { AGPT_BVH_BUILDER_HOST = 0, AGPT_BVH_BUILDER_DEVICE = 1 };

@@ -138,6 +138,8 @@ using CameraDesc = agpt_camera_desc;
 // agpt_scene_set_bvh_builder: where the BVH of later primitives_push_back(mesh) calls is built; both give the same bytes
 enum class BvhBuilder { Host = AGPT_BVH_BUILDER_HOST, Device = AGPT_BVH_BUILDER_DEVICE };
 // agpt_scene_set_shading_arith: exact (default, bit-identical to the oracle) or fast shading arithmetic for later renders
+// agpt_scene_update_mesh: keep the tree and refit its boxes, or build a new one
+enum class MeshUpdate { Refit = AGPT_UPDATE_REFIT, Rebuild = AGPT_UPDATE_REBUILD };
 enum class ShadingArith { Exact = AGPT_SHADING_EXACT, Fast = AGPT_SHADING_FAST };
 
 class Scene {
@@ -212,6 +214,15 @@ public:
     void commit() {
         check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera");
         check(agpt_scene_commit(h_), "agpt_scene_commit");
+    }
+    // geometry moved (agpt_scene_update_mesh): new positions -- and vertex normals, if the mesh has any -- for mesh primitive `prim` of
+    // the committed scene; indices, texture coordinates and material stay.  Refit keeps the BVH's topology and rewrites the mesh's
+    // records on the GPU; Rebuild builds a new tree and uploads the scene again.  The host applies the result like a camera move:
+    // `scene.UpdateMesh(prim, mesh); accumulator.Clear();`
+    void UpdateMesh(int prim, const TriangleMesh& m, MeshUpdate mode = MeshUpdate::Refit) {
+        check(agpt_scene_update_mesh(h_, prim, m.vertices.data(), (int)m.vertices.size() / 3, m.normals.empty() ? nullptr : m.normals.data(),
+                                     (int)m.normals.size() / 3, (int)mode),
+              "agpt_scene_update_mesh");
     }
     // camera moved (RotatingCamera::update): re-derive the camera only, geometry stays in HBM
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }
