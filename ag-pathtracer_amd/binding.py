@@ -39,7 +39,7 @@ EXPORTS = [
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
-    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_li_batch", "agpt_resolve",
+    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -103,6 +103,37 @@ class DenoiseParams(C.Structure):
 
 
 DENOISE_SIGMA_Z, DENOISE_SIGMA_N, DENOISE_SIGMA_L = 1.0, 0.25, 4.0
+
+
+class TemporalParams(C.Structure):
+    """agpt_temporal_params (include/agpt.h); the depth_tol / normal_cos defaults are AGPT_TEMPORAL_*."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("cam_cur", CameraDesc), ("cam_prev", CameraDesc),
+                ("max_history", C.c_float), ("depth_tol", C.c_float), ("normal_cos", C.c_float)]
+
+
+TEMPORAL_DEPTH_TOL, TEMPORAL_NORMAL_COS, TEMPORAL_MIN_WEIGHT = 0.05, 0.9, 1e-2
+
+
+def camera_desc(lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
+    """A CameraDesc from the arguments of Scene.set_camera, rounded to fp32 the same way."""
+    d = CameraDesc()
+    d.lookfrom[:] = [float(x) for x in np.float32(lookfrom)]
+    d.lookat[:] = [float(x) for x in np.float32(lookat)]
+    d.vup[:] = [float(x) for x in np.float32(vup)]
+    d.aspect_ratio = float(np.float32(aspect_ratio))
+    d.vfov = float(vfov)
+    d.aperture = float(aperture)
+    return d
+
+
+def camera_vectors(desc):
+    """agpt_camera_vectors: Camera(desc) as the library derives it -- float32[22] = origin, u, v, w, lower_left_corner, horizontal,
+    vertical (3 each), lens_radius.  Host only, no GPU needed.  desc: a CameraDesc or the argument tuple of Scene.set_camera."""
+    if not isinstance(desc, CameraDesc):
+        desc = camera_desc(*desc)
+    out = np.zeros(22, np.float32)
+    _check(lib().agpt_camera_vectors(C.byref(desc), out.ctypes.data_as(C.POINTER(C.c_float))), "agpt_camera_vectors")
+    return out
 
 
 def library_path():
@@ -171,6 +202,8 @@ def lib():
     L.agpt_resolve_counts.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_render_features.argtypes = [vp, C.POINTER(RenderParams), vp, vp]
     L.agpt_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
+    L.agpt_camera_vectors.argtypes = [C.POINTER(CameraDesc), fp]
+    L.agpt_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalParams)] + [vp] * 10
     L.agpt_li_batch.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), C.POINTER(Stats)]
     L.agpt_resolve.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -457,6 +490,40 @@ class Context:
             for p in ptrs:
                 self.free(p)
 
+    def temporal_accumulate(self, params, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
+                            albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out):
+        """agpt_temporal_accumulate: this frame's adaptive-render and feature buffers plus the previous frame's history (this
+        call's outputs then) and feature buffers -- all four None / 0 on the first frame -- into the history buffers, which have the
+        form denoise reads.  All DEVICE pointers, full film."""
+        _check(self.L.agpt_temporal_accumulate(self.h, C.byref(params), *[C.c_void_p(int(p)) if p else None for p in
+                                               (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
+                                                albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out)]),
+               "agpt_temporal_accumulate")
+
+    def temporal_to_host(self, cam_cur, cam_prev, accum, moment2, albedo, normal_depth, prev=None, max_history=32.0,
+                         depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS):
+        """Convenience for tests and tools: uploads this frame's host buffers ([H,W,4], [H,W], [H,W,4], [H,W,4]) and, unless prev is
+        None (first frame), prev = (hist_accum, hist_moment2, albedo, normal_depth) of the previous frame; runs temporal_accumulate;
+        returns (hist_accum[H,W,4], hist_moment2[H,W]).  cam_cur / cam_prev: CameraDesc or the argument tuple of Scene.set_camera."""
+        H, W = np.shape(moment2)
+        cams = [c if isinstance(c, CameraDesc) else camera_desc(*c) for c in (cam_cur, cam_prev)]
+        host = [np.ascontiguousarray(a, np.float32) for a in (accum, moment2, albedo, normal_depth) + (tuple(prev) if prev is not None else ())]
+        ptrs = []
+        try:
+            for a in host:
+                ptrs.append(self.alloc(a.nbytes))
+                self.upload(ptrs[-1], a)
+            if prev is None:
+                ptrs += [0, 0, 0, 0]
+            ptrs.append(self.alloc(W * H * 16))
+            ptrs.append(self.alloc(W * H * 4))
+            self.temporal_accumulate(TemporalParams(W, H, cams[0], cams[1], max_history, depth_tol, normal_cos), *ptrs)
+            return self.download(ptrs[-2], (H, W, 4)), self.download(ptrs[-1], (H, W))
+        finally:
+            for p in ptrs:
+                if p:
+                    self.free(p)
+
 
 def comm_unique_id():
     """agpt_comm_unique_id: 128 bytes (ncclUniqueId) that rank 0 hands to the other ranks."""
@@ -644,13 +711,7 @@ class Scene:
                "agpt_scene_set_texture_sampler")
 
     def set_camera(self, lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
-        d = CameraDesc()
-        d.lookfrom[:] = [float(x) for x in np.float32(lookfrom)]
-        d.lookat[:] = [float(x) for x in np.float32(lookat)]
-        d.vup[:] = [float(x) for x in np.float32(vup)]
-        d.aspect_ratio = float(np.float32(aspect_ratio))
-        d.vfov = float(vfov)
-        d.aperture = float(aperture)
+        d = camera_desc(lookfrom, lookat, vup, aspect_ratio, vfov, aperture)
         _check(self.L.agpt_scene_set_camera(self.h, C.byref(d)), "agpt_scene_set_camera")
 
     def commit(self):

@@ -25,14 +25,14 @@ SHADE_FAST_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
 SHADE_NORMAL_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=3"]
 SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_shade_kernels_fast.hip", "agpt_shade_kernels_textured.hip", "agpt_shade_kernels_textured_fast.hip",
            "agpt_shade_kernels_mapped.hip", "agpt_shade_kernels_mapped_fast.hip", "agpt_shade_kernels_sampled.hip", "agpt_shade_kernels_sampled_fast.hip",
-           "agpt_shade_kernels_normal.hip", "agpt_shade_kernels_normal_fast.hip", "agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+           "agpt_shade_kernels_normal.hip", "agpt_shade_kernels_normal_fast.hip", "agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_temporal.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {"agpt_shade_kernels.hip": SHADE_FLAGS, "agpt_shade_kernels_fast.hip": SHADE_FAST_FLAGS,
                 "agpt_shade_kernels_textured.hip": SHADE_FLAGS, "agpt_shade_kernels_textured_fast.hip": SHADE_FAST_FLAGS,
                 "agpt_shade_kernels_mapped.hip": SHADE_FLAGS, "agpt_shade_kernels_mapped_fast.hip": SHADE_FAST_FLAGS,
                 "agpt_shade_kernels_sampled.hip": SHADE_FLAGS, "agpt_shade_kernels_sampled_fast.hip": SHADE_FAST_FLAGS,
                 "agpt_shade_kernels_normal.hip": SHADE_NORMAL_FLAGS, "agpt_shade_kernels_normal_fast.hip": SHADE_NORMAL_FLAGS}
 HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h", "agpt_shade_arith.h",
-           "agpt_host_scene.hpp", "agpt_bvh_device.h", "agpt_update.h", "agpt_adaptive.h", "agpt_denoise.h", os.path.join("..", "..", "include", "agpt.h")]
+           "agpt_host_scene.hpp", "agpt_bvh_device.h", "agpt_update.h", "agpt_adaptive.h", "agpt_denoise.h", "agpt_temporal.h", os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);
 # explicit __builtin_fmaf calls (Markstein division in agpt_trace.h) stay fused.
 # -fno-slp-vectorize: the SLP pass packs adjacent f32 adds/muls into v_pk_*_f32, which on gfx950 cost more than the two

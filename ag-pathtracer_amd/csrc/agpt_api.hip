@@ -16,6 +16,7 @@
 #include "agpt_denoise.h"
 #include "agpt_host_scene.hpp"
 #include "agpt_kernels.h"
+#include "agpt_temporal.h"
 #include "agpt_update.h"
 
 // LDS stack entries of the production trace kernel (23 KiB of stack + 8 KiB = 31 KiB per block -> five blocks per CU) and the
@@ -1701,6 +1702,55 @@ int agpt_denoise(agpt_ctx* c, const agpt_denoise_params* p, const float* accum_d
         dc.last = i == p->iterations - 1;
         agpt::launch_denoise_pass(c->stream, dc, buf[cur], (const float4*)albedo_dev, (const float4*)normal_depth_dev, buf[cur ^ 1]);
     }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AGPT_OK;
+}
+
+int agpt_camera_vectors(const agpt_camera_desc* d, float out22[22]) {
+    if (!d || !out22) return fail(AGPT_ERR_INVALID, "agpt_camera_vectors: NULL argument");
+    const DevCamera cam = agpt::make_camera(*d);
+    static_assert(sizeof(DevCamera) == 22 * sizeof(float), "origin, u, v, w, lower_left_corner, horizontal, vertical, lens_radius");
+    std::memcpy(out22, &cam, sizeof(cam));
+    return AGPT_OK;
+}
+
+// One k_temporal launch: this frame's buffers plus the previous frame's history, reprojected, into the history buffers the next
+// agpt_denoise and the next frame's call read.
+int agpt_temporal_accumulate(agpt_ctx* c, const agpt_temporal_params* p, const float* accum_cur_dev, const float* moment2_cur_dev,
+                             const float* albedo_cur_dev, const float* normal_depth_cur_dev, const float* hist_accum_prev_dev,
+                             const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
+                             float* hist_accum_out_dev, float* hist_moment2_out_dev) {
+    if (!p) return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: NULL argument");
+    if (p->width <= 0 || p->height <= 0 || (uint64_t)p->width * (uint64_t)p->height > 0x7FFFFFFFull)
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: bad film size");
+    if (!(p->max_history > 0.f) || std::isinf(p->max_history))
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: max_history must be positive and finite");
+    if (!(p->depth_tol >= 0.f) || std::isinf(p->depth_tol))
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: depth_tol must be non-negative and finite");
+    if (!(p->normal_cos >= -1.f && p->normal_cos <= 1.f))
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: normal_cos must be in [-1, 1]");
+    if (!c || !accum_cur_dev || !moment2_cur_dev || !albedo_cur_dev || !normal_depth_cur_dev || !hist_accum_out_dev || !hist_moment2_out_dev)
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: NULL argument");
+    const float* prev[4] = {hist_accum_prev_dev, hist_moment2_prev_dev, albedo_prev_dev, normal_depth_prev_dev};
+    const int n_prev = (prev[0] != nullptr) + (prev[1] != nullptr) + (prev[2] != nullptr) + (prev[3] != nullptr);
+    if (n_prev != 0 && n_prev != 4)
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: the four prev buffers must be all NULL (first frame) or all given");
+    const float* in[8] = {accum_cur_dev, moment2_cur_dev, albedo_cur_dev, normal_depth_cur_dev, prev[0], prev[1], prev[2], prev[3]};
+    for (const float* q : in)
+        if (q && (q == hist_accum_out_dev || q == hist_moment2_out_dev))
+            return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: an output aliases an input");
+    if (hist_accum_out_dev == hist_moment2_out_dev) return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: the two outputs are one buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    TemporalConsts tc{};
+    tc.W = p->width; tc.H = p->height;
+    tc.identity = std::memcmp(&p->cam_prev, &p->cam_cur, sizeof(agpt_camera_desc)) == 0;
+    tc.max_history = p->max_history; tc.depth_tol = p->depth_tol; tc.normal_cos = p->normal_cos;
+    tc.cur = agpt::make_camera(p->cam_cur);
+    tc.prev = agpt::make_camera(p->cam_prev);
+    agpt::launch_temporal(c->stream, tc, (const float4*)accum_cur_dev, moment2_cur_dev, (const float4*)albedo_cur_dev,
+                          (const float4*)normal_depth_cur_dev, (const float4*)hist_accum_prev_dev, hist_moment2_prev_dev,
+                          (const float4*)albedo_prev_dev, (const float4*)normal_depth_prev_dev, (float4*)hist_accum_out_dev, hist_moment2_out_dev);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return AGPT_OK;

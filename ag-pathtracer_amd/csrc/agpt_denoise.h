@@ -16,6 +16,20 @@ struct DenoiseConsts {
     float sigma_z, sigma_n, sigma_l;
 };
 
+// The pixel-centre camera ray of film pixel (x, y): film position ((x + .5) / W, (y + .5) / H) -> Camera::GetRay (camera.h:58-64) with
+// rd = 0 whatever the aperture (myapp.cpp:165-167); the Ray that Scene::Intersect then receives normalises the direction once more
+// (camera.h:6), as the rays of agpt_intersect_device do (k_prepare_rays).  Shared by k_feature_rays and k_temporal (agpt_temporal.hip),
+// which reprojects the point that ray hit: one arithmetic, so the two agree bit for bit.
+__device__ __forceinline__ void feature_ray(const DevCamera& c, int x, int y, int32_t W, int32_t H, v3& O, v3& D) {
+    const float px = x + 0.5f, py = y + 0.5f;
+    const float s = px / W, t = py / H;
+    const v3 rd = V3s(0.f);
+    const v3 offset = c.u * rd.x + c.v * rd.y;
+    const v3 pixel = c.lower_left_corner + s * c.horizontal + t * c.vertical;
+    O = c.origin + offset;
+    D = normalize(normalize(pixel - c.origin - offset));
+}
+
 namespace agpt {
 // the pixel-centre camera rays of the tile (rc.NP pixels in pixel_of order), ready for a closest-hit trace launch
 void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d);

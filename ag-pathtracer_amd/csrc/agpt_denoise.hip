@@ -29,9 +29,7 @@ __device__ __forceinline__ v3 albedo_floor(float4 a) {
 
 }  // namespace
 
-// myapp.cpp:165-167 for the pixel centre: film position ((x + .5) / W, (y + .5) / H) -> Camera::GetRay (camera.h:58-64) with rd = 0
-// whatever the aperture; the Ray that Scene::Intersect then receives normalises the direction once more (camera.h:6), as the rays
-// of agpt_intersect_device do (k_prepare_rays).
+// one feature_ray (agpt_denoise.h) per tile pixel
 __global__ void __launch_bounds__(AGPT_BLOCK)
 k_feature_rays(DevCamera c, RenderConsts rc, float4* __restrict__ ray_o, float4* __restrict__ ray_d) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,13 +37,8 @@ k_feature_rays(DevCamera c, RenderConsts rc, float4* __restrict__ ray_o, float4*
     int x, y;
     size_t unused_index;
     pixel_of(rc, i, x, y, unused_index);
-    const float px = x + 0.5f, py = y + 0.5f;
-    const float s = px / rc.W, t = py / rc.H;
-    const v3 rd = V3s(0.f);
-    const v3 offset = c.u * rd.x + c.v * rd.y;
-    const v3 pixel = c.lower_left_corner + s * c.horizontal + t * c.vertical;
-    const v3 O = c.origin + offset;
-    const v3 D = normalize(normalize(pixel - c.origin - offset));
+    v3 O, D;
+    feature_ray(c, x, y, rc.W, rc.H, O, D);
     float4 o4, d4;
     o4.x = O.x; o4.y = O.y; o4.z = O.z; o4.w = AGPT_FLT_MAX;
     d4.x = D.x; d4.y = D.y; d4.z = D.z; d4.w = 0.f;

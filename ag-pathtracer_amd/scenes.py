@@ -142,6 +142,16 @@ class SceneDesc:
         return target
 
 
+def orbit_camera(camera, degrees):
+    """`camera` (the argument tuple of set_camera) with lookfrom turned by `degrees` about the vertical axis through lookat: one
+    frame of an orbit (tools/render.py --frames, tools/temporal_demo.py)"""
+    lookfrom, lookat = np.asarray(camera[0], np.float64), np.asarray(camera[1], np.float64)
+    a = np.deg2rad(degrees)
+    d = lookfrom - lookat
+    turned = np.array([np.cos(a) * d[0] + np.sin(a) * d[2], d[1], np.cos(a) * d[2] - np.sin(a) * d[0]])
+    return ((lookat + turned).astype(F),) + tuple(camera[1:])
+
+
 # ---- mesh generators (fp64 maths, rounded once to fp32: the arrays ARE the scene) -----------------------------
 def _iota_idx(tris):
     """[m,3] vertex ids -> [3m,3] index_type rows with v = n = t (trianglemesh.h:10)."""

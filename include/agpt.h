@@ -448,6 +448,67 @@ typedef struct {
 int agpt_denoise(agpt_ctx*, const agpt_denoise_params*, const float* accum_dev, const float* moment2_dev, const float* albedo_dev,
                  const float* normal_depth_dev, float* out_dev);
 
+/* ---- temporal reprojection of render history -----------------------------------------------------------------------
+ * Camera(desc) (camera.h:29-56) as the library derives it: out22 = origin, u, v, w, lower_left_corner, horizontal, vertical
+ * (3 floats each) and lens_radius -- the values agpt_scene_set_camera stores.  Host-only, needs no context: for hosts that project
+ * points themselves.  AGPT_ERR_INVALID for a NULL argument. */
+int agpt_camera_vectors(const agpt_camera_desc*, float out22[22]);
+
+/* agpt_temporal_accumulate: the temporal half of the SVGF-style filter agpt_denoise is the spatial half of.  Per frame the host
+ * renders a few samples (agpt_render_adaptive -> accum_cur, moment2_cur, fresh buffers) and the feature buffers (agpt_render_features
+ * -> albedo_cur, normal_depth_cur) with cam_cur; this call finds for every pixel where the surface it sees was on the previous
+ * film, fetches the history accumulated there and adds it to the frame's sums:
+ *     agpt_temporal_accumulate -> agpt_denoise(ctx, ..., hist_accum_out, hist_moment2_out, albedo_cur, normal_depth_cur, out)
+ * The host keeps hist_accum_out, hist_moment2_out, albedo_cur and normal_depth_cur for the next frame, where they are
+ * hist_accum_prev, hist_moment2_prev, albedo_prev and normal_depth_prev (all four NULL on the first frame, else all non-NULL).
+ * The outputs have the form of agpt_render_adaptive's buffers -- sums with the count in w, and the luminance second moment --, so
+ * agpt_denoise and agpt_resolve_counts take them as they are; but their w is an EFFECTIVE count that need not be an integer: they
+ * must NOT be handed back to agpt_render_adaptive.
+ * Everything is fp32, every operation rounded on its own (no fma), divisions and square roots IEEE; dot (summed left to right),
+ * length = sqrt(dot) and normalize = v * (1 / sqrt(dot)).  For film pixel (x, y), buffer index i = (H-1-y) * W + x:
+ *   1. a = accum_cur[i] (rgb sums, n_c = a.w), m_c = moment2_cur[i], flag = albedo_cur[i].w, g = normal_depth_cur[i].
+ *   2. First frame (prev NULL): the outputs are the current values, bit for bit.
+ *   3. The position on the previous film.  If the bytes of cam_prev equal the bytes of cam_cur (decided once per call):
+ *      x0 = x, y0 = y, fx = fy = 0, te = g.w, without arithmetic.  Otherwise, with C = Camera(cam_cur), P = Camera(cam_prev):
+ *        D = the direction agpt_render_features' ray through (x, y) has with C
+ *        Q = flag != 0 ? (C.origin + g.w * D) - P.origin : D        (a miss is a point at infinity: the sky reprojects under rotation)
+ *        te = length(Q);  L = P.lower_left_corner - P.origin;  dw = dot(Q, P.w);  !(dw < 0): NO HISTORY (not in front of P)
+ *        k = dot(L, P.w) / dw;  R = Q * k - L
+ *        s = dot(R, P.horizontal) / dot(P.horizontal, P.horizontal);  t likewise with P.vertical
+ *        sx = s * W - .5f,  sy = t * H - .5f;  !(sx > -1 && sx < W && sy > -1 && sy < H): NO HISTORY (also for NaN)
+ *        x0 = (int)floorf(sx), fx = sx - floorf(sx);  y0, fy likewise
+ *   4. The taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) in this order, b = (1-fx)*(1-fy), fx*(1-fy), (1-fx)*fy, fx*fy.
+ *      A tap q (buffer index by its own row flip) is used iff it lies inside the film, b > 0, n_q = hist_accum_prev[q].w > 0,
+ *      albedo_prev[q].w == flag and, if flag != 0, fabsf(te - normal_depth_prev[q].w) <= depth_tol * fmaxf(te, 1e-3f) and
+ *      dot(g.xyz, normal_depth_prev[q].xyz) >= normal_cos.  In tap order:
+ *        sb += b;  sn += b * n_q;  sc += b * (hist_accum_prev[q].rgb / n_q) per channel;  sm += b * (hist_moment2_prev[q] / n_q)
+ *   5. !(sb >= AGPT_TEMPORAL_MIN_WEIGHT): NO HISTORY.  Otherwise n_h = fminf(sn / sb, max_history), c_h = sc / sb, m_h = sm / sb,
+ *        out.rgb = a.rgb + c_h * n_h,  out.w = n_c + n_h,  moment2_out = m_c + m_h * n_h
+ *      (a current pixel with n_c == 0 takes the history alone).
+ *   6. NO HISTORY (disocclusion): the outputs are the current values, bit for bit.
+ * One thread computes one pixel in this fixed order, without atomics: repeated calls are bit-identical.  The outputs alias no
+ * input and not each other; the inputs are not written.  Enqueued on the context's stream and synchronised before returning.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order, for: NULL params; a bad film size (as agpt_denoise);
+ * max_history not positive and finite; depth_tol negative or not finite; normal_cos outside [-1, 1] or NaN; a NULL context or a
+ * NULL current or output pointer; prev pointers that are partly NULL; an output that aliases an input or the other output.
+ * Not covered: per-object motion vectors -- moving geometry is handled only by the depth, normal and flag tests rejecting stale
+ * history --; history behind specular bounces (a mirror image is reprojected as the mirror's surface); more than one GPU or
+ * buffers that are not the full film; variance clamping; sub-pixel jitter. */
+typedef struct {
+    int32_t width, height;            /* all buffers: full film, pitch = width, Accumulator::pixels order (row H-1-y) */
+    agpt_camera_desc cam_cur, cam_prev;
+    float max_history;                /* cap on the reprojected sample count, > 0, finite */
+    float depth_tol;                  /* relative depth tolerance, >= 0, finite   (default 0.05) */
+    float normal_cos;                 /* minimum dot(ns_cur, ns_prev), in [-1, 1] (default 0.9)  */
+} agpt_temporal_params;
+#define AGPT_TEMPORAL_DEPTH_TOL 0.05f
+#define AGPT_TEMPORAL_NORMAL_COS 0.9f
+#define AGPT_TEMPORAL_MIN_WEIGHT 1e-2f
+int agpt_temporal_accumulate(agpt_ctx*, const agpt_temporal_params*,
+        const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
+        const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
+        float* hist_accum_out_dev, float* hist_moment2_out_dev);
+
 /* Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) of PathTracer (integrator.h:120-191) for n rays of the caller --
  * the single-ray entry the reference's split-screen compare (myapp.cpp:168) and mouse picking (myapp.cpp:197-201) use, batched.
  * rays / rng_states / radiance3_out are HOST arrays.  rng_states[i] is the xorshift32 state the path's RandomFloat() calls start

@@ -410,6 +410,30 @@ public:
               "agpt_denoise");
         out.SetSamples(1);
     }
+    // agpt_temporal_accumulate: this frame -- these buffers and `features`, both rendered with cam_cur -- plus the history the previous
+    // frame's call left (prev_history, with that frame's prev_features and cam_prev; both null on the first frame), reprojected,
+    // into history_out.  history_out has this class' form (its w an effective, possibly fractional count): Denoise and CopyToSurface
+    // apply to it, RenderAdaptive must not continue it.  The host keeps history_out and `features` for the next frame.
+    void TemporalAccumulate(const FeatureBuffers& features, const agpt_camera_desc& cam_cur, const AdaptiveAccumulator* prev_history,
+                            const FeatureBuffers* prev_features, const agpt_camera_desc& cam_prev, AdaptiveAccumulator& history_out,
+                            float max_history = 32.f, float depth_tol = AGPT_TEMPORAL_DEPTH_TOL,
+                            float normal_cos = AGPT_TEMPORAL_NORMAL_COS) const {
+        agpt_temporal_params p{};
+        p.width = width;
+        p.height = height;
+        p.cam_cur = cam_cur;
+        p.cam_prev = cam_prev;
+        p.max_history = max_history;
+        p.depth_tol = depth_tol;
+        p.normal_cos = normal_cos;
+        check(agpt_temporal_accumulate(ctx_.handle(), &p, device_pixels(), device_moment2(), features.device_albedo(),
+                                       features.device_normal_depth(), prev_history ? prev_history->device_pixels() : nullptr,
+                                       prev_history ? prev_history->device_moment2() : nullptr,
+                                       prev_features ? prev_features->device_albedo() : nullptr,
+                                       prev_features ? prev_features->device_normal_depth() : nullptr, history_out.device_pixels(),
+                                       history_out.device_moment2()),
+              "agpt_temporal_accumulate");
+    }
     std::vector<float> DownloadMoment2() const {
         std::vector<float> out((size_t)width * height);
         check(agpt_device_download(ctx_.handle(), out.data(), moment2_, out.size() * 4), "agpt_device_download");

@@ -3,6 +3,7 @@
 0x00RRGGBB) -- the presentation end of SURVEY.md section 8(f) rank 4.
 
     python tools/render.py --scene c3 --width 960 --height 540 --spp 64 --out gpurun_out/c3.png
+    python tools/render.py --scene c3 --spp 4 --frames 8 --orbit 8 --temporal --out out/orbit.png   (out/orbit_0000.png ...)
 """
 import argparse
 import os
@@ -26,6 +27,41 @@ def stud_normal_map(studs_x=4, studs_y=4, cell=16, height=0.35):
     n = np.stack([gx, gy, np.ones_like(gx)], -1)
     n /= np.linalg.norm(n, axis=-1, keepdims=True)
     return (0.5 * n + 0.5).astype(np.float32)
+
+
+def render_sequence(a, ctx, scene, desc, W, H):
+    """--frames: per frame render, features, (temporal accumulate,) denoise, resolve.  Between frames the host keeps the history
+    buffers the frame wrote and the frame's feature buffers: two sets that alternate."""
+    pt = ag.PathTracer(5)
+    spp = max(2, a.spp)
+    iterations = a.denoise if a.denoise is not None else 5
+    n16, n4 = W * H * 16, W * H * 4
+    acc, m2, out = ctx.alloc(n16), ctx.alloc(n4), ctx.alloc(n16)
+    sets = [(ctx.alloc(n16), ctx.alloc(n4), ctx.alloc(n16), ctx.alloc(n16)) for _ in range(2)]   # history accum, moment2, albedo, normal_depth
+    stem, ext = os.path.splitext(a.out)
+    cam_prev = None
+    for k in range(a.frames):
+        cam = ag.scenes.orbit_camera(desc.camera, a.orbit * k / (a.frames - 1))
+        cur, prev = sets[k & 1], sets[(k & 1) ^ 1]
+        scene.set_camera(*cam)
+        ctx.memset(acc, 0, n16)
+        ctx.memset(m2, 0, n4)
+        t0 = time.time()
+        pt.render_adaptive(scene, W, H, acc, m2, spp, spp, spp, 0.0, seed_base=k)
+        pt.render_features(scene, W, H, cur[2], cur[3])
+        hist = (acc, m2)
+        if a.temporal:
+            params = ag.TemporalParams(W, H, ag.camera_desc(*cam), ag.camera_desc(*(cam_prev or cam)), a.max_history,
+                                       ag.TEMPORAL_DEPTH_TOL, ag.TEMPORAL_NORMAL_COS)
+            ctx.temporal_accumulate(params, acc, m2, cur[2], cur[3], *(prev if cam_prev else (0, 0, 0, 0)), cur[0], cur[1])
+            hist = cur[:2]
+        ctx.denoise(ag.DenoiseParams(W, H, iterations, 1, ag.DENOISE_SIGMA_Z, ag.DENOISE_SIGMA_N, ag.DENOISE_SIGMA_L), hist[0], hist[1],
+                    cur[2], cur[3], out)
+        dt = time.time() - t0
+        path = "%s_%04d%s" % (stem, k, ext)
+        ag.binding.write_png(path, ctx.resolve_counts(out, W * H), W, H)
+        print("frame %d: %d spp%s, %.1f ms -> %s" % (k, spp, " + history" if a.temporal and cam_prev else "", dt * 1e3, path))
+        cam_prev = cam
 
 
 def main():
@@ -56,7 +92,15 @@ def main():
     ap.add_argument("--normal-map", type=float, nargs="?", const=1.0, default=None, metavar="SCALE",
                     help="scenes textured / mapped: a procedural bump image (a field of round studs) as tangent-space normal map on both mesh "
                          "materials, read like the other textures (agpt_scene_set_material_normal_texture)")
+    ap.add_argument("--frames", type=int, default=1, metavar="N",
+                    help="render a sequence of N frames at --spp each (uniform, denoised) into numbered files OUT_0000.png ...")
+    ap.add_argument("--orbit", type=float, default=0.0, metavar="DEG", help="--frames: the camera turns DEG degrees about its lookat over the sequence")
+    ap.add_argument("--temporal", action="store_true",
+                    help="--frames: add each frame's reprojected history (agpt_temporal_accumulate) before the denoiser")
+    ap.add_argument("--max-history", type=float, default=32.0, help="--temporal: cap on the reprojected sample count")
     a = ap.parse_args()
+    if (a.temporal or a.orbit) and a.frames < 2:
+        ap.error("--temporal and --orbit apply to a sequence (--frames N, N >= 2)")
     W, H = a.width, a.height
     aspect = W / float(H)
     desc = {"c1": lambda: ag.scenes.scene_c1(), "c2": lambda: ag.scenes.scene_c2(aspect=aspect),
@@ -84,9 +128,11 @@ def main():
     scene.set_shading_arith(a.shading)
     scene = desc.instantiate(scene)
     print("scene build + BVH + upload: %.2f s" % (time.time() - t0))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.frames > 1:
+        return render_sequence(a, ctx, scene, desc, W, H)
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     features = None
     if a.denoise is not None or a.features_png:
         features = (ctx.alloc(W * H * 16), ctx.alloc(W * H * 16))
