@@ -5,7 +5,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagpt_hip.so")
-# (source, extra flags): agpt_shade_kernels.hip -- k_shade, k_resolve_pending -- is compiled with MachineLICM off and k_shade
+# (source, extra flags): agpt_shade_kernels.hip -- k_shade and the finishing kernels k_accumulate, k_export_li, k_resolve_pending -- is compiled with MachineLICM off and k_shade
 # held to four waves per SIMD: the pass hoists the two v_mov of every fp64 polynomial coefficient of the trigonometry out of the
 # path loop and keeps the pairs live for the whole kernel (168 registers + 7-14 spilled against 134 + 0; at the 128 of four waves
 # 2 spilled).  Measured on C3: k_shade -3.5 ms per step; the same flag on the trace kernels costs them 2 ms, hence two units.

@@ -170,19 +170,17 @@ k_generate_list(DevScene sc, RenderConsts rc, const uint32_t* __restrict__ list,
     pb.ext_d[i] = d4;
     pb.beta4[i] = b4;
     pb.L4[i] = l4;
-    q.active[i] = i;
     q.ext[i] = i;
     if (i == 0) {
         QCOUNT(q, 0) = total;
-        QCOUNT(q, 1) = total;
+        QCOUNT(q, 1) = 0;
         QCOUNT(q, 2) = 0;
-        QCOUNT(q, 3) = 0;
-        QCOUNT(q, 4) = 0;
     }
 }
 
 // k_accumulate over the listed pixels (same rgb additions in sample order, same NaN / inf reject), plus the luminance second
-// moment moment2 += Y * Y and the count accum.w += S
+// moment moment2 += Y * Y and the count accum.w += S.  Reads finished paths: agpt_render_adaptive runs agpt::launch_finish_paths
+// (k_resolve_pending, agpt_shade_kernels.h) over the batch first, which adds an ended path's pending light sample to L4
 __global__ void __launch_bounds__(AGPT_BLOCK)
 k_accumulate_list(RenderConsts rc, const uint32_t* __restrict__ list, uint32_t a0, uint32_t na, PathBuffers pb, float4* __restrict__ accum,
                   float* __restrict__ moment2, DevCounters* __restrict__ counters) {

@@ -1071,7 +1071,7 @@ int agpt_device_upload(agpt_ctx* c, void* dst, const void* src, size_t bytes) {
 #define X(T, name) +sizeof(T)
 constexpr size_t AGPT_BYTES_PER_PATH = (0 AGPT_POOL_BUFFERS(X)) + 2 * AGPT_NQUEUES * sizeof(uint32_t);
 #undef X
-static_assert(AGPT_BYTES_PER_PATH == 256, "11 float4 arrays + 2 hit arrays (16 B) + 2 flag words + 10 queue words");
+static_assert(AGPT_BYTES_PER_PATH == 240, "11 float4 arrays + 2 hit arrays (16 B) + 2 flag words + 6 queue words");
 // extra pool bytes per path for a scene: the candidate words of lists longer than 64 primitives (k_candidates)
 static size_t candidate_bytes_per_path(int n_prims) { return n_prims > 64 ? 4 + 8 * (size_t)((n_prims + 63) / 64) : 0; }
 static int ensure_pool(agpt_ctx* c, size_t paths, int n_prims) {
@@ -1140,8 +1140,7 @@ static int begin_wavefront(agpt_ctx* c, const agpt_scene* s, int enable_counters
 #undef X
     for (int i = 0; i < 2; i++) {
         Queues& q = run.q[i];
-        q.active = c->q[i][0].p; q.ext = c->q[i][1].p; q.mis = c->q[i][2].p; q.shadow = c->q[i][3].p;
-        q.resolve = c->q[i][4].p;
+        q.ext = c->q[i][0].p; q.mis = c->q[i][1].p; q.shadow = c->q[i][2].p;
         q.counts = c->qcounts.p + AGPT_NQUEUES * AGPT_QSTRIDE * i;
     }
     run.count = enable_counters == 2 ? 2 : (enable_counters != 0 ? 1 : 0);
@@ -1169,9 +1168,10 @@ static void set_wavefront_consts(RenderConsts& rc, const WavefrontRun& run, int 
 }
 
 // The wavefront loop of PathTracer::Li (integrator.h:124-191) over the paths k_generate / k_generate_li have set up in q[0]:
-// per iteration the three trace launches, k_shade and k_resolve_pending.  A path needs at most max_depth + 2 iterations unless it
-// crosses emitter spheres (pass-through re-casts do not count as bounces, integrator.h:152-161): that many run without a host
-// round trip, then the loop keeps going while the active or the resolve queue is non-empty.
+// per iteration the three trace launches and k_shade.  A path needs at most max_depth + 2 iterations unless it crosses emitter
+// spheres (pass-through re-casts do not count as bounces, integrator.h:152-161): that many run without a host round trip, then the
+// loop keeps going while any of the three queues is non-empty -- an ended path's last shadow ray and MIS query have to be traced
+// before the batch is finished (finished_radiance, agpt_shade_kernels.h, reads their answers).
 static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, WavefrontRun& run) {
     const int count = run.count;
     const PathBuffers& pb = run.pb;
@@ -1191,18 +1191,18 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, Wa
     const int planned = rcn.max_depth + 2;
     for (int it = 0;; it++) {
         if (it >= planned) {
-            // Termination check, one iteration behind: this iteration's queue counters (active and, 4 counters further on,
-            // resolve) are copied out asynchronously, and what is looked at is the copy made an iteration ago, which has
+            // Termination check, one iteration behind: this iteration's queue counters (ext, mis and shadow) are copied out
+            // asynchronously, and what is looked at is the copy made an iteration ago, which has
             // arrived by now -- the stream never waits for the host (a synchronous check left it idle for ~50 us per iteration,
             // and the iterations out here are a few hundred microseconds long).  The price is one iteration of launches over
             // empty queues at the very end (the kernels return at once on those).
             uint32_t* slot = c->host_pinned + (it & 1) * (AGPT_NQUEUES * AGPT_QSTRIDE);
-            HIP_TRY(hipMemcpyAsync(slot, q[cur].counts, (4 * AGPT_QSTRIDE + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream));
+            HIP_TRY(hipMemcpyAsync(slot, q[cur].counts, ((AGPT_NQUEUES - 1) * AGPT_QSTRIDE + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream));
             HIP_TRY(hipEventRecord(c->ev[2 + (it & 1)], main_stream));
             if (it > planned) {
                 const uint32_t* seen = c->host_pinned + ((it - 1) & 1) * (AGPT_NQUEUES * AGPT_QSTRIDE);
                 HIP_TRY(hipEventSynchronize(c->ev[2 + ((it - 1) & 1)]));
-                if (seen[0] == 0 && seen[4 * AGPT_QSTRIDE] == 0) break;
+                if (seen[0] == 0 && seen[AGPT_QSTRIDE] == 0 && seen[2 * AGPT_QSTRIDE] == 0) break;
             }
             if (it > 4096) return fail(AGPT_ERR_LIMIT, "agpt: path did not terminate");
         }
@@ -1213,11 +1213,11 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, Wa
         uint32_t* const heads[4] = {c->work.p, c->work.p + AGPT_FRONTIERS * AGPT_QSTRIDE, c->work.p + 2 * AGPT_FRONTIERS * AGPT_QSTRIDE,
                                     c->work.p + 3 * AGPT_FRONTIERS * AGPT_QSTRIDE};
         // (the closest-hit launch over the continuation rays may re-cast in place, see k_trace_fast)
-        const TraceLaunch ext{main_stream, q[cur].ext, &QCOUNT(q[cur], 1), 0, heads[0], pb.ext_o, pb.ext_d, pb.hit, nullptr,
+        const TraceLaunch ext{main_stream, q[cur].ext, &QCOUNT(q[cur], 0), 0, heads[0], pb.ext_o, pb.ext_d, pb.hit, nullptr,
                               count, small_batch, recast};
-        const TraceLaunch mis{mis_stream, q[cur].mis, &QCOUNT(q[cur], 2), 0, heads[1], pb.mis_o, pb.mis_d,
+        const TraceLaunch mis{mis_stream, q[cur].mis, &QCOUNT(q[cur], 1), 0, heads[1], pb.mis_o, pb.mis_d,
                               run.mis_mode ? nullptr : pb.mis_hit, run.mis_mode ? pb.mis_ok : nullptr, count, small_batch, false};
-        const TraceLaunch shadow{shadow_stream, q[cur].shadow, &QCOUNT(q[cur], 3), 0, heads[2], pb.sh_o, pb.sh_d, nullptr, pb.occluded,
+        const TraceLaunch shadow{shadow_stream, q[cur].shadow, &QCOUNT(q[cur], 2), 0, heads[2], pb.sh_o, pb.sh_d, nullptr, pb.occluded,
                                  count, small_batch, false};
         auto trace_ext = [&]() { launch_trace_timed<0>(c, run.timing, 0, s->dev, ext); };
         auto trace_mis = [&]() {
@@ -1241,7 +1241,7 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, Wa
             trace_mis();
             trace_shadow();
         }
-        agpt::launch_shading(main_stream, run.shade, shade_grid, c->num_cus * 8, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p, heads[3]);
+        agpt::launch_shading(main_stream, run.shade, shade_grid, s->dev, rcn, pb, q[cur], q[nxt], c->counters.p, heads[3]);
         cur = nxt;
         run.iterations++;
         run.launches += 3;
@@ -1526,8 +1526,7 @@ int agpt_render(agpt_scene* s, const agpt_render_params* rp, float* accum_dev, a
         hipLaunchKernelGGL(k_generate, dim3((total + AGPT_BLOCK - 1) / AGPT_BLOCK), dim3(AGPT_BLOCK), 0, c->stream, s->dev, rcn, run.pb,
                            run.q[0]);
         if ((rc = run_wavefront(c, s, rcn, run))) return rc;
-        hipLaunchKernelGGL(k_accumulate, dim3((NP + AGPT_BLOCK - 1) / AGPT_BLOCK), dim3(AGPT_BLOCK), 0, c->stream, rcn, run.pb,
-                           (float4*)accum_dev, c->counters.p);
+        agpt::launch_accumulate(c->stream, run.shade.fast, s->dev, rcn, run.pb, (float4*)accum_dev, c->counters.p);
     }
     if ((rc = end_wavefront(c))) return rc;
     return fill_stats(c, run, (uint64_t)NP * (uint64_t)rp->spp_count, stats);
@@ -1591,6 +1590,7 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
                 RenderConsts rcw = rcg;
                 rcw.NP = nc;   // (run_wavefront reads NP * S only to pick the small-batch trace kernels: the batch's real path count)
                 if (const int rc_run = run_wavefront(c, s, rcw, run)) return rc_run;
+                agpt::launch_finish_paths(c->stream, run.shade.fast, s->dev, rcg, run.pb, nc * (uint32_t)rcg.S);
                 agpt::launch_accumulate_list(c->stream, rcg, list, a0, nc, run.pb, accum, moment2_dev, c->counters.p);
             }
         }
@@ -1784,7 +1784,7 @@ int agpt_li_batch(agpt_scene* s, const agpt_ray* rays, const uint32_t* rng_state
     hipLaunchKernelGGL(k_generate_li, grid, block, 0, c->stream, (const agpt_ray*)d_rays.p, (const uint32_t*)d_rng.p, (uint32_t)n, run.pb,
                        run.q[0], max_depth);
     if ((rc = run_wavefront(c, s, rcn, run))) return rc;
-    hipLaunchKernelGGL(k_export_li, grid, block, 0, c->stream, run.pb, (uint32_t)n, d_out.p, rng_states_out ? d_rng.p : (uint32_t*)nullptr);
+    agpt::launch_export_li(c->stream, run.shade.fast, s->dev, rcn, run.pb, (uint32_t)n, d_out.p, rng_states_out ? d_rng.p : (uint32_t*)nullptr);
     if ((rc = end_wavefront(c))) return rc;
     HIP_TRY(hipMemcpyAsync(radiance3_out, d_out.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (rng_states_out) HIP_TRY(hipMemcpyAsync(rng_states_out, d_rng.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));

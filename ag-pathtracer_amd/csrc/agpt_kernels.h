@@ -4,12 +4,13 @@
 //     k_trace_fast<0>(ext queue)     continuation rays, closest hit                     -> hit[]
 //     k_trace_fast<2>(mis queue)     BSDF-sampled MIS rays as exact early-exit queries  -> mis_ok[]
 //     k_trace_fast<1>(shadow queue)  NEE shadow rays, any hit                           -> occluded[]
-//     k_shade(active queue)          resolves the previous vertex' NEE, then PathTracer::Li's loop body for the
+//     k_shade(ext queue)             resolves the previous vertex' NEE, then PathTracer::Li's loop body for the
 //                                    new hit; appends to the next iteration's queues with one atomic per queue per
 //                                    wave-private 256-path tile (ballot counts, order-preserving offsets)
-//     k_resolve_pending(resolve q.)  ended paths: adds the last vertex' light sample once its rays have been traced
-// (k_shade and k_resolve_pending live in agpt_shade_kernels.h, a translation unit of their own with its own code-generation options;
-// the instrumented / fallback k_trace traces MIS rays as closest hits into mis_hit[]).  Scenes with more than 64
+// A path that ends with its last vertex' light sample pending joins no queue: the sample is added where the batch is consumed
+// (finished_radiance: in k_accumulate and k_export_li themselves; for agpt_render_adaptive by one k_resolve_pending pass over the
+// finished batch).  (k_shade, k_accumulate, k_export_li and k_resolve_pending live in agpt_shade_kernels.h, translation units of their own with
+// their own code-generation options; the instrumented / fallback k_trace traces MIS rays as closest hits into mis_hit[]).  Scenes with more than 64
 // primitives run k_candidates (top-level tree over Scene::primitives) in front of each trace launch.  The trace kernels are
 // persistent: a fixed grid of waves pulls 64-ray chunks off the queue; queue lengths stay on the device (no host round
 // trip per iteration).  Path state is SoA float4 in HBM (coalesced 16 B/lane); the per-lane traversal stack lives in LDS
@@ -941,14 +942,11 @@ k_generate(DevScene sc, RenderConsts rc, PathBuffers pb, Queues q) {
     pb.ext_d[i] = d4;
     pb.beta4[i] = b4;
     pb.L4[i] = l4;
-    q.active[i] = i;
     q.ext[i] = i;
     if (i == 0) {
         QCOUNT(q, 0) = total;
-        QCOUNT(q, 1) = total;
+        QCOUNT(q, 1) = 0;
         QCOUNT(q, 2) = 0;
-        QCOUNT(q, 3) = 0;
-        QCOUNT(q, 4) = 0;
     }
 }
 
@@ -970,69 +968,16 @@ k_generate_li(const agpt_ray* __restrict__ rays, const uint32_t* __restrict__ rn
     pb.ext_d[i] = d4;
     pb.beta4[i] = b4;
     pb.L4[i] = l4;
-    q.active[i] = i;
     q.ext[i] = i;
     if (i == 0) {
         QCOUNT(q, 0) = n;
-        QCOUNT(q, 1) = n;
+        QCOUNT(q, 1) = 0;
         QCOUNT(q, 2) = 0;
-        QCOUNT(q, 3) = 0;
-        QCOUNT(q, 4) = 0;
     }
 }
-// Li's return value as it is (the NaN / inf filter belongs to MyApp::Tick, myapp.cpp:169-172, not to the integrator) and the
-// stream's state after the path, so that a host can go on drawing from it
-__global__ void k_export_li(PathBuffers pb, uint32_t n, float* __restrict__ radiance3, uint32_t* __restrict__ rng_out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 l4 = pb.L4[i];
-    radiance3[3 * i] = l4.x;
-    radiance3[3 * i + 1] = l4.y;
-    radiance3[3 * i + 2] = l4.z;
-    if (rng_out) rng_out[i] = __float_as_uint(l4.w);
-}
+// (k_export_li, which hands out Li's return value and the stream's end state, finishes the paths: agpt_shade_kernels.h)
 
 // ---------------------------------------------------------------------------------------------------------
-// myapp.cpp:169-173 NaN/inf reject + Accumulator::AddSample (myapp.h:17-19): samples are added in sample order
-__global__ void __launch_bounds__(AGPT_BLOCK)
-k_accumulate(RenderConsts rc, PathBuffers pb, float4* __restrict__ accum, DevCounters* __restrict__ counters) {
-    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= rc.NP) return;
-    int x, y;
-    size_t ai;
-    pixel_of(rc, p, x, y, ai);
-    float4 a = accum[ai];
-    uint32_t bad = 0;
-    const uint32_t G = sample_group(rc.S);
-    auto add = [&](float4 l4) {   // (one sample; the order of the additions is the sample order)
-        v3 clr = V3(l4.x, l4.y, l4.z);
-        if (isnan(clr.x) || isnan(clr.y) || isnan(clr.z) || isinf(luminance(clr))) {
-            clr = V3s(0.f);
-            bad++;
-        }
-        a.x += clr.x;
-        a.y += clr.y;
-        a.z += clr.z;
-    };
-    if ((G & 3u) == 0u) {
-        // a pixel's samples lie in runs of G consecutive records: fetch a whole 64-byte line (4 samples) per step
-        for (uint32_t sg = 0; sg < (uint32_t)rc.S / G; ++sg) {
-            const float4* run = pb.L4 + ((size_t)sg * rc.NP + p) * G;
-            for (uint32_t j = 0; j < G; j += 4) {
-                const float4 l0 = run[j], l1 = run[j + 1], l2 = run[j + 2], l3 = run[j + 3];
-                add(l0);
-                add(l1);
-                add(l2);
-                add(l3);
-            }
-        }
-    } else {
-        for (int s = 0; s < rc.S; s++) add(pb.L4[((size_t)((uint32_t)s / G) * rc.NP + p) * G + (uint32_t)s % G]);
-    }
-    accum[ai] = a;
-    if (bad) atomicAdd(&counters->outliers, (unsigned long long)bad);  // outliers are rare
-}
-
 // Accumulator::CopyToSurface (myapp.h:34-41) with lin2rgb / rgb2uint (template/common.h:41-51)
 __global__ void k_resolve(const float4* __restrict__ accum, int n, int samples, uint32_t* __restrict__ out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;

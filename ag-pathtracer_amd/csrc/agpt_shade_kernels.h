@@ -1,5 +1,7 @@
 // agpt_shade_kernels.h -- the shading kernels of the wavefront path tracer (see agpt_kernels.h for the iteration they are part
-// of): k_shade = PathTracer::Li's loop body (integrator.h:132-188) for every live path, k_resolve_pending for the ended ones.
+// of): k_shade = PathTracer::Li's loop body (integrator.h:132-188) for every live path, and the kernels that consume a finished batch
+// (k_accumulate, k_export_li; k_resolve_pending for the one consumer that lives elsewhere), which add an ended path's last light sample
+// in this unit's arithmetic.
 // Compiled as their own translation unit (agpt_shade_kernels.hip) with MachineLICM off: the pass hoists the materialisation of
 // every fp64 polynomial coefficient of the trigonometry (two v_mov each) out of the path loop and keeps the pairs in registers
 // for the whole kernel -- 168 registers and 7-14 spilled, against 134 and none without it, which is what lets the kernel be
@@ -56,11 +58,9 @@
 // ---------------------------------------------------------------------------------------------------------
 // PathTracer::Li's loop body (integrator.h:132-188) in wavefront form, for one path.  Returns which of the next
 // iteration's queues the path goes to.
-#define SB_ACTIVE 1u
-#define SB_EXT 2u
-#define SB_MIS 4u
-#define SB_SHADOW 8u
-#define SB_RESOLVE 16u        // (bits 0..4 = the queue the path is appended to, in Queues order)
+#define SB_EXT 1u
+#define SB_MIS 2u
+#define SB_SHADOW 4u          // (bits 0..2 = the queue the path is appended to, in Queues order)
 #define SB_SHADED 32u
 #define SB_MIS_ANSWERED 64u   // a MIS query answered in k_shade (counted as the Scene::Intersect call it replaces, not enqueued)
 #define SB_RAY_ANSWERED 128u  // a continuation ray whose hit nothing reads (same bookkeeping)
@@ -489,8 +489,8 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
                         // The ray that would follow ends the path whatever it hits: at the next vertex the loop adds emission
                         // only after a specular bounce (integrator.h:139-147) and breaks on `bounces >= maxDepth` (:150) before
                         // anything else looks at the intersection.  The reference still makes that Scene::Intersect call; its
-                        // answer cannot reach the image, so the production path counts the ray and does not trace it.  (The
-                        // path stays in the active queue for one more pass if this vertex' light sample is still pending.)
+                        // answer cannot reach the image, so the production path counts the ray and does not trace it.  (This
+                        // vertex' light sample, if one is pending, is added when the batch is consumed: finished_radiance.)
                         flags |= PF_DEAD;
                         bits |= SB_RAY_ANSWERED;
                     } else {
@@ -518,11 +518,9 @@ __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderC
             }
         }
     }
-    // a path that goes on has a continuation ray; one that has ended but still owes its last light sample (which waits for
-    // this iteration's shadow ray / MIS query) goes to the resolve queue: k_resolve_pending adds the sample without the
-    // records, the lanes and the code of a full k_shade pass
-    if (bits & SB_EXT) bits |= SB_ACTIVE;
-    else if (flags & PF_PENDING) bits |= SB_RESOLVE;
+    // a path that goes on has a continuation ray (SB_EXT: the queue k_shade reads next).  One that has ended but still owes its
+    // last light sample (which waits for the next iteration's shadow ray / MIS query) joins no queue and keeps PF_PENDING: the
+    // sample is added where the path's radiance is consumed (finished_radiance below)
     b4.x = beta.x; b4.y = beta.y; b4.z = beta.z; b4.w = __uint_as_float(flags);
     pb.beta4[pid] = b4;
     l4.x = L.x; l4.y = L.y; l4.z = L.z; l4.w = __uint_as_float(rng);
@@ -603,7 +601,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
     const unsigned long long sck_begin = sck_last;
 #endif
     // Wave-private tiles of 64 * SHADE_U queue entries: the wave shades them, counts its appends per queue with ballots and
-    // reserves the slots with one atomic per queue (lanes 0..3, one queue each).  No block barrier: with block-wide tiles
+    // reserves the slots with one atomic per queue (lanes 0..2, one queue each).  No block barrier: with block-wide tiles
     // the three __syncthreads per tile made every wave wait for the slowest of its block -- 10 % of the kernel's wave
     // time (s_memtime phase clocks) -- while 4x the atomics (one per queue per 256 paths) stay far below the ~11 ns per
     // same-line atomic that had made per-wave-per-64-paths appends the bottleneck.
@@ -653,7 +651,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
         return false;
     };
     for (uint32_t t = 0; next_tile(t);) {
-        uint32_t total[AGPT_NQUEUES] = {0, 0, 0, 0, 0};
+        uint32_t total[AGPT_NQUEUES] = {0, 0, 0};
 #pragma unroll 1
         for (int u = 0; u < SHADE_U; ++u) {
 #ifdef AGPT_SHADE_CLOCK
@@ -662,7 +660,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
             const uint32_t qi = t * wtile + (uint32_t)u * 64u + (uint32_t)lane;
             uint32_t pid = 0, bits = 0;
             if (qi < n_active) {
-                pid = qin.active[qi];
+                pid = qin.ext[qi];
                 bits = shade_path<ENV>(sc, rc, pb, pid, AGPT_SHADE_TEXTURED == 4 ? sc_in.material_texture : nullptr SCK_ARGS);
             }
             s_pid[u][tid] = pid;     // (slots private to the thread: no synchronisation)
@@ -684,7 +682,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
                 const bool pred = (bits >> q) & 1u;
                 const unsigned long long m = __ballot(pred);
                 if (pred) {
-                    uint32_t* qq = q == 0 ? qout.active : (q == 1 ? qout.ext : (q == 2 ? qout.mis : (q == 3 ? qout.shadow : qout.resolve)));
+                    uint32_t* qq = q == 0 ? qout.ext : (q == 1 ? qout.mis : qout.shadow);
                     qq[run[q] + (uint32_t)__popcll(m & lt_mask)] = pid;
                 }
                 run[q] += (uint32_t)__popcll(m);
@@ -710,27 +708,110 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Paths that have ended (MaxDepth reached, miss, black sample) while their last vertex' light sample was still waiting for its
-// shadow ray / MIS query: add the sample (integrator.h:166) and let the path go.  They used to ride through a whole
-// k_shade pass for this -- after the last bounce that is EVERY path of the batch: 10 records loaded, 3 wave slots per SIMD.
-#if !AGPT_SHADE_TEXTURED   // (no BSDF, no material: the TEXTURED units launch the plain units' kernel)
+// The radiance of a finished path.  A path that has ended (MaxDepth reached, miss, black sample) while its last vertex' light
+// sample was still waiting for its shadow ray / MIS query keeps PF_PENDING: the rays have been traced by the time the batch is
+// finished, the operands are where k_shade left them (an ended path issues no more rays and owns its slots), and the sample is
+// added (integrator.h:166) here, where L4 is consumed -- the expressions and their order are those of k_shade's own resolve of a
+// live path's pending sample.  (Ended paths used to leave through a fifth queue and a kernel of their own, which re-read all of
+// this and wrote L4 back for the accumulate pass to read again: after the last bounce that is every path of the batch.)
+// The operands are fetched only for a pending path, fac4 (the chosen light) only where the closest-hit form of the MIS query needs it.
+__device__ __forceinline__ v3 finished_radiance(const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t pid, float4 b4,
+                                                float4 l4) {
+    const v3 L = V3(l4.x, l4.y, l4.z);
+    const uint32_t flags = __float_as_uint(b4.w);
+    if (!(flags & PF_PENDING)) return L;
+    const uint32_t was_occluded = pb.occluded[pid], was_mis_ok = pb.mis_ok[pid];
+    const float4 c1_4 = pb.c1[pid], c2_4 = pb.c2[pid];
+    float4 f4 = {0.f, 0.f, 0.f, 0.f};
+    if (!rc.mis_mode) f4 = pb.fac4[pid];
+    const v3 Ld = pending_light_sample(sc, rc, pb, pid, flags, was_occluded, was_mis_ok, c1_4, c2_4, f4);
+    const float lightPdf = sh_rcp(sc.n_lights);         // integrator.h:100,104
+    return L + V3(b4.x, b4.y, b4.z) * sh_div3(Ld, lightPdf);   // integrator.h:166
+}
+
+#if !AGPT_SHADE_TEXTURED   // (no BSDF, no material: every scene runs the plain unit's kernels of its arithmetic)
+// myapp.cpp:169-173 NaN/inf reject + Accumulator::AddSample (myapp.h:17-19): samples are added in sample order.
+// A block owns AGPT_BLOCK / G pixels (G = sample_group: a pixel's samples lie in runs of G consecutive path ids, so the block's runs
+// of one sample group are AGPT_BLOCK consecutive ids).  Per sample group every thread finishes ONE path -- the reads of L4, beta4 and
+// a pending path's operands are coalesced, 64 lanes on 64 neighbouring records -- and parks the sample in LDS; then the first
+// AGPT_BLOCK / G threads add their pixel's G samples in sample order, ((a + s0) + s1) + ..., continuing over the sample groups.
+// (One thread per pixel walking its own samples kept the additions and the loads in one lane: with the operands of a pending path
+// to fetch behind each flag test that was 10 ms per C3 step against the 0.45 ms of adding up L4 alone.)
 __global__ void __launch_bounds__(AGPT_BLOCK)
-AGPT_SHADE_KNAME(k_resolve_pending)(DevScene sc, RenderConsts rc, PathBuffers pb, Queues qin) {
-    const uint32_t n = QCOUNT(qin, 4);
-    for (uint32_t i = blockIdx.x * AGPT_BLOCK + threadIdx.x; i < n; i += gridDim.x * AGPT_BLOCK) {
-        const uint32_t pid = qin.resolve[i];
-        const float4 b4 = pb.beta4[pid];
-        float4 l4 = pb.L4[pid];
-        const float4 f4 = pb.fac4[pid];
-        const uint32_t was_occluded = pb.occluded[pid], was_mis_ok = pb.mis_ok[pid];
-        const float4 c1_4 = pb.c1[pid], c2_4 = pb.c2[pid];
-        const uint32_t flags = __float_as_uint(b4.w);
-        const v3 Ld = pending_light_sample(sc, rc, pb, pid, flags, was_occluded, was_mis_ok, c1_4, c2_4, f4);
-        const float lightPdf = sh_rcp(sc.n_lights);
-        const v3 L = V3(l4.x, l4.y, l4.z) + V3(b4.x, b4.y, b4.z) * sh_div3(Ld, lightPdf);
-        l4.x = L.x; l4.y = L.y; l4.z = L.z;
-        pb.L4[pid] = l4;
+AGPT_SHADE_KNAME(k_accumulate)(DevScene sc, RenderConsts rc, PathBuffers pb, float4* __restrict__ accum, DevCounters* __restrict__ counters) {
+    __shared__ float4 s_clr[AGPT_BLOCK];
+    const uint32_t G = sample_group(rc.S), per_block = AGPT_BLOCK / G;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t p0 = blockIdx.x * per_block;
+    const uint32_t pf = p0 + tid / G;                 // the pixel whose sample this thread finishes
+    const bool owner = tid < per_block && p0 + tid < rc.NP;   // ... and the one it adds up
+    float4 a = {0.f, 0.f, 0.f, 0.f};
+    size_t ai = 0;
+    if (owner) {
+        int x, y;
+        pixel_of(rc, p0 + tid, x, y, ai);
+        a = accum[ai];
     }
+    uint32_t bad = 0;
+    for (uint32_t sg = 0; sg < (uint32_t)rc.S / G; ++sg) {
+        if (pf < rc.NP) {
+            const uint32_t i = (sg * rc.NP + p0) * G + tid;   // = (sg * NP + pf) * G + tid % G (path ids fit 31 bits: agpt_render's batch limit)
+            v3 clr = finished_radiance(sc, rc, pb, i, pb.beta4[i], pb.L4[i]);
+            if (isnan(clr.x) || isnan(clr.y) || isnan(clr.z) || isinf(luminance(clr))) {
+                clr = V3s(0.f);
+                bad++;
+            }
+            float4 c4;
+            c4.x = clr.x; c4.y = clr.y; c4.z = clr.z; c4.w = 0.f;
+            s_clr[tid] = c4;
+        }
+        __syncthreads();
+        if (owner) {
+#pragma unroll 4
+            for (uint32_t j = 0; j < G; ++j) {   // (the order of the additions is the sample order)
+                const float4 c4 = s_clr[tid * G + j];
+                a.x += c4.x;
+                a.y += c4.y;
+                a.z += c4.z;
+            }
+        }
+        __syncthreads();
+    }
+    if (owner) accum[ai] = a;
+    if (bad) atomicAdd(&counters->outliers, (unsigned long long)bad);  // outliers are rare
+}
+
+// agpt_li_batch's consumer: Li's return value as it is (the NaN / inf filter belongs to MyApp::Tick, myapp.cpp:169-172, not to the
+// integrator) and the stream's state after the path, so that a host can go on drawing from it
+__global__ void __launch_bounds__(AGPT_BLOCK)
+AGPT_SHADE_KNAME(k_export_li)(DevScene sc, RenderConsts rc, PathBuffers pb, uint32_t n, float* __restrict__ radiance3, uint32_t* __restrict__ rng_out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 l4 = pb.L4[i];
+    const v3 L = finished_radiance(sc, rc, pb, i, pb.beta4[i], l4);
+    radiance3[3 * i] = L.x;
+    radiance3[3 * i + 1] = L.y;
+    radiance3[3 * i + 2] = L.z;
+    if (rng_out) rng_out[i] = __float_as_uint(l4.w);
+}
+
+// agpt_render_adaptive's consumer, k_accumulate_list, belongs to agpt_adaptive.hip, a unit with other code-generation options: for it
+// ONE pass over the batch's n paths, after its last iteration, puts a pending path's radiance into L4 and clears the flags
+// (idempotent).  No queue, no launch per iteration: it keeps the name of the per-iteration kernel it replaces, the one kernel of
+// these units that does nothing but add pending light samples.
+__global__ void __launch_bounds__(AGPT_BLOCK)
+AGPT_SHADE_KNAME(k_resolve_pending)(DevScene sc, RenderConsts rc, PathBuffers pb, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 b4 = pb.beta4[i];
+    const uint32_t flags = __float_as_uint(b4.w);
+    if (!(flags & PF_PENDING)) return;
+    float4 l4 = pb.L4[i];
+    const v3 L = finished_radiance(sc, rc, pb, i, b4, l4);
+    l4.x = L.x; l4.y = L.y; l4.z = L.z;
+    pb.L4[i] = l4;
+    b4.w = __uint_as_float(flags & ~(PF_PENDING | PF_PEND_C1 | PF_PEND_C2));
+    pb.beta4[i] = b4;
 }
 #endif
 
@@ -740,10 +821,17 @@ AGPT_SHADE_KNAME(k_resolve_pending)(DevScene sc, RenderConsts rc, PathBuffers pb
 namespace agpt {
 using ShadeLaunch = void(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
                          const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
-using ResolveLaunch = void(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, const Queues& qin);
+using AccumulateLaunch = void(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
+                               DevCounters* counters);
+using FinishPathsLaunch = void(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n);
 ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast, launch_shade_mapped, launch_shade_mapped_fast,
     launch_shade_sampled, launch_shade_sampled_fast, launch_shade_normal, launch_shade_normal_fast;
-ResolveLaunch launch_resolve_pending, launch_resolve_pending_fast;   // (the TEXTURED, MAPPED, SAMPLED and NORMAL units have none, see k_resolve_pending)
+// (the TEXTURED, MAPPED, SAMPLED and NORMAL units have none of these, see k_accumulate)
+AccumulateLaunch finish_accumulate, finish_accumulate_fast;
+FinishPathsLaunch finish_paths, finish_paths_fast;
+using ExportLiLaunch = void(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n, float* radiance3,
+                            uint32_t* rng_out);
+ExportLiLaunch finish_export_li, finish_export_li_fast;
 
 void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_tables, bool env, const DevScene& sc, const RenderConsts& rc,
                                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters,
@@ -759,9 +847,17 @@ void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_table
         hipLaunchKernelGGL((AGPT_SHADE_KNAME(k_shade)<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
 }
 #if !AGPT_SHADE_TEXTURED
-void AGPT_SHADE_KNAME(launch_resolve_pending)(hipStream_t stream, int grid, const DevScene& sc, const RenderConsts& rc,
-                                              const PathBuffers& pb, const Queues& qin) {
-    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_resolve_pending), dim3(grid), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, qin);
+static inline dim3 finish_blocks(uint64_t n) { return dim3((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)); }
+void AGPT_SHADE_KNAME(finish_accumulate)(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
+                                         DevCounters* counters) {
+    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_accumulate), finish_blocks((uint64_t)rc.NP * sample_group(rc.S))   /* blocks own AGPT_BLOCK / G pixels each */, dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, accum, counters);
+}
+void AGPT_SHADE_KNAME(finish_paths)(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n) {
+    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_resolve_pending), finish_blocks(n), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, n);
+}
+void AGPT_SHADE_KNAME(finish_export_li)(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n,
+                                        float* radiance3, uint32_t* rng_out) {
+    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_export_li), finish_blocks(n), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, n, radiance3, rng_out);
 }
 #endif
 }  // namespace agpt

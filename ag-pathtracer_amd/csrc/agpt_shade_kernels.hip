@@ -11,7 +11,7 @@ bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights) {
     return n_prims <= AGPT_SHADE_LDS_PRIMS && n_materials <= AGPT_SHADE_LDS_MATERIALS && n_lights <= AGPT_SHADE_LDS_LIGHTS;
 }
 
-void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, int resolve_grid, const DevScene& sc, const RenderConsts& rc,
+void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, const DevScene& sc, const RenderConsts& rc,
                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
     ShadeLaunch* const shade = v.normal     ? (v.fast ? launch_shade_normal_fast : launch_shade_normal)
                                : v.sampled  ? (v.fast ? launch_shade_sampled_fast : launch_shade_sampled)
@@ -19,10 +19,20 @@ void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, i
                                : v.textured ? (v.fast ? launch_shade_textured_fast : launch_shade_textured)
                                             : (v.fast ? launch_shade_fast : launch_shade);
     shade(stream, shade_grid, v.lds_tables, v.env, sc, rc, pb, qin, qout, counters, tile_heads);
-    // The TEXTURED, MAPPED, SAMPLED and NORMAL units have no k_resolve_pending (no BSDF and no material in it): their ended paths use the plain unit's of the same
-    // arithmetic.  (Independent of k_shade: different paths.)
-    ResolveLaunch* const resolve = v.fast ? launch_resolve_pending_fast : launch_resolve_pending;
-    resolve(stream, resolve_grid, sc, rc, pb, qin);
+}
+
+// The TEXTURED, MAPPED, SAMPLED and NORMAL units have no finishing kernels (no BSDF and no material in them): their batches use the plain
+// unit's of the same arithmetic.
+void launch_accumulate(hipStream_t stream, bool fast, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
+                       DevCounters* counters) {
+    (fast ? finish_accumulate_fast : finish_accumulate)(stream, sc, rc, pb, accum, counters);
+}
+void launch_export_li(hipStream_t stream, bool fast, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n,
+                      float* radiance3, uint32_t* rng_out) {
+    (fast ? finish_export_li_fast : finish_export_li)(stream, sc, rc, pb, n, radiance3, rng_out);
+}
+void launch_finish_paths(hipStream_t stream, bool fast, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n) {
+    (fast ? finish_paths_fast : finish_paths)(stream, sc, rc, pb, n);
 }
 
 }  // namespace agpt

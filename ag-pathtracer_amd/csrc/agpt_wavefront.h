@@ -1,7 +1,7 @@
 // agpt_wavefront.h -- what the kernels of the wavefront path tracer share: the per-path state in HBM (PathBuffers), the path-id
 // queues between the kernels, the per-batch constants, the path / pixel order and the counters.  Included by agpt_kernels.h
-// (trace, generate, accumulate, ...) and by agpt_shade_kernels.h (k_shade, k_resolve_pending), which are separate translation
-// units because they are compiled with different code-generation options (build.py).
+// (trace, generate, ...) and by agpt_shade_kernels.h (k_shade and the kernels that finish a batch: k_accumulate, k_export_li,
+// k_resolve_pending), which are separate translation units because they are compiled with different code-generation options (build.py).
 #pragma once
 
 #include "agpt_math.h"
@@ -13,7 +13,7 @@
 // path flags (beta4.w)
 #define PF_BOUNCE_MASK 0xFFu
 #define PF_SPECULAR 0x100u   // specularBounce
-#define PF_DEAD 0x200u       // path ended; only the pending NEE of its last vertex is left to resolve
+#define PF_DEAD 0x200u       // path ended; only the pending NEE of its last vertex is left to add (finished_radiance, agpt_shade_kernels.h)
 #define PF_PEND_C1 0x400u    // light-sampling leg contribution waits for its shadow ray
 #define PF_PEND_C2 0x800u    // BSDF-sampling leg contribution waits for its MIS ray
 #define PF_PENDING 0x1000u   // a vertex' UniformSampleOneLight result is still to be added to L
@@ -35,12 +35,13 @@ struct PathBuffers {
 #ifndef AGPT_FRONTIERS
 #define AGPT_FRONTIERS 8u
 #endif // work-queue frontiers per trace launch (one per XCD), AGPT_QSTRIDE words apart
+// ext: the live paths, each with a continuation ray -- what k_trace_fast<0> traces is what k_shade then shades.  A path that has
+// ended is in no queue: its last shadow ray / MIS query, if any, is in those two, and its radiance is complete once they are traced.
 struct Queues {
-    uint32_t *active, *ext, *mis, *shadow;   // path ids
-    uint32_t* resolve;                       // ended paths whose last light sample is still to be added (k_resolve_pending)
-    uint32_t* counts;                        // [q * AGPT_QSTRIDE]: q = 0 active, 1 ext, 2 mis, 3 shadow, 4 resolve
+    uint32_t *ext, *mis, *shadow;   // path ids
+    uint32_t* counts;               // [q * AGPT_QSTRIDE]: q = 0 ext, 1 mis, 2 shadow
 };
-#define AGPT_NQUEUES 5
+#define AGPT_NQUEUES 3
 #define QCOUNT(q, i) ((q).counts[(i) * AGPT_QSTRIDE])
 
 struct RenderConsts {
@@ -59,7 +60,7 @@ struct RenderConsts {
 // of two <= 64 that divides S (path id = ((s / G) * NP + p) * G + s % G), so that with 64 spp a wave starts on the 64 samples
 // of ONE pixel: the primary rays of a wave are one bundle and the first hits share a few triangles (-3.5 ms per C3 step over
 // one-sample-per-pixel waves).  Like the pixel order below, invisible outside.
-__device__ __forceinline__ uint32_t sample_group(int32_t S) {
+__host__ __device__ __forceinline__ uint32_t sample_group(int32_t S) {   // (host: k_accumulate's grid)
     const uint32_t low = (uint32_t)S & (0u - (uint32_t)S);
     return low < 64u ? low : 64u;
 }
@@ -147,9 +148,20 @@ bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights);
 struct ShadeVariant {
     bool fast, textured, mapped, sampled, normal, lds_tables, env;
 };
-// the shading of one wavefront iteration: k_shade over qin's active paths, k_resolve_pending over its ended ones
-void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, int resolve_grid, const DevScene& sc, const RenderConsts& rc,
+// the shading of one wavefront iteration: k_shade over qin's live paths
+void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, const DevScene& sc, const RenderConsts& rc,
                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads);
+// What consumes a finished batch.  A path that ended with its last light sample pending still has it in c1 / c2 / occluded / mis_ok:
+// it is added by finished_radiance, in the arithmetic of the shading unit `fast` names.
+// k_accumulate: the batch of rc into the accumulator, samples in sample order
+void launch_accumulate(hipStream_t stream, bool fast, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
+                       DevCounters* counters);
+// k_export_li: Li's return value (radiance3[3 n]) and, if asked for, the RNG end state of the paths 0 .. n of agpt_li_batch
+void launch_export_li(hipStream_t stream, bool fast, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n,
+                      float* radiance3, uint32_t* rng_out);
+// k_resolve_pending: the same for the consumer that lives in another unit (k_accumulate_list, agpt_adaptive.hip) -- one pass over the
+// finished batch's paths 0 .. n that leaves every path's radiance complete in L4
+void launch_finish_paths(hipStream_t stream, bool fast, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n);
 // the known-answer kernels of the fast-arithmetic unit (k_kat_bsdf_eval_fast, k_kat_bsdf_sample_fast; one lane per case, 64-lane blocks)
 void launch_kat_bsdf_eval_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* wi3, float* f3o,
                                float* pdfo);

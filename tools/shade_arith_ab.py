@@ -1,6 +1,6 @@
 """Developer measurement: exact against fast shading arithmetic (agpt_scene_set_shading_arith) in one process, on C3 at
 1080p / 64 spp and on one rank's share of an 8-way split of C5 at 4K (64 spp), each mode run three times, alternating, after a
-warm-up.  Per mode: step ms, trace ms, non-trace ms (k_shade, k_resolve_pending and the iteration's small launches), shaded
+warm-up.  Per mode: step ms, trace ms, non-trace ms (k_shade, k_generate, k_accumulate and the iteration's small launches), shaded
 vertices and non-trace ns per shaded vertex (medians).
     python tools/shade_arith_ab.py [--out profiles/shade_arith_ab.json] [--reps 3] [--scenes c3,c5] [--no-warmup]
 (--scenes c3 --reps 1 --no-warmup: exactly one C3 render per mode, for a rocprofv3 run whose sums are per step)"""

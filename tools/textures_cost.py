@@ -153,7 +153,7 @@ def main():
     if a.kernel_trace:
         rows = list(csv.DictReader(open(a.kernel_trace)))
         res["kernel_trace"] = {r["Name"].split("(")[0]: dict(calls=int(r["Calls"]), total_ms=float(r["TotalDurationNs"]) / 1e6)
-                               for r in rows if "k_shade" in r["Name"] or "k_resolve_pending" in r["Name"]}
+                               for r in rows if "k_shade" in r["Name"] or r["Name"].startswith("k_accumulate(") or r["Name"].startswith("k_accumulate_fast(")}
         if a.kernel_trace_run:   # where the kernel times come from: another run of this tool, under the profiler
             run = json.load(open(a.kernel_trace_run))
             if run["library_sha256"] != res["library_sha256"]:
