@@ -6,11 +6,10 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
  * The shipped product (ag-pathtracer_amd/, libagpt_hip.so) never links or imports it.
  *
- * PARITY PIN: the reference itself cannot be compiled in this image without stand-in headers
- * (template/precomp.h:20,41 include <io.h>/<windows.h> unconditionally), so this restatement is
- * pinned against outputs of the *unmodified* reference recorded in BASELINE.md section 2 / SURVEY.md
- * section 6 (smoke-scene mean RGB to 6 digits, exact ray counts of two 1-spp renders, BVH node counts,
- * first RNG float) -- see tests/test_oracle_pins.py.  What those do not cover is "parity unpinned".
+ * PARITY PIN: this restatement is held, function by function and per ray, to the reference's own hot path compiled in
+ * place against small stand-in platform headers (oracle/ref_standins, oracle/ref_hotpath.cpp -> tests/golden/refpin_*.npz
+ * -> tests/test_refpin.py), in both trig modes; and, for myapp.cpp's pixel loop and the global-stream render, to outputs of
+ * the *unmodified* reference recorded in BASELINE.md section 2 / SURVEY.md section 6 (tests/test_oracle_pins.py).
  */
 #ifndef AGPT_ORACLE_H
 #define AGPT_ORACLE_H

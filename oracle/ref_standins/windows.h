@@ -1,0 +1,11 @@
+// oracle/ref_standins -- TEST INFRASTRUCTURE ONLY.  Stand-in for a platform/SDK header that the reference's template/precomp.h includes
+// unconditionally; written for this project, it holds only what that header needs to parse (see oracle/Makefile, _ref/libref_hotpath.so).
+#pragma once
+#include <memory>
+#include <cstring>
+#include <cfloat>
+typedef void* HANDLE;
+typedef unsigned long DWORD;
+typedef struct { long long QuadPart; } LARGE_INTEGER;
+typedef struct { void* opaque; } CRITICAL_SECTION;
+#define __forceinline inline

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generates the golden fixtures of tests/golden/ from the CPU oracle (oracle/oracle.c, itself pinned to the
-reference's recorded outputs -- tests/test_oracle_pins.py).  The reference cannot run in this image, so these vectors
-are oracle outputs: they freeze today's pinned behaviour so that the oracle and the HIP path cannot drift together.
+reference's recorded outputs -- tests/test_oracle_pins.py -- and to the reference compiled in place -- tests/test_refpin.py,
+whose fixtures make_refpin_golden.py records from the reference itself).  THESE vectors are oracle outputs: they freeze today's
+pinned behaviour so that the oracle and the HIP path cannot drift together.
 
     python tests/golden/make_golden.py        (rewrites tests/golden/*.npz; commit the result)
 

@@ -1,8 +1,11 @@
 """Pins the CPU oracle (oracle/oracle.c) against outputs of the UNMODIFIED reference.
 
-The reference cannot be compiled in this image without stand-in headers, so the pins are the
-reference-run outputs the survey stage recorded in BASELINE.md section 2 / SURVEY.md section 6
-(same scenes, same global xorshift32 stream seeded 0x12345678, reference loop myapp.cpp:163-175):
+These pins are the reference-run outputs the survey stage recorded in BASELINE.md section 2 / SURVEY.md section 6 (same scenes,
+same global xorshift32 stream seeded 0x12345678, reference loop myapp.cpp:163-175).  They are aggregates, and they are what pins
+myapp.cpp's pixel loop and the global-stream render, which nothing else reaches.  The hot path below that loop is pinned function
+by function, per ray, against the reference's own code compiled in place with small stand-in platform headers
+(oracle/ref_standins, oracle/ref_hotpath.cpp -> tests/golden/refpin_*.npz -> tests/test_refpin.py): BSDFs, Scene::Intersect,
+BVHTriMesh's node bytes, CreateBackdrop, Camera and PathTracer::Li.  The aggregates:
 
   * first RandomFloat() from seed 0x12345678 = 0.52966851              
   * smoke scene 64x64 @1spp: mean RGB = (0.340035, 0.360720, 0.248226), 0 outliers, 71 BVH nodes
