@@ -5,32 +5,27 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libagpt_hip.so")
-# (source, extra flags): agpt_shade_kernels.hip -- k_shade and the finishing kernels k_accumulate, k_export_li, k_resolve_pending -- is compiled with MachineLICM off and k_shade
-# held to four waves per SIMD: the pass hoists the two v_mov of every fp64 polynomial coefficient of the trigonometry out of the
-# path loop and keeps the pairs live for the whole kernel (168 registers + 7-14 spilled against 134 + 0; at the 128 of four waves
-# 2 spilled).  Measured on C3: k_shade -3.5 ms per step; the same flag on the trace kernels costs them 2 ms, hence two units.
-SHADE_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
-# agpt_shade_kernels_fast.hip -- the same kernels with the fast value arithmetic (k_shade_fast, ...; agpt_shade_arith.h) -- keeps
-# the exact unit's flags: the sampling trigonometry (fp64) is still there, and measured on C3 three waves without spills (133
-# registers) cost 3 ms of non-trace time per step against four waves with 2 spilled.
-SHADE_FAST_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=4"]
-# agpt_shade_kernels_textured.hip / _textured_fast.hip -- k_shade for scenes with an image-textured material (AGPT_SHADE_TEXTURED) -- are
-# the same header compiled once more per arithmetic, with the flags of the unit they vary; agpt_shade_kernels_mapped.hip / _mapped_fast.hip
-# -- k_shade for scenes with a roughness / metallic map (AGPT_SHADE_TEXTURED 2) -- likewise, and agpt_shade_kernels_sampled.hip /
-# _sampled_fast.hip -- k_shade for scenes with a filtered, clamped or mirrored texture (AGPT_SHADE_TEXTURED 3), and agpt_shade_kernels_normal.hip /
-# _normal_fast.hip -- k_shade for scenes with a normal map (AGPT_SHADE_TEXTURED 4) -- are the same header again, but held to THREE waves per
-# SIMD: the fourth lookup's addresses and taps are live beside the other three's, and at the 128 registers of four waves the kernel spills
-# 10-19 of them; at three waves it needs 143-151 and spills none.  Measured on the all-bilinear mapped C3 with a normal map on every
-# material, interleaved processes on one GPU: non-trace time 114.9 ms at three waves against 118.1 ms at four (FAST: 111.1 against 112.8 ms; profiles/normal_map_c3.json).
-SHADE_NORMAL_FLAGS = ["-mllvm", "-disable-machine-licm", "-DAGPT_SHADE_WAVES=3"]
-SOURCES = ["agpt_api.hip", "agpt_shade_kernels.hip", "agpt_shade_kernels_fast.hip", "agpt_shade_kernels_textured.hip", "agpt_shade_kernels_textured_fast.hip",
-           "agpt_shade_kernels_mapped.hip", "agpt_shade_kernels_mapped_fast.hip", "agpt_shade_kernels_sampled.hip", "agpt_shade_kernels_sampled_fast.hip",
-           "agpt_shade_kernels_normal.hip", "agpt_shade_kernels_normal_fast.hip", "agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_temporal.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
-SOURCE_FLAGS = {"agpt_shade_kernels.hip": SHADE_FLAGS, "agpt_shade_kernels_fast.hip": SHADE_FAST_FLAGS,
-                "agpt_shade_kernels_textured.hip": SHADE_FLAGS, "agpt_shade_kernels_textured_fast.hip": SHADE_FAST_FLAGS,
-                "agpt_shade_kernels_mapped.hip": SHADE_FLAGS, "agpt_shade_kernels_mapped_fast.hip": SHADE_FAST_FLAGS,
-                "agpt_shade_kernels_sampled.hip": SHADE_FLAGS, "agpt_shade_kernels_sampled_fast.hip": SHADE_FAST_FLAGS,
-                "agpt_shade_kernels_normal.hip": SHADE_NORMAL_FLAGS, "agpt_shade_kernels_normal_fast.hip": SHADE_NORMAL_FLAGS}
+# The shading units: agpt_shade_kernels.h compiled once per texturing level (AGPT_SHADE_LEVEL, the table in that header) and arithmetic
+# (AGPT_SHADE_FAST, agpt_shade_arith.h), each with k_shade held to a number of waves per SIMD.
+# (file suffix, level, fast, waves per SIMD)
+SHADE_UNITS = [("", 0, 0, 4), ("_fast", 0, 1, 4), ("_textured", 1, 0, 4), ("_textured_fast", 1, 1, 4), ("_mapped", 2, 0, 4), ("_mapped_fast", 2, 1, 4),
+               ("_sampled", 3, 0, 4), ("_sampled_fast", 3, 1, 4), ("_normal", 4, 0, 3), ("_normal_fast", 4, 1, 3)]
+# Every shading unit -- at level 0 k_shade and the finishing kernels k_accumulate, k_export_li, k_resolve_pending -- is compiled with
+# MachineLICM off and, below the NORMAL level, k_shade held to four waves per SIMD: the pass hoists the two v_mov of every fp64 polynomial
+# coefficient of the trigonometry out of the path loop and keeps the pairs live for the whole kernel (168 registers + 7-14 spilled against
+# 134 + 0; at the 128 of four waves 2 spilled).  Measured on C3: k_shade -3.5 ms per step; the same flag on the trace kernels costs them
+# 2 ms, hence units of their own.
+# The fast-arithmetic units keep the exact units' flags: the sampling trigonometry (fp64) is still there, and measured on C3 three waves
+# without spills (133 registers) cost 3 ms of non-trace time per step against four waves with 2 spilled.
+# The NORMAL units are held to THREE waves per SIMD: the fourth lookup's addresses and taps are live beside the other three's, and at the
+# 128 registers of four waves the kernel spills 10-19 of them; at three waves it needs 143-151 and spills none.  Measured on the
+# all-bilinear mapped C3 with a normal map on every material, interleaved processes on one GPU: non-trace time 114.9 ms at three waves
+# against 118.1 ms at four (FAST: 111.1 against 112.8 ms; profiles/normal_map_c3.json).
+SHADE_FLAGS = ["-mllvm", "-disable-machine-licm"]
+SHADE_SOURCES = ["agpt_shade_kernels%s.hip" % suffix for suffix, _, _, _ in SHADE_UNITS]
+SOURCES = ["agpt_api.hip"] + SHADE_SOURCES + ["agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_temporal.hip",
+                                               "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+SOURCE_FLAGS = {src: SHADE_FLAGS + ["-DAGPT_SHADE_WAVES=%d" % waves] for src, (_, _, _, waves) in zip(SHADE_SOURCES, SHADE_UNITS)}
 HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h", "agpt_shade_arith.h",
            "agpt_host_scene.hpp", "agpt_bvh_device.h", "agpt_update.h", "agpt_adaptive.h", "agpt_denoise.h", "agpt_temporal.h", os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);

@@ -169,13 +169,11 @@ struct agpt_scene {
     std::vector<HostTexture> textures;
     std::vector<int32_t> material_texture;
     std::vector<uint32_t> material_param_slots;   // agpt_scene_set_material_param_texture: per material, param_slots_pack (0 = no map)
-    bool textured = false;   // set by agpt_scene_commit: a material has a texture or a map -> the TEXTURED shading / feature kernels
-    bool mapped = false;     // set by agpt_scene_commit: a material has a roughness / metallic map -> the MAPPED shading kernels
-    bool sampled = false;    // set by agpt_scene_commit: a material names a texture with a non-default sampler -> the SAMPLED kernels
+    // set by agpt_scene_commit: the highest texturing level a material needs -> which shading / feature kernels run (agpt_shade_kernels.h)
+    agpt::ShadeLevel shade_level = agpt::SHADE_PLAIN;
     // agpt_scene_set_material_normal_texture: per material the texture id (-1 = no normal map) and the scale
     std::vector<int32_t> material_normal_texture;
     std::vector<float> material_normal_scale;
-    bool normal = false;     // set by agpt_scene_commit: a material has a normal map -> the NORMAL kernels
     DevBuf<float4> d_tri_uv;
     DevBuf<DevTexture> d_textures;
     DevBuf<int32_t> d_material_texture;
@@ -646,16 +644,20 @@ static int sync_mirror(agpt_scene* s) {
 int agpt_scene_commit(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_commit: scene is NULL");
     if (const int rc = sync_mirror(s)) return rc;
-    bool textured = false, mapped = false, normal = false;
-    for (int32_t t : s->material_texture) textured = textured || t >= 0;
-    for (uint32_t slots : s->material_param_slots) mapped = mapped || slots != 0;
-    for (int32_t t : s->material_normal_texture) normal = normal || t >= 0;
-    textured = textured || mapped || normal;   // (the MAPPED and NORMAL kernels are TEXTURED ones: same uv records, same texture table)
-    // SAMPLED: a texture that a material names -- in its colour slot or in a parameter slot -- has a sampler of its own
-    bool sampled = false;
-    for (size_t m = 0; m < s->material_texture.size(); m++)
+    // The scene's texturing level: the highest one a material needs.  Every level's kernels are those of the level below plus one
+    // thing (same uv records, same texture table), so the conditions below compare against it.
+    bool has_texture = false, has_map = false, has_sampler = false, has_normal_map = false;
+    for (size_t m = 0; m < s->material_texture.size(); m++) {
+        has_texture = has_texture || s->material_texture[m] >= 0;
+        has_map = has_map || s->material_param_slots[m] != 0;
+        has_normal_map = has_normal_map || s->material_normal_texture[m] >= 0;
+        // a texture that the material names -- in its colour slot or in a parameter slot -- has a sampler of its own
         for (int t : {(int)s->material_texture[m], param_slot_texture(s->material_param_slots[m], 0), param_slot_texture(s->material_param_slots[m], 1)})
-            sampled = sampled || (t >= 0 && !s->textures[t].default_sampler());
+            has_sampler = has_sampler || (t >= 0 && !s->textures[t].default_sampler());
+    }
+    const agpt::ShadeLevel level = has_normal_map ? agpt::SHADE_NORMAL : has_sampler ? agpt::SHADE_SAMPLED : has_map ? agpt::SHADE_MAPPED
+                                   : has_texture  ? agpt::SHADE_TEXTURED : agpt::SHADE_PLAIN;
+    const bool textured = level >= agpt::SHADE_TEXTURED;
     if (textured)
         for (const agpt::HostPrim& hp : s->prims)
             if (hp.type != AGPT_PRIM_MESH && hp.material >= 0 &&
@@ -729,7 +731,7 @@ int agpt_scene_commit(agpt_scene* s) {
                 table[m] = (int32_t)(s->textures.size() + own_texels.size());
                 own_texels.push_back(std::vector<float4>(1, s->colors[m]));
             }
-        if (mapped || sampled || normal)   // (the SAMPLED and NORMAL kernels are MAPPED ones: they read the slots, all 0 in a scene without maps)
+        if (level >= agpt::SHADE_MAPPED)   // (the kernels above MAPPED read the slots too: all 0 in a scene without maps)
             table.insert(table.end(), s->material_param_slots.begin(), s->material_param_slots.end());
         textures.resize(s->textures.size() + own_texels.size());
         s->d_texels.resize(textures.size());
@@ -739,12 +741,12 @@ int agpt_scene_commit(agpt_scene* s) {
             textures[i].texels = s->d_texels[i].p;
             textures[i].width = own ? 1 : s->textures[i].width;
             textures[i].height = own ? 1 : s->textures[i].height;
-            if ((sampled || normal) && !own) {   // (only the SAMPLED and NORMAL kernels decode the size words, agpt_scene.h: DevTexture)
+            if (level >= agpt::SHADE_SAMPLED && !own) {   // (only the kernels from SAMPLED up decode the size words, agpt_scene.h: DevTexture)
                 textures[i].width = texture_size_pack(s->textures[i].width, s->textures[i].wrap_u, s->textures[i].filter);
                 textures[i].height = texture_size_pack(s->textures[i].height, s->textures[i].wrap_v, 0);
             }
         }
-        if (normal) {   // one DevNormalSlot per material behind the two halves (agpt_scene.h)
+        if (level == agpt::SHADE_NORMAL) {   // one DevNormalSlot per material behind the two halves (agpt_scene.h)
             static_assert(sizeof(DevNormalSlot) == 8 * sizeof(int32_t), "a normal slot is two 16-byte loads");
             const size_t off = (size_t)normal_slots_offset((int)s->materials.size());
             table.resize(off + 8 * s->materials.size(), 0);
@@ -762,10 +764,7 @@ int agpt_scene_commit(agpt_scene* s) {
         if ((rc = upload(s->d_material_texture, table, st))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
-    s->textured = textured;
-    s->mapped = mapped;
-    s->sampled = sampled;
-    s->normal = normal;
+    s->shade_level = level;
     s->dev.tri_uv = textured ? s->d_tri_uv.p : nullptr;
     s->dev.textures = textured ? s->d_textures.p : nullptr;
     s->dev.material_texture = textured ? s->d_material_texture.p : nullptr;
@@ -1147,10 +1146,7 @@ static int begin_wavefront(agpt_ctx* c, const agpt_scene* s, int enable_counters
     run.mis_mode = use_fast_trace(c, s->dev, run.count) && !c->mis_closest;
     run.timing = timing;
     run.shade.fast = s->shading_arith == AGPT_SHADING_FAST;   // agpt_scene_set_shading_arith
-    run.shade.textured = s->textured;                         // a material of the scene has a texture
-    run.shade.mapped = s->mapped;                             // ... a roughness / metallic map
-    run.shade.sampled = s->sampled;                           // ... a texture with a sampler of its own
-    run.shade.normal = s->normal;                             // ... a normal map
+    run.shade.level = s->shade_level;                         // agpt_scene_commit
     run.shade.lds_tables = shade_tables_fit_lds(s->dev);
     run.shade.env = !s->envs.empty();                         // an InfiniteAreaLight is present
     c->tev_used = 0;
@@ -1663,7 +1659,7 @@ int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* alb
     HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
     agpt::launch_feature_rays(c->stream, s->dev, rcn, c->ext_o.p, c->ext_d.p);
     trace_rays(c, s->dev, NP, false, 0);
-    agpt::launch_features(c->stream, s->dev, s->sampled, s->normal, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
+    agpt::launch_features(c->stream, s->dev, s->shade_level, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
                           (float4*)normal_depth_dev);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());

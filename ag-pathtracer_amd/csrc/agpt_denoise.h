@@ -33,9 +33,9 @@ __device__ __forceinline__ void feature_ray(const DevCamera& c, int x, int y, in
 namespace agpt {
 // the pixel-centre camera rays of the tile (rc.NP pixels in pixel_of order), ready for a closest-hit trace launch
 void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d);
-// colors: one float4 per material, rgb = the colour agpt_scene_add_material was given; sampled: a material of the scene names a texture with
-// a non-default sampler (agpt_scene_set_texture_sampler); normal: one has a normal map (agpt_scene_set_material_normal_texture)
-void launch_features(hipStream_t stream, const DevScene& sc, bool sampled, bool normal, const RenderConsts& rc, const float4* colors,
+// colors: one float4 per material, rgb = the colour agpt_scene_add_material was given; level: the scene's texturing
+// level (agpt_scene_commit), which picks the feature kernel
+void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, const RenderConsts& rc, const float4* colors,
                      const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth);
 // state = (c.rgb, v); v = -1 marks a pixel without samples
 void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,

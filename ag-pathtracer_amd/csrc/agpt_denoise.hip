@@ -261,19 +261,17 @@ static inline dim3 blocks_for(uint64_t n) { return dim3((unsigned)((n + AGPT_BLO
 void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d) {
     hipLaunchKernelGGL(k_feature_rays, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc.cam, rc, ray_o, ray_d);
 }
-void launch_features(hipStream_t stream, const DevScene& sc, bool sampled, bool normal, const RenderConsts& rc, const float4* colors,
+void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, const RenderConsts& rc, const float4* colors,
                      const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth) {
-    if (normal)      // a material has a normal map (the lookups are the next case's)
-        hipLaunchKernelGGL(k_features_normal, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
-                           normal_depth);
-    else if (sampled)     // a material names a texture with a sampler of its own (which implies the next case)
-        hipLaunchKernelGGL(k_features_sampled, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
-                           normal_depth);
-    else if (sc.tri_uv)   // the scene has a textured material
-        hipLaunchKernelGGL(k_features_textured, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo,
-                           normal_depth);
-    else
-        hipLaunchKernelGGL(k_features, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+    auto* kernel = k_features;   // SHADE_PLAIN
+    switch (level) {
+    case SHADE_TEXTURED:
+    case SHADE_MAPPED: kernel = k_features_textured; break;   // (the albedo is the colour slot's nearest texel at both levels)
+    case SHADE_SAMPLED: kernel = k_features_sampled; break;
+    case SHADE_NORMAL: kernel = k_features_normal; break;
+    default: break;
+    }
+    hipLaunchKernelGGL(kernel, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
 void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,
                             float4* state) {

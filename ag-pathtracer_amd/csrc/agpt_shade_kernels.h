@@ -12,48 +12,41 @@
 #include "agpt_trace.h"   // TraceRay + sphere_test_c: MIS queries answered without a traversal
 #include "agpt_wavefront.h"
 
-// The kernels of a unit compiled with AGPT_SHADE_FAST 1 (agpt_shade_kernels_fast.hip, agpt_shade_arith.h) carry the suffix
-// _fast: their host-side stubs would otherwise collide with the exact unit's at link time.
-// A unit compiled with AGPT_SHADE_TEXTURED 1 (agpt_shade_kernels_textured.hip, agpt_shade_kernels_textured_fast.hip) holds the
-// TEXTURED variant of k_shade -- a material's colour at a mesh hit comes from its image texture (agpt_scene.h: tri_uv, textures,
-// material_texture) -- as k_shade_textured / k_shade_textured_fast; the launchers pick it for scenes that have a textured
-// material, every other scene runs the kernels of the two plain units, whose code the flag does not touch.
-// AGPT_SHADE_TEXTURED 2 (agpt_shade_kernels_mapped.hip, agpt_shade_kernels_mapped_fast.hip) is the MAPPED variant on top of it -- roughness
-// and metallic at a mesh hit come from image textures too (agpt_scene.h: param_slots_pack), so the whole Disney constructor runs per
-// hit -- as k_shade_mapped / k_shade_mapped_fast, for scenes in which a material has such a map; it leaves the code of the other four
-// units alone in the same way.
-// AGPT_SHADE_TEXTURED 3 (agpt_shade_kernels_sampled.hip, agpt_shade_kernels_sampled_fast.hip) is the SAMPLED variant on top of that -- the MAPPED
-// kernel whose lookups honour each texture's sampler (agpt_scene.h: DevTexture; bilinear filtering, clamp and mirror wrap) -- as
-// k_shade_sampled / k_shade_sampled_fast, for scenes in which a material names a texture with a non-default sampler.  One level covers
-// the colour slot and both maps; the other six units are left alone in the same way.
-// AGPT_SHADE_TEXTURED 4 (agpt_shade_kernels_normal.hip, agpt_shade_kernels_normal_fast.hip) is the NORMAL variant on top of that -- the SAMPLED
-// kernel plus the normal-map slot (agpt_scene.h: DevNormalSlot; agpt_shade.h: surface_apply_normal_map), whose taps ride in the same round
-// trip as the other slots' -- as k_shade_normal / k_shade_normal_fast, for scenes in which a material has a normal map; the other eight
-// units are left alone in the same way.
-#ifndef AGPT_SHADE_TEXTURED
-#define AGPT_SHADE_TEXTURED 0
+// The texturing levels (AGPT_SHADE_LEVEL here, agpt::ShadeLevel on the host).  Each level is the one below plus one thing, and is
+// compiled as a unit of its own per arithmetic (agpt_shade_kernels<suffix>.hip, agpt_shade_kernels<suffix>_fast.hip), so adding a level
+// leaves the code of the units below it alone.  agpt_scene_commit gives a scene the highest level that one of its materials needs.
+//   level       adds, at a mesh hit                                                     kernel              selected by
+//   0 PLAIN     --                                                                      k_shade             (a scene without textures)
+//   1 TEXTURED  the material's colour comes from its image texture                      k_shade_textured    agpt_scene_set_material_texture
+//               (agpt_scene.h: tri_uv, textures, material_texture)
+//   2 MAPPED    roughness and metallic come from image textures too (param_slots_pack), k_shade_mapped      agpt_scene_set_material_param_texture
+//               so the whole Disney constructor runs per hit
+//   3 SAMPLED   the lookups honour each texture's sampler (DevTexture: bilinear         k_shade_sampled     agpt_scene_set_texture_sampler, non-default,
+//               filtering, clamp and mirror wrap), colour slot and both maps alike                          on a texture that a material names
+//   4 NORMAL    the normal-map slot (DevNormalSlot; agpt_shade.h:                       k_shade_normal      agpt_scene_set_material_normal_texture
+//               surface_apply_normal_map), its taps in the other slots' round trip
+// One row per level: (level, suffix of the unit's file, kernels and launcher).
+#define AGPT_SHADE_LEVEL_LIST(X) X(0, ) X(1, _textured) X(2, _mapped) X(3, _sampled) X(4, _normal)
+#ifndef AGPT_SHADE_LEVEL
+#define AGPT_SHADE_LEVEL 0
 #endif
-#if AGPT_SHADE_TEXTURED == 4 && AGPT_SHADE_FAST
-#define AGPT_SHADE_KNAME(n) n##_normal_fast
-#elif AGPT_SHADE_TEXTURED == 4
-#define AGPT_SHADE_KNAME(n) n##_normal
-#elif AGPT_SHADE_TEXTURED == 3 && AGPT_SHADE_FAST
-#define AGPT_SHADE_KNAME(n) n##_sampled_fast
-#elif AGPT_SHADE_TEXTURED == 3
-#define AGPT_SHADE_KNAME(n) n##_sampled
-#elif AGPT_SHADE_TEXTURED == 2 && AGPT_SHADE_FAST
-#define AGPT_SHADE_KNAME(n) n##_mapped_fast
-#elif AGPT_SHADE_TEXTURED == 2
-#define AGPT_SHADE_KNAME(n) n##_mapped
-#elif AGPT_SHADE_TEXTURED && AGPT_SHADE_FAST
-#define AGPT_SHADE_KNAME(n) n##_textured_fast
-#elif AGPT_SHADE_TEXTURED
-#define AGPT_SHADE_KNAME(n) n##_textured
-#elif AGPT_SHADE_FAST
-#define AGPT_SHADE_KNAME(n) n##_fast
+// A unit's kernels and launchers are named name + its level's suffix + _fast for a unit compiled with AGPT_SHADE_FAST 1
+// (agpt_shade_arith.h): the host-side stubs of two units would otherwise collide at link time.
+#if AGPT_SHADE_FAST
+#define AGPT_SHADE_FAST_SUFFIX _fast
 #else
-#define AGPT_SHADE_KNAME(n) n
+#define AGPT_SHADE_FAST_SUFFIX
 #endif
+#define AGPT_SHADE_NTH_0(s0, ...) s0
+#define AGPT_SHADE_NTH_1(s0, s1, ...) s1
+#define AGPT_SHADE_NTH_2(s0, s1, s2, ...) s2
+#define AGPT_SHADE_NTH_3(s0, s1, s2, s3, ...) s3
+#define AGPT_SHADE_NTH_4(s0, s1, s2, s3, s4, ...) s4
+#define AGPT_SHADE_SUFFIX_ARG(level, suffix) suffix,
+#define AGPT_SHADE_CAT_(a, b, c) a##b##c
+#define AGPT_SHADE_CAT(a, b, c) AGPT_SHADE_CAT_(a, b, c)
+#define AGPT_SHADE_NTH(n, list) AGPT_SHADE_CAT(AGPT_SHADE_NTH_, n, )(list)   // (the list's commas separate arguments only on this rescan)
+#define AGPT_SHADE_KNAME(n) AGPT_SHADE_CAT(n, AGPT_SHADE_NTH(AGPT_SHADE_LEVEL, AGPT_SHADE_LEVEL_LIST(AGPT_SHADE_SUFFIX_ARG)), AGPT_SHADE_FAST_SUFFIX)
 
 // ---------------------------------------------------------------------------------------------------------
 // PathTracer::Li's loop body (integrator.h:132-188) in wavefront form, for one path.  Returns which of the next
@@ -108,22 +101,22 @@ __device__ __forceinline__ v3 pending_light_sample(const DevScene& sc, const Ren
 // ENV: the scene has an InfiniteAreaLight (lights.cpp:31-112).  Its sampling / pdf / Le helpers are out-of-line calls whose mere
 // presence costs the register allocation of every path (values live across a call site go to callee-saved registers); scenes
 // without an environment map -- every BASELINE configuration -- run the instantiation that does not contain them.
-// TEXTURED: see AGPT_SHADE_TEXTURED above.  The hit triangle's two uv records are fetched beside its tri_shade record (one more
+// TEXTURED (level 1 above): the hit triangle's two uv records are fetched beside its tri_shade record (one more
 // pair of 16-B loads in the same round trip); the texel gather follows the material lookup, and material_set_color puts what
 // make_material derives from a colour -- diffuse_R, R0, mirror_R -- into a register copy of the material, which is what
 // bsdf_setup, lobe_eval, disney_fresnel and lobe_sample then read.
-// MAPPED: see AGPT_SHADE_TEXTURED 2 above.  Up to three texels per vertex (colour, roughness, metallic), one gather per DISTINCT
+// MAPPED (level 2): up to three texels per vertex (colour, roughness, metallic), one gather per DISTINCT
 // texture -- slots that name the same image, as glTF's metallic-roughness image does, share its texel -- all issued before
 // material_set_disney rebuilds the register copy, lobe set included.
-// SAMPLED: see AGPT_SHADE_TEXTURED 3 above.  MAPPED with texture_address / texture_load / texture_blend (agpt_shade.h) in texture_value's place: one tap of a NEAREST
+// SAMPLED (level 3): MAPPED with texture_address / texture_load / texture_blend (agpt_shade.h) in texture_value's place: one tap of a NEAREST
 // texture, four of a BILINEAR one, the taps of every distinct texture issued before the first blend (up to twelve 16-B gathers in
 // flight behind the material lookup instead of three round trips of four).
-// NORMAL: see AGPT_SHADE_TEXTURED 4 above.  SAMPLED with a fourth lookup: the material's DevNormalSlot is read from the global-memory table
+// NORMAL (level 4): SAMPLED with a fourth lookup: the material's DevNormalSlot is read from the global-memory table
 // (`normal_table`: sc.material_texture before the LDS copy took its place; nullptr in every other variant) beside the other slots' texture
 // records, its address and its taps are formed and issued with theirs -- up to sixteen gathers in one round trip; an image that another
 // slot names shares that slot's taps -- and surface_apply_normal_map perturbs the shading normal before bsdf_setup.
-template <bool ENV, bool TEXTURED = (AGPT_SHADE_TEXTURED != 0), bool MAPPED = (AGPT_SHADE_TEXTURED >= 2), bool SAMPLED = (AGPT_SHADE_TEXTURED >= 3),
-          bool NORMAL = (AGPT_SHADE_TEXTURED == 4)>
+template <bool ENV, bool TEXTURED = (AGPT_SHADE_LEVEL >= 1), bool MAPPED = (AGPT_SHADE_LEVEL >= 2), bool SAMPLED = (AGPT_SHADE_LEVEL >= 3),
+          bool NORMAL = (AGPT_SHADE_LEVEL == 4)>
 __device__ __forceinline__ uint32_t shade_path(const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t pid,
                                                const int32_t* normal_table SCK_PARAMS) {
     uint32_t bits = 0;
@@ -561,11 +554,11 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
     __shared__ DevPrim s_tab_prims[LDS_TABLES ? AGPT_SHADE_LDS_PRIMS : 1];
     __shared__ DevMaterial s_tab_materials[LDS_TABLES ? AGPT_SHADE_LDS_MATERIALS : 1];
     __shared__ DevLight s_tab_lights[LDS_TABLES ? AGPT_SHADE_LDS_LIGHTS : 1];
-#if AGPT_SHADE_TEXTURED
+#if AGPT_SHADE_LEVEL
     // 512 B beside the 9.5 KB of materials; MAPPED, SAMPLED: both halves of the table, 1 KB (40,960 B per block in all: still four blocks
     // per CU; the sampler state rides in the texture records, agpt_scene.h).  NORMAL: the same 1 KB -- a fifth block-wide kilobyte would
     // cost the fourth block of the CU, so the normal slots stay in global memory
-    constexpr int n_tab_halves = AGPT_SHADE_TEXTURED >= 2 ? 2 : 1;
+    constexpr int n_tab_halves = AGPT_SHADE_LEVEL >= 2 ? 2 : 1;
     __shared__ int32_t s_tab_material_texture[LDS_TABLES ? n_tab_halves * AGPT_SHADE_LDS_MATERIALS : 1];
 #endif
     // (a launch over a short queue: one wave per 256-path tile is all it can use -- the rest of the grid leaves before setting up)
@@ -583,7 +576,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
         sc.prims = s_tab_prims;
         sc.materials = s_tab_materials;
         sc.lights = s_tab_lights;
-#if AGPT_SHADE_TEXTURED
+#if AGPT_SHADE_LEVEL
         copy_words(s_tab_material_texture, sc_in.material_texture, n_tab_halves * sc_in.n_materials * (int)sizeof(int32_t));
         sc.material_texture = s_tab_material_texture;
 #endif
@@ -661,7 +654,7 @@ AGPT_SHADE_KNAME(k_shade)(DevScene sc_in, RenderConsts rc, PathBuffers pb, Queue
             uint32_t pid = 0, bits = 0;
             if (qi < n_active) {
                 pid = qin.ext[qi];
-                bits = shade_path<ENV>(sc, rc, pb, pid, AGPT_SHADE_TEXTURED == 4 ? sc_in.material_texture : nullptr SCK_ARGS);
+                bits = shade_path<ENV>(sc, rc, pb, pid, AGPT_SHADE_LEVEL == 4 ? sc_in.material_texture : nullptr SCK_ARGS);
             }
             s_pid[u][tid] = pid;     // (slots private to the thread: no synchronisation)
             s_bits[u][tid] = bits;
@@ -729,7 +722,7 @@ __device__ __forceinline__ v3 finished_radiance(const DevScene& sc, const Render
     return L + V3(b4.x, b4.y, b4.z) * sh_div3(Ld, lightPdf);   // integrator.h:166
 }
 
-#if !AGPT_SHADE_TEXTURED   // (no BSDF, no material: every scene runs the plain unit's kernels of its arithmetic)
+#if !AGPT_SHADE_LEVEL   // (no BSDF, no material: every scene runs the plain unit's kernels of its arithmetic)
 // myapp.cpp:169-173 NaN/inf reject + Accumulator::AddSample (myapp.h:17-19): samples are added in sample order.
 // A block owns AGPT_BLOCK / G pixels (G = sample_group: a pixel's samples lie in runs of G consecutive path ids, so the block's runs
 // of one sample group are AGPT_BLOCK consecutive ids).  Per sample group every thread finishes ONE path -- the reads of L4, beta4 and
@@ -824,9 +817,10 @@ using ShadeLaunch = void(hipStream_t stream, int grid, bool lds_tables, bool env
 using AccumulateLaunch = void(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
                                DevCounters* counters);
 using FinishPathsLaunch = void(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n);
-ShadeLaunch launch_shade, launch_shade_fast, launch_shade_textured, launch_shade_textured_fast, launch_shade_mapped, launch_shade_mapped_fast,
-    launch_shade_sampled, launch_shade_sampled_fast, launch_shade_normal, launch_shade_normal_fast;
-// (the TEXTURED, MAPPED, SAMPLED and NORMAL units have none of these, see k_accumulate)
+#define X(level, suffix) ShadeLaunch launch_shade##suffix, launch_shade##suffix##_fast;
+AGPT_SHADE_LEVEL_LIST(X)
+#undef X
+// (only the two level-0 units have these, see k_accumulate)
 AccumulateLaunch finish_accumulate, finish_accumulate_fast;
 FinishPathsLaunch finish_paths, finish_paths_fast;
 using ExportLiLaunch = void(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n, float* radiance3,
@@ -846,7 +840,7 @@ void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_table
     else
         hipLaunchKernelGGL((AGPT_SHADE_KNAME(k_shade)<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
 }
-#if !AGPT_SHADE_TEXTURED
+#if !AGPT_SHADE_LEVEL
 static inline dim3 finish_blocks(uint64_t n) { return dim3((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)); }
 void AGPT_SHADE_KNAME(finish_accumulate)(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
                                          DevCounters* counters) {

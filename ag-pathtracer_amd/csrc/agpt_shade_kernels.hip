@@ -1,6 +1,8 @@
 // agpt_shade_kernels.hip -- translation unit of the shading kernels (agpt_shade_kernels.h) and their host-side launchers (the unit's own come with the header; launch_shading picks the unit).
 // build.py compiles it with -mllvm -disable-machine-licm (see the header for why); everything else of the library is in
 // agpt_api.hip.
+#define AGPT_SHADE_LEVEL 0
+#define AGPT_SHADE_FAST 0
 #include <hip/hip_runtime.h>
 
 #include "agpt_shade_kernels.h"
@@ -13,15 +15,13 @@ bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights) {
 
 void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, const DevScene& sc, const RenderConsts& rc,
                     const PathBuffers& pb, const Queues& qin, const Queues& qout, DevCounters* counters, uint32_t* tile_heads) {
-    ShadeLaunch* const shade = v.normal     ? (v.fast ? launch_shade_normal_fast : launch_shade_normal)
-                               : v.sampled  ? (v.fast ? launch_shade_sampled_fast : launch_shade_sampled)
-                               : v.mapped   ? (v.fast ? launch_shade_mapped_fast : launch_shade_mapped)
-                               : v.textured ? (v.fast ? launch_shade_textured_fast : launch_shade_textured)
-                                            : (v.fast ? launch_shade_fast : launch_shade);
-    shade(stream, shade_grid, v.lds_tables, v.env, sc, rc, pb, qin, qout, counters, tile_heads);
+#define X(level, suffix) {launch_shade##suffix, launch_shade##suffix##_fast},
+    static ShadeLaunch* const table[SHADE_LEVELS][2] = {AGPT_SHADE_LEVEL_LIST(X)};   // (rows in level order)
+#undef X
+    table[v.level][v.fast](stream, shade_grid, v.lds_tables, v.env, sc, rc, pb, qin, qout, counters, tile_heads);
 }
 
-// The TEXTURED, MAPPED, SAMPLED and NORMAL units have no finishing kernels (no BSDF and no material in them): their batches use the plain
+// The units above level 0 have no finishing kernels (no BSDF and no material in them): their batches use the plain
 // unit's of the same arithmetic.
 void launch_accumulate(hipStream_t stream, bool fast, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
                        DevCounters* counters) {

@@ -2,6 +2,7 @@
 // agpt_shade_arith.h): k_shade_fast, the finishing kernels k_accumulate_fast, k_export_li_fast and k_resolve_pending_fast and the BSDF known-answer kernels k_kat_bsdf_*_fast, with their
 // host-side launchers.  agpt_scene_set_shading_arith(AGPT_SHADING_FAST) selects them.  The unit keeps -ffp-contract=off
 // -fno-fast-math like every other: agpt_trace.h, which it includes for sphere_test_c, must answer a ray as the trace kernels do.
+#define AGPT_SHADE_LEVEL 0
 #define AGPT_SHADE_FAST 1
 #include <hip/hip_runtime.h>
 

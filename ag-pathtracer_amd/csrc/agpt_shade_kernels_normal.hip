@@ -1,8 +1,6 @@
-// agpt_shade_kernels_normal.hip -- k_shade_normal: the NORMAL variant of the shading kernel (AGPT_SHADE_TEXTURED 4, agpt_shade_kernels.h).
-// agpt_scene_set_material_normal_texture on any material of a scene selects it at launch; every other scene never runs it.  Flags of
-// agpt_shade_kernels.hip (MachineLICM off, -ffp-contract=off), but three waves per SIMD: no spilled registers, and measured faster
-// than four waves with spills (build.py).
-#define AGPT_SHADE_TEXTURED 4
+// agpt_shade_kernels_normal.hip -- k_shade_normal: the shading kernel of level 4 (NORMAL) in exact arithmetic; see the table in agpt_shade_kernels.h.
+#define AGPT_SHADE_LEVEL 4
+#define AGPT_SHADE_FAST 0
 #include <hip/hip_runtime.h>
 
 #include "agpt_shade_kernels.h"

@@ -1,9 +1,6 @@
-// agpt_shade_kernels_sampled_fast.hip -- k_shade_sampled_fast: the SAMPLED variant of the shading kernel (AGPT_SHADE_TEXTURED 3, agpt_shade_kernels.h) in fast arithmetic (AGPT_SHADE_FAST, agpt_shade_arith.h).
-// agpt_scene_set_texture_sampler with a filter or a wrap mode other than the default, on a texture that a material of the scene names,
-// selects it at launch; every other scene never runs it.  Same flags as agpt_shade_kernels_fast.hip (MachineLICM off, four waves per SIMD,
-// -ffp-contract=off).
+// agpt_shade_kernels_sampled_fast.hip -- k_shade_sampled_fast: the shading kernel of level 3 (SAMPLED) in fast arithmetic; see the table in agpt_shade_kernels.h.
+#define AGPT_SHADE_LEVEL 3
 #define AGPT_SHADE_FAST 1
-#define AGPT_SHADE_TEXTURED 3
 #include <hip/hip_runtime.h>
 
 #include "agpt_shade_kernels.h"

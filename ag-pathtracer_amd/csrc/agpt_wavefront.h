@@ -137,16 +137,18 @@ __device__ __forceinline__ void queue_push(uint32_t* q, uint32_t* count, bool pr
 
 
 // ---------------------------------------------------------------------------------------------------------
-// host side of the shading translation units (agpt_shade_kernels.hip, agpt_shade_kernels_fast.hip and their _textured, _mapped, _sampled and _normal twins)
+// host side of the shading translation units (agpt_shade_kernels*.hip)
 namespace agpt {
 // the scene's Scene::primitives records, materials and lights fit the LDS copies k_shade<LDS_TABLES> works from
 bool shade_tables_fit_lds(int n_prims, int n_materials, int n_lights);
-// Which shading kernels an iteration runs: the unit (fast: agpt_scene_set_shading_arith(AGPT_SHADING_FAST); textured: a material of
-// the scene has a texture; mapped: one has a roughness / metallic map, which implies textured; sampled: one names a texture with a
-// non-default sampler, which implies textured and takes the place of mapped; normal: one has a normal map, which takes the place of
-// sampled) and k_shade's <LDS_TABLES, ENV> instantiation in it.
+// The texturing level of a scene: each level is the one below plus what its row in agpt_shade_kernels.h's table adds.
+// agpt_scene_commit derives it, and it picks the shading unit (launch_shading) and the feature kernel (launch_features).
+enum ShadeLevel { SHADE_PLAIN = 0, SHADE_TEXTURED = 1, SHADE_MAPPED = 2, SHADE_SAMPLED = 3, SHADE_NORMAL = 4, SHADE_LEVELS = 5 };
+// Which shading kernels an iteration runs: the unit (level; fast: agpt_scene_set_shading_arith(AGPT_SHADING_FAST)) and k_shade's
+// <LDS_TABLES, ENV> instantiation in it.
 struct ShadeVariant {
-    bool fast, textured, mapped, sampled, normal, lds_tables, env;
+    ShadeLevel level;
+    bool fast, lds_tables, env;
 };
 // the shading of one wavefront iteration: k_shade over qin's live paths
 void launch_shading(hipStream_t stream, const ShadeVariant& v, int shade_grid, const DevScene& sc, const RenderConsts& rc,
