@@ -38,7 +38,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
@@ -187,6 +187,10 @@ def lib():
     L.agpt_bvh_build.argtypes = [fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.agpt_bvh_refit.argtypes = [fp, C.c_int, ip, C.c_int, ip, vp, C.c_int]
     L.agpt_scene_update_mesh.argtypes = [vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int]
+    for name, args in (("agpt_scene_update_mesh_device", [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int]),
+                       ("agpt_scene_transform_mesh", [vp, C.c_int, fp, C.c_int]), ("agpt_transform_arrays", [fp, fp, C.c_int, fp, C.c_int, fp, fp])):
+        if not variant or hasattr(L, name):   # (an A/B variant built from an older commit lacks them: tools/mesh_update_time.py --parent-lib)
+            getattr(L, name).argtypes = args
     L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
     L.agpt_scene_set_shading_arith.argtypes = [vp, C.c_int]
     L.agpt_bvh_build_device.argtypes = [vp, fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -372,6 +376,21 @@ def load_obj(path=None, text=None, transform=None, ignore_normals=False):
     return v, (n if nn.value else None), (t if nt.value else None), ix
 
 
+def transform_arrays(matrix4x4, verts, normals=None):
+    """agpt_transform_arrays on the host (no GPU needed): positions through the row-major 4x4 as the reference's TransformPoint,
+    normals through TransformVector of its inverse transpose -> (verts[n, 3], normals[m, 3] or None), the arithmetic of load_obj's
+    `transform` and of Scene.transform_mesh."""
+    m = np.ascontiguousarray(matrix4x4, np.float32).reshape(16)
+    v, pv = _f(np.asarray(verts).reshape(-1, 3))
+    n, pn = (None, None) if normals is None else _f(np.asarray(normals).reshape(-1, 3))
+    vo = np.empty_like(v)
+    no = None if n is None else np.empty_like(n)
+    fp = C.POINTER(C.c_float)
+    _check(lib().agpt_transform_arrays(m.ctypes.data_as(fp), pv, v.shape[0], pn, 0 if n is None else n.shape[0], vo.ctypes.data_as(fp),
+                                       None if no is None else no.ctypes.data_as(fp)), "agpt_transform_arrays")
+    return vo, no
+
+
 class Context:
     """One GPU. `stream` may be a raw hipStream_t handle (e.g. torch.cuda.current_stream().cuda_stream)."""
 
@@ -381,10 +400,12 @@ class Context:
         _check(self.L.agpt_init(int(device), C.byref(h)), "agpt_init")
         self.h = h
         self.device = device
+        self.stream = 0
         if stream is not None:
             self.set_stream(stream)
 
     def set_stream(self, stream):
+        self.stream = int(stream) if stream else 0
         _check(self.L.agpt_set_stream(self.h, C.c_void_p(int(stream) if stream else 0)), "agpt_set_stream")
 
     def close(self):
@@ -616,18 +637,66 @@ class Scene:
                                                  ix.shape[0], int(material), int(max_prims_in_node)),
                       "agpt_scene_add_mesh")
 
+    @staticmethod
+    def _update_mode(mode, what):
+        if isinstance(mode, str):
+            if mode not in ("refit", "rebuild"):
+                raise ValueError("%s: unknown mode %r (refit, rebuild)" % (what, mode))
+            mode = UPDATE_REFIT if mode == "refit" else UPDATE_REBUILD
+        return int(mode)
+
+    def _device_tensor(self, t, what):
+        """data_ptr of a torch tensor handed to update_mesh: contiguous float32 (n, 3) on the context's GPU"""
+        import torch
+        if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.ctx.device:
+            raise ValueError("update_mesh: %s is on %s, the context is on GPU %d (a CPU tensor goes through .numpy())" % (what, t.device, self.ctx.device))
+        if t.dtype != torch.float32:
+            raise ValueError("update_mesh: %s is %s, not float32" % (what, t.dtype))
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("update_mesh: %s has shape %s, not (n, 3)" % (what, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("update_mesh: %s is not contiguous" % what)
+        return t.data_ptr()
+
     def update_mesh(self, prim, verts, normals=None, mode=UPDATE_REFIT):
         """agpt_scene_update_mesh: new positions (and vertex normals, if the mesh has any) for mesh primitive `prim` of the committed
         scene.  mode: UPDATE_REFIT / "refit" (the tree keeps its topology, the mesh's records are rewritten on the GPU) or
-        UPDATE_REBUILD / "rebuild" (a new BVH and the full upload)."""
-        if isinstance(mode, str):
-            if mode not in ("refit", "rebuild"):
-                raise ValueError("update_mesh: unknown mode %r (refit, rebuild)" % mode)
-            mode = UPDATE_REFIT if mode == "refit" else UPDATE_REBUILD
+        UPDATE_REBUILD / "rebuild" (a new BVH and the full upload).
+        torch tensors on the context's GPU (contiguous float32, shape (n, 3)) are handed over as device pointers
+        (agpt_scene_update_mesh_device) after torch's current stream has been synchronised -- unless the context runs on that very
+        stream; anything else (ndarray, list, CPU tensor) goes through the host call."""
+        mode = self._update_mode(mode, "update_mesh")
+        tensors = [type(a).__module__.split(".")[0] == "torch" and a.device.type != "cpu" for a in (verts, normals)]
+        if tensors[0] or tensors[1]:
+            import torch
+            if not tensors[0] or (normals is not None and not tensors[1]):
+                raise ValueError("update_mesh: positions and normals must both be device tensors, or neither")
+            pv = self._device_tensor(verts, "verts")
+            pn = None if normals is None else self._device_tensor(normals, "normals")
+            stream = torch.cuda.current_stream(verts.device)
+            if not self.ctx.stream or int(stream.cuda_stream) != self.ctx.stream:   # (a context on the null stream always waits)
+                stream.synchronize()
+            _check(self.L.agpt_scene_update_mesh_device(self.h, int(prim), C.c_void_p(pv), verts.shape[0], C.c_void_p(pn),
+                                                        0 if normals is None else normals.shape[0], mode), "agpt_scene_update_mesh_device")
+            return
         v, pv = _f(np.asarray(verts).reshape(-1, 3))
         n, pn = (None, None) if normals is None else _f(np.asarray(normals).reshape(-1, 3))
-        _check(self.L.agpt_scene_update_mesh(self.h, int(prim), pv, v.shape[0], pn, 0 if n is None else n.shape[0], int(mode)),
+        _check(self.L.agpt_scene_update_mesh(self.h, int(prim), pv, v.shape[0], pn, 0 if n is None else n.shape[0], mode),
                "agpt_scene_update_mesh")
+
+    def update_mesh_device(self, prim, verts_ptr, n_vertices, normals_ptr=None, n_normals=0, mode=UPDATE_REFIT):
+        """agpt_scene_update_mesh_device with raw device pointers (Context.alloc / upload, or a tensor's data_ptr()): the arrays must
+        be complete, or produced on the context's stream."""
+        _check(self.L.agpt_scene_update_mesh_device(self.h, int(prim), C.c_void_p(verts_ptr), int(n_vertices), C.c_void_p(normals_ptr or None),
+                                                    int(n_normals), self._update_mode(mode, "update_mesh_device")), "agpt_scene_update_mesh_device")
+
+    def transform_mesh(self, prim, matrix4x4, mode=UPDATE_REFIT):
+        """agpt_scene_transform_mesh: mesh primitive `prim` placed by a row-major 4x4 applied on the GPU to its rest pose (the arrays
+        it last received from add_mesh / update_mesh); absolute, not cumulative.  The scene is what update_mesh(prim,
+        *transform_arrays(matrix4x4, rest_verts, rest_normals), mode) leaves."""
+        m = np.ascontiguousarray(matrix4x4, np.float32).reshape(16)
+        _check(self.L.agpt_scene_transform_mesh(self.h, int(prim), m.ctypes.data_as(C.POINTER(C.c_float)), self._update_mode(mode, "transform_mesh")),
+               "agpt_scene_transform_mesh")
 
     def set_bvh_builder(self, builder):
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""

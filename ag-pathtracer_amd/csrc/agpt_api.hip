@@ -197,8 +197,16 @@ struct agpt_scene {
     DevScene dev{};
     // agpt_scene_update_mesh: per mesh the device path's cache (created by the mesh's first REFIT, agpt_update.h) and whether the
     // bounds of HostMesh::nodes are behind the device's (root box excepted; brought up to date by sync_mirror)
+    // arrays_stale: HostMesh::vertices / normals are behind the device's as well (a device-pointer or transform REFIT: the new arrays
+    // exist only in the updater); rest: the rest pose of agpt_scene_transform_mesh, a host copy taken by the mesh's first transform
+    // after its arrays were last given explicitly (DESIGN.md section 5.7 lists who reads the mirror).
     std::vector<agpt::MeshUpdater*> updaters;
-    std::vector<char> bounds_stale;
+    std::vector<char> bounds_stale, arrays_stale;
+    struct RestPose {
+        bool valid = false;
+        std::vector<v3> vertices, normals;
+    };
+    std::vector<RestPose> rest;
     ~agpt_scene() {
         for (agpt::MeshUpdater* u : updaters) agpt::mesh_updater_destroy(u);
     }
@@ -630,20 +638,27 @@ int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
     return AGPT_OK;
 }
 
-// the bounds of the host copies of meshes that were refitted on the device (agpt_scene_update_mesh)
-static int sync_mirror(agpt_scene* s) {
-    for (size_t m = 0; m < s->bounds_stale.size(); m++)
+// the bounds of the host copies of meshes that were refitted on the device (agpt_scene_update_mesh) and, with `arrays`, the positions
+// and normals of those whose new arrays never existed on the host (agpt_scene_update_mesh_device, agpt_scene_transform_mesh)
+static int sync_mirror(agpt_scene* s, bool arrays) {
+    for (size_t m = 0; m < s->bounds_stale.size(); m++) {
         if (s->bounds_stale[m]) {
             HIP_TRY(hipSetDevice(s->ctx->device));
             if (const int rc = agpt::download_bounds(s->ctx->stream, s->updaters[m], s->meshes[m])) return rc;
             s->bounds_stale[m] = 0;
         }
+        if (arrays && s->arrays_stale[m]) {
+            HIP_TRY(hipSetDevice(s->ctx->device));
+            if (const int rc = agpt::download_arrays(s->ctx->stream, s->updaters[m], s->meshes[m].vertices, s->meshes[m].normals)) return rc;
+            s->arrays_stale[m] = 0;
+        }
+    }
     return AGPT_OK;
 }
 
 int agpt_scene_commit(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_commit: scene is NULL");
-    if (const int rc = sync_mirror(s)) return rc;
+    if (const int rc = sync_mirror(s, true)) return rc;   // flatten_scene reads every mesh's arrays and boxes
     // The scene's texturing level: the highest one a material needs.  Every level's kernels are those of the level below plus one
     // thing (same uv records, same texture table), so the conditions below compare against it.
     bool has_texture = false, has_map = false, has_sampler = false, has_normal_map = false;
@@ -812,7 +827,7 @@ int agpt_mesh_num_prims(const agpt_scene* s, int prim) {
 int agpt_mesh_get_bvh(const agpt_scene* s, int prim, agpt_bvh_node* nodes_out, int32_t* prim_index_out) {
     const agpt::HostMesh* m = mesh_of(s, prim);
     if (!m) return fail(AGPT_ERR_INVALID, "agpt_mesh_get_bvh: not a mesh primitive");
-    if (const int rc = sync_mirror(const_cast<agpt_scene*>(s))) return rc;
+    if (const int rc = sync_mirror(const_cast<agpt_scene*>(s), false)) return rc;   // (the boxes only)
     if (nodes_out) std::memcpy(nodes_out, m->nodes.data(), m->nodes.size() * sizeof(agpt_bvh_node));
     if (prim_index_out) std::memcpy(prim_index_out, m->prim_index.data(), m->prim_index.size() * sizeof(int32_t));
     return AGPT_OK;
@@ -880,60 +895,78 @@ static int upload_toplevel(agpt_scene* s) {
     return AGPT_OK;
 }
 
-int agpt_scene_update_mesh(agpt_scene* s, int prim, const float* vertices, int n_vertices, const float* normals, int n_normals, int mode) {
-    if (!s || !vertices) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: NULL scene or vertices");
-    if (!s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: the scene is not committed");
+// the argument checks the three update calls share, in agpt_scene_update_mesh's order (`fn` names the call in the message)
+static int check_update(const char* fn, const agpt_scene* s, int prim, const void* vertices, int n_vertices, const void* normals, int n_normals,
+                        int mode) {
+    const std::string f(fn);
+    if (!s || !vertices) return fail(AGPT_ERR_INVALID, f + ": NULL scene or vertices");
+    if (!s->committed) return fail(AGPT_ERR_INVALID, f + ": the scene is not committed");
     if (prim < 0 || prim >= (int)s->prims.size() || s->prims[prim].type != AGPT_PRIM_MESH)
-        return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: primitive " + std::to_string(prim) + " is not a mesh of this scene");
-    const size_t mi = (size_t)s->prims[prim].index;
-    agpt::HostMesh& mesh = s->meshes[mi];
+        return fail(AGPT_ERR_INVALID, f + ": primitive " + std::to_string(prim) + " is not a mesh of this scene");
+    const agpt::HostMesh& mesh = s->meshes[(size_t)s->prims[prim].index];
     if (n_vertices != (int)mesh.vertices.size() || n_normals != (int)mesh.normals.size() || (!normals && !mesh.normals.empty()))
-        return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: the mesh has " + std::to_string(mesh.vertices.size()) + " vertices and " +
+        return fail(AGPT_ERR_INVALID, f + ": the mesh has " + std::to_string(mesh.vertices.size()) + " vertices and " +
                                           std::to_string(mesh.normals.size()) + " normals; both counts stay (normals may be NULL only without any)");
-    if (mode != AGPT_UPDATE_REFIT && mode != AGPT_UPDATE_REBUILD)
-        return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: unknown mode " + std::to_string(mode));
-    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (mode != AGPT_UPDATE_REFIT && mode != AGPT_UPDATE_REBUILD) return fail(AGPT_ERR_INVALID, f + ": unknown mode " + std::to_string(mode));
+    return AGPT_OK;
+}
+
+static void size_update_state(agpt_scene* s) {
     if (s->updaters.size() < s->meshes.size()) {
         s->updaters.resize(s->meshes.size(), nullptr);
         s->bounds_stale.resize(s->meshes.size(), 0);
+        s->arrays_stale.resize(s->meshes.size(), 0);
+        s->rest.resize(s->meshes.size());
     }
-    bool finite = true;
-    for (int i = 0; i < 3 * n_vertices && finite; i++) finite = std::isfinite(vertices[i]);
+}
+
+// the mesh's arrays were given explicitly: they are the rest pose of the transforms that follow
+static void forget_rest(agpt_scene* s, size_t mi) {
+    s->rest[mi] = agpt_scene::RestPose();
+    agpt::drop_rest(s->updaters[mi]);
+}
+
+// Host orchestration of what exists, from host arrays: a new tree (REBUILD) or the host refit (a non-finite position under REFIT),
+// then the full commit.
+static int update_on_host(agpt_scene* s, size_t mi, const float* vertices, const float* normals, int mode) {
+    agpt::HostMesh& mesh = s->meshes[mi];
+    const int n_vertices = (int)mesh.vertices.size(), n_normals = (int)mesh.normals.size();
     auto set_arrays = [&]() {
         for (int i = 0; i < n_vertices; i++) mesh.vertices[i] = V3(vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);
         for (int i = 0; i < n_normals; i++) mesh.normals[i] = V3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
     };
-    if (mode == AGPT_UPDATE_REBUILD || !finite) {
-        // host orchestration of what exists: a new tree (REBUILD) or the host refit (a non-finite position), then the full commit
-        if (mode == AGPT_UPDATE_REBUILD && s->bvh_builder == AGPT_BVH_BUILDER_DEVICE) {
-            const int n_tris = (int)mesh.prim_index.size();
-            std::vector<agpt_bvh_node> nodes((size_t)2 * n_tris + 2);
-            std::vector<int32_t> order(n_tris);
-            int total = 0, depth = 0, on_device = 0;
-            const int rc = agpt::build_bvh_device(s->ctx->stream, vertices, n_vertices, mesh.indices.data(), n_tris, mesh.max_prims_in_node,
-                                                  nodes.data(), order.data(), &total, &depth, &on_device);
-            if (rc != AGPT_OK) return rc;
-            nodes.resize((size_t)total + 1);
-            set_arrays();
-            mesh.nodes.swap(nodes);
-            mesh.prim_index.swap(order);
-            mesh.total_nodes = total;
-            mesh.max_depth = depth;
-        } else if (mode == AGPT_UPDATE_REBUILD) {
-            set_arrays();
-            agpt::build_bvh(mesh, mesh.max_prims_in_node);
-        } else {
-            set_arrays();
-            agpt::refit_bvh(mesh.vertices, mesh.indices, mesh.prim_index, mesh.nodes.data(), mesh.total_nodes);
-        }
-        s->bounds_stale[mi] = 0;   // every box of this mesh has just been computed on the host
-        if (mode == AGPT_UPDATE_REBUILD) {   // the cache holds the old topology
-            agpt::mesh_updater_destroy(s->updaters[mi]);
-            s->updaters[mi] = nullptr;
-        }
-        return agpt_scene_commit(s);
+    if (mode == AGPT_UPDATE_REBUILD && s->bvh_builder == AGPT_BVH_BUILDER_DEVICE) {
+        const int n_tris = (int)mesh.prim_index.size();
+        std::vector<agpt_bvh_node> nodes((size_t)2 * n_tris + 2);
+        std::vector<int32_t> order(n_tris);
+        int total = 0, depth = 0, on_device = 0;
+        const int rc = agpt::build_bvh_device(s->ctx->stream, vertices, n_vertices, mesh.indices.data(), n_tris, mesh.max_prims_in_node,
+                                              nodes.data(), order.data(), &total, &depth, &on_device);
+        if (rc != AGPT_OK) return rc;
+        nodes.resize((size_t)total + 1);
+        set_arrays();
+        mesh.nodes.swap(nodes);
+        mesh.prim_index.swap(order);
+        mesh.total_nodes = total;
+        mesh.max_depth = depth;
+    } else if (mode == AGPT_UPDATE_REBUILD) {
+        set_arrays();
+        agpt::build_bvh(mesh, mesh.max_prims_in_node);
+    } else {
+        set_arrays();
+        agpt::refit_bvh(mesh.vertices, mesh.indices, mesh.prim_index, mesh.nodes.data(), mesh.total_nodes);
     }
-    // REFIT on the device: where flatten_scene put this mesh
+    s->bounds_stale[mi] = 0;   // every box of this mesh has just been computed on the host,
+    s->arrays_stale[mi] = 0;   // from arrays that are now the mirror's
+    if (mode == AGPT_UPDATE_REBUILD) {   // the cache holds the old topology
+        agpt::mesh_updater_destroy(s->updaters[mi]);
+        s->updaters[mi] = nullptr;
+    }
+    return agpt_scene_commit(s);
+}
+
+// REFIT on the device: where flatten_scene put this mesh
+static agpt::UpdateTarget update_target(const agpt_scene* s, int prim, size_t mi) {
     size_t node_base = 0, tri_base = 0;
     for (size_t m = 0; m < mi; m++) {
         node_base += (s->meshes[m].nodes.size() + 1) & ~size_t(1);
@@ -952,14 +985,102 @@ int agpt_scene_update_mesh(agpt_scene* s, int prim, const float* vertices, int n
     tg.node_base = (uint32_t)node_base;
     tg.tri_base = (uint32_t)tri_base;
     tg.prim_id = (uint32_t)prim;
-    float root[6];
-    if (const int rc = agpt::update_mesh_device(s->ctx->stream, &s->updaters[mi], mesh, vertices, normals, tg, root)) return rc;
-    set_arrays();
+    return tg;
+}
+
+// the host's share of a device REFIT: the root box (the top-level tree is built from it) and what the mirror now lacks
+static int refit_done(agpt_scene* s, size_t mi, const float root[6], bool arrays_on_device_only) {
+    agpt::HostMesh& mesh = s->meshes[mi];
     std::memcpy(mesh.nodes[0].bmin, root, 12);
     std::memcpy(mesh.nodes[0].bmax, root + 3, 12);
     s->bounds_stale[mi] = 1;
+    s->arrays_stale[mi] = arrays_on_device_only ? 1 : 0;
     if (s->prims.size() > 64) return upload_toplevel(s);
     return AGPT_OK;
+}
+
+int agpt_scene_update_mesh(agpt_scene* s, int prim, const float* vertices, int n_vertices, const float* normals, int n_normals, int mode) {
+    if (const int rc = check_update("agpt_scene_update_mesh", s, prim, vertices, n_vertices, normals, n_normals, mode)) return rc;
+    const size_t mi = (size_t)s->prims[prim].index;
+    agpt::HostMesh& mesh = s->meshes[mi];
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    size_update_state(s);
+    forget_rest(s, mi);
+    bool finite = true;
+    for (int i = 0; i < 3 * n_vertices && finite; i++) finite = std::isfinite(vertices[i]);
+    if (mode == AGPT_UPDATE_REBUILD || !finite) return update_on_host(s, mi, vertices, normals, mode);
+    const agpt::UpdateTarget tg = update_target(s, prim, mi);
+    float root[6];
+    if (const int rc = agpt::update_mesh_device(s->ctx->stream, &s->updaters[mi], mesh, vertices, normals, tg, root)) return rc;
+    for (int i = 0; i < n_vertices; i++) mesh.vertices[i] = V3(vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);
+    for (int i = 0; i < n_normals; i++) mesh.normals[i] = V3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+    return refit_done(s, mi, root, false);
+}
+
+// the new arrays are in the mesh's updater (copied or transformed there): REFIT from them, or -- REBUILD, a non-finite position --
+// bring them to the host and do what agpt_scene_update_mesh does with host arrays
+static int update_from_updater(agpt_scene* s, int prim, size_t mi, int mode) {
+    agpt::HostMesh& mesh = s->meshes[mi];
+    if (mode == AGPT_UPDATE_REFIT) {
+        const agpt::UpdateTarget tg = update_target(s, prim, mi);
+        float root[6];
+        bool finite = true;
+        if (const int rc = agpt::refit_device_arrays(s->ctx->stream, s->updaters[mi], mesh, tg, root, &finite)) return rc;
+        if (finite) return refit_done(s, mi, root, true);
+    }
+    std::vector<v3> v(mesh.vertices.size()), n(mesh.normals.size());
+    if (const int rc = agpt::download_arrays(s->ctx->stream, s->updaters[mi], v, n)) return rc;
+    return update_on_host(s, mi, &v.data()->x, n.empty() ? nullptr : &n.data()->x, mode);
+}
+
+int agpt_scene_update_mesh_device(agpt_scene* s, int prim, const float* vertices_dev, int n_vertices, const float* normals_dev, int n_normals,
+                                  int mode) {
+    if (const int rc = check_update("agpt_scene_update_mesh_device", s, prim, vertices_dev, n_vertices, normals_dev, n_normals, mode)) return rc;
+    const size_t mi = (size_t)s->prims[prim].index;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    size_update_state(s);
+    if (mode == AGPT_UPDATE_REBUILD) {   // the builders take host arrays
+        std::vector<float> v((size_t)3 * n_vertices), n((size_t)3 * n_normals);
+        HIP_TRY(hipMemcpyAsync(v.data(), vertices_dev, v.size() * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
+        if (!n.empty()) HIP_TRY(hipMemcpyAsync(n.data(), normals_dev, n.size() * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+        forget_rest(s, mi);
+        return update_on_host(s, mi, v.data(), n.empty() ? nullptr : n.data(), mode);
+    }
+    if (const int rc = agpt::copy_arrays_device(s->ctx->stream, &s->updaters[mi], s->meshes[mi], vertices_dev, normals_dev)) return rc;
+    forget_rest(s, mi);
+    return update_from_updater(s, prim, mi, mode);
+}
+
+int agpt_scene_transform_mesh(agpt_scene* s, int prim, const float* transform16, int mode) {
+    {   // the checks of agpt_scene_update_mesh with the mesh's own counts, then the matrix
+        const agpt::HostMesh* m = s && s->committed ? mesh_of(s, prim) : nullptr;
+        const int dummy = 0;
+        if (const int rc = check_update("agpt_scene_transform_mesh", s, prim, &dummy, m ? (int)m->vertices.size() : 0, &dummy,
+                                        m ? (int)m->normals.size() : 0, mode))
+            return rc;
+    }
+    if (!transform16) return fail(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: NULL matrix");
+    agpt::Mat4 M;
+    std::memcpy(M.c, transform16, sizeof(M.c));
+    for (float c : M.c)
+        if (!std::isfinite(c)) return fail(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: the matrix has a non-finite entry");
+    float det = 0;
+    const agpt::Mat4 N = agpt::inverse_transpose(M, &det);
+    if (det == 0) return fail(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: the matrix is singular (its determinant is exactly 0)");
+    const size_t mi = (size_t)s->prims[prim].index;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    size_update_state(s);
+    agpt_scene::RestPose& rest = s->rest[mi];
+    if (!rest.valid) {   // the arrays the mesh last received explicitly: the mirror, brought up to date if they came as device pointers
+        if (const int rc = sync_mirror(s, true)) return rc;
+        rest.vertices = s->meshes[mi].vertices;
+        rest.normals = s->meshes[mi].normals;
+        rest.valid = true;
+        agpt::drop_rest(s->updaters[mi]);
+    }
+    if (const int rc = agpt::transform_arrays_device(s->ctx->stream, &s->updaters[mi], s->meshes[mi], rest.vertices, rest.normals, M, N)) return rc;
+    return update_from_updater(s, prim, mi, mode);
 }
 
 int agpt_scene_set_bvh_builder(agpt_scene* s, int builder) {

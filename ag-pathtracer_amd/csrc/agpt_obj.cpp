@@ -58,8 +58,8 @@
 //     COPYRIGHT HOLDERS BE LIABLE FOR ANY CLAIM, DAMAGES OR OTHER LIABILITY, WHETHER IN AN ACTION OF CONTRACT, TORT OR
 //     OTHERWISE, ARISING FROM, OUT OF OR IN CONNECTION WITH THE SOFTWARE OR THE USE OR OTHER DEALINGS IN THE SOFTWARE.
 //
-// inverse_transpose() evaluates the 4x4 cofactor expansion of Mesa's gluInvertMatrix (SGI Free Software License B), the
-// form the reference's mat4::Inverted uses (template/precomp.h:948-990): the operation order decides the rounded normals.
+// The mat4 arithmetic (transform_point, transform_vector, inverse_transpose) lives in agpt_transform.h, shared with the device
+// path of agpt_scene_transform_mesh; its notice (Mesa's gluInvertMatrix, SGI Free Software License B) is there.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -71,76 +71,22 @@
 #include <vector>
 
 #include "../../include/agpt.h"
+#include "agpt_transform.h"
+
+namespace agpt {
+int report_error(int code, const std::string& msg);   // agpt_api.hip (agpt_last_error)
+}
 
 namespace {
+
+using agpt::Mat4;
+using agpt::inverse_transpose;
+using agpt::transform_point;
+using agpt::transform_vector;
 
 struct Corner {
     int v, vt, vn;
 };
-
-struct Mat4 {
-    float c[16];
-};
-
-Mat4 identity() {
-    Mat4 m;
-    std::memset(m.c, 0, sizeof(m.c));
-    m.c[0] = m.c[5] = m.c[10] = m.c[15] = 1.f;
-    return m;
-}
-
-// mat4::Inverted (template/precomp.h:948-990, the MESA cofactor expansion) followed by ::Transposed (3x3 part)
-Mat4 inverse_transpose(const Mat4& M) {
-    const float* cell = M.c;
-    const float inv[16] = {
-        cell[5] * cell[10] * cell[15] - cell[5] * cell[11] * cell[14] - cell[9] * cell[6] * cell[15] + cell[9] * cell[7] * cell[14] + cell[13] * cell[6] * cell[11] - cell[13] * cell[7] * cell[10],
-        -cell[1] * cell[10] * cell[15] + cell[1] * cell[11] * cell[14] + cell[9] * cell[2] * cell[15] - cell[9] * cell[3] * cell[14] - cell[13] * cell[2] * cell[11] + cell[13] * cell[3] * cell[10],
-        cell[1] * cell[6] * cell[15] - cell[1] * cell[7] * cell[14] - cell[5] * cell[2] * cell[15] + cell[5] * cell[3] * cell[14] + cell[13] * cell[2] * cell[7] - cell[13] * cell[3] * cell[6],
-        -cell[1] * cell[6] * cell[11] + cell[1] * cell[7] * cell[10] + cell[5] * cell[2] * cell[11] - cell[5] * cell[3] * cell[10] - cell[9] * cell[2] * cell[7] + cell[9] * cell[3] * cell[6],
-        -cell[4] * cell[10] * cell[15] + cell[4] * cell[11] * cell[14] + cell[8] * cell[6] * cell[15] - cell[8] * cell[7] * cell[14] - cell[12] * cell[6] * cell[11] + cell[12] * cell[7] * cell[10],
-        cell[0] * cell[10] * cell[15] - cell[0] * cell[11] * cell[14] - cell[8] * cell[2] * cell[15] + cell[8] * cell[3] * cell[14] + cell[12] * cell[2] * cell[11] - cell[12] * cell[3] * cell[10],
-        -cell[0] * cell[6] * cell[15] + cell[0] * cell[7] * cell[14] + cell[4] * cell[2] * cell[15] - cell[4] * cell[3] * cell[14] - cell[12] * cell[2] * cell[7] + cell[12] * cell[3] * cell[6],
-        cell[0] * cell[6] * cell[11] - cell[0] * cell[7] * cell[10] - cell[4] * cell[2] * cell[11] + cell[4] * cell[3] * cell[10] + cell[8] * cell[2] * cell[7] - cell[8] * cell[3] * cell[6],
-        cell[4] * cell[9] * cell[15] - cell[4] * cell[11] * cell[13] - cell[8] * cell[5] * cell[15] + cell[8] * cell[7] * cell[13] + cell[12] * cell[5] * cell[11] - cell[12] * cell[7] * cell[9],
-        -cell[0] * cell[9] * cell[15] + cell[0] * cell[11] * cell[13] + cell[8] * cell[1] * cell[15] - cell[8] * cell[3] * cell[13] - cell[12] * cell[1] * cell[11] + cell[12] * cell[3] * cell[9],
-        cell[0] * cell[5] * cell[15] - cell[0] * cell[7] * cell[13] - cell[4] * cell[1] * cell[15] + cell[4] * cell[3] * cell[13] + cell[12] * cell[1] * cell[7] - cell[12] * cell[3] * cell[5],
-        -cell[0] * cell[5] * cell[11] + cell[0] * cell[7] * cell[9] + cell[4] * cell[1] * cell[11] - cell[4] * cell[3] * cell[9] - cell[8] * cell[1] * cell[7] + cell[8] * cell[3] * cell[5],
-        -cell[4] * cell[9] * cell[14] + cell[4] * cell[10] * cell[13] + cell[8] * cell[5] * cell[14] - cell[8] * cell[6] * cell[13] - cell[12] * cell[5] * cell[10] + cell[12] * cell[6] * cell[9],
-        cell[0] * cell[9] * cell[14] - cell[0] * cell[10] * cell[13] - cell[8] * cell[1] * cell[14] + cell[8] * cell[2] * cell[13] + cell[12] * cell[1] * cell[10] - cell[12] * cell[2] * cell[9],
-        -cell[0] * cell[5] * cell[14] + cell[0] * cell[6] * cell[13] + cell[4] * cell[1] * cell[14] - cell[4] * cell[2] * cell[13] - cell[12] * cell[1] * cell[6] + cell[12] * cell[2] * cell[5],
-        cell[0] * cell[5] * cell[10] - cell[0] * cell[6] * cell[9] - cell[4] * cell[1] * cell[10] + cell[4] * cell[2] * cell[9] + cell[8] * cell[1] * cell[6] - cell[8] * cell[2] * cell[5]};
-    const float det = cell[0] * inv[0] + cell[1] * inv[4] + cell[2] * inv[8] + cell[3] * inv[12];
-    Mat4 I = identity();
-    if (det != 0) {
-        const float invdet = 1.0f / det;
-        for (int i = 0; i < 16; i++) I.c[i] = inv[i] * invdet;
-    }
-    Mat4 T = identity();  // Transposed(): 3x3 part only, the rest stays identity (template/precomp.h:940-947)
-    T.c[0] = I.c[0]; T.c[1] = I.c[4]; T.c[2] = I.c[8];
-    T.c[4] = I.c[1]; T.c[5] = I.c[5]; T.c[6] = I.c[9];
-    T.c[8] = I.c[2]; T.c[9] = I.c[6]; T.c[10] = I.c[10];
-    return T;
-}
-
-void transform_point(const Mat4& M, const float v[3], float out[3]) {
-    const float* c = M.c;
-    float rx = c[0] * v[0] + c[1] * v[1] + c[2] * v[2] + c[3];
-    float ry = c[4] * v[0] + c[5] * v[1] + c[6] * v[2] + c[7];
-    float rz = c[8] * v[0] + c[9] * v[1] + c[10] * v[2] + c[11];
-    const float w = c[12] * v[0] + c[13] * v[1] + c[14] * v[2] + c[15];
-    if (w == 1) {
-        out[0] = rx; out[1] = ry; out[2] = rz;
-        return;
-    }
-    const float iw = 1.f / w;
-    out[0] = rx * iw; out[1] = ry * iw; out[2] = rz * iw;
-}
-void transform_vector(const Mat4& M, const float v[3], float out[3]) {
-    const float* c = M.c;
-    out[0] = c[0] * v[0] + c[1] * v[1] + c[2] * v[2];
-    out[1] = c[4] * v[0] + c[5] * v[1] + c[6] * v[2];
-    out[2] = c[8] * v[0] + c[9] * v[1] + c[10] * v[2];
-}
 
 // ---- OBJ token parsers ---------------------------------------------------------------------------------------------------------
 // The functions from here to the end of triangulate_polygon() restate, in this file's own form, algorithms of tinyobjloader 2.0.0
@@ -365,7 +311,7 @@ int agpt_obj_parse(const char* text, size_t length, const float* transform16, in
         g_obj_error = "agpt_obj_parse: NULL argument";
         return AGPT_ERR_INVALID;
     }
-    Mat4 M = identity();
+    Mat4 M = agpt::mat4_identity();
     if (transform16) std::memcpy(M.c, transform16, sizeof(M.c));
     const Mat4 N = inverse_transpose(M);
     std::vector<float> v, vn, vt;
@@ -504,5 +450,27 @@ int agpt_obj_get(const agpt_obj_mesh* m, float* vertices, float* normals, float*
 }
 
 void agpt_obj_free(agpt_obj_mesh* m) { delete m; }
+
+int agpt_transform_arrays(const float* transform16, const float* vertices, int n_vertices, const float* normals, int n_normals,
+                          float* vertices_out, float* normals_out) {
+    if (!transform16 || !vertices || !vertices_out)
+        return agpt::report_error(AGPT_ERR_INVALID, "agpt_transform_arrays: NULL transform16, vertices or vertices_out");
+    if (n_vertices < 0 || n_normals < 0 || (n_normals > 0 && (!normals || !normals_out)))
+        return agpt::report_error(AGPT_ERR_INVALID, "agpt_transform_arrays: a negative count, or n_normals > 0 with NULL normals or normals_out");
+    Mat4 M;
+    std::memcpy(M.c, transform16, sizeof(M.c));
+    const Mat4 N = inverse_transpose(M);
+    for (int i = 0; i < n_vertices; i++) {   // (through a temporary: vertices_out may be vertices)
+        float p[3];
+        transform_point(M, vertices + 3 * (size_t)i, p);
+        std::memcpy(vertices_out + 3 * (size_t)i, p, sizeof(p));
+    }
+    for (int i = 0; i < n_normals; i++) {
+        float p[3];
+        transform_vector(N, normals + 3 * (size_t)i, p);
+        std::memcpy(normals_out + 3 * (size_t)i, p, sizeof(p));
+    }
+    return AGPT_OK;
+}
 
 }  // extern "C"

@@ -7,10 +7,15 @@
 //                    which k_update_tris has just written), an interior node takes (left, right) of its child pair.  Launched
 //                    once for all leaves, then once per level of interior nodes from the deepest up, on one stream: a launch sees
 //                    what the launches before it wrote, and the output does not depend on the launch shape.
-// Both are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair); 64-lane blocks, 16-byte
-// accesses of the float4 records, no LDS.
+//   k_check_finite   one lane per coordinate of the position array: one flag word set if any is Inf or NaN (the rule of the host
+//                    path, which looks at every coordinate, referenced by a triangle or not).
+//   k_transform_mesh one lane per vertex and one per normal: the mesh's rest arrays through transform_point / transform_vector of
+//                    agpt_transform.h into the arrays k_update_tris reads (agpt_scene_transform_mesh).
+// All are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair, 24 B per transformed vertex); 64-lane
+// blocks, 16-byte accesses of the float4 records, no LDS.
 #include "agpt_update.h"
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -158,6 +163,41 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(RefitArgs a) {
     }
 }
 
+__global__ __launch_bounds__(kBlock) void k_check_finite(const float* x, size_t n, uint32_t* flag) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool bad = i < n && (__float_as_uint(x[i]) & 0x7f800000u) == 0x7f800000u;
+    if (__any(bad) && (threadIdx.x & 63) == 0) *flag = 1u;   // (every wave that sees one stores the same word)
+}
+
+struct TransformArgs {
+    Mat4 M, N;                 // N = inverse_transpose(M), formed on the host
+    const float* rest_verts;
+    const float* rest_normals;
+    float* verts;
+    float* normals;
+    int n_vertices, n_normals;
+};
+
+__global__ __launch_bounds__(kBlock) void k_transform_mesh(TransformArgs a) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < (size_t)a.n_vertices) {
+        const float v[3] = {a.rest_verts[3 * i], a.rest_verts[3 * i + 1], a.rest_verts[3 * i + 2]};
+        float out[3];
+        transform_point(a.M, v, out);
+        a.verts[3 * i] = out[0];
+        a.verts[3 * i + 1] = out[1];
+        a.verts[3 * i + 2] = out[2];
+    } else if (i < (size_t)a.n_vertices + (size_t)a.n_normals) {
+        const size_t j = i - (size_t)a.n_vertices;
+        const float v[3] = {a.rest_normals[3 * j], a.rest_normals[3 * j + 1], a.rest_normals[3 * j + 2]};
+        float out[3];
+        transform_vector(a.N, v, out);
+        a.normals[3 * j] = out[0];
+        a.normals[3 * j + 1] = out[1];
+        a.normals[3 * j + 2] = out[2];
+    }
+}
+
 template <class T>
 struct Buf {
     T* p = nullptr;
@@ -174,12 +214,22 @@ struct Buf {
         }
         return count ? hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
     }
+    hipError_t reserve(size_t count) {
+        if (p) return hipSuccess;
+        const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
 };
 
 }  // namespace
 
 struct MeshUpdater {
     Buf<float> verts, normals;
+    // agpt_scene_transform_mesh: the rest pose k_transform_mesh reads (uploaded by the first transform after the arrays were given)
+    Buf<float> rest_verts, rest_normals;
+    bool has_rest = false;
+    Buf<uint32_t> flag;        // k_check_finite's word
     Buf<v2> uv;
     Buf<int32_t> indices, prim_index, lists;
     Buf<int2> topo;
@@ -235,22 +285,29 @@ static int prepare(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh) {
     return AGPT_OK;
 }
 
-int update_mesh_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices, const float* normals,
-                       const UpdateTarget& tg, float root6[6]) {
-    if (!*cache) {
-        MeshUpdater* u = new MeshUpdater();
-        const int rc = prepare(stream, *u, mesh);
-        if (rc != AGPT_OK) {
-            delete u;
-            return rc;
-        }
-        *cache = u;
+static int ensure(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh) {
+    if (*cache) return AGPT_OK;
+    MeshUpdater* u = new MeshUpdater();
+    const int rc = prepare(stream, *u, mesh);
+    if (rc != AGPT_OK) {
+        delete u;
+        return rc;
     }
-    MeshUpdater& u = **cache;
-    const int n_tris = (int)mesh.prim_index.size();
-    UPD_TRY(u.verts.upload(vertices, 3 * mesh.vertices.size(), stream));
-    if (!mesh.normals.empty()) UPD_TRY(u.normals.upload(normals, 3 * mesh.normals.size(), stream));
+    *cache = u;
+    return AGPT_OK;
+}
 
+// The records of the mesh from u.verts / u.normals, then the root box; with `finite`, k_check_finite runs ahead of the rest and its
+// flag comes back beside the box.  A non-finite position harms nothing here (every index comes from the topology): the caller
+// replaces what this wrote through the host path.
+static int refit(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh, const UpdateTarget& tg, float root6[6], bool* finite) {
+    const int n_tris = (int)mesh.prim_index.size();
+    if (finite) {
+        const size_t n = 3 * mesh.vertices.size();
+        UPD_TRY(u.flag.reserve(1));
+        UPD_TRY(hipMemsetAsync(u.flag.p, 0, sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(k_check_finite, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, u.verts.p, n, u.flag.p);
+    }
     TriArgs ta;
     ta.verts = u.verts.p;
     ta.normals = mesh.normals.empty() ? nullptr : u.normals.p;
@@ -281,10 +338,80 @@ int update_mesh_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& 
     }
     UPD_TRY(hipGetLastError());
     float4 root[2];
+    uint32_t flag = 0;
     UPD_TRY(hipMemcpyAsync(root, u.bounds.p, sizeof(root), hipMemcpyDeviceToHost, stream));
+    if (finite) UPD_TRY(hipMemcpyAsync(&flag, u.flag.p, sizeof(flag), hipMemcpyDeviceToHost, stream));
     UPD_TRY(hipStreamSynchronize(stream));
+    if (finite) *finite = flag == 0;
     root6[0] = root[0].x; root6[1] = root[0].y; root6[2] = root[0].z;
     root6[3] = root[1].x; root6[4] = root[1].y; root6[5] = root[1].z;
+    return AGPT_OK;
+}
+
+int update_mesh_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices, const float* normals,
+                       const UpdateTarget& tg, float root6[6]) {
+    if (const int rc = ensure(stream, cache, mesh)) return rc;
+    MeshUpdater& u = **cache;
+    UPD_TRY(u.verts.upload(vertices, 3 * mesh.vertices.size(), stream));
+    if (!mesh.normals.empty()) UPD_TRY(u.normals.upload(normals, 3 * mesh.normals.size(), stream));
+    return refit(stream, u, mesh, tg, root6, nullptr);
+}
+
+int copy_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices_dev, const float* normals_dev) {
+    if (const int rc = ensure(stream, cache, mesh)) return rc;
+    MeshUpdater& u = **cache;
+    const size_t nv = 3 * mesh.vertices.size(), nn = 3 * mesh.normals.size();
+    UPD_TRY(u.verts.reserve(nv));
+    UPD_TRY(hipMemcpyAsync(u.verts.p, vertices_dev, nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if (nn) {
+        UPD_TRY(u.normals.reserve(nn));
+        UPD_TRY(hipMemcpyAsync(u.normals.p, normals_dev, nn * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    }
+    return AGPT_OK;
+}
+
+int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
+                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N) {
+    if (const int rc = ensure(stream, cache, mesh)) return rc;
+    MeshUpdater& u = **cache;
+    const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
+    if (rest_vertices.size() != nv || rest_normals.size() != nn)
+        return report_error(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: the rest pose does not have the mesh's counts");
+    if (!u.has_rest) {
+        UPD_TRY(u.rest_verts.upload(&rest_vertices.data()->x, 3 * nv, stream));
+        if (nn) UPD_TRY(u.rest_normals.upload(&rest_normals.data()->x, 3 * nn, stream));
+        UPD_TRY(hipStreamSynchronize(stream));   // (the caller's vectors may change behind this call)
+        u.has_rest = true;
+    }
+    UPD_TRY(u.verts.reserve(3 * nv));
+    if (nn) UPD_TRY(u.normals.reserve(3 * nn));
+    TransformArgs a;
+    a.M = M;
+    a.N = N;
+    a.rest_verts = u.rest_verts.p;
+    a.rest_normals = nn ? u.rest_normals.p : nullptr;
+    a.verts = u.verts.p;
+    a.normals = nn ? u.normals.p : nullptr;
+    a.n_vertices = (int)nv;
+    a.n_normals = (int)nn;
+    hipLaunchKernelGGL(k_transform_mesh, dim3((unsigned)((nv + nn + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    UPD_TRY(hipGetLastError());
+    return AGPT_OK;
+}
+
+int refit_device_arrays(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh, const UpdateTarget& tg, float root6[6], bool* finite) {
+    return refit(stream, *cache, mesh, tg, root6, finite);
+}
+
+void drop_rest(MeshUpdater* cache) {
+    if (cache) cache->has_rest = false;
+}
+
+int download_arrays(hipStream_t stream, const MeshUpdater* u, std::vector<v3>& vertices, std::vector<v3>& normals) {
+    static_assert(sizeof(v3) == 3 * sizeof(float), "v3 is three packed floats");
+    if (!vertices.empty()) UPD_TRY(hipMemcpyAsync(vertices.data(), u->verts.p, vertices.size() * sizeof(v3), hipMemcpyDeviceToHost, stream));
+    if (!normals.empty()) UPD_TRY(hipMemcpyAsync(normals.data(), u->normals.p, normals.size() * sizeof(v3), hipMemcpyDeviceToHost, stream));
+    UPD_TRY(hipStreamSynchronize(stream));
     return AGPT_OK;
 }
 

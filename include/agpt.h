@@ -287,6 +287,54 @@ int agpt_bvh_refit(const float* vertices, int n_vertices, const int32_t* indices
  * may be NULL only if the mesh has none); an unknown mode.  A refused call changes nothing. */
 enum { AGPT_UPDATE_REFIT = 0, AGPT_UPDATE_REBUILD = 1 };
 int agpt_scene_update_mesh(agpt_scene*, int prim, const float* vertices, int n_vertices, const float* normals, int n_normals, int mode);
+/* agpt_scene_update_mesh with the two arrays in DEVICE memory of the context's GPU (packed xyz floats, the mesh's own counts): the
+ * call behaves as agpt_scene_update_mesh would with host copies of them, and leaves the same bytes everywhere.
+ *   ordering   the library does not know the stream that produced the arrays: they must be complete when the call is made, or have
+ *              been produced on the context's stream (agpt_set_stream).  The call enqueues on the context's stream and synchronises
+ *              with it.
+ *   ownership  REFIT copies the arrays device-to-device into buffers of its own, REBUILD downloads them, before the call returns;
+ *              the caller may reuse them afterwards.
+ *   REFIT      one kernel looks at all 3 * n_vertices coordinates (referenced by a triangle or not, the host call's rule) and
+ *              reduces "is any Inf or NaN" to one flag; the triangle records and the bounds are rewritten on the GPU as for
+ *              agpt_scene_update_mesh.  The flag and the 24-byte root box are all that comes back.  With the flag set the arrays
+ *              are downloaded and the host call's path is taken: the host refit and the full upload.
+ *   REBUILD    the arrays are downloaded and the scene's builder runs as for agpt_scene_update_mesh.
+ * The scene's host copy of the mesh is brought up to date -- by a download -- when something next reads it: a later full upload
+ * (agpt_scene_commit, a REBUILD or a non-finite update of any mesh) or the first agpt_scene_transform_mesh of this mesh.
+ * agpt_mesh_get_bvh downloads the bounds only.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error) for the same conditions in the same order as agpt_scene_update_mesh (NULL scene or
+ * NULL vertices_dev; not committed; not a mesh; counts; unknown mode); a refused call changes nothing.  A pointer that is not
+ * device memory is not detected: the copy fails with AGPT_ERR_DEVICE or faults.
+ * Not covered: index or texture-coordinate changes, spheres, planes and lights, per-object motion vectors (agpt_temporal_accumulate
+ * still sees moved geometry only through its depth / normal tests), fewer launches per tree level. */
+int agpt_scene_update_mesh_device(agpt_scene*, int prim, const float* vertices_dev, int n_vertices, const float* normals_dev, int n_normals,
+                                  int mode);
+/* The reference's mat4 applied to a mesh's arrays, host-only like agpt_bvh_build (no GPU, no context).  transform16 is a row-major
+ * 4x4 as in agpt_obj_load, and the arithmetic is that loader's (TriangleMesh::LoadObj), fp32, every operation rounded on its own,
+ * nothing contracted into an fma, sums left to right:
+ *   position   r = (m[4i] * x + m[4i+1] * y + m[4i+2] * z + m[4i+3]) for rows i = 0, 1, 2; w the same with row 3; the result is r
+ *              if w == 1, else r * (1 / w) per component.
+ *   normal     (n[4i] * x + n[4i+1] * y + n[4i+2] * z) for rows i = 0, 1, 2 of n = the 3x3 transpose of the inverse of m; the inverse
+ *              is the cofactor expansion (the 16 cofactors, det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12], each
+ *              cofactor times 1 / det).  A matrix whose det is exactly 0 leaves the normals as they are (the reference's rule).
+ *              Normals are not renormalised.
+ * n_normals may be 0 (normals and normals_out are then ignored).  An output may be its own input.  AGPT_ERR_INVALID for a NULL
+ * transform16, vertices or vertices_out, a negative count, or n_normals > 0 with NULL normals or normals_out. */
+int agpt_transform_arrays(const float* transform16, const float* vertices, int n_vertices, const float* normals, int n_normals,
+                          float* vertices_out, float* normals_out);
+/* Mesh primitive `prim` of a COMMITTED scene placed by a matrix, on the GPU: afterwards the scene is byte for byte what
+ * agpt_scene_update_mesh(scene, prim, V, n_vertices, N, n_normals, mode) leaves, with V and N = agpt_transform_arrays(transform16,
+ * the mesh's rest pose).  The rest pose is the arrays the mesh last received explicitly -- agpt_scene_add_mesh,
+ * agpt_scene_update_mesh or agpt_scene_update_mesh_device --, so the transform is absolute, not cumulative: repeated calls do not
+ * drift, the same matrix gives the same bytes, and the identity gives the rest pose back.  One lane per vertex and per normal runs
+ * agpt_transform_arrays' arithmetic (one source for host and device); the inverse transpose is formed once on the host.  The rest
+ * arrays go to the GPU with the mesh's first transform and stay there; per call only the matrix goes up, and under REFIT the
+ * finiteness flag and the root box come down (a non-finite transformed position takes the host path, as above).  REBUILD downloads
+ * the transformed arrays and rebuilds.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order: the conditions of agpt_scene_update_mesh that apply (NULL
+ * scene; not committed; not a mesh; unknown mode); a NULL matrix; a non-finite entry; a determinant (the value above) of exactly 0.
+ * A refused call changes nothing.  Not covered: as for agpt_scene_update_mesh_device. */
+int agpt_scene_transform_mesh(agpt_scene*, int prim, const float* transform16, int mode);
 /* Which builder agpt_scene_add_mesh uses for the BVH of later meshes on this scene (default HOST).  Both produce the same
  * bytes; DEVICE runs agpt_bvh_build_device on the scene's context. */
 enum { AGPT_BVH_BUILDER_HOST = 0, AGPT_BVH_BUILDER_DEVICE = 1 };

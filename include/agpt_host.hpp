@@ -88,6 +88,15 @@ struct TriangleMesh {
         return m;
     }
 
+    // this mesh with its positions and normals through a row-major mat4 (agpt_transform_arrays: the arithmetic of LoadObj's transform
+    // and of Scene::TransformMesh), on the host
+    TriangleMesh Transformed(const float transform16[16]) const {
+        TriangleMesh m = *this;
+        if (agpt_transform_arrays(transform16, vertices.data(), (int)vertices.size() / 3, normals.data(), (int)normals.size() / 3,
+                                  m.vertices.data(), m.normals.data()) < 0)
+            throw std::runtime_error(std::string("agpt_transform_arrays: ") + agpt_last_error());
+        return m;
+    }
     static TriangleMesh CreateBackdrop(float3 origin, float3 size, float radius, int steps) {
         TriangleMesh m;
         const int nv = 2 * (steps + 5), ni = 6 * (steps + 4);
@@ -223,6 +232,18 @@ public:
         check(agpt_scene_update_mesh(h_, prim, m.vertices.data(), (int)m.vertices.size() / 3, m.normals.empty() ? nullptr : m.normals.data(),
                                      (int)m.normals.size() / 3, (int)mode),
               "agpt_scene_update_mesh");
+    }
+    // the same with the arrays in DEVICE memory of the context's GPU (agpt_scene_update_mesh_device): packed xyz floats of the mesh's
+    // own counts, complete when the call is made or produced on the context's stream; the library copies them before it returns
+    void UpdateMeshDevice(int prim, const float* vertices_dev, int n_vertices, const float* normals_dev, int n_normals,
+                          MeshUpdate mode = MeshUpdate::Refit) {
+        check(agpt_scene_update_mesh_device(h_, prim, vertices_dev, n_vertices, normals_dev, n_normals, (int)mode), "agpt_scene_update_mesh_device");
+    }
+    // a rigid (or any affine / projective) placement, applied on the GPU to the mesh's rest pose -- the arrays it last received from
+    // primitives_push_back / UpdateMesh / UpdateMeshDevice (agpt_scene_transform_mesh): transform16 is a row-major mat4, absolute, not
+    // cumulative; 16 floats per object per frame instead of the mesh.  `scene.TransformMesh(prim, m); accumulator.Clear();`
+    void TransformMesh(int prim, const float transform16[16], MeshUpdate mode = MeshUpdate::Refit) {
+        check(agpt_scene_transform_mesh(h_, prim, transform16, (int)mode), "agpt_scene_transform_mesh");
     }
     // camera moved (RotatingCamera::update): re-derive the camera only, geometry stays in HBM
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }

@@ -1,0 +1,203 @@
+"""agpt_scene_update_mesh_device on the GPU: every case builds two identical scenes, updates A through the host call and B through
+the device-pointer call (arrays from agpt_device_alloc / agpt_device_upload), and compares -- bit for bit -- every mesh's
+agpt_mesh_get_bvh, closest- and any-hit records on the same rays, and a render with its ray totals (device_update_cases.snapshot).
+The host call itself is pinned to the oracle by test_gpu_mesh_update.py."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import ag_pathtracer_amd as ag
+import device_update_cases as dc
+from helpers import gpu_context, gpu_scene
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def pair(builder="host", desc=None):
+    desc = desc or dc.zoo_scene()
+    scenes = []
+    for _ in range(2):
+        g = ag.Scene(gpu_context())
+        g.set_bvh_builder(builder)
+        scenes.append(desc.instantiate(g))
+    return desc, scenes[0], scenes[1]
+
+
+@pytest.mark.parametrize("mode,builder", [("refit", "host"), ("refit", "device"), ("rebuild", "host"), ("rebuild", "device")])
+def test_device_arrays_equal_host_arrays(mode, builder):
+    """all eight meshes of the zoo (1 triangle, 65 vertices, 288 triangles at max_prims_in_node 1 and 4; with and without normals; no
+    texture coordinates), then a second update of each (the cached path)"""
+    desc, a, b = pair(builder)
+    before = dc.snapshot(b, desc, dc.PRIMS)
+    for pose in (1, 2):
+        for prim in dc.PRIMS:
+            v, n = dc.zoo_arrays(prim, pose)
+            a.update_mesh(prim, v, n, mode)
+            dc.update_through_device(b, prim, v, n, mode)
+        sa, sb = dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS)
+        dc.assert_same(sa, sb)
+        assert sb["render"] != before["render"] and sb["bvh1"] != before["bvh1"]   # (the update shows)
+        before = sb
+    a.close()
+    b.close()
+
+
+def test_a_stale_mirror_survives_the_rebuild_of_another_mesh():
+    """device-REFIT of one mesh, then a host REBUILD of another: the full flatten behind the REBUILD must see the first mesh's NEW
+    arrays, which exist only on the device until then"""
+    desc, a, b = pair()
+    moved, other = dc.GRID1_N, dc.GRID4
+    v, n = dc.zoo_arrays(moved, 2)
+    a.update_mesh(moved, v, n, "refit")
+    dc.update_through_device(b, moved, v, n, "refit")
+    still = b.bvh(moved)[0].tobytes()
+    w, _ = dc.zoo_arrays(other, 1)
+    for g in (a, b):
+        g.update_mesh(other, w, None, "rebuild")
+    sa, sb = dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS)
+    dc.assert_same(sa, sb)
+    assert b.bvh(moved)[0].tobytes() == still   # the new pose, in the mirror too
+    fresh = gpu_scene(desc)
+    assert fresh.bvh(moved)[0].tobytes() != still
+    # and the other way round: the fallback's commit (a non-finite update of a third mesh) after a device REFIT
+    u, _ = dc.zoo_arrays(dc.GRID1, 1)
+    u[dc.REFERENCED, 1] = np.nan
+    for g in (a, b):
+        g.update_mesh(dc.GRID1, u, None, "refit")
+    dc.assert_same(dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS))
+    for g in (a, b, fresh):
+        g.close()
+
+
+def seventy_prims():
+    d = ag.SceneDesc("device-update-70")
+    mats = [d.add_material(ag.MAT_DIFFUSE_ONLY, c) for c in ([.8, .3, .2], [.2, .7, .3], [.3, .4, .8])]
+    for k in range(70):
+        c = (1.4 * (k % 10) - 6.3, 0.9 * ((k // 10) % 7) - 2.0, 1.1 * (k % 3))
+        d.add_mesh(*ag.scenes.blob_mesh(5, 4, center=c, radius=0.45, seed=k), mats[k % 3], 1)
+    d.add_area_light([0.0, 8.0, -4.0], 0.8, [70, 65, 60])
+    d.add_uniform_infinite_light([.25, .3, .35])
+    d.set_camera([0, 1, -16], [0, 0.5, 0], [0, 1, 0], 1.0, 50.0, 0.0)
+    return d
+
+
+def test_a_seventy_primitive_scene_gets_its_top_level_tree_again():
+    desc, a, b = pair(desc=seventy_prims())
+    prim = 7
+    v, n, _, _ = ag.scenes.blob_mesh(5, 4, center=(0.5, 2.0, -9.0), radius=1.2, seed=7)   # well outside its old root box
+    before = dc.snapshot(b, desc, [prim])
+    a.update_mesh(prim, v, n, "refit")
+    dc.update_through_device(b, prim, v, n, "refit")
+    sa, sb = dc.snapshot(a, desc, [prim]), dc.snapshot(b, desc, [prim])
+    dc.assert_same(sa, sb)
+    assert sb["render"] != before["render"] and sb["closest"] != before["closest"]
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("vertex", [dc.UNREFERENCED, dc.REFERENCED])
+def test_a_non_finite_coordinate_takes_the_fallback(vertex):
+    """one NaN, in a vertex no triangle references and in one that several do: the kernel looks at every coordinate (the host
+    path's rule), and the result is the host call's"""
+    desc, a, b = pair()
+    for prim in (dc.GRID4_N, dc.GRID1):
+        v, n = dc.zoo_arrays(prim, 1)
+        v[vertex, 2] = np.nan
+        a.update_mesh(prim, v, n, "refit")
+        dc.update_through_device(b, prim, v, n, "refit")
+    dc.assert_same(dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS))
+    # the scene is usable afterwards: a finite device update of the same mesh
+    v, n = dc.zoo_arrays(dc.GRID1, 2)
+    a.update_mesh(dc.GRID1, v, n, "refit")
+    dc.update_through_device(b, dc.GRID1, v, n, "refit")
+    dc.assert_same(dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS))
+    a.close()
+    b.close()
+
+
+def test_refusals_in_the_documented_order_change_nothing():
+    ctx = gpu_context()
+    g = ag.Scene(ctx)
+    desc = dc.zoo_scene()
+    L = g.L
+    v, n = dc.zoo_arrays(dc.GRID1_N, 1)
+    d = dc.DeviceArrays(ctx, v, n)
+    pv, pn = C.c_void_p(d.pv), C.c_void_p(d.pn)
+
+    def refused(what, *args):
+        assert L.agpt_scene_update_mesh_device(*args) == -1
+        assert b"agpt_scene_update_mesh_device" in L.agpt_last_error() and what in L.agpt_last_error(), L.agpt_last_error()
+    refused(b"NULL", None, 99, pv, 1, None, 0, 7)
+    refused(b"NULL", g.h, 99, None, 0, None, 0, 7)                       # NULL vertices first
+    refused(b"not committed", g.h, 99, pv, 1, None, 0, 7)                # then the commit state
+    desc.instantiate(g)
+    before = dc.snapshot(g, desc, dc.PRIMS)
+    sphere_light = len(dc.PRIMS) + 1
+    for prim in (-1, sphere_light, 99):
+        refused(b"not a mesh", g.h, prim, pv, 1, None, 0, 7)             # then the primitive
+    refused(b"vertices and", g.h, dc.GRID1_N, pv, len(v) - 1, pn, len(n), 7)
+    refused(b"vertices and", g.h, dc.GRID1_N, pv, len(v), pn, len(n) - 1, 7)
+    refused(b"vertices and", g.h, dc.GRID1_N, pv, len(v), None, len(n), 7)   # NULL normals on a mesh that has them
+    refused(b"vertices and", g.h, dc.GRID1, pv, len(v), pn, len(n), 7)       # normals for a mesh that has none
+    refused(b"unknown mode", g.h, dc.GRID1_N, pv, len(v), pn, len(n), 7)
+    dc.assert_same(dc.snapshot(g, desc, dc.PRIMS), before)
+    d.free()
+    g.close()
+
+
+TORCH_CHILD = r"""
+import sys
+sys.path[:0] = [%(root)r, %(tests)r]
+import torch                      # before the library touches the GPU (INTEGRATION.md section 3)
+import numpy as np
+torch.zeros(1, device="cuda")
+import ag_pathtracer_amd as ag
+import device_update_cases as dc
+
+desc = dc.zoo_scene()
+for own_stream in (False, True):
+    ctx = ag.Context(0, stream=torch.cuda.current_stream().cuda_stream if own_stream else None)
+    a, b = desc.instantiate(ag.Scene(ctx)), desc.instantiate(ag.Scene(ctx))
+    for prim in (dc.GRID1_N, dc.GRID4, dc.PRIMS[0]):
+        v, n = dc.zoo_arrays(prim, 1)
+        a.update_mesh(prim, v, n)
+        tv = torch.from_numpy(v).cuda() * 1.0          # produced on torch's stream
+        tn = None if n is None else torch.from_numpy(n).cuda()
+        b.update_mesh(prim, tv, tn, "refit")
+        tv.fill_(float("nan"))
+    dc.assert_same(dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS))
+    v, n = dc.zoo_arrays(dc.GRID1_N, 2)
+    a.update_mesh(dc.GRID1_N, v, n)
+    b.update_mesh(dc.GRID1_N, torch.from_numpy(v), torch.from_numpy(n))   # CPU tensors: the host call
+    dc.assert_same(dc.snapshot(a, desc, [dc.GRID1_N]), dc.snapshot(b, desc, [dc.GRID1_N]))
+    before = dc.snapshot(b, desc, [dc.GRID1_N])
+    tv, tn = torch.from_numpy(v).cuda(), torch.from_numpy(n).cuda()
+    bad = [(tv.double(), tn), (tv.half(), tn), (tv.reshape(-1), tn), (tv.t().contiguous(), tn), (torch.cat([tv, tv], 1)[:, :3], tn),
+           (tv, tn.double()), (tv, torch.from_numpy(n)), (torch.from_numpy(v), tn), (torch.empty(tv.shape, device="meta"), tn)]
+    for x, y in bad:
+        try:
+            b.update_mesh(dc.GRID1_N, x, y)
+        except ValueError as e:
+            assert "update_mesh" in str(e)
+        else:
+            raise AssertionError("accepted %%s %%s %%s" %% (x.dtype, tuple(x.shape), x.device))
+    dc.assert_same(dc.snapshot(b, desc, [dc.GRID1_N]), before)
+    a.close(); b.close(); ctx.close()
+print("torch-ok")
+"""
+
+
+def test_torch_device_tensors_equal_ndarrays():
+    """Scene.update_mesh with torch tensors on the GPU (data_ptr() handed to agpt_scene_update_mesh_device after torch's stream was
+    synchronised; once with the context on torch's stream) against the ndarray call; wrong dtype, shape, layout or device is refused
+    in Python.  In a child process: torch must initialise the GPU before the library does."""
+    code = TORCH_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0 and "torch-ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

@@ -1,0 +1,179 @@
+"""What one mesh update costs, per path: agpt_scene_update_mesh (host arrays), agpt_scene_update_mesh_device (device arrays),
+agpt_scene_transform_mesh (16 floats), and REBUILD with the host and the device builder -- on C3's largest mesh inside C3 and on a
+1 M-triangle heightfield.  Host clock around the synchronised calls; per operation the median and the min-max of `--runs` runs after
+one warm-up, and the bytes that cross PCIe per call (up / down, from the sizes; REBUILD re-uploads the whole scene).
+
+    python tools/mesh_update_time.py [--runs 9] [--out profiles/mesh_update_times.json] [--parent-lib TAG] [--rounds 3]
+
+--parent-lib TAG compares the host-pointer REFIT of this build with the build `libagpt_hip_TAG.so` of the parent commit
+(tools/build_variant.py run in a checkout of it, the file copied beside libagpt_hip.so): child processes, alternating parent / this
+for `--rounds` rounds on the same GPU, each timing `--runs` updates per mesh; the new median must lie within the parent's own min-max
+spread, and both sets of numbers go into the JSON."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import ag_pathtracer_amd as ag  # noqa: E402
+
+F = np.float32
+HEIGHTFIELD_QUADS = 707   # 2 * 707^2 = 999,698 triangles
+
+
+def cases():
+    """(name, scene description, primitive that moves)"""
+    c3 = ag.scenes.scene_c3()
+    meshes = [(len(op[4]) // 3, k) for k, op in enumerate(o for o in c3.ops if o[0] in ("mesh", "sphere", "plane", "area_light")) if op[0] == "mesh"]
+    return [("c3_largest_mesh", c3, max(meshes)[1]), ("heightfield_1m", ag.scenes.scene_heightfield(HEIGHTFIELD_QUADS), 0)]
+
+
+def arrays_of(desc, prim):
+    op = [o for o in desc.ops if o[0] in ("mesh", "sphere", "plane", "area_light")][prim]
+    return op[1], op[2], len(op[4]) // 3
+
+
+def stats(ts):
+    return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4), "runs": len(ts)}
+
+
+def timed(fn, runs):
+    fn(0)
+    ts = []
+    for k in range(1, runs + 1):
+        t0 = time.perf_counter()
+        fn(k)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return stats(ts)
+
+
+def wobble(v, k):
+    """the pose of run k: the build pose with a small smooth displacement (every run uploads different bytes)"""
+    return (v + F(0.002 * (k % 5)) * np.sin(v[:, ::-1] * F(3.0) + F(k))).astype(F)
+
+
+def spin(v, k):
+    c = 0.5 * (v.min(0).astype(np.float64) + v.max(0))
+    a = 0.01 * k
+    m = np.eye(4)
+    m[0, 0], m[0, 2], m[2, 0], m[2, 2] = np.cos(a), np.sin(a), -np.sin(a), np.cos(a)
+    t0, t1 = np.eye(4), np.eye(4)
+    t0[:3, 3], t1[:3, 3] = -c, c
+    return (t1 @ m @ t0).astype(F)
+
+
+def host_refit_only(runs):
+    """the child of --parent-lib: the host-pointer REFIT alone, through whichever library AGPT_LIB_VARIANT names"""
+    ctx = ag.Context(0)
+    out = {}
+    for name, desc, prim in cases():
+        g = desc.instantiate(ag.Scene(ctx))
+        v, n, _ = arrays_of(desc, prim)
+        poses = [wobble(v, k) for k in range(runs + 1)]
+        out[name] = timed(lambda k: g.update_mesh(prim, poses[k], n, "refit"), runs)
+        g.close()
+    ctx.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def compare_with_parent(tag, runs, rounds):
+    sets = {"parent": [], "this": []}
+    for _ in range(rounds):
+        for which in ("parent", "this"):
+            env = dict(os.environ)
+            env.pop("AGPT_LIB_VARIANT", None)
+            if which == "parent":
+                env["AGPT_LIB_VARIANT"] = tag
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--runs", str(runs)], env=env, capture_output=True, text=True,
+                               timeout=900, check=True)
+            line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")][-1]
+            sets[which].append(json.loads(line[7:]))
+            print(which, line[7:], flush=True)
+    out = {"method": "child processes alternating parent / this on one GPU, %d rounds of %d timed updates each after one warm-up; "
+                     "per build the median of the rounds' medians, the lowest min and the highest max" % (rounds, runs)}
+    for name in sets["this"][0]:
+        row = {}
+        for which in ("parent", "this"):
+            rs = [s[name] for s in sets[which]]
+            row[which] = {"median_ms": round(statistics.median(r["median_ms"] for r in rs), 4), "min_ms": min(r["min_ms"] for r in rs),
+                          "max_ms": max(r["max_ms"] for r in rs), "rounds": rs}
+        row["this_median_within_parent_spread"] = bool(row["parent"]["min_ms"] <= row["this"]["median_ms"] <= row["parent"]["max_ms"])
+        row["this_median_not_above_parent_max"] = bool(row["this"]["median_ms"] <= row["parent"]["max_ms"])
+        out[name] = row
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=9)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--parent-lib", default=None, metavar="TAG")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.runs < 7:
+        ap.error("--runs: at least 7")
+    if a.child:
+        return host_refit_only(a.runs)
+    result = {"runs": a.runs, "statistic": "host clock around the synchronised call, ms: median and min-max of the runs after one warm-up",
+              "pcie_bytes": "per call, from the sizes: up = host to device, down = device to host", "cases": {}}
+    ctx = ag.Context(0)
+    for name, desc, prim in cases():
+        v, n, tris = arrays_of(desc, prim)
+        nv, nn = len(v), 0 if n is None else len(n)
+        arrays_bytes = 12 * (nv + nn)
+        rows = {}
+        g = desc.instantiate(ag.Scene(ctx))
+        poses = [wobble(v, k) for k in range(a.runs + 1)]
+        rows["refit_host_pointer"] = dict(timed(lambda k: g.update_mesh(prim, poses[k], n, "refit"), a.runs), pcie_up=arrays_bytes, pcie_down=32)
+        pv, pn = ctx.alloc(12 * nv), (ctx.alloc(12 * nn) if nn else None)
+        if nn:
+            ctx.upload(pn, n)
+
+        def device_refit(k):
+            g.update_mesh_device(prim, pv, nv, pn, nn, "refit")
+        ctx.upload(pv, poses[1])
+        rows["refit_device_pointer"] = dict(timed(device_refit, a.runs), pcie_up=0, pcie_down=36)
+        g.update_mesh(prim, v, n, "refit")   # the rest pose again
+        mats = [spin(v, k) for k in range(a.runs + 1)]
+        g.transform_mesh(prim, mats[0])      # (the one-time upload of the rest arrays is not part of a frame)
+        rows["refit_transform"] = dict(timed(lambda k: g.transform_mesh(prim, mats[k]), a.runs), pcie_up=128, pcie_down=36,
+                                       first_call_up=arrays_bytes)
+        ctx.free(pv)
+        if pn:
+            ctx.free(pn)
+        commit_bytes = None
+        for builder in ("host", "device"):
+            g.close()
+            g = ag.Scene(ctx)
+            g.set_bvh_builder(builder)
+            desc.instantiate(g)
+            rows["rebuild_%s_builder" % builder] = dict(timed(lambda k: g.update_mesh(prim, poses[k], n, "rebuild"), a.runs),
+                                                        pcie="the arrays (device builder: up; its tree comes down) and the whole scene's "
+                                                             "flattened records up again (agpt_scene_commit)")
+        g.close()
+        result["cases"][name] = {"triangles": tris, "vertices": nv, "normals": nn, "scene_triangles": desc.n_tris, "operations": rows}
+        for k, r in rows.items():
+            print("%-16s %-24s median %9.3f ms  (%.3f .. %.3f)" % (name, k, r["median_ms"], r["min_ms"], r["max_ms"]), flush=True)
+    ctx.close()
+    if a.parent_lib:
+        result["host_pointer_refit_parent_against_this"] = compare_with_parent(a.parent_lib, a.runs, a.rounds)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+    cmp_ = result.get("host_pointer_refit_parent_against_this", {})
+    slower = [k for k, r in cmp_.items() if isinstance(r, dict) and not r["this_median_not_above_parent_max"]]
+    if slower:
+        sys.exit("host-pointer REFIT got slower than the parent's spread on: %s" % ", ".join(slower))
+
+
+if __name__ == "__main__":
+    main()

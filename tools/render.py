@@ -4,6 +4,7 @@
 
     python tools/render.py --scene c3 --width 960 --height 540 --spp 64 --out gpurun_out/c3.png
     python tools/render.py --scene c3 --spp 4 --frames 8 --orbit 8 --temporal --out out/orbit.png   (out/orbit_0000.png ...)
+    python tools/render.py --scene textured --spp 16 --spin 12 --out out/spin.png                  (out/spin_0000.png ...)
 """
 import argparse
 import os
@@ -64,6 +65,31 @@ def render_sequence(a, ctx, scene, desc, W, H):
         cam_prev = cam
 
 
+def render_spin(a, ctx, scene, desc, W, H):
+    """--spin: the scene's last mesh turned once about the vertical axis through its centre over N frames, each frame placed with
+    Scene.transform_mesh (16 floats up, the mesh's records rewritten on the GPU) and rendered at --spp into OUT_0000.png ..."""
+    meshes = [(k, op) for k, op in enumerate(o for o in desc.ops if o[0] in ("mesh", "sphere", "plane", "area_light")) if op[0] == "mesh"]
+    prim, op = meshes[-1] if a.spin_prim is None else [m for m in meshes if m[0] == a.spin_prim][0]
+    c = 0.5 * (op[1].min(0).astype(np.float64) + op[1].max(0))
+    stem, ext = os.path.splitext(a.out)
+    ptr = ctx.alloc(W * H * 16)
+    for k in range(a.spin):
+        ang = 2 * np.pi * k / a.spin
+        m = np.eye(4)
+        m[0, 0], m[0, 2], m[2, 0], m[2, 2] = np.cos(ang), np.sin(ang), -np.sin(ang), np.cos(ang)
+        m[:3, 3] = c - m[:3, :3] @ c
+        t0 = time.time()
+        scene.transform_mesh(prim, m.astype(np.float32))
+        t1 = time.time()
+        ctx.memset(ptr, 0, W * H * 16)
+        ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
+        path = "%s_%04d%s" % (stem, k, ext)
+        ag.binding.write_png(path, ctx.resolve(ptr, W * H, a.spp), W, H)
+        print("frame %d: primitive %d turned %.0f degrees in %.2f ms, %d spp in %.1f ms -> %s" %
+              (k, prim, np.degrees(ang), (t1 - t0) * 1e3, a.spp, (time.time() - t1) * 1e3, path))
+    ctx.free(ptr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="c3", choices=["c1", "c2", "c3", "c5", "simple", "heightfield", "textured", "mapped"])
@@ -98,7 +124,12 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="--frames: add each frame's reprojected history (agpt_temporal_accumulate) before the denoiser")
     ap.add_argument("--max-history", type=float, default=32.0, help="--temporal: cap on the reprojected sample count")
+    ap.add_argument("--spin", type=int, default=0, metavar="N",
+                    help="N frames at --spp each with one mesh turned about its vertical axis by agpt_scene_transform_mesh (OUT_0000.png ...)")
+    ap.add_argument("--spin-prim", type=int, default=None, metavar="PRIM", help="--spin: the mesh primitive that turns (default: the scene's last mesh)")
     a = ap.parse_args()
+    if a.spin and a.frames > 1:
+        ap.error("--spin and --frames are separate sequences")
     if (a.temporal or a.orbit) and a.frames < 2:
         ap.error("--temporal and --orbit apply to a sequence (--frames N, N >= 2)")
     W, H = a.width, a.height
@@ -131,6 +162,8 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     if a.frames > 1:
         return render_sequence(a, ctx, scene, desc, W, H)
+    if a.spin:
+        return render_spin(a, ctx, scene, desc, W, H)
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
     features = None
