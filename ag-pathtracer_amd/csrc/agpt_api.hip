@@ -656,6 +656,19 @@ static int sync_mirror(agpt_scene* s, bool arrays) {
     return AGPT_OK;
 }
 
+// DevScene::mdiv_coords_ok from the host's copies of the root boxes (kept current by commit and by refit_done).  A non-finite
+// coordinate does not clear it: such a mesh is traced as before (the reference's own answer to a NaN vertex is a hit at t = NaN and,
+// behind it, a path that an emitter re-casts for ever).
+static int32_t mdiv_coords_ok(const agpt_scene* s) {
+    auto outside = [](float x) { return std::isfinite(x) && !(std::fabs(x) < AGPT_MDIV_COORD_LIMIT); };
+    for (const agpt::HostMesh& m : s->meshes) {
+        if (m.nodes.empty()) continue;
+        for (int a = 0; a < 3; a++)
+            if (outside(m.nodes[0].bmin[a]) || outside(m.nodes[0].bmax[a])) return 0;
+    }
+    return 1;
+}
+
 int agpt_scene_commit(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_commit: scene is NULL");
     if (const int rc = sync_mirror(s, true)) return rc;   // flatten_scene reads every mesh's arrays and boxes
@@ -808,6 +821,7 @@ int agpt_scene_commit(agpt_scene* s) {
     for (const DevPrim& dp : flat.prims)
         if (dp.type == AGPT_PRIM_MESH && dp.n_tris > 0) s->dev.n_meshes++;
     s->dev.cam = s->cam;
+    s->dev.mdiv_coords_ok = mdiv_coords_ok(s);
     s->committed = true;
     return AGPT_OK;
 }
@@ -995,6 +1009,7 @@ static int refit_done(agpt_scene* s, size_t mi, const float root[6], bool arrays
     std::memcpy(mesh.nodes[0].bmax, root + 3, 12);
     s->bounds_stale[mi] = 1;
     s->arrays_stale[mi] = arrays_on_device_only ? 1 : 0;
+    s->dev.mdiv_coords_ok = mdiv_coords_ok(s);
     if (s->prims.size() > 64) return upload_toplevel(s);
     return AGPT_OK;
 }

@@ -188,6 +188,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     constexpr uint32_t CUR_IDLE = 0x7FFFFFFFu, CUR_RECAST = 0x7FFFFFFEu, CUR_PICK = 0x7FFFFFFDu, CUR_FETCH = 0x7FFFFFFCu;
     constexpr uint32_t CUR_B_END = LIST ? CUR_FETCH : CUR_PICK;   // state B: cur < CUR_B_END
     const uint32_t rootpair_base = sc.rootpair_base;
+    const bool coords_ok = sc.mdiv_coords_ok != 0;   // agpt_trace.h: the scene's boxes lie in the Markstein divide's domain
     const unsigned long long mesh_mask0 = sc.mesh_masks[0];
     // LIST lane state: the mesh bits of the current chunk
     unsigned long long mmask = 0;
@@ -304,7 +305,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                 const uint32_t npid = pfc_pid;
                 float4 o = pfc_o;
                 const float4 d = pfc_d;
-                const TraceRay nr = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z));
+                const TraceRay nr = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), coords_ok);
                 unsigned long long skip_bit = 0;
                 if (MIS) {   // MIS rays carry the sampled light's sphere (primitive index, ~0u = infinite light) in o.w; tmax = inf
                     const uint32_t shape = __float_as_uint(o.w);
@@ -451,7 +452,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                 const v3 p = r.O + rayt * r.D;
                 const v3 nO = p + AGPT_EPSILON * r.D;
                 const v3 nD = normalize(r.D);
-                const TraceRay nr = make_trace_ray(nO, nD);
+                const TraceRay nr = make_trace_ray(nO, nD, coords_ok);
                 if (nr.fast) {
                     const float kind = ray_d_w[pid].w;
                     if (kind == 2.f) {
@@ -521,7 +522,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                         if (cvisit) enter_chunk((uint32_t)__ffs((int)cvisit) - 1u);
                     }
                     float4 o = ray_o[pid], d = ray_d[pid];
-                    r = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z));
+                    r = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), coords_ok);
                     rayt = o.w;
                     if (MIS) {
                         mis_area = false;
@@ -587,7 +588,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     bool hl, hr;
                     const uint32_t encl = __float_as_uint(np.n3.x), encr = __float_as_uint(np.n3.y);
                     pair_boxes_fast(np, r, rayt, hl, hr, dl, dr);
-                    if (any_slow) {  // scalar branch: rays with a direction component below 2^-40 (true divisions)
+                    if (any_slow) {  // scalar branch: rays outside the Markstein divide's domain, agpt_trace.h (true divisions)
                         if (!r.fast) pair_boxes_exact(np, r, rayt, hl, hr, dl, dr);
                     }
                     if (COUNT) {
@@ -787,11 +788,12 @@ k_candidates(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     const uint32_t count = count_ptr ? *count_ptr : count_imm;
     const int n_chunks = (sc.n_prims + 63) / 64;
     const int tid = threadIdx.x;
+    const bool coords_ok = sc.mdiv_coords_ok != 0;
     for (uint32_t i = blockIdx.x * AGPT_BLOCK + tid; i < count; i += gridDim.x * AGPT_BLOCK) {
         const uint32_t pid = queue ? queue[i] : i;
         float4 o = ray_o[pid];
         const float4 d = ray_d[pid];
-        const TraceRay nr = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z));
+        const TraceRay nr = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), coords_ok);
         uint32_t skip = 0xFFFFFFFFu;
         if (MIS) {   // MIS rays carry the sampled light's sphere (primitive index, ~0u = infinite light) in o.w; tmax = inf
             const uint32_t shape = __float_as_uint(o.w);
@@ -804,7 +806,7 @@ k_candidates(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
             }
         }
         int n_found = 0;
-        bool all = !nr.fast;   // a direction component below 2^-40: the conservative form does not hold
+        bool all = !nr.fast;   // outside the Markstein divide's domain (agpt_trace.h): the conservative form does not hold
         if (!all) {
             // same conservative form and slack as the short-list prefilter (k_trace_fast: pump_consume)
             const float nox = -(nr.O.x * nr.R.x), noy = -(nr.O.y * nr.R.y), noz = -(nr.O.z * nr.R.z);

@@ -54,6 +54,9 @@
 #define AGPT_ENC_LEAF 0x80000000u
 #define AGPT_ENC_BIGLEAF 0xF0000000u
 
+// bound on |coordinate| of ray origins and mesh boxes under which the trace kernels' Markstein divide equals the division (agpt_trace.h)
+#define AGPT_MDIV_COORD_LIMIT 0x1p86f
+
 struct DevPrim {
     int32_t type;
     int32_t material;   // -1 = nullptr (emitter spheres)
@@ -243,6 +246,10 @@ struct DevScene {
     const DevTexture* textures;
     const int32_t* material_texture;   // [n_materials], or [2 * n_materials] in a scene with roughness / metallic maps (see above)
                                        // (+ DevNormalSlot[n_materials] at normal_slots_offset in a scene with a normal map)
+    // 1 iff every finite coordinate of every mesh root box (hence of every node box) is below AGPT_MDIV_COORD_LIMIT in magnitude: the
+    // condition on the scene under which the trace kernels' Markstein divide equals the division (agpt_trace.h).  Set by
+    // agpt_scene_commit and again after every refit.
+    int32_t mdiv_coords_ok;
 };
 
 // 16-B hit record written by the trace kernel

@@ -13,10 +13,26 @@
 //   Scene::Intersect / P       scene.h:5-19          linear walk over primitives sharing ray.t
 //
 // The six true divisions per box of the reference are evaluated as q = a*r; q += fma(-b,q,a)*r with
-// r = RN(1/D) computed once per ray (Markstein's correction): bit-identical to a/b (checked over 6.4e9
-// operand pairs incl. adversarial mantissas, and by tests/test_gpu_intersect.py), 3 full-rate VALU ops
-// instead of the ~11-op IEEE divide expansion.  Rays with a direction component below 2^-40 (incl. 0, where
-// the reference relies on inf/NaN propagation) take the true-division path.
+// r = RN(1/D) computed once per ray (Markstein's correction), 3 full-rate VALU ops instead of the ~11-op IEEE
+// divide expansion.  Domain of that form, with a = b_box - O and b = D (a CPU model of the three operations over
+// all exponents of a, tests/test_ray_edges.py: test_mdiv_model_pins_the_domain, tests/test_gpu_ray_edges.py):
+//   * |b| >= 2^-40 keeps r = RN(1/b) finite and normal.  It does NOT bound the quotient: that needs a bound on a.
+//   * bit-identical to a/b for |a| in [2^-100, 2^88) with |b| in [2^-40, 2^100] (denormal quotients included), and for a = 0.
+//   * where the quotient overflows (exponent 129 and up, half of the pairs at 128) q = a*r is +-inf, the
+//     correction fma(-b,q,a) the opposite infinity and the result inf - inf = NaN where the division gives
+//     +-inf.  The hardware min/max of box_test_fast drop that NaN where the reference's comparator min/max
+//     carry the infinity: a box whose far plane overflows was REJECTED although the ray enters it (a mesh with
+//     one vertex at y = 2^90 under a ray with D.y = 2^-39 lost the hits on its ordinary triangles), and a box
+//     2^89 away along such an axis was walked although the reference rejects it.
+//   * for 0 < |a| <= 2^-107 the correction term underflows and the quotient can be one ulp off (0.4 % of the
+//     pairs).  No ray on which that changes a box decision while the reference still reports a hit has been
+//     constructed (the triangle and sphere tests lose their own products long before); the cases stay as
+//     tests (ray_edge_cases.domain_edge: tiny-floor).
+// The fast path is therefore taken only when every |D| component is >= 2^-40 AND every |O| component is below
+// AGPT_MDIV_COORD_LIMIT = 2^86 AND every mesh root box of the scene lies within that limit too
+// (DevScene::mdiv_coords_ok, set at commit and after every refit): |a| <= |b_box| + |O| stays below 2^88.  All
+// other rays (incl. zero direction components, where the reference relies on inf/NaN propagation, and non-finite
+// origins) take the true-division path.
 #pragma once
 
 #include "agpt_scene.h"
@@ -24,16 +40,19 @@
 struct TraceRay {
     v3 O, D;
     v3 R;        // RN(1/D)
-    bool fast;   // all |D| >= 2^-40
+    bool fast;   // all |D| >= 2^-40, all |O| < 2^86, the scene's boxes within 2^86: the Markstein divide equals a/b
 };
 
-__device__ __forceinline__ TraceRay make_trace_ray(v3 O, v3 D) {
+// coords_ok: DevScene::mdiv_coords_ok of the scene the ray is traced in
+__device__ __forceinline__ TraceRay make_trace_ray(v3 O, v3 D, bool coords_ok) {
     TraceRay r;
     r.O = O;
     r.D = D;
     r.R = V3(1.0f / D.x, 1.0f / D.y, 1.0f / D.z);
     const float lim = 0x1p-40f;
-    r.fast = (fabsf(D.x) >= lim) && (fabsf(D.y) >= lim) && (fabsf(D.z) >= lim);
+    const float olim = AGPT_MDIV_COORD_LIMIT;
+    r.fast = coords_ok && (fabsf(D.x) >= lim) && (fabsf(D.y) >= lim) && (fabsf(D.z) >= lim) &&
+             (fabsf(O.x) < olim) && (fabsf(O.y) < olim) && (fabsf(O.z) < olim);
     return r;
 }
 
@@ -69,7 +88,7 @@ __device__ __forceinline__ bool box_test_t(float bx0, float by0, float bz0, floa
     return ok;
 }
 
-// Fast-path slab test (all |D| >= 2^-40: every quotient is a finite non-NaN number).  Equivalent to the reference's
+// Fast-path slab test (TraceRay::fast, see the top of this file: every quotient is a finite non-NaN number).  Equivalent to the reference's
 // per-axis chain (bvhtrimesh.h:22-33) because
 //   * with no NaNs the comparator min/max (a<b?a:b) and the hardware v_min/v_max agree up to the sign of zero,
 //     which no later comparison can observe;
@@ -218,7 +237,7 @@ struct TraceCounters {
 template <bool ANY, bool COUNT>
 __device__ __forceinline__ bool trace_scene(const DevScene& sc, v3 O, v3 D, float tmax_in, DevHit& hit,
                                             uint32_t* stack, int stride, TraceCounters& cnt) {
-    TraceRay r = make_trace_ray(O, D);
+    TraceRay r = make_trace_ray(O, D, sc.mdiv_coords_ok != 0);
     float rayt = tmax_in;
     hit.t = tmax_in;
     hit.id = AGPT_HIT_MISS;
