@@ -27,7 +27,7 @@ SOURCES = ["agpt_api.hip"] + SHADE_SOURCES + ["agpt_bvh_device.hip", "agpt_updat
                                                "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {src: SHADE_FLAGS + ["-DAGPT_SHADE_WAVES=%d" % waves] for src, (_, _, _, waves) in zip(SHADE_SOURCES, SHADE_UNITS)}
 HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h", "agpt_shade_arith.h",
-           "agpt_host_scene.hpp", "agpt_bvh_device.h", "agpt_update.h", "agpt_transform.h", "agpt_adaptive.h", "agpt_denoise.h", "agpt_temporal.h", os.path.join("..", "..", "include", "agpt.h")]
+           "agpt_host_scene.hpp", "agpt_bvh_arith.h", "agpt_records.h", "agpt_bvh_device.h", "agpt_update.h", "agpt_transform.h", "agpt_adaptive.h", "agpt_denoise.h", "agpt_temporal.h", os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);
 # explicit __builtin_fmaf calls (Markstein division in agpt_trace.h) stay fused.
 # -fno-slp-vectorize: the SLP pass packs adjacent f32 adds/muls into v_pk_*_f32, which on gfx950 cost more than the two

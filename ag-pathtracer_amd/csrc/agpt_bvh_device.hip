@@ -1,4 +1,5 @@
-// agpt_bvh_device.hip -- build_bvh (agpt_host_scene.cpp) on the GPU, byte for byte.
+// agpt_bvh_device.hip -- build_bvh (agpt_host_scene.cpp) on the GPU, byte for byte.  The box, the SAH decision, a triangle's box and
+// centroid and the union of a child pair are SHARED with the host builder (agpt_bvh_arith.h); what differs is how the work is spread.
 //
 // Work tiers (thresholds in include/agpt.h):
 //   big nodes   (n > AGPT_BVH_DEVICE_LANE_MAX)  level by level; every node is cut into chunks of AGPT_BVH_DEVICE_CHUNK
@@ -11,7 +12,7 @@
 // Exactness.  tminf/tmaxf folds keep the later of equal operands, so a fold's result is "the extreme value, taken from the
 // last position holding it" (this only matters for +0.0 vs -0.0).  Every fold here reduces 64-bit keys
 // (order-preserving value bits with -0 == +0, position) with integer min/max -- commutative and exact in any order, also
-// as atomics -- and reads the winning position's value back.  The initial +-1e34 of Box() is position 0.
+// as atomics -- and reads the winning position's value back.  The initial +-kBoxEmpty of Box() is position 0.
 // Partition: std::partition (libstdc++, bidirectional) swaps the i-th non-matching primitive from the left with the i-th
 // matching one from the right; with m matching primitives that is "rank the non-matching ones of [start, start+m) from
 // the left, the matching ones of [start+m, end) from the right, swap equal ranks".
@@ -22,8 +23,8 @@
 #include <string>
 #include <vector>
 
+#include "agpt_bvh_arith.h"
 #include "agpt_host_scene.hpp"
-#include "agpt_math.h"
 
 namespace agpt {
 int report_error(int code, const std::string& msg);  // agpt_api.hip
@@ -31,92 +32,15 @@ int report_error(int code, const std::string& msg);  // agpt_api.hip
 
 namespace {
 
+using namespace agpt;  // agpt_bvh_arith.h
+
 typedef unsigned long long u64;
 
-constexpr int kBuckets = 12;
 constexpr int kLaneMax = AGPT_BVH_DEVICE_LANE_MAX;
 constexpr int kChunk = AGPT_BVH_DEVICE_CHUNK;
 constexpr int kWave = 64;
 static_assert(kLaneMax >= 2, "big nodes must not reach the n <= 2 rule");
 static_assert(kChunk % kWave == 0, "");
-
-// Box of agpt_host_scene.cpp (Box() = +-1e34, tminf/tmaxf growth), same operation order
-struct DBox {
-    float lo[3], hi[3];
-    AGPT_HD DBox() {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = 1e34f;
-            hi[a] = -1e34f;
-        }
-    }
-    AGPT_HD void grow(const DBox& b) {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = tminf(lo[a], b.lo[a]);
-            hi[a] = tmaxf(hi[a], b.hi[a]);
-        }
-    }
-    AGPT_HD void grow(float x, float y, float z) {
-        lo[0] = tminf(lo[0], x);
-        lo[1] = tminf(lo[1], y);
-        lo[2] = tminf(lo[2], z);
-        hi[0] = tmaxf(hi[0], x);
-        hi[1] = tmaxf(hi[1], y);
-        hi[2] = tmaxf(hi[2], z);
-    }
-    AGPT_HD float extent(int a) const { return hi[a] - lo[a]; }
-    AGPT_HD int longest_axis() const {
-        int a = 0;
-        if (extent(1) > extent(0)) a = 1;
-        if (extent(2) > extent(a)) a = 2;
-        return a;
-    }
-    AGPT_HD float area() const {
-        float dx = extent(0), dy = extent(1), dz = extent(2);
-        return 2 * (dx * dy + dx * dz + dy * dz);
-    }
-    AGPT_HD float offset(float p, int a) const {
-        float o = p - lo[a];
-        if (hi[a] > lo[a]) o /= hi[a] - lo[a];
-        return o;
-    }
-};
-
-AGPT_HD int bucket_of(const DBox& cb, float c, int axis) {
-    int b = (int)(kBuckets * cb.offset(c, axis));
-    if (b == kBuckets) b = kBuckets - 1;
-    return b;
-}
-
-// the SAH part of choose_split (agpt_host_scene.cpp): 11 costs in the host's operation order, first minimum wins
-AGPT_HD int sah_pick(const DBox* bb, const int* count, const DBox& bounds, float* min_cost_out) {
-    float cost[kBuckets - 1];
-#pragma unroll
-    for (int i = 0; i < kBuckets - 1; i++) {
-        DBox b0, b1;
-        int c0 = 0, c1 = 0;
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-            b0.grow(bb[j]);
-            c0 += count[j];
-        }
-#pragma unroll
-        for (int j = i + 1; j < kBuckets; j++) {
-            b1.grow(bb[j]);
-            c1 += count[j];
-        }
-        cost[i] = 1 + (c0 * b0.area() + c1 * b1.area()) / bounds.area();
-    }
-    float min_cost = cost[0];
-    int split = 0;
-#pragma unroll
-    for (int i = 1; i < kBuckets - 1; i++)
-        if (cost[i] < min_cost) {
-            min_cost = cost[i];
-            split = i;
-        }
-    *min_cost_out = min_cost;
-    return split;
-}
 
 // ---- per-triangle data: A = (lo.xyz, c.x), B = (hi.xyz, c.y), C = c.z -------------------------------------------------
 struct Tris {
@@ -137,9 +61,9 @@ struct Tris {
         }
     }
     __device__ float cent(int t, int axis) const { return comp(t, 6 + axis); }
-    __device__ DBox box(int t) const {
+    __device__ Box box(int t) const {
         const float4 a = A[t], b = B[t];
-        DBox r;
+        Box r;
         r.lo[0] = a.x, r.lo[1] = a.y, r.lo[2] = a.z;
         r.hi[0] = b.x, r.hi[1] = b.y, r.hi[2] = b.z;
         return r;
@@ -175,7 +99,7 @@ struct Rec {             // one per node the level passes create (big nodes and 
 struct Lvl {             // a big node of the current level
     int rec, blk_first, nblk, act;  // act: 1 = binned and split this level
     int axis, split, m, k;          // split bucket, primitives on the left, swaps of the partition
-    DBox bounds, cb;
+    Box bounds, cb;
 };
 struct Ctr {
     int blocks, next_cnt;  // reset per level (adjacent: one memset)
@@ -200,10 +124,13 @@ struct Bufs {
     int n, rec_cap, lvl_cap, blk_cap, max_prims;
 };
 
-__device__ __forceinline__ float key_value(const Bufs& B, u64 k, bool is_min, int q, float init) {
+// the initial keys of a fold (Box()'s values at position 0) and the value a folded key stands for
+__device__ __forceinline__ u64 kmin0() { return kmin(kBoxEmpty, 0); }
+__device__ __forceinline__ u64 kmax0() { return kmax(-kBoxEmpty, 0); }
+__device__ __forceinline__ float key_value(const Bufs& B, u64 k, bool is_min, int q) {
     const uint32_t lo = (uint32_t)k;
     const uint32_t pos1 = is_min ? 0xFFFFFFFFu - lo : lo;
-    return pos1 == 0 ? init : B.tr.comp(B.perm[pos1 - 1], q);
+    return pos1 == 0 ? (is_min ? kBoxEmpty : -kBoxEmpty) : B.tr.comp(B.perm[pos1 - 1], q);
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------
@@ -212,16 +139,15 @@ __global__ void k_prep(Bufs B, const float* __restrict__ V, const int32_t* __res
     bool bad = false;
     uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0, 0, 0};
     if (t < B.n) {
-        DBox b;
+        v3 p[3];
         for (int k = 0; k < 3; k++) {
             const int v = I[(size_t)9 * t + 3 * k];
-            const float x = V[(size_t)3 * v], y = V[(size_t)3 * v + 1], z = V[(size_t)3 * v + 2];
-            bad |= !__builtin_isfinite(x) || !__builtin_isfinite(y) || !__builtin_isfinite(z);
-            b.grow(x, y, z);
+            p[k] = V3(V[(size_t)3 * v], V[(size_t)3 * v + 1], V[(size_t)3 * v + 2]);
+            bad |= !__builtin_isfinite(p[k].x) || !__builtin_isfinite(p[k].y) || !__builtin_isfinite(p[k].z);
         }
         float c[3];
+        const Box b = tri_box(p[0], p[1], p[2], c);
         for (int a = 0; a < 3; a++) {
-            c[a] = (b.lo[a] + b.hi[a]) * 0.5f;
             bad |= !__builtin_isfinite(c[a]);
             mn[a] = ord_bits(b.lo[a]);
             mx[a] = ord_bits(b.hi[a]);
@@ -278,7 +204,7 @@ __global__ void k_level_setup(Bufs B, const int* __restrict__ ids, int cnt) {
         return;
     }
     for (int b = 0; b < nb; b++) B.blk_node[first + b] = j;
-    const u64 imin = kmin(1e34f, 0), imax = kmax(-1e34f, 0);
+    const u64 imin = kmin0(), imax = kmax0();
     for (int a = 0; a < 3; a++) {
         B.keys[(size_t)j * 12 + a] = imin;
         B.keys[(size_t)j * 12 + 3 + a] = imax;
@@ -314,8 +240,8 @@ __global__ void __launch_bounds__(kWave) k_bounds(Bufs B) {
     const int lane = threadIdx.x;
     u64 k[12];
     for (int a = 0; a < 3; a++) {
-        k[a] = k[6 + a] = kmin(1e34f, 0);
-        k[3 + a] = k[9 + a] = kmax(-1e34f, 0);
+        k[a] = k[6 + a] = kmin0();
+        k[3 + a] = k[9 + a] = kmax0();
     }
     for (int i = lo + lane; i < hi; i += kWave) {
         const int t = B.perm[i];
@@ -361,12 +287,12 @@ __global__ void k_split_axis(Bufs B, int cnt) {
     Lvl& L = B.lv[j];
     Rec& r = B.recs[L.rec];
     const u64* k = B.keys + (size_t)j * 12;
-    DBox bounds, cb;
+    Box bounds, cb;
     for (int a = 0; a < 3; a++) {
-        bounds.lo[a] = key_value(B, k[a], true, a, 1e34f);
-        bounds.hi[a] = key_value(B, k[3 + a], false, 3 + a, -1e34f);
-        cb.lo[a] = key_value(B, k[6 + a], true, 6 + a, 1e34f);
-        cb.hi[a] = key_value(B, k[9 + a], false, 6 + a, -1e34f);
+        bounds.lo[a] = key_value(B, k[a], true, a);
+        bounds.hi[a] = key_value(B, k[3 + a], false, 3 + a);
+        cb.lo[a] = key_value(B, k[6 + a], true, 6 + a);
+        cb.hi[a] = key_value(B, k[9 + a], false, 6 + a);
         r.lo[a] = bounds.lo[a];
         r.hi[a] = bounds.hi[a];
     }
@@ -390,10 +316,10 @@ __global__ void __launch_bounds__(kWave) k_bins(Bufs B) {
     __shared__ u64 sk[kBuckets * 6];
     __shared__ int sc[kBuckets];
     const int lane = threadIdx.x;
-    for (int q = lane; q < kBuckets * 6; q += kWave) sk[q] = (q % 6) < 3 ? kmin(1e34f, 0) : kmax(-1e34f, 0);
+    for (int q = lane; q < kBuckets * 6; q += kWave) sk[q] = (q % 6) < 3 ? kmin0() : kmax0();
     if (lane < kBuckets) sc[lane] = 0;
     __syncthreads();
-    const DBox cb = L.cb;
+    const Box cb = L.cb;
     const int axis = L.axis;
     for (int i = lo + lane; i < hi; i += kWave) {
         const int t = B.perm[i];
@@ -428,7 +354,7 @@ __global__ void k_split_sah(Bufs B, int cnt, int* __restrict__ next_ids) {
     Lvl& L = B.lv[j];
     if (!L.act) return;
     Rec& r = B.recs[L.rec];
-    DBox bb[kBuckets];
+    Box bb[kBuckets];
     int count[kBuckets];
 #pragma unroll
     for (int b = 0; b < kBuckets; b++) {
@@ -436,14 +362,13 @@ __global__ void k_split_sah(Bufs B, int cnt, int* __restrict__ next_ids) {
         count[b] = B.bincnt[o];
         if (count[b] > 0)
             for (int a = 0; a < 3; a++) {
-                bb[b].lo[a] = key_value(B, B.binkeys[o * 6 + a], true, a, 1e34f);
-                bb[b].hi[a] = key_value(B, B.binkeys[o * 6 + 3 + a], false, 3 + a, -1e34f);
+                bb[b].lo[a] = key_value(B, B.binkeys[o * 6 + a], true, a);
+                bb[b].hi[a] = key_value(B, B.binkeys[o * 6 + 3 + a], false, 3 + a);
             }
     }
     float min_cost;
     const int split = sah_pick(bb, count, L.bounds, &min_cost);
-    const float leaf_cost = (float)r.n;
-    if (!(r.n > B.max_prims || min_cost < leaf_cost)) {
+    if (!sah_splits(r.n, B.max_prims, min_cost)) {
         L.act = 0;
         leaf_rec(B, r);
         return;
@@ -579,18 +504,18 @@ __global__ void __launch_bounds__(kWave) k_part_swap(Bufs B) {
     }
 }
 
-// ---- lane tier: Builder::build / choose_split of agpt_host_scene.cpp on one lane ------------------------------------
+// ---- lane tier: Builder::build / choose_split of agpt_host_scene.cpp on one lane, over the shared arithmetic ---------
 struct LaneBins {
     float (*bb)[kWave];  // [kBuckets * 6][kWave]
     int (*cnt)[kWave];   // [kBuckets][kWave]
 };
 
-__device__ int lane_choose(const Bufs& B, int start, int end, DBox& bounds, LaneBins sh, int lane) {
-    bounds = DBox();
+__device__ int lane_choose(const Bufs& B, int start, int end, Box& bounds, LaneBins sh, int lane) {
+    bounds = Box();
     for (int i = start; i < end; i++) bounds.grow(B.tr.box(B.perm[i]));
     const int n = end - start;
     if (n == 1) return -1;
-    DBox cb;
+    Box cb;
     for (int i = start; i < end; i++) {
         const int t = B.perm[i];
         cb.grow(B.tr.cent(t, 0), B.tr.cent(t, 1), B.tr.cent(t, 2));
@@ -609,21 +534,21 @@ __device__ int lane_choose(const Bufs& B, int start, int end, DBox& bounds, Lane
     for (int b = 0; b < kBuckets; b++) {
         sh.cnt[b][lane] = 0;
         for (int a = 0; a < 3; a++) {
-            sh.bb[b * 6 + a][lane] = 1e34f;
-            sh.bb[b * 6 + 3 + a][lane] = -1e34f;
+            sh.bb[b * 6 + a][lane] = kBoxEmpty;
+            sh.bb[b * 6 + 3 + a][lane] = -kBoxEmpty;
         }
     }
     for (int i = start; i < end; i++) {
         const int t = B.perm[i];
         const int b = bucket_of(cb, B.tr.cent(t, axis), axis);
         sh.cnt[b][lane]++;
-        const DBox pb = B.tr.box(t);
+        const Box pb = B.tr.box(t);
         for (int a = 0; a < 3; a++) {
             sh.bb[b * 6 + a][lane] = tminf(sh.bb[b * 6 + a][lane], pb.lo[a]);
             sh.bb[b * 6 + 3 + a][lane] = tmaxf(sh.bb[b * 6 + 3 + a][lane], pb.hi[a]);
         }
     }
-    DBox bb[kBuckets];
+    Box bb[kBuckets];
     int count[kBuckets];
 #pragma unroll
     for (int b = 0; b < kBuckets; b++) {
@@ -635,8 +560,7 @@ __device__ int lane_choose(const Bufs& B, int start, int end, DBox& bounds, Lane
     }
     float min_cost;
     const int split = sah_pick(bb, count, bounds, &min_cost);
-    const float leaf_cost = (float)n;
-    if (n > B.max_prims || min_cost < leaf_cost) {
+    if (sah_splits(n, B.max_prims, min_cost)) {
         // std::partition (libstdc++, bidirectional iterators)
         int first = start, last = end;
         auto pred = [&](int i) { return bucket_of(cb, B.tr.cent(B.perm[i], axis), axis) <= split; };
@@ -679,7 +603,7 @@ __global__ void __launch_bounds__(kWave) k_lane(Bufs B, int cnt) {
     while (sp > 0) {
         const int4 f = stk[--sp];
         total++;
-        DBox bounds;
+        Box bounds;
         const int mid = lane_choose(B, f.x, f.y, bounds, sh, lane);
         agpt_bvh_node& o = nd[f.z];
         if (mid < 0) {
@@ -704,10 +628,7 @@ __global__ void __launch_bounds__(kWave) k_lane(Bufs B, int cnt) {
         if (s == 1 || nd[s].count != 0) continue;
         agpt_bvh_node& o = nd[s];
         const agpt_bvh_node &c0 = nd[o.first], &c1 = nd[o.first + 1];
-        for (int a = 0; a < 3; a++) {
-            o.bmin[a] = tminf(c0.bmin[a], c1.bmin[a]);
-            o.bmax[a] = tmaxf(c0.bmax[a], c1.bmax[a]);
-        }
+        pair_union(c0.bmin, c0.bmax, c1.bmin, c1.bmax, o.bmin, o.bmax);
     }
     r.total = total;
     for (int a = 0; a < 3; a++) {
@@ -725,10 +646,7 @@ __global__ void k_up(Bufs B, int rb, int re) {
     if (r.kind != REC_INTERIOR) return;
     const Rec &L = B.recs[r.left], &R = B.recs[r.left + 1];
     r.total = 1 + L.total + R.total;
-    for (int a = 0; a < 3; a++) {
-        r.lo[a] = tminf(L.lo[a], R.lo[a]);
-        r.hi[a] = tmaxf(L.hi[a], R.hi[a]);
-    }
+    pair_union(L.lo, L.hi, R.lo, R.hi, r.lo, r.hi);
 }
 
 __global__ void k_down(Bufs B, int rb, int re) {

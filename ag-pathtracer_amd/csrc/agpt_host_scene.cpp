@@ -1,6 +1,7 @@
 // agpt_host_scene.cpp -- host-side scene preparation (runs once per scene; the reference does the same work in
 // BVHTriMesh's constructor, DisneyMaterial's constructor and Camera's constructor).
 #include "agpt_host_scene.hpp"
+#include "agpt_bvh_arith.h"
 #include "agpt_update.h"
 
 #include <algorithm>
@@ -28,53 +29,16 @@ using uv_t = v2;
 // ------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct Box {
-    float lo[3], hi[3];
-    Box() {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = 1e34f;
-            hi[a] = -1e34f;
-        }
-    }
-    void grow(const Box& b) {
-        for (int a = 0; a < 3; a++) {
-            lo[a] = tminf(lo[a], b.lo[a]);
-            hi[a] = tmaxf(hi[a], b.hi[a]);
-        }
-    }
-    void grow(v3 p) {
-        lo[0] = tminf(lo[0], p.x);
-        lo[1] = tminf(lo[1], p.y);
-        lo[2] = tminf(lo[2], p.z);
-        hi[0] = tmaxf(hi[0], p.x);
-        hi[1] = tmaxf(hi[1], p.y);
-        hi[2] = tmaxf(hi[2], p.z);
-    }
-    float extent(int a) const { return hi[a] - lo[a]; }
-    int longest_axis() const {
-        int a = 0;
-        if (extent(1) > extent(0)) a = 1;
-        if (extent(2) > extent(a)) a = 2;
-        return a;
-    }
-    float area() const {
-        float dx = extent(0), dy = extent(1), dz = extent(2);
-        return 2 * (dx * dy + dx * dz + dy * dz);
-    }
-    float offset(float p, int a) const {
-        float o = p - lo[a];
-        if (hi[a] > lo[a]) o /= hi[a] - lo[a];
-        return o;
-    }
-};
+// an interior node's bounds from its child pair
+inline void node_union(const agpt_bvh_node& l, const agpt_bvh_node& r, agpt_bvh_node& nd) {
+    pair_union(l.bmin, l.bmax, r.bmin, r.bmax, nd.bmin, nd.bmax);
+}
 
 struct BuildPrim {
     int32_t index;
     Box box;
     float c[3];
 };
-
-constexpr int kBuckets = 12;
 
 struct Builder {
     std::vector<BuildPrim>& prims;  // shared; every task works on its own [start, end) range
@@ -85,12 +49,6 @@ struct Builder {
     int max_depth = 0;
 
     Builder(std::vector<agpt_bvh_node>& n, std::vector<BuildPrim>& p, int mp) : prims(p), nodes(n), max_prims(mp) {}
-
-    static int bucket_of(const Box& cb, const BuildPrim& p, int axis) {
-        int b = (int)(kBuckets * cb.offset(p.c[axis], axis));
-        if (b == kBuckets) b = kBuckets - 1;
-        return b;
-    }
 
     void leaf(int slot, int start, int n, const Box& b, int depth) {
         agpt_bvh_node& nd = nodes[slot];
@@ -109,7 +67,7 @@ struct Builder {
         const int n = end - start;
         if (n == 1) return -1;
         Box cb;
-        for (int i = start; i < end; i++) cb.grow(V3(prims[i].c[0], prims[i].c[1], prims[i].c[2]));
+        for (int i = start; i < end; i++) cb.grow(prims[i].c[0], prims[i].c[1], prims[i].c[2]);
         const int axis = cb.longest_axis();
         if (cb.lo[axis] == cb.hi[axis]) return -1;
         int mid = (start + end) / 2;
@@ -121,35 +79,15 @@ struct Builder {
         int count[kBuckets] = {0};
         Box bb[kBuckets];
         for (int i = start; i < end; i++) {
-            int b = bucket_of(cb, prims[i], axis);
+            int b = bucket_of(cb, prims[i].c[axis], axis);
             count[b]++;
             bb[b].grow(prims[i].box);
         }
-        float cost[kBuckets - 1];
-        for (int i = 0; i < kBuckets - 1; i++) {
-            Box b0, b1;
-            int c0 = 0, c1 = 0;
-            for (int j = 0; j <= i; j++) {
-                b0.grow(bb[j]);
-                c0 += count[j];
-            }
-            for (int j = i + 1; j < kBuckets; j++) {
-                b1.grow(bb[j]);
-                c1 += count[j];
-            }
-            cost[i] = 1 + (c0 * b0.area() + c1 * b1.area()) / bounds.area();
-        }
-        float min_cost = cost[0];
-        int split = 0;
-        for (int i = 1; i < kBuckets - 1; i++)
-            if (cost[i] < min_cost) {
-                min_cost = cost[i];
-                split = i;
-            }
-        const float leaf_cost = (float)n;
-        if (n > max_prims || min_cost < leaf_cost) {
+        float min_cost;
+        const int split = sah_pick(bb, count, bounds, &min_cost);
+        if (sah_splits(n, max_prims, min_cost)) {
             BuildPrim* pmid = std::partition(&prims[start], &prims[end - 1] + 1,
-                                             [&](const BuildPrim& p) { return bucket_of(cb, p, axis) <= split; });
+                                             [&](const BuildPrim& p) { return bucket_of(cb, p.c[axis], axis) <= split; });
             return (int)(pmid - &prims[0]);
         }
         return -1;
@@ -164,11 +102,8 @@ struct Builder {
         next_pair += 2;
         build(start, mid, first, depth + 1);
         build(mid, end, first + 1, depth + 1);
-        agpt_bvh_node& nd = nodes[slot];  // Bounds::Union of the children (bvhtrimesh.h:113-118)
-        for (int a = 0; a < 3; a++) {
-            nd.bmin[a] = tminf(nodes[first].bmin[a], nodes[first + 1].bmin[a]);
-            nd.bmax[a] = tmaxf(nodes[first].bmax[a], nodes[first + 1].bmax[a]);
-        }
+        agpt_bvh_node& nd = nodes[slot];
+        node_union(nodes[first], nodes[first + 1], nd);
         nd.first = first;
         nd.count = 0;
     }
@@ -220,10 +155,7 @@ SubTree build_subtree(std::vector<BuildPrim>& shared, int start, int end, int ma
     embed(L, 2, baseL);
     embed(R, 3, baseR);
     agpt_bvh_node& nd = out.nodes[0];
-    for (int a = 0; a < 3; a++) {
-        nd.bmin[a] = tminf(out.nodes[2].bmin[a], out.nodes[3].bmin[a]);
-        nd.bmax[a] = tmaxf(out.nodes[2].bmax[a], out.nodes[3].bmax[a]);
-    }
+    node_union(out.nodes[2], out.nodes[3], nd);
     nd.first = 2;
     nd.count = 0;
     return out;
@@ -237,8 +169,8 @@ void build_bvh(HostMesh& mesh, int max_prims_in_node) {
     for (int t = 0; t < n_tris; t++) {
         BuildPrim& p = prims[t];
         p.index = 3 * t;
-        for (int k = 0; k < 3; k++) p.box.grow(mesh.vertices[mesh.indices[9 * t + 3 * k]]);
-        for (int a = 0; a < 3; a++) p.c[a] = (p.box.lo[a] + p.box.hi[a]) * 0.5f;
+        const int32_t* ix = &mesh.indices[9 * t];
+        p.box = tri_box(mesh.vertices[ix[0]], mesh.vertices[ix[3]], mesh.vertices[ix[6]], p.c);
     }
     // the top levels of the recursion fan out over host threads (subtrees touch disjoint primitive ranges); the result
     // is byte-identical to the sequential build
@@ -267,18 +199,14 @@ bool refit_bvh(const std::vector<v3>& vertices, const std::vector<int32_t>& indi
             if (nd.first < 0 || nd.count > n_tris - nd.first) return false;
             Box bounds;
             for (int s = nd.first; s < nd.first + nd.count; s++) {
-                Box box;
-                for (int k = 0; k < 3; k++) box.grow(vertices[indices[3 * (size_t)prim_index[s] + 3 * k]]);
-                bounds.grow(box);
+                const int32_t* ix = &indices[3 * (size_t)prim_index[s]];
+                bounds.grow(tri_box(vertices[ix[0]], vertices[ix[3]], vertices[ix[6]]));
             }
             std::memcpy(nd.bmin, bounds.lo, 12);
             std::memcpy(nd.bmax, bounds.hi, 12);
         } else {
             if (nd.count < 0 || nd.first <= i || nd.first < 2 || nd.first >= total_nodes) return false;
-            for (int a = 0; a < 3; a++) {
-                nd.bmin[a] = tminf(nodes[nd.first].bmin[a], nodes[nd.first + 1].bmin[a]);
-                nd.bmax[a] = tmaxf(nodes[nd.first].bmax[a], nodes[nd.first + 1].bmax[a]);
-            }
+            node_union(nodes[nd.first], nodes[nd.first + 1], nd);
         }
     }
     return true;
@@ -537,51 +465,20 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
             if (i == 1) continue;  // unused slot
             const agpt_bvh_node& n = mesh.nodes[i];
             uint32_t first = (uint32_t)n.first + (uint32_t)(n.count > 0 ? tb : nb);
-            // .z = the traversal encoding of this node (what a parent pushes / descends to), precomputed here so the
-            // kernels do not rebuild it per visit; big leaves keep first/count and are flagged in .w
-            uint32_t z = first, w = (uint32_t)n.count;
-            if (n.count > 0) {
-                if (n.count <= 7 && first < 0x10000000u)
-                    z = AGPT_ENC_LEAF | ((uint32_t)(n.count - 1) << 28) | first;
-                else {
-                    z = AGPT_ENC_BIGLEAF | (uint32_t)out.bigleaves.size();
-                    out.bigleaves.push_back(first);
-                    out.bigleaves.push_back((uint32_t)n.count);
-                }
-            }
-            // sibling pairs (node indices 2k, 2k+1) share one 64-B record with the two boxes interleaved component by
-            // component, so a lane's four 16-B loads land as (left, right) register pairs for packed-fp32 slab maths:
-            //   [0] lx0 rx0 ly0 ry0   [1] lz0 rz0 lx1 rx1   [2] ly1 ry1 lz1 rz1   [3] zL zR wL wR
+            // the node's half of its sibling pair's record (agpt_scene.h), with its traversal encoding precomputed
             float* rec = reinterpret_cast<float*>(&out.nodes[4 * ((nb + i) >> 1)]);
-            const size_t side = (nb + i) & 1;
-            for (int a = 0; a < 3; a++) {
-                rec[2 * a + side] = n.bmin[a];
-                rec[6 + 2 * a + side] = n.bmax[a];
-            }
-            rec[12 + side] = bits(z);
-            rec[14 + side] = bits(w);
+            pair_record_set_box(rec, (nb + i) & 1, n.bmin, n.bmax);
+            pair_record_set_enc(rec, (nb + i) & 1, node_encoding(first, n.count, out.bigleaves), (uint32_t)n.count);
         }
         {
             const agpt_bvh_node& r = mesh.nodes[0];
             std::memcpy(dp.root_bmin, r.bmin, 12);
             std::memcpy(dp.root_bmax, r.bmax, 12);
-            uint32_t first = (uint32_t)r.first + (uint32_t)(r.count > 0 ? tb : nb);
-            if (r.count == 0)
-                dp.root_enc = first;
-            else if (r.count <= 7 && first < 0x10000000u)
-                dp.root_enc = AGPT_ENC_LEAF | ((uint32_t)(r.count - 1) << 28) | first;
-            else {
-                dp.root_enc = AGPT_ENC_BIGLEAF | (uint32_t)(out.bigleaves.size() / 2);
-                out.bigleaves.push_back(first);
-                out.bigleaves.push_back((uint32_t)r.count);
-            }
+            dp.root_enc = node_encoding((uint32_t)r.first + (uint32_t)(r.count > 0 ? tb : nb), r.count, out.bigleaves);
         }
         if (pi < 64 * AGPT_MAX_CHUNKS && n_tris > 0) {
             float* rec = reinterpret_cast<float*>(&out.nodes[4 * ((out.rootpair_base + 2 * pi) >> 1)]);
-            for (int a = 0; a < 3; a++) {
-                rec[2 * a] = rec[2 * a + 1] = dp.root_bmin[a];
-                rec[6 + 2 * a] = rec[6 + 2 * a + 1] = dp.root_bmax[a];
-            }
+            rootpair_record_set_box(rec, dp.root_bmin, dp.root_bmax);
             rec[12] = rec[13] = bits(dp.root_enc);
             out.mesh_masks[pi / 64] |= 1ull << (pi % 64);
         }
@@ -597,24 +494,17 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
                 uv1 = mesh.texcoords[ix[5]];
                 uv2 = mesh.texcoords[ix[8]];
             } else {
-                uv0.x = 0; uv0.y = 0;
-                uv1.x = 1; uv1.y = 0;
-                uv2.x = 1; uv2.y = 1;
+                default_uv(uv0, uv1, uv2);
             }
-            const TriFrame f = triangle_frame(v0, v1, v2, uv0, uv1, uv2);   // (agpt_update.h: shared with the device update)
+            const TriFrame f = triangle_frame(v0, v1, v2, uv0, uv1, uv2);   // (agpt_records.h: shared with the device update)
             reject[t] = f.reject;
-            const v3 ng = f.ng, ss = f.ss;
             v3 n0 = V3s(0), n1 = V3s(0), n2 = V3s(0);
             if (dp.has_normals) {
                 n0 = mesh.normals[ix[1]];
                 n1 = mesh.normals[ix[4]];
                 n2 = mesh.normals[ix[7]];
             }
-            float4* q = &out.tri_shade[4 * (tb + t)];
-            q[0] = F4(ng.x, ng.y, ng.z, ss.x);
-            q[1] = F4(ss.y, ss.z, n0.x, n0.y);
-            q[2] = F4(n0.z, n1.x, n1.y, n1.z);
-            q[3] = F4(n2.x, n2.y, n2.z, bits((uint32_t)pi));
+            pack_tri_shade(&out.tri_shade[4 * (tb + t)], f, n0, n1, n2, (uint32_t)pi);
             if (out.want_tri_uv) {
                 out.tri_uv[2 * (tb + t)] = F4(uv0.x, uv0.y, uv1.x, uv1.y);
                 out.tri_uv[2 * (tb + t) + 1] = F4(uv2.x, uv2.y, 0.f, 0.f);
@@ -624,10 +514,7 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
             const int t = mesh.prim_index[s] / 3;
             const int32_t* ix = &mesh.indices[9 * t];
             const v3 v0 = mesh.vertices[ix[0]], v1 = mesh.vertices[ix[3]], v2 = mesh.vertices[ix[6]];
-            float4* q = &out.tri_verts[3 * (tb + s)];
-            q[0] = F4(v0.x, v0.y, v0.z, bits((uint32_t)(tb + t)));
-            q[1] = F4(v1.x, v1.y, v1.z, bits(reject[t]));
-            q[2] = F4(v2.x, v2.y, v2.z, 0.f);
+            pack_tri_verts(&out.tri_verts[3 * (tb + s)], v0, v1, v2, (uint32_t)(tb + t), reject[t]);
         }
         out.prims.push_back(dp);
     }
@@ -642,8 +529,9 @@ void flatten_scene(const std::vector<HostMesh>& meshes, const std::vector<HostSp
             if (dp.type != AGPT_PRIM_MESH)
                 out.analytic_masks[c] |= 1ull << (pi % 64);
             else if (dp.n_tris > 0) {
-                out.prefilter.push_back(F4(dp.root_bmin[0], dp.root_bmin[1], dp.root_bmin[2], bits((uint32_t)(pi % 64))));
-                out.prefilter.push_back(F4(dp.root_bmax[0], dp.root_bmax[1], dp.root_bmax[2], 0.f));
+                out.prefilter.push_back(F4(0, 0, 0, bits((uint32_t)(pi % 64))));
+                out.prefilter.push_back(F4(0, 0, 0, 0));
+                prefilter_record_set_box(&out.prefilter[out.prefilter.size() - 2].x, dp.root_bmin, dp.root_bmax);
             }
         }
     }

@@ -28,6 +28,8 @@
 //                           from global memory: the halves above are all the LDS a block of k_shade has left
 //   prims      DevPrim[P]   Scene::primitives in insertion order (scene.h:5-19 walks them linearly)
 //   materials  DevMaterial[M], lights DevLight[L]
+// The node, root-pair, prefilter, tri_verts and tri_shade records are written by the functions of agpt_records.h alone, on the host
+// (flatten_scene) and on the device (agpt_update.hip).
 #pragma once
 
 #include "agpt_math.h"

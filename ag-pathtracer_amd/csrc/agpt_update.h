@@ -1,6 +1,7 @@
 // agpt_update.h -- agpt_scene_update_mesh's device path (agpt_update.hip): the records of ONE mesh of a committed scene -- its
 // triangles' tri_verts / tri_shade entries, the bounds of its BVH nodes, its root box wherever the scene keeps a copy -- rewritten
-// on the GPU for new vertex positions and normals, byte for byte what flatten_scene (agpt_host_scene.cpp) writes for them.
+// on the GPU for new vertex positions and normals, byte for byte what flatten_scene (agpt_host_scene.cpp) writes for them: both call
+// the record writers of agpt_records.h and the box arithmetic of agpt_bvh_arith.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,46 +10,10 @@
 #include <vector>
 
 #include "agpt_host_scene.hpp"
+#include "agpt_records.h"
 #include "agpt_transform.h"
 
 namespace agpt {
-
-// The ray-independent part of TriangleIntersect (trianglemesh.cpp:46-80 + the SurfaceInteraction ctor, intersectable.h:69): uv
-// deltas, dpdu / dpdv, the degenerate branches, the geometric normal and ss = normalize(dpdu).  flatten_scene runs it on the host
-// and k_update_tris on the device: ONE source, every operation rounded on its own (both units compile with -ffp-contract=off,
-// correctly rounded divide and square root), so the two produce the same bits -- these fields decide rays.
-struct TriFrame {
-    v3 ng, ss;
-    uint32_t reject;   // AGPT_TRI_FLAG_REJECT for a zero-area triangle (quirk 11)
-};
-AGPT_HD TriFrame triangle_frame(v3 v0, v3 v1, v3 v2, struct v2 uv0, struct v2 uv1, struct v2 uv2) {
-    TriFrame f;
-    f.reject = 0;
-    const float du02x = uv0.x - uv2.x, du02y = uv0.y - uv2.y;
-    const float du12x = uv1.x - uv2.x, du12y = uv1.y - uv2.y;
-    const v3 dp02 = v0 - v2, dp12 = v1 - v2;
-    const float determinant = du02x * du12y - du02y * du12x;
-    const bool degenerate_uv = (double)fabsf(determinant) < 1e-8;
-    v3 dpdu = V3s(0), dpdv = V3s(0);
-    if (!degenerate_uv) {
-        const float invdet = 1 / determinant;
-        dpdu = (du12y * dp02 - du02y * dp12) * invdet;
-        dpdv = (-du12x * dp02 + du02x * dp12) * invdet;
-    }
-    if (degenerate_uv || sqrlen(cross(dpdu, dpdv)) == 0) {
-        v3 ng = cross(v2 - v0, v1 - v0);
-        if (sqrlen(ng) == 0) {
-            f.reject = AGPT_TRI_FLAG_REJECT;
-            dpdu = V3(1, 0, 0);
-            dpdv = V3(0, 1, 0);
-        } else {
-            coordinate_system(normalize(ng), &dpdu, &dpdv);
-        }
-    }
-    f.ng = normalize(cross(dpdu, dpdv));  // SurfaceInteraction ctor, intersectable.h:69
-    f.ss = normalize(dpdu);                // BSDF::ss (reflection.cpp:10) and trianglemesh.cpp:100
-    return f;
-}
 
 // Where one mesh lives in the committed scene's device arrays (agpt_scene.h).
 struct UpdateTarget {

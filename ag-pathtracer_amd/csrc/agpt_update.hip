@@ -2,9 +2,11 @@
 // triangle records decide rays, so every operation rounds on its own and divides / square roots are correctly rounded.
 //
 //   k_update_tris    one lane per triangle SLOT (BVH leaf order): the three float4 of tri_verts at the slot, the four float4 of
-//                    tri_shade at the triangle's global id -- flatten_scene's two per-triangle loops, fused.
-//   k_refit_nodes    one lane per node of a list: a leaf grows the +-1e34 box over its slots' vertices (read back from tri_verts,
-//                    which k_update_tris has just written), an interior node takes (left, right) of its child pair.  Launched
+//                    tri_shade at the triangle's global id -- flatten_scene's two per-triangle loops, fused, writing through the
+//                    SHARED packers of agpt_records.h.
+//   k_refit_nodes    one lane per node of a list: a leaf grows the empty box over its slots' triangle boxes (vertices read back from
+//                    tri_verts, which k_update_tris has just written), an interior node takes (left, right) of its child pair -- the
+//                    SHARED arithmetic of agpt_bvh_arith.h, stored through the record writers of agpt_records.h.  Launched
 //                    once for all leaves, then once per level of interior nodes from the deepest up, on one stream: a launch sees
 //                    what the launches before it wrote, and the output does not depend on the launch shape.
 //   k_check_finite   one lane per coordinate of the position array: one flag word set if any is Inf or NaN (the rule of the host
@@ -18,6 +20,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "agpt_bvh_arith.h"
 
 namespace agpt {
 
@@ -61,9 +65,7 @@ __global__ __launch_bounds__(kBlock) void k_update_tris(TriArgs a) {
         uv1 = a.uv[ix[5]];
         uv2 = a.uv[ix[8]];
     } else {
-        uv0.x = 0; uv0.y = 0;
-        uv1.x = 1; uv1.y = 0;
-        uv2.x = 1; uv2.y = 1;
+        default_uv(uv0, uv1, uv2);
     }
     const TriFrame f = triangle_frame(v0, v1, v2_, uv0, uv1, uv2);
     v3 n0 = V3s(0), n1 = V3s(0), n2 = V3s(0);
@@ -73,15 +75,8 @@ __global__ __launch_bounds__(kBlock) void k_update_tris(TriArgs a) {
         n2 = load3(a.normals, ix[7]);
     }
     const uint32_t gid = a.tri_base + (uint32_t)t;
-    float4* q = a.tri_shade + 4 * (size_t)gid;
-    q[0] = make_float4(f.ng.x, f.ng.y, f.ng.z, f.ss.x);
-    q[1] = make_float4(f.ss.y, f.ss.z, n0.x, n0.y);
-    q[2] = make_float4(n0.z, n1.x, n1.y, n1.z);
-    q[3] = make_float4(n2.x, n2.y, n2.z, __uint_as_float(a.prim_id));
-    float4* p = a.tri_verts + 3 * (size_t)(a.tri_base + (uint32_t)s);
-    p[0] = make_float4(v0.x, v0.y, v0.z, __uint_as_float(gid));
-    p[1] = make_float4(v1.x, v1.y, v1.z, __uint_as_float(f.reject));
-    p[2] = make_float4(v2_.x, v2_.y, v2_.z, 0.f);
+    pack_tri_shade(a.tri_shade + 4 * (size_t)gid, f, n0, n1, n2, a.prim_id);
+    pack_tri_verts(a.tri_verts + 3 * (size_t)(a.tri_base + (uint32_t)s), v0, v1, v2_, gid, f.reject);
 }
 
 struct RefitArgs {
@@ -103,63 +98,31 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(RefitArgs a) {
     if (k >= a.n) return;
     const int i = a.list[k];
     const int2 fc = a.topo[i];
-    float lo[3], hi[3];
+    Box bounds;
     if (fc.y > 0) {
-        // Builder::choose_split's `bounds`: Box() grown over the primitives' boxes, each Box() grown over its three vertices
-        for (int c = 0; c < 3; c++) {
-            lo[c] = 1e34f;
-            hi[c] = -1e34f;
-        }
+        // Builder::choose_split's `bounds`: the box of every primitive of the leaf, in slot order
         const float4* tv = a.tri_verts + 3 * (size_t)(a.tri_base + (uint32_t)fc.x);
         for (int s = 0; s < fc.y; s++) {
-            float plo[3] = {1e34f, 1e34f, 1e34f}, phi[3] = {-1e34f, -1e34f, -1e34f};
-            for (int v = 0; v < 3; v++) {
-                const float4 q = tv[3 * (size_t)s + v];
-                plo[0] = tminf(plo[0], q.x);
-                plo[1] = tminf(plo[1], q.y);
-                plo[2] = tminf(plo[2], q.z);
-                phi[0] = tmaxf(phi[0], q.x);
-                phi[1] = tmaxf(phi[1], q.y);
-                phi[2] = tmaxf(phi[2], q.z);
-            }
-            for (int c = 0; c < 3; c++) {
-                lo[c] = tminf(lo[c], plo[c]);
-                hi[c] = tmaxf(hi[c], phi[c]);
-            }
+            const float4 q0 = tv[3 * (size_t)s], q1 = tv[3 * (size_t)s + 1], q2 = tv[3 * (size_t)s + 2];
+            bounds.grow(tri_box(V3(q0.x, q0.y, q0.z), V3(q1.x, q1.y, q1.z), V3(q2.x, q2.y, q2.z)));
         }
     } else {
         const float4 llo = a.bounds[2 * (size_t)fc.x], lhi = a.bounds[2 * (size_t)fc.x + 1];
         const float4 rlo = a.bounds[2 * (size_t)fc.x + 2], rhi = a.bounds[2 * (size_t)fc.x + 3];
-        lo[0] = tminf(llo.x, rlo.x);
-        lo[1] = tminf(llo.y, rlo.y);
-        lo[2] = tminf(llo.z, rlo.z);
-        hi[0] = tmaxf(lhi.x, rhi.x);
-        hi[1] = tmaxf(lhi.y, rhi.y);
-        hi[2] = tmaxf(lhi.z, rhi.z);
+        pair_union(&llo.x, &lhi.x, &rlo.x, &rhi.x, bounds.lo, bounds.hi);
     }
+    const float *lo = bounds.lo, *hi = bounds.hi;
     a.bounds[2 * (size_t)i] = make_float4(lo[0], lo[1], lo[2], 0.f);
     a.bounds[2 * (size_t)i + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
-    // the pair record of agpt_scene.h: [0] lx0 rx0 ly0 ry0  [1] lz0 rz0 lx1 rx1  [2] ly1 ry1 lz1 rz1  [3] untouched
     const size_t g = (size_t)a.node_base + (size_t)i;
-    float* rec = a.nodes + 16 * (g >> 1);
-    const size_t side = g & 1;
-    for (int c = 0; c < 3; c++) {
-        rec[2 * c + side] = lo[c];
-        rec[6 + 2 * c + side] = hi[c];
-    }
-    if (i == 0) {
+    pair_record_set_box(a.nodes + 16 * (g >> 1), g & 1, lo, hi);   // (the encodings of the record stay)
+    if (i == 0) {   // the copies of the root box
         for (int c = 0; c < 3; c++) {
             a.prim->root_bmin[c] = lo[c];
             a.prim->root_bmax[c] = hi[c];
-            if (a.rootpair) {
-                a.rootpair[2 * c] = a.rootpair[2 * c + 1] = lo[c];
-                a.rootpair[6 + 2 * c] = a.rootpair[6 + 2 * c + 1] = hi[c];
-            }
-            if (a.prefilter) {
-                a.prefilter[c] = lo[c];
-                a.prefilter[4 + c] = hi[c];
-            }
         }
+        if (a.rootpair) rootpair_record_set_box(a.rootpair, lo, hi);
+        if (a.prefilter) prefilter_record_set_box(a.prefilter, lo, hi);
     }
 }
 

@@ -83,5 +83,25 @@ def random_rays(desc, n, seed=1, tmax=None):
     return rays
 
 
+def signed_zero_grid(n):
+    """(verts, indices) of an n x n grid of quads (2 n^2 triangles) in the plane y = 0 whose zeros carry both signs: y is -0 at every
+    third vertex and +0 elsewhere, x = 0 is -0.  The two triangles of a quad share their box, hence their centroid, so every leaf of
+    the grid's BVH holds two of them whatever max_prims_in_node is."""
+    g = np.linspace(-1, 1, n + 1).astype(np.float32)
+    X, Z = np.meshgrid(g, g, indexing="ij")
+    Y = np.where((np.arange(X.size) % 3).reshape(X.shape) == 0, np.float32(-0.0), np.float32(0.0))
+    X = np.where(X == 0, np.float32(-0.0), X)
+    verts = np.stack([X, Y, Z], -1).reshape(-1, 3).astype(np.float32)
+    tri = []
+    for i in range(n):
+        for j in range(n):
+            a, b, c, d = i * (n + 1) + j, (i + 1) * (n + 1) + j, i * (n + 1) + j + 1, (i + 1) * (n + 1) + j + 1
+            tri += [a, b, c, c, b, d]
+    idx = np.zeros((len(tri), 3), np.int32)
+    idx[:, 0] = tri
+    assert np.signbit(verts).any()
+    return verts, idx
+
+
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)

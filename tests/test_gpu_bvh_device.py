@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import gpu_context, oracle_scene, random_rays
+from helpers import gpu_context, oracle_scene, random_rays, signed_zero_grid
 from oracle import binding as ob
 
 pytestmark = pytest.mark.gpu
@@ -94,19 +94,7 @@ def test_equal_centroids_in_two_triangle_nodes():
 
 
 def test_signed_zero_grid():
-    n = 60
-    g = np.linspace(-1, 1, n + 1).astype(np.float32)
-    X, Z = np.meshgrid(g, g, indexing="ij")
-    Y = np.where((np.arange(X.size) % 3).reshape(X.shape) == 0, np.float32(-0.0), np.float32(0.0))
-    X = np.where(X == 0, np.float32(-0.0), X)
-    verts = np.stack([X, Y, Z], -1).reshape(-1, 3).astype(np.float32)
-    tri = []
-    for i in range(n):
-        for j in range(n):
-            a, b, c, d = i * (n + 1) + j, (i + 1) * (n + 1) + j, i * (n + 1) + j + 1, (i + 1) * (n + 1) + j + 1
-            tri += [a, b, c, c, b, d]
-    idx = np.zeros((len(tri), 3), np.int32)
-    idx[:, 0] = tri
+    verts, idx = signed_zero_grid(60)
     assert np.signbit(verts).any()
     for mp in (1, 2):
         check_same(verts, idx, mp)

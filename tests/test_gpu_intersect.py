@@ -110,6 +110,34 @@ def test_more_than_64_primitives_go_through_the_top_level_tree():
     assert hits > 20000
 
 
+def big_leaf_mesh(clusters=3, copies=9):
+    """`clusters` stacks of `copies` triangles that share their box, hence their centroid: each stack is one leaf of more than 7
+    primitives, which the node encoding keeps in the side table (agpt_scene.h: AGPT_ENC_BIGLEAF | k, bigleaves[2k..])."""
+    tris = []
+    for c in range(clusters):
+        for k in range(copies):   # the two diagonals' triangles of one quad, alternating
+            quad = np.float32([[0, 0, 0], [1, 0, 0], [0, 1, 0]] if k % 2 == 0 else [[1, 1, 0], [0, 1, 0], [1, 0, 0]])
+            tris.append(quad + np.float32([3 * c, 0, 0]))
+    v = np.concatenate(tris).astype(np.float32)
+    idx = np.zeros((len(v), 3), np.int32)
+    idx[:, 0] = np.arange(len(v))
+    return v, idx
+
+
+def test_every_big_leaf_of_a_mesh_is_found_through_the_side_table():
+    v, idx = big_leaf_mesh()
+    nodes, _, _ = ag.bvh_build(v, idx, 1)
+    assert np.count_nonzero(nodes["count"] > 7) == 3
+    d = ag.SceneDesc("big-leaves")
+    d.add_mesh(v, None, None, idx, d.add_material(ag.MAT_DIFFUSE_ONLY, [.5, .5, .5]), 1)
+    rng = np.random.RandomState(21)
+    rays = np.zeros(2000, ag.RAY_DTYPE)
+    rays["o"] = rng.uniform([-1, -1, 1], [8, 2, 3], (2000, 3)) * np.where(np.arange(2000) % 2, -1, 1)[:, None] ** [0, 0, 1]
+    rays["d"] = rng.uniform([-.5, -.5, 0], [7.5, 1.5, 0], (2000, 3)) - rays["o"]
+    rays["tmax"] = np.float32(3.402823466e+38)
+    assert check_closest(d, rays) > 300
+
+
 def test_generic_kernel_forced(monkeypatch):
     """The generic (reference-order, instrumentable) kernel and the production kernel give identical records."""
     desc = ag.scenes.scene_c3(scale=0.05)

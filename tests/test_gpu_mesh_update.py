@@ -12,7 +12,7 @@ import pytest
 import ag_pathtracer_amd as ag
 import bvh_refit_model as model
 import mesh_update_cases as cases
-from helpers import bits, gpu_context, gpu_scene, oracle_scene, random_rays
+from helpers import bits, gpu_context, gpu_scene, oracle_scene, random_rays, signed_zero_grid
 from oracle import binding as ob
 
 pytestmark = pytest.mark.gpu
@@ -171,6 +171,45 @@ def test_refit_under_a_general_deformation_equals_the_model_and_the_host_flatten
     assert render(a, 1)[0].tobytes() == oracle_render(0, 1.0)[1].tobytes()
     a.close()
     b.close()
+
+
+@pytest.mark.parametrize("mpn", [1, 4])
+def test_refit_of_the_signed_zero_grid_equals_a_fresh_commit(mpn):
+    """The tie rule of the shared box (tminf / tmaxf keep the later of equal operands: +0 against -0) through the device refit: the
+    same arrays, then every coordinate negated and negated back, must leave the tree and a closest-hit batch a fresh commit's."""
+    v, idx = signed_zero_grid(12)   # 288 triangles, two per leaf
+    d = ag.SceneDesc("signed-zero-grid")
+    d.add_mesh(v, None, None, idx, d.add_material(ag.MAT_DIFFUSE_ONLY, [.7, .7, .7]), mpn)
+    d.add_uniform_infinite_light([.4, .45, .5])
+    d.set_camera([0, 2, -4], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
+    rng = np.random.RandomState(12)
+    rays = np.zeros(384, ag.RAY_DTYPE)
+    o = rng.uniform(-1.2, 1.2, (384, 3)).astype(F)
+    o[:, 1] = np.where(np.arange(384) % 2 == 0, F(2), F(-2))
+    target = v[rng.randint(len(v), size=384)].copy()           # exact vertices: shared edges and corners, the x = -0 line
+    target[:128] += rng.normal(0, 0.05, (128, 3)).astype(F)
+    o[256:, 0], o[256:, 2] = target[256:, 0], target[256:, 2]  # straight down / up onto a vertex: zero direction components
+    rays["o"], rays["d"], rays["tmax"] = o, target - o, F(3.402823466e+38)
+    fresh, g = gpu_scene(d), gpu_scene(d)
+    nodes, order = fresh.bvh(0)
+    used = np.arange(len(nodes)) != 1
+    assert (nodes["count"][used] > 1).any() and (np.signbit(nodes["bmin"][used]) & (nodes["bmin"][used] == 0)).any()
+    hits, _ = fresh.Intersect(rays)
+    assert np.count_nonzero(hits["hit"]) > 100
+
+    def same_as_fresh():
+        got_nodes, got_order = g.bvh(0)
+        for f in ("bmin", "bmax"):
+            assert np.array_equal(bits(got_nodes[f][used]), bits(nodes[f][used]))
+        assert got_nodes.tobytes() == nodes.tobytes() and got_order.tobytes() == order.tobytes()
+        assert g.Intersect(rays)[0].tobytes() == hits.tobytes()
+    g.update_mesh(0, v, None, "refit")
+    same_as_fresh()
+    g.update_mesh(0, -v, None, "refit")
+    g.update_mesh(0, -(-v), None, "refit")
+    same_as_fresh()
+    fresh.close()
+    g.close()
 
 
 def test_refit_still_finds_the_geometry():

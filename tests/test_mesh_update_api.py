@@ -11,6 +11,7 @@ import pytest
 import ag_pathtracer_amd as ag
 import bvh_refit_model as model
 import mesh_update_cases as cases
+from helpers import bits, signed_zero_grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "agpt.h")).read()
@@ -68,6 +69,24 @@ def test_refit_with_the_build_vertices_returns_the_build(pose, mpn):
     used = np.arange(len(nodes)) != 1   # (slot 1 is the unused one: nobody writes it)
     scrubbed["bmin"][used], scrubbed["bmax"][used] = 7.0, -7.0
     assert ag.bvh_refit(v, idx, order, scrubbed).tobytes() == nodes.tobytes()
+
+
+@pytest.mark.parametrize("mpn", [1, 4])
+def test_refit_of_the_signed_zero_grid_returns_the_build_bit_for_bit(mpn):
+    """The tie rule of the shared box: tminf / tmaxf keep the later of equal operands, so whether a bound is +0 or -0 depends on the
+    order "box per primitive, then union over the leaf's slots" -- the refit must reproduce the builder's signs."""
+    v, idx = signed_zero_grid(12)   # 288 triangles
+    nodes, order, _ = ag.bvh_build(v, idx, mpn)
+    used = np.arange(len(nodes)) != 1
+    assert (nodes["count"][used] > 1).any()   # multi-slot leaves
+    for f in ("bmin", "bmax"):   # zeros of both signs among the bounds
+        zero = nodes[f][used] == 0
+        assert (zero & np.signbit(nodes[f][used])).any() and (zero & ~np.signbit(nodes[f][used])).any()
+    scrubbed = nodes.copy()
+    scrubbed["bmin"][used], scrubbed["bmax"][used] = 7.0, -7.0
+    got = ag.bvh_refit(v, idx, order, scrubbed)
+    assert np.array_equal(bits(got["bmin"]), bits(nodes["bmin"])) and np.array_equal(bits(got["bmax"]), bits(nodes["bmax"]))
+    assert np.array_equal(got["first"], nodes["first"]) and np.array_equal(got["count"], nodes["count"])
 
 
 @pytest.mark.parametrize("pose,mpn", MESHES)
