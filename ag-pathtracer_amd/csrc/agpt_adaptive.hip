@@ -6,7 +6,8 @@
 // A pixel's samples use the streams of agpt_render (sample_seed(pixel, W*H, sample, seed_base)) and are added in sample order with
 // k_accumulate's arithmetic, so a pixel that holds n samples is bit-identical to agpt_render's pixel at spp = n.  The count lives in
 // accum.w, the luminance second moment in moment2 (one float per pixel, indexed like accum).  Compiled with the library's common
-// flags (-ffp-contract=off, no fast math): k_generate_list must compute the camera rays of k_generate bit for bit.
+// flags (-ffp-contract=off, no fast math): k_generate_list computes the camera rays of k_generate bit for bit (one camera_sample_ray,
+// agpt_wavefront.h, under the same flags).
 #include <hip/hip_runtime.h>
 
 #include "agpt_adaptive.h"
@@ -124,7 +125,7 @@ k_adaptive_compact(const uint32_t* __restrict__ masks, const uint32_t* __restric
 }
 
 // k_generate over the listed pixels: path id ((s / G) * na + a) * G + s % G for sample s of listed pixel a (G = sample_group(S)),
-// sample index n + s with n = the pixel's count.  The body from the jitter on is k_generate's (agpt_kernels.h).
+// sample index n + s with n = the pixel's count; from the seed on it is k_generate (agpt_kernels.h), through the same two functions.
 __global__ void __launch_bounds__(AGPT_BLOCK)
 k_generate_list(DevScene sc, RenderConsts rc, const uint32_t* __restrict__ list, uint32_t a0, uint32_t na, const float4* __restrict__ accum,
                 PathBuffers pb, Queues q) {
@@ -144,41 +145,12 @@ k_generate_list(DevScene sc, RenderConsts rc, const uint32_t* __restrict__ list,
     float px = x + rng_float(rng);
     float py = y + rng_float(rng);
     float s = px / rc.W, t = py / rc.H;
-    const DevCamera& c = sc.cam;
-    v3 rd = V3s(0.f);
-    if (c.lens_radius > 0.f) {
-        for (;;) {
-            float a = -1.f + (1.f - -1.f) * rng_float(rng);
-            float b = -1.f + (1.f - -1.f) * rng_float(rng);
-            v3 pd = V3(a, b, 0);
-            if (sqrlen(pd) >= 1) continue;
-            rd = c.lens_radius * pd;
-            break;
-        }
-    }
-    v3 offset = c.u * rd.x + c.v * rd.y;
-    v3 pixel = c.lower_left_corner + s * c.horizontal + t * c.vertical;
-    v3 O = c.origin + offset;
-    v3 D = normalize(pixel - c.origin - offset);
-    float4 o4, d4, b4, l4;
-    o4.x = O.x; o4.y = O.y; o4.z = O.z; o4.w = AGPT_FLT_MAX;
-    d4.x = D.x; d4.y = D.y; d4.z = D.z;
-    d4.w = rc.max_depth > 0 ? 2.f : 0.f;   // (as in k_generate)
-    b4.x = 1.f; b4.y = 1.f; b4.z = 1.f; b4.w = __uint_as_float(0u);
-    l4.x = 0.f; l4.y = 0.f; l4.z = 0.f; l4.w = __uint_as_float(rng);
-    pb.ext_o[i] = o4;
-    pb.ext_d[i] = d4;
-    pb.beta4[i] = b4;
-    pb.L4[i] = l4;
-    q.ext[i] = i;
-    if (i == 0) {
-        QCOUNT(q, 0) = total;
-        QCOUNT(q, 1) = 0;
-        QCOUNT(q, 2) = 0;
-    }
+    v3 O, D;
+    camera_sample_ray(sc.cam, s, t, rng, O, D);
+    start_path(pb, q, i, total, O, D, AGPT_FLT_MAX, rng, rc.max_depth);
 }
 
-// k_accumulate over the listed pixels (same rgb additions in sample order, same NaN / inf reject), plus the luminance second
+// k_accumulate over the listed pixels (same rgb additions in sample order, film_sample's NaN / inf reject), plus the luminance second
 // moment moment2 += Y * Y and the count accum.w += S.  Reads finished paths: agpt_render_adaptive runs agpt::launch_finish_paths
 // (k_resolve_pending, agpt_shade_kernels.h) over the batch first, which adds an ended path's pending light sample to L4
 __global__ void __launch_bounds__(AGPT_BLOCK)
@@ -196,11 +168,9 @@ k_accumulate_list(RenderConsts rc, const uint32_t* __restrict__ list, uint32_t a
     const uint32_t G = sample_group(rc.S);
     for (int s = 0; s < rc.S; s++) {
         const float4 l4 = pb.L4[((size_t)((uint32_t)s / G) * na + i) * G + (uint32_t)s % G];
-        v3 clr = V3(l4.x, l4.y, l4.z);
-        if (isnan(clr.x) || isnan(clr.y) || isnan(clr.z) || isinf(luminance(clr))) {
-            clr = V3s(0.f);
-            bad++;
-        }
+        const FilmSample fs = film_sample(V3(l4.x, l4.y, l4.z), bad);
+        const v3 clr = fs.clr;
+        bad = fs.bad;
         a.x += clr.x;
         a.y += clr.y;
         a.z += clr.z;
@@ -213,7 +183,7 @@ k_accumulate_list(RenderConsts rc, const uint32_t* __restrict__ list, uint32_t a
     if (bad) atomicAdd(&counters->outliers, (unsigned long long)bad);  // outliers are rare
 }
 
-// k_resolve (Accumulator::CopyToSurface, myapp.h:34-41) with each pixel's own count accum.w; a pixel without samples resolves to 0
+// k_resolve (resolve_word) with each pixel's own count accum.w; a pixel without samples resolves to 0
 __global__ void k_resolve_counts(const float4* __restrict__ accum, int n, uint32_t* __restrict__ out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -222,18 +192,10 @@ __global__ void k_resolve_counts(const float4* __restrict__ accum, int n, uint32
         out[i] = 0u;
         return;
     }
-    float e = 1 / 2.2f;
-    float inv = a.w;
-    float r = powf(a.x / inv, e), g = powf(a.y / inv, e), b = powf(a.z / inv, e);
-    int ri = (int)(256 * tclampf(r, 0.0f, 0.999f));
-    int gi = (int)(256 * tclampf(g, 0.0f, 0.999f));
-    int bi = (int)(256 * tclampf(b, 0.0f, 0.999f));
-    out[i] = (uint32_t)((ri << 16) + (gi << 8) + bi);
+    out[i] = resolve_word(a, a.w);
 }
 
 namespace agpt {
-
-static inline dim3 blocks_for(uint64_t n) { return dim3((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)); }
 
 void launch_adaptive_select(hipStream_t stream, const RenderConsts& rc, const AdaptiveConsts& ac, const float4* accum, const float* moment2,
                             uint32_t* masks, uint32_t* block_counts, uint32_t* words) {
@@ -247,15 +209,15 @@ void launch_adaptive_compact(hipStream_t stream, uint32_t np, const uint32_t* ma
 }
 void launch_generate_list(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const uint32_t* list, uint32_t a0, uint32_t na,
                           const float4* accum, const PathBuffers& pb, const Queues& q) {
-    hipLaunchKernelGGL(k_generate_list, blocks_for((uint64_t)na * (uint64_t)rc.S), dim3(AGPT_BLOCK), 0, stream, sc, rc, list, a0, na, accum,
+    hipLaunchKernelGGL(k_generate_list, agpt_blocks((uint64_t)na * (uint64_t)rc.S), dim3(AGPT_BLOCK), 0, stream, sc, rc, list, a0, na, accum,
                        pb, q);
 }
 void launch_accumulate_list(hipStream_t stream, const RenderConsts& rc, const uint32_t* list, uint32_t a0, uint32_t na, const PathBuffers& pb,
                             float4* accum, float* moment2, DevCounters* counters) {
-    hipLaunchKernelGGL(k_accumulate_list, blocks_for(na), dim3(AGPT_BLOCK), 0, stream, rc, list, a0, na, pb, accum, moment2, counters);
+    hipLaunchKernelGGL(k_accumulate_list, agpt_blocks(na), dim3(AGPT_BLOCK), 0, stream, rc, list, a0, na, pb, accum, moment2, counters);
 }
 void launch_resolve_counts(hipStream_t stream, const float4* accum, int n, uint32_t* out) {
-    hipLaunchKernelGGL(k_resolve_counts, blocks_for((uint64_t)n), dim3(AGPT_BLOCK), 0, stream, accum, n, out);
+    hipLaunchKernelGGL(k_resolve_counts, agpt_blocks((uint64_t)n), dim3(AGPT_BLOCK), 0, stream, accum, n, out);
 }
 
 }  // namespace agpt

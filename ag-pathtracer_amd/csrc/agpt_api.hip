@@ -238,7 +238,7 @@ struct TraceLaunch {
     const uint32_t* count_ptr;
     uint32_t count_imm;
     uint32_t* work_head;         // the launch's work-queue frontiers in agpt_ctx::work, zeroed by the caller
-    const float4 *ro, *rd;
+    float4 *ro, *rd;             // (written only by a re-casting launch)
     DevHit* hits;
     uint32_t* occ;
     int count;                   // see use_fast_trace
@@ -252,11 +252,10 @@ static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch
     const dim3 block(AGPT_BLOCK), g(fast_grid(c));
     const int refill = MODE == 0 ? c->refill : c->refill_any;
     if (sc.n_prims <= 64) {
-        float4* ro_w = MODE == 0 && t.recast ? const_cast<float4*>(t.ro) : nullptr;
-        float4* rd_w = MODE == 0 && t.recast ? const_cast<float4*>(t.rd) : nullptr;
         hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, false, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
-                           t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, refill, 0u, c->spill.p,
-                           (const unsigned long long*)nullptr, (const uint32_t*)nullptr, ro_w, rd_w, (const float4*)c->beta4.p, c->L4.p);
+                           t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p,
+                           refill, 0u, c->spill.p, (const unsigned long long*)nullptr, (const uint32_t*)nullptr, MODE == 0 && t.recast,
+                           (const float4*)c->beta4.p, c->L4.p);
         return;
     }
     // more than 64 primitives: the top-level tree gives every ray its candidates (one word per chunk of 64 primitives), then
@@ -270,8 +269,8 @@ static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch
                        c->cand_mask.p, c->cand_chunks.p, stride);
     hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, true, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
                        t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, refill, stride, c->spill.p,
-                       (const unsigned long long*)c->cand_mask.p, (const uint32_t*)c->cand_chunks.p, (float4*)nullptr, (float4*)nullptr,
-                       (const float4*)nullptr, (float4*)nullptr);
+                       (const unsigned long long*)c->cand_mask.p, (const uint32_t*)c->cand_chunks.p, false, (const float4*)nullptr,
+                       (float4*)nullptr);
 }
 
 template <bool ANY, bool COUNT, int DEPTH>
@@ -1530,15 +1529,15 @@ int agpt_intersect_device(agpt_scene* s, const agpt_ray* d_rays, int n, agpt_hit
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
     HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
-    int blocks = (n + AGPT_BLOCK - 1) / AGPT_BLOCK;
-    hipLaunchKernelGGL(k_prepare_rays, dim3(blocks), dim3(AGPT_BLOCK), 0, c->stream, d_rays, n, c->ext_o.p, c->ext_d.p);
+    const dim3 blocks = agpt_blocks((uint64_t)n);
+    hipLaunchKernelGGL(k_prepare_rays, blocks, dim3(AGPT_BLOCK), 0, c->stream, d_rays, n, c->ext_o.p, c->ext_d.p);
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
     // stats requested -> the instrumented reference-order kernel (work counters); AGPT_INTERSECT_TIMING=1 (developer knob)
     // keeps the production kernel so that stats->trace_ms times it
     const int instrumented = (stats != nullptr && !getenv("AGPT_INTERSECT_TIMING")) ? 1 : 0;
     trace_rays(c, s->dev, (uint32_t)n, any_hit != 0, instrumented);
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    hipLaunchKernelGGL(k_export_hits, dim3(blocks), dim3(AGPT_BLOCK), 0, c->stream, s->dev, c->hit.p, c->occluded.p, n, any_hit,
+    hipLaunchKernelGGL(k_export_hits, blocks, dim3(AGPT_BLOCK), 0, c->stream, s->dev, c->hit.p, c->occluded.p, n, any_hit,
                        d_out);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());
@@ -1655,7 +1654,7 @@ int agpt_render(agpt_scene* s, const agpt_render_params* rp, float* accum_dev, a
         rcn.s0 = s0;
         rcn.S = std::min(S, rp->spp_begin + rp->spp_count - s0);
         const uint32_t total = NP * (uint32_t)rcn.S;
-        hipLaunchKernelGGL(k_generate, dim3((total + AGPT_BLOCK - 1) / AGPT_BLOCK), dim3(AGPT_BLOCK), 0, c->stream, s->dev, rcn, run.pb,
+        hipLaunchKernelGGL(k_generate, agpt_blocks(total), dim3(AGPT_BLOCK), 0, c->stream, s->dev, rcn, run.pb,
                            run.q[0]);
         if ((rc = run_wavefront(c, s, rcn, run))) return rc;
         agpt::launch_accumulate(c->stream, run.shade.fast, s->dev, rcn, run.pb, (float4*)accum_dev, c->counters.p);
@@ -1912,7 +1911,7 @@ int agpt_li_batch(agpt_scene* s, const agpt_ray* rays, const uint32_t* rng_state
     if ((rc = begin_wavefront(c, s, 0, false, run))) return rc;
     RenderConsts rcn{};
     set_wavefront_consts(rcn, run, max_depth, false);
-    const dim3 grid((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)), block(AGPT_BLOCK);
+    const dim3 grid = agpt_blocks((uint64_t)n), block(AGPT_BLOCK);
     hipLaunchKernelGGL(k_generate_li, grid, block, 0, c->stream, (const agpt_ray*)d_rays.p, (const uint32_t*)d_rng.p, (uint32_t)n, run.pb,
                        run.q[0], max_depth);
     if ((rc = run_wavefront(c, s, rcn, run))) return rc;
@@ -1929,7 +1928,7 @@ int agpt_resolve(agpt_ctx* c, const float* accum_dev, int n_pixels, int samples,
     HIP_TRY(hipSetDevice(c->device));
     DevBuf<uint32_t> d;
     HIP_TRY(d.alloc((size_t)n_pixels));
-    hipLaunchKernelGGL(k_resolve, dim3((n_pixels + 255) / 256), dim3(256), 0, c->stream, (const float4*)accum_dev, n_pixels, samples, d.p);
+    hipLaunchKernelGGL(k_resolve, agpt_blocks((uint64_t)n_pixels), dim3(AGPT_BLOCK), 0, c->stream, (const float4*)accum_dev, n_pixels, samples, d.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_rgb, d.p, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2197,7 +2196,7 @@ int agpt_deinterleave_tiles(agpt_ctx* c, const float* compact_dev, int width, in
     const int rows = interleave_rows(height, block_rows, world, rank);
     if (!rows) return AGPT_OK;
     const size_t n = (size_t)rows * (size_t)width;
-    hipLaunchKernelGGL(k_deinterleave, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)compact_dev,
+    hipLaunchKernelGGL(k_deinterleave, agpt_blocks(n), dim3(AGPT_BLOCK), 0, c->stream, (const float4*)compact_dev,
                        (float4*)full_accum_dev, width, height, block_rows, world, rank, rows);
     HIP_TRY(hipGetLastError());
     return AGPT_OK;

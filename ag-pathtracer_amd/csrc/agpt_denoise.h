@@ -23,11 +23,8 @@ struct DenoiseConsts {
 __device__ __forceinline__ void feature_ray(const DevCamera& c, int x, int y, int32_t W, int32_t H, v3& O, v3& D) {
     const float px = x + 0.5f, py = y + 0.5f;
     const float s = px / W, t = py / H;
-    const v3 rd = V3s(0.f);
-    const v3 offset = c.u * rd.x + c.v * rd.y;
-    const v3 pixel = c.lower_left_corner + s * c.horizontal + t * c.vertical;
-    O = c.origin + offset;
-    D = normalize(normalize(pixel - c.origin - offset));
+    camera_ray(c, s, t, 0.f, 0.f, O, D);
+    D = normalize(D);
 }
 
 namespace agpt {

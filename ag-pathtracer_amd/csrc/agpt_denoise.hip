@@ -256,10 +256,8 @@ k_denoise_pass(DenoiseConsts dc, const float4* __restrict__ state_in, const floa
 
 namespace agpt {
 
-static inline dim3 blocks_for(uint64_t n) { return dim3((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)); }
-
 void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, float4* ray_o, float4* ray_d) {
-    hipLaunchKernelGGL(k_feature_rays, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc.cam, rc, ray_o, ray_d);
+    hipLaunchKernelGGL(k_feature_rays, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc.cam, rc, ray_o, ray_d);
 }
 void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, const RenderConsts& rc, const float4* colors,
                      const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth) {
@@ -271,11 +269,11 @@ void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, c
     case SHADE_NORMAL: kernel = k_features_normal; break;
     default: break;
     }
-    hipLaunchKernelGGL(kernel, blocks_for(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+    hipLaunchKernelGGL(kernel, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
 void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,
                             float4* state) {
-    hipLaunchKernelGGL(k_denoise_prepare, blocks_for((uint64_t)dc.W * (uint64_t)dc.H), dim3(AGPT_BLOCK), 0, stream, dc, accum, moment2, albedo,
+    hipLaunchKernelGGL(k_denoise_prepare, agpt_blocks((uint64_t)dc.W * (uint64_t)dc.H), dim3(AGPT_BLOCK), 0, stream, dc, accum, moment2, albedo,
                        state);
 }
 void launch_denoise_pass(hipStream_t stream, const DenoiseConsts& dc, const float4* state_in, const float4* albedo,

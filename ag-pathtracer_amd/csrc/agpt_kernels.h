@@ -16,7 +16,14 @@
 // trip per iteration).  Path state is SoA float4 in HBM (coalesced 16 B/lane); the per-lane traversal stack lives in LDS
 // (23 entries x 4 B x 256 lanes = 23 KiB/block, deeper entries in an HBM spill column).  A continuation ray that retires on a
 // primitive without a material is re-cast by the closest-hit kernel itself (CUR_RECAST), so a render has max_depth + 3 iterations.
+//
+// Rules that kernels must agree on bit for bit live in one place each: path start, film write-back and launch grid (camera_sample_ray,
+// start_path, film_sample, resolve_word, agpt_blocks) in agpt_wavefront.h; the conservative slab test (conservative_slab) and the hit
+// record (store_hit) in agpt_trace.h.  Still written out more than once, each copy with a note that names the other: the MIS-query decoding
+// (3), the analytic loop (2), the primitive record (2), pop-or-pick_next (2) in k_trace_fast / k_candidates; the counter flush (k_trace, k_trace_fast).
 #pragma once
+
+#include <type_traits>
 
 #include "agpt_shade.h"
 #include "agpt_trace.h"
@@ -56,6 +63,8 @@ k_trace(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restr
                 hits[pid] = h;
         }
     }
+    // (k_trace_fast ends with the same flush, the second copy: its counters go in the order interior, roots, tris, here interior,
+    // tris, roots.  One by-value function for both changed the code of every counting k_trace_fast instantiation, and of this kernel.)
     if (COUNT) {
         for (int off = 32; off > 0; off >>= 1) {
             cnt.interior += __shfl_down(cnt.interior, off);
@@ -120,13 +129,18 @@ k_trace(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restr
 #ifndef AGPT_TRACE_WAVES
 #define AGPT_TRACE_WAVES 1   // minimum waves per SIMD the register allocation of k_trace_fast is held to
 #endif
+// The rays of a launch.  The short-list closest-hit instantiations re-cast a ray in place (CUR_RECAST below): they read and write
+// the rays through one plain pointer each; every other instantiation only reads them, and says so.
+template <int MODE, bool LIST>
+using TraceRays = std::conditional_t<MODE == 0 && !LIST, float4*, const float4* __restrict__>;
+// recast_on (MODE 0, short lists): the rays carry d.w and may be re-cast; path_beta4 / path_L4 are then the paths' state
 template <int MODE, int DEPTH, bool LIST, bool COUNT, bool SPILL, bool PEEK>
 __global__ void __launch_bounds__(AGPT_BLOCK, AGPT_TRACE_WAVES)
 k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
-             uint32_t* __restrict__ work_head, const float4* __restrict__ ray_o, const float4* __restrict__ ray_d,
+             uint32_t* __restrict__ work_head, TraceRays<MODE, LIST> ray_o, TraceRays<MODE, LIST> ray_d,
              DevHit* __restrict__ hits, uint32_t* __restrict__ occluded, DevCounters* __restrict__ counters, int refill,
              uint32_t cand_stride, uint32_t* __restrict__ spill, const unsigned long long* __restrict__ cand_mask,
-             const uint32_t* __restrict__ cand_chunks, float4* ray_o_w, float4* ray_d_w, const float4* path_beta4, float4* path_L4) {
+             const uint32_t* __restrict__ cand_chunks, bool recast_on, const float4* path_beta4, float4* path_L4) {
     constexpr bool ANY = MODE != 0;
     constexpr bool MIS = MODE == 2;
     constexpr int BLOCK = AGPT_BLOCK;
@@ -156,7 +170,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     const int n_prims = LIST ? 0 : sc.n_prims;   // (short lists: the primitive records live in LDS)
     if (PRIM_LDS && (int)threadIdx.x < n_prims) {
         const DevPrim& P = sc.prims[threadIdx.x];
-        float4 a, b;
+        float4 a, b;   // (the record; its kind and operands are formed once more in the !PRIM_LDS branch of state A, which says why)
         if (P.type == AGPT_PRIM_SPHERE) {
             a.x = P.cx; a.y = P.cy; a.z = P.cz; a.w = 1.f;
             b.x = P.r2; b.y = 0.f; b.z = P.material < 0 ? 1.f : 0.f; b.w = 0.f;   // b.z: no material (an emitter's sphere)
@@ -307,6 +321,10 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                 const float4 d = pfc_d;
                 const TraceRay nr = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), coords_ok);
                 unsigned long long skip_bit = 0;
+                // (The decoding of a MIS query is written out three times -- here, at the hand-over below and in k_candidates -- and so
+                // is the analytic loop further down, here and in k_candidates.  As functions of agpt_trace.h (results by reference, by
+                // value in a struct, the test of one primitive alone) each form compiled these kernels to other code: other register
+                // numbers and instruction order at best.)
                 if (MIS) {   // MIS rays carry the sampled light's sphere (primitive index, ~0u = infinite light) in o.w; tmax = inf
                     const uint32_t shape = __float_as_uint(o.w);
                     o.w = AGPT_FLT_MAX;
@@ -318,12 +336,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                         skip_bit = 1ull << shape;
                     }
                 }
-                // t ~ fma(b, R, -RN(O*R)) differs from the exact quotient (b-O)/D by at most 2^-23 |t| + 2^-24 |O*R|
-                // (R = RN(1/D), one rounding of O*R, one of the fma); rejecting only when tmax*(1+2e-6) + 2E < tmin with
-                // E = 2^-22 max|O*R| can therefore only over-accept -- the exact Bounds::Intersect still decides where the
-                // reference runs it.
-                const float nox = -(nr.O.x * nr.R.x), noy = -(nr.O.y * nr.R.y), noz = -(nr.O.z * nr.R.z);
-                const float slack2 = 0x1p-21f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
+                const SlabRay sr = make_slab_ray(nr);
                 // The records come through SCALAR loads (wave-uniform index, constant address space: scene arrays are
                 // read-only for the whole launch, and only loads from that address space are selected as s_load without a
                 // no-clobber proof), so the box coordinates are SGPR operands of the FMAs and the loads of several records
@@ -336,12 +349,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
 #pragma unroll 4
                 for (int j = j0; j < j1; ++j) {   // non-empty meshes: conservative slab test of the root box
                     ConstF* q = pf + 8 * j;   // (bmin.xyz, bit index), (bmax.xyz, -)
-                    float t0x = __builtin_fmaf(q[0], nr.R.x, nox), t1x = __builtin_fmaf(q[4], nr.R.x, nox);
-                    float t0y = __builtin_fmaf(q[1], nr.R.y, noy), t1y = __builtin_fmaf(q[5], nr.R.y, noy);
-                    float t0z = __builtin_fmaf(q[2], nr.R.z, noz), t1z = __builtin_fmaf(q[6], nr.R.z, noz);
-                    float tmin = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fmaxf(fminf(t0z, t1z), 0.f));
-                    float tmax = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), o.w));
-                    const bool h = !(__builtin_fmaf(tmax, 1.000002f, slack2) < tmin);
+                    const bool h = conservative_slab(sr, q[0], q[1], q[2], q[4], q[5], q[6], o.w);
                     m |= (unsigned long long)(h ? 1u : 0u) << __float_as_uint(q[3]);
                 }
                 ConstPrim* pr = (ConstPrim*)sc.prims;
@@ -447,14 +455,14 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
         // ray is a Scene::Intersect call of its own (counted), walks every primitive of the list, and k_shade finds it in
         // ext_o / ext_d.  A re-cast that would need the true-division slab test is left to k_shade: the hit is written after all.
         // (Out here, not in the retire branch of the vote loop, where the same code cost the loop four registers and 1 ms.)
-        if (MODE == 0 && !LIST && __ballot(cur == CUR_RECAST) != 0) {
-            if (cur == CUR_RECAST) {
+        if constexpr (MODE == 0 && !LIST) {
+            if (__ballot(cur == CUR_RECAST) != 0 && cur == CUR_RECAST) {
                 const v3 p = r.O + rayt * r.D;
                 const v3 nO = p + AGPT_EPSILON * r.D;
                 const v3 nD = normalize(r.D);
                 const TraceRay nr = make_trace_ray(nO, nD, coords_ok);
                 if (nr.fast) {
-                    const float kind = ray_d_w[pid].w;
+                    const float kind = ray_d[pid].w;
                     if (kind == 2.f) {
                         // a camera ray (d.w = 2): the vertex first adds the emitter's radiance (integrator.h:139-147, bounces == 0;
                         // nothing of an earlier vertex is pending on it), then re-casts
@@ -469,8 +477,8 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     float4 no4, nd4;
                     no4.x = nO.x; no4.y = nO.y; no4.z = nO.z; no4.w = AGPT_FLT_MAX;
                     nd4.x = nD.x; nd4.y = nD.y; nd4.z = nD.z; nd4.w = kind;
-                    ray_o_w[pid] = no4;
-                    ray_d_w[pid] = nd4;
+                    ray_o[pid] = no4;
+                    ray_d[pid] = nd4;
                     atomicAdd(&counters->closest_rays, 1ull);
                     r = nr;
                     rayt = AGPT_FLT_MAX;
@@ -481,12 +489,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     mask = all_prims;
                     cur = pick_next(mask);
                 } else {
-                    DevHit h;
-                    h.t = rayt;
-                    h.id = hid;
-                    h.b1 = hb1;
-                    h.b2 = hb2;
-                    hits[pid] = h;
+                    store_hit(hits, pid, rayt, hid, hb1, hb2);
                     cur = CUR_IDLE;
                 }
             }
@@ -524,7 +527,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     float4 o = ray_o[pid], d = ray_d[pid];
                     r = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), coords_ok);
                     rayt = o.w;
-                    if (MIS) {
+                    if (MIS) {   // (pump_consume's decoding once more, see there)
                         mis_area = false;
                         mis_skip = -1;
                         mis_reach = true;
@@ -605,6 +608,8 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                         cur = encl;
                     } else if (hr) {
                         cur = encr;
+                    // (Pop the stack or pick_next: written out again at the end of the leaf step below, the second copy.  As one
+                    // lambda -- [&] on sp / cur / mask, by reference or by value -- it changed every k_trace_fast instantiation.)
                     } else if (sp == 0) {
                         cur = pick_next(mask);
                     } else {
@@ -646,7 +651,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     if (ANY && done) {
                         occluded[pid] = MIS ? 0u : 1u;   // MODE 2 writes "ok" (1 = add the BSDF-leg contribution)
                         cur = CUR_IDLE;
-                    } else if (sp == 0) {
+                    } else if (sp == 0) {   // (the interior step's pop or pick_next, the other copy, see there)
                         cur = pick_next(mask);
                     } else {
                         sp--;
@@ -671,23 +676,18 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                         // A closest hit on a primitive without a material (an emitter's sphere), on a ray whose next vertex would
                         // do nothing but re-cast it (d.w = 1, set by k_shade): the lane is parked for the re-cast at the top of the
                         // outer loop instead of retiring.
-                        if (!LIST && ray_o_w && hid != AGPT_HIT_MISS && (hid & AGPT_HIT_SPHERE))
-                            recast = s_prim[2 * (hid & 0x7FFFFFFFu) + 1].z != 0.f && ray_d_w[pid].w != 0.f;
-                        if (!recast) {
-                            DevHit h;
-                            h.t = rayt;
-                            h.id = hid;
-                            h.b1 = hb1;
-                            h.b2 = hb2;
-                            hits[pid] = h;
-                        }
+                        if (!LIST && recast_on && hid != AGPT_HIT_MISS && (hid & AGPT_HIT_SPHERE))
+                            recast = s_prim[2 * (hid & 0x7FFFFFFFu) + 1].z != 0.f && ray_d[pid].w != 0.f;
+                        if (!recast) store_hit(hits, pid, rayt, hid, hb1, hb2);
                     }
                     cur = recast ? CUR_RECAST : CUR_IDLE;
                 } else {
                     const int k = (LIST ? 64 * (int)cchunk : 0) + __ffsll((long long)mask) - 1;   // list index
                     mask &= mask - 1;
                     float4 pa, pb2;
-                    if (!PRIM_LDS) {   // (the short-list instantiation keeps these records in LDS)
+                    // (The long-list instantiation forms the fields it needs of the record staged at the kernel's top, the other copy:
+                    // one function for both, by reference or by value, compiled the short-list instantiations to other code.)
+                    if (!PRIM_LDS) {
                         const DevPrim& P = sc.prims[k];
                         const bool sphere = P.type == AGPT_PRIM_SPHERE;
                         pa.x = P.cx; pa.y = P.cy; pa.z = P.cz; pa.w = sphere ? 1.f : (P.type == AGPT_PRIM_PLANE ? 3.f : 2.f);
@@ -743,7 +743,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
         TCK(atomicAdd(d + 10, tk_refill); atomicAdd(d + 11, tk_vote); atomicAdd(d + 12, tk_bmem); atomicAdd(d + 13, tk_balu);
             atomicAdd(d + 14, tk_c); atomicAdd(d + 15, tk_a); atomicAdd(counters->dbg + 48 + MODE, TCK_NOW() - tk_begin);)
     })
-    if (COUNT) {
+    if (COUNT) {   // (k_trace's flush, the other copy, see there; here in the order interior, roots, tris)
         for (int off = 32; off > 0; off >>= 1) {
             c_int += __shfl_down(c_int, off);
             c_root += __shfl_down(c_root, off);
@@ -795,7 +795,7 @@ k_candidates(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
         const float4 d = ray_d[pid];
         const TraceRay nr = make_trace_ray(V3(o.x, o.y, o.z), V3(d.x, d.y, d.z), coords_ok);
         uint32_t skip = 0xFFFFFFFFu;
-        if (MIS) {   // MIS rays carry the sampled light's sphere (primitive index, ~0u = infinite light) in o.w; tmax = inf
+        if (MIS) {   // k_trace_fast's decoding (pump_consume; why it is a copy is said there): the sampled light's sphere in o.w, tmax = inf
             const uint32_t shape = __float_as_uint(o.w);
             o.w = AGPT_FLT_MAX;
             if (shape != 0xFFFFFFFFu) {
@@ -808,9 +808,7 @@ k_candidates(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
         int n_found = 0;
         bool all = !nr.fast;   // outside the Markstein divide's domain (agpt_trace.h): the conservative form does not hold
         if (!all) {
-            // same conservative form and slack as the short-list prefilter (k_trace_fast: pump_consume)
-            const float nox = -(nr.O.x * nr.R.x), noy = -(nr.O.y * nr.R.y), noz = -(nr.O.z * nr.R.z);
-            const float slack2 = 0x1p-21f * fmaxf(fmaxf(fabsf(nox), fabsf(noy)), fabsf(noz));
+            const SlabRay sr = make_slab_ray(nr);
             uint32_t k = 0;
             const uint32_t k_end = (uint32_t)sc.n_toplevel;
             while (k < k_end) {
@@ -818,12 +816,7 @@ k_candidates(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                 auto h2f = [](uint32_t bits16) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16); };
                 const float lox = h2f(nd.x & 0xFFFFu), loy = h2f(nd.x >> 16), loz = h2f(nd.y & 0xFFFFu);
                 const float hix = h2f(nd.y >> 16), hiy = h2f(nd.z & 0xFFFFu), hiz = h2f(nd.z >> 16);
-                float t0x = __builtin_fmaf(lox, nr.R.x, nox), t1x = __builtin_fmaf(hix, nr.R.x, nox);
-                float t0y = __builtin_fmaf(loy, nr.R.y, noy), t1y = __builtin_fmaf(hiy, nr.R.y, noy);
-                float t0z = __builtin_fmaf(loz, nr.R.z, noz), t1z = __builtin_fmaf(hiz, nr.R.z, noz);
-                float tmin = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fmaxf(fminf(t0z, t1z), 0.f));
-                float tmax = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), o.w));
-                const bool h = !(__builtin_fmaf(tmax, 1.000002f, slack2) < tmin);
+                const bool h = conservative_slab(sr, lox, loy, loz, hix, hiy, hiz, o.w);
                 const uint32_t prim = nd.w >> 16;
                 if (h && prim != 0xFFFFu) {
                     if (n_found < AGPT_CAND_LIST) s_list[n_found][tid] = (uint16_t)prim;
@@ -845,7 +838,7 @@ k_candidates(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     const uint32_t prim = s_list[j][tid];
                     if ((int)(prim >> 6) == c) m |= 1ull << (prim & 63u);
                 }
-                for (unsigned long long am = sc.analytic_masks[c]; am; am &= am - 1) {   // spheres, planes: exact, as in the short-list prefilter
+                for (unsigned long long am = sc.analytic_masks[c]; am; am &= am - 1) {   // spheres, planes: exact -- pump_consume's loop (k_trace_fast; a copy, see there)
                     const int b = __ffsll((long long)am) - 1;
                     const DevPrim& P = sc.prims[64 * c + b];
                     float root;
@@ -901,7 +894,7 @@ __global__ void k_export_hits(const DevScene sc, const DevHit* __restrict__ hits
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// myapp.cpp:165-167: jittered film position -> Camera::GetRay (camera.h:58-64; lens: common.h:65-71)
+// myapp.cpp:165-167: jittered film position -> camera_sample_ray -> start_path (agpt_wavefront.h)
 __global__ void __launch_bounds__(AGPT_BLOCK)
 k_generate(DevScene sc, RenderConsts rc, PathBuffers pb, Queues q) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -918,38 +911,9 @@ k_generate(DevScene sc, RenderConsts rc, PathBuffers pb, Queues q) {
     float px = x + rng_float(rng);
     float py = y + rng_float(rng);
     float s = px / rc.W, t = py / rc.H;
-    const DevCamera& c = sc.cam;
-    v3 rd = V3s(0.f);
-    if (c.lens_radius > 0.f) {
-        for (;;) {
-            float a = -1.f + (1.f - -1.f) * rng_float(rng);
-            float b = -1.f + (1.f - -1.f) * rng_float(rng);
-            v3 pd = V3(a, b, 0);
-            if (sqrlen(pd) >= 1) continue;
-            rd = c.lens_radius * pd;
-            break;
-        }
-    }
-    v3 offset = c.u * rd.x + c.v * rd.y;
-    v3 pixel = c.lower_left_corner + s * c.horizontal + t * c.vertical;
-    v3 O = c.origin + offset;
-    v3 D = normalize(pixel - c.origin - offset);
-    float4 o4, d4, b4, l4;
-    o4.x = O.x; o4.y = O.y; o4.z = O.z; o4.w = AGPT_FLT_MAX;
-    d4.x = D.x; d4.y = D.y; d4.z = D.z;
-    d4.w = rc.max_depth > 0 ? 2.f : 0.f;   // 2: a camera ray that may be re-cast through emitters by the trace kernel (see k_trace_fast)
-    b4.x = 1.f; b4.y = 1.f; b4.z = 1.f; b4.w = __uint_as_float(0u);
-    l4.x = 0.f; l4.y = 0.f; l4.z = 0.f; l4.w = __uint_as_float(rng);
-    pb.ext_o[i] = o4;
-    pb.ext_d[i] = d4;
-    pb.beta4[i] = b4;
-    pb.L4[i] = l4;
-    q.ext[i] = i;
-    if (i == 0) {
-        QCOUNT(q, 0) = total;
-        QCOUNT(q, 1) = 0;
-        QCOUNT(q, 2) = 0;
-    }
+    v3 O, D;
+    camera_sample_ray(sc.cam, s, t, rng, O, D);
+    start_path(pb, q, i, total, O, D, AGPT_FLT_MAX, rng, rc.max_depth);
 }
 
 // agpt_li_batch: Integrator::Li(ray, scene) (integrator.h:28-31) for n caller-supplied rays, each with its own RandomFloat() stream
@@ -960,38 +924,16 @@ k_generate_li(const agpt_ray* __restrict__ rays, const uint32_t* __restrict__ rn
     if (i >= n) return;
     const agpt_ray r = rays[i];
     const v3 d = normalize(V3(r.d[0], r.d[1], r.d[2]));
-    float4 o4, d4, b4, l4;
-    o4.x = r.o[0]; o4.y = r.o[1]; o4.z = r.o[2]; o4.w = r.tmax;
-    d4.x = d.x; d4.y = d.y; d4.z = d.z;
-    d4.w = max_depth > 0 ? 2.f : 0.f;   // (as in k_generate)
-    b4.x = 1.f; b4.y = 1.f; b4.z = 1.f; b4.w = __uint_as_float(0u);
-    l4.x = 0.f; l4.y = 0.f; l4.z = 0.f; l4.w = __uint_as_float(rng_states[i]);
-    pb.ext_o[i] = o4;
-    pb.ext_d[i] = d4;
-    pb.beta4[i] = b4;
-    pb.L4[i] = l4;
-    q.ext[i] = i;
-    if (i == 0) {
-        QCOUNT(q, 0) = n;
-        QCOUNT(q, 1) = 0;
-        QCOUNT(q, 2) = 0;
-    }
+    start_path(pb, q, i, n, V3(r.o[0], r.o[1], r.o[2]), d, r.tmax, rng_states[i], max_depth);
 }
 // (k_export_li, which hands out Li's return value and the stream's end state, finishes the paths: agpt_shade_kernels.h)
 
 // ---------------------------------------------------------------------------------------------------------
-// Accumulator::CopyToSurface (myapp.h:34-41) with lin2rgb / rgb2uint (template/common.h:41-51)
+// Accumulator::CopyToSurface over the accumulator of a uniform render (resolve_word, agpt_wavefront.h)
 __global__ void k_resolve(const float4* __restrict__ accum, int n, int samples, uint32_t* __restrict__ out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float4 a = accum[i];
-    float e = 1 / 2.2f;
-    float inv = (float)samples;
-    float r = powf(a.x / inv, e), g = powf(a.y / inv, e), b = powf(a.z / inv, e);
-    int ri = (int)(256 * tclampf(r, 0.0f, 0.999f));
-    int gi = (int)(256 * tclampf(g, 0.0f, 0.999f));
-    int bi = (int)(256 * tclampf(b, 0.0f, 0.999f));
-    out[i] = (uint32_t)((ri << 16) + (gi << 8) + bi);
+    out[i] = resolve_word(accum[i], (float)samples);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -723,7 +723,7 @@ __device__ __forceinline__ v3 finished_radiance(const DevScene& sc, const Render
 }
 
 #if !AGPT_SHADE_LEVEL   // (no BSDF, no material: every scene runs the plain unit's kernels of its arithmetic)
-// myapp.cpp:169-173 NaN/inf reject + Accumulator::AddSample (myapp.h:17-19): samples are added in sample order.
+// film_sample (agpt_wavefront.h: the NaN / inf reject) + Accumulator::AddSample (myapp.h:17-19): samples are added in sample order.
 // A block owns AGPT_BLOCK / G pixels (G = sample_group: a pixel's samples lie in runs of G consecutive path ids, so the block's runs
 // of one sample group are AGPT_BLOCK consecutive ids).  Per sample group every thread finishes ONE path -- the reads of L4, beta4 and
 // a pending path's operands are coalesced, 64 lanes on 64 neighbouring records -- and parks the sample in LDS; then the first
@@ -749,11 +749,9 @@ AGPT_SHADE_KNAME(k_accumulate)(DevScene sc, RenderConsts rc, PathBuffers pb, flo
     for (uint32_t sg = 0; sg < (uint32_t)rc.S / G; ++sg) {
         if (pf < rc.NP) {
             const uint32_t i = (sg * rc.NP + p0) * G + tid;   // = (sg * NP + pf) * G + tid % G (path ids fit 31 bits: agpt_render's batch limit)
-            v3 clr = finished_radiance(sc, rc, pb, i, pb.beta4[i], pb.L4[i]);
-            if (isnan(clr.x) || isnan(clr.y) || isnan(clr.z) || isinf(luminance(clr))) {
-                clr = V3s(0.f);
-                bad++;
-            }
+            const FilmSample fs = film_sample(finished_radiance(sc, rc, pb, i, pb.beta4[i], pb.L4[i]), bad);
+            const v3 clr = fs.clr;
+            bad = fs.bad;
             float4 c4;
             c4.x = clr.x; c4.y = clr.y; c4.z = clr.z; c4.w = 0.f;
             s_clr[tid] = c4;
@@ -841,17 +839,16 @@ void AGPT_SHADE_KNAME(launch_shade)(hipStream_t stream, int grid, bool lds_table
         hipLaunchKernelGGL((AGPT_SHADE_KNAME(k_shade)<false, false>), g, b, 0, stream, sc, rc, pb, qin, qout, counters, tile_heads);
 }
 #if !AGPT_SHADE_LEVEL
-static inline dim3 finish_blocks(uint64_t n) { return dim3((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)); }
 void AGPT_SHADE_KNAME(finish_accumulate)(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, float4* accum,
                                          DevCounters* counters) {
-    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_accumulate), finish_blocks((uint64_t)rc.NP * sample_group(rc.S))   /* blocks own AGPT_BLOCK / G pixels each */, dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, accum, counters);
+    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_accumulate), agpt_blocks((uint64_t)rc.NP * sample_group(rc.S))   /* blocks own AGPT_BLOCK / G pixels each */, dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, accum, counters);
 }
 void AGPT_SHADE_KNAME(finish_paths)(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n) {
-    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_resolve_pending), finish_blocks(n), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, n);
+    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_resolve_pending), agpt_blocks(n), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, n);
 }
 void AGPT_SHADE_KNAME(finish_export_li)(hipStream_t stream, const DevScene& sc, const RenderConsts& rc, const PathBuffers& pb, uint32_t n,
                                         float* radiance3, uint32_t* rng_out) {
-    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_export_li), finish_blocks(n), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, n, radiance3, rng_out);
+    hipLaunchKernelGGL(AGPT_SHADE_KNAME(k_export_li), agpt_blocks(n), dim3(AGPT_BLOCK), 0, stream, sc, rc, pb, n, radiance3, rng_out);
 }
 #endif
 }  // namespace agpt

@@ -214,6 +214,35 @@ __device__ __forceinline__ bool sphere_test(const DevPrim& P, const TraceRay& r,
     return sphere_test_c(V3(P.cx, P.cy, P.cz), P.r2, r, rayt, root_out);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Ray admission: the conservative slab test of a fast ray (TraceRay::fast) against a box, by which the short-list prefilter
+// (k_trace_fast: pump_consume) and the top-level walk of long lists (k_candidates), agpt_kernels.h, decide what a ray may touch:
+// t ~ fma(b, R, -RN(O*R)) differs from the exact quotient (b-O)/D by at most 2^-23 |t| + 2^-24 |O*R|
+// (R = RN(1/D), one rounding of O*R, one of the fma); rejecting only when tmax*(1+2e-6) + 2E < tmin with
+// E = 2^-22 max|O*R| can therefore only over-accept -- the exact Bounds::Intersect still decides where the
+// reference runs it.
+struct SlabRay { v3 R, NO; float slack2; };   // RN(1/D), -RN(O*R), 2E
+__device__ __forceinline__ SlabRay make_slab_ray(const TraceRay& r) {
+    const v3 NO = V3(-(r.O.x * r.R.x), -(r.O.y * r.R.y), -(r.O.z * r.R.z));
+    return SlabRay{r.R, NO, 0x1p-21f * fmaxf(fmaxf(fabsf(NO.x), fabsf(NO.y)), fabsf(NO.z))};
+}
+// false only if the ray misses the box (lo, hi) within [0, rayt]
+__device__ __forceinline__ bool conservative_slab(const SlabRay& s, float lox, float loy, float loz, float hix, float hiy, float hiz,
+                                                  float rayt) {
+    float t0x = __builtin_fmaf(lox, s.R.x, s.NO.x), t1x = __builtin_fmaf(hix, s.R.x, s.NO.x);
+    float t0y = __builtin_fmaf(loy, s.R.y, s.NO.y), t1y = __builtin_fmaf(hiy, s.R.y, s.NO.y);
+    float t0z = __builtin_fmaf(loz, s.R.z, s.NO.z), t1z = __builtin_fmaf(hiz, s.R.z, s.NO.z);
+    float tmin = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fmaxf(fminf(t0z, t1z), 0.f));
+    float tmax = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), rayt));
+    return !(__builtin_fmaf(tmax, 1.000002f, s.slack2) < tmin);
+}
+// a ray's closest hit as k_shade reads it
+__device__ __forceinline__ void store_hit(DevHit* hits, uint32_t pid, float t, uint32_t id, float b1, float b2) {
+    DevHit h;
+    h.t = t; h.id = id; h.b1 = b1; h.b2 = b2;
+    hits[pid] = h;
+}
+
 struct TraceCounters {
     uint32_t interior;
     uint32_t tris;

@@ -95,6 +95,76 @@ __device__ __forceinline__ void pixel_of(const RenderConsts& rc, uint32_t p, int
     }
 }
 
+// the grid of a one-thread-per-item launch with AGPT_BLOCK threads per block (64-bit: n may be a product of two 32-bit counts)
+static inline dim3 agpt_blocks(uint64_t n) { return dim3((unsigned)((n + AGPT_BLOCK - 1) / AGPT_BLOCK)); }
+
+// ---------------------------------------------------------------------------------------------------------
+// The two ends of a path, each written once: how it starts (k_generate, k_generate_li, k_generate_list; the pixel-centre rays of
+// agpt_denoise.h) and how its radiance reaches the film (k_accumulate, k_accumulate_list; k_resolve, k_resolve_counts).
+// Camera::GetRay (camera.h:58-64) for the film position (s, t) and the lens offset rd: the ray is (O, D), D normalised once
+__device__ __forceinline__ void camera_ray(const DevCamera& c, float s, float t, float rdx, float rdy, v3& O, v3& D) {
+    v3 offset = c.u * rdx + c.v * rdy;
+    v3 pixel = c.lower_left_corner + s * c.horizontal + t * c.vertical;
+    O = c.origin + offset;
+    D = normalize(pixel - c.origin - offset);
+}
+// ... with rd drawn on the lens disk by rejection (common.h:65-71) from the path's stream; no draw for a pinhole
+__device__ __forceinline__ void camera_sample_ray(const DevCamera& c, float s, float t, uint32_t& rng, v3& O, v3& D) {
+    v3 rd = V3s(0.f);
+    if (c.lens_radius > 0.f) {
+        for (;;) {
+            float a = -1.f + (1.f - -1.f) * rng_float(rng);
+            float b = -1.f + (1.f - -1.f) * rng_float(rng);
+            v3 pd = V3(a, b, 0);
+            if (sqrlen(pd) >= 1) continue;
+            rd = c.lens_radius * pd;
+            break;
+        }
+    }
+    camera_ray(c, s, t, rd.x, rd.y, O, D);
+}
+// The initial state of path i of a batch of `total`: its continuation ray, beta = 1, L = 0 with the stream's state, its place in
+// the ext queue; path 0 sets the three queue lengths.
+__device__ __forceinline__ void start_path(const PathBuffers& pb, const Queues& q, uint32_t i, uint32_t total, v3 O, v3 D, float tmax,
+                                           uint32_t rng, int32_t max_depth) {
+    float4 o4, d4, b4, l4;
+    o4.x = O.x; o4.y = O.y; o4.z = O.z; o4.w = tmax;
+    d4.x = D.x; d4.y = D.y; d4.z = D.z;
+    d4.w = max_depth > 0 ? 2.f : 0.f;   // 2: a camera ray that may be re-cast through emitters by the trace kernel (see k_trace_fast)
+    b4.x = 1.f; b4.y = 1.f; b4.z = 1.f; b4.w = __uint_as_float(0u);
+    l4.x = 0.f; l4.y = 0.f; l4.z = 0.f; l4.w = __uint_as_float(rng);
+    pb.ext_o[i] = o4;
+    pb.ext_d[i] = d4;
+    pb.beta4[i] = b4;
+    pb.L4[i] = l4;
+    q.ext[i] = i;
+    if (i == 0) {
+        QCOUNT(q, 0) = total;
+        QCOUNT(q, 1) = 0;
+        QCOUNT(q, 2) = 0;
+    }
+}
+// myapp.cpp:169-173: a sample with a NaN component or an infinite luminance is added as black and counted in `bad`.  (Values in,
+// values out: with clr or bad passed by reference the kernels compile to other code than with the test written out in them.)
+struct FilmSample { v3 clr; uint32_t bad; };
+__device__ __forceinline__ FilmSample film_sample(v3 clr, uint32_t bad) {
+    if (isnan(clr.x) || isnan(clr.y) || isnan(clr.z) || isinf(luminance(clr))) {
+        clr = V3s(0.f);
+        bad++;
+    }
+    return FilmSample{clr, bad};
+}
+// Accumulator::CopyToSurface (myapp.h:34-41) with lin2rgb / rgb2uint (template/common.h:41-51): the display word of a pixel that holds
+// the sum a.xyz of n samples
+__device__ __forceinline__ uint32_t resolve_word(const float4& a, float n) {
+    float e = 1 / 2.2f;
+    float r = powf(a.x / n, e), g = powf(a.y / n, e), b = powf(a.z / n, e);
+    int ri = (int)(256 * tclampf(r, 0.0f, 0.999f));
+    int gi = (int)(256 * tclampf(g, 0.0f, 0.999f));
+    int bi = (int)(256 * tclampf(b, 0.0f, 0.999f));
+    return (uint32_t)((ri << 16) + (gi << 8) + bi);
+}
+
 struct DevCounters {
     unsigned long long closest_rays, anyhit_rays, interior, tris, shaded, outliers, samples, roots, answered;
 #if defined(AGPT_TRACE_STATS) || defined(AGPT_SHADE_CLOCK)

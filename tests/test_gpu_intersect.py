@@ -170,15 +170,15 @@ def test_plane_primitive():
     compare(d, 96, 96, 2)
 
 
-def deep_mesh():
+def deep_mesh(unit=1.0):
     """A pathological mesh whose binned-SAH tree (depth 39) is deeper than the 23 stack entries the production kernel keeps in LDS
     (the rest live in its HBM spill column): triangle sizes in geometric progression (x8) along one axis make every split peel
-    off one triangle."""
+    off one triangle.  unit: a power of two that scales the whole mesh (the largest triangle measures 8^19 units)."""
     n = 40
     v, tris, scale = [], [], []
     x = 0.0
     for i in range(n):
-        w = 8.0 ** (i - n // 2)
+        w = 8.0 ** (i - n // 2) * unit
         v += [[x, 0, 0], [x + w, 0, 0], [x, w, 0]]
         tris.append([3 * i, 3 * i + 1, 3 * i + 2])
         scale.append(w)
@@ -188,9 +188,9 @@ def deep_mesh():
     return v, idx, scale, x
 
 
-def deep_mesh_scene():
+def deep_mesh_scene(unit=1.0):
     """deep_mesh() with a camera in front of its largest triangles, a sphere light and a sky."""
-    v, idx, scale, x = deep_mesh()
+    v, idx, scale, x = deep_mesh(unit)
     d = ag.SceneDesc("deep")
     m = d.add_material(ag.MAT_DIFFUSE_ONLY, [.5, .5, .5])
     d.add_mesh(v, None, None, idx, m, 1)

@@ -229,3 +229,73 @@ def test_side_streams_for_the_mis_and_shadow_launches(monkeypatch):
         ctx.close()
         assert a.tobytes() == b.tobytes(), d.name
         assert (sa.rays, sa.shaded_vertices, sa.iterations) == (sb.rays, sb.shaded_vertices, sb.iterations), d.name
+
+
+DEEP_UNIT = 2.0 ** -54   # deep_mesh() scaled so that its largest triangle measures 8
+
+
+def deep_mesh_with_emitter():
+    """test_gpu_intersect's deep_mesh_scene() -- a BVH deeper than the 23 stack entries k_trace_fast keeps in LDS -- with one small
+    emitter sphere (an area light's sphere: no material) on the view axis between the camera and the mesh.  Returns the scene, the
+    sphere's primitive index and the depth of the mesh's BVH.
+    The mesh is scaled down by a power of two: at its own size the camera sits at coordinates of 1e17, where the re-cast's origin
+    p + EPSILON * D (integrator.h:152-161) rounds to p, the ray leaves the sphere at t = 0 again and again, and the reference's
+    own loop never ends (the oracle does not return from such a render).  At this size the smallest triangles' areas underflow
+    and the builder's tree is 34 deep instead of 39: still eleven entries past the LDS stack."""
+    from test_gpu_intersect import deep_mesh, deep_mesh_scene
+    v, idx, scale, x = deep_mesh(DEEP_UNIT)
+    depth = ag.bvh_build(v, idx, 1)[2]
+    d = deep_mesh_scene(DEEP_UNIT)
+    d.name = "deep-emitter"
+    s = float(scale[-1])
+    prim = d.add_area_light([float(x) * 0.6, s * 0.3, s * 1.5], s * 0.15, [4., 3., 2.])
+    return d, prim, depth
+
+
+def emitter_pixels(d, prim, W, H):
+    """How many of the W x H pixel-centre camera rays have the primitive `prim` as the oracle's closest hit (CPU only)."""
+    import temporal_model as tm
+    cam = ag.camera_vectors(d.camera)
+    rays = np.zeros(W * H, ag.RAY_DTYPE)
+    rays["o"] = tm.camera(cam)["origin"]
+    rays["d"] = tm.feature_directions(cam, W, H).reshape(-1, 3)
+    rays["tmax"] = 3.402823466e+38
+    o = oracle_scene(d)
+    hits, _ = o.intersect(rays, any_hit=False)
+    return int(np.sum((hits["hit"] == 1) & (hits["prim"] == prim) & (hits["tri"] < 0)))
+
+
+def test_recast_in_the_spilling_closest_hit_kernels(monkeypatch):
+    """The re-cast of a ray that retires on an emitter's sphere, in the k_trace_fast instantiations whose traversal stack spills to
+    HBM: the small-batch launch (counters off) and the counting launch (counters=2) both read and re-write the rays through one
+    pointer.  Image bits and ray total equal the oracle's in both, and a depth-1 render takes fewer wavefront iterations than
+    the flow that sends such a path through k_shade (AGPT_NO_RECAST=1): the re-cast did run in the kernel."""
+    W, H, spp, depth = 64, 48, 2, 5
+    d, prim, bvh_depth = deep_mesh_with_emitter()
+    assert bvh_depth > 23   # (the SPILL instantiations)
+    n = emitter_pixels(d, prim, W, H)
+    print("pixel-centre rays whose closest hit is the emitter sphere: %d of %d" % (n, W * H))
+    assert n >= 20   # (the re-cast runs: the test cannot pass without one)
+    o = oracle_scene(d, depth)
+    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
+    try:
+        oacc, ost = o.render(W, H, spp, rng_mode=ob.RNG_PER_SAMPLE, threads=8)
+    finally:
+        ob.set_trig_mode(ob.TRIG_LIBM)
+    g = gpu_scene(d)
+    for counters in (0, 2):
+        acc, st = ag.PathTracer(depth).render_to_host(g, W, H, spp, counters=counters)
+        assert np.array_equal(acc[..., :3].view(np.uint32), oacc[..., :3].view(np.uint32)), counters
+        assert st.rays == ost.rays, (counters, st.rays, ost.rays)
+        # The re-cast ran in the kernel: the flow that sends such a path through k_shade (AGPT_NO_RECAST=1) gives the same image in
+        # more wavefront iterations.  Shown at depth 1: a render always runs max_depth + 3 iterations, a path that crosses the
+        # sphere (two re-casts) and then hits the mesh needs up to max_depth + 4 through k_shade, and at depth 5 no path on this
+        # one-sided mesh lives that long.
+        a, sa = ag.PathTracer(1).render_to_host(g, W, H, spp, counters=counters)
+        monkeypatch.setenv("AGPT_NO_RECAST", "1")
+        b, sb = ag.PathTracer(1).render_to_host(g, W, H, spp, counters=counters)
+        monkeypatch.delenv("AGPT_NO_RECAST")
+        print("counters=%d: iterations with the in-kernel re-cast %d, without %d" % (counters, sa.iterations, sb.iterations))
+        assert a.tobytes() == b.tobytes(), counters
+        assert sa.iterations < sb.iterations, counters
+    g.close()
