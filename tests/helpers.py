@@ -1,8 +1,16 @@
-"""Shared test helpers: instantiate one SceneDesc on the CPU oracle (checker) and on the GPU (product)."""
+"""Shared test helpers: instantiate one SceneDesc on the CPU oracle (checker) and on the GPU (product), render it on either, build the
+C and C++ programs the tests run against include/, and the comparisons more than one test file makes."""
+import ctypes as C
+import os
+import re
+import subprocess
+
 import numpy as np
 
 import ag_pathtracer_amd as ag
 from oracle import binding as ob
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def oracle_scene(desc, max_depth=None):
@@ -10,6 +18,21 @@ def oracle_scene(desc, max_depth=None):
     if max_depth is not None:
         s.set_max_depth(max_depth)
     return s
+
+
+def oracle_render_on(o, W, H, spp, **kw):
+    """o.render on the GPU's per-(pixel, sample) RNG streams, with correctly-rounded trig -- what the kernels compute -- for the call"""
+    kw.setdefault("threads", 8)
+    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
+    try:
+        return o.render(W, H, spp, rng_mode=ob.RNG_PER_SAMPLE, **kw)
+    finally:
+        ob.set_trig_mode(ob.TRIG_LIBM)
+
+
+def oracle_render(desc, W, H, spp, max_depth=5, **kw):
+    """(accumulator, stats) of oracle_render_on for a fresh oracle scene of desc"""
+    return oracle_render_on(oracle_scene(desc, max_depth), W, H, spp, **kw)
 
 
 _CTX = None
@@ -24,6 +47,15 @@ def gpu_context():
 
 def gpu_scene(desc):
     return desc.instantiate(ag.Scene(gpu_context()))
+
+
+def render(g, W, H, spp, depth=5, arith="exact"):
+    g.set_shading_arith(arith)
+    return ag.PathTracer(depth).render_to_host(g, W, H, spp)
+
+
+def scene_c1():
+    return ag.scenes.scene_c1()
 
 
 def scene_bounds(desc):
@@ -105,3 +137,68 @@ def signed_zero_grid(n):
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def close_fraction(a, b, rel):
+    """the share of pixels with every channel within rel |b| + 1e-6"""
+    return float(np.all(np.abs(a - b) <= rel * np.abs(b) + 1e-6, axis=-1).mean())
+
+
+def compare_with_model(out, model, what):
+    """the denoiser against tests/denoise_model.py, within the bound that model states"""
+    differ = (out != model).any(-1)
+    n = int(differ.sum())
+    err = np.abs(out.astype(np.float64) - model.astype(np.float64))
+    bound = 2.0 ** -18 * np.abs(model.astype(np.float64)) + 1e-7
+    print("%s: %d of %d pixels differ from the model, max abs difference %.3g" % (what, n, differ.size, err.max()))
+    assert n <= 4, (what, n, np.argwhere(differ)[:8])
+    assert (err <= bound).all(), (what, err.max(), np.argwhere(err > bound)[:8])
+
+
+def tile_rows(acc, H, tile):
+    """the rgb rows [h, w, 3] of tile (x0, y0, w, h) in an accumulator of height H (row 0 = top)"""
+    x0, y0, w, h = tile
+    return acc[H - y0 - h:H - y0, x0:x0 + w, :3]
+
+
+def build_cpp_example(tmp_path, name, wall=True):
+    """examples/NAME.cpp -- or, for a path, that C++ file -- compiled against include/ and linked to the built library; the executable"""
+    src = name if os.path.isabs(str(name)) else os.path.join(ROOT, "examples", name + ".cpp")
+    exe = str(tmp_path / os.path.splitext(os.path.basename(str(src)))[0])
+    lib = ag.library_path()
+    subprocess.check_call(["g++", "-std=c++17"] + ["-Wall"] * wall +
+                          ["-I" + os.path.join(ROOT, "include"), str(src), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
+    return exe
+
+
+def struct_layout(tmp_path, structs):
+    """{C struct name: ctypes class}: sizeof and every offsetof, printed by a C probe compiled against include/agpt.h, are the class's"""
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "agpt.h"', "int main(void) {"]
+    for cname, cls in structs.items():
+        lines.append('printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
+        for f, _ in cls._fields_:
+            lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f))
+    lines.append("return 0; }")
+    src = tmp_path / "probe.c"
+    src.write_text("\n".join(lines))
+    exe = str(tmp_path / "probe")
+    subprocess.check_call(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
+    got = {}
+    for ln in subprocess.check_output([exe]).decode().split("\n"):
+        if ln:
+            s, f, v = ln.split()
+            got[(s, f)] = int(v)
+    for cname, cls in structs.items():
+        assert got[(cname, "sizeof")] == C.sizeof(cls), cname
+        for f, _ in cls._fields_:
+            assert got[(cname, f)] == getattr(cls, f).offset, (cname, f)
+
+
+def assert_exported(names):
+    """every name is declared in include/agpt.h, listed in ag.EXPORTS and exported by the built library"""
+    header = open(os.path.join(ROOT, "include", "agpt.h")).read()
+    L = ag.lib()
+    for name in names:
+        assert re.search(r"\b%s\s*\(" % name, header), name
+        assert name in ag.EXPORTS, name
+        assert hasattr(L, name), name

@@ -12,6 +12,7 @@ import pytest
 
 import adaptive_model as am
 import ag_pathtracer_amd as ag
+from helpers import assert_exported, struct_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _spec = importlib.util.spec_from_file_location("agpt_build", os.path.join(ROOT, "ag-pathtracer_amd", "build.py"))
@@ -20,36 +21,12 @@ _spec.loader.exec_module(b)
 
 
 def test_symbols_declared_and_exported():
-    header = open(os.path.join(ROOT, "include", "agpt.h")).read()
-    L = ag.lib()
-    for name in ("agpt_render_adaptive", "agpt_resolve_counts"):
-        assert re.search(r"\b%s\s*\(" % name, header), name
-        assert name in ag.EXPORTS
-        assert hasattr(L, name)
+    assert_exported(("agpt_render_adaptive", "agpt_resolve_counts"))
     assert "agpt_adaptive.hip" in b.SOURCES
 
 
 def test_struct_layout_matches_ctypes(tmp_path):
-    fields = {"agpt_adaptive_params": ag.AdaptiveParams, "agpt_adaptive_stats": ag.AdaptiveStats}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "agpt.h"', "int main(void) {"]
-    for cname, cls in fields.items():
-        lines.append('printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
-        for f, _ in cls._fields_:
-            lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f))
-    lines.append("return 0; }")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "probe")
-    subprocess.check_call(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = {}
-    for ln in subprocess.check_output([exe]).decode().split("\n"):
-        if ln:
-            s, f, v = ln.split()
-            got[(s, f)] = int(v)
-    for cname, cls in fields.items():
-        assert got[(cname, "sizeof")] == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert got[(cname, f)] == getattr(cls, f).offset, (cname, f)
+    struct_layout(tmp_path, {"agpt_adaptive_params": ag.AdaptiveParams, "agpt_adaptive_stats": ag.AdaptiveStats})
 
 
 def test_null_arguments_are_invalid_without_a_gpu():

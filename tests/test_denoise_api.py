@@ -14,7 +14,7 @@ import adaptive_model as am
 import ag_pathtracer_amd as ag
 import denoise_model as dm
 from denoise_features import host_features
-from helpers import oracle_scene
+from helpers import assert_exported, oracle_scene, struct_layout
 from oracle import binding as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,12 +26,8 @@ INVALID = -1
 
 
 def test_symbols_declared_and_exported():
+    assert_exported(("agpt_render_features", "agpt_denoise"))
     header = open(os.path.join(ROOT, "include", "agpt.h")).read()
-    L = ag.lib()
-    for name in ("agpt_render_features", "agpt_denoise"):
-        assert re.search(r"\b%s\s*\(" % name, header), name
-        assert name in ag.EXPORTS
-        assert hasattr(L, name)
     assert "agpt_denoise.hip" in b.SOURCES
     assert "agpt_denoise.h" in b.HEADERS
     # the defaults the binding and the model carry are the header's
@@ -42,24 +38,7 @@ def test_symbols_declared_and_exported():
 
 
 def test_struct_layout_matches_ctypes(tmp_path):
-    cname, cls = "agpt_denoise_params", ag.DenoiseParams
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "agpt.h"', "int main(void) {",
-             'printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname)]
-    for f, _ in cls._fields_:
-        lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f))
-    lines.append("return 0; }")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "probe")
-    subprocess.check_call(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = {}
-    for ln in subprocess.check_output([exe]).decode().split("\n"):
-        if ln:
-            s, f, v = ln.split()
-            got[f] = int(v)
-    assert got["sizeof"] == C.sizeof(cls)
-    for f, _ in cls._fields_:
-        assert got[f] == getattr(cls, f).offset, f
+    struct_layout(tmp_path, {"agpt_denoise_params": ag.DenoiseParams})
 
 
 def test_invalid_arguments_without_a_gpu():

@@ -10,18 +10,14 @@ import pytest
 
 import adaptive_model as am
 import ag_pathtracer_amd as ag
-from helpers import gpu_context, gpu_scene, oracle_scene
-from oracle import binding as ob
+import helpers
+from helpers import gpu_context, gpu_scene, scene_c1
 
 pytestmark = pytest.mark.gpu
 
 W, H = 64, 48
 MIN, STEP, MAX = 4, 4, 32
 FLOOR = 0.01
-
-
-def scene_c1():
-    return ag.scenes.scene_c1()
 
 
 def scene_lens_mirror():
@@ -52,13 +48,8 @@ _CACHE = {}
 
 
 def oracle_render(desc, spp, spp_begin=0):
-    o = oracle_scene(desc, 5)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        acc, _ = o.render(W, H, spp, spp_begin=spp_begin, rng_mode=ob.RNG_PER_SAMPLE, threads=8)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-    return acc
+    """helpers.oracle_render at this file's film size: the accumulator alone"""
+    return helpers.oracle_render(desc, W, H, spp, spp_begin=spp_begin)[0]
 
 
 def setup(name):

@@ -9,28 +9,19 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import oracle_scene
+from helpers import build_cpp_example, oracle_scene
 from oracle import binding as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "simple_test_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "simple_test_scene.cpp"), "-o", exe, lib,
-                           "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_example_compiles_and_links(tmp_path):
-    build_example(tmp_path)
+    build_cpp_example(tmp_path, "simple_test_scene")
 
 
 @pytest.mark.gpu
 def test_cpp_example_matches_oracle(tmp_path):
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "simple_test_scene")
     out = subprocess.check_output([exe, "4"]).decode()
     m = re.search(r"frames=4 rays=(\d+) mean_rgb=([\d.]+) ([\d.]+) ([\d.]+)", out)
     assert m, out
@@ -83,7 +74,7 @@ def test_cpp_example_matches_oracle(tmp_path):
 def test_cpp_example_lit_by_an_hdr_file_matches_oracle(tmp_path):
     """The reference's default lighting (myapp.cpp:113): agpt::InfiniteAreaLight("file.hdr") = agpt_hdr_load + the library's
     Distribution1D, through the C++ adapter; the oracle gets the pixels the vendored stb_image decoded (tests/golden/hdr_cases.npz)."""
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "simple_test_scene")
     g = np.load(os.path.join(ROOT, "tests", "golden", "hdr_cases.npz"))
     hdr = tmp_path / "env.hdr"
     hdr.write_bytes(g["rle_64x32_sky/bytes"].tobytes())
@@ -128,10 +119,7 @@ def test_bunny_scene_example_obj_orbit_png(tmp_path):
     """examples/bunny_scene.cpp = the reference's BunnyScene (myapp.cpp:13-52) with an OBJ stand-in: LoadObj with a
     transform, backdrop, three sphere lights + sky, 8 progressive frames, an orbit step, PNG + PFM output.  The PFM is
     compared with the same scene rendered through the Python mirror (same library, same OBJ loader)."""
-    exe = str(tmp_path / "bunny_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "bunny_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
+    exe = build_cpp_example(tmp_path, "bunny_scene")
     v, n, t, idx = ag.scenes.blob_mesh(40, 30, center=(0.0, 1.0, 0.0), radius=0.8, seed=5)
     obj = str(tmp_path / "blob.obj")
     write_obj(obj, v, n, idx)
@@ -238,8 +226,5 @@ int main() {
     std::printf("%s\n", ok ? "identical" : "DIFFERENT");
     return 0;
 }''')
-    exe = str(tmp_path / "shares")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe, lib,
-                           "-Wl,-rpath," + os.path.dirname(lib)])
+    exe = build_cpp_example(tmp_path, str(src))
     assert subprocess.check_output([exe]).decode().strip() == "identical"

@@ -1,6 +1,5 @@
 """The C++ adapter's adaptive path (include/agpt_host.hpp: AdaptiveAccumulator, PathTracer::RenderAdaptive): a small program
 compiled with g++ against libagpt_hip.so renders adaptively in two calls, and must give the bytes the Python path gives."""
-import os
 import re
 import subprocess
 
@@ -8,9 +7,8 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import gpu_scene
+from helpers import build_cpp_example, gpu_scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 96, 64
 
 PROGRAM = r"""
@@ -60,11 +58,7 @@ int main(int argc, char** argv) {
 def build_program(tmp_path):
     src = tmp_path / "adaptive.cpp"
     src.write_text(PROGRAM % dict(W=W, H=H))
-    exe = str(tmp_path / "adaptive")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe, lib,
-                           "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
+    return build_cpp_example(tmp_path, str(src))
 
 
 def test_cpp_adaptive_program_compiles_and_links(tmp_path):

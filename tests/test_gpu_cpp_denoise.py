@@ -1,7 +1,6 @@
 """The C++ adapter's denoising path (include/agpt_host.hpp: FeatureBuffers, PathTracer::RenderFeatures,
 AdaptiveAccumulator::Denoise): examples/denoise_scene.cpp compiled with g++ against libagpt_hip.so must give the bytes the
 Python path gives."""
-import os
 import re
 import subprocess
 
@@ -9,27 +8,18 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import gpu_scene
+from helpers import build_cpp_example, gpu_scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 96, 64
 
 
-def build_program(tmp_path):
-    exe = str(tmp_path / "denoise_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "denoise_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_denoise_program_compiles_and_links(tmp_path):
-    build_program(tmp_path)
+    build_cpp_example(tmp_path, "denoise_scene")
 
 
 @pytest.mark.gpu
 def test_cpp_denoise_matches_python(tmp_path):
-    exe = build_program(tmp_path)
+    exe = build_cpp_example(tmp_path, "denoise_scene")
     out_path = str(tmp_path / "out.bin")
     out = subprocess.check_output([exe, out_path, str(W), str(H)], timeout=300).decode()
     assert re.search(r"denoised %dx%d samples=1" % (W, H), out), out

@@ -1,6 +1,5 @@
 """The C++ adapter's frame loop (include/agpt_host.hpp: AdaptiveAccumulator::TemporalAccumulate): examples/temporal_scene.cpp
 compiled with g++ against libagpt_hip.so must leave the history bytes the Python path leaves after the same frames."""
-import os
 import re
 import subprocess
 
@@ -8,27 +7,18 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import gpu_scene
+from helpers import build_cpp_example, gpu_scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, FRAMES = 48, 40, 3
 
 
-def build_program(tmp_path):
-    exe = str(tmp_path / "temporal_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "temporal_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_temporal_program_compiles_and_links(tmp_path):
-    build_program(tmp_path)
+    build_cpp_example(tmp_path, "temporal_scene")
 
 
 @pytest.mark.gpu
 def test_cpp_temporal_matches_python(tmp_path):
-    exe = build_program(tmp_path)
+    exe = build_cpp_example(tmp_path, "temporal_scene")
     out_path = str(tmp_path / "out.bin")
     out = subprocess.check_output([exe, out_path, str(W), str(H), str(FRAMES)], timeout=300).decode()
     assert re.search(r"temporal %dx%d frames=%d" % (W, H, FRAMES), out), out

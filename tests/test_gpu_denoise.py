@@ -14,14 +14,10 @@ import pytest
 import ag_pathtracer_amd as ag
 import denoise_model as dm
 from denoise_features import host_features, primitive_table
-from helpers import gpu_context, gpu_scene
+from helpers import compare_with_model, gpu_context, gpu_scene, scene_c1
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-
-
-def scene_c1():
-    return ag.scenes.scene_c1()
 
 
 def scene_c3_small():
@@ -194,16 +190,6 @@ def render_inputs(name, kind):
         acc, m2, _, _ = pt.render_adaptive_to_host(g, W, H, kind, kind, kind, 0.0)
         assert (acc[..., 3] == kind).all()
     return acc, m2
-
-
-def compare_with_model(out, model, what):
-    differ = (out != model).any(-1)
-    n = int(differ.sum())
-    err = np.abs(out.astype(np.float64) - model.astype(np.float64))
-    bound = 2.0 ** -18 * np.abs(model.astype(np.float64)) + 1e-7
-    print("%s: %d of %d pixels differ from the model, max abs difference %.3g" % (what, n, differ.size, err.max()))
-    assert n <= 4, (what, n, np.argwhere(differ)[:8])
-    assert (err <= bound).all(), (what, err.max(), np.argwhere(err > bound)[:8])
 
 
 @pytest.mark.parametrize("name", ["c1", "c3_small"])

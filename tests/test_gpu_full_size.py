@@ -7,24 +7,14 @@ import pytest
 
 import ag_pathtracer_amd as ag
 from ag_pathtracer_amd import tiles
-from helpers import gpu_scene, oracle_scene
+from helpers import gpu_scene, oracle_render, oracle_scene, tile_rows
 from oracle import binding as ob
 
 pytestmark = pytest.mark.gpu
 
 
 def oracle_tile(desc, W, H, spp, tile):
-    o = oracle_scene(desc)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        return o.render(W, H, spp, tile=tile, threads=8)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-
-
-def tile_rows(acc, H, tile):
-    x0, y0, w, h = tile
-    return acc[H - y0 - h:H - y0, x0:x0 + w, :3]
+    return oracle_render(desc, W, H, spp, None, tile=tile)
 
 
 def test_c3_full_scene_1080p_tile_vs_oracle_and_invariances():

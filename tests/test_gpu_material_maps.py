@@ -2,7 +2,6 @@
 textures (test_gpu_textures.py) every test is built so that it is still the yardstick: a map of one value must equal the plain
 material, a texel per mesh must equal a material per mesh -- lobe set, alpha clamp and all -- bit for bit."""
 import copy
-import os
 import re
 import subprocess
 
@@ -10,34 +9,14 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
+import texture_cases as tc
 import texture_model as tm
-from helpers import bits, gpu_scene, oracle_scene
+from helpers import bits, build_cpp_example, gpu_scene, oracle_render, oracle_scene, render
 from oracle import binding as ob
+from texture_cases import K, PALETTE, SOUP, palette_meshes, soup_excluded_pixels, without, without_textures
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 R, M = ag.PARAM_ROUGHNESS, ag.PARAM_METALLIC
-TEXTURE_OPS = ("texture", "material_texture", "material_param_texture")
-
-
-def oracle_render(desc, W, H, spp, max_depth=5, **kw):
-    o = oracle_scene(desc, max_depth)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        return o.render(W, H, spp, rng_mode=ob.RNG_PER_SAMPLE, threads=8, **kw)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-
-
-def without(desc, kinds):
-    d = copy.copy(desc)
-    d.ops = [op for op in desc.ops if op[0] not in kinds]
-    d.n_textures = sum(op[0] == "texture" for op in d.ops)
-    return d
-
-
-def without_textures(desc):
-    return without(desc, TEXTURE_OPS)
 
 
 def without_maps(desc):
@@ -66,11 +45,6 @@ def with_constant_maps(desc, tw, th, constant_colour_too=False):
         if constant_colour_too:
             d.set_material_texture(m, d.add_texture(np.broadcast_to(np.asarray(c, F), (th, tw, 3))))
     return d
-
-
-def render(g, W, H, spp, depth=5, arith="exact"):
-    g.set_shading_arith(arith)
-    return ag.PathTracer(depth).render_to_host(g, W, H, spp)
 
 
 # ---- 1. a map of one value is no map ---------------------------------------------------------------------------------------
@@ -115,9 +89,6 @@ def test_constant_map_equals_no_map(which, size):
 
 
 # ---- 2. one texel per mesh = one material per mesh -----------------------------------------------------------------------------
-K = 8
-PALETTE = np.array([[.80, .78, .70], [.85, .30, .25], [.20, .55, .80], [.95, .93, .88], [.35, .70, .30], [.90, .75, .35],
-                    [.55, .35, .75], [.25, .25, .28]], F)
 # (roughness, metallic) per texel: metallic 0, 1 and .5 -- the lobe set changes per hit --, roughness 0 and .02 -- both below the
 # .001 clamp of alpha = r * r --, .35 and 1
 PARAMS = np.array([[1.0, 0.0], [.35, 1.0], [0.0, .5], [.02, 0.0], [.6, .5], [0.0, 1.0], [.02, 1.0], [.5, .3]], F)
@@ -129,25 +100,6 @@ def test_parameter_palette_has_the_required_values():
     assert {0.0, 1.0, 0.5} <= set(PARAMS[:, 1].tolist())
     assert {F(0.0), F(.02), F(.35), F(1.0)} <= set(PARAMS[:, 0])
     assert (PARAMS[:, 0][PARAMS[:, 0] <= F(.02)] ** 2 < F(.001)).all()
-
-
-def palette_meshes(degenerate_uv):
-    """K meshes -- a floor and K - 1 blobs around the origin -- whose texture coordinates all lie inside texel k's footprint
-    [(k + .5) / K, (k + 1.5) / K) of a K x 1 palette, a tenth of a texel away from its ends"""
-    rng = np.random.RandomState(5)
-    meshes = []
-    for k in range(K):
-        if k == 0:
-            v, n, t, idx = ag.scenes.grid_mesh(lambda U, V: np.stack([-6 + 12 * U, -1 + 0 * U, -6 + 12 * V], -1), 6, 6)
-        else:
-            a = 2 * np.pi * k / (K - 1)
-            v, n, t, idx = ag.scenes.blob_mesh(10, 8, center=(2.4 * np.cos(a), -0.2 + 0.5 * (k % 3), 2.4 * np.sin(a)), radius=0.85, seed=k)
-        if degenerate_uv:
-            uv = np.broadcast_to(np.array([(k + 1.0) / K, 0.5], F), (len(v), 2)).copy()
-        else:
-            uv = np.stack([(k + 0.6 + 0.8 * rng.uniform(size=len(v))) / K, rng.uniform(0.1, 0.9, len(v))], 1).astype(F)
-        meshes.append((v, n, uv, idx))
-    return meshes
 
 
 def variant_values(variant):
@@ -164,7 +116,6 @@ def palette_scene(degenerate_uv, variant, mapped):
     """mapped: K meshes sharing ONE Disney material whose colour / roughness / metallic come from K x 1 images as `variant` says;
     otherwise one plain material per mesh with those values (what the oracle renders)"""
     d = ag.SceneDesc("palette-" + variant)
-    meshes = palette_meshes(degenerate_uv)
     colour, rough, metal = variant_values(variant)
     if mapped:
         m = d.add_material(ag.MAT_DISNEY, CONST_COLOUR, CONST_ROUGH, CONST_METAL)
@@ -188,15 +139,9 @@ def palette_scene(degenerate_uv, variant, mapped):
         else:                                                    # one_image
             d.set_material_param_texture(m, R, ctex, 0)
             d.set_material_param_texture(m, M, ctex, 1)
-        for v, n, uv, idx in meshes:
-            d.add_mesh(v, n, uv, idx, m, 1)
-    else:
-        for k, (v, n, uv, idx) in enumerate(meshes):
-            d.add_mesh(v, n, uv, idx, d.add_material(ag.MAT_DISNEY, colour[k], float(rough[k]), float(metal[k])), 1)
-    d.add_area_light([0, 9, -2], 1.0, ag.scenes.KEY_LIGHT * F(60))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.5, 4.5, -7.5], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+        return tc.palette_scene(d, palette_meshes(degenerate_uv), lambda k: m)
+    return tc.palette_scene(d, palette_meshes(degenerate_uv),
+                            lambda k: d.add_material(ag.MAT_DISNEY, colour[k], float(rough[k]), float(metal[k])))
 
 
 def test_palette_footprints():
@@ -269,59 +214,20 @@ def test_slots_are_independent(variant):
 
 
 # ---- 4. variation inside one mesh, whole paths ----------------------------------------------------------------------------
-def triangle_soup():
-    """a bumpy floor and a blob as ONE mesh of T unshared triangles, each with its three uvs inside one palette texel"""
-    parts = [ag.scenes.heightfield(10, S=3.0), ag.scenes.blob_mesh(10, 8, center=(0.2, 1.3, 0.1), radius=0.9, seed=2)]
-    V, N, UV, texel = [], [], [], []
-    rng = np.random.RandomState(8)
-    for v, n, t, idx in parts:
-        tri = idx[:, 0].reshape(-1, 3)
-        for a in tri:
-            k = int(rng.randint(K))
-            V.append(v[a])
-            N.append(n[a])
-            UV.append(np.stack([(k + 0.6 + 0.8 * rng.uniform(size=3)) / K, rng.uniform(0.1, 0.9, 3)], 1))
-            texel.append(k)
-    return np.concatenate(V).astype(F), np.concatenate(N).astype(F), np.concatenate(UV).astype(F), np.array(texel)
-
-
 def soup_scene(mode):
     """mode "mapped": the single mesh, roughness and metallic per triangle through the parameter palette; "single" / "grouped": the
     single mesh / the triangles regrouped into K meshes by texel, all with ONE material; "grouped_params": regrouped with K plain
     materials"""
-    v, n, uv, texel = triangle_soup()
-    d = ag.SceneDesc("soup-" + mode)
-    one = PALETTE[0]
-
-    def mesh(sel, material):
-        ids = np.repeat(3 * np.nonzero(sel)[0], 3) + np.tile(np.arange(3), int(sel.sum()))
-        ix = np.arange(len(ids), dtype=np.int32)
-        d.add_mesh(v[ids], n[ids], uv[ids], np.stack([ix, ix, ix], 1), material, 1)
-
-    if mode in ("mapped", "single"):
-        m = d.add_material(ag.MAT_DISNEY, one, 0.5, 0.3)
+    def material(d, k):
+        r, mt = (float(PARAMS[k, 0]), float(PARAMS[k, 1])) if mode == "grouped_params" else (0.5, 0.3)
+        m = d.add_material(ag.MAT_DISNEY, PALETTE[0], r, mt)
         if mode == "mapped":
             image = d.add_texture(np.stack([np.zeros(K, F), PARAMS[:, 0], PARAMS[:, 1]], -1)[None])
             d.set_material_param_texture(m, R, image, 1)
             d.set_material_param_texture(m, M, image, 2)
-        mesh(np.ones(len(texel), bool), m)
-    else:
-        for k in range(K):
-            r, mt = (float(PARAMS[k, 0]), float(PARAMS[k, 1])) if mode == "grouped_params" else (0.5, 0.3)
-            mesh(texel == k, d.add_material(ag.MAT_DISNEY, one, r, mt))
-    d.add_area_light([1, 7, -2], 0.8, ag.scenes.KEY_LIGHT * F(50))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.4, 3.4, -5.2], [0, 0.4, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+        return m
 
-
-SOUP = dict(W=64, H=64, spp=2, depth=5)
-
-
-def soup_excluded_pixels():
-    a, _ = oracle_render(soup_scene("single"), SOUP["W"], SOUP["H"], SOUP["spp"], SOUP["depth"])
-    b, _ = oracle_render(soup_scene("grouped"), SOUP["W"], SOUP["H"], SOUP["spp"], SOUP["depth"])
-    return (bits(a[..., :3]) != bits(b[..., :3])).any(-1)
+    return tc.soup_scene("soup-" + mode, material, grouped=mode.startswith("grouped"))
 
 
 def test_regrouping_changes_few_pixels_for_the_oracle():
@@ -444,22 +350,14 @@ def test_fast_mapped_equals_fast_per_mesh_materials(degenerate_uv):
 
 
 # ---- 8. the C++ adapter ---------------------------------------------------------------------------------------------------
-def build_example(tmp_path):
-    exe = str(tmp_path / "mapped_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "mapped_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_mapped_example_compiles_and_links(tmp_path):
-    build_example(tmp_path)
+    build_cpp_example(tmp_path, "mapped_scene")
 
 
 @pytest.mark.gpu
 def test_cpp_mapped_example_matches_python(tmp_path):
     W, H = 96, 64
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "mapped_scene")
     out_path = str(tmp_path / "out.bin")
     out = subprocess.check_output([exe, out_path, str(W), str(H)], timeout=300).decode()
     assert re.search(r"mapped %dx%d samples=4" % (W, H), out), out

@@ -12,7 +12,7 @@ import pytest
 import ag_pathtracer_amd as ag
 import bvh_refit_model as model
 import mesh_update_cases as cases
-from helpers import bits, gpu_context, gpu_scene, oracle_scene, random_rays, signed_zero_grid
+from helpers import bits, build_cpp_example, gpu_context, gpu_scene, oracle_render_on, oracle_scene, random_rays, signed_zero_grid
 from oracle import binding as ob
 
 pytestmark = pytest.mark.gpu
@@ -34,12 +34,9 @@ def render(g, counters_mode=0, w=W, h=H):
 
 @functools.lru_cache(maxsize=None)
 def oracle_render(pose, scale):
+    """the oracle scene of both blobs in `pose` -- kept: the tests query it too -- and its render, once per argument set"""
     o = oracle_scene(cases.scene(pose, pose, scale), 5)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        acc, st = o.render(W, H, SPP, rng_mode=ob.RNG_PER_SAMPLE, threads=8)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
+    acc, st = oracle_render_on(o, W, H, SPP)
     acc.setflags(write=False)
     return o, acc, st
 
@@ -329,8 +326,7 @@ def test_a_non_finite_vertex_takes_the_host_path():
 
 def test_cpp_animated_example_writes_a_frame_per_pose(tmp_path):
     import subprocess
-    from test_mesh_update_api import build_example
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "animated_scene")
     out = subprocess.run([exe, str(tmp_path / "f"), "3", "32", "24"], check=True, capture_output=True, text=True).stdout
     frames = [(tmp_path / ("f_%03d.png" % k)).read_bytes() for k in range(3)]
     assert out.count("samples=8") == 3

@@ -2,7 +2,6 @@
 maps; every test is built so that it is still the yardstick: the perturbation alone against the numpy model (tests/normal_map_model.py)
 bit for bit, a flat map against no map, the first-hit normal against the model fed the oracle's hits, and invariance of the render."""
 import functools
-import os
 import re
 import subprocess
 
@@ -15,10 +14,10 @@ import normal_map_model as nm
 import texture_filter_model as fm
 import texture_model as tm
 from denoise_features import host_features, primitive_table
-from helpers import bits, gpu_context, gpu_scene, oracle_scene
+from helpers import bits, build_cpp_example, close_fraction, compare_with_model, gpu_context, gpu_scene, oracle_scene, render
 from oracle import binding as ob
+from texture_cases import varying_lights_and_camera, varying_mesh
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 BILINEAR, NEAREST = ag.FILTER_BILINEAR, ag.FILTER_NEAREST
 KINDS = {"disney": ag.MAT_DISNEY, "mirror": ag.MAT_MIRROR, "diffuse": ag.MAT_DIFFUSE_ONLY}
@@ -62,14 +61,6 @@ def test_kat_is_the_model_bit_for_bit(scale):
 
 
 # ---- shared scenes -----------------------------------------------------------------------------------------------------------
-def varying_mesh(with_normals=True):
-    """test_gpu_texture_filter.varying_scene's mesh: a heightfield whose uvs are a rotated, scaled copy of the grid's own and leave [0, 1]"""
-    v, n, t, idx = ag.scenes.heightfield(24)
-    c, s = np.cos(0.4), np.sin(0.4)
-    uv = np.stack([1.7 * (c * t[:, 0] - s * t[:, 1]) - 0.3, 1.3 * (s * t[:, 0] + c * t[:, 1]) + 0.2], 1).astype(F)
-    return v, (n if with_normals else None), uv, idx
-
-
 def varying_scene(kind="disney", normal=None, with_normals=True):
     """the varying mesh with one material of `kind`, a gold sphere beside it (its material has no map) and two lights; normal: None or
     (image, filter, wrap_u, wrap_v, scale)"""
@@ -83,15 +74,7 @@ def varying_scene(kind="disney", normal=None, with_normals=True):
         t = d.add_texture(image)
         d.set_texture_sampler(t, filter, wu, wv)
         d.set_material_normal_texture(m, t, scale)
-    d.add_area_light([0, 6, 0], 0.5, ag.scenes.KEY_LIGHT * F(30))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.3, 3.2, -3.6], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
-
-
-def render(g, W, H, spp, depth=5, arith="exact"):
-    g.set_shading_arith(arith)
-    return ag.PathTracer(depth).render_to_host(g, W, H, spp)
+    return varying_lights_and_camera(d)
 
 
 # ---- 2. a flat map is no map -----------------------------------------------------------------------------------------------
@@ -393,11 +376,6 @@ def quad_oracle(mode, spp):
     return acc[..., :3].reshape(-1, 3)
 
 
-def close_fraction(a, b, rel):
-    """test_gpu_shading_fast.close_fraction: the share of pixels with every channel within rel |b| + 1e-6"""
-    return float(np.all(np.abs(a - b) <= rel * np.abs(b) + 1e-6, axis=-1).mean())
-
-
 def mean_rel(a, b):
     ma, mb = a.mean(0, dtype=np.float64), b.mean(0, dtype=np.float64)
     return np.abs(ma - mb) / np.maximum(np.abs(mb), 1e-12)
@@ -438,17 +416,6 @@ def test_whole_paths_match_the_oracle_on_baked_normals(arith):
 
 
 # ---- 6. adaptive sampling and the denoiser ---------------------------------------------------------------------------------
-def compare_with_model(out, model, what):
-    """test_gpu_denoise.compare_with_model: the bound of tests/denoise_model.py"""
-    differ = (out != model).any(-1)
-    n = int(differ.sum())
-    err = np.abs(out.astype(np.float64) - model.astype(np.float64))
-    bound = 2.0 ** -18 * np.abs(model.astype(np.float64)) + 1e-7
-    print("%s: %d of %d pixels differ from the model, max abs difference %.3g" % (what, n, differ.size, err.max()))
-    assert n <= 4, (what, n, np.argwhere(differ)[:8])
-    assert (err <= bound).all(), (what, err.max(), np.argwhere(err > bound)[:8])
-
-
 @pytest.mark.gpu
 def test_adaptive_render_features_and_denoise_match_the_model():
     W = H = 64
@@ -481,22 +448,14 @@ def test_adaptive_render_features_and_denoise_match_the_model():
 
 
 # ---- 7. the C++ adapter ------------------------------------------------------------------------------------------------------
-def build_example(tmp_path):
-    exe = str(tmp_path / "normal_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "normal_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_normal_example_compiles_and_links(tmp_path):
-    build_example(tmp_path)
+    build_cpp_example(tmp_path, "normal_scene")
 
 
 @pytest.mark.gpu
 def test_cpp_normal_example_matches_python(tmp_path):
     W, H = 64, 48
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "normal_scene")
     out_path = str(tmp_path / "out.bin")
     out = subprocess.check_output([exe, out_path, str(W), str(H)], timeout=300).decode()
     assert re.search(r"normal-mapped %dx%d samples=4" % (W, H), out), out

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
+import helpers
 from ag_pathtracer_amd import tiles
 from helpers import gpu_scene, oracle_scene
 from oracle import binding as ob
@@ -42,14 +43,10 @@ _ORACLE = {}
 
 
 def oracle_render(W, H, spp, depth, spp_begin=0):
+    """helpers.oracle_render of the retire scene, once per argument set: (read-only accumulator, (closest, any-hit, outliers))"""
     key = (W, H, spp, depth, spp_begin)
     if key not in _ORACLE:
-        o = oracle_scene(retire_scene(), depth)
-        ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-        try:
-            acc, st = o.render(W, H, spp, spp_begin=spp_begin, rng_mode=ob.RNG_PER_SAMPLE, threads=8)
-        finally:
-            ob.set_trig_mode(ob.TRIG_LIBM)
+        acc, st = helpers.oracle_render(retire_scene(), W, H, spp, depth, spp_begin=spp_begin)
         acc.setflags(write=False)
         _ORACLE[key] = (acc, (int(st.closest_rays), int(st.anyhit_rays), int(st.outliers)))
     return _ORACLE[key]
@@ -132,6 +129,7 @@ def scenes():
 
 
 def same_bits(a, b):
+    """rgb of two float32 accumulators (test_dist1d.same_bits is another function: whole arrays, flattened, the first converted)"""
     return np.array_equal(np.asarray(a)[..., :3].view(np.uint32), np.asarray(b)[..., :3].view(np.uint32))
 
 

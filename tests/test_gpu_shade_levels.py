@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import bits, gpu_scene
+from helpers import bits, close_fraction, gpu_scene
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -87,17 +87,12 @@ def renders(level):
     return out
 
 
-def close_fraction(a, b, rel=1e-3):
-    """test_gpu_shading_fast.close_fraction: the share of pixels with every channel within rel |b| + 1e-6"""
-    return float(np.all(np.abs(a - b) <= rel * np.abs(b) + 1e-6, axis=-1).mean())
-
-
 @pytest.mark.parametrize("level", [1, 2, 3, 4])
 def test_each_level_runs_its_own_kernels_in_both_arithmetics(level):
     r, below = renders(level), renders(level - 1)
     exact, fast = r["exact"][0], r["fast"][0]
-    apart = close_fraction(exact, below["exact"][0])
-    close = close_fraction(fast, exact)
+    apart = close_fraction(exact, below["exact"][0], 1e-3)
+    close = close_fraction(fast, exact, 1e-3)
     print("level %d: EXACT agrees with level %d's on %.4f of the pixels, FAST with EXACT on %.4f" % (level, level - 1, apart, close))
     assert apart < 0.90                                   # the precondition: the level below is another image
     assert r["exact"][1].tobytes() == exact.tobytes()

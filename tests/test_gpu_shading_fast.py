@@ -15,8 +15,7 @@ import pytest
 
 import ag_pathtracer_amd as ag
 from ag_pathtracer_amd import tiles
-from helpers import gpu_context, gpu_scene, oracle_scene
-from oracle import binding as ob
+from helpers import close_fraction, gpu_context, gpu_scene, oracle_render, oracle_scene, tile_rows
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
@@ -53,36 +52,22 @@ def desc_of(name):
     return _DESC[name]
 
 
-def tile_rows(acc, H, tile):
-    x0, y0, w, h = tile
-    return acc[H - y0 - h:H - y0, x0:x0 + w, :3].reshape(-1, 3)
-
-
 def oracle_tile(name, spp, seed_base):
     _, W, H, tile, depth = SCENES[name]
-    o = oracle_scene(desc_of(name), depth)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        acc, st = o.render(W, H, spp, tile=tile, seed_base=seed_base, rng_mode=ob.RNG_PER_SAMPLE, threads=16)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-    return tile_rows(acc, H, tile), st
+    acc, st = oracle_render(desc_of(name), W, H, spp, depth, tile=tile, seed_base=seed_base, threads=16)
+    return tile_rows(acc, H, tile).reshape(-1, 3), st
 
 
 def gpu_tile(g, name, spp, seed_base, **kw):
     _, W, H, tile, depth = SCENES[name]
     acc, st = ag.PathTracer(depth).render_to_host(g, W, H, spp, tile=tile, seed_base=seed_base, **kw)
-    return tile_rows(acc, H, tile), st
+    return tile_rows(acc, H, tile).reshape(-1, 3), st
 
 
 def scene_in_mode(name, mode):
     g = gpu_scene(desc_of(name))
     g.set_shading_arith(mode)
     return g
-
-
-def close_fraction(a, b, rel):
-    return float(np.all(np.abs(a - b) <= rel * np.abs(b) + 1e-6, axis=-1).mean())
 
 
 # ---- L1 ------------------------------------------------------------------------------------------------------

@@ -4,7 +4,6 @@ yardstick: a constant image must equal no image, the blended value -- a pure fp3
 (tests/texture_filter_model.py) evaluates -- handed to the oracle as a plain material must render the same bits."""
 import copy
 import functools
-import os
 import re
 import subprocess
 
@@ -15,36 +14,14 @@ import ag_pathtracer_amd as ag
 import texture_filter_model as fm
 import texture_model as tm
 from denoise_features import host_features, primitive_table
-from helpers import bits, gpu_scene, oracle_scene
+from helpers import bits, build_cpp_example, gpu_scene, oracle_render, oracle_scene, render
 from oracle import binding as ob
+from texture_cases import K, PALETTE, palette_lights_and_camera, varying_lights_and_camera, varying_mesh, without_textures
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 R, M = ag.PARAM_ROUGHNESS, ag.PARAM_METALLIC
 BILINEAR, NEAREST = ag.FILTER_BILINEAR, ag.FILTER_NEAREST
 WRAPS = {"repeat": ag.WRAP_REPEAT, "clamp": ag.WRAP_CLAMP, "mirror": ag.WRAP_MIRROR}
-TEXTURE_OPS = ("texture", "material_texture", "material_param_texture", "texture_sampler")
-
-
-def oracle_render(desc, W, H, spp, max_depth=5):
-    o = oracle_scene(desc, max_depth)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        return o.render(W, H, spp, rng_mode=ob.RNG_PER_SAMPLE, threads=8)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-
-
-def without_textures(desc):
-    d = copy.copy(desc)
-    d.ops = [op for op in desc.ops if op[0] not in TEXTURE_OPS]
-    d.n_textures = 0
-    return d
-
-
-def render(g, W, H, spp, depth=5, arith="exact"):
-    g.set_shading_arith(arith)
-    return ag.PathTracer(depth).render_to_host(g, W, H, spp)
 
 
 def check_li_against_oracle(g, plain_desc, depth, n=1000):
@@ -144,21 +121,14 @@ def wrap_pair(wrap):
 
 
 def varying_scene(tex, filter, wrap_u, wrap_v):
-    """test_gpu_textures.varying_scene's construction: a heightfield whose uvs are a rotated, scaled copy of the grid's own and
-    leave [0, 1]"""
+    """test_gpu_textures.varying_scene's construction, the image with a sampler"""
     d = ag.SceneDesc("varying-filtered")
     m = d.add_material(ag.MAT_DISNEY, [.5, .5, .5], .7, .2)
-    v, n, t, idx = ag.scenes.heightfield(24)
-    c, s = np.cos(0.4), np.sin(0.4)
-    uv = np.stack([1.7 * (c * t[:, 0] - s * t[:, 1]) - 0.3, 1.3 * (s * t[:, 0] + c * t[:, 1]) + 0.2], 1).astype(F)
-    d.add_mesh(v, n, uv, idx, m, 1)
+    d.add_mesh(*varying_mesh(), m, 1)
     ti = d.add_texture(tex)
     d.set_material_texture(m, ti)
     d.set_texture_sampler(ti, filter, wrap_u, wrap_v)
-    d.add_area_light([0, 6, 0], 0.5, ag.scenes.KEY_LIGHT * F(30))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.3, 3.2, -3.6], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+    return varying_lights_and_camera(d)
 
 
 @functools.lru_cache(None)
@@ -234,9 +204,6 @@ def test_first_hit_albedo_is_the_model(image, filter, wrap):
 
 
 # ---- 3. tap selection along whole paths ------------------------------------------------------------------------------------
-K = 8
-PALETTE = np.array([[.80, .78, .70], [.85, .30, .25], [.20, .55, .80], [.95, .93, .88], [.35, .70, .30], [.90, .75, .35],
-                    [.55, .35, .75], [.25, .25, .28]], F)
 # (roughness, metallic) per plateau: metallic 0, 1 and .5 -- a wrong tap changes the lobe set and the ray count --, roughness below the
 # .001 clamp of alpha, .35 and 1
 PARAMS = np.array([[1.0, 0.0], [.35, 1.0], [0.0, .5], [.02, 0.0], [.6, .5], [0.0, 1.0], [.02, 1.0], [.5, .3]], F)
@@ -341,10 +308,7 @@ def plateau_scene(slot, wrap, textured, filter=BILINEAR):
         params = plateau_values(PARAMS, wrap)
         for k, (v, n, uv, idx) in enumerate(meshes):
             d.add_mesh(v, n, uv, idx, d.add_material(ag.MAT_DISNEY, PALETTE[3], float(params[k, 0]), float(params[k, 1])), 1)
-    d.add_area_light([0, 9, -2], 1.0, ag.scenes.KEY_LIGHT * F(60))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.5, 4.5, -7.5], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+    return palette_lights_and_camera(d)
 
 
 @pytest.mark.gpu
@@ -424,10 +388,7 @@ def corner_scene(wrap, textured):
             c, r, mt = values[k]
             m = d.add_material(ag.MAT_DISNEY, c, float(r), float(mt))
         d.add_mesh(v, n, np.zeros_like(uv), idx, m, 1)
-    d.add_area_light([0, 9, -2], 1.0, ag.scenes.KEY_LIGHT * F(60))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.5, 4.5, -7.5], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+    return palette_lights_and_camera(d)
 
 
 @pytest.mark.gpu
@@ -520,10 +481,7 @@ def mixed_scene(third, bilinear):
             d.add_mesh(v, n, uv, idx, mc, 1)
         else:
             d.add_mesh(v, n, rng.uniform(-1.5, 2.5, uv.shape).astype(F), idx, ma if k % 3 == 0 else mb, 1)
-    d.add_area_light([0, 9, -2], 1.0, ag.scenes.KEY_LIGHT * F(60))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.5, 4.5, -7.5], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+    return palette_lights_and_camera(d)
 
 
 @pytest.mark.gpu
@@ -557,22 +515,14 @@ def test_nearest_textures_in_a_sampled_scene():
 
 
 # ---- 7. the C++ adapter ----------------------------------------------------------------------------------------------------
-def build_example(tmp_path):
-    exe = str(tmp_path / "filtered_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "filtered_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_filtered_example_compiles_and_links(tmp_path):
-    build_example(tmp_path)
+    build_cpp_example(tmp_path, "filtered_scene")
 
 
 @pytest.mark.gpu
 def test_cpp_filtered_example_matches_python(tmp_path):
     W, H = 64, 48
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "filtered_scene")
     out_path = str(tmp_path / "out.bin")
     out = subprocess.check_output([exe, out_path, str(W), str(H)], timeout=300).decode()
     assert re.search(r"filtered %dx%d samples=4" % (W, H), out), out

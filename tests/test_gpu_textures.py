@@ -2,8 +2,6 @@
 textures; every test below is built so that it is still the yardstick: a texture of one colour must equal the plain material,
 a texel per mesh must equal a material per mesh, first hits are checked through the oracle's intersections and the numpy model
 of the lookup (tests/texture_model.py)."""
-import copy
-import os
 import re
 import subprocess
 
@@ -12,29 +10,15 @@ import pytest
 
 import ag_pathtracer_amd as ag
 import denoise_model as dm
+import texture_cases as tc
 import texture_model as tm
 from denoise_features import host_features, primitive_table
-from helpers import bits, gpu_context, gpu_scene, oracle_scene
+from helpers import bits, build_cpp_example, gpu_context, gpu_scene, oracle_render, oracle_scene
 from oracle import binding as ob
+from texture_cases import (K, PALETTE, SOUP, palette_meshes, soup_excluded_pixels, varying_lights_and_camera, varying_mesh,
+                           without_textures)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-def oracle_render(desc, W, H, spp, max_depth=5, **kw):
-    o = oracle_scene(desc, max_depth)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        return o.render(W, H, spp, rng_mode=ob.RNG_PER_SAMPLE, threads=8, **kw)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-
-
-def without_textures(desc):
-    d = copy.copy(desc)
-    d.ops = [op for op in desc.ops if op[0] not in ("texture", "material_texture")]
-    d.n_textures = 0
-    return d
 
 
 def with_constant_textures(desc, tw, th):
@@ -82,50 +66,25 @@ def test_constant_texture_equals_no_texture(which, size):
 
 
 # ---- 4. one texel per mesh = one material per mesh ---------------------------------------------------------------------
-K = 8
-PALETTE = np.array([[.80, .78, .70], [.85, .30, .25], [.20, .55, .80], [.95, .93, .88], [.35, .70, .30], [.90, .75, .35],
-                    [.55, .35, .75], [.25, .25, .28]], F)
 KINDS = [(ag.MAT_DISNEY, 1.0, 0.0), (ag.MAT_DISNEY, 0.35, 1.0), (ag.MAT_MIRROR, 0.0, 0.0), (ag.MAT_DIFFUSE_ONLY, 0.0, 0.0),
          (ag.MAT_DISNEY, 0.6, 0.5)]
 
 
-def palette_meshes(degenerate_uv):
-    """K meshes -- a floor and K - 1 blobs around the origin -- whose texture coordinates all lie inside texel k's footprint
-    [(k + .5) / K, (k + 1.5) / K) of a K x 1 palette, a tenth of a texel away from its ends"""
-    rng = np.random.RandomState(5)
-    meshes = []
-    for k in range(K):
-        if k == 0:
-            v, n, t, idx = ag.scenes.grid_mesh(lambda U, V: np.stack([-6 + 12 * U, -1 + 0 * U, -6 + 12 * V], -1), 6, 6)
-        else:
-            a = 2 * np.pi * k / (K - 1)
-            v, n, t, idx = ag.scenes.blob_mesh(10, 8, center=(2.4 * np.cos(a), -0.2 + 0.5 * (k % 3), 2.4 * np.sin(a)), radius=0.85, seed=k)
-        if degenerate_uv:
-            uv = np.broadcast_to(np.array([(k + 1.0) / K, 0.5], F), (len(v), 2)).copy()
-        else:
-            uv = np.stack([(k + 0.6 + 0.8 * rng.uniform(size=len(v))) / K, rng.uniform(0.1, 0.9, len(v))], 1).astype(F)
-        meshes.append((v, n, uv, idx))
-    return meshes
-
-
 def palette_scene(degenerate_uv, textured):
     d = ag.SceneDesc("palette")
-    meshes = palette_meshes(degenerate_uv)
     if textured:   # the materials are shared: one per kind, all pointing at the palette
         mats = [d.add_material(t, [.5, .5, .5], r, m) for (t, r, m) in KINDS]
         tex = d.add_texture(PALETTE[None])
         for m in mats:
             d.set_material_texture(m, tex)
-        for k, (v, n, uv, idx) in enumerate(meshes):
-            d.add_mesh(v, n, uv, idx, mats[k % len(KINDS)], 1)
-    else:          # one plain material per mesh, its colour the texel
-        for k, (v, n, uv, idx) in enumerate(meshes):
-            t, r, m = KINDS[k % len(KINDS)]
-            d.add_mesh(v, n, uv, idx, d.add_material(t, PALETTE[k], r, m), 1)
-    d.add_area_light([0, 9, -2], 1.0, ag.scenes.KEY_LIGHT * F(60))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.5, 4.5, -7.5], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+
+    def material(k):
+        if textured:
+            return mats[k % len(KINDS)]
+        t, r, m = KINDS[k % len(KINDS)]
+        return d.add_material(t, PALETTE[k], r, m)     # one plain material per mesh, its colour the texel
+
+    return tc.palette_scene(d, palette_meshes(degenerate_uv), material)
 
 
 def test_palette_footprints():
@@ -175,17 +134,10 @@ def test_one_texel_per_mesh_equals_one_material_per_mesh(degenerate_uv):
 def varying_scene():
     d = ag.SceneDesc("varying")
     m = d.add_material(ag.MAT_DISNEY, [.5, .5, .5], .7, .2)
-    v, n, t, idx = ag.scenes.heightfield(24)
-    # texture coordinates that vary smoothly and leave [0, 1]: a rotated, scaled copy of the grid's own
-    c, s = np.cos(0.4), np.sin(0.4)
-    uv = np.stack([1.7 * (c * t[:, 0] - s * t[:, 1]) - 0.3, 1.3 * (s * t[:, 0] + c * t[:, 1]) + 0.2], 1).astype(F)
-    d.add_mesh(v, n, uv, idx, m, 1)
+    d.add_mesh(*varying_mesh(), m, 1)
     tex = np.random.RandomState(21).uniform(0.05, 0.95, (16, 16, 3)).astype(F)
     d.set_material_texture(m, d.add_texture(tex))
-    d.add_area_light([0, 6, 0], 0.5, ag.scenes.KEY_LIGHT * F(30))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.3, 3.2, -3.6], [0, 0, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d, tex
+    return varying_lights_and_camera(d), tex
 
 
 def expected_first_hit_albedo(desc, tex, W, H):
@@ -243,56 +195,16 @@ def test_first_hit_albedo_is_the_texel():
 
 
 # ---- 6. variation inside a mesh, whole paths -----------------------------------------------------------------------------
-def triangle_soup():
-    """a bumpy floor and a blob as ONE mesh of T unshared triangles, each with its three uvs inside one palette texel"""
-    parts = [ag.scenes.heightfield(10, S=3.0), ag.scenes.blob_mesh(10, 8, center=(0.2, 1.3, 0.1), radius=0.9, seed=2)]
-    V, N, UV, colour = [], [], [], []
-    rng = np.random.RandomState(8)
-    for v, n, t, idx in parts:
-        tri = idx[:, 0].reshape(-1, 3)
-        for a in tri:
-            k = int(rng.randint(K))
-            V.append(v[a])
-            N.append(n[a])
-            UV.append(np.stack([(k + 0.6 + 0.8 * rng.uniform(size=3)) / K, rng.uniform(0.1, 0.9, 3)], 1))
-            colour.append(k)
-    return np.concatenate(V).astype(F), np.concatenate(N).astype(F), np.concatenate(UV).astype(F), np.array(colour)
-
-
 def soup_scene(mode):
     """mode "textured": the single mesh with the palette; "single" / "grouped": the single mesh / the triangles regrouped into K
     meshes by colour, all in ONE colour; "grouped_colours": regrouped with K plain materials"""
-    v, n, uv, colour = triangle_soup()
-    d = ag.SceneDesc("soup-" + mode)
-    one = PALETTE[0]
-
-    def mesh(sel, material):
-        ids = np.repeat(3 * np.nonzero(sel)[0], 3) + np.tile(np.arange(3), int(sel.sum()))
-        ix = np.arange(len(ids), dtype=np.int32)
-        d.add_mesh(v[ids], n[ids], uv[ids], np.stack([ix, ix, ix], 1), material, 1)
-
-    if mode in ("textured", "single"):
-        m = d.add_material(ag.MAT_DISNEY, one, 0.5, 0.3)
+    def material(d, k):
+        m = d.add_material(ag.MAT_DISNEY, PALETTE[k] if mode == "grouped_colours" else PALETTE[0], 0.5, 0.3)
         if mode == "textured":
             d.set_material_texture(m, d.add_texture(PALETTE[None]))
-        mesh(np.ones(len(colour), bool), m)
-    else:
-        for k in range(K):
-            m = d.add_material(ag.MAT_DISNEY, PALETTE[k] if mode == "grouped_colours" else one, 0.5, 0.3)
-            mesh(colour == k, m)
-    d.add_area_light([1, 7, -2], 0.8, ag.scenes.KEY_LIGHT * F(50))
-    d.add_uniform_infinite_light([.4, .45, .5])
-    d.set_camera([0.4, 3.4, -5.2], [0, 0.4, 0], [0, 1, 0], 1.0, 45.0, 0.0)
-    return d
+        return m
 
-
-SOUP = dict(W=64, H=64, spp=2, depth=5)
-
-
-def soup_excluded_pixels():
-    a, _ = oracle_render(soup_scene("single"), SOUP["W"], SOUP["H"], SOUP["spp"], SOUP["depth"])
-    b, _ = oracle_render(soup_scene("grouped"), SOUP["W"], SOUP["H"], SOUP["spp"], SOUP["depth"])
-    return (bits(a[..., :3]) != bits(b[..., :3])).any(-1)
+    return tc.soup_scene("soup-" + mode, material, grouped=mode.startswith("grouped"))
 
 
 def test_regrouping_changes_few_pixels_for_the_oracle():
@@ -387,22 +299,14 @@ def test_denoise_demodulates_the_textured_albedo():
 
 
 # ---- 9. the C++ adapter ---------------------------------------------------------------------------------------------------
-def build_example(tmp_path):
-    exe = str(tmp_path / "textured_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "textured_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_textured_example_compiles_and_links(tmp_path):
-    build_example(tmp_path)
+    build_cpp_example(tmp_path, "textured_scene")
 
 
 @pytest.mark.gpu
 def test_cpp_textured_example_matches_python(tmp_path):
     W, H = 96, 64
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "textured_scene")
     out_path = str(tmp_path / "out.bin")
     out = subprocess.check_output([exe, out_path, str(W), str(H)], timeout=300).decode()
     assert re.search(r"textured %dx%d samples=4" % (W, H), out), out

@@ -2,7 +2,6 @@
 agpt_transform_arrays(M, rest pose) -- the host twin that test_transform_arrays.py pins to the OBJ loader's arithmetic --, scene B the
 transform call; BVH bytes, hit records and renders must be bit-identical (device_update_cases.snapshot)."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -10,13 +9,12 @@ import pytest
 
 import ag_pathtracer_amd as ag
 import device_update_cases as dc
-from helpers import gpu_context, gpu_scene
+from helpers import build_cpp_example, gpu_context, gpu_scene
 from test_gpu_mesh_update_device import pair
 from test_transform_arrays import MATRICES
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # x and w exchanged: w = x, which is exactly 0 on the middle column of the grids -> Inf / NaN positions from finite input
 SWAP_XW = np.array([[0, 0, 0, 1], [0, 1, 0, 0], [0, 0, 1, 0], [1, 0, 0, 0]], F)
 
@@ -162,19 +160,11 @@ def frame_hash(rgb_words):
     return int(h)
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "rigid_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "rigid_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_rigid_example_matches_python(tmp_path):
     """examples/rigid_scene.cpp spins an octahedron over a backdrop with Scene::TransformMesh; the FNV-1a hashes it prints for its
     first and last frame are those of the same frames through the Python binding"""
     import re
-    exe = build_example(tmp_path)
+    exe = build_cpp_example(tmp_path, "rigid_scene")
     frames, w, h, spp = 4, 32, 24, 4
     out = subprocess.run([exe, str(frames), str(w), str(h)], check=True, capture_output=True, text=True, timeout=120).stdout
     got = {int(k): int(x, 16) for k, x in re.findall(r"frame (\d+) hash ([0-9a-f]{16})", out)}

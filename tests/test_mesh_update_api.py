@@ -11,7 +11,7 @@ import pytest
 import ag_pathtracer_amd as ag
 import bvh_refit_model as model
 import mesh_update_cases as cases
-from helpers import bits, signed_zero_grid
+from helpers import assert_exported, bits, build_cpp_example, signed_zero_grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "agpt.h")).read()
@@ -20,10 +20,10 @@ MESHES = [(pose, mpn) for pose in (0, 1) for mpn in (1, 4)]
 
 
 def test_symbols_declared_and_exported():
-    L = ag.lib()
-    for name in ("agpt_scene_update_mesh", "agpt_bvh_refit"):
+    names = ("agpt_scene_update_mesh", "agpt_bvh_refit")
+    assert_exported(names)
+    for name in names:
         assert re.search(r"\bint %s\s*\(" % name, HEADER), name
-        assert name in ag.EXPORTS and hasattr(L, name)
     assert re.search(r"AGPT_UPDATE_REFIT\s*=\s*0\b", HEADER) and ag.UPDATE_REFIT == 0
     assert re.search(r"AGPT_UPDATE_REBUILD\s*=\s*1\b", HEADER) and ag.UPDATE_REBUILD == 1
     assert "slower to" in HEADER and "REBUILD" in HEADER   # the documented consequence of refitting far from the build pose
@@ -120,14 +120,5 @@ def test_scaling_by_two_commutes_with_the_build(pose, mpn):
         assert ag.bvh_refit(base * F(2), idx, order, nodes).tobytes() == nodes2.tobytes()
 
 
-def build_example(tmp_path):
-    import subprocess
-    exe = str(tmp_path / "animated_scene")
-    lib = ag.library_path()
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "examples", "animated_scene.cpp"), "-o", exe, lib, "-Wl,-rpath," + os.path.dirname(lib)])
-    return exe
-
-
 def test_cpp_animated_example_compiles_and_links(tmp_path):
-    build_example(tmp_path)
+    build_cpp_example(tmp_path, "animated_scene")

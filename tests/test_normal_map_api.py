@@ -9,6 +9,7 @@ import pytest
 
 import ag_pathtracer_amd as ag
 import normal_map_model as nm
+from helpers import assert_exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -22,10 +23,8 @@ def test_symbols_are_declared_and_exported():
     assert re.search(r"int agpt_scene_set_material_normal_texture\(agpt_scene\*, int material, int texture, float scale\);", h)
     assert re.search(r"int agpt_kat_normal_map\(agpt_ctx\*, int n, const float\* ns3, const float\* ss3, const float\* rgb3, float scale, "
                      r"float\* ns_out3\);", h)
-    L = ag.lib()
-    for name in ("agpt_scene_set_material_normal_texture", "agpt_kat_normal_map"):
-        assert name in ag.EXPORTS and hasattr(L, name)
-    assert L.agpt_scene_set_material_normal_texture.argtypes == [C.c_void_p, C.c_int, C.c_int, C.c_float]
+    assert_exported(("agpt_scene_set_material_normal_texture", "agpt_kat_normal_map"))
+    assert ag.lib().agpt_scene_set_material_normal_texture.argtypes == [C.c_void_p, C.c_int, C.c_int, C.c_float]
 
 
 def test_null_arguments_are_invalid_with_a_message():

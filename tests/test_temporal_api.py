@@ -12,6 +12,7 @@ import numpy as np
 
 import ag_pathtracer_amd as ag
 import temporal_model as tm
+from helpers import assert_exported, struct_layout
 from oracle import binding as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,12 +26,8 @@ CAM_B = ([0.5, 1.3, -5.8], [0.1, 0, 0], [0, 1, 0], 37 / 29., 42.0, 0.0)
 
 
 def test_symbols_declared_and_exported():
+    assert_exported(("agpt_camera_vectors", "agpt_temporal_accumulate"))
     header = open(os.path.join(ROOT, "include", "agpt.h")).read()
-    L = ag.lib()
-    for name in ("agpt_camera_vectors", "agpt_temporal_accumulate"):
-        assert re.search(r"\b%s\s*\(" % name, header), name
-        assert name in ag.EXPORTS
-        assert hasattr(L, name)
     assert "agpt_temporal.hip" in b.SOURCES
     assert "agpt_temporal.h" in b.HEADERS
     for macro, value, model in (("AGPT_TEMPORAL_DEPTH_TOL", ag.TEMPORAL_DEPTH_TOL, tm.DEPTH_TOL),
@@ -40,24 +37,7 @@ def test_symbols_declared_and_exported():
 
 
 def test_struct_layout_matches_ctypes(tmp_path):
-    cname, cls = "agpt_temporal_params", ag.TemporalParams
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "agpt.h"', "int main(void) {",
-             'printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname)]
-    for f, _ in cls._fields_:
-        lines.append('printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f))
-    lines.append("return 0; }")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = str(tmp_path / "probe")
-    subprocess.check_call(["gcc", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
-    got = {}
-    for ln in subprocess.check_output([exe]).decode().split("\n"):
-        if ln:
-            s, f, v = ln.split()
-            got[f] = int(v)
-    assert got["sizeof"] == C.sizeof(cls)
-    for f, _ in cls._fields_:
-        assert got[f] == getattr(cls, f).offset, f
+    struct_layout(tmp_path, {"agpt_temporal_params": ag.TemporalParams})
 
 
 def params(**kw):

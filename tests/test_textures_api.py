@@ -9,6 +9,7 @@ import pytest
 
 import ag_pathtracer_amd as ag
 import texture_model as tm
+from helpers import assert_exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -23,9 +24,8 @@ def test_symbols_are_declared_and_exported():
     h = header()
     assert re.search(r"int agpt_scene_add_texture\(agpt_scene\*, const float\* rgb, int width, int height\);", h)
     assert re.search(r"int agpt_scene_set_material_texture\(agpt_scene\*, int material, int texture\);", h)
+    assert_exported(("agpt_scene_add_texture", "agpt_scene_set_material_texture"))
     L = ag.lib()
-    for name in ("agpt_scene_add_texture", "agpt_scene_set_material_texture"):
-        assert name in ag.EXPORTS and hasattr(L, name)
     assert L.agpt_scene_add_texture.argtypes == [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int]
     assert L.agpt_scene_set_material_texture.argtypes == [C.c_void_p, C.c_int, C.c_int]
 

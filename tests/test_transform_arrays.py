@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
+from helpers import assert_exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "agpt.h")).read()
@@ -48,10 +49,10 @@ MATRICES = {
 
 
 def test_symbols_declared_and_exported():
-    L = ag.lib()
-    for name in ("agpt_transform_arrays", "agpt_scene_transform_mesh", "agpt_scene_update_mesh_device"):
+    names = ("agpt_transform_arrays", "agpt_scene_transform_mesh", "agpt_scene_update_mesh_device")
+    assert_exported(names)
+    for name in names:
         assert re.search(r"\bint %s\s*\(" % name, HEADER), name
-        assert name in ag.EXPORTS and hasattr(L, name)
 
 
 @pytest.mark.parametrize("with_normals", [True, False])

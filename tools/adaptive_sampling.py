@@ -31,6 +31,7 @@ def rmse(img, ref):
 def rmse_display(img, ref):
     """RMSE of the radiance clamped to [0, 1] (what CopyToSurface can show): the linear RMSE is dominated by a few very bright
     pixels (directly seen emitters, fireflies)"""
+    # (tools/denoise_quality.py has its own rmse_display)
     return rmse(np.clip(img, 0, 1), np.clip(ref, 0, 1))
 
 

@@ -23,6 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import ag_pathtracer_amd as ag  # noqa: E402
+from adaptive_sampling import rmse  # noqa: E402  (tools/ is on the path of a script run from it)
 
 W, H = 1920, 1080
 ITER = 5
@@ -49,11 +50,8 @@ class HipEvents:
         return float(ms.value)
 
 
-def rmse(img, ref):
-    return float(np.sqrt(np.mean((img.astype(np.float64) - ref) ** 2)))
-
-
 def rmse_display(img, ref):
+    # (tools/adaptive_sampling.py has its own rmse_display, with the reason for the clamp)
     return rmse(np.clip(img, 0, 1), np.clip(ref, 0, 1))
 
 
