@@ -23,11 +23,11 @@ SHADE_UNITS = [("", 0, 0, 4), ("_fast", 0, 1, 4), ("_textured", 1, 0, 4), ("_tex
 # against 118.1 ms at four (FAST: 111.1 against 112.8 ms; profiles/normal_map_c3.json).
 SHADE_FLAGS = ["-mllvm", "-disable-machine-licm"]
 SHADE_SOURCES = ["agpt_shade_kernels%s.hip" % suffix for suffix, _, _, _ in SHADE_UNITS]
-SOURCES = ["agpt_api.hip"] + SHADE_SOURCES + ["agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip", "agpt_denoise.hip", "agpt_temporal.hip",
-                                               "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+SOURCES = ["agpt_api.hip"] + SHADE_SOURCES + ["agpt_scene_api.hip", "agpt_kat.hip", "agpt_comm.hip", "agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip",
+                                               "agpt_denoise.hip", "agpt_temporal.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {src: SHADE_FLAGS + ["-DAGPT_SHADE_WAVES=%d" % waves] for src, (_, _, _, waves) in zip(SHADE_SOURCES, SHADE_UNITS)}
-HEADERS = ["agpt_math.h", "agpt_scene.h", "agpt_trace.h", "agpt_shade.h", "agpt_wavefront.h", "agpt_kernels.h", "agpt_shade_kernels.h", "agpt_shade_arith.h",
-           "agpt_host_scene.hpp", "agpt_bvh_arith.h", "agpt_records.h", "agpt_bvh_device.h", "agpt_update.h", "agpt_transform.h", "agpt_adaptive.h", "agpt_denoise.h", "agpt_temporal.h", os.path.join("..", "..", "include", "agpt.h")]
+# every header: an edit to any of them rebuilds the library (needs_build)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [os.path.join("..", "..", "include", "agpt.h")]
 # -ffp-contract=off + no fast-math: every fp32 op rounds on its own, exactly as written (parity with the oracle);
 # explicit __builtin_fmaf calls (Markstein division in agpt_trace.h) stay fused.
 # -fno-slp-vectorize: the SLP pass packs adjacent f32 adds/muls into v_pk_*_f32, which on gfx950 cost more than the two

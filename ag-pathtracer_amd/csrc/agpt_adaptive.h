@@ -1,5 +1,5 @@
-// agpt_adaptive.h -- host-side launchers of the adaptive-sampling unit (agpt_adaptive.hip), used by agpt_render_adaptive and
-// agpt_resolve_counts in agpt_api.hip.
+// agpt_adaptive.h -- host-side launchers of the adaptive-sampling unit (agpt_adaptive.hip, which also defines agpt_resolve_counts),
+// used by agpt_render_adaptive in agpt_api.hip.
 #pragma once
 
 #include "agpt_wavefront.h"
@@ -34,5 +34,4 @@ void launch_generate_list(hipStream_t stream, const DevScene& sc, const RenderCo
                           const float4* accum, const PathBuffers& pb, const Queues& q);
 void launch_accumulate_list(hipStream_t stream, const RenderConsts& rc, const uint32_t* list, uint32_t a0, uint32_t na, const PathBuffers& pb,
                             float4* accum, float* moment2, DevCounters* counters);
-void launch_resolve_counts(hipStream_t stream, const float4* accum, int n, uint32_t* out);
 }  // namespace agpt

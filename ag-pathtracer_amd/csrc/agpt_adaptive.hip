@@ -11,6 +11,9 @@
 #include <hip/hip_runtime.h>
 
 #include "agpt_adaptive.h"
+#include "agpt_internal.h"
+
+using agpt::fail;
 
 namespace {
 
@@ -216,8 +219,21 @@ void launch_accumulate_list(hipStream_t stream, const RenderConsts& rc, const ui
                             float4* accum, float* moment2, DevCounters* counters) {
     hipLaunchKernelGGL(k_accumulate_list, agpt_blocks(na), dim3(AGPT_BLOCK), 0, stream, rc, list, a0, na, pb, accum, moment2, counters);
 }
-void launch_resolve_counts(hipStream_t stream, const float4* accum, int n, uint32_t* out) {
-    hipLaunchKernelGGL(k_resolve_counts, agpt_blocks((uint64_t)n), dim3(AGPT_BLOCK), 0, stream, accum, n, out);
-}
 
 }  // namespace agpt
+
+extern "C" {
+
+int agpt_resolve_counts(agpt_ctx* c, const float* accum_dev, int n_pixels, uint32_t* out_rgb) {
+    if (!c || !accum_dev || !out_rgb || n_pixels <= 0) return fail(AGPT_ERR_INVALID, "agpt_resolve_counts: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<uint32_t> d;
+    HIP_TRY(d.alloc((size_t)n_pixels));
+    hipLaunchKernelGGL(k_resolve_counts, agpt_blocks((uint64_t)n_pixels), dim3(AGPT_BLOCK), 0, c->stream, (const float4*)accum_dev, n_pixels, d.p);
+    HIP_TRY(hipGetLastError());
+    if (const int rc = d.out(out_rgb, (size_t)n_pixels, &c->stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AGPT_OK;
+}
+
+}  // extern "C"

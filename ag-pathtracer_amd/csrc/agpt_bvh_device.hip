@@ -27,7 +27,7 @@
 #include "agpt_host_scene.hpp"
 
 namespace agpt {
-int report_error(int code, const std::string& msg);  // agpt_api.hip
+int fail(int code, const std::string& msg);   // agpt_api.hip: the message of agpt_last_error
 }
 
 namespace {
@@ -729,7 +729,7 @@ namespace agpt {
     do {                                                                                                      \
         hipError_t e_ = (expr);                                                                               \
         if (e_ != hipSuccess) {                                                                               \
-            err = report_error(AGPT_ERR_DEVICE, std::string("agpt_bvh_build_device: ") + #expr + ": " +       \
+            err = fail(AGPT_ERR_DEVICE, std::string("agpt_bvh_build_device: ") + #expr + ": " +       \
                                                     hipGetErrorString(e_));                                   \
             goto done;                                                                                        \
         }                                                                                                     \
@@ -783,7 +783,7 @@ int build_bvh_device(hipStream_t stream, const float* vertices, int n_vertices, 
         const hipError_t e = hipMalloc((void**)&ar.base, probe.used);
         if (e != hipSuccess) {
             ar.base = nullptr;
-            return report_error(AGPT_ERR_NOMEM, std::string("agpt_bvh_build_device: hipMalloc: ") + hipGetErrorString(e));
+            return fail(AGPT_ERR_NOMEM, std::string("agpt_bvh_build_device: hipMalloc: ") + hipGetErrorString(e));
         }
     }
     dV = ar.take<float>((size_t)3 * n_vertices);
@@ -858,7 +858,7 @@ int build_bvh_device(hipStream_t stream, const float* vertices, int n_vertices, 
         BVH_TRY(hipMemcpyAsync(hc, B.ctr, sizeof(Ctr), hipMemcpyDeviceToHost, stream));
         BVH_TRY(hipStreamSynchronize(stream));
         if (hc->overflow) {
-            err = report_error(AGPT_ERR_LIMIT, "agpt_bvh_build_device: scratch capacity exceeded");
+            err = fail(AGPT_ERR_LIMIT, "agpt_bvh_build_device: scratch capacity exceeded");
             goto done;
         }
         ranges.push_back(hc->records);
@@ -883,7 +883,7 @@ int build_bvh_device(hipStream_t stream, const float* vertices, int n_vertices, 
         BVH_TRY(hipMemcpyAsync(hc, B.ctr, sizeof(Ctr), hipMemcpyDeviceToHost, stream));
         BVH_TRY(hipStreamSynchronize(stream));
         if (total < 1 || total > 2 * n - 1) {
-            err = report_error(AGPT_ERR_DEVICE, "agpt_bvh_build_device: inconsistent node count " + std::to_string(total));
+            err = fail(AGPT_ERR_DEVICE, "agpt_bvh_build_device: inconsistent node count " + std::to_string(total));
             goto done;
         }
         if (nodes_out)

@@ -1,5 +1,5 @@
-// agpt_denoise.h -- host-side launchers of the feature-buffer / denoiser unit (agpt_denoise.hip), used by agpt_render_features and
-// agpt_denoise in agpt_api.hip.
+// agpt_denoise.h -- what the feature-buffer / denoiser unit (agpt_denoise.hip, which also defines agpt_denoise) shares: the launchers
+// agpt_render_features (agpt_api.hip) calls, and the tiling, constants and pixel-centre ray that agpt_temporal.hip uses as well.
 #pragma once
 
 #include "agpt_wavefront.h"
@@ -34,9 +34,4 @@ void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderCon
 // level (agpt_scene_commit), which picks the feature kernel
 void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, const RenderConsts& rc, const float4* colors,
                      const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth);
-// state = (c.rgb, v); v = -1 marks a pixel without samples
-void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,
-                            float4* state);
-void launch_denoise_pass(hipStream_t stream, const DenoiseConsts& dc, const float4* state_in, const float4* albedo,
-                         const float4* normal_depth, float4* state_out);
 }  // namespace agpt

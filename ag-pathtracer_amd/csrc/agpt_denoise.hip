@@ -11,8 +11,13 @@
 // reproduces it operation by operation.  Compiled with the library's common flags (-ffp-contract=off, IEEE divide / sqrt).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 #include "agpt_denoise.h"
+#include "agpt_internal.h"
 #include "agpt_shade.h"
+
+using agpt::fail;
 
 #define AGPT_DN_ALBEDO_FLOOR 1e-3f
 #define AGPT_DN_DEPTH_FLOOR 1e-3f
@@ -271,16 +276,50 @@ void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, c
     }
     hipLaunchKernelGGL(kernel, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
-void launch_denoise_prepare(hipStream_t stream, const DenoiseConsts& dc, const float4* accum, const float* moment2, const float4* albedo,
-                            float4* state) {
-    hipLaunchKernelGGL(k_denoise_prepare, agpt_blocks((uint64_t)dc.W * (uint64_t)dc.H), dim3(AGPT_BLOCK), 0, stream, dc, accum, moment2, albedo,
-                       state);
-}
-void launch_denoise_pass(hipStream_t stream, const DenoiseConsts& dc, const float4* state_in, const float4* albedo,
-                         const float4* normal_depth, float4* state_out) {
-    static_assert(AGPT_DN_TX * AGPT_DN_TY == AGPT_BLOCK, "one thread per tile pixel");
-    const dim3 g((unsigned)((dc.W + AGPT_DN_TX - 1) / AGPT_DN_TX), (unsigned)((dc.H + AGPT_DN_TY - 1) / AGPT_DN_TY));
-    hipLaunchKernelGGL(k_denoise_pass, g, dim3(AGPT_BLOCK), 0, stream, dc, state_in, albedo, normal_depth, state_out);
-}
 
 }  // namespace agpt
+
+extern "C" {
+
+// k_denoise_prepare, then `iterations` passes that ping-pong between out_dev and the context's scratch buffer so that the last one,
+// which also re-modulates and sets w = 1, lands in out_dev.
+int agpt_denoise(agpt_ctx* c, const agpt_denoise_params* p, const float* accum_dev, const float* moment2_dev, const float* albedo_dev,
+                 const float* normal_depth_dev, float* out_dev) {
+    if (!p) return fail(AGPT_ERR_INVALID, "agpt_denoise: NULL argument");
+    if (p->width <= 0 || p->height <= 0 || (uint64_t)p->width * (uint64_t)p->height > 0x7FFFFFFFull)
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: bad film size");
+    if (p->iterations < 1 || p->iterations > 8) return fail(AGPT_ERR_INVALID, "agpt_denoise: iterations must be in 1..8");
+    if (p->demodulate != 0 && p->demodulate != 1) return fail(AGPT_ERR_INVALID, "agpt_denoise: demodulate must be 0 or 1");
+    if (!(p->sigma_z > 0.f) || !(p->sigma_n > 0.f) || !(p->sigma_l > 0.f) || std::isinf(p->sigma_z) || std::isinf(p->sigma_n) ||
+        std::isinf(p->sigma_l))
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: sigma_z, sigma_n and sigma_l must be positive and finite");
+    if (!c || !accum_dev || !moment2_dev || !albedo_dev || !normal_depth_dev || !out_dev)
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: NULL argument");
+    if (out_dev == accum_dev || out_dev == moment2_dev || out_dev == albedo_dev || out_dev == normal_depth_dev)
+        return fail(AGPT_ERR_INVALID, "agpt_denoise: out_dev aliases an input");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    const int rc = c->denoise_state.ensure(n);
+    if (rc) return rc;
+    DenoiseConsts dc{};
+    dc.W = p->width; dc.H = p->height; dc.demodulate = p->demodulate;
+    dc.sigma_z = p->sigma_z; dc.sigma_n = p->sigma_n; dc.sigma_l = p->sigma_l;
+    float4* buf[2] = {(float4*)out_dev, c->denoise_state.p};
+    int cur = p->iterations & 1;   // pass i reads buf[cur] and writes the other: an even number of passes starts in out_dev
+    // state = (c.rgb, v); v = -1 marks a pixel without samples
+    hipLaunchKernelGGL(k_denoise_prepare, agpt_blocks(n), dim3(AGPT_BLOCK), 0, c->stream, dc, (const float4*)accum_dev, moment2_dev,
+                       (const float4*)albedo_dev, buf[cur]);
+    static_assert(AGPT_DN_TX * AGPT_DN_TY == AGPT_BLOCK, "one thread per tile pixel");
+    const dim3 tiles((unsigned)((dc.W + AGPT_DN_TX - 1) / AGPT_DN_TX), (unsigned)((dc.H + AGPT_DN_TY - 1) / AGPT_DN_TY));
+    for (int i = 0; i < p->iterations; ++i, cur ^= 1) {
+        dc.step = 1 << i;
+        dc.last = i == p->iterations - 1;
+        hipLaunchKernelGGL(k_denoise_pass, tiles, dim3(AGPT_BLOCK), 0, c->stream, dc, (const float4*)buf[cur], (const float4*)albedo_dev,
+                           (const float4*)normal_depth_dev, buf[cur ^ 1]);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AGPT_OK;
+}
+
+}  // extern "C"

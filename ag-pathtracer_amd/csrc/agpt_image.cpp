@@ -18,7 +18,7 @@
 #include "../../include/agpt.h"
 
 namespace agpt {
-int report_error(int code, const std::string& msg);  // agpt_api.hip
+int fail(int code, const std::string& msg);   // agpt_api.hip: the message of agpt_last_error
 }
 
 namespace {
@@ -57,7 +57,7 @@ void put_chunk(std::vector<uint8_t>& out, const char tag[4], const std::vector<u
 }  // namespace
 
 extern "C" int agpt_write_png(const char* path, const uint32_t* rgb, int width, int height) {
-    if (!path || !rgb || width <= 0 || height <= 0) return agpt::report_error(AGPT_ERR_INVALID, "agpt_write_png: bad argument");
+    if (!path || !rgb || width <= 0 || height <= 0) return agpt::fail(AGPT_ERR_INVALID, "agpt_write_png: bad argument");
     // scanlines: filter byte 0 + RGB
     const size_t stride = 1 + 3 * (size_t)width;
     std::vector<uint8_t> raw(stride * height);
@@ -100,17 +100,17 @@ extern "C" int agpt_write_png(const char* path, const uint32_t* rgb, int width, 
     put_chunk(out, "IDAT", z);
     put_chunk(out, "IEND", {});
     FILE* f = std::fopen(path, "wb");
-    if (!f) return agpt::report_error(AGPT_ERR_IO, std::string("agpt_write_png: cannot open ") + path);
+    if (!f) return agpt::fail(AGPT_ERR_IO, std::string("agpt_write_png: cannot open ") + path);
     const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
     std::fclose(f);
-    return ok ? AGPT_OK : agpt::report_error(AGPT_ERR_IO, std::string("agpt_write_png: short write to ") + path);
+    return ok ? AGPT_OK : agpt::fail(AGPT_ERR_IO, std::string("agpt_write_png: short write to ") + path);
 }
 
 extern "C" int agpt_write_pfm(const char* path, const float* accum_host, int width, int height, int samples) {
     if (!path || !accum_host || width <= 0 || height <= 0 || samples <= 0)
-        return agpt::report_error(AGPT_ERR_INVALID, "agpt_write_pfm: bad argument");
+        return agpt::fail(AGPT_ERR_INVALID, "agpt_write_pfm: bad argument");
     FILE* f = std::fopen(path, "wb");
-    if (!f) return agpt::report_error(AGPT_ERR_IO, std::string("agpt_write_pfm: cannot open ") + path);
+    if (!f) return agpt::fail(AGPT_ERR_IO, std::string("agpt_write_pfm: cannot open ") + path);
     std::fprintf(f, "PF\n%d %d\n-1.0\n", width, height);  // negative scale = little endian
     std::vector<float> row(3 * (size_t)width);
     const float inv = 1.0f / (float)samples;
@@ -122,7 +122,7 @@ extern "C" int agpt_write_pfm(const char* path, const float* accum_host, int wid
         ok = std::fwrite(row.data(), 4, row.size(), f) == row.size();
     }
     std::fclose(f);
-    return ok ? AGPT_OK : agpt::report_error(AGPT_ERR_IO, std::string("agpt_write_pfm: short write to ") + path);
+    return ok ? AGPT_OK : agpt::fail(AGPT_ERR_IO, std::string("agpt_write_pfm: short write to ") + path);
 }
 
 
@@ -178,7 +178,7 @@ inline void rgbe_to_rgb(const uint8_t q[4], float* rgb) {
     rgb[2] = (float)q[2] * scale;
 }
 
-int hdr_fail(const std::string& why) { return agpt::report_error(AGPT_ERR_INVALID, "agpt_hdr_parse: " + why); }
+int hdr_fail(const std::string& why) { return agpt::fail(AGPT_ERR_INVALID, "agpt_hdr_parse: " + why); }
 
 // the rest of the image as 4-byte pixels, starting at pixel index `first`
 bool hdr_flat_pixels(ByteCursor& in, float* rgb, size_t first, size_t n_pixels) {
@@ -193,7 +193,7 @@ bool hdr_flat_pixels(ByteCursor& in, float* rgb, size_t first, size_t n_pixels) 
 }  // namespace
 
 extern "C" int agpt_hdr_parse(const void* bytes, size_t length, int* width_out, int* height_out, float** rgb_out) {
-    if (!bytes || !width_out || !height_out || !rgb_out) return agpt::report_error(AGPT_ERR_INVALID, "agpt_hdr_parse: bad argument");
+    if (!bytes || !width_out || !height_out || !rgb_out) return agpt::fail(AGPT_ERR_INVALID, "agpt_hdr_parse: bad argument");
     *rgb_out = nullptr;
     ByteCursor in{(const uint8_t*)bytes, (const uint8_t*)bytes + length};
     // stbi__hdr_test: the signature line must be exactly one of these, '\n' included
@@ -221,7 +221,7 @@ extern "C" int agpt_hdr_parse(const void* bytes, size_t length, int* width_out, 
     if ((long long)width * height * 12 > (long long)INT_MAX) return hdr_fail("image is too large (stb_image limits w*h*12 to INT_MAX)");
     const size_t n_pixels = (size_t)width * height;
     float* rgb = (float*)malloc(n_pixels * 3 * sizeof(float));
-    if (!rgb) return agpt::report_error(AGPT_ERR_NOMEM, "agpt_hdr_parse: out of memory");
+    if (!rgb) return agpt::fail(AGPT_ERR_NOMEM, "agpt_hdr_parse: out of memory");
     auto give_up = [&](const char* why) {
         free(rgb);
         return hdr_fail(why);
@@ -270,9 +270,9 @@ extern "C" int agpt_hdr_parse(const void* bytes, size_t length, int* width_out, 
 }
 
 extern "C" int agpt_hdr_load(const char* path, int* width_out, int* height_out, float** rgb_out) {
-    if (!path) return agpt::report_error(AGPT_ERR_INVALID, "agpt_hdr_load: bad argument");
+    if (!path) return agpt::fail(AGPT_ERR_INVALID, "agpt_hdr_load: bad argument");
     FILE* f = std::fopen(path, "rb");
-    if (!f) return agpt::report_error(AGPT_ERR_IO, std::string("agpt_hdr_load: cannot open ") + path);
+    if (!f) return agpt::fail(AGPT_ERR_IO, std::string("agpt_hdr_load: cannot open ") + path);
     std::vector<uint8_t> data;
     uint8_t chunk[1 << 16];
     size_t got;

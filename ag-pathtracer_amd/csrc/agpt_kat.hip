@@ -1,0 +1,150 @@
+// agpt_kat.hip -- the known-answer entry points of include/agpt.h and their kernels: one piece of the device arithmetic each (the
+// BSDF functions and the normal-map perturbation of agpt_shade.h, the environment map's sampler, the RNG streams), run on caller-supplied
+// cases, one lane per case.  The exact arithmetic; the fast-arithmetic BSDF kernels are compiled in their own unit
+// (agpt_shade_kernels_fast.hip).
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "agpt_internal.h"
+#include "agpt_shade.h"
+
+using agpt::fail;
+
+// known-answer kernels (one lane per case)
+__global__ void k_kat_bsdf_eval(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ wi3,
+                                float* __restrict__ f3o, float* __restrict__ pdfo) {
+    kat_bsdf_eval_lane(sc, material, n, wo3, wi3, f3o, pdfo);
+}
+__global__ void k_kat_bsdf_sample(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ u2,
+                                  float* __restrict__ wi3o, float* __restrict__ f3o, float* __restrict__ pdfo,
+                                  int32_t* __restrict__ speco) {
+    kat_bsdf_sample_lane(sc, material, n, wo3, u2, wi3o, f3o, pdfo, speco);
+}
+// known-answer kernel: Distribution1D::SampleContinuous (env_sample_continuous) for k draws, one lane each
+// agpt_kat_normal_map: surface_apply_normal_map (agpt_shade.h) alone, one lane per item
+__global__ void k_kat_normal_map(int n, const float* __restrict__ ns3, const float* __restrict__ ss3, const float* __restrict__ rgb3, float scale,
+                                 float* __restrict__ out3) {
+    kat_normal_map_lane(n, ns3, ss3, rgb3, scale, out3);
+}
+__global__ void k_kat_distribution1d(DevEnv e, const float* __restrict__ u, int k, float* __restrict__ x_out, float* __restrict__ pdf_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= k) return;
+    float pdf;
+    x_out[i] = env_sample_continuous(e, u[i], &pdf);
+    pdf_out[i] = pdf;
+}
+__global__ void k_kat_rng(uint32_t pixel, uint32_t wh, uint32_t sample, uint32_t seed_base, int n, float* __restrict__ out,
+                          uint32_t* __restrict__ seed_out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    uint32_t s = sample_seed(pixel, wh, sample, seed_base);
+    *seed_out = s;
+    for (int i = 0; i < n; i++) out[i] = rng_float(s);
+}
+
+// what follows every launch here: its launch error, then its completion
+static int launched(agpt_ctx* c) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AGPT_OK;
+}
+
+extern "C" {
+
+int agpt_kat_bsdf_eval(agpt_scene* s, int material, int n, const float* wo3, const float* wi3, float* f3_out, float* pdf_out) {
+    if (!s || !s->committed || material < 0 || material >= (int)s->materials.size() || n <= 0 || !wo3 || !wi3 || !f3_out || !pdf_out)
+        return fail(AGPT_ERR_INVALID, "agpt_kat_bsdf_eval: bad argument");
+    agpt_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> d_wo, d_wi, d_f, d_p;
+    int rc;
+    if ((rc = d_wo.in(wo3, 3 * (size_t)n)) || (rc = d_wi.in(wi3, 3 * (size_t)n))) return rc;
+    HIP_TRY(d_f.alloc(3 * (size_t)n));
+    HIP_TRY(d_p.alloc((size_t)n));
+    if (s->shading_arith == AGPT_SHADING_FAST)
+        agpt::launch_kat_bsdf_eval_fast(c->stream, s->dev, material, n, d_wo.p, d_wi.p, d_f.p, d_p.p);
+    else
+        hipLaunchKernelGGL(k_kat_bsdf_eval, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, material, n, d_wo.p, d_wi.p, d_f.p, d_p.p);
+    if ((rc = launched(c)) || (rc = d_f.out(f3_out, 3 * (size_t)n))) return rc;
+    return d_p.out(pdf_out, (size_t)n);
+}
+
+int agpt_kat_bsdf_sample(agpt_scene* s, int material, int n, const float* wo3, const float* u2, float* wi3_out, float* f3_out,
+                         float* pdf_out, int32_t* specular_out) {
+    if (!s || !s->committed || material < 0 || material >= (int)s->materials.size() || n <= 0 || !wo3 || !u2 || !wi3_out ||
+        !f3_out || !pdf_out || !specular_out)
+        return fail(AGPT_ERR_INVALID, "agpt_kat_bsdf_sample: bad argument");
+    agpt_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> d_wo, d_u, d_wi, d_f, d_p;
+    DevBuf<int32_t> d_s;
+    int rc;
+    if ((rc = d_wo.in(wo3, 3 * (size_t)n)) || (rc = d_u.in(u2, 2 * (size_t)n))) return rc;
+    HIP_TRY(d_wi.alloc(3 * (size_t)n));
+    HIP_TRY(d_f.alloc(3 * (size_t)n));
+    HIP_TRY(d_p.alloc((size_t)n));
+    HIP_TRY(d_s.alloc((size_t)n));
+    if (s->shading_arith == AGPT_SHADING_FAST)
+        agpt::launch_kat_bsdf_sample_fast(c->stream, s->dev, material, n, d_wo.p, d_u.p, d_wi.p, d_f.p, d_p.p, d_s.p);
+    else
+        hipLaunchKernelGGL(k_kat_bsdf_sample, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, material, n, d_wo.p, d_u.p, d_wi.p, d_f.p,
+                           d_p.p, d_s.p);
+    if ((rc = launched(c)) || (rc = d_wi.out(wi3_out, 3 * (size_t)n)) || (rc = d_f.out(f3_out, 3 * (size_t)n)) ||
+        (rc = d_p.out(pdf_out, (size_t)n)))
+        return rc;
+    return d_s.out(specular_out, (size_t)n);
+}
+
+int agpt_kat_normal_map(agpt_ctx* c, int n, const float* ns3, const float* ss3, const float* rgb3, float scale, float* ns_out3) {
+    if (!c || n <= 0 || !ns3 || !ss3 || !rgb3 || !ns_out3) return fail(AGPT_ERR_INVALID, "agpt_kat_normal_map: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> d_ns, d_ss, d_rgb, d_o;
+    int rc;
+    if ((rc = d_ns.in(ns3, 3 * (size_t)n)) || (rc = d_ss.in(ss3, 3 * (size_t)n)) || (rc = d_rgb.in(rgb3, 3 * (size_t)n))) return rc;
+    HIP_TRY(d_o.alloc(3 * (size_t)n));
+    hipLaunchKernelGGL(k_kat_normal_map, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_ns.p, d_ss.p, d_rgb.p, scale, d_o.p);
+    if ((rc = launched(c))) return rc;
+    return d_o.out(ns_out3, 3 * (size_t)n);
+}
+
+int agpt_kat_rng(agpt_ctx* c, uint32_t pixel, uint32_t wh, uint32_t sample, uint32_t seed_base, int n, float* out,
+                 uint32_t* seed_out) {
+    if (!c || n <= 0 || !out || !seed_out) return fail(AGPT_ERR_INVALID, "agpt_kat_rng: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> d_o;
+    DevBuf<uint32_t> d_s;
+    HIP_TRY(d_o.alloc((size_t)n));
+    HIP_TRY(d_s.alloc(1));
+    hipLaunchKernelGGL(k_kat_rng, dim3(1), dim3(64), 0, c->stream, pixel, wh, sample, seed_base, n, d_o.p, d_s.p);
+    int rc;
+    if ((rc = launched(c)) || (rc = d_o.out(out, (size_t)n))) return rc;
+    return d_s.out(seed_out, 1);
+}
+
+int agpt_kat_distribution1d(agpt_ctx* c, const float* func, int n, const float* u, int k, float* cdf_out, float* func_int_out,
+                            float* x_out, float* pdf_out) {
+    if (!c || !func || n <= 0 || k < 0 || (k && (!u || !x_out || !pdf_out)))
+        return fail(AGPT_ERR_INVALID, "agpt_kat_distribution1d: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<float> cdf((size_t)n + 1);
+    const float func_int = agpt::build_distribution1d(func, n, cdf.data());
+    if (cdf_out) memcpy(cdf_out, cdf.data(), 4 * cdf.size());
+    if (func_int_out) *func_int_out = func_int;
+    if (k == 0) return AGPT_OK;
+    DevBuf<float> d_f, d_c, d_u, d_x, d_p;
+    int rc;
+    if ((rc = d_f.in(func, (size_t)n)) || (rc = d_c.in(cdf.data(), cdf.size())) || (rc = d_u.in(u, (size_t)k))) return rc;
+    HIP_TRY(d_x.alloc((size_t)k));
+    HIP_TRY(d_p.alloc((size_t)k));
+    DevEnv e{};
+    e.func = d_f.p;
+    e.cdf = d_c.p;
+    e.n = n;
+    e.funcInt = func_int;
+    hipLaunchKernelGGL(k_kat_distribution1d, dim3((k + 63) / 64), dim3(64), 0, c->stream, e, d_u.p, k, d_x.p, d_p.p);
+    if ((rc = launched(c)) || (rc = d_x.out(x_out, (size_t)k))) return rc;
+    return d_p.out(pdf_out, (size_t)k);
+}
+
+}  // extern "C"

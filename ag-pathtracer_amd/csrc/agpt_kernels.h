@@ -89,15 +89,13 @@ k_trace(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restr
 // Production trace kernel (the generic k_trace above stays as the instrumented variant and the fallback for more than
 // 2048 primitives; both are checked against the oracle and against each other).  Same decisions as trace_scene(),
 // restructured for wave efficiency on 64-wide CDNA4 wavefronts:
-//   * persistent waves with IN-FLIGHT REFILL: when at least AGPT_REFILL lanes have retired their rays the wave hands
+//   * persistent waves with IN-FLIGHT REFILL: when at least AGPT_REFILL lanes (agpt_internal.h) have retired their rays the wave hands
 //     them new rays from a wave-private LDS ring instead of idling until all 64 are done;
 //   * PREFILTER RING: rays enter the ring 64 at a time (one atomic on the frontier counter of the wave's queue segment)
 //     with a per-primitive candidate mask from a cheap conservative slab test, all 64 lanes busy; the exact
 //     Bounds::Intersect is re-run per lane where the reference runs it;
 //   * VOTE-SCHEDULED traversal: a lane is between primitives (A), at an interior node (B) or at a leaf (C); each step
 //     the wave executes the body most lanes wait for.  A mesh's root-box test is an interior step on its root pair.
-#define AGPT_REFILL 20      // idle lanes that trigger a refill, closest-hit launches (tuned on C3: 16-24 equal)
-#define AGPT_REFILL_ANY 40  // same, any-hit / MIS-query launches: short traversals, refills are cheaper in bulk
 #define AGPT_RING 128  // entries of the per-wave ring of pre-filtered rays (power of two, >= 64 + 63)
 // per-primitive root record staged in LDS: [2k] = (bmin.xyz | sphere centre.xyz, kind), [2k+1] = (bmax.xyz, root_enc) |
 // (r2, -, -, -) | (half x, half z, -, -); kind 0 = mesh, 1 = sphere, 2 = empty mesh (never hit), 3 = plane
@@ -934,36 +932,4 @@ __global__ void k_resolve(const float4* __restrict__ accum, int n, int samples, 
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     out[i] = resolve_word(accum[i], (float)samples);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// known-answer kernels (one lane per case)
-__global__ void k_kat_bsdf_eval(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ wi3,
-                                float* __restrict__ f3o, float* __restrict__ pdfo) {
-    kat_bsdf_eval_lane(sc, material, n, wo3, wi3, f3o, pdfo);
-}
-__global__ void k_kat_bsdf_sample(DevScene sc, int material, int n, const float* __restrict__ wo3, const float* __restrict__ u2,
-                                  float* __restrict__ wi3o, float* __restrict__ f3o, float* __restrict__ pdfo,
-                                  int32_t* __restrict__ speco) {
-    kat_bsdf_sample_lane(sc, material, n, wo3, u2, wi3o, f3o, pdfo, speco);
-}
-// known-answer kernel: Distribution1D::SampleContinuous (env_sample_continuous) for k draws, one lane each
-// agpt_kat_normal_map: surface_apply_normal_map (agpt_shade.h) alone, one lane per item
-__global__ void k_kat_normal_map(int n, const float* __restrict__ ns3, const float* __restrict__ ss3, const float* __restrict__ rgb3, float scale,
-                                 float* __restrict__ out3) {
-    kat_normal_map_lane(n, ns3, ss3, rgb3, scale, out3);
-}
-__global__ void k_kat_distribution1d(DevEnv e, const float* __restrict__ u, int k, float* __restrict__ x_out, float* __restrict__ pdf_out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= k) return;
-    float pdf;
-    x_out[i] = env_sample_continuous(e, u[i], &pdf);
-    pdf_out[i] = pdf;
-}
-__global__ void k_kat_rng(uint32_t pixel, uint32_t wh, uint32_t sample, uint32_t seed_base, int n, float* __restrict__ out,
-                          uint32_t* __restrict__ seed_out) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    uint32_t s = sample_seed(pixel, wh, sample, seed_base);
-    *seed_out = s;
-    for (int i = 0; i < n; i++) out[i] = rng_float(s);
 }

@@ -74,7 +74,7 @@
 #include "agpt_transform.h"
 
 namespace agpt {
-int report_error(int code, const std::string& msg);   // agpt_api.hip (agpt_last_error)
+int fail(int code, const std::string& msg);   // agpt_api.hip: the message of agpt_last_error
 }
 
 namespace {
@@ -454,9 +454,9 @@ void agpt_obj_free(agpt_obj_mesh* m) { delete m; }
 int agpt_transform_arrays(const float* transform16, const float* vertices, int n_vertices, const float* normals, int n_normals,
                           float* vertices_out, float* normals_out) {
     if (!transform16 || !vertices || !vertices_out)
-        return agpt::report_error(AGPT_ERR_INVALID, "agpt_transform_arrays: NULL transform16, vertices or vertices_out");
+        return agpt::fail(AGPT_ERR_INVALID, "agpt_transform_arrays: NULL transform16, vertices or vertices_out");
     if (n_vertices < 0 || n_normals < 0 || (n_normals > 0 && (!normals || !normals_out)))
-        return agpt::report_error(AGPT_ERR_INVALID, "agpt_transform_arrays: a negative count, or n_normals > 0 with NULL normals or normals_out");
+        return agpt::fail(AGPT_ERR_INVALID, "agpt_transform_arrays: a negative count, or n_normals > 0 with NULL normals or normals_out");
     Mat4 M;
     std::memcpy(M.c, transform16, sizeof(M.c));
     const Mat4 N = inverse_transpose(M);

@@ -2,7 +2,7 @@
 // chooses.  Value-only: what a BSDF's f and pdf are (lobe evaluation, Fresnel, the microfacet D and G), the pdfs of the lights,
 // MIS weights and the path's contributions and throughput.
 //
-//   AGPT_SHADE_FAST 0 (default; agpt_api.hip, agpt_shade_kernels.hip): each helper is exactly the expression it replaces --
+//   AGPT_SHADE_FAST 0 (default; agpt_api.hip, agpt_kat.hip, agpt_shade_kernels.hip): each helper is exactly the expression it replaces --
 //     correctly rounded fp32 divide and square root.  Bit-exact parity with the oracle rests on this; the unit's code is the
 //     code the plain expressions compile to.
 //   AGPT_SHADE_FAST 1 (agpt_shade_kernels_fast.hip, agpt_scene_set_shading_arith(AGPT_SHADING_FAST)): a / b is a * v_rcp_f32(b),

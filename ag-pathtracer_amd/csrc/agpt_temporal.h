@@ -1,5 +1,4 @@
-// agpt_temporal.h -- host-side launcher of the temporal reprojection unit (agpt_temporal.hip), used by agpt_temporal_accumulate in
-// agpt_api.hip.
+// agpt_temporal.h -- the constants of k_temporal (agpt_temporal.hip, which also defines agpt_temporal_accumulate).
 #pragma once
 
 #include "agpt_denoise.h"
@@ -10,10 +9,3 @@ struct TemporalConsts {
     float max_history, depth_tol, normal_cos;
     DevCamera cur, prev;   // make_camera of the two descriptions
 };
-
-namespace agpt {
-// one thread per film pixel in k_denoise_pass' tiling; the four prev pointers are all NULL (first frame) or all set
-void launch_temporal(hipStream_t stream, const TemporalConsts& tc, const float4* accum_cur, const float* moment2_cur, const float4* albedo_cur,
-                     const float4* normal_depth_cur, const float4* hist_accum_prev, const float* hist_moment2_prev, const float4* albedo_prev,
-                     const float4* normal_depth_prev, float4* hist_accum_out, float* hist_moment2_out);
-}  // namespace agpt

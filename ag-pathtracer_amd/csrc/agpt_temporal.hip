@@ -9,9 +9,13 @@
 // around the reprojected position (neighbouring pixels land on neighbouring taps: the lines are shared through L1 / L2).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstring>
+
+#include "agpt_internal.h"
 #include "agpt_temporal.h"
 
-#include "../../include/agpt.h"
+using agpt::fail;
 
 #define AGPT_TP_DEPTH_FLOOR 1e-3f
 
@@ -99,15 +103,51 @@ k_temporal(TemporalConsts tc, const float4* __restrict__ accum_cur, const float*
     hist_moment2_out[i] = m_out;
 }
 
-namespace agpt {
+extern "C" {
 
-void launch_temporal(hipStream_t stream, const TemporalConsts& tc, const float4* accum_cur, const float* moment2_cur, const float4* albedo_cur,
-                     const float4* normal_depth_cur, const float4* hist_accum_prev, const float* hist_moment2_prev, const float4* albedo_prev,
-                     const float4* normal_depth_prev, float4* hist_accum_out, float* hist_moment2_out) {
+// One k_temporal launch: this frame's buffers plus the previous frame's history, reprojected, into the history buffers the next
+// agpt_denoise and the next frame's call read.
+int agpt_temporal_accumulate(agpt_ctx* c, const agpt_temporal_params* p, const float* accum_cur_dev, const float* moment2_cur_dev,
+                             const float* albedo_cur_dev, const float* normal_depth_cur_dev, const float* hist_accum_prev_dev,
+                             const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
+                             float* hist_accum_out_dev, float* hist_moment2_out_dev) {
+    if (!p) return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: NULL argument");
+    if (p->width <= 0 || p->height <= 0 || (uint64_t)p->width * (uint64_t)p->height > 0x7FFFFFFFull)
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: bad film size");
+    if (!(p->max_history > 0.f) || std::isinf(p->max_history))
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: max_history must be positive and finite");
+    if (!(p->depth_tol >= 0.f) || std::isinf(p->depth_tol))
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: depth_tol must be non-negative and finite");
+    if (!(p->normal_cos >= -1.f && p->normal_cos <= 1.f))
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: normal_cos must be in [-1, 1]");
+    if (!c || !accum_cur_dev || !moment2_cur_dev || !albedo_cur_dev || !normal_depth_cur_dev || !hist_accum_out_dev || !hist_moment2_out_dev)
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: NULL argument");
+    const float* prev[4] = {hist_accum_prev_dev, hist_moment2_prev_dev, albedo_prev_dev, normal_depth_prev_dev};
+    const int n_prev = (prev[0] != nullptr) + (prev[1] != nullptr) + (prev[2] != nullptr) + (prev[3] != nullptr);
+    if (n_prev != 0 && n_prev != 4)
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: the four prev buffers must be all NULL (first frame) or all given");
+    const float* in[8] = {accum_cur_dev, moment2_cur_dev, albedo_cur_dev, normal_depth_cur_dev, prev[0], prev[1], prev[2], prev[3]};
+    for (const float* q : in)
+        if (q && (q == hist_accum_out_dev || q == hist_moment2_out_dev))
+            return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: an output aliases an input");
+    if (hist_accum_out_dev == hist_moment2_out_dev) return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate: the two outputs are one buffer");
+    HIP_TRY(hipSetDevice(c->device));
+    TemporalConsts tc{};
+    tc.W = p->width; tc.H = p->height;
+    tc.identity = std::memcmp(&p->cam_prev, &p->cam_cur, sizeof(agpt_camera_desc)) == 0;
+    tc.max_history = p->max_history; tc.depth_tol = p->depth_tol; tc.normal_cos = p->normal_cos;
+    tc.cur = agpt::make_camera(p->cam_cur);
+    tc.prev = agpt::make_camera(p->cam_prev);
+    // one thread per film pixel in k_denoise_pass' tiling
     static_assert(AGPT_DN_TX * AGPT_DN_TY == AGPT_BLOCK, "one thread per tile pixel");
-    const dim3 g((unsigned)((tc.W + AGPT_DN_TX - 1) / AGPT_DN_TX), (unsigned)((tc.H + AGPT_DN_TY - 1) / AGPT_DN_TY));
-    hipLaunchKernelGGL(k_temporal, g, dim3(AGPT_BLOCK), 0, stream, tc, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev,
-                       hist_moment2_prev, albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out);
+    const dim3 tiles((unsigned)((tc.W + AGPT_DN_TX - 1) / AGPT_DN_TX), (unsigned)((tc.H + AGPT_DN_TY - 1) / AGPT_DN_TY));
+    hipLaunchKernelGGL(k_temporal, tiles, dim3(AGPT_BLOCK), 0, c->stream, tc, (const float4*)accum_cur_dev, moment2_cur_dev,
+                       (const float4*)albedo_cur_dev, (const float4*)normal_depth_cur_dev, (const float4*)hist_accum_prev_dev,
+                       hist_moment2_prev_dev, (const float4*)albedo_prev_dev, (const float4*)normal_depth_prev_dev,
+                       (float4*)hist_accum_out_dev, hist_moment2_out_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AGPT_OK;
 }
 
-}  // namespace agpt
+}  // extern "C"

@@ -25,7 +25,7 @@
 
 namespace agpt {
 
-int report_error(int code, const std::string& msg);   // agpt_api.hip
+int fail(int code, const std::string& msg);   // agpt_api.hip: the message of agpt_last_error
 
 namespace {
 
@@ -33,7 +33,7 @@ namespace {
     do {                                                                                                  \
         hipError_t e_ = (expr);                                                                           \
         if (e_ != hipSuccess)                                                                             \
-            return report_error(e_ == hipErrorOutOfMemory ? AGPT_ERR_NOMEM : AGPT_ERR_DEVICE,             \
+            return fail(e_ == hipErrorOutOfMemory ? AGPT_ERR_NOMEM : AGPT_ERR_DEVICE,             \
                                 std::string(#expr) + ": " + hipGetErrorString(e_));                       \
     } while (0)
 
@@ -216,13 +216,13 @@ static int prepare(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh) {
         if (i == 1) continue;
         const agpt_bvh_node& nd = mesh.nodes[i];
         topo[i] = make_int2(nd.first, nd.count);
-        if (depth[i] < 0) return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: the mesh's BVH has an unreachable node");
+        if (depth[i] < 0) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: the mesh's BVH has an unreachable node");
         if (nd.count > 0) {
-            if (nd.first < 0 || nd.count > n_tris - nd.first) return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: leaf range outside the mesh");
+            if (nd.first < 0 || nd.count > n_tris - nd.first) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: leaf range outside the mesh");
             lists.push_back(i);
         } else {
             if (nd.count < 0 || nd.first <= i || nd.first < 2 || nd.first >= total)
-                return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: child pair outside the tree");
+                return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: child pair outside the tree");
             depth[nd.first] = depth[nd.first + 1] = depth[i] + 1;
             if ((int)interior.size() <= depth[i]) interior.resize((size_t)depth[i] + 1);
             interior[depth[i]].push_back(i);
@@ -235,7 +235,7 @@ static int prepare(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh) {
         u.begin.push_back((int)lists.size());
     }
     for (int32_t p : mesh.prim_index)
-        if (p < 0 || p % 3 != 0 || p / 3 >= n_tris) return report_error(AGPT_ERR_INVALID, "agpt_scene_update_mesh: bad prim_index");
+        if (p < 0 || p % 3 != 0 || p / 3 >= n_tris) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: bad prim_index");
     u.total_nodes = total;
     UPD_TRY(u.topo.upload(topo.data(), topo.size(), stream));
     UPD_TRY(u.lists.upload(lists.data(), lists.size(), stream));
@@ -339,7 +339,7 @@ int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostM
     MeshUpdater& u = **cache;
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
     if (rest_vertices.size() != nv || rest_normals.size() != nn)
-        return report_error(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: the rest pose does not have the mesh's counts");
+        return fail(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: the rest pose does not have the mesh's counts");
     if (!u.has_rest) {
         UPD_TRY(u.rest_verts.upload(&rest_vertices.data()->x, 3 * nv, stream));
         if (nn) UPD_TRY(u.rest_normals.upload(&rest_normals.data()->x, 3 * nn, stream));
