@@ -59,12 +59,22 @@ struct TraceLaunch {
     bool small_batch;            // the rays of the batch number fewer than AGPT_SMALL_BATCH: k_trace_fast<PEEK>
     bool recast;                 // the wavefront loop's own closest-hit launch (its rays carry d.w): may re-cast a ray in place, see
                                  // the retire branch of k_trace_fast
+    bool coherent;               // the rays are k_generate's camera rays in sample groups of 64, a pixel per wave: k_trace_fast<COH>
+                                 // (run_wavefront says when; no other caller sets it)
 };
 
 template <int MODE, bool COUNT, bool SPILL, bool PEEK>
 static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch& t) {
     const dim3 block(AGPT_BLOCK), g(fast_grid(c));
     const int refill = MODE == 0 ? c->refill : c->refill_any;
+    if constexpr (MODE == 0 && !COUNT) {
+        if (t.coherent && sc.n_prims <= 64) {   // (a wave takes a whole 64-ray chunk, and only when it is empty: refill = 64)
+            hipLaunchKernelGGL((k_trace_fast<0, AGPT_FAST_STACK, false, false, SPILL, PEEK, true>), g, block, 0, t.stream, sc, t.queue,
+                               t.count_ptr, t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, 64, 0u, c->spill.p,
+                               (const unsigned long long*)nullptr, (const uint32_t*)nullptr, t.recast, (const float4*)c->beta4.p, c->L4.p);
+            return;
+        }
+    }
     if (sc.n_prims <= 64) {
         hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, false, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
                            t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p,
@@ -307,6 +317,7 @@ struct WavefrontRun {
     PathBuffers pb;
     Queues q[2];
     bool mis_mode, timing;
+    bool camera_rays = false;   // the batches come from k_generate (agpt_render): a run of sample_group(S) path ids is one pixel's samples
     int count;              // enable_counters, normalised (see use_fast_trace)
     agpt::ShadeVariant shade;
     uint64_t iterations = 0, launches = 0;
@@ -354,6 +365,10 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, Wa
     const int shade_grid = c->num_cus * c->shade_blocks_per_cu;
     const bool small_batch = (unsigned long long)rcn.NP * (unsigned long long)rcn.S < AGPT_SMALL_BATCH;
     const bool recast = !getenv("AGPT_NO_RECAST");   // (developer knob: emitter pass-throughs through k_shade, an iteration each)
+    // iteration 0 of an agpt_render batch at a sample group of 64: every wave of the closest-hit launch traces one pixel's camera rays
+    // (k_trace_fast<COH>); AGPT_NO_COHERENT (developer knob) keeps the ordinary instantiation
+    const bool coherent = run.camera_rays && sample_group(rcn.S) == 64 && use_fast_trace(c, s->dev, count) && s->dev.n_prims <= 64 &&
+                          count == 0 && !getenv("AGPT_NO_COHERENT");
     // side streams: not where the launches share scratch buffers (the HBM stack spill of deep BVHs, the candidate words of long
     // lists), nor with the reference-order kernels
     const bool side = (c->multi_stream == 2 || (c->multi_stream == 1 && small_batch)) && use_fast_trace(c, s->dev, count) &&
@@ -389,11 +404,11 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, Wa
                                     c->work.p + 3 * AGPT_FRONTIERS * AGPT_QSTRIDE};
         // (the closest-hit launch over the continuation rays may re-cast in place, see k_trace_fast)
         const TraceLaunch ext{main_stream, q[cur].ext, &QCOUNT(q[cur], 0), 0, heads[0], pb.ext_o, pb.ext_d, pb.hit, nullptr,
-                              count, small_batch, recast};
+                              count, small_batch, recast, coherent && it == 0};
         const TraceLaunch mis{mis_stream, q[cur].mis, &QCOUNT(q[cur], 1), 0, heads[1], pb.mis_o, pb.mis_d,
-                              run.mis_mode ? nullptr : pb.mis_hit, run.mis_mode ? pb.mis_ok : nullptr, count, small_batch, false};
+                              run.mis_mode ? nullptr : pb.mis_hit, run.mis_mode ? pb.mis_ok : nullptr, count, small_batch, false, false};
         const TraceLaunch shadow{shadow_stream, q[cur].shadow, &QCOUNT(q[cur], 2), 0, heads[2], pb.sh_o, pb.sh_d, nullptr, pb.occluded,
-                                 count, small_batch, false};
+                                 count, small_batch, false, false};
         auto trace_ext = [&]() { launch_trace_timed<0>(c, run.timing, 0, s->dev, ext); };
         auto trace_mis = [&]() {
             if (run.mis_mode) launch_trace_timed<2>(c, run.timing, 1, s->dev, mis);
@@ -463,10 +478,15 @@ static int fill_stats(agpt_ctx* c, const WavefrontRun& run, uint64_t samples, ag
     }
 #endif
 #ifdef AGPT_TRACE_STATS
-    for (int mode = 0; mode < 3; ++mode) {
-        const unsigned long long* d = dc.dbg + 16 * mode;
+    for (int mode = 0; mode < 4; ++mode) {   // (3: the coherent closest-hit launch, counted apart from the other mode-0 launches)
+        const unsigned long long* d = dc.dbg + (mode < 3 ? 16 * mode : AGPT_DBG_COH);
         const double steps = (double)(d[0] + d[1] + d[2]);
         if (steps == 0) continue;
+        if (mode == 3)
+            std::fprintf(stderr, "[trace stats mode 3] scalar path: B %.3g of %.3g wave-steps (%.1f%%), %.3g of %.3g lane-steps (%.1f%%);  "
+                         "C %.3g of %.3g wave-steps (%.1f%%), %.3g of %.3g lane-steps (%.1f%%)\n",
+                         (double)d[16], (double)d[1], d[1] ? 100. * d[16] / d[1] : 0., (double)d[18], (double)d[4], d[4] ? 100. * d[18] / d[4] : 0.,
+                         (double)d[17], (double)d[2], d[2] ? 100. * d[17] / d[2] : 0., (double)d[19], (double)d[5], d[5] ? 100. * d[19] / d[5] : 0.);
         std::fprintf(stderr,
                      "[trace stats mode %d] steps A/B/C %.3g/%.3g/%.3g (%.1f%%/%.1f%%/%.1f%%)  lanes per step A %.1f B %.1f C %.1f  "
                      "active lanes per step %.1f  refills %.3g (%.1f lanes each)  prefilter batches %.3g\n", mode,
@@ -551,7 +571,7 @@ static uint64_t samples_per_batch(const agpt_render_params* rp, uint32_t NP) {
 // n rays in ext_o / ext_d -> hit / occluded, one launch outside the wavefront loop (agpt_intersect_device, agpt_render_features)
 static void trace_rays(agpt_ctx* c, const DevScene& sc, uint32_t n, bool any_hit, int count) {
     const TraceLaunch t{c->stream, nullptr, nullptr, n, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p,
-                        count, (unsigned long long)n < AGPT_SMALL_BATCH, false};
+                        count, (unsigned long long)n < AGPT_SMALL_BATCH, false, false};
     if (any_hit) launch_trace<1>(c, sc, t);
     else launch_trace<0>(c, sc, t);
 }
@@ -626,6 +646,7 @@ int agpt_render(agpt_scene* s, const agpt_render_params* rp, float* accum_dev, a
     RenderConsts rcn = tile_consts(rp, NP);
     rcn.seed_base = rp->seed_base;
     set_wavefront_consts(rcn, run, rp->max_depth, rp->trace_all_rays != 0);
+    run.camera_rays = true;
     for (int s0 = rp->spp_begin; s0 < rp->spp_begin + rp->spp_count; s0 += S) {
         rcn.s0 = s0;
         rcn.S = std::min(S, rp->spp_begin + rp->spp_count - s0);

@@ -132,8 +132,13 @@ k_trace(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restr
 template <int MODE, bool LIST>
 using TraceRays = std::conditional_t<MODE == 0 && !LIST, float4*, const float4* __restrict__>;
 // recast_on (MODE 0, short lists): the rays carry d.w and may be re-cast; path_beta4 / path_L4 are then the paths' state
-template <int MODE, int DEPTH, bool LIST, bool COUNT, bool SPILL, bool PEEK>
-__global__ void __launch_bounds__(AGPT_BLOCK, AGPT_TRACE_WAVES)
+// COH (MODE 0, short lists, no counting): the launch over the camera rays of a 64-sample group.  A wave takes one pixel's 64 rays
+// at a time (the host passes refill = 64), and where every lane that is about to run an interior or a leaf step stands at the SAME
+// node, the wave fetches that record once, through scalar loads, instead of 64 times through the vector L1: the box and triangle
+// coordinates are then SGPR operands of the very same per-lane arithmetic.  Lanes that stand at different nodes run the vector
+// step of every other instantiation.  Only loads go through the scalar unit.
+template <int MODE, int DEPTH, bool LIST, bool COUNT, bool SPILL, bool PEEK, bool COH = false>
+__global__ void __launch_bounds__(AGPT_BLOCK, COH ? 5 : AGPT_TRACE_WAVES)
 k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
              uint32_t* __restrict__ work_head, TraceRays<MODE, LIST> ray_o, TraceRays<MODE, LIST> ray_d,
              DevHit* __restrict__ hits, uint32_t* __restrict__ occluded, DevCounters* __restrict__ counters, int refill,
@@ -141,7 +146,9 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
              const uint32_t* __restrict__ cand_chunks, bool recast_on, const float4* path_beta4, float4* path_L4) {
     constexpr bool ANY = MODE != 0;
     constexpr bool MIS = MODE == 2;
+    static_assert(!COH || (MODE == 0 && !LIST && !COUNT), "the coherent instantiation is a plain short-list closest-hit launch");
     constexpr int BLOCK = AGPT_BLOCK;
+    if constexpr (COH) refill = 64;    // (what the host passes: a wave takes a whole 64-ray chunk, and only when it is empty)
     constexpr bool PRIM_LDS = !LIST;   // short lists: the primitive records live in LDS
     __shared__ uint32_t s_stack[DEPTH * BLOCK];
     __shared__ float4 s_prim[PRIM_LDS ? 2 * 64 : 2];
@@ -279,7 +286,8 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     uint32_t c_int = 0, c_root = 0, c_tri = 0;   // COUNT
     TS(unsigned long long ts_steps[3] = {0, 0, 0}; unsigned long long ts_lanes[3] = {0, 0, 0}; unsigned long long ts_act = 0;
        unsigned long long ts_refills = 0; unsigned long long ts_refilled = 0; unsigned long long ts_pref = 0;
-       uint32_t ts_push[5] = {0, 0, 0, 0, 0};)
+       uint32_t ts_push[5] = {0, 0, 0, 0, 0};
+       unsigned long long ts_usteps[2] = {0, 0}; unsigned long long ts_ulanes[2] = {0, 0};)   // COH: B / C steps on the scalar path
     TCK(unsigned long long tk_refill = 0, tk_vote = 0, tk_bmem = 0, tk_balu = 0, tk_c = 0, tk_a = 0; const unsigned long long tk_begin = TCK_NOW();)
 
     uint32_t pfa_off = 0;       // lane 0: offset returned by the pending frontier atomic (stage A)
@@ -574,7 +582,60 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
             TS(ts_act += (unsigned long long)n_active; if (!(nB >= nA && nB >= nC) && !(nC >= nA)) { ts_steps[0]++; ts_lanes[0] += nA; })
             if (nB >= nA && nB >= nC) {
                 TS(ts_steps[1]++; ts_lanes[1] += nB;)
-                if (cur < CUR_B_END) {
+                if constexpr (COH) {
+                    // the step below, once per record source: `np` is the pair record, in SGPRs on the scalar path
+                    auto interior = [&](const NodePair& np) {
+                        float dl, dr;
+                        bool hl, hr;
+                        const uint32_t encl = __float_as_uint(np.n3.x), encr = __float_as_uint(np.n3.y);
+                        pair_boxes_fast(np, r, rayt, hl, hr, dl, dr);
+                        if (any_slow) {
+                            if (!r.fast) pair_boxes_exact(np, r, rayt, hl, hr, dl, dr);
+                        }
+                        hr = hr && cur < rootpair_base;
+                        if (hl && hr) {
+                            const bool swap = dr < dl;
+                            stack_push(sp, swap ? encl : encr);
+                            sp++;
+                            TS(ts_push[0]++; ts_push[1] += sp > 4; ts_push[2] += sp > 6; ts_push[3] += sp > 8; ts_push[4] += sp > 12;)
+                            cur = swap ? encr : encl;
+                        } else if (hl) {
+                            cur = encl;
+                        } else if (hr) {
+                            cur = encr;
+                        } else if (sp == 0) {
+                            cur = pick_next(mask);
+                        } else {
+                            sp--;
+                            cur = stack_at(sp);
+                        }
+                    };
+                    const bool in_b = cur < CUR_B_END;
+                    const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)cur, __ffsll((long long)__ballot(in_b)) - 1);
+                    if (__ballot(in_b && cur != u) == 0) {
+                        // every voting lane stands at pair u: one 64-byte scalar fetch for the wave (the constant address space, as
+                        // for the prefilter records in pump_consume)
+                        TS(ts_usteps[0]++; ts_ulanes[0] += nB;)
+                        typedef const float __attribute__((address_space(4))) ConstF;
+                        ConstF* q = (ConstF*)sc.nodes + 8 * (size_t)u;
+                        NodePair np;
+                        np.n0.x = q[0]; np.n0.y = q[1]; np.n0.z = q[2]; np.n0.w = q[3];
+                        np.n1.x = q[4]; np.n1.y = q[5]; np.n1.z = q[6]; np.n1.w = q[7];
+                        np.n2.x = q[8]; np.n2.y = q[9]; np.n2.z = q[10]; np.n2.w = q[11];
+                        np.n3.x = q[12]; np.n3.y = q[13]; np.n3.z = q[14]; np.n3.w = q[15];
+                        // (one batch of loads and one wait: left to itself the compiler fetches the child encodings by a second load
+                        // where they are first used, behind the box arithmetic)
+                        asm volatile("" : "+s"(np.n0.x), "+s"(np.n0.y), "+s"(np.n0.z), "+s"(np.n0.w), "+s"(np.n1.x), "+s"(np.n1.y), "+s"(np.n1.z),
+                                     "+s"(np.n1.w), "+s"(np.n2.x), "+s"(np.n2.y), "+s"(np.n2.z), "+s"(np.n2.w), "+s"(np.n3.x), "+s"(np.n3.y));
+                        if (in_b) interior(np);
+                    } else if (in_b) {
+                        __builtin_amdgcn_s_setprio(1);
+                        const NodePair np = load_pair(sc, cur);
+                        asm volatile("" ::: "memory");
+                        __builtin_amdgcn_s_setprio(0);
+                        interior(np);
+                    }
+                } else if (cur < CUR_B_END) {
                     // the wave is about to wait for these loads whatever happens: let its issue win the arbitration against
                     // waves in the middle of their arithmetic (-1.5 ms per C3 step on the closest-hit and MIS launches; the
                     // short any-hit steps lose 0.3 ms with it)
@@ -618,7 +679,50 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                 TCK(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tk_balu += TCK_NOW() - tk_v1;)
             } else if (nC >= nA) {
                 TS(ts_steps[2]++; ts_lanes[2] += nC;)
-                if ((int32_t)cur < 0) {
+                const bool in_c = (int32_t)cur < 0;
+                bool same_leaf = false;
+                uint32_t u = 0;
+                if constexpr (COH) {
+                    u = (uint32_t)__builtin_amdgcn_readlane((int)cur, __ffsll((long long)__ballot(in_c)) - 1);
+                    same_leaf = __ballot(in_c && cur != u) == 0;
+                }
+                if (COH && same_leaf) {
+                    // every voting lane stands at leaf u: its range and its triangle records come through scalar loads
+                    TS(ts_usteps[1]++; ts_ulanes[1] += nC;)
+                    typedef const float __attribute__((address_space(4))) ConstF;
+                    typedef const uint32_t __attribute__((address_space(4))) ConstU;
+                    uint32_t first, cnt;   // (leaf_range on the wave's value)
+                    if ((u & AGPT_ENC_BIGLEAF) == AGPT_ENC_BIGLEAF) {
+                        ConstU* bl = (ConstU*)sc.bigleaves + 2 * (size_t)(u & 0x0FFFFFFFu);
+                        first = bl[0];
+                        cnt = bl[1];
+                    } else {
+                        first = u & 0x0FFFFFFFu;
+                        cnt = ((u >> 28) & 7u) + 1u;
+                    }
+                    if (in_c) {
+                        for (uint32_t i = 0; i < cnt; ++i) {
+                            ConstF* tp = (ConstF*)sc.tri_verts + 12 * (size_t)(first + i);
+                            const v3 q0 = V3(tp[0], tp[1], tp[2]), q1 = V3(tp[4], tp[5], tp[6]), q2 = V3(tp[8], tp[9], tp[10]);
+                            const uint32_t q_id = __float_as_uint(tp[3]), q_flags = __float_as_uint(tp[7]);
+                            float t, b1, b2;
+                            if (tri_test(q0, q1, q2, r, rayt, t, b1, b2)) {
+                                if (!(q_flags & AGPT_TRI_FLAG_REJECT)) {
+                                    rayt = t;
+                                    hid = q_id;
+                                    hb1 = b1;
+                                    hb2 = b2;
+                                }
+                            }
+                        }
+                        if (sp == 0) {
+                            cur = pick_next(mask);
+                        } else {
+                            sp--;
+                            cur = stack_at(sp);
+                        }
+                    }
+                } else if ((int32_t)cur < 0) {
                     uint32_t first, cnt;
                     leaf_range(sc, cur, first, cnt);
                     bool done = false;
@@ -721,14 +825,17 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
             }
         }
     }
+    // (stats build: the coherent launch keeps its own set of slots, mode "3")
+    TS(constexpr int TS_BASE = COH ? AGPT_DBG_COH : 16 * MODE;)
     TS(if (lane == 0) {
-        unsigned long long* d = counters->dbg + 16 * MODE;
+        unsigned long long* d = counters->dbg + TS_BASE;
+        if (COH) for (int k = 0; k < 2; ++k) { atomicAdd(d + 16 + k, ts_usteps[k]); atomicAdd(d + 18 + k, ts_ulanes[k]); }
         for (int k = 0; k < 3; ++k) { atomicAdd(d + k, ts_steps[k]); atomicAdd(d + 3 + k, ts_lanes[k]); }
         atomicAdd(d + 6, ts_act); atomicAdd(d + 7, ts_refills); atomicAdd(d + 8, ts_refilled); atomicAdd(d + 9, ts_pref);
     })
 #if defined(AGPT_TRACE_STATS) && !defined(AGPT_TRACE_CLOCK)
     {   // stack-depth histogram of the pushes (per lane; slots 10..14 are the phase clocks' in the clock build)
-        unsigned long long* d = counters->dbg + 16 * MODE;
+        unsigned long long* d = counters->dbg + TS_BASE;
         for (int k = 0; k < 5; ++k) {
             uint32_t v = ts_push[k];
             for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
@@ -737,9 +844,9 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     }
 #endif
     TS(if (lane == 0) {
-        unsigned long long* d = counters->dbg + 16 * MODE;
+        unsigned long long* d = counters->dbg + TS_BASE;
         TCK(atomicAdd(d + 10, tk_refill); atomicAdd(d + 11, tk_vote); atomicAdd(d + 12, tk_bmem); atomicAdd(d + 13, tk_balu);
-            atomicAdd(d + 14, tk_c); atomicAdd(d + 15, tk_a); atomicAdd(counters->dbg + 48 + MODE, TCK_NOW() - tk_begin);)
+            atomicAdd(d + 14, tk_c); atomicAdd(d + 15, tk_a); atomicAdd(counters->dbg + 48 + (COH ? 3 : MODE), TCK_NOW() - tk_begin);)
     })
     if (COUNT) {   // (k_trace's flush, the other copy, see there; here in the order interior, roots, tris)
         for (int off = 32; off > 0; off >>= 1) {

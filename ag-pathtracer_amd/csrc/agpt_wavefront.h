@@ -168,7 +168,8 @@ __device__ __forceinline__ uint32_t resolve_word(const float4& a, float n) {
 struct DevCounters {
     unsigned long long closest_rays, anyhit_rays, interior, tris, shaded, outliers, samples, roots, answered;
 #if defined(AGPT_TRACE_STATS) || defined(AGPT_SHADE_CLOCK)
-    unsigned long long dbg[64];  // developer builds only (tools/build_variant.py): wave-step statistics of k_trace_fast, phase clocks
+    unsigned long long dbg[96];  // developer builds only (tools/build_variant.py): wave-step statistics of k_trace_fast, phase clocks
+#define AGPT_DBG_COH 64          // first of the 20 slots of the coherent closest-hit launch (the 16 of a mode + its scalar-path counts)
 #endif
 };
 #ifdef AGPT_TRACE_STATS
