@@ -38,7 +38,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
@@ -193,6 +193,8 @@ def lib():
             getattr(L, name).argtypes = args
     L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
     L.agpt_scene_set_shading_arith.argtypes = [vp, C.c_int]
+    if not variant or hasattr(L, "agpt_scene_shade_variant"):
+        L.agpt_scene_shade_variant.argtypes = [vp, C.POINTER(C.c_int32)]
     L.agpt_bvh_build_device.argtypes = [vp, fp, C.c_int, ip, C.c_int, C.c_int, vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                         C.POINTER(C.c_int)]
     L.agpt_toplevel_build.argtypes = [fp, C.c_int, fp]
@@ -712,6 +714,14 @@ class Scene:
                 raise ValueError("set_shading_arith: unknown mode %r (exact, fast)" % mode)
             mode = SHADING_EXACT if mode == "exact" else SHADING_FAST
         _check(self.L.agpt_scene_set_shading_arith(self.h, int(mode)), "agpt_scene_set_shading_arith")
+
+    def shade_variant(self):
+        """agpt_scene_shade_variant: (level, fast, lds_tables, env) of the shading kernels the next render or Li call on this committed
+        scene launches -- texturing level 0 .. 4, arithmetic, scene tables in LDS or in global memory (the counts, or
+        AGPT_SHADE_GLOBAL_TABLES in the environment), an InfiniteAreaLight present.  Host-only."""
+        out = (C.c_int32 * 4)()
+        _check(self.L.agpt_scene_shade_variant(self.h, out), "agpt_scene_shade_variant")
+        return tuple(int(x) for x in out)
 
     def add_sphere(self, center, radius, material):
         _, p = _f(center)

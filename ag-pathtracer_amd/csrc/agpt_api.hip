@@ -311,6 +311,24 @@ static bool shade_tables_fit_lds(const DevScene& d) {
     return agpt::shade_tables_fit_lds(d.n_prims, d.n_materials, d.n_lights) && !getenv("AGPT_SHADE_GLOBAL_TABLES");
 }
 
+// Which shading kernels the next call on the scene launches (begin_wavefront, agpt_scene_shade_variant)
+static agpt::ShadeVariant shade_variant_of(const agpt_scene* s) {
+    agpt::ShadeVariant v;
+    v.fast = s->shading_arith == AGPT_SHADING_FAST;   // agpt_scene_set_shading_arith
+    v.level = s->shade_level;                         // agpt_scene_commit
+    v.lds_tables = shade_tables_fit_lds(s->dev);
+    v.env = !s->envs.empty();                         // an InfiniteAreaLight is present
+    return v;
+}
+
+int agpt_scene_shade_variant(const agpt_scene* s, int32_t out4[4]) {
+    if (!s || !out4) return fail(AGPT_ERR_INVALID, "agpt_scene_shade_variant: NULL scene or output");
+    if (!s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_shade_variant: scene not committed");
+    const agpt::ShadeVariant v = shade_variant_of(s);
+    out4[0] = (int32_t)v.level; out4[1] = v.fast ? 1 : 0; out4[2] = v.lds_tables ? 1 : 0; out4[3] = v.env ? 1 : 0;
+    return AGPT_OK;
+}
+
 // What a call that runs the wavefront loop sets up once (begin_wavefront): the pool as the kernels see it, how rays are traced and
 // counted, which shading kernels run; and what the loop adds up for the call's statistics (fill_stats).
 struct WavefrontRun {
@@ -335,10 +353,7 @@ static int begin_wavefront(agpt_ctx* c, const agpt_scene* s, int enable_counters
     run.count = enable_counters == 2 ? 2 : (enable_counters != 0 ? 1 : 0);
     run.mis_mode = use_fast_trace(c, s->dev, run.count) && !c->mis_closest;
     run.timing = timing;
-    run.shade.fast = s->shading_arith == AGPT_SHADING_FAST;   // agpt_scene_set_shading_arith
-    run.shade.level = s->shade_level;                         // agpt_scene_commit
-    run.shade.lds_tables = shade_tables_fit_lds(s->dev);
-    run.shade.env = !s->envs.empty();                         // an InfiniteAreaLight is present
+    run.shade = shade_variant_of(s);
     c->tev_used = 0;
     c->tev_kind.clear();
     HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));

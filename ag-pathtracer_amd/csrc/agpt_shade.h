@@ -237,7 +237,7 @@ __device__ __forceinline__ LobeEval lobe_eval(const DevMaterial& m, int lobe, v3
         bool f_ok = !(cosThetaI == 0 || cosThetaO == 0) && !(whs.x == 0 && whs.y == 0 && whs.z == 0);
         bool pdf_ok = same_hemisphere(wo, wi);
         if (f_ok || pdf_ok) {
-            v3 wh = sh_normalize(whs);
+            v3 wh = sh_normalize_rn(whs);   // (normalize's bits in both arithmetics: tr_D amplifies an ulp of wh.z, agpt_shade_arith.h)
             float D = tr_D(m, wh);
             float G1o = wc.G1o;
             if (f_ok) {

@@ -345,7 +345,8 @@ int agpt_scene_set_bvh_builder(agpt_scene*, int builder);
  *          bit-identical to the oracle.
  *   FAST:  the path weights -- BSDF f and pdf (lobe evaluation, Fresnel, microfacet D and G), light pdfs, MIS weights, the
  *          contributions and the throughput -- use the hardware reciprocal (a * rcp(b) for a / b), square root and reciprocal
- *          square root.  What decides a ray stays exact: sampled directions and their trigonometry, surface frames, the
+ *          square root (the half vector of the microfacet lobe alone keeps its exact bits: a smooth lobe turns its last bit
+ *          into a tenth of D).  What decides a ray stays exact: sampled directions and their trigonometry, surface frames, the
  *          environment map's texel choices, ray origins / directions / tmax, traversal and intersection (the MIS pre-test
  *          included), camera rays, the RNG streams, accumulation and the queue logic.  A FAST render therefore traces the same
  *          rays as an EXACT one and is deterministic: bit-identical across repeated calls, samples_per_batch splits and rank
@@ -354,6 +355,13 @@ int agpt_scene_set_bvh_builder(agpt_scene*, int builder);
  * A NULL scene or an unknown mode returns AGPT_ERR_INVALID. */
 enum { AGPT_SHADING_EXACT = 0, AGPT_SHADING_FAST = 1 };
 int agpt_scene_set_shading_arith(agpt_scene*, int mode);
+/* Which of the library's shading kernels the next agpt_render / agpt_render_adaptive / agpt_li_batch on a committed scene launches,
+ * host-only (no GPU work): out4 = { texturing level 0 .. 4 (plain, colour textures, parameter maps, non-default samplers, normal
+ * maps), arithmetic (AGPT_SHADING_EXACT / _FAST), scene tables in LDS (1) or read from global memory (0: more than 256 primitives,
+ * 128 materials or 64 lights, or AGPT_SHADE_GLOBAL_TABLES set in the environment), an InfiniteAreaLight is present }.  Computed
+ * by the code those calls use, the environment read included.  All instantiations compute the same values; the query is for tests
+ * and profiling.  A NULL argument or an uncommitted scene returns AGPT_ERR_INVALID. */
+int agpt_scene_shade_variant(const agpt_scene*, int32_t out4[4]);
 /* agpt_bvh_build on the context's GPU: same arguments, same outputs byte for byte; synchronises with the context's stream.
  * *on_device_out (may be NULL) is 0 when a referenced coordinate is non-finite or the mesh's extent overflows: then the host
  * builder ran (the device folds are exact only on finite input).  HIP errors return AGPT_ERR_DEVICE / AGPT_ERR_NOMEM. */

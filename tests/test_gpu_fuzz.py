@@ -1,19 +1,25 @@
 """Seeded random scenes: every primitive kind, material kind and light kind the path supports, mixed at random (including
 degenerate, tiny and huge triangles, overlapping spheres, multi-triangle leaves, sphere-only and light-less scenes, thin-lens
-cameras and varying MaxDepth), rendered and ray-cast on the GPU and compared with the oracle bit for bit."""
+cameras and varying MaxDepth), rendered and ray-cast on the GPU and compared with the oracle bit for bit.  A second family decorates
+such scenes with the material features the oracle does not know -- colour images, roughness / metallic maps, samplers, normal maps --
+in forms that change nothing (a constant image of the material's own value, a flat normal map), so the oracle's render of the undecorated
+scene is still the reference while the shading kernels of every texturing level run, from LDS tables and from global memory."""
+import copy
 import os
 
 import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import bits, gpu_scene, oracle_scene, random_rays
+from helpers import bits, gpu_scene, oracle_render, oracle_scene, random_rays
 from oracle import binding as ob
+from texture_cases import FLAT
 
-pytestmark = pytest.mark.gpu
+F = np.float32
 
 
-def random_scene(seed):
+def random_scene(seed, textured=False):
+    """the scene of `seed`; textured: decorated by with_noop_textures (the undecorated scene is what it is without the flag)"""
     rng = np.random.RandomState(seed)
     d = ag.SceneDesc("fuzz-%d" % seed)
     mats = []
@@ -74,9 +80,58 @@ def random_scene(seed):
     eye = rng.uniform(-1, 1, 3) * 2 + np.array([0, 1, -5])
     d.set_camera(eye, rng.uniform(-0.5, 0.5, 3), [0, 1, 0], float(rng.choice([1.0, 16 / 9])), float(rng.uniform(25, 70)),
                  float(rng.choice([0.0, 0.0, 0.15])))
+    return with_noop_textures(d, seed) if textured else d
+
+
+def mesh_only_materials(desc):
+    analytic = {op[3] for op in desc.ops if op[0] in ("sphere", "plane")}
+    return sorted({op[5] for op in desc.ops if op[0] == "mesh"} - analytic)
+
+
+def with_noop_textures(desc, seed):
+    """desc with, at random, on the materials that only meshes use: a constant colour image of the material's colour, ONE constant
+    image (0, roughness, metallic) serving both parameter slots of a Disney material, a random sampler on each of those images, and a
+    flat normal map at a random scale -- each proven to change nothing (test_gpu_textures, _material_maps, _texture_filter, _normal_map).
+    `top` caps the features of a scene, so that the seeds spread over the texturing levels."""
+    rng = np.random.RandomState(77000 + seed)
+    d = copy.copy(desc)
+    d.ops = list(desc.ops)
+    materials = [op for op in desc.ops if op[0] == "material"]
+    top = int(rng.randint(1, 5))
+
+    def image(value):
+        t = d.add_texture(np.broadcast_to(np.asarray(value, F), (int(rng.randint(1, 5)), int(rng.randint(1, 6)), 3)))
+        if top >= 3 and rng.uniform() < 0.7:
+            d.set_texture_sampler(t, int(rng.randint(2)), int(rng.randint(3)), int(rng.randint(3)))
+        return t
+
+    for m in mesh_only_materials(desc):
+        _, kind, colour, roughness, metallic = materials[m]
+        if rng.uniform() < 0.7:
+            d.set_material_texture(m, image(colour))
+        if top >= 2 and kind == ag.MAT_DISNEY and rng.uniform() < 0.7:
+            t = image([0, roughness, metallic])
+            d.set_material_param_texture(m, ag.PARAM_ROUGHNESS, t, 1)
+            d.set_material_param_texture(m, ag.PARAM_METALLIC, t, 2)
+        if top >= 4 and rng.uniform() < 0.7:
+            d.set_material_normal_texture(m, image(FLAT[0, 0]), float(rng.choice([0.25, 1.0, 3.0, rng.uniform(0, 4)])))
     return d
 
 
+def texturing_level(desc):
+    """the level agpt_scene_commit derives (agpt_shade_kernels.h): the highest one a material needs"""
+    sampled = {op[1] for op in desc.ops if op[0] == "texture_sampler" and tuple(op[2:]) != (0, 0, 0)}
+    named = {op[2] for op in desc.ops if op[0] == "material_texture"} | {op[3] for op in desc.ops if op[0] == "material_param_texture"}
+    if any(op[0] == "material_normal_texture" and op[2] >= 0 for op in desc.ops):
+        return 4
+    if sampled & named:
+        return 3
+    if any(op[0] == "material_param_texture" for op in desc.ops):
+        return 2
+    return 1 if named else 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("seed", range(int(os.environ.get("AGPT_FUZZ_SEEDS", "24"))))
 def test_random_scene_matches_oracle(seed):
     d = random_scene(1000 + seed)
@@ -110,3 +165,56 @@ def test_random_scene_matches_oracle(seed):
         op_, _ = o.intersect(rays, any_hit=True)
         assert np.array_equal(gp["hit"], op_["hit"])
     g.close()
+
+
+# ---- the same, decorated with material features that change nothing ----------------------------------------------------------------
+# seeds of random_scene chosen on the CPU (test_textured_seeds_cover_levels_placements_and_env): a mesh-only material in each, the
+# texturing levels 1 .. 4 twice, once with and once without an environment map
+TEXTURED_SEEDS = [2001, 2029, 2006, 2021, 2011, 2028, 2049, 2027]
+
+
+def textured_case(seed):
+    """(decorated scene, plain scene, W, H, spp, depth, whether AGPT_SHADE_GLOBAL_TABLES is set, the variant the render must report)"""
+    plain, d = random_scene(seed), random_scene(seed, textured=True)
+    rng = np.random.RandomState(seed)
+    W, H, spp = int(rng.choice([24, 40, 64])), int(rng.choice([24, 36])), int(rng.choice([1, 3]))
+    depth = int(rng.choice([1, 2, 5, 5, 8]))
+    knob = bool(rng.uniform() < 0.5)
+    assert d.n_prims <= 256 and d.n_materials <= 128 and d.n_lights <= 64      # (below the limits: the knob alone decides the placement)
+    variant = (texturing_level(d), 0, int(not knob), int(any(op[0] == "env_light" for op in d.ops)))
+    return d, plain, W, H, spp, depth, knob, variant
+
+
+def test_textured_seeds_cover_levels_placements_and_env():
+    """on the CPU: what the eight cases will run (each asserts on the GPU that it does)"""
+    variants = []
+    for seed in TEXTURED_SEEDS:
+        d, plain, *_, variant = textured_case(seed)
+        assert any(op[0] == "mesh" for op in plain.ops) and mesh_only_materials(plain) and d.n_textures >= 1
+        kinds = [op[0] for op in d.ops]       # the plain scene's calls, then texture calls alone
+        assert kinds[:len(plain.ops)] == [op[0] for op in plain.ops]
+        assert set(kinds[len(plain.ops):]) <= {"texture", "material_texture", "material_param_texture", "material_normal_texture", "texture_sampler"}
+        variants.append(variant)
+    print("textured fuzz variants (level, fast, lds, env):", variants)
+    assert len({v[0] for v in variants}) >= 3
+    assert {v[2] for v in variants} == {0, 1}
+    assert any(v[3] for v in variants)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", TEXTURED_SEEDS)
+def test_random_textured_scene_matches_oracle(seed, monkeypatch):
+    d, plain, W, H, spp, depth, knob, variant = textured_case(seed)
+    oacc, ost = oracle_render(plain, W, H, spp, depth, seed_base=seed)
+    monkeypatch.delenv("AGPT_SHADE_GLOBAL_TABLES", raising=False)
+    if knob:
+        monkeypatch.setenv("AGPT_SHADE_GLOBAL_TABLES", "1")
+    g = gpu_scene(d)
+    try:
+        print("textured fuzz %d: shade variant (level, fast, lds, env) = %s, %d textures" % (seed, g.shade_variant(), d.n_textures))
+        assert g.shade_variant() == variant
+        gacc, gst = ag.PathTracer(depth).render_to_host(g, W, H, spp, seed_base=seed)
+    finally:
+        g.close()
+    assert np.array_equal(bits(gacc[..., :3]), bits(oacc[..., :3])), d.name
+    assert (gst.closest_rays, gst.anyhit_rays, gst.outliers, gst.shaded_vertices) == (ost.closest_rays, ost.anyhit_rays, ost.outliers, ost.shaded_vertices)

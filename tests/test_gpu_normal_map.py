@@ -16,12 +16,11 @@ import texture_model as tm
 from denoise_features import host_features, primitive_table
 from helpers import bits, build_cpp_example, close_fraction, compare_with_model, gpu_context, gpu_scene, oracle_scene, render
 from oracle import binding as ob
-from texture_cases import varying_lights_and_camera, varying_mesh
+from texture_cases import FLAT, varying_lights_and_camera, varying_mesh
 
 F = np.float32
 BILINEAR, NEAREST = ag.FILTER_BILINEAR, ag.FILTER_NEAREST
 KINDS = {"disney": ag.MAT_DISNEY, "mirror": ag.MAT_MIRROR, "diffuse": ag.MAT_DIFFUSE_ONLY}
-FLAT = np.broadcast_to(np.array([.5, .5, 1], F), (4, 4, 3))
 
 
 # ---- 1. the perturbation alone ---------------------------------------------------------------------------------------------

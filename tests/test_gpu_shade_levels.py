@@ -1,6 +1,9 @@
 """launch_shading's table of shading units, cell by cell: a ladder of scenes S0 .. S4 on one quad, each needing exactly its texturing
-level (agpt_shade_kernels.h), rendered in both arithmetics.  The exact kernels of every level are pinned to the oracle by the tests of
-their own features (test_gpu_textures, _material_maps, _texture_filter, _normal_map); here they are the reference: FAST must land
+level (agpt_shade_kernels.h), rendered in both arithmetics.  The exact kernels of every level are pinned to the oracle in their
+<LDS tables, no ENV> instantiation by the tests of their own features (test_gpu_textures, _material_maps, _texture_filter, _normal_map),
+and in the instantiations with an environment map or with the scene tables in global memory by test_gpu_shade_matrix.py (every level
+against the oracle under ENV, global tables byte for byte against LDS tables and at the three count limits) and the textured fuzz of
+test_gpu_fuzz.py; here they are the reference: FAST must land
 within the project's L2 rule (test_gpu_shading_fast: >= 99 % of pixels with every channel within 1e-3 |exact| + 1e-6) of the EXACT
 render of the same level, and the EXACT renders of neighbouring levels must be far apart under that rule (fewer than 90 % of pixels
 agree), so a launcher one level off cannot pass.
@@ -77,6 +80,7 @@ def renders(level):
     try:
         pt = ag.PathTracer(DEPTH)
         out = {}
+        assert g.shade_variant()[0] == level
         for arith in ("exact", "fast"):
             g.set_shading_arith(arith)
             out[arith] = [pt.render_to_host(g, W, H, SPP, seed_base=SEED)[0][..., :3].reshape(-1, 3) for _ in range(2)]

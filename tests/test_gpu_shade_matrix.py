@@ -1,0 +1,384 @@
+"""All 40 shading kernels launch_shading can dispatch -- texturing level 0 .. 4 x arithmetic (exact, fast) x scene tables (LDS copies,
+global memory) x ENV (an InfiniteAreaLight is present) -- each run and pinned.  Every case first asserts, through
+Scene.shade_variant() (agpt_scene_shade_variant: the code begin_wavefront dispatches by), that it runs the cell it claims.
+
+  A  table placement is invisible: the ladder scenes of test_gpu_shade_levels.py, with and without an environment map, rendered from
+     LDS tables and again under AGPT_SHADE_GLOBAL_TABLES -- the same bytes and ray counts, in both arithmetics (every unit is built with
+     -ffp-contract=off and FAST uses the same intrinsics in both instantiations).  All 40 cells.
+  B  the LDS cells of levels 1 .. 4 with and without ENV against the oracle.  The oracle knows no textures: the features are stacked
+     on the plateau meshes (texture_cases.py), where every lookup gives one value per mesh that the oracle's scene carries as a plain
+     material -- EXACT bit for bit, FAST byte-identical to FAST on that plain scene and within the L2 rule (>= 99 % of pixels
+     within 1e-3) of the oracle.  The flat normal map of those scenes cannot show that the normal table is read, so the tilted quads
+     of test_gpu_normal_map.py run under an environment map as well, by that file's criteria, from both table placements.
+  C  the limits reached by counts: 128 / 129 materials, 64 / 65 lights, 256 / 257 primitives on the level-4 ENV scene, the used
+     records at the END of each table; EXACT against the oracle bit for bit on both sides of each limit.
+  D  is in test_gpu_fuzz.py: random scenes decorated with no-op textures.
+
+The last test asserts that the cases of this file ran all 40 cells.
+
+Observed on an MI355X: every EXACT case 4096 of 4096 pixels bit-identical with equal ray counts (41,580 .. 46,550 rays); FAST within
+1e-3 of the oracle on 1.00000 of the pixels at every level -- the first run gave 0.96997 at level 2, on FAST's own arithmetic, not on a
+table: the half vector of the smooth Disney plateaus (agpt_shade_arith.h: sh_normalize_rn); the tilted quads under
+the environment map 1.00000 of the pixels at 2 spp and mean rel below 1e-7 at 16 spp in both arithmetics and placements.  With a
+scratch library that never launches the ENV kernels all twelve env = 1 cases of part B fail (879 of 4096 pixels bit-identical, FAST
+0.22 and the quads 0.30 of the pixels within 1e-3) and the eight env = 0 cases pass."""
+import functools
+import itertools
+
+import numpy as np
+import pytest
+
+import ag_pathtracer_amd as ag
+from helpers import bits, close_fraction, gpu_scene, oracle_render, render
+from test_gpu_normal_map import mean_rel, quad_scene
+from test_gpu_shade_levels import ladder_scene
+from texture_cases import (FLAT, KINDS, PALETTE, PARAM_TEXELS, check_li_against_oracle, matrix_samplers, palette_lights_and_camera, plateau,
+                           plateau_meshes, plateau_values)
+
+F = np.float32
+KNOB = "AGPT_SHADE_GLOBAL_TABLES"
+ARITHS = ["exact", "fast"]
+STATS = ("closest_rays", "anyhit_rays", "answered_rays", "outliers", "shaded_vertices")
+SEEN = set()          # the (level, fast, lds_tables, env) cells the cases of this file have run
+
+
+def env_map():
+    return ag.scenes.synthetic_hdr(16, 8)
+
+
+def claim(g, level, arith, lds, env):
+    """g is about to run k_shade's cell (level, arith, lds, env): asserted, printed, noted for the last test"""
+    cell = (int(level), int(arith == "fast"), int(lds), int(env))
+    got = g.shade_variant()
+    print("shade variant (level, fast, lds, env) = %s" % (got,))
+    assert got == cell
+    SEEN.add(cell)
+
+
+# ---- A. table placement is invisible -------------------------------------------------------------------------------------------
+WA = HA = 48
+SPP_A, DEPTH_A, SEED_A = 4, 3, 0x5EED
+
+
+def ladder(level, env):
+    d = ladder_scene(level)
+    if env:
+        d.add_infinite_area_light(env_map())
+    return d
+
+
+def ladder_render(level, arith, env, lds):
+    g = gpu_scene(ladder(level, env))
+    try:
+        g.set_shading_arith(arith)
+        claim(g, level, arith, lds, env)
+        acc, st = ag.PathTracer(DEPTH_A).render_to_host(g, WA, HA, SPP_A, seed_base=SEED_A)
+    finally:
+        g.close()
+    return acc, {name: int(getattr(st, name)) for name in STATS}
+
+
+@functools.lru_cache(None)
+def ladder_render_lds(level, arith, env):
+    return ladder_render(level, arith, env, 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("env", [0, 1])
+@pytest.mark.parametrize("arith", ARITHS)
+@pytest.mark.parametrize("level", [0, 1, 2, 3, 4])
+def test_table_placement_is_invisible(level, arith, env, monkeypatch):
+    monkeypatch.delenv(KNOB, raising=False)
+    acc, st = ladder_render_lds(level, arith, env)
+    monkeypatch.setenv(KNOB, "1")
+    acc_g, st_g = ladder_render(level, arith, env, 0)
+    monkeypatch.delenv(KNOB)
+    same = (bits(acc_g) == bits(acc)).all(-1)
+    print("level %d %s env %d: %d of %d pixels byte-identical from global tables; LDS %s, global %s" % (level, arith, env, same.sum(), same.size, st, st_g))
+    assert acc_g.tobytes() == acc.tobytes()
+    assert st_g == st
+    if env:      # the environment map is seen: a dead ENV branch would render the scene without it
+        plain, _ = ladder_render_lds(level, arith, 0)
+        differ = (bits(acc[..., :3]) != bits(plain[..., :3])).any(-1).mean()
+        print("level %d %s: the environment map changes %.4f of the pixels" % (level, arith, differ))
+        assert acc.tobytes() != plain.tobytes()
+
+
+# ---- B. the stacked levels against the oracle ----------------------------------------------------------------------------------
+WB = HB = 64
+SPP_B, DEPTH_B = 3, 5
+NO_PAD = (0, 0, 0)
+
+
+def matrix_scene(level, env, textured, pad=NO_PAD):
+    """The plateau meshes, mesh k of kind KINDS[k % 5] (three Disney kinds, a mirror, a diffuse one), under the palette scene's lights and,
+    with env, an environment map.  textured (the GPU's scene): ONE material per kind; level >= 1 colour from plateau(PALETTE), level >= 2
+    the Disney kinds' roughness and metallic from channels 1 and 2 of plateau(PARAM_TEXELS), level >= 3 both images BILINEAR, the colour
+    wrapped MIRROR and the parameters CLAMP (the meshes outside [0, 1] tell the wraps apart), level 4 the FLAT normal map at scale .25
+    on every mesh material.  Not textured (the oracle's scene): one plain material per mesh with the values the model gives for those
+    lookups.  pad = (materials, lights, primitives) adds that many records AHEAD of the used ones: unused Disney materials with
+    distinct parameters, dim uniform infinite lights, small spheres of a plain material among the meshes."""
+    pad_materials, pad_lights, pad_prims = pad
+    (cf, cw), (pf, pw) = matrix_samplers(level)
+    d = ag.SceneDesc("matrix-L%d-env%d-%s-pad%d.%d.%d" % ((level, env, "textured" if textured else "plain") + tuple(pad)))
+    for i in range(pad_materials):
+        d.add_material(ag.MAT_DISNEY, [.1 + .8 * ((7 * i) % 11) / 10, .1 + .8 * ((3 * i) % 13) / 12, .1 + .8 * ((5 * i) % 17) / 16], (i % 9) / 8, (i % 5) / 4)
+    if pad_prims:
+        rng = np.random.RandomState(41)
+        grey = d.add_material(ag.MAT_DIFFUSE_ONLY, [.6, .6, .55])
+        for i in range(pad_prims):
+            d.add_sphere([rng.uniform(-3.2, 3.2), rng.uniform(-0.8, 2.2), rng.uniform(-3.2, 3.2)], float(rng.uniform(0.04, 0.11)), grey)
+    meshes = plateau_meshes()
+    disney = [t == ag.MAT_DISNEY for t, _, _ in KINDS]
+    if textured:
+        mats = [d.add_material(t, [.5, .5, .5], r, m) for t, r, m in KINDS]
+        colour = d.add_texture(plateau(PALETTE))
+        for m in mats:
+            d.set_material_texture(m, colour)
+        if level >= 2:
+            params = d.add_texture(plateau(PARAM_TEXELS))
+            for m in mats:
+                if disney[m - mats[0]]:
+                    d.set_material_param_texture(m, ag.PARAM_ROUGHNESS, params, 1)
+                    d.set_material_param_texture(m, ag.PARAM_METALLIC, params, 2)
+        if level >= 3:
+            d.set_texture_sampler(colour, cf, cw, cw)
+            d.set_texture_sampler(params, pf, pw, pw)
+        if level >= 4:
+            flat = d.add_texture(FLAT)
+            for m in mats:
+                d.set_material_normal_texture(m, flat, 0.25)
+        for k, (v, n, uv, idx) in enumerate(meshes):
+            d.add_mesh(v, n, uv, idx, mats[k % len(KINDS)], 1)
+    else:
+        colours, params = plateau_values(PALETTE, cw, cf), plateau_values(PARAM_TEXELS, pw, pf)
+        for k, (v, n, uv, idx) in enumerate(meshes):
+            t, r, m = KINDS[k % len(KINDS)]
+            if level >= 2 and t == ag.MAT_DISNEY:
+                r, m = float(params[k, 1]), float(params[k, 2])
+            d.add_mesh(v, n, uv, idx, d.add_material(t, colours[k], r, m), 1)
+    for i in range(pad_lights):
+        d.add_uniform_infinite_light([.01 + .0001 * i, .01 + .00007 * (i % 7), .012 - .00005 * (i % 5)])
+    palette_lights_and_camera(d)
+    if env:
+        d.add_infinite_area_light(env_map())
+    return d
+
+
+def plain_level(level):
+    """the level whose plain scene `level` shares: what the oracle renders depends on the samplers alone from level 2 up"""
+    return min(level, 3)
+
+
+@functools.lru_cache(None)
+def matrix_oracle(level, env, pad=NO_PAD):
+    """the oracle's render of the plain scene, (rgb [H, W, 3], rays, outliers); level is a plain_level"""
+    acc, st = oracle_render(matrix_scene(level, env, False, pad), WB, HB, SPP_B, DEPTH_B)
+    acc.setflags(write=False)
+    return acc[..., :3], st.rays, int(st.outliers)
+
+
+@functools.lru_cache(None)
+def matrix_fast_plain(level, env, pad=NO_PAD):
+    """the GPU's own FAST render of the plain scene (FAST is compared with FAST); level is a plain_level"""
+    g = gpu_scene(matrix_scene(level, env, False, pad))
+    try:
+        acc, st = render(g, WB, HB, SPP_B, DEPTH_B, arith="fast")
+    finally:
+        g.close()
+    acc.setflags(write=False)
+    return acc, st.rays
+
+
+def test_matrix_scenes_keep_their_kinds():
+    """the construction, on the CPU: a mirror kind, and Disney meshes with metallic 0, .5 and 1 at every level (the lookups themselves:
+    test_gpu_texture_filter.test_plateau_footprints)"""
+    for level, env in itertools.product((1, 2, 3, 4), (0, 1)):
+        plain, textured = matrix_scene(level, env, False), matrix_scene(level, env, True)
+        mats = [op for op in plain.ops if op[0] == "material"]
+        assert len(mats) == len(plateau_meshes()) and textured.n_materials == len(KINDS)
+        assert any(op[1] == ag.MAT_MIRROR for op in mats)
+        assert {0.0, 0.5, 1.0} <= {op[4] for op in mats if op[1] == ag.MAT_DISNEY}
+        assert plain.n_lights == textured.n_lights == 2 + env and plain.n_prims == textured.n_prims == len(plateau_meshes()) + 1
+        assert (textured.ops[-1][0] == "env_light") == bool(env)
+
+
+def check_exact(g, level, env, pad=NO_PAD, distinct=True):
+    want, rays, outliers = matrix_oracle(plain_level(level), env, pad)
+    acc, st = render(g, WB, HB, SPP_B, DEPTH_B)
+    same = (bits(acc[..., :3]) == bits(want)).all(-1)
+    n_distinct = len(np.unique(bits(acc[..., :3]).reshape(-1, 3), axis=0))
+    print("level %d env %d pad %s: %d of %d pixels bit-identical to the oracle, rays %d / %d, outliers %d / %d, %d distinct pixel values" % (
+        level, env, pad, same.sum(), same.size, st.rays, rays, st.outliers, outliers, n_distinct))
+    assert same.all()
+    assert st.rays == rays and st.outliers == outliers
+    if distinct:
+        assert n_distinct > WB * HB // 2
+    return acc
+
+
+def check_fast(g, level, env, pad=NO_PAD, oracle=True):
+    want, want_rays = matrix_fast_plain(plain_level(level), env, pad)
+    acc, st = render(g, WB, HB, SPP_B, DEPTH_B, arith="fast")
+    same = (bits(acc) == bits(want)).all(-1)
+    print("level %d env %d pad %s FAST: %d of %d pixels byte-identical to FAST on the plain scene, rays %d / %d" % (level, env, pad, same.sum(), same.size, st.rays, want_rays))
+    assert acc.tobytes() == want.tobytes() and st.rays == want_rays
+    if oracle:
+        ref, _, _ = matrix_oracle(plain_level(level), env, pad)
+        exact, _ = render(g, WB, HB, SPP_B, DEPTH_B, arith="exact")
+        assert acc.tobytes() != exact.tobytes()
+        close = close_fraction(acc[..., :3].reshape(-1, 3), ref.reshape(-1, 3), 1e-3)
+        print("level %d env %d FAST: %.5f of the pixels within 1e-3 of the oracle" % (level, env, close))
+        assert close >= 0.99
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("arith", ARITHS)
+@pytest.mark.parametrize("env", [0, 1])
+@pytest.mark.parametrize("level", [1, 2, 3, 4])
+def test_stacked_levels_match_the_oracle(level, env, arith, monkeypatch):
+    monkeypatch.delenv(KNOB, raising=False)
+    g = gpu_scene(matrix_scene(level, env, True))
+    try:
+        g.set_shading_arith(arith)
+        claim(g, level, arith, 1, env)
+        if arith == "exact":
+            check_exact(g, level, env)
+        else:
+            check_fast(g, level, env)
+    finally:
+        g.close()
+
+
+# the tilted quads of test_gpu_normal_map.py under an environment map: the normal table is read, from either placement
+def quad_env_scene(mode):
+    d = quad_scene(mode)
+    d.add_infinite_area_light(env_map())
+    return d
+
+
+@functools.lru_cache(None)
+def quad_env_oracle(mode, spp):
+    acc, _ = oracle_render(quad_env_scene(mode), 64, 64, spp, 5)
+    return acc[..., :3].reshape(-1, 3)
+
+
+def test_quad_construction_under_the_environment_map_on_the_cpu():
+    """the precondition test_gpu_normal_map.test_quad_construction_on_the_cpu states for the oracle alone, re-checked with the environment
+    map in the scene: one ulp on the baked normals stays inside the criteria, the untilted quads fail them.  It holds at the map's own
+    strength (observed: 1.00000 of the pixels, mean rel below 3e-8; untilted 0.150), so the light is left as it is."""
+    frac = close_fraction(quad_env_oracle("baked+1", 2), quad_env_oracle("baked", 2), 1e-3)
+    rel = mean_rel(quad_env_oracle("baked+1", 16), quad_env_oracle("baked", 16))
+    flat = close_fraction(quad_env_oracle("flat", 2), quad_env_oracle("baked", 2), 1e-3)
+    print("oracle under the environment map, baked normals moved by one ulp: %.5f of the pixels within 1e-3, mean rel %s; untilted quads: %.5f" % (frac, rel, flat))
+    assert frac >= 0.99 and (rel <= 1e-3).all()
+    assert flat < 0.5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lds", [1, 0])
+@pytest.mark.parametrize("arith", ARITHS)
+def test_normal_table_is_read_under_the_environment_map(arith, lds, monkeypatch):
+    monkeypatch.delenv(KNOB, raising=False)
+    if not lds:
+        monkeypatch.setenv(KNOB, "1")
+    g = gpu_scene(quad_env_scene("mapped"))
+    try:
+        g.set_shading_arith(arith)
+        claim(g, 4, arith, lds, 1)
+        got2, _ = render(g, 64, 64, 2, arith=arith)
+        got16, _ = render(g, 64, 64, 16, arith=arith)
+    finally:
+        g.close()
+    frac = close_fraction(got2[..., :3].reshape(-1, 3), quad_env_oracle("baked", 2), 1e-3)
+    rel = mean_rel(got16[..., :3].reshape(-1, 3), quad_env_oracle("baked", 16))
+    print("normal-mapped quads under the environment map (%s, lds %d) against the oracle on baked normals: %.5f of the pixels within 1e-3 at 2 spp, "
+          "mean rel %s at 16 spp" % (arith, lds, frac, rel))
+    assert frac >= 0.99
+    assert (rel <= 1e-3).all()
+
+
+# ---- C. the limits, reached by counts ------------------------------------------------------------------------------------------
+N_MESHES = len(plateau_meshes())
+LIMITS = {   # what a pad adds to, with the count of the level-4 ENV scene before padding, and the largest count the LDS copies hold
+    "materials": (0, len(KINDS), 128),
+    "lights": (1, 3, 64),
+    "primitives": (2, N_MESHES + 1, 256),       # (the pad spheres bring a material of their own)
+}
+LIMIT_CASES = [(what, over) for what in LIMITS for over in (0, 1)]
+
+
+def limit_pad(what, over):
+    slot, base, limit = LIMITS[what]
+    pad = [0, 0, 0]
+    pad[slot] = limit + over - base
+    return tuple(pad)
+
+
+def test_limit_scenes_sit_on_both_sides_of_each_limit():
+    """the construction, on the CPU: the counts, and the used records at the end of their tables"""
+    for what, over in LIMIT_CASES:
+        d = matrix_scene(4, 1, True, limit_pad(what, over))
+        count = {"materials": d.n_materials, "lights": d.n_lights, "primitives": d.n_prims}
+        assert count[what] == LIMITS[what][2] + over
+        assert all(count[other] <= LIMITS[other][2] for other in LIMITS if other != what)
+        kinds = [op[0] for op in d.ops]
+        if what == "materials":      # the used materials are the last five
+            meshes = [op for op in d.ops if op[0] == "mesh"]
+            assert sorted({op[5] for op in meshes}) == list(range(d.n_materials - len(KINDS), d.n_materials))
+        elif what == "lights":       # the area light, the sky and the environment map at the last three indices
+            lights = [k for k in kinds if k in ("area_light", "infinite_light", "env_light")]
+            assert lights[-3:] == ["area_light", "infinite_light", "env_light"] and set(lights[:-3]) == {"infinite_light"}
+            assert len({op[1].tobytes() for op in d.ops if op[0] == "infinite_light"}) == d.n_lights - 2
+        else:                        # every mesh record behind the spheres; the area light's sphere is the last primitive
+            prims = [k for k in kinds if k in ("mesh", "sphere", "plane", "area_light")]
+            assert prims == ["sphere"] * (d.n_prims - N_MESHES - 1) + ["mesh"] * N_MESHES + ["area_light"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("what,over", LIMIT_CASES)
+def test_limits_switch_the_tables_and_nothing_else(what, over, monkeypatch):
+    monkeypatch.delenv(KNOB, raising=False)
+    pad = limit_pad(what, over)
+    d = matrix_scene(4, 1, True, pad)
+    assert {"materials": d.n_materials, "lights": d.n_lights, "primitives": d.n_prims}[what] == LIMITS[what][2] + over
+    g = gpu_scene(d)
+    try:
+        claim(g, 4, "exact", 1 - over, 1)
+        check_exact(g, 4, 1, pad, distinct=False)
+    finally:
+        g.close()
+
+
+@pytest.mark.gpu
+def test_li_batch_from_global_tables_with_129_materials(monkeypatch):
+    monkeypatch.delenv(KNOB, raising=False)
+    pad = limit_pad("materials", 1)
+    g = gpu_scene(matrix_scene(4, 1, True, pad))
+    try:
+        claim(g, 4, "exact", 0, 1)
+        check_li_against_oracle(g, matrix_scene(3, 1, False, pad), DEPTH_B, 300)
+    finally:
+        g.close()
+
+
+@pytest.mark.gpu
+def test_fast_from_global_tables_with_129_materials(monkeypatch):
+    monkeypatch.delenv(KNOB, raising=False)
+    pad = limit_pad("materials", 1)
+    g = gpu_scene(matrix_scene(4, 1, True, pad))
+    try:
+        g.set_shading_arith("fast")
+        claim(g, 4, "fast", 0, 1)
+        check_fast(g, 4, 1, pad, oracle=False)
+    finally:
+        g.close()
+
+
+# ---- every cell ran ------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_every_variant_ran():
+    """the cases above, run as one file, have claimed all 40 (level, fast, lds, env) cells"""
+    cells = set(itertools.product(range(5), (0, 1), (0, 1), (0, 1)))
+    print("cells run: %d of %d; missing: %s" % (len(SEEN & cells), len(cells), sorted(cells - SEEN)))
+    assert SEEN == cells

@@ -111,6 +111,49 @@ def test_l1_bsdf_known_answers(mode):
         assert v >= (1.0 if mode == "exact" else 0.999), (k, frac)
 
 
+def peak_directions(n=512, seed=13):
+    """(wo, wi) in the shading frame with the half vector inside the narrowest lobe the materials have -- alpha at its clamp of .001 --:
+    tan(theta_h) = .001 t, t in [0, 3], where sin^2(theta_h) = 1 - wh.z^2 is about 1e-6 and an ulp of wh.z is a tenth of D"""
+    rng = np.random.RandomState(seed)
+    wo = rng.normal(size=(n, 3))
+    wo[:, 2] = np.abs(wo[:, 2]) + 0.2
+    wo /= np.linalg.norm(wo, axis=1, keepdims=True)
+    tan, phi = 1e-3 * rng.uniform(0, 3, n), rng.uniform(0, 2 * np.pi, n)
+    wh = np.stack([tan * np.cos(phi), tan * np.sin(phi), np.ones(n)], 1)
+    wh /= np.linalg.norm(wh, axis=1, keepdims=True)
+    wi = 2 * (wo * wh).sum(1, keepdims=True) * wh - wo
+    return wo.astype(np.float32), wi.astype(np.float32)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_l1_bsdf_at_the_peak_of_the_narrowest_lobe(mode):
+    """L1 where the fixture's materials (roughness >= .25) do not reach: the oracle's f and pdf of smooth Disney materials at half
+    vectors inside the lobe.  The half vector keeps normalize's bits in the fast units (agpt_shade_arith.h: sh_normalize_rn); through
+    v_rsq_f32 the fast f and pdf were off by up to a tenth here."""
+    wo, wi = peak_directions()
+    d = ag.SceneDesc("peak")
+    mats = [d.add_material(ag.MAT_DISNEY, [0.944, 0.776, 0.373], rough, metal) for rough, metal in ((0.0, 1.0), (0.02, 0.0), (0.0, 0.5))]
+    d.add_sphere([0, 0, 0], 1.0, mats[0])
+    o, s = oracle_scene(d), gpu_scene(d)
+    s.set_shading_arith(mode)
+    ok = []
+    try:
+        for m in mats:
+            f, pdf = s.bsdf_eval(m, wo, wi)
+            want = [o.bsdf_eval(m, a, b) for a, b in zip(wo, wi)]
+            want_f, want_pdf = np.array([w[0] for w in want], np.float32), np.array([w[1] for w in want], np.float32)
+            assert (want_pdf > 100).mean() > 0.9                 # inside the lobe: its pdf is 1 / (pi alpha^2) ~ 3e5 at the centre
+            ok.append(np.abs(f - want_f) <= 1e-4 * np.abs(want_f) + 1e-6)
+            ok.append((np.abs(pdf - want_pdf) <= 1e-4 * np.abs(want_pdf) + 1e-6)[:, None])
+            if mode == "exact":
+                assert f.tobytes() == want_f.tobytes() and pdf.tobytes() == want_pdf.tobytes()
+    finally:
+        s.close()
+    frac = float(np.concatenate([a.reshape(-1) for a in ok]).mean())
+    print(mode, "f / pdf entries within rel 1e-4 of the oracle at the lobe's peak: %.5f" % frac)
+    assert frac >= (1.0 if mode == "exact" else 0.999)
+
+
 # ---- L2 ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("name", ["c2", "c3", "c5", "simple", "lens_mirror"])

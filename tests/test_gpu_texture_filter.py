@@ -14,33 +14,14 @@ import ag_pathtracer_amd as ag
 import texture_filter_model as fm
 import texture_model as tm
 from denoise_features import host_features, primitive_table
-from helpers import bits, build_cpp_example, gpu_scene, oracle_render, oracle_scene, render
-from oracle import binding as ob
-from texture_cases import K, PALETTE, palette_lights_and_camera, varying_lights_and_camera, varying_mesh, without_textures
+from helpers import bits, build_cpp_example, gpu_scene, oracle_render, render
+from texture_cases import (K, KINDS, OUTSIDE, PALETTE, PARAM_TEXELS, PARAMS, check_li_against_oracle, matrix_samplers, palette_lights_and_camera, plateau,
+                           plateau_meshes, plateau_values, varying_lights_and_camera, varying_mesh, without_textures)
 
 F = np.float32
 R, M = ag.PARAM_ROUGHNESS, ag.PARAM_METALLIC
 BILINEAR, NEAREST = ag.FILTER_BILINEAR, ag.FILTER_NEAREST
 WRAPS = {"repeat": ag.WRAP_REPEAT, "clamp": ag.WRAP_CLAMP, "mirror": ag.WRAP_MIRROR}
-
-
-def check_li_against_oracle(g, plain_desc, depth, n=1000):
-    """agpt_li_batch on camera rays against the oracle's Li on the plain scene: values and RNG end states"""
-    o = oracle_scene(plain_desc, depth)
-    rng = np.random.RandomState(11)
-    rays, states = np.zeros(n, ag.RAY_DTYPE), np.zeros(n, np.uint32)
-    for i in range(n):
-        rays[i], states[i] = o.camera_ray(float(rng.uniform()), float(rng.uniform()), rng=int(rng.randint(1, 2 ** 31 - 1)))
-    want, after = np.zeros((n, 3), F), np.zeros(n, np.uint32)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        for i in range(n):
-            want[i], after[i], _ = o.li(rays[i], int(states[i]))
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-    got, got_after, _ = ag.PathTracer(depth).Li(g, rays, states)
-    print("Li: %d of %d values bit-identical, %d RNG end states" % ((bits(got) == bits(want)).all(-1).sum(), n, (got_after == after).sum()))
-    assert np.array_equal(bits(got), bits(want)) and np.array_equal(got_after, after)
 
 
 # ---- 1. a constant image is no image, whatever the sampler -------------------------------------------------------------------
@@ -204,60 +185,6 @@ def test_first_hit_albedo_is_the_model(image, filter, wrap):
 
 
 # ---- 3. tap selection along whole paths ------------------------------------------------------------------------------------
-# (roughness, metallic) per plateau: metallic 0, 1 and .5 -- a wrong tap changes the lobe set and the ray count --, roughness below the
-# .001 clamp of alpha, .35 and 1
-PARAMS = np.array([[1.0, 0.0], [.35, 1.0], [0.0, .5], [.02, 0.0], [.6, .5], [0.0, 1.0], [.02, 1.0], [.5, .3]], F)
-KINDS = [(ag.MAT_DISNEY, 1.0, 0.0), (ag.MAT_DISNEY, 0.35, 1.0), (ag.MAT_MIRROR, 0.0, 0.0), (ag.MAT_DIFFUSE_ONLY, 0.0, 0.0),
-         (ag.MAT_DISNEY, 0.6, 0.5)]
-# meshes beyond the first K: (plateau their footprint would have inside [0, 1], whole periods it is shifted by).  REPEAT reads the
-# plateau itself, CLAMP the last (shift > 0) or the first (shift < 0) texel, MIRROR with an odd shift plateau K - 1 - j
-OUTSIDE = [(2, 1), (5, -1), (1, 2), (3, -3)]
-
-
-def plateau(values):
-    """[K, C] -> image [1, 2K, 3]: texels 2k and 2k + 1 both hold values[k] (C < 3: zero-filled)"""
-    values = np.asarray(values, F)
-    img = np.zeros((1, 2 * len(values), 3), F)
-    img[0, :, :values.shape[1]] = np.repeat(values, 2, axis=0)
-    return img
-
-
-def plateau_meshes():
-    """K + len(OUTSIDE) meshes -- a floor, K - 1 blobs around the origin, more blobs above them.  Mesh k < K has every u strictly
-    between the centres of texels 2k and 2k + 1 of a 2K x 1 image (a tenth of a texel from both), so both horizontal taps of a
-    BILINEAR lookup are that pair; the others have such a footprint shifted by whole periods, outside [0, 1].  v is anywhere in
-    [-2, 3]: the image has one row."""
-    rng = np.random.RandomState(5)
-    meshes = []
-    for k in range(K + len(OUTSIDE)):
-        if k == 0:
-            v, n, t, idx = ag.scenes.grid_mesh(lambda U, V: np.stack([-6 + 12 * U, -1 + 0 * U, -6 + 12 * V], -1), 6, 6)
-        elif k < K:
-            a = 2 * np.pi * k / (K - 1)
-            v, n, t, idx = ag.scenes.blob_mesh(10, 8, center=(2.4 * np.cos(a), -0.2 + 0.5 * (k % 3), 2.4 * np.sin(a)), radius=0.85, seed=k)
-        else:
-            a = 2 * np.pi * (k - K + .5) / len(OUTSIDE)
-            v, n, t, idx = ag.scenes.blob_mesh(10, 8, center=(1.1 * np.cos(a), 1.5, 1.1 * np.sin(a)), radius=0.6, seed=k)
-        j, shift = (k, 0) if k < K else OUTSIDE[k - K]
-        u = (2 * j + 0.6 + 0.8 * rng.uniform(size=len(v))) / (2 * K) + shift
-        meshes.append((v, n, np.stack([u, rng.uniform(-2, 3, len(v))], 1).astype(F), idx))
-    return meshes
-
-
-def plateau_values(values, wrap):
-    """per mesh the value a BILINEAR lookup of plateau(values) gives at EVERY vertex uv of the mesh, from the model (asserts that it
-    is one value per mesh, and that the position keeps 0.05 texels from both centres)"""
-    img = plateau(values)
-    out = []
-    for v, n, uv, idx in plateau_meshes():
-        c = fm.value(img, uv[:, 0], uv[:, 1], BILINEAR, wrap, wrap)
-        assert (bits(c) == bits(c[0])).all()
-        x0, x1, y0, y1, fx, fy = fm.taps(img, uv[:, 0], uv[:, 1], BILINEAR, wrap, wrap)
-        assert (fx > 0.05).all() and (fx < 0.95).all() and (y0 == 0).all() and (y1 == 0).all()
-        out.append(c[0, :np.asarray(values).shape[1]])
-    return np.array(out, F)
-
-
 def test_plateau_footprints():
     """the construction, checked on the CPU with the model"""
     got = {w: plateau_values(PALETTE, WRAPS[w]) for w in WRAPS}
@@ -275,6 +202,19 @@ def test_plateau_footprints():
     for v, n, uv, idx in plateau_meshes():
         for w in WRAPS.values():
             assert np.array_equal(fm.value(plateau(PALETTE), uv[:, 0], uv[:, 1], NEAREST, w, w), fm.value(plateau(PALETTE), uv[:, 0], uv[:, 1], BILINEAR, w, w))
+
+
+    # the stacked scenes of test_gpu_shade_matrix.py: one value per mesh (plateau_values asserts it) under every sampler they use, the
+    # colour from the plateau MIRROR picks, the parameters from the one CLAMP picks
+    for level in (1, 2, 3, 4):
+        (cf, cw), (pf, pw) = matrix_samplers(level)
+        colour, params = plateau_values(PALETTE, cw, cf), plateau_values(PARAM_TEXELS, pw, pf)[:, 1:]
+        assert colour.shape == (K + len(OUTSIDE), 3) and params.shape == (K + len(OUTSIDE), 2)
+        assert np.array_equal(colour[:K], PALETTE) and np.array_equal(params[:K], PARAMS)
+        for i, (j, shift) in enumerate(OUTSIDE):
+            assert np.array_equal(colour[K + i], PALETTE[(K - 1 - j if shift % 2 else j) if cw == ag.WRAP_MIRROR else j])
+            assert np.array_equal(params[K + i], PARAMS[(K - 1 if shift > 0 else 0) if pw == ag.WRAP_CLAMP else j])
+    assert {matrix_samplers(level) for level in (1, 2, 3, 4)} == {((NEAREST, ag.WRAP_REPEAT),) * 2, ((BILINEAR, ag.WRAP_MIRROR), (BILINEAR, ag.WRAP_CLAMP))}
 
 
 def plateau_scene(slot, wrap, textured, filter=BILINEAR):

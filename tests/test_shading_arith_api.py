@@ -47,6 +47,18 @@ def test_null_scene_is_invalid():
     assert L.agpt_scene_set_shading_arith(None, 7) == enum_value("AGPT_ERR_INVALID")
 
 
+def test_shade_variant_query_is_exported_and_refuses_null():
+    """agpt_scene_shade_variant (host-only): declared, exported, and a NULL scene or output fails loudly with the function's name"""
+    import ctypes
+    L = ag.lib()
+    name = "agpt_scene_shade_variant"
+    assert re.search(r"\b%s\s*\(" % name, HEADER) and name in ag.EXPORTS and hasattr(L, name)
+    out = (ctypes.c_int32 * 4)(7, 7, 7, 7)
+    assert L.agpt_scene_shade_variant(None, out) == enum_value("AGPT_ERR_INVALID")
+    assert b"agpt_scene_shade_variant" in L.agpt_last_error()
+    assert list(out) == [7, 7, 7, 7]
+
+
 def device_asm(src, tmp):
     """build.py's flags for `src`, device code only, as assembly."""
     flags = [f for f in b.FLAGS if f not in ("-shared", "-fPIC")]
