@@ -38,7 +38,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
@@ -188,7 +188,9 @@ def lib():
     L.agpt_bvh_refit.argtypes = [fp, C.c_int, ip, C.c_int, ip, vp, C.c_int]
     L.agpt_scene_update_mesh.argtypes = [vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int]
     for name, args in (("agpt_scene_update_mesh_device", [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int]),
-                       ("agpt_scene_transform_mesh", [vp, C.c_int, fp, C.c_int]), ("agpt_transform_arrays", [fp, fp, C.c_int, fp, C.c_int, fp, fp])):
+                       ("agpt_scene_transform_mesh", [vp, C.c_int, fp, C.c_int]), ("agpt_transform_arrays", [fp, fp, C.c_int, fp, C.c_int, fp, fp]),
+                       ("agpt_skin_arrays", [fp, C.c_int, C.c_int, fp, C.c_int, ip, fp, fp, C.c_int, ip, fp, fp, fp]),
+                       ("agpt_scene_set_mesh_skin", [vp, C.c_int, C.c_int, C.c_int, ip, fp, ip, fp]), ("agpt_scene_pose_mesh", [vp, C.c_int, fp, C.c_int, C.c_int])):
         if not variant or hasattr(L, name):   # (an A/B variant built from an older commit lacks them: tools/mesh_update_time.py --parent-lib)
             getattr(L, name).argtypes = args
     L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
@@ -390,6 +392,40 @@ def transform_arrays(matrix4x4, verts, normals=None):
     fp = C.POINTER(C.c_float)
     _check(lib().agpt_transform_arrays(m.ctypes.data_as(fp), pv, v.shape[0], pn, 0 if n is None else n.shape[0], vo.ctypes.data_as(fp),
                                        None if no is None else no.ctypes.data_as(fp)), "agpt_transform_arrays")
+    return vo, no
+
+
+def _joint_matrices(matrices):
+    m = np.ascontiguousarray(matrices, np.float32)
+    if m.ndim < 2 or m.size % 16 or m.shape[1:] not in ((4, 4), (16,)):
+        raise ValueError("joint matrices have shape %s, not (n_joints, 4, 4) or (n_joints, 16)" % (m.shape,))
+    return m.reshape(-1, 16)
+
+
+def _influences(joints, weights, what):
+    j, w = np.asarray(joints), np.asarray(weights)
+    if j.ndim != 2 or j.shape != w.shape:
+        raise ValueError("%s joints %s and weights %s must both have shape (n, influences)" % (what, j.shape, w.shape))
+    return _i(j) + _f(w)
+
+
+def skin_arrays(matrices, verts, joints, weights, normals=None, normal_joints=None, normal_weights=None):
+    """agpt_skin_arrays on the host (no GPU needed): linear-blend skinning of verts[n, 3] (and normals[m, 3]) by matrices[n_joints, 4, 4]
+    (row-major, last row (0, 0, 0, 1)) with joints / weights of shape (n, K), K = 1 .. 8; normals take normal_joints / normal_weights
+    (m, K), or the vertices' when m == n and none are given -> (verts[n, 3], normals[m, 3] or None), the arithmetic of
+    Scene.pose_mesh."""
+    m = _joint_matrices(matrices)
+    v, pv = _f(np.asarray(verts).reshape(-1, 3))
+    j, pj, w, pw = _influences(joints, weights, "vertex")
+    n, pn = (None, None) if normals is None else _f(np.asarray(normals).reshape(-1, 3))
+    nj, pnj, nw, pnw = (None,) * 4 if normal_joints is None else _influences(normal_joints, normal_weights, "normal")
+    if j.shape[0] != v.shape[0] or (nj is not None and (n is None or nj.shape != (n.shape[0], j.shape[1]))):
+        raise ValueError("skin_arrays: one row of K influences per vertex (and per normal)")
+    vo = np.empty_like(v)
+    no = None if n is None else np.empty_like(n)
+    fp = C.POINTER(C.c_float)
+    _check(lib().agpt_skin_arrays(m.ctypes.data_as(fp), m.shape[0], j.shape[1], pv, v.shape[0], pj, pw, pn, 0 if n is None else n.shape[0], pnj, pnw,
+                                  vo.ctypes.data_as(fp), None if no is None else no.ctypes.data_as(fp)), "agpt_skin_arrays")
     return vo, no
 
 
@@ -699,6 +735,31 @@ class Scene:
         m = np.ascontiguousarray(matrix4x4, np.float32).reshape(16)
         _check(self.L.agpt_scene_transform_mesh(self.h, int(prim), m.ctypes.data_as(C.POINTER(C.c_float)), self._update_mode(mode, "transform_mesh")),
                "agpt_scene_transform_mesh")
+
+    def set_mesh_skin(self, prim, joints, weights, normal_joints=None, normal_weights=None, n_joints=None):
+        """agpt_scene_set_mesh_skin: the binding of mesh primitive `prim` for pose_mesh -- joints / weights of shape (n_vertices, K),
+        K = 1 .. 8, and normal_joints / normal_weights (n_normals, K) unless the mesh has as many normals as vertices and they share
+        the influences.  n_joints: the number of matrices every pose brings (default: the highest index used + 1).  joints=None
+        removes the skin."""
+        if joints is None:
+            _check(self.L.agpt_scene_set_mesh_skin(self.h, int(prim), 0, 0, None, None, None, None), "agpt_scene_set_mesh_skin")
+            return
+        j, pj, w, pw = _influences(joints, weights, "vertex")
+        nj, pnj, nw, pnw = (None,) * 4 if normal_joints is None else _influences(normal_joints, normal_weights, "normal")
+        if nj is not None and nj.shape[1] != j.shape[1]:
+            raise ValueError("set_mesh_skin: vertices and normals have the same number of influences")
+        if n_joints is None:
+            n_joints = 1 + max(int(j.max(initial=0)), 0 if nj is None else int(nj.max(initial=0)))
+        _check(self.L.agpt_scene_set_mesh_skin(self.h, int(prim), j.shape[1], int(n_joints), pj, pw, pnj, pnw), "agpt_scene_set_mesh_skin")
+
+    def pose_mesh(self, prim, matrices, mode=UPDATE_REFIT):
+        """agpt_scene_pose_mesh: mesh primitive `prim` posed on the GPU by matrices[n_joints, 4, 4] (or [n_joints, 16]; row-major, last
+        row (0, 0, 0, 1)) through the binding of set_mesh_skin, from its rest pose (the arrays it last received from add_mesh /
+        update_mesh); absolute, not cumulative.  The scene is what update_mesh(prim, *skin_arrays(matrices, rest_verts, joints,
+        weights, rest_normals, ...), mode) leaves."""
+        m = _joint_matrices(matrices)
+        _check(self.L.agpt_scene_pose_mesh(self.h, int(prim), m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], self._update_mode(mode, "pose_mesh")),
+               "agpt_scene_pose_mesh")
 
     def set_bvh_builder(self, builder):
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""

@@ -71,6 +71,7 @@
 #include <vector>
 
 #include "../../include/agpt.h"
+#include "agpt_skin.h"
 #include "agpt_transform.h"
 
 namespace agpt {
@@ -469,6 +470,41 @@ int agpt_transform_arrays(const float* transform16, const float* vertices, int n
         float p[3];
         transform_vector(N, normals + 3 * (size_t)i, p);
         std::memcpy(normals_out + 3 * (size_t)i, p, sizeof(p));
+    }
+    return AGPT_OK;
+}
+
+int agpt_skin_arrays(const float* joints16, int n_joints, int influences, const float* vertices, int n_vertices, const int32_t* vertex_joints,
+                     const float* vertex_weights, const float* normals, int n_normals, const int32_t* normal_joints, const float* normal_weights,
+                     float* vertices_out, float* normals_out) {
+    const std::string f = "agpt_skin_arrays: ";
+    if (!joints16 || !vertices || !vertex_joints || !vertex_weights || !vertices_out)
+        return agpt::fail(AGPT_ERR_INVALID, f + "NULL joints16, vertices, vertex_joints, vertex_weights or vertices_out");
+    if (n_vertices < 0 || n_normals < 0 || (n_normals > 0 && (!normals || !normals_out)))
+        return agpt::fail(AGPT_ERR_INVALID, f + "a negative count, or n_normals > 0 with NULL normals or normals_out");
+    std::string bad = agpt::skin_check_counts(influences, n_joints);
+    if (!bad.empty()) return agpt::fail(AGPT_ERR_INVALID, f + bad);
+    const bool own = n_normals > 0 && normal_joints && normal_weights;
+    if (n_normals > 0 && !own && ((normal_joints || normal_weights) || n_normals != n_vertices))
+        return agpt::fail(AGPT_ERR_INVALID, f + "normal_joints and normal_weights may be NULL (both) only when n_normals == n_vertices");
+    bad = agpt::skin_check_influences("vertex", influences, n_joints, (size_t)n_vertices, vertex_joints, vertex_weights);
+    if (bad.empty() && own) bad = agpt::skin_check_influences("normal", influences, n_joints, (size_t)n_normals, normal_joints, normal_weights);
+    if (bad.empty()) bad = agpt::skin_check_last_rows(joints16, n_joints);
+    if (!bad.empty()) return agpt::fail(AGPT_ERR_INVALID, f + bad);
+    const std::vector<float> palette = agpt::skin_pack_palette(joints16, n_joints, n_normals > 0, nullptr);
+    const int stride = agpt::skin_palette_stride(n_normals > 0);
+    const size_t K = (size_t)influences;
+    for (size_t i = 0; i < (size_t)n_vertices; i++) {   // (through a temporary: vertices_out may be vertices)
+        float p[3];
+        agpt::skin_blend<true>(palette.data(), stride, vertex_joints + K * i, vertex_weights + K * i, influences, vertices + 3 * i, p);
+        std::memcpy(vertices_out + 3 * i, p, sizeof(p));
+    }
+    const int32_t* nj = own ? normal_joints : vertex_joints;
+    const float* nw = own ? normal_weights : vertex_weights;
+    for (size_t i = 0; i < (size_t)n_normals; i++) {
+        float p[3];
+        agpt::skin_blend<false>(palette.data(), stride, nj + K * i, nw + K * i, influences, normals + 3 * i, p);
+        std::memcpy(normals_out + 3 * i, p, sizeof(p));
     }
     return AGPT_OK;
 }

@@ -709,6 +709,77 @@ int agpt_scene_transform_mesh(agpt_scene* s, int prim, const float* transform16,
     return update_from_updater(s, prim, mi, mode);
 }
 
+int agpt_scene_set_mesh_skin(agpt_scene* s, int prim, int influences, int n_joints, const int32_t* vertex_joints, const float* vertex_weights,
+                             const int32_t* normal_joints, const float* normal_weights) {
+    const std::string f = "agpt_scene_set_mesh_skin: ";
+    if (!s) return fail(AGPT_ERR_INVALID, f + "NULL scene");
+    const agpt::HostMesh* m = mesh_of(s, prim);
+    if (!m) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " is not a mesh of this scene");
+    agpt_scene::MeshUpdate& up = s->updates[(size_t)s->prims[prim].index];
+    agpt::SkinBinding skin;
+    if (influences != 0) {   // the twin's rules, with the mesh's own counts
+        const size_t nv = m->vertices.size(), nn = m->normals.size();
+        std::string bad = agpt::skin_check_counts(influences, n_joints);
+        if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
+        if (!vertex_joints || !vertex_weights) return fail(AGPT_ERR_INVALID, f + "NULL vertex_joints or vertex_weights");
+        const bool own = nn && normal_joints && normal_weights;
+        if (nn && !own && ((normal_joints || normal_weights) || nn != nv))
+            return fail(AGPT_ERR_INVALID, f + "normal_joints and normal_weights may be NULL (both) only when the mesh has as many normals as vertices; it has " +
+                                              std::to_string(nv) + " vertices and " + std::to_string(nn) + " normals");
+        bad = agpt::skin_check_influences("vertex", influences, n_joints, nv, vertex_joints, vertex_weights);
+        if (bad.empty() && own) bad = agpt::skin_check_influences("normal", influences, n_joints, nn, normal_joints, normal_weights);
+        if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
+        skin.influences = influences;
+        skin.n_joints = n_joints;
+        skin.vertex_joints.assign(vertex_joints, vertex_joints + nv * (size_t)influences);
+        skin.vertex_weights.assign(vertex_weights, vertex_weights + nv * (size_t)influences);
+        if (own) {
+            skin.normal_joints.assign(normal_joints, normal_joints + nn * (size_t)influences);
+            skin.normal_weights.assign(normal_weights, normal_weights + nn * (size_t)influences);
+        }
+    }
+    if (up.updater) HIP_TRY(hipSetDevice(s->ctx->device));
+    agpt::drop_skin(up.updater);   // (nothing goes up here: the next pose uploads the new binding)
+    up.skin = std::move(skin);
+    return AGPT_OK;
+}
+
+int agpt_scene_pose_mesh(agpt_scene* s, int prim, const float* joints16, int n_joints, int mode) {
+    const std::string f = "agpt_scene_pose_mesh: ";
+    {   // the checks of agpt_scene_update_mesh with the mesh's own counts
+        const agpt::HostMesh* m = s && s->committed ? mesh_of(s, prim) : nullptr;
+        const int dummy = 0;
+        if (const int rc = check_update("agpt_scene_pose_mesh", s, prim, &dummy, m ? (int)m->vertices.size() : 0, &dummy,
+                                        m ? (int)m->normals.size() : 0, mode))
+            return rc;
+    }
+    const size_t mi = (size_t)s->prims[prim].index;
+    agpt_scene::MeshUpdate& up = s->updates[mi];
+    if (up.skin.influences == 0) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no skin (agpt_scene_set_mesh_skin)");
+    if (!joints16) return fail(AGPT_ERR_INVALID, f + "NULL joints16");
+    if (n_joints != up.skin.n_joints)
+        return fail(AGPT_ERR_INVALID, f + "n_joints is " + std::to_string(n_joints) + ", the skin was set with " + std::to_string(up.skin.n_joints));
+    for (size_t i = 0; i < 16 * (size_t)n_joints; i++)
+        if (!std::isfinite(joints16[i])) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(i / 16) + " has a non-finite entry");
+    const std::string bad = agpt::skin_check_last_rows(joints16, n_joints);
+    if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
+    int singular = -1;
+    const std::vector<float> palette = agpt::skin_pack_palette(joints16, n_joints, !s->meshes[mi].normals.empty(), &singular);
+    if (singular >= 0) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(singular) + " is singular (its determinant is exactly 0)");
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (!up.rest_valid) {   // as for agpt_scene_transform_mesh: the two share the rest pose
+        if (const int rc = sync_mirror(s, true)) return rc;
+        up.rest_vertices = s->meshes[mi].vertices;
+        up.rest_normals = s->meshes[mi].normals;
+        up.rest_valid = true;
+        agpt::drop_rest(up.updater);
+    }
+    if (const int rc = agpt::skin_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, up.skin, palette,
+                                                s->ctx->num_cus))
+        return rc;
+    return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `palette` lives until then)
+}
+
 int agpt_scene_set_bvh_builder(agpt_scene* s, int builder) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_set_bvh_builder: NULL scene");
     if (builder != AGPT_BVH_BUILDER_HOST && builder != AGPT_BVH_BUILDER_DEVICE)

@@ -13,10 +13,34 @@
 //                    path, which looks at every coordinate, referenced by a triangle or not).
 //   k_transform_mesh one lane per vertex and one per normal: the mesh's rest arrays through transform_point / transform_vector of
 //                    agpt_transform.h into the arrays k_update_tris reads (agpt_scene_transform_mesh).
-// All are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair, 24 B per transformed vertex); 64-lane
-// blocks, 16-byte accesses of the float4 records, no LDS.
+//   k_skin_mesh      one lane per vertex and one per normal: the rest arrays through skin_blend of agpt_skin.h -- up to 8 (joint,
+//                    weight) slots per item, each a gather of the joint's palette entry -- into the arrays k_update_tris reads
+//                    (agpt_scene_pose_mesh).
+// All are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair, 24 B per transformed vertex, 24 + 8 K B
+// per skinned vertex); all but k_skin_mesh run 64-lane blocks, 16-byte accesses of the float4 records, no LDS.
+//
+// k_skin_mesh's palette.  The per-lane gather by joint index is the one access here that is not a stream, and neighbouring vertices
+// mostly name the same few joints.  A palette of up to 40 KiB (487 joints with normals, 787 without) is staged in LDS; a larger one is
+// read from global memory, and AGPT_SKIN_GLOBAL_PALETTE in the environment, read at every call, forces that route.  Both routes run
+// the same arithmetic on the same floats and write the same bytes.  What follows from staging:
+//   launch   64-lane blocks, one per 64 items, would stage the palette 16 k times for a 1 M-vertex mesh.  The kernel runs 256-lane
+//            blocks on a capped grid, 4 per CU, and strides over the items, so every block stages once and then streams.
+//   cap      40 KiB is 160 KiB / 4: all four blocks of a CU stay resident.  Measured with the cap lifted, 1,024 joints with normals
+//            (84 KiB, one block per CU) posed the 1 M-triangle heightfield in 0.322 ms against 0.302 ms from global memory: the streams
+//            need the waves more than the gather needs the LDS.  At 64 joints the two routes are level.
+//   layout   per JOINT, not per component: entry j is `stride` consecutive floats (M's 12, then N's 9; 13 / 21 with the pad).  Lanes
+//            that name the same joint read the same address, which the LDS serves as one broadcast -- the common case costs what
+//            one lane costs.  Lanes that name DIFFERENT joints read component c at dword stride * j + c, on bank (stride * j + c)
+//            mod 32: the natural strides are the bad ones (12 puts joints j and j + 8 on one bank, 16 or 32 every second or every
+//            joint), so each entry is padded to an ODD stride and two joints meet on a bank only when j = j' (mod 32).  The
+//            entries are read with 4-byte LDS loads (an odd stride has no 16-byte alignment); the kernel is bound by its global
+//            streams, not by these.
+//   N-less   a mesh without normals stages M only (stride 13): the same kernel, the stride is an argument.
 #include "agpt_update.h"
 
+#include <cstdlib>
+
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -161,11 +185,67 @@ __global__ __launch_bounds__(kBlock) void k_transform_mesh(TransformArgs a) {
     }
 }
 
+struct SkinArgs {
+    const float* palette;      // n_joints entries of `stride` floats (agpt_skin.h)
+    int stride, n_joints, influences;
+    const float* rest_verts;
+    const float* rest_normals;
+    const int32_t* vertex_joints;
+    const float* vertex_weights;
+    const int32_t* normal_joints;   // (the vertex arrays again when they serve both)
+    const float* normal_weights;
+    float* verts;
+    float* normals;
+    int n_vertices, n_normals;
+};
+
+constexpr int kSkinBlock = 256;
+constexpr int kSkinBlocksPerCU = 4;
+constexpr size_t kLdsPerCU = 160 * 1024;
+constexpr size_t kSkinLdsBytes = kLdsPerCU / kSkinBlocksPerCU;   // the largest staged palette, 40 KiB: all four blocks stay resident
+
+template <bool kLds>
+__global__ __launch_bounds__(kSkinBlock) void k_skin_mesh(SkinArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float skin_lds[];
+    if (kLds) {
+        const int n = a.n_joints * a.stride;
+        for (int i = threadIdx.x; i < n; i += kSkinBlock) skin_lds[i] = a.palette[i];
+        __syncthreads();
+    }
+    const size_t nv = (size_t)a.n_vertices, total = nv + (size_t)a.n_normals, K = (size_t)a.influences;
+    for (size_t i = (size_t)blockIdx.x * kSkinBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kSkinBlock) {
+        const bool point = i < nv;
+        const size_t j = point ? i : i - nv;
+        const float* rest = (point ? a.rest_verts : a.rest_normals) + 3 * j;
+        const int32_t* joints = (point ? a.vertex_joints : a.normal_joints) + K * j;
+        const float* weights = (point ? a.vertex_weights : a.normal_weights) + K * j;
+        const float r[3] = {rest[0], rest[1], rest[2]};
+        float out[3];
+        if (point) {
+            if (kLds)
+                skin_blend<true>(skin_lds, a.stride, joints, weights, a.influences, r, out);
+            else
+                skin_blend<true>(a.palette, a.stride, joints, weights, a.influences, r, out);
+        } else {
+            if (kLds)
+                skin_blend<false>(skin_lds, a.stride, joints, weights, a.influences, r, out);
+            else
+                skin_blend<false>(a.palette, a.stride, joints, weights, a.influences, r, out);
+        }
+        float* dst = (point ? a.verts : a.normals) + 3 * j;
+        dst[0] = out[0];
+        dst[1] = out[1];
+        dst[2] = out[2];
+    }
+}
+
 template <class T>
 struct Buf {
     T* p = nullptr;
-    ~Buf() {
+    ~Buf() { release(); }
+    void release() {
         if (p) (void)hipFree(p);
+        p = nullptr;
     }
     hipError_t upload(const T* host, size_t count, hipStream_t st) {
         if (!p) {
@@ -192,6 +272,10 @@ struct MeshUpdater {
     // agpt_scene_transform_mesh: the rest pose k_transform_mesh reads (uploaded by the first transform after the arrays were given)
     Buf<float> rest_verts, rest_normals;
     bool has_rest = false;
+    // agpt_scene_pose_mesh: the binding (uploaded by the first pose after it was set) and the palette of the last pose
+    Buf<int32_t> skin_vertex_joints, skin_normal_joints;
+    Buf<float> skin_vertex_weights, skin_normal_weights, skin_palette;
+    bool has_skin = false;
     Buf<uint32_t> flag;        // k_check_finite's word
     Buf<v2> uv;
     Buf<int32_t> indices, prim_index, lists;
@@ -333,13 +417,15 @@ int copy_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& 
     return AGPT_OK;
 }
 
-int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N) {
+// the cache, the rest pose on the device (uploaded when the cache holds none) and room for the posed arrays: what the transform and the
+// pose share (`fn` names the call in the message)
+static int ensure_rest(const char* fn, hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
+                       const std::vector<v3>& rest_normals) {
     if (const int rc = ensure(stream, cache, mesh)) return rc;
     MeshUpdater& u = **cache;
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
     if (rest_vertices.size() != nv || rest_normals.size() != nn)
-        return fail(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: the rest pose does not have the mesh's counts");
+        return fail(AGPT_ERR_INVALID, std::string(fn) + ": the rest pose does not have the mesh's counts");
     if (!u.has_rest) {
         UPD_TRY(u.rest_verts.upload(&rest_vertices.data()->x, 3 * nv, stream));
         if (nn) UPD_TRY(u.rest_normals.upload(&rest_normals.data()->x, 3 * nn, stream));
@@ -348,6 +434,14 @@ int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostM
     }
     UPD_TRY(u.verts.reserve(3 * nv));
     if (nn) UPD_TRY(u.normals.reserve(3 * nn));
+    return AGPT_OK;
+}
+
+int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
+                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N) {
+    if (const int rc = ensure_rest("agpt_scene_transform_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
+    MeshUpdater& u = **cache;
+    const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
     TransformArgs a;
     a.M = M;
     a.N = N;
@@ -360,6 +454,65 @@ int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostM
     hipLaunchKernelGGL(k_transform_mesh, dim3((unsigned)((nv + nn + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
     UPD_TRY(hipGetLastError());
     return AGPT_OK;
+}
+
+int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
+                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus) {
+    if (const int rc = ensure_rest("agpt_scene_pose_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
+    MeshUpdater& u = **cache;
+    const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), K = (size_t)skin.influences;
+    const int stride = skin_palette_stride(nn != 0);
+    const bool own_normal_slots = nn && !skin.normal_joints.empty();
+    // what the kernel indexes with, against what it indexes (the joint indices were checked against n_joints when the skin was set)
+    if (K < 1 || K > (size_t)kSkinMaxInfluences || skin.vertex_joints.size() != nv * K || skin.vertex_weights.size() != nv * K ||
+        (own_normal_slots ? skin.normal_joints.size() != nn * K || skin.normal_weights.size() != nn * K : nn && nn != nv) ||
+        palette.size() != (size_t)skin.n_joints * (size_t)stride)
+        return fail(AGPT_ERR_INVALID, "agpt_scene_pose_mesh: the binding does not have the mesh's counts");
+    if (!u.has_skin) {
+        UPD_TRY(u.skin_vertex_joints.upload(skin.vertex_joints.data(), nv * K, stream));
+        UPD_TRY(u.skin_vertex_weights.upload(skin.vertex_weights.data(), nv * K, stream));
+        if (own_normal_slots) {
+            UPD_TRY(u.skin_normal_joints.upload(skin.normal_joints.data(), nn * K, stream));
+            UPD_TRY(u.skin_normal_weights.upload(skin.normal_weights.data(), nn * K, stream));
+        }
+        UPD_TRY(hipStreamSynchronize(stream));   // (the binding may be replaced behind this call)
+        u.has_skin = true;
+    }
+    UPD_TRY(u.skin_palette.upload(palette.data(), palette.size(), stream));   // (the caller keeps `palette` until the stream is synchronised)
+    SkinArgs a;
+    a.palette = u.skin_palette.p;
+    a.stride = stride;
+    a.n_joints = skin.n_joints;
+    a.influences = skin.influences;
+    a.rest_verts = u.rest_verts.p;
+    a.rest_normals = nn ? u.rest_normals.p : nullptr;
+    a.vertex_joints = u.skin_vertex_joints.p;
+    a.vertex_weights = u.skin_vertex_weights.p;
+    a.normal_joints = own_normal_slots ? u.skin_normal_joints.p : u.skin_vertex_joints.p;
+    a.normal_weights = own_normal_slots ? u.skin_normal_weights.p : u.skin_vertex_weights.p;
+    a.verts = u.verts.p;
+    a.normals = nn ? u.normals.p : nullptr;
+    a.n_vertices = (int)nv;
+    a.n_normals = (int)nn;
+    const size_t lds = palette.size() * sizeof(float), blocks = (nv + nn + kSkinBlock - 1) / kSkinBlock;
+    const size_t cus = (size_t)(num_cus > 0 ? num_cus : 1);
+    if (lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE")) {
+        hipLaunchKernelGGL(k_skin_mesh<true>, dim3((unsigned)std::min(blocks, cus * kSkinBlocksPerCU)), dim3(kSkinBlock), lds, stream, a);
+    } else {
+        hipLaunchKernelGGL(k_skin_mesh<false>, dim3((unsigned)std::min(blocks, cus * kSkinBlocksPerCU)), dim3(kSkinBlock), 0, stream, a);
+    }
+    UPD_TRY(hipGetLastError());
+    return AGPT_OK;
+}
+
+void drop_skin(MeshUpdater* cache) {
+    if (!cache) return;
+    cache->skin_vertex_joints.release();
+    cache->skin_vertex_weights.release();
+    cache->skin_normal_joints.release();
+    cache->skin_normal_weights.release();
+    cache->skin_palette.release();
+    cache->has_skin = false;
 }
 
 int refit_device_arrays(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh, const UpdateTarget& tg, float root6[6], bool* finite) {

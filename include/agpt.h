@@ -335,6 +335,51 @@ int agpt_transform_arrays(const float* transform16, const float* vertices, int n
  * scene; not committed; not a mesh; unknown mode); a NULL matrix; a non-finite entry; a determinant (the value above) of exactly 0.
  * A refused call changes nothing.  Not covered: as for agpt_scene_update_mesh_device. */
 int agpt_scene_transform_mesh(agpt_scene*, int prim, const float* transform16, int mode);
+/* Linear-blend skinning of a mesh's arrays by a palette of joint matrices, host-only like agpt_transform_arrays (no GPU, no context)
+ * and built on its arithmetic: fp32, every operation rounded on its own, nothing contracted into an fma.
+ *   inputs     joints16: n_joints (1 .. 65536) row-major 4x4 M_j, each with the last row exactly (0, 0, 0, 1).  Every vertex has
+ *              `influences` = K (1 .. 8) slots (joint, weight): vertex_joints / vertex_weights are flat, stride K.  Normals have
+ *              slots of their own (normal_joints / normal_weights, n_normals * K); both may be NULL only when n_normals == n_vertices,
+ *              and the vertex slots then serve both.  n_normals may be 0.
+ *   position   the slots in order k = 0 .. K-1; a slot whose weight is exactly 0 (either sign) is skipped; the first used slot sets
+ *              acc = w * P per component, every later one acc = acc + w * P, with P = agpt_transform_arrays' position through M_j;
+ *              a vertex whose every weight is 0 keeps its rest position.  Weights are used as given: neither normalised nor
+ *              reordered.
+ *   normal     the same walk over the normal's slots with agpt_transform_arrays' normal through n_j = the 3x3 transpose of the
+ *              inverse of M_j (a determinant of exactly 0 gives the identity, the reference's rule).  Not renormalised.
+ * One used slot of weight 1 gives the bits of agpt_transform_arrays(M_j, ...); so do two slots of 0.5 with the same joint.
+ * An output may be its own input.  AGPT_ERR_INVALID (+ agpt_last_error) for a NULL argument or a bad count, influences outside
+ * 1 .. 8, n_joints outside 1 .. 65536, a joint index out of range, a weight that is negative or not finite, a last row that is not
+ * exactly (0, 0, 0, 1); a refused call writes nothing. */
+int agpt_skin_arrays(const float* joints16, int n_joints, int influences,
+                     const float* vertices, int n_vertices, const int32_t* vertex_joints, const float* vertex_weights,
+                     const float* normals, int n_normals, const int32_t* normal_joints, const float* normal_weights,
+                     float* vertices_out, float* normals_out);
+/* The binding of mesh primitive `prim` for agpt_scene_pose_mesh: its vertices' (and normals') influences as in agpt_skin_arrays, with
+ * the mesh's own counts, and the number of joints every later pose must bring.  May be called any time after agpt_scene_add_mesh, on
+ * a committed scene or not.  The scene keeps a host copy and uploads nothing; the first pose takes the binding to the GPU, where it
+ * stays.  Setting it again replaces the binding (the device copies are dropped); influences == 0 removes it (the other arguments are
+ * then ignored).  agpt_scene_update_mesh / _device keep the binding: the counts cannot change, and the new arrays become the rest pose.
+ * AGPT_ERR_INVALID (+ agpt_last_error) for a NULL scene, a prim that is not a mesh of the scene, and agpt_skin_arrays' conditions on
+ * influences, n_joints, the four arrays and their contents; a refused call changes nothing. */
+int agpt_scene_set_mesh_skin(agpt_scene*, int prim, int influences, int n_joints, const int32_t* vertex_joints, const float* vertex_weights,
+                             const int32_t* normal_joints, const float* normal_weights);
+/* Mesh primitive `prim` of a COMMITTED scene posed by its skin, on the GPU: afterwards the scene is byte for byte what
+ * agpt_scene_update_mesh(scene, prim, V, n_vertices, N, n_normals, mode) leaves, with V and N = agpt_skin_arrays(joints16, the mesh's
+ * rest pose, the binding).  The rest pose is agpt_scene_transform_mesh's -- the arrays the mesh last received explicitly --, so a pose
+ * is absolute, not cumulative; pose and transform calls may alternate, and the last one wins.  One lane per vertex and per normal runs
+ * agpt_skin_arrays' arithmetic (one source for host and device) on a palette of M_j and n_j formed on the host: per call
+ * n_joints * (12 + 9) floats go up (12 for a mesh without normals), and under REFIT the finiteness flag and the root box come down (a
+ * non-finite posed position takes the host path, as for the other update calls).  REBUILD downloads the posed arrays and rebuilds;
+ * the binding goes up again with the next pose.  A palette of up to 40 KiB is staged in LDS; AGPT_SKIN_GLOBAL_PALETTE in the
+ * environment (read at every call) makes the kernel read it from global memory instead, as a larger one is.  Same bytes either way.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order: the conditions of agpt_scene_update_mesh that apply (NULL
+ * scene; not committed; not a mesh; unknown mode); a mesh without a skin; NULL joints16; an n_joints that is not the binding's; a
+ * non-finite entry; a last row that is not exactly (0, 0, 0, 1); a joint whose determinant (agpt_transform_arrays' value) is exactly
+ * 0, named in the message.  A refused call changes nothing.
+ * Out of scope: morph targets, dual-quaternion blending, joint matrices given in device memory, renormalised normals, motion
+ * vectors (and what agpt_scene_update_mesh_device does not cover). */
+int agpt_scene_pose_mesh(agpt_scene*, int prim, const float* joints16, int n_joints, int mode);
 /* Which builder agpt_scene_add_mesh uses for the BVH of later meshes on this scene (default HOST).  Both produce the same
  * bytes; DEVICE runs agpt_bvh_build_device on the scene's context. */
 enum { AGPT_BVH_BUILDER_HOST = 0, AGPT_BVH_BUILDER_DEVICE = 1 };

@@ -245,6 +245,19 @@ public:
     void TransformMesh(int prim, const float transform16[16], MeshUpdate mode = MeshUpdate::Refit) {
         check(agpt_scene_transform_mesh(h_, prim, transform16, (int)mode), "agpt_scene_transform_mesh");
     }
+    // an articulated mesh: SetMeshSkin gives the binding once (agpt_scene_set_mesh_skin) -- `influences` (joint, weight) slots per
+    // vertex, flat arrays of n_vertices * influences; the normals' own slots, or none when the mesh has as many normals as vertices and
+    // they share the vertices' --, PoseMesh the n_joints row-major mat4 of a frame (agpt_scene_pose_mesh), applied on the GPU to the
+    // rest pose TransformMesh uses: absolute, not cumulative.  `scene.PoseMesh(prim, joints); accumulator.Clear();`
+    void SetMeshSkin(int prim, int influences, int n_joints, const std::vector<int32_t>& vertex_joints, const std::vector<float>& vertex_weights,
+                     const std::vector<int32_t>& normal_joints = {}, const std::vector<float>& normal_weights = {}) {
+        check(agpt_scene_set_mesh_skin(h_, prim, influences, n_joints, vertex_joints.data(), vertex_weights.data(),
+                                       normal_joints.empty() ? nullptr : normal_joints.data(), normal_weights.empty() ? nullptr : normal_weights.data()),
+              "agpt_scene_set_mesh_skin");
+    }
+    void PoseMesh(int prim, const std::vector<float>& joints16, MeshUpdate mode = MeshUpdate::Refit) {
+        check(agpt_scene_pose_mesh(h_, prim, joints16.data(), (int)(joints16.size() / 16), (int)mode), "agpt_scene_pose_mesh");
+    }
     // camera moved (RotatingCamera::update): re-derive the camera only, geometry stays in HBM
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }
     void Intersect(const agpt_ray* rays, int n, agpt_hit* hits) const {

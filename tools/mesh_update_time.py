@@ -4,6 +4,11 @@ agpt_scene_transform_mesh (16 floats), and REBUILD with the host and the device 
 one warm-up, and the bytes that cross PCIe per call (up / down, from the sizes; REBUILD re-uploads the whole scene).
 
     python tools/mesh_update_time.py [--runs 9] [--out profiles/mesh_update_times.json] [--parent-lib TAG] [--rounds 3]
+    python tools/mesh_update_time.py --pose [--runs 9] [--out profiles/mesh_pose_times.json]
+
+--pose times agpt_scene_pose_mesh instead (REFIT, 4 influences per vertex, 64 and 1,024 joints, the palette staged in LDS and read
+from global memory -- AGPT_SKIN_GLOBAL_PALETTE), with, in the same process on the same GPU, agpt_scene_transform_mesh and the route a
+host has without it: agpt_skin_arrays on the CPU, then agpt_scene_update_mesh with its output.
 
 --parent-lib TAG compares the host-pointer REFIT of this build with the build `libagpt_hip_TAG.so` of the parent commit
 (tools/build_variant.py run in a checkout of it, the file copied beside libagpt_hip.so): child processes, alternating parent / this
@@ -69,6 +74,88 @@ def spin(v, k):
     return (t1 @ m @ t0).astype(F)
 
 
+POSE_INFLUENCES = 4
+POSE_ROUNDS = 3
+SKIN_LDS_BYTES = 40 * 1024   # agpt_update.hip: the largest palette k_skin_mesh stages
+
+
+def pose_binding(v, count, n_joints):
+    """`count` rows of 4 influences: joints in bands along the mesh's longest axis (neighbours share joints, as on a rigged mesh),
+    weights .4 .3 .2 .1 on the band and its neighbours"""
+    axis = int(np.argmax(v.max(0) - v.min(0)))
+    x = np.resize(v[:, axis], count).astype(np.float64)
+    band = np.clip(((x - x.min()) / max(x.max() - x.min(), 1e-30) * n_joints).astype(np.int64), 0, n_joints - 1)
+    J = np.clip(np.stack([band, band + 1, band - 1, band + 2], 1), 0, n_joints - 1).astype(np.int32)
+    W = np.tile(np.array([.4, .3, .2, .1], F), (count, 1))
+    return J, W
+
+
+def pose_palette(v, n_joints, k):
+    """run k: every joint a small turn about the vertical axis through the mesh's centre and a small lift, different per joint"""
+    c = 0.5 * (v.min(0).astype(np.float64) + v.max(0))
+    out = np.tile(np.eye(4), (n_joints, 1, 1))
+    ang = 0.002 * (k + 1) * np.sin(0.37 * np.arange(n_joints) + k)
+    out[:, 0, 0], out[:, 0, 2], out[:, 2, 0], out[:, 2, 2] = np.cos(ang), np.sin(ang), -np.sin(ang), np.cos(ang)
+    out[:, :3, 3] = c - np.einsum("jab,b->ja", out[:, :3, :3], c)
+    out[:, 1, 3] += 0.001 * np.cos(0.11 * np.arange(n_joints) + k)
+    return out.astype(F)
+
+
+def pose_leg(runs):
+    result = {"runs": runs, "influences": POSE_INFLUENCES,
+              "statistic": "host clock around the synchronised call, ms: median and min-max of the runs after one warm-up (the warm-up "
+                           "uploads the rest pose and the binding); all rows of a case from one process on one GPU; the pose rows are "
+                           "%d rounds alternating the two palette routes: the median of the rounds' medians, the lowest min, the highest "
+                           "max.  A palette over 40 KiB is not staged: its `lds` row took the global route too" % POSE_ROUNDS,
+              "cases": {}}
+    ctx = ag.Context(0)
+    for name, desc, prim in cases():
+        v, n, tris = arrays_of(desc, prim)
+        nv, nn = len(v), 0 if n is None else len(n)
+        g = desc.instantiate(ag.Scene(ctx))
+        rows = {}
+        mats = [spin(v, k) for k in range(runs + 1)]
+        g.transform_mesh(prim, mats[0])
+        rows["refit_transform"] = dict(timed(lambda k: g.transform_mesh(prim, mats[k]), runs), pcie_up=128, pcie_down=36)
+        for n_joints in (64, 1024):
+            J, W = pose_binding(v, nv, n_joints)
+            nJ, nW = pose_binding(v, nn, n_joints) if nn and nn != nv else (None, None)
+            g.set_mesh_skin(prim, J, W, nJ, nW, n_joints=n_joints)
+            palettes = [pose_palette(v, n_joints, k) for k in range(runs + 1)]
+            floats = n_joints * (21 if nn else 12)
+            staged = 4 * n_joints * (21 if nn else 13) <= SKIN_LDS_BYTES
+            per_route = {"lds": [], "global": []}
+            for _ in range(POSE_ROUNDS):       # the two routes in turn, so that neither has the GPU in a better hour
+                for route in ("lds", "global"):
+                    if route == "global":
+                        os.environ["AGPT_SKIN_GLOBAL_PALETTE"] = "1"
+                    try:
+                        per_route[route].append(timed(lambda k: g.pose_mesh(prim, palettes[k]), runs))
+                    finally:
+                        os.environ.pop("AGPT_SKIN_GLOBAL_PALETTE", None)
+            for route, rs in per_route.items():
+                rows["refit_pose_%d_joints_%s" % (n_joints, route)] = {
+                    "median_ms": round(statistics.median(r["median_ms"] for r in rs), 4), "min_ms": min(r["min_ms"] for r in rs),
+                    "max_ms": max(r["max_ms"] for r in rs), "runs": runs, "rounds": [r["median_ms"] for r in rs], "pcie_up": 4 * floats,
+                    "pcie_down": 36, "palette_staged_in_lds": bool(staged and route == "lds")}
+            # the route without the call: the blend on the CPU, then the arrays up
+            t0 = time.perf_counter()
+            posed = [ag.skin_arrays(palettes[k], v, J, W, n, nJ, nW) for k in range(2)]
+            twin_ms = (time.perf_counter() - t0) * 1e3 / 2
+            rows["host_skin_arrays_%d_joints" % n_joints] = {"mean_ms": round(twin_ms, 3), "runs": 2, "what": "agpt_skin_arrays on the CPU, one thread"}
+            rows["refit_host_pointer_%d_joints" % n_joints] = dict(timed(lambda k: g.update_mesh(prim, posed[k & 1][0], posed[k & 1][1], "refit"), runs),
+                                                                   pcie_up=12 * (nv + nn), pcie_down=32)
+        g.close()
+        result["cases"][name] = {"triangles": tris, "vertices": nv, "normals": nn, "scene_triangles": desc.n_tris, "operations": rows}
+        for k, r in rows.items():
+            if "median_ms" in r:
+                print("%-16s %-36s median %9.3f ms  (%.3f .. %.3f)" % (name, k, r["median_ms"], r["min_ms"], r["max_ms"]), flush=True)
+            else:
+                print("%-16s %-36s mean   %9.3f ms" % (name, k, r["mean_ms"]), flush=True)
+    ctx.close()
+    return result
+
+
 def host_refit_only(runs):
     """the child of --parent-lib: the host-pointer REFIT alone, through whichever library AGPT_LIB_VARIANT names"""
     ctx = ag.Context(0)
@@ -116,12 +203,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--parent-lib", default=None, metavar="TAG")
+    ap.add_argument("--pose", action="store_true", help="time agpt_scene_pose_mesh (see above) instead of the update paths")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.runs < 7:
         ap.error("--runs: at least 7")
     if a.child:
         return host_refit_only(a.runs)
+    if a.pose:
+        result = pose_leg(a.runs)
+        with open(a.out or os.path.join(ROOT, "profiles", "mesh_pose_times.json"), "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+        return
     result = {"runs": a.runs, "statistic": "host clock around the synchronised call, ms: median and min-max of the runs after one warm-up",
               "pcie_bytes": "per call, from the sizes: up = host to device, down = device to host", "cases": {}}
     ctx = ag.Context(0)

@@ -90,6 +90,39 @@ def render_spin(a, ctx, scene, desc, W, H):
     ctx.free(ptr)
 
 
+def render_bend(a, ctx, scene, desc, W, H):
+    """--bend: the scene's last mesh bound to two joints -- the second one's weight grows smoothly from 0 to 1 along the mesh's x
+    extent -- and bent to and fro about the z axis through its centre over N frames, each frame posed with Scene.pose_mesh (two
+    matrices up, the blend and the mesh's records on the GPU) and rendered at --spp into OUT_0000.png ..."""
+    meshes = [(k, op) for k, op in enumerate(o for o in desc.ops if o[0] in ("mesh", "sphere", "plane", "area_light")) if op[0] == "mesh"]
+    prim, op = meshes[-1]
+    v, n = op[1], op[2]
+    if n is not None and len(n) != len(v):
+        raise SystemExit("--bend: the mesh has %d normals for %d vertices; its normals need influences of their own" % (len(n), len(v)))
+    lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
+    c = 0.5 * (lo + hi)
+    t = (v[:, 0] - lo[0]) / max(hi[0] - lo[0], 1e-30)
+    t = (t * t * (3 - 2 * t)).astype(np.float32)
+    scene.set_mesh_skin(prim, np.tile(np.array([0, 1], np.int32), (len(v), 1)), np.stack([np.float32(1) - t, t], 1), n_joints=2)
+    stem, ext = os.path.splitext(a.out)
+    ptr = ctx.alloc(W * H * 16)
+    for k in range(a.bend):
+        ang = np.radians(50.0) * np.sin(2 * np.pi * k / a.bend)
+        m = np.eye(4)
+        m[0, 0], m[0, 1], m[1, 0], m[1, 1] = np.cos(ang), -np.sin(ang), np.sin(ang), np.cos(ang)
+        m[:3, 3] = c - m[:3, :3] @ c
+        t0 = time.time()
+        scene.pose_mesh(prim, np.stack([np.eye(4), m]).astype(np.float32))
+        t1 = time.time()
+        ctx.memset(ptr, 0, W * H * 16)
+        ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
+        path = "%s_%04d%s" % (stem, k, ext)
+        ag.binding.write_png(path, ctx.resolve(ptr, W * H, a.spp), W, H)
+        print("frame %d: primitive %d bent %.0f degrees in %.2f ms, %d spp in %.1f ms -> %s" %
+              (k, prim, np.degrees(ang), (t1 - t0) * 1e3, a.spp, (time.time() - t1) * 1e3, path))
+    ctx.free(ptr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="c3", choices=["c1", "c2", "c3", "c5", "simple", "heightfield", "textured", "mapped"])
@@ -127,9 +160,12 @@ def main():
     ap.add_argument("--spin", type=int, default=0, metavar="N",
                     help="N frames at --spp each with one mesh turned about its vertical axis by agpt_scene_transform_mesh (OUT_0000.png ...)")
     ap.add_argument("--spin-prim", type=int, default=None, metavar="PRIM", help="--spin: the mesh primitive that turns (default: the scene's last mesh)")
+    ap.add_argument("--bend", type=int, default=0, metavar="N",
+                    help="N frames at --spp each with the scene's last mesh (the blob of textured / mapped) bent by two joints through "
+                         "agpt_scene_set_mesh_skin / agpt_scene_pose_mesh (OUT_0000.png ...)")
     a = ap.parse_args()
-    if a.spin and a.frames > 1:
-        ap.error("--spin and --frames are separate sequences")
+    if (a.spin or a.bend) and a.frames > 1 or (a.spin and a.bend):
+        ap.error("--spin, --bend and --frames are separate sequences")
     if (a.temporal or a.orbit) and a.frames < 2:
         ap.error("--temporal and --orbit apply to a sequence (--frames N, N >= 2)")
     W, H = a.width, a.height
@@ -164,6 +200,8 @@ def main():
         return render_sequence(a, ctx, scene, desc, W, H)
     if a.spin:
         return render_spin(a, ctx, scene, desc, W, H)
+    if a.bend:
+        return render_bend(a, ctx, scene, desc, W, H)
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
     features = None
