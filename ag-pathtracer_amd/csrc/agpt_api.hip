@@ -67,11 +67,14 @@ template <int MODE, bool COUNT, bool SPILL, bool PEEK>
 static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch& t) {
     const dim3 block(AGPT_BLOCK), g(fast_grid(c));
     const int refill = MODE == 0 ? c->refill : c->refill_any;
+    // (developer knob, read at each launch: AGPT_ROOT_STEP=1 makes short-list launches enter every mesh at its root pair again)
+    const bool root_entry = !getenv("AGPT_ROOT_STEP");
     if constexpr (MODE == 0 && !COUNT) {
         if (t.coherent && sc.n_prims <= 64) {   // (a wave takes a whole 64-ray chunk, and only when it is empty: refill = 64)
             hipLaunchKernelGGL((k_trace_fast<0, AGPT_FAST_STACK, false, false, SPILL, PEEK, true>), g, block, 0, t.stream, sc, t.queue,
                                t.count_ptr, t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, 64, 0u, c->spill.p,
-                               (const unsigned long long*)nullptr, (const uint32_t*)nullptr, t.recast, (const float4*)c->beta4.p, c->L4.p);
+                               (const unsigned long long*)nullptr, (const uint32_t*)nullptr, t.recast, (const float4*)c->beta4.p, c->L4.p,
+                               root_entry);
             return;
         }
     }
@@ -79,7 +82,7 @@ static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch
         hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, false, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
                            t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p,
                            refill, 0u, c->spill.p, (const unsigned long long*)nullptr, (const uint32_t*)nullptr, MODE == 0 && t.recast,
-                           (const float4*)c->beta4.p, c->L4.p);
+                           (const float4*)c->beta4.p, c->L4.p, root_entry);
         return;
     }
     // more than 64 primitives: the top-level tree gives every ray its candidates (one word per chunk of 64 primitives), then
@@ -94,7 +97,7 @@ static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch
     hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, true, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
                        t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, refill, stride, c->spill.p,
                        (const unsigned long long*)c->cand_mask.p, (const uint32_t*)c->cand_chunks.p, false, (const float4*)nullptr,
-                       (float4*)nullptr);
+                       (float4*)nullptr, false);
 }
 
 template <bool ANY, bool COUNT, int DEPTH>
@@ -509,6 +512,8 @@ static int fill_stats(agpt_ctx* c, const WavefrontRun& run, uint64_t samples, ag
                      d[0] ? (double)d[3] / d[0] : 0., d[1] ? (double)d[4] / d[1] : 0., d[2] ? (double)d[5] / d[2] : 0.,
                      (double)d[6] / steps, (double)d[7], d[7] ? (double)d[8] / d[7] : 0., (double)d[9]);
 #ifndef AGPT_TRACE_CLOCK
+        std::fprintf(stderr, "[trace stats mode %d] root-pair lane-steps %.4g (%.2f%% of B lane-steps), root box passes on %.4g of them (%.2f%%)\n", mode,
+                     (double)d[15], d[4] ? 100. * d[15] / d[4] : 0., (double)dc.dbg[AGPT_DBG_ROOT_PASS + mode], d[15] ? 100. * dc.dbg[AGPT_DBG_ROOT_PASS + mode] / d[15] : 0.);
         std::fprintf(stderr, "[trace stats mode %d] stack pushes %.3g: to depth > 4 %.2f%%  > 6 %.3f%%  > 8 %.4f%%  > 12 %.5f%%\n", mode, (double)d[10],
                      d[10] ? 100. * d[11] / d[10] : 0., d[10] ? 100. * d[12] / d[10] : 0., d[10] ? 100. * d[13] / d[10] : 0.,
                      d[10] ? 100. * d[14] / d[10] : 0.);

@@ -95,7 +95,8 @@ k_trace(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restr
 //     with a per-primitive candidate mask from a cheap conservative slab test, all 64 lanes busy; the exact
 //     Bounds::Intersect is re-run per lane where the reference runs it;
 //   * VOTE-SCHEDULED traversal: a lane is between primitives (A), at an interior node (B) or at a leaf (C); each step
-//     the wave executes the body most lanes wait for.  A mesh's root-box test is an interior step on its root pair.
+//     the wave executes the body most lanes wait for.  A mesh's root-box test is an interior step on its root pair, which a
+//     fast ray skips on short lists (pick_next: ROOT ENTRY).
 #define AGPT_RING 128  // entries of the per-wave ring of pre-filtered rays (power of two, >= 64 + 63)
 // per-primitive root record staged in LDS: [2k] = (bmin.xyz | sphere centre.xyz, kind), [2k+1] = (bmax.xyz, root_enc) |
 // (r2, -, -, -) | (half x, half z, -, -); kind 0 = mesh, 1 = sphere, 2 = empty mesh (never hit), 3 = plane
@@ -116,9 +117,10 @@ k_trace(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __restr
 // any (cand_mask[chunk * cand_stride + path], cand_chunks[path]); the lane walks its candidates chunk by chunk in list
 // order -- exactly Scene::Intersect's sequential walk with a shared ray.t (scene.h:5-19), minus the primitives the ray
 // cannot touch.  The prefilter and the LDS copy of the primitive records belong to the short-list instantiation only.
-// COUNT: the same kernel also counts the work it does -- child-pair records fetched (interior), root-pair records fetched
-// (roots: the mesh root-box tests that survive the prefilter) and triangle tests -- for bench.py's roofline; the counts
-// are per-lane sums, deterministic for a given queue (every lane's own operation sequence is fixed).
+// COUNT: the same kernel also counts the work it does -- pair records fetched (interior), the first record fetched of each mesh
+// (roots: the mesh entries that survive the prefilter -- the root pair, or the root's child pair where pick_next enters there)
+// and triangle tests -- for bench.py's roofline; the counts are per-lane sums, deterministic for a given queue (every lane's own
+// operation sequence is fixed).
 // DEPTH = per-lane stack entries kept in LDS.  SPILL: the scene's BVHs are deeper than that -- entries DEPTH and up live
 // in a per-thread column of an HBM buffer (spill[(k - DEPTH) * threads_in_grid + thread]); near-first descent rarely needs
 // them.  Occupancy is LDS-bound (DEPTH KiB of stack + 8 KiB per block): 23 entries -> 5 blocks = 20 waves per CU, which
@@ -143,7 +145,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
              uint32_t* __restrict__ work_head, TraceRays<MODE, LIST> ray_o, TraceRays<MODE, LIST> ray_d,
              DevHit* __restrict__ hits, uint32_t* __restrict__ occluded, DevCounters* __restrict__ counters, int refill,
              uint32_t cand_stride, uint32_t* __restrict__ spill, const unsigned long long* __restrict__ cand_mask,
-             const uint32_t* __restrict__ cand_chunks, bool recast_on, const float4* path_beta4, float4* path_L4) {
+             const uint32_t* __restrict__ cand_chunks, bool recast_on, const float4* path_beta4, float4* path_L4, bool root_entry) {
     constexpr bool ANY = MODE != 0;
     constexpr bool MIS = MODE == 2;
     static_assert(!COH || (MODE == 0 && !LIST && !COUNT), "the coherent instantiation is a plain short-list closest-hit launch");
@@ -211,6 +213,12 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     const unsigned long long mesh_mask0 = sc.mesh_masks[0];
     // LIST lane state: the mesh bits of the current chunk
     unsigned long long mmask = 0;
+    TraceRay r;   // the lane's ray: set before every pick_next() call, which looks at r.fast
+    r.O = V3s(0.f);
+    r.D = V3(0.f, 0.f, 1.f);
+    r.R = V3s(1.f);
+    r.fast = true;
+    bool at_entry = false;   // COUNT: the record the lane fetches next is the first of a mesh (counted as a root test)
     uint32_t cvisit = 0, cchunk = 0;   // LIST: chunks of the ray's candidates still to visit (one bit each), the current chunk
     // the sphere of an area light as (centre, r2), wherever it sits in the primitive list
     auto light_sphere = [&](int shape, v3& c, float& r2) {
@@ -227,19 +235,33 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     // Scene::Intersect's walk to the next primitive of the list (scene.h:8-17).  A mesh is entered through its root
     // pair -- the root-box test becomes the lane's next interior step (state B); spheres, planes and the end of the
     // list go through state A.
+    // ROOT ENTRY (short lists, root_entry: off with the developer knob AGPT_ROOT_STEP=1): a fast ray enters a mesh whose root is
+    // interior at the root's CHILD pair (the root_enc staged in s_prim[2k+1].w) and never runs the root-box step.  box_test_fast is
+    // monotone under box containment (a box inside a rejected box is rejected), and a root box is the exact
+    // union of its children's: where the reference rejects the root, both children are rejected at the same rayt and the lane
+    // moves on after the same one step; where it accepts the root, its next step is this very pair at an unchanged rayt.  Slow
+    // rays (NaN / inf quotients: not monotone) and meshes whose root is a leaf keep the root pair.
     auto pick_next = [&](unsigned long long& m) -> uint32_t {
         const unsigned long long low = m & (0ull - m);
         if (LIST) {
             if (m == 0) return cvisit ? CUR_FETCH : CUR_PICK;
             if (low & mmask) {
                 m ^= low;
+                if (COUNT) at_entry = true;
                 return rootpair_base + 2u * (64u * cchunk + (uint32_t)(__ffsll((long long)low) - 1));
             }
             return CUR_PICK;
         }
         if (low & mesh_mask0) {
             m ^= low;
-            return rootpair_base + 2u * (uint32_t)(__ffsll((long long)low) - 1);
+            const uint32_t k = (uint32_t)(__ffsll((long long)low) - 1);
+            if (COUNT) at_entry = true;
+            uint32_t entry = rootpair_base + 2u * k;
+            if (root_entry) {   // (wave-uniform)
+                const uint32_t enc = __float_as_uint(s_prim[2 * k + 1].w);
+                entry = (r.fast && (int32_t)enc >= 0) ? enc : entry;
+            }
+            return entry;
         }
         return CUR_PICK;
     };
@@ -267,11 +289,6 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     uint32_t cur = CUR_IDLE, hid = AGPT_HIT_MISS;
     int sp = 0;
     float rayt = 0.f, hb1 = 0.f, hb2 = 0.f;
-    TraceRay r;
-    r.O = V3s(0.f);
-    r.D = V3(0.f, 0.f, 1.f);
-    r.R = V3s(1.f);
-    r.fast = true;
 
     // wave-private ring of pre-filtered rays (path id + primitive mask), filled 64 rays at a time
     __shared__ uint32_t s_ring_pid[BLOCK / 64][AGPT_RING];
@@ -286,7 +303,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
     uint32_t c_int = 0, c_root = 0, c_tri = 0;   // COUNT
     TS(unsigned long long ts_steps[3] = {0, 0, 0}; unsigned long long ts_lanes[3] = {0, 0, 0}; unsigned long long ts_act = 0;
        unsigned long long ts_refills = 0; unsigned long long ts_refilled = 0; unsigned long long ts_pref = 0;
-       uint32_t ts_push[5] = {0, 0, 0, 0, 0};
+       uint32_t ts_push[5] = {0, 0, 0, 0, 0}; uint32_t ts_root = 0, ts_root_pass = 0;   // root-pair steps, and those whose root box passes
        unsigned long long ts_usteps[2] = {0, 0}; unsigned long long ts_ulanes[2] = {0, 0};)   // COH: B / C steps on the scalar path
     TCK(unsigned long long tk_refill = 0, tk_vote = 0, tk_bmem = 0, tk_balu = 0, tk_c = 0, tk_a = 0; const unsigned long long tk_begin = TCK_NOW();)
 
@@ -592,6 +609,7 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                         if (any_slow) {
                             if (!r.fast) pair_boxes_exact(np, r, rayt, hl, hr, dl, dr);
                         }
+                        TS(if (cur >= rootpair_base) { ts_root++; ts_root_pass += hl ? 1u : 0u; })
                         hr = hr && cur < rootpair_base;
                         if (hl && hr) {
                             const bool swap = dr < dl;
@@ -653,9 +671,11 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     if (any_slow) {  // scalar branch: rays outside the Markstein divide's domain, agpt_trace.h (true divisions)
                         if (!r.fast) pair_boxes_exact(np, r, rayt, hl, hr, dl, dr);
                     }
-                    if (COUNT) {
-                        if (cur < rootpair_base) c_int++; else c_root++;
+                    if (COUNT) {   // the first record of a mesh is its root test, whichever record the lane entered at
+                        if (at_entry) c_root++; else c_int++;
+                        at_entry = false;
                     }
+                    TS(if (cur >= rootpair_base) { ts_root++; ts_root_pass += hl ? 1u : 0u; })
                     hr = hr && cur < rootpair_base;   // a root pair has no right child
                     if (hl && hr) {
                         bool swap = ANY ? false : (dr < dl);
@@ -840,6 +860,12 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
             uint32_t v = ts_push[k];
             for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
             if (lane == 0) atomicAdd(d + 10 + k, (unsigned long long)v);
+        }
+        // root-pair steps (slot 15) and the passing ones (AGPT_DBG_ROOT_PASS): what entering at the child pair saves, counted with AGPT_ROOT_STEP=1
+        for (int off = 32; off > 0; off >>= 1) { ts_root += __shfl_down(ts_root, off); ts_root_pass += __shfl_down(ts_root_pass, off); }
+        if (lane == 0) {
+            atomicAdd(d + 15, (unsigned long long)ts_root);
+            atomicAdd(counters->dbg + AGPT_DBG_ROOT_PASS + (COH ? 3 : MODE), (unsigned long long)ts_root_pass);
         }
     }
 #endif

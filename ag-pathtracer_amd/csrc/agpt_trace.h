@@ -263,6 +263,10 @@ struct TraceCounters {
 //           exactly where the reference tests it (bvhtrimesh.h:187,195), then traverse.  Lanes move on to their
 //           next primitive independently.
 // Decisions, visit order, accepted hits and the work counters are those of the reference's recursion.
+// (This function, the reference-order variant, runs every root-box test.  The short-list instantiations of k_trace_fast do not: a
+// fast ray enters a mesh with an interior root at the root's child pair -- a rejected root box implies two rejected children, an
+// accepted one is followed by exactly that pair at the same t -- and only slow rays and leaf roots keep the re-test; agpt_kernels.h:
+// pick_next)
 template <bool ANY, bool COUNT>
 __device__ __forceinline__ bool trace_scene(const DevScene& sc, v3 O, v3 D, float tmax_in, DevHit& hit,
                                             uint32_t* stack, int stride, TraceCounters& cnt) {

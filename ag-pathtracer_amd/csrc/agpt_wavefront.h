@@ -170,6 +170,7 @@ struct DevCounters {
 #if defined(AGPT_TRACE_STATS) || defined(AGPT_SHADE_CLOCK)
     unsigned long long dbg[96];  // developer builds only (tools/build_variant.py): wave-step statistics of k_trace_fast, phase clocks
 #define AGPT_DBG_COH 64          // first of the 20 slots of the coherent closest-hit launch (the 16 of a mode + its scalar-path counts)
+#define AGPT_DBG_ROOT_PASS 84    // four slots (modes 0..2, coherent): root-pair steps whose root box passes (the steps: slot 15 of the mode)
 #endif
 };
 #ifdef AGPT_TRACE_STATS
