@@ -430,7 +430,10 @@ def skin_arrays(matrices, verts, joints, weights, normals=None, normal_joints=No
 
 
 class Context:
-    """One GPU. `stream` may be a raw hipStream_t handle (e.g. torch.cuda.current_stream().cuda_stream)."""
+    """One GPU. `stream` may be a raw hipStream_t handle (e.g. torch.cuda.Stream().cuda_stream; torch's default stream is handle 0, the
+    null stream).  A non-null handle must come from the HIP runtime instance libagpt_hip.so is bound to: with torch imported first
+    that is the wheel's copy, and exactly one libamdhip64 is then listed in /proc/self/maps.  set_stream
+    waits for the stream it leaves (include/agpt.h)."""
 
     def __init__(self, device=0, stream=None):
         self.L = lib()

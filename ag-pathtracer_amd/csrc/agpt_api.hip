@@ -206,6 +206,11 @@ int agpt_init(int device, agpt_ctx** out) {
 
 int agpt_set_stream(agpt_ctx* c, void* s) {
     if (!c) return fail(AGPT_ERR_INVALID, "agpt_set_stream: ctx is NULL");
+    if ((hipStream_t)s == c->stream) return AGPT_OK;
+    // the pool, queues, counters, events and pinned words are one set per context: what the stream being left still has queued
+    // (agpt_render's accumulate pass, the tile kernels) finishes before a call on the new stream can touch them
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     c->stream = (hipStream_t)s;
     return AGPT_OK;
 }

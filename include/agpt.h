@@ -119,7 +119,14 @@ typedef struct {
 const char* agpt_last_error(void);
 int agpt_version(void);
 
-/* context: picks the GPU.  stream = hipStream_t to launch on, or NULL for the null stream */
+/* context: picks the GPU.  stream = hipStream_t to launch on, or NULL for the null stream.
+ * agpt_set_stream: every later call on the context enqueues on `hip_stream` and is ordered with the caller's other work there, a
+ *   stream created with hipStreamNonBlocking included.  The context's scratch memory, queues, counters and events are one set shared
+ *   by all its calls, and some calls return with work still queued (agpt_render without stats, the tile calls): the call therefore
+ *   SYNCHRONISES THE STREAM IT LEAVES before it stores the new one, so that work in flight on the old stream never shares that state
+ *   with a call on the new one.  Setting the handle the context already has does nothing.  The handle must belong to the HIP runtime
+ *   instance this library is linked to (a process can hold more than one copy of libamdhip64; a handle of another copy is
+ *   meaningless here). */
 int agpt_init(int device, agpt_ctx** out);
 int agpt_set_stream(agpt_ctx*, void* hip_stream);
 void agpt_destroy(agpt_ctx*);

@@ -152,6 +152,7 @@ def test_refusals_in_the_documented_order_change_nothing():
 
 
 TORCH_CHILD = r"""
+import contextlib
 import sys
 sys.path[:0] = [%(root)r, %(tests)r]
 import torch                      # before the library touches the GPU (INTEGRATION.md section 3)
@@ -160,44 +161,70 @@ torch.zeros(1, device="cuda")
 import ag_pathtracer_amd as ag
 import device_update_cases as dc
 
+# a stream handle means something only to the HIP runtime copy that made it: torch's streams may reach the library only if torch and
+# the library are bound to ONE libamdhip64 (the check comes before the use)
+ag.lib()
+with open("/proc/self/maps") as f:
+    runtimes = sorted({ln.split(None, 5)[5].strip() for ln in f if "libamdhip64" in ln and len(ln.split(None, 5)) == 6})
+print("libamdhip64 mapped: %%d %%s" %% (len(runtimes), runtimes))
+assert len(runtimes) == 1, "torch and libagpt_hip.so are bound to different HIP runtime copies: a torch stream is no handle for the library"
+
+waits = [0]
+stream_synchronize = torch.cuda.Stream.synchronize
+def counted(self):
+    waits[0] += 1
+    return stream_synchronize(self)
+torch.cuda.Stream.synchronize = counted
+
 desc = dc.zoo_scene()
 for own_stream in (False, True):
-    ctx = ag.Context(0, stream=torch.cuda.current_stream().cuda_stream if own_stream else None)
-    a, b = desc.instantiate(ag.Scene(ctx)), desc.instantiate(ag.Scene(ctx))
-    for prim in (dc.GRID1_N, dc.GRID4, dc.PRIMS[0]):
-        v, n = dc.zoo_arrays(prim, 1)
-        a.update_mesh(prim, v, n)
-        tv = torch.from_numpy(v).cuda() * 1.0          # produced on torch's stream
-        tn = None if n is None else torch.from_numpy(n).cuda()
-        b.update_mesh(prim, tv, tn, "refit")
-        tv.fill_(float("nan"))
-    dc.assert_same(dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS))
-    v, n = dc.zoo_arrays(dc.GRID1_N, 2)
-    a.update_mesh(dc.GRID1_N, v, n)
-    b.update_mesh(dc.GRID1_N, torch.from_numpy(v), torch.from_numpy(n))   # CPU tensors: the host call
-    dc.assert_same(dc.snapshot(a, desc, [dc.GRID1_N]), dc.snapshot(b, desc, [dc.GRID1_N]))
-    before = dc.snapshot(b, desc, [dc.GRID1_N])
-    tv, tn = torch.from_numpy(v).cuda(), torch.from_numpy(n).cuda()
-    bad = [(tv.double(), tn), (tv.half(), tn), (tv.reshape(-1), tn), (tv.t().contiguous(), tn), (torch.cat([tv, tv], 1)[:, :3], tn),
-           (tv, tn.double()), (tv, torch.from_numpy(n)), (torch.from_numpy(v), tn), (torch.empty(tv.shape, device="meta"), tn)]
-    for x, y in bad:
-        try:
-            b.update_mesh(dc.GRID1_N, x, y)
-        except ValueError as e:
-            assert "update_mesh" in str(e)
-        else:
-            raise AssertionError("accepted %%s %%s %%s" %% (x.dtype, tuple(x.shape), x.device))
-    dc.assert_same(dc.snapshot(b, desc, [dc.GRID1_N]), before)
-    a.close(); b.close(); ctx.close()
+    # own_stream: the context runs on a stream of torch's pool (non-blocking, a non-zero handle -- torch's DEFAULT stream is handle 0,
+    # the null stream) and the tensors are produced on it, so Scene.update_mesh hands them over without a wait
+    s = torch.cuda.Stream() if own_stream else None
+    ctx = ag.Context(0, stream=s.cuda_stream if own_stream else None)
+    assert (ctx.stream != 0) == own_stream
+    with (torch.cuda.stream(s) if own_stream else contextlib.nullcontext()):
+        a, b = desc.instantiate(ag.Scene(ctx)), desc.instantiate(ag.Scene(ctx))
+        waits[0] = 0
+        for prim in (dc.GRID1_N, dc.GRID4, dc.PRIMS[0]):
+            v, n = dc.zoo_arrays(prim, 1)
+            a.update_mesh(prim, v, n)
+            tv = torch.from_numpy(v).cuda() * 1.0          # produced on torch's current stream
+            tn = None if n is None else torch.from_numpy(n).cuda()
+            b.update_mesh(prim, tv, tn, "refit")
+            tv.fill_(float("nan"))
+        assert waits[0] == (0 if own_stream else 3), waits   # (the shortcut: no wait when the context runs on that very stream)
+        dc.assert_same(dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS))
+        v, n = dc.zoo_arrays(dc.GRID1_N, 2)
+        a.update_mesh(dc.GRID1_N, v, n)
+        b.update_mesh(dc.GRID1_N, torch.from_numpy(v), torch.from_numpy(n))   # CPU tensors: the host call
+        dc.assert_same(dc.snapshot(a, desc, [dc.GRID1_N]), dc.snapshot(b, desc, [dc.GRID1_N]))
+        before = dc.snapshot(b, desc, [dc.GRID1_N])
+        tv, tn = torch.from_numpy(v).cuda(), torch.from_numpy(n).cuda()
+        bad = [(tv.double(), tn), (tv.half(), tn), (tv.reshape(-1), tn), (tv.t().contiguous(), tn), (torch.cat([tv, tv], 1)[:, :3], tn),
+               (tv, tn.double()), (tv, torch.from_numpy(n)), (torch.from_numpy(v), tn), (torch.empty(tv.shape, device="meta"), tn)]
+        for x, y in bad:
+            try:
+                b.update_mesh(dc.GRID1_N, x, y)
+            except ValueError as e:
+                assert "update_mesh" in str(e)
+            else:
+                raise AssertionError("accepted %%s %%s %%s" %% (x.dtype, tuple(x.shape), x.device))
+        dc.assert_same(dc.snapshot(b, desc, [dc.GRID1_N]), before)
+        torch.cuda.current_stream().synchronize()
+        a.close(); b.close(); ctx.close()
 print("torch-ok")
 """
 
 
 def test_torch_device_tensors_equal_ndarrays():
     """Scene.update_mesh with torch tensors on the GPU (data_ptr() handed to agpt_scene_update_mesh_device after torch's stream was
-    synchronised; once with the context on torch's stream) against the ndarray call; wrong dtype, shape, layout or device is refused
-    in Python.  In a child process: torch must initialise the GPU before the library does."""
+    synchronised; and once with the context on a torch.cuda.Stream() that also produces the tensors, which needs no wait) against the
+    ndarray call; wrong dtype, shape, layout or device is refused in Python.  In a child process: torch must initialise the GPU before
+    the library does, and the child first checks that both are bound to one HIP runtime copy -- only then is torch's stream a handle
+    the library may be given."""
     code = TORCH_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}
     cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
+    print(r.stdout[-2000:])
     assert r.returncode == 0 and "torch-ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
