@@ -116,6 +116,29 @@ void oracle_dbg_li(const oracle_scene*, const oracle_ray* ray, float L_out[3]);
 void oracle_camera_ray(const oracle_scene*, float s, float t, uint32_t* rng, oracle_ray* out);
 /* one full path (PathTracer::Li) from an explicit RNG state; returns radiance */
 void oracle_li(const oracle_scene*, const oracle_ray* ray, uint32_t* rng, float L_out[3], oracle_stats* stats);
+/* oracle_li plus how often the path entered each rarely-taken branch of surface and light sampling (tests/shade_edge_cases.py).
+ * The triangle counters are per passed triangle test, as TriangleIntersect builds its SurfaceInteraction there -- a hit that a
+ * nearer one replaces counts too -- the sphere-light ones per Sample_Li / Pdf_Li call, SHADED per path vertex.  Counting changes no
+ * output: same radiance, stream and stats as oracle_li. */
+enum {
+    ORACLE_TALLY_INSIDE_SAMPLE = 0,     /* Sphere::Sample(ref): |ref.p - c|^2 <= r^2, uniform-sphere sampling */
+    ORACLE_TALLY_INSIDE_PDF,            /* Sphere::Pdf: the same test, 1 / (4 pi) */
+    ORACLE_TALLY_SMALL_CONE,            /* Sphere::Sample(ref): sinThetaMax2 < 0.00068523f */
+    ORACLE_TALLY_WIDE_CONE,             /* ... and the other side */
+    ORACLE_TALLY_NS_ZERO,               /* interpolated normal of zero length -> geometric normal */
+    ORACLE_TALLY_TS_ZERO,               /* cross(ss, ns) of zero length -> CoordinateSystem(ns) */
+    ORACLE_TALLY_DEGENERATE_FRAME,      /* degenerate uv or dpdu x dpdv == 0 -> CoordinateSystem(ng) */
+    ORACLE_TALLY_ZERO_AREA_REJECT,      /* ... with ng of zero length: the hit is rejected after its t test (quirk 11) */
+    ORACLE_TALLY_SPHERE_POLE,           /* Sphere::Intersect: pHit.x == 0 && pHit.y == 0 fix-up */
+    ORACLE_TALLY_LIGHT_SAMPLE_REJECTED, /* AreaLight::Sample_Li: pdf == 0 or the sample is the reference point */
+    ORACLE_TALLY_INSIDE_PDF_INF,        /* Sphere::Sample(ref), inside: the converted pdf is infinite */
+    ORACLE_TALLY_MIS_LIGHT_PDF_ZERO,    /* EstimateDirect: Pdf_Li == 0 for the BSDF sample */
+    ORACLE_TALLY_BSDF_BLACK_END,        /* PathTracer::Li: the path ends on a black f or a zero pdf */
+    ORACLE_TALLY_SHADED,                /* path vertices with a material */
+    ORACLE_TALLY_COUNT
+};
+void oracle_li_tally(const oracle_scene*, const oracle_ray* ray, uint32_t* rng, float L_out[3], oracle_stats* stats,
+                     uint32_t counts[ORACLE_TALLY_COUNT]);
 
 /* Host-side scene prep restated for tests: TriangleMesh::CreateBackdrop (trianglemesh.cpp:232-318).
  * Output capacities: verts/normals 3*(2*(steps+5)) floats, uvs 2*(2*(steps+5)), indices 3*6*(steps+4) ints */

@@ -29,6 +29,10 @@ class Stats(C.Structure):
         return int(self.closest_rays + self.anyhit_rays)
 
 
+# oracle_li_tally's counters, in the order of agpt_oracle.h's ORACLE_TALLY_* enum
+TALLY_NAMES = ("inside_sample", "inside_pdf", "small_cone", "wide_cone", "ns_zero", "ts_zero", "degenerate_frame", "zero_area_reject",
+               "sphere_pole", "light_sample_rejected", "inside_pdf_inf", "mis_light_pdf_zero", "bsdf_black_end", "shaded")
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("tmax", np.float32)])
 HIT_DTYPE = np.dtype([("hit", np.int32), ("prim", np.int32), ("tri", np.int32),
                       ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
@@ -83,6 +87,7 @@ def lib():
     L.oracle_camera_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_uint32), C.c_void_p]
     L.oracle_dbg_li.argtypes = [C.c_void_p, C.c_void_p, fp]
     L.oracle_li.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), fp, C.POINTER(Stats)]
+    L.oracle_li_tally.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), fp, C.POINTER(Stats), C.POINTER(C.c_uint32)]
     L.oracle_create_backdrop.argtypes = [fp, fp, C.c_float, C.c_int, fp, fp, fp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.oracle_pin_heightfield.argtypes = [C.c_int, C.c_float, fp, fp, fp, ip]
     L.oracle_set_trig_mode.argtypes = [C.c_int]
@@ -267,12 +272,18 @@ class OracleScene:
         self.L.oracle_camera_ray(self.h, float(s), float(t), C.byref(state), r.ctypes.data_as(C.c_void_p))
         return r[0], state.value
 
-    def li(self, ray, rng):
+    def li(self, ray, rng, tally=False):
+        """(radiance, stream state after the path, stats); with tally=True also the branch counts, uint32 [len(TALLY_NAMES)]"""
         r = np.zeros(1, RAY_DTYPE)
         r[0] = ray
         state = C.c_uint32(rng)
         out = np.zeros(3, np.float32)
         st = Stats()
+        if tally:
+            counts = np.zeros(len(TALLY_NAMES), np.uint32)
+            self.L.oracle_li_tally(self.h, r.ctypes.data_as(C.c_void_p), C.byref(state), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                   C.byref(st), counts.ctypes.data_as(C.POINTER(C.c_uint32)))
+            return out, state.value, st, counts
         self.L.oracle_li(self.h, r.ctypes.data_as(C.c_void_p), C.byref(state), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st))
         return out, state.value, st
 

@@ -26,7 +26,9 @@
 typedef struct {
     uint32_t* rng;
     oracle_stats st;
+    uint32_t tally[ORACLE_TALLY_COUNT]; /* branch counts of this call (oracle_li_tally); nothing reads them back */
 } octx;
+#define TALLY(c, which) ((c)->tally[ORACLE_TALLY_##which]++)
 
 static inline uint32_t rng_uint(uint32_t* s) {
     *s ^= *s << 13;
@@ -767,7 +769,8 @@ static int triangle_intersect(const Mesh* m, int shape, Ray* ray, int tridx, Sur
     }
     if (degenerateUV || f3_sqrlen(f3_cross(dpdu, dpdv)) == 0) {
         f3 ng = f3_cross(f3_sub(v2, v0), f3_sub(v1, v0));
-        if (f3_sqrlen(ng) == 0) return 0; /* quirk 11: reject after the t test, hit/ray.t untouched */
+        if (f3_sqrlen(ng) == 0) { TALLY(c, ZERO_AREA_REJECT); return 0; } /* quirk 11: reject after the t test, hit/ray.t untouched */
+        TALLY(c, DEGENERATE_FRAME);
         coordinate_system(f3_normalize(ng), &dpdu, &dpdv);
     }
 
@@ -781,14 +784,16 @@ static int triangle_intersect(const Mesh* m, int shape, Ray* ray, int tridx, Sur
         f3 n2 = m->normals[m->indices[tridx + 2].n];
         f3 ns = f3_add(f3_add(f3_muls(n0, b0), f3_muls(n1, b1)), f3_muls(n2, b2));
         if (f3_sqrlen(ns) > 0.f) ns = f3_normalize(ns);
-        else ns = hit->n;
+        else { ns = hit->n; TALLY(c, NS_ZERO); }
         f3 ss = f3_normalize(hit->dpdu);
         f3 ts = f3_cross(ss, ns);
         if (f3_sqrlen(ts) > 0.f) {
             ts = f3_normalize(ts);
             ss = f3_cross(ts, ns);
-        } else
+        } else {
+            TALLY(c, TS_ZERO);
             coordinate_system(ns, &ss, &ts);
+        }
         si_set_shading_geometry(hit, ss, ts, 1);
     }
     return 1;
@@ -880,7 +885,7 @@ static int mesh_intersect_p(const Mesh* m, const Ray* ray, octx* c) {
 /* ------------------------------------------------------------------------------------------------
  * Sphere -- intersectable.h:164-226 (Intersect/IntersectP), :228-317 (Area/Sample/Pdf)
  * ---------------------------------------------------------------------------------------------- */
-static int sphere_intersect(const Sphere* sp, int shape, Ray* ray, SurfaceInteraction* hit) {
+static int sphere_intersect(const Sphere* sp, int shape, Ray* ray, SurfaceInteraction* hit, octx* c) {
     f3 oc = f3_sub(ray->O, sp->Center);
     float half_b = f3_dot(oc, ray->D);
     float cc = f3_sqrlen(oc) - sp->r2;
@@ -894,7 +899,7 @@ static int sphere_intersect(const Sphere* sp, int shape, Ray* ray, SurfaceIntera
     }
     f3 p = ray_at(ray, root);
     f3 pHit = f3_sub(p, sp->Center);
-    if (pHit.x == 0 && pHit.y == 0) pHit.x = O_EPSILON * sp->r;
+    if (pHit.x == 0 && pHit.y == 0) { pHit.x = O_EPSILON * sp->r; TALLY(c, SPHERE_POLE); }
     float phi = o_atan2f(pHit.y, pHit.x);   /* (only DbgIntegrator reads u) */
     if (phi < 0) phi += O_TWOPI;
     float u = phi * O_INV2PI;
@@ -937,10 +942,11 @@ static Interaction sphere_sample_u(const Sphere* sp, f2 u, float* pdf) { /* :230
     *pdf = 1 / sphere_area(sp);
     return it;
 }
-static Interaction sphere_sample_ref(const Sphere* sp, const SurfaceInteraction* ref, f2 u, float* pdf) { /* :239-304 */
+static Interaction sphere_sample_ref(const Sphere* sp, const SurfaceInteraction* ref, f2 u, float* pdf, octx* c) { /* :239-304 */
     f3 pCenter = sp->Center;
     f3 pOrigin = ref->p;
     if (f3_sqrlen(f3_sub(pOrigin, pCenter)) <= sp->r2) {
+        TALLY(c, INSIDE_SAMPLE);
         Interaction intr = sphere_sample_u(sp, u, pdf);
         f3 wi = f3_sub(intr.p, ref->p);
         if (f3_sqrlen(wi) == 0)
@@ -949,7 +955,7 @@ static Interaction sphere_sample_ref(const Sphere* sp, const SurfaceInteraction*
             wi = f3_normalize(wi);
             *pdf *= f3_sqrlen(f3_sub(ref->p, intr.p)) / f3_absdot(intr.n, f3_neg(wi));
         }
-        if (isinf(*pdf)) *pdf = 0;
+        if (isinf(*pdf)) { *pdf = 0; TALLY(c, INSIDE_PDF_INF); }
         return intr;
     }
     float dc = f3_len(f3_sub(ref->p, pCenter));
@@ -964,9 +970,11 @@ static Interaction sphere_sample_ref(const Sphere* sp, const SurfaceInteraction*
     float cosTheta = (cosThetaMax - 1) * u.x + 1;
     float sinTheta2 = 1 - cosTheta * cosTheta;
     if (sinThetaMax2 < 0.00068523f) {
+        TALLY(c, SMALL_CONE);
         sinTheta2 = sinThetaMax2 * u.x;
         cosTheta = sqrtf(1 - sinTheta2);
-    }
+    } else
+        TALLY(c, WIDE_CONE);
     float cosAlpha = sinTheta2 * invSinThetaMax +
                      cosTheta * sqrtf(s_maxf(0.f, 1.f - sinTheta2 * invSinThetaMax * invSinThetaMax));
     float sinAlpha = sqrtf(s_maxf(0.f, 1.f - cosAlpha * cosAlpha));
@@ -979,11 +987,11 @@ static Interaction sphere_sample_ref(const Sphere* sp, const SurfaceInteraction*
     *pdf = 1 / (2 * O_PI * (1 - cosThetaMax));
     return it;
 }
-static float sphere_pdf(const Sphere* sp, const SurfaceInteraction* ref, f3 wi) { /* :306-317 */
+static float sphere_pdf(const Sphere* sp, const SurfaceInteraction* ref, f3 wi, octx* c) { /* :306-317 */
     (void)wi;
     f3 pCenter = sp->Center;
     f3 pOrigin = ref->p;
-    if (f3_sqrlen(f3_sub(pOrigin, pCenter)) <= sp->r2) return 1 / (4 * O_PI);
+    if (f3_sqrlen(f3_sub(pOrigin, pCenter)) <= sp->r2) { TALLY(c, INSIDE_PDF); return 1 / (4 * O_PI); }
     float sinThetaMax2 = sp->r2 / f3_sqrlen(f3_sub(ref->p, pCenter));
     float cosThetaMax = sqrtf(s_maxf(0.f, 1 - sinThetaMax2));
     return uniform_cone_pdf(cosThetaMax);
@@ -1024,7 +1032,7 @@ static int scene_intersect(const oracle_scene* s, Ray* ray, SurfaceInteraction* 
     for (int i = 0; i < s->n_prims; i++) {
         const ScenePrim* p = &s->prims[i];
         int h = (p->type == PRIM_MESH)    ? mesh_intersect(&s->meshes[p->index], i, ray, hit, c)
-                : (p->type == PRIM_SPHERE) ? sphere_intersect(&s->spheres[p->index], i, ray, hit)
+                : (p->type == PRIM_SPHERE) ? sphere_intersect(&s->spheres[p->index], i, ray, hit, c)
                                            : plane_intersect(&s->planes[p->index], i, ray, hit);
         if (h) found = 1;
     }
@@ -1462,8 +1470,9 @@ static f3 light_sample_li(const oracle_scene* s, const Light* l, const SurfaceIn
         return l->Lemit;
     }
     const Sphere* sp = &s->spheres[s->prims[l->shape].index];
-    Interaction pShape = sphere_sample_ref(sp, ref, u, pdf);
+    Interaction pShape = sphere_sample_ref(sp, ref, u, pdf, c);
     if (*pdf == 0 || f3_sqrlen(f3_sub(pShape.p, ref->p)) == 0) {
+        TALLY(c, LIGHT_SAMPLE_REJECTED);
         *pdf = 0;
         return F3s(0.f);
     }
@@ -1473,7 +1482,7 @@ static f3 light_sample_li(const oracle_scene* s, const Light* l, const SurfaceIn
     *vis = make_ray(f3_add(ref->p, f3_muls(*wi, O_EPSILON)), *wi, dist - 10 * O_EPSILON);
     return l->Lemit;
 }
-static float light_pdf_li(const oracle_scene* s, const Light* l, const SurfaceInteraction* ref, f3 wi) {
+static float light_pdf_li(const oracle_scene* s, const Light* l, const SurfaceInteraction* ref, f3 wi, octx* c) {
     if (l->type == LIGHT_UNIFORM_INFINITE) return f3_dot(ref->n, wi) > 0 ? O_INV2PI : 0.f;
     if (l->type == LIGHT_INFINITE_AREA) { /* lights.cpp:92-106 */
         const EnvMap* e = l->env;
@@ -1491,7 +1500,7 @@ static float light_pdf_li(const oracle_scene* s, const Light* l, const SurfaceIn
         float discrete = e->func[y * e->width + x] / (e->funcInt * e->n); /* DiscretePDF sampling.h:63-65 */
         return e->n * discrete / (2 * O_PI * O_PI * sinTheta);
     }
-    return sphere_pdf(&s->spheres[s->prims[l->shape].index], ref, wi);
+    return sphere_pdf(&s->spheres[s->prims[l->shape].index], ref, wi, c);
 }
 static f3 light_Le(const Light* l, f3 D) {
     if (l->type == LIGHT_UNIFORM_INFINITE) return l->Lemit;
@@ -1532,8 +1541,8 @@ static f3 EstimateDirect(const oracle_scene* s, const SurfaceInteraction* si, f2
         f = f3_muls(f, f3_absdot(wi, si->shading.n));
         if (!f3_isblack(f) && scatteringPdf > 0) {
             float weight = 1;
-            lightPdf = light_pdf_li(s, light, si, wi);
-            if (lightPdf == 0) return Ld;
+            lightPdf = light_pdf_li(s, light, si, wi, c);
+            if (lightPdf == 0) { TALLY(c, MIS_LIGHT_PDF_ZERO); return Ld; }
             weight = PowerHeuristic(1, scatteringPdf, 1, lightPdf);
             SurfaceInteraction lightIsect;
             lightIsect.shape = -1;
@@ -1586,6 +1595,7 @@ static f3 PathTracer_Li(const oracle_scene* s, const Ray* r, octx* c) {
             continue;
         }
         c->st.shaded_vertices++;
+        TALLY(c, SHADED);
         if (!bsdf_is_perfectly_specular(&isect.bsdf)) L = f3_add(L, f3_mul(beta, UniformSampleOneLight(s, &isect, c)));
         f3 wo = f3_neg(ray.D), wi = F3s(0.f);
         f2 u;
@@ -1593,7 +1603,7 @@ static f3 PathTracer_Li(const oracle_scene* s, const Ray* r, octx* c) {
         float pdf = 0;
         int sampledSpecular = 0;
         f3 f = bsdf_sample_f(&isect.bsdf, wo, &wi, u, &pdf, 0, &sampledSpecular);
-        if (f3_isblack(f) || pdf == 0) break;
+        if (f3_isblack(f) || pdf == 0) { TALLY(c, BSDF_BLACK_END); break; }
         beta = f3_mul(beta, f3_divs(f3_muls(f, f3_absdot(wi, isect.shading.n)), pdf));
         specularBounce = sampledSpecular;
         /* Russian roulette :180-185 tests the `depth` parameter (always 0): never fires, 0 draws */
@@ -1698,12 +1708,17 @@ void oracle_camera_ray(const oracle_scene* s, float sx, float ty, uint32_t* rng,
     out->d[0] = r.D.x; out->d[1] = r.D.y; out->d[2] = r.D.z;
     out->tmax = r.t;
 }
-void oracle_li(const oracle_scene* s, const oracle_ray* ray, uint32_t* rng, float L_out[3], oracle_stats* stats) {
+void oracle_li_tally(const oracle_scene* s, const oracle_ray* ray, uint32_t* rng, float L_out[3], oracle_stats* stats,
+                     uint32_t counts[ORACLE_TALLY_COUNT]) {
     octx c; memset(&c, 0, sizeof(c)); c.rng = rng;
     Ray r = make_ray(F3(ray->o[0], ray->o[1], ray->o[2]), F3(ray->d[0], ray->d[1], ray->d[2]), ray->tmax);
     f3 L = PathTracer_Li(s, &r, &c);
     L_out[0] = L.x; L_out[1] = L.y; L_out[2] = L.z;
     if (stats) *stats = c.st;
+    if (counts) memcpy(counts, c.tally, sizeof(c.tally));
+}
+void oracle_li(const oracle_scene* s, const oracle_ray* ray, uint32_t* rng, float L_out[3], oracle_stats* stats) {
+    oracle_li_tally(s, ray, rng, L_out, stats, NULL);
 }
 
 /* DbgIntegrator::Li -- integrator.h:107-118: the hit's uv as a colour ((u, v, 0) / 5; red where u or v is exactly 0), black on a miss */
