@@ -38,7 +38,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_morph_arrays", "agpt_scene_set_mesh_morph_targets", "agpt_scene_morph_mesh", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
@@ -190,7 +190,10 @@ def lib():
     for name, args in (("agpt_scene_update_mesh_device", [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int]),
                        ("agpt_scene_transform_mesh", [vp, C.c_int, fp, C.c_int]), ("agpt_transform_arrays", [fp, fp, C.c_int, fp, C.c_int, fp, fp]),
                        ("agpt_skin_arrays", [fp, C.c_int, C.c_int, fp, C.c_int, ip, fp, fp, C.c_int, ip, fp, fp, fp]),
-                       ("agpt_scene_set_mesh_skin", [vp, C.c_int, C.c_int, C.c_int, ip, fp, ip, fp]), ("agpt_scene_pose_mesh", [vp, C.c_int, fp, C.c_int, C.c_int])):
+                       ("agpt_scene_set_mesh_skin", [vp, C.c_int, C.c_int, C.c_int, ip, fp, ip, fp]), ("agpt_scene_pose_mesh", [vp, C.c_int, fp, C.c_int, C.c_int]),
+                       ("agpt_morph_arrays", [fp, C.c_int, fp, C.c_int, fp, fp, C.c_int, fp, fp, fp]),
+                       ("agpt_scene_set_mesh_morph_targets", [vp, C.c_int, C.c_int, fp, fp]),
+                       ("agpt_scene_morph_mesh", [vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int])):
         if not variant or hasattr(L, name):   # (an A/B variant built from an older commit lacks them: tools/mesh_update_time.py --parent-lib)
             getattr(L, name).argtypes = args
     L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
@@ -426,6 +429,32 @@ def skin_arrays(matrices, verts, joints, weights, normals=None, normal_joints=No
     fp = C.POINTER(C.c_float)
     _check(lib().agpt_skin_arrays(m.ctypes.data_as(fp), m.shape[0], j.shape[1], pv, v.shape[0], pj, pw, pn, 0 if n is None else n.shape[0], pnj, pnw,
                                   vo.ctypes.data_as(fp), None if no is None else no.ctypes.data_as(fp)), "agpt_skin_arrays")
+    return vo, no
+
+
+def _deltas(deltas, n, what):
+    d = np.ascontiguousarray(deltas, np.float32)
+    if d.ndim != 3 or d.shape[1:] != (n, 3) or d.shape[0] < 1:
+        raise ValueError("%s deltas have shape %s, not (n_targets, %d, 3)" % (what, d.shape, n))
+    return d, d.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def morph_arrays(weights, verts, position_deltas, normals=None, normal_deltas=None):
+    """agpt_morph_arrays on the host (no GPU needed): verts[n, 3] plus the weighted position_deltas[T, n, 3], the targets in order, a
+    target of weight 0 skipped, and normals[m, 3] plus normal_deltas[T, m, 3] likewise (None: the normals are returned as they are)
+    -> (verts[n, 3], normals[m, 3] or None), the arithmetic of Scene.morph_mesh."""
+    v, pv = _f(np.asarray(verts).reshape(-1, 3))
+    w, pw = _f(np.asarray(weights).reshape(-1))
+    d, pd = _deltas(position_deltas, v.shape[0], "position")
+    n, pn = (None, None) if normals is None else _f(np.asarray(normals).reshape(-1, 3))
+    nd, pnd = (None, None) if normal_deltas is None or n is None else _deltas(normal_deltas, n.shape[0], "normal")
+    if w.shape[0] != d.shape[0] or (nd is not None and nd.shape[0] != d.shape[0]):
+        raise ValueError("morph_arrays: one weight and one row of deltas per target")
+    vo = np.empty_like(v)
+    no = None if n is None else np.empty_like(n)
+    fp = C.POINTER(C.c_float)
+    _check(lib().agpt_morph_arrays(pw, d.shape[0], pv, v.shape[0], pd, pn, 0 if n is None else n.shape[0], pnd,
+                                   vo.ctypes.data_as(fp), None if no is None else no.ctypes.data_as(fp)), "agpt_morph_arrays")
     return vo, no
 
 
@@ -763,6 +792,31 @@ class Scene:
         m = _joint_matrices(matrices)
         _check(self.L.agpt_scene_pose_mesh(self.h, int(prim), m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], self._update_mode(mode, "pose_mesh")),
                "agpt_scene_pose_mesh")
+
+    def set_mesh_morph_targets(self, prim, position_deltas, normal_deltas=None):
+        """agpt_scene_set_mesh_morph_targets: the targets of mesh primitive `prim` for morph_mesh -- position_deltas of shape
+        (T, n_vertices, 3) and, optionally, normal_deltas (T, n_normals, 3), with the mesh's own counts (the library reads that many).
+        position_deltas=None removes them."""
+        if position_deltas is None:
+            _check(self.L.agpt_scene_set_mesh_morph_targets(self.h, int(prim), 0, None, None), "agpt_scene_set_mesh_morph_targets")
+            return
+        d = np.ascontiguousarray(position_deltas, np.float32)
+        nd = None if normal_deltas is None else np.ascontiguousarray(normal_deltas, np.float32)
+        if d.ndim != 3 or d.shape[2] != 3 or (nd is not None and (nd.ndim != 3 or nd.shape[2] != 3 or nd.shape[0] != d.shape[0])):
+            raise ValueError("set_mesh_morph_targets: deltas of shape (n_targets, n, 3), as many targets for normals as for positions")
+        fp = C.POINTER(C.c_float)
+        _check(self.L.agpt_scene_set_mesh_morph_targets(self.h, int(prim), d.shape[0], d.ctypes.data_as(fp), None if nd is None else nd.ctypes.data_as(fp)),
+               "agpt_scene_set_mesh_morph_targets")
+
+    def morph_mesh(self, prim, weights, matrices=None, mode=UPDATE_REFIT):
+        """agpt_scene_morph_mesh: mesh primitive `prim` morphed on the GPU by weights[T] through the targets of set_mesh_morph_targets
+        and then, with matrices[n_joints, 4, 4] (or [n_joints, 16]), posed through the binding of set_mesh_skin, from its rest pose;
+        absolute, not cumulative.  The scene is what update_mesh(prim, *morph_arrays(weights, rest_verts, ...), mode) leaves -- with
+        matrices, those arrays through skin_arrays."""
+        w, pw = _f(np.asarray(weights).reshape(-1))
+        m = None if matrices is None else _joint_matrices(matrices)
+        _check(self.L.agpt_scene_morph_mesh(self.h, int(prim), pw, w.shape[0], None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
+                                            0 if m is None else m.shape[0], self._update_mode(mode, "morph_mesh")), "agpt_scene_morph_mesh")
 
     def set_bvh_builder(self, builder):
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""

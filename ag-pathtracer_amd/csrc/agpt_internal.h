@@ -201,18 +201,21 @@ struct agpt_scene {
     // mesh's first REFIT, agpt_update.h; owned).  bounds_stale: the bounds of HostMesh::nodes are behind the device's (root box
     // excepted; brought up to date by sync_mirror).  arrays_stale: HostMesh::vertices / normals are behind the device's as well (a
     // device-pointer or transform REFIT: the new arrays exist only in the updater).  rest_*: the rest pose of
-    // agpt_scene_transform_mesh and agpt_scene_pose_mesh, a host copy taken by the mesh's first transform or pose after its arrays were
-    // last given explicitly (DESIGN.md section 5.7 lists who reads the mirror).  skin: the binding of agpt_scene_set_mesh_skin (host
-    // copy; the updater holds the device copies from the first pose on).
+    // agpt_scene_transform_mesh, agpt_scene_pose_mesh and agpt_scene_morph_mesh, a host copy taken by the mesh's first transform, pose or
+    // morph after its arrays were last given explicitly (DESIGN.md section 5.7 lists who reads the mirror).  skin: the binding of
+    // agpt_scene_set_mesh_skin (host copy; the updater holds the device copies from the first pose on).  morph: the targets of
+    // agpt_scene_set_mesh_morph_targets, likewise (device copies from the first morph on).
     struct MeshUpdate {
         agpt::MeshUpdater* updater = nullptr;
         bool bounds_stale = false, arrays_stale = false, rest_valid = false;
         std::vector<v3> rest_vertices, rest_normals;
         agpt::SkinBinding skin;
+        agpt::MorphTargets morph;
         MeshUpdate() = default;
         MeshUpdate(MeshUpdate&& o) noexcept
             : updater(o.updater), bounds_stale(o.bounds_stale), arrays_stale(o.arrays_stale), rest_valid(o.rest_valid),
-              rest_vertices(std::move(o.rest_vertices)), rest_normals(std::move(o.rest_normals)), skin(std::move(o.skin)) {
+              rest_vertices(std::move(o.rest_vertices)), rest_normals(std::move(o.rest_normals)), skin(std::move(o.skin)),
+              morph(std::move(o.morph)) {
             o.updater = nullptr;
         }
         ~MeshUpdate() { agpt::mesh_updater_destroy(updater); }

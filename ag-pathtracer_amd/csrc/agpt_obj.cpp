@@ -71,6 +71,7 @@
 #include <vector>
 
 #include "../../include/agpt.h"
+#include "agpt_morph.h"
 #include "agpt_skin.h"
 #include "agpt_transform.h"
 
@@ -504,6 +505,33 @@ int agpt_skin_arrays(const float* joints16, int n_joints, int influences, const 
     for (size_t i = 0; i < (size_t)n_normals; i++) {
         float p[3];
         agpt::skin_blend<false>(palette.data(), stride, nj + K * i, nw + K * i, influences, normals + 3 * i, p);
+        std::memcpy(normals_out + 3 * i, p, sizeof(p));
+    }
+    return AGPT_OK;
+}
+
+int agpt_morph_arrays(const float* weights, int n_targets, const float* vertices, int n_vertices, const float* position_deltas, const float* normals,
+                      int n_normals, const float* normal_deltas, float* vertices_out, float* normals_out) {
+    const std::string f = "agpt_morph_arrays: ";
+    if (!weights || !vertices || !position_deltas || !vertices_out)
+        return agpt::fail(AGPT_ERR_INVALID, f + "NULL weights, vertices, position_deltas or vertices_out");
+    if (n_vertices < 0 || n_normals < 0 || (n_normals > 0 && (!normals || !normals_out)))
+        return agpt::fail(AGPT_ERR_INVALID, f + "a negative count, or n_normals > 0 with NULL normals or normals_out");
+    std::string bad = agpt::morph_check_count(n_targets);
+    if (bad.empty()) bad = agpt::morph_check_weights(weights, n_targets);
+    if (bad.empty()) bad = agpt::morph_check_deltas("position", "vertex", n_targets, (size_t)n_vertices, position_deltas);
+    if (bad.empty() && normal_deltas) bad = agpt::morph_check_deltas("normal", "normal", n_targets, (size_t)n_normals, normal_deltas);
+    if (!bad.empty()) return agpt::fail(AGPT_ERR_INVALID, f + bad);
+    const std::vector<agpt::MorphActive> active = agpt::morph_active_list(weights, n_targets);
+    for (size_t i = 0; i < (size_t)n_vertices; i++) {   // (through a temporary: vertices_out may be vertices)
+        float p[3];
+        agpt::morph_blend(active.data(), (int)active.size(), position_deltas, (size_t)n_vertices, i, vertices + 3 * i, p);
+        std::memcpy(vertices_out + 3 * i, p, sizeof(p));
+    }
+    if (n_normals > 0 && !normal_deltas) std::memmove(normals_out, normals, (size_t)n_normals * 3 * sizeof(float));   // the rest normals
+    for (size_t i = 0; normal_deltas && i < (size_t)n_normals; i++) {
+        float p[3];
+        agpt::morph_blend(active.data(), (int)active.size(), normal_deltas, (size_t)n_normals, i, normals + 3 * i, p);
         std::memcpy(normals_out + 3 * i, p, sizeof(p));
     }
     return AGPT_OK;

@@ -679,6 +679,19 @@ int agpt_scene_update_mesh_device(agpt_scene* s, int prim, const float* vertices
     return update_from_updater(s, prim, mi, mode);
 }
 
+// the rest pose of the transform, the pose and the morph: the arrays the mesh last received explicitly -- the mirror, brought up to date
+// if they came as device pointers
+static int take_rest(agpt_scene* s, size_t mi) {
+    agpt_scene::MeshUpdate& up = s->updates[mi];
+    if (up.rest_valid) return AGPT_OK;
+    if (const int rc = sync_mirror(s, true)) return rc;
+    up.rest_vertices = s->meshes[mi].vertices;
+    up.rest_normals = s->meshes[mi].normals;
+    up.rest_valid = true;
+    agpt::drop_rest(up.updater);
+    return AGPT_OK;
+}
+
 int agpt_scene_transform_mesh(agpt_scene* s, int prim, const float* transform16, int mode) {
     {   // the checks of agpt_scene_update_mesh with the mesh's own counts, then the matrix
         const agpt::HostMesh* m = s && s->committed ? mesh_of(s, prim) : nullptr;
@@ -698,13 +711,7 @@ int agpt_scene_transform_mesh(agpt_scene* s, int prim, const float* transform16,
     const size_t mi = (size_t)s->prims[prim].index;
     HIP_TRY(hipSetDevice(s->ctx->device));
     agpt_scene::MeshUpdate& up = s->updates[mi];
-    if (!up.rest_valid) {   // the arrays the mesh last received explicitly: the mirror, brought up to date if they came as device pointers
-        if (const int rc = sync_mirror(s, true)) return rc;
-        up.rest_vertices = s->meshes[mi].vertices;
-        up.rest_normals = s->meshes[mi].normals;
-        up.rest_valid = true;
-        agpt::drop_rest(up.updater);
-    }
+    if (const int rc = take_rest(s, mi)) return rc;
     if (const int rc = agpt::transform_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, M, N)) return rc;
     return update_from_updater(s, prim, mi, mode);
 }
@@ -744,6 +751,24 @@ int agpt_scene_set_mesh_skin(agpt_scene* s, int prim, int influences, int n_join
     return AGPT_OK;
 }
 
+// the checks of a frame's joint matrices that agpt_scene_pose_mesh and agpt_scene_morph_mesh share, in their order, then the palette
+// (`f` is the call's name and ": ")
+static int pose_palette(const std::string& f, int prim, const agpt::SkinBinding& skin, bool with_normals, const float* joints16, int n_joints,
+                        std::vector<float>& palette) {
+    if (skin.influences == 0) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no skin (agpt_scene_set_mesh_skin)");
+    if (!joints16) return fail(AGPT_ERR_INVALID, f + "NULL joints16");
+    if (n_joints != skin.n_joints)
+        return fail(AGPT_ERR_INVALID, f + "n_joints is " + std::to_string(n_joints) + ", the skin was set with " + std::to_string(skin.n_joints));
+    for (size_t i = 0; i < 16 * (size_t)n_joints; i++)
+        if (!std::isfinite(joints16[i])) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(i / 16) + " has a non-finite entry");
+    const std::string bad = agpt::skin_check_last_rows(joints16, n_joints);
+    if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
+    int singular = -1;
+    palette = agpt::skin_pack_palette(joints16, n_joints, with_normals, &singular);
+    if (singular >= 0) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(singular) + " is singular (its determinant is exactly 0)");
+    return AGPT_OK;
+}
+
 int agpt_scene_pose_mesh(agpt_scene* s, int prim, const float* joints16, int n_joints, int mode) {
     const std::string f = "agpt_scene_pose_mesh: ";
     {   // the checks of agpt_scene_update_mesh with the mesh's own counts
@@ -755,29 +780,69 @@ int agpt_scene_pose_mesh(agpt_scene* s, int prim, const float* joints16, int n_j
     }
     const size_t mi = (size_t)s->prims[prim].index;
     agpt_scene::MeshUpdate& up = s->updates[mi];
-    if (up.skin.influences == 0) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no skin (agpt_scene_set_mesh_skin)");
-    if (!joints16) return fail(AGPT_ERR_INVALID, f + "NULL joints16");
-    if (n_joints != up.skin.n_joints)
-        return fail(AGPT_ERR_INVALID, f + "n_joints is " + std::to_string(n_joints) + ", the skin was set with " + std::to_string(up.skin.n_joints));
-    for (size_t i = 0; i < 16 * (size_t)n_joints; i++)
-        if (!std::isfinite(joints16[i])) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(i / 16) + " has a non-finite entry");
-    const std::string bad = agpt::skin_check_last_rows(joints16, n_joints);
-    if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
-    int singular = -1;
-    const std::vector<float> palette = agpt::skin_pack_palette(joints16, n_joints, !s->meshes[mi].normals.empty(), &singular);
-    if (singular >= 0) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(singular) + " is singular (its determinant is exactly 0)");
+    std::vector<float> palette;
+    if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty(), joints16, n_joints, palette)) return rc;
     HIP_TRY(hipSetDevice(s->ctx->device));
-    if (!up.rest_valid) {   // as for agpt_scene_transform_mesh: the two share the rest pose
-        if (const int rc = sync_mirror(s, true)) return rc;
-        up.rest_vertices = s->meshes[mi].vertices;
-        up.rest_normals = s->meshes[mi].normals;
-        up.rest_valid = true;
-        agpt::drop_rest(up.updater);
-    }
+    if (const int rc = take_rest(s, mi)) return rc;   // as for agpt_scene_transform_mesh: the two share the rest pose
     if (const int rc = agpt::skin_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, up.skin, palette,
                                                 s->ctx->num_cus))
         return rc;
     return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `palette` lives until then)
+}
+
+int agpt_scene_set_mesh_morph_targets(agpt_scene* s, int prim, int n_targets, const float* position_deltas, const float* normal_deltas) {
+    const std::string f = "agpt_scene_set_mesh_morph_targets: ";
+    if (!s) return fail(AGPT_ERR_INVALID, f + "NULL scene");
+    const agpt::HostMesh* m = mesh_of(s, prim);
+    if (!m) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " is not a mesh of this scene");
+    agpt_scene::MeshUpdate& up = s->updates[(size_t)s->prims[prim].index];
+    agpt::MorphTargets morph;
+    if (n_targets != 0) {   // the twin's rules, with the mesh's own counts
+        const size_t nv = m->vertices.size(), nn = m->normals.size(), T = (size_t)n_targets;
+        std::string bad = agpt::morph_check_count(n_targets);
+        if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
+        if (!position_deltas) return fail(AGPT_ERR_INVALID, f + "NULL position_deltas");
+        bad = agpt::morph_check_deltas("position", "vertex", n_targets, nv, position_deltas);
+        if (bad.empty() && normal_deltas) bad = agpt::morph_check_deltas("normal", "normal", n_targets, nn, normal_deltas);
+        if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
+        morph.n_targets = n_targets;
+        morph.position_deltas.assign(position_deltas, position_deltas + T * nv * 3);
+        if (normal_deltas) morph.normal_deltas.assign(normal_deltas, normal_deltas + T * nn * 3);   // (nothing for a mesh without normals)
+    }
+    if (up.updater) HIP_TRY(hipSetDevice(s->ctx->device));
+    agpt::drop_morph(up.updater);   // (nothing goes up here: the next morph uploads the new targets)
+    up.morph = std::move(morph);
+    return AGPT_OK;
+}
+
+int agpt_scene_morph_mesh(agpt_scene* s, int prim, const float* weights, int n_targets, const float* joints16, int n_joints, int mode) {
+    const std::string f = "agpt_scene_morph_mesh: ";
+    {   // the checks of agpt_scene_update_mesh with the mesh's own counts
+        const agpt::HostMesh* m = s && s->committed ? mesh_of(s, prim) : nullptr;
+        const int dummy = 0;
+        if (const int rc = check_update("agpt_scene_morph_mesh", s, prim, &dummy, m ? (int)m->vertices.size() : 0, &dummy,
+                                        m ? (int)m->normals.size() : 0, mode))
+            return rc;
+    }
+    const size_t mi = (size_t)s->prims[prim].index;
+    agpt_scene::MeshUpdate& up = s->updates[mi];
+    if (up.morph.n_targets == 0)
+        return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no morph targets (agpt_scene_set_mesh_morph_targets)");
+    if (!weights) return fail(AGPT_ERR_INVALID, f + "NULL weights");
+    if (n_targets != up.morph.n_targets)
+        return fail(AGPT_ERR_INVALID, f + "n_targets is " + std::to_string(n_targets) + ", the targets were set with " + std::to_string(up.morph.n_targets));
+    const std::string bad = agpt::morph_check_weights(weights, n_targets);
+    if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
+    std::vector<float> palette;
+    if (joints16)   // morph, then skin: agpt_scene_pose_mesh's checks
+        if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty(), joints16, n_joints, palette)) return rc;
+    const std::vector<agpt::MorphActive> active = agpt::morph_active_list(weights, n_targets);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (const int rc = take_rest(s, mi)) return rc;   // the rest pose the transform and the pose use
+    if (const int rc = agpt::morph_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, up.morph, active,
+                                                 joints16 ? &up.skin : nullptr, joints16 ? &palette : nullptr, s->ctx->num_cus))
+        return rc;
+    return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `active` and `palette` live until then)
 }
 
 int agpt_scene_set_bvh_builder(agpt_scene* s, int builder) {

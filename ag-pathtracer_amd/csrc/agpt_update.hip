@@ -16,8 +16,11 @@
 //   k_skin_mesh      one lane per vertex and one per normal: the rest arrays through skin_blend of agpt_skin.h -- up to 8 (joint,
 //                    weight) slots per item, each a gather of the joint's palette entry -- into the arrays k_update_tris reads
 //                    (agpt_scene_pose_mesh).
+//   k_morph_mesh     one lane per vertex and one per normal: the rest arrays plus the ACTIVE morph targets' deltas (morph_blend of
+//                    agpt_morph.h) and, fused (kSkin), straight on through skin_blend (agpt_scene_morph_mesh).
 // All are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair, 24 B per transformed vertex, 24 + 8 K B
-// per skinned vertex); all but k_skin_mesh run 64-lane blocks, 16-byte accesses of the float4 records, no LDS.
+// per skinned vertex, 24 + 12 A B per vertex morphed by A active targets); all but k_skin_mesh and k_morph_mesh run 64-lane blocks,
+// 16-byte accesses of the float4 records, no LDS.
 //
 // k_skin_mesh's palette.  The per-lane gather by joint index is the one access here that is not a stream, and neighbouring vertices
 // mostly name the same few joints.  A palette of up to 40 KiB (487 joints with normals, 787 without) is staged in LDS; a larger one is
@@ -36,6 +39,33 @@
 //            entries are read with 4-byte LDS loads (an odd stride has no 16-byte alignment); the kernel is bound by its global
 //            streams, not by these.
 //   N-less   a mesh without normals stages M only (stride 13): the same kernel, the stride is an argument.
+//
+// k_morph_mesh<kSkin, kLds>.  Per item (a vertex, or a normal of a mesh whose targets carry normal deltas) with A targets ACTIVE -- weight
+// not 0 -- out of the T bound: 12 B of the rest array read, 12 A B of deltas read, 12 B written: 24 + 12 A bytes, independent of T; a
+// normal without normal deltas is copied (24 B).  kSkin adds the skin kernel's 8 K B of slots and its palette gather; the morphed value
+// stays in registers between morph_blend and skin_blend, so fusing saves the 24 B per item of an intermediate array and a launch.
+//   active   the host compacts a frame's weights into the (target, weight) pairs in use, in target order, and uploads only those
+//            (8 B each).  The list is a kernel argument of its own, `const ... __restrict__`: index and weight are the same for
+//            every lane, the compiler reads them with scalar loads (s_load_dwordx2) and the delta base of a target is formed in SGPRs.
+//   deltas   target-major, packed xyz ([t][item][3] floats, positions and normals in buffers of their own): the 64 lanes of a wave
+//            read one contiguous 768-B run per active target, one 12-byte load per lane (global_load_dwordx3) like the rest arrays'.
+//            Padding to float4 records was NOT measured and not adopted: it would move 16 instead of 12 B per item and active
+//            target through a kernel that is bound by exactly those bytes.  Offsets are size_t (T * items * 3 passes 2^31 for a
+//            1 M-vertex mesh with 200 targets).
+//   launch   256-lane blocks on a capped grid with a stride loop.  Fused: k_skin_mesh's shape and LDS cap (4 blocks per CU, a palette
+//            of up to 40 KiB staged, a larger one or AGPT_SKIN_GLOBAL_PALETTE read from global memory).  Morph only: no LDS, 8 blocks
+//            per CU (every wave slot of the CU; against 4 it measured 0.301 against 0.305 ms at 16 active).
+//            AGPT_MORPH_MAX_BLOCKS in the environment, read at every call, lowers the cap of either: same bytes, it exists so that a
+//            test can drive the stride loop on a small mesh.
+//   loop     the walk over the active list is left rolled: one scalar load of (target, weight) and one 12-byte delta load per lane and
+//            iteration.  Unrolled by four (four delta loads in flight) it was no faster on the 1 M-triangle heightfield and 3 % slower
+//            at 64 active targets (0.419 against 0.408 ms per call, three alternating rounds): the CU's other waves already cover
+//            the latency.
+//   code     from the gfx950 code object of this unit (VGPRs / SGPRs / spilled / scratch bytes):
+//              k_morph_mesh<false, false>  33 / 46 / 0 / 0        (morph only)
+//              k_morph_mesh<true, false>   50 / 53 / 0 / 0        (fused, palette in global memory)
+//              k_morph_mesh<true, true>    52 / 55 / 0 / 0        (fused, palette in LDS)
+//            kLds has no meaning without kSkin: <false, true> is not instantiated, so there are three, not four.
 #include "agpt_update.h"
 
 #include <cstdlib>
@@ -239,6 +269,53 @@ __global__ __launch_bounds__(kSkinBlock) void k_skin_mesh(SkinArgs a) {
     }
 }
 
+struct MorphArgs {
+    const float* position_deltas;   // [t][vertex][3]
+    const float* normal_deltas;     // [t][normal][3]; NULL: the normals keep their rest values
+    SkinArgs s;                     // rest arrays, outputs and counts; with kSkin the binding and the palette as well
+};
+
+constexpr int kMorphBlocksPerCU = 8;   // morph only (no LDS): 8 x 256 lanes are the 32 wave slots of a CU
+
+// `active` is an argument of its own so that it can be `__restrict__`: uniform, never written here -> scalar loads
+template <bool kSkin, bool kLds>
+__global__ __launch_bounds__(kSkinBlock) void k_morph_mesh(const MorphActive* __restrict__ active, int n_active, MorphArgs m) {
+    extern __shared__ __attribute__((aligned(16))) float skin_lds[];
+    const SkinArgs& a = m.s;
+    if (kSkin && kLds) {
+        const int n = a.n_joints * a.stride;
+        for (int i = threadIdx.x; i < n; i += kSkinBlock) skin_lds[i] = a.palette[i];
+        __syncthreads();
+    }
+    const size_t nv = (size_t)a.n_vertices, nn = (size_t)a.n_normals, total = nv + nn, K = (size_t)a.influences;
+    for (size_t i = (size_t)blockIdx.x * kSkinBlock + threadIdx.x; i < total; i += (size_t)gridDim.x * kSkinBlock) {
+        const bool point = i < nv;
+        const size_t j = point ? i : i - nv;
+        const float* rest = (point ? a.rest_verts : a.rest_normals) + 3 * j;
+        const float* deltas = point ? m.position_deltas : m.normal_deltas;
+        const float r[3] = {rest[0], rest[1], rest[2]};
+        float morphed[3] = {r[0], r[1], r[2]}, out[3];
+        if (deltas) morph_blend(active, n_active, deltas, point ? nv : nn, j, r, morphed);
+        if (kSkin) {
+            const int32_t* joints = (point ? a.vertex_joints : a.normal_joints) + K * j;
+            const float* weights = (point ? a.vertex_weights : a.normal_weights) + K * j;
+            const float* palette = kLds ? skin_lds : a.palette;
+            if (point)
+                skin_blend<true>(palette, a.stride, joints, weights, a.influences, morphed, out);
+            else
+                skin_blend<false>(palette, a.stride, joints, weights, a.influences, morphed, out);
+        } else {
+            out[0] = morphed[0];
+            out[1] = morphed[1];
+            out[2] = morphed[2];
+        }
+        float* dst = (point ? a.verts : a.normals) + 3 * j;
+        dst[0] = out[0];
+        dst[1] = out[1];
+        dst[2] = out[2];
+    }
+}
+
 template <class T>
 struct Buf {
     T* p = nullptr;
@@ -276,6 +353,10 @@ struct MeshUpdater {
     Buf<int32_t> skin_vertex_joints, skin_normal_joints;
     Buf<float> skin_vertex_weights, skin_normal_weights, skin_palette;
     bool has_skin = false;
+    // agpt_scene_morph_mesh: the targets' deltas (uploaded by the first morph after they were set) and the active list of the last morph
+    Buf<float> morph_position_deltas, morph_normal_deltas;
+    Buf<MorphActive> morph_active;
+    bool has_morph = false;
     Buf<uint32_t> flag;        // k_check_finite's word
     Buf<v2> uv;
     Buf<int32_t> indices, prim_index, lists;
@@ -456,10 +537,10 @@ int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostM
     return AGPT_OK;
 }
 
-int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus) {
-    if (const int rc = ensure_rest("agpt_scene_pose_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
-    MeshUpdater& u = **cache;
+// the binding on the device (uploaded when the cache holds none), this call's palette, and k_skin_mesh's arguments: what the pose and the
+// fused morph share (`fn` names the call in the message)
+static int skin_on_device(const char* fn, hipStream_t stream, MeshUpdater& u, const HostMesh& mesh, const SkinBinding& skin,
+                          const std::vector<float>& palette, SkinArgs& a) {
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), K = (size_t)skin.influences;
     const int stride = skin_palette_stride(nn != 0);
     const bool own_normal_slots = nn && !skin.normal_joints.empty();
@@ -467,7 +548,7 @@ int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& 
     if (K < 1 || K > (size_t)kSkinMaxInfluences || skin.vertex_joints.size() != nv * K || skin.vertex_weights.size() != nv * K ||
         (own_normal_slots ? skin.normal_joints.size() != nn * K || skin.normal_weights.size() != nn * K : nn && nn != nv) ||
         palette.size() != (size_t)skin.n_joints * (size_t)stride)
-        return fail(AGPT_ERR_INVALID, "agpt_scene_pose_mesh: the binding does not have the mesh's counts");
+        return fail(AGPT_ERR_INVALID, std::string(fn) + ": the binding does not have the mesh's counts");
     if (!u.has_skin) {
         UPD_TRY(u.skin_vertex_joints.upload(skin.vertex_joints.data(), nv * K, stream));
         UPD_TRY(u.skin_vertex_weights.upload(skin.vertex_weights.data(), nv * K, stream));
@@ -479,27 +560,91 @@ int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& 
         u.has_skin = true;
     }
     UPD_TRY(u.skin_palette.upload(palette.data(), palette.size(), stream));   // (the caller keeps `palette` until the stream is synchronised)
-    SkinArgs a;
     a.palette = u.skin_palette.p;
     a.stride = stride;
     a.n_joints = skin.n_joints;
     a.influences = skin.influences;
-    a.rest_verts = u.rest_verts.p;
-    a.rest_normals = nn ? u.rest_normals.p : nullptr;
     a.vertex_joints = u.skin_vertex_joints.p;
     a.vertex_weights = u.skin_vertex_weights.p;
     a.normal_joints = own_normal_slots ? u.skin_normal_joints.p : u.skin_vertex_joints.p;
     a.normal_weights = own_normal_slots ? u.skin_normal_weights.p : u.skin_vertex_weights.p;
+    return AGPT_OK;
+}
+
+// the arrays of the rest pose and of the result (ensure_rest has made them)
+static void rest_args(const MeshUpdater& u, const HostMesh& mesh, SkinArgs& a) {
+    const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
+    a.rest_verts = u.rest_verts.p;
+    a.rest_normals = nn ? u.rest_normals.p : nullptr;
     a.verts = u.verts.p;
     a.normals = nn ? u.normals.p : nullptr;
     a.n_vertices = (int)nv;
     a.n_normals = (int)nn;
-    const size_t lds = palette.size() * sizeof(float), blocks = (nv + nn + kSkinBlock - 1) / kSkinBlock;
+}
+
+int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
+                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus) {
+    if (const int rc = ensure_rest("agpt_scene_pose_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
+    MeshUpdater& u = **cache;
+    SkinArgs a;
+    if (const int rc = skin_on_device("agpt_scene_pose_mesh", stream, u, mesh, skin, palette, a)) return rc;
+    rest_args(u, mesh, a);
+    const size_t lds = palette.size() * sizeof(float), blocks = (mesh.vertices.size() + mesh.normals.size() + kSkinBlock - 1) / kSkinBlock;
     const size_t cus = (size_t)(num_cus > 0 ? num_cus : 1);
     if (lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE")) {
         hipLaunchKernelGGL(k_skin_mesh<true>, dim3((unsigned)std::min(blocks, cus * kSkinBlocksPerCU)), dim3(kSkinBlock), lds, stream, a);
     } else {
         hipLaunchKernelGGL(k_skin_mesh<false>, dim3((unsigned)std::min(blocks, cus * kSkinBlocksPerCU)), dim3(kSkinBlock), 0, stream, a);
+    }
+    UPD_TRY(hipGetLastError());
+    return AGPT_OK;
+}
+
+int morph_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
+                        const std::vector<v3>& rest_normals, const MorphTargets& morph, const std::vector<MorphActive>& active,
+                        const SkinBinding* skin, const std::vector<float>* palette, int num_cus) {
+    const char* fn = "agpt_scene_morph_mesh";
+    if (const int rc = ensure_rest(fn, stream, cache, mesh, rest_vertices, rest_normals)) return rc;
+    MeshUpdater& u = **cache;
+    const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), T = (size_t)morph.n_targets;
+    const bool normal_deltas = nn && !morph.normal_deltas.empty();
+    // what the kernel indexes with, against what it indexes
+    if (T < 1 || T > (size_t)kMorphMaxTargets || morph.position_deltas.size() != T * nv * 3 ||
+        (normal_deltas && morph.normal_deltas.size() != T * nn * 3) || active.size() > T || !skin != !palette)
+        return fail(AGPT_ERR_INVALID, std::string(fn) + ": the targets do not have the mesh's counts");
+    for (const MorphActive& t : active)
+        if (t.target < 0 || (size_t)t.target >= T) return fail(AGPT_ERR_INVALID, std::string(fn) + ": an active target outside the targets");
+    if (!u.has_morph) {
+        UPD_TRY(u.morph_position_deltas.upload(morph.position_deltas.data(), T * nv * 3, stream));
+        if (normal_deltas) UPD_TRY(u.morph_normal_deltas.upload(morph.normal_deltas.data(), T * nn * 3, stream));
+        UPD_TRY(hipStreamSynchronize(stream));   // (the targets may be replaced behind this call)
+        u.has_morph = true;
+    }
+    UPD_TRY(u.morph_active.reserve(T));   // (room for every target: the list of a later frame may be longer)
+    if (!active.empty())   // (the caller keeps `active` until the stream is synchronised)
+        UPD_TRY(hipMemcpyAsync(u.morph_active.p, active.data(), active.size() * sizeof(MorphActive), hipMemcpyHostToDevice, stream));
+    MorphArgs m;
+    m.position_deltas = u.morph_position_deltas.p;
+    m.normal_deltas = normal_deltas ? u.morph_normal_deltas.p : nullptr;
+    m.s = SkinArgs();
+    if (skin)
+        if (const int rc = skin_on_device(fn, stream, u, mesh, *skin, *palette, m.s)) return rc;
+    rest_args(u, mesh, m.s);
+    const size_t cus = (size_t)(num_cus > 0 ? num_cus : 1);
+    size_t blocks = std::min((nv + nn + kSkinBlock - 1) / kSkinBlock, cus * (skin ? kSkinBlocksPerCU : kMorphBlocksPerCU));
+    if (const char* cap = getenv("AGPT_MORPH_MAX_BLOCKS")) {
+        const long c = std::strtol(cap, nullptr, 10);
+        if (c >= 1) blocks = std::min(blocks, (size_t)c);
+    }
+    const dim3 grid((unsigned)std::max(blocks, (size_t)1)), block(kSkinBlock);
+    const int n_active = (int)active.size();
+    const size_t lds = skin ? palette->size() * sizeof(float) : 0;
+    if (!skin) {
+        hipLaunchKernelGGL((k_morph_mesh<false, false>), grid, block, 0, stream, u.morph_active.p, n_active, m);
+    } else if (lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE")) {
+        hipLaunchKernelGGL((k_morph_mesh<true, true>), grid, block, lds, stream, u.morph_active.p, n_active, m);
+    } else {
+        hipLaunchKernelGGL((k_morph_mesh<true, false>), grid, block, 0, stream, u.morph_active.p, n_active, m);
     }
     UPD_TRY(hipGetLastError());
     return AGPT_OK;
@@ -513,6 +658,14 @@ void drop_skin(MeshUpdater* cache) {
     cache->skin_normal_weights.release();
     cache->skin_palette.release();
     cache->has_skin = false;
+}
+
+void drop_morph(MeshUpdater* cache) {
+    if (!cache) return;
+    cache->morph_position_deltas.release();
+    cache->morph_normal_deltas.release();
+    cache->morph_active.release();
+    cache->has_morph = false;
 }
 
 int refit_device_arrays(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh, const UpdateTarget& tg, float root6[6], bool* finite) {

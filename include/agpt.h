@@ -384,9 +384,59 @@ int agpt_scene_set_mesh_skin(agpt_scene*, int prim, int influences, int n_joints
  * scene; not committed; not a mesh; unknown mode); a mesh without a skin; NULL joints16; an n_joints that is not the binding's; a
  * non-finite entry; a last row that is not exactly (0, 0, 0, 1); a joint whose determinant (agpt_transform_arrays' value) is exactly
  * 0, named in the message.  A refused call changes nothing.
- * Out of scope: morph targets, dual-quaternion blending, joint matrices given in device memory, renormalised normals, motion
- * vectors (and what agpt_scene_update_mesh_device does not cover). */
+ * Out of scope: sparse morph targets, tangent deltas, weights or joint matrices given in device memory, dual-quaternion blending,
+ * renormalised normals, motion vectors (and what agpt_scene_update_mesh_device does not cover).  Morph targets: agpt_scene_morph_mesh. */
 int agpt_scene_pose_mesh(agpt_scene*, int prim, const float* joints16, int n_joints, int mode);
+/* Morph targets (blend shapes) applied to a mesh's arrays, host-only like agpt_skin_arrays (no GPU, no context): fp32, every operation
+ * rounded on its own, nothing contracted into an fma.
+ *   inputs     n_targets = T (1 .. 4096) targets and T weights.  Target t has one position delta per vertex and, optionally, one normal
+ *              delta per NORMAL (a mesh may have other counts of normals than vertices): position_deltas is T * n_vertices * 3 floats,
+ *              normal_deltas T * n_normals * 3 or NULL, both target-major ([t][item][xyz]).  n_normals may be 0.
+ *   position   acc = the vertex; the targets in order t = 0 .. T-1; a target whose weight is exactly 0 (either sign) is skipped; every
+ *              other one adds acc = acc + w[t] * delta[t][i] per component, the product rounded, then the sum.  Weights are used as
+ *              given: any finite value, negative and above 1 included, neither normalised nor reordered.
+ *   normal     the same walk with the normal deltas; with normal_deltas == NULL the normals are copied through.  Not renormalised.
+ * All weights zero gives the input arrays bit for bit.  The skip is by weight, not by delta: a target of weight 1 with an all-zero
+ * delta turns a coordinate of -0.0 into +0.0.
+ * An output may be its own input.  AGPT_ERR_INVALID (+ agpt_last_error) for a NULL argument or a bad count, n_targets outside
+ * 1 .. 4096, a weight that is not finite, a delta that is not finite (the message names target and item); a refused call writes
+ * nothing. */
+int agpt_morph_arrays(const float* weights, int n_targets,
+                      const float* vertices, int n_vertices, const float* position_deltas,
+                      const float* normals, int n_normals, const float* normal_deltas,
+                      float* vertices_out, float* normals_out);
+/* The morph targets of mesh primitive `prim` for agpt_scene_morph_mesh: deltas as in agpt_morph_arrays, with the mesh's own counts
+ * (normal_deltas NULL: the targets leave the normals alone; ignored for a mesh without normals), and the number of weights every later
+ * morph must bring.  May be called any time after agpt_scene_add_mesh, on a committed scene or not.  The scene keeps a host copy and
+ * uploads nothing; the first morph takes the deltas to the GPU, where they stay.  Setting them again replaces the targets (the device
+ * copies are dropped); n_targets == 0 removes them (the other arguments are then ignored).  agpt_scene_update_mesh / _device keep the
+ * targets: the counts cannot change, and the new arrays become the rest pose.  A REBUILD -- by any update call of this mesh --
+ * destroys the mesh's device cache, so the next morph uploads the deltas again: for a large target set that re-upload
+ * (n_targets * (n_vertices + n_normals) * 12 bytes) is the cost of REBUILD.
+ * AGPT_ERR_INVALID (+ agpt_last_error) for a NULL scene, a prim that is not a mesh of the scene, n_targets outside 0 .. 4096, NULL
+ * position_deltas, a delta that is not finite; a refused call changes nothing. */
+int agpt_scene_set_mesh_morph_targets(agpt_scene*, int prim, int n_targets, const float* position_deltas, const float* normal_deltas);
+/* Mesh primitive `prim` of a COMMITTED scene morphed by its targets and, with joints16 != NULL, then posed by its skin (glTF's order),
+ * on the GPU: afterwards the scene is byte for byte what agpt_scene_update_mesh(scene, prim, V, n_vertices, N, n_normals, mode) leaves,
+ * with (V, N) = agpt_morph_arrays(weights, the mesh's rest pose, the targets) when joints16 is NULL (n_joints is then ignored), and
+ * agpt_skin_arrays(joints16, the binding, that (V, N)) otherwise -- so a vertex without a used slot keeps its MORPHED position.  The
+ * rest pose is the one of agpt_scene_transform_mesh and agpt_scene_pose_mesh: the call is absolute, not cumulative; the three may
+ * alternate, and the last one wins.  One lane per vertex and per normal runs the twins' arithmetic (one source for host and device);
+ * the morphed value goes to the skin in registers: one kernel, no intermediate array.  Per call only the ACTIVE targets go up -- 8 bytes
+ * (index, weight) for every weight that is not 0 -- and, with a skin, agpt_scene_pose_mesh's palette; the kernel walks the active list, so
+ * a frame costs by the targets in use, not by the targets bound.  Under REFIT the finiteness flag and the root box come down (a
+ * non-finite morphed position takes the host path, as for the other update calls); REBUILD downloads the arrays and rebuilds, and the
+ * deltas (and the binding) go up again with the next morph.  The palette is staged as for agpt_scene_pose_mesh
+ * (AGPT_SKIN_GLOBAL_PALETTE applies).  AGPT_MORPH_MAX_BLOCKS in the environment (a positive integer, read at every call) lowers the
+ * number of blocks the kernel is launched with; same bytes whatever its value -- it exists so that a test can drive the kernel's stride
+ * loop on a small mesh.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order: the conditions of agpt_scene_update_mesh that apply (NULL
+ * scene; not committed; not a mesh; unknown mode); a mesh without morph targets; NULL weights; an n_targets that is not the one the
+ * targets were set with; a weight that is not finite; then, with joints16, agpt_scene_pose_mesh's remaining checks in its order (a mesh
+ * without a skin; n_joints; a non-finite entry; a last row; a singular joint).  A refused call changes nothing.
+ * Out of scope: sparse targets (a delta for every item of every target is stored), tangent deltas, weights or joint matrices given in
+ * device memory, renormalised normals, motion vectors (and what agpt_scene_update_mesh_device does not cover). */
+int agpt_scene_morph_mesh(agpt_scene*, int prim, const float* weights, int n_targets, const float* joints16, int n_joints, int mode);
 /* Which builder agpt_scene_add_mesh uses for the BVH of later meshes on this scene (default HOST).  Both produce the same
  * bytes; DEVICE runs agpt_bvh_build_device on the scene's context. */
 enum { AGPT_BVH_BUILDER_HOST = 0, AGPT_BVH_BUILDER_DEVICE = 1 };

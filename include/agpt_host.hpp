@@ -258,6 +258,19 @@ public:
     void PoseMesh(int prim, const std::vector<float>& joints16, MeshUpdate mode = MeshUpdate::Refit) {
         check(agpt_scene_pose_mesh(h_, prim, joints16.data(), (int)(joints16.size() / 16), (int)mode), "agpt_scene_pose_mesh");
     }
+    // morph targets (blend shapes): SetMeshMorphTargets gives the deltas once (agpt_scene_set_mesh_morph_targets) -- target-major,
+    // n_targets * n_vertices * 3 floats, and the normals' n_targets * n_normals * 3 or none --, MorphMesh the weights of a frame and,
+    // for a skinned mesh, its joints (agpt_scene_morph_mesh): morph, then skin, in one kernel from the rest pose TransformMesh and
+    // PoseMesh use: absolute, not cumulative.  `scene.MorphMesh(prim, weights, joints); accumulator.Clear();`
+    void SetMeshMorphTargets(int prim, int n_targets, const std::vector<float>& position_deltas, const std::vector<float>& normal_deltas = {}) {
+        check(agpt_scene_set_mesh_morph_targets(h_, prim, n_targets, position_deltas.data(), normal_deltas.empty() ? nullptr : normal_deltas.data()),
+              "agpt_scene_set_mesh_morph_targets");
+    }
+    void MorphMesh(int prim, const std::vector<float>& weights, const std::vector<float>& joints16 = {}, MeshUpdate mode = MeshUpdate::Refit) {
+        check(agpt_scene_morph_mesh(h_, prim, weights.data(), (int)weights.size(), joints16.empty() ? nullptr : joints16.data(),
+                                    (int)(joints16.size() / 16), (int)mode),
+              "agpt_scene_morph_mesh");
+    }
     // camera moved (RotatingCamera::update): re-derive the camera only, geometry stays in HBM
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }
     void Intersect(const agpt_ray* rays, int n, agpt_hit* hits) const {

@@ -5,10 +5,15 @@ one warm-up, and the bytes that cross PCIe per call (up / down, from the sizes; 
 
     python tools/mesh_update_time.py [--runs 9] [--out profiles/mesh_update_times.json] [--parent-lib TAG] [--rounds 3]
     python tools/mesh_update_time.py --pose [--runs 9] [--out profiles/mesh_pose_times.json]
+    python tools/mesh_update_time.py --morph [--runs 9] [--out profiles/mesh_morph_times.json]
 
 --pose times agpt_scene_pose_mesh instead (REFIT, 4 influences per vertex, 64 and 1,024 joints, the palette staged in LDS and read
 from global memory -- AGPT_SKIN_GLOBAL_PALETTE), with, in the same process on the same GPU, agpt_scene_transform_mesh and the route a
 host has without it: agpt_skin_arrays on the CPU, then agpt_scene_update_mesh with its output.
+
+--morph times agpt_scene_morph_mesh (REFIT, 64 targets bound with normal deltas, 0 / 4 / 16 / 64 of them active; 16 active fused with a
+64-joint skin of 4 influences) with, in the same process on the same GPU, agpt_scene_transform_mesh, agpt_scene_pose_mesh with the same
+skin, and the route a host has without it: agpt_morph_arrays on the CPU, then agpt_scene_update_mesh with its output.
 
 --parent-lib TAG compares the host-pointer REFIT of this build with the build `libagpt_hip_TAG.so` of the parent commit
 (tools/build_variant.py run in a checkout of it, the file copied beside libagpt_hip.so): child processes, alternating parent / this
@@ -156,6 +161,113 @@ def pose_leg(runs):
     return result
 
 
+MORPH_TARGETS = 64
+MORPH_ACTIVE = (0, 4, 16, 64)
+MORPH_FUSED_ACTIVE = 16
+MORPH_JOINTS = 64
+MORPH_ROUNDS = 3
+
+
+def morph_deltas(v, count, seed):
+    """MORPH_TARGETS x count x 3 deltas of a few thousandths of the mesh's extent (the mesh stays where the camera and the tree expect it)"""
+    scale = F(0.004 * float((v.max(0) - v.min(0)).max()))
+    return (np.random.default_rng(seed).random((MORPH_TARGETS, count, 3), dtype=F) - F(0.5)) * scale
+
+
+def morph_weights(active, k):
+    """run k: `active` targets spread over the bound ones, every run with other values"""
+    w = np.zeros(MORPH_TARGETS, F)
+    if active:
+        t = (np.arange(active) * MORPH_TARGETS) // active
+        w[t] = 0.1 * (1 + (k + t) % 5)
+    return w
+
+
+def median_of_rounds(rs, runs):
+    return {"median_ms": round(statistics.median(r["median_ms"] for r in rs), 4), "min_ms": min(r["min_ms"] for r in rs),
+            "max_ms": max(r["max_ms"] for r in rs), "runs": runs, "rounds": [r["median_ms"] for r in rs]}
+
+
+def morph_leg(runs):
+    import torch
+    num_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    result = {"runs": runs, "targets_bound": MORPH_TARGETS, "influences": POSE_INFLUENCES, "joints": MORPH_JOINTS, "compute_units": num_cus,
+              "statistic": "host clock around the synchronised call, ms: median and min-max of the runs after one warm-up (the warm-up "
+                           "uploads the rest pose, the deltas and the binding); all rows of a case from one process on one GPU; every "
+                           "row is %d rounds that take the operations in turn: the median of the rounds' medians, the lowest min, the "
+                           "highest max.  kernel_bytes: what k_morph_mesh moves by its header, (vertices + normals) * (24 + 12 * active); "
+                           "call_gb_per_s: those bytes over the median of the whole call (kernel, refit, flag and root box); "
+                           "marginal_gb_per_s: the bytes and the time a row adds to the 0-active row" % MORPH_ROUNDS,
+              "cases": {}}
+    ctx = ag.Context(0)
+    for name, desc, prim in cases():
+        v, n, tris = arrays_of(desc, prim)
+        nv, nn = len(v), 0 if n is None else len(n)
+        g = desc.instantiate(ag.Scene(ctx))
+        dP = morph_deltas(v, nv, 1)
+        dN = morph_deltas(v, nn, 2) if nn else None
+        g.set_mesh_morph_targets(prim, dP, dN)
+        J, W = pose_binding(v, nv, MORPH_JOINTS)
+        nJ, nW = pose_binding(v, nn, MORPH_JOINTS) if nn and nn != nv else (None, None)
+        g.set_mesh_skin(prim, J, W, nJ, nW, n_joints=MORPH_JOINTS)
+        mats = [spin(v, k) for k in range(runs + 1)]
+        palettes = [pose_palette(v, MORPH_JOINTS, k) for k in range(runs + 1)]
+        ws = {a: [morph_weights(a, k) for k in range(runs + 1)] for a in MORPH_ACTIVE}
+        ops = {"refit_transform": lambda k: g.transform_mesh(prim, mats[k]),
+               "refit_pose_%d_joints" % MORPH_JOINTS: lambda k: g.pose_mesh(prim, palettes[k])}
+        for active in MORPH_ACTIVE:
+            ops["refit_morph_%d_active" % active] = lambda k, a=active: g.morph_mesh(prim, ws[a][k])
+        ops["refit_morph_%d_active_fused_%d_joints" % (MORPH_FUSED_ACTIVE, MORPH_JOINTS)] = \
+            lambda k: g.morph_mesh(prim, ws[MORPH_FUSED_ACTIVE][k], palettes[k])
+        # the launch shape of the morph-only kernel: its 8 blocks per CU against the skin kernel's 4 (AGPT_MORPH_MAX_BLOCKS lowers the cap)
+        capped = "refit_morph_%d_active_4_blocks_per_cu" % MORPH_FUSED_ACTIVE
+        ops[capped] = lambda k: g.morph_mesh(prim, ws[MORPH_FUSED_ACTIVE][k])
+        per_op = {k: [] for k in ops}
+        for _ in range(MORPH_ROUNDS):       # the operations in turn, so that none has the GPU in a better hour
+            for op, fn in ops.items():
+                if op == capped:
+                    os.environ["AGPT_MORPH_MAX_BLOCKS"] = str(4 * num_cus)
+                try:
+                    per_op[op].append(timed(fn, runs))
+                finally:
+                    os.environ.pop("AGPT_MORPH_MAX_BLOCKS", None)
+        rows = {op: median_of_rounds(rs, runs) for op, rs in per_op.items()}
+        rows["refit_transform"].update(pcie_up=128, pcie_down=36)
+        palette_bytes = 4 * MORPH_JOINTS * (21 if nn else 12)
+        rows["refit_pose_%d_joints" % MORPH_JOINTS].update(pcie_up=palette_bytes, pcie_down=36)
+        floor = rows["refit_morph_0_active"]["median_ms"]
+        for op, r in rows.items():
+            if not op.startswith("refit_morph"):
+                continue
+            active = int(op.split("_")[2])
+            fused = "fused" in op
+            r.update(pcie_up=8 * active + (palette_bytes if fused else 0), pcie_down=36)
+            if not fused:
+                r["kernel_bytes"] = (nv + nn) * (24 + 12 * active)
+                r["call_gb_per_s"] = round(r["kernel_bytes"] / (r["median_ms"] * 1e-3) / 1e9, 1)
+                if active and r["median_ms"] > floor:
+                    r["marginal_gb_per_s"] = round((nv + nn) * 12 * active / ((r["median_ms"] - floor) * 1e-3) / 1e9, 1)
+        # the route without the call: the blend on the CPU, then the arrays up
+        t0 = time.perf_counter()
+        blended = [ag.morph_arrays(w, v, dP, n, dN) for w in ws[MORPH_FUSED_ACTIVE][:2]]
+        twin_ms = (time.perf_counter() - t0) * 1e3 / 2
+        rows["host_morph_arrays_%d_active" % MORPH_FUSED_ACTIVE] = {
+            "mean_ms": round(twin_ms, 3), "runs": 2, "what": "agpt_morph_arrays on the CPU, one thread; it also checks every delta of the %d targets for finiteness" % MORPH_TARGETS}
+        rows["refit_host_pointer_%d_active" % MORPH_FUSED_ACTIVE] = dict(
+            timed(lambda k: g.update_mesh(prim, blended[k & 1][0], blended[k & 1][1], "refit"), runs), pcie_up=12 * (nv + nn), pcie_down=32)
+        g.close()
+        result["cases"][name] = {"triangles": tris, "vertices": nv, "normals": nn, "scene_triangles": desc.n_tris,
+                                 "delta_bytes_on_device": 12 * MORPH_TARGETS * (nv + nn), "operations": rows}
+        for k, r in rows.items():
+            if "median_ms" in r:
+                print("%-16s %-44s median %9.3f ms  (%.3f .. %.3f)%s" % (name, k, r["median_ms"], r["min_ms"], r["max_ms"],
+                      "  %s GB/s of the call, %s marginal" % (r["call_gb_per_s"], r.get("marginal_gb_per_s", "-")) if "kernel_bytes" in r else ""), flush=True)
+            else:
+                print("%-16s %-44s mean   %9.3f ms" % (name, k, r["mean_ms"]), flush=True)
+    ctx.close()
+    return result
+
+
 def host_refit_only(runs):
     """the child of --parent-lib: the host-pointer REFIT alone, through whichever library AGPT_LIB_VARIANT names"""
     ctx = ag.Context(0)
@@ -204,15 +316,16 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--parent-lib", default=None, metavar="TAG")
     ap.add_argument("--pose", action="store_true", help="time agpt_scene_pose_mesh (see above) instead of the update paths")
+    ap.add_argument("--morph", action="store_true", help="time agpt_scene_morph_mesh (see above) instead of the update paths")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.runs < 7:
         ap.error("--runs: at least 7")
     if a.child:
         return host_refit_only(a.runs)
-    if a.pose:
-        result = pose_leg(a.runs)
-        with open(a.out or os.path.join(ROOT, "profiles", "mesh_pose_times.json"), "w") as f:
+    if a.pose or a.morph:
+        result = morph_leg(a.runs) if a.morph else pose_leg(a.runs)
+        with open(a.out or os.path.join(ROOT, "profiles", "mesh_morph_times.json" if a.morph else "mesh_pose_times.json"), "w") as f:
             json.dump(result, f, indent=1)
             f.write("\n")
         return

@@ -123,6 +123,35 @@ def render_bend(a, ctx, scene, desc, W, H):
     ctx.free(ptr)
 
 
+def render_morph(a, ctx, scene, desc, W, H):
+    """--morph: the scene's last mesh with two morph targets -- a swelling of its far half along x and a squash towards its middle height
+    (position deltas only: the normals keep their rest values) -- whose weights swing out of phase over N frames, each frame morphed
+    with Scene.morph_mesh (two weights up, the blend and the mesh's records on the GPU) and rendered at --spp into OUT_0000.png ..."""
+    meshes = [(k, op) for k, op in enumerate(o for o in desc.ops if o[0] in ("mesh", "sphere", "plane", "area_light")) if op[0] == "mesh"]
+    prim, op = meshes[-1]
+    v = op[1].astype(np.float64)
+    lo, hi = v.min(0), v.max(0)
+    c = 0.5 * (lo + hi)
+    t = np.clip((v[:, 0] - c[0]) / max(hi[0] - c[0], 1e-30), 0, 1)
+    swell = 0.6 * (t * t * (3 - 2 * t))[:, None] * (v - c) * [0, 1, 1]
+    squash = -0.5 * (v - c) * [0, 1, 0]
+    scene.set_mesh_morph_targets(prim, np.stack([swell, squash]).astype(np.float32))
+    stem, ext = os.path.splitext(a.out)
+    ptr = ctx.alloc(W * H * 16)
+    for k in range(a.morph):
+        w = np.array([0.5 - 0.5 * np.cos(2 * np.pi * k / a.morph), np.sin(2 * np.pi * k / a.morph)], np.float32)
+        t0 = time.time()
+        scene.morph_mesh(prim, w)
+        t1 = time.time()
+        ctx.memset(ptr, 0, W * H * 16)
+        ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
+        path = "%s_%04d%s" % (stem, k, ext)
+        ag.binding.write_png(path, ctx.resolve(ptr, W * H, a.spp), W, H)
+        print("frame %d: primitive %d morphed by weights (%.2f, %.2f) in %.2f ms, %d spp in %.1f ms -> %s" %
+              (k, prim, w[0], w[1], (t1 - t0) * 1e3, a.spp, (time.time() - t1) * 1e3, path))
+    ctx.free(ptr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", default="c3", choices=["c1", "c2", "c3", "c5", "simple", "heightfield", "textured", "mapped"])
@@ -163,9 +192,12 @@ def main():
     ap.add_argument("--bend", type=int, default=0, metavar="N",
                     help="N frames at --spp each with the scene's last mesh (the blob of textured / mapped) bent by two joints through "
                          "agpt_scene_set_mesh_skin / agpt_scene_pose_mesh (OUT_0000.png ...)")
+    ap.add_argument("--morph", type=int, default=0, metavar="N",
+                    help="N frames at --spp each with the scene's last mesh (the blob of textured / mapped) morphed by two targets through "
+                         "agpt_scene_set_mesh_morph_targets / agpt_scene_morph_mesh (OUT_0000.png ...)")
     a = ap.parse_args()
-    if (a.spin or a.bend) and a.frames > 1 or (a.spin and a.bend):
-        ap.error("--spin, --bend and --frames are separate sequences")
+    if (a.spin or a.bend or a.morph) and a.frames > 1 or (a.spin > 0) + (a.bend > 0) + (a.morph > 0) > 1:
+        ap.error("--spin, --bend, --morph and --frames are separate sequences")
     if (a.temporal or a.orbit) and a.frames < 2:
         ap.error("--temporal and --orbit apply to a sequence (--frames N, N >= 2)")
     W, H = a.width, a.height
@@ -202,6 +234,8 @@ def main():
         return render_spin(a, ctx, scene, desc, W, H)
     if a.bend:
         return render_bend(a, ctx, scene, desc, W, H)
+    if a.morph:
+        return render_morph(a, ctx, scene, desc, W, H)
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
     features = None
