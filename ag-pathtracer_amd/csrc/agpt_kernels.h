@@ -589,15 +589,29 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
         // changes.  (A while-while loop makes every lane wait for the longest descent in the wave: 37 % active lanes.)
         for (;;) {
             TCK(const unsigned long long tk_v0 = TCK_NOW();)
-            const int nA = __popcll(__ballot(LIST ? cur - CUR_FETCH < 2u : cur == CUR_PICK)), nB = __popcll(__ballot(cur < CUR_B_END)),
-                      nC = __popcll(__ballot((int32_t)cur < 0));
-            const int n_active = nA + nB + nC;
-            if (n_active == 0 || (n_active <= 64 - refill && !(drained() && ring_head == ring_tail))) break;
+            // (the counts as 32-bit words in scalar registers, see uni_word(): as the 64-bit popcounts they were, the majority tests
+            // below ran as 64-bit compares on the vector unit)
+            const uint32_t nA = uni_word((uint32_t)__popcll(__ballot(LIST ? cur - CUR_FETCH < 2u : cur == CUR_PICK))),
+                           nB = uni_word((uint32_t)__popcll(__ballot(cur < CUR_B_END))), nC = uni_word((uint32_t)__popcll(__ballot((int32_t)cur < 0)));
+            const uint32_t n_active = nA + nB + nC, n_refill = (uint32_t)(64 - refill);   // (refill is 1..64)
+            if (n_active == 0 || (n_active <= n_refill && !(drained() && ring_head == ring_tail))) break;
             // (nothing left to refill with: lanes parked for a re-cast would wait for the last active lane of the wave)
-            if (MODE == 0 && !LIST && n_active <= 64 - refill && __ballot(cur == CUR_RECAST) != 0) break;
+            if (MODE == 0 && !LIST && n_active <= n_refill && __ballot(cur == CUR_RECAST) != 0) break;
             TCK(const unsigned long long tk_v1 = TCK_NOW(); tk_vote += tk_v1 - tk_v0;)
             TS(ts_act += (unsigned long long)n_active; if (!(nB >= nA && nB >= nC) && !(nC >= nA)) { ts_steps[0]++; ts_lanes[0] += nA; })
-            if (nB >= nA && nB >= nC) {
+            // The three bodies stand one after the other, each behind a flag of its own that the compiler cannot relate to the other two
+            // (exactly one is set).  As an if / else-if chain the bodies were laid out as alternatives that meet again behind
+            // the last one: the state a body writes (cur, sp, mask; rayt and the hit record in C) and the state the next
+            // alternative reads were then live side by side, in two sets of registers, and every round copied one into the other
+            // at the entry of its body and back at the loop's end.  In sequence each body updates the one set in place.
+            // (The flags in integer arithmetic -- counts of at most 64: a difference's sign bit is "less than" -- which stays on the scalar unit;
+            // a flag made from a comparison's result goes through a lane mask and a vector select.)
+            const uint32_t nAC = nA > nC ? nA : nC;
+            const uint32_t do_b = uni_word(1u ^ ((nB - nAC) >> 31));                 // nB >= nA && nB >= nC
+            const uint32_t do_c = uni_word((1u ^ do_b) & (1u ^ ((nC - nA) >> 31)));   // else nC >= nA
+            const uint32_t do_a = uni_word(1u ^ (do_b | do_c));
+            if (do_b) {
+                asm volatile("");   // (keeps the flag a scalar branch of its own: folded into the lanes' own test it costs a v_cmp in every round)
                 TS(ts_steps[1]++; ts_lanes[1] += nB;)
                 if constexpr (COH) {
                     // the step below, once per record source: `np` is the pair record, in SGPRs on the scalar path
@@ -697,7 +711,10 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     }
                 }
                 TCK(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tk_balu += TCK_NOW() - tk_v1;)
-            } else if (nC >= nA) {
+                if (LIST) continue;   // (the long-list instantiations keep the layout as alternatives: in sequence they need up to three registers more)
+            }
+            if (do_c) {
+                asm volatile("");
                 TS(ts_steps[2]++; ts_lanes[2] += nC;)
                 const bool in_c = (int32_t)cur < 0;
                 bool same_leaf = false;
@@ -781,7 +798,11 @@ k_trace_fast(DevScene sc, const uint32_t* __restrict__ queue, const uint32_t* __
                     }
                 }
                 TCK(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); tk_c += TCK_NOW() - tk_v1;)
-            } else if (LIST && cur == CUR_FETCH) {
+                if (LIST) continue;
+            }
+            if (!do_a) continue;
+            asm volatile("");
+            if (LIST && cur == CUR_FETCH) {
                 // the next chunk that holds candidates of this ray (one dependent load; list steps are rare)
                 enter_chunk((uint32_t)__ffs((int)cvisit) - 1u);
                 cur = pick_next(mask);

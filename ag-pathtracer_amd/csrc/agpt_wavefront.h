@@ -190,6 +190,13 @@ struct DevCounters {
 // branches) are pinned to scalar registers with readfirstlane: they then cost SALU instead of VALU + exec-mask juggling.
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ bool uni(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
+// A value the compiler already holds in a scalar register, made opaque as a 32-bit word: what is computed from it afterwards is not
+// rewritten in terms of the wider value it was narrowed from (a popcount of a ballot: readfirstlane of it folds away, and a compare of
+// two of them goes back to 64 bits, for which the scalar unit has no ordered compare).
+__device__ __forceinline__ uint32_t uni_word(uint32_t v) {
+    asm("" : "+s"(v));
+    return v;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // wave-aggregated queue append: one atomic per wave, order inside the wave preserved
