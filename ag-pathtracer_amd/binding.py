@@ -22,6 +22,7 @@ HIT_DTYPE = np.dtype([("hit", np.int32), ("prim", np.int32), ("tri", np.int32),
 BVH_BUILDER_HOST, BVH_BUILDER_DEVICE = 0, 1
 # agpt_scene_update_mesh (include/agpt.h)
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
+NORMALS_GIVEN, NORMALS_SMOOTH = 0, 1
 # agpt_scene_set_shading_arith (include/agpt.h)
 SHADING_EXACT, SHADING_FAST = 0, 1
 # agpt_scene_set_material_param_texture (include/agpt.h)
@@ -38,7 +39,7 @@ EXPORTS = [
     "agpt_scene_destroy", "agpt_scene_add_material", "agpt_scene_add_mesh", "agpt_scene_add_sphere",
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
-    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_morph_arrays", "agpt_scene_set_mesh_morph_targets", "agpt_scene_morph_mesh", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
+    "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_morph_arrays", "agpt_scene_set_mesh_morph_targets", "agpt_scene_morph_mesh", "agpt_vertex_normals_arrays", "agpt_scene_set_mesh_normals_mode", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
@@ -193,7 +194,9 @@ def lib():
                        ("agpt_scene_set_mesh_skin", [vp, C.c_int, C.c_int, C.c_int, ip, fp, ip, fp]), ("agpt_scene_pose_mesh", [vp, C.c_int, fp, C.c_int, C.c_int]),
                        ("agpt_morph_arrays", [fp, C.c_int, fp, C.c_int, fp, fp, C.c_int, fp, fp, fp]),
                        ("agpt_scene_set_mesh_morph_targets", [vp, C.c_int, C.c_int, fp, fp]),
-                       ("agpt_scene_morph_mesh", [vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int])):
+                       ("agpt_scene_morph_mesh", [vp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int]),
+                       ("agpt_vertex_normals_arrays", [fp, C.c_int, ip, C.c_int, C.c_int, fp]),
+                       ("agpt_scene_set_mesh_normals_mode", [vp, C.c_int, C.c_int])):
         if not variant or hasattr(L, name):   # (an A/B variant built from an older commit lacks them: tools/mesh_update_time.py --parent-lib)
             getattr(L, name).argtypes = args
     L.agpt_scene_set_bvh_builder.argtypes = [vp, C.c_int]
@@ -458,6 +461,19 @@ def morph_arrays(weights, verts, position_deltas, normals=None, normal_deltas=No
     return vo, no
 
 
+def vertex_normals_arrays(vertices, indices, n_normals):
+    """agpt_vertex_normals_arrays on the host (no GPU needed): smooth vertex normals of verts[n, 3] under indices[k, 3] -- one (vertex,
+    normal, texcoord) triplet per corner, as for Scene.add_mesh -- -> normals[n_normals, 3]: per normal item the area-weighted face
+    vectors of the corners that name it, summed in corner order and normalised; (0, 0, 0) where that sum has no direction (shading then
+    uses the geometric normal).  The arithmetic of a mesh in "smooth" normals mode (Scene.set_mesh_normals_mode)."""
+    v, pv = _f(np.asarray(vertices).reshape(-1, 3))
+    ix, pi = _i(np.asarray(indices).reshape(-1, 3))
+    out = np.empty((max(int(n_normals), 0), 3), np.float32)
+    _check(lib().agpt_vertex_normals_arrays(pv, v.shape[0], pi, ix.shape[0], int(n_normals), out.ctypes.data_as(C.POINTER(C.c_float))),
+           "agpt_vertex_normals_arrays")
+    return out
+
+
 class Context:
     """One GPU. `stream` may be a raw hipStream_t handle (e.g. torch.cuda.Stream().cuda_stream; torch's default stream is handle 0, the
     null stream).  A non-null handle must come from the HIP runtime instance libagpt_hip.so is bound to: with torch imported first
@@ -685,6 +701,8 @@ class Scene:
         _check(self.L.agpt_scene_create(ctx.h, C.byref(h)), "agpt_scene_create")
         self.h = h
         self.n_lights = 0
+        self._mesh_normals = {}   # prim -> its number of normals (update_mesh passes it with normals=None in "smooth" mode)
+        self._smooth = set()      # the prims in "smooth" normals mode
 
     def close(self):
         if self.h:
@@ -703,9 +721,11 @@ class Scene:
         t = np.zeros((0, 2), np.float32) if uvs is None else np.asarray(uvs).reshape(-1, 2)
         t, pt = _f(t)
         ix, pi = _i(np.asarray(indices).reshape(-1, 3))
-        return _check(self.L.agpt_scene_add_mesh(self.h, pv, v.shape[0], pn, n.shape[0], pt, t.shape[0], pi,
+        prim = _check(self.L.agpt_scene_add_mesh(self.h, pv, v.shape[0], pn, n.shape[0], pt, t.shape[0], pi,
                                                  ix.shape[0], int(material), int(max_prims_in_node)),
                       "agpt_scene_add_mesh")
+        self._mesh_normals[prim] = n.shape[0]
+        return prim
 
     @staticmethod
     def _update_mode(mode, what):
@@ -734,8 +754,11 @@ class Scene:
         UPDATE_REBUILD / "rebuild" (a new BVH and the full upload).
         torch tensors on the context's GPU (contiguous float32, shape (n, 3)) are handed over as device pointers
         (agpt_scene_update_mesh_device) after torch's current stream has been synchronised -- unless the context runs on that very
-        stream; anything else (ndarray, list, CPU tensor) goes through the host call."""
+        stream; anything else (ndarray, list, CPU tensor) goes through the host call.
+        For a mesh in "smooth" normals mode (set_mesh_normals_mode) normals may be None -- NULL goes through with the mesh's own count --
+        and is never read."""
         mode = self._update_mode(mode, "update_mesh")
+        n_smooth = self._mesh_normals.get(int(prim), 0) if int(prim) in self._smooth else 0   # (the count that goes with a NULL)
         tensors = [type(a).__module__.split(".")[0] == "torch" and a.device.type != "cpu" for a in (verts, normals)]
         if tensors[0] or tensors[1]:
             import torch
@@ -747,11 +770,11 @@ class Scene:
             if not self.ctx.stream or int(stream.cuda_stream) != self.ctx.stream:   # (a context on the null stream always waits)
                 stream.synchronize()
             _check(self.L.agpt_scene_update_mesh_device(self.h, int(prim), C.c_void_p(pv), verts.shape[0], C.c_void_p(pn),
-                                                        0 if normals is None else normals.shape[0], mode), "agpt_scene_update_mesh_device")
+                                                        n_smooth if normals is None else normals.shape[0], mode), "agpt_scene_update_mesh_device")
             return
         v, pv = _f(np.asarray(verts).reshape(-1, 3))
         n, pn = (None, None) if normals is None else _f(np.asarray(normals).reshape(-1, 3))
-        _check(self.L.agpt_scene_update_mesh(self.h, int(prim), pv, v.shape[0], pn, 0 if n is None else n.shape[0], mode),
+        _check(self.L.agpt_scene_update_mesh(self.h, int(prim), pv, v.shape[0], pn, n_smooth if n is None else n.shape[0], mode),
                "agpt_scene_update_mesh")
 
     def update_mesh_device(self, prim, verts_ptr, n_vertices, normals_ptr=None, n_normals=0, mode=UPDATE_REFIT):
@@ -817,6 +840,18 @@ class Scene:
         m = None if matrices is None else _joint_matrices(matrices)
         _check(self.L.agpt_scene_morph_mesh(self.h, int(prim), pw, w.shape[0], None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
                                             0 if m is None else m.shape[0], self._update_mode(mode, "morph_mesh")), "agpt_scene_morph_mesh")
+
+    def set_mesh_normals_mode(self, prim, mode):
+        """agpt_scene_set_mesh_normals_mode: "given" (default; NORMALS_GIVEN) -- the normals of mesh primitive `prim` come from the caller or
+        from the rest normals -- or "smooth" (NORMALS_SMOOTH) -- every update call of the mesh (update_mesh, transform_mesh, pose_mesh,
+        morph_mesh) recomputes them on the GPU from the new positions: the scene is what update_mesh(prim, V, vertex_normals_arrays(V,
+        indices, n_normals), mode) leaves in "given" mode.  Changes nothing by itself."""
+        if isinstance(mode, str):
+            if mode not in ("given", "smooth"):
+                raise ValueError("set_mesh_normals_mode: unknown mode %r (given, smooth)" % (mode,))
+            mode = NORMALS_GIVEN if mode == "given" else NORMALS_SMOOTH
+        _check(self.L.agpt_scene_set_mesh_normals_mode(self.h, int(prim), int(mode)), "agpt_scene_set_mesh_normals_mode")
+        (self._smooth.add if int(mode) == NORMALS_SMOOTH else self._smooth.discard)(int(prim))
 
     def set_bvh_builder(self, builder):
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""

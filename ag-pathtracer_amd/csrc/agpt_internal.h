@@ -205,17 +205,20 @@ struct agpt_scene {
     // morph after its arrays were last given explicitly (DESIGN.md section 5.7 lists who reads the mirror).  skin: the binding of
     // agpt_scene_set_mesh_skin (host copy; the updater holds the device copies from the first pose on).  morph: the targets of
     // agpt_scene_set_mesh_morph_targets, likewise (device copies from the first morph on).
+    // normals_mode: agpt_scene_set_mesh_normals_mode; SMOOTH makes update_from_updater recompute the normals from the new positions
+    // (agpt_normals.h; the updater holds the adjacency from the first such REFIT on).
     struct MeshUpdate {
         agpt::MeshUpdater* updater = nullptr;
         bool bounds_stale = false, arrays_stale = false, rest_valid = false;
         std::vector<v3> rest_vertices, rest_normals;
         agpt::SkinBinding skin;
         agpt::MorphTargets morph;
+        int normals_mode = 0;   // AGPT_NORMALS_GIVEN / _SMOOTH (agpt_scene_set_mesh_normals_mode)
         MeshUpdate() = default;
         MeshUpdate(MeshUpdate&& o) noexcept
             : updater(o.updater), bounds_stale(o.bounds_stale), arrays_stale(o.arrays_stale), rest_valid(o.rest_valid),
               rest_vertices(std::move(o.rest_vertices)), rest_normals(std::move(o.rest_normals)), skin(std::move(o.skin)),
-              morph(std::move(o.morph)) {
+              morph(std::move(o.morph)), normals_mode(o.normals_mode) {
             o.updater = nullptr;
         }
         ~MeshUpdate() { agpt::mesh_updater_destroy(updater); }

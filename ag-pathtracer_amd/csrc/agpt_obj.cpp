@@ -72,6 +72,7 @@
 
 #include "../../include/agpt.h"
 #include "agpt_morph.h"
+#include "agpt_normals.h"
 #include "agpt_skin.h"
 #include "agpt_transform.h"
 
@@ -534,6 +535,20 @@ int agpt_morph_arrays(const float* weights, int n_targets, const float* vertices
         agpt::morph_blend(active.data(), (int)active.size(), normal_deltas, (size_t)n_normals, i, normals + 3 * i, p);
         std::memcpy(normals_out + 3 * i, p, sizeof(p));
     }
+    return AGPT_OK;
+}
+
+int agpt_vertex_normals_arrays(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int n_normals, float* normals_out) {
+    const std::string f = "agpt_vertex_normals_arrays: ";
+    if (!vertices || !indices || !normals_out) return agpt::fail(AGPT_ERR_INVALID, f + "NULL vertices, indices or normals_out");
+    if (n_vertices <= 0 || n_normals <= 0) return agpt::fail(AGPT_ERR_INVALID, f + "n_vertices and n_normals must be positive");
+    if (n_indices < 3 || n_indices % 3 != 0) return agpt::fail(AGPT_ERR_INVALID, f + "n_indices must be a positive multiple of 3");
+    for (int i = 0; i < n_indices; i++) {   // agpt_scene_add_mesh's two rules
+        const int32_t* ix = indices + 3 * (size_t)i;
+        if (ix[0] < 0 || ix[0] >= n_vertices) return agpt::fail(AGPT_ERR_INVALID, f + "vertex index out of range");
+        if (ix[1] < 0 || ix[1] >= n_normals) return agpt::fail(AGPT_ERR_INVALID, f + "normal index out of range");
+    }
+    agpt::vertex_normals_host(vertices, indices, (size_t)n_indices, (size_t)n_normals, normals_out);
     return AGPT_OK;
 }
 

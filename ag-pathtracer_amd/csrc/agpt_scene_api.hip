@@ -12,6 +12,7 @@
 
 #include "agpt_bvh_device.h"
 #include "agpt_internal.h"
+#include "agpt_normals.h"
 
 using agpt::fail;
 
@@ -538,7 +539,8 @@ static int check_update(const char* fn, const agpt_scene* s, int prim, const voi
     if (prim < 0 || prim >= (int)s->prims.size() || s->prims[prim].type != AGPT_PRIM_MESH)
         return fail(AGPT_ERR_INVALID, f + ": primitive " + std::to_string(prim) + " is not a mesh of this scene");
     const agpt::HostMesh& mesh = s->meshes[(size_t)s->prims[prim].index];
-    if (n_vertices != (int)mesh.vertices.size() || n_normals != (int)mesh.normals.size() || (!normals && !mesh.normals.empty()))
+    const bool smooth = s->updates[(size_t)s->prims[prim].index].normals_mode == AGPT_NORMALS_SMOOTH;   // (its normals are never read)
+    if (n_vertices != (int)mesh.vertices.size() || n_normals != (int)mesh.normals.size() || (!normals && !mesh.normals.empty() && !smooth))
         return fail(AGPT_ERR_INVALID, f + ": the mesh has " + std::to_string(mesh.vertices.size()) + " vertices and " +
                                           std::to_string(mesh.normals.size()) + " normals; both counts stay (normals may be NULL only without any)");
     if (mode != AGPT_UPDATE_REFIT && mode != AGPT_UPDATE_REBUILD) return fail(AGPT_ERR_INVALID, f + ": unknown mode " + std::to_string(mode));
@@ -593,6 +595,18 @@ static int update_on_host(agpt_scene* s, size_t mi, const float* vertices, const
     return agpt_scene_commit(s);
 }
 
+static bool smooth_normals(const agpt_scene* s, size_t mi) { return s->updates[mi].normals_mode == AGPT_NORMALS_SMOOTH; }
+
+// update_on_host for a mesh in AGPT_NORMALS_SMOOTH mode: the normals are the twin's (agpt_normals.h), from the new positions
+static int update_on_host_smooth(agpt_scene* s, size_t mi, const float* vertices, int mode) {
+    const agpt::HostMesh& mesh = s->meshes[mi];
+    std::vector<float> n(3 * mesh.normals.size());
+    agpt::vertex_normals_host(vertices, mesh.indices.data(), mesh.indices.size() / 3, mesh.normals.size(), n.data());
+    return update_on_host(s, mi, vertices, n.data(), mode);
+}
+
+static int update_from_updater(agpt_scene* s, int prim, size_t mi, int mode);
+
 // REFIT on the device: where flatten_scene put this mesh
 static agpt::UpdateTarget update_target(const agpt_scene* s, int prim, size_t mi) {
     size_t node_base = 0, tri_base = 0;
@@ -636,6 +650,11 @@ int agpt_scene_update_mesh(agpt_scene* s, int prim, const float* vertices, int n
     forget_rest(s, mi);
     bool finite = true;
     for (int i = 0; i < 3 * n_vertices && finite; i++) finite = std::isfinite(vertices[i]);
+    if (smooth_normals(s, mi)) {   // `normals` is not read
+        if (mode == AGPT_UPDATE_REBUILD || !finite) return update_on_host_smooth(s, mi, vertices, mode);
+        if (const int rc = agpt::upload_positions_device(s->ctx->stream, &s->updates[mi].updater, mesh, vertices)) return rc;
+        return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `vertices` lives until then)
+    }
     if (mode == AGPT_UPDATE_REBUILD || !finite) return update_on_host(s, mi, vertices, normals, mode);
     const agpt::UpdateTarget tg = update_target(s, prim, mi);
     float root[6];
@@ -649,15 +668,20 @@ int agpt_scene_update_mesh(agpt_scene* s, int prim, const float* vertices, int n
 // bring them to the host and do what agpt_scene_update_mesh does with host arrays
 static int update_from_updater(agpt_scene* s, int prim, size_t mi, int mode) {
     agpt::HostMesh& mesh = s->meshes[mi];
+    const bool smooth = smooth_normals(s, mi);   // the front end left positions only: the normals are recomputed from them
     if (mode == AGPT_UPDATE_REFIT) {
         const agpt::UpdateTarget tg = update_target(s, prim, mi);
         float root[6];
         bool finite = true;
+        if (smooth)
+            if (const int rc = agpt::smooth_normals_device(s->ctx->stream, s->updates[mi].updater, mesh)) return rc;
         if (const int rc = agpt::refit_device_arrays(s->ctx->stream, s->updates[mi].updater, mesh, tg, root, &finite)) return rc;
         if (finite) return refit_done(s, mi, root, true);
     }
     std::vector<v3> v(mesh.vertices.size()), n(mesh.normals.size());
+    if (smooth) n.clear();   // (not fetched: the host twin fills them)
     if (const int rc = agpt::download_arrays(s->ctx->stream, s->updates[mi].updater, v, n)) return rc;
+    if (smooth) return update_on_host_smooth(s, mi, &v.data()->x, mode);
     return update_on_host(s, mi, &v.data()->x, n.empty() ? nullptr : &n.data()->x, mode);
 }
 
@@ -667,14 +691,18 @@ int agpt_scene_update_mesh_device(agpt_scene* s, int prim, const float* vertices
     const size_t mi = (size_t)s->prims[prim].index;
     HIP_TRY(hipSetDevice(s->ctx->device));
     if (mode == AGPT_UPDATE_REBUILD) {   // the builders take host arrays
-        std::vector<float> v((size_t)3 * n_vertices), n((size_t)3 * n_normals);
+        const bool smooth = smooth_normals(s, mi);   // `normals_dev` is not read
+        std::vector<float> v((size_t)3 * n_vertices), n(smooth ? 0 : (size_t)3 * n_normals);
         HIP_TRY(hipMemcpyAsync(v.data(), vertices_dev, v.size() * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
         if (!n.empty()) HIP_TRY(hipMemcpyAsync(n.data(), normals_dev, n.size() * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
         HIP_TRY(hipStreamSynchronize(s->ctx->stream));
         forget_rest(s, mi);
+        if (smooth) return update_on_host_smooth(s, mi, v.data(), mode);
         return update_on_host(s, mi, v.data(), n.empty() ? nullptr : n.data(), mode);
     }
-    if (const int rc = agpt::copy_arrays_device(s->ctx->stream, &s->updates[mi].updater, s->meshes[mi], vertices_dev, normals_dev)) return rc;
+    if (const int rc = agpt::copy_arrays_device(s->ctx->stream, &s->updates[mi].updater, s->meshes[mi], vertices_dev,
+                                                smooth_normals(s, mi) ? nullptr : normals_dev))
+        return rc;
     forget_rest(s, mi);
     return update_from_updater(s, prim, mi, mode);
 }
@@ -712,7 +740,9 @@ int agpt_scene_transform_mesh(agpt_scene* s, int prim, const float* transform16,
     HIP_TRY(hipSetDevice(s->ctx->device));
     agpt_scene::MeshUpdate& up = s->updates[mi];
     if (const int rc = take_rest(s, mi)) return rc;
-    if (const int rc = agpt::transform_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, M, N)) return rc;
+    if (const int rc = agpt::transform_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, M, N,
+                                                     !smooth_normals(s, mi)))
+        return rc;
     return update_from_updater(s, prim, mi, mode);
 }
 
@@ -781,11 +811,12 @@ int agpt_scene_pose_mesh(agpt_scene* s, int prim, const float* joints16, int n_j
     const size_t mi = (size_t)s->prims[prim].index;
     agpt_scene::MeshUpdate& up = s->updates[mi];
     std::vector<float> palette;
-    if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty(), joints16, n_joints, palette)) return rc;
+    const bool with_normals = !smooth_normals(s, mi);   // (smooth: the palette carries M only)
+    if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty() && with_normals, joints16, n_joints, palette)) return rc;
     HIP_TRY(hipSetDevice(s->ctx->device));
     if (const int rc = take_rest(s, mi)) return rc;   // as for agpt_scene_transform_mesh: the two share the rest pose
     if (const int rc = agpt::skin_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, up.skin, palette,
-                                                s->ctx->num_cus))
+                                                s->ctx->num_cus, with_normals))
         return rc;
     return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `palette` lives until then)
 }
@@ -834,15 +865,28 @@ int agpt_scene_morph_mesh(agpt_scene* s, int prim, const float* weights, int n_t
     const std::string bad = agpt::morph_check_weights(weights, n_targets);
     if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
     std::vector<float> palette;
+    const bool with_normals = !smooth_normals(s, mi);
     if (joints16)   // morph, then skin: agpt_scene_pose_mesh's checks
-        if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty(), joints16, n_joints, palette)) return rc;
+        if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty() && with_normals, joints16, n_joints, palette)) return rc;
     const std::vector<agpt::MorphActive> active = agpt::morph_active_list(weights, n_targets);
     HIP_TRY(hipSetDevice(s->ctx->device));
     if (const int rc = take_rest(s, mi)) return rc;   // the rest pose the transform and the pose use
     if (const int rc = agpt::morph_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, up.morph, active,
-                                                 joints16 ? &up.skin : nullptr, joints16 ? &palette : nullptr, s->ctx->num_cus))
+                                                 joints16 ? &up.skin : nullptr, joints16 ? &palette : nullptr, s->ctx->num_cus, with_normals))
         return rc;
     return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `active` and `palette` live until then)
+}
+
+int agpt_scene_set_mesh_normals_mode(agpt_scene* s, int prim, int mode) {
+    const std::string f = "agpt_scene_set_mesh_normals_mode: ";
+    if (!s) return fail(AGPT_ERR_INVALID, f + "NULL scene");
+    const agpt::HostMesh* m = mesh_of(s, prim);
+    if (!m) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " is not a mesh of this scene");
+    if (mode != AGPT_NORMALS_GIVEN && mode != AGPT_NORMALS_SMOOTH) return fail(AGPT_ERR_INVALID, f + "unknown mode " + std::to_string(mode));
+    if (mode == AGPT_NORMALS_SMOOTH && m->normals.empty())
+        return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no normals (the counts of a mesh cannot change)");
+    s->updates[(size_t)s->prims[prim].index].normals_mode = mode;
+    return AGPT_OK;
 }
 
 int agpt_scene_set_bvh_builder(agpt_scene* s, int builder) {

@@ -30,8 +30,8 @@ struct UpdateTarget {
 
 // What the device path keeps per mesh between updates: indices, texture coordinates, prim_index, the tree's topology and per-level
 // node lists (uploaded on the first update), positions / normals, the rest pose of agpt_scene_transform_mesh, agpt_scene_pose_mesh
-// and agpt_scene_morph_mesh, the binding and palette of a skin, the deltas and active list of morph targets, and the bounds in the
-// reference layout.
+// and agpt_scene_morph_mesh, the binding and palette of a skin, the deltas and active list of morph targets, the adjacency and face
+// vectors of smooth normals, and the bounds in the reference layout.
 struct MeshUpdater;
 void mesh_updater_destroy(MeshUpdater*);
 
@@ -59,12 +59,21 @@ int update_mesh_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& 
 // Only the flag and the root box come back.  download_arrays fetches the buffers' contents (vertices / normals keep their sizes).
 int copy_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices_dev, const float* normals_dev);
 int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N);
+                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N, bool with_normals);
 int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus);
+                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus,
+                       bool with_normals);
 int morph_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
                         const std::vector<v3>& rest_normals, const MorphTargets& morph, const std::vector<MorphActive>& active,
-                        const SkinBinding* skin, const std::vector<float>* palette, int num_cus);
+                        const SkinBinding* skin, const std::vector<float>* palette, int num_cus, bool with_normals);
+// AGPT_NORMALS_SMOOTH.  The three kernels above take with_normals == false for a mesh in that mode: their normal halves get an item
+// count of zero and the palette carries M only (stride 13).  copy_arrays_device accepts normals_dev == NULL (room is made, nothing is
+// copied), and upload_positions_device is its host-array form (the caller keeps `vertices` until the stream is synchronised).
+// smooth_normals_device then writes the cache's normals buffer from its positions: k_face_normals and k_vertex_normals
+// (agpt_normals.h), enqueued on `stream` without synchronising.  The CSR adjacency of the normal items is built on the host and
+// uploaded when the cache holds none (the mesh's first smooth update, and the first after a REBUILD destroyed the cache) and kept.
+int upload_positions_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices);
+int smooth_normals_device(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh);
 int refit_device_arrays(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh, const UpdateTarget& target, float root6[6], bool* finite);
 void drop_rest(MeshUpdater* cache);   // the rest pose changed (NULL is fine)
 void drop_skin(MeshUpdater* cache);   // the binding changed: its device copies are freed (NULL is fine)

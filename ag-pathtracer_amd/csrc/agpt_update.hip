@@ -18,6 +18,13 @@
 //                    (agpt_scene_pose_mesh).
 //   k_morph_mesh     one lane per vertex and one per normal: the rest arrays plus the ACTIVE morph targets' deltas (morph_blend of
 //                    agpt_morph.h) and, fused (kSkin), straight on through skin_blend (agpt_scene_morph_mesh).
+//   k_face_normals   one lane per triangle: its three vertex indices (the index array k_update_tris reads) and positions, face_vector of
+//                    agpt_normals.h, one float4 g_t (w unused) into a per-mesh scratch of n_tris x 16 B.
+//   k_vertex_normals one lane per normal item: offsets[j], offsets[j + 1] of the CSR adjacency, then per incident corner the triangle id
+//                    and one 16-byte gather of its g, summed in ascending corner order and finished by vertex_normal / normal_finish of
+//                    agpt_normals.h: 12 B of the normals buffer.  Both run only for a mesh in AGPT_NORMALS_SMOOTH mode, between the
+//                    front end that leaves positions in `verts` and k_update_tris; no atomics, so the bytes do not depend on the
+//                    launch.  An item of very high valence is walked by one lane: correct and slow.
 // All are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair, 24 B per transformed vertex, 24 + 8 K B
 // per skinned vertex, 24 + 12 A B per vertex morphed by A active targets); all but k_skin_mesh and k_morph_mesh run 64-lane blocks,
 // 16-byte accesses of the float4 records, no LDS.
@@ -76,6 +83,7 @@
 #include <vector>
 
 #include "agpt_bvh_arith.h"
+#include "agpt_normals.h"
 
 namespace agpt {
 
@@ -184,6 +192,24 @@ __global__ __launch_bounds__(kBlock) void k_check_finite(const float* x, size_t 
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const bool bad = i < n && (__float_as_uint(x[i]) & 0x7f800000u) == 0x7f800000u;
     if (__any(bad) && (threadIdx.x & 63) == 0) *flag = 1u;   // (every wave that sees one stores the same word)
+}
+
+__global__ __launch_bounds__(kBlock) void k_face_normals(const float* verts, const int32_t* indices, float4* face, int n_tris) {
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_tris) return;
+    const int32_t* ix = indices + 9 * (size_t)t;
+    const v3 g = face_vector(load3(verts, ix[0]), load3(verts, ix[3]), load3(verts, ix[6]));
+    face[t] = make_float4(g.x, g.y, g.z, 0.f);
+}
+
+__global__ __launch_bounds__(kBlock) void k_vertex_normals(const int32_t* offsets, const int32_t* corner_tri, const float4* face, float* normals,
+                                                           int n_normals) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n_normals) return;
+    const v3 n = vertex_normal(offsets, corner_tri, face, (size_t)j);
+    normals[3 * (size_t)j] = n.x;
+    normals[3 * (size_t)j + 1] = n.y;
+    normals[3 * (size_t)j + 2] = n.z;
 }
 
 struct TransformArgs {
@@ -357,6 +383,11 @@ struct MeshUpdater {
     Buf<float> morph_position_deltas, morph_normal_deltas;
     Buf<MorphActive> morph_active;
     bool has_morph = false;
+    // AGPT_NORMALS_SMOOTH: the CSR adjacency of the normal items (built and uploaded by the first smooth update of this cache) and the
+    // face vectors of the last one
+    Buf<int32_t> normal_offsets, normal_corner_tri;
+    Buf<float4> face_normals;
+    bool has_adjacency = false;
     Buf<uint32_t> flag;        // k_check_finite's word
     Buf<v2> uv;
     Buf<int32_t> indices, prim_index, lists;
@@ -493,8 +524,39 @@ int copy_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& 
     UPD_TRY(hipMemcpyAsync(u.verts.p, vertices_dev, nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (nn) {
         UPD_TRY(u.normals.reserve(nn));
-        UPD_TRY(hipMemcpyAsync(u.normals.p, normals_dev, nn * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (normals_dev) UPD_TRY(hipMemcpyAsync(u.normals.p, normals_dev, nn * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
+    return AGPT_OK;
+}
+
+int upload_positions_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices) {
+    if (const int rc = ensure(stream, cache, mesh)) return rc;
+    MeshUpdater& u = **cache;
+    UPD_TRY(u.verts.upload(vertices, 3 * mesh.vertices.size(), stream));   // (the caller keeps `vertices` until the stream is synchronised)
+    UPD_TRY(u.normals.reserve(3 * mesh.normals.size()));
+    return AGPT_OK;
+}
+
+int smooth_normals_device(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh) {
+    MeshUpdater& u = *cache;
+    const size_t nn = mesh.normals.size(), n_corners = mesh.indices.size() / 3, n_tris = n_corners / 3;
+    // what the kernels index with, against what they index (the indices were checked by agpt_scene_add_mesh)
+    if (nn == 0 || n_tris == 0 || n_tris != mesh.prim_index.size() || n_corners > (size_t)INT32_MAX || !u.verts.p || !u.normals.p)
+        return fail(AGPT_ERR_INVALID, "smooth normals: the mesh has no normals, or the cache does not hold its arrays");
+    if (!u.has_adjacency) {
+        std::vector<int32_t> offsets, corner_tri;
+        normal_adjacency(mesh.indices.data(), n_corners, nn, offsets, corner_tri);
+        UPD_TRY(u.normal_offsets.upload(offsets.data(), offsets.size(), stream));
+        UPD_TRY(u.normal_corner_tri.upload(corner_tri.data(), corner_tri.size(), stream));
+        UPD_TRY(u.face_normals.reserve(n_tris));
+        UPD_TRY(hipStreamSynchronize(stream));   // the staging vectors go out of scope
+        u.has_adjacency = true;
+    }
+    hipLaunchKernelGGL(k_face_normals, dim3((unsigned)((n_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, u.verts.p, u.indices.p,
+                       u.face_normals.p, (int)n_tris);
+    hipLaunchKernelGGL(k_vertex_normals, dim3((unsigned)((nn + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, u.normal_offsets.p,
+                       u.normal_corner_tri.p, u.face_normals.p, u.normals.p, (int)nn);
+    UPD_TRY(hipGetLastError());
     return AGPT_OK;
 }
 
@@ -519,10 +581,10 @@ static int ensure_rest(const char* fn, hipStream_t stream, MeshUpdater** cache, 
 }
 
 int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N) {
+                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N, bool with_normals) {
     if (const int rc = ensure_rest("agpt_scene_transform_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
     MeshUpdater& u = **cache;
-    const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
+    const size_t nv = mesh.vertices.size(), nn = with_normals ? mesh.normals.size() : 0;
     TransformArgs a;
     a.M = M;
     a.N = N;
@@ -540,9 +602,9 @@ int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostM
 // the binding on the device (uploaded when the cache holds none), this call's palette, and k_skin_mesh's arguments: what the pose and the
 // fused morph share (`fn` names the call in the message)
 static int skin_on_device(const char* fn, hipStream_t stream, MeshUpdater& u, const HostMesh& mesh, const SkinBinding& skin,
-                          const std::vector<float>& palette, SkinArgs& a) {
+                          const std::vector<float>& palette, bool with_normals, SkinArgs& a) {
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), K = (size_t)skin.influences;
-    const int stride = skin_palette_stride(nn != 0);
+    const int stride = skin_palette_stride(nn != 0 && with_normals);   // (without: M only, as for a mesh that has no normals)
     const bool own_normal_slots = nn && !skin.normal_joints.empty();
     // what the kernel indexes with, against what it indexes (the joint indices were checked against n_joints when the skin was set)
     if (K < 1 || K > (size_t)kSkinMaxInfluences || skin.vertex_joints.size() != nv * K || skin.vertex_weights.size() != nv * K ||
@@ -559,6 +621,7 @@ static int skin_on_device(const char* fn, hipStream_t stream, MeshUpdater& u, co
         UPD_TRY(hipStreamSynchronize(stream));   // (the binding may be replaced behind this call)
         u.has_skin = true;
     }
+    UPD_TRY(u.skin_palette.reserve((size_t)skin.n_joints * (size_t)skin_palette_stride(true)));   // (room for either stride)
     UPD_TRY(u.skin_palette.upload(palette.data(), palette.size(), stream));   // (the caller keeps `palette` until the stream is synchronised)
     a.palette = u.skin_palette.p;
     a.stride = stride;
@@ -572,8 +635,8 @@ static int skin_on_device(const char* fn, hipStream_t stream, MeshUpdater& u, co
 }
 
 // the arrays of the rest pose and of the result (ensure_rest has made them)
-static void rest_args(const MeshUpdater& u, const HostMesh& mesh, SkinArgs& a) {
-    const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
+static void rest_args(const MeshUpdater& u, const HostMesh& mesh, bool with_normals, SkinArgs& a) {
+    const size_t nv = mesh.vertices.size(), nn = with_normals ? mesh.normals.size() : 0;
     a.rest_verts = u.rest_verts.p;
     a.rest_normals = nn ? u.rest_normals.p : nullptr;
     a.verts = u.verts.p;
@@ -583,13 +646,14 @@ static void rest_args(const MeshUpdater& u, const HostMesh& mesh, SkinArgs& a) {
 }
 
 int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus) {
+                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus,
+                       bool with_normals) {
     if (const int rc = ensure_rest("agpt_scene_pose_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
     MeshUpdater& u = **cache;
     SkinArgs a;
-    if (const int rc = skin_on_device("agpt_scene_pose_mesh", stream, u, mesh, skin, palette, a)) return rc;
-    rest_args(u, mesh, a);
-    const size_t lds = palette.size() * sizeof(float), blocks = (mesh.vertices.size() + mesh.normals.size() + kSkinBlock - 1) / kSkinBlock;
+    if (const int rc = skin_on_device("agpt_scene_pose_mesh", stream, u, mesh, skin, palette, with_normals, a)) return rc;
+    rest_args(u, mesh, with_normals, a);
+    const size_t lds = palette.size() * sizeof(float), blocks = ((size_t)a.n_vertices + (size_t)a.n_normals + kSkinBlock - 1) / kSkinBlock;
     const size_t cus = (size_t)(num_cus > 0 ? num_cus : 1);
     if (lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE")) {
         hipLaunchKernelGGL(k_skin_mesh<true>, dim3((unsigned)std::min(blocks, cus * kSkinBlocksPerCU)), dim3(kSkinBlock), lds, stream, a);
@@ -602,7 +666,7 @@ int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& 
 
 int morph_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
                         const std::vector<v3>& rest_normals, const MorphTargets& morph, const std::vector<MorphActive>& active,
-                        const SkinBinding* skin, const std::vector<float>* palette, int num_cus) {
+                        const SkinBinding* skin, const std::vector<float>* palette, int num_cus, bool with_normals) {
     const char* fn = "agpt_scene_morph_mesh";
     if (const int rc = ensure_rest(fn, stream, cache, mesh, rest_vertices, rest_normals)) return rc;
     MeshUpdater& u = **cache;
@@ -628,10 +692,10 @@ int morph_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh&
     m.normal_deltas = normal_deltas ? u.morph_normal_deltas.p : nullptr;
     m.s = SkinArgs();
     if (skin)
-        if (const int rc = skin_on_device(fn, stream, u, mesh, *skin, *palette, m.s)) return rc;
-    rest_args(u, mesh, m.s);
+        if (const int rc = skin_on_device(fn, stream, u, mesh, *skin, *palette, with_normals, m.s)) return rc;
+    rest_args(u, mesh, with_normals, m.s);
     const size_t cus = (size_t)(num_cus > 0 ? num_cus : 1);
-    size_t blocks = std::min((nv + nn + kSkinBlock - 1) / kSkinBlock, cus * (skin ? kSkinBlocksPerCU : kMorphBlocksPerCU));
+    size_t blocks = std::min(((size_t)m.s.n_vertices + (size_t)m.s.n_normals + kSkinBlock - 1) / kSkinBlock, cus * (skin ? kSkinBlocksPerCU : kMorphBlocksPerCU));
     if (const char* cap = getenv("AGPT_MORPH_MAX_BLOCKS")) {
         const long c = std::strtol(cap, nullptr, 10);
         if (c >= 1) blocks = std::min(blocks, (size_t)c);

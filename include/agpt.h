@@ -385,7 +385,8 @@ int agpt_scene_set_mesh_skin(agpt_scene*, int prim, int influences, int n_joints
  * non-finite entry; a last row that is not exactly (0, 0, 0, 1); a joint whose determinant (agpt_transform_arrays' value) is exactly
  * 0, named in the message.  A refused call changes nothing.
  * Out of scope: sparse morph targets, tangent deltas, weights or joint matrices given in device memory, dual-quaternion blending,
- * renormalised normals, motion vectors (and what agpt_scene_update_mesh_device does not cover).  Morph targets: agpt_scene_morph_mesh. */
+ * motion vectors (and what agpt_scene_update_mesh_device does not cover).  Morph targets: agpt_scene_morph_mesh.  Normals recomputed from
+ * the posed positions: agpt_scene_set_mesh_normals_mode. */
 int agpt_scene_pose_mesh(agpt_scene*, int prim, const float* joints16, int n_joints, int mode);
 /* Morph targets (blend shapes) applied to a mesh's arrays, host-only like agpt_skin_arrays (no GPU, no context): fp32, every operation
  * rounded on its own, nothing contracted into an fma.
@@ -435,8 +436,54 @@ int agpt_scene_set_mesh_morph_targets(agpt_scene*, int prim, int n_targets, cons
  * targets were set with; a weight that is not finite; then, with joints16, agpt_scene_pose_mesh's remaining checks in its order (a mesh
  * without a skin; n_joints; a non-finite entry; a last row; a singular joint).  A refused call changes nothing.
  * Out of scope: sparse targets (a delta for every item of every target is stored), tangent deltas, weights or joint matrices given in
- * device memory, renormalised normals, motion vectors (and what agpt_scene_update_mesh_device does not cover). */
+ * device memory, motion vectors (and what agpt_scene_update_mesh_device does not cover).  Normals recomputed from the morphed
+ * positions (glTF's advice for targets without normal deltas): agpt_scene_set_mesh_normals_mode. */
 int agpt_scene_morph_mesh(agpt_scene*, int prim, const float* weights, int n_targets, const float* joints16, int n_joints, int mode);
+/* Smooth vertex normals from positions and topology, host-only like agpt_morph_arrays (no GPU, no context): fp32, every operation
+ * rounded on its own, nothing contracted into an fma.  indices are n_indices (vertex, normal, texcoord) triplets -- corners -- as in
+ * agpt_scene_add_mesh; triangle t owns the corners 3t, 3t+1, 3t+2.
+ *   face vector   g_t = cross(p_b - p_a, p_c - p_a), a, b, c the vertex indices of the corners 3t, 3t+1, 3t+2: area-weighted, not normalised.
+ *   normal item j the corners in ascending order whose normal index is j: the first sets acc = g of its triangle, every later one
+ *                 acc = acc + g per component.  A triangle that names j at two corners contributes twice.  The order is part of the
+ *                 definition.
+ *   finish        l2 = dot(acc, acc); the result is (+0, +0, +0) if no corner names j, if !(l2 > 0) or if l2 is not finite; otherwise
+ *                 acc * (1.0f / sqrtf(l2)).
+ * Shading reads a zero normal as "use the geometric normal", so an unreferenced item, zero-area or exactly cancelling faces, a sum whose
+ * square underflows (|acc| below about 2^-75) or overflows (above 2^64) and NaN or Inf positions -- which are NOT refused -- all have a
+ * defined, harmless value.  Writes 3 * n_normals floats; also serves a host that loads an OBJ without normals.
+ * AGPT_ERR_INVALID (+ agpt_last_error) for a NULL pointer, n_vertices <= 0 or n_normals <= 0, n_indices < 3 or not a multiple of 3, a
+ * vertex or normal index out of range (agpt_scene_add_mesh's rules); a refused call writes nothing.
+ * Limit: an item of very high valence is summed by one thread (on the GPU: one lane).  Out of scope: angle-weighted or crease-angle
+ * normals, tangents. */
+int agpt_vertex_normals_arrays(const float* vertices, int n_vertices, const int32_t* indices, int n_indices, int n_normals,
+                               float* normals_out);
+/* Where the normals of mesh primitive `prim` come from at an update.  GIVEN (the default): from the caller, or from the transform, skin
+ * or morph of the rest normals, as documented at each call.  SMOOTH: EVERY update call of the mesh -- agpt_scene_update_mesh, _device,
+ * agpt_scene_transform_mesh, agpt_scene_pose_mesh, agpt_scene_morph_mesh, fused morph + skin included -- leaves the scene byte for byte
+ * what the same call's positions V would leave through agpt_scene_update_mesh(scene, prim, V, n_vertices, N, n_normals, mode) in GIVEN
+ * mode with N = agpt_vertex_normals_arrays(V, the mesh's indices).
+ *   update_mesh / _device   normals (normals_dev) may be NULL and is never read; n_normals is still checked against the mesh's count,
+ *              and every other refusal and their order are unchanged.
+ *   transform / pose / morph   the normal halves of their kernels get an item count of zero, and the palette goes up without its
+ *              normal part; normal deltas and normal slots are kept but not read.
+ *   REFIT      after the front end has left the positions on the GPU, k_face_normals (one lane per triangle, 16 bytes each into a
+ *              per-mesh scratch) and k_vertex_normals (one lane per normal item, walking a CSR adjacency in ascending corner order)
+ *              write the normals there, and the refit runs as before: no normals cross the bus, no atomics, the same bytes every run.
+ *              The adjacency (4 * (n_normals + 1 + n_indices) bytes) is built on the host and uploaded by the mesh's first SMOOTH
+ *              device update, and kept.  A REBUILD -- by any update call of this mesh -- destroys the mesh's device cache, so the next
+ *              REFIT uploads it again.
+ *   REBUILD and a non-finite position   the positions come down as for GIVEN, agpt_vertex_normals_arrays' function fills the normals
+ *              on the host, and the host path continues.
+ *   rest pose  stays "the arrays the mesh last received explicitly": an explicit update in SMOOTH mode makes (V, the recomputed N) the
+ *              rest pose.  Switching back to GIVEN changes nothing until the next call, which then uses the rest normals as before.
+ * May be called any time after agpt_scene_add_mesh, on a committed scene or not; it stores the mode and changes nothing else (no
+ * record, no buffer: the scene reads the same before and after).  A mesh in GIVEN mode runs what it ran before, with no new launch.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order: NULL scene; a prim that is not a mesh of the scene; an unknown
+ * mode; SMOOTH for a mesh without normals (the counts cannot change, so there is nothing to write into).
+ * Limit: a normal item of very high valence is summed by one lane.  Out of scope: angle-weighted or crease-angle normals, adding
+ * normals to a mesh that has none, tangents, spheres, planes and lights, motion vectors. */
+enum { AGPT_NORMALS_GIVEN = 0, AGPT_NORMALS_SMOOTH = 1 };
+int agpt_scene_set_mesh_normals_mode(agpt_scene*, int prim, int mode);
 /* Which builder agpt_scene_add_mesh uses for the BVH of later meshes on this scene (default HOST).  Both produce the same
  * bytes; DEVICE runs agpt_bvh_build_device on the scene's context. */
 enum { AGPT_BVH_BUILDER_HOST = 0, AGPT_BVH_BUILDER_DEVICE = 1 };

@@ -149,6 +149,8 @@ enum class BvhBuilder { Host = AGPT_BVH_BUILDER_HOST, Device = AGPT_BVH_BUILDER_
 // agpt_scene_set_shading_arith: exact (default, bit-identical to the oracle) or fast shading arithmetic for later renders
 // agpt_scene_update_mesh: keep the tree and refit its boxes, or build a new one
 enum class MeshUpdate { Refit = AGPT_UPDATE_REFIT, Rebuild = AGPT_UPDATE_REBUILD };
+// agpt_scene_set_mesh_normals_mode: a mesh's normals come from the caller / its rest normals, or are recomputed from every update's positions
+enum class MeshNormals { Given = AGPT_NORMALS_GIVEN, Smooth = AGPT_NORMALS_SMOOTH };
 enum class ShadingArith { Exact = AGPT_SHADING_EXACT, Fast = AGPT_SHADING_FAST };
 
 class Scene {
@@ -270,6 +272,14 @@ public:
         check(agpt_scene_morph_mesh(h_, prim, weights.data(), (int)weights.size(), joints16.empty() ? nullptr : joints16.data(),
                                     (int)(joints16.size() / 16), (int)mode),
               "agpt_scene_morph_mesh");
+    }
+    // smooth vertex normals recomputed on the GPU (agpt_scene_set_mesh_normals_mode): with MeshNormals::Smooth every later UpdateMesh,
+    // UpdateMeshDevice, TransformMesh, PoseMesh and MorphMesh of the mesh writes its normals from the new positions -- area-weighted face
+    // vectors summed per normal in corner order, normalised; (0, 0, 0), "use the geometric normal", where that sum has no direction --
+    // and the normals those calls are given (normals_dev may be NULL) are not read.  Changes nothing by itself.
+    // `scene.SetMeshNormalsMode(prim, MeshNormals::Smooth);` once, then `scene.UpdateMesh(prim, mesh); accumulator.Clear();` per frame.
+    void SetMeshNormalsMode(int prim, MeshNormals mode) {
+        check(agpt_scene_set_mesh_normals_mode(h_, prim, (int)mode), "agpt_scene_set_mesh_normals_mode");
     }
     // camera moved (RotatingCamera::update): re-derive the camera only, geometry stays in HBM
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }

@@ -6,6 +6,7 @@ one warm-up, and the bytes that cross PCIe per call (up / down, from the sizes; 
     python tools/mesh_update_time.py [--runs 9] [--out profiles/mesh_update_times.json] [--parent-lib TAG] [--rounds 3]
     python tools/mesh_update_time.py --pose [--runs 9] [--out profiles/mesh_pose_times.json]
     python tools/mesh_update_time.py --morph [--runs 9] [--out profiles/mesh_morph_times.json]
+    python tools/mesh_update_time.py --normals [--runs 9] [--out profiles/mesh_normals_times.json]
 
 --pose times agpt_scene_pose_mesh instead (REFIT, 4 influences per vertex, 64 and 1,024 joints, the palette staged in LDS and read
 from global memory -- AGPT_SKIN_GLOBAL_PALETTE), with, in the same process on the same GPU, agpt_scene_transform_mesh and the route a
@@ -14,6 +15,11 @@ host has without it: agpt_skin_arrays on the CPU, then agpt_scene_update_mesh wi
 --morph times agpt_scene_morph_mesh (REFIT, 64 targets bound with normal deltas, 0 / 4 / 16 / 64 of them active; 16 active fused with a
 64-joint skin of 4 influences) with, in the same process on the same GPU, agpt_scene_transform_mesh, agpt_scene_pose_mesh with the same
 skin, and the route a host has without it: agpt_morph_arrays on the CPU, then agpt_scene_update_mesh with its output.
+
+--normals times the AGPT_NORMALS_SMOOTH mode (agpt_scene_set_mesh_normals_mode): agpt_scene_update_mesh_device REFIT with the caller's
+normals (the floor) against the same call in SMOOTH mode with NULL normals, agpt_scene_morph_mesh at 16 active targets once GIVEN with
+normal deltas and once SMOOTH without, the rows taking turns in one process on the same GPU, and agpt_vertex_normals_arrays on one CPU
+thread.
 
 --parent-lib TAG compares the host-pointer REFIT of this build with the build `libagpt_hip_TAG.so` of the parent commit
 (tools/build_variant.py run in a checkout of it, the file copied beside libagpt_hip.so): child processes, alternating parent / this
@@ -268,6 +274,72 @@ def morph_leg(runs):
     return result
 
 
+NORMALS_TARGETS = 16   # all of them active
+NORMALS_ROUNDS = 3
+
+
+def normals_leg(runs):
+    result = {"runs": runs, "targets_bound_and_active": NORMALS_TARGETS,
+              "statistic": "host clock around the synchronised call, ms: median and min-max of the runs after one warm-up (the warm-up "
+                           "uploads the adjacency, the rest pose and the deltas); all rows of a case from one process on one GPU, two "
+                           "scenes of it -- one with the mesh in GIVEN, one in SMOOTH mode --; every GPU row is %d rounds that take the "
+                           "operations in turn: the median of the rounds' medians, the lowest min, the highest max.  kernel_bytes: what "
+                           "k_face_normals and k_vertex_normals move by their header: per triangle 36 B of indices, 36 B of positions "
+                           "and 16 B of g written, per normal item 8 B of offsets and 12 B written, per corner 4 B of triangle id and a "
+                           "16-byte gather" % NORMALS_ROUNDS,
+              "cases": {}}
+    ctx = ag.Context(0)
+    for name, desc, prim in cases():
+        op = [o for o in desc.ops if o[0] in ("mesh", "sphere", "plane", "area_light")][prim]
+        v, n, ix = op[1], op[2], np.asarray(op[4], np.int32).reshape(-1, 3)
+        nv, nn, tris = len(v), len(n), len(ix) // 3
+        given, smooth = (desc.instantiate(ag.Scene(ctx)) for _ in range(2))
+        smooth.set_mesh_normals_mode(prim, "smooth")
+        dP = (np.random.default_rng(1).random((NORMALS_TARGETS, nv, 3), dtype=F) - F(0.5)) * F(0.004 * float((v.max(0) - v.min(0)).max()))
+        dN = (np.random.default_rng(2).random((NORMALS_TARGETS, nn, 3), dtype=F) - F(0.5)) * F(0.01)
+        given.set_mesh_morph_targets(prim, dP, dN)
+        smooth.set_mesh_morph_targets(prim, dP, None)
+        ws = [(0.1 * (1 + (k + np.arange(NORMALS_TARGETS)) % 5)).astype(F) for k in range(runs + 1)]
+        poses = [wobble(v, k) for k in range(2)]
+        pv = [ctx.alloc(12 * nv) for _ in poses]
+        for p, pose in zip(pv, poses):
+            ctx.upload(p, pose)
+        pn = ctx.alloc(12 * nn)
+        ctx.upload(pn, n)
+        ops = {"refit_device_pointer_given_normals": lambda k: given.update_mesh_device(prim, pv[k & 1], nv, pn, nn, "refit"),
+               "refit_device_pointer_smooth_null_normals": lambda k: smooth.update_mesh_device(prim, pv[k & 1], nv, None, nn, "refit"),
+               "refit_morph_%d_active_given_normal_deltas" % NORMALS_TARGETS: lambda k: given.morph_mesh(prim, ws[k]),
+               "refit_morph_%d_active_smooth_no_normal_deltas" % NORMALS_TARGETS: lambda k: smooth.morph_mesh(prim, ws[k])}
+        per_op = {k: [] for k in ops}
+        for _ in range(NORMALS_ROUNDS):       # the operations in turn, so that none has the GPU in a better hour
+            for name_op, fn in ops.items():
+                per_op[name_op].append(timed(fn, runs))
+        rows = {k: median_of_rounds(rs, runs) for k, rs in per_op.items()}
+        kernel_bytes = tris * (36 + 36 + 16) + nn * (8 + 12) + 3 * tris * (4 + 16)
+        rows["refit_device_pointer_given_normals"].update(pcie_up=0, pcie_down=36)
+        rows["refit_device_pointer_smooth_null_normals"].update(pcie_up=0, pcie_down=36, first_call_up=4 * (nn + 1 + 3 * tris), kernel_bytes=kernel_bytes)
+        for k in rows:
+            if "morph" in k:
+                rows[k].update(pcie_up=8 * NORMALS_TARGETS, pcie_down=36)
+        t0 = time.perf_counter()
+        for pose in poses:
+            ag.vertex_normals_arrays(pose, ix, nn)
+        rows["host_vertex_normals_arrays"] = {"mean_ms": round((time.perf_counter() - t0) * 1e3 / len(poses), 3), "runs": len(poses),
+                                              "what": "agpt_vertex_normals_arrays on the CPU, one thread; it builds the adjacency every call"}
+        for p in pv + [pn]:
+            ctx.free(p)
+        given.close()
+        smooth.close()
+        result["cases"][name] = {"triangles": tris, "vertices": nv, "normals": nn, "scene_triangles": desc.n_tris, "operations": rows}
+        for k, r in rows.items():
+            if "median_ms" in r:
+                print("%-16s %-48s median %9.3f ms  (%.3f .. %.3f)" % (name, k, r["median_ms"], r["min_ms"], r["max_ms"]), flush=True)
+            else:
+                print("%-16s %-48s mean   %9.3f ms" % (name, k, r["mean_ms"]), flush=True)
+    ctx.close()
+    return result
+
+
 def host_refit_only(runs):
     """the child of --parent-lib: the host-pointer REFIT alone, through whichever library AGPT_LIB_VARIANT names"""
     ctx = ag.Context(0)
@@ -317,15 +389,17 @@ def main():
     ap.add_argument("--parent-lib", default=None, metavar="TAG")
     ap.add_argument("--pose", action="store_true", help="time agpt_scene_pose_mesh (see above) instead of the update paths")
     ap.add_argument("--morph", action="store_true", help="time agpt_scene_morph_mesh (see above) instead of the update paths")
+    ap.add_argument("--normals", action="store_true", help="time the AGPT_NORMALS_SMOOTH mode (see above) instead of the update paths")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.runs < 7:
         ap.error("--runs: at least 7")
     if a.child:
         return host_refit_only(a.runs)
-    if a.pose or a.morph:
-        result = morph_leg(a.runs) if a.morph else pose_leg(a.runs)
-        with open(a.out or os.path.join(ROOT, "profiles", "mesh_morph_times.json" if a.morph else "mesh_pose_times.json"), "w") as f:
+    if a.pose or a.morph or a.normals:
+        result = normals_leg(a.runs) if a.normals else morph_leg(a.runs) if a.morph else pose_leg(a.runs)
+        default = "mesh_normals_times.json" if a.normals else "mesh_morph_times.json" if a.morph else "mesh_pose_times.json"
+        with open(a.out or os.path.join(ROOT, "profiles", default), "w") as f:
             json.dump(result, f, indent=1)
             f.write("\n")
         return

@@ -65,12 +65,22 @@ def render_sequence(a, ctx, scene, desc, W, H):
         cam_prev = cam
 
 
+def smooth_normals(a, scene, prim, op):
+    """--smooth-normals: the moving mesh in "smooth" normals mode -- every frame's update recomputes its vertex normals on the GPU from
+    the new positions (Scene.set_mesh_normals_mode) instead of turning, blending or keeping the rest normals"""
+    if a.smooth_normals:
+        if op[2] is None:
+            raise SystemExit("--smooth-normals: primitive %d has no normals to write into" % prim)
+        scene.set_mesh_normals_mode(prim, "smooth")
+
+
 def render_spin(a, ctx, scene, desc, W, H):
     """--spin: the scene's last mesh turned once about the vertical axis through its centre over N frames, each frame placed with
     Scene.transform_mesh (16 floats up, the mesh's records rewritten on the GPU) and rendered at --spp into OUT_0000.png ..."""
     meshes = [(k, op) for k, op in enumerate(o for o in desc.ops if o[0] in ("mesh", "sphere", "plane", "area_light")) if op[0] == "mesh"]
     prim, op = meshes[-1] if a.spin_prim is None else [m for m in meshes if m[0] == a.spin_prim][0]
     c = 0.5 * (op[1].min(0).astype(np.float64) + op[1].max(0))
+    smooth_normals(a, scene, prim, op)
     stem, ext = os.path.splitext(a.out)
     ptr = ctx.alloc(W * H * 16)
     for k in range(a.spin):
@@ -99,6 +109,7 @@ def render_bend(a, ctx, scene, desc, W, H):
     v, n = op[1], op[2]
     if n is not None and len(n) != len(v):
         raise SystemExit("--bend: the mesh has %d normals for %d vertices; its normals need influences of their own" % (len(n), len(v)))
+    smooth_normals(a, scene, prim, op)
     lo, hi = v.min(0).astype(np.float64), v.max(0).astype(np.float64)
     c = 0.5 * (lo + hi)
     t = (v[:, 0] - lo[0]) / max(hi[0] - lo[0], 1e-30)
@@ -125,10 +136,11 @@ def render_bend(a, ctx, scene, desc, W, H):
 
 def render_morph(a, ctx, scene, desc, W, H):
     """--morph: the scene's last mesh with two morph targets -- a swelling of its far half along x and a squash towards its middle height
-    (position deltas only: the normals keep their rest values) -- whose weights swing out of phase over N frames, each frame morphed
+    (position deltas only: the normals keep their rest values unless --smooth-normals recomputes them) -- whose weights swing out of phase over N frames, each frame morphed
     with Scene.morph_mesh (two weights up, the blend and the mesh's records on the GPU) and rendered at --spp into OUT_0000.png ..."""
     meshes = [(k, op) for k, op in enumerate(o for o in desc.ops if o[0] in ("mesh", "sphere", "plane", "area_light")) if op[0] == "mesh"]
     prim, op = meshes[-1]
+    smooth_normals(a, scene, prim, op)
     v = op[1].astype(np.float64)
     lo, hi = v.min(0), v.max(0)
     c = 0.5 * (lo + hi)
@@ -195,7 +207,12 @@ def main():
     ap.add_argument("--morph", type=int, default=0, metavar="N",
                     help="N frames at --spp each with the scene's last mesh (the blob of textured / mapped) morphed by two targets through "
                          "agpt_scene_set_mesh_morph_targets / agpt_scene_morph_mesh (OUT_0000.png ...)")
+    ap.add_argument("--smooth-normals", action="store_true",
+                    help="--spin, --bend, --morph: the moving mesh in AGPT_NORMALS_SMOOTH mode (agpt_scene_set_mesh_normals_mode): its vertex "
+                         "normals are recomputed on the GPU from every frame's positions")
     a = ap.parse_args()
+    if a.smooth_normals and not (a.spin or a.bend or a.morph):
+        ap.error("--smooth-normals applies to --spin, --bend and --morph")
     if (a.spin or a.bend or a.morph) and a.frames > 1 or (a.spin > 0) + (a.bend > 0) + (a.morph > 0) > 1:
         ap.error("--spin, --bend, --morph and --frames are separate sequences")
     if (a.temporal or a.orbit) and a.frames < 2:
