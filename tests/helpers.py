@@ -171,6 +171,20 @@ def build_cpp_example(tmp_path, name, wall=True):
     return exe
 
 
+FAKE_RCCL_SOURCE = os.path.join(ROOT, "tests", "fake_rccl", "fake_rccl.cpp")
+
+
+def build_fake_rccl(tmp_path):
+    """tests/fake_rccl/fake_rccl.cpp -- the stand-in transport of test_gpu_fake_rccl_gather.py -- as a shared object in tmp_path whose SONAME is
+    librccl.so.1, against the headers and the HIP runtime of the ROCm that hipcc belongs to; the file.  It is loaded by this path only."""
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))))
+    out = str(tmp_path / "libfake_rccl.so")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-O1", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
+                           "-I" + os.path.join(rocm, "include"), FAKE_RCCL_SOURCE, "-o", out, "-Wl,-soname,librccl.so.1",
+                           "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(rocm, "lib")])
+    return out
+
+
 def struct_layout(tmp_path, structs):
     """{C struct name: ctypes class}: sizeof and every offsetof, printed by a C probe compiled against include/agpt.h, are the class's"""
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "agpt.h"', "int main(void) {"]

@@ -1,6 +1,7 @@
 """Multi-GPU sharding logic on the CPU: partition properties of the row-block interleave, and a world_size-2 gloo run
 of the exact gather/de-interleave path bench.py uses (with the CPU oracle standing in for the per-rank renderer,
-so the check needs no GPU): the gathered image must be bit-identical to a single-process render."""
+so the check needs no GPU): the gathered image must be bit-identical to a single-process render.  The library's own multi-rank
+gather (agpt_gather_tiles with world > 1) runs on one GPU over a stand-in transport in test_gpu_fake_rccl_gather.py."""
 import os
 import socket
 import sys
@@ -100,7 +101,8 @@ def test_gpu_gather_tiles_c_abi():
     """agpt_gather_tiles / agpt_deinterleave_tiles (include/agpt.h): the compact per-rank buffers that agpt_render's row
     interleave fills come back as the full Accumulator::pixels image.  One GPU: the three shares of a world-3 split are
     rendered one after the other and de-interleaved by the library's kernel; the world-1 gather runs through
-    agpt_gather_tiles itself (no RCCL involved).  The RCCL send/recv path needs one GPU per rank and is NOT exercised here."""
+    agpt_gather_tiles itself (no RCCL involved).  The world > 1 path of agpt_gather_tiles -- grouped send / recv into the staging buffer,
+    then this kernel -- runs in test_gpu_fake_rccl_gather.py over a stand-in transport; RCCL's own transfer needs one GPU per rank."""
     import ag_pathtracer_amd as ag
     from ag_pathtracer_amd import tiles
     from helpers import gpu_context, gpu_scene
