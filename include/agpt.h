@@ -621,8 +621,10 @@ int agpt_render_features(agpt_scene*, const agpt_render_params* rp, float* albed
  * accum_dev / moment2_dev are agpt_render_adaptive's (the count in accum.w); a UNIFORM render for denoising is agpt_render_adaptive
  * with rel_error <= 0 and min_spp = max_spp.  All buffers cover the full film, pitch = width, Accumulator::pixels order.
  * Everything is fp32, every operation rounded on its own, divisions and square roots IEEE; luminance(c) = 0.212671 r + 0.715160 g +
- * 0.072169 b summed left to right; expc(x) = (float)exp((double)x), the correctly rounded value through fp64.
- *   Prepare, per pixel:  n = accum.w.  n == 0: the pixel is EXCLUDED (weight 0 as a tap, output rgb 0).  Otherwise
+ * 0.072169 b summed left to right; expc(x) = (float)exp((double)x), the correctly rounded value through fp64; every max(a, b) is
+ * fmaxf: a NaN operand yields the other one.  Subnormal values are kept, not flushed.
+ *   Prepare, per pixel:  n = accum.w.  Unless n > 0 (0, -0, a negative or a NaN count) the pixel is EXCLUDED (weight 0 as a tap,
+ *       output rgb 0).  Otherwise (n need not be an integer: agpt_temporal_accumulate hands over effective counts)
  *       c = accum.rgb / n;   v = 0 for n < 2, else with mu = luminance(accum.rgb) / n:
  *       v = max(0, moment2 / n - mu * mu) * n / (n - 1) / n        (the variance of the mean luminance, agpt_render_adaptive's estimate)
  *       with demodulate:  a = max(albedo.rgb, 1e-3) per channel,  c = c / a,  v = v / (luminance(a) * luminance(a))
@@ -637,6 +639,11 @@ int agpt_render_features(agpt_scene*, const agpt_render_params* rp, float* albed
  *           sw += w;  sc += w * c_q (per channel);  sv += (w * w) * v_q             (in tap order; the centre tap has w = h)
  *       c' = sc / sw,  v' = sv / (sw * sw)
  *   Finish (in the last pass): rgb = c' * a with demodulate, else c';  out.w = 1.
+ * Non-finite inputs: a NaN albedo channel is the floor 1e-3 and a NaN moment2 a variance of 0 (fmaxf).  A NaN t_p also floors ez's
+ * denominator, but ez's numerator is NaN with it.  The filter does not contain non-finite radiance: an Inf or NaN accum.rgb, or a NaN
+ * t, makes w * c_q NaN (0 * Inf included) for every pixel of the same flag that taps the pixel, and each pass carries that on, so after
+ * k iterations the pixels within 2 * (2^k - 1) of it in x and in y may be NaN, and none farther.  Hosts clamp or drop non-finite
+ * samples before denoising.
  * out_dev: DEVICE float4, rgb = the denoised MEAN radiance, w = 1 -- agpt_resolve(out, n, 1) and agpt_resolve_counts(out, n) both
  * display it.  It must not alias an input; the inputs are not written.  The one ping-pong scratch buffer is the context's
  * (allocated on first use, released by agpt_destroy).  No atomics and a fixed order: repeated calls are bit-identical.  Enqueued

@@ -155,6 +155,17 @@ def compare_with_model(out, model, what):
     assert (err <= bound).all(), (what, err.max(), np.argwhere(err > bound)[:8])
 
 
+def denoise_edge(out, model, what):
+    """the denoiser against tests/denoise_model.py on a synthetic film (tests/denoise_cases.py): no pixel may differ.  The figures
+    compare_with_model would judge by are printed first."""
+    differ = (out != model).any(-1)
+    err = np.abs(out.astype(np.float64) - model.astype(np.float64))
+    bound = 2.0 ** -18 * np.abs(model.astype(np.float64)) + 1e-7
+    print("%s: %d of %d pixels differ from the model, max abs difference %.3g, %d channels beyond rel 2^-18"
+          % (what, int(differ.sum()), differ.size, err.max(), int((err > bound).sum())))
+    assert out.tobytes() == model.tobytes(), (what, np.argwhere(differ)[:8])
+
+
 def tile_rows(acc, H, tile):
     """the rgb rows [h, w, 3] of tile (x0, y0, w, h) in an accumulator of height H (row 0 = top)"""
     x0, y0, w, h = tile
