@@ -40,7 +40,8 @@ EXPORTS = [
     "agpt_scene_add_plane", "agpt_scene_add_area_light", "agpt_scene_add_uniform_infinite_light", "agpt_scene_add_infinite_area_light",
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_morph_arrays", "agpt_scene_set_mesh_morph_targets", "agpt_scene_morph_mesh", "agpt_vertex_normals_arrays", "agpt_scene_set_mesh_normals_mode", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
-    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate", "agpt_li_batch", "agpt_resolve",
+    "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate",
+    "agpt_scene_snapshot_positions", "agpt_render_features_motion", "agpt_temporal_accumulate_motion", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -218,6 +219,10 @@ def lib():
     L.agpt_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
     L.agpt_camera_vectors.argtypes = [C.POINTER(CameraDesc), fp]
     L.agpt_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalParams)] + [vp] * 10
+    if not variant or hasattr(L, "agpt_scene_snapshot_positions"):   # (an A/B variant built from an older commit lacks them)
+        L.agpt_scene_snapshot_positions.argtypes = [vp]
+        L.agpt_render_features_motion.argtypes = [vp, C.POINTER(RenderParams), vp, vp, vp]
+        L.agpt_temporal_accumulate_motion.argtypes = [vp, C.POINTER(TemporalParams)] + [vp] * 11
     L.agpt_li_batch.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), C.POINTER(Stats)]
     L.agpt_resolve.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -607,11 +612,22 @@ class Context:
                                                 albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out)]),
                "agpt_temporal_accumulate")
 
+    def temporal_accumulate_motion(self, params, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
+                                   albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur):
+        """agpt_temporal_accumulate_motion: temporal_accumulate, reprojecting for every pixel whose prev_point_cur.w is 1 the point
+        PathTracer.render_features_motion wrote there (where the surface was) instead of the point it sees now.  All DEVICE pointers,
+        full film."""
+        _check(self.L.agpt_temporal_accumulate_motion(self.h, C.byref(params), *[C.c_void_p(int(p)) if p else None for p in
+                                                      (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
+                                                       albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur)]),
+               "agpt_temporal_accumulate_motion")
+
     def temporal_to_host(self, cam_cur, cam_prev, accum, moment2, albedo, normal_depth, prev=None, max_history=32.0,
-                         depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS):
+                         depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS, prev_point=None):
         """Convenience for tests and tools: uploads this frame's host buffers ([H,W,4], [H,W], [H,W,4], [H,W,4]) and, unless prev is
         None (first frame), prev = (hist_accum, hist_moment2, albedo, normal_depth) of the previous frame; runs temporal_accumulate;
-        returns (hist_accum[H,W,4], hist_moment2[H,W]).  cam_cur / cam_prev: CameraDesc or the argument tuple of Scene.set_camera."""
+        returns (hist_accum[H,W,4], hist_moment2[H,W]).  cam_cur / cam_prev: CameraDesc or the argument tuple of Scene.set_camera.
+        prev_point ([H,W,4], render_features_motion's third buffer): temporal_accumulate_motion runs instead."""
         H, W = np.shape(moment2)
         cams = [c if isinstance(c, CameraDesc) else camera_desc(*c) for c in (cam_cur, cam_prev)]
         host = [np.ascontiguousarray(a, np.float32) for a in (accum, moment2, albedo, normal_depth) + (tuple(prev) if prev is not None else ())]
@@ -624,8 +640,15 @@ class Context:
                 ptrs += [0, 0, 0, 0]
             ptrs.append(self.alloc(W * H * 16))
             ptrs.append(self.alloc(W * H * 4))
-            self.temporal_accumulate(TemporalParams(W, H, cams[0], cams[1], max_history, depth_tol, normal_cos), *ptrs)
-            return self.download(ptrs[-2], (H, W, 4)), self.download(ptrs[-1], (H, W))
+            params = TemporalParams(W, H, cams[0], cams[1], max_history, depth_tol, normal_cos)
+            if prev_point is None:
+                self.temporal_accumulate(params, *ptrs)
+                return self.download(ptrs[-2], (H, W, 4)), self.download(ptrs[-1], (H, W))
+            m = np.ascontiguousarray(prev_point, np.float32)
+            ptrs.append(self.alloc(m.nbytes))
+            self.upload(ptrs[-1], m)
+            self.temporal_accumulate_motion(params, *ptrs)
+            return self.download(ptrs[-3], (H, W, 4)), self.download(ptrs[-2], (H, W))
         finally:
             for p in ptrs:
                 if p:
@@ -852,6 +875,11 @@ class Scene:
             mode = NORMALS_GIVEN if mode == "given" else NORMALS_SMOOTH
         _check(self.L.agpt_scene_set_mesh_normals_mode(self.h, int(prim), int(mode)), "agpt_scene_set_mesh_normals_mode")
         (self._smooth.add if int(mode) == NORMALS_SMOOTH else self._smooth.discard)(int(prim))
+
+    def snapshot_positions(self):
+        """agpt_scene_snapshot_positions: once per frame, after the frame's mesh updates and before render_features_motion -- the
+        scene's newer generation of triangle positions becomes the older one and the newer one is filled from the device."""
+        _check(self.L.agpt_scene_snapshot_positions(self.h), "agpt_scene_snapshot_positions")
 
     def set_bvh_builder(self, builder):
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""
@@ -1100,6 +1128,32 @@ class PathTracer:
                 ctx.free(pn)
         finally:
             ctx.free(pa)
+
+    def render_features_motion(self, scene, W, H, albedo_ptr, normal_depth_ptr, prev_point_ptr, tile=None, accum_pitch=None, accum_row0=0):
+        """agpt_render_features_motion: render_features plus, from the same hits, prev_point_ptr (DEVICE float4, indexed like the other
+        two) = (where the hit surface point was at the scene's older position snapshot, w): w 0 a miss, 2 not moved, 1 moved.  Needs
+        scene.snapshot_positions() first."""
+        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
+        rp = RenderParams(W, H, x0, y0, w, h, 0, 0, 0, self.MaxDepth, accum_pitch if accum_pitch is not None else W, accum_row0,
+                          0, 0, 0, 0, 0, 0, 0)
+        _check(scene.L.agpt_render_features_motion(scene.h, C.byref(rp), *[C.c_void_p(int(p)) if p else None for p in
+                                                                           (albedo_ptr, normal_depth_ptr, prev_point_ptr)]),
+               "agpt_render_features_motion")
+
+    def render_features_motion_to_host(self, scene, W, H, **kw):
+        """Convenience for tests and tools: render_features_motion into zeroed full-film buffers, returns (albedo[H,W,4],
+        normal_depth[H,W,4], prev_point[H,W,4])."""
+        ctx = scene.ctx
+        ptrs = []
+        try:
+            for _ in range(3):
+                ptrs.append(ctx.alloc(W * H * 16))
+                ctx.memset(ptrs[-1], 0, W * H * 16)
+            self.render_features_motion(scene, W, H, *ptrs, **kw)
+            return tuple(ctx.download(p, (H, W, 4)) for p in ptrs)
+        finally:
+            for p in ptrs:
+                ctx.free(p)
 
     def Li(self, scene, rays, rng_states):
         """Integrator::Li (integrator.h:28-31, 120-191) for a batch of rays (RAY_DTYPE) with one xorshift32 state each:

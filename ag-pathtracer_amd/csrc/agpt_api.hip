@@ -15,6 +15,7 @@
 #include "agpt_denoise.h"
 #include "agpt_internal.h"
 #include "agpt_kernels.h"
+#include "agpt_motion.h"
 
 namespace agpt {
 
@@ -792,22 +793,32 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
 }
 
 // One closest-hit query per tile pixel through the pixel centre (k_feature_rays -> the trace launch of agpt_intersect_device), then
-// k_features: material colour + flag and shading normal + t.
-int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev) {
-    if (!rp) return fail(AGPT_ERR_INVALID, "agpt_render_features: NULL argument");
+// k_features: material colour + flag and shading normal + t.  motion (agpt_render_features_motion, `fn` names the entry point that was
+// called): k_motion then reads the same hits and rays into prev_point_dev.
+static int render_features(const char* fn, bool motion, agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev,
+                           float* prev_point_dev) {
+    const std::string f(fn);
+    if (!rp) return fail(AGPT_ERR_INVALID, f + ": NULL argument");
     if (rp->spp_begin != 0 || rp->spp_count != 0)
-        return fail(AGPT_ERR_INVALID, "agpt_render_features: spp_begin and spp_count must be 0 (one unjittered ray per pixel)");
+        return fail(AGPT_ERR_INVALID, f + ": spp_begin and spp_count must be 0 (one unjittered ray per pixel)");
     if (rp->interleave_block != 0 || rp->interleave_world != 0 || rp->interleave_rank != 0)
-        return fail(AGPT_ERR_INVALID, "agpt_render_features: the interleave fields must be 0");
-    if (!s || !albedo_dev || !normal_depth_dev) return fail(AGPT_ERR_INVALID, "agpt_render_features: NULL argument");
-    if (!s->committed || !s->has_camera) return fail(AGPT_ERR_INVALID, "agpt_render_features: scene not committed or camera not set");
+        return fail(AGPT_ERR_INVALID, f + ": the interleave fields must be 0");
+    if (!s || !albedo_dev || !normal_depth_dev) return fail(AGPT_ERR_INVALID, f + ": NULL argument");
+    if (!s->committed || !s->has_camera) return fail(AGPT_ERR_INVALID, f + ": scene not committed or camera not set");
     int rc;
-    if ((rc = check_tile("agpt_render_features", rp))) return rc;
-    if (albedo_dev == normal_depth_dev) return fail(AGPT_ERR_INVALID, "agpt_render_features: the two outputs are one buffer");
+    if ((rc = check_tile(fn, rp))) return rc;
+    if (albedo_dev == normal_depth_dev) return fail(AGPT_ERR_INVALID, f + ": the two outputs are one buffer");
+    if (motion) {
+        if (!prev_point_dev) return fail(AGPT_ERR_INVALID, f + ": NULL prev_point_dev");
+        if (prev_point_dev == albedo_dev || prev_point_dev == normal_depth_dev)
+            return fail(AGPT_ERR_INVALID, f + ": prev_point_dev aliases another output");
+        if (!s->snapshots.valid)
+            return fail(AGPT_ERR_INVALID, f + ": no position snapshot yet (agpt_scene_snapshot_positions comes first)");
+    }
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint64_t np64 = (uint64_t)rp->w * (uint64_t)rp->h;
-    if (np64 > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, "agpt_render_features: tile too large");
+    if (np64 > 0x7FFFFFFFull) return fail(AGPT_ERR_LIMIT, f + ": tile too large");
     const uint32_t NP = (uint32_t)np64;
     if ((rc = ensure_pool(c, (size_t)NP, s->dev.n_prims))) return rc;
     s->dev.cam = s->cam;
@@ -818,10 +829,23 @@ int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* alb
     trace_rays(c, s->dev, NP, false, 0);
     agpt::launch_features(c->stream, s->dev, s->shade_level, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
                           (float4*)normal_depth_dev);
+    if (motion) {
+        const agpt_scene::PositionSnapshots& ps = s->snapshots;
+        agpt::launch_motion(c->stream, rcn, c->hit.p, c->ext_o.p, c->ext_d.p, ps.gen[ps.newest ^ 1].p, ps.gen[ps.newest].p, (uint32_t)ps.n_tris,
+                            (float4*)prev_point_dev);
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(c->take_deferred());
     return AGPT_OK;
+}
+
+int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev) {
+    return render_features("agpt_render_features", false, s, rp, albedo_dev, normal_depth_dev, nullptr);
+}
+
+int agpt_render_features_motion(agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev, float* prev_point_dev) {
+    return render_features("agpt_render_features_motion", true, s, rp, albedo_dev, normal_depth_dev, prev_point_dev);
 }
 
 int agpt_li_batch(agpt_scene* s, const agpt_ray* rays, const uint32_t* rng_states, int n, int max_depth, float* radiance3_out,

@@ -36,6 +36,14 @@ int fail(int code, const std::string& msg);
 // film rows of the row blocks k with k % world == rank (blocks of `block` rows, the last one of a film may be shorter)
 int interleave_rows(int H, int block, int world, int rank);
 }  // namespace agpt
+struct TemporalConsts;
+struct agpt_ctx;
+namespace agpt {
+// (agpt_temporal.hip) agpt_temporal_accumulate's argument checks in the header's order under the name `fn`, then k_temporal's
+// constants and grid; in = the four current and the four prev buffers
+int temporal_prepare(const char* fn, agpt_ctx* c, const agpt_temporal_params* p, const float* const in[8], const float* hist_accum_out_dev,
+                     const float* hist_moment2_out_dev, TemporalConsts& tc, dim3& tiles);
+}  // namespace agpt
 
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
@@ -224,6 +232,22 @@ struct agpt_scene {
         ~MeshUpdate() { agpt::mesh_updater_destroy(updater); }
     };
     std::vector<MeshUpdate> updates;
+    // agpt_scene_snapshot_positions: two generations of world-space triangle positions, float4[3 * n_tris] each, indexed by the GLOBAL
+    // triangle id (not by BVH slot).  Allocated by the first snapshot; gen[newest] is the newer one.  agpt_scene_commit drops them; an
+    // AGPT_UPDATE_REBUILD, which re-commits with the triangle ids unchanged, keeps them (update_on_host).
+    struct PositionSnapshots {
+        DevBuf<float4> gen[2];
+        int newest = 0;
+        size_t n_tris = 0;
+        bool valid = false;
+        void drop() {
+            gen[0].release();
+            gen[1].release();
+            n_tris = 0;
+            valid = false;
+        }
+    };
+    PositionSnapshots snapshots;
 };
 
 template <class T>

@@ -1,0 +1,160 @@
+// agpt_motion.hip -- per-object motion vectors for the temporal reprojection (include/agpt.h): the kernels of
+// agpt_scene_snapshot_positions, agpt_render_features_motion (the entry point is in agpt_api.hip, beside agpt_render_features) and
+// agpt_temporal_accumulate_motion.
+//
+// k_snapshot_positions copies the world-space positions the update calls left in tri_verts (BVH slot order) into a buffer indexed by
+// the global triangle id, so two snapshots compare triangle by triangle whatever a rebuild did to the slot order.  k_motion turns a
+// feature-pass hit into the point the hit surface had in the older snapshot.  k_temporal_motion is k_temporal's body (agpt_temporal.h)
+// reprojecting that point.  One thread per item, fixed order, no atomics, no LDS: tests/motion_model.py reproduces each operation by
+// operation.  Compiled with the library's common flags (-ffp-contract=off, IEEE divide / sqrt).
+// All three are bandwidth kernels.  k_snapshot_positions: 48 B read contiguous per wave, 48 B written to 3 * gid -- scattered within
+// a mesh's range by its leaf order.  k_motion: per pixel 16 B of hit and 32 B of ray, contiguous, and on a mesh hit 2 x 48 B gathered at
+// the hit triangle (a wave's pixels share a few triangles), 16 B written.  k_temporal_motion: k_temporal plus 16 B per pixel.
+#include <hip/hip_runtime.h>
+
+#include "agpt_internal.h"
+#include "agpt_motion.h"
+#include "agpt_temporal.h"
+
+using agpt::fail;
+
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_snapshot_positions(const float4* __restrict__ tri_verts, uint32_t n_tris, float4* __restrict__ gen) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_tris) return;
+    float4 v0 = tri_verts[3 * (size_t)s], v1 = tri_verts[3 * (size_t)s + 1], v2 = tri_verts[3 * (size_t)s + 2];
+    const uint32_t gid = __float_as_uint(v0.w);
+    if (gid >= n_tris) return;   // (no record of a committed scene: pack_tri_verts writes ids below the triangle count)
+    v0.w = 0.f; v1.w = 0.f; v2.w = 0.f;
+    float4* out = gen + 3 * (size_t)gid;
+    out[0] = v0;
+    out[1] = v1;
+    out[2] = v2;
+}
+
+// prev_point = (p.xyz, w): w = 0 a miss (p = 0); w = 2 a surface that did not move between the two snapshots -- a sphere, a plane, a
+// triangle whose 36 position bytes are the same in both --, p = O + t * D; w = 1 a triangle that moved, p = its older positions at this
+// hit's barycentrics
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_motion(RenderConsts rc, const DevHit* __restrict__ hits, const float4* __restrict__ ray_o, const float4* __restrict__ ray_d,
+         const float4* __restrict__ gen_old, const float4* __restrict__ gen_new, uint32_t n_tris, float4* __restrict__ prev_point) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rc.NP) return;
+    int x, y;
+    size_t ai;
+    pixel_of(rc, i, x, y, ai);
+    const DevHit h = hits[i];
+    float4 m;
+    m.x = 0.f; m.y = 0.f; m.z = 0.f; m.w = 0.f;
+    if (h.id != AGPT_HIT_MISS) {
+        const float4 o4 = ray_o[i], d4 = ray_d[i];
+        const v3 O = V3(o4.x, o4.y, o4.z), D = V3(d4.x, d4.y, d4.z);
+        v3 p = O + h.t * D;
+        m.w = 2.f;
+        if (!(h.id & AGPT_HIT_SPHERE) && h.id < n_tris) {
+            const float4* a = gen_old + 3 * (size_t)h.id;
+            const float4* b = gen_new + 3 * (size_t)h.id;
+            const float4 a0 = a[0], a1 = a[1], a2 = a[2], b0 = b[0], b1 = b[1], b2 = b[2];
+            // the bytes, not the values: -0 against +0 counts as moved, a NaN against itself does not
+            const uint32_t differ = (__float_as_uint(a0.x) ^ __float_as_uint(b0.x)) | (__float_as_uint(a0.y) ^ __float_as_uint(b0.y)) |
+                                    (__float_as_uint(a0.z) ^ __float_as_uint(b0.z)) | (__float_as_uint(a1.x) ^ __float_as_uint(b1.x)) |
+                                    (__float_as_uint(a1.y) ^ __float_as_uint(b1.y)) | (__float_as_uint(a1.z) ^ __float_as_uint(b1.z)) |
+                                    (__float_as_uint(a2.x) ^ __float_as_uint(b2.x)) | (__float_as_uint(a2.y) ^ __float_as_uint(b2.y)) |
+                                    (__float_as_uint(a2.z) ^ __float_as_uint(b2.z));
+            if (differ) {
+                const float w0 = (1.f - h.b1) - h.b2;
+                p = (V3(a0.x, a0.y, a0.z) * w0 + V3(a1.x, a1.y, a1.z) * h.b1) + V3(a2.x, a2.y, a2.z) * h.b2;
+                m.w = 1.f;
+            }
+        }
+        m.x = p.x; m.y = p.y; m.z = p.z;
+    }
+    prev_point[ai] = m;
+}
+
+__global__ void __launch_bounds__(AGPT_BLOCK)
+k_temporal_motion(TemporalConsts tc, const float4* __restrict__ accum_cur, const float* __restrict__ moment2_cur,
+                  const float4* __restrict__ albedo_cur, const float4* __restrict__ normal_depth_cur, const float4* __restrict__ hist_accum_prev,
+                  const float* __restrict__ hist_moment2_prev, const float4* __restrict__ albedo_prev,
+                  const float4* __restrict__ normal_depth_prev, const float4* __restrict__ prev_point_cur, float4* __restrict__ hist_accum_out,
+                  float* __restrict__ hist_moment2_out) {
+    temporal_pixel<true>(tc, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev,
+                         normal_depth_prev, prev_point_cur, hist_accum_out, hist_moment2_out);
+}
+
+namespace agpt {
+
+void launch_snapshot_positions(hipStream_t stream, const float4* tri_verts, uint32_t n_tris, float4* gen) {
+    hipLaunchKernelGGL(k_snapshot_positions, agpt_blocks(n_tris), dim3(AGPT_BLOCK), 0, stream, tri_verts, n_tris, gen);
+}
+void launch_motion(hipStream_t stream, const RenderConsts& rc, const DevHit* hits, const float4* ray_o, const float4* ray_d,
+                   const float4* gen_old, const float4* gen_new, uint32_t n_tris, float4* prev_point) {
+    hipLaunchKernelGGL(k_motion, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, rc, hits, ray_o, ray_d, gen_old, gen_new, n_tris,
+                       prev_point);
+}
+
+}  // namespace agpt
+
+extern "C" {
+
+// The newer generation becomes the older one; the newer one is filled from what the update calls left in tri_verts.  The first call
+// allocates both and fills both with the same bytes.
+int agpt_scene_snapshot_positions(agpt_scene* s) {
+    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_snapshot_positions: NULL scene");
+    if (!s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_snapshot_positions: the scene is not committed");
+    size_t n_tris = 0;
+    for (const agpt::HostMesh& m : s->meshes) n_tris += m.prim_index.size();
+    agpt_scene::PositionSnapshots& ps = s->snapshots;
+    if (n_tris == 0) {   // nothing to hold: every hit of such a scene is a sphere, a plane or a miss
+        ps.valid = true;
+        return AGPT_OK;
+    }
+    if (3 * n_tris > s->d_tri_verts.n || n_tris > 0x7FFFFFFFull)
+        return fail(AGPT_ERR_DEVICE, "agpt_scene_snapshot_positions: the scene's triangle records do not cover its meshes");
+    agpt_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool first = !ps.valid;
+    if (first) {
+        if (ps.gen[0].alloc(3 * n_tris) != hipSuccess || ps.gen[1].alloc(3 * n_tris) != hipSuccess) {
+            ps.drop();
+            return fail(AGPT_ERR_NOMEM, "agpt_scene_snapshot_positions: out of device memory");
+        }
+        ps.n_tris = n_tris;
+        ps.newest = 0;
+    } else {
+        ps.newest ^= 1;
+    }
+    agpt::launch_snapshot_positions(c->stream, s->d_tri_verts.p, (uint32_t)n_tris, ps.gen[ps.newest].p);
+    HIP_TRY(hipGetLastError());
+    if (first)
+        HIP_TRY(hipMemcpyAsync(ps.gen[ps.newest ^ 1].p, ps.gen[ps.newest].p, 3 * n_tris * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    ps.valid = true;
+    return AGPT_OK;
+}
+
+// agpt_temporal_accumulate with step 3 decided per pixel by prev_point_cur: one k_temporal_motion launch
+int agpt_temporal_accumulate_motion(agpt_ctx* c, const agpt_temporal_params* p, const float* accum_cur_dev, const float* moment2_cur_dev,
+                                    const float* albedo_cur_dev, const float* normal_depth_cur_dev, const float* hist_accum_prev_dev,
+                                    const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
+                                    float* hist_accum_out_dev, float* hist_moment2_out_dev, const float* prev_point_cur_dev) {
+    const float* in[8] = {accum_cur_dev, moment2_cur_dev, albedo_cur_dev, normal_depth_cur_dev,
+                          hist_accum_prev_dev, hist_moment2_prev_dev, albedo_prev_dev, normal_depth_prev_dev};
+    TemporalConsts tc;
+    dim3 tiles;
+    if (const int rc = agpt::temporal_prepare("agpt_temporal_accumulate_motion", c, p, in, hist_accum_out_dev, hist_moment2_out_dev, tc, tiles))
+        return rc;
+    if (!prev_point_cur_dev) return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate_motion: NULL prev_point_cur_dev");
+    if (prev_point_cur_dev == hist_accum_out_dev || prev_point_cur_dev == hist_moment2_out_dev)
+        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate_motion: an output aliases prev_point_cur_dev");
+    HIP_TRY(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_temporal_motion, tiles, dim3(AGPT_BLOCK), 0, c->stream, tc, (const float4*)accum_cur_dev, moment2_cur_dev,
+                       (const float4*)albedo_cur_dev, (const float4*)normal_depth_cur_dev, (const float4*)hist_accum_prev_dev,
+                       hist_moment2_prev_dev, (const float4*)albedo_prev_dev, (const float4*)normal_depth_prev_dev,
+                       (const float4*)prev_point_cur_dev, (float4*)hist_accum_out_dev, hist_moment2_out_dev);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return AGPT_OK;
+}
+
+}  // extern "C"

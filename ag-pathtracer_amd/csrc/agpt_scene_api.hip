@@ -315,6 +315,7 @@ int agpt_scene_commit(agpt_scene* s) {
                 return fail(AGPT_ERR_INVALID, "agpt_scene_commit: a sphere or a plane has a material with a colour texture, a roughness / metallic map or a normal map "
                                               "(textures apply to triangle meshes only)");
     HIP_TRY(hipSetDevice(s->ctx->device));
+    s->snapshots.drop();   // agpt_scene_snapshot_positions: the triangle ids may change meaning (update_on_host puts them back)
     agpt::FlatScene flat;
     flat.want_tri_uv = textured;
     agpt::flatten_scene(s->meshes, s->spheres, s->prims, flat);
@@ -592,7 +593,12 @@ static int update_on_host(agpt_scene* s, size_t mi, const float* vertices, const
         agpt::mesh_updater_destroy(up.updater);
         up.updater = nullptr;
     }
-    return agpt_scene_commit(s);
+    // the commit below leaves every triangle its global id (same meshes, same index arrays): the position snapshots stay valid
+    agpt_scene::PositionSnapshots kept = std::move(s->snapshots);
+    s->snapshots = agpt_scene::PositionSnapshots();
+    const int rc = agpt_scene_commit(s);
+    if (rc == AGPT_OK) s->snapshots = std::move(kept);
+    return rc;
 }
 
 static bool smooth_normals(const agpt_scene* s, size_t mi) { return s->updates[mi].normals_mode == AGPT_NORMALS_SMOOTH; }

@@ -312,8 +312,8 @@ int agpt_scene_update_mesh(agpt_scene*, int prim, const float* vertices, int n_v
  * Returns AGPT_ERR_INVALID (+ agpt_last_error) for the same conditions in the same order as agpt_scene_update_mesh (NULL scene or
  * NULL vertices_dev; not committed; not a mesh; counts; unknown mode); a refused call changes nothing.  A pointer that is not
  * device memory is not detected: the copy fails with AGPT_ERR_DEVICE or faults.
- * Not covered: index or texture-coordinate changes, spheres, planes and lights, per-object motion vectors (agpt_temporal_accumulate
- * still sees moved geometry only through its depth / normal tests), fewer launches per tree level. */
+ * Not covered: index or texture-coordinate changes, spheres, planes and lights, fewer launches per tree level.  (Temporal history
+ * follows the moved meshes through agpt_scene_snapshot_positions and agpt_temporal_accumulate_motion.) */
 int agpt_scene_update_mesh_device(agpt_scene*, int prim, const float* vertices_dev, int n_vertices, const float* normals_dev, int n_normals,
                                   int mode);
 /* The reference's mat4 applied to a mesh's arrays, host-only like agpt_bvh_build (no GPU, no context).  transform16 is a row-major
@@ -384,8 +384,8 @@ int agpt_scene_set_mesh_skin(agpt_scene*, int prim, int influences, int n_joints
  * scene; not committed; not a mesh; unknown mode); a mesh without a skin; NULL joints16; an n_joints that is not the binding's; a
  * non-finite entry; a last row that is not exactly (0, 0, 0, 1); a joint whose determinant (agpt_transform_arrays' value) is exactly
  * 0, named in the message.  A refused call changes nothing.
- * Out of scope: sparse morph targets, tangent deltas, weights or joint matrices given in device memory, dual-quaternion blending,
- * motion vectors (and what agpt_scene_update_mesh_device does not cover).  Morph targets: agpt_scene_morph_mesh.  Normals recomputed from
+ * Out of scope: sparse morph targets, tangent deltas, weights or joint matrices given in device memory, dual-quaternion blending
+ * (and what agpt_scene_update_mesh_device does not cover).  Morph targets: agpt_scene_morph_mesh.  Normals recomputed from
  * the posed positions: agpt_scene_set_mesh_normals_mode. */
 int agpt_scene_pose_mesh(agpt_scene*, int prim, const float* joints16, int n_joints, int mode);
 /* Morph targets (blend shapes) applied to a mesh's arrays, host-only like agpt_skin_arrays (no GPU, no context): fp32, every operation
@@ -436,7 +436,7 @@ int agpt_scene_set_mesh_morph_targets(agpt_scene*, int prim, int n_targets, cons
  * targets were set with; a weight that is not finite; then, with joints16, agpt_scene_pose_mesh's remaining checks in its order (a mesh
  * without a skin; n_joints; a non-finite entry; a last row; a singular joint).  A refused call changes nothing.
  * Out of scope: sparse targets (a delta for every item of every target is stored), tangent deltas, weights or joint matrices given in
- * device memory, motion vectors (and what agpt_scene_update_mesh_device does not cover).  Normals recomputed from the morphed
+ * device memory (and what agpt_scene_update_mesh_device does not cover).  Normals recomputed from the morphed
  * positions (glTF's advice for targets without normal deltas): agpt_scene_set_mesh_normals_mode. */
 int agpt_scene_morph_mesh(agpt_scene*, int prim, const float* weights, int n_targets, const float* joints16, int n_joints, int mode);
 /* Smooth vertex normals from positions and topology, host-only like agpt_morph_arrays (no GPU, no context): fp32, every operation
@@ -481,7 +481,7 @@ int agpt_vertex_normals_arrays(const float* vertices, int n_vertices, const int3
  * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order: NULL scene; a prim that is not a mesh of the scene; an unknown
  * mode; SMOOTH for a mesh without normals (the counts cannot change, so there is nothing to write into).
  * Limit: a normal item of very high valence is summed by one lane.  Out of scope: angle-weighted or crease-angle normals, adding
- * normals to a mesh that has none, tangents, spheres, planes and lights, motion vectors. */
+ * normals to a mesh that has none, tangents, spheres, planes and lights. */
 enum { AGPT_NORMALS_GIVEN = 0, AGPT_NORMALS_SMOOTH = 1 };
 int agpt_scene_set_mesh_normals_mode(agpt_scene*, int prim, int mode);
 /* Which builder agpt_scene_add_mesh uses for the BVH of later meshes on this scene (default HOST).  Both produce the same
@@ -703,9 +703,10 @@ int agpt_camera_vectors(const agpt_camera_desc*, float out22[22]);
  * Returns AGPT_ERR_INVALID (+ agpt_last_error), checked in this order, for: NULL params; a bad film size (as agpt_denoise);
  * max_history not positive and finite; depth_tol negative or not finite; normal_cos outside [-1, 1] or NaN; a NULL context or a
  * NULL current or output pointer; prev pointers that are partly NULL; an output that aliases an input or the other output.
- * Not covered: per-object motion vectors -- moving geometry is handled only by the depth, normal and flag tests rejecting stale
- * history --; history behind specular bounces (a mirror image is reprojected as the mirror's surface); more than one GPU or
- * buffers that are not the full film; variance clamping; sub-pixel jitter. */
+ * Not covered: moving geometry -- here it is handled only by the depth, normal and flag tests rejecting stale history;
+ * agpt_temporal_accumulate_motion (below) follows meshes that the update calls moved --; history behind specular bounces (a mirror
+ * image is reprojected as the mirror's surface); more than one GPU or buffers that are not the full film; variance clamping;
+ * sub-pixel jitter. */
 typedef struct {
     int32_t width, height;            /* all buffers: full film, pitch = width, Accumulator::pixels order (row H-1-y) */
     agpt_camera_desc cam_cur, cam_prev;
@@ -720,6 +721,51 @@ int agpt_temporal_accumulate(agpt_ctx*, const agpt_temporal_params*,
         const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
         const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
         float* hist_accum_out_dev, float* hist_moment2_out_dev);
+
+/* ---- motion vectors: temporal history that follows moved meshes -------------------------------------------------------
+ * Step 3 above reprojects the point the pixel sees NOW; for a mesh that agpt_scene_update_mesh / _device, agpt_scene_transform_mesh,
+ * agpt_scene_pose_mesh or agpt_scene_morph_mesh moved since the previous frame that is the wrong place on the previous film.  The three
+ * calls below reproject where that surface point WAS instead.  Per frame:
+ *     update calls -> agpt_scene_snapshot_positions -> agpt_render_adaptive -> agpt_render_features_motion
+ *                  -> agpt_temporal_accumulate_motion -> agpt_denoise
+ *
+ * agpt_scene_snapshot_positions: once per frame, after that frame's mesh updates and before its feature pass.  The scene owns two
+ * generations of world-space triangle positions, float4[3 * T] each (T = the scene's triangles), indexed by the GLOBAL triangle id
+ * (meshes in the order they were added, each mesh's triangles in index-array order) and not by BVH slot, so an AGPT_UPDATE_REBUILD
+ * between two snapshots changes nothing.  The call makes the newer generation the older one and fills the newer one from the positions
+ * the update calls left on the device (every route: no updater knows about snapshots); the w lanes are 0.  The first call allocates
+ * both generations and leaves the same bytes in both: nothing has moved yet.  A scene that never calls this allocates and launches
+ * nothing.  T == 0 succeeds without a launch.  agpt_scene_commit (anything that re-commits the scene) drops both generations.
+ * AGPT_ERR_INVALID for a NULL or an uncommitted scene.  Enqueued on the context's stream behind the updates and synchronised. */
+int agpt_scene_snapshot_positions(agpt_scene*);
+
+/* agpt_render_features_motion: agpt_render_features -- the same ray, the same one trace launch, albedo and normal_depth byte for
+ * byte -- plus, from the same hit, prev_point_dev (DEVICE float4, indexed like the other two) = (p.xyz, w):
+ *     a miss                        (0, 0, 0, 0)
+ *     a sphere or a plane           p = O + t * D, w = 2                 (O, D: the pixel's ray; these are never moved)
+ *     a triangle with global id g   if its 36 position bytes are the same in the two generations: p = O + t * D, w = 2 (not moved);
+ *                                   otherwise w = 1 and, with v0, v1, v2 its positions in the OLDER generation and (b1, b2) the hit's
+ *                                   barycentrics, b0 = (1 - b1) - b2,  p = (v0 * b0 + v1 * b1) + v2 * b2 per component
+ * fp32, every operation rounded on its own, no fma.  The comparison is on bytes: -0 against +0 counts as moved (harmless: the point is
+ * the same).  rp and the argument checks as for agpt_render_features; then AGPT_ERR_INVALID for a NULL prev_point_dev, for
+ * prev_point_dev aliasing another output, and for a scene without a snapshot.  Synchronises with the context's stream. */
+int agpt_render_features_motion(agpt_scene*, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev, float* prev_point_dev);
+
+/* agpt_temporal_accumulate_motion: agpt_temporal_accumulate's contract with step 3 decided per pixel by m = prev_point_cur[i]
+ * (agpt_render_features_motion's output for this frame, full film):
+ *     m.w != 1 (a miss, static geometry, any other value, NaN): step 3 exactly as above, the same-camera-bytes shortcut included.
+ *     m.w == 1: no shortcut, even if the camera bytes are equal.  Q = m.xyz - P.origin, and from te = length(Q) on step 3 continues
+ *               as written (dw, k, R, s, t, sx, sy and the NO HISTORY exits); steps 4-6 unchanged.
+ * On the first frame (prev NULL) the outputs are the current values bit for bit and prev_point_cur is not read.  Where every w != 1
+ * the outputs are agpt_temporal_accumulate's, bit for bit.  Checks: agpt_temporal_accumulate's in their order, then a NULL
+ * prev_point_cur_dev, then an output aliasing it (AGPT_ERR_INVALID).
+ * Limits: the normal test still compares the current normal with the previous tap's, so a surface that turns by more than
+ * acos(normal_cos) within one frame is rejected; no motion vectors behind specular bounces and none for lights; nothing for a moved
+ * sphere or plane (the library moves none); one GPU, full film. */
+int agpt_temporal_accumulate_motion(agpt_ctx*, const agpt_temporal_params*,
+        const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
+        const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
+        float* hist_accum_out_dev, float* hist_moment2_out_dev, const float* prev_point_cur_dev);
 
 /* Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) of PathTracer (integrator.h:120-191) for n rays of the caller --
  * the single-ray entry the reference's split-screen compare (myapp.cpp:168) and mouse picking (myapp.cpp:197-201) use, batched.

@@ -152,6 +152,9 @@ enum class MeshUpdate { Refit = AGPT_UPDATE_REFIT, Rebuild = AGPT_UPDATE_REBUILD
 // agpt_scene_set_mesh_normals_mode: a mesh's normals come from the caller / its rest normals, or are recomputed from every update's positions
 enum class MeshNormals { Given = AGPT_NORMALS_GIVEN, Smooth = AGPT_NORMALS_SMOOTH };
 enum class ShadingArith { Exact = AGPT_SHADING_EXACT, Fast = AGPT_SHADING_FAST };
+// AdaptiveAccumulator::TemporalAccumulate: reproject the point a pixel sees now (agpt_temporal_accumulate), or where a moved mesh's
+// surface point was a frame ago (agpt_temporal_accumulate_motion, with the features of PathTracer::RenderFeaturesMotion)
+enum class Motion { Ignore, Follow };
 
 class Scene {
 public:
@@ -282,6 +285,9 @@ public:
         check(agpt_scene_set_mesh_normals_mode(h_, prim, (int)mode), "agpt_scene_set_mesh_normals_mode");
     }
     // camera moved (RotatingCamera::update): re-derive the camera only, geometry stays in HBM
+    // motion vectors (agpt_scene_snapshot_positions): once per frame, after the frame's UpdateMesh / TransformMesh / PoseMesh / MorphMesh
+    // calls and before PathTracer::RenderFeaturesMotion -- the scene keeps the triangle positions of this frame and of the one before
+    void SnapshotPositions() { check(agpt_scene_snapshot_positions(h_), "agpt_scene_snapshot_positions"); }
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }
     void Intersect(const agpt_ray* rays, int n, agpt_hit* hits) const {
         check(agpt_intersect_batch(h_, rays, n, hits, 0, nullptr), "agpt_intersect_batch");
@@ -396,6 +402,7 @@ public:
         check(agpt_device_alloc(ctx.handle(), (size_t)w * h * 16, &normal_depth_), "agpt_device_alloc");
     }
     ~FeatureBuffers() {
+        if (prev_point_) agpt_device_free(ctx_.handle(), prev_point_);
         agpt_device_free(ctx_.handle(), normal_depth_);
         agpt_device_free(ctx_.handle(), albedo_);
     }
@@ -403,8 +410,16 @@ public:
     FeatureBuffers& operator=(const FeatureBuffers&) = delete;
     float* device_albedo() const { return static_cast<float*>(albedo_); }
     float* device_normal_depth() const { return static_cast<float*>(normal_depth_); }
+    // prev_point of agpt_render_features_motion: (where the hit surface point was a frame ago, w: 0 miss / 1 moved / 2 not moved);
+    // allocated by the first call, null until PathTracer::RenderFeaturesMotion has filled it
+    float* device_prev_point() {
+        if (!prev_point_) check(agpt_device_alloc(ctx_.handle(), (size_t)width * height * 16, &prev_point_), "agpt_device_alloc");
+        return static_cast<float*>(prev_point_);
+    }
+    const float* prev_point_or_null() const { return static_cast<const float*>(prev_point_); }
     std::vector<float> DownloadAlbedo() const { return download(albedo_); }
     std::vector<float> DownloadNormalDepth() const { return download(normal_depth_); }
+    std::vector<float> DownloadPrevPoint() const { return prev_point_ ? download(prev_point_) : std::vector<float>(); }
     const int width, height;
 
 private:
@@ -416,6 +431,7 @@ private:
     Context& ctx_;
     void* albedo_ = nullptr;
     void* normal_depth_ = nullptr;
+    void* prev_point_ = nullptr;
 };
 
 // The buffers of an adaptive render (agpt_render_adaptive): the float4 sums with each pixel's own sample count in w, and the
@@ -474,7 +490,7 @@ public:
     void TemporalAccumulate(const FeatureBuffers& features, const agpt_camera_desc& cam_cur, const AdaptiveAccumulator* prev_history,
                             const FeatureBuffers* prev_features, const agpt_camera_desc& cam_prev, AdaptiveAccumulator& history_out,
                             float max_history = 32.f, float depth_tol = AGPT_TEMPORAL_DEPTH_TOL,
-                            float normal_cos = AGPT_TEMPORAL_NORMAL_COS) const {
+                            float normal_cos = AGPT_TEMPORAL_NORMAL_COS, Motion motion = Motion::Ignore) const {
         agpt_temporal_params p{};
         p.width = width;
         p.height = height;
@@ -483,11 +499,21 @@ public:
         p.max_history = max_history;
         p.depth_tol = depth_tol;
         p.normal_cos = normal_cos;
+        const float* hp = prev_history ? prev_history->device_pixels() : nullptr;
+        const float* hm = prev_history ? prev_history->device_moment2() : nullptr;
+        const float* pa = prev_features ? prev_features->device_albedo() : nullptr;
+        const float* pn = prev_features ? prev_features->device_normal_depth() : nullptr;
+        if (motion == Motion::Follow) {
+            // agpt_temporal_accumulate_motion: `features` were rendered by PathTracer::RenderFeaturesMotion, whose prev_point says per
+            // pixel where a moved mesh's surface point was a frame ago -- that point is reprojected instead of the one seen now
+            check(agpt_temporal_accumulate_motion(ctx_.handle(), &p, device_pixels(), device_moment2(), features.device_albedo(),
+                                                  features.device_normal_depth(), hp, hm, pa, pn, history_out.device_pixels(),
+                                                  history_out.device_moment2(), features.prev_point_or_null()),
+                  "agpt_temporal_accumulate_motion");
+            return;
+        }
         check(agpt_temporal_accumulate(ctx_.handle(), &p, device_pixels(), device_moment2(), features.device_albedo(),
-                                       features.device_normal_depth(), prev_history ? prev_history->device_pixels() : nullptr,
-                                       prev_history ? prev_history->device_moment2() : nullptr,
-                                       prev_features ? prev_features->device_albedo() : nullptr,
-                                       prev_features ? prev_features->device_normal_depth() : nullptr, history_out.device_pixels(),
+                                       features.device_normal_depth(), hp, hm, pa, pn, history_out.device_pixels(),
                                        history_out.device_moment2()),
               "agpt_temporal_accumulate");
     }
@@ -638,6 +664,17 @@ public:
         p.h = features.height;
         p.accum_pitch = features.width;
         check(agpt_render_features(scene.handle(), &p, features.device_albedo(), features.device_normal_depth()), "agpt_render_features");
+    }
+    // agpt_render_features_motion: RenderFeatures plus features.device_prev_point() from the same hits (Scene::SnapshotPositions first)
+    void RenderFeaturesMotion(Scene& scene, FeatureBuffers& features) const {
+        agpt_render_params p{};
+        p.width = features.width;
+        p.height = features.height;
+        p.w = features.width;
+        p.h = features.height;
+        p.accum_pitch = features.width;
+        check(agpt_render_features_motion(scene.handle(), &p, features.device_albedo(), features.device_normal_depth(), features.device_prev_point()),
+              "agpt_render_features_motion");
     }
     // Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) for n rays -- what MyApp::Tick calls per pixel (myapp.cpp:168)
     // and the mouse-pick overlay per click (myapp.cpp:197-201).  rng[i] is the RandomFloat() state path i starts from and receives

@@ -5,6 +5,7 @@
     python tools/render.py --scene c3 --width 960 --height 540 --spp 64 --out gpurun_out/c3.png
     python tools/render.py --scene c3 --spp 4 --frames 8 --orbit 8 --temporal --out out/orbit.png   (out/orbit_0000.png ...)
     python tools/render.py --scene textured --spp 16 --spin 12 --out out/spin.png                  (out/spin_0000.png ...)
+    python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --out out/spin.png
 """
 import argparse
 import os
@@ -65,6 +66,60 @@ def render_sequence(a, ctx, scene, desc, W, H):
         cam_prev = cam
 
 
+def sequence_frames(a, n):
+    """--spin / --bend / --morph N: all N frames of the cycle, or with --frames F its first F"""
+    return min(n, a.frames) if a.frames > 1 else n
+
+
+class FrameDrawer:
+    """One frame of --spin / --bend / --morph after the frame's mesh update: --spp samples, resolved and written to OUT_kkkk.png.
+    With --temporal the frame goes through the loop of render_sequence instead (uniform samples, features, the reprojected history
+    of the frame before, the denoiser) under the scene's static camera; with --motion the history follows the moved mesh: a position
+    snapshot behind the update, then agpt_render_features_motion and agpt_temporal_accumulate_motion.  The mean effective sample count
+    over the moving mesh's pixels (prev_point.w == 1; the snapshot and prev_point are taken without --motion too, for this figure alone)
+    is printed per frame."""
+
+    def __init__(self, a, ctx, scene, desc, W, H):
+        self.a, self.ctx, self.scene, self.W, self.H = a, ctx, scene, W, H
+        self.stem, self.ext = os.path.splitext(a.out)
+        self.cam = ag.camera_desc(*desc.camera)
+        n16, n4 = W * H * 16, W * H * 4
+        self.acc = ctx.alloc(n16)
+        if a.temporal:
+            self.m2, self.out, self.point = ctx.alloc(n4), ctx.alloc(n16), ctx.alloc(n16)
+            self.sets = [(ctx.alloc(n16), ctx.alloc(n4), ctx.alloc(n16), ctx.alloc(n16)) for _ in range(2)]
+
+    def __call__(self, k):
+        """-> (path, a note for the frame's line)"""
+        a, ctx, scene, W, H = self.a, self.ctx, self.scene, self.W, self.H
+        path = "%s_%04d%s" % (self.stem, k, self.ext)
+        pt = ag.PathTracer(5)
+        ctx.memset(self.acc, 0, W * H * 16)
+        if not a.temporal:
+            pt.render(scene, W, H, a.spp, self.acc)
+            ag.binding.write_png(path, ctx.resolve(self.acc, W * H, a.spp), W, H)
+            return path, ""
+        spp = max(2, a.spp)
+        cur, prev = self.sets[k & 1], self.sets[(k & 1) ^ 1]
+        scene.snapshot_positions()
+        ctx.memset(self.m2, 0, W * H * 4)
+        pt.render_adaptive(scene, W, H, self.acc, self.m2, spp, spp, spp, 0.0, seed_base=k)
+        pt.render_features_motion(scene, W, H, cur[2], cur[3], self.point)
+        params = ag.TemporalParams(W, H, self.cam, self.cam, a.max_history, ag.TEMPORAL_DEPTH_TOL, ag.TEMPORAL_NORMAL_COS)
+        buffers = (self.acc, self.m2, cur[2], cur[3]) + (prev if k else (0, 0, 0, 0)) + (cur[0], cur[1])
+        if a.motion:
+            ctx.temporal_accumulate_motion(params, *buffers, self.point)
+        else:
+            ctx.temporal_accumulate(params, *buffers)
+        ctx.denoise(ag.DenoiseParams(W, H, a.denoise if a.denoise is not None else 5, 1, ag.DENOISE_SIGMA_Z, ag.DENOISE_SIGMA_N,
+                                     ag.DENOISE_SIGMA_L), cur[0], cur[1], cur[2], cur[3], self.out)
+        ag.binding.write_png(path, ctx.resolve_counts(self.out, W * H), W, H)
+        moving = ctx.download(self.point, (H, W, 4))[..., 3] == 1
+        counts = ctx.download(cur[0], (H, W, 4))[..., 3]
+        note = ", %d moving pixels with %.2f effective samples on average" % (moving.sum(), counts[moving].mean()) if moving.any() else ""
+        return path, " + history%s%s" % (" with motion vectors" if a.motion else "", note)
+
+
 def smooth_normals(a, scene, prim, op):
     """--smooth-normals: the moving mesh in "smooth" normals mode -- every frame's update recomputes its vertex normals on the GPU from
     the new positions (Scene.set_mesh_normals_mode) instead of turning, blending or keeping the rest normals"""
@@ -81,9 +136,8 @@ def render_spin(a, ctx, scene, desc, W, H):
     prim, op = meshes[-1] if a.spin_prim is None else [m for m in meshes if m[0] == a.spin_prim][0]
     c = 0.5 * (op[1].min(0).astype(np.float64) + op[1].max(0))
     smooth_normals(a, scene, prim, op)
-    stem, ext = os.path.splitext(a.out)
-    ptr = ctx.alloc(W * H * 16)
-    for k in range(a.spin):
+    draw = FrameDrawer(a, ctx, scene, desc, W, H)
+    for k in range(sequence_frames(a, a.spin)):
         ang = 2 * np.pi * k / a.spin
         m = np.eye(4)
         m[0, 0], m[0, 2], m[2, 0], m[2, 2] = np.cos(ang), np.sin(ang), -np.sin(ang), np.cos(ang)
@@ -91,13 +145,9 @@ def render_spin(a, ctx, scene, desc, W, H):
         t0 = time.time()
         scene.transform_mesh(prim, m.astype(np.float32))
         t1 = time.time()
-        ctx.memset(ptr, 0, W * H * 16)
-        ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
-        path = "%s_%04d%s" % (stem, k, ext)
-        ag.binding.write_png(path, ctx.resolve(ptr, W * H, a.spp), W, H)
-        print("frame %d: primitive %d turned %.0f degrees in %.2f ms, %d spp in %.1f ms -> %s" %
-              (k, prim, np.degrees(ang), (t1 - t0) * 1e3, a.spp, (time.time() - t1) * 1e3, path))
-    ctx.free(ptr)
+        path, note = draw(k)
+        print("frame %d: primitive %d turned %.0f degrees in %.2f ms, %d spp%s in %.1f ms -> %s" %
+              (k, prim, np.degrees(ang), (t1 - t0) * 1e3, a.spp, note, (time.time() - t1) * 1e3, path))
 
 
 def render_bend(a, ctx, scene, desc, W, H):
@@ -115,9 +165,8 @@ def render_bend(a, ctx, scene, desc, W, H):
     t = (v[:, 0] - lo[0]) / max(hi[0] - lo[0], 1e-30)
     t = (t * t * (3 - 2 * t)).astype(np.float32)
     scene.set_mesh_skin(prim, np.tile(np.array([0, 1], np.int32), (len(v), 1)), np.stack([np.float32(1) - t, t], 1), n_joints=2)
-    stem, ext = os.path.splitext(a.out)
-    ptr = ctx.alloc(W * H * 16)
-    for k in range(a.bend):
+    draw = FrameDrawer(a, ctx, scene, desc, W, H)
+    for k in range(sequence_frames(a, a.bend)):
         ang = np.radians(50.0) * np.sin(2 * np.pi * k / a.bend)
         m = np.eye(4)
         m[0, 0], m[0, 1], m[1, 0], m[1, 1] = np.cos(ang), -np.sin(ang), np.sin(ang), np.cos(ang)
@@ -125,13 +174,9 @@ def render_bend(a, ctx, scene, desc, W, H):
         t0 = time.time()
         scene.pose_mesh(prim, np.stack([np.eye(4), m]).astype(np.float32))
         t1 = time.time()
-        ctx.memset(ptr, 0, W * H * 16)
-        ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
-        path = "%s_%04d%s" % (stem, k, ext)
-        ag.binding.write_png(path, ctx.resolve(ptr, W * H, a.spp), W, H)
-        print("frame %d: primitive %d bent %.0f degrees in %.2f ms, %d spp in %.1f ms -> %s" %
-              (k, prim, np.degrees(ang), (t1 - t0) * 1e3, a.spp, (time.time() - t1) * 1e3, path))
-    ctx.free(ptr)
+        path, note = draw(k)
+        print("frame %d: primitive %d bent %.0f degrees in %.2f ms, %d spp%s in %.1f ms -> %s" %
+              (k, prim, np.degrees(ang), (t1 - t0) * 1e3, a.spp, note, (time.time() - t1) * 1e3, path))
 
 
 def render_morph(a, ctx, scene, desc, W, H):
@@ -148,20 +193,15 @@ def render_morph(a, ctx, scene, desc, W, H):
     swell = 0.6 * (t * t * (3 - 2 * t))[:, None] * (v - c) * [0, 1, 1]
     squash = -0.5 * (v - c) * [0, 1, 0]
     scene.set_mesh_morph_targets(prim, np.stack([swell, squash]).astype(np.float32))
-    stem, ext = os.path.splitext(a.out)
-    ptr = ctx.alloc(W * H * 16)
-    for k in range(a.morph):
+    draw = FrameDrawer(a, ctx, scene, desc, W, H)
+    for k in range(sequence_frames(a, a.morph)):
         w = np.array([0.5 - 0.5 * np.cos(2 * np.pi * k / a.morph), np.sin(2 * np.pi * k / a.morph)], np.float32)
         t0 = time.time()
         scene.morph_mesh(prim, w)
         t1 = time.time()
-        ctx.memset(ptr, 0, W * H * 16)
-        ag.PathTracer(5).render(scene, W, H, a.spp, ptr)
-        path = "%s_%04d%s" % (stem, k, ext)
-        ag.binding.write_png(path, ctx.resolve(ptr, W * H, a.spp), W, H)
-        print("frame %d: primitive %d morphed by weights (%.2f, %.2f) in %.2f ms, %d spp in %.1f ms -> %s" %
-              (k, prim, w[0], w[1], (t1 - t0) * 1e3, a.spp, (time.time() - t1) * 1e3, path))
-    ctx.free(ptr)
+        path, note = draw(k)
+        print("frame %d: primitive %d morphed by weights (%.2f, %.2f) in %.2f ms, %d spp%s in %.1f ms -> %s" %
+              (k, prim, w[0], w[1], (t1 - t0) * 1e3, a.spp, note, (time.time() - t1) * 1e3, path))
 
 
 def main():
@@ -198,6 +238,9 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="--frames: add each frame's reprojected history (agpt_temporal_accumulate) before the denoiser")
     ap.add_argument("--max-history", type=float, default=32.0, help="--temporal: cap on the reprojected sample count")
+    ap.add_argument("--motion", action="store_true",
+                    help="--temporal with --spin, --bend or --morph: the history follows the moved mesh (agpt_scene_snapshot_positions after "
+                         "each frame's update, agpt_render_features_motion, agpt_temporal_accumulate_motion)")
     ap.add_argument("--spin", type=int, default=0, metavar="N",
                     help="N frames at --spp each with one mesh turned about its vertical axis by agpt_scene_transform_mesh (OUT_0000.png ...)")
     ap.add_argument("--spin-prim", type=int, default=None, metavar="PRIM", help="--spin: the mesh primitive that turns (default: the scene's last mesh)")
@@ -213,10 +256,15 @@ def main():
     a = ap.parse_args()
     if a.smooth_normals and not (a.spin or a.bend or a.morph):
         ap.error("--smooth-normals applies to --spin, --bend and --morph")
-    if (a.spin or a.bend or a.morph) and a.frames > 1 or (a.spin > 0) + (a.bend > 0) + (a.morph > 0) > 1:
-        ap.error("--spin, --bend, --morph and --frames are separate sequences")
-    if (a.temporal or a.orbit) and a.frames < 2:
-        ap.error("--temporal and --orbit apply to a sequence (--frames N, N >= 2)")
+    animated = a.spin or a.bend or a.morph
+    if (a.spin > 0) + (a.bend > 0) + (a.morph > 0) > 1:
+        ap.error("--spin, --bend and --morph are separate sequences")
+    if animated and a.orbit:
+        ap.error("--orbit applies to --frames alone: --spin, --bend and --morph keep the scene's camera (with --frames F they stop after F frames)")
+    if a.orbit and a.frames < 2 or a.temporal and a.frames < 2 and not animated:
+        ap.error("--temporal and --orbit apply to a sequence (--frames N, N >= 2; --temporal also to --spin, --bend and --morph)")
+    if a.motion and not (a.temporal and animated):
+        ap.error("--motion applies to --temporal with one of --spin, --bend and --morph")
     W, H = a.width, a.height
     aspect = W / float(H)
     desc = {"c1": lambda: ag.scenes.scene_c1(), "c2": lambda: ag.scenes.scene_c2(aspect=aspect),
@@ -245,7 +293,7 @@ def main():
     scene = desc.instantiate(scene)
     print("scene build + BVH + upload: %.2f s" % (time.time() - t0))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    if a.frames > 1:
+    if a.frames > 1 and not animated:
         return render_sequence(a, ctx, scene, desc, W, H)
     if a.spin:
         return render_spin(a, ctx, scene, desc, W, H)
