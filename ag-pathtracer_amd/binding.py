@@ -41,7 +41,7 @@ EXPORTS = [
     "agpt_scene_add_texture", "agpt_scene_set_material_texture", "agpt_scene_set_material_param_texture", "agpt_scene_set_material_normal_texture", "agpt_scene_set_texture_sampler", "agpt_scene_set_camera",
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_morph_arrays", "agpt_scene_set_mesh_morph_targets", "agpt_scene_morph_mesh", "agpt_vertex_normals_arrays", "agpt_scene_set_mesh_normals_mode", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate",
-    "agpt_scene_snapshot_positions", "agpt_render_features_motion", "agpt_temporal_accumulate_motion", "agpt_li_batch", "agpt_resolve",
+    "agpt_scene_snapshot_positions", "agpt_render_features_motion", "agpt_temporal_accumulate_motion", "agpt_temporal_accumulate_clamped", "agpt_li_batch", "agpt_resolve",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -114,6 +114,12 @@ class TemporalParams(C.Structure):
 
 
 TEMPORAL_DEPTH_TOL, TEMPORAL_NORMAL_COS, TEMPORAL_MIN_WEIGHT = 0.05, 0.9, 1e-2
+
+
+class TemporalClampParams(C.Structure):
+    """agpt_temporal_clamp_params (include/agpt.h): the window's half-width (1..3), whether the statistics and the clamp work on
+    radiance / albedo, the box half-width in standard deviations, and the history count a clamped pixel keeps at most."""
+    _fields_ = [("radius", C.c_int32), ("demodulate", C.c_int32), ("gamma", C.c_float), ("clamped_max_history", C.c_float)]
 
 
 def camera_desc(lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
@@ -223,6 +229,8 @@ def lib():
         L.agpt_scene_snapshot_positions.argtypes = [vp]
         L.agpt_render_features_motion.argtypes = [vp, C.POINTER(RenderParams), vp, vp, vp]
         L.agpt_temporal_accumulate_motion.argtypes = [vp, C.POINTER(TemporalParams)] + [vp] * 11
+    if not variant or hasattr(L, "agpt_temporal_accumulate_clamped"):
+        L.agpt_temporal_accumulate_clamped.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(TemporalClampParams)] + [vp] * 11
     L.agpt_li_batch.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), C.POINTER(Stats)]
     L.agpt_resolve.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -622,12 +630,24 @@ class Context:
                                                        albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur)]),
                "agpt_temporal_accumulate_motion")
 
+    def temporal_accumulate_clamped(self, params, clamp, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev,
+                                    hist_moment2_prev, albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur=None):
+        """agpt_temporal_accumulate_clamped: temporal_accumulate -- or, with prev_point_cur, temporal_accumulate_motion -- whose
+        reprojected history is clamped to mean +- clamp.gamma standard deviations of the current frame's neighbourhood
+        (clamp: a TemporalClampParams).  All DEVICE pointers, full film."""
+        _check(self.L.agpt_temporal_accumulate_clamped(self.h, C.byref(params), C.byref(clamp) if clamp is not None else None,
+                                                       *[C.c_void_p(int(p)) if p else None for p in
+                                                         (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
+                                                          albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur)]),
+               "agpt_temporal_accumulate_clamped")
+
     def temporal_to_host(self, cam_cur, cam_prev, accum, moment2, albedo, normal_depth, prev=None, max_history=32.0,
-                         depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS, prev_point=None):
+                         depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS, prev_point=None, clamp=None):
         """Convenience for tests and tools: uploads this frame's host buffers ([H,W,4], [H,W], [H,W,4], [H,W,4]) and, unless prev is
         None (first frame), prev = (hist_accum, hist_moment2, albedo, normal_depth) of the previous frame; runs temporal_accumulate;
         returns (hist_accum[H,W,4], hist_moment2[H,W]).  cam_cur / cam_prev: CameraDesc or the argument tuple of Scene.set_camera.
-        prev_point ([H,W,4], render_features_motion's third buffer): temporal_accumulate_motion runs instead."""
+        prev_point ([H,W,4], render_features_motion's third buffer): temporal_accumulate_motion runs instead.
+        clamp (a TemporalClampParams): temporal_accumulate_clamped runs instead of either, with prev_point if that is given."""
         H, W = np.shape(moment2)
         cams = [c if isinstance(c, CameraDesc) else camera_desc(*c) for c in (cam_cur, cam_prev)]
         host = [np.ascontiguousarray(a, np.float32) for a in (accum, moment2, albedo, normal_depth) + (tuple(prev) if prev is not None else ())]
@@ -641,14 +661,17 @@ class Context:
             ptrs.append(self.alloc(W * H * 16))
             ptrs.append(self.alloc(W * H * 4))
             params = TemporalParams(W, H, cams[0], cams[1], max_history, depth_tol, normal_cos)
-            if prev_point is None:
+            if prev_point is not None:
+                m = np.ascontiguousarray(prev_point, np.float32)
+                ptrs.append(self.alloc(m.nbytes))
+                self.upload(ptrs[-1], m)
+            if clamp is not None:
+                self.temporal_accumulate_clamped(params, clamp, *ptrs)      # (ten buffers, or eleven with prev_point)
+            elif prev_point is not None:
+                self.temporal_accumulate_motion(params, *ptrs)
+            else:
                 self.temporal_accumulate(params, *ptrs)
-                return self.download(ptrs[-2], (H, W, 4)), self.download(ptrs[-1], (H, W))
-            m = np.ascontiguousarray(prev_point, np.float32)
-            ptrs.append(self.alloc(m.nbytes))
-            self.upload(ptrs[-1], m)
-            self.temporal_accumulate_motion(params, *ptrs)
-            return self.download(ptrs[-3], (H, W, 4)), self.download(ptrs[-2], (H, W))
+            return self.download(ptrs[8], (H, W, 4)), self.download(ptrs[9], (H, W))
         finally:
             for p in ptrs:
                 if p:

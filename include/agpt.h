@@ -705,8 +705,8 @@ int agpt_camera_vectors(const agpt_camera_desc*, float out22[22]);
  * NULL current or output pointer; prev pointers that are partly NULL; an output that aliases an input or the other output.
  * Not covered: moving geometry -- here it is handled only by the depth, normal and flag tests rejecting stale history;
  * agpt_temporal_accumulate_motion (below) follows meshes that the update calls moved --; history behind specular bounces (a mirror
- * image is reprojected as the mirror's surface); more than one GPU or buffers that are not the full film; variance clamping;
- * sub-pixel jitter. */
+ * image is reprojected as the mirror's surface); more than one GPU or buffers that are not the full film; variance clamping --
+ * agpt_temporal_accumulate_clamped (below) clamps the history to the current frame's neighbourhood --; sub-pixel jitter. */
 typedef struct {
     int32_t width, height;            /* all buffers: full film, pitch = width, Accumulator::pixels order (row H-1-y) */
     agpt_camera_desc cam_cur, cam_prev;
@@ -766,6 +766,45 @@ int agpt_temporal_accumulate_motion(agpt_ctx*, const agpt_temporal_params*,
         const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
         const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
         float* hist_accum_out_dev, float* hist_moment2_out_dev, const float* prev_point_cur_dev);
+
+/* ---- neighbourhood clamping of temporal history against stale lighting ------------------------------------------------
+ * The two calls above accept history by geometry alone (flag, depth, normal).  A static receiver whose LIGHTING changed -- the floor
+ * a moved mesh's shadow left -- passes all three, and its history of up to max_history samples keeps saying "in shadow": the shadow
+ * trails behind the object.  agpt_temporal_accumulate_clamped clamps the reprojected history mean to a box mu +- gamma * sigma built
+ * from the CURRENT frame's neighbourhood, and cuts a clamped pixel's history count so that what is left of it fades.
+ * prev_point_cur_dev == NULL: steps 1-4 and 6 are agpt_temporal_accumulate's; otherwise agpt_temporal_accumulate_motion's.  The first
+ * frame (prev NULL) returns the current values bit for bit and reads nothing else.  Only step 5 changes.
+ *   Neighbourhood statistics of pixel p = (x, y), from the current frame only: taps q = (x + dx, y + dy) in film coordinates,
+ *   dy = -r .. r outermost, dx = -r .. r.  A tap is used iff it lies inside the film, n_q = accum_cur[q].w > 0 and
+ *   albedo_cur[q].w == albedo_cur[p].w.  x_q = accum_cur[q].rgb / n_q; with demodulate, x_q = x_q / fmaxf(albedo_cur[q].rgb, 1e-3f)
+ *   per channel.  In tap order, starting from +0:  k += 1.f;  s1 += x_q;  s2 += x_q * x_q  (per channel).  Then per channel
+ *       mu = s1 / k,  var = fmaxf(s2 / k - mu * mu, 0),  sd = sqrtf(var),  lo = mu - gamma * sd,  hi = mu + gamma * sd.
+ *   5'. !(sb >= AGPT_TEMPORAL_MIN_WEIGHT): NO HISTORY (and the window is not read).  Otherwise
+ *       n_raw = fminf(sn / sb, max_history), c_h = sc / sb, m_h = sm / sb.  If k > 0, per channel j, with
+ *       a_j = fmaxf(albedo_cur[p].j, 1e-3f):   d = demodulate ? c_h.j / a_j : c_h.j;   e = fminf(fmaxf(d, lo_j), hi_j);
+ *       if !(e == d) the channel is CLAMPED: c_h.j = demodulate ? e * a_j : e.  (The == is deliberate: an unclamped channel keeps its
+ *       bits -- no demodulation round trip --, and signed zeros do not count.)  If any channel was clamped, with Y = agpt_denoise's
+ *       luminance, c_old the three channels before and c_new after the clamp:
+ *           m_h = fmaxf(m_h - Y(c_old) * Y(c_old), 0) + Y(c_new) * Y(c_new)       (the history keeps its variance around the new mean)
+ *           n_h = fminf(n_raw, clamped_max_history)
+ *       otherwise n_h = n_raw.  Then, as in step 5:  out.rgb = a.rgb + c_h * n_h,  out.w = n_c + n_h,  moment2_out = m_c + m_h * n_h.
+ * Every fmaxf / fminf returns the other operand for a NaN, as in agpt_denoise: NaN bounds (a NaN neighbour, or Inf * 0 from
+ * gamma = +Inf and sd = 0) clamp nothing; a NaN history channel is replaced by a bound.  With gamma = +Inf and finite buffers the
+ * outputs are the unclamped call's, bit for bit.  fp32, every operation rounded on its own (no fma), divide and square root IEEE; one
+ * thread produces one pixel, without atomics: repeated calls are bit-identical.
+ * Checks (AGPT_ERR_INVALID): agpt_temporal_accumulate's in their order, then a NULL clamp struct; radius outside 1..3; demodulate
+ * not 0 or 1; gamma negative or NaN; clamped_max_history not positive and finite; an output aliasing prev_point_cur_dev.
+ * Not covered: clamping in another colour space or to a min/max box; what the other two calls do not cover. */
+typedef struct {
+    int32_t radius;               /* window half-width r: (2r+1)^2 taps of the CURRENT frame; 1..3 */
+    int32_t demodulate;           /* 0 / 1: statistics and clamp on radiance / max(albedo, 1e-3), as agpt_denoise demodulates */
+    float   gamma;                /* box half-width in standard deviations; >= 0, not NaN; +Inf never clamps */
+    float   clamped_max_history;  /* cap on the history count of a pixel whose history was clamped; > 0, finite */
+} agpt_temporal_clamp_params;
+int agpt_temporal_accumulate_clamped(agpt_ctx*, const agpt_temporal_params*, const agpt_temporal_clamp_params*,
+        const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
+        const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
+        float* hist_accum_out_dev, float* hist_moment2_out_dev, const float* prev_point_cur_dev /* may be NULL */);
 
 /* Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) of PathTracer (integrator.h:120-191) for n rays of the caller --
  * the single-ray entry the reference's split-screen compare (myapp.cpp:168) and mouse picking (myapp.cpp:197-201) use, batched.

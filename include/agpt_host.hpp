@@ -487,10 +487,13 @@ public:
     // frame's call left (prev_history, with that frame's prev_features and cam_prev; both null on the first frame), reprojected,
     // into history_out.  history_out has this class' form (its w an effective, possibly fractional count): Denoise and CopyToSurface
     // apply to it, RenderAdaptive must not continue it.  The host keeps history_out and `features` for the next frame.
+    // clamp (agpt_temporal_accumulate_clamped): the reprojected history is clamped to mean +- gamma standard deviations of this frame's
+    // own neighbourhood, so that lighting which changed on unchanged geometry -- the shadow a moved mesh left -- does not trail.
     void TemporalAccumulate(const FeatureBuffers& features, const agpt_camera_desc& cam_cur, const AdaptiveAccumulator* prev_history,
                             const FeatureBuffers* prev_features, const agpt_camera_desc& cam_prev, AdaptiveAccumulator& history_out,
                             float max_history = 32.f, float depth_tol = AGPT_TEMPORAL_DEPTH_TOL,
-                            float normal_cos = AGPT_TEMPORAL_NORMAL_COS, Motion motion = Motion::Ignore) const {
+                            float normal_cos = AGPT_TEMPORAL_NORMAL_COS, Motion motion = Motion::Ignore,
+                            const agpt_temporal_clamp_params* clamp = nullptr) const {
         agpt_temporal_params p{};
         p.width = width;
         p.height = height;
@@ -503,6 +506,15 @@ public:
         const float* hm = prev_history ? prev_history->device_moment2() : nullptr;
         const float* pa = prev_features ? prev_features->device_albedo() : nullptr;
         const float* pn = prev_features ? prev_features->device_normal_depth() : nullptr;
+        if (clamp && (motion == Motion::Ignore || features.prev_point_or_null())) {
+            // (Motion::Follow without a prev_point buffer is left to agpt_temporal_accumulate_motion below, which refuses it)
+            check(agpt_temporal_accumulate_clamped(ctx_.handle(), &p, clamp, device_pixels(), device_moment2(), features.device_albedo(),
+                                                   features.device_normal_depth(), hp, hm, pa, pn, history_out.device_pixels(),
+                                                   history_out.device_moment2(),
+                                                   motion == Motion::Follow ? features.prev_point_or_null() : nullptr),
+                  "agpt_temporal_accumulate_clamped");
+            return;
+        }
         if (motion == Motion::Follow) {
             // agpt_temporal_accumulate_motion: `features` were rendered by PathTracer::RenderFeaturesMotion, whose prev_point says per
             // pixel where a moved mesh's surface point was a frame ago -- that point is reprojected instead of the one seen now

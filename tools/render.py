@@ -6,6 +6,7 @@
     python tools/render.py --scene c3 --spp 4 --frames 8 --orbit 8 --temporal --out out/orbit.png   (out/orbit_0000.png ...)
     python tools/render.py --scene textured --spp 16 --spin 12 --out out/spin.png                  (out/spin_0000.png ...)
     python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --out out/spin.png
+    python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --clamp 1.5 --clamp-radius 2 --out out/spin.png
 """
 import argparse
 import os
@@ -55,7 +56,11 @@ def render_sequence(a, ctx, scene, desc, W, H):
         if a.temporal:
             params = ag.TemporalParams(W, H, ag.camera_desc(*cam), ag.camera_desc(*(cam_prev or cam)), a.max_history,
                                        ag.TEMPORAL_DEPTH_TOL, ag.TEMPORAL_NORMAL_COS)
-            ctx.temporal_accumulate(params, acc, m2, cur[2], cur[3], *(prev if cam_prev else (0, 0, 0, 0)), cur[0], cur[1])
+            buffers = (acc, m2, cur[2], cur[3]) + (prev if cam_prev else (0, 0, 0, 0)) + (cur[0], cur[1])
+            if a.clamp is not None:
+                ctx.temporal_accumulate_clamped(params, clamp_params(a), *buffers)
+            else:
+                ctx.temporal_accumulate(params, *buffers)
             hist = cur[:2]
         ctx.denoise(ag.DenoiseParams(W, H, iterations, 1, ag.DENOISE_SIGMA_Z, ag.DENOISE_SIGMA_N, ag.DENOISE_SIGMA_L), hist[0], hist[1],
                     cur[2], cur[3], out)
@@ -64,6 +69,12 @@ def render_sequence(a, ctx, scene, desc, W, H):
         ag.binding.write_png(path, ctx.resolve_counts(out, W * H), W, H)
         print("frame %d: %d spp%s, %.1f ms -> %s" % (k, spp, " + history" if a.temporal and cam_prev else "", dt * 1e3, path))
         cam_prev = cam
+
+
+def clamp_params(a):
+    """--clamp [GAMMA] --clamp-radius R: the history is clamped to the current frame's neighbourhood (agpt_temporal_accumulate_clamped),
+    on demodulated radiance like the denoiser's; a clamped pixel keeps at most a quarter of --max-history"""
+    return ag.TemporalClampParams(a.clamp_radius, 1, a.clamp, max(1.0, a.max_history / 4))
 
 
 def sequence_frames(a, n):
@@ -107,7 +118,9 @@ class FrameDrawer:
         pt.render_features_motion(scene, W, H, cur[2], cur[3], self.point)
         params = ag.TemporalParams(W, H, self.cam, self.cam, a.max_history, ag.TEMPORAL_DEPTH_TOL, ag.TEMPORAL_NORMAL_COS)
         buffers = (self.acc, self.m2, cur[2], cur[3]) + (prev if k else (0, 0, 0, 0)) + (cur[0], cur[1])
-        if a.motion:
+        if a.clamp is not None:
+            ctx.temporal_accumulate_clamped(params, clamp_params(a), *buffers, self.point if a.motion else 0)
+        elif a.motion:
             ctx.temporal_accumulate_motion(params, *buffers, self.point)
         else:
             ctx.temporal_accumulate(params, *buffers)
@@ -117,7 +130,7 @@ class FrameDrawer:
         moving = ctx.download(self.point, (H, W, 4))[..., 3] == 1
         counts = ctx.download(cur[0], (H, W, 4))[..., 3]
         note = ", %d moving pixels with %.2f effective samples on average" % (moving.sum(), counts[moving].mean()) if moving.any() else ""
-        return path, " + history%s%s" % (" with motion vectors" if a.motion else "", note)
+        return path, " + history%s%s%s" % (" with motion vectors" if a.motion else "", ", clamped" if a.clamp is not None else "", note)
 
 
 def smooth_normals(a, scene, prim, op):
@@ -238,6 +251,10 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="--frames: add each frame's reprojected history (agpt_temporal_accumulate) before the denoiser")
     ap.add_argument("--max-history", type=float, default=32.0, help="--temporal: cap on the reprojected sample count")
+    ap.add_argument("--clamp", type=float, nargs="?", const=1.0, default=None, metavar="GAMMA",
+                    help="--temporal: clamp the reprojected history to mean +- GAMMA standard deviations (default 1) of the frame's own "
+                         "neighbourhood (agpt_temporal_accumulate_clamped): shadows and bounce light do not trail behind what moved")
+    ap.add_argument("--clamp-radius", type=int, default=2, choices=(1, 2, 3), help="--clamp: the neighbourhood's half-width in pixels")
     ap.add_argument("--motion", action="store_true",
                     help="--temporal with --spin, --bend or --morph: the history follows the moved mesh (agpt_scene_snapshot_positions after "
                          "each frame's update, agpt_render_features_motion, agpt_temporal_accumulate_motion)")
@@ -263,6 +280,10 @@ def main():
         ap.error("--orbit applies to --frames alone: --spin, --bend and --morph keep the scene's camera (with --frames F they stop after F frames)")
     if a.orbit and a.frames < 2 or a.temporal and a.frames < 2 and not animated:
         ap.error("--temporal and --orbit apply to a sequence (--frames N, N >= 2; --temporal also to --spin, --bend and --morph)")
+    if a.clamp is not None and not a.temporal:
+        ap.error("--clamp applies to --temporal")
+    if a.clamp is not None and not a.clamp >= 0:
+        ap.error("--clamp GAMMA must be non-negative")
     if a.motion and not (a.temporal and animated):
         ap.error("--motion applies to --temporal with one of --spin, --bend and --morph")
     W, H = a.width, a.height
