@@ -42,6 +42,8 @@ EXPORTS = [
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_morph_arrays", "agpt_scene_set_mesh_morph_targets", "agpt_scene_morph_mesh", "agpt_vertex_normals_arrays", "agpt_scene_set_mesh_normals_mode", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate",
     "agpt_scene_snapshot_positions", "agpt_render_features_motion", "agpt_temporal_accumulate_motion", "agpt_temporal_accumulate_clamped", "agpt_li_batch", "agpt_resolve",
+    "agpt_scene_update_sphere", "agpt_scene_update_plane", "agpt_scene_set_area_light_radiance", "agpt_scene_set_infinite_light_radiance",
+    "agpt_scene_update_spheres_device",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -231,6 +233,12 @@ def lib():
         L.agpt_temporal_accumulate_motion.argtypes = [vp, C.POINTER(TemporalParams)] + [vp] * 11
     if not variant or hasattr(L, "agpt_temporal_accumulate_clamped"):
         L.agpt_temporal_accumulate_clamped.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(TemporalClampParams)] + [vp] * 11
+    if not variant or hasattr(L, "agpt_scene_update_spheres_device"):
+        L.agpt_scene_update_sphere.argtypes = [vp, C.c_int, fp, C.c_float]
+        L.agpt_scene_update_plane.argtypes = [vp, C.c_int, fp, fp]
+        L.agpt_scene_set_area_light_radiance.argtypes = [vp, C.c_int, fp]
+        L.agpt_scene_set_infinite_light_radiance.argtypes = [vp, C.c_int, fp]
+        L.agpt_scene_update_spheres_device.argtypes = [vp, ip, C.c_int, vp]
     L.agpt_li_batch.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), C.POINTER(Stats)]
     L.agpt_resolve.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -899,9 +907,69 @@ class Scene:
         _check(self.L.agpt_scene_set_mesh_normals_mode(self.h, int(prim), int(mode)), "agpt_scene_set_mesh_normals_mode")
         (self._smooth.add if int(mode) == NORMALS_SMOOTH else self._smooth.discard)(int(prim))
 
+    def update_sphere(self, prim, center, radius):
+        """agpt_scene_update_sphere: a new centre and radius for sphere primitive `prim` of the committed scene -- a sphere, or the
+        sphere of an area light (what add_area_light returned).  Absolute, not cumulative; the scene is what building it with the new
+        values gives.  Non-finite values and radius <= 0 are refused."""
+        c = np.ascontiguousarray(center, np.float32).reshape(3)
+        _check(self.L.agpt_scene_update_sphere(self.h, int(prim), c.ctypes.data_as(C.POINTER(C.c_float)), float(radius)), "agpt_scene_update_sphere")
+
+    def update_plane(self, prim, o, size):
+        """agpt_scene_update_plane: a new origin o[3] and size[2] for plane primitive `prim` of the committed scene."""
+        po = np.ascontiguousarray(o, np.float32).reshape(3)
+        ps = np.ascontiguousarray(size, np.float32).reshape(2)
+        _check(self.L.agpt_scene_update_plane(self.h, int(prim), po.ctypes.data_as(C.POINTER(C.c_float)), ps.ctypes.data_as(C.POINTER(C.c_float))),
+               "agpt_scene_update_plane")
+
+    def set_area_light_radiance(self, prim, L):
+        """agpt_scene_set_area_light_radiance: the radiance of the area light whose sphere is primitive `prim`."""
+        l = np.ascontiguousarray(L, np.float32).reshape(3)
+        _check(self.L.agpt_scene_set_area_light_radiance(self.h, int(prim), l.ctypes.data_as(C.POINTER(C.c_float))), "agpt_scene_set_area_light_radiance")
+
+    def set_infinite_light_radiance(self, light, L):
+        """agpt_scene_set_infinite_light_radiance: the radiance of uniform infinite light `light` (what add_uniform_infinite_light returned)."""
+        l = np.ascontiguousarray(L, np.float32).reshape(3)
+        _check(self.L.agpt_scene_set_infinite_light_radiance(self.h, int(light), l.ctypes.data_as(C.POINTER(C.c_float))),
+               "agpt_scene_set_infinite_light_radiance")
+
+    def update_spheres(self, prims, records):
+        """agpt_scene_update_spheres_device: records[n, 4] = (cx, cy, cz, radius) for the n distinct sphere primitives `prims`.  A torch
+        tensor on the context's GPU (contiguous float32) is handed over as a device pointer after torch's current stream has been
+        synchronised -- unless the context runs on that very stream, as update_mesh does; anything else (ndarray, list, CPU tensor)
+        is uploaded by this call.  A record with a non-finite value or a radius <= 0 refuses the whole batch with nothing written."""
+        ids, pi = _i(np.asarray(prims).reshape(-1))
+        n = ids.shape[0]
+        if type(records).__module__.split(".")[0] == "torch" and records.device.type != "cpu":
+            import torch
+            t = records
+            if (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.ctx.device:
+                raise ValueError("update_spheres: records is on %s, the context is on GPU %d" % (t.device, self.ctx.device))
+            if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (n, 4) or not t.is_contiguous():
+                raise ValueError("update_spheres: records must be a contiguous float32 tensor of shape (%d, 4), got %s %s" % (n, t.dtype, tuple(t.shape)))
+            stream = torch.cuda.current_stream(t.device)
+            if not self.ctx.stream or int(stream.cuda_stream) != self.ctx.stream:   # (a context on the null stream always waits)
+                stream.synchronize()
+            _check(self.L.agpt_scene_update_spheres_device(self.h, pi, n, C.c_void_p(t.data_ptr())), "agpt_scene_update_spheres_device")
+            return
+        r = np.ascontiguousarray(np.asarray(records, np.float32).reshape(-1, 4))
+        if r.shape[0] != n:
+            raise ValueError("update_spheres: %d ids but %d records" % (n, r.shape[0]))
+        ptr = self.ctx.alloc(max(r.nbytes, 16))
+        try:
+            self.ctx.upload(ptr, r)
+            _check(self.L.agpt_scene_update_spheres_device(self.h, pi, n, C.c_void_p(ptr)), "agpt_scene_update_spheres_device")
+        finally:
+            self.ctx.free(ptr)
+
+    def update_spheres_device(self, prims, records_ptr):
+        """agpt_scene_update_spheres_device with a raw device pointer (Context.alloc / upload, or a tensor's data_ptr())."""
+        ids, pi = _i(np.asarray(prims).reshape(-1))
+        _check(self.L.agpt_scene_update_spheres_device(self.h, pi, ids.shape[0], C.c_void_p(records_ptr)), "agpt_scene_update_spheres_device")
+
     def snapshot_positions(self):
-        """agpt_scene_snapshot_positions: once per frame, after the frame's mesh updates and before render_features_motion -- the
-        scene's newer generation of triangle positions becomes the older one and the newer one is filled from the device."""
+        """agpt_scene_snapshot_positions: once per frame, after the frame's updates (meshes, spheres, planes) and before
+        render_features_motion -- the scene's newer generation of triangle positions and analytic records becomes the older one and the
+        newer one is filled from the device."""
         _check(self.L.agpt_scene_snapshot_positions(self.h), "agpt_scene_snapshot_positions")
 
     def set_bvh_builder(self, builder):

@@ -832,7 +832,7 @@ static int render_features(const char* fn, bool motion, agpt_scene* s, const agp
     if (motion) {
         const agpt_scene::PositionSnapshots& ps = s->snapshots;
         agpt::launch_motion(c->stream, rcn, c->hit.p, c->ext_o.p, c->ext_d.p, ps.gen[ps.newest ^ 1].p, ps.gen[ps.newest].p, (uint32_t)ps.n_tris,
-                            (float4*)prev_point_dev);
+                            ps.analytic[ps.newest ^ 1].p, ps.analytic[ps.newest].p, (uint32_t)ps.n_prims, (float4*)prev_point_dev);
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());

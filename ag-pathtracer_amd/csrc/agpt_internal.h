@@ -1,7 +1,7 @@
 // agpt_internal.h -- what the units that define the C entry points of include/agpt.h share: error reporting, the owning device
 // buffer, and the context and the scene behind the two opaque handles.  Those units are agpt_api.hip (context, pool, trace launches,
 // wavefront loop, renderers), agpt_scene_api.hip (scene building, commit, host BVH, mesh updates), agpt_kat.hip, agpt_comm.hip, and
-// the entry points that sit beside their kernels (agpt_adaptive.hip, agpt_denoise.hip, agpt_temporal.hip).  Only .hip / .cpp units
+// the entry points that sit beside their kernels (agpt_adaptive.hip, agpt_denoise.hip, agpt_temporal.hip, agpt_motion.hip, agpt_analytic.hip).  Only .hip / .cpp units
 // include this file, no other header does.
 #pragma once
 
@@ -235,19 +235,28 @@ struct agpt_scene {
     // agpt_scene_snapshot_positions: two generations of world-space triangle positions, float4[3 * n_tris] each, indexed by the GLOBAL
     // triangle id (not by BVH slot).  Allocated by the first snapshot; gen[newest] is the newer one.  agpt_scene_commit drops them; an
     // AGPT_UPDATE_REBUILD, which re-commits with the triangle ids unchanged, keeps them (update_on_host).
+    // analytic[]: the same two generations of the sphere and plane records, two float4 per primitive index (agpt_analytic.h), with the
+    // same lifetime; filled from d_prims, so every update route is seen.  Empty for a scene without a sphere or a plane.
     struct PositionSnapshots {
-        DevBuf<float4> gen[2];
+        DevBuf<float4> gen[2], analytic[2];
         int newest = 0;
-        size_t n_tris = 0;
+        size_t n_tris = 0, n_prims = 0;
         bool valid = false;
         void drop() {
-            gen[0].release();
-            gen[1].release();
-            n_tris = 0;
+            for (int g = 0; g < 2; g++) {
+                gen[g].release();
+                analytic[g].release();
+            }
+            n_tris = n_prims = 0;
             valid = false;
         }
     };
     PositionSnapshots snapshots;
+    // agpt_scene_update_spheres_device (agpt_analytic.hip): the uploaded id list and k_check_spheres' word, allocated by the first such
+    // call.  spheres_stale: `spheres` is behind d_prims (brought up to date by sync_mirror before anything reads it).
+    DevBuf<int32_t> d_sphere_ids;
+    DevBuf<uint32_t> d_sphere_flag;
+    bool spheres_stale = false;
 };
 
 template <class T>

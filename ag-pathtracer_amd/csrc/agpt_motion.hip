@@ -12,6 +12,7 @@
 // the hit triangle (a wave's pixels share a few triangles), 16 B written.  k_temporal_motion: k_temporal plus 16 B per pixel.
 #include <hip/hip_runtime.h>
 
+#include "agpt_analytic.h"
 #include "agpt_internal.h"
 #include "agpt_motion.h"
 #include "agpt_temporal.h"
@@ -32,12 +33,17 @@ k_snapshot_positions(const float4* __restrict__ tri_verts, uint32_t n_tris, floa
     out[2] = v2;
 }
 
-// prev_point = (p.xyz, w): w = 0 a miss (p = 0); w = 2 a surface that did not move between the two snapshots -- a sphere, a plane, a
-// triangle whose 36 position bytes are the same in both --, p = O + t * D; w = 1 a triangle that moved, p = its older positions at this
-// hit's barycentrics
+// prev_point = (p.xyz, w): w = 0 a miss (p = 0); w = 2 a surface that did not move between the two snapshots -- a triangle whose 36
+// position bytes, a sphere or a plane whose 20 record bytes are the same in both --, p = O + t * D; w = 1 a triangle that moved, p = its
+// older positions at this hit's barycentrics.
+// A sphere or a plane k (an_old / an_new: the analytic generations, agpt_analytic.h; n_prims == 0 without them) whose 20 record bytes
+// differ: w = 1 and p = c_old + (p - c_new) * s per component, s = (q, q, q) with q = r_old / r_new for a sphere and
+// (r_old / r_new, 1, r2_old / r2_new) -- the half-sizes -- for a plane; a component of s or of that point that is not finite leaves
+// w = 2 and p = O + t * D.
 __global__ void __launch_bounds__(AGPT_BLOCK)
 k_motion(RenderConsts rc, const DevHit* __restrict__ hits, const float4* __restrict__ ray_o, const float4* __restrict__ ray_d,
-         const float4* __restrict__ gen_old, const float4* __restrict__ gen_new, uint32_t n_tris, float4* __restrict__ prev_point) {
+         const float4* __restrict__ gen_old, const float4* __restrict__ gen_new, uint32_t n_tris, const float4* __restrict__ an_old,
+         const float4* __restrict__ an_new, uint32_t n_prims, float4* __restrict__ prev_point) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rc.NP) return;
     int x, y;
@@ -66,6 +72,22 @@ k_motion(RenderConsts rc, const DevHit* __restrict__ hits, const float4* __restr
                 p = (V3(a0.x, a0.y, a0.z) * w0 + V3(a1.x, a1.y, a1.z) * h.b1) + V3(a2.x, a2.y, a2.z) * h.b2;
                 m.w = 1.f;
             }
+        } else if ((h.id & AGPT_HIT_SPHERE) && (h.id & 0x7FFFFFFFu) < n_prims) {
+            const size_t k = AGPT_ANALYTIC_GEN_STRIDE * (size_t)(h.id & 0x7FFFFFFFu);
+            const float4 a0 = an_old[k], a1 = an_old[k + 1], b0 = an_new[k], b1 = an_new[k + 1];
+            const uint32_t differ = (__float_as_uint(a0.x) ^ __float_as_uint(b0.x)) | (__float_as_uint(a0.y) ^ __float_as_uint(b0.y)) |
+                                    (__float_as_uint(a0.z) ^ __float_as_uint(b0.z)) | (__float_as_uint(a0.w) ^ __float_as_uint(b0.w)) |
+                                    (__float_as_uint(a1.x) ^ __float_as_uint(b1.x));
+            if (differ) {
+                const float q = a0.w / b0.w;
+                const bool plane = __float_as_uint(b1.y) == (uint32_t)AGPT_PRIM_PLANE;
+                const v3 s = plane ? V3(q, 1.f, a1.x / b1.x) : V3(q, q, q);
+                const v3 was = V3(a0.x, a0.y, a0.z) + (p - V3(b0.x, b0.y, b0.z)) * s;
+                if (analytic_finite(s.x) && analytic_finite(s.z) && analytic_finite(was.x) && analytic_finite(was.y) && analytic_finite(was.z)) {
+                    p = was;
+                    m.w = 1.f;
+                }
+            }
         }
         m.x = p.x; m.y = p.y; m.z = p.z;
     }
@@ -88,46 +110,59 @@ void launch_snapshot_positions(hipStream_t stream, const float4* tri_verts, uint
     hipLaunchKernelGGL(k_snapshot_positions, agpt_blocks(n_tris), dim3(AGPT_BLOCK), 0, stream, tri_verts, n_tris, gen);
 }
 void launch_motion(hipStream_t stream, const RenderConsts& rc, const DevHit* hits, const float4* ray_o, const float4* ray_d,
-                   const float4* gen_old, const float4* gen_new, uint32_t n_tris, float4* prev_point) {
-    hipLaunchKernelGGL(k_motion, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, rc, hits, ray_o, ray_d, gen_old, gen_new, n_tris,
-                       prev_point);
+                   const float4* gen_old, const float4* gen_new, uint32_t n_tris, const float4* an_old, const float4* an_new, uint32_t n_prims,
+                   float4* prev_point) {
+    hipLaunchKernelGGL(k_motion, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, rc, hits, ray_o, ray_d, gen_old, gen_new, n_tris, an_old,
+                       an_new, n_prims, prev_point);
 }
 
 }  // namespace agpt
 
 extern "C" {
 
-// The newer generation becomes the older one; the newer one is filled from what the update calls left in tri_verts.  The first call
-// allocates both and fills both with the same bytes.
+// The newer generation becomes the older one; the newer one is filled from what the update calls left in tri_verts and -- the spheres
+// and planes -- in d_prims.  The first call allocates both and fills both with the same bytes.
 int agpt_scene_snapshot_positions(agpt_scene* s) {
     if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_snapshot_positions: NULL scene");
     if (!s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_snapshot_positions: the scene is not committed");
-    size_t n_tris = 0;
+    size_t n_tris = 0, n_prims = 0;
     for (const agpt::HostMesh& m : s->meshes) n_tris += m.prim_index.size();
+    if (!s->spheres.empty()) n_prims = s->prims.size();   // (records by primitive index; none for a scene of meshes only)
     agpt_scene::PositionSnapshots& ps = s->snapshots;
-    if (n_tris == 0) {   // nothing to hold: every hit of such a scene is a sphere, a plane or a miss
+    if (n_tris == 0 && n_prims == 0) {   // nothing to hold: every hit of such a scene is a miss
         ps.valid = true;
         return AGPT_OK;
     }
-    if (3 * n_tris > s->d_tri_verts.n || n_tris > 0x7FFFFFFFull)
-        return fail(AGPT_ERR_DEVICE, "agpt_scene_snapshot_positions: the scene's triangle records do not cover its meshes");
+    if (3 * n_tris > s->d_tri_verts.n || n_tris > 0x7FFFFFFFull || n_prims > s->d_prims.n)
+        return fail(AGPT_ERR_DEVICE, "agpt_scene_snapshot_positions: the scene's records do not cover its meshes and primitives");
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const bool first = !ps.valid;
+    const size_t n_analytic = AGPT_ANALYTIC_GEN_STRIDE * n_prims;
     if (first) {
-        if (ps.gen[0].alloc(3 * n_tris) != hipSuccess || ps.gen[1].alloc(3 * n_tris) != hipSuccess) {
+        bool ok = true;
+        for (int g = 0; g < 2; g++) {
+            if (n_tris) ok = ok && ps.gen[g].alloc(3 * n_tris) == hipSuccess;
+            if (n_prims) ok = ok && ps.analytic[g].alloc(n_analytic) == hipSuccess;
+        }
+        if (!ok) {
             ps.drop();
             return fail(AGPT_ERR_NOMEM, "agpt_scene_snapshot_positions: out of device memory");
         }
         ps.n_tris = n_tris;
+        ps.n_prims = n_prims;
         ps.newest = 0;
     } else {
         ps.newest ^= 1;
     }
-    agpt::launch_snapshot_positions(c->stream, s->d_tri_verts.p, (uint32_t)n_tris, ps.gen[ps.newest].p);
+    if (n_tris) agpt::launch_snapshot_positions(c->stream, s->d_tri_verts.p, (uint32_t)n_tris, ps.gen[ps.newest].p);
+    if (n_prims) agpt::launch_snapshot_analytic(c->stream, s->d_prims.p, (uint32_t)n_prims, ps.analytic[ps.newest].p);
     HIP_TRY(hipGetLastError());
-    if (first)
+    if (first && n_tris)
         HIP_TRY(hipMemcpyAsync(ps.gen[ps.newest ^ 1].p, ps.gen[ps.newest].p, 3 * n_tris * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    if (first && n_prims)
+        HIP_TRY(hipMemcpyAsync(ps.analytic[ps.newest ^ 1].p, ps.analytic[ps.newest].p, n_analytic * sizeof(float4), hipMemcpyDeviceToDevice,
+                               c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     ps.valid = true;
     return AGPT_OK;

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "agpt_analytic.h"
 #include "agpt_bvh_device.h"
 #include "agpt_internal.h"
 #include "agpt_normals.h"
@@ -113,10 +114,11 @@ int agpt_scene_add_mesh(agpt_scene* s, const float* vertices, int n_vertices, co
 int agpt_scene_add_sphere(agpt_scene* s, const float center[3], float radius, int material) {
     if (!s || !center) return fail(AGPT_ERR_INVALID, "agpt_scene_add_sphere: NULL argument");
     if (material < -1 || material >= (int)s->materials.size()) return fail(AGPT_ERR_INVALID, "agpt_scene_add_sphere: bad material id");
+    const AnalyticRecord a = sphere_record(center[0], center[1], center[2], radius);
     agpt::HostSphere sp;
-    sp.center = V3(center[0], center[1], center[2]);
-    sp.r = radius;
-    sp.r2 = radius * radius;
+    sp.center = V3(a.cx, a.cy, a.cz);
+    sp.r = a.r;
+    sp.r2 = a.r2;
     s->spheres.push_back(sp);
     return add_prim(s, AGPT_PRIM_SPHERE, (int)s->spheres.size() - 1, material);
 }
@@ -260,8 +262,10 @@ int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
 }
 
 // the bounds of the host copies of meshes that were refitted on the device (agpt_scene_update_mesh) and, with `arrays`, the positions
-// and normals of those whose new arrays never existed on the host (agpt_scene_update_mesh_device, agpt_scene_transform_mesh)
+// and normals of those whose new arrays never existed on the host (agpt_scene_update_mesh_device, agpt_scene_transform_mesh); the
+// spheres that agpt_scene_update_spheres_device moved
 static int sync_mirror(agpt_scene* s, bool arrays) {
+    if (const int rc = agpt::download_spheres(s)) return rc;
     for (size_t m = 0; m < s->updates.size(); m++) {
         agpt_scene::MeshUpdate& up = s->updates[m];
         if (up.bounds_stale) {
@@ -973,8 +977,9 @@ int agpt_dbg_li_batch(agpt_scene* s, const agpt_ray* rays, int n, float* radianc
     if (!s || !rays || !radiance3_out || n < 0) return fail(AGPT_ERR_INVALID, "agpt_dbg_li_batch: bad argument");
     if (n == 0) return AGPT_OK;
     std::vector<agpt_hit> hits((size_t)n);
-    const int rc = agpt_intersect_batch(s, rays, n, hits.data(), 0, nullptr);
+    int rc = agpt_intersect_batch(s, rays, n, hits.data(), 0, nullptr);
     if (rc) return rc;
+    if ((rc = sync_mirror(s, false))) return rc;   // (the spheres: the uv below is computed from the host copy)
     for (int i = 0; i < n; ++i) {
         float* L = radiance3_out + 3 * (size_t)i;
         L[0] = L[1] = L[2] = 0.f;

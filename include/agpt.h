@@ -722,7 +722,40 @@ int agpt_temporal_accumulate(agpt_ctx*, const agpt_temporal_params*,
         const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
         float* hist_accum_out_dev, float* hist_moment2_out_dev);
 
-/* ---- motion vectors: temporal history that follows moved meshes -------------------------------------------------------
+/* ---- spheres, planes and lights of a COMMITTED scene, moved in place ---------------------------------------------------
+ * A sphere or a plane is five floats of one device record, a light's radiance three; nothing else on the device is derived from them.
+ * The calls below rewrite those bytes and the host's copy, enqueue on the context's stream, synchronise with it and leave the scene
+ * committed.  Afterwards the scene is, byte for byte, what agpt_scene_commit uploads for a scene built with the new values, so every
+ * render, agpt_li_batch, agpt_intersect_*, agpt_render_features and agpt_dbg_li_batch result is that scene's.  The values are
+ * absolute, not cumulative.  The host applies the result like a camera move (clear the accumulator).
+ *   agpt_scene_update_sphere     prim: a sphere (agpt_scene_add_sphere) or a light's sphere (what agpt_scene_add_area_light returned);
+ *                                the record of agpt_scene_add_sphere: the centre, the radius and radius * radius.
+ *   agpt_scene_update_plane      prim: a plane; the record of agpt_scene_add_plane: o and size / 2 per axis.
+ *   agpt_scene_set_area_light_radiance      prim: what agpt_scene_add_area_light returned.
+ *   agpt_scene_set_infinite_light_radiance  light: what agpt_scene_add_uniform_infinite_light returned.
+ * AGPT_ERR_INVALID (+ agpt_last_error), checked in this order, scene untouched: a NULL argument; a scene that is not committed; a prim
+ * (a light) out of range or of another type; for the area-light call a sphere without a light; any non-finite value, radius <= 0, a
+ * plane size <= 0.  The last rule is stricter than the add calls' on purpose: a NaN primitive can make an emitter re-cast a path for
+ * ever, and that must not be reachable from a per-frame call.  L may be any finite value, zero and negative included. */
+int agpt_scene_update_sphere(agpt_scene*, int prim, const float center[3], float radius);
+int agpt_scene_update_plane(agpt_scene*, int prim, const float o[3], const float size[2]);
+int agpt_scene_set_area_light_radiance(agpt_scene*, int prim, const float L[3]);
+int agpt_scene_set_infinite_light_radiance(agpt_scene*, int light, const float L[3]);
+/* agpt_scene_update_sphere for n spheres at once with the new values in DEVICE memory of the context's GPU (a particle or rigid-body
+ * step that never visits the host): prims is a HOST array of n distinct sphere primitive ids (lights' spheres among them),
+ * center_radius_dev n records (cx, cy, cz, radius) of 16 bytes each, 16-byte aligned.  Ordering as for agpt_scene_update_mesh_device:
+ * the records must be complete when the call is made, or have been produced on the context's stream.
+ * One kernel reduces "any value Inf or NaN, or a radius <= 0" over the n records to one flag word, the only thing that comes back;
+ * with the flag set the call returns AGPT_ERR_INVALID and nothing has been written.  Otherwise one lane per record writes the five
+ * floats of its primitive: the same bytes as n agpt_scene_update_sphere calls.
+ * AGPT_ERR_INVALID before any launch, in this order: a NULL argument; a scene that is not committed; n < 0; a pointer that is not
+ * 16-byte aligned; walking the list, an id out of range or not a sphere, or an id listed twice.  n == 0 is AGPT_OK and launches
+ * nothing.  A pointer that is not device memory is not detected.
+ * The scene's host copy of the spheres is brought up to date -- by a download -- when something next reads it: agpt_scene_commit, an
+ * AGPT_UPDATE_REBUILD of any mesh, agpt_dbg_li_batch. */
+int agpt_scene_update_spheres_device(agpt_scene*, const int32_t* prims, int n, const float* center_radius_dev);
+
+/* ---- motion vectors: temporal history that follows moved meshes, spheres and planes ------------------------------------
  * Step 3 above reprojects the point the pixel sees NOW; for a mesh that agpt_scene_update_mesh / _device, agpt_scene_transform_mesh,
  * agpt_scene_pose_mesh or agpt_scene_morph_mesh moved since the previous frame that is the wrong place on the previous film.  The three
  * calls below reproject where that surface point WAS instead.  Per frame:
@@ -735,14 +768,22 @@ int agpt_temporal_accumulate(agpt_ctx*, const agpt_temporal_params*,
  * between two snapshots changes nothing.  The call makes the newer generation the older one and fills the newer one from the positions
  * the update calls left on the device (every route: no updater knows about snapshots); the w lanes are 0.  The first call allocates
  * both generations and leaves the same bytes in both: nothing has moved yet.  A scene that never calls this allocates and launches
- * nothing.  T == 0 succeeds without a launch.  agpt_scene_commit (anything that re-commits the scene) drops both generations.
+ * nothing.  A scene with a sphere or a plane also keeps two generations of analytic records by PRIMITIVE index -- (cx, cy, cz, r) and r2,
+ * for a plane o and the two half-sizes --, filled by one more small launch from the device's primitive records (so agpt_scene_update_sphere,
+ * _plane and _spheres_device are all seen) under the same rules.  T == 0 skips the triangle part only; a scene with neither triangles
+ * nor spheres nor planes succeeds without a launch.  agpt_scene_commit drops both generations of both kinds; an AGPT_UPDATE_REBUILD,
+ * which re-commits with every id unchanged, keeps them.
  * AGPT_ERR_INVALID for a NULL or an uncommitted scene.  Enqueued on the context's stream behind the updates and synchronised. */
 int agpt_scene_snapshot_positions(agpt_scene*);
 
 /* agpt_render_features_motion: agpt_render_features -- the same ray, the same one trace launch, albedo and normal_depth byte for
  * byte -- plus, from the same hit, prev_point_dev (DEVICE float4, indexed like the other two) = (p.xyz, w):
  *     a miss                        (0, 0, 0, 0)
- *     a sphere or a plane           p = O + t * D, w = 2                 (O, D: the pixel's ray; these are never moved)
+ *     a sphere or a plane k         if its 20 record bytes are the same in the two generations: p = O + t * D, w = 2 (O, D: the pixel's
+ *                                   ray).  Otherwise w = 1 and, with c the centre (a plane's o), _old / _new the generation and
+ *                                   s = (q, q, q), q = r_old / r_new for a sphere, s = (r_old / r_new, 1, r2_old / r2_new) for a plane:
+ *                                   p = c_old + ((O + t * D) - c_new) * s per component -- the same point of the surface before the move
+ *                                   (spheres do not rotate).  If a component of s or of that p is not finite: w = 2, p = O + t * D.
  *     a triangle with global id g   if its 36 position bytes are the same in the two generations: p = O + t * D, w = 2 (not moved);
  *                                   otherwise w = 1 and, with v0, v1, v2 its positions in the OLDER generation and (b1, b2) the hit's
  *                                   barycentrics, b0 = (1 - b1) - b2,  p = (v0 * b0 + v1 * b1) + v2 * b2 per component
@@ -760,8 +801,8 @@ int agpt_render_features_motion(agpt_scene*, const agpt_render_params* rp, float
  * the outputs are agpt_temporal_accumulate's, bit for bit.  Checks: agpt_temporal_accumulate's in their order, then a NULL
  * prev_point_cur_dev, then an output aliasing it (AGPT_ERR_INVALID).
  * Limits: the normal test still compares the current normal with the previous tap's, so a surface that turns by more than
- * acos(normal_cos) within one frame is rejected; no motion vectors behind specular bounces and none for lights; nothing for a moved
- * sphere or plane (the library moves none); one GPU, full film. */
+ * acos(normal_cos) within one frame is rejected; no motion vectors behind specular bounces; a moved light's sphere carries its own
+ * history, but what it lights is followed by agpt_temporal_accumulate_clamped only; one GPU, full film. */
 int agpt_temporal_accumulate_motion(agpt_ctx*, const agpt_temporal_params*,
         const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
         const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,

@@ -284,9 +284,36 @@ public:
     void SetMeshNormalsMode(int prim, MeshNormals mode) {
         check(agpt_scene_set_mesh_normals_mode(h_, prim, (int)mode), "agpt_scene_set_mesh_normals_mode");
     }
+    // spheres, planes and lights of the committed scene moved in place (agpt_scene_update_sphere and the calls beside it): `prim` is what
+    // primitives_push_back / addAreaLight returned, `light` what lights_push_back(UniformInfiniteLight) returned.  The values are absolute;
+    // the scene is what building it with them gives.  Non-finite values, a radius <= 0 and a plane size <= 0 are refused.
+    // `scene.updateSphere(light, Sphere{c, r}); accumulator.Clear();`
+    void updateSphere(int prim, const Sphere& s) {
+        const float c[3] = {s.center.x, s.center.y, s.center.z};
+        check(agpt_scene_update_sphere(h_, prim, c, s.radius), "agpt_scene_update_sphere");
+    }
+    void updatePlane(int prim, const Plane& p) {
+        const float o[3] = {p.o.x, p.o.y, p.o.z}, sz[2] = {p.size_x, p.size_z};
+        check(agpt_scene_update_plane(h_, prim, o, sz), "agpt_scene_update_plane");
+    }
+    void setAreaLightRadiance(int prim, float3 L) {
+        const float l[3] = {L.x, L.y, L.z};
+        check(agpt_scene_set_area_light_radiance(h_, prim, l), "agpt_scene_set_area_light_radiance");
+    }
+    void setInfiniteLightRadiance(int light, float3 L) {
+        const float l[3] = {L.x, L.y, L.z};
+        check(agpt_scene_set_infinite_light_radiance(h_, light, l), "agpt_scene_set_infinite_light_radiance");
+    }
+    // n spheres at once from DEVICE memory of the context's GPU (agpt_scene_update_spheres_device): prims are distinct sphere ids,
+    // center_radius_dev one 16-byte record (cx, cy, cz, radius) each, complete when the call is made or produced on the context's stream
+    void updateSpheresDevice(const std::vector<int32_t>& prims, const float* center_radius_dev) {
+        if (prims.empty()) return;
+        check(agpt_scene_update_spheres_device(h_, prims.data(), (int)prims.size(), center_radius_dev), "agpt_scene_update_spheres_device");
+    }
     // camera moved (RotatingCamera::update): re-derive the camera only, geometry stays in HBM
-    // motion vectors (agpt_scene_snapshot_positions): once per frame, after the frame's UpdateMesh / TransformMesh / PoseMesh / MorphMesh
-    // calls and before PathTracer::RenderFeaturesMotion -- the scene keeps the triangle positions of this frame and of the one before
+    // motion vectors (agpt_scene_snapshot_positions): once per frame, after the frame's UpdateMesh / TransformMesh / PoseMesh / MorphMesh /
+    // updateSphere / updatePlane calls and before PathTracer::RenderFeaturesMotion -- the scene keeps the triangle positions and the sphere
+    // and plane records of this frame and of the one before
     void SnapshotPositions() { check(agpt_scene_snapshot_positions(h_), "agpt_scene_snapshot_positions"); }
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }
     void Intersect(const agpt_ray* rays, int n, agpt_hit* hits) const {

@@ -7,6 +7,7 @@
     python tools/render.py --scene textured --spp 16 --spin 12 --out out/spin.png                  (out/spin_0000.png ...)
     python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --out out/spin.png
     python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --clamp 1.5 --clamp-radius 2 --out out/spin.png
+    python tools/render.py --scene c1 --spp 4 --frames 8 --light-orbit 10 --temporal --motion --clamp 1.5 --out out/light.png
 """
 import argparse
 import os
@@ -131,6 +132,30 @@ class FrameDrawer:
         counts = ctx.download(cur[0], (H, W, 4))[..., 3]
         note = ", %d moving pixels with %.2f effective samples on average" % (moving.sum(), counts[moving].mean()) if moving.any() else ""
         return path, " + history%s%s%s" % (" with motion vectors" if a.motion else "", ", clamped" if a.clamp is not None else "", note)
+
+
+def render_light_orbit(a, ctx, scene, desc, W, H):
+    """--light-orbit DEG: the scene's first area light moved DEG degrees further per frame about the vertical axis through the camera's
+    lookat, each frame placed with Scene.update_sphere (20 bytes of one device record; nothing is uploaded again) and rendered at --spp
+    into OUT_0000.png ...  With --temporal --motion the light's own pixels keep their history; --clamp is what keeps the shadows it
+    moves from trailing."""
+    prims = [op for op in desc.ops if op[0] in ("mesh", "sphere", "plane", "area_light")]
+    lights = [k for k, op in enumerate(prims) if op[0] == "area_light"]
+    if not lights:
+        raise SystemExit("--light-orbit: the scene has no area light")
+    prim, op = lights[0], prims[lights[0]]
+    axis = np.asarray(desc.camera[1], np.float64)
+    d = op[1].astype(np.float64) - axis
+    draw = FrameDrawer(a, ctx, scene, desc, W, H)
+    for k in range(a.frames):
+        ang = np.deg2rad(a.light_orbit * k)
+        c = axis + np.array([np.cos(ang) * d[0] + np.sin(ang) * d[2], d[1], np.cos(ang) * d[2] - np.sin(ang) * d[0]])
+        t0 = time.time()
+        scene.update_sphere(prim, c.astype(np.float32), op[2])
+        t1 = time.time()
+        path, note = draw(k)
+        print("frame %d: light (primitive %d) at %.0f degrees in %.3f ms, %d spp%s in %.1f ms -> %s" %
+              (k, prim, a.light_orbit * k, (t1 - t0) * 1e3, a.spp, note, (time.time() - t1) * 1e3, path))
 
 
 def smooth_normals(a, scene, prim, op):
@@ -267,15 +292,20 @@ def main():
     ap.add_argument("--morph", type=int, default=0, metavar="N",
                     help="N frames at --spp each with the scene's last mesh (the blob of textured / mapped) morphed by two targets through "
                          "agpt_scene_set_mesh_morph_targets / agpt_scene_morph_mesh (OUT_0000.png ...)")
+    ap.add_argument("--light-orbit", type=float, default=0.0, metavar="DEG",
+                    help="--frames N: the scene's first area light moves DEG degrees per frame about the vertical axis through the camera's "
+                         "lookat (agpt_scene_update_sphere); the camera stays")
     ap.add_argument("--smooth-normals", action="store_true",
                     help="--spin, --bend, --morph: the moving mesh in AGPT_NORMALS_SMOOTH mode (agpt_scene_set_mesh_normals_mode): its vertex "
                          "normals are recomputed on the GPU from every frame's positions")
     a = ap.parse_args()
     if a.smooth_normals and not (a.spin or a.bend or a.morph):
         ap.error("--smooth-normals applies to --spin, --bend and --morph")
-    animated = a.spin or a.bend or a.morph
-    if (a.spin > 0) + (a.bend > 0) + (a.morph > 0) > 1:
-        ap.error("--spin, --bend and --morph are separate sequences")
+    animated = a.spin or a.bend or a.morph or a.light_orbit
+    if (a.spin > 0) + (a.bend > 0) + (a.morph > 0) + (a.light_orbit != 0) > 1:
+        ap.error("--spin, --bend, --morph and --light-orbit are separate sequences")
+    if a.light_orbit and a.frames < 2:
+        ap.error("--light-orbit applies to a sequence (--frames N, N >= 2)")
     if animated and a.orbit:
         ap.error("--orbit applies to --frames alone: --spin, --bend and --morph keep the scene's camera (with --frames F they stop after F frames)")
     if a.orbit and a.frames < 2 or a.temporal and a.frames < 2 and not animated:
@@ -285,7 +315,7 @@ def main():
     if a.clamp is not None and not a.clamp >= 0:
         ap.error("--clamp GAMMA must be non-negative")
     if a.motion and not (a.temporal and animated):
-        ap.error("--motion applies to --temporal with one of --spin, --bend and --morph")
+        ap.error("--motion applies to --temporal with one of --spin, --bend, --morph and --light-orbit")
     W, H = a.width, a.height
     aspect = W / float(H)
     desc = {"c1": lambda: ag.scenes.scene_c1(), "c2": lambda: ag.scenes.scene_c2(aspect=aspect),
@@ -322,6 +352,8 @@ def main():
         return render_bend(a, ctx, scene, desc, W, H)
     if a.morph:
         return render_morph(a, ctx, scene, desc, W, H)
+    if a.light_orbit:
+        return render_light_orbit(a, ctx, scene, desc, W, H)
     ptr = ctx.alloc(W * H * 16)
     ctx.memset(ptr, 0, W * H * 16)
     features = None
