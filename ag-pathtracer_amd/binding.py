@@ -42,6 +42,7 @@ EXPORTS = [
     "agpt_scene_commit", "agpt_mesh_num_nodes", "agpt_mesh_num_prims", "agpt_mesh_get_bvh", "agpt_bvh_build", "agpt_bvh_refit", "agpt_scene_update_mesh", "agpt_scene_update_mesh_device", "agpt_scene_transform_mesh", "agpt_transform_arrays", "agpt_skin_arrays", "agpt_scene_set_mesh_skin", "agpt_scene_pose_mesh", "agpt_morph_arrays", "agpt_scene_set_mesh_morph_targets", "agpt_scene_morph_mesh", "agpt_vertex_normals_arrays", "agpt_scene_set_mesh_normals_mode", "agpt_scene_set_bvh_builder", "agpt_scene_set_shading_arith", "agpt_scene_shade_variant", "agpt_bvh_build_device", "agpt_toplevel_build", "agpt_toplevel_pack16", "agpt_create_backdrop",
     "agpt_intersect_batch", "agpt_intersect_device", "agpt_render", "agpt_render_adaptive", "agpt_render_features", "agpt_denoise", "agpt_camera_vectors", "agpt_temporal_accumulate",
     "agpt_scene_snapshot_positions", "agpt_render_features_motion", "agpt_temporal_accumulate_motion", "agpt_temporal_accumulate_clamped", "agpt_li_batch", "agpt_resolve",
+    "agpt_scene_snapshot_surfaces", "agpt_render_features_surface_motion", "agpt_temporal_accumulate_surface_motion", "agpt_kat_surface",
     "agpt_scene_update_sphere", "agpt_scene_update_plane", "agpt_scene_set_area_light_radiance", "agpt_scene_set_infinite_light_radiance",
     "agpt_scene_update_spheres_device",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
@@ -233,6 +234,11 @@ def lib():
         L.agpt_temporal_accumulate_motion.argtypes = [vp, C.POINTER(TemporalParams)] + [vp] * 11
     if not variant or hasattr(L, "agpt_temporal_accumulate_clamped"):
         L.agpt_temporal_accumulate_clamped.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(TemporalClampParams)] + [vp] * 11
+    if not variant or hasattr(L, "agpt_scene_snapshot_surfaces"):
+        L.agpt_scene_snapshot_surfaces.argtypes = [vp]
+        L.agpt_render_features_surface_motion.argtypes = [vp, C.POINTER(RenderParams), vp, vp, vp, vp]
+        L.agpt_temporal_accumulate_surface_motion.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(TemporalClampParams)] + [vp] * 12
+        L.agpt_kat_surface.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint32), fp, fp, fp, fp]
     if not variant or hasattr(L, "agpt_scene_update_spheres_device"):
         L.agpt_scene_update_sphere.argtypes = [vp, C.c_int, fp, C.c_float]
         L.agpt_scene_update_plane.argtypes = [vp, C.c_int, fp, fp]
@@ -649,13 +655,31 @@ class Context:
                                                           albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur)]),
                "agpt_temporal_accumulate_clamped")
 
+    def temporal_accumulate_surface_motion(self, params, clamp, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev,
+                                           hist_moment2_prev, albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur,
+                                           prev_normal_cur):
+        """agpt_temporal_accumulate_surface_motion: temporal_accumulate_motion (clamp None) or temporal_accumulate_clamped with
+        prev_point_cur (clamp: a TemporalClampParams) whose normal test uses, for every pixel whose prev_point_cur.w is 1, the normal
+        PathTracer.render_features_surface_motion wrote into prev_normal_cur -- the one the surface point had a frame ago.  All DEVICE
+        pointers, full film."""
+        _check(self.L.agpt_temporal_accumulate_surface_motion(self.h, C.byref(params), C.byref(clamp) if clamp is not None else None,
+                                                              *[C.c_void_p(int(p)) if p else None for p in
+                                                                (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev,
+                                                                 hist_moment2_prev, albedo_prev, normal_depth_prev, hist_accum_out,
+                                                                 hist_moment2_out, prev_point_cur, prev_normal_cur)]),
+               "agpt_temporal_accumulate_surface_motion")
+
     def temporal_to_host(self, cam_cur, cam_prev, accum, moment2, albedo, normal_depth, prev=None, max_history=32.0,
-                         depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS, prev_point=None, clamp=None):
+                         depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS, prev_point=None, clamp=None, prev_normal=None):
         """Convenience for tests and tools: uploads this frame's host buffers ([H,W,4], [H,W], [H,W,4], [H,W,4]) and, unless prev is
         None (first frame), prev = (hist_accum, hist_moment2, albedo, normal_depth) of the previous frame; runs temporal_accumulate;
         returns (hist_accum[H,W,4], hist_moment2[H,W]).  cam_cur / cam_prev: CameraDesc or the argument tuple of Scene.set_camera.
         prev_point ([H,W,4], render_features_motion's third buffer): temporal_accumulate_motion runs instead.
-        clamp (a TemporalClampParams): temporal_accumulate_clamped runs instead of either, with prev_point if that is given."""
+        clamp (a TemporalClampParams): temporal_accumulate_clamped runs instead of either, with prev_point if that is given.
+        prev_normal ([H,W,4], render_features_surface_motion's fourth buffer; needs prev_point): temporal_accumulate_surface_motion
+        runs, with or without clamp."""
+        if prev_normal is not None and prev_point is None:
+            raise ValueError("temporal_to_host: prev_normal needs prev_point")
         H, W = np.shape(moment2)
         cams = [c if isinstance(c, CameraDesc) else camera_desc(*c) for c in (cam_cur, cam_prev)]
         host = [np.ascontiguousarray(a, np.float32) for a in (accum, moment2, albedo, normal_depth) + (tuple(prev) if prev is not None else ())]
@@ -673,7 +697,12 @@ class Context:
                 m = np.ascontiguousarray(prev_point, np.float32)
                 ptrs.append(self.alloc(m.nbytes))
                 self.upload(ptrs[-1], m)
-            if clamp is not None:
+            if prev_normal is not None:
+                m = np.ascontiguousarray(prev_normal, np.float32)
+                ptrs.append(self.alloc(m.nbytes))
+                self.upload(ptrs[-1], m)
+                self.temporal_accumulate_surface_motion(params, clamp, *ptrs)
+            elif clamp is not None:
                 self.temporal_accumulate_clamped(params, clamp, *ptrs)      # (ten buffers, or eleven with prev_point)
             elif prev_point is not None:
                 self.temporal_accumulate_motion(params, *ptrs)
@@ -972,6 +1001,26 @@ class Scene:
         newer one is filled from the device."""
         _check(self.L.agpt_scene_snapshot_positions(self.h), "agpt_scene_snapshot_positions")
 
+    def snapshot_surfaces(self):
+        """agpt_scene_snapshot_surfaces: snapshot_positions plus two generations of the per-triangle shading records; once per frame
+        in its place, before render_features_surface_motion."""
+        _check(self.L.agpt_scene_snapshot_surfaces(self.h), "agpt_scene_snapshot_surfaces")
+
+    def kat_surface(self, tri_ids, b1, b2, generation=-1):
+        """agpt_kat_surface: the surface reconstruction of a mesh hit alone for n global triangle ids and barycentrics, from the live
+        shading records (generation -1) or the newer (0) / older (1) generation of snapshot_surfaces -> (ns[n, 3], ss[n, 3])."""
+        ids = np.ascontiguousarray(np.asarray(tri_ids).reshape(-1), np.uint32)
+        b1, p1 = _f(np.asarray(b1).reshape(-1))
+        b2, p2 = _f(np.asarray(b2).reshape(-1))
+        if not ids.shape == b1.shape == b2.shape:
+            raise ValueError("kat_surface: tri_ids, b1 and b2 must have the same number of items")
+        ns = np.zeros((ids.shape[0], 3), np.float32)
+        ss = np.zeros((ids.shape[0], 3), np.float32)
+        fp = C.POINTER(C.c_float)
+        _check(self.L.agpt_kat_surface(self.h, int(generation), ids.shape[0], ids.ctypes.data_as(C.POINTER(C.c_uint32)), p1, p2,
+                                       ns.ctypes.data_as(fp), ss.ctypes.data_as(fp)), "agpt_kat_surface")
+        return ns, ss
+
     def set_bvh_builder(self, builder):
         """agpt_scene_set_bvh_builder: "host" (default) or "device" for the meshes added after this call; same bytes either way."""
         code = {"host": BVH_BUILDER_HOST, "device": BVH_BUILDER_DEVICE}[builder]
@@ -1241,6 +1290,34 @@ class PathTracer:
                 ptrs.append(ctx.alloc(W * H * 16))
                 ctx.memset(ptrs[-1], 0, W * H * 16)
             self.render_features_motion(scene, W, H, *ptrs, **kw)
+            return tuple(ctx.download(p, (H, W, 4)) for p in ptrs)
+        finally:
+            for p in ptrs:
+                ctx.free(p)
+
+    def render_features_surface_motion(self, scene, W, H, albedo_ptr, normal_depth_ptr, prev_point_ptr, prev_normal_ptr, tile=None,
+                                       accum_pitch=None, accum_row0=0):
+        """agpt_render_features_surface_motion: render_features_motion plus prev_normal_ptr (DEVICE float4, indexed like the other
+        three) = (the shading normal the hit surface point had at the scene's older snapshot, prev_point's w).  Needs
+        scene.snapshot_surfaces() first."""
+        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
+        rp = RenderParams(W, H, x0, y0, w, h, 0, 0, 0, self.MaxDepth, accum_pitch if accum_pitch is not None else W, accum_row0,
+                          0, 0, 0, 0, 0, 0, 0)
+        _check(scene.L.agpt_render_features_surface_motion(scene.h, C.byref(rp), *[C.c_void_p(int(p)) if p else None for p in
+                                                                                   (albedo_ptr, normal_depth_ptr, prev_point_ptr,
+                                                                                    prev_normal_ptr)]),
+               "agpt_render_features_surface_motion")
+
+    def render_features_surface_motion_to_host(self, scene, W, H, **kw):
+        """Convenience for tests and tools: render_features_surface_motion into zeroed full-film buffers, returns (albedo[H,W,4],
+        normal_depth[H,W,4], prev_point[H,W,4], prev_normal[H,W,4])."""
+        ctx = scene.ctx
+        ptrs = []
+        try:
+            for _ in range(4):
+                ptrs.append(ctx.alloc(W * H * 16))
+                ctx.memset(ptrs[-1], 0, W * H * 16)
+            self.render_features_surface_motion(scene, W, H, *ptrs, **kw)
             return tuple(ctx.download(p, (H, W, 4)) for p in ptrs)
         finally:
             for p in ptrs:

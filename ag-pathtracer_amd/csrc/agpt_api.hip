@@ -794,9 +794,10 @@ int agpt_render_adaptive(agpt_scene* s, const agpt_render_params* rp, const agpt
 
 // One closest-hit query per tile pixel through the pixel centre (k_feature_rays -> the trace launch of agpt_intersect_device), then
 // k_features: material colour + flag and shading normal + t.  motion (agpt_render_features_motion, `fn` names the entry point that was
-// called): k_motion then reads the same hits and rays into prev_point_dev.
-static int render_features(const char* fn, bool motion, agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev,
-                           float* prev_point_dev) {
+// called): k_motion then reads the same hits and rays into prev_point_dev.  surfaces (agpt_render_features_surface_motion): k_motion runs
+// first and the feature kernel's PREV sibling reads its prev_point and the older tri_shade generation into prev_normal_dev.
+static int render_features(const char* fn, bool motion, bool surfaces, agpt_scene* s, const agpt_render_params* rp, float* albedo_dev,
+                           float* normal_depth_dev, float* prev_point_dev, float* prev_normal_dev) {
     const std::string f(fn);
     if (!rp) return fail(AGPT_ERR_INVALID, f + ": NULL argument");
     if (rp->spp_begin != 0 || rp->spp_count != 0)
@@ -815,6 +816,13 @@ static int render_features(const char* fn, bool motion, agpt_scene* s, const agp
         if (!s->snapshots.valid)
             return fail(AGPT_ERR_INVALID, f + ": no position snapshot yet (agpt_scene_snapshot_positions comes first)");
     }
+    if (surfaces) {
+        if (!prev_normal_dev) return fail(AGPT_ERR_INVALID, f + ": NULL prev_normal_dev");
+        if (prev_normal_dev == albedo_dev || prev_normal_dev == normal_depth_dev || prev_normal_dev == prev_point_dev)
+            return fail(AGPT_ERR_INVALID, f + ": prev_normal_dev aliases another output");
+        if (!s->snapshots.surfaces)
+            return fail(AGPT_ERR_INVALID, f + ": no generations of the shading records (agpt_scene_snapshot_surfaces comes first)");
+    }
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint64_t np64 = (uint64_t)rp->w * (uint64_t)rp->h;
@@ -827,13 +835,17 @@ static int render_features(const char* fn, bool motion, agpt_scene* s, const agp
     HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
     agpt::launch_feature_rays(c->stream, s->dev, rcn, c->ext_o.p, c->ext_d.p);
     trace_rays(c, s->dev, NP, false, 0);
-    agpt::launch_features(c->stream, s->dev, s->shade_level, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
-                          (float4*)normal_depth_dev);
-    if (motion) {
-        const agpt_scene::PositionSnapshots& ps = s->snapshots;
+    const agpt_scene::PositionSnapshots& ps = s->snapshots;
+    if (!surfaces)
+        agpt::launch_features(c->stream, s->dev, s->shade_level, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
+                              (float4*)normal_depth_dev);
+    if (motion)
         agpt::launch_motion(c->stream, rcn, c->hit.p, c->ext_o.p, c->ext_d.p, ps.gen[ps.newest ^ 1].p, ps.gen[ps.newest].p, (uint32_t)ps.n_tris,
                             ps.analytic[ps.newest ^ 1].p, ps.analytic[ps.newest].p, (uint32_t)ps.n_prims, (float4*)prev_point_dev);
-    }
+    if (surfaces)
+        agpt::launch_features_prev(c->stream, s->dev, s->shade_level, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,
+                                   (float4*)normal_depth_dev, ps.shade[ps.newest ^ 1].p, (const float4*)prev_point_dev,
+                                   (float4*)prev_normal_dev);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipGetLastError());
     HIP_TRY(c->take_deferred());
@@ -841,11 +853,17 @@ static int render_features(const char* fn, bool motion, agpt_scene* s, const agp
 }
 
 int agpt_render_features(agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev) {
-    return render_features("agpt_render_features", false, s, rp, albedo_dev, normal_depth_dev, nullptr);
+    return render_features("agpt_render_features", false, false, s, rp, albedo_dev, normal_depth_dev, nullptr, nullptr);
 }
 
 int agpt_render_features_motion(agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev, float* prev_point_dev) {
-    return render_features("agpt_render_features_motion", true, s, rp, albedo_dev, normal_depth_dev, prev_point_dev);
+    return render_features("agpt_render_features_motion", true, false, s, rp, albedo_dev, normal_depth_dev, prev_point_dev, nullptr);
+}
+
+int agpt_render_features_surface_motion(agpt_scene* s, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev,
+                                        float* prev_point_dev, float* prev_normal_dev) {
+    return render_features("agpt_render_features_surface_motion", true, true, s, rp, albedo_dev, normal_depth_dev, prev_point_dev,
+                           prev_normal_dev);
 }
 
 int agpt_li_batch(agpt_scene* s, const agpt_ray* rays, const uint32_t* rng_states, int n, int max_depth, float* radiance3_out,

@@ -34,4 +34,10 @@ void launch_feature_rays(hipStream_t stream, const DevScene& sc, const RenderCon
 // level (agpt_scene_commit), which picks the feature kernel
 void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, const RenderConsts& rc, const float4* colors,
                      const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth);
+// launch_features through the kernels' PREV siblings (agpt_render_features_surface_motion): prev_normal as well, from prev_point -- which
+// launch_motion (agpt_motion.h) wrote for the same hits, earlier on the stream -- and the older generation of tri_shade records.
+// tri_shade_old is read for pixels whose prev_point.w is 1 on a triangle only; NULL for a scene without triangles.
+void launch_features_prev(hipStream_t stream, const DevScene& sc, ShadeLevel level, const RenderConsts& rc, const float4* colors,
+                          const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth,
+                          const float4* tri_shade_old, const float4* prev_point, float4* prev_normal);
 }  // namespace agpt

@@ -3,7 +3,8 @@
 // Features: k_feature_rays writes one camera ray per tile pixel through the pixel centre (Camera::GetRay with a zero lens offset, no
 // RNG), the library's closest-hit trace launch follows (agpt_api.hip, the path of agpt_intersect_device), and k_features turns each
 // hit record into (material colour, flag) and (shading normal, t) with the surface reconstruction k_shade uses (agpt_shade.h;
-// spheres: (p - c) / r, see k_features).
+// spheres: (p - c) / r, see k_features).  agpt_render_features_surface_motion runs the PREV siblings of the four feature kernels, which
+// also write the shading normal a moved triangle's hit had a frame ago (features_pixel's PREV flag).
 //
 // Denoiser: k_denoise_prepare turns the adaptive buffers into the per-pixel state (mean radiance -- demodulated by the albedo on
 // request --, variance of the mean luminance), k_denoise_pass is one a-trous pass of 25 taps at a given spacing.  Every pixel is
@@ -58,11 +59,16 @@ k_feature_rays(DevCamera c, RenderConsts rc, float4* __restrict__ ray_o, float4*
 // sampler): the filtered colour k_shade_sampled shades it with (texture_address / texture_load / texture_blend); NORMAL (scenes in which
 // a material has a normal map): SAMPLED, and normal_depth.xyz is the shading normal k_shade_normal perturbs at that hit
 // (surface_apply_normal_map, agpt_shade.h) -- the albedo stays the colour
-template <bool TEXTURED, bool SAMPLED = false, bool NORMAL = false>
+// PREV (agpt_render_features_surface_motion): prev_normal = (n.xyz, prev_point.w), prev_point being what k_motion wrote for this launch's
+// hits.  n = normal_depth.xyz, except on a moved triangle (w == 1): there the same reconstruction runs a second time on the triangle's
+// record in tri_shade_old -- the older generation of agpt_scene_snapshot_surfaces -- at this hit's barycentrics, and at NORMAL the same
+// texel and scale perturb it: the shading normal this surface point had a frame ago.  Zero on a miss.
+template <bool TEXTURED, bool SAMPLED = false, bool NORMAL = false, bool PREV = false>
 __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderConsts& rc, const float4* __restrict__ colors,
                                                const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
                                                const float4* __restrict__ ray_d, float4* __restrict__ albedo,
-                                               float4* __restrict__ normal_depth) {
+                                               float4* __restrict__ normal_depth, const float4* __restrict__ tri_shade_old = nullptr,
+                                               const float4* __restrict__ prev_point = nullptr, float4* __restrict__ prev_normal = nullptr) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rc.NP) return;
     int x, y;
@@ -72,10 +78,17 @@ __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderC
     float4 a, nd;
     a.x = 1.f; a.y = 1.f; a.z = 1.f; a.w = 0.f;
     nd.x = 0.f; nd.y = 0.f; nd.z = 0.f; nd.w = 0.f;
+    [[maybe_unused]] float4 pn;
+    [[maybe_unused]] Surface s_old;
+    [[maybe_unused]] bool followed = false;   // a moved triangle: s_old is its hit as the older record has it
+    if constexpr (PREV) {
+        pn.x = 0.f; pn.y = 0.f; pn.z = 0.f; pn.w = 0.f;
+    }
     if (h.id != AGPT_HIT_MISS) {
         const float4 o4 = ray_o[i], d4 = ray_d[i];
         const v3 O = V3(o4.x, o4.y, o4.z), D = V3(d4.x, d4.y, d4.z);
         Surface s;
+        if constexpr (PREV) pn.w = prev_point[ai].w;
         if (h.id & AGPT_HIT_SPHERE) {
             const int prim = (int)(h.id & 0x7FFFFFFFu);
             const DevPrim& P = sc.prims[prim];
@@ -91,6 +104,14 @@ __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderC
             }
         } else {
             surface_from_triangle(sc, h.id, h.b1, h.b2, O, D, h.t, s);
+            if constexpr (PREV) {
+                if (pn.w == 1.f) {   // (k_motion sets it for ids below the snapshots' triangle count only)
+                    DevScene was = sc;
+                    was.tri_shade = tri_shade_old;
+                    surface_from_triangle(was, h.id, h.b1, h.b2, O, D, h.t, s_old);
+                    followed = true;
+                }
+            }
         }
         const int mat = sc.prims[s.prim].material;
         a.w = 2.f;
@@ -115,7 +136,13 @@ __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderC
                         texture_load(ta, k);
                         if (n_own) texture_load(na, nk);
                         c = texture_blend(ta, k);
-                        if (slot.texture >= 0) surface_apply_normal_map(s, n_own ? texture_blend(na, nk) : c, slot.scale);
+                        if (slot.texture >= 0) {
+                            const v3 texel = n_own ? texture_blend(na, nk) : c;
+                            surface_apply_normal_map(s, texel, slot.scale);
+                            if constexpr (PREV) {
+                                if (followed) surface_apply_normal_map(s_old, texel, slot.scale);
+                            }
+                        }
                     } else if constexpr (SAMPLED) {
                         TextureAddress ta;
                         TextureTaps k;
@@ -131,9 +158,14 @@ __device__ __forceinline__ void features_pixel(const DevScene& sc, const RenderC
             a.w = 1.f;
         }
         nd.x = s.ns.x; nd.y = s.ns.y; nd.z = s.ns.z; nd.w = h.t;
+        if constexpr (PREV) {
+            const v3 n = followed ? s_old.ns : s.ns;
+            pn.x = n.x; pn.y = n.y; pn.z = n.z;
+        }
     }
     albedo[ai] = a;
     normal_depth[ai] = nd;
+    if constexpr (PREV) prev_normal[ai] = pn;
 }
 __global__ void __launch_bounds__(AGPT_BLOCK)
 k_features(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,
@@ -159,6 +191,20 @@ k_features_normal(DevScene sc, RenderConsts rc, const float4* __restrict__ color
                   float4* __restrict__ normal_depth) {
     features_pixel<true, true, true>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
 }
+
+// the four siblings of agpt_render_features_surface_motion: the same bodies with PREV
+#define AGPT_FEATURES_PREV_KERNEL(name, ...)                                                                                            \
+    __global__ void __launch_bounds__(AGPT_BLOCK)                                                                                       \
+    name(DevScene sc, RenderConsts rc, const float4* __restrict__ colors, const DevHit* __restrict__ hits, const float4* __restrict__ ray_o,   \
+         const float4* __restrict__ ray_d, float4* __restrict__ albedo, float4* __restrict__ normal_depth,                              \
+         const float4* __restrict__ tri_shade_old, const float4* __restrict__ prev_point, float4* __restrict__ prev_normal) {            \
+        features_pixel<__VA_ARGS__, true>(sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth, tri_shade_old, prev_point, prev_normal); \
+    }
+AGPT_FEATURES_PREV_KERNEL(k_features_prev, false, false, false)
+AGPT_FEATURES_PREV_KERNEL(k_features_textured_prev, true, false, false)
+AGPT_FEATURES_PREV_KERNEL(k_features_sampled_prev, true, true, false)
+AGPT_FEATURES_PREV_KERNEL(k_features_normal_prev, true, true, true)
+#undef AGPT_FEATURES_PREV_KERNEL
 
 // state = (c.rgb, v): c = accum.rgb / n, v = the variance of the mean luminance from agpt_render_adaptive's estimate
 // (max(0, moment2 / n - mu * mu) * n / (n - 1) / n; 0 for n < 2); with demodulate both in units of the floored albedo.
@@ -275,6 +321,20 @@ void launch_features(hipStream_t stream, const DevScene& sc, ShadeLevel level, c
     default: break;
     }
     hipLaunchKernelGGL(kernel, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth);
+}
+void launch_features_prev(hipStream_t stream, const DevScene& sc, ShadeLevel level, const RenderConsts& rc, const float4* colors,
+                          const DevHit* hits, const float4* ray_o, const float4* ray_d, float4* albedo, float4* normal_depth,
+                          const float4* tri_shade_old, const float4* prev_point, float4* prev_normal) {
+    auto* kernel = k_features_prev;   // SHADE_PLAIN
+    switch (level) {
+    case SHADE_TEXTURED:
+    case SHADE_MAPPED: kernel = k_features_textured_prev; break;
+    case SHADE_SAMPLED: kernel = k_features_sampled_prev; break;
+    case SHADE_NORMAL: kernel = k_features_normal_prev; break;
+    default: break;
+    }
+    hipLaunchKernelGGL(kernel, agpt_blocks(rc.NP), dim3(AGPT_BLOCK), 0, stream, sc, rc, colors, hits, ray_o, ray_d, albedo, normal_depth,
+                       tri_shade_old, prev_point, prev_normal);
 }
 
 }  // namespace agpt

@@ -1,7 +1,7 @@
 // agpt_internal.h -- what the units that define the C entry points of include/agpt.h share: error reporting, the owning device
 // buffer, and the context and the scene behind the two opaque handles.  Those units are agpt_api.hip (context, pool, trace launches,
 // wavefront loop, renderers), agpt_scene_api.hip (scene building, commit, host BVH, mesh updates), agpt_kat.hip, agpt_comm.hip, and
-// the entry points that sit beside their kernels (agpt_adaptive.hip, agpt_denoise.hip, agpt_temporal.hip, agpt_motion.hip, agpt_analytic.hip).  Only .hip / .cpp units
+// the entry points that sit beside their kernels (agpt_adaptive.hip, agpt_denoise.hip, agpt_temporal.hip, agpt_motion.hip, agpt_analytic.hip, agpt_temporal_clamp.hip, agpt_surface_motion.hip).  Only .hip / .cpp units
 // include this file, no other header does.
 #pragma once
 
@@ -237,16 +237,25 @@ struct agpt_scene {
     // AGPT_UPDATE_REBUILD, which re-commits with the triangle ids unchanged, keeps them (update_on_host).
     // analytic[]: the same two generations of the sphere and plane records, two float4 per primitive index (agpt_analytic.h), with the
     // same lifetime; filled from d_prims, so every update route is seen.  Empty for a scene without a sphere or a plane.
+    // shade[]: agpt_scene_snapshot_surfaces' two generations of the tri_shade records, float4[4 * n_tris] each, copied from d_tri_shade,
+    // flipped with the positions (shade[newest] is the newer one).  surfaces: they are present -- the scene's last snapshot was made by
+    // agpt_scene_snapshot_surfaces; agpt_scene_snapshot_positions frees them.  Never allocated for a scene that does not call it.
     struct PositionSnapshots {
-        DevBuf<float4> gen[2], analytic[2];
+        DevBuf<float4> gen[2], analytic[2], shade[2];
         int newest = 0;
         size_t n_tris = 0, n_prims = 0;
-        bool valid = false;
+        bool valid = false, surfaces = false;
+        void drop_surfaces() {
+            shade[0].release();
+            shade[1].release();
+            surfaces = false;
+        }
         void drop() {
             for (int g = 0; g < 2; g++) {
                 gen[g].release();
                 analytic[g].release();
             }
+            drop_surfaces();
             n_tris = n_prims = 0;
             valid = false;
         }

@@ -1,5 +1,5 @@
 // agpt_kat.hip -- the known-answer entry points of include/agpt.h and their kernels: one piece of the device arithmetic each (the
-// BSDF functions and the normal-map perturbation of agpt_shade.h, the environment map's sampler, the RNG streams), run on caller-supplied
+// BSDF functions, the surface reconstruction and the normal-map perturbation of agpt_shade.h, the environment map's sampler, the RNG streams), run on caller-supplied
 // cases, one lane per case.  The exact arithmetic; the fast-arithmetic BSDF kernels are compiled in their own unit
 // (agpt_shade_kernels_fast.hip).
 #include <hip/hip_runtime.h>
@@ -41,6 +41,20 @@ __global__ void k_kat_rng(uint32_t pixel, uint32_t wh, uint32_t sample, uint32_t
     uint32_t s = sample_seed(pixel, wh, sample, seed_base);
     *seed_out = s;
     for (int i = 0; i < n; i++) out[i] = rng_float(s);
+}
+
+// agpt_kat_surface: surface_from_triangle (agpt_shade.h) alone on the records at tri_shade -- the scene's, or a generation of
+// agpt_scene_snapshot_surfaces --, one lane per item; the ray (origin 0, direction +z, t = 1) reaches p and wo only, which are not returned
+__global__ void k_kat_surface(DevScene sc, const float4* __restrict__ tri_shade, int n, const uint32_t* __restrict__ tri_ids,
+                              const float* __restrict__ b1, const float* __restrict__ b2, float* __restrict__ ns3, float* __restrict__ ss3) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    DevScene from = sc;
+    from.tri_shade = tri_shade;
+    Surface s;
+    surface_from_triangle(from, tri_ids[i], b1[i], b2[i], V3s(0.f), V3(0.f, 0.f, 1.f), 1.f, s);
+    ns3[3 * i] = s.ns.x; ns3[3 * i + 1] = s.ns.y; ns3[3 * i + 2] = s.ns.z;
+    ss3[3 * i] = s.ss_bsdf.x; ss3[3 * i + 1] = s.ss_bsdf.y; ss3[3 * i + 2] = s.ss_bsdf.z;
 }
 
 // what follows every launch here: its launch error, then its completion
@@ -106,6 +120,34 @@ int agpt_kat_normal_map(agpt_ctx* c, int n, const float* ns3, const float* ss3, 
     hipLaunchKernelGGL(k_kat_normal_map, dim3((n + 63) / 64), dim3(64), 0, c->stream, n, d_ns.p, d_ss.p, d_rgb.p, scale, d_o.p);
     if ((rc = launched(c))) return rc;
     return d_o.out(ns_out3, 3 * (size_t)n);
+}
+
+int agpt_kat_surface(agpt_scene* s, int generation, int n, const uint32_t* tri_ids, const float* b1, const float* b2, float* ns3_out,
+                     float* ss3_out) {
+    if (!s || !s->committed || generation < -1 || generation > 1 || n <= 0 || !tri_ids || !b1 || !b2 || !ns3_out || !ss3_out)
+        return fail(AGPT_ERR_INVALID, "agpt_kat_surface: bad argument");
+    size_t n_tris = 0;
+    for (const agpt::HostMesh& m : s->meshes) n_tris += m.prim_index.size();
+    const agpt_scene::PositionSnapshots& ps = s->snapshots;
+    const float4* records = s->d_tri_shade.p;
+    if (generation >= 0) {
+        if (!ps.surfaces || !n_tris) return fail(AGPT_ERR_INVALID, "agpt_kat_surface: the scene has no such generation of shading records");
+        records = ps.shade[ps.newest ^ generation].p;
+    }
+    if (4 * n_tris > s->d_tri_shade.n) return fail(AGPT_ERR_DEVICE, "agpt_kat_surface: the scene's records do not cover its meshes");
+    for (int i = 0; i < n; i++)
+        if (tri_ids[i] >= n_tris) return fail(AGPT_ERR_INVALID, "agpt_kat_surface: triangle id out of range");
+    agpt_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<uint32_t> d_id;
+    DevBuf<float> d_b1, d_b2, d_ns, d_ss;
+    int rc;
+    if ((rc = d_id.in(tri_ids, (size_t)n)) || (rc = d_b1.in(b1, (size_t)n)) || (rc = d_b2.in(b2, (size_t)n))) return rc;
+    HIP_TRY(d_ns.alloc(3 * (size_t)n));
+    HIP_TRY(d_ss.alloc(3 * (size_t)n));
+    hipLaunchKernelGGL(k_kat_surface, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, records, n, d_id.p, d_b1.p, d_b2.p, d_ns.p, d_ss.p);
+    if ((rc = launched(c)) || (rc = d_ns.out(ns3_out, 3 * (size_t)n))) return rc;
+    return d_ss.out(ss3_out, 3 * (size_t)n);
 }
 
 int agpt_kat_rng(agpt_ctx* c, uint32_t pixel, uint32_t wh, uint32_t sample, uint32_t seed_base, int n, float* out,

@@ -1,6 +1,7 @@
 // agpt_motion.hip -- per-object motion vectors for the temporal reprojection (include/agpt.h): the kernels of
 // agpt_scene_snapshot_positions, agpt_render_features_motion (the entry point is in agpt_api.hip, beside agpt_render_features) and
-// agpt_temporal_accumulate_motion.
+// agpt_temporal_accumulate_motion.  agpt_scene_snapshot_surfaces is defined here too: the same snapshot plus a device-to-device copy of
+// the tri_shade records, no kernel of its own.
 //
 // k_snapshot_positions copies the world-space positions the update calls left in tri_verts (BVH slot order) into a buffer indexed by
 // the global triangle id, so two snapshots compare triangle by triangle whatever a rebuild did to the slot order.  k_motion turns a
@@ -11,6 +12,8 @@
 // a mesh's range by its leaf order.  k_motion: per pixel 16 B of hit and 32 B of ray, contiguous, and on a mesh hit 2 x 48 B gathered at
 // the hit triangle (a wave's pixels share a few triangles), 16 B written.  k_temporal_motion: k_temporal plus 16 B per pixel.
 #include <hip/hip_runtime.h>
+
+#include <string>
 
 #include "agpt_analytic.h"
 #include "agpt_internal.h"
@@ -118,23 +121,25 @@ void launch_motion(hipStream_t stream, const RenderConsts& rc, const DevHit* hit
 
 }  // namespace agpt
 
-extern "C" {
-
 // The newer generation becomes the older one; the newer one is filled from what the update calls left in tri_verts and -- the spheres
 // and planes -- in d_prims.  The first call allocates both and fills both with the same bytes.
-int agpt_scene_snapshot_positions(agpt_scene* s) {
-    if (!s) return fail(AGPT_ERR_INVALID, "agpt_scene_snapshot_positions: NULL scene");
-    if (!s->committed) return fail(AGPT_ERR_INVALID, "agpt_scene_snapshot_positions: the scene is not committed");
+// surfaces (agpt_scene_snapshot_surfaces, `fn` names the entry point that was called): the tri_shade records as well, one device-to-device
+// copy behind the updates; without it the shading generations are freed.
+static int snapshot(const char* fn, bool surfaces, agpt_scene* s) {
+    const std::string f(fn);
+    if (!s) return fail(AGPT_ERR_INVALID, f + ": NULL scene");
+    if (!s->committed) return fail(AGPT_ERR_INVALID, f + ": the scene is not committed");
     size_t n_tris = 0, n_prims = 0;
     for (const agpt::HostMesh& m : s->meshes) n_tris += m.prim_index.size();
     if (!s->spheres.empty()) n_prims = s->prims.size();   // (records by primitive index; none for a scene of meshes only)
     agpt_scene::PositionSnapshots& ps = s->snapshots;
     if (n_tris == 0 && n_prims == 0) {   // nothing to hold: every hit of such a scene is a miss
         ps.valid = true;
+        ps.surfaces = surfaces;
         return AGPT_OK;
     }
-    if (3 * n_tris > s->d_tri_verts.n || n_tris > 0x7FFFFFFFull || n_prims > s->d_prims.n)
-        return fail(AGPT_ERR_DEVICE, "agpt_scene_snapshot_positions: the scene's records do not cover its meshes and primitives");
+    if (3 * n_tris > s->d_tri_verts.n || n_tris > 0x7FFFFFFFull || n_prims > s->d_prims.n || (surfaces && 4 * n_tris > s->d_tri_shade.n))
+        return fail(AGPT_ERR_DEVICE, f + ": the scene's records do not cover its meshes and primitives");
     agpt_ctx* c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const bool first = !ps.valid;
@@ -147,7 +152,7 @@ int agpt_scene_snapshot_positions(agpt_scene* s) {
         }
         if (!ok) {
             ps.drop();
-            return fail(AGPT_ERR_NOMEM, "agpt_scene_snapshot_positions: out of device memory");
+            return fail(AGPT_ERR_NOMEM, f + ": out of device memory");
         }
         ps.n_tris = n_tris;
         ps.n_prims = n_prims;
@@ -163,10 +168,34 @@ int agpt_scene_snapshot_positions(agpt_scene* s) {
     if (first && n_prims)
         HIP_TRY(hipMemcpyAsync(ps.analytic[ps.newest ^ 1].p, ps.analytic[ps.newest].p, n_analytic * sizeof(float4), hipMemcpyDeviceToDevice,
                                c->stream));
+    if (!surfaces) {
+        ps.drop_surfaces();
+    } else if (n_tris) {
+        // absent (no snapshot yet, or the last one was agpt_scene_snapshot_positions'): both generations get the current bytes.
+        // d_tri_shade.p is read now: an AGPT_UPDATE_REBUILD may have reallocated it.
+        const bool absent = !ps.surfaces;
+        const size_t bytes = 4 * n_tris * sizeof(float4);
+        if (absent && (ps.shade[0].alloc(4 * n_tris) != hipSuccess || ps.shade[1].alloc(4 * n_tris) != hipSuccess)) {
+            ps.drop_surfaces();
+            (void)hipStreamSynchronize(c->stream);
+            ps.valid = true;   // (the positions were taken)
+            return fail(AGPT_ERR_NOMEM, f + ": out of device memory");
+        }
+        HIP_TRY(hipMemcpyAsync(ps.shade[ps.newest].p, s->d_tri_shade.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (absent) HIP_TRY(hipMemcpyAsync(ps.shade[ps.newest ^ 1].p, s->d_tri_shade.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     ps.valid = true;
+    ps.surfaces = surfaces;
     return AGPT_OK;
 }
+
+extern "C" {
+
+int agpt_scene_snapshot_positions(agpt_scene* s) { return snapshot("agpt_scene_snapshot_positions", false, s); }
+
+// agpt_scene_snapshot_positions plus two generations of the tri_shade records (PositionSnapshots::shade)
+int agpt_scene_snapshot_surfaces(agpt_scene* s) { return snapshot("agpt_scene_snapshot_surfaces", true, s); }
 
 // agpt_temporal_accumulate with step 3 decided per pixel by prev_point_cur: one k_temporal_motion launch
 int agpt_temporal_accumulate_motion(agpt_ctx* c, const agpt_temporal_params* p, const float* accum_cur_dev, const float* moment2_cur_dev,

@@ -23,14 +23,25 @@ struct TemporalSums {
 // Steps 3 and 4 for film pixel (x, y), buffer index i, by the calling thread alone -> whether the pixel has history (step 5's
 // sb >= AGPT_TEMPORAL_MIN_WEIGHT), and then its sums.  moved: reproject the point m (agpt_temporal_accumulate_motion's w == 1:
 // Q = m - P.origin, with the arithmetic even when the cameras are the same bytes) instead of the point the pixel sees now.
+// SURFACE (agpt_temporal_accumulate_surface_motion): for a moved pixel the normal that step 4 compares with each tap's is
+// prev_normal_cur[i].xyz -- the one that surface point had a frame ago (agpt_render_features_surface_motion) -- read for moved pixels only;
+// every other pixel, and every caller without SURFACE, compares the current one.
+template <bool SURFACE = false>
 __device__ __forceinline__ bool temporal_gather(const TemporalConsts& tc, int x, int y, size_t i, bool moved, v3 m,
                                                 const float4* __restrict__ albedo_cur, const float4* __restrict__ normal_depth_cur,
                                                 const float4* __restrict__ hist_accum_prev, const float* __restrict__ hist_moment2_prev,
                                                 const float4* __restrict__ albedo_prev, const float4* __restrict__ normal_depth_prev,
-                                                TemporalSums& ts) {
+                                                TemporalSums& ts, const float4* __restrict__ prev_normal_cur = nullptr) {
     const float flag = albedo_cur[i].w;
     const float4 g = normal_depth_cur[i];
     const bool geometry = flag != 0.f;
+    v3 nref = V3(g.x, g.y, g.z);
+    if constexpr (SURFACE) {
+        if (moved) {
+            const float4 pn = prev_normal_cur[i];
+            nref = V3(pn.x, pn.y, pn.z);
+        }
+    }
     // the position on the previous film
     bool found = true;
     int x0 = x, y0 = y;
@@ -80,7 +91,7 @@ __device__ __forceinline__ bool temporal_gather(const TemporalConsts& tc, int x,
             const float4 gq = normal_depth_prev[q];
             // (one test on the whole record: the compiler would split a short-circuit into a 4-byte and a 12-byte load)
             const bool near = fabsf(te - gq.w) <= zmax;
-            const bool facing = dot(V3(g.x, g.y, g.z), V3(gq.x, gq.y, gq.z)) >= tc.normal_cos;
+            const bool facing = dot(nref, V3(gq.x, gq.y, gq.z)) >= tc.normal_cos;
             if (!(near & facing)) continue;
         }
         sb += b;
@@ -97,13 +108,14 @@ __device__ __forceinline__ bool temporal_gather(const TemporalConsts& tc, int x,
 // One film pixel of agpt_temporal_accumulate's contract (include/agpt.h), steps 1-6, by the calling thread alone.
 // MOTION (agpt_temporal_accumulate_motion): prev_point_cur[i] = (p.xyz, w) of agpt_render_features_motion; w == 1 makes p the point
 // that is reprojected, any other w leaves step 3 as it is without MOTION.  Read only when there is history to fetch.
-template <bool MOTION>
+// SURFACE: temporal_gather's, with prev_normal_cur.
+template <bool MOTION, bool SURFACE = false>
 __device__ __forceinline__ void temporal_pixel(const TemporalConsts& tc, const float4* __restrict__ accum_cur, const float* __restrict__ moment2_cur,
                                                const float4* __restrict__ albedo_cur, const float4* __restrict__ normal_depth_cur,
                                                const float4* __restrict__ hist_accum_prev, const float* __restrict__ hist_moment2_prev,
                                                const float4* __restrict__ albedo_prev, const float4* __restrict__ normal_depth_prev,
                                                const float4* __restrict__ prev_point_cur, float4* __restrict__ hist_accum_out,
-                                               float* __restrict__ hist_moment2_out) {
+                                               float* __restrict__ hist_moment2_out, const float4* __restrict__ prev_normal_cur = nullptr) {
     const int x = (int)(blockIdx.x * AGPT_DN_TX + (threadIdx.x & (AGPT_DN_TX - 1)));
     const int row = (int)(blockIdx.y * AGPT_DN_TY + threadIdx.x / AGPT_DN_TX);   // buffer row: film row H - 1 - row
     if (x >= tc.W || row >= tc.H) return;
@@ -120,8 +132,8 @@ __device__ __forceinline__ void temporal_pixel(const TemporalConsts& tc, const f
             m = V3(m4.x, m4.y, m4.z);
         }
         TemporalSums ts;
-        if (temporal_gather(tc, x, y, i, moved, m, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev,
-                            normal_depth_prev, ts)) {
+        if (temporal_gather<SURFACE>(tc, x, y, i, moved, m, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev,
+                                     normal_depth_prev, ts, prev_normal_cur)) {
             const float n_h = fminf(ts.sn / ts.sb, tc.max_history);
             out.x = out.x + (ts.sr / ts.sb) * n_h;
             out.y = out.y + (ts.sg / ts.sb) * n_h;

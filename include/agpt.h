@@ -800,8 +800,9 @@ int agpt_render_features_motion(agpt_scene*, const agpt_render_params* rp, float
  * On the first frame (prev NULL) the outputs are the current values bit for bit and prev_point_cur is not read.  Where every w != 1
  * the outputs are agpt_temporal_accumulate's, bit for bit.  Checks: agpt_temporal_accumulate's in their order, then a NULL
  * prev_point_cur_dev, then an output aliasing it (AGPT_ERR_INVALID).
- * Limits: the normal test still compares the current normal with the previous tap's, so a surface that turns by more than
- * acos(normal_cos) within one frame is rejected; no motion vectors behind specular bounces; a moved light's sphere carries its own
+ * Limits: the normal test compares the current normal with the previous tap's, so a surface that turns by more than
+ * acos(normal_cos) within one frame is rejected -- agpt_temporal_accumulate_surface_motion (below) compares the normal the surface
+ * point had a frame ago instead; no motion vectors behind specular bounces; a moved light's sphere carries its own
  * history, but what it lights is followed by agpt_temporal_accumulate_clamped only; one GPU, full film. */
 int agpt_temporal_accumulate_motion(agpt_ctx*, const agpt_temporal_params*,
         const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
@@ -846,6 +847,50 @@ int agpt_temporal_accumulate_clamped(agpt_ctx*, const agpt_temporal_params*, con
         const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
         const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
         float* hist_accum_out_dev, float* hist_moment2_out_dev, const float* prev_point_cur_dev /* may be NULL */);
+
+/* ---- previous-frame normals: temporal history that follows turning surfaces --------------------------------------------
+ * agpt_temporal_accumulate_motion finds the previous pixel of a moved surface point and then tests the normal it has NOW against the
+ * normal the previous frame stored there: a surface that turned by more than acos(normal_cos) loses its history.  The three calls
+ * below carry the shading normal the point had a frame ago.  Per frame:
+ *     update calls -> agpt_scene_snapshot_surfaces -> agpt_render_adaptive -> agpt_render_features_surface_motion
+ *                  -> agpt_temporal_accumulate_surface_motion -> agpt_denoise
+ *
+ * agpt_scene_snapshot_surfaces: agpt_scene_snapshot_positions -- the same rules, the same generation flip, the same analytic records --
+ * and two generations of the per-triangle shading records (64 B per global triangle id: geometric normal, tangent, the three vertex
+ * normals, primitive id; float4[4 * T] each, 128 B per triangle for the two).  The newer one is filled by one device-to-device copy of the
+ * records every update route leaves on the device, on the context's stream behind the updates.  The first call allocates both and
+ * leaves the same bytes in both.  If the scene's last snapshot was made by agpt_scene_snapshot_positions, or there was none, the shading
+ * generations count as absent and the call behaves like a first call for them; agpt_scene_snapshot_positions after this call frees them.
+ * agpt_scene_commit drops them, an AGPT_UPDATE_REBUILD keeps them.  T == 0 skips the shading part.  Errors as agpt_scene_snapshot_positions. */
+int agpt_scene_snapshot_surfaces(agpt_scene*);
+
+/* agpt_render_features_surface_motion: agpt_render_features_motion -- albedo, normal_depth and prev_point byte for byte -- plus
+ * prev_normal_dev (DEVICE float4, indexed like the others) = (n.xyz, w), w = prev_point's w:
+ *     a miss                           (0, 0, 0, 0)
+ *     w == 2                           n = the bits of normal_depth.xyz
+ *     w == 1, a sphere or a plane      n = the bits of normal_depth.xyz (spheres do not rotate; a plane's normal is +y)
+ *     w == 1, a triangle g             n = what normal_depth.xyz would be for this hit if g's shading record were the OLDER generation's:
+ *                                      the same reconstruction at this hit's barycentrics (the interpolated-normal frame and its
+ *                                      fallbacks included) and, for a material with a normal map, the same texel and scale
+ *                                      (texture coordinates and images do not move)
+ * Checks: agpt_render_features_motion's in their order, then AGPT_ERR_INVALID for a NULL prev_normal_dev, for prev_normal_dev aliasing
+ * another output, and for a scene whose shading generations are absent.
+ * Limits: a triangle whose normals changed while its 36 position bytes did not stays w == 2 and is not followed. */
+int agpt_render_features_surface_motion(agpt_scene*, const agpt_render_params* rp, float* albedo_dev, float* normal_depth_dev,
+                                        float* prev_point_dev, float* prev_normal_dev);
+
+/* agpt_temporal_accumulate_surface_motion: with clamp == NULL agpt_temporal_accumulate_motion's contract, otherwise
+ * agpt_temporal_accumulate_clamped's with a non-NULL prev_point_cur_dev, and one change in step 4: for a pixel with prev_point_cur.w == 1
+ * the normal compared with each tap's is prev_normal_cur[i].xyz (agpt_render_features_surface_motion's output for this frame, full
+ * film) instead of normal_depth_cur[i].xyz.  A NaN there fails the >=: the tap is rejected.  The depth test, the first-frame rule and
+ * everything else are unchanged; prev_normal_cur is read for w == 1 pixels only.  One launch.  Where every prev_normal_cur.xyz has the
+ * bits of normal_depth_cur.xyz the outputs are the other two calls', bit for bit.
+ * Checks (AGPT_ERR_INVALID): those of the call it extends in their order (with clamp, a NULL prev_point_cur_dev after the clamp
+ * parameters), then a NULL prev_normal_cur_dev, then an output aliasing it. */
+int agpt_temporal_accumulate_surface_motion(agpt_ctx*, const agpt_temporal_params*, const agpt_temporal_clamp_params* clamp /* may be NULL */,
+        const float* accum_cur_dev, const float* moment2_cur_dev, const float* albedo_cur_dev, const float* normal_depth_cur_dev,
+        const float* hist_accum_prev_dev, const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
+        float* hist_accum_out_dev, float* hist_moment2_out_dev, const float* prev_point_cur_dev, const float* prev_normal_cur_dev);
 
 /* Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) of PathTracer (integrator.h:120-191) for n rays of the caller --
  * the single-ray entry the reference's split-screen compare (myapp.cpp:168) and mouse picking (myapp.cpp:197-201) use, batched.
@@ -920,6 +965,11 @@ int agpt_kat_bsdf_sample(agpt_scene*, int material, int n, const float* wo3, con
 /* known-answer: the perturbation of agpt_scene_set_material_normal_texture alone, one lane per item (n items: ns3, ss3, rgb3 in,
  * ns_out3 out; HOST arrays) */
 int agpt_kat_normal_map(agpt_ctx*, int n, const float* ns3, const float* ss3, const float* rgb3, float scale, float* ns_out3);
+/* known-answer: the surface reconstruction of a mesh hit alone -- shading normal (ns3_out) and tangent (ss3_out) -- for n global
+ * triangle ids and barycentrics (HOST arrays), from the scene's live shading records (generation -1) or from the newer (0) or the
+ * older (1) generation of agpt_scene_snapshot_surfaces.  AGPT_ERR_INVALID for an id out of range or an absent generation. */
+int agpt_kat_surface(agpt_scene*, int generation, int n, const uint32_t* tri_ids, const float* b1, const float* b2, float* ns3_out,
+                     float* ss3_out);
 /* RNG stream of a (pixel, sample): first n floats (template.cpp:667-675 + cl/tools.cl:1-2) */
 int agpt_kat_rng(agpt_ctx*, uint32_t pixel, uint32_t wh, uint32_t sample, uint32_t seed_base, int n, float* out,
                  uint32_t* seed_out);

@@ -153,8 +153,10 @@ enum class MeshUpdate { Refit = AGPT_UPDATE_REFIT, Rebuild = AGPT_UPDATE_REBUILD
 enum class MeshNormals { Given = AGPT_NORMALS_GIVEN, Smooth = AGPT_NORMALS_SMOOTH };
 enum class ShadingArith { Exact = AGPT_SHADING_EXACT, Fast = AGPT_SHADING_FAST };
 // AdaptiveAccumulator::TemporalAccumulate: reproject the point a pixel sees now (agpt_temporal_accumulate), or where a moved mesh's
-// surface point was a frame ago (agpt_temporal_accumulate_motion, with the features of PathTracer::RenderFeaturesMotion)
-enum class Motion { Ignore, Follow };
+// surface point was a frame ago (agpt_temporal_accumulate_motion, with the features of PathTracer::RenderFeaturesMotion), or that
+// and, in the normal test, the shading normal that point had a frame ago, so that a surface which turned keeps its history
+// (agpt_temporal_accumulate_surface_motion, with Scene::SnapshotSurfaces and PathTracer::RenderFeaturesSurfaceMotion)
+enum class Motion { Ignore, Follow, FollowSurfaces };
 
 class Scene {
 public:
@@ -315,6 +317,9 @@ public:
     // updateSphere / updatePlane calls and before PathTracer::RenderFeaturesMotion -- the scene keeps the triangle positions and the sphere
     // and plane records of this frame and of the one before
     void SnapshotPositions() { check(agpt_scene_snapshot_positions(h_), "agpt_scene_snapshot_positions"); }
+    // agpt_scene_snapshot_surfaces: SnapshotPositions plus two generations of the per-triangle shading records (128 B per triangle), in its
+    // place, before PathTracer::RenderFeaturesSurfaceMotion
+    void SnapshotSurfaces() { check(agpt_scene_snapshot_surfaces(h_), "agpt_scene_snapshot_surfaces"); }
     void set_camera() { check(agpt_scene_set_camera(h_, &camera), "agpt_scene_set_camera"); }
     void Intersect(const agpt_ray* rays, int n, agpt_hit* hits) const {
         check(agpt_intersect_batch(h_, rays, n, hits, 0, nullptr), "agpt_intersect_batch");
@@ -429,6 +434,7 @@ public:
         check(agpt_device_alloc(ctx.handle(), (size_t)w * h * 16, &normal_depth_), "agpt_device_alloc");
     }
     ~FeatureBuffers() {
+        if (prev_normal_) agpt_device_free(ctx_.handle(), prev_normal_);
         if (prev_point_) agpt_device_free(ctx_.handle(), prev_point_);
         agpt_device_free(ctx_.handle(), normal_depth_);
         agpt_device_free(ctx_.handle(), albedo_);
@@ -444,9 +450,17 @@ public:
         return static_cast<float*>(prev_point_);
     }
     const float* prev_point_or_null() const { return static_cast<const float*>(prev_point_); }
+    // prev_normal of agpt_render_features_surface_motion: (the shading normal the hit surface point had a frame ago, prev_point's w);
+    // allocated by the first call, null until PathTracer::RenderFeaturesSurfaceMotion has filled it
+    float* device_prev_normal() {
+        if (!prev_normal_) check(agpt_device_alloc(ctx_.handle(), (size_t)width * height * 16, &prev_normal_), "agpt_device_alloc");
+        return static_cast<float*>(prev_normal_);
+    }
+    const float* prev_normal_or_null() const { return static_cast<const float*>(prev_normal_); }
     std::vector<float> DownloadAlbedo() const { return download(albedo_); }
     std::vector<float> DownloadNormalDepth() const { return download(normal_depth_); }
     std::vector<float> DownloadPrevPoint() const { return prev_point_ ? download(prev_point_) : std::vector<float>(); }
+    std::vector<float> DownloadPrevNormal() const { return prev_normal_ ? download(prev_normal_) : std::vector<float>(); }
     const int width, height;
 
 private:
@@ -459,6 +473,7 @@ private:
     void* albedo_ = nullptr;
     void* normal_depth_ = nullptr;
     void* prev_point_ = nullptr;
+    void* prev_normal_ = nullptr;
 };
 
 // The buffers of an adaptive render (agpt_render_adaptive): the float4 sums with each pixel's own sample count in w, and the
@@ -533,6 +548,16 @@ public:
         const float* hm = prev_history ? prev_history->device_moment2() : nullptr;
         const float* pa = prev_features ? prev_features->device_albedo() : nullptr;
         const float* pn = prev_features ? prev_features->device_normal_depth() : nullptr;
+        if (motion == Motion::FollowSurfaces) {
+            // agpt_temporal_accumulate_surface_motion: `features` were rendered by PathTracer::RenderFeaturesSurfaceMotion; with or
+            // without clamp (missing buffers are refused by the call)
+            check(agpt_temporal_accumulate_surface_motion(ctx_.handle(), &p, clamp, device_pixels(), device_moment2(), features.device_albedo(),
+                                                          features.device_normal_depth(), hp, hm, pa, pn, history_out.device_pixels(),
+                                                          history_out.device_moment2(), features.prev_point_or_null(),
+                                                          features.prev_normal_or_null()),
+                  "agpt_temporal_accumulate_surface_motion");
+            return;
+        }
         if (clamp && (motion == Motion::Ignore || features.prev_point_or_null())) {
             // (Motion::Follow without a prev_point buffer is left to agpt_temporal_accumulate_motion below, which refuses it)
             check(agpt_temporal_accumulate_clamped(ctx_.handle(), &p, clamp, device_pixels(), device_moment2(), features.device_albedo(),
@@ -714,6 +739,18 @@ public:
         p.accum_pitch = features.width;
         check(agpt_render_features_motion(scene.handle(), &p, features.device_albedo(), features.device_normal_depth(), features.device_prev_point()),
               "agpt_render_features_motion");
+    }
+    // agpt_render_features_surface_motion: RenderFeaturesMotion plus features.device_prev_normal() (Scene::SnapshotSurfaces first)
+    void RenderFeaturesSurfaceMotion(Scene& scene, FeatureBuffers& features) const {
+        agpt_render_params p{};
+        p.width = features.width;
+        p.height = features.height;
+        p.w = features.width;
+        p.h = features.height;
+        p.accum_pitch = features.width;
+        check(agpt_render_features_surface_motion(scene.handle(), &p, features.device_albedo(), features.device_normal_depth(),
+                                                  features.device_prev_point(), features.device_prev_normal()),
+              "agpt_render_features_surface_motion");
     }
     // Integrator::Li(const Ray&, const Scene&) (integrator.h:28-31) for n rays -- what MyApp::Tick calls per pixel (myapp.cpp:168)
     // and the mouse-pick overlay per click (myapp.cpp:197-201).  rng[i] is the RandomFloat() state path i starts from and receives

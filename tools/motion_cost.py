@@ -11,7 +11,11 @@ process (row A, row B, row A, ...) after one warm-up turn, --runs timed turns, a
              hit pixel moved (w == 1, the point being the one seen now), on two 4-spp frames of C3 at 1080p one degree of orbit apart
 --parent-lib TAG: agpt_temporal_accumulate of this build against the build `libagpt_hip_TAG.so` of the parent commit
 (tools/build_variant.py run in a checkout of it, the file copied beside libagpt_hip.so): child processes, alternating parent / this
-for --rounds rounds on the same GPU."""
+for --rounds rounds on the same GPU.
+--surfaces: the previous-frame-normal calls beside those rows, into profiles/surface_motion_c3.json: agpt_scene_snapshot_surfaces beside
+agpt_scene_snapshot_positions (the difference is a device copy of 64 B per triangle), agpt_render_features_surface_motion beside
+agpt_render_features_motion, agpt_temporal_accumulate_surface_motion beside agpt_temporal_accumulate_motion and beside
+agpt_temporal_accumulate_clamped (r = 2), with nothing moved and with every hit pixel moved (prev_normal = the current normal)."""
 import argparse
 import json
 import os
@@ -111,8 +115,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "motion_c3.json"))
     ap.add_argument("--parent-lib", default=None, metavar="TAG")
+    ap.add_argument("--surfaces", action="store_true")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.surfaces and a.out == ap.get_default("out"):
+        a.out = os.path.join(os.path.dirname(a.out), "surface_motion_c3.json")
     if a.runs < 9:
         ap.error("--runs: at least 9")
     if a.child:
@@ -122,7 +129,8 @@ def main():
     ctx = ag.Context(0)
     # (the command as far as it decides what is measured: where the file goes is left out)
     res = {"device": torch.cuda.get_device_name(0),
-           "command": "python tools/motion_cost.py --runs %d --rounds %d%s" % (a.runs, a.rounds, " --parent-lib " + a.parent_lib if a.parent_lib else ""),
+           "command": "python tools/motion_cost.py --runs %d --rounds %d%s%s" % (a.runs, a.rounds, " --surfaces" if a.surfaces else "",
+                                                                                " --parent-lib " + a.parent_lib if a.parent_lib else ""),
            "library_sha256": hashlib.sha256(open(ag.library_path(), "rb").read()).hexdigest(),
            "method": "host clock around each synchronised call; the rows of a group take turns in one process, one warm-up turn, then "
                      "%d timed turns: median (min - max)" % a.runs,
@@ -133,6 +141,12 @@ def main():
     res["snapshot"] = turns({"agpt_scene_snapshot_positions c3": f.scene.snapshot_positions,
                              "agpt_scene_snapshot_positions heightfield": hf.snapshot_positions}, a.runs)
     show("snapshot", res["snapshot"])
+    if a.surfaces:
+        # (after the rows above: consecutive agpt_scene_snapshot_surfaces calls keep the shading generations allocated, as a frame loop does)
+        res["snapshot_surfaces"] = turns({"agpt_scene_snapshot_surfaces c3": f.scene.snapshot_surfaces,
+                                          "agpt_scene_snapshot_surfaces heightfield": hf.snapshot_surfaces}, a.runs)
+        res["snapshot_surfaces"]["copy_bytes"] = {k: 64 * v for k, v in res["triangles"].items()}
+        show("snapshot", {k: v for k, v in res["snapshot_surfaces"].items() if "median_ms" in v})
     hf.close()
 
     pt = ag.PathTracer(5)
@@ -141,6 +155,12 @@ def main():
     f.scene.set_camera(*f.cams[1])
     res["features"] = turns({"agpt_render_features": lambda: pt.render_features(f.scene, W, H, albedo, nd),
                              "agpt_render_features_motion": lambda: pt.render_features_motion(f.scene, W, H, albedo, nd, point)}, a.runs)
+    if a.surfaces:
+        normal = ctx.alloc(n16)
+        f.scene.snapshot_surfaces()
+        res["features"].update(turns({"agpt_render_features_motion (beside the next row)": lambda: pt.render_features_motion(f.scene, W, H, albedo, nd, point),
+                                      "agpt_render_features_surface_motion": lambda: pt.render_features_surface_motion(f.scene, W, H, albedo, nd, point, normal)},
+                                     a.runs))
     show("features", res["features"])
 
     pp = ctx.download(point, (H, W, 4))
@@ -153,6 +173,23 @@ def main():
                              "agpt_temporal_accumulate_motion, every w in {0, 2}": lambda: ctx.temporal_accumulate_motion(f.params, *f.buffers, point),
                              "agpt_temporal_accumulate_motion, every hit pixel w == 1": lambda: ctx.temporal_accumulate_motion(f.params, *f.buffers, point_moved)},
                             a.runs)
+    if a.surfaces:
+        same = np.concatenate([ctx.download(f.sets[1][3], (H, W, 4))[..., :3], pp[..., 3:]], -1)
+        same_moved = np.concatenate([same[..., :3], moved[..., 3:]], -1)
+        normal_same, normal_moved = ctx.alloc(n16), ctx.alloc(n16)
+        ctx.upload(normal_same, same)
+        ctx.upload(normal_moved, same_moved)
+        clamp = ag.TemporalClampParams(2, 1, 1.0, 8.0)
+        rows = {}
+        for what, pt_, pn_ in (("every w in {0, 2}", point, normal_same), ("every hit pixel w == 1", point_moved, normal_moved)):
+            rows["agpt_temporal_accumulate_motion, " + what + " (again)"] = lambda pt_=pt_: ctx.temporal_accumulate_motion(f.params, *f.buffers, pt_)
+            rows["agpt_temporal_accumulate_surface_motion, " + what] = \
+                lambda pt_=pt_, pn_=pn_: ctx.temporal_accumulate_surface_motion(f.params, None, *f.buffers, pt_, pn_)
+            rows["agpt_temporal_accumulate_clamped r = 2, " + what] = lambda pt_=pt_: ctx.temporal_accumulate_clamped(f.params, clamp, *f.buffers, pt_)
+            rows["agpt_temporal_accumulate_surface_motion clamp r = 2, " + what] = \
+                lambda pt_=pt_, pn_=pn_: ctx.temporal_accumulate_surface_motion(f.params, clamp, *f.buffers, pt_, pn_)
+        res["temporal_surfaces"] = turns(rows, a.runs)
+        show("temporal", res["temporal_surfaces"])
     res["temporal"]["hit_pixels"] = int((pp[..., 3] == 2).sum())
     show("temporal", {k: v for k, v in res["temporal"].items() if isinstance(v, dict)})
     f.scene.close()

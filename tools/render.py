@@ -7,6 +7,7 @@
     python tools/render.py --scene textured --spp 16 --spin 12 --out out/spin.png                  (out/spin_0000.png ...)
     python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --out out/spin.png
     python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --clamp 1.5 --clamp-radius 2 --out out/spin.png
+    python tools/render.py --scene textured --spp 4 --frames 8 --spin 12 --temporal --motion --follow-normals --out out/spin.png
     python tools/render.py --scene c1 --spp 4 --frames 8 --light-orbit 10 --temporal --motion --clamp 1.5 --out out/light.png
 """
 import argparse
@@ -89,7 +90,8 @@ class FrameDrawer:
     of the frame before, the denoiser) under the scene's static camera; with --motion the history follows the moved mesh: a position
     snapshot behind the update, then agpt_render_features_motion and agpt_temporal_accumulate_motion.  The mean effective sample count
     over the moving mesh's pixels (prev_point.w == 1; the snapshot and prev_point are taken without --motion too, for this figure alone)
-    is printed per frame."""
+    is printed per frame.  With --follow-normals the three calls are agpt_scene_snapshot_surfaces, agpt_render_features_surface_motion and
+    agpt_temporal_accumulate_surface_motion (with or without --clamp): a mesh that turned keeps its history."""
 
     def __init__(self, a, ctx, scene, desc, W, H):
         self.a, self.ctx, self.scene, self.W, self.H = a, ctx, scene, W, H
@@ -99,6 +101,7 @@ class FrameDrawer:
         self.acc = ctx.alloc(n16)
         if a.temporal:
             self.m2, self.out, self.point = ctx.alloc(n4), ctx.alloc(n16), ctx.alloc(n16)
+            self.normal = ctx.alloc(n16) if a.follow_normals else 0
             self.sets = [(ctx.alloc(n16), ctx.alloc(n4), ctx.alloc(n16), ctx.alloc(n16)) for _ in range(2)]
 
     def __call__(self, k):
@@ -113,13 +116,21 @@ class FrameDrawer:
             return path, ""
         spp = max(2, a.spp)
         cur, prev = self.sets[k & 1], self.sets[(k & 1) ^ 1]
-        scene.snapshot_positions()
+        if a.follow_normals:
+            scene.snapshot_surfaces()
+        else:
+            scene.snapshot_positions()
         ctx.memset(self.m2, 0, W * H * 4)
         pt.render_adaptive(scene, W, H, self.acc, self.m2, spp, spp, spp, 0.0, seed_base=k)
-        pt.render_features_motion(scene, W, H, cur[2], cur[3], self.point)
+        if a.follow_normals:
+            pt.render_features_surface_motion(scene, W, H, cur[2], cur[3], self.point, self.normal)
+        else:
+            pt.render_features_motion(scene, W, H, cur[2], cur[3], self.point)
         params = ag.TemporalParams(W, H, self.cam, self.cam, a.max_history, ag.TEMPORAL_DEPTH_TOL, ag.TEMPORAL_NORMAL_COS)
         buffers = (self.acc, self.m2, cur[2], cur[3]) + (prev if k else (0, 0, 0, 0)) + (cur[0], cur[1])
-        if a.clamp is not None:
+        if a.follow_normals:
+            ctx.temporal_accumulate_surface_motion(params, clamp_params(a) if a.clamp is not None else None, *buffers, self.point, self.normal)
+        elif a.clamp is not None:
             ctx.temporal_accumulate_clamped(params, clamp_params(a), *buffers, self.point if a.motion else 0)
         elif a.motion:
             ctx.temporal_accumulate_motion(params, *buffers, self.point)
@@ -131,7 +142,8 @@ class FrameDrawer:
         moving = ctx.download(self.point, (H, W, 4))[..., 3] == 1
         counts = ctx.download(cur[0], (H, W, 4))[..., 3]
         note = ", %d moving pixels with %.2f effective samples on average" % (moving.sum(), counts[moving].mean()) if moving.any() else ""
-        return path, " + history%s%s%s" % (" with motion vectors" if a.motion else "", ", clamped" if a.clamp is not None else "", note)
+        how = " with motion vectors and previous normals" if a.follow_normals else " with motion vectors" if a.motion else ""
+        return path, " + history%s%s%s" % (how, ", clamped" if a.clamp is not None else "", note)
 
 
 def render_light_orbit(a, ctx, scene, desc, W, H):
@@ -283,6 +295,10 @@ def main():
     ap.add_argument("--motion", action="store_true",
                     help="--temporal with --spin, --bend or --morph: the history follows the moved mesh (agpt_scene_snapshot_positions after "
                          "each frame's update, agpt_render_features_motion, agpt_temporal_accumulate_motion)")
+    ap.add_argument("--follow-normals", action="store_true",
+                    help="--temporal --motion: the normal test uses the normal the surface point had a frame ago, so a mesh that turns keeps "
+                         "its history (agpt_scene_snapshot_surfaces, agpt_render_features_surface_motion, "
+                         "agpt_temporal_accumulate_surface_motion); with or without --clamp")
     ap.add_argument("--spin", type=int, default=0, metavar="N",
                     help="N frames at --spp each with one mesh turned about its vertical axis by agpt_scene_transform_mesh (OUT_0000.png ...)")
     ap.add_argument("--spin-prim", type=int, default=None, metavar="PRIM", help="--spin: the mesh primitive that turns (default: the scene's last mesh)")
@@ -316,6 +332,8 @@ def main():
         ap.error("--clamp GAMMA must be non-negative")
     if a.motion and not (a.temporal and animated):
         ap.error("--motion applies to --temporal with one of --spin, --bend, --morph and --light-orbit")
+    if a.follow_normals and not (a.temporal and a.motion):
+        ap.error("--follow-normals applies to --temporal --motion")
     W, H = a.width, a.height
     aspect = W / float(H)
     desc = {"c1": lambda: ag.scenes.scene_c1(), "c2": lambda: ag.scenes.scene_c2(aspect=aspect),
