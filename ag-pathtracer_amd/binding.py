@@ -624,36 +624,40 @@ class Context:
             for p in ptrs:
                 self.free(p)
 
+    _NO_CLAMP = object()
+
+    def _temporal(self, name, params, ptrs, clamp=_NO_CLAMP):
+        """One agpt_temporal_accumulate* call by name.  ptrs: its DEVICE pointers in the C order (None / 0 -> NULL); clamp, for an entry
+        point that takes clamp parameters: a TemporalClampParams, or None -> NULL."""
+        head = [C.byref(params)] + ([] if clamp is Context._NO_CLAMP else [C.byref(clamp) if clamp is not None else None])
+        _check(getattr(self.L, name)(self.h, *head, *[C.c_void_p(int(p)) if p else None for p in ptrs]), name)
+
     def temporal_accumulate(self, params, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
                             albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out):
         """agpt_temporal_accumulate: this frame's adaptive-render and feature buffers plus the previous frame's history (this
         call's outputs then) and feature buffers -- all four None / 0 on the first frame -- into the history buffers, which have the
         form denoise reads.  All DEVICE pointers, full film."""
-        _check(self.L.agpt_temporal_accumulate(self.h, C.byref(params), *[C.c_void_p(int(p)) if p else None for p in
-                                               (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
-                                                albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out)]),
-               "agpt_temporal_accumulate")
+        self._temporal("agpt_temporal_accumulate", params,
+                       (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev, normal_depth_prev,
+                        hist_accum_out, hist_moment2_out))
 
     def temporal_accumulate_motion(self, params, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
                                    albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur):
         """agpt_temporal_accumulate_motion: temporal_accumulate, reprojecting for every pixel whose prev_point_cur.w is 1 the point
         PathTracer.render_features_motion wrote there (where the surface was) instead of the point it sees now.  All DEVICE pointers,
         full film."""
-        _check(self.L.agpt_temporal_accumulate_motion(self.h, C.byref(params), *[C.c_void_p(int(p)) if p else None for p in
-                                                      (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
-                                                       albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur)]),
-               "agpt_temporal_accumulate_motion")
+        self._temporal("agpt_temporal_accumulate_motion", params,
+                       (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev, normal_depth_prev,
+                        hist_accum_out, hist_moment2_out, prev_point_cur))
 
     def temporal_accumulate_clamped(self, params, clamp, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev,
                                     hist_moment2_prev, albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur=None):
         """agpt_temporal_accumulate_clamped: temporal_accumulate -- or, with prev_point_cur, temporal_accumulate_motion -- whose
         reprojected history is clamped to mean +- clamp.gamma standard deviations of the current frame's neighbourhood
         (clamp: a TemporalClampParams).  All DEVICE pointers, full film."""
-        _check(self.L.agpt_temporal_accumulate_clamped(self.h, C.byref(params), C.byref(clamp) if clamp is not None else None,
-                                                       *[C.c_void_p(int(p)) if p else None for p in
-                                                         (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev,
-                                                          albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur)]),
-               "agpt_temporal_accumulate_clamped")
+        self._temporal("agpt_temporal_accumulate_clamped", params,
+                       (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev, normal_depth_prev,
+                        hist_accum_out, hist_moment2_out, prev_point_cur), clamp)
 
     def temporal_accumulate_surface_motion(self, params, clamp, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev,
                                            hist_moment2_prev, albedo_prev, normal_depth_prev, hist_accum_out, hist_moment2_out, prev_point_cur,
@@ -662,12 +666,9 @@ class Context:
         prev_point_cur (clamp: a TemporalClampParams) whose normal test uses, for every pixel whose prev_point_cur.w is 1, the normal
         PathTracer.render_features_surface_motion wrote into prev_normal_cur -- the one the surface point had a frame ago.  All DEVICE
         pointers, full film."""
-        _check(self.L.agpt_temporal_accumulate_surface_motion(self.h, C.byref(params), C.byref(clamp) if clamp is not None else None,
-                                                              *[C.c_void_p(int(p)) if p else None for p in
-                                                                (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev,
-                                                                 hist_moment2_prev, albedo_prev, normal_depth_prev, hist_accum_out,
-                                                                 hist_moment2_out, prev_point_cur, prev_normal_cur)]),
-               "agpt_temporal_accumulate_surface_motion")
+        self._temporal("agpt_temporal_accumulate_surface_motion", params,
+                       (accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev, normal_depth_prev,
+                        hist_accum_out, hist_moment2_out, prev_point_cur, prev_normal_cur), clamp)
 
     def temporal_to_host(self, cam_cur, cam_prev, accum, moment2, albedo, normal_depth, prev=None, max_history=32.0,
                          depth_tol=TEMPORAL_DEPTH_TOL, normal_cos=TEMPORAL_NORMAL_COS, prev_point=None, clamp=None, prev_normal=None):
@@ -1240,88 +1241,65 @@ class PathTracer:
             ctx.free(pa)
         return acc, m2, st, ast
 
+    def _features(self, name, scene, W, H, ptrs, tile=None, accum_pitch=None, accum_row0=0, seed_base=0, spp_begin=0, spp_count=0,
+                  interleave=None):
+        """One agpt_render_features* call by name: ptrs are its DEVICE output buffers in the C order"""
+        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
+        il = interleave if interleave is not None else (0, 0, 0)
+        rp = RenderParams(W, H, x0, y0, w, h, spp_begin, spp_count, seed_base & 0xFFFFFFFF, self.MaxDepth,
+                          accum_pitch if accum_pitch is not None else W, accum_row0, 0, 0, 0, il[0], il[1], il[2], 0)
+        _check(getattr(scene.L, name)(scene.h, C.byref(rp), *[C.c_void_p(int(p)) if p else None for p in ptrs]), name)
+
+    def _features_to_host(self, call, n, scene, W, H, **kw):
+        """call (one of the render_features* methods) into its n zeroed full-film buffers -> the n arrays [H,W,4]"""
+        ctx = scene.ctx
+        ptrs = []
+        try:
+            for _ in range(n):
+                ptrs.append(ctx.alloc(W * H * 16))
+                ctx.memset(ptrs[-1], 0, W * H * 16)
+            call(scene, W, H, *ptrs, **kw)
+            return tuple(ctx.download(p, (H, W, 4)) for p in ptrs)
+        finally:
+            for p in ptrs:
+                ctx.free(p)
+
     def render_features(self, scene, W, H, albedo_ptr, normal_depth_ptr, tile=None, accum_pitch=None, accum_row0=0, seed_base=0,
                         spp_begin=0, spp_count=0, interleave=None):
         """agpt_render_features: one unjittered closest-hit query per pixel of `tile`; albedo_ptr / normal_depth_ptr are DEVICE
         float4 buffers indexed like render's accum: (material colour, flag 0 miss / 1 surface / 2 emitter) and (shading normal, t).
         seed_base is ignored; spp_begin, spp_count and interleave must stay at their defaults."""
-        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
-        il = interleave if interleave is not None else (0, 0, 0)
-        rp = RenderParams(W, H, x0, y0, w, h, spp_begin, spp_count, seed_base & 0xFFFFFFFF, self.MaxDepth,
-                          accum_pitch if accum_pitch is not None else W, accum_row0, 0, 0, 0, il[0], il[1], il[2], 0)
-        _check(scene.L.agpt_render_features(scene.h, C.byref(rp), C.c_void_p(int(albedo_ptr)) if albedo_ptr else None,
-                                            C.c_void_p(int(normal_depth_ptr)) if normal_depth_ptr else None), "agpt_render_features")
+        self._features("agpt_render_features", scene, W, H, (albedo_ptr, normal_depth_ptr), tile, accum_pitch, accum_row0, seed_base,
+                       spp_begin, spp_count, interleave)
 
     def render_features_to_host(self, scene, W, H, **kw):
         """Convenience for tests and tools: render_features into zeroed full-film buffers, returns (albedo[H,W,4],
         normal_depth[H,W,4])."""
-        ctx = scene.ctx
-        pa = ctx.alloc(W * H * 16)
-        try:
-            pn = ctx.alloc(W * H * 16)
-            try:
-                ctx.memset(pa, 0, W * H * 16)
-                ctx.memset(pn, 0, W * H * 16)
-                self.render_features(scene, W, H, pa, pn, **kw)
-                return ctx.download(pa, (H, W, 4)), ctx.download(pn, (H, W, 4))
-            finally:
-                ctx.free(pn)
-        finally:
-            ctx.free(pa)
+        return self._features_to_host(self.render_features, 2, scene, W, H, **kw)
 
     def render_features_motion(self, scene, W, H, albedo_ptr, normal_depth_ptr, prev_point_ptr, tile=None, accum_pitch=None, accum_row0=0):
         """agpt_render_features_motion: render_features plus, from the same hits, prev_point_ptr (DEVICE float4, indexed like the other
         two) = (where the hit surface point was at the scene's older position snapshot, w): w 0 a miss, 2 not moved, 1 moved.  Needs
         scene.snapshot_positions() first."""
-        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
-        rp = RenderParams(W, H, x0, y0, w, h, 0, 0, 0, self.MaxDepth, accum_pitch if accum_pitch is not None else W, accum_row0,
-                          0, 0, 0, 0, 0, 0, 0)
-        _check(scene.L.agpt_render_features_motion(scene.h, C.byref(rp), *[C.c_void_p(int(p)) if p else None for p in
-                                                                           (albedo_ptr, normal_depth_ptr, prev_point_ptr)]),
-               "agpt_render_features_motion")
+        self._features("agpt_render_features_motion", scene, W, H, (albedo_ptr, normal_depth_ptr, prev_point_ptr), tile, accum_pitch, accum_row0)
 
     def render_features_motion_to_host(self, scene, W, H, **kw):
         """Convenience for tests and tools: render_features_motion into zeroed full-film buffers, returns (albedo[H,W,4],
         normal_depth[H,W,4], prev_point[H,W,4])."""
-        ctx = scene.ctx
-        ptrs = []
-        try:
-            for _ in range(3):
-                ptrs.append(ctx.alloc(W * H * 16))
-                ctx.memset(ptrs[-1], 0, W * H * 16)
-            self.render_features_motion(scene, W, H, *ptrs, **kw)
-            return tuple(ctx.download(p, (H, W, 4)) for p in ptrs)
-        finally:
-            for p in ptrs:
-                ctx.free(p)
+        return self._features_to_host(self.render_features_motion, 3, scene, W, H, **kw)
 
     def render_features_surface_motion(self, scene, W, H, albedo_ptr, normal_depth_ptr, prev_point_ptr, prev_normal_ptr, tile=None,
                                        accum_pitch=None, accum_row0=0):
         """agpt_render_features_surface_motion: render_features_motion plus prev_normal_ptr (DEVICE float4, indexed like the other
         three) = (the shading normal the hit surface point had at the scene's older snapshot, prev_point's w).  Needs
         scene.snapshot_surfaces() first."""
-        x0, y0, w, h = tile if tile is not None else (0, 0, W, H)
-        rp = RenderParams(W, H, x0, y0, w, h, 0, 0, 0, self.MaxDepth, accum_pitch if accum_pitch is not None else W, accum_row0,
-                          0, 0, 0, 0, 0, 0, 0)
-        _check(scene.L.agpt_render_features_surface_motion(scene.h, C.byref(rp), *[C.c_void_p(int(p)) if p else None for p in
-                                                                                   (albedo_ptr, normal_depth_ptr, prev_point_ptr,
-                                                                                    prev_normal_ptr)]),
-               "agpt_render_features_surface_motion")
+        self._features("agpt_render_features_surface_motion", scene, W, H, (albedo_ptr, normal_depth_ptr, prev_point_ptr, prev_normal_ptr), tile,
+                       accum_pitch, accum_row0)
 
     def render_features_surface_motion_to_host(self, scene, W, H, **kw):
         """Convenience for tests and tools: render_features_surface_motion into zeroed full-film buffers, returns (albedo[H,W,4],
         normal_depth[H,W,4], prev_point[H,W,4], prev_normal[H,W,4])."""
-        ctx = scene.ctx
-        ptrs = []
-        try:
-            for _ in range(4):
-                ptrs.append(ctx.alloc(W * H * 16))
-                ctx.memset(ptrs[-1], 0, W * H * 16)
-            self.render_features_surface_motion(scene, W, H, *ptrs, **kw)
-            return tuple(ctx.download(p, (H, W, 4)) for p in ptrs)
-        finally:
-            for p in ptrs:
-                ctx.free(p)
+        return self._features_to_host(self.render_features_surface_motion, 4, scene, W, H, **kw)
 
     def Li(self, scene, rays, rng_states):
         """Integrator::Li (integrator.h:28-31, 120-191) for a batch of rays (RAY_DTYPE) with one xorshift32 state each:

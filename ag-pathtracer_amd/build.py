@@ -24,7 +24,7 @@ SHADE_UNITS = [("", 0, 0, 4), ("_fast", 0, 1, 4), ("_textured", 1, 0, 4), ("_tex
 SHADE_FLAGS = ["-mllvm", "-disable-machine-licm"]
 SHADE_SOURCES = ["agpt_shade_kernels%s.hip" % suffix for suffix, _, _, _ in SHADE_UNITS]
 SOURCES = ["agpt_api.hip"] + SHADE_SOURCES + ["agpt_scene_api.hip", "agpt_kat.hip", "agpt_comm.hip", "agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip",
-                                               "agpt_denoise.hip", "agpt_temporal.hip", "agpt_motion.hip", "agpt_analytic.hip", "agpt_temporal_clamp.hip", "agpt_surface_motion.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
+                                               "agpt_denoise.hip", "agpt_temporal.hip", "agpt_motion.hip", "agpt_analytic.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {src: SHADE_FLAGS + ["-DAGPT_SHADE_WAVES=%d" % waves] for src, (_, _, _, waves) in zip(SHADE_SOURCES, SHADE_UNITS)}
 # every header: an edit to any of them rebuilds the library (needs_build)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [os.path.join("..", "..", "include", "agpt.h")]

@@ -1,8 +1,8 @@
 // agpt_internal.h -- what the units that define the C entry points of include/agpt.h share: error reporting, the owning device
 // buffer, and the context and the scene behind the two opaque handles.  Those units are agpt_api.hip (context, pool, trace launches,
 // wavefront loop, renderers), agpt_scene_api.hip (scene building, commit, host BVH, mesh updates), agpt_kat.hip, agpt_comm.hip, and
-// the entry points that sit beside their kernels (agpt_adaptive.hip, agpt_denoise.hip, agpt_temporal.hip, agpt_motion.hip, agpt_analytic.hip, agpt_temporal_clamp.hip, agpt_surface_motion.hip).  Only .hip / .cpp units
-// include this file, no other header does.
+// the entry points that sit beside their kernels (agpt_adaptive.hip, agpt_denoise.hip, agpt_temporal.hip, agpt_motion.hip,
+// agpt_analytic.hip).  Only .hip / .cpp units include this file, no other header does.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,14 +35,6 @@ namespace agpt {
 int fail(int code, const std::string& msg);
 // film rows of the row blocks k with k % world == rank (blocks of `block` rows, the last one of a film may be shorter)
 int interleave_rows(int H, int block, int world, int rank);
-}  // namespace agpt
-struct TemporalConsts;
-struct agpt_ctx;
-namespace agpt {
-// (agpt_temporal.hip) agpt_temporal_accumulate's argument checks in the header's order under the name `fn`, then k_temporal's
-// constants and grid; in = the four current and the four prev buffers
-int temporal_prepare(const char* fn, agpt_ctx* c, const agpt_temporal_params* p, const float* const in[8], const float* hist_accum_out_dev,
-                     const float* hist_moment2_out_dev, TemporalConsts& tc, dim3& tiles);
 }  // namespace agpt
 
 #define HIP_TRY(expr)                                                                                   \

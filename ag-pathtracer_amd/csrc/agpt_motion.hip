@@ -1,16 +1,16 @@
 // agpt_motion.hip -- per-object motion vectors for the temporal reprojection (include/agpt.h): the kernels of
-// agpt_scene_snapshot_positions, agpt_render_features_motion (the entry point is in agpt_api.hip, beside agpt_render_features) and
-// agpt_temporal_accumulate_motion.  agpt_scene_snapshot_surfaces is defined here too: the same snapshot plus a device-to-device copy of
-// the tri_shade records, no kernel of its own.
+// agpt_scene_snapshot_positions and agpt_render_features_motion (the entry point is in agpt_api.hip, beside agpt_render_features).
+// agpt_scene_snapshot_surfaces is defined here too: the same snapshot plus a device-to-device copy of the tri_shade records, no kernel
+// of its own.  The call that reprojects the points, agpt_temporal_accumulate_motion, is in agpt_temporal.hip with the other temporal calls.
 //
 // k_snapshot_positions copies the world-space positions the update calls left in tri_verts (BVH slot order) into a buffer indexed by
 // the global triangle id, so two snapshots compare triangle by triangle whatever a rebuild did to the slot order.  k_motion turns a
-// feature-pass hit into the point the hit surface had in the older snapshot.  k_temporal_motion is k_temporal's body (agpt_temporal.h)
-// reprojecting that point.  One thread per item, fixed order, no atomics, no LDS: tests/motion_model.py reproduces each operation by
-// operation.  Compiled with the library's common flags (-ffp-contract=off, IEEE divide / sqrt).
-// All three are bandwidth kernels.  k_snapshot_positions: 48 B read contiguous per wave, 48 B written to 3 * gid -- scattered within
+// feature-pass hit into the point the hit surface had in the older snapshot.  One thread per item, fixed order, no atomics, no LDS:
+// tests/motion_model.py reproduces each operation by operation.  Compiled with the library's common flags (-ffp-contract=off, IEEE
+// divide / sqrt).
+// Both are bandwidth kernels.  k_snapshot_positions: 48 B read contiguous per wave, 48 B written to 3 * gid -- scattered within
 // a mesh's range by its leaf order.  k_motion: per pixel 16 B of hit and 32 B of ray, contiguous, and on a mesh hit 2 x 48 B gathered at
-// the hit triangle (a wave's pixels share a few triangles), 16 B written.  k_temporal_motion: k_temporal plus 16 B per pixel.
+// the hit triangle (a wave's pixels share a few triangles), 16 B written.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -18,7 +18,6 @@
 #include "agpt_analytic.h"
 #include "agpt_internal.h"
 #include "agpt_motion.h"
-#include "agpt_temporal.h"
 
 using agpt::fail;
 
@@ -95,16 +94,6 @@ k_motion(RenderConsts rc, const DevHit* __restrict__ hits, const float4* __restr
         m.x = p.x; m.y = p.y; m.z = p.z;
     }
     prev_point[ai] = m;
-}
-
-__global__ void __launch_bounds__(AGPT_BLOCK)
-k_temporal_motion(TemporalConsts tc, const float4* __restrict__ accum_cur, const float* __restrict__ moment2_cur,
-                  const float4* __restrict__ albedo_cur, const float4* __restrict__ normal_depth_cur, const float4* __restrict__ hist_accum_prev,
-                  const float* __restrict__ hist_moment2_prev, const float4* __restrict__ albedo_prev,
-                  const float4* __restrict__ normal_depth_prev, const float4* __restrict__ prev_point_cur, float4* __restrict__ hist_accum_out,
-                  float* __restrict__ hist_moment2_out) {
-    temporal_pixel<true>(tc, accum_cur, moment2_cur, albedo_cur, normal_depth_cur, hist_accum_prev, hist_moment2_prev, albedo_prev,
-                         normal_depth_prev, prev_point_cur, hist_accum_out, hist_moment2_out);
 }
 
 namespace agpt {
@@ -196,29 +185,5 @@ int agpt_scene_snapshot_positions(agpt_scene* s) { return snapshot("agpt_scene_s
 
 // agpt_scene_snapshot_positions plus two generations of the tri_shade records (PositionSnapshots::shade)
 int agpt_scene_snapshot_surfaces(agpt_scene* s) { return snapshot("agpt_scene_snapshot_surfaces", true, s); }
-
-// agpt_temporal_accumulate with step 3 decided per pixel by prev_point_cur: one k_temporal_motion launch
-int agpt_temporal_accumulate_motion(agpt_ctx* c, const agpt_temporal_params* p, const float* accum_cur_dev, const float* moment2_cur_dev,
-                                    const float* albedo_cur_dev, const float* normal_depth_cur_dev, const float* hist_accum_prev_dev,
-                                    const float* hist_moment2_prev_dev, const float* albedo_prev_dev, const float* normal_depth_prev_dev,
-                                    float* hist_accum_out_dev, float* hist_moment2_out_dev, const float* prev_point_cur_dev) {
-    const float* in[8] = {accum_cur_dev, moment2_cur_dev, albedo_cur_dev, normal_depth_cur_dev,
-                          hist_accum_prev_dev, hist_moment2_prev_dev, albedo_prev_dev, normal_depth_prev_dev};
-    TemporalConsts tc;
-    dim3 tiles;
-    if (const int rc = agpt::temporal_prepare("agpt_temporal_accumulate_motion", c, p, in, hist_accum_out_dev, hist_moment2_out_dev, tc, tiles))
-        return rc;
-    if (!prev_point_cur_dev) return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate_motion: NULL prev_point_cur_dev");
-    if (prev_point_cur_dev == hist_accum_out_dev || prev_point_cur_dev == hist_moment2_out_dev)
-        return fail(AGPT_ERR_INVALID, "agpt_temporal_accumulate_motion: an output aliases prev_point_cur_dev");
-    HIP_TRY(hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_temporal_motion, tiles, dim3(AGPT_BLOCK), 0, c->stream, tc, (const float4*)accum_cur_dev, moment2_cur_dev,
-                       (const float4*)albedo_cur_dev, (const float4*)normal_depth_cur_dev, (const float4*)hist_accum_prev_dev,
-                       hist_moment2_prev_dev, (const float4*)albedo_prev_dev, (const float4*)normal_depth_prev_dev,
-                       (const float4*)prev_point_cur_dev, (float4*)hist_accum_out_dev, hist_moment2_out_dev);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return AGPT_OK;
-}
 
 }  // extern "C"

@@ -139,6 +139,17 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def unit(v):
+    v = np.asarray(v, np.float64)
+    return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(np.float32)
+
+
+def film_point(P, s, t, depth):
+    """the world point at distance `depth` from the camera P (temporal_model.camera's dict) through its film position (s, t), in float64"""
+    d = (P["llc"].astype(np.float64) + s * P["horizontal"].astype(np.float64) + t * P["vertical"].astype(np.float64)) - P["origin"].astype(np.float64)
+    return P["origin"].astype(np.float64) + depth * d / np.linalg.norm(d)
+
+
 def close_fraction(a, b, rel):
     """the share of pixels with every channel within rel |b| + 1e-6"""
     return float(np.all(np.abs(a - b) <= rel * np.abs(b) + 1e-6, axis=-1).mean())

@@ -80,28 +80,9 @@ def position(cam_cur, cam_prev, identity, flag, depth, prev_point, W, H):
     pos = tm.position(cam_cur, cam_prev, identity, flag, depth, W, H)
     m = np.asarray(prev_point, F)
     moved = m[..., 3] == 1
-    P = tm.camera(cam_prev)
-    dot = tm.dot
     with np.errstate(all="ignore"):
-        Q = (m[..., :3] - P["origin"]).astype(F)
-        te = np.sqrt(dot(Q, Q))
-        L = P["llc"] - P["origin"]
-        dw = dot(Q, P["w"])
-        behind = ~(dw < 0)
-        k = dot(L, P["w"]) / dw
-        R = Q * k[..., None] - L
-        s = dot(R, P["horizontal"]) / dot(P["horizontal"], P["horizontal"])
-        t = dot(R, P["vertical"]) / dot(P["vertical"], P["vertical"])
-        sx = s * F(W) - F(0.5)
-        sy = t * F(H) - F(0.5)
-        inside = (sx > -1) & (sx < W) & (sy > -1) & (sy < H)
-        found = ~behind & inside
-        flx, fly = np.floor(sx), np.floor(sy)
-        fx, fy = sx - flx, sy - fly
-    x0 = np.where(found, flx, 0).astype(np.int64)
-    y0 = np.where(found, fly, 0).astype(np.int64)
-    mine = dict(found=found, x0=x0, y0=y0, fx=fx.astype(F), fy=fy.astype(F), te=te.astype(F))
-    return {k: np.where(moved, mine[k], pos[k]) for k in mine}, moved
+        mine = tm.project(cam_prev, (m[..., :3] - tm.camera(cam_prev)["origin"]).astype(F), W, H)
+    return {k: np.where(moved, mine[k], pos[k]) for k in ("found", "x0", "y0", "fx", "fy", "te")}, moved
 
 
 def accumulate_motion(cam_cur, cam_prev, accum, moment2, albedo, normal_depth, prev, prev_point, max_history=32.0,
@@ -112,39 +93,14 @@ def accumulate_motion(cam_cur, cam_prev, accum, moment2, albedo, normal_depth, p
     H, W = moment2.shape
     if prev is None:
         return accum.copy(), moment2.copy()
-    h_acc, h_m2, p_albedo, p_nd = (np.asarray(a, F) for a in prev)
+    prev = tuple(np.asarray(a, F) for a in prev)
     if identity is None:
         identity = np.asarray(cam_cur, F).tobytes() == np.asarray(cam_prev, F).tobytes()
     flag = albedo[..., 3]
-    geometry = flag != 0
     pos, _ = position(cam_cur, cam_prev, identity, flag, nd[..., 3], prev_point, W, H)
-    found, x0, y0, fx, fy, te = (pos[k] for k in ("found", "x0", "y0", "fx", "fy", "te"))
-    one = F(1)
-    weights = ((one - fx) * (one - fy), fx * (one - fy), (one - fx) * fy, fx * fy)
-    sb, sn, sm = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W), F)
-    sc = np.zeros((H, W, 3), F)
+    sb, sn, sc, sm, history = tm.gather(pos, flag, nd[..., :3], prev, depth_tol, normal_cos)
     with np.errstate(all="ignore"):
-        zmax = F(depth_tol) * np.fmax(te, tm.DEPTH_FLOOR)
-        for tap in range(4):
-            qx, qy = x0 + (tap & 1), y0 + (tap >> 1)
-            b = weights[tap].astype(F)
-            inside = found & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H) & (b > 0)
-            r, c = np.clip(H - 1 - qy, 0, H - 1), np.clip(qx, 0, W - 1)
-            n_q = h_acc[r, c, 3]
-            near = np.abs(te - p_nd[r, c, 3]) <= zmax
-            facing = tm.dot(nd[..., :3], p_nd[r, c, :3]) >= F(normal_cos)
-            use = inside & (n_q > 0) & (p_albedo[r, c, 3] == flag) & (~geometry | (near & facing))
-            sb = np.where(use, sb + b, sb)
-            sn = np.where(use, sn + b * n_q, sn)
-            sc = np.where(use[..., None], sc + b[..., None] * (h_acc[r, c, :3] / n_q[..., None]), sc)
-            sm = np.where(use, sm + b * (h_m2[r, c] / n_q), sm)
-        history = found & (sb >= F(tm.MIN_WEIGHT))
-        n_h = np.fmin(sn / sb, F(max_history))
-        out = accum.copy()
-        out[..., :3] = np.where(history[..., None], accum[..., :3] + (sc / sb[..., None]) * n_h[..., None], accum[..., :3])
-        out[..., 3] = np.where(history, accum[..., 3] + n_h, accum[..., 3])
-        m_out = np.where(history, moment2 + (sm / sb) * n_h, moment2).astype(F)
-    return out.astype(F), m_out
+        return tm.blend(accum, moment2, history, sc / sb[..., None], sm / sb, np.fmin(sn / sb, F(max_history)))
 
 
 # ---- the card scene of the tests ---------------------------------------------------------------------------------------------

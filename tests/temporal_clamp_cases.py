@@ -7,6 +7,7 @@ import ag_pathtracer_amd as ag
 import motion_model as mm
 import temporal_model as tm
 from adaptive_model import luminance
+from helpers import film_point, unit
 
 F = np.float32
 
@@ -55,17 +56,6 @@ MAX_HISTORY, DEPTH_TOL, NORMAL_COS = 10.0, 0.0625, 0.9
 GAMMA, CLAMPED_MAX_HISTORY = 1.0, 6.0
 FILMS = [(1, 1), (5, 3), (37, 19), (70, 9)]
 LONE_FLAG = 5.0
-
-
-def unit(v):
-    v = np.asarray(v, np.float64)
-    return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(F)
-
-
-def film_point(P, s, t, depth):
-    """the world point at distance `depth` from the previous camera through its film position (s, t), in float64"""
-    d = (P["llc"].astype(np.float64) + s * P["horizontal"].astype(np.float64) + t * P["vertical"].astype(np.float64)) - P["origin"].astype(np.float64)
-    return P["origin"].astype(np.float64) + depth * d / np.linalg.norm(d)
 
 
 def synthetic(W, H, cameras, motion, seed=20251020):

@@ -1,7 +1,7 @@
 """A numpy model of agpt_temporal_accumulate_clamped's contract (include/agpt.h): float32 operation by operation like
-tests/temporal_model.py and tests/motion_model.py, whose position() it uses for step 3.  It restates the four-tap loop of step 4,
-the neighbourhood statistics in the contract's tap order (dy = -r .. r outermost in FILM rows, dx = -r .. r) and step 5', and
-returns the masks the tests take their census from.  Buffers are [H, W, ...] in Accumulator::pixels order (buffer row r holds film
+tests/temporal_model.py and tests/motion_model.py, whose position() it uses for step 3 and whose gather() for step 4.  It adds the
+neighbourhood statistics in the contract's tap order (dy = -r .. r outermost in FILM rows, dx = -r .. r) and step 5', and returns
+the masks the tests take their census from.  Buffers are [H, W, ...] in Accumulator::pixels order (buffer row r holds film
 row y = H - 1 - r)."""
 import numpy as np
 
@@ -67,38 +67,17 @@ def accumulate_clamped(cam_cur, cam_prev, accum, moment2, albedo, normal_depth, 
     H, W = moment2.shape
     if prev is None:
         return (accum.copy(), moment2.copy()) + (({},) if return_masks else ())
-    h_acc, h_m2, p_albedo, p_nd = (np.asarray(a, F) for a in prev)
+    prev = tuple(np.asarray(a, F) for a in prev)
     if identity is None:
         identity = np.asarray(cam_cur, F).tobytes() == np.asarray(cam_prev, F).tobytes()
     flag = albedo[..., 3]
-    geometry = flag != 0
     if prev_point is None:
         pos = tm.position(cam_cur, cam_prev, identity, flag, nd[..., 3], W, H)
     else:
         pos, _ = mm.position(cam_cur, cam_prev, identity, flag, nd[..., 3], prev_point, W, H)
-    found, x0, y0, fx, fy, te = (pos[k] for k in ("found", "x0", "y0", "fx", "fy", "te"))
-    one = F(1)
-    weights = ((one - fx) * (one - fy), fx * (one - fy), (one - fx) * fy, fx * fy)
-    sb, sn, sm = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W), F)
-    sc = np.zeros((H, W, 3), F)
+    sb, sn, sc, sm, history = tm.gather(pos, flag, nd[..., :3], prev, depth_tol, normal_cos)      # step 4
     g, cmh = F(gamma), F(clamped_max_history)
     with np.errstate(all="ignore"):
-        # step 4
-        zmax = F(depth_tol) * np.fmax(te, tm.DEPTH_FLOOR)
-        for tap in range(4):
-            qx, qy = x0 + (tap & 1), y0 + (tap >> 1)
-            b = weights[tap].astype(F)
-            inside = found & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H) & (b > 0)
-            r, c = np.clip(H - 1 - qy, 0, H - 1), np.clip(qx, 0, W - 1)
-            n_q = h_acc[r, c, 3]
-            near = np.abs(te - p_nd[r, c, 3]) <= zmax
-            facing = tm.dot(nd[..., :3], p_nd[r, c, :3]) >= F(normal_cos)
-            use = inside & (n_q > 0) & (p_albedo[r, c, 3] == flag) & (~geometry | (near & facing))
-            sb = np.where(use, sb + b, sb)
-            sn = np.where(use, sn + b * n_q, sn)
-            sc = np.where(use[..., None], sc + b[..., None] * (h_acc[r, c, :3] / n_q[..., None]), sc)
-            sm = np.where(use, sm + b * (h_m2[r, c] / n_q), sm)
-        history = found & (sb >= F(tm.MIN_WEIGHT))
         # the statistics of the current frame
         st = statistics(accum, albedo, radius, demodulate)
         k = st["k"]
@@ -121,10 +100,7 @@ def accumulate_clamped(cam_cur, cam_prev, accum, moment2, albedo, normal_depth, 
         y_old, y_new = luminance(c_h), luminance(c_new)
         m_new = np.where(clamped, np.fmax(m_h - y_old * y_old, F(0)) + y_new * y_new, m_h)
         n_h = np.where(clamped, np.fmin(n_raw, cmh), n_raw)
-        out = accum.copy()
-        out[..., :3] = np.where(history[..., None], accum[..., :3] + c_new * n_h[..., None], accum[..., :3])
-        out[..., 3] = np.where(history, accum[..., 3] + n_h, accum[..., 3])
-        m_out = np.where(history, moment2 + m_new * n_h, moment2).astype(F)
+        out, m_out = tm.blend(accum, moment2, history, c_new, m_new, n_h)
         if return_masks:
             nan_bound = np.isnan(lo) | np.isnan(hi)
             masks = dict(
@@ -135,5 +111,5 @@ def accumulate_clamped(cam_cur, cam_prev, accum, moment2, albedo, normal_depth, 
                 k0=history & ~has_k, sd0=history & has_k & (sd == 0).any(-1),
                 nan_bound_unclamped=history & has_k & (nan_bound & ~channel).any(-1) & ~clamped,
                 nan_history=history & np.isnan(c_h).any(-1), k=k)
-            return out.astype(F), m_out, masks
-    return out.astype(F), m_out
+            return out, m_out, masks
+    return out, m_out

@@ -13,7 +13,7 @@ import pytest
 import ag_pathtracer_amd as ag
 import motion_model as mm
 import temporal_model as tm
-from helpers import gpu_context, gpu_scene
+from helpers import bits as u32, film_point, gpu_context, gpu_scene, unit
 from morph_cases import targets as morph_targets
 from skin_cases import binding
 
@@ -23,10 +23,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CW, CH = mm.CARD_W, mm.CARD_H
 CARD_BASES = {0: 0, mm.CARD_PRIM: mm.CARD_BASE}
 PT = ag.PathTracer(5)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def model_prev_point(g, cam, W, H, meshes_old, meshes_new, bases):
@@ -409,17 +405,6 @@ def test_card_scene_history_follows_the_card(move):
 CAM_CUR = ([0.3, 1.4, -6.0], [0.0, 0.0, 0.0], [0, 1, 0], 37 / 19.0, 42.0, 0.0)
 CAM_PREV = ([0.58, 0.62, -3.62], [0.5, 0.3, 0.0], [0.05, 1, 0], 37 / 19.0, 42.0, 0.0)
 MAX_HISTORY, DEPTH_TOL, NORMAL_COS = 6.0, 0.0625, 0.9
-
-
-def unit(v):
-    v = np.asarray(v, np.float64)
-    return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(F)
-
-
-def film_point(P, s, t, depth):
-    """the world point at distance `depth` from the previous camera through its film position (s, t), in float64"""
-    d = (P["llc"].astype(np.float64) + s * P["horizontal"].astype(np.float64) + t * P["vertical"].astype(np.float64)) - P["origin"].astype(np.float64)
-    return P["origin"].astype(np.float64) + depth * d / np.linalg.norm(d)
 
 
 def synthetic(W, H, cam_prev, seed=20250114):

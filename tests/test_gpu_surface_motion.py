@@ -16,7 +16,7 @@ import motion_model as mm
 import surface_motion_model as sm
 import texture_filter_model as fm
 import texture_model as txm
-from helpers import build_cpp_example, gpu_context, gpu_scene
+from helpers import bits as u32, build_cpp_example, gpu_context, gpu_scene, unit
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -24,15 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CW, CH = mm.CARD_W, mm.CARD_H
 PT = ag.PathTracer(5)
 KW = dict(max_history=6.0, depth_tol=0.0625, normal_cos=0.9)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def unit(v):
-    v = np.asarray(v, np.float64)
-    return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(F)
 
 
 # ---- 1. the temporal call against the merged calls ------------------------------------------------------------------------------

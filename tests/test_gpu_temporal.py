@@ -7,7 +7,7 @@ import pytest
 import ag_pathtracer_amd as ag
 import denoise_model as dm
 import temporal_model as tm
-from helpers import gpu_context, gpu_scene
+from helpers import gpu_context, gpu_scene, unit
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -17,11 +17,6 @@ CAM_CUR = ([0.3, 1.4, -6.0], [0.0, 0.0, 0.0], [0, 1, 0], W / float(H), 42.0, 0.0
 # just in front of it project far off its film
 CAM_PREV = ([0.58, 0.62, -3.62], [0.5, 0.3, 0.0], [0.05, 1, 0], W / float(H), 42.0, 0.0)
 MAX_HISTORY, DEPTH_TOL, NORMAL_COS = 6.0, 0.0625, 0.9
-
-
-def unit(v):
-    v = np.asarray(v, np.float64)
-    return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(F)
 
 
 def synthetic_inputs(seed=20240917):

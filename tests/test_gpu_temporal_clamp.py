@@ -14,16 +14,12 @@ import temporal_clamp_model as cm
 import temporal_model as tm
 from adaptive_model import luminance
 from denoise_cases import same_but_for_nan_payloads
-from helpers import gpu_context, gpu_scene
+from helpers import bits as u32, gpu_context, gpu_scene
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 PT = ag.PathTracer(5)
 KW = dict(max_history=cases.MAX_HISTORY, depth_tol=cases.DEPTH_TOL, normal_cos=cases.NORMAL_COS)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def same(got, want):

@@ -70,9 +70,9 @@ def test_motion_unit_compiles_without_scratch_or_lds():
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
     names = re.findall(r"remark: Function Name: (\S+)", p.stderr)
-    assert len(names) == 3 and all(any(k in n for n in names) for k in ("k_snapshot_positions", "k_motion", "k_temporal_motion")), names
+    assert len(names) == 2 and all(any(k in n for n in names) for k in ("k_snapshot_positions", "k_motion")), names
     for what in (r"ScratchSize \[bytes/lane\]", r"VGPRs Spill", r"SGPRs Spill", r"LDS Size \[bytes/block\]"):
-        assert [int(v) for v in re.findall(what + r": (\d+)", p.stderr)] == [0, 0, 0], what
+        assert [int(v) for v in re.findall(what + r": (\d+)", p.stderr)] == [0, 0], what
     assert "-ffp-contract=off" in flags and not b.SOURCE_FLAGS.get("agpt_motion.hip")
 
 

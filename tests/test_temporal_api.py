@@ -137,7 +137,12 @@ def test_feature_directions_are_the_pixel_centre_rays_of_the_oracle():
         assert D[H - 1 - y, x].tobytes() == tm.normalize(np.asarray(ray["d"], F)).tobytes(), (x, y)
 
 
-def test_temporal_unit_compiles_without_scratch_or_lds():
+PLAIN_KERNELS = ("k_temporal", "k_temporal_motion", "k_temporal_surface")
+CLAMP_KERNELS = ("k_temporal_clamp", "k_temporal_clamp_surface")
+LDS_BYTES = (64 + 2 * 3) * (4 + 2 * 3) * 16      # AGPT_TC_LDS_BYTES: the 64 x 4 tile plus a halo of 3, one float4 a pixel
+
+
+def test_temporal_unit_compiles_to_its_five_kernels_with_the_stated_resources():
     flags = [f for f in b.FLAGS if f not in ("-shared", "-fPIC")]
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "agpt_temporal.s")
@@ -145,11 +150,28 @@ def test_temporal_unit_compiles_without_scratch_or_lds():
             ["--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", "-o", out, os.path.join(b.CSRC, "agpt_temporal.hip")]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
-    names = re.findall(r"remark: Function Name: (\S+)", p.stderr)
-    assert len(names) == 1 and "k_temporal" in names[0], names
-    for what in (r"ScratchSize \[bytes/lane\]", r"VGPRs Spill", r"SGPRs Spill", r"LDS Size \[bytes/block\]"):
-        assert [int(v) for v in re.findall(what + r": (\d+)", p.stderr)] == [0], what
+    # the remarks of one kernel follow its "Function Name" remark; the name is the first component of the mangled one
+    usage = {}
+    for part in p.stderr.split("remark: Function Name: ")[1:]:
+        mangled = part.split()[0]
+        n = re.match(r"_Z(\d+)", mangled)
+        name = mangled[n.end():n.end() + int(n.group(1))]
+        assert name not in usage, name
+        usage[name] = {what: int(re.search(re.escape(what) + r": (\d+)", part).group(1))
+                       for what in ("ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")}
+    assert sorted(usage) == sorted(PLAIN_KERNELS + CLAMP_KERNELS), sorted(usage)
+    for name, u in usage.items():
+        for what in ("ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill"):
+            assert u[what] == 0, (name, what, u[what])
+        assert u["LDS Size [bytes/block]"] == (LDS_BYTES if name in CLAMP_KERNELS else 0), (name, u)
+    assert LDS_BYTES == 11200
+    assert re.search(r"#define AGPT_TC_LDS_BYTES \(AGPT_TC_TILE_W \* AGPT_TC_TILE_H \* 16\)", open(os.path.join(b.CSRC, "agpt_temporal.h")).read())
     assert "-ffp-contract=off" in flags and not b.SOURCE_FLAGS.get("agpt_temporal.hip")
+    # what DESIGN.md section 5.5.3 states
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("5.5.3"):]
+    assert "%d B" % LDS_BYTES in section
+    assert "%d waves per SIMD" % usage["k_temporal_clamp"]["Occupancy [waves/SIMD]"] in section
 
 
 # ---- the model on hand-made buffers ------------------------------------------------------------------------------------
