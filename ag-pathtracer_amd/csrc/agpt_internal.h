@@ -37,11 +37,13 @@ int fail(int code, const std::string& msg);
 int interleave_rows(int H, int block, int world, int rank);
 }  // namespace agpt
 
+// AGPT_ERR_NOMEM when the runtime says it is out of memory, AGPT_ERR_DEVICE for every other failure
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess)                                                                           \
-            return agpt::fail(AGPT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
+            return agpt::fail(e_ == hipErrorOutOfMemory ? AGPT_ERR_NOMEM : AGPT_ERR_DEVICE,             \
+                              std::string(#expr) + ": " + hipGetErrorString(e_));                       \
     } while (0)
 
 // A device allocation that belongs to its holder: freed when the holder goes (a context, a scene, a local of an entry point on
@@ -197,33 +199,8 @@ struct agpt_scene {
     std::vector<DevBuf<float4>> d_env_pixels;
     std::vector<DevBuf<float>> d_env_func, d_env_cdf;
     DevScene dev{};
-    // agpt_scene_update_mesh, one per mesh (added with it by agpt_scene_add_mesh).  updater: the device path's cache (created by the
-    // mesh's first REFIT, agpt_update.h; owned).  bounds_stale: the bounds of HostMesh::nodes are behind the device's (root box
-    // excepted; brought up to date by sync_mirror).  arrays_stale: HostMesh::vertices / normals are behind the device's as well (a
-    // device-pointer or transform REFIT: the new arrays exist only in the updater).  rest_*: the rest pose of
-    // agpt_scene_transform_mesh, agpt_scene_pose_mesh and agpt_scene_morph_mesh, a host copy taken by the mesh's first transform, pose or
-    // morph after its arrays were last given explicitly (DESIGN.md section 5.7 lists who reads the mirror).  skin: the binding of
-    // agpt_scene_set_mesh_skin (host copy; the updater holds the device copies from the first pose on).  morph: the targets of
-    // agpt_scene_set_mesh_morph_targets, likewise (device copies from the first morph on).
-    // normals_mode: agpt_scene_set_mesh_normals_mode; SMOOTH makes update_from_updater recompute the normals from the new positions
-    // (agpt_normals.h; the updater holds the adjacency from the first such REFIT on).
-    struct MeshUpdate {
-        agpt::MeshUpdater* updater = nullptr;
-        bool bounds_stale = false, arrays_stale = false, rest_valid = false;
-        std::vector<v3> rest_vertices, rest_normals;
-        agpt::SkinBinding skin;
-        agpt::MorphTargets morph;
-        int normals_mode = 0;   // AGPT_NORMALS_GIVEN / _SMOOTH (agpt_scene_set_mesh_normals_mode)
-        MeshUpdate() = default;
-        MeshUpdate(MeshUpdate&& o) noexcept
-            : updater(o.updater), bounds_stale(o.bounds_stale), arrays_stale(o.arrays_stale), rest_valid(o.rest_valid),
-              rest_vertices(std::move(o.rest_vertices)), rest_normals(std::move(o.rest_normals)), skin(std::move(o.skin)),
-              morph(std::move(o.morph)), normals_mode(o.normals_mode) {
-            o.updater = nullptr;
-        }
-        ~MeshUpdate() { agpt::mesh_updater_destroy(updater); }
-    };
-    std::vector<MeshUpdate> updates;
+    // agpt_scene_update_mesh and its front ends: one owner of the update state per mesh, host copies and device cache (agpt_update.h)
+    std::vector<agpt::MeshUpdate> updates;
     // agpt_scene_snapshot_positions: two generations of world-space triangle positions, float4[3 * n_tris] each, indexed by the GLOBAL
     // triangle id (not by BVH slot).  Allocated by the first snapshot; gen[newest] is the newer one.  agpt_scene_commit drops them; an
     // AGPT_UPDATE_REBUILD, which re-commits with the triangle ids unchanged, keeps them (update_on_host).
@@ -260,10 +237,15 @@ struct agpt_scene {
     bool spheres_stale = false;
 };
 
+// `count` elements of `host` into `buf` (grown if it holds fewer, at least one element) as a copy enqueued on `st`
+template <class T>
+static int upload(DevBuf<T>& buf, const T* host, size_t count, hipStream_t st) {
+    int rc = buf.ensure(count ? count : 1);
+    if (rc) return rc;
+    if (count) HIP_TRY(hipMemcpyAsync(buf.p, host, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return AGPT_OK;
+}
 template <class T>
 static int upload(DevBuf<T>& buf, const std::vector<T>& host, hipStream_t st) {
-    int rc = buf.ensure(host.empty() ? 1 : host.size());
-    if (rc) return rc;
-    if (!host.empty()) HIP_TRY(hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, st));
-    return AGPT_OK;
+    return upload(buf, host.data(), host.size(), st);
 }

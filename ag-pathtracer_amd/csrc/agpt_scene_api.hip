@@ -267,15 +267,15 @@ int agpt_scene_set_camera(agpt_scene* s, const agpt_camera_desc* d) {
 static int sync_mirror(agpt_scene* s, bool arrays) {
     if (const int rc = agpt::download_spheres(s)) return rc;
     for (size_t m = 0; m < s->updates.size(); m++) {
-        agpt_scene::MeshUpdate& up = s->updates[m];
+        agpt::MeshUpdate& up = s->updates[m];
         if (up.bounds_stale) {
             HIP_TRY(hipSetDevice(s->ctx->device));
-            if (const int rc = agpt::download_bounds(s->ctx->stream, up.updater, s->meshes[m])) return rc;
+            if (const int rc = up.download_bounds(s->ctx->stream, s->meshes[m])) return rc;
             up.bounds_stale = false;
         }
         if (arrays && up.arrays_stale) {
             HIP_TRY(hipSetDevice(s->ctx->device));
-            if (const int rc = agpt::download_arrays(s->ctx->stream, up.updater, s->meshes[m].vertices, s->meshes[m].normals)) return rc;
+            if (const int rc = up.download_arrays(s->ctx->stream, s->meshes[m].vertices, s->meshes[m].normals)) return rc;
             up.arrays_stale = false;
         }
     }
@@ -535,36 +535,45 @@ static int upload_toplevel(agpt_scene* s) {
     return AGPT_OK;
 }
 
-// the argument checks the three update calls share, in agpt_scene_update_mesh's order (`fn` names the call in the message)
-static int check_update(const char* fn, const agpt_scene* s, int prim, const void* vertices, int n_vertices, const void* normals, int n_normals,
-                        int mode) {
+// the arrays an update call brings; the calls that bring none (transform, pose, morph) keep the mesh's own counts by construction
+struct GivenArrays {
+    const void* vertices;
+    int n_vertices;
+    const void* normals;
+    int n_normals;
+};
+
+static bool smooth_normals(const agpt_scene* s, size_t mi) { return s->updates[mi].normals_mode == AGPT_NORMALS_SMOOTH; }
+
+// the argument checks every update call shares, in agpt_scene_update_mesh's order (`fn` names the call in the message)
+static int check_update(const char* fn, const agpt_scene* s, int prim, const GivenArrays* given, int mode) {
     const std::string f(fn);
-    if (!s || !vertices) return fail(AGPT_ERR_INVALID, f + ": NULL scene or vertices");
+    if (!s || (given && !given->vertices)) return fail(AGPT_ERR_INVALID, f + ": NULL scene or vertices");
     if (!s->committed) return fail(AGPT_ERR_INVALID, f + ": the scene is not committed");
     if (prim < 0 || prim >= (int)s->prims.size() || s->prims[prim].type != AGPT_PRIM_MESH)
         return fail(AGPT_ERR_INVALID, f + ": primitive " + std::to_string(prim) + " is not a mesh of this scene");
-    const agpt::HostMesh& mesh = s->meshes[(size_t)s->prims[prim].index];
-    const bool smooth = s->updates[(size_t)s->prims[prim].index].normals_mode == AGPT_NORMALS_SMOOTH;   // (its normals are never read)
-    if (n_vertices != (int)mesh.vertices.size() || n_normals != (int)mesh.normals.size() || (!normals && !mesh.normals.empty() && !smooth))
+    const size_t mi = (size_t)s->prims[prim].index;
+    const agpt::HostMesh& mesh = s->meshes[mi];
+    if (given && (given->n_vertices != (int)mesh.vertices.size() || given->n_normals != (int)mesh.normals.size() ||
+                  (!given->normals && !mesh.normals.empty() && !smooth_normals(s, mi))))   // (SMOOTH: its normals are never read)
         return fail(AGPT_ERR_INVALID, f + ": the mesh has " + std::to_string(mesh.vertices.size()) + " vertices and " +
                                           std::to_string(mesh.normals.size()) + " normals; both counts stay (normals may be NULL only without any)");
     if (mode != AGPT_UPDATE_REFIT && mode != AGPT_UPDATE_REBUILD) return fail(AGPT_ERR_INVALID, f + ": unknown mode " + std::to_string(mode));
     return AGPT_OK;
 }
 
-// the mesh's arrays were given explicitly: they are the rest pose of the transforms that follow
-static void forget_rest(agpt_scene* s, size_t mi) {
-    agpt_scene::MeshUpdate& up = s->updates[mi];
-    up.rest_valid = false;
-    up.rest_vertices = up.rest_normals = std::vector<v3>();
-    agpt::drop_rest(up.updater);
-}
-
 // Host orchestration of what exists, from host arrays: a new tree (REBUILD) or the host refit (a non-finite position under REFIT),
-// then the full commit.
+// then the full commit.  normals == NULL for a mesh in AGPT_NORMALS_SMOOTH mode: they are the twin's (agpt_normals.h), from the new
+// positions.
 static int update_on_host(agpt_scene* s, size_t mi, const float* vertices, const float* normals, int mode) {
     agpt::HostMesh& mesh = s->meshes[mi];
     const int n_vertices = (int)mesh.vertices.size(), n_normals = (int)mesh.normals.size();
+    std::vector<float> twin;
+    if (!normals && smooth_normals(s, mi)) {
+        twin.resize(3 * mesh.normals.size());
+        agpt::vertex_normals_host(vertices, mesh.indices.data(), mesh.indices.size() / 3, mesh.normals.size(), twin.data());
+        normals = twin.data();
+    }
     auto set_arrays = [&]() {
         set_v3(mesh.vertices, vertices, n_vertices);
         set_v3(mesh.normals, normals, n_normals);
@@ -590,29 +599,16 @@ static int update_on_host(agpt_scene* s, size_t mi, const float* vertices, const
         set_arrays();
         agpt::refit_bvh(mesh.vertices, mesh.indices, mesh.prim_index, mesh.nodes.data(), mesh.total_nodes);
     }
-    agpt_scene::MeshUpdate& up = s->updates[mi];
+    agpt::MeshUpdate& up = s->updates[mi];
     up.bounds_stale = false;   // every box of this mesh has just been computed on the host,
     up.arrays_stale = false;   // from arrays that are now the mirror's
-    if (mode == AGPT_UPDATE_REBUILD) {   // the cache holds the old topology
-        agpt::mesh_updater_destroy(up.updater);
-        up.updater = nullptr;
-    }
+    if (mode == AGPT_UPDATE_REBUILD) up.topology_changed();   // the cache holds the old topology
     // the commit below leaves every triangle its global id (same meshes, same index arrays): the position snapshots stay valid
     agpt_scene::PositionSnapshots kept = std::move(s->snapshots);
     s->snapshots = agpt_scene::PositionSnapshots();
     const int rc = agpt_scene_commit(s);
     if (rc == AGPT_OK) s->snapshots = std::move(kept);
     return rc;
-}
-
-static bool smooth_normals(const agpt_scene* s, size_t mi) { return s->updates[mi].normals_mode == AGPT_NORMALS_SMOOTH; }
-
-// update_on_host for a mesh in AGPT_NORMALS_SMOOTH mode: the normals are the twin's (agpt_normals.h), from the new positions
-static int update_on_host_smooth(agpt_scene* s, size_t mi, const float* vertices, int mode) {
-    const agpt::HostMesh& mesh = s->meshes[mi];
-    std::vector<float> n(3 * mesh.normals.size());
-    agpt::vertex_normals_host(vertices, mesh.indices.data(), mesh.indices.size() / 3, mesh.normals.size(), n.data());
-    return update_on_host(s, mi, vertices, n.data(), mode);
 }
 
 static int update_from_updater(agpt_scene* s, int prim, size_t mi, int mode);
@@ -653,91 +649,87 @@ static int refit_done(agpt_scene* s, size_t mi, const float root[6], bool arrays
 }
 
 int agpt_scene_update_mesh(agpt_scene* s, int prim, const float* vertices, int n_vertices, const float* normals, int n_normals, int mode) {
-    if (const int rc = check_update("agpt_scene_update_mesh", s, prim, vertices, n_vertices, normals, n_normals, mode)) return rc;
+    const GivenArrays given{vertices, n_vertices, normals, n_normals};
+    if (const int rc = check_update("agpt_scene_update_mesh", s, prim, &given, mode)) return rc;
     const size_t mi = (size_t)s->prims[prim].index;
     agpt::HostMesh& mesh = s->meshes[mi];
+    agpt::MeshUpdate& up = s->updates[mi];
     HIP_TRY(hipSetDevice(s->ctx->device));
-    forget_rest(s, mi);
+    up.arrays_given();
     bool finite = true;
     for (int i = 0; i < 3 * n_vertices && finite; i++) finite = std::isfinite(vertices[i]);
-    if (smooth_normals(s, mi)) {   // `normals` is not read
-        if (mode == AGPT_UPDATE_REBUILD || !finite) return update_on_host_smooth(s, mi, vertices, mode);
-        if (const int rc = agpt::upload_positions_device(s->ctx->stream, &s->updates[mi].updater, mesh, vertices)) return rc;
+    const bool smooth = smooth_normals(s, mi);   // `normals` is not read
+    if (mode == AGPT_UPDATE_REBUILD || !finite) return update_on_host(s, mi, vertices, smooth ? nullptr : normals, mode);
+    if (smooth) {
+        if (const int rc = up.upload_positions(s->ctx->stream, mesh, vertices)) return rc;
         return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `vertices` lives until then)
     }
-    if (mode == AGPT_UPDATE_REBUILD || !finite) return update_on_host(s, mi, vertices, normals, mode);
-    const agpt::UpdateTarget tg = update_target(s, prim, mi);
     float root[6];
-    if (const int rc = agpt::update_mesh_device(s->ctx->stream, &s->updates[mi].updater, mesh, vertices, normals, tg, root)) return rc;
+    if (const int rc = up.update(s->ctx->stream, mesh, vertices, normals, update_target(s, prim, mi), root)) return rc;
     set_v3(mesh.vertices, vertices, n_vertices);
     set_v3(mesh.normals, normals, n_normals);
     return refit_done(s, mi, root, false);
 }
 
-// the new arrays are in the mesh's updater (copied or transformed there): REFIT from them, or -- REBUILD, a non-finite position --
+// the new arrays are in the mesh's device cache (copied or deformed there): REFIT from them, or -- REBUILD, a non-finite position --
 // bring them to the host and do what agpt_scene_update_mesh does with host arrays
 static int update_from_updater(agpt_scene* s, int prim, size_t mi, int mode) {
     agpt::HostMesh& mesh = s->meshes[mi];
+    agpt::MeshUpdate& up = s->updates[mi];
     const bool smooth = smooth_normals(s, mi);   // the front end left positions only: the normals are recomputed from them
     if (mode == AGPT_UPDATE_REFIT) {
-        const agpt::UpdateTarget tg = update_target(s, prim, mi);
         float root[6];
         bool finite = true;
         if (smooth)
-            if (const int rc = agpt::smooth_normals_device(s->ctx->stream, s->updates[mi].updater, mesh)) return rc;
-        if (const int rc = agpt::refit_device_arrays(s->ctx->stream, s->updates[mi].updater, mesh, tg, root, &finite)) return rc;
+            if (const int rc = up.smooth_normals(s->ctx->stream, mesh)) return rc;
+        if (const int rc = up.refit(s->ctx->stream, mesh, update_target(s, prim, mi), root, &finite)) return rc;
         if (finite) return refit_done(s, mi, root, true);
     }
-    std::vector<v3> v(mesh.vertices.size()), n(mesh.normals.size());
-    if (smooth) n.clear();   // (not fetched: the host twin fills them)
-    if (const int rc = agpt::download_arrays(s->ctx->stream, s->updates[mi].updater, v, n)) return rc;
-    if (smooth) return update_on_host_smooth(s, mi, &v.data()->x, mode);
+    std::vector<v3> v(mesh.vertices.size()), n(smooth ? 0 : mesh.normals.size());   // (smooth: not fetched, the host twin fills them)
+    if (const int rc = up.download_arrays(s->ctx->stream, v, n)) return rc;
     return update_on_host(s, mi, &v.data()->x, n.empty() ? nullptr : &n.data()->x, mode);
 }
 
 int agpt_scene_update_mesh_device(agpt_scene* s, int prim, const float* vertices_dev, int n_vertices, const float* normals_dev, int n_normals,
                                   int mode) {
-    if (const int rc = check_update("agpt_scene_update_mesh_device", s, prim, vertices_dev, n_vertices, normals_dev, n_normals, mode)) return rc;
+    const GivenArrays given{vertices_dev, n_vertices, normals_dev, n_normals};
+    if (const int rc = check_update("agpt_scene_update_mesh_device", s, prim, &given, mode)) return rc;
     const size_t mi = (size_t)s->prims[prim].index;
+    agpt::MeshUpdate& up = s->updates[mi];
+    const bool smooth = smooth_normals(s, mi);   // `normals_dev` is not read
     HIP_TRY(hipSetDevice(s->ctx->device));
     if (mode == AGPT_UPDATE_REBUILD) {   // the builders take host arrays
-        const bool smooth = smooth_normals(s, mi);   // `normals_dev` is not read
         std::vector<float> v((size_t)3 * n_vertices), n(smooth ? 0 : (size_t)3 * n_normals);
         HIP_TRY(hipMemcpyAsync(v.data(), vertices_dev, v.size() * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
         if (!n.empty()) HIP_TRY(hipMemcpyAsync(n.data(), normals_dev, n.size() * sizeof(float), hipMemcpyDeviceToHost, s->ctx->stream));
         HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-        forget_rest(s, mi);
-        if (smooth) return update_on_host_smooth(s, mi, v.data(), mode);
+        up.arrays_given();
         return update_on_host(s, mi, v.data(), n.empty() ? nullptr : n.data(), mode);
     }
-    if (const int rc = agpt::copy_arrays_device(s->ctx->stream, &s->updates[mi].updater, s->meshes[mi], vertices_dev,
-                                                smooth_normals(s, mi) ? nullptr : normals_dev))
-        return rc;
-    forget_rest(s, mi);
+    if (const int rc = up.copy_arrays(s->ctx->stream, s->meshes[mi], vertices_dev, smooth ? nullptr : normals_dev)) return rc;
+    up.arrays_given();
     return update_from_updater(s, prim, mi, mode);
 }
 
-// the rest pose of the transform, the pose and the morph: the arrays the mesh last received explicitly -- the mirror, brought up to date
-// if they came as device pointers
-static int take_rest(agpt_scene* s, size_t mi) {
-    agpt_scene::MeshUpdate& up = s->updates[mi];
-    if (up.rest_valid) return AGPT_OK;
-    if (const int rc = sync_mirror(s, true)) return rc;
-    up.rest_vertices = s->meshes[mi].vertices;
-    up.rest_normals = s->meshes[mi].normals;
-    up.rest_valid = true;
-    agpt::drop_rest(up.updater);
-    return AGPT_OK;
+// The tail the transform, the pose and the morph share.  The rest pose: the arrays the mesh last received explicitly -- the mirror,
+// brought up to date if they came as device pointers.  Then the one launcher and the refit.  Synchronises with the stream: what the
+// request points to lives until then.
+static int deform_mesh(agpt_scene* s, int prim, int mode, agpt::DeformRequest rq) {
+    const size_t mi = (size_t)s->prims[prim].index;
+    agpt::MeshUpdate& up = s->updates[mi];
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (!up.has_rest()) {
+        if (const int rc = sync_mirror(s, true)) return rc;
+        up.rest_taken(s->meshes[mi].vertices, s->meshes[mi].normals);
+    }
+    rq.with_normals = !smooth_normals(s, mi);
+    rq.num_cus = s->ctx->num_cus;
+    if (const int rc = up.deform(s->ctx->stream, s->meshes[mi], rq)) return rc;
+    return update_from_updater(s, prim, mi, mode);
 }
 
 int agpt_scene_transform_mesh(agpt_scene* s, int prim, const float* transform16, int mode) {
-    {   // the checks of agpt_scene_update_mesh with the mesh's own counts, then the matrix
-        const agpt::HostMesh* m = s && s->committed ? mesh_of(s, prim) : nullptr;
-        const int dummy = 0;
-        if (const int rc = check_update("agpt_scene_transform_mesh", s, prim, &dummy, m ? (int)m->vertices.size() : 0, &dummy,
-                                        m ? (int)m->normals.size() : 0, mode))
-            return rc;
-    }
+    if (const int rc = check_update("agpt_scene_transform_mesh", s, prim, nullptr, mode)) return rc;
     if (!transform16) return fail(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: NULL matrix");
     agpt::Mat4 M;
     std::memcpy(M.c, transform16, sizeof(M.c));
@@ -746,23 +738,27 @@ int agpt_scene_transform_mesh(agpt_scene* s, int prim, const float* transform16,
     float det = 0;
     const agpt::Mat4 N = agpt::inverse_transpose(M, &det);
     if (det == 0) return fail(AGPT_ERR_INVALID, "agpt_scene_transform_mesh: the matrix is singular (its determinant is exactly 0)");
-    const size_t mi = (size_t)s->prims[prim].index;
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    agpt_scene::MeshUpdate& up = s->updates[mi];
-    if (const int rc = take_rest(s, mi)) return rc;
-    if (const int rc = agpt::transform_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, M, N,
-                                                     !smooth_normals(s, mi)))
-        return rc;
-    return update_from_updater(s, prim, mi, mode);
+    agpt::DeformRequest rq{"agpt_scene_transform_mesh"};
+    rq.M = &M;
+    rq.N = &N;
+    return deform_mesh(s, prim, mode, rq);
+}
+
+// the scene and the mesh primitive of a setter (`f` is the call's name and ": "): the mesh and its update state
+static int setter_mesh(const std::string& f, agpt_scene* s, int prim, const agpt::HostMesh** m, agpt::MeshUpdate** up) {
+    if (!s) return fail(AGPT_ERR_INVALID, f + "NULL scene");
+    *m = mesh_of(s, prim);
+    if (!*m) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " is not a mesh of this scene");
+    *up = &s->updates[(size_t)s->prims[prim].index];
+    return AGPT_OK;
 }
 
 int agpt_scene_set_mesh_skin(agpt_scene* s, int prim, int influences, int n_joints, const int32_t* vertex_joints, const float* vertex_weights,
                              const int32_t* normal_joints, const float* normal_weights) {
     const std::string f = "agpt_scene_set_mesh_skin: ";
-    if (!s) return fail(AGPT_ERR_INVALID, f + "NULL scene");
-    const agpt::HostMesh* m = mesh_of(s, prim);
-    if (!m) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " is not a mesh of this scene");
-    agpt_scene::MeshUpdate& up = s->updates[(size_t)s->prims[prim].index];
+    const agpt::HostMesh* m;
+    agpt::MeshUpdate* up;
+    if (const int rc = setter_mesh(f, s, prim, &m, &up)) return rc;
     agpt::SkinBinding skin;
     if (influences != 0) {   // the twin's rules, with the mesh's own counts
         const size_t nv = m->vertices.size(), nn = m->normals.size();
@@ -785,16 +781,16 @@ int agpt_scene_set_mesh_skin(agpt_scene* s, int prim, int influences, int n_join
             skin.normal_weights.assign(normal_weights, normal_weights + nn * (size_t)influences);
         }
     }
-    if (up.updater) HIP_TRY(hipSetDevice(s->ctx->device));
-    agpt::drop_skin(up.updater);   // (nothing goes up here: the next pose uploads the new binding)
-    up.skin = std::move(skin);
+    if (up->on_device()) HIP_TRY(hipSetDevice(s->ctx->device));
+    up->skin_changed(std::move(skin));
     return AGPT_OK;
 }
 
 // the checks of a frame's joint matrices that agpt_scene_pose_mesh and agpt_scene_morph_mesh share, in their order, then the palette
-// (`f` is the call's name and ": ")
-static int pose_palette(const std::string& f, int prim, const agpt::SkinBinding& skin, bool with_normals, const float* joints16, int n_joints,
-                        std::vector<float>& palette) {
+// (`f` is the call's name and ": "; for a mesh in AGPT_NORMALS_SMOOTH mode, as for one without normals, the palette carries M only)
+static int pose_palette(const std::string& f, const agpt_scene* s, int prim, const float* joints16, int n_joints, std::vector<float>& palette) {
+    const size_t mi = (size_t)s->prims[prim].index;
+    const agpt::SkinBinding& skin = s->updates[mi].skin();
     if (skin.influences == 0) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no skin (agpt_scene_set_mesh_skin)");
     if (!joints16) return fail(AGPT_ERR_INVALID, f + "NULL joints16");
     if (n_joints != skin.n_joints)
@@ -804,39 +800,25 @@ static int pose_palette(const std::string& f, int prim, const agpt::SkinBinding&
     const std::string bad = agpt::skin_check_last_rows(joints16, n_joints);
     if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
     int singular = -1;
-    palette = agpt::skin_pack_palette(joints16, n_joints, with_normals, &singular);
+    palette = agpt::skin_pack_palette(joints16, n_joints, !s->meshes[mi].normals.empty() && !smooth_normals(s, mi), &singular);
     if (singular >= 0) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(singular) + " is singular (its determinant is exactly 0)");
     return AGPT_OK;
 }
 
 int agpt_scene_pose_mesh(agpt_scene* s, int prim, const float* joints16, int n_joints, int mode) {
-    const std::string f = "agpt_scene_pose_mesh: ";
-    {   // the checks of agpt_scene_update_mesh with the mesh's own counts
-        const agpt::HostMesh* m = s && s->committed ? mesh_of(s, prim) : nullptr;
-        const int dummy = 0;
-        if (const int rc = check_update("agpt_scene_pose_mesh", s, prim, &dummy, m ? (int)m->vertices.size() : 0, &dummy,
-                                        m ? (int)m->normals.size() : 0, mode))
-            return rc;
-    }
-    const size_t mi = (size_t)s->prims[prim].index;
-    agpt_scene::MeshUpdate& up = s->updates[mi];
+    if (const int rc = check_update("agpt_scene_pose_mesh", s, prim, nullptr, mode)) return rc;
     std::vector<float> palette;
-    const bool with_normals = !smooth_normals(s, mi);   // (smooth: the palette carries M only)
-    if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty() && with_normals, joints16, n_joints, palette)) return rc;
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    if (const int rc = take_rest(s, mi)) return rc;   // as for agpt_scene_transform_mesh: the two share the rest pose
-    if (const int rc = agpt::skin_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, up.skin, palette,
-                                                s->ctx->num_cus, with_normals))
-        return rc;
-    return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `palette` lives until then)
+    if (const int rc = pose_palette("agpt_scene_pose_mesh: ", s, prim, joints16, n_joints, palette)) return rc;
+    agpt::DeformRequest rq{"agpt_scene_pose_mesh"};
+    rq.palette = &palette;
+    return deform_mesh(s, prim, mode, rq);
 }
 
 int agpt_scene_set_mesh_morph_targets(agpt_scene* s, int prim, int n_targets, const float* position_deltas, const float* normal_deltas) {
     const std::string f = "agpt_scene_set_mesh_morph_targets: ";
-    if (!s) return fail(AGPT_ERR_INVALID, f + "NULL scene");
-    const agpt::HostMesh* m = mesh_of(s, prim);
-    if (!m) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " is not a mesh of this scene");
-    agpt_scene::MeshUpdate& up = s->updates[(size_t)s->prims[prim].index];
+    const agpt::HostMesh* m;
+    agpt::MeshUpdate* up;
+    if (const int rc = setter_mesh(f, s, prim, &m, &up)) return rc;
     agpt::MorphTargets morph;
     if (n_targets != 0) {   // the twin's rules, with the mesh's own counts
         const size_t nv = m->vertices.size(), nn = m->normals.size(), T = (size_t)n_targets;
@@ -850,52 +832,40 @@ int agpt_scene_set_mesh_morph_targets(agpt_scene* s, int prim, int n_targets, co
         morph.position_deltas.assign(position_deltas, position_deltas + T * nv * 3);
         if (normal_deltas) morph.normal_deltas.assign(normal_deltas, normal_deltas + T * nn * 3);   // (nothing for a mesh without normals)
     }
-    if (up.updater) HIP_TRY(hipSetDevice(s->ctx->device));
-    agpt::drop_morph(up.updater);   // (nothing goes up here: the next morph uploads the new targets)
-    up.morph = std::move(morph);
+    if (up->on_device()) HIP_TRY(hipSetDevice(s->ctx->device));
+    up->morph_changed(std::move(morph));
     return AGPT_OK;
 }
 
 int agpt_scene_morph_mesh(agpt_scene* s, int prim, const float* weights, int n_targets, const float* joints16, int n_joints, int mode) {
     const std::string f = "agpt_scene_morph_mesh: ";
-    {   // the checks of agpt_scene_update_mesh with the mesh's own counts
-        const agpt::HostMesh* m = s && s->committed ? mesh_of(s, prim) : nullptr;
-        const int dummy = 0;
-        if (const int rc = check_update("agpt_scene_morph_mesh", s, prim, &dummy, m ? (int)m->vertices.size() : 0, &dummy,
-                                        m ? (int)m->normals.size() : 0, mode))
-            return rc;
-    }
-    const size_t mi = (size_t)s->prims[prim].index;
-    agpt_scene::MeshUpdate& up = s->updates[mi];
-    if (up.morph.n_targets == 0)
-        return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no morph targets (agpt_scene_set_mesh_morph_targets)");
+    if (const int rc = check_update("agpt_scene_morph_mesh", s, prim, nullptr, mode)) return rc;
+    const int bound = s->updates[(size_t)s->prims[prim].index].morph().n_targets;
+    if (bound == 0) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no morph targets (agpt_scene_set_mesh_morph_targets)");
     if (!weights) return fail(AGPT_ERR_INVALID, f + "NULL weights");
-    if (n_targets != up.morph.n_targets)
-        return fail(AGPT_ERR_INVALID, f + "n_targets is " + std::to_string(n_targets) + ", the targets were set with " + std::to_string(up.morph.n_targets));
+    if (n_targets != bound)
+        return fail(AGPT_ERR_INVALID, f + "n_targets is " + std::to_string(n_targets) + ", the targets were set with " + std::to_string(bound));
     const std::string bad = agpt::morph_check_weights(weights, n_targets);
     if (!bad.empty()) return fail(AGPT_ERR_INVALID, f + bad);
     std::vector<float> palette;
-    const bool with_normals = !smooth_normals(s, mi);
     if (joints16)   // morph, then skin: agpt_scene_pose_mesh's checks
-        if (const int rc = pose_palette(f, prim, up.skin, !s->meshes[mi].normals.empty() && with_normals, joints16, n_joints, palette)) return rc;
+        if (const int rc = pose_palette(f, s, prim, joints16, n_joints, palette)) return rc;
     const std::vector<agpt::MorphActive> active = agpt::morph_active_list(weights, n_targets);
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    if (const int rc = take_rest(s, mi)) return rc;   // the rest pose the transform and the pose use
-    if (const int rc = agpt::morph_arrays_device(s->ctx->stream, &up.updater, s->meshes[mi], up.rest_vertices, up.rest_normals, up.morph, active,
-                                                 joints16 ? &up.skin : nullptr, joints16 ? &palette : nullptr, s->ctx->num_cus, with_normals))
-        return rc;
-    return update_from_updater(s, prim, mi, mode);   // (synchronises with the stream: `active` and `palette` live until then)
+    agpt::DeformRequest rq{"agpt_scene_morph_mesh"};
+    rq.active = &active;
+    if (joints16) rq.palette = &palette;
+    return deform_mesh(s, prim, mode, rq);
 }
 
 int agpt_scene_set_mesh_normals_mode(agpt_scene* s, int prim, int mode) {
     const std::string f = "agpt_scene_set_mesh_normals_mode: ";
-    if (!s) return fail(AGPT_ERR_INVALID, f + "NULL scene");
-    const agpt::HostMesh* m = mesh_of(s, prim);
-    if (!m) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " is not a mesh of this scene");
+    const agpt::HostMesh* m;
+    agpt::MeshUpdate* up;
+    if (const int rc = setter_mesh(f, s, prim, &m, &up)) return rc;
     if (mode != AGPT_NORMALS_GIVEN && mode != AGPT_NORMALS_SMOOTH) return fail(AGPT_ERR_INVALID, f + "unknown mode " + std::to_string(mode));
     if (mode == AGPT_NORMALS_SMOOTH && m->normals.empty())
         return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no normals (the counts of a mesh cannot change)");
-    s->updates[(size_t)s->prims[prim].index].normals_mode = mode;
+    up->normals_mode = mode;
     return AGPT_OK;
 }
 

@@ -1,12 +1,15 @@
 // agpt_update.h -- agpt_scene_update_mesh's device path (agpt_update.hip): the records of ONE mesh of a committed scene -- its
 // triangles' tri_verts / tri_shade entries, the bounds of its BVH nodes, its root box wherever the scene keeps a copy -- rewritten
 // on the GPU for new vertex positions and normals, byte for byte what flatten_scene (agpt_host_scene.cpp) writes for them: both call
-// the record writers of agpt_records.h and the box arithmetic of agpt_bvh_arith.h.
+// the record writers of agpt_records.h and the box arithmetic of agpt_bvh_arith.h.  MeshUpdate is the one owner of what a mesh keeps
+// between such calls, on the host and on the device; MeshUpdate::deform is the one launcher of the kernels that make new arrays from
+// the rest pose.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "agpt_host_scene.hpp"
@@ -28,58 +31,87 @@ struct UpdateTarget {
     uint32_t node_base, tri_base, prim_id;
 };
 
-// What the device path keeps per mesh between updates: indices, texture coordinates, prim_index, the tree's topology and per-level
-// node lists (uploaded on the first update), positions / normals, the rest pose of agpt_scene_transform_mesh, agpt_scene_pose_mesh
-// and agpt_scene_morph_mesh, the binding and palette of a skin, the deltas and active list of morph targets, the adjacency and face
-// vectors of smooth normals, and the bounds in the reference layout.
-struct MeshUpdater;
-void mesh_updater_destroy(MeshUpdater*);
+// What a frame asks of MeshUpdate::deform.  One of three shapes: M and N (agpt_scene_transform_mesh: N = inverse_transpose(M)); `palette`
+// (agpt_scene_pose_mesh: agpt_skin.h's packed palette for the state's binding); `active` (agpt_scene_morph_mesh: the frame's (target,
+// weight) pairs for the state's targets), with `palette` as well when the morph runs on through the skin.  The caller keeps what the
+// pointers name until the stream is synchronised.
+struct DeformRequest {
+    const char* fn;            // the entry point, named in the messages
+    const Mat4 *M = nullptr, *N = nullptr;
+    const std::vector<float>* palette = nullptr;
+    const std::vector<MorphActive>* active = nullptr;
+    bool with_normals = true;  // false for a mesh in AGPT_NORMALS_SMOOTH mode: the normal halves get an item count of zero and the palette
+                               // carries M only (stride 13)
+    int num_cus = 1;           // sizes the grids of k_skin_mesh and k_morph_mesh
+};
 
-// Uploads the new arrays and rewrites the mesh's records on `stream`; *cache is created on the first call.  root6 receives the new
-// root box (bmin, bmax).  Synchronises with the stream.  AGPT_OK or AGPT_ERR_DEVICE / _NOMEM / _INVALID with the message recorded.
-int update_mesh_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices, const float* normals,
-                       const UpdateTarget& target, float root6[6]);
-// The four device-resident front ends of the same rewrite (agpt_scene_update_mesh_device, agpt_scene_transform_mesh,
-// agpt_scene_pose_mesh, agpt_scene_morph_mesh).  Each leaves the new arrays in the cache's own buffers without synchronising:
-//   copy_arrays_device       device-to-device copies of the caller's packed xyz arrays, enqueued on `stream`;
-//   transform_arrays_device  k_transform_mesh: the rest pose through M (positions) and N = inverse_transpose(M) (normals).  The rest
-//                            arrays are uploaded from the host vectors when the cache holds none (the first call, and the first
-//                            after drop_rest) and kept; otherwise the vectors are only measured.
-//   skin_arrays_device       k_skin_mesh: the rest pose through the palette (agpt_skin.h) and the binding's influences.  The rest
-//                            arrays as above; the binding is uploaded when the cache holds none (the first pose, the first after drop_skin
-//                            or after the cache was destroyed) and kept; the palette goes up with every call, and the caller keeps
-//                            it until the stream is synchronised.  num_cus sizes the grid.
-//   morph_arrays_device      k_morph_mesh: the rest pose plus the active targets' deltas (agpt_morph.h) and, with `skin` and `palette`
-//                            (both or neither), through the skin in the same kernel.  Rest arrays and binding as above; the targets'
-//                            deltas are uploaded when the cache holds none (the first morph, the first after drop_morph or after the
-//                            cache was destroyed) and kept; `active` (and the palette) go up with every call, and the caller keeps
-//                            them until the stream is synchronised.
-// refit_device_arrays then rewrites the mesh's records from those buffers like update_mesh_device; *finite is false if any of the
-// 3 * n_vertices coordinates is Inf or NaN (k_check_finite), and the caller must then replace the records through the host path.
-// Only the flag and the root box come back.  download_arrays fetches the buffers' contents (vertices / normals keep their sizes).
-int copy_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices_dev, const float* normals_dev);
-int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N, bool with_normals);
-int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus,
-                       bool with_normals);
-int morph_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                        const std::vector<v3>& rest_normals, const MorphTargets& morph, const std::vector<MorphActive>& active,
-                        const SkinBinding* skin, const std::vector<float>* palette, int num_cus, bool with_normals);
-// AGPT_NORMALS_SMOOTH.  The three kernels above take with_normals == false for a mesh in that mode: their normal halves get an item
-// count of zero and the palette carries M only (stride 13).  copy_arrays_device accepts normals_dev == NULL (room is made, nothing is
-// copied), and upload_positions_device is its host-array form (the caller keeps `vertices` until the stream is synchronised).
-// smooth_normals_device then writes the cache's normals buffer from its positions: k_face_normals and k_vertex_normals
-// (agpt_normals.h), enqueued on `stream` without synchronising.  The CSR adjacency of the normal items is built on the host and
-// uploaded when the cache holds none (the mesh's first smooth update, and the first after a REBUILD destroyed the cache) and kept.
-int upload_positions_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices);
-int smooth_normals_device(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh);
-int refit_device_arrays(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh, const UpdateTarget& target, float root6[6], bool* finite);
-void drop_rest(MeshUpdater* cache);   // the rest pose changed (NULL is fine)
-void drop_skin(MeshUpdater* cache);   // the binding changed: its device copies are freed (NULL is fine)
-void drop_morph(MeshUpdater* cache);  // the targets changed: their device copies are freed (NULL is fine)
-int download_arrays(hipStream_t stream, const MeshUpdater* cache, std::vector<v3>& vertices, std::vector<v3>& normals);
-// mesh.nodes' bounds from the last update_mesh_device of this cache (the host mirror is brought up to date on demand)
-int download_bounds(hipStream_t stream, const MeshUpdater* cache, HostMesh& mesh);
+struct MeshDeviceCache;   // agpt_update.hip
+
+// Everything agpt_scene_update_mesh and its front ends keep per mesh between calls, behind ONE owner (one per mesh of a scene, added
+// with it by agpt_scene_add_mesh).
+//   host    the rest pose of transform / pose / morph (a copy of the arrays the mesh last received explicitly, taken by the first of
+//           those calls after them), the binding of agpt_scene_set_mesh_skin, the targets of agpt_scene_set_mesh_morph_targets, the
+//           normals mode, and what the mirror (HostMesh) lacks: bounds_stale -- the bounds of HostMesh::nodes are behind the device's,
+//           root box excepted --, arrays_stale -- HostMesh::vertices / normals are as well (a REFIT whose new arrays exist only on the
+//           device).  The scene's sync_mirror brings both up to date (DESIGN.md section 5.7 lists who reads the mirror).
+//   device  the cache, created by the mesh's first REFIT: indices, texture coordinates, prim_index, the tree's topology and per-level
+//           node lists, positions / normals, the bounds in the reference layout, and -- each uploaded by the first call that needs it
+//           and kept -- the rest pose, the binding, the targets' deltas, the CSR adjacency of smooth normals; per call the palette, the
+//           active list and the face vectors.
+// The host copies change only through the four methods below, and each drops the device copies that were made from them: no caller
+// can invalidate one side without the other.  The methods that free device memory need the scene's device current (on_device()).
+class MeshUpdate {
+public:
+    bool bounds_stale = false, arrays_stale = false;
+    int normals_mode = 0;   // AGPT_NORMALS_GIVEN / _SMOOTH (agpt_scene_set_mesh_normals_mode)
+
+    MeshUpdate();
+    MeshUpdate(MeshUpdate&& o) noexcept;
+    ~MeshUpdate();
+
+    bool has_rest() const { return rest_valid_; }
+    const SkinBinding& skin() const { return skin_; }
+    const MorphTargets& morph() const { return morph_; }
+    bool on_device() const { return dev_ != nullptr; }
+
+    void arrays_given();                                                                   // explicit arrays: the rest pose is forgotten
+    void rest_taken(const std::vector<v3>& vertices, const std::vector<v3>& normals);     // ... and these are the new one
+    void skin_changed(SkinBinding&& skin);
+    void morph_changed(MorphTargets&& morph);
+    void topology_changed();   // a REBUILD: the whole cache goes; the mirror has just been written, so nothing of it is stale
+
+    // The device path.  Every call returns AGPT_OK or AGPT_ERR_DEVICE / _NOMEM / _INVALID with the message recorded; the cache is created
+    // by the first that needs it.
+    // update: uploads the new arrays and rewrites the mesh's records on `stream`; root6 receives the new root box (bmin, bmax).
+    // Synchronises with the stream.
+    int update(hipStream_t stream, const HostMesh& mesh, const float* vertices, const float* normals, const UpdateTarget& target, float root6[6]);
+    // The front ends of the same rewrite leave the new arrays in the cache's own buffers without synchronising:
+    //   copy_arrays       device-to-device copies of the caller's packed xyz arrays; normals_dev == NULL (SMOOTH mode): room is made,
+    //                     nothing is copied
+    //   upload_positions  its host-array form for SMOOTH mode (the caller keeps `vertices` until the stream is synchronised)
+    //   deform            k_transform_mesh, k_skin_mesh or k_morph_mesh by the request, from the rest pose
+    //   smooth_normals    then writes the normals buffer from the positions: k_face_normals and k_vertex_normals (agpt_normals.h)
+    // refit then rewrites the mesh's records from those buffers like update; *finite is false if any of the 3 * n_vertices coordinates
+    // is Inf or NaN (k_check_finite), and the caller must then replace the records through the host path.  Only the flag and the root
+    // box come back.
+    int copy_arrays(hipStream_t stream, const HostMesh& mesh, const float* vertices_dev, const float* normals_dev);
+    int upload_positions(hipStream_t stream, const HostMesh& mesh, const float* vertices);
+    int deform(hipStream_t stream, const HostMesh& mesh, const DeformRequest& rq);
+    int smooth_normals(hipStream_t stream, const HostMesh& mesh);
+    int refit(hipStream_t stream, const HostMesh& mesh, const UpdateTarget& target, float root6[6], bool* finite);
+    // the buffers' contents (vertices / normals keep their sizes), and mesh.nodes' bounds from the last refit
+    int download_arrays(hipStream_t stream, std::vector<v3>& vertices, std::vector<v3>& normals) const;
+    int download_bounds(hipStream_t stream, HostMesh& mesh) const;
+
+private:
+    int ensure_cache(hipStream_t stream, const HostMesh& mesh);
+    int ensure_rest(const char* fn, hipStream_t stream, const HostMesh& mesh);
+
+    bool rest_valid_ = false;
+    std::vector<v3> rest_vertices_, rest_normals_;
+    SkinBinding skin_;
+    MorphTargets morph_;
+    std::unique_ptr<MeshDeviceCache> dev_;
+};
 
 }  // namespace agpt

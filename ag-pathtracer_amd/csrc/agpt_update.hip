@@ -73,31 +73,26 @@
 //              k_morph_mesh<true, false>   50 / 53 / 0 / 0        (fused, palette in global memory)
 //              k_morph_mesh<true, true>    52 / 55 / 0 / 0        (fused, palette in LDS)
 //            kLds has no meaning without kSkin: <false, true> is not instantiated, so there are three, not four.
-#include "agpt_update.h"
-
+//
+// The host half.  MeshDeviceCache holds the device copies of one mesh; MeshUpdate (agpt_update.h) owns it beside the host copies and
+// is the only one to invalidate either.  MeshUpdate::deform is the one launcher of k_transform_mesh, k_skin_mesh and k_morph_mesh: rest
+// pose, uploads, argument records, grid and the LDS-or-global route are worked out once.  The bodies of k_skin_mesh and k_morph_mesh
+// stay written out: one shared deform_block<kMorph, kSkin, kLds> was tried and grew k_skin_mesh by 12 (LDS) and 20 (global) instructions.
 #include <cstdlib>
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "agpt_bvh_arith.h"
+#include "agpt_internal.h"
 #include "agpt_normals.h"
 
 namespace agpt {
 
-int fail(int code, const std::string& msg);   // agpt_api.hip: the message of agpt_last_error
-
 namespace {
-
-#define UPD_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return fail(e_ == hipErrorOutOfMemory ? AGPT_ERR_NOMEM : AGPT_ERR_DEVICE,             \
-                                std::string(#expr) + ": " + hipGetErrorString(e_));                       \
-    } while (0)
 
 constexpr int kBlock = 64;
 
@@ -342,66 +337,77 @@ __global__ __launch_bounds__(kSkinBlock) void k_morph_mesh(const MorphActive* __
     }
 }
 
-template <class T>
-struct Buf {
-    T* p = nullptr;
-    ~Buf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t upload(const T* host, size_t count, hipStream_t st) {
-        if (!p) {
-            const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
-            if (e != hipSuccess) {
-                p = nullptr;
-                return e;
-            }
-        }
-        return count ? hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
-    }
-    hipError_t reserve(size_t count) {
-        if (p) return hipSuccess;
-        const hipError_t e = hipMalloc((void**)&p, (count ? count : 1) * sizeof(T));
-        if (e != hipSuccess) p = nullptr;
-        return e;
-    }
-};
-
 }  // namespace
 
-struct MeshUpdater {
-    Buf<float> verts, normals;
-    // agpt_scene_transform_mesh: the rest pose k_transform_mesh reads (uploaded by the first transform after the arrays were given)
-    Buf<float> rest_verts, rest_normals;
+struct MeshDeviceCache {
+    DevBuf<float> verts, normals;
+    // the rest pose k_transform_mesh, k_skin_mesh and k_morph_mesh read (uploaded by the first deform after the arrays were given)
+    DevBuf<float> rest_verts, rest_normals;
     bool has_rest = false;
-    // agpt_scene_pose_mesh: the binding (uploaded by the first pose after it was set) and the palette of the last pose
-    Buf<int32_t> skin_vertex_joints, skin_normal_joints;
-    Buf<float> skin_vertex_weights, skin_normal_weights, skin_palette;
+    // the binding (uploaded by the first pose after it was set) and the palette of the last pose
+    DevBuf<int32_t> skin_vertex_joints, skin_normal_joints;
+    DevBuf<float> skin_vertex_weights, skin_normal_weights, skin_palette;
     bool has_skin = false;
-    // agpt_scene_morph_mesh: the targets' deltas (uploaded by the first morph after they were set) and the active list of the last morph
-    Buf<float> morph_position_deltas, morph_normal_deltas;
-    Buf<MorphActive> morph_active;
+    // the targets' deltas (uploaded by the first morph after they were set) and the active list of the last morph
+    DevBuf<float> morph_position_deltas, morph_normal_deltas;
+    DevBuf<MorphActive> morph_active;
     bool has_morph = false;
     // AGPT_NORMALS_SMOOTH: the CSR adjacency of the normal items (built and uploaded by the first smooth update of this cache) and the
     // face vectors of the last one
-    Buf<int32_t> normal_offsets, normal_corner_tri;
-    Buf<float4> face_normals;
+    DevBuf<int32_t> normal_offsets, normal_corner_tri;
+    DevBuf<float4> face_normals;
     bool has_adjacency = false;
-    Buf<uint32_t> flag;        // k_check_finite's word
-    Buf<v2> uv;
-    Buf<int32_t> indices, prim_index, lists;
-    Buf<int2> topo;
-    Buf<float4> bounds;
+    DevBuf<uint32_t> flag;        // k_check_finite's word
+    DevBuf<v2> uv;
+    DevBuf<int32_t> indices, prim_index, lists;
+    DevBuf<int2> topo;
+    DevBuf<float4> bounds;
     // lists: all leaves first, then the interior nodes level by level from the deepest up; launch l covers [begin[l], begin[l + 1])
     std::vector<int> begin;
     int total_nodes = 0;
 };
 
-void mesh_updater_destroy(MeshUpdater* u) { delete u; }
+MeshUpdate::MeshUpdate() = default;
+MeshUpdate::MeshUpdate(MeshUpdate&&) noexcept = default;
+MeshUpdate::~MeshUpdate() = default;
+
+void MeshUpdate::arrays_given() {
+    rest_valid_ = false;
+    rest_vertices_ = rest_normals_ = std::vector<v3>();
+    if (dev_) dev_->has_rest = false;
+}
+
+void MeshUpdate::rest_taken(const std::vector<v3>& vertices, const std::vector<v3>& normals) {
+    rest_vertices_ = vertices;
+    rest_normals_ = normals;
+    rest_valid_ = true;
+    if (dev_) dev_->has_rest = false;
+}
+
+void MeshUpdate::skin_changed(SkinBinding&& skin) {
+    skin_ = std::move(skin);
+    if (!dev_) return;   // (nothing goes up here: the next pose uploads the new binding)
+    for (DevBuf<int32_t>* b : {&dev_->skin_vertex_joints, &dev_->skin_normal_joints}) b->release();
+    for (DevBuf<float>* b : {&dev_->skin_vertex_weights, &dev_->skin_normal_weights, &dev_->skin_palette}) b->release();
+    dev_->has_skin = false;
+}
+
+void MeshUpdate::morph_changed(MorphTargets&& morph) {
+    morph_ = std::move(morph);
+    if (!dev_) return;   // (nothing goes up here: the next morph uploads the new targets)
+    dev_->morph_position_deltas.release();
+    dev_->morph_normal_deltas.release();
+    dev_->morph_active.release();
+    dev_->has_morph = false;
+}
+
+void MeshUpdate::topology_changed() {
+    dev_.reset();
+    bounds_stale = arrays_stale = false;
+}
 
 // the topology and the per-level node lists of a tree of build_bvh's, checked against the sizes the kernels index with
-static int prepare(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh) {
+static int prepare(hipStream_t stream, MeshDeviceCache& u, const HostMesh& mesh) {
     const int total = mesh.total_nodes, n_tris = (int)mesh.prim_index.size();
     std::vector<int2> topo((size_t)total + 1, make_int2(0, 0));
     std::vector<int> depth((size_t)total + 1, -1);
@@ -433,38 +439,36 @@ static int prepare(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh) {
     for (int32_t p : mesh.prim_index)
         if (p < 0 || p % 3 != 0 || p / 3 >= n_tris) return fail(AGPT_ERR_INVALID, "agpt_scene_update_mesh: bad prim_index");
     u.total_nodes = total;
-    UPD_TRY(u.topo.upload(topo.data(), topo.size(), stream));
-    UPD_TRY(u.lists.upload(lists.data(), lists.size(), stream));
-    UPD_TRY(u.indices.upload(mesh.indices.data(), mesh.indices.size(), stream));
-    UPD_TRY(u.prim_index.upload(mesh.prim_index.data(), mesh.prim_index.size(), stream));
-    if (!mesh.texcoords.empty()) UPD_TRY(u.uv.upload(mesh.texcoords.data(), mesh.texcoords.size(), stream));
-    UPD_TRY(hipMalloc((void**)&u.bounds.p, 2 * ((size_t)total + 1) * sizeof(float4)));
-    UPD_TRY(hipMemsetAsync(u.bounds.p, 0, 2 * ((size_t)total + 1) * sizeof(float4), stream));
-    UPD_TRY(hipStreamSynchronize(stream));   // the staging vectors above go out of scope
+    if (const int rc = upload(u.topo, topo, stream)) return rc;
+    if (const int rc = upload(u.lists, lists, stream)) return rc;
+    if (const int rc = upload(u.indices, mesh.indices, stream)) return rc;
+    if (const int rc = upload(u.prim_index, mesh.prim_index, stream)) return rc;
+    if (!mesh.texcoords.empty())
+        if (const int rc = upload(u.uv, mesh.texcoords, stream)) return rc;
+    if (const int rc = u.bounds.ensure(2 * ((size_t)total + 1))) return rc;
+    HIP_TRY(hipMemsetAsync(u.bounds.p, 0, 2 * ((size_t)total + 1) * sizeof(float4), stream));
+    HIP_TRY(hipStreamSynchronize(stream));   // the staging vectors above go out of scope
     return AGPT_OK;
 }
 
-static int ensure(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh) {
-    if (*cache) return AGPT_OK;
-    MeshUpdater* u = new MeshUpdater();
-    const int rc = prepare(stream, *u, mesh);
-    if (rc != AGPT_OK) {
-        delete u;
-        return rc;
-    }
-    *cache = u;
+int MeshUpdate::ensure_cache(hipStream_t stream, const HostMesh& mesh) {
+    if (dev_) return AGPT_OK;
+    std::unique_ptr<MeshDeviceCache> u(new MeshDeviceCache());
+    if (const int rc = prepare(stream, *u, mesh)) return rc;
+    dev_ = std::move(u);
     return AGPT_OK;
 }
 
-// The records of the mesh from u.verts / u.normals, then the root box; with `finite`, k_check_finite runs ahead of the rest and its
-// flag comes back beside the box.  A non-finite position harms nothing here (every index comes from the topology): the caller
+// The records of the mesh from the cache's verts / normals, then the root box; with `finite`, k_check_finite runs ahead of the rest and
+// its flag comes back beside the box.  A non-finite position harms nothing here (every index comes from the topology): the caller
 // replaces what this wrote through the host path.
-static int refit(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh, const UpdateTarget& tg, float root6[6], bool* finite) {
+int MeshUpdate::refit(hipStream_t stream, const HostMesh& mesh, const UpdateTarget& tg, float root6[6], bool* finite) {
+    MeshDeviceCache& u = *dev_;
     const int n_tris = (int)mesh.prim_index.size();
     if (finite) {
         const size_t n = 3 * mesh.vertices.size();
-        UPD_TRY(u.flag.reserve(1));
-        UPD_TRY(hipMemsetAsync(u.flag.p, 0, sizeof(uint32_t), stream));
+        if (const int rc = u.flag.ensure(1)) return rc;
+        HIP_TRY(hipMemsetAsync(u.flag.p, 0, sizeof(uint32_t), stream));
         hipLaunchKernelGGL(k_check_finite, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, u.verts.p, n, u.flag.p);
     }
     TriArgs ta;
@@ -495,50 +499,48 @@ static int refit(hipStream_t stream, MeshUpdater& u, const HostMesh& mesh, const
         ra.n = u.begin[l + 1] - u.begin[l];
         if (ra.n > 0) hipLaunchKernelGGL(k_refit_nodes, dim3((ra.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, ra);
     }
-    UPD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     float4 root[2];
     uint32_t flag = 0;
-    UPD_TRY(hipMemcpyAsync(root, u.bounds.p, sizeof(root), hipMemcpyDeviceToHost, stream));
-    if (finite) UPD_TRY(hipMemcpyAsync(&flag, u.flag.p, sizeof(flag), hipMemcpyDeviceToHost, stream));
-    UPD_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(root, u.bounds.p, sizeof(root), hipMemcpyDeviceToHost, stream));
+    if (finite) HIP_TRY(hipMemcpyAsync(&flag, u.flag.p, sizeof(flag), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     if (finite) *finite = flag == 0;
     root6[0] = root[0].x; root6[1] = root[0].y; root6[2] = root[0].z;
     root6[3] = root[1].x; root6[4] = root[1].y; root6[5] = root[1].z;
     return AGPT_OK;
 }
 
-int update_mesh_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices, const float* normals,
-                       const UpdateTarget& tg, float root6[6]) {
-    if (const int rc = ensure(stream, cache, mesh)) return rc;
-    MeshUpdater& u = **cache;
-    UPD_TRY(u.verts.upload(vertices, 3 * mesh.vertices.size(), stream));
-    if (!mesh.normals.empty()) UPD_TRY(u.normals.upload(normals, 3 * mesh.normals.size(), stream));
-    return refit(stream, u, mesh, tg, root6, nullptr);
+int MeshUpdate::update(hipStream_t stream, const HostMesh& mesh, const float* vertices, const float* normals, const UpdateTarget& tg,
+                       float root6[6]) {
+    if (const int rc = ensure_cache(stream, mesh)) return rc;
+    if (const int rc = upload(dev_->verts, vertices, 3 * mesh.vertices.size(), stream)) return rc;
+    if (!mesh.normals.empty())
+        if (const int rc = upload(dev_->normals, normals, 3 * mesh.normals.size(), stream)) return rc;
+    return refit(stream, mesh, tg, root6, nullptr);
 }
 
-int copy_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices_dev, const float* normals_dev) {
-    if (const int rc = ensure(stream, cache, mesh)) return rc;
-    MeshUpdater& u = **cache;
+int MeshUpdate::copy_arrays(hipStream_t stream, const HostMesh& mesh, const float* vertices_dev, const float* normals_dev) {
+    if (const int rc = ensure_cache(stream, mesh)) return rc;
+    MeshDeviceCache& u = *dev_;
     const size_t nv = 3 * mesh.vertices.size(), nn = 3 * mesh.normals.size();
-    UPD_TRY(u.verts.reserve(nv));
-    UPD_TRY(hipMemcpyAsync(u.verts.p, vertices_dev, nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if (const int rc = u.verts.ensure(nv)) return rc;
+    HIP_TRY(hipMemcpyAsync(u.verts.p, vertices_dev, nv * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (nn) {
-        UPD_TRY(u.normals.reserve(nn));
-        if (normals_dev) UPD_TRY(hipMemcpyAsync(u.normals.p, normals_dev, nn * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (const int rc = u.normals.ensure(nn)) return rc;
+        if (normals_dev) HIP_TRY(hipMemcpyAsync(u.normals.p, normals_dev, nn * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
     return AGPT_OK;
 }
 
-int upload_positions_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const float* vertices) {
-    if (const int rc = ensure(stream, cache, mesh)) return rc;
-    MeshUpdater& u = **cache;
-    UPD_TRY(u.verts.upload(vertices, 3 * mesh.vertices.size(), stream));   // (the caller keeps `vertices` until the stream is synchronised)
-    UPD_TRY(u.normals.reserve(3 * mesh.normals.size()));
-    return AGPT_OK;
+int MeshUpdate::upload_positions(hipStream_t stream, const HostMesh& mesh, const float* vertices) {
+    if (const int rc = ensure_cache(stream, mesh)) return rc;
+    if (const int rc = upload(dev_->verts, vertices, 3 * mesh.vertices.size(), stream)) return rc;
+    return dev_->normals.ensure(3 * mesh.normals.size());
 }
 
-int smooth_normals_device(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh) {
-    MeshUpdater& u = *cache;
+int MeshUpdate::smooth_normals(hipStream_t stream, const HostMesh& mesh) {
+    MeshDeviceCache& u = *dev_;
     const size_t nn = mesh.normals.size(), n_corners = mesh.indices.size() / 3, n_tris = n_corners / 3;
     // what the kernels index with, against what they index (the indices were checked by agpt_scene_add_mesh)
     if (nn == 0 || n_tris == 0 || n_tris != mesh.prim_index.size() || n_corners > (size_t)INT32_MAX || !u.verts.p || !u.normals.p)
@@ -546,62 +548,52 @@ int smooth_normals_device(hipStream_t stream, MeshUpdater* cache, const HostMesh
     if (!u.has_adjacency) {
         std::vector<int32_t> offsets, corner_tri;
         normal_adjacency(mesh.indices.data(), n_corners, nn, offsets, corner_tri);
-        UPD_TRY(u.normal_offsets.upload(offsets.data(), offsets.size(), stream));
-        UPD_TRY(u.normal_corner_tri.upload(corner_tri.data(), corner_tri.size(), stream));
-        UPD_TRY(u.face_normals.reserve(n_tris));
-        UPD_TRY(hipStreamSynchronize(stream));   // the staging vectors go out of scope
+        if (const int rc = upload(u.normal_offsets, offsets, stream)) return rc;
+        if (const int rc = upload(u.normal_corner_tri, corner_tri, stream)) return rc;
+        if (const int rc = u.face_normals.ensure(n_tris)) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));   // the staging vectors go out of scope
         u.has_adjacency = true;
     }
     hipLaunchKernelGGL(k_face_normals, dim3((unsigned)((n_tris + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, u.verts.p, u.indices.p,
                        u.face_normals.p, (int)n_tris);
     hipLaunchKernelGGL(k_vertex_normals, dim3((unsigned)((nn + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, u.normal_offsets.p,
                        u.normal_corner_tri.p, u.face_normals.p, u.normals.p, (int)nn);
-    UPD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return AGPT_OK;
 }
 
-// the cache, the rest pose on the device (uploaded when the cache holds none) and room for the posed arrays: what the transform and the
-// pose share (`fn` names the call in the message)
-static int ensure_rest(const char* fn, hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                       const std::vector<v3>& rest_normals) {
-    if (const int rc = ensure(stream, cache, mesh)) return rc;
-    MeshUpdater& u = **cache;
+// the cache, the rest pose on the device (uploaded when the cache holds none) and room for the deformed arrays
+int MeshUpdate::ensure_rest(const char* fn, hipStream_t stream, const HostMesh& mesh) {
+    if (const int rc = ensure_cache(stream, mesh)) return rc;
+    MeshDeviceCache& u = *dev_;
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size();
-    if (rest_vertices.size() != nv || rest_normals.size() != nn)
+    if (rest_vertices_.size() != nv || rest_normals_.size() != nn)
         return fail(AGPT_ERR_INVALID, std::string(fn) + ": the rest pose does not have the mesh's counts");
     if (!u.has_rest) {
-        UPD_TRY(u.rest_verts.upload(&rest_vertices.data()->x, 3 * nv, stream));
-        if (nn) UPD_TRY(u.rest_normals.upload(&rest_normals.data()->x, 3 * nn, stream));
-        UPD_TRY(hipStreamSynchronize(stream));   // (the caller's vectors may change behind this call)
+        if (const int rc = upload(u.rest_verts, &rest_vertices_.data()->x, 3 * nv, stream)) return rc;
+        if (nn)
+            if (const int rc = upload(u.rest_normals, &rest_normals_.data()->x, 3 * nn, stream)) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));   // (the rest vectors may change behind this call)
         u.has_rest = true;
     }
-    UPD_TRY(u.verts.reserve(3 * nv));
-    if (nn) UPD_TRY(u.normals.reserve(3 * nn));
-    return AGPT_OK;
+    if (const int rc = u.verts.ensure(3 * nv)) return rc;
+    return nn ? u.normals.ensure(3 * nn) : AGPT_OK;
 }
 
-int transform_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                            const std::vector<v3>& rest_normals, const Mat4& M, const Mat4& N, bool with_normals) {
-    if (const int rc = ensure_rest("agpt_scene_transform_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
-    MeshUpdater& u = **cache;
+// the arrays of the rest pose and of the result (ensure_rest has made them): the six fields the three argument records share
+template <class Args>
+static void rest_args(const MeshDeviceCache& u, const HostMesh& mesh, bool with_normals, Args& a) {
     const size_t nv = mesh.vertices.size(), nn = with_normals ? mesh.normals.size() : 0;
-    TransformArgs a;
-    a.M = M;
-    a.N = N;
     a.rest_verts = u.rest_verts.p;
     a.rest_normals = nn ? u.rest_normals.p : nullptr;
     a.verts = u.verts.p;
     a.normals = nn ? u.normals.p : nullptr;
     a.n_vertices = (int)nv;
     a.n_normals = (int)nn;
-    hipLaunchKernelGGL(k_transform_mesh, dim3((unsigned)((nv + nn + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
-    UPD_TRY(hipGetLastError());
-    return AGPT_OK;
 }
 
-// the binding on the device (uploaded when the cache holds none), this call's palette, and k_skin_mesh's arguments: what the pose and the
-// fused morph share (`fn` names the call in the message)
-static int skin_on_device(const char* fn, hipStream_t stream, MeshUpdater& u, const HostMesh& mesh, const SkinBinding& skin,
+// the binding on the device (uploaded when the cache holds none), this call's palette, and the skin's share of the kernel arguments
+static int skin_on_device(const char* fn, hipStream_t stream, MeshDeviceCache& u, const HostMesh& mesh, const SkinBinding& skin,
                           const std::vector<float>& palette, bool with_normals, SkinArgs& a) {
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), K = (size_t)skin.influences;
     const int stride = skin_palette_stride(nn != 0 && with_normals);   // (without: M only, as for a mesh that has no normals)
@@ -612,17 +604,18 @@ static int skin_on_device(const char* fn, hipStream_t stream, MeshUpdater& u, co
         palette.size() != (size_t)skin.n_joints * (size_t)stride)
         return fail(AGPT_ERR_INVALID, std::string(fn) + ": the binding does not have the mesh's counts");
     if (!u.has_skin) {
-        UPD_TRY(u.skin_vertex_joints.upload(skin.vertex_joints.data(), nv * K, stream));
-        UPD_TRY(u.skin_vertex_weights.upload(skin.vertex_weights.data(), nv * K, stream));
+        if (const int rc = upload(u.skin_vertex_joints, skin.vertex_joints, stream)) return rc;
+        if (const int rc = upload(u.skin_vertex_weights, skin.vertex_weights, stream)) return rc;
         if (own_normal_slots) {
-            UPD_TRY(u.skin_normal_joints.upload(skin.normal_joints.data(), nn * K, stream));
-            UPD_TRY(u.skin_normal_weights.upload(skin.normal_weights.data(), nn * K, stream));
+            if (const int rc = upload(u.skin_normal_joints, skin.normal_joints, stream)) return rc;
+            if (const int rc = upload(u.skin_normal_weights, skin.normal_weights, stream)) return rc;
         }
-        UPD_TRY(hipStreamSynchronize(stream));   // (the binding may be replaced behind this call)
+        HIP_TRY(hipStreamSynchronize(stream));   // (the binding may be replaced behind this call)
         u.has_skin = true;
     }
-    UPD_TRY(u.skin_palette.reserve((size_t)skin.n_joints * (size_t)skin_palette_stride(true)));   // (room for either stride)
-    UPD_TRY(u.skin_palette.upload(palette.data(), palette.size(), stream));   // (the caller keeps `palette` until the stream is synchronised)
+    // room for either stride (ensure only grows: the narrow palette of a later call lands in the same allocation)
+    if (const int rc = u.skin_palette.ensure((size_t)skin.n_joints * (size_t)skin_palette_stride(true))) return rc;
+    if (const int rc = upload(u.skin_palette, palette, stream)) return rc;
     a.palette = u.skin_palette.p;
     a.stride = stride;
     a.n_joints = skin.n_joints;
@@ -634,125 +627,98 @@ static int skin_on_device(const char* fn, hipStream_t stream, MeshUpdater& u, co
     return AGPT_OK;
 }
 
-// the arrays of the rest pose and of the result (ensure_rest has made them)
-static void rest_args(const MeshUpdater& u, const HostMesh& mesh, bool with_normals, SkinArgs& a) {
-    const size_t nv = mesh.vertices.size(), nn = with_normals ? mesh.normals.size() : 0;
-    a.rest_verts = u.rest_verts.p;
-    a.rest_normals = nn ? u.rest_normals.p : nullptr;
-    a.verts = u.verts.p;
-    a.normals = nn ? u.normals.p : nullptr;
-    a.n_vertices = (int)nv;
-    a.n_normals = (int)nn;
-}
-
-int skin_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                       const std::vector<v3>& rest_normals, const SkinBinding& skin, const std::vector<float>& palette, int num_cus,
-                       bool with_normals) {
-    if (const int rc = ensure_rest("agpt_scene_pose_mesh", stream, cache, mesh, rest_vertices, rest_normals)) return rc;
-    MeshUpdater& u = **cache;
-    SkinArgs a;
-    if (const int rc = skin_on_device("agpt_scene_pose_mesh", stream, u, mesh, skin, palette, with_normals, a)) return rc;
-    rest_args(u, mesh, with_normals, a);
-    const size_t lds = palette.size() * sizeof(float), blocks = ((size_t)a.n_vertices + (size_t)a.n_normals + kSkinBlock - 1) / kSkinBlock;
-    const size_t cus = (size_t)(num_cus > 0 ? num_cus : 1);
-    if (lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE")) {
-        hipLaunchKernelGGL(k_skin_mesh<true>, dim3((unsigned)std::min(blocks, cus * kSkinBlocksPerCU)), dim3(kSkinBlock), lds, stream, a);
-    } else {
-        hipLaunchKernelGGL(k_skin_mesh<false>, dim3((unsigned)std::min(blocks, cus * kSkinBlocksPerCU)), dim3(kSkinBlock), 0, stream, a);
-    }
-    UPD_TRY(hipGetLastError());
-    return AGPT_OK;
-}
-
-int morph_arrays_device(hipStream_t stream, MeshUpdater** cache, const HostMesh& mesh, const std::vector<v3>& rest_vertices,
-                        const std::vector<v3>& rest_normals, const MorphTargets& morph, const std::vector<MorphActive>& active,
-                        const SkinBinding* skin, const std::vector<float>* palette, int num_cus, bool with_normals) {
-    const char* fn = "agpt_scene_morph_mesh";
-    if (const int rc = ensure_rest(fn, stream, cache, mesh, rest_vertices, rest_normals)) return rc;
-    MeshUpdater& u = **cache;
+// the targets' deltas on the device (uploaded when the cache holds none), this call's active list, and the morph's share of the arguments
+static int morph_on_device(const char* fn, hipStream_t stream, MeshDeviceCache& u, const HostMesh& mesh, const MorphTargets& morph,
+                           const std::vector<MorphActive>& active, MorphArgs& m) {
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), T = (size_t)morph.n_targets;
     const bool normal_deltas = nn && !morph.normal_deltas.empty();
     // what the kernel indexes with, against what it indexes
     if (T < 1 || T > (size_t)kMorphMaxTargets || morph.position_deltas.size() != T * nv * 3 ||
-        (normal_deltas && morph.normal_deltas.size() != T * nn * 3) || active.size() > T || !skin != !palette)
+        (normal_deltas && morph.normal_deltas.size() != T * nn * 3) || active.size() > T)
         return fail(AGPT_ERR_INVALID, std::string(fn) + ": the targets do not have the mesh's counts");
     for (const MorphActive& t : active)
         if (t.target < 0 || (size_t)t.target >= T) return fail(AGPT_ERR_INVALID, std::string(fn) + ": an active target outside the targets");
     if (!u.has_morph) {
-        UPD_TRY(u.morph_position_deltas.upload(morph.position_deltas.data(), T * nv * 3, stream));
-        if (normal_deltas) UPD_TRY(u.morph_normal_deltas.upload(morph.normal_deltas.data(), T * nn * 3, stream));
-        UPD_TRY(hipStreamSynchronize(stream));   // (the targets may be replaced behind this call)
+        if (const int rc = upload(u.morph_position_deltas, morph.position_deltas, stream)) return rc;
+        if (normal_deltas)
+            if (const int rc = upload(u.morph_normal_deltas, morph.normal_deltas, stream)) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));   // (the targets may be replaced behind this call)
         u.has_morph = true;
     }
-    UPD_TRY(u.morph_active.reserve(T));   // (room for every target: the list of a later frame may be longer)
-    if (!active.empty())   // (the caller keeps `active` until the stream is synchronised)
-        UPD_TRY(hipMemcpyAsync(u.morph_active.p, active.data(), active.size() * sizeof(MorphActive), hipMemcpyHostToDevice, stream));
-    MorphArgs m;
+    if (const int rc = u.morph_active.ensure(T)) return rc;   // (room for every target: the list of a later frame may be longer)
+    if (const int rc = upload(u.morph_active, active, stream)) return rc;
     m.position_deltas = u.morph_position_deltas.p;
     m.normal_deltas = normal_deltas ? u.morph_normal_deltas.p : nullptr;
-    m.s = SkinArgs();
-    if (skin)
-        if (const int rc = skin_on_device(fn, stream, u, mesh, *skin, *palette, with_normals, m.s)) return rc;
-    rest_args(u, mesh, with_normals, m.s);
-    const size_t cus = (size_t)(num_cus > 0 ? num_cus : 1);
-    size_t blocks = std::min(((size_t)m.s.n_vertices + (size_t)m.s.n_normals + kSkinBlock - 1) / kSkinBlock, cus * (skin ? kSkinBlocksPerCU : kMorphBlocksPerCU));
-    if (const char* cap = getenv("AGPT_MORPH_MAX_BLOCKS")) {
-        const long c = std::strtol(cap, nullptr, 10);
-        if (c >= 1) blocks = std::min(blocks, (size_t)c);
+    return AGPT_OK;
+}
+
+// The one launcher of the three deforming kernels.  A pose is a morph without targets as far as the host is concerned: the same rest
+// arrays, uploads and grid, k_skin_mesh in place of k_morph_mesh.
+int MeshUpdate::deform(hipStream_t stream, const HostMesh& mesh, const DeformRequest& rq) {
+    if (const int rc = ensure_rest(rq.fn, stream, mesh)) return rc;
+    MeshDeviceCache& u = *dev_;
+    if (rq.M) {
+        TransformArgs a;
+        a.M = *rq.M;
+        a.N = *rq.N;
+        rest_args(u, mesh, rq.with_normals, a);
+        const size_t items = (size_t)a.n_vertices + (size_t)a.n_normals;
+        hipLaunchKernelGGL(k_transform_mesh, dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+        return AGPT_OK;
     }
-    const dim3 grid((unsigned)std::max(blocks, (size_t)1)), block(kSkinBlock);
-    const int n_active = (int)active.size();
-    const size_t lds = skin ? palette->size() * sizeof(float) : 0;
-    if (!skin) {
+    const bool morph = rq.active != nullptr, skin = rq.palette != nullptr;
+    if (!morph && !skin) return fail(AGPT_ERR_INVALID, std::string(rq.fn) + ": neither a matrix, a palette nor an active list");
+    MorphArgs m;
+    m.position_deltas = m.normal_deltas = nullptr;
+    m.s = SkinArgs();
+    if (morph)
+        if (const int rc = morph_on_device(rq.fn, stream, u, mesh, morph_, *rq.active, m)) return rc;
+    if (skin)
+        if (const int rc = skin_on_device(rq.fn, stream, u, mesh, skin_, *rq.palette, rq.with_normals, m.s)) return rc;
+    rest_args(u, mesh, rq.with_normals, m.s);
+    // 256-lane blocks on a capped grid: 4 per CU with a skin (its LDS cap), 8 for the morph alone
+    const size_t cus = (size_t)(rq.num_cus > 0 ? rq.num_cus : 1);
+    size_t blocks = std::min(((size_t)m.s.n_vertices + (size_t)m.s.n_normals + kSkinBlock - 1) / kSkinBlock, cus * (skin ? kSkinBlocksPerCU : kMorphBlocksPerCU));
+    if (morph) {   // AGPT_MORPH_MAX_BLOCKS is k_morph_mesh's alone
+        if (const char* cap = getenv("AGPT_MORPH_MAX_BLOCKS")) {
+            const long c = std::strtol(cap, nullptr, 10);
+            if (c >= 1) blocks = std::min(blocks, (size_t)c);
+        }
+        blocks = std::max(blocks, (size_t)1);
+    }
+    const dim3 grid((unsigned)blocks), block(kSkinBlock);
+    const size_t lds = skin ? rq.palette->size() * sizeof(float) : 0;
+    const bool staged = skin && lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE");
+    const int n_active = morph ? (int)rq.active->size() : 0;
+    if (!morph) {
+        if (staged) hipLaunchKernelGGL(k_skin_mesh<true>, grid, block, lds, stream, m.s);
+        else hipLaunchKernelGGL(k_skin_mesh<false>, grid, block, 0, stream, m.s);
+    } else if (!skin) {
         hipLaunchKernelGGL((k_morph_mesh<false, false>), grid, block, 0, stream, u.morph_active.p, n_active, m);
-    } else if (lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE")) {
+    } else if (staged) {
         hipLaunchKernelGGL((k_morph_mesh<true, true>), grid, block, lds, stream, u.morph_active.p, n_active, m);
     } else {
         hipLaunchKernelGGL((k_morph_mesh<true, false>), grid, block, 0, stream, u.morph_active.p, n_active, m);
     }
-    UPD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return AGPT_OK;
 }
 
-void drop_skin(MeshUpdater* cache) {
-    if (!cache) return;
-    cache->skin_vertex_joints.release();
-    cache->skin_vertex_weights.release();
-    cache->skin_normal_joints.release();
-    cache->skin_normal_weights.release();
-    cache->skin_palette.release();
-    cache->has_skin = false;
-}
-
-void drop_morph(MeshUpdater* cache) {
-    if (!cache) return;
-    cache->morph_position_deltas.release();
-    cache->morph_normal_deltas.release();
-    cache->morph_active.release();
-    cache->has_morph = false;
-}
-
-int refit_device_arrays(hipStream_t stream, MeshUpdater* cache, const HostMesh& mesh, const UpdateTarget& tg, float root6[6], bool* finite) {
-    return refit(stream, *cache, mesh, tg, root6, finite);
-}
-
-void drop_rest(MeshUpdater* cache) {
-    if (cache) cache->has_rest = false;
-}
-
-int download_arrays(hipStream_t stream, const MeshUpdater* u, std::vector<v3>& vertices, std::vector<v3>& normals) {
+int MeshUpdate::download_arrays(hipStream_t stream, std::vector<v3>& vertices, std::vector<v3>& normals) const {
     static_assert(sizeof(v3) == 3 * sizeof(float), "v3 is three packed floats");
-    if (!vertices.empty()) UPD_TRY(hipMemcpyAsync(vertices.data(), u->verts.p, vertices.size() * sizeof(v3), hipMemcpyDeviceToHost, stream));
-    if (!normals.empty()) UPD_TRY(hipMemcpyAsync(normals.data(), u->normals.p, normals.size() * sizeof(v3), hipMemcpyDeviceToHost, stream));
-    UPD_TRY(hipStreamSynchronize(stream));
+    if (!vertices.empty()) HIP_TRY(hipMemcpyAsync(vertices.data(), dev_->verts.p, vertices.size() * sizeof(v3), hipMemcpyDeviceToHost, stream));
+    if (!normals.empty()) HIP_TRY(hipMemcpyAsync(normals.data(), dev_->normals.p, normals.size() * sizeof(v3), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return AGPT_OK;
 }
 
-int download_bounds(hipStream_t stream, const MeshUpdater* u, HostMesh& mesh) {
-    std::vector<float4> b(2 * ((size_t)u->total_nodes + 1));
-    UPD_TRY(hipMemcpyAsync(b.data(), u->bounds.p, b.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
-    UPD_TRY(hipStreamSynchronize(stream));
-    for (int i = 0; i <= u->total_nodes; i++) {
+int MeshUpdate::download_bounds(hipStream_t stream, HostMesh& mesh) const {
+    const int total = dev_->total_nodes;
+    std::vector<float4> b(2 * ((size_t)total + 1));
+    HIP_TRY(hipMemcpyAsync(b.data(), dev_->bounds.p, b.size() * sizeof(float4), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (int i = 0; i <= total; i++) {
         if (i == 1) continue;
         agpt_bvh_node& nd = mesh.nodes[i];
         nd.bmin[0] = b[2 * (size_t)i].x; nd.bmin[1] = b[2 * (size_t)i].y; nd.bmin[2] = b[2 * (size_t)i].z;

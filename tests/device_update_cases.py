@@ -1,10 +1,14 @@
-"""The meshes, scenes and comparisons of the device-pointer and transform update tests (test_gpu_mesh_update_device.py,
-test_gpu_transform_mesh.py): the smallest meshes at which the update kernels can still go wrong, all in ONE scene, and the snapshot
-of a scene that two update paths must leave bit-identical."""
+"""The meshes, scenes and comparisons of the mesh-update tests on the GPU (test_gpu_mesh_update_device.py, test_gpu_transform_mesh.py,
+test_gpu_pose_mesh.py, test_gpu_morph_mesh.py, test_gpu_smooth_normals.py, test_gpu_streams.py): the smallest meshes at which the
+update kernels can still go wrong, all in ONE scene, the snapshot of a scene that two update paths must leave bit-identical, and the
+matrices, bindings and targets that more than one of those files gives a mesh."""
 import numpy as np
 
 import ag_pathtracer_amd as ag
-from helpers import random_rays
+from helpers import gpu_context, random_rays
+from morph_cases import targets
+from skin_cases import JOINTS3, binding, flat_shaded
+from transform_cases import MATRICES
 
 F = np.float32
 W = H = 32
@@ -157,3 +161,121 @@ def update_through_device(g, prim, v, n, mode="refit"):
         g.ctx.memset(d.pv, 0xFF, d.v.nbytes)
     finally:
         d.free()
+
+
+def pair(builder="host", desc=None):
+    """(description, scene A, scene B): two identical scenes of the zoo (or of desc) on the GPU"""
+    desc = desc or zoo_scene()
+    scenes = []
+    for _ in range(2):
+        g = ag.Scene(gpu_context())
+        g.set_bvh_builder(builder)
+        scenes.append(desc.instantiate(g))
+    return desc, scenes[0], scenes[1]
+
+
+def seventy_prims():
+    d = ag.SceneDesc("device-update-70")
+    mats = [d.add_material(ag.MAT_DIFFUSE_ONLY, c) for c in ([.8, .3, .2], [.2, .7, .3], [.3, .4, .8])]
+    for k in range(70):
+        c = (1.4 * (k % 10) - 6.3, 0.9 * ((k // 10) % 7) - 2.0, 1.1 * (k % 3))
+        d.add_mesh(*ag.scenes.blob_mesh(5, 4, center=c, radius=0.45, seed=k), mats[k % 3], 1)
+    d.add_area_light([0.0, 8.0, -4.0], 0.8, [70, 65, 60])
+    d.add_uniform_infinite_light([.25, .3, .35])
+    d.set_camera([0, 1, -16], [0, 0.5, 0], [0, 1, 0], 1.0, 50.0, 0.0)
+    return d
+
+
+def about(prim, M):
+    """M applied about the mesh's place in the zoo (so that it stays in view): T(c) M T(-c), in float32 as given to both paths"""
+    c = np.array(ZOO[prim - 1][4], np.float64)
+    t0, t1 = np.eye(4), np.eye(4)
+    t0[:3, 3], t1[:3, 3] = -c, c
+    return (t1 @ M.astype(np.float64) @ t0).astype(F)
+
+
+def frame_hash(rgb_words):
+    """the FNV-1a hash the C++ examples print for a frame"""
+    h = np.uint64(1469598103934665603)
+    with np.errstate(over="ignore"):
+        for w in np.asarray(rgb_words, np.uint32).reshape(-1):
+            h = (h ^ np.uint64(w)) * np.uint64(1099511628211)
+    return int(h)
+
+
+def palette(prim, pose):
+    """three joints about the mesh's place in the zoo; the two poses move every joint differently"""
+    return np.stack([about(prim, JOINTS3[i]) for i in ((0, 1, 2), (1, 2, 0))[pose]])
+
+
+BIG, FLAT = 10, 11         # the two meshes big_scene() adds to the zoo (prim 9 is the light)
+BIG_N = 33                 # 33 x 33 = 1,089 vertices and as many normals: 2,178 items, 8.5 blocks of 256
+
+
+def big_grid():
+    x, z = np.meshgrid(np.linspace(-1, 1, BIG_N), np.linspace(-1, 1, BIG_N), indexing="ij")
+    y = 0.2 * np.sin(2.7 * x + 0.3) * np.cos(3.1 * z)
+    v = (np.stack([x, y + 0.5, z], -1).reshape(-1, 3) + [3.4, 0.0, -0.6]).astype(F)
+    tris = []
+    for i in range(BIG_N - 1):
+        for j in range(BIG_N - 1):
+            a, b, c, d = i * BIG_N + j, i * BIG_N + j + 1, (i + 1) * BIG_N + j, (i + 1) * BIG_N + j + 1
+            tris += [(a, b, c), (b, d, c)]
+    return v, _normals(v, 9), _corners(tris, True)
+
+
+def flat_grid():
+    """bumpy_grid with one normal per triangle: 170 vertices, 288 normals"""
+    v, _, ix = bumpy_grid(False)
+    v = (v + np.array([-3.4, 0.0, -0.6], F)).astype(F)
+    n = flat_shaded(v, ix[:, 0])
+    corners = ix.copy()
+    corners[:, 1] = np.repeat(np.arange(len(n), dtype=np.int32), 3)
+    return v, n, corners
+
+
+def big_scene():
+    d = zoo_scene()
+    d.name = "morph-zoo"
+    for k, (v, n, ix) in enumerate((big_grid(), flat_grid())):
+        d.add_mesh(v, n, None, ix, k, 4)
+    return d
+
+
+def arrays_of(prim):
+    if prim == BIG:
+        return big_grid()[:2]
+    if prim == FLAT:
+        return flat_grid()[:2]
+    return zoo_arrays(prim)
+
+
+def morph_targets(g, prim, T=3, seed=None, normal_deltas=True):
+    """seeded targets of mesh prim, set on scene g (if any) -> (dP, dN or None)"""
+    v, n = arrays_of(prim)
+    seed = 10 * prim + T if seed is None else seed
+    dP = targets(len(v), T, seed, extent=2.0)
+    dN = targets(len(n), T, seed + 1, extent=5.0) if n is not None and normal_deltas else None
+    if g is not None:
+        g.set_mesh_morph_targets(prim, dP, dN)
+    return dP, dN
+
+
+def skin_of(g, prim, n_joints=3):
+    v, n = arrays_of(prim)
+    J, W = binding(len(v), 4, seed=prim)
+    nJ, nW = binding(len(n), 4, seed=prim + 50) if n is not None and len(n) != len(v) else (None, None)
+    g.set_mesh_skin(prim, J, W, nJ, nW, n_joints=n_joints)
+    return J, W, nJ, nW
+
+
+def joints_of(prim, k):
+    """three joint matrices about the mesh's own place: the zoo's palette, or the same matrices about the centre of an added mesh"""
+    if prim in PRIMS:
+        return palette(prim, k)
+    v = arrays_of(prim)[0].astype(np.float64)
+    c = 0.5 * (v.min(0) + v.max(0))
+    t0, t1 = np.eye(4), np.eye(4)
+    t0[:3, 3], t1[:3, 3] = -c, c
+    order = ("rotation+translation", "scale+shear", "identity")
+    return np.stack([(t1 @ MATRICES[order[(i + k) % 3]].astype(np.float64) @ t0).astype(F) for i in range(3)])

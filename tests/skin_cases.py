@@ -1,7 +1,7 @@
 """Joints, bindings and meshes the skinning tests share (test_skin_arrays.py on the host, test_gpu_pose_mesh.py on the GPU)."""
 import numpy as np
 
-from test_transform_arrays import MATRICES
+from transform_cases import MATRICES
 
 F = np.float32
 # a rotation + translation, a scale + shear and the identity

@@ -12,21 +12,15 @@ import pytest
 
 import ag_pathtracer_amd as ag
 import device_update_cases as dc
+from device_update_cases import pair, seventy_prims
 from helpers import gpu_context, gpu_scene
+from morph_cases import weights
+from skin_cases import JOINTS3, binding
+from transform_cases import MATRICES
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def pair(builder="host", desc=None):
-    desc = desc or dc.zoo_scene()
-    scenes = []
-    for _ in range(2):
-        g = ag.Scene(gpu_context())
-        g.set_bvh_builder(builder)
-        scenes.append(desc.instantiate(g))
-    return desc, scenes[0], scenes[1]
 
 
 @pytest.mark.parametrize("mode,builder", [("refit", "host"), ("refit", "device"), ("rebuild", "host"), ("rebuild", "device")])
@@ -75,18 +69,6 @@ def test_a_stale_mirror_survives_the_rebuild_of_another_mesh():
         g.close()
 
 
-def seventy_prims():
-    d = ag.SceneDesc("device-update-70")
-    mats = [d.add_material(ag.MAT_DIFFUSE_ONLY, c) for c in ([.8, .3, .2], [.2, .7, .3], [.3, .4, .8])]
-    for k in range(70):
-        c = (1.4 * (k % 10) - 6.3, 0.9 * ((k // 10) % 7) - 2.0, 1.1 * (k % 3))
-        d.add_mesh(*ag.scenes.blob_mesh(5, 4, center=c, radius=0.45, seed=k), mats[k % 3], 1)
-    d.add_area_light([0.0, 8.0, -4.0], 0.8, [70, 65, 60])
-    d.add_uniform_infinite_light([.25, .3, .35])
-    d.set_camera([0, 1, -16], [0, 0.5, 0], [0, 1, 0], 1.0, 50.0, 0.0)
-    return d
-
-
 def test_a_seventy_primitive_scene_gets_its_top_level_tree_again():
     desc, a, b = pair(desc=seventy_prims())
     prim = 7
@@ -117,6 +99,77 @@ def test_a_non_finite_coordinate_takes_the_fallback(vertex):
     a.update_mesh(dc.GRID1, v, n, "refit")
     dc.update_through_device(b, dc.GRID1, v, n, "refit")
     dc.assert_same(dc.snapshot(a, desc, dc.PRIMS), dc.snapshot(b, desc, dc.PRIMS))
+    a.close()
+    b.close()
+
+
+def test_one_mesh_through_every_front_end_in_a_row():
+    """the 170-vertex grid with normals and the one without, each through transform, skin + pose, device arrays (the rest pose is
+    forgotten, the binding kept), pose, targets + fused morph, a REBUILD morph (the device cache goes), pose, -- the mesh with normals
+    only -- SMOOTH mode with a morph and a pose, new targets (T = 2) + morph, a new skin (K = 2, five joints) + pose, GIVEN mode again and
+    a host update with a NaN vertex (the fallback), and a transform: after every step scene B equals scene A, which received the host
+    twins' arrays through agpt_scene_update_mesh"""
+    desc, a, b = pair()
+    prims = (dc.GRID4_N, dc.GRID1)
+    rest = {p: dc.zoo_arrays(p) for p in prims}
+    corners = {p: dc.ZOO[p - 1][1](dc.ZOO[p - 1][2])[2] for p in prims}
+    smooth, skins, tg = set(), {}, {}
+    assert len(rest[dc.GRID4_N][0]) == 170 == len(rest[dc.GRID4_N][1]) and rest[dc.GRID1][1] is None
+    last = [dc.snapshot(b, desc, prims)]
+
+    def step(arrays, call, mode="refit", moves=True):
+        """arrays(p) -> the (V, N) the step stands for, call(p): the front end on scene B"""
+        for p in prims:
+            v, n = arrays(p)
+            if p in smooth:
+                n = ag.vertex_normals_arrays(v, corners[p], len(rest[p][1]))
+            a.update_mesh(p, v, n, mode)
+            call(p)
+        sa, sb = dc.snapshot(a, desc, prims), dc.snapshot(b, desc, prims)
+        dc.assert_same(sa, sb)
+        assert not moves or sb["render"] != last[0]["render"]
+        last[0] = sb
+
+    def posed(p, mats, v=None, n=None):
+        return ag.skin_arrays(mats, rest[p][0] if v is None else v, *skins[p][:2], rest[p][1] if n is None else n, *skins[p][2:])
+
+    def morphed(p, w):
+        return ag.morph_arrays(w, rest[p][0], tg[p][0], rest[p][1], tg[p][1])
+
+    M = {p: dc.about(p, MATRICES["rotation+translation"]) for p in prims}
+    step(lambda p: ag.transform_arrays(M[p], *rest[p]), lambda p: b.transform_mesh(p, M[p]))                          # 1
+    skins.update({p: dc.skin_of(b, p) for p in prims})
+    step(lambda p: posed(p, dc.palette(p, 0)), lambda p: b.pose_mesh(p, dc.palette(p, 0)))                            # 2
+    rest = {p: dc.zoo_arrays(p, 2) for p in prims}
+    step(lambda p: rest[p], lambda p: dc.update_through_device(b, p, *rest[p]))                                       # 3
+    step(lambda p: posed(p, dc.palette(p, 1)), lambda p: b.pose_mesh(p, dc.palette(p, 1)))                            # 4: the new rest pose
+    tg.update({p: dc.morph_targets(b, p, 3) for p in prims})
+    w3 = {p: weights(3, p, [0, 2]) for p in prims}
+    step(lambda p: posed(p, dc.palette(p, 0), *morphed(p, w3[p])), lambda p: b.morph_mesh(p, w3[p], dc.palette(p, 0)))   # 5: fused
+    w3 = {p: weights(3, p + 1, [0, 1, 2]) for p in prims}
+    step(lambda p: morphed(p, w3[p]), lambda p: b.morph_mesh(p, w3[p], mode="rebuild"), "rebuild")                    # 6
+    step(lambda p: posed(p, dc.palette(p, 1)), lambda p: b.pose_mesh(p, dc.palette(p, 1), "refit"))                   # 7
+    b.set_mesh_normals_mode(dc.GRID4_N, "smooth")                                                                     # 8
+    smooth.add(dc.GRID4_N)
+    step(lambda p: morphed(p, w3[p]), lambda p: b.morph_mesh(p, w3[p]))
+    step(lambda p: posed(p, dc.palette(p, 0)), lambda p: b.pose_mesh(p, dc.palette(p, 0)))
+    tg.update({p: dc.morph_targets(b, p, 2) for p in prims})                                                          # 9
+    w2 = {p: weights(2, p, [0, 1]) for p in prims}
+    step(lambda p: morphed(p, w2[p]), lambda p: b.morph_mesh(p, w2[p]))
+    for p in prims:                                                                                                   # 10
+        J, W = binding(len(rest[p][0]), 2, seed=p + 7, n_joints=5)
+        b.set_mesh_skin(p, J, W, n_joints=5)
+        skins[p] = (J, W, None, None)
+    five = {p: np.stack([dc.about(p, JOINTS3[i]) for i in (2, 0, 1, 0, 2)]) for p in prims}
+    step(lambda p: posed(p, five[p]), lambda p: b.pose_mesh(p, five[p]))
+    b.set_mesh_normals_mode(dc.GRID4_N, "given")                                                                      # 11
+    smooth.clear()
+    rest = {p: dc.zoo_arrays(p, 1) for p in prims}
+    for p in prims:
+        rest[p][0][dc.REFERENCED, 1] = np.nan
+    step(lambda p: rest[p], lambda p: b.update_mesh(p, *rest[p]))
+    M = {p: dc.about(p, MATRICES["scale+shear"]) for p in prims}
+    step(lambda p: ag.transform_arrays(M[p], *rest[p]), lambda p: b.transform_mesh(p, M[p]))                          # 12
     a.close()
     b.close()
 

@@ -12,96 +12,22 @@ import pytest
 import ag_pathtracer_amd as ag
 import device_update_cases as dc
 import morph_model
+from device_update_cases import (BIG, FLAT, about, arrays_of, big_scene, frame_hash, joints_of, morph_targets, pair, palette, seventy_prims,
+                                 skin_of)
 from helpers import build_cpp_example, gpu_context, gpu_scene
 from morph_cases import targets, weights
-from skin_cases import binding, flat_shaded
-from test_gpu_mesh_update_device import pair, seventy_prims
-from test_gpu_pose_mesh import palette
+from skin_cases import binding
 from test_gpu_streams import MOVED, Stage, assert_rays_through_updated_scene, twin_scene
-from test_gpu_transform_mesh import about, frame_hash
-from test_transform_arrays import MATRICES
+from transform_cases import MATRICES
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 EYE = np.eye(4, dtype=F)
-BIG, FLAT = 10, 11         # the two meshes big_scene() adds to the zoo (prim 9 is the light)
-BIG_N = 33                 # 33 x 33 = 1,089 vertices and as many normals: 2,178 items, 8.5 blocks of 256
-
-
-def big_grid():
-    x, z = np.meshgrid(np.linspace(-1, 1, BIG_N), np.linspace(-1, 1, BIG_N), indexing="ij")
-    y = 0.2 * np.sin(2.7 * x + 0.3) * np.cos(3.1 * z)
-    v = (np.stack([x, y + 0.5, z], -1).reshape(-1, 3) + [3.4, 0.0, -0.6]).astype(F)
-    tris = []
-    for i in range(BIG_N - 1):
-        for j in range(BIG_N - 1):
-            a, b, c, d = i * BIG_N + j, i * BIG_N + j + 1, (i + 1) * BIG_N + j, (i + 1) * BIG_N + j + 1
-            tris += [(a, b, c), (b, d, c)]
-    return v, dc._normals(v, 9), dc._corners(tris, True)
-
-
-def flat_grid():
-    """bumpy_grid with one normal per triangle: 170 vertices, 288 normals"""
-    v, _, ix = dc.bumpy_grid(False)
-    v = (v + np.array([-3.4, 0.0, -0.6], F)).astype(F)
-    n = flat_shaded(v, ix[:, 0])
-    corners = ix.copy()
-    corners[:, 1] = np.repeat(np.arange(len(n), dtype=np.int32), 3)
-    return v, n, corners
-
-
-def big_scene():
-    d = dc.zoo_scene()
-    d.name = "morph-zoo"
-    for k, (v, n, ix) in enumerate((big_grid(), flat_grid())):
-        d.add_mesh(v, n, None, ix, k, 4)
-    return d
-
-
-def arrays_of(prim):
-    if prim == BIG:
-        return big_grid()[:2]
-    if prim == FLAT:
-        return flat_grid()[:2]
-    return dc.zoo_arrays(prim)
-
-
-def morph_targets(g, prim, T=3, seed=None, normal_deltas=True):
-    """seeded targets of mesh prim, set on scene g (if any) -> (dP, dN or None)"""
-    v, n = arrays_of(prim)
-    seed = 10 * prim + T if seed is None else seed
-    dP = targets(len(v), T, seed, extent=2.0)
-    dN = targets(len(n), T, seed + 1, extent=5.0) if n is not None and normal_deltas else None
-    if g is not None:
-        g.set_mesh_morph_targets(prim, dP, dN)
-    return dP, dN
-
-
 def by_definition(g, prim, w, rest, dP, dN, mode="refit", mats=None, skin=None):
     v, n = ag.morph_arrays(w, rest[0], dP, rest[1], dN)
     if mats is not None:
         v, n = ag.skin_arrays(mats, v, *skin[:2], n, *skin[2:])
     g.update_mesh(prim, v, n, mode)
-
-
-def skin_of(g, prim, n_joints=3):
-    v, n = arrays_of(prim)
-    J, W = binding(len(v), 4, seed=prim)
-    nJ, nW = binding(len(n), 4, seed=prim + 50) if n is not None and len(n) != len(v) else (None, None)
-    g.set_mesh_skin(prim, J, W, nJ, nW, n_joints=n_joints)
-    return J, W, nJ, nW
-
-
-def joints_of(prim, k):
-    """three joint matrices about the mesh's own place: the zoo's palette, or the same matrices about the centre of an added mesh"""
-    if prim in dc.PRIMS:
-        return palette(prim, k)
-    v = arrays_of(prim)[0].astype(np.float64)
-    c = 0.5 * (v.min(0) + v.max(0))
-    t0, t1 = np.eye(4), np.eye(4)
-    t0[:3, 3], t1[:3, 3] = -c, c
-    order = ("rotation+translation", "scale+shear", "identity")
-    return np.stack([(t1 @ MATRICES[order[(i + k) % 3]].astype(np.float64) @ t0).astype(F) for i in range(3)])
 
 
 WEIGHT_SETS = ([0, 2], [0, 1, 2])      # the first leaves the all-zero target idle (its weight is -0.0), the second uses it

@@ -11,19 +11,13 @@ import pytest
 import ag_pathtracer_amd as ag
 import device_update_cases as dc
 import skin_model
+from device_update_cases import about, frame_hash, pair, palette, seventy_prims
 from helpers import build_cpp_example, gpu_context, gpu_scene
 from skin_cases import JOINTS3, binding, single_slot
-from test_gpu_mesh_update_device import pair, seventy_prims
-from test_gpu_transform_mesh import about, frame_hash
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 EYE = np.eye(4, dtype=F)
-
-
-def palette(prim, pose):
-    """three joints about the mesh's place in the zoo; the two poses move every joint differently"""
-    return np.stack([about(prim, JOINTS3[i]) for i in ((0, 1, 2), (1, 2, 0))[pose]])
 
 
 def bound(g, prim, K=4, seed=None):

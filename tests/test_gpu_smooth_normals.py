@@ -14,13 +14,11 @@ import pytest
 import ag_pathtracer_amd as ag
 import device_update_cases as dc
 import normals_cases as nc
+from device_update_cases import BIG, FLAT, about, arrays_of, big_scene, frame_hash, joints_of, morph_targets, pair, seventy_prims, skin_of
 from helpers import build_cpp_example, gpu_context, gpu_scene, oracle_render
 from morph_cases import weights
-from test_gpu_mesh_update_device import pair, seventy_prims
-from test_gpu_morph_mesh import BIG, FLAT, arrays_of, big_scene, joints_of, morph_targets, skin_of
 from test_gpu_streams import Stage, assert_rays_through_updated_scene, posed_zoo, twin_scene
-from test_gpu_transform_mesh import about, frame_hash
-from test_transform_arrays import MATRICES
+from transform_cases import MATRICES
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -33,11 +31,9 @@ MATS = ("rotation+translation", "scale+shear")
 
 def corners_of(prim):
     if prim == BIG:
-        from test_gpu_morph_mesh import big_grid
-        return big_grid()[2]
+        return dc.big_grid()[2]
     if prim == FLAT:
-        from test_gpu_morph_mesh import flat_grid
-        return flat_grid()[2]
+        return dc.flat_grid()[2]
     _, make, wn, _, _ = dc.ZOO[prim - 1]
     return make(wn)[2]
 

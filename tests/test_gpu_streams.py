@@ -31,15 +31,13 @@ import ray_edge_cases as rec
 import temporal_model as tm
 from ag_pathtracer_amd import tiles
 from denoise_features import host_features, primitive_table
+from device_update_cases import about, palette, seventy_prims
 from helpers import bits, compare_with_model, gpu_context, oracle_render, oracle_render_on, oracle_scene, random_rays, scene_c1
 from skin_cases import binding
 from test_gpu_coherent_trace import small_c3
 from test_gpu_denoise import check_features
 from test_gpu_intersect import deep_mesh_scene
-from test_gpu_mesh_update_device import seventy_prims
-from test_gpu_pose_mesh import palette
-from test_gpu_transform_mesh import about
-from test_transform_arrays import MATRICES
+from transform_cases import MATRICES
 
 pytestmark = pytest.mark.gpu
 F = np.float32

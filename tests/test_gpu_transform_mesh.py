@@ -9,22 +9,14 @@ import pytest
 
 import ag_pathtracer_amd as ag
 import device_update_cases as dc
+from device_update_cases import about, frame_hash, pair, seventy_prims
 from helpers import build_cpp_example, gpu_context, gpu_scene
-from test_gpu_mesh_update_device import pair
-from test_transform_arrays import MATRICES
+from transform_cases import MATRICES
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 # x and w exchanged: w = x, which is exactly 0 on the middle column of the grids -> Inf / NaN positions from finite input
 SWAP_XW = np.array([[0, 0, 0, 1], [0, 1, 0, 0], [0, 0, 1, 0], [1, 0, 0, 0]], F)
-
-
-def about(prim, M):
-    """M applied about the mesh's place in the zoo (so that it stays in view): T(c) M T(-c), in float32 as given to both paths"""
-    c = np.array(dc.ZOO[prim - 1][4], np.float64)
-    t0, t1 = np.eye(4), np.eye(4)
-    t0[:3, 3], t1[:3, 3] = -c, c
-    return (t1 @ M.astype(np.float64) @ t0).astype(F)
 
 
 def by_definition(g, prim, M, rest, mode):
@@ -86,7 +78,6 @@ def test_an_explicit_update_resets_the_rest_pose(through):
 
 
 def test_a_transform_in_a_seventy_primitive_scene_and_a_stale_mirror():
-    from test_gpu_mesh_update_device import seventy_prims
     desc, a, b = pair(desc=seventy_prims())
     prim = 7
     rest = desc.ops[3 + prim][1:3]
@@ -150,14 +141,6 @@ def test_refusals_change_nothing():
         g.transform_mesh(dc.GRID1_N, np.zeros((4, 4), F))
     dc.assert_same(dc.snapshot(g, desc, dc.PRIMS), before)
     g.close()
-
-
-def frame_hash(rgb_words):
-    h = np.uint64(1469598103934665603)
-    with np.errstate(over="ignore"):
-        for w in np.asarray(rgb_words, np.uint32).reshape(-1):
-            h = (h ^ np.uint64(w)) * np.uint64(1099511628211)
-    return int(h)
 
 
 def test_cpp_rigid_example_matches_python(tmp_path):

@@ -10,6 +10,7 @@ import pytest
 
 import ag_pathtracer_amd as ag
 from helpers import assert_exported
+from transform_cases import MATRICES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "agpt.h")).read()
@@ -28,24 +29,6 @@ def obj_text(with_normals, seed=4, n=37):
         a, b, c = 1, k + 1, k + 2
         lines.append(("f %d//%d %d//%d %d//%d" % (a, a, b, b, c, c)) if with_normals else "f %d %d %d" % (a, b, c))
     return "\n".join(lines) + "\n"
-
-
-def rotation_translation():
-    a, b = 0.7, -1.9
-    rz = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
-    rx = np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
-    m = np.eye(4)
-    m[:3, :3] = rz @ rx
-    m[:3, 3] = [1.25, -0.3, 7.1]
-    return m.astype(F)
-
-
-MATRICES = {
-    "rotation+translation": rotation_translation(),
-    "scale+shear": np.array([[2.5, 0.3, 0, 0], [0, 0.4, -0.7, 0], [0.1, 0, -1.75, 0], [0, 0, 0, 1]], F),
-    "projective": np.array([[1, 0.2, 0, 0.5], [0, 1.1, 0, 0], [0.3, 0, 0.9, -2], [0.01, -0.02, 0.03, 1.5]], F),   # w != 1
-    "identity": np.eye(4, dtype=F),
-}
 
 
 def test_symbols_declared_and_exported():

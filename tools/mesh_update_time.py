@@ -24,7 +24,8 @@ thread.
 --parent-lib TAG compares the host-pointer REFIT of this build with the build `libagpt_hip_TAG.so` of the parent commit
 (tools/build_variant.py run in a checkout of it, the file copied beside libagpt_hip.so): child processes, alternating parent / this
 for `--rounds` rounds on the same GPU, each timing `--runs` updates per mesh; the new median must lie within the parent's own min-max
-spread, and both sets of numbers go into the JSON."""
+spread, and both sets of numbers go into the JSON.  With --pose or --morph it compares every GPU row of that leg the same way (each
+child runs the whole leg) and writes only the comparison to --out."""
 import argparse
 import json
 import os
@@ -354,7 +355,17 @@ def host_refit_only(runs):
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def compare_with_parent(tag, runs, rounds):
+def leg_rows(result):
+    """the child of --parent-lib with --pose / --morph: the leg's GPU rows as {case/operation: stats}"""
+    out = {}
+    for case, c in result["cases"].items():
+        for op, r in c["operations"].items():
+            if "median_ms" in r:
+                out["%s/%s" % (case, op)] = {k: r[k] for k in ("median_ms", "min_ms", "max_ms")}
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def compare_with_parent(tag, runs, rounds, leg=()):
     sets = {"parent": [], "this": []}
     for _ in range(rounds):
         for which in ("parent", "this"):
@@ -362,8 +373,8 @@ def compare_with_parent(tag, runs, rounds):
             env.pop("AGPT_LIB_VARIANT", None)
             if which == "parent":
                 env["AGPT_LIB_VARIANT"] = tag
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--runs", str(runs)], env=env, capture_output=True, text=True,
-                               timeout=900, check=True)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--runs", str(runs)] + list(leg), env=env, capture_output=True,
+                               text=True, timeout=900, check=True)
             line = [x for x in r.stdout.splitlines() if x.startswith("RESULT ")][-1]
             sets[which].append(json.loads(line[7:]))
             print(which, line[7:], flush=True)
@@ -395,7 +406,17 @@ def main():
     if a.runs < 7:
         ap.error("--runs: at least 7")
     if a.child:
-        return host_refit_only(a.runs)
+        return leg_rows(morph_leg(a.runs) if a.morph else pose_leg(a.runs)) if a.pose or a.morph else host_refit_only(a.runs)
+    if a.parent_lib and (a.pose or a.morph):
+        result = compare_with_parent(a.parent_lib, a.runs, a.rounds, ["--morph" if a.morph else "--pose"])
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+        slower = [k for k, r in result.items() if isinstance(r, dict) and not r["this_median_not_above_parent_max"]]
+        if slower:
+            sys.exit("slower than the parent's spread on: %s" % ", ".join(slower))
+        return
     if a.pose or a.morph or a.normals:
         result = normals_leg(a.runs) if a.normals else morph_leg(a.runs) if a.morph else pose_leg(a.runs)
         default = "mesh_normals_times.json" if a.normals else "mesh_morph_times.json" if a.morph else "mesh_pose_times.json"
