@@ -569,6 +569,8 @@ int agpt_render(agpt_scene*, const agpt_render_params*, float* accum_dev, agpt_s
  * accum.rgb; n = accum.w) is ACTIVE when n < max_spp and either n < min_spp or the stop test fails:
  *     mu = luminance(accum.rgb) / n,  var = max(0, moment2 / n - mu*mu) * n / (n - 1)
  *     stop <=> sqrt(var / n) <= rel_error * max(mu, abs_floor)          (rel_error <= 0: never -- every pixel to max_spp)
+ * The test is fp32, every operation rounded on its own, the divisions and the square root IEEE; every max(a, b) is fmaxf: a NaN
+ * operand yields the other one, so a NaN moment2 is a variance of 0 (the pixel stops), as in agpt_denoise below.
  * An active pixel takes samples [n, n + step_spp) in sample order: accum.rgb += clr exactly as agpt_render, moment2 += Y*Y
  * (Y = luminance(clr) after the NaN / inf reject, fp32), accum.w = n + step_spp.  Rounds repeat until no pixel is active.  The
  * decision reads only the pixel's own buffers, so the result is independent of batching, tiles, rank shares and how calls are

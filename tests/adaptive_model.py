@@ -20,13 +20,14 @@ def reject(clr):
 
 
 def test_value(S, M, n, rel_error, abs_floor):
-    """(lhs, rhs) of the stop test sqrt(var / n) <= rel_error * max(mu, abs_floor), in float32, for n >= 2."""
+    """(lhs, rhs) of the stop test sqrt(var / n) <= rel_error * max(mu, abs_floor), in float32, for n >= 2.  Every max is fmaxf
+    (include/agpt.h): a NaN operand yields the other one, so a NaN moment2 is a variance of 0."""
     nf = np.asarray(n, F)
-    with np.errstate(invalid="ignore", divide="ignore"):
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
         mu = luminance(S) / nf
-        var = np.maximum(F(0), M / nf - mu * mu) * nf / (nf - F(1))
+        var = np.fmax(F(0), np.asarray(M, F) / nf - mu * mu) * nf / (nf - F(1))
         lhs = np.sqrt(var / nf)
-    rhs = F(rel_error) * np.maximum(mu, F(abs_floor))
+        rhs = F(rel_error) * np.fmax(mu, F(abs_floor))
     return lhs, rhs
 
 
@@ -39,7 +40,8 @@ def decide(S, M, n, min_spp, max_spp, rel_error, abs_floor, near_rel=1e-4):
         lhs, rhs = test_value(S, M, np.maximum(n, 2), rel_error, abs_floor)
         stop = lhs <= rhs
         active &= (n < min_spp) | ~stop
-        near = tested & (np.abs(lhs.astype(np.float64) - rhs) <= near_rel * np.abs(rhs.astype(np.float64)))
+        with np.errstate(invalid="ignore"):   # (inf - inf where both sides are infinite: not near)
+            near = tested & (np.abs(lhs.astype(np.float64) - rhs) <= near_rel * np.abs(rhs.astype(np.float64)))
     return active, near
 
 

@@ -35,6 +35,24 @@ def oracle_render(desc, W, H, spp, max_depth=5, **kw):
     return oracle_render_on(oracle_scene(desc, max_depth), W, H, spp, **kw)
 
 
+def oracle_samples(desc, W, H, n, first=0, tile=None, max_depth=5):
+    """[n, H, W, 3]: the oracle's radiance of samples first .. first + n - 1 of every pixel (of the tile; zero elsewhere), one by one"""
+    o = oracle_scene(desc, max_depth)
+    return np.stack([oracle_render_on(o, W, H, 1, spp_begin=first + s, tile=tile)[0][..., :3] for s in range(n)])
+
+
+def deinterleave_np(compact, H, block, world, rank, full):
+    """rank's compact rows -> their places in the full buffer (row H-1-y), for any per-pixel element shape"""
+    j = 0
+    while True:
+        yb = (j * world + rank) * block
+        if yb >= H:
+            return
+        hb = min(block, H - yb)
+        full[H - yb - hb:H - yb] = compact[j * block:j * block + hb]
+        j += 1
+
+
 _CTX = None
 
 

@@ -11,7 +11,7 @@ import pytest
 import adaptive_model as am
 import ag_pathtracer_amd as ag
 import helpers
-from helpers import gpu_context, gpu_scene, scene_c1
+from helpers import deinterleave_np, gpu_context, gpu_scene, scene_c1
 
 pytestmark = pytest.mark.gpu
 
@@ -108,18 +108,6 @@ def test_pixels_match_oracle_and_model(name):
     assert ast.samples == int(counts.sum()) and st.samples == ast.samples
     assert ast.rounds >= 2 and ast.active_last > 0
     assert ast.pixels_stopped == int(((counts >= MIN) & (counts < MAX)).sum())
-
-
-def deinterleave_np(compact, H, block, world, rank, full):
-    """rank's compact rows -> their places in the full buffer (row H-1-y), for any per-pixel element shape"""
-    j = 0
-    while True:
-        yb = (j * world + rank) * block
-        if yb >= H:
-            return
-        hb = min(block, H - yb)
-        full[H - yb - hb:H - yb] = compact[j * block:j * block + hb]
-        j += 1
 
 
 @pytest.mark.parametrize("name", ["c1", "prims700"])
