@@ -45,6 +45,7 @@ EXPORTS = [
     "agpt_scene_snapshot_surfaces", "agpt_render_features_surface_motion", "agpt_temporal_accumulate_surface_motion", "agpt_kat_surface",
     "agpt_scene_update_sphere", "agpt_scene_update_plane", "agpt_scene_set_area_light_radiance", "agpt_scene_set_infinite_light_radiance",
     "agpt_scene_update_spheres_device",
+    "agpt_scene_pose_mesh_device", "agpt_scene_morph_mesh_device", "agpt_skin_palette", "agpt_morph_active", "agpt_kat_skin_palette", "agpt_kat_morph_active",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
     "agpt_kat_bsdf_sample", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
@@ -245,6 +246,13 @@ def lib():
         L.agpt_scene_set_area_light_radiance.argtypes = [vp, C.c_int, fp]
         L.agpt_scene_set_infinite_light_radiance.argtypes = [vp, C.c_int, fp]
         L.agpt_scene_update_spheres_device.argtypes = [vp, ip, C.c_int, vp]
+    if not variant or hasattr(L, "agpt_scene_pose_mesh_device"):
+        L.agpt_scene_pose_mesh_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+        L.agpt_scene_morph_mesh_device.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int]
+        L.agpt_skin_palette.argtypes = [fp, C.c_int, C.c_int, fp, C.POINTER(C.c_int)]
+        L.agpt_morph_active.argtypes = [fp, C.c_int, ip, fp, C.POINTER(C.c_int)]
+        L.agpt_kat_skin_palette.argtypes = [vp, fp, C.c_int, C.c_int, fp, C.POINTER(C.c_uint32)]
+        L.agpt_kat_morph_active.argtypes = [vp, fp, C.c_int, ip, fp, C.POINTER(C.c_uint32)]
     L.agpt_li_batch.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, fp, C.POINTER(C.c_uint32), C.POINTER(Stats)]
     L.agpt_resolve.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(C.c_uint32)]
     L.agpt_device_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -435,6 +443,11 @@ def _joint_matrices(matrices):
     return m.reshape(-1, 16)
 
 
+def _on_device(a):
+    """a torch tensor that is not on the CPU (update_mesh's test)"""
+    return type(a).__module__.split(".")[0] == "torch" and a.device.type != "cpu"
+
+
 def _influences(joints, weights, what):
     j, w = np.asarray(joints), np.asarray(weights)
     if j.ndim != 2 or j.shape != w.shape:
@@ -460,6 +473,29 @@ def skin_arrays(matrices, verts, joints, weights, normals=None, normal_joints=No
     _check(lib().agpt_skin_arrays(m.ctypes.data_as(fp), m.shape[0], j.shape[1], pv, v.shape[0], pj, pw, pn, 0 if n is None else n.shape[0], pnj, pnw,
                                   vo.ctypes.data_as(fp), None if no is None else no.ctypes.data_as(fp)), "agpt_skin_arrays")
     return vo, no
+
+
+def skin_palette(matrices, with_normals=True):
+    """agpt_skin_palette on the host (no GPU needed): the palette Scene.pose_mesh forms from matrices[n_joints, 4, 4] -- per joint rows
+    0 .. 2 of M and, with_normals, the 3x3 of its inverse transpose -> (palette[n_joints, 21 or 13], the first joint whose determinant
+    is exactly 0 or -1).  What the GPU writes itself when the matrices are a device tensor."""
+    m = _joint_matrices(matrices)
+    out = np.zeros((m.shape[0], 21 if with_normals else 13), np.float32)
+    singular = C.c_int(-1)
+    fp = C.POINTER(C.c_float)
+    _check(lib().agpt_skin_palette(m.ctypes.data_as(fp), m.shape[0], 1 if with_normals else 0, out.ctypes.data_as(fp), C.byref(singular)), "agpt_skin_palette")
+    return out, singular.value
+
+
+def morph_active(weights):
+    """agpt_morph_active on the host (no GPU needed): the (target, weight) pairs Scene.morph_mesh forms from weights[T] -- the weights
+    that are not 0, in target order -> (targets[A] int32, weights[A] float32)."""
+    w, pw = _f(np.asarray(weights).reshape(-1))
+    t, pt = _i(np.zeros(max(w.shape[0], 1), np.int32))
+    a, pa = _f(np.zeros(max(w.shape[0], 1), np.float32))
+    n = C.c_int(0)
+    _check(lib().agpt_morph_active(pw, w.shape[0], pt, pa, C.byref(n)), "agpt_morph_active")
+    return t[:n.value].copy(), a[:n.value].copy()
 
 
 def _deltas(deltas, n, what):
@@ -567,6 +603,28 @@ class Context:
         _check(self.L.agpt_kat_normal_map(self.h, ns.shape[0], pns, pss, prgb, float(scale), out.ctypes.data_as(C.POINTER(C.c_float))),
                "agpt_kat_normal_map")
         return out
+
+    def kat_skin_palette(self, matrices, with_normals=True):
+        """agpt_kat_skin_palette: k_pack_palette, the kernel of Scene.pose_mesh with a device tensor, on matrices[n_joints, 4, 4] ->
+        (palette[n_joints, 21 or 13], status[3] uint32: the lowest joint with a non-finite entry, a bad last row, a determinant of
+        exactly 0; 0xFFFFFFFF = none)."""
+        m = _joint_matrices(matrices)
+        out = np.zeros((m.shape[0], 21 if with_normals else 13), np.float32)
+        status = np.zeros(3, np.uint32)
+        fp = C.POINTER(C.c_float)
+        _check(self.L.agpt_kat_skin_palette(self.h, m.ctypes.data_as(fp), m.shape[0], 1 if with_normals else 0, out.ctypes.data_as(fp),
+                                            status.ctypes.data_as(C.POINTER(C.c_uint32))), "agpt_kat_skin_palette")
+        return out, status
+
+    def kat_morph_active(self, weights):
+        """agpt_kat_morph_active: k_morph_active, the kernel of Scene.morph_mesh with a device tensor, on weights[T] -> (targets[A],
+        weights[A], status[2] uint32: A, the lowest target with a non-finite weight or 0xFFFFFFFF)."""
+        w, pw = _f(np.asarray(weights).reshape(-1))
+        t, pt = _i(np.zeros(max(w.shape[0], 1), np.int32))
+        a, pa = _f(np.zeros(max(w.shape[0], 1), np.float32))
+        status = np.zeros(2, np.uint32)
+        _check(self.L.agpt_kat_morph_active(self.h, pw, w.shape[0], pt, pa, status.ctypes.data_as(C.POINTER(C.c_uint32))), "agpt_kat_morph_active")
+        return t[:int(status[0])].copy(), a[:int(status[0])].copy(), status
 
     def distribution1d(self, func, u):
         """Distribution1D(func) and SampleContinuous(u[i]) (sampling.h:19-52): (cdf[n + 1], funcInt, x[k], pdf[k])."""
@@ -895,10 +953,47 @@ class Scene:
         """agpt_scene_pose_mesh: mesh primitive `prim` posed on the GPU by matrices[n_joints, 4, 4] (or [n_joints, 16]; row-major, last
         row (0, 0, 0, 1)) through the binding of set_mesh_skin, from its rest pose (the arrays it last received from add_mesh /
         update_mesh); absolute, not cumulative.  The scene is what update_mesh(prim, *skin_arrays(matrices, rest_verts, joints,
-        weights, rest_normals, ...), mode) leaves."""
+        weights, rest_normals, ...), mode) leaves.
+        A torch tensor on the context's GPU (contiguous float32, (n_joints, 4, 4) or (n_joints, 16)) is handed over as a device pointer
+        (agpt_scene_pose_mesh_device: the GPU forms the palette and checks the matrices itself) after torch's current stream has been
+        synchronised -- unless the context runs on that very stream, as update_mesh does; anything else (ndarray, list, CPU tensor)
+        goes through the host call."""
+        if _on_device(matrices):
+            ptr, n = self._input_tensor(matrices, "pose_mesh", "matrices", matrix=True)
+            self._wait_for_torch(matrices)
+            self.pose_mesh_device(prim, ptr, n, mode)
+            return
         m = _joint_matrices(matrices)
         _check(self.L.agpt_scene_pose_mesh(self.h, int(prim), m.ctypes.data_as(C.POINTER(C.c_float)), m.shape[0], self._update_mode(mode, "pose_mesh")),
                "agpt_scene_pose_mesh")
+
+    def pose_mesh_device(self, prim, matrices_ptr, n_joints, mode=UPDATE_REFIT):
+        """agpt_scene_pose_mesh_device with a raw device pointer (Context.alloc / upload, or a tensor's data_ptr(); 16-byte aligned): the
+        matrices must be complete, or produced on the context's stream."""
+        _check(self.L.agpt_scene_pose_mesh_device(self.h, int(prim), C.c_void_p(matrices_ptr), int(n_joints), self._update_mode(mode, "pose_mesh_device")),
+               "agpt_scene_pose_mesh_device")
+
+    def _input_tensor(self, t, fn, what, matrix):
+        """(data_ptr, count) of a torch tensor handed to pose_mesh / morph_mesh: contiguous float32 on the context's GPU, (n, 4, 4) or
+        (n, 16) for matrices, (T,) for weights"""
+        import torch
+        if t.device.type != "cuda" or (t.device.index if t.device.index is not None else torch.cuda.current_device()) != self.ctx.device:
+            raise ValueError("%s: %s is on %s, the context is on GPU %d" % (fn, what, t.device, self.ctx.device))
+        if t.dtype != torch.float32:
+            raise ValueError("%s: %s is %s, not float32" % (fn, what, t.dtype))
+        shape = tuple(t.shape)
+        if (len(shape) < 2 or shape[1:] not in ((4, 4), (16,))) if matrix else len(shape) != 1:
+            raise ValueError("%s: %s has shape %s, not %s" % (fn, what, shape, "(n_joints, 4, 4) or (n_joints, 16)" if matrix else "(n_targets,)"))
+        if not t.is_contiguous():
+            raise ValueError("%s: %s is not contiguous" % (fn, what))
+        return t.data_ptr(), shape[0]
+
+    def _wait_for_torch(self, t):
+        """the same-stream rule of update_mesh: torch's current stream is synchronised unless the context runs on it"""
+        import torch
+        stream = torch.cuda.current_stream(t.device)
+        if not self.ctx.stream or int(stream.cuda_stream) != self.ctx.stream:   # (a context on the null stream always waits)
+            stream.synchronize()
 
     def set_mesh_morph_targets(self, prim, position_deltas, normal_deltas=None):
         """agpt_scene_set_mesh_morph_targets: the targets of mesh primitive `prim` for morph_mesh -- position_deltas of shape
@@ -919,11 +1014,41 @@ class Scene:
         """agpt_scene_morph_mesh: mesh primitive `prim` morphed on the GPU by weights[T] through the targets of set_mesh_morph_targets
         and then, with matrices[n_joints, 4, 4] (or [n_joints, 16]), posed through the binding of set_mesh_skin, from its rest pose;
         absolute, not cumulative.  The scene is what update_mesh(prim, *morph_arrays(weights, rest_verts, ...), mode) leaves -- with
-        matrices, those arrays through skin_arrays."""
+        matrices, those arrays through skin_arrays.
+        Torch tensors on the context's GPU (contiguous float32: weights (T,), matrices (n_joints, 4, 4) or (n_joints, 16)) are handed
+        over as device pointers (agpt_scene_morph_mesh_device: the GPU compacts the weights and forms the palette itself) after torch's
+        current stream has been synchronised -- unless the context runs on that very stream, as update_mesh does.  If only one of the two
+        is such a tensor, the other is uploaded by this call.  Host data on both sides goes through the host call."""
+        if _on_device(weights) or _on_device(matrices):
+            held = []   # this call's uploads of the host one of the two
+
+            def device(a, what, matrix):
+                if _on_device(a):
+                    ptr_count = self._input_tensor(a, "morph_mesh", what, matrix)
+                    self._wait_for_torch(a)
+                    return ptr_count
+                h = _joint_matrices(a) if matrix else np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1))
+                held.append(self.ctx.alloc(max(h.nbytes, 16)))
+                self.ctx.upload(held[-1], h)
+                return held[-1], h.shape[0]
+            try:
+                pw, T = device(weights, "weights", False)
+                pm, J = (None, 0) if matrices is None else device(matrices, "matrices", True)
+                self.morph_mesh_device(prim, pw, T, pm, J, mode)
+            finally:
+                for p in held:
+                    self.ctx.free(p)
+            return
         w, pw = _f(np.asarray(weights).reshape(-1))
         m = None if matrices is None else _joint_matrices(matrices)
         _check(self.L.agpt_scene_morph_mesh(self.h, int(prim), pw, w.shape[0], None if m is None else m.ctypes.data_as(C.POINTER(C.c_float)),
                                             0 if m is None else m.shape[0], self._update_mode(mode, "morph_mesh")), "agpt_scene_morph_mesh")
+
+    def morph_mesh_device(self, prim, weights_ptr, n_targets, matrices_ptr=None, n_joints=0, mode=UPDATE_REFIT):
+        """agpt_scene_morph_mesh_device with raw device pointers (Context.alloc / upload, or a tensor's data_ptr(); the matrices 16-byte
+        aligned): the arrays must be complete, or produced on the context's stream."""
+        _check(self.L.agpt_scene_morph_mesh_device(self.h, int(prim), C.c_void_p(weights_ptr), int(n_targets), C.c_void_p(matrices_ptr or None),
+                                                   int(n_joints), self._update_mode(mode, "morph_mesh_device")), "agpt_scene_morph_mesh_device")
 
     def set_mesh_normals_mode(self, prim, mode):
         """agpt_scene_set_mesh_normals_mode: "given" (default; NORMALS_GIVEN) -- the normals of mesh primitive `prim` come from the caller or

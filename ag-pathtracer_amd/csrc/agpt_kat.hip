@@ -189,4 +189,46 @@ int agpt_kat_distribution1d(agpt_ctx* c, const float* func, int n, const float* 
     return d_p.out(pdf_out, (size_t)k);
 }
 
+// the two front-end kernels of the device-pointer mesh calls (agpt_update.hip), launched as MeshUpdate::device_inputs launches them
+int agpt_kat_skin_palette(agpt_ctx* c, const float* joints16, int n_joints, int with_normals, float* palette_out, uint32_t status_out[3]) {
+    if (!c || !joints16 || n_joints < 1 || n_joints > agpt::kSkinMaxJoints || !palette_out || !status_out)
+        return fail(AGPT_ERR_INVALID, "agpt_kat_skin_palette: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)n_joints * (size_t)agpt::skin_palette_stride(with_normals != 0);
+    DevBuf<float> d_j, d_p;
+    DevBuf<uint32_t> d_s;
+    int rc;
+    if ((rc = d_j.in(joints16, 16 * (size_t)n_joints))) return rc;
+    HIP_TRY(d_p.alloc(n));
+    HIP_TRY(d_s.alloc(3));
+    HIP_TRY(hipMemsetAsync(d_s.p, 0xFF, 3 * sizeof(uint32_t), c->stream));
+    if ((rc = agpt::launch_pack_palette(c->stream, d_j.p, n_joints, with_normals != 0, d_p.p, d_s.p)) || (rc = launched(c)) ||
+        (rc = d_p.out(palette_out, n)))
+        return rc;
+    return d_s.out(status_out, 3);
+}
+
+int agpt_kat_morph_active(agpt_ctx* c, const float* weights, int n_targets, int32_t* targets_out, float* weights_out, uint32_t status_out[2]) {
+    if (!c || !weights || n_targets < 1 || n_targets > agpt::kMorphMaxTargets || !targets_out || !weights_out || !status_out)
+        return fail(AGPT_ERR_INVALID, "agpt_kat_morph_active: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> d_w;
+    DevBuf<agpt::MorphActive> d_a;
+    DevBuf<uint32_t> d_s;
+    int rc;
+    if ((rc = d_w.in(weights, (size_t)n_targets))) return rc;
+    HIP_TRY(d_a.alloc((size_t)n_targets));
+    HIP_TRY(d_s.alloc(2));
+    if ((rc = agpt::launch_morph_active(c->stream, d_w.p, n_targets, d_a.p, d_s.p)) || (rc = launched(c)) || (rc = d_s.out(status_out, 2))) return rc;
+    if (status_out[0] > (uint32_t)n_targets) return fail(AGPT_ERR_DEVICE, "agpt_kat_morph_active: the kernel reports more pairs than targets");
+    std::vector<agpt::MorphActive> active(status_out[0]);
+    if (!active.empty())
+        if ((rc = d_a.out(active.data(), active.size()))) return rc;
+    for (size_t k = 0; k < active.size(); k++) {
+        targets_out[k] = active[k].target;
+        weights_out[k] = active[k].weight;
+    }
+    return AGPT_OK;
+}
+
 }  // extern "C"

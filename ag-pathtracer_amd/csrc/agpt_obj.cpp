@@ -511,6 +511,38 @@ int agpt_skin_arrays(const float* joints16, int n_joints, int influences, const 
     return AGPT_OK;
 }
 
+int agpt_skin_palette(const float* joints16, int n_joints, int with_normals, float* palette_out, int* singular_out) {
+    const std::string f = "agpt_skin_palette: ";
+    if (!joints16 || !palette_out) return agpt::fail(AGPT_ERR_INVALID, f + "NULL joints16 or palette_out");
+    if (n_joints < 1 || n_joints > agpt::kSkinMaxJoints)
+        return agpt::fail(AGPT_ERR_INVALID, f + "n_joints is " + std::to_string(n_joints) + ", outside 1 .. " + std::to_string(agpt::kSkinMaxJoints));
+    for (size_t i = 0; i < 16 * (size_t)n_joints; i++)   // agpt_scene_pose_mesh's checks of the matrices, in its order and words
+        if (!std::isfinite(joints16[i])) return agpt::fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(i / 16) + " has a non-finite entry");
+    const std::string bad = agpt::skin_check_last_rows(joints16, n_joints);
+    if (!bad.empty()) return agpt::fail(AGPT_ERR_INVALID, f + bad);
+    int singular = -1;
+    const std::vector<float> palette = agpt::skin_pack_palette(joints16, n_joints, with_normals != 0, &singular);
+    std::memcpy(palette_out, palette.data(), palette.size() * sizeof(float));
+    if (singular_out) *singular_out = singular;
+    return AGPT_OK;
+}
+
+int agpt_morph_active(const float* weights, int n_targets, int32_t* targets_out, float* weights_out, int* n_active_out) {
+    const std::string f = "agpt_morph_active: ";
+    if (!weights || !targets_out || !weights_out || !n_active_out)
+        return agpt::fail(AGPT_ERR_INVALID, f + "NULL weights, targets_out, weights_out or n_active_out");
+    std::string bad = agpt::morph_check_count(n_targets);
+    if (bad.empty()) bad = agpt::morph_check_weights(weights, n_targets);
+    if (!bad.empty()) return agpt::fail(AGPT_ERR_INVALID, f + bad);
+    const std::vector<agpt::MorphActive> active = agpt::morph_active_list(weights, n_targets);
+    for (size_t k = 0; k < active.size(); k++) {
+        targets_out[k] = active[k].target;
+        weights_out[k] = active[k].weight;
+    }
+    *n_active_out = (int)active.size();
+    return AGPT_OK;
+}
+
 int agpt_morph_arrays(const float* weights, int n_targets, const float* vertices, int n_vertices, const float* position_deltas, const float* normals,
                       int n_normals, const float* normal_deltas, float* vertices_out, float* normals_out) {
     const std::string f = "agpt_morph_arrays: ";

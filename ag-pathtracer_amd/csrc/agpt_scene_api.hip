@@ -711,19 +711,36 @@ int agpt_scene_update_mesh_device(agpt_scene* s, int prim, const float* vertices
     return update_from_updater(s, prim, mi, mode);
 }
 
+// What the status words of a device-pointer call refuse, in the host calls' order and words -- the weights first, then the joints: a
+// non-finite entry, a last row, a determinant of 0, each naming the lowest offender -- or "" when they are clean.
+static std::string device_refusal(const agpt::DeviceInputStatus& st) {
+    if (st.nonfinite_weight != agpt::kNoItem) return "non-finite weight (target " + std::to_string(st.nonfinite_weight) + ")";
+    if (st.nonfinite_joint != agpt::kNoItem) return "joint " + std::to_string(st.nonfinite_joint) + " has a non-finite entry";
+    if (st.bad_row_joint != agpt::kNoItem) return "the last row of joint " + std::to_string(st.bad_row_joint) + " is not (0, 0, 0, 1)";
+    if (st.singular_joint != agpt::kNoItem) return "joint " + std::to_string(st.singular_joint) + " is singular (its determinant is exactly 0)";
+    return "";
+}
+
 // The tail the transform, the pose and the morph share.  The rest pose: the arrays the mesh last received explicitly -- the mirror,
 // brought up to date if they came as device pointers.  Then the one launcher and the refit.  Synchronises with the stream: what the
 // request points to lives until then.
+// A request with device pointers (rq.status) starts with the front-end kernels and their status words, ahead of anything that touches
+// the mesh: a refused call changes nothing.
 static int deform_mesh(agpt_scene* s, int prim, int mode, agpt::DeformRequest rq) {
     const size_t mi = (size_t)s->prims[prim].index;
     agpt::MeshUpdate& up = s->updates[mi];
     HIP_TRY(hipSetDevice(s->ctx->device));
+    rq.with_normals = !smooth_normals(s, mi);
+    rq.num_cus = s->ctx->num_cus;
+    if (rq.status) {
+        if (const int rc = up.device_inputs(s->ctx->stream, s->meshes[mi], rq)) return rc;
+        const std::string bad = device_refusal(*rq.status);
+        if (!bad.empty()) return fail(AGPT_ERR_INVALID, std::string(rq.fn) + ": " + bad);
+    }
     if (!up.has_rest()) {
         if (const int rc = sync_mirror(s, true)) return rc;
         up.rest_taken(s->meshes[mi].vertices, s->meshes[mi].normals);
     }
-    rq.with_normals = !smooth_normals(s, mi);
-    rq.num_cus = s->ctx->num_cus;
     if (const int rc = up.deform(s->ctx->stream, s->meshes[mi], rq)) return rc;
     return update_from_updater(s, prim, mi, mode);
 }
@@ -786,15 +803,22 @@ int agpt_scene_set_mesh_skin(agpt_scene* s, int prim, int influences, int n_join
     return AGPT_OK;
 }
 
+// the checks of a frame's joint matrices that need no look at them, shared by the host and the device-pointer calls: the refusal's
+// message, or ""
+static std::string pose_args(const agpt_scene* s, int prim, const float* joints16, int n_joints) {
+    const agpt::SkinBinding& skin = s->updates[(size_t)s->prims[prim].index].skin();
+    if (skin.influences == 0) return "primitive " + std::to_string(prim) + " has no skin (agpt_scene_set_mesh_skin)";
+    if (!joints16) return "NULL joints16";
+    if (n_joints != skin.n_joints) return "n_joints is " + std::to_string(n_joints) + ", the skin was set with " + std::to_string(skin.n_joints);
+    return "";
+}
+
 // the checks of a frame's joint matrices that agpt_scene_pose_mesh and agpt_scene_morph_mesh share, in their order, then the palette
 // (`f` is the call's name and ": "; for a mesh in AGPT_NORMALS_SMOOTH mode, as for one without normals, the palette carries M only)
 static int pose_palette(const std::string& f, const agpt_scene* s, int prim, const float* joints16, int n_joints, std::vector<float>& palette) {
     const size_t mi = (size_t)s->prims[prim].index;
-    const agpt::SkinBinding& skin = s->updates[mi].skin();
-    if (skin.influences == 0) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no skin (agpt_scene_set_mesh_skin)");
-    if (!joints16) return fail(AGPT_ERR_INVALID, f + "NULL joints16");
-    if (n_joints != skin.n_joints)
-        return fail(AGPT_ERR_INVALID, f + "n_joints is " + std::to_string(n_joints) + ", the skin was set with " + std::to_string(skin.n_joints));
+    const std::string args = pose_args(s, prim, joints16, n_joints);
+    if (!args.empty()) return fail(AGPT_ERR_INVALID, f + args);
     for (size_t i = 0; i < 16 * (size_t)n_joints; i++)
         if (!std::isfinite(joints16[i])) return fail(AGPT_ERR_INVALID, f + "joint " + std::to_string(i / 16) + " has a non-finite entry");
     const std::string bad = agpt::skin_check_last_rows(joints16, n_joints);
@@ -812,6 +836,20 @@ int agpt_scene_pose_mesh(agpt_scene* s, int prim, const float* joints16, int n_j
     agpt::DeformRequest rq{"agpt_scene_pose_mesh"};
     rq.palette = &palette;
     return deform_mesh(s, prim, mode, rq);
+}
+
+int agpt_scene_pose_mesh_device(agpt_scene* s, int prim, const float* joints16_dev, int n_joints, int mode) {
+    const std::string f = "agpt_scene_pose_mesh_device: ";
+    if (const int rc = check_update("agpt_scene_pose_mesh_device", s, prim, nullptr, mode)) return rc;
+    const std::string args = pose_args(s, prim, joints16_dev, n_joints);
+    if (!args.empty()) return fail(AGPT_ERR_INVALID, f + args);
+    if (((uintptr_t)joints16_dev & 15) != 0) return fail(AGPT_ERR_INVALID, f + "joints16_dev is not 16-byte aligned");
+    agpt::DeviceInputStatus status;
+    agpt::DeformRequest rq{"agpt_scene_pose_mesh_device"};
+    rq.joints16_dev = joints16_dev;
+    rq.n_joints = n_joints;
+    rq.status = &status;
+    return deform_mesh(s, prim, mode, rq);   // (the matrices' own checks are k_pack_palette's)
 }
 
 int agpt_scene_set_mesh_morph_targets(agpt_scene* s, int prim, int n_targets, const float* position_deltas, const float* normal_deltas) {
@@ -854,6 +892,36 @@ int agpt_scene_morph_mesh(agpt_scene* s, int prim, const float* weights, int n_t
     agpt::DeformRequest rq{"agpt_scene_morph_mesh"};
     rq.active = &active;
     if (joints16) rq.palette = &palette;
+    return deform_mesh(s, prim, mode, rq);
+}
+
+int agpt_scene_morph_mesh_device(agpt_scene* s, int prim, const float* weights_dev, int n_targets, const float* joints16_dev, int n_joints, int mode) {
+    const std::string f = "agpt_scene_morph_mesh_device: ";
+    if (const int rc = check_update("agpt_scene_morph_mesh_device", s, prim, nullptr, mode)) return rc;
+    const size_t mi = (size_t)s->prims[prim].index;
+    const int bound = s->updates[mi].morph().n_targets;
+    if (bound == 0) return fail(AGPT_ERR_INVALID, f + "primitive " + std::to_string(prim) + " has no morph targets (agpt_scene_set_mesh_morph_targets)");
+    if (!weights_dev) return fail(AGPT_ERR_INVALID, f + "NULL weights");
+    if (n_targets != bound)
+        return fail(AGPT_ERR_INVALID, f + "n_targets is " + std::to_string(n_targets) + ", the targets were set with " + std::to_string(bound));
+    if (((uintptr_t)weights_dev & 3) != 0) return fail(AGPT_ERR_INVALID, f + "weights_dev is not 4-byte aligned");
+    agpt::DeviceInputStatus status;
+    agpt::DeformRequest rq{"agpt_scene_morph_mesh_device"};
+    rq.weights_dev = weights_dev;
+    rq.n_targets = n_targets;
+    rq.status = &status;
+    std::string args = joints16_dev ? pose_args(s, prim, joints16_dev, n_joints) : "";
+    if (args.empty() && joints16_dev && ((uintptr_t)joints16_dev & 15) != 0) args = "joints16_dev is not 16-byte aligned";
+    if (!args.empty()) {   // the host call looks at the weights before it looks at the skin: k_morph_active alone, then this refusal
+        HIP_TRY(hipSetDevice(s->ctx->device));
+        if (const int rc = s->updates[mi].device_inputs(s->ctx->stream, s->meshes[mi], rq)) return rc;
+        const std::string weights = device_refusal(status);
+        return fail(AGPT_ERR_INVALID, f + (weights.empty() ? args : weights));
+    }
+    if (joints16_dev) {
+        rq.joints16_dev = joints16_dev;
+        rq.n_joints = n_joints;
+    }
     return deform_mesh(s, prim, mode, rq);
 }
 

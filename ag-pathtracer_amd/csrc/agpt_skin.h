@@ -4,7 +4,8 @@
 // is fp32 and rounds on its own, so the two produce the same bits.
 //
 //   vertex i has K influences (joint[i][k], weight[i][k]), k = 0 .. K-1, flat arrays of stride K; joint j has a row-major 4x4 M_j with
-//   the last row (0, 0, 0, 1) and N_j = inverse_transpose(M_j), formed on the host.
+//   the last row (0, 0, 0, 1) and N_j = inverse_transpose(M_j), formed on the host (skin_pack_palette) or, for matrices given in device
+//   memory, by k_pack_palette (agpt_update.hip): the same function, the same floats.
 //   position   the slots in order; a slot whose weight is exactly 0 (either sign) is skipped; the first used slot sets
 //              acc = w * transform_point(M_j, p) per component, every later one acc = acc + w * transform_point(M_j, p); a vertex
 //              without a used slot keeps its rest position.  Weights are used as given (not normalised, not reordered).

@@ -23,8 +23,9 @@ AGPT_HD Mat4 mat4_identity() {
 }
 
 // mat4::Inverted (the MESA cofactor expansion) followed by ::Transposed (3x3 part).  *det_out (may be NULL) receives the determinant
-// the expansion computes; a matrix whose determinant is exactly 0 inverts to the identity, as in the reference.
-inline Mat4 inverse_transpose(const Mat4& M, float* det_out = nullptr) {
+// the expansion computes; a matrix whose determinant is exactly 0 inverts to the identity, as in the reference.  Host and device
+// (k_pack_palette, agpt_update.hip) evaluate this one text, in this order.
+AGPT_HD Mat4 inverse_transpose(const Mat4& M, float* det_out = nullptr) {
     const float* cell = M.c;
     const float inv[16] = {
         cell[5] * cell[10] * cell[15] - cell[5] * cell[11] * cell[14] - cell[9] * cell[6] * cell[15] + cell[9] * cell[7] * cell[14] + cell[13] * cell[6] * cell[11] - cell[13] * cell[7] * cell[10],

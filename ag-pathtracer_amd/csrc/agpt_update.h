@@ -33,13 +33,32 @@ struct UpdateTarget {
 
 // What a frame asks of MeshUpdate::deform.  One of three shapes: M and N (agpt_scene_transform_mesh: N = inverse_transpose(M)); `palette`
 // (agpt_scene_pose_mesh: agpt_skin.h's packed palette for the state's binding); `active` (agpt_scene_morph_mesh: the frame's (target,
-// weight) pairs for the state's targets), with `palette` as well when the morph runs on through the skin.  The caller keeps what the
-// pointers name until the stream is synchronised.
+// weight) pairs for the state's targets), with `palette` as well when the morph runs on through the skin.  Either of the two may come
+// in its device-pointer form instead.  The caller keeps what the pointers name until the stream is synchronised.
+// The status words of a request whose joint matrices or weights are in device memory (k_pack_palette, k_morph_active): each the lowest
+// offending index, kNoItem for none; 20 bytes, the one download of MeshUpdate::device_inputs.  The order of the first three is the
+// order in which agpt_scene_pose_mesh refuses.
+constexpr uint32_t kNoItem = 0xFFFFFFFFu;
+struct DeviceInputStatus {
+    uint32_t nonfinite_joint = kNoItem, bad_row_joint = kNoItem, singular_joint = kNoItem;
+    uint32_t n_active = 0;     // the pairs k_morph_active wrote
+    uint32_t nonfinite_weight = kNoItem;
+    bool clean() const { return nonfinite_joint == kNoItem && bad_row_joint == kNoItem && singular_joint == kNoItem && nonfinite_weight == kNoItem; }
+};
+
 struct DeformRequest {
     const char* fn;            // the entry point, named in the messages
     const Mat4 *M = nullptr, *N = nullptr;
     const std::vector<float>* palette = nullptr;
     const std::vector<MorphActive>* active = nullptr;
+    // The device-pointer forms of `palette` and `active` (agpt_scene_pose_mesh_device, agpt_scene_morph_mesh_device): n_joints row-major
+    // 4x4 (16-byte aligned) and n_targets weights in device memory, complete or produced on the stream.  MeshUpdate::device_inputs turns
+    // them into the cache's palette and active list and fills *status; deform takes the request only with a clean status.
+    const float* joints16_dev = nullptr;
+    int n_joints = 0;
+    const float* weights_dev = nullptr;
+    int n_targets = 0;
+    DeviceInputStatus* status = nullptr;
     bool with_normals = true;  // false for a mesh in AGPT_NORMALS_SMOOTH mode: the normal halves get an item count of zero and the palette
                                // carries M only (stride 13)
     int num_cus = 1;           // sizes the grids of k_skin_mesh and k_morph_mesh
@@ -97,6 +116,11 @@ public:
     int copy_arrays(hipStream_t stream, const HostMesh& mesh, const float* vertices_dev, const float* normals_dev);
     int upload_positions(hipStream_t stream, const HostMesh& mesh, const float* vertices);
     int deform(hipStream_t stream, const HostMesh& mesh, const DeformRequest& rq);
+    // The front end of a request with device pointers, ahead of deform (k_check_spheres -> synchronise -> k_update_spheres' shape,
+    // agpt_analytic.hip): k_pack_palette writes the cache's palette from rq.joints16_dev, k_morph_active its active list from
+    // rq.weights_dev, and the status words come back in one download (*rq.status).  Synchronises with the stream.  Reads rq.with_normals;
+    // touches nothing but the palette, the active list and the status words, which every call overwrites.
+    int device_inputs(hipStream_t stream, const HostMesh& mesh, const DeformRequest& rq);
     int smooth_normals(hipStream_t stream, const HostMesh& mesh);
     int refit(hipStream_t stream, const HostMesh& mesh, const UpdateTarget& target, float root6[6], bool* finite);
     // the buffers' contents (vertices / normals keep their sizes), and mesh.nodes' bounds from the last refit
@@ -113,5 +137,14 @@ private:
     MorphTargets morph_;
     std::unique_ptr<MeshDeviceCache> dev_;
 };
+
+// The launches of the two front-end kernels, for device_inputs and for the known-answer entry points (agpt_kat.hip), which run the very
+// kernels the scene calls run.  Everything is device memory; nothing is synchronised.
+//   launch_pack_palette  joints16_dev (16-byte aligned) -> palette_dev, n_joints * skin_palette_stride(with_normals) floats in
+//                        skin_pack_palette's layout; status3_dev must hold kNoItem three times and receives DeviceInputStatus' first three.
+//   launch_morph_active  weights_dev (1 .. kMorphMaxTargets) -> active_dev (room for n_targets pairs), morph_active_list's bytes;
+//                        status2_dev receives n_active and the lowest index of a non-finite weight (kNoItem: none).
+int launch_pack_palette(hipStream_t stream, const float* joints16_dev, int n_joints, bool with_normals, float* palette_dev, uint32_t* status3_dev);
+int launch_morph_active(hipStream_t stream, const float* weights_dev, int n_targets, MorphActive* active_dev, uint32_t* status2_dev);
 
 }  // namespace agpt

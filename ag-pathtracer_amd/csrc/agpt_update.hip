@@ -18,6 +18,12 @@
 //                    (agpt_scene_pose_mesh).
 //   k_morph_mesh     one lane per vertex and one per normal: the rest arrays plus the ACTIVE morph targets' deltas (morph_blend of
 //                    agpt_morph.h) and, fused (kSkin), straight on through skin_blend (agpt_scene_morph_mesh).
+//   k_pack_palette   one lane per joint of a frame's matrices in DEVICE memory (agpt_scene_pose_mesh_device, _morph_mesh_device): four
+//                    16-byte loads of M, inverse_transpose of agpt_transform.h -- the host's text -- and the joint's entry of the
+//                    palette k_skin_mesh reads, skin_pack_palette's floats; three status words take the lowest joint with a non-finite
+//                    entry, a last row that is not (0, 0, 0, 1), a determinant of exactly 0.
+//   k_morph_active   one block: a frame's weights in device memory into the (target, weight) list k_morph_mesh walks, morph_active_list's
+//                    bytes, its length and the lowest target with a non-finite weight.
 //   k_face_normals   one lane per triangle: its three vertex indices (the index array k_update_tris reads) and positions, face_vector of
 //                    agpt_normals.h, one float4 g_t (w unused) into a per-mesh scratch of n_tris x 16 B.
 //   k_vertex_normals one lane per normal item: offsets[j], offsets[j + 1] of the CSR adjacency, then per incident corner the triangle id
@@ -26,8 +32,9 @@
 //                    front end that leaves positions in `verts` and k_update_tris; no atomics, so the bytes do not depend on the
 //                    launch.  An item of very high valence is walked by one lane: correct and slow.
 // All are bandwidth kernels (about 72 B read and 112 B written per triangle, 64 B per node pair, 24 B per transformed vertex, 24 + 8 K B
-// per skinned vertex, 24 + 12 A B per vertex morphed by A active targets); all but k_skin_mesh and k_morph_mesh run 64-lane blocks,
-// 16-byte accesses of the float4 records, no LDS.
+// per skinned vertex, 24 + 12 A B per vertex morphed by A active targets; k_pack_palette and k_morph_active move a few KB and cost their
+// launch); all but k_skin_mesh, k_morph_mesh and the one-block k_morph_active run 64-lane blocks, 16-byte accesses of the float4 records,
+// no LDS.
 //
 // k_skin_mesh's palette.  The per-lane gather by joint index is the one access here that is not a stream, and neighbouring vertices
 // mostly name the same few joints.  A palette of up to 40 KiB (487 joints with normals, 787 without) is staged in LDS; a larger one is
@@ -73,6 +80,26 @@
 //              k_morph_mesh<true, false>   50 / 53 / 0 / 0        (fused, palette in global memory)
 //              k_morph_mesh<true, true>    52 / 55 / 0 / 0        (fused, palette in LDS)
 //            kLds has no meaning without kSkin: <false, true> is not instantiated, so there are three, not four.
+//
+// k_pack_palette and k_morph_active: the front end of a frame whose matrices and weights are already on the GPU.  What the host did per
+// frame -- n_joints inverse transposes, the compaction of the weights, two small uploads -- runs here, and 20 bytes come back
+// (DeviceInputStatus): the deform kernels above are launched only when they are clean, k_check_spheres -> synchronise ->
+// k_update_spheres' shape (agpt_analytic.hip), and take n_active by value as before.
+//   palette  one 64-lane block per 64 joints.  A joint is 64 B read as four float4 (hence the 16-byte alignment asked of the caller) and
+//            84 or 52 B written with 4-byte stores (the odd stride has no wider alignment); at 1,024 joints that is 150 KB, a launch
+//            and nothing else.  An M-only palette (stride 13) still computes the determinant: the host refuses a singular joint either
+//            way.  The pad of an M-only entry is written as 0, as the host's is.
+//   status   every lane of a wave arrives at the three ballots; the lowest set bit is the wave's lowest offender (lanes hold consecutive
+//            joints) and lane 0 issues one vector atomicMin per word that has one -- aggregated by hand, as everywhere in this library
+//            (the atomic optimizer is off).  The words start at 0xFFFFFFFF; a clean call leaves them there, so the memset of the 20
+//            bytes is paid by the first call and by the one after a refusal.  They come down into pinned host memory of the cache.
+//   active   T <= 4,096 weights, 256 at a time: a pair's place is the pairs of the chunks before, of the waves before (four counts in
+//            LDS) and of the lanes before (popcount of the ballot below the lane): no atomic, so the list is in target order whatever
+//            the schedule, and its bytes are the host's.  -0.0 is skipped (!(w == 0)).
+//   code     from the gfx950 code object of this unit (VGPRs / SGPRs / spilled / scratch bytes):
+//              k_pack_palette              50 / 23 / 0 / 0
+//              k_morph_active              18 / 28 / 0 / 0        (32 B of LDS)
+//            k_skin_mesh and k_morph_mesh keep the figures above.
 //
 // The host half.  MeshDeviceCache holds the device copies of one mesh; MeshUpdate (agpt_update.h) owns it beside the host copies and
 // is the only one to invalidate either.  MeshUpdate::deform is the one launcher of k_transform_mesh, k_skin_mesh and k_morph_mesh: rest
@@ -337,7 +364,112 @@ __global__ __launch_bounds__(kSkinBlock) void k_morph_mesh(const MorphActive* __
     }
 }
 
+__device__ __forceinline__ bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// The lowest item of a wave whose lane has `bad` set, into *word: the lanes of a wave hold consecutive items, so it is the lowest set
+// bit of the ballot, and lane 0 issues the one vector atomicMin.  Every lane of the wave must arrive.
+__device__ __forceinline__ void wave_lowest(bool bad, uint32_t wave_first_item, uint32_t* word) {
+    const unsigned long long b = __ballot(bad);
+    if (b != 0 && (threadIdx.x & 63) == 0) atomicMin(word, wave_first_item + (uint32_t)(__ffsll(b) - 1));
+}
+
+struct PaletteArgs {
+    const float4* joints;      // four float4 per joint: the rows of M
+    int n_joints, stride;
+    float* palette;
+    uint32_t* status;          // DeviceInputStatus' first three words, kNoItem on entry
+};
+
+__global__ __launch_bounds__(kBlock) void k_pack_palette(PaletteArgs a) {
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    bool nonfinite = false, bad_row = false, singular = false;
+    if (j < a.n_joints) {
+        Mat4 M;
+        for (int r = 0; r < 4; r++) {
+            const float4 q = a.joints[4 * (size_t)j + r];
+            M.c[4 * r] = q.x; M.c[4 * r + 1] = q.y; M.c[4 * r + 2] = q.z; M.c[4 * r + 3] = q.w;
+        }
+        for (int i = 0; i < 16; i++) nonfinite |= non_finite(M.c[i]);
+        bad_row = !(M.c[12] == 0 && M.c[13] == 0 && M.c[14] == 0 && M.c[15] == 1);   // skin_check_last_rows' test
+        float det = 0;
+        const Mat4 N = inverse_transpose(M, &det);   // (computed for an M-only palette as well: the host refuses a singular joint either way)
+        singular = det == 0;
+        float* e = a.palette + (size_t)j * (size_t)a.stride;   // skin_pack_palette's entry
+        for (int i = 0; i < 12; i++) e[i] = M.c[i];
+        if (a.stride == skin_palette_stride(true)) {
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) e[12 + 3 * r + c] = N.c[4 * r + c];
+        } else {
+            e[12] = 0.f;   // the pad of the M-only entry
+        }
+    }
+    const uint32_t first = (uint32_t)(blockIdx.x * kBlock);   // (kBlock is one wave)
+    wave_lowest(nonfinite, first, a.status);
+    wave_lowest(bad_row, first, a.status + 1);
+    wave_lowest(singular, first, a.status + 2);
+}
+
+constexpr int kActiveBlock = 256, kActiveWaves = kActiveBlock / 64;
+
+// One block.  The targets are taken kActiveBlock at a time, in order; the place of a pair is the pairs of the chunks before (`base`, the
+// same in every lane), of the waves before in this chunk, and of the lanes before in this wave -- ballots and popcounts, no atomic, so
+// the list is in target order whatever the schedule.
+__global__ __launch_bounds__(kActiveBlock) void k_morph_active(const float* __restrict__ weights, int n_targets, MorphActive* __restrict__ active,
+                                                               uint32_t* __restrict__ status) {
+    __shared__ uint32_t wave_count[kActiveWaves], wave_bad[kActiveWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t base = 0, bad = kNoItem;
+    for (int first = 0; first < n_targets; first += kActiveBlock) {
+        const int t = first + (int)threadIdx.x;
+        const float w = t < n_targets ? weights[t] : 0.f;
+        const bool use = !(w == 0);   // morph_active_list's test: -0.0 is skipped
+        if (bad == kNoItem && non_finite(w)) bad = (uint32_t)t;   // (a lane's targets ascend: its first is its lowest)
+        const unsigned long long b = __ballot(use);
+        if (lane == 0) wave_count[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (int k = 0; k < kActiveWaves; k++) {
+            const uint32_t c = wave_count[k];
+            before += k < wave ? c : 0u;
+            all += c;
+        }
+        if (use) active[base + before + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = MorphActive{t, w};
+        base += all;
+        __syncthreads();   // (the next chunk rewrites wave_count)
+    }
+    for (int o = 32; o > 0; o >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, o));
+    if (lane == 0) wave_bad[wave] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < kActiveWaves; k++) bad = min(bad, wave_bad[k]);
+        status[0] = base;
+        status[1] = bad;
+    }
+}
+
 }  // namespace
+
+int launch_pack_palette(hipStream_t stream, const float* joints16_dev, int n_joints, bool with_normals, float* palette_dev, uint32_t* status3_dev) {
+    if (!joints16_dev || !palette_dev || !status3_dev || n_joints < 1 || n_joints > kSkinMaxJoints || ((uintptr_t)joints16_dev & 15) != 0)
+        return fail(AGPT_ERR_INVALID, "k_pack_palette: NULL or misaligned pointer, or n_joints outside 1 .. " + std::to_string(kSkinMaxJoints));
+    PaletteArgs a;
+    a.joints = reinterpret_cast<const float4*>(joints16_dev);
+    a.n_joints = n_joints;
+    a.stride = skin_palette_stride(with_normals);
+    a.palette = palette_dev;
+    a.status = status3_dev;
+    hipLaunchKernelGGL(k_pack_palette, dim3((unsigned)((n_joints + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return AGPT_OK;
+}
+
+int launch_morph_active(hipStream_t stream, const float* weights_dev, int n_targets, MorphActive* active_dev, uint32_t* status2_dev) {
+    if (!weights_dev || !active_dev || !status2_dev || n_targets < 1 || n_targets > kMorphMaxTargets)
+        return fail(AGPT_ERR_INVALID, "k_morph_active: NULL pointer, or n_targets outside 1 .. " + std::to_string(kMorphMaxTargets));
+    hipLaunchKernelGGL(k_morph_active, dim3(1), dim3(kActiveBlock), 0, stream, weights_dev, n_targets, active_dev, status2_dev);
+    HIP_TRY(hipGetLastError());
+    return AGPT_OK;
+}
 
 struct MeshDeviceCache {
     DevBuf<float> verts, normals;
@@ -358,6 +490,14 @@ struct MeshDeviceCache {
     DevBuf<float4> face_normals;
     bool has_adjacency = false;
     DevBuf<uint32_t> flag;        // k_check_finite's word
+    // DeviceInputStatus' five words (k_pack_palette, k_morph_active) and the pinned host words they are downloaded into.  joint_words_clean:
+    // the three atomicMin words hold kNoItem -- a clean call leaves them so, and only a refused one (or a new allocation) costs a memset
+    DevBuf<uint32_t> input_status;
+    uint32_t* input_status_host = nullptr;
+    bool joint_words_clean = false;
+    ~MeshDeviceCache() {
+        if (input_status_host) (void)hipHostFree(input_status_host);
+    }
     DevBuf<v2> uv;
     DevBuf<int32_t> indices, prim_index, lists;
     DevBuf<int2> topo;
@@ -592,16 +732,17 @@ static void rest_args(const MeshDeviceCache& u, const HostMesh& mesh, bool with_
     a.n_normals = (int)nn;
 }
 
-// the binding on the device (uploaded when the cache holds none), this call's palette, and the skin's share of the kernel arguments
+// the binding on the device (uploaded when the cache holds none), this call's palette -- `palette` == NULL: k_pack_palette has written
+// it from `n_joints` matrices in device memory --, and the skin's share of the kernel arguments
 static int skin_on_device(const char* fn, hipStream_t stream, MeshDeviceCache& u, const HostMesh& mesh, const SkinBinding& skin,
-                          const std::vector<float>& palette, bool with_normals, SkinArgs& a) {
+                          const std::vector<float>* palette, int n_joints, bool with_normals, SkinArgs& a) {
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), K = (size_t)skin.influences;
     const int stride = skin_palette_stride(nn != 0 && with_normals);   // (without: M only, as for a mesh that has no normals)
     const bool own_normal_slots = nn && !skin.normal_joints.empty();
     // what the kernel indexes with, against what it indexes (the joint indices were checked against n_joints when the skin was set)
     if (K < 1 || K > (size_t)kSkinMaxInfluences || skin.vertex_joints.size() != nv * K || skin.vertex_weights.size() != nv * K ||
         (own_normal_slots ? skin.normal_joints.size() != nn * K || skin.normal_weights.size() != nn * K : nn && nn != nv) ||
-        palette.size() != (size_t)skin.n_joints * (size_t)stride)
+        (palette ? palette->size() != (size_t)skin.n_joints * (size_t)stride : n_joints != skin.n_joints || !u.skin_palette.p))
         return fail(AGPT_ERR_INVALID, std::string(fn) + ": the binding does not have the mesh's counts");
     if (!u.has_skin) {
         if (const int rc = upload(u.skin_vertex_joints, skin.vertex_joints, stream)) return rc;
@@ -615,7 +756,8 @@ static int skin_on_device(const char* fn, hipStream_t stream, MeshDeviceCache& u
     }
     // room for either stride (ensure only grows: the narrow palette of a later call lands in the same allocation)
     if (const int rc = u.skin_palette.ensure((size_t)skin.n_joints * (size_t)skin_palette_stride(true))) return rc;
-    if (const int rc = upload(u.skin_palette, palette, stream)) return rc;
+    if (palette)
+        if (const int rc = upload(u.skin_palette, *palette, stream)) return rc;
     a.palette = u.skin_palette.p;
     a.stride = stride;
     a.n_joints = skin.n_joints;
@@ -627,17 +769,21 @@ static int skin_on_device(const char* fn, hipStream_t stream, MeshDeviceCache& u
     return AGPT_OK;
 }
 
-// the targets' deltas on the device (uploaded when the cache holds none), this call's active list, and the morph's share of the arguments
+// the targets' deltas on the device (uploaded when the cache holds none), this call's active list -- `active` == NULL: k_morph_active has
+// written its n_active pairs from `n_targets` weights in device memory, every target below n_targets by construction --, and the morph's
+// share of the arguments
 static int morph_on_device(const char* fn, hipStream_t stream, MeshDeviceCache& u, const HostMesh& mesh, const MorphTargets& morph,
-                           const std::vector<MorphActive>& active, MorphArgs& m) {
+                           const std::vector<MorphActive>* active, int n_targets, size_t n_active, MorphArgs& m) {
     const size_t nv = mesh.vertices.size(), nn = mesh.normals.size(), T = (size_t)morph.n_targets;
     const bool normal_deltas = nn && !morph.normal_deltas.empty();
     // what the kernel indexes with, against what it indexes
     if (T < 1 || T > (size_t)kMorphMaxTargets || morph.position_deltas.size() != T * nv * 3 ||
-        (normal_deltas && morph.normal_deltas.size() != T * nn * 3) || active.size() > T)
+        (normal_deltas && morph.normal_deltas.size() != T * nn * 3) || n_active > T ||
+        (!active && ((size_t)n_targets != T || !u.morph_active.p)))
         return fail(AGPT_ERR_INVALID, std::string(fn) + ": the targets do not have the mesh's counts");
-    for (const MorphActive& t : active)
-        if (t.target < 0 || (size_t)t.target >= T) return fail(AGPT_ERR_INVALID, std::string(fn) + ": an active target outside the targets");
+    for (size_t k = 0; active && k < active->size(); k++)
+        if ((*active)[k].target < 0 || (size_t)(*active)[k].target >= T)
+            return fail(AGPT_ERR_INVALID, std::string(fn) + ": an active target outside the targets");
     if (!u.has_morph) {
         if (const int rc = upload(u.morph_position_deltas, morph.position_deltas, stream)) return rc;
         if (normal_deltas)
@@ -646,9 +792,45 @@ static int morph_on_device(const char* fn, hipStream_t stream, MeshDeviceCache& 
         u.has_morph = true;
     }
     if (const int rc = u.morph_active.ensure(T)) return rc;   // (room for every target: the list of a later frame may be longer)
-    if (const int rc = upload(u.morph_active, active, stream)) return rc;
+    if (active)
+        if (const int rc = upload(u.morph_active, *active, stream)) return rc;
     m.position_deltas = u.morph_position_deltas.p;
     m.normal_deltas = normal_deltas ? u.morph_normal_deltas.p : nullptr;
+    return AGPT_OK;
+}
+
+int MeshUpdate::device_inputs(hipStream_t stream, const HostMesh& mesh, const DeformRequest& rq) {
+    const std::string f = std::string(rq.fn) + ": ";
+    if (!rq.status || (!rq.joints16_dev && !rq.weights_dev)) return fail(AGPT_ERR_INVALID, f + "no device inputs, or nowhere to put their status");
+    if ((rq.joints16_dev && rq.n_joints != skin_.n_joints) || (rq.weights_dev && rq.n_targets != morph_.n_targets))
+        return fail(AGPT_ERR_INVALID, f + "the device inputs do not have the binding's or the targets' counts");
+    if (const int rc = ensure_cache(stream, mesh)) return rc;
+    MeshDeviceCache& u = *dev_;
+    static_assert(sizeof(DeviceInputStatus) == 5 * sizeof(uint32_t), "DeviceInputStatus is the five words of the download");
+    if (!u.input_status.p) u.joint_words_clean = false;
+    if (const int rc = u.input_status.ensure(5)) return rc;
+    if (!u.input_status_host) HIP_TRY(hipHostMalloc((void**)&u.input_status_host, sizeof(DeviceInputStatus), hipHostMallocDefault));
+    if (!u.joint_words_clean) HIP_TRY(hipMemsetAsync(u.input_status.p, 0xFF, sizeof(DeviceInputStatus), stream));   // kNoItem everywhere
+    u.joint_words_clean = false;   // until they have come back clean
+    if (rq.joints16_dev) {
+        // room for either stride, as skin_on_device makes it (which then finds the allocation as it is)
+        if (const int rc = u.skin_palette.ensure((size_t)rq.n_joints * (size_t)skin_palette_stride(true))) return rc;
+        if (const int rc = launch_pack_palette(stream, rq.joints16_dev, rq.n_joints, !mesh.normals.empty() && rq.with_normals, u.skin_palette.p,
+                                               u.input_status.p))
+            return rc;
+    }
+    if (rq.weights_dev) {
+        if (const int rc = u.morph_active.ensure((size_t)rq.n_targets)) return rc;
+        if (const int rc = launch_morph_active(stream, rq.weights_dev, rq.n_targets, u.morph_active.p, u.input_status.p + 3)) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(u.input_status_host, u.input_status.p, sizeof(DeviceInputStatus), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    std::memcpy(rq.status, u.input_status_host, sizeof(DeviceInputStatus));
+    u.joint_words_clean = rq.status->nonfinite_joint == kNoItem && rq.status->bad_row_joint == kNoItem && rq.status->singular_joint == kNoItem;
+    if (!rq.weights_dev) {   // (k_morph_active did not run: its two words are those of an earlier call)
+        rq.status->n_active = 0;
+        rq.status->nonfinite_weight = kNoItem;
+    }
     return AGPT_OK;
 }
 
@@ -667,15 +849,19 @@ int MeshUpdate::deform(hipStream_t stream, const HostMesh& mesh, const DeformReq
         HIP_TRY(hipGetLastError());
         return AGPT_OK;
     }
-    const bool morph = rq.active != nullptr, skin = rq.palette != nullptr;
+    const bool morph = rq.active || rq.weights_dev, skin = rq.palette || rq.joints16_dev;
     if (!morph && !skin) return fail(AGPT_ERR_INVALID, std::string(rq.fn) + ": neither a matrix, a palette nor an active list");
+    // device pointers: device_inputs has left the palette and the active list in the cache, and nothing is launched on a status that is not clean
+    if ((rq.weights_dev || rq.joints16_dev) && (!rq.status || !rq.status->clean()))
+        return fail(AGPT_ERR_INVALID, std::string(rq.fn) + ": device inputs without a clean status");
+    const int n_active = rq.active ? (int)rq.active->size() : rq.weights_dev ? (int)rq.status->n_active : 0;
     MorphArgs m;
     m.position_deltas = m.normal_deltas = nullptr;
     m.s = SkinArgs();
     if (morph)
-        if (const int rc = morph_on_device(rq.fn, stream, u, mesh, morph_, *rq.active, m)) return rc;
+        if (const int rc = morph_on_device(rq.fn, stream, u, mesh, morph_, rq.active, rq.n_targets, (size_t)n_active, m)) return rc;
     if (skin)
-        if (const int rc = skin_on_device(rq.fn, stream, u, mesh, skin_, *rq.palette, rq.with_normals, m.s)) return rc;
+        if (const int rc = skin_on_device(rq.fn, stream, u, mesh, skin_, rq.palette, rq.n_joints, rq.with_normals, m.s)) return rc;
     rest_args(u, mesh, rq.with_normals, m.s);
     // 256-lane blocks on a capped grid: 4 per CU with a skin (its LDS cap), 8 for the morph alone
     const size_t cus = (size_t)(rq.num_cus > 0 ? rq.num_cus : 1);
@@ -688,9 +874,8 @@ int MeshUpdate::deform(hipStream_t stream, const HostMesh& mesh, const DeformReq
         blocks = std::max(blocks, (size_t)1);
     }
     const dim3 grid((unsigned)blocks), block(kSkinBlock);
-    const size_t lds = skin ? rq.palette->size() * sizeof(float) : 0;
+    const size_t lds = skin ? (size_t)m.s.n_joints * (size_t)m.s.stride * sizeof(float) : 0;   // the palette's bytes, host- or device-made
     const bool staged = skin && lds <= kSkinLdsBytes && !getenv("AGPT_SKIN_GLOBAL_PALETTE");
-    const int n_active = morph ? (int)rq.active->size() : 0;
     if (!morph) {
         if (staged) hipLaunchKernelGGL(k_skin_mesh<true>, grid, block, lds, stream, m.s);
         else hipLaunchKernelGGL(k_skin_mesh<false>, grid, block, 0, stream, m.s);

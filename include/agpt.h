@@ -384,10 +384,34 @@ int agpt_scene_set_mesh_skin(agpt_scene*, int prim, int influences, int n_joints
  * scene; not committed; not a mesh; unknown mode); a mesh without a skin; NULL joints16; an n_joints that is not the binding's; a
  * non-finite entry; a last row that is not exactly (0, 0, 0, 1); a joint whose determinant (agpt_transform_arrays' value) is exactly
  * 0, named in the message.  A refused call changes nothing.
- * Out of scope: sparse morph targets, tangent deltas, weights or joint matrices given in device memory, dual-quaternion blending
- * (and what agpt_scene_update_mesh_device does not cover).  Morph targets: agpt_scene_morph_mesh.  Normals recomputed from
- * the posed positions: agpt_scene_set_mesh_normals_mode. */
+ * Out of scope: sparse morph targets, tangent deltas, dual-quaternion blending (and what agpt_scene_update_mesh_device does not
+ * cover).  Morph targets: agpt_scene_morph_mesh.  Joint matrices in device memory: agpt_scene_pose_mesh_device.  Normals recomputed
+ * from the posed positions: agpt_scene_set_mesh_normals_mode. */
 int agpt_scene_pose_mesh(agpt_scene*, int prim, const float* joints16, int n_joints, int mode);
+/* The palette agpt_scene_pose_mesh forms from a frame's joint matrices, host-only like agpt_skin_arrays (no GPU, no context): per joint
+ * rows 0 .. 2 of M_j (12 floats) and, with_normals != 0, the 3x3 of n_j (9 floats, agpt_skin_arrays' arithmetic) -- palette_out
+ * receives n_joints * 21 floats, or n_joints * 13 without (the odd strides of the GPU's staging; the thirteenth float is a pad
+ * of 0).  *singular_out (may be NULL) receives the first joint whose determinant is exactly 0, or -1: such a joint is reported, not
+ * refused, and its n_j is the identity.  AGPT_ERR_INVALID (+ agpt_last_error) for NULL joints16 or palette_out, n_joints outside
+ * 1 .. 65536, a non-finite entry, a last row that is not exactly (0, 0, 0, 1), in that order and in agpt_scene_pose_mesh's words;
+ * a refused call writes nothing. */
+int agpt_skin_palette(const float* joints16, int n_joints, int with_normals, float* palette_out, int* singular_out);
+/* agpt_scene_pose_mesh with the matrices in DEVICE memory of the context's GPU (n_joints row-major 4x4, packed): the call leaves the
+ * scene byte for byte what agpt_scene_pose_mesh leaves with a host copy of them -- REFIT, REBUILD and the non-finite-position path,
+ * either normals mode, either palette route.  Nothing of the matrices crosses the bus: k_pack_palette, one lane per joint, runs
+ * agpt_skin_palette's arithmetic (one source for host and device) into the palette k_skin_mesh reads and reduces the three checks of
+ * the matrices to three words, each the lowest offending joint; those come back in one 20-byte download, and the pose is launched
+ * only when they are clean.  That is one stream round trip more than agpt_scene_pose_mesh makes.
+ *   ordering   as for agpt_scene_update_mesh_device: the matrices must be complete when the call is made, or have been produced on
+ *              the context's stream (agpt_set_stream).  The call enqueues on that stream and synchronises with it.
+ *   ownership  the caller may reuse the array when the call returns.
+ *   alignment  joints16_dev must be 16-byte aligned (the kernel reads a matrix as four 16-byte rows).
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error) for agpt_scene_pose_mesh's conditions in its order, with its messages behind this
+ * call's name -- they name the same joint: the lowest with a non-finite entry; if there is none, the lowest with a bad last row; if
+ * there is none, the lowest with a determinant of exactly 0 -- and, after the n_joints check, for a joints16_dev that is not 16-byte
+ * aligned.  A refused call changes nothing in the scene.  A pointer that is not device memory is not detected.
+ * Out of scope: a binding given in device memory; a variant without the extra round trip (the pose predicated on the status words). */
+int agpt_scene_pose_mesh_device(agpt_scene*, int prim, const float* joints16_dev, int n_joints, int mode);
 /* Morph targets (blend shapes) applied to a mesh's arrays, host-only like agpt_skin_arrays (no GPU, no context): fp32, every operation
  * rounded on its own, nothing contracted into an fma.
  *   inputs     n_targets = T (1 .. 4096) targets and T weights.  Target t has one position delta per vertex and, optionally, one normal
@@ -435,10 +459,28 @@ int agpt_scene_set_mesh_morph_targets(agpt_scene*, int prim, int n_targets, cons
  * scene; not committed; not a mesh; unknown mode); a mesh without morph targets; NULL weights; an n_targets that is not the one the
  * targets were set with; a weight that is not finite; then, with joints16, agpt_scene_pose_mesh's remaining checks in its order (a mesh
  * without a skin; n_joints; a non-finite entry; a last row; a singular joint).  A refused call changes nothing.
- * Out of scope: sparse targets (a delta for every item of every target is stored), tangent deltas, weights or joint matrices given in
- * device memory (and what agpt_scene_update_mesh_device does not cover).  Normals recomputed from the morphed
- * positions (glTF's advice for targets without normal deltas): agpt_scene_set_mesh_normals_mode. */
+ * Out of scope: sparse targets (a delta for every item of every target is stored), tangent deltas (and what
+ * agpt_scene_update_mesh_device does not cover).  Weights and joint matrices in device memory: agpt_scene_morph_mesh_device.  Normals
+ * recomputed from the morphed positions (glTF's advice for targets without normal deltas): agpt_scene_set_mesh_normals_mode. */
 int agpt_scene_morph_mesh(agpt_scene*, int prim, const float* weights, int n_targets, const float* joints16, int n_joints, int mode);
+/* The active list agpt_scene_morph_mesh forms from a frame's weights, host-only like agpt_morph_arrays (no GPU, no context): the
+ * (target, weight) pairs of the weights that are not 0 (either sign of zero is skipped), in ascending target order.  targets_out and
+ * weights_out have room for n_targets entries; *n_active_out receives the number written.  AGPT_ERR_INVALID (+ agpt_last_error) for a
+ * NULL argument, n_targets outside 1 .. 4096, a weight that is not finite (agpt_morph_arrays' message); a refused call writes nothing. */
+int agpt_morph_active(const float* weights, int n_targets, int32_t* targets_out, float* weights_out, int* n_active_out);
+/* agpt_scene_morph_mesh with the weights and, for the fused call, the joint matrices in DEVICE memory of the context's GPU (joints16_dev
+ * may be NULL: no skin stage, n_joints is ignored): the call leaves the scene byte for byte what agpt_scene_morph_mesh leaves with
+ * host copies of them, in every mode, either normals mode, either palette route and whatever AGPT_MORPH_MAX_BLOCKS says.  k_morph_active,
+ * one block, compacts the weights into agpt_morph_active's list -- a pair's place comes from ballots and popcounts, never from an
+ * atomic, so the list is in target order -- and counts it; with joints16_dev, agpt_scene_pose_mesh_device's k_pack_palette runs beside
+ * it.  The count and the status words come back in one 20-byte download, and the morph is launched only when they are clean: one
+ * stream round trip more than agpt_scene_morph_mesh makes, and nothing goes up per frame.
+ * Ordering, ownership and the alignment of joints16_dev: as for agpt_scene_pose_mesh_device; weights_dev needs the 4 bytes of a float.
+ * Returns AGPT_ERR_INVALID (+ agpt_last_error) for agpt_scene_morph_mesh's conditions in its order, with its messages behind this
+ * call's name: they name the lowest target with a non-finite weight, then agpt_scene_pose_mesh_device's joint.  A refused call
+ * changes nothing in the scene.  Out of scope: targets' deltas given in device memory; as for agpt_scene_pose_mesh_device. */
+int agpt_scene_morph_mesh_device(agpt_scene*, int prim, const float* weights_dev, int n_targets, const float* joints16_dev, int n_joints,
+                                 int mode);
 /* Smooth vertex normals from positions and topology, host-only like agpt_morph_arrays (no GPU, no context): fp32, every operation
  * rounded on its own, nothing contracted into an fma.  indices are n_indices (vertex, normal, texcoord) triplets -- corners -- as in
  * agpt_scene_add_mesh; triangle t owns the corners 3t, 3t+1, 3t+2.
@@ -980,6 +1022,15 @@ int agpt_kat_rng(agpt_ctx*, uint32_t pixel, uint32_t wh, uint32_t sample, uint32
  * for k draws u[k] -> x_out[k], pdf_out[k] */
 int agpt_kat_distribution1d(agpt_ctx*, const float* func, int n, const float* u, int k, float* cdf_out, float* func_int_out,
                             float* x_out, float* pdf_out);
+/* known-answer: k_pack_palette, the kernel agpt_scene_pose_mesh_device runs, on n_joints (1 .. 65536) HOST matrices: uploads them, runs
+ * it, downloads palette_out (agpt_skin_palette's floats) and status_out = the lowest joint with a non-finite entry, with a last row
+ * that is not (0, 0, 0, 1), with a determinant of exactly 0 (0xFFFFFFFF: none).  Nothing is refused for its contents: the palette is
+ * written whatever the status says. */
+int agpt_kat_skin_palette(agpt_ctx*, const float* joints16, int n_joints, int with_normals, float* palette_out, uint32_t status_out[3]);
+/* known-answer: k_morph_active, the kernel agpt_scene_morph_mesh_device runs, on n_targets (1 .. 4096) HOST weights: status_out =
+ * (the number of pairs, the lowest target with a non-finite weight or 0xFFFFFFFF), targets_out / weights_out (room for n_targets) the
+ * pairs -- agpt_morph_active's for finite weights. */
+int agpt_kat_morph_active(agpt_ctx*, const float* weights, int n_targets, int32_t* targets_out, float* weights_out, uint32_t status_out[2]);
 
 #ifdef __cplusplus
 }

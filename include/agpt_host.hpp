@@ -265,6 +265,12 @@ public:
     void PoseMesh(int prim, const std::vector<float>& joints16, MeshUpdate mode = MeshUpdate::Refit) {
         check(agpt_scene_pose_mesh(h_, prim, joints16.data(), (int)(joints16.size() / 16), (int)mode), "agpt_scene_pose_mesh");
     }
+    // PoseMesh for an animation system that leaves its joint matrices on the GPU (agpt_scene_pose_mesh_device): n_joints row-major mat4
+    // in device memory, 16-byte aligned, complete or produced on the context's stream; the GPU forms the palette and checks the matrices,
+    // nothing of them crosses the bus, and the same bytes result.
+    void PoseMeshDevice(int prim, const float* joints16_dev, int n_joints, MeshUpdate mode = MeshUpdate::Refit) {
+        check(agpt_scene_pose_mesh_device(h_, prim, joints16_dev, n_joints, (int)mode), "agpt_scene_pose_mesh_device");
+    }
     // morph targets (blend shapes): SetMeshMorphTargets gives the deltas once (agpt_scene_set_mesh_morph_targets) -- target-major,
     // n_targets * n_vertices * 3 floats, and the normals' n_targets * n_normals * 3 or none --, MorphMesh the weights of a frame and,
     // for a skinned mesh, its joints (agpt_scene_morph_mesh): morph, then skin, in one kernel from the rest pose TransformMesh and
@@ -277,6 +283,12 @@ public:
         check(agpt_scene_morph_mesh(h_, prim, weights.data(), (int)weights.size(), joints16.empty() ? nullptr : joints16.data(),
                                     (int)(joints16.size() / 16), (int)mode),
               "agpt_scene_morph_mesh");
+    }
+    // MorphMesh with the frame's weights and, for a skinned mesh, its joints in device memory (agpt_scene_morph_mesh_device; joints16_dev
+    // may be NULL): the GPU compacts the weights into the active list itself.  Ordering and alignment as for PoseMeshDevice.
+    void MorphMeshDevice(int prim, const float* weights_dev, int n_targets, const float* joints16_dev = nullptr, int n_joints = 0,
+                         MeshUpdate mode = MeshUpdate::Refit) {
+        check(agpt_scene_morph_mesh_device(h_, prim, weights_dev, n_targets, joints16_dev, n_joints, (int)mode), "agpt_scene_morph_mesh_device");
     }
     // smooth vertex normals recomputed on the GPU (agpt_scene_set_mesh_normals_mode): with MeshNormals::Smooth every later UpdateMesh,
     // UpdateMeshDevice, TransformMesh, PoseMesh and MorphMesh of the mesh writes its normals from the new positions -- area-weighted face

@@ -7,6 +7,7 @@ one warm-up, and the bytes that cross PCIe per call (up / down, from the sizes; 
     python tools/mesh_update_time.py --pose [--runs 9] [--out profiles/mesh_pose_times.json]
     python tools/mesh_update_time.py --morph [--runs 9] [--out profiles/mesh_morph_times.json]
     python tools/mesh_update_time.py --normals [--runs 9] [--out profiles/mesh_normals_times.json]
+    python tools/mesh_update_time.py --device-inputs [--runs 9] [--out profiles/mesh_device_inputs_times.json]
 
 --pose times agpt_scene_pose_mesh instead (REFIT, 4 influences per vertex, 64 and 1,024 joints, the palette staged in LDS and read
 from global memory -- AGPT_SKIN_GLOBAL_PALETTE), with, in the same process on the same GPU, agpt_scene_transform_mesh and the route a
@@ -20,6 +21,10 @@ skin, and the route a host has without it: agpt_morph_arrays on the CPU, then ag
 normals (the floor) against the same call in SMOOTH mode with NULL normals, agpt_scene_morph_mesh at 16 active targets once GIVEN with
 normal deltas and once SMOOTH without, the rows taking turns in one process on the same GPU, and agpt_vertex_normals_arrays on one CPU
 thread.
+
+--device-inputs times Scene.pose_mesh (REFIT, 64 and 1,024 joints) three ways in turn -- host matrices, a torch tensor on the GPU
+(agpt_scene_pose_mesh_device), and that tensor through .cpu().numpy() and the host call, the route a torch user had before -- and
+Scene.morph_mesh at 16 of 64 targets active with host and with device weights, alone and fused with a 64-joint skin.
 
 --parent-lib TAG compares the host-pointer REFIT of this build with the build `libagpt_hip_TAG.so` of the parent commit
 (tools/build_variant.py run in a checkout of it, the file copied beside libagpt_hip.so): child processes, alternating parent / this
@@ -341,6 +346,82 @@ def normals_leg(runs):
     return result
 
 
+INPUTS_ROUNDS = 3
+INPUTS_ACTIVE = 16
+
+
+def device_inputs_leg(runs):
+    """--device-inputs: pose_mesh / morph_mesh with the frame's matrices and weights as torch tensors on the GPU (agpt_scene_pose_mesh_device,
+    agpt_scene_morph_mesh_device) against the host-array calls and against the route a torch user had before: tensor -> .cpu().numpy() ->
+    the host call"""
+    import torch
+    torch.zeros(1, device="cuda")   # torch initialises the GPU before the library does
+    result = {"runs": runs, "influences": POSE_INFLUENCES, "targets_bound": MORPH_TARGETS, "targets_active": INPUTS_ACTIVE, "morph_joints": MORPH_JOINTS,
+              "statistic": "host clock around the synchronised call, ms: median and min-max of the runs after one warm-up; all rows of a case "
+                           "from one process on one GPU; every row is %d rounds that take the rows of its group in turn (the three pose rows "
+                           "of a joint count; the four morph rows): the median of the rounds' medians, the lowest min, the highest max.  The "
+                           "context runs on the null stream, as torch's default stream does: Scene.pose_mesh synchronises it before a tensor "
+                           "is handed over.  *_device_tensor: the tensors exist before the clock starts.  *_download_and_call: the same "
+                           "tensor through .cpu().numpy() and the host call" % INPUTS_ROUNDS,
+              "cases": {}}
+    ctx = ag.Context(0)
+
+    def in_turn(ops):
+        per_op = {k: [] for k in ops}
+        for _ in range(INPUTS_ROUNDS):
+            for op, fn in ops.items():
+                per_op[op].append(timed(fn, runs))
+        return {op: median_of_rounds(rs, runs) for op, rs in per_op.items()}
+
+    for name, desc, prim in cases():
+        v, n, tris = arrays_of(desc, prim)
+        nv, nn = len(v), 0 if n is None else len(n)
+        g = desc.instantiate(ag.Scene(ctx))
+        rows = {}
+        for n_joints in (64, 1024):
+            J, W = pose_binding(v, nv, n_joints)
+            nJ, nW = pose_binding(v, nn, n_joints) if nn and nn != nv else (None, None)
+            g.set_mesh_skin(prim, J, W, nJ, nW, n_joints=n_joints)
+            palettes = [pose_palette(v, n_joints, k) for k in range(runs + 1)]
+            tensors = [torch.from_numpy(p).cuda() for p in palettes]
+            torch.cuda.synchronize()
+            got = in_turn({"refit_pose_%d_joints_host_matrices" % n_joints: lambda k: g.pose_mesh(prim, palettes[k]),
+                           "refit_pose_%d_joints_device_tensor" % n_joints: lambda k: g.pose_mesh(prim, tensors[k]),
+                           "refit_pose_%d_joints_download_and_call" % n_joints: lambda k: g.pose_mesh(prim, tensors[k].cpu().numpy())})
+            floats = n_joints * (21 if nn else 12)
+            got["refit_pose_%d_joints_host_matrices" % n_joints].update(pcie_up=4 * floats, pcie_down=36)
+            got["refit_pose_%d_joints_device_tensor" % n_joints].update(pcie_up=0, pcie_down=20 + 36)
+            got["refit_pose_%d_joints_download_and_call" % n_joints].update(pcie_up=4 * floats, pcie_down=64 * n_joints + 36)
+            rows.update(got)
+        dP = morph_deltas(v, nv, 1)
+        dN = morph_deltas(v, nn, 2) if nn else None
+        g.set_mesh_morph_targets(prim, dP, dN)
+        J, W = pose_binding(v, nv, MORPH_JOINTS)
+        nJ, nW = pose_binding(v, nn, MORPH_JOINTS) if nn and nn != nv else (None, None)
+        g.set_mesh_skin(prim, J, W, nJ, nW, n_joints=MORPH_JOINTS)
+        palettes = [pose_palette(v, MORPH_JOINTS, k) for k in range(runs + 1)]
+        ws = [morph_weights(INPUTS_ACTIVE, k) for k in range(runs + 1)]
+        tp, tw = [torch.from_numpy(p).cuda() for p in palettes], [torch.from_numpy(w).cuda() for w in ws]
+        torch.cuda.synchronize()
+        tag = "refit_morph_%d_of_%d" % (INPUTS_ACTIVE, MORPH_TARGETS)
+        got = in_turn({tag + "_host_weights": lambda k: g.morph_mesh(prim, ws[k]),
+                       tag + "_device_tensor": lambda k: g.morph_mesh(prim, tw[k]),
+                       tag + "_fused_%d_joints_host" % MORPH_JOINTS: lambda k: g.morph_mesh(prim, ws[k], palettes[k]),
+                       tag + "_fused_%d_joints_device_tensors" % MORPH_JOINTS: lambda k: g.morph_mesh(prim, tw[k], tp[k])})
+        palette_bytes = 4 * MORPH_JOINTS * (21 if nn else 12)
+        got[tag + "_host_weights"].update(pcie_up=8 * INPUTS_ACTIVE, pcie_down=36)
+        got[tag + "_device_tensor"].update(pcie_up=0, pcie_down=20 + 36)
+        got[tag + "_fused_%d_joints_host" % MORPH_JOINTS].update(pcie_up=8 * INPUTS_ACTIVE + palette_bytes, pcie_down=36)
+        got[tag + "_fused_%d_joints_device_tensors" % MORPH_JOINTS].update(pcie_up=0, pcie_down=20 + 36)
+        rows.update(got)
+        g.close()
+        result["cases"][name] = {"triangles": tris, "vertices": nv, "normals": nn, "scene_triangles": desc.n_tris, "operations": rows}
+        for k, r in rows.items():
+            print("%-16s %-52s median %9.3f ms  (%.3f .. %.3f)" % (name, k, r["median_ms"], r["min_ms"], r["max_ms"]), flush=True)
+    ctx.close()
+    return result
+
+
 def host_refit_only(runs):
     """the child of --parent-lib: the host-pointer REFIT alone, through whichever library AGPT_LIB_VARIANT names"""
     ctx = ag.Context(0)
@@ -401,6 +482,7 @@ def main():
     ap.add_argument("--pose", action="store_true", help="time agpt_scene_pose_mesh (see above) instead of the update paths")
     ap.add_argument("--morph", action="store_true", help="time agpt_scene_morph_mesh (see above) instead of the update paths")
     ap.add_argument("--normals", action="store_true", help="time the AGPT_NORMALS_SMOOTH mode (see above) instead of the update paths")
+    ap.add_argument("--device-inputs", action="store_true", help="time pose_mesh / morph_mesh with torch tensors on the GPU (see above) instead of the update paths")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.runs < 7:
@@ -417,9 +499,10 @@ def main():
         if slower:
             sys.exit("slower than the parent's spread on: %s" % ", ".join(slower))
         return
-    if a.pose or a.morph or a.normals:
-        result = normals_leg(a.runs) if a.normals else morph_leg(a.runs) if a.morph else pose_leg(a.runs)
-        default = "mesh_normals_times.json" if a.normals else "mesh_morph_times.json" if a.morph else "mesh_pose_times.json"
+    if a.pose or a.morph or a.normals or a.device_inputs:
+        result = device_inputs_leg(a.runs) if a.device_inputs else normals_leg(a.runs) if a.normals else morph_leg(a.runs) if a.morph else pose_leg(a.runs)
+        default = ("mesh_device_inputs_times.json" if a.device_inputs else "mesh_normals_times.json" if a.normals else
+                   "mesh_morph_times.json" if a.morph else "mesh_pose_times.json")
         with open(a.out or os.path.join(ROOT, "profiles", default), "w") as f:
             json.dump(result, f, indent=1)
             f.write("\n")
