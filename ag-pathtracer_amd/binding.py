@@ -48,7 +48,7 @@ EXPORTS = [
     "agpt_scene_pose_mesh_device", "agpt_scene_morph_mesh_device", "agpt_skin_palette", "agpt_morph_active", "agpt_kat_skin_palette", "agpt_kat_morph_active",
     "agpt_resolve_counts", "agpt_device_alloc", "agpt_device_free",
     "agpt_device_memset", "agpt_device_download", "agpt_device_upload", "agpt_kat_bsdf_eval",
-    "agpt_kat_bsdf_sample", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
+    "agpt_kat_bsdf_sample", "agpt_kat_env_light", "agpt_kat_normal_map", "agpt_kat_rng", "agpt_kat_distribution1d", "agpt_dbg_li_batch", "agpt_obj_load", "agpt_obj_parse", "agpt_obj_counts", "agpt_obj_get",
     "agpt_obj_free", "agpt_obj_last_error", "agpt_write_png", "agpt_write_pfm", "agpt_hdr_load", "agpt_hdr_parse", "agpt_hdr_free",
     "agpt_comm_unique_id", "agpt_comm_init", "agpt_comm_destroy", "agpt_gather_tiles", "agpt_deinterleave_tiles",
 ]
@@ -262,6 +262,7 @@ def lib():
     L.agpt_device_upload.argtypes = [vp, vp, vp, C.c_size_t]
     L.agpt_kat_bsdf_eval.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
     L.agpt_kat_bsdf_sample.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp, ip]
+    L.agpt_kat_env_light.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, C.c_int, fp, fp, fp, fp, ip]
     L.agpt_kat_rng.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, fp, C.POINTER(C.c_uint32)]
     L.agpt_kat_normal_map.argtypes = [vp, C.c_int, fp, fp, fp, C.c_float, fp]
     L.agpt_dbg_li_batch.argtypes = [vp, vp, C.c_int, fp]
@@ -1302,6 +1303,21 @@ class Scene:
                                            pdf.ctypes.data_as(fp), spec.ctypes.data_as(C.POINTER(C.c_int32))),
                "agpt_kat_bsdf_sample")
         return wi, f, pdf, spec
+
+    def env_light(self, light, d=None, u=None):
+        """agpt_kat_env_light: the device's InfiniteAreaLight functions on the map of light `light` of this scene's light list, in the
+        scene's shading arithmetic.  d[n, 3] directions, taken as given -> Le[n, 3], Pdf_Li[n]; u[k] draws -> Sample_Li's wi[k, 3],
+        pdf[k], radiance[k, 3], ok[k] (0 and zeros where it samples nothing).  Returns the six arrays in that order."""
+        d, pd = _f(np.zeros((0, 3), np.float32) if d is None else np.asarray(d).reshape(-1, 3))
+        u, pu = _f(np.zeros(0, np.float32) if u is None else np.asarray(u).reshape(-1))
+        n, k = d.shape[0], u.shape[0]
+        le, pli = np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        wi, pdf, sle, ok = np.zeros((k, 3), np.float32), np.zeros(k, np.float32), np.zeros((k, 3), np.float32), np.zeros(k, np.int32)
+        fp = C.POINTER(C.c_float)
+        P = lambda a: a.ctypes.data_as(fp) if a.size else None
+        _check(self.L.agpt_kat_env_light(self.h, int(light), n, P(d), P(le), P(pli), k, P(u), P(wi), P(pdf), P(sle),
+                                         ok.ctypes.data_as(C.POINTER(C.c_int32)) if k else None), "agpt_kat_env_light")
+        return le, pli, wi, pdf, sle, ok
 
 
 class PathTracer:

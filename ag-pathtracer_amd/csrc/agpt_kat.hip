@@ -1,6 +1,6 @@
 // agpt_kat.hip -- the known-answer entry points of include/agpt.h and their kernels: one piece of the device arithmetic each (the
-// BSDF functions, the surface reconstruction and the normal-map perturbation of agpt_shade.h, the environment map's sampler, the RNG streams), run on caller-supplied
-// cases, one lane per case.  The exact arithmetic; the fast-arithmetic BSDF kernels are compiled in their own unit
+// BSDF functions, the surface reconstruction and the normal-map perturbation of agpt_shade.h, the environment map's sampler and the environment light's three functions, the RNG streams), run on caller-supplied
+// cases, one lane per case.  The exact arithmetic; the fast-arithmetic BSDF and environment-light kernels are compiled in their own unit
 // (agpt_shade_kernels_fast.hip).
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,12 @@ __global__ void k_kat_bsdf_sample(DevScene sc, int material, int n, const float*
                                   float* __restrict__ wi3o, float* __restrict__ f3o, float* __restrict__ pdfo,
                                   int32_t* __restrict__ speco) {
     kat_bsdf_sample_lane(sc, material, n, wo3, u2, wi3o, f3o, pdfo, speco);
+}
+// agpt_kat_env_light: env_Le, env_pdf_li and env_sample_li (agpt_shade.h) on one light's map, one lane per direction or draw
+__global__ void k_kat_env_light(DevScene sc, int light, int n_dirs, const float* __restrict__ d3, float* __restrict__ le3o,
+                                float* __restrict__ pdf_li_o, int n_draws, const float* __restrict__ u, float* __restrict__ wi3o,
+                                float* __restrict__ pdfo, float* __restrict__ sle3o, int32_t* __restrict__ oko) {
+    kat_env_light_lane(sc, light, n_dirs, d3, le3o, pdf_li_o, n_draws, u, wi3o, pdfo, sle3o, oko);
 }
 // known-answer kernel: Distribution1D::SampleContinuous (env_sample_continuous) for k draws, one lane each
 // agpt_kat_normal_map: surface_apply_normal_map (agpt_shade.h) alone, one lane per item
@@ -108,6 +114,46 @@ int agpt_kat_bsdf_sample(agpt_scene* s, int material, int n, const float* wo3, c
         (rc = d_p.out(pdf_out, (size_t)n)))
         return rc;
     return d_s.out(specular_out, (size_t)n);
+}
+
+int agpt_kat_env_light(agpt_scene* s, int light, int n_dirs, const float* d3, float* le3_out, float* pdf_li_out, int n_draws, const float* u,
+                       float* wi3_out, float* pdf_out, float* sample_le3_out, int32_t* ok_out) {
+    if (!s || !s->committed || light < 0 || light >= (int)s->lights.size() || n_dirs < 0 || n_draws < 0 || n_dirs + (long long)n_draws <= 0 ||
+        n_dirs + (long long)n_draws > (1 << 28) || (n_dirs && (!d3 || !le3_out || !pdf_li_out)) ||
+        (n_draws && (!u || !wi3_out || !pdf_out || !sample_le3_out || !ok_out)))
+        return fail(AGPT_ERR_INVALID, "agpt_kat_env_light: bad argument");
+    const agpt::HostLight& hl = s->lights[light];
+    if (hl.type != AGPT_LIGHT_INFINITE_AREA || hl.env < 0 || hl.env >= (int)s->envs.size())
+        return fail(AGPT_ERR_INVALID, "agpt_kat_env_light: the light is no infinite-area light");
+    agpt_ctx* c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    DevBuf<float> d_d, d_le, d_pl, d_u, d_wi, d_p, d_sle;
+    DevBuf<int32_t> d_ok;
+    int rc;
+    if (n_dirs) {
+        if ((rc = d_d.in(d3, 3 * (size_t)n_dirs))) return rc;
+        HIP_TRY(d_le.alloc(3 * (size_t)n_dirs));
+        HIP_TRY(d_pl.alloc((size_t)n_dirs));
+    }
+    if (n_draws) {
+        if ((rc = d_u.in(u, (size_t)n_draws))) return rc;
+        HIP_TRY(d_wi.alloc(3 * (size_t)n_draws));
+        HIP_TRY(d_p.alloc((size_t)n_draws));
+        HIP_TRY(d_sle.alloc(3 * (size_t)n_draws));
+        HIP_TRY(d_ok.alloc((size_t)n_draws));
+    }
+    const int n = n_dirs + n_draws;
+    if (s->shading_arith == AGPT_SHADING_FAST)
+        agpt::launch_kat_env_light_fast(c->stream, s->dev, light, n_dirs, d_d.p, d_le.p, d_pl.p, n_draws, d_u.p, d_wi.p, d_p.p, d_sle.p, d_ok.p);
+    else
+        hipLaunchKernelGGL(k_kat_env_light, dim3((n + 63) / 64), dim3(64), 0, c->stream, s->dev, light, n_dirs, d_d.p, d_le.p, d_pl.p, n_draws,
+                           d_u.p, d_wi.p, d_p.p, d_sle.p, d_ok.p);
+    if ((rc = launched(c))) return rc;
+    if (n_dirs && ((rc = d_le.out(le3_out, 3 * (size_t)n_dirs)) || (rc = d_pl.out(pdf_li_out, (size_t)n_dirs)))) return rc;
+    if (n_draws && ((rc = d_wi.out(wi3_out, 3 * (size_t)n_draws)) || (rc = d_p.out(pdf_out, (size_t)n_draws)) ||
+                    (rc = d_sle.out(sample_le3_out, 3 * (size_t)n_draws)) || (rc = d_ok.out(ok_out, (size_t)n_draws))))
+        return rc;
+    return AGPT_OK;
 }
 
 int agpt_kat_normal_map(agpt_ctx* c, int n, const float* ns3, const float* ss3, const float* rgb3, float scale, float* ns_out3) {

@@ -717,6 +717,33 @@ __device__ __noinline__ float env_pdf_li(const DevEnv* ep, v3 wi) {
     float discrete = sh_div(e.func[y * e.width + x], e.funcInt * e.n);
     return sh_div(e.n * discrete, 2 * AGPT_PI * AGPT_PI * sinTheta);
 }
+// known-answer kernel body (agpt_kat_env_light): the three calls k_shade makes, on light `light`'s map, one lane per item -- items
+// 0 .. n_dirs are directions (Le and Pdf_Li of d as given), items n_dirs .. n_dirs + n_draws are draws (Sample_Li, then Le of the
+// normalized wi as the shadow ray carries it; a draw that samples nothing leaves zeros and ok = 0)
+__device__ __forceinline__ void kat_env_light_lane(const DevScene& sc, int light, int n_dirs, const float* __restrict__ d3,
+                                                   float* __restrict__ le3o, float* __restrict__ pdf_li_o, int n_draws,
+                                                   const float* __restrict__ u, float* __restrict__ wi3o, float* __restrict__ pdfo,
+                                                   float* __restrict__ sle3o, int32_t* __restrict__ oko) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const DevEnv* env = &sc.envs[sc.lights[light].env];
+    if (i < n_dirs) {
+        const v3 d = V3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+        const v3 L = env_Le(env, d);
+        le3o[3 * i] = L.x; le3o[3 * i + 1] = L.y; le3o[3 * i + 2] = L.z;
+        pdf_li_o[i] = env_pdf_li(env, d);
+    } else if (i < n_dirs + n_draws) {
+        const int k = i - n_dirs;
+        v3 wi = V3s(0.f), L = V3s(0.f);
+        float pdf = 0.f;
+        const bool ok = env_sample_li(env, u[k], &wi, &pdf);
+        if (ok) L = env_Le(env, normalize(wi));
+        else { wi = V3s(0.f); pdf = 0.f; }
+        wi3o[3 * k] = wi.x; wi3o[3 * k + 1] = wi.y; wi3o[3 * k + 2] = wi.z;
+        pdfo[k] = pdf;
+        sle3o[3 * k] = L.x; sle3o[3 * k + 1] = L.y; sle3o[3 * k + 2] = L.z;
+        oko[k] = ok ? 1 : 0;
+    }
+}
 
 // integrator.h:33-36
 __device__ __forceinline__ float power_heuristic(int nf, float fPdf, int ng, float gPdf) {

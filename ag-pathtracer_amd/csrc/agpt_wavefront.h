@@ -248,4 +248,7 @@ void launch_kat_bsdf_eval_fast(hipStream_t stream, const DevScene& sc, int mater
                                float* pdfo);
 void launch_kat_bsdf_sample_fast(hipStream_t stream, const DevScene& sc, int material, int n, const float* wo3, const float* u2, float* wi3o,
                                  float* f3o, float* pdfo, int32_t* speco);
+// k_kat_env_light_fast: one lane per direction (n_dirs) or draw (n_draws)
+void launch_kat_env_light_fast(hipStream_t stream, const DevScene& sc, int light, int n_dirs, const float* d3, float* le3o, float* pdf_li_o,
+                               int n_draws, const float* u, float* wi3o, float* pdfo, float* sle3o, int32_t* oko);
 }  // namespace agpt

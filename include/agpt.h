@@ -1022,6 +1022,15 @@ int agpt_kat_rng(agpt_ctx*, uint32_t pixel, uint32_t wh, uint32_t sample, uint32
  * for k draws u[k] -> x_out[k], pdf_out[k] */
 int agpt_kat_distribution1d(agpt_ctx*, const float* func, int n, const float* u, int k, float* cdf_out, float* func_int_out,
                             float* x_out, float* pdf_out);
+/* known-answer: the environment light's three device functions -- InfiniteAreaLight::Le, Pdf_Li and Sample_Li (lights.cpp:50-112), the
+ * very functions the shading kernels call -- on the map of light `light` (an index into the scene's light list), one lane per item, in
+ * the scene's shading arithmetic (agpt_scene_set_shading_arith).  HOST arrays.  n_dirs directions d3, taken as given (not normalized
+ * first; finite and not of zero length): le3_out = Le, pdf_li_out = Pdf_Li.  n_draws draws u, each the one value Sample_Li takes from the
+ * stream: wi3_out, pdf_out, sample_le3_out = the radiance it returns (Le of the normalized wi) and ok_out = 1, or zeros and ok_out = 0
+ * where it samples nothing (a texel of weight zero).  Either count may be 0, with its arrays NULL.  AGPT_ERR_INVALID for a light that is
+ * not an infinite-area light. */
+int agpt_kat_env_light(agpt_scene*, int light, int n_dirs, const float* d3, float* le3_out, float* pdf_li_out, int n_draws, const float* u,
+                       float* wi3_out, float* pdf_out, float* sample_le3_out, int32_t* ok_out);
 /* known-answer: k_pack_palette, the kernel agpt_scene_pose_mesh_device runs, on n_joints (1 .. 65536) HOST matrices: uploads them, runs
  * it, downloads palette_out (agpt_skin_palette's floats) and status_out = the lowest joint with a non-finite entry, with a last row
  * that is not (0, 0, 0, 1), with a determinant of exactly 0 (0xFFFFFFFF: none).  Nothing is refused for its contents: the palette is

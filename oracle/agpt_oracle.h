@@ -140,6 +140,17 @@ enum {
 void oracle_li_tally(const oracle_scene*, const oracle_ray* ray, uint32_t* rng, float L_out[3], oracle_stats* stats,
                      uint32_t counts[ORACLE_TALLY_COUNT]);
 
+/* Known-answer: InfiniteAreaLight::Le / Pdf_Li / Sample_Li (lights.cpp:50-112) of light `light` of the scene's list, through the
+ * functions the path tracer calls.  d3 is taken as given (Le normalizes it once).  Sample_Li runs once per draw u[i], the value its one
+ * RandomFloat() returns; ok_out[i] = 0 where it returned before writing wi and pdf (both 0 there); le3_out is what it returned.
+ * oracle_env_table copies the constructor's table (func[n], cdf[n + 1], funcInt; any may be NULL) and returns n.  All return 0 when the
+ * light is no InfiniteAreaLight. */
+int oracle_env_le(const oracle_scene*, int light, int n, const float* d3, float* rgb_out);
+int oracle_env_pdf_li(const oracle_scene*, int light, int n, const float* wi3, float* pdf_out);
+int oracle_env_sample_li(const oracle_scene*, int light, int n, const float* u, float* wi3_out, float* pdf_out, float* le3_out,
+                         int32_t* ok_out);
+int oracle_env_table(const oracle_scene*, int light, float* func_out, float* cdf_out, float* funcInt_out);
+
 /* Host-side scene prep restated for tests: TriangleMesh::CreateBackdrop (trianglemesh.cpp:232-318).
  * Output capacities: verts/normals 3*(2*(steps+5)) floats, uvs 2*(2*(steps+5)), indices 3*6*(steps+4) ints */
 void oracle_create_backdrop(const float origin[3], const float size[3], float radius, int steps, float* verts,

@@ -84,7 +84,11 @@ def lib():
     L.oracle_bounds_intersect.argtypes = [fp, fp, C.c_void_p, fp]
     L.oracle_bsdf_eval.argtypes = [C.c_void_p, C.c_int, fp, fp, fp, fp]
     L.oracle_bsdf_sample.argtypes = [C.c_void_p, C.c_int, fp, fp, fp, fp, fp, C.POINTER(C.c_int)]
-    L.oracle_camera_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_uint32), C.c_void_p]
+    L.oracle_env_le.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp]
+    L.oracle_env_pdf_li.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp]
+    L.oracle_env_sample_li.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp, fp, fp, ip]
+    L.oracle_env_table.argtypes = [C.c_void_p, C.c_int, fp, fp, fp]
+    L.oracle_camera_ray.argtypes =[C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_uint32), C.c_void_p]
     L.oracle_dbg_li.argtypes = [C.c_void_p, C.c_void_p, fp]
     L.oracle_li.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), fp, C.POINTER(Stats)]
     L.oracle_li_tally.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), fp, C.POINTER(Stats), C.POINTER(C.c_uint32)]
@@ -265,6 +269,43 @@ class OracleScene:
         self.L.oracle_bsdf_sample(self.h, material, pa, pb, wi.ctypes.data_as(C.POINTER(C.c_float)),
                                   f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(pdf), C.byref(spec))
         return wi, f, pdf.value, spec.value
+
+    def env_le(self, light, d):
+        """InfiniteAreaLight::Le of light `light` of the scene's list for directions d[n, 3], taken as given -> rgb[n, 3]."""
+        d, pd = _f(np.asarray(d).reshape(-1, 3))
+        out = np.zeros_like(d)
+        if self.L.oracle_env_le(self.h, int(light), d.shape[0], pd, out.ctypes.data_as(C.POINTER(C.c_float))) != 1:
+            raise ValueError("light %d is no InfiniteAreaLight" % light)
+        return out
+
+    def env_pdf_li(self, light, wi):
+        """InfiniteAreaLight::Pdf_Li for wi[n, 3] -> pdf[n]."""
+        wi, pw = _f(np.asarray(wi).reshape(-1, 3))
+        out = np.zeros(wi.shape[0], np.float32)
+        if self.L.oracle_env_pdf_li(self.h, int(light), wi.shape[0], pw, out.ctypes.data_as(C.POINTER(C.c_float))) != 1:
+            raise ValueError("light %d is no InfiniteAreaLight" % light)
+        return out
+
+    def env_sample_li(self, light, u):
+        """InfiniteAreaLight::Sample_Li, one call per draw u[i] -> (wi[n, 3], pdf[n], Le[n, 3], ok[n]); see agpt_oracle.h."""
+        u, pu = _f(np.asarray(u).reshape(-1))
+        n = u.shape[0]
+        fp = C.POINTER(C.c_float)
+        wi, pdf, le, ok = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        if self.L.oracle_env_sample_li(self.h, int(light), n, pu, wi.ctypes.data_as(fp), pdf.ctypes.data_as(fp), le.ctypes.data_as(fp),
+                                       ok.ctypes.data_as(C.POINTER(C.c_int32))) != 1:
+            raise ValueError("light %d is no InfiniteAreaLight" % light)
+        return wi, pdf, le, ok
+
+    def env_table(self, light):
+        """The table InfiniteAreaLight's constructor built for light `light`: (func[n], cdf[n + 1], funcInt)."""
+        n = self.L.oracle_env_table(self.h, int(light), None, None, None)
+        if n <= 0:
+            raise ValueError("light %d is no InfiniteAreaLight" % light)
+        fp = C.POINTER(C.c_float)
+        func, cdf, fi = np.zeros(n, np.float32), np.zeros(n + 1, np.float32), C.c_float(0)
+        self.L.oracle_env_table(self.h, int(light), func.ctypes.data_as(fp), cdf.ctypes.data_as(fp), C.byref(fi))
+        return func, cdf, np.float32(fi.value)
 
     def camera_ray(self, s, t, rng=0x12345678):
         r = np.zeros(1, RAY_DTYPE)

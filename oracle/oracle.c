@@ -25,6 +25,7 @@
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     uint32_t* rng;
+    const float* draw; /* known-answer calls (oracle_env_sample_li): the value every rng_float returns, instead of the stream's */
     oracle_stats st;
     uint32_t tally[ORACLE_TALLY_COUNT]; /* branch counts of this call (oracle_li_tally); nothing reads them back */
 } octx;
@@ -36,7 +37,7 @@ static inline uint32_t rng_uint(uint32_t* s) {
     *s ^= *s << 5;
     return *s;
 }
-static inline float rng_float(octx* c) { return rng_uint(c->rng) * 2.3283064365387e-10f; }
+static inline float rng_float(octx* c) { return c->draw ? *c->draw : rng_uint(c->rng) * 2.3283064365387e-10f; }
 
 uint32_t oracle_wang_hash(uint32_t s) {
     s = (s ^ 61) ^ (s >> 16);
@@ -1700,6 +1701,62 @@ void oracle_bsdf_sample(const oracle_scene* s, int material, const float wo_[3],
     wi_out[0] = wi.x; wi_out[1] = wi.y; wi_out[2] = wi.z;
     f_out[0] = f.x; f_out[1] = f.y; f_out[2] = f.z;
     *pdf_out = pdf; *specular_out = spec;
+}
+/* InfiniteAreaLight::Le / Pdf_Li / Sample_Li of light `light`, through the functions the path tracer calls (light_Le, light_pdf_li,
+ * light_sample_li); each returns 0 when that light is no InfiniteAreaLight.  Pinned to the reference's own class by
+ * tests/golden/envlight_cases.npz (oracle/ref_hotpath.cpp: ref_env_*). */
+static const Light* env_light(const oracle_scene* s, int light) {
+    if (light < 0 || light >= s->n_lights || s->lights[light].type != LIGHT_INFINITE_AREA) return NULL;
+    return &s->lights[light];
+}
+int oracle_env_le(const oracle_scene* s, int light, int n, const float* d3, float* rgb_out) {
+    const Light* l = env_light(s, light);
+    if (!l) return 0;
+    for (int i = 0; i < n; i++) {
+        f3 L = light_Le(l, F3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]));
+        rgb_out[3 * i] = L.x; rgb_out[3 * i + 1] = L.y; rgb_out[3 * i + 2] = L.z;
+    }
+    return 1;
+}
+int oracle_env_pdf_li(const oracle_scene* s, int light, int n, const float* wi3, float* pdf_out) {
+    const Light* l = env_light(s, light);
+    if (!l) return 0;
+    octx c; memset(&c, 0, sizeof(c));
+    SurfaceInteraction si; canonical_si(&si);
+    for (int i = 0; i < n; i++) pdf_out[i] = light_pdf_li(s, l, &si, F3(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]), &c);
+    return 1;
+}
+/* one call per draw u[i]; a call that returns before it writes wi and pdf is ok = 0 with wi = pdf = 0 */
+int oracle_env_sample_li(const oracle_scene* s, int light, int n, const float* u, float* wi3_out, float* pdf_out, float* le3_out,
+                         int32_t* ok_out) {
+    const Light* l = env_light(s, light);
+    if (!l) return 0;
+    const float sentinel = -12345.f;
+    SurfaceInteraction si; canonical_si(&si);
+    for (int i = 0; i < n; i++) {
+        octx c; memset(&c, 0, sizeof(c)); c.draw = &u[i];
+        f3 wi = F3s(sentinel);
+        float pdf = sentinel;
+        f2 u2 = {0, 0};
+        Ray vis; memset(&vis, 0, sizeof(vis));
+        f3 L = light_sample_li(s, l, &si, u2, &wi, &pdf, &vis, &c);
+        int ok = !(wi.x == sentinel && wi.y == sentinel && wi.z == sentinel && pdf == sentinel);
+        ok_out[i] = ok;
+        wi3_out[3 * i] = ok ? wi.x : 0.f; wi3_out[3 * i + 1] = ok ? wi.y : 0.f; wi3_out[3 * i + 2] = ok ? wi.z : 0.f;
+        pdf_out[i] = ok ? pdf : 0.f;
+        le3_out[3 * i] = L.x; le3_out[3 * i + 1] = L.y; le3_out[3 * i + 2] = L.z;
+    }
+    return 1;
+}
+/* the table InfiniteAreaLight's constructor left: func[n] (texel weight times sin(theta) of its row), cdf[n + 1]; returns n, 0 for another light */
+int oracle_env_table(const oracle_scene* s, int light, float* func_out, float* cdf_out, float* funcInt_out) {
+    const Light* l = env_light(s, light);
+    if (!l) return 0;
+    const EnvMap* e = l->env;
+    if (func_out) memcpy(func_out, e->func, sizeof(float) * (size_t)e->n);
+    if (cdf_out) memcpy(cdf_out, e->cdf, sizeof(float) * ((size_t)e->n + 1));
+    if (funcInt_out) *funcInt_out = e->funcInt;
+    return e->n;
 }
 void oracle_camera_ray(const oracle_scene* s, float sx, float ty, uint32_t* rng, oracle_ray* out) {
     octx c; memset(&c, 0, sizeof(c)); c.rng = rng;

@@ -26,6 +26,20 @@ def available():
     return os.path.exists(PATH)
 
 
+ENV_LIGHT = ("ref_env_le", "ref_env_pdf_li", "ref_env_sample_li")
+
+
+def has_env_light():
+    """The library is there and exports InfiniteAreaLight's three functions: one built from an earlier ref_hotpath.cpp does not (build
+    products are not tracked; __graft_entry__.build() rebuilds such a file where the reference is).  Read from the file, not from a
+    loaded handle: a library that was replaced on disk stays what it was in a process that has loaded it."""
+    if not available():
+        return False
+    with open(PATH, "rb") as f:
+        data = f.read()
+    return all(name.encode() + b"\0" in data for name in ENV_LIGHT)
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -55,6 +69,10 @@ def lib():
         L.ref_camera.argtypes = [fp, fp, fp, C.c_float, C.c_float, C.c_float, fp]
         L.ref_camera_rays.argtypes = [C.c_void_p, fp, C.c_int, up, C.c_void_p]
         L.ref_li.argtypes = [C.c_void_p, C.c_void_p, up, C.c_int, C.c_int, fp, up, ip, C.POINTER(C.c_longlong)]
+        if all(hasattr(L, name) for name in ENV_LIGHT):     # (absent from a library built before they were added: has_env_light)
+            L.ref_env_le.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp]
+            L.ref_env_pdf_li.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp]
+            L.ref_env_sample_li.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp, fp, fp, ip]
         _LIB = L
     return _LIB
 
@@ -260,6 +278,34 @@ class RefScene:
         rays = np.zeros(st.shape[0], RAY_DTYPE)
         self.L.ref_camera_rays(self.h, pst, st.shape[0], states.ctypes.data_as(up), rays.ctypes.data_as(C.c_void_p))
         return rays, states
+
+    def env_le(self, light, d):
+        """InfiniteAreaLight::Le of light `light` of the scene's list for directions d[n, 3], taken as given -> rgb[n, 3]."""
+        d, pd = _f(np.asarray(d).reshape(-1, 3))
+        out = np.zeros_like(d)
+        if self.L.ref_env_le(self.h, int(light), d.shape[0], pd, out.ctypes.data_as(fp)) != 1:
+            raise ValueError("light %d is no InfiniteAreaLight" % light)
+        return out
+
+    def env_pdf_li(self, light, wi):
+        """InfiniteAreaLight::Pdf_Li for wi[n, 3] -> pdf[n]."""
+        wi, pw = _f(np.asarray(wi).reshape(-1, 3))
+        out = np.zeros(wi.shape[0], np.float32)
+        if self.L.ref_env_pdf_li(self.h, int(light), wi.shape[0], pw, out.ctypes.data_as(fp)) != 1:
+            raise ValueError("light %d is no InfiniteAreaLight" % light)
+        return out
+
+    def env_sample_li(self, light, u):
+        """InfiniteAreaLight::Sample_Li, one call per draw u[i] (what its RandomFloat() returns) -> (wi[n, 3], pdf[n], Le[n, 3], ok[n]);
+        ok = 0 where the call returned before it wrote wi and pdf (both 0 there)."""
+        u, pu = _f(np.asarray(u).reshape(-1))
+        n = u.shape[0]
+        wi, pdf, le, ok = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        rc = self.L.ref_env_sample_li(self.h, int(light), n, pu, wi.ctypes.data_as(fp), pdf.ctypes.data_as(fp), le.ctypes.data_as(fp),
+                                      ok.ctypes.data_as(ip))
+        if rc != 1:
+            raise ValueError("light %d is no InfiniteAreaLight" % light if rc == 0 else "Sample_Li did not take exactly one draw")
+        return wi, pdf, le, ok
 
     def li(self, rays, states, max_depth):
         """PathTracer(max_depth).Li per ray -> (radiance[n, 3], states after, draws[n], (Scene::Intersect calls, IntersectP calls))."""

@@ -5,8 +5,10 @@
 // reflection.cpp, Intersectable.cpp, lights.cpp and trianglemesh.cpp are compiled as translation units of their own (precomp.h has no
 // include guard).  The platform headers precomp.h includes unconditionally are the empty-or-nearly-empty files of oracle/ref_standins.
 // This file only CALLS the reference's classes (DisneyMaterial, MirrorMaterial, BSDF, BVHTriMesh, Sphere, Plane, Scene, Camera,
-// PathTracer, DbgIntegrator, the lights, TriangleMesh::CreateBackdrop); it restates none of their bodies.  Where a value is a protected
-// member, a derived class with an accessor reads it.  tests/golden/make_refpin_golden.py turns its outputs into tests/golden/refpin_*.npz.
+// PathTracer, DbgIntegrator, the lights -- InfiniteAreaLight's Le, Pdf_Li and Sample_Li also one by one, ref_env_* --,
+// TriangleMesh::CreateBackdrop); it restates none of their bodies.  Where a value is a protected
+// member, a derived class with an accessor reads it.  tests/golden/make_refpin_golden.py turns its outputs into tests/golden/refpin_*.npz,
+// tests/golden/make_envlight_golden.py into tests/golden/envlight_cases.npz.
 //
 // What the harness itself supplies, because the reference gets it from files that are not compiled here:
 //   RandomUInt / RandomFloat   (template.cpp, full of GL): xorshift32 on the state the caller passes per ray, or draws from a
@@ -429,5 +431,57 @@ void ref_li(void* s_, const ref_ray* rays, const uint32_t* rng_states, int n, in
     s->scene.primitives.erase(s->scene.primitives.begin());
     calls_out[0] = counter->closest;
     calls_out[1] = counter->any;
+}
+
+// ---- InfiniteAreaLight::Le / Pdf_Li / Sample_Li of entry `light` of the scene's light list, through its public members only.  Each
+// returns 0 when that entry is no InfiniteAreaLight. ----------------------------------------------------------------------------------
+static const InfiniteAreaLight* env_light(RefScene* s, int light) {
+    if (light < 0 || light >= (int)s->scene.lights.size()) return nullptr;
+    return dynamic_cast<const InfiniteAreaLight*>(s->scene.lights[light].get());
+}
+// Le(ray) with ray.D = d as given (Ray's constructor would normalize it a first time; PathTracer::Li hands Le a ray it made itself)
+int ref_env_le(void* s_, int light, int n, const float* d3, float* rgb_out) {
+    const InfiniteAreaLight* l = env_light((RefScene*)s_, light);
+    if (!l) return 0;
+    for (int i = 0; i < n; i++) {
+        Ray ray;
+        ray.O = float3(0.f);
+        ray.D = F3(d3 + 3 * i);
+        ray.t = FLT_MAX;
+        float3 L = l->Le(ray);
+        rgb_out[3 * i] = L.x; rgb_out[3 * i + 1] = L.y; rgb_out[3 * i + 2] = L.z;
+    }
+    return 1;
+}
+int ref_env_pdf_li(void* s_, int light, int n, const float* wi3, float* pdf_out) {
+    const InfiniteAreaLight* l = env_light((RefScene*)s_, light);
+    if (!l) return 0;
+    SurfaceInteraction si;
+    for (int i = 0; i < n; i++) pdf_out[i] = l->Pdf_Li(si, F3(wi3 + 3 * i));
+    return 1;
+}
+// Sample_Li, one call per draw: u[i] is what its one RandomFloat() returns.  wi and pdf start at a sentinel; a call that leaves them
+// untouched (the return before the texel is chosen) is recorded as ok = 0 with wi = pdf = 0.  le3_out is the returned radiance.
+int ref_env_sample_li(void* s_, int light, int n, const float* u, float* wi3_out, float* pdf_out, float* le3_out, int32_t* ok_out) {
+    const InfiniteAreaLight* l = env_light((RefScene*)s_, light);
+    if (!l) return 0;
+    const float sentinel = -12345.f;
+    SurfaceInteraction ref(float3(0.f), float2(0, 0), float3(0, 0, 1), float3(1, 0, 0), float3(0, 1, 0), nullptr);
+    for (int i = 0; i < n; i++) {
+        ref_set_draws(u + i, 1);
+        float3 wi(sentinel);
+        float pdf = sentinel;
+        VisibilityTester vis;
+        float3 L = l->Sample_Li(ref, float2(0, 0), &wi, &pdf, &vis);
+        const bool ok = !(bits(wi.x) == bits(sentinel) && bits(wi.y) == bits(sentinel) && bits(wi.z) == bits(sentinel) &&
+                          bits(pdf) == bits(sentinel));
+        if (g_draws_used != 1) { ref_set_draws(nullptr, 0); return -1; }
+        ok_out[i] = ok ? 1 : 0;
+        wi3_out[3 * i] = ok ? wi.x : 0.f; wi3_out[3 * i + 1] = ok ? wi.y : 0.f; wi3_out[3 * i + 2] = ok ? wi.z : 0.f;
+        pdf_out[i] = ok ? pdf : 0.f;
+        le3_out[3 * i] = L.x; le3_out[3 * i + 1] = L.y; le3_out[3 * i + 2] = L.z;
+    }
+    ref_set_draws(nullptr, 0);
+    return 1;
 }
 }

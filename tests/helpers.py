@@ -72,6 +72,25 @@ def render(g, W, H, spp, depth=5, arith="exact"):
     return ag.PathTracer(depth).render_to_host(g, W, H, spp)
 
 
+def compare_render_with_oracle(desc, W, H, spp):
+    """a depth-5 render of desc on the GPU and on the oracle (correctly rounded trig): the same bits in every pixel, the same ray count"""
+    g = gpu_scene(desc)
+    acc, st = ag.PathTracer(5).render_to_host(g, W, H, spp)
+    g.close()
+    o = oracle_scene(desc)
+    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
+    try:
+        oacc, ost = o.render(W, H, spp, threads=8)
+    finally:
+        ob.set_trig_mode(ob.TRIG_LIBM)
+    same = np.all(acc[..., :3].view(np.uint32) == oacc[..., :3].view(np.uint32), axis=-1)
+    close = np.all(np.abs(acc[..., :3] - oacc[..., :3]) <= 1e-4 * np.abs(oacc[..., :3]) + 1e-6, axis=-1)
+    print(desc.name, "bit-exact %.5f close %.5f rays %d/%d" % (same.mean(), close.mean(), st.rays, ost.rays))
+    assert same.all()
+    assert st.rays == ost.rays
+    assert acc[..., :3].mean() > 0.01
+
+
 def scene_c1():
     return ag.scenes.scene_c1()
 

@@ -91,6 +91,10 @@ def test_invalid_arguments_return_errors():
     assert b"agpt_bvh_build" in L.agpt_last_error()
     with pytest.raises(ag.AgptError):
         ag.bvh_build(np.zeros((3, 3), np.float32), np.array([[0, 0, 0], [1, 1, 1], [7, 7, 7]], np.int32))
+    # agpt_kat_env_light(scene, light, n_dirs, d3, le3_out, pdf_li_out, n_draws, u, wi3_out, pdf_out, sample_le3_out, ok_out): no scene,
+    # no device call (a light that is no infinite-area light is refused on a live scene, tests/test_gpu_envlight_pins.py)
+    assert L.agpt_kat_env_light(None, 0, 0, None, None, None, 0, None, None, None, None, None) == -1      # AGPT_ERR_INVALID
+    assert b"agpt_kat_env_light" in L.agpt_last_error()
 
 
 def test_header_is_plain_c(tmp_path):

@@ -1,34 +1,15 @@
 """InfiniteAreaLight + Distribution1D + HDRTexture (lights.cpp:31-112, sampling.h, texture.h)
 on the GPU against the oracle.  Distribution1D is pinned against the reference's own sampling.h (tests/test_dist1d.py);
-the rest of this light (HDRTexture lookup, the spherical mapping of Sample_Li / Pdf_Li / Le) is PARITY UNPINNED against the
-reference itself: it ships no .hdr asset and no recorded output for an environment-lit scene, so the oracle side of those is
-a restatement checked only here."""
+the rest of this light (HDRTexture lookup, the spherical mapping of Sample_Li / Pdf_Li / Le) is pinned to the reference's own
+InfiniteAreaLight function by function, on maps of every shape, by tests/test_envlight_pins.py (oracle) and
+tests/test_gpu_envlight_pins.py (kernels); here whole renders of the default 128x64 map and of 8x16 maps are compared."""
 import numpy as np
 import pytest
 
 import ag_pathtracer_amd as ag
-from helpers import gpu_scene, oracle_scene
-from oracle import binding as ob
+from helpers import compare_render_with_oracle as compare
 
 pytestmark = pytest.mark.gpu
-
-
-def compare(desc, W, H, spp):
-    g = gpu_scene(desc)
-    acc, st = ag.PathTracer(5).render_to_host(g, W, H, spp)
-    g.close()
-    o = oracle_scene(desc)
-    ob.set_trig_mode(ob.TRIG_CORRECTLY_ROUNDED)
-    try:
-        oacc, ost = o.render(W, H, spp, threads=8)
-    finally:
-        ob.set_trig_mode(ob.TRIG_LIBM)
-    same = np.all(acc[..., :3].view(np.uint32) == oacc[..., :3].view(np.uint32), axis=-1)
-    close = np.all(np.abs(acc[..., :3] - oacc[..., :3]) <= 1e-4 * np.abs(oacc[..., :3]) + 1e-6, axis=-1)
-    print(desc.name, "bit-exact %.5f close %.5f rays %d/%d" % (same.mean(), close.mean(), st.rays, ost.rays))
-    assert same.all()
-    assert st.rays == ost.rays
-    assert acc[..., :3].mean() > 0.01
 
 
 def test_simple_test_scene_env_lit_with_lens():

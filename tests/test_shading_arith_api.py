@@ -18,7 +18,7 @@ b = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(b)
 HEADER = open(os.path.join(ROOT, "include", "agpt.h")).read()
 FAST_KERNELS = ["k_shade_fast<true, true>", "k_shade_fast<true, false>", "k_shade_fast<false, true>", "k_shade_fast<false, false>",
-                "k_resolve_pending_fast", "k_kat_bsdf_eval_fast", "k_kat_bsdf_sample_fast"]
+                "k_resolve_pending_fast", "k_kat_bsdf_eval_fast", "k_kat_bsdf_sample_fast", "k_kat_env_light_fast"]
 
 
 def enum_value(name):
