@@ -44,7 +44,8 @@ static bool use_fast_trace(const agpt_ctx* c, const DevScene& sc, int count) {
     return count != 1 && sc.n_prims <= 64 * AGPT_MAX_CHUNKS && !c->force_generic;
 }
 
-#define AGPT_SMALL_BATCH (48ull << 20)   // paths: below this the trace launches run the PEEK instantiation (see k_trace_fast)
+#define AGPT_SMALL_BATCH (48ull << 20)   // paths: below this the trace launches run the PEEK instantiation (see k_trace_fast);
+                                         // the default of agpt_ctx::small_batch_paths
 
 // One trace launch, said in full: where it is enqueued, what it reads and writes, and what picks its kernel instantiation.
 struct TraceLaunch {
@@ -57,7 +58,7 @@ struct TraceLaunch {
     DevHit* hits;
     uint32_t* occ;
     int count;                   // see use_fast_trace
-    bool small_batch;            // the rays of the batch number fewer than AGPT_SMALL_BATCH: k_trace_fast<PEEK>
+    bool small_batch;            // the rays of the batch number fewer than agpt_ctx::small_batch_paths: k_trace_fast<PEEK>
     bool recast;                 // the wavefront loop's own closest-hit launch (its rays carry d.w): may re-cast a ray in place, see
                                  // the retire branch of k_trace_fast
     bool coherent;               // the rays are k_generate's camera rays in sample groups of 64, a pixel per wave: k_trace_fast<COH>
@@ -193,6 +194,8 @@ int agpt_init(int device, agpt_ctx** out) {
     for (auto& st : c->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     for (auto& ev : c->aux_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     if (const char* ms = getenv("AGPT_MULTI_STREAM")) c->multi_stream = atoi(ms);
+    c->small_batch_paths = AGPT_SMALL_BATCH;
+    if (const char* sp = getenv("AGPT_SMALL_BATCH_PATHS")) c->small_batch_paths = strtoull(sp, nullptr, 10);
     HIP_TRY(hipHostMalloc((void**)&c->host_pinned, 2 * AGPT_NQUEUES * AGPT_QSTRIDE * sizeof(uint32_t)));
     const char* fg = getenv("AGPT_FORCE_GENERIC");
     c->force_generic = fg && fg[0] == '1';
@@ -387,7 +390,7 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, Wa
     const PathBuffers& pb = run.pb;
     Queues* const q = run.q;
     const int shade_grid = c->num_cus * c->shade_blocks_per_cu;
-    const bool small_batch = (unsigned long long)rcn.NP * (unsigned long long)rcn.S < AGPT_SMALL_BATCH;
+    const bool small_batch = (unsigned long long)rcn.NP * (unsigned long long)rcn.S < c->small_batch_paths;
     const bool recast = !getenv("AGPT_NO_RECAST");   // (developer knob: emitter pass-throughs through k_shade, an iteration each)
     // iteration 0 of an agpt_render batch at a sample group of 64: every wave of the closest-hit launch traces one pixel's camera rays
     // (k_trace_fast<COH>); AGPT_NO_COHERENT (developer knob) keeps the ordinary instantiation
@@ -597,7 +600,7 @@ static uint64_t samples_per_batch(const agpt_render_params* rp, uint32_t NP) {
 // n rays in ext_o / ext_d -> hit / occluded, one launch outside the wavefront loop (agpt_intersect_device, agpt_render_features)
 static void trace_rays(agpt_ctx* c, const DevScene& sc, uint32_t n, bool any_hit, int count) {
     const TraceLaunch t{c->stream, nullptr, nullptr, n, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p,
-                        count, (unsigned long long)n < AGPT_SMALL_BATCH, false, false};
+                        count, (unsigned long long)n < c->small_batch_paths, false, false};
     if (any_hit) launch_trace<1>(c, sc, t);
     else launch_trace<0>(c, sc, t);
 }

@@ -137,6 +137,7 @@ struct agpt_ctx {
     int refill_any = AGPT_REFILL_ANY;  // AGPT_REFILL_ANY: same for the any-hit / MIS-query launches
     bool mis_closest = false;    // AGPT_MIS_CLOSEST=1: trace MIS rays as full closest-hit queries (A/B, tests)
     bool force_generic = false;  // AGPT_FORCE_GENERIC=1: always use the generic k_trace (tests)
+    unsigned long long small_batch_paths = 48ull << 20;   // AGPT_SMALL_BATCH_PATHS=<n>: batches below n paths (rays) run k_trace_fast<PEEK>; 0 = none (tests)
     // per-launch HIP-event timing of the trace kernels (agpt_render_params::enable_timing)
     std::vector<hipEvent_t> tev;
     size_t tev_used = 0;

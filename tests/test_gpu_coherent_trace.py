@@ -3,8 +3,9 @@ one pixel's 64 camera rays, and a step at which all voting lanes stand at the sa
 scalar loads.  The arithmetic is the per-lane arithmetic of every other instantiation on the same fp32 operands, so nothing may change:
 each case renders once as is and once with AGPT_NO_COHERENT=1 (the ordinary instantiation) and requires the two accumulators byte for
 byte equal, the ray totals equal, and the image bit-identical to the CPU oracle's with the oracle's ray total, as test_gpu_render.py
-compares.  Films are 32x16 at 64 spp (32,768 paths; 512 waves of the coherent launch); the full-size (!PEEK) instantiations need a
-batch of 48 Mi paths and are held by bench.py's output dumps instead."""
+compares.  Films are 32x16 at 64 spp (32,768 paths; 512 waves of the coherent launch): batches this small run the PEEK instantiations.  The
+full-size (!PEEK) ones, which a batch of 48 Mi paths selects, run the same cases through check() on a context created with
+AGPT_SMALL_BATCH_PATHS=0 in test_gpu_full_batch_trace.py."""
 import functools
 
 import numpy as np
@@ -18,9 +19,10 @@ pytestmark = pytest.mark.gpu
 DEPTH = 5
 
 
-def check(monkeypatch, desc, W, H, spp, spb=0):
+def check(monkeypatch, desc, W, H, spp, spb=0, ctx=None):
+    """ctx: the context the scene is instantiated on (default: the shared one).  Returns the film and its stats."""
     oacc, ost = oracle_render(desc, W, H, spp, DEPTH)
-    g = gpu_scene(desc)
+    g = gpu_scene(desc) if ctx is None else desc.instantiate(ag.Scene(ctx))
     pt = ag.PathTracer(DEPTH)
     a, sa = pt.render_to_host(g, W, H, spp, samples_per_batch=spb)
     monkeypatch.setenv("AGPT_NO_COHERENT", "1")
@@ -35,6 +37,7 @@ def check(monkeypatch, desc, W, H, spp, spb=0):
     assert np.array_equal(bits(a[..., :3]), bits(oacc[..., :3]))
     assert sa.rays == ost.rays
     assert sa.outliers == ost.outliers
+    return a, sa
 
 
 @functools.lru_cache(maxsize=None)

@@ -10,8 +10,9 @@ from helpers import bits, gpu_scene, oracle_scene, random_rays
 pytestmark = pytest.mark.gpu
 
 
-def check_closest(desc, rays):
-    g = gpu_scene(desc)
+def check_closest(desc, rays, ctx=None):
+    """ctx: the context the scene is instantiated on (default: the shared one)"""
+    g = gpu_scene(desc) if ctx is None else desc.instantiate(ag.Scene(ctx))
     o = oracle_scene(desc)
     gh, gst = g.Intersect(rays, counters=True)   # instrumented generic kernel
     gf, _ = g.Intersect(rays)                     # production kernel
@@ -95,8 +96,8 @@ def test_empty_and_invalid_inputs():
     g.close()
 
 
-def test_more_than_64_primitives_go_through_the_top_level_tree():
-    """> 64 primitives: k_candidates + k_trace_fast<LIST> (75 primitives = candidate words for 2 chunks of the list)."""
+def scene_75_primitives():
+    """70 small meshes (with and without normals and uvs) and 5 spheres: candidate words for 2 chunks of the list"""
     rng = np.random.RandomState(5)
     d = ag.SceneDesc("many")
     m = d.add_material(ag.MAT_DIFFUSE_ONLY, [.5, .5, .5])
@@ -106,6 +107,12 @@ def test_more_than_64_primitives_go_through_the_top_level_tree():
         d.add_mesh(v, n if i % 2 else None, t if i % 3 else None, idx, m, 1)
     for i in range(5):
         d.add_sphere(rng.uniform(-4, 4, 3), 0.4, m)
+    return d
+
+
+def test_more_than_64_primitives_go_through_the_top_level_tree():
+    """> 64 primitives: k_candidates + k_trace_fast<LIST> (75 primitives = candidate words for 2 chunks of the list)."""
+    d = scene_75_primitives()
     hits = check_closest(d, random_rays(d, 150000, seed=16))
     assert hits > 20000
 
@@ -124,7 +131,8 @@ def big_leaf_mesh(clusters=3, copies=9):
     return v, idx
 
 
-def test_every_big_leaf_of_a_mesh_is_found_through_the_side_table():
+def big_leaf_case():
+    """(scene, rays): big_leaf_mesh() under 2,000 rays from either side of its plane towards points on and around the stacks"""
     v, idx = big_leaf_mesh()
     nodes, _, _ = ag.bvh_build(v, idx, 1)
     assert np.count_nonzero(nodes["count"] > 7) == 3
@@ -135,7 +143,11 @@ def test_every_big_leaf_of_a_mesh_is_found_through_the_side_table():
     rays["o"] = rng.uniform([-1, -1, 1], [8, 2, 3], (2000, 3)) * np.where(np.arange(2000) % 2, -1, 1)[:, None] ** [0, 0, 1]
     rays["d"] = rng.uniform([-.5, -.5, 0], [7.5, 1.5, 0], (2000, 3)) - rays["o"]
     rays["tmax"] = np.float32(3.402823466e+38)
-    assert check_closest(d, rays) > 300
+    return d, rays
+
+
+def test_every_big_leaf_of_a_mesh_is_found_through_the_side_table():
+    assert check_closest(*big_leaf_case()) > 300
 
 
 def test_generic_kernel_forced(monkeypatch):
@@ -200,8 +212,8 @@ def deep_mesh_scene(unit=1.0):
     return d
 
 
-def test_deep_bvh_spills_the_traversal_stack():
-    """Closest-hit / any-hit records on deep_mesh() against the oracle, then a rendered image through the same spill path."""
+def deep_mesh_case():
+    """(scene, rays): deep_mesh() alone under 20,000 rays aimed at and just past the edges of its triangles, large and small alike"""
     v, idx, scale, x = deep_mesh()
     n = len(scale)
     nodes, order, depth = ag.bvh_build(v, idx, 1)
@@ -218,7 +230,12 @@ def test_deep_bvh_spills_the_traversal_stack():
     rays["o"] = tgt + w * (np.float32([0, 0, 1.0]) + rng.normal(0, 0.3, (len(rays), 3)).astype(np.float32))
     rays["d"] = tgt - rays["o"]
     rays["tmax"] = 3.402823466e+38
-    check_closest(d, rays)
+    return d, rays
+
+
+def test_deep_bvh_spills_the_traversal_stack():
+    """Closest-hit / any-hit records on deep_mesh() against the oracle, then a rendered image through the same spill path."""
+    check_closest(*deep_mesh_case())
     # the full path on the same mesh
     from test_gpu_render import compare
     compare(deep_mesh_scene(), 64, 64, 2)

@@ -52,16 +52,22 @@ def test_gpu_2000_primitives_chunks_beyond_the_sixteenth_and_the_fallback_beyond
     assert check_closest(d, random_rays(d, 20000, seed=7)) > 3000
 
 
-@pytest.mark.gpu
-def test_gpu_render_1500_primitives_against_oracle():
-    from test_gpu_render import compare
+def lit_1500_primitives():
+    """1,500 primitives (24 chunks of the list) with an area light, a floor plane, a sky and a camera: closest-hit, any-hit and MIS
+    launches all go through k_candidates + k_trace_fast<LIST>."""
     d = _many_prims(1498, 24)
     d.add_area_light([0.0, 8.0, 0.0], 0.8, [70, 65, 60])
     d.add_plane([0, -6.5, 0], [10, 10], 0)
     d.add_uniform_infinite_light([.25, .3, .35])
     d.set_camera([0, 3, -16], [0, 0, 0], [0, 1, 0], 1.5, 50.0, 0.0)
     assert d.n_prims == 1500
-    compare(d, 48, 36, 2)
+    return d
+
+
+@pytest.mark.gpu
+def test_gpu_render_1500_primitives_against_oracle():
+    from test_gpu_render import compare
+    compare(lit_1500_primitives(), 48, 36, 2)
 
 
 @pytest.mark.gpu
