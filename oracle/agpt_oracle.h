@@ -72,6 +72,44 @@ int oracle_add_area_light(oracle_scene*, const float center[3], float radius, co
 int oracle_add_uniform_infinite_light(oracle_scene*, const float L[3]);
 /* scene.lights.push_back(make_shared<InfiniteAreaLight>(texmap)) with the HDR image given as W*H RGB floats */
 int oracle_add_infinite_area_light(oracle_scene*, const float* rgb, int width, int height);
+/* ---- image textures, material maps, samplers, normal maps -------------------------------------------------------------------
+ * Not part of the reference: a second, independent implementation of the contract in include/agpt.h (the block from
+ * agpt_scene_add_texture to agpt_scene_set_material_normal_texture), written from that text, fp32 operation by operation.  The five
+ * calls mirror agpt_scene_add_texture, agpt_scene_set_material_texture, agpt_scene_set_material_param_texture,
+ * agpt_scene_set_material_normal_texture and agpt_scene_set_texture_sampler: same arguments, texture = -1 restores the constant,
+ * 0 (or the texture id) on success, -1 for an argument that agpt.h refuses.  At a mesh hit of a material with any slot the material
+ * is rebuilt from texels by oracle_add_material's own statements and the normal map is applied before the BSDF's frame is formed; a
+ * material without slots takes the path it always took.  oracle_scene_check returns -1 where agpt_scene_commit would refuse the scene:
+ * a sphere or a plane carries a material with a slot. */
+enum { ORACLE_PARAM_ROUGHNESS = 0, ORACLE_PARAM_METALLIC = 1 };
+enum { ORACLE_FILTER_NEAREST = 0, ORACLE_FILTER_BILINEAR = 1 };
+enum { ORACLE_WRAP_REPEAT = 0, ORACLE_WRAP_CLAMP = 1, ORACLE_WRAP_MIRROR = 2 };
+int oracle_add_texture(oracle_scene*, const float* rgb, int width, int height);
+int oracle_set_material_texture(oracle_scene*, int material, int texture);
+int oracle_set_material_param_texture(oracle_scene*, int material, int param, int texture, int channel);
+int oracle_set_material_normal_texture(oracle_scene*, int material, int texture, float scale);
+int oracle_set_texture_sampler(oracle_scene*, int texture, int filter, int wrap_u, int wrap_v);
+int oracle_scene_check(const oracle_scene*);
+/* Known-answer: value(u, v) of `texture` through its sampler for n (u, v) pairs -> rgb[n * 3]; and the normal map's perturbation alone
+ * for n items (ns, ss, rgb: [n * 3]) at one scale -> the perturbed normal, ns itself where the no-op rule holds */
+void oracle_texture_value(const oracle_scene*, int texture, int n, const float* uv, float* rgb_out);
+void oracle_normal_map(int n, const float* ns, const float* ss, const float* rgb, float scale, float* out);
+/* What the textured paths of the last oracle_render (summed over its threads), oracle_li or oracle_li_tally did.  Counting changes no
+ * output, and oracle_stats keeps its layout. */
+enum {
+    ORACLE_CENSUS_LOOKUP_COLOUR = 0,    /* lookups per slot, one per slot and hit even where two slots name one image */
+    ORACLE_CENSUS_LOOKUP_ROUGHNESS,
+    ORACLE_CENSUS_LOOKUP_METALLIC,
+    ORACLE_CENSUS_LOOKUP_NORMAL,
+    ORACLE_CENSUS_BILINEAR_FRACTIONAL,  /* BILINEAR lookups with fx != 0 or fy != 0 */
+    ORACLE_CENSUS_LOOKUP_DEEP,          /* lookups at path vertex 2 or deeper (vertex 1 = the camera ray's hit) */
+    ORACLE_CENSUS_NORMAL_APPLIED,       /* normal-map perturbations applied ... */
+    ORACLE_CENSUS_NORMAL_NOOP,          /* ... and hits the no-op rule left as they were */
+    ORACLE_CENSUS_REBUILD_FEWER_LOBES,  /* per-hit Disney rebuilds with two lobes fewer than the constant material has */
+    ORACLE_CENSUS_COUNT
+};
+void oracle_census(uint64_t out[ORACLE_CENSUS_COUNT]);
+
 /* CameraDesc + Camera ctor (camera.h:17-56,77-90) */
 void oracle_set_camera(oracle_scene*, const float lookfrom[3], const float lookat[3], const float vup[3],
                        float aspect_ratio, float vfov, float aperture);

@@ -33,6 +33,13 @@ class Stats(C.Structure):
 TALLY_NAMES = ("inside_sample", "inside_pdf", "small_cone", "wide_cone", "ns_zero", "ts_zero", "degenerate_frame", "zero_area_reject",
                "sphere_pole", "light_sample_rejected", "inside_pdf_inf", "mis_light_pdf_zero", "bsdf_black_end", "shaded")
 
+# oracle_census' counters, in the order of agpt_oracle.h's ORACLE_CENSUS_* enum
+CENSUS_NAMES = ("lookup_colour", "lookup_roughness", "lookup_metallic", "lookup_normal", "bilinear_fractional", "lookup_deep",
+                "normal_applied", "normal_noop", "rebuild_fewer_lobes")
+PARAM_ROUGHNESS, PARAM_METALLIC = 0, 1
+FILTER_NEAREST, FILTER_BILINEAR = 0, 1
+WRAP_REPEAT, WRAP_CLAMP, WRAP_MIRROR = 0, 1, 2
+
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("d", np.float32, 3), ("tmax", np.float32)])
 HIT_DTYPE = np.dtype([("hit", np.int32), ("prim", np.int32), ("tri", np.int32),
                       ("t", np.float32), ("b1", np.float32), ("b2", np.float32)])
@@ -67,6 +74,15 @@ def lib():
     L.oracle_add_area_light.argtypes = [C.c_void_p, fp, C.c_float, fp]
     L.oracle_add_uniform_infinite_light.argtypes = [C.c_void_p, fp]
     L.oracle_add_infinite_area_light.argtypes = [C.c_void_p, fp, C.c_int, C.c_int]
+    L.oracle_add_texture.argtypes = [C.c_void_p, fp, C.c_int, C.c_int]
+    L.oracle_set_material_texture.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.oracle_set_material_param_texture.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.oracle_set_material_normal_texture.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
+    L.oracle_set_texture_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.oracle_scene_check.argtypes = [C.c_void_p]
+    L.oracle_texture_value.argtypes = [C.c_void_p, C.c_int, C.c_int, fp, fp]
+    L.oracle_normal_map.argtypes = [C.c_int, fp, fp, fp, C.c_float, fp]
+    L.oracle_census.argtypes = [C.POINTER(C.c_uint64)]
     L.oracle_set_camera.argtypes = [C.c_void_p, fp, fp, fp, C.c_float, C.c_float, C.c_float]
     L.oracle_set_max_depth.argtypes = [C.c_void_p, C.c_int]
     L.oracle_mesh_num_nodes.argtypes = [C.c_void_p, C.c_int]
@@ -217,6 +233,46 @@ class OracleScene:
         h, w = img.shape[0], img.shape[1]
         return self.L.oracle_add_infinite_area_light(self.h, img.ctypes.data_as(C.POINTER(C.c_float)), w, h)
 
+    # ---- image textures, material maps, samplers, normal maps: the calls SceneDesc.instantiate replays (see agpt_oracle.h) ----
+    def _checked(self, rc, what, *args):
+        if rc < 0:
+            raise ValueError("oracle: %s%r refused" % (what, args))
+        return rc
+
+    def add_texture(self, rgb):
+        img = np.ascontiguousarray(rgb, np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("oracle: add_texture wants rgb[H, W, 3]")
+        h, w = img.shape[0], img.shape[1]
+        return self._checked(self.L.oracle_add_texture(self.h, img.ctypes.data_as(C.POINTER(C.c_float)), w, h), "add_texture", w, h)
+
+    def set_material_texture(self, material, texture):
+        self._checked(self.L.oracle_set_material_texture(self.h, int(material), int(texture)), "set_material_texture", material, texture)
+
+    def set_material_param_texture(self, material, param, texture, channel=0):
+        self._checked(self.L.oracle_set_material_param_texture(self.h, int(material), int(param), int(texture), int(channel)),
+                      "set_material_param_texture", material, param, texture, channel)
+
+    def set_material_normal_texture(self, material, texture, scale=1.0):
+        self._checked(self.L.oracle_set_material_normal_texture(self.h, int(material), int(texture), float(scale)),
+                      "set_material_normal_texture", material, texture, scale)
+
+    def set_texture_sampler(self, texture, filter=0, wrap_u=0, wrap_v=0):
+        self._checked(self.L.oracle_set_texture_sampler(self.h, int(texture), int(filter), int(wrap_u), int(wrap_v)),
+                      "set_texture_sampler", texture, filter, wrap_u, wrap_v)
+
+    def commit(self):
+        """what agpt_scene_commit refuses is refused here: a material with a texture slot on a sphere or a plane"""
+        self._checked(self.L.oracle_scene_check(self.h), "commit: a textured material on a sphere or a plane; the scene")
+
+    def texture_value(self, texture, u, v):
+        """value(u, v) of `texture` through its sampler: rgb[..., 3] for u, v of one shape"""
+        u, v = np.broadcast_arrays(np.asarray(u, np.float32), np.asarray(v, np.float32))
+        uv, puv = _f(np.stack([u, v], -1).reshape(-1, 2))
+        out = np.zeros((uv.shape[0], 3), np.float32)
+        self.L.oracle_texture_value(self.h, int(texture), uv.shape[0], puv, out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out.reshape(u.shape + (3,))
+
     def set_camera(self, lookfrom, lookat, vup, aspect_ratio, vfov=45.0, aperture=0.0):
         a, pa = _f(lookfrom)
         b, pb = _f(lookat)
@@ -335,6 +391,24 @@ class OracleScene:
         for i in range(r.shape[0]):
             self.L.oracle_dbg_li(self.h, r[i:i + 1].ctypes.data_as(C.c_void_p), out[i].ctypes.data_as(C.POINTER(C.c_float)))
         return out
+
+
+def normal_map(ns, ss, rgb, scale):
+    """the normal map's perturbation alone for items ns, ss, rgb [n, 3] at one scale -> [n, 3] (ns where the no-op rule holds)"""
+    a, pa = _f(np.asarray(ns).reshape(-1, 3))
+    b, pb = _f(np.asarray(ss).reshape(-1, 3))
+    c, pc = _f(np.asarray(rgb).reshape(-1, 3))
+    assert a.shape == b.shape == c.shape
+    out = np.zeros_like(a)
+    lib().oracle_normal_map(a.shape[0], pa, pb, pc, float(scale), out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+def census():
+    """{name: count} of the texture work of the last render (or li) call; see agpt_oracle.h"""
+    out = (C.c_uint64 * len(CENSUS_NAMES))()
+    lib().oracle_census(out)
+    return {n: int(out[i]) for i, n in enumerate(CENSUS_NAMES)}
 
 
 TRIG_LIBM, TRIG_CORRECTLY_ROUNDED = 0, 1

@@ -28,8 +28,11 @@ typedef struct {
     const float* draw; /* known-answer calls (oracle_env_sample_li): the value every rng_float returns, instead of the stream's */
     oracle_stats st;
     uint32_t tally[ORACLE_TALLY_COUNT]; /* branch counts of this call (oracle_li_tally); nothing reads them back */
+    uint64_t census[ORACLE_CENSUS_COUNT]; /* texture work of this call (oracle_census); counting changes no output */
+    int vertex;                          /* the path vertex being shaded, 1 = the camera ray's hit */
 } octx;
 #define TALLY(c, which) ((c)->tally[ORACLE_TALLY_##which]++)
+#define CENSUS(c, which) do { if (c) (c)->census[ORACLE_CENSUS_##which]++; } while (0)
 
 static inline uint32_t rng_uint(uint32_t* s) {
     *s ^= *s << 13;
@@ -235,6 +238,7 @@ typedef struct {
     float b1, b2;
     struct { f3 n, dpdu, dpdv; } shading;
     BSDF bsdf;
+    Material hitmat; /* the material rebuilt at this hit from texels (include/agpt.h); bsdf.m points here then */
 } SurfaceInteraction;
 
 /* intersectable.h:66-78 */
@@ -321,8 +325,29 @@ typedef struct {
     float lens_radius, focus_dist, viewport_width, viewport_height;
 } Camera;
 
+/* image textures and the slots of a material that name them -- include/agpt.h, agpt_scene_add_texture .. agpt_scene_set_material_normal_texture;
+ * not part of the reference.  A texture is width * height RGB texels, row 0 = top, with its sampler. */
+typedef struct {
+    int width, height;
+    f3* pixels;
+    int filter, wrap_u, wrap_v;
+} Texture;
+/* what oracle_add_material was given, and the slots set since: the arguments of the per-hit rebuild */
+typedef struct {
+    int type;
+    f3 color;
+    float roughness, metallic;
+    int tex_color;               /* -1 = the constant */
+    int tex_rough, ch_rough;
+    int tex_metal, ch_metal;
+    int tex_normal;
+    float normal_scale;
+} MaterialArgs;
+
 struct oracle_scene {
     Material* materials; int n_materials;
+    MaterialArgs* matargs;       /* [n_materials] */
+    Texture* textures; int n_textures;
     Mesh* meshes; int n_meshes;
     Sphere* spheres; int n_spheres;
     Plane* planes; int n_planes;
@@ -346,6 +371,8 @@ void oracle_scene_free(oracle_scene* s) {
     }
     for (int i = 0; i < s->n_lights; i++)
         if (s->lights[i].env) { free(s->lights[i].env->pixels); free(s->lights[i].env->func); free(s->lights[i].env->cdf); free(s->lights[i].env); }
+    for (int i = 0; i < s->n_textures; i++) free(s->textures[i].pixels);
+    free(s->matargs); free(s->textures);
     free(s->materials); free(s->meshes); free(s->spheres); free(s->planes); free(s->prims); free(s->lights);
     free(s);
 }
@@ -356,12 +383,11 @@ void oracle_set_max_depth(oracle_scene* s, int d) { s->MaxDepth = d; }
 /* disney.h:23 */
 static float SchlickR0FromEta(float eta) { return ((eta - 1) * (eta - 1)) / ((eta + 1) * (eta + 1)); }
 
-/* material.h:14-49 DisneyMaterial ctor; material.h:72-77 MirrorMaterial */
-int oracle_add_material(oracle_scene* s, int type, const float color[3], float roughness, float metallic) {
-    Material* m = PUSH(s->materials, s->n_materials, Material);
+/* material.h:14-49 DisneyMaterial ctor; material.h:72-77 MirrorMaterial.  One body for oracle_add_material and for the rebuild at a hit
+ * whose colour, roughness or metallic come from a texel (si_eval_material) */
+static void material_build(Material* m, int type, f3 c, float roughness, float metallic) {
     memset(m, 0, sizeof(*m));
     m->type = type;
-    f3 c = F3(color[0], color[1], color[2]);
     if (type == ORACLE_MAT_DISNEY) {
         float metallicWeight = metallic;
         float e = 1.5f; /* material.h:65 `float eta = 1.5f` */
@@ -392,6 +418,19 @@ int oracle_add_material(oracle_scene* s, int type, const float color[3], float r
         m->has_diffuse = 1;
         m->diffuse_R = c;
     }
+}
+int oracle_add_material(oracle_scene* s, int type, const float color[3], float roughness, float metallic) {
+    s->matargs = (MaterialArgs*)realloc(s->matargs, sizeof(MaterialArgs) * (size_t)(s->n_materials + 1));
+    MaterialArgs* a = &s->matargs[s->n_materials];
+    a->type = type;
+    a->color = F3(color[0], color[1], color[2]);
+    a->roughness = roughness;
+    a->metallic = metallic;
+    a->tex_color = a->tex_rough = a->tex_metal = a->tex_normal = -1;
+    a->ch_rough = a->ch_metal = 0;
+    a->normal_scale = 1.f;
+    Material* m = PUSH(s->materials, s->n_materials, Material);
+    material_build(m, type, a->color, roughness, metallic);
     return s->n_materials - 1;
 }
 
@@ -1369,11 +1408,182 @@ static float bsdf_pdf(const BSDF* b, f3 woWorld, f3 wiWorld, int skipSpecular) {
     return matchingComps > 0 ? pdf / matchingComps : 0.f;
 }
 
-/* intersectable.h:91-96 */
-static int si_eval_material(const oracle_scene* s, SurfaceInteraction* si) {
+/* ------------------------------------------------------------------------------------------------
+ * Image textures, material maps, samplers and normal maps -- written from the contract in include/agpt.h (the block from
+ * agpt_scene_add_texture to agpt_scene_set_material_normal_texture), operation by operation in fp32.  None of this is in the
+ * reference; a material without slots never comes here.
+ * ---------------------------------------------------------------------------------------------- */
+int oracle_add_texture(oracle_scene* s, const float* rgb, int width, int height) {
+    if (!s || !rgb || width <= 0 || height <= 0) return -1;
+    Texture* t = PUSH(s->textures, s->n_textures, Texture);
+    t->width = width; t->height = height;
+    t->filter = ORACLE_FILTER_NEAREST; t->wrap_u = t->wrap_v = ORACLE_WRAP_REPEAT;
+    size_t n = (size_t)width * (size_t)height;
+    t->pixels = (f3*)malloc(sizeof(f3) * n);
+    for (size_t i = 0; i < n; i++) t->pixels[i] = F3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]);
+    return s->n_textures - 1;
+}
+int oracle_set_texture_sampler(oracle_scene* s, int texture, int filter, int wrap_u, int wrap_v) {
+    if (!s || texture < 0 || texture >= s->n_textures) return -1;
+    if (filter != ORACLE_FILTER_NEAREST && filter != ORACLE_FILTER_BILINEAR) return -1;
+    if (wrap_u < ORACLE_WRAP_REPEAT || wrap_u > ORACLE_WRAP_MIRROR || wrap_v < ORACLE_WRAP_REPEAT || wrap_v > ORACLE_WRAP_MIRROR) return -1;
+    Texture* t = &s->textures[texture];
+    t->filter = filter; t->wrap_u = wrap_u; t->wrap_v = wrap_v;
+    return 0;
+}
+int oracle_set_material_texture(oracle_scene* s, int material, int texture) {
+    if (!s || material < 0 || material >= s->n_materials || texture < -1 || texture >= s->n_textures) return -1;
+    s->matargs[material].tex_color = texture;
+    return 0;
+}
+int oracle_set_material_param_texture(oracle_scene* s, int material, int param, int texture, int channel) {
+    if (!s || material < 0 || material >= s->n_materials || texture < -1 || texture >= s->n_textures) return -1;
+    if (param != ORACLE_PARAM_ROUGHNESS && param != ORACLE_PARAM_METALLIC) return -1;
+    if (texture >= 0 && (channel < 0 || channel > 2)) return -1;
+    MaterialArgs* a = &s->matargs[material];
+    if (a->type != ORACLE_MAT_DISNEY) return -1; /* mirror and diffuse-only materials have neither parameter */
+    if (param == ORACLE_PARAM_ROUGHNESS) { a->tex_rough = texture; a->ch_rough = texture >= 0 ? channel : 0; }
+    else { a->tex_metal = texture; a->ch_metal = texture >= 0 ? channel : 0; }
+    return 0;
+}
+int oracle_set_material_normal_texture(oracle_scene* s, int material, int texture, float scale) {
+    if (!s || material < 0 || material >= s->n_materials || texture < -1 || texture >= s->n_textures) return -1;
+    if (texture >= 0 && !isfinite(scale)) return -1;
+    s->matargs[material].tex_normal = texture;
+    s->matargs[material].normal_scale = texture >= 0 ? scale : 1.f;
+    return 0;
+}
+static int material_has_slots(const MaterialArgs* a) {
+    return a->tex_color >= 0 || a->tex_rough >= 0 || a->tex_metal >= 0 || a->tex_normal >= 0;
+}
+/* what agpt_scene_commit refuses: a sphere or a plane whose material has a slot (textures are for triangle meshes) */
+int oracle_scene_check(const oracle_scene* s) {
+    for (int i = 0; i < s->n_prims; i++) {
+        const ScenePrim* p = &s->prims[i];
+        if (p->type != PRIM_MESH && p->material >= 0 && material_has_slots(&s->matargs[p->material])) return -1;
+    }
+    return 0;
+}
+
+/* (int)f of f = floorf(position), made total: a bare C cast of a float outside int's range is undefined, so the conversion saturates
+ * by comparison.  *saturated: |f| >= 2^31, or f is no number (the result is then 0) */
+static int64_t tex_float_to_int(float f, int* saturated) {
+    *saturated = !(fabsf(f) < 2147483648.f);
+    if (f != f) return 0;
+    if (f >= 2147483648.f) return INT32_MAX;
+    if (f <= -2147483648.f) return INT32_MIN;
+    return (int64_t)(int32_t)f;
+}
+/* Mod (texture.h:76-79) on a coordinate that may be INT_MAX + 1: in 64 bits, so that x0 + 1 never overflows */
+static int64_t tex_mod(int64_t a, int64_t b) {
+    int64_t result = a - (a / b) * b;
+    return (result < 0) ? result + b : result;
+}
+static int tex_wrap(int64_t x, int n, int mode) {
+    if (mode == ORACLE_WRAP_CLAMP) return (int)(x < 0 ? 0 : (x > n - 1 ? n - 1 : x));
+    if (mode == ORACLE_WRAP_MIRROR) {
+        int64_t m = tex_mod(x, 2 * (int64_t)n);
+        return (int)(m < n ? m : 2 * (int64_t)n - 1 - m);
+    }
+    return (int)tex_mod(x, n);
+}
+/* one axis: the wrapped coordinates of the two taps and the weight of the second */
+static void tex_axis(float pos, int n, int mode, int* x0, int* x1, float* f) {
+    float fl = floorf(pos);
+    int saturated;
+    int64_t i = tex_float_to_int(fl, &saturated);
+    *f = saturated ? 0.f : pos - fl;
+    *x0 = tex_wrap(i, n, mode);
+    *x1 = tex_wrap(i + 1, n, mode);
+}
+static float tex_blend(float c00, float c10, float c01, float c11, float fx, float fy) {
+    float top = c00 + fx * (c10 - c00);
+    float bot = c01 + fx * (c11 - c01);
+    return top + fy * (bot - top);
+}
+/* value(u, v) of a texture through its sampler.  c (may be NULL) takes the census of fractional bilinear weights */
+static f3 tex_value(const Texture* t, float u, float v, octx* c) {
+    if (!isfinite(u) || !isfinite(v)) return t->pixels[0];
+    float s = u * t->width - .5f;
+    float tt = v * t->height - .5f;
+    int x0, x1, y0, y1;
+    float fx, fy;
+    tex_axis(s, t->width, t->wrap_u, &x0, &x1, &fx);
+    tex_axis(tt, t->height, t->wrap_v, &y0, &y1, &fy);
+    f3 c00 = t->pixels[(size_t)y0 * t->width + x0];
+    if (t->filter == ORACLE_FILTER_NEAREST) return c00;
+    if (fx != 0 || fy != 0) CENSUS(c, BILINEAR_FRACTIONAL);
+    f3 c10 = t->pixels[(size_t)y0 * t->width + x1];
+    f3 c01 = t->pixels[(size_t)y1 * t->width + x0];
+    f3 c11 = t->pixels[(size_t)y1 * t->width + x1];
+    return F3(tex_blend(c00.x, c10.x, c01.x, c11.x, fx, fy), tex_blend(c00.y, c10.y, c01.y, c11.y, fx, fy),
+              tex_blend(c00.z, c10.z, c01.z, c11.z, fx, fy));
+}
+/* a slot's lookup at a hit, counted */
+static f3 tex_lookup(const oracle_scene* s, int texture, const SurfaceInteraction* si, octx* c, int slot) {
+    if (c) {
+        c->census[slot]++;
+        if (c->vertex >= 2) c->census[ORACLE_CENSUS_LOOKUP_DEEP]++;
+    }
+    return tex_value(&s->textures[texture], si->uv.x, si->uv.y, c);
+}
+void oracle_texture_value(const oracle_scene* s, int texture, int n, const float* uv, float* rgb_out) {
+    for (int i = 0; i < n; i++) {
+        f3 c = tex_value(&s->textures[texture], uv[2 * i], uv[2 * i + 1], NULL);
+        rgb_out[3 * i] = c.x; rgb_out[3 * i + 1] = c.y; rgb_out[3 * i + 2] = c.z;
+    }
+}
+
+/* the normal map's perturbation of the shading normal ns in the frame (ss, cross(ns, ss), ns); returns 0 and leaves *out alone where the
+ * no-op rule holds */
+static int normal_map_perturb(f3 ns, f3 ss, f3 rgb, float scale, f3* out) {
+    float tx = (2 * rgb.x - 1) * scale;
+    float ty = (2 * rgb.y - 1) * scale;
+    float tz = 2 * rgb.z - 1;
+    if (tx == 0 && ty == 0 && tz > 0) return 0;
+    f3 ts = f3_cross(ns, ss);
+    f3 m = F3(ss.x * tx + ts.x * ty + ns.x * tz, ss.y * tx + ts.y * ty + ns.y * tz, ss.z * tx + ts.z * ty + ns.z * tz);
+    if (!isfinite(m.x) || !isfinite(m.y) || !isfinite(m.z)) return 0;
+    float len2 = f3_dot(m, m);
+    if (len2 == 0) return 0;
+    *out = f3_muls(m, 1 / sqrtf(len2));
+    return 1;
+}
+void oracle_normal_map(int n, const float* ns, const float* ss, const float* rgb, float scale, float* out) {
+    for (int i = 0; i < n; i++) {
+        f3 r = F3(ns[3 * i], ns[3 * i + 1], ns[3 * i + 2]);
+        normal_map_perturb(r, F3(ss[3 * i], ss[3 * i + 1], ss[3 * i + 2]), F3(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]), scale, &r);
+        out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+    }
+}
+
+/* intersectable.h:91-96; at a mesh hit of a material with a slot, the material of include/agpt.h: colour, roughness and metallic each
+ * the texel channel or the constant, through the constructor again, and the normal map on the shading normal before the BSDF's frame */
+static int si_eval_material(const oracle_scene* s, SurfaceInteraction* si, octx* c) {
     int mat = s->prims[si->shape].material;
     if (mat < 0) return 0;
-    bsdf_init(&si->bsdf, si, &s->materials[mat]);
+    const MaterialArgs* a = &s->matargs[mat];
+    if (s->prims[si->shape].type != PRIM_MESH || !material_has_slots(a)) {
+        bsdf_init(&si->bsdf, si, &s->materials[mat]);
+        return 1;
+    }
+    f3 colour = a->color;
+    float roughness = a->roughness, metallic = a->metallic;
+    if (a->tex_color >= 0) colour = tex_lookup(s, a->tex_color, si, c, ORACLE_CENSUS_LOOKUP_COLOUR);
+    if (a->tex_rough >= 0) roughness = f3_get(tex_lookup(s, a->tex_rough, si, c, ORACLE_CENSUS_LOOKUP_ROUGHNESS), a->ch_rough);
+    if (a->tex_metal >= 0) metallic = f3_get(tex_lookup(s, a->tex_metal, si, c, ORACLE_CENSUS_LOOKUP_METALLIC), a->ch_metal);
+    material_build(&si->hitmat, a->type, colour, roughness, metallic);
+    const Material* constant = &s->materials[mat];
+    if (a->type == ORACLE_MAT_DISNEY &&
+        si->hitmat.has_diffuse + si->hitmat.has_retro + 2 == constant->has_diffuse + constant->has_retro)
+        CENSUS(c, REBUILD_FEWER_LOBES);
+    if (a->tex_normal >= 0) {
+        f3 rgb = tex_lookup(s, a->tex_normal, si, c, ORACLE_CENSUS_LOOKUP_NORMAL);
+        f3 ss = f3_normalize(si->shading.dpdu); /* the tangent bsdf_init builds its frame on */
+        if (normal_map_perturb(si->shading.n, ss, rgb, a->normal_scale, &si->shading.n)) CENSUS(c, NORMAL_APPLIED);
+        else CENSUS(c, NORMAL_NOOP);
+    }
+    bsdf_init(&si->bsdf, si, &si->hitmat);
     return 1;
 }
 /* Intersectable.cpp:5-8 + lights.h:82 */
@@ -1590,7 +1800,8 @@ static f3 PathTracer_Li(const oracle_scene* s, const Ray* r, octx* c) {
             }
         }
         if (!foundIntersection || bounces >= s->MaxDepth) break;
-        if (!si_eval_material(s, &isect)) {
+        c->vertex = bounces + 1;
+        if (!si_eval_material(s, &isect, c)) {
             ray = make_ray(f3_add(isect.p, f3_muls(ray.D, O_EPSILON)), ray.D, FLT_MAX);
             bounces--;
             continue;
@@ -1622,6 +1833,13 @@ static void stats_add(oracle_stats* a, const oracle_stats* b) {
     a->shaded_vertices += b->shaded_vertices; a->samples += b->samples; a->outliers += b->outliers;
 }
 
+/* the texture census of the last oracle_render (summed over its threads) or oracle_li / oracle_li_tally call */
+static uint64_t g_census[ORACLE_CENSUS_COUNT];
+void oracle_census(uint64_t out[ORACLE_CENSUS_COUNT]) { memcpy(out, g_census, sizeof(g_census)); }
+static void census_add(uint64_t* a, const uint64_t* b) {
+    for (int i = 0; i < ORACLE_CENSUS_COUNT; i++) a[i] += b[i];
+}
+
 static void render_sample(const oracle_scene* s, octx* c, int W, int H, int x, int y, float* accum) {
     float px = x + rng_float(c);
     float py = y + rng_float(c);
@@ -1640,6 +1858,7 @@ static void render_sample(const oracle_scene* s, octx* c, int W, int H, int x, i
 void oracle_render(const oracle_scene* s, int W, int H, int x0, int y0, int w, int h, int spp_begin, int spp_count,
                    uint32_t seed_base, int rng_mode, int threads, float* accum, oracle_stats* stats) {
     oracle_stats total; memset(&total, 0, sizeof(total));
+    uint64_t census[ORACLE_CENSUS_COUNT]; memset(census, 0, sizeof(census));
     if (rng_mode == ORACLE_RNG_GLOBAL) {
         uint32_t seed = seed_base;
         octx c; memset(&c, 0, sizeof(c)); c.rng = &seed;
@@ -1647,6 +1866,7 @@ void oracle_render(const oracle_scene* s, int W, int H, int x0, int y0, int w, i
             for (int y = y0; y < y0 + h; y++)
                 for (int x = x0; x < x0 + w; x++) render_sample(s, &c, W, H, x, y, accum);
         total = c.st;
+        census_add(census, c.census);
     } else {
         if (threads < 1) threads = 1;
 #ifdef _OPENMP
@@ -1668,9 +1888,13 @@ void oracle_render(const oracle_scene* s, int W, int H, int x0, int y0, int w, i
 #ifdef _OPENMP
 #pragma omp critical
 #endif
-            stats_add(&total, &c.st);
+            {
+                stats_add(&total, &c.st);
+                census_add(census, c.census);
+            }
         }
     }
+    memcpy(g_census, census, sizeof(census));
     if (stats) *stats = total;
 }
 
@@ -1773,6 +1997,7 @@ void oracle_li_tally(const oracle_scene* s, const oracle_ray* ray, uint32_t* rng
     L_out[0] = L.x; L_out[1] = L.y; L_out[2] = L.z;
     if (stats) *stats = c.st;
     if (counts) memcpy(counts, c.tally, sizeof(c.tally));
+    memcpy(g_census, c.census, sizeof(c.census));
 }
 void oracle_li(const oracle_scene* s, const oracle_ray* ray, uint32_t* rng, float L_out[3], oracle_stats* stats) {
     oracle_li_tally(s, ray, rng, L_out, stats, NULL);

@@ -1,9 +1,11 @@
 """Seeded random scenes: every primitive kind, material kind and light kind the path supports, mixed at random (including
 degenerate, tiny and huge triangles, overlapping spheres, multi-triangle leaves, sphere-only and light-less scenes, thin-lens
 cameras and varying MaxDepth), rendered and ray-cast on the GPU and compared with the oracle bit for bit.  A second family decorates
-such scenes with the material features the oracle does not know -- colour images, roughness / metallic maps, samplers, normal maps --
+such scenes with the material features the oracle did not know when the family was written -- colour images, roughness / metallic maps, samplers, normal maps --
 in forms that change nothing (a constant image of the material's own value, a flat normal map), so the oracle's render of the undecorated
-scene is still the reference while the shading kernels of every texturing level run, from LDS tables and from global memory."""
+scene is still the reference while the shading kernels of every texturing level run, from LDS tables and from global memory.  A third
+family decorates them with random images that do change the picture, and compares with the textured oracle's render of the same
+decorated scene."""
 import copy
 import os
 
@@ -118,6 +120,50 @@ def with_noop_textures(desc, seed):
     return d
 
 
+def with_random_textures(desc, seed):
+    """desc with, at random, on the materials that only meshes use: a random colour image, ONE random image (0, roughness, metallic)
+    serving both parameter slots of a Disney material -- its texels exact 0s and 1s among random values --, a random sampler on each
+    image, and a normal map of random tilts around (.5, .5, 1), a few texels exactly flat, at a random scale of either sign.  Images are
+    1 to 8 texels a side with values in (.05, .95).  `top` caps the features of a scene as in with_noop_textures, from the same draw."""
+    rng = np.random.RandomState(77000 + seed)
+    d = copy.copy(desc)
+    d.ops = list(desc.ops)
+    materials = [op for op in desc.ops if op[0] == "material"]
+    top = int(rng.randint(1, 5))
+    rng = np.random.RandomState(88000 + seed)
+
+    def image(texels):
+        h, w = int(rng.randint(1, 9)), int(rng.randint(1, 9))
+        t = d.add_texture(texels(h, w))
+        if top >= 3 and rng.uniform() < 0.8:
+            d.set_texture_sampler(t, int(rng.randint(2)), int(rng.randint(3)), int(rng.randint(3)))
+        return t
+
+    def colour(h, w):
+        return rng.uniform(0.05, 0.95, (h, w, 3))
+
+    def params(h, w):
+        img = rng.uniform(0.05, 0.95, (h, w, 3))
+        edge = rng.uniform(size=(h, w, 3))
+        return np.where(edge < 0.25, 0.0, np.where(edge < 0.5, 1.0, img))
+
+    def normal(h, w):
+        img = np.stack([0.5 + rng.uniform(-0.3, 0.3, (h, w)), 0.5 + rng.uniform(-0.3, 0.3, (h, w)), rng.uniform(0.7, 0.95, (h, w))], -1)
+        return np.where((rng.uniform(size=(h, w)) < 0.15)[..., None], FLAT[0, 0], img)
+
+    for m in mesh_only_materials(desc):
+        kind = materials[m][1]
+        if rng.uniform() < 0.8:
+            d.set_material_texture(m, image(colour))
+        if top >= 2 and kind == ag.MAT_DISNEY and rng.uniform() < 0.8:
+            t = image(params)
+            d.set_material_param_texture(m, ag.PARAM_ROUGHNESS, t, 1)
+            d.set_material_param_texture(m, ag.PARAM_METALLIC, t, 2)
+        if top >= 4 and rng.uniform() < 0.8:
+            d.set_material_normal_texture(m, image(normal), float(rng.choice([0.25, 1.0, 3.0, -1.0, rng.uniform(-4, 4)])))
+    return d
+
+
 def texturing_level(desc):
     """the level agpt_scene_commit derives (agpt_shade_kernels.h): the highest one a material needs"""
     sampled = {op[1] for op in desc.ops if op[0] == "texture_sampler" and tuple(op[2:]) != (0, 0, 0)}
@@ -185,6 +231,52 @@ def textured_case(seed):
     return d, plain, W, H, spp, depth, knob, variant
 
 
+def varied_case(seed):
+    """textured_case with with_random_textures in place of with_noop_textures: (decorated scene, W, H, spp, depth, knob, variant)"""
+    _, plain, W, H, spp, depth, knob, _ = textured_case(seed)
+    d = with_random_textures(plain, seed)
+    variant = (texturing_level(d), 0, int(not knob), int(any(op[0] == "env_light" for op in d.ops)))
+    return d, W, H, spp, depth, knob, variant
+
+
+def slot_counters(desc):
+    """the census counters (oracle.binding.CENSUS_NAMES) whose slot some material of desc has filled"""
+    out = set()
+    for op in desc.ops:
+        if op[0] == "material_texture" and op[2] >= 0:
+            out.add("lookup_colour")
+        elif op[0] == "material_param_texture" and op[3] >= 0:
+            out.add("lookup_roughness" if op[2] == ag.PARAM_ROUGHNESS else "lookup_metallic")
+        elif op[0] == "material_normal_texture" and op[2] >= 0:
+            out.add("lookup_normal")
+    return sorted(out)
+
+
+def test_varied_seeds_cover_levels_placements_and_env():
+    """on the CPU, for the family with images that vary: the same spread as the no-op family's, and per seed the textured oracle's
+    census -- every kind of slot the decoration fills is looked up along the seed's paths"""
+    variants = []
+    for seed in TEXTURED_SEEDS:
+        d, W, H, spp, depth, knob, variant = varied_case(seed)
+        plain = random_scene(seed)
+        kinds = [op[0] for op in d.ops]       # the plain scene's calls, then texture calls alone
+        assert kinds[:len(plain.ops)] == [op[0] for op in plain.ops] and d.n_textures >= 1
+        assert set(kinds[len(plain.ops):]) <= {"texture", "material_texture", "material_param_texture", "material_normal_texture", "texture_sampler"}
+        for op in d.ops:
+            if op[0] == "texture":
+                assert 1 <= op[1].shape[0] <= 8 and 1 <= op[1].shape[1] <= 8
+        oracle_render(d, W, H, spp, depth, seed_base=seed)
+        census = ob.census()
+        print("varied fuzz %d: variant (level, fast, lds, env) = %s, census %s" % (seed, variant, census))
+        for name in slot_counters(d):
+            assert census[name] > 0, (seed, name)
+        assert slot_counters(d)
+        variants.append(variant)
+    assert len({v[0] for v in variants}) >= 3
+    assert {v[2] for v in variants} == {0, 1}
+    assert any(v[3] for v in variants)
+
+
 def test_textured_seeds_cover_levels_placements_and_env():
     """on the CPU: what the eight cases will run (each asserts on the GPU that it does)"""
     variants = []
@@ -217,4 +309,26 @@ def test_random_textured_scene_matches_oracle(seed, monkeypatch):
     finally:
         g.close()
     assert np.array_equal(bits(gacc[..., :3]), bits(oacc[..., :3])), d.name
+    assert (gst.closest_rays, gst.anyhit_rays, gst.outliers, gst.shaded_vertices) == (ost.closest_rays, ost.anyhit_rays, ost.outliers, ost.shaded_vertices)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", TEXTURED_SEEDS)
+def test_random_varied_textured_scene_matches_oracle(seed, monkeypatch):
+    """images that vary inside triangles: the textured oracle renders the same decorated scene"""
+    d, W, H, spp, depth, knob, variant = varied_case(seed)
+    oacc, ost = oracle_render(d, W, H, spp, depth, seed_base=seed)
+    monkeypatch.delenv("AGPT_SHADE_GLOBAL_TABLES", raising=False)
+    if knob:
+        monkeypatch.setenv("AGPT_SHADE_GLOBAL_TABLES", "1")
+    g = gpu_scene(d)
+    try:
+        print("varied fuzz %d: shade variant (level, fast, lds, env) = %s, %d textures" % (seed, g.shade_variant(), d.n_textures))
+        assert g.shade_variant() == variant
+        gacc, gst = ag.PathTracer(depth).render_to_host(g, W, H, spp, seed_base=seed)
+    finally:
+        g.close()
+    same = (bits(gacc[..., :3]) == bits(oacc[..., :3])).all(-1)
+    print("varied fuzz %d: %d of %d pixels bit-identical" % (seed, same.sum(), same.size))
+    assert same.all(), d.name
     assert (gst.closest_rays, gst.anyhit_rays, gst.outliers, gst.shaded_vertices) == (ost.closest_rays, ost.anyhit_rays, ost.outliers, ost.shaded_vertices)

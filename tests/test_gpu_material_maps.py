@@ -1,5 +1,6 @@
-"""Roughness / metallic maps on the GPU (agpt_scene_set_material_param_texture).  The CPU oracle knows no textures; as for colour
-textures (test_gpu_textures.py) every test is built so that it is still the yardstick: a map of one value must equal the plain
+"""Roughness / metallic maps on the GPU (agpt_scene_set_material_param_texture).  The tests below go back to when the CPU
+oracle knew no textures (whole textured paths against it: test_gpu_textured_paths.py); as for colour textures
+(test_gpu_textures.py) every test is built so that the untextured oracle is still the yardstick: a map of one value must equal the plain
 material, a texel per mesh must equal a material per mesh -- lobe set, alpha clamp and all -- bit for bit."""
 import copy
 import re

@@ -1,5 +1,6 @@
-"""Tangent-space normal maps on the GPU (agpt_scene_set_material_normal_texture).  The CPU oracle knows neither textures nor normal
-maps; every test is built so that it is still the yardstick: the perturbation alone against the numpy model (tests/normal_map_model.py)
+"""Tangent-space normal maps on the GPU (agpt_scene_set_material_normal_texture).  The tests below go back to when the CPU
+oracle knew neither textures nor normal maps (whole textured paths against it: test_gpu_textured_paths.py); every test is built so that
+the untextured oracle is still the yardstick: the perturbation alone against the numpy model (tests/normal_map_model.py)
 bit for bit, a flat map against no map, the first-hit normal against the model fed the oracle's hits, and invariance of the render."""
 import functools
 import re

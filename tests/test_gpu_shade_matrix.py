@@ -5,7 +5,7 @@ Scene.shade_variant() (agpt_scene_shade_variant: the code begin_wavefront dispat
   A  table placement is invisible: the ladder scenes of test_gpu_shade_levels.py, with and without an environment map, rendered from
      LDS tables and again under AGPT_SHADE_GLOBAL_TABLES -- the same bytes and ray counts, in both arithmetics (every unit is built with
      -ffp-contract=off and FAST uses the same intrinsics in both instantiations).  All 40 cells.
-  B  the LDS cells of levels 1 .. 4 with and without ENV against the oracle.  The oracle knows no textures: the features are stacked
+  B  the LDS cells of levels 1 .. 4 with and without ENV against the oracle.  The oracle is given no textures: the features are stacked
      on the plateau meshes (texture_cases.py), where every lookup gives one value per mesh that the oracle's scene carries as a plain
      material -- EXACT bit for bit, FAST byte-identical to FAST on that plain scene and within the L2 rule (>= 99 % of pixels
      within 1e-3) of the oracle.  The flat normal map of those scenes cannot show that the normal table is read, so the tilted quads

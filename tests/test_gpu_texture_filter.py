@@ -1,5 +1,6 @@
-"""Texture samplers on the GPU (agpt_scene_set_texture_sampler: bilinear filtering, clamp and mirror wrap).  The CPU oracle knows no
-textures; as for the nearest lookup (test_gpu_textures.py, test_gpu_material_maps.py) every test is built so that it is still the
+"""Texture samplers on the GPU (agpt_scene_set_texture_sampler: bilinear filtering, clamp and mirror wrap).  The tests below go back
+to when the CPU oracle knew no textures (whole textured paths against it: test_gpu_textured_paths.py); as for the nearest lookup
+(test_gpu_textures.py, test_gpu_material_maps.py) every test is built so that the untextured oracle is still the
 yardstick: a constant image must equal no image, the blended value -- a pure fp32 function of (image, u, v) that the numpy model
 (tests/texture_filter_model.py) evaluates -- handed to the oracle as a plain material must render the same bits."""
 import copy

@@ -1,5 +1,6 @@
-"""Image-textured materials on the GPU (agpt_scene_add_texture / agpt_scene_set_material_texture).  The CPU oracle knows no
-textures; every test below is built so that it is still the yardstick: a texture of one colour must equal the plain material,
+"""Image-textured materials on the GPU (agpt_scene_add_texture / agpt_scene_set_material_texture).  The tests below go
+back to when the CPU oracle knew no textures (whole textured paths against it: test_gpu_textured_paths.py); every test is built so
+that the untextured oracle is still the yardstick: a texture of one colour must equal the plain material,
 a texel per mesh must equal a material per mesh, first hits are checked through the oracle's intersections and the numpy model
 of the lookup (tests/texture_model.py)."""
 import re
