@@ -23,7 +23,8 @@ SHADE_UNITS = [("", 0, 0, 4), ("_fast", 0, 1, 4), ("_textured", 1, 0, 4), ("_tex
 # against 118.1 ms at four (FAST: 111.1 against 112.8 ms; profiles/normal_map_c3.json).
 SHADE_FLAGS = ["-mllvm", "-disable-machine-licm"]
 SHADE_SOURCES = ["agpt_shade_kernels%s.hip" % suffix for suffix, _, _, _ in SHADE_UNITS]
-SOURCES = ["agpt_api.hip"] + SHADE_SOURCES + ["agpt_scene_api.hip", "agpt_kat.hip", "agpt_comm.hip", "agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip",
+# (agpt_trace_kernels.hip first: the longest job of the parallel build)
+SOURCES = ["agpt_trace_kernels.hip", "agpt_api.hip"] + SHADE_SOURCES + ["agpt_scene_api.hip", "agpt_kat.hip", "agpt_comm.hip", "agpt_bvh_device.hip", "agpt_update.hip", "agpt_adaptive.hip",
                                                "agpt_denoise.hip", "agpt_temporal.hip", "agpt_motion.hip", "agpt_analytic.hip", "agpt_host_scene.cpp", "agpt_obj.cpp", "agpt_image.cpp"]
 SOURCE_FLAGS = {src: SHADE_FLAGS + ["-DAGPT_SHADE_WAVES=%d" % waves] for src, (_, _, _, waves) in zip(SHADE_SOURCES, SHADE_UNITS)}
 # every header: an edit to any of them rebuilds the library (needs_build)

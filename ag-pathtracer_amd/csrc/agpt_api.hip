@@ -1,7 +1,8 @@
-// agpt_api.hip -- the C ABI of include/agpt.h on top of the kernels in agpt_kernels.h: the context and its path-state pool, the trace
-// launches, the wavefront loop and the entry points that run them.  The only unit that includes agpt_kernels.h (its kernels are not
-// templates: a second includer would define them again).  The other entry points: agpt_scene_api.hip, agpt_kat.hip, agpt_comm.hip, and
-// agpt_adaptive.hip / agpt_denoise.hip / agpt_temporal.hip beside their kernels.
+// agpt_api.hip -- the C ABI of include/agpt.h: the context and its path-state pool, the wavefront loop and the entry points that run
+// them.  The trace kernels are behind agpt::launch_trace (agpt_trace_kernels.hip); the small kernels of agpt_kernels.h are launched
+// from here, the only unit that includes it (they are not templates: a second includer would define them again).  The other
+// entry points: agpt_scene_api.hip, agpt_kat.hip, agpt_comm.hip, and agpt_adaptive.hip / agpt_denoise.hip / agpt_temporal.hip beside
+// their kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,112 +36,9 @@ int interleave_rows(int H, int block, int world, int rank) {
 }  // namespace agpt
 using agpt::fail;
 
-static int trace_grid(const agpt_ctx* c) { return c->num_cus * c->blocks_per_cu; }           // generic kernel
-static int fast_grid(const agpt_ctx* c) { return c->num_cus * c->fast_blocks_per_cu; }       // production kernel
-
-// count: 0 = off, 1 = reference-order counters (the generic kernel: what the reference's recursion does, equal to the
-// oracle's counters), 2 = the production kernel counting its own work (bench.py's roofline)
-static bool use_fast_trace(const agpt_ctx* c, const DevScene& sc, int count) {
-    return count != 1 && sc.n_prims <= 64 * AGPT_MAX_CHUNKS && !c->force_generic;
-}
-
-#define AGPT_SMALL_BATCH (48ull << 20)   // paths: below this the trace launches run the PEEK instantiation (see k_trace_fast);
-                                         // the default of agpt_ctx::small_batch_paths
-
-// One trace launch, said in full: where it is enqueued, what it reads and writes, and what picks its kernel instantiation.
-struct TraceLaunch {
-    hipStream_t stream;
-    const uint32_t* queue;       // path ids and their number on the device, or (nullptr, nullptr, n): the rays 0 .. n
-    const uint32_t* count_ptr;
-    uint32_t count_imm;
-    uint32_t* work_head;         // the launch's work-queue frontiers in agpt_ctx::work, zeroed by the caller
-    float4 *ro, *rd;             // (written only by a re-casting launch)
-    DevHit* hits;
-    uint32_t* occ;
-    int count;                   // see use_fast_trace
-    bool small_batch;            // the rays of the batch number fewer than agpt_ctx::small_batch_paths: k_trace_fast<PEEK>
-    bool recast;                 // the wavefront loop's own closest-hit launch (its rays carry d.w): may re-cast a ray in place, see
-                                 // the retire branch of k_trace_fast
-    bool coherent;               // the rays are k_generate's camera rays in sample groups of 64, a pixel per wave: k_trace_fast<COH>
-                                 // (run_wavefront says when; no other caller sets it)
-};
-
-template <int MODE, bool COUNT, bool SPILL, bool PEEK>
-static void launch_trace_fast(agpt_ctx* c, const DevScene& sc, const TraceLaunch& t) {
-    const dim3 block(AGPT_BLOCK), g(fast_grid(c));
-    const int refill = MODE == 0 ? c->refill : c->refill_any;
-    // (developer knob, read at each launch: AGPT_ROOT_STEP=1 makes short-list launches enter every mesh at its root pair again)
-    const bool root_entry = !getenv("AGPT_ROOT_STEP");
-    if constexpr (MODE == 0 && !COUNT) {
-        if (t.coherent && sc.n_prims <= 64) {   // (a wave takes a whole 64-ray chunk, and only when it is empty: refill = 64)
-            hipLaunchKernelGGL((k_trace_fast<0, AGPT_FAST_STACK, false, false, SPILL, PEEK, true>), g, block, 0, t.stream, sc, t.queue,
-                               t.count_ptr, t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, 64, 0u, c->spill.p,
-                               (const unsigned long long*)nullptr, (const uint32_t*)nullptr, t.recast, (const float4*)c->beta4.p, c->L4.p,
-                               root_entry);
-            return;
-        }
-    }
-    if (sc.n_prims <= 64) {
-        hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, false, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
-                           t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p,
-                           refill, 0u, c->spill.p, (const unsigned long long*)nullptr, (const uint32_t*)nullptr, MODE == 0 && t.recast,
-                           (const float4*)c->beta4.p, c->L4.p, root_entry);
-        return;
-    }
-    // more than 64 primitives: the top-level tree gives every ray its candidates (one word per chunk of 64 primitives), then
-    // ONE traversal launch walks them in list order
-    const uint32_t stride = (uint32_t)c->pool_paths;
-    if (c->cand_chunks.n < c->pool_paths || c->cand_mask.n < (size_t)((sc.n_prims + 63) / 64) * c->pool_paths) {
-        c->note(hipErrorOutOfMemory);   // (ensure_pool sizes both for the scene: not reached)
-        return;
-    }
-    hipLaunchKernelGGL((k_candidates<MODE>), dim3(c->num_cus * 8), block, 0, t.stream, sc, t.queue, t.count_ptr, t.count_imm, t.ro, t.rd,
-                       c->cand_mask.p, c->cand_chunks.p, stride);
-    hipLaunchKernelGGL((k_trace_fast<MODE, AGPT_FAST_STACK, true, COUNT, SPILL, PEEK>), g, block, 0, t.stream, sc, t.queue, t.count_ptr,
-                       t.count_imm, t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p, refill, stride, c->spill.p,
-                       (const unsigned long long*)c->cand_mask.p, (const uint32_t*)c->cand_chunks.p, false, (const float4*)nullptr,
-                       (float4*)nullptr, false);
-}
-
-template <bool ANY, bool COUNT, int DEPTH>
-static void launch_trace_generic(agpt_ctx* c, int grid, const DevScene& sc, const TraceLaunch& t) {
-    hipLaunchKernelGGL((k_trace<ANY, COUNT, DEPTH>), dim3(grid), dim3(AGPT_BLOCK), 0, t.stream, sc, t.queue, t.count_ptr, t.count_imm,
-                       t.work_head, t.ro, t.rd, t.hits, t.occ, c->counters.p);
-}
-
-// MODE 0 closest, 1 any-hit, 2 MIS query (production kernel only; the generic kernel traces MIS rays as closest hits)
-template <int MODE>
-static void launch_trace(agpt_ctx* c, const DevScene& sc, const TraceLaunch& t) {
-    constexpr bool ANY = MODE == 1;
-    if (use_fast_trace(c, sc, t.count)) {
-        const bool spill = sc.max_depth > AGPT_FAST_STACK;
-        if (spill) {
-            // one column of (max_depth - AGPT_FAST_STACK) entries per thread of the grid
-            const size_t need = (size_t)(sc.max_depth - AGPT_FAST_STACK) * (size_t)fast_grid(c) * AGPT_BLOCK;
-            if (c->spill.ensure(need) != AGPT_OK) {
-                c->note(hipErrorOutOfMemory);
-                return;
-            }
-        }
-        // <COUNT, SPILL, PEEK>: a counting launch never peeks, so six of the eight combinations exist
-        if (t.count) {
-            if (spill) launch_trace_fast<MODE, true, true, false>(c, sc, t);
-            else launch_trace_fast<MODE, true, false, false>(c, sc, t);
-        } else if (t.small_batch) {   // (see PEEK in k_trace_fast)
-            if (spill) launch_trace_fast<MODE, false, true, true>(c, sc, t);
-            else launch_trace_fast<MODE, false, false, true>(c, sc, t);
-        } else {
-            if (spill) launch_trace_fast<MODE, false, true, false>(c, sc, t);
-            else launch_trace_fast<MODE, false, false, false>(c, sc, t);
-        }
-    } else if (sc.max_depth > AGPT_STACK_DEPTH) {
-        if (t.count) launch_trace_generic<ANY, true, AGPT_STACK_DEPTH_MAX>(c, c->num_cus * 2, sc, t);
-        else launch_trace_generic<ANY, false, AGPT_STACK_DEPTH_MAX>(c, c->num_cus * 2, sc, t);
-    } else if (t.count)
-        launch_trace_generic<ANY, true, AGPT_STACK_DEPTH>(c, trace_grid(c), sc, t);
-    else
-        launch_trace_generic<ANY, false, AGPT_STACK_DEPTH>(c, trace_grid(c), sc, t);
-}
+using agpt::launch_trace;
+using agpt::TraceLaunch;
+using agpt::use_fast_trace;
 
 static void release_pool(agpt_ctx* c) {
 #define X(T, name) c->name.release();
@@ -162,13 +60,12 @@ static hipEvent_t next_event(agpt_ctx* c) {
 }
 
 // a trace launch of the wavefront loop: its asynchronous errors are noted, and with `timing` it sits between two events of `kind`
-template <int MODE>
-static void launch_trace_timed(agpt_ctx* c, bool timing, int kind, const DevScene& sc, const TraceLaunch& t) {
+static void launch_trace_timed(agpt_ctx* c, int mode, bool timing, int kind, const DevScene& sc, const TraceLaunch& t) {
     if (timing) {
         c->note(hipEventRecord(next_event(c), t.stream));
         c->tev_kind.push_back(kind);
     }
-    launch_trace<MODE>(c, sc, t);
+    launch_trace(c, mode, sc, t);
     c->note(hipGetLastError());
     if (timing) c->note(hipEventRecord(next_event(c), t.stream));
 }
@@ -194,7 +91,6 @@ int agpt_init(int device, agpt_ctx** out) {
     for (auto& st : c->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     for (auto& ev : c->aux_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     if (const char* ms = getenv("AGPT_MULTI_STREAM")) c->multi_stream = atoi(ms);
-    c->small_batch_paths = AGPT_SMALL_BATCH;
     if (const char* sp = getenv("AGPT_SMALL_BATCH_PATHS")) c->small_batch_paths = strtoull(sp, nullptr, 10);
     HIP_TRY(hipHostMalloc((void**)&c->host_pinned, 2 * AGPT_NQUEUES * AGPT_QSTRIDE * sizeof(uint32_t)));
     const char* fg = getenv("AGPT_FORCE_GENERIC");
@@ -436,12 +332,9 @@ static int run_wavefront(agpt_ctx* c, agpt_scene* s, const RenderConsts& rcn, Wa
                               run.mis_mode ? nullptr : pb.mis_hit, run.mis_mode ? pb.mis_ok : nullptr, count, small_batch, false, false};
         const TraceLaunch shadow{shadow_stream, q[cur].shadow, &QCOUNT(q[cur], 2), 0, heads[2], pb.sh_o, pb.sh_d, nullptr, pb.occluded,
                                  count, small_batch, false, false};
-        auto trace_ext = [&]() { launch_trace_timed<0>(c, run.timing, 0, s->dev, ext); };
-        auto trace_mis = [&]() {
-            if (run.mis_mode) launch_trace_timed<2>(c, run.timing, 1, s->dev, mis);
-            else launch_trace_timed<0>(c, run.timing, 1, s->dev, mis);
-        };
-        auto trace_shadow = [&]() { launch_trace_timed<1>(c, run.timing, 2, s->dev, shadow); };
+        auto trace_ext = [&]() { launch_trace_timed(c, 0, run.timing, 0, s->dev, ext); };
+        auto trace_mis = [&]() { launch_trace_timed(c, run.mis_mode ? 2 : 0, run.timing, 1, s->dev, mis); };
+        auto trace_shadow = [&]() { launch_trace_timed(c, 1, run.timing, 2, s->dev, shadow); };
         if (side) {
             HIP_TRY(hipEventRecord(c->aux_ev[0], main_stream));
             HIP_TRY(hipStreamWaitEvent(mis_stream, c->aux_ev[0], 0));
@@ -598,11 +491,10 @@ static uint64_t samples_per_batch(const agpt_render_params* rp, uint32_t NP) {
 }
 
 // n rays in ext_o / ext_d -> hit / occluded, one launch outside the wavefront loop (agpt_intersect_device, agpt_render_features)
-static void trace_rays(agpt_ctx* c, const DevScene& sc, uint32_t n, bool any_hit, int count) {
+static void trace_rays(agpt_ctx* c, int mode, const DevScene& sc, uint32_t n, int count) {
     const TraceLaunch t{c->stream, nullptr, nullptr, n, c->work.p, c->ext_o.p, c->ext_d.p, c->hit.p, c->occluded.p,
                         count, (unsigned long long)n < c->small_batch_paths, false, false};
-    if (any_hit) launch_trace<1>(c, sc, t);
-    else launch_trace<0>(c, sc, t);
+    launch_trace(c, mode, sc, t);
 }
 
 int agpt_intersect_device(agpt_scene* s, const agpt_ray* d_rays, int n, agpt_hit* d_out, int any_hit, agpt_stats* stats) {
@@ -621,7 +513,7 @@ int agpt_intersect_device(agpt_scene* s, const agpt_ray* d_rays, int n, agpt_hit
     // stats requested -> the instrumented reference-order kernel (work counters); AGPT_INTERSECT_TIMING=1 (developer knob)
     // keeps the production kernel so that stats->trace_ms times it
     const int instrumented = (stats != nullptr && !getenv("AGPT_INTERSECT_TIMING")) ? 1 : 0;
-    trace_rays(c, s->dev, (uint32_t)n, any_hit != 0, instrumented);
+    trace_rays(c, any_hit ? 1 : 0, s->dev, (uint32_t)n, instrumented);
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
     hipLaunchKernelGGL(k_export_hits, blocks, dim3(AGPT_BLOCK), 0, c->stream, s->dev, c->hit.p, c->occluded.p, n, any_hit,
                        d_out);
@@ -837,7 +729,7 @@ static int render_features(const char* fn, bool motion, bool surfaces, agpt_scen
     HIP_TRY(hipMemsetAsync(c->counters.p, 0, sizeof(DevCounters), c->stream));
     HIP_TRY(hipMemsetAsync(c->work.p, 0, AGPT_FRONTIERS * AGPT_QSTRIDE * sizeof(uint32_t), c->stream));
     agpt::launch_feature_rays(c->stream, s->dev, rcn, c->ext_o.p, c->ext_d.p);
-    trace_rays(c, s->dev, NP, false, 0);
+    trace_rays(c, 0, s->dev, NP, 0);
     const agpt_scene::PositionSnapshots& ps = s->snapshots;
     if (!surfaces)
         agpt::launch_features(c->stream, s->dev, s->shade_level, rcn, s->d_colors.p, c->hit.p, c->ext_o.p, c->ext_d.p, (float4*)albedo_dev,

@@ -1,6 +1,6 @@
 // agpt_internal.h -- what the units that define the C entry points of include/agpt.h share: error reporting, the owning device
-// buffer, and the context and the scene behind the two opaque handles.  Those units are agpt_api.hip (context, pool, trace launches,
-// wavefront loop, renderers), agpt_scene_api.hip (scene building, commit, host BVH, mesh updates), agpt_kat.hip, agpt_comm.hip, and
+// buffer, and the context and the scene behind the two opaque handles.  Those units are agpt_api.hip (context, pool, wavefront loop,
+// renderers; its trace launches go through launch_trace below, agpt_trace_kernels.hip), agpt_scene_api.hip (scene building, commit, host BVH, mesh updates), agpt_kat.hip, agpt_comm.hip, and
 // the entry points that sit beside their kernels (agpt_adaptive.hip, agpt_denoise.hip, agpt_temporal.hip, agpt_motion.hip,
 // agpt_analytic.hip).  Only .hip / .cpp units include this file, no other header does.
 #pragma once
@@ -24,7 +24,7 @@
 #ifndef AGPT_FAST_BLOCKS_PER_CU
 #define AGPT_FAST_BLOCKS_PER_CU 5
 #endif
-// the `refill` argument of k_trace_fast (agpt_kernels.h): the defaults of agpt_ctx::refill / refill_any
+// the `refill` argument of k_trace_fast (agpt_trace_kernels.h): the defaults of agpt_ctx::refill / refill_any
 #define AGPT_REFILL 20      // idle lanes that trigger a refill, closest-hit launches (tuned on C3: 16-24 equal)
 #define AGPT_REFILL_ANY 40  // same, any-hit / MIS-query launches: short traversals, refills are cheaper in bulk
 
@@ -137,7 +137,9 @@ struct agpt_ctx {
     int refill_any = AGPT_REFILL_ANY;  // AGPT_REFILL_ANY: same for the any-hit / MIS-query launches
     bool mis_closest = false;    // AGPT_MIS_CLOSEST=1: trace MIS rays as full closest-hit queries (A/B, tests)
     bool force_generic = false;  // AGPT_FORCE_GENERIC=1: always use the generic k_trace (tests)
-    unsigned long long small_batch_paths = 48ull << 20;   // AGPT_SMALL_BATCH_PATHS=<n>: batches below n paths (rays) run k_trace_fast<PEEK>; 0 = none (tests)
+    // AGPT_SMALL_BATCH_PATHS=<n>: batches below n paths (rays) run the PEEK instantiation of the trace launches (see k_trace_fast);
+    // 0 = none (tests)
+    unsigned long long small_batch_paths = 48ull << 20;
     // per-launch HIP-event timing of the trace kernels (agpt_render_params::enable_timing)
     std::vector<hipEvent_t> tev;
     size_t tev_used = 0;
@@ -154,6 +156,33 @@ struct agpt_ctx {
         return e;
     }
 };
+
+// The trace launches (agpt_trace_kernels.hip, the only unit that sees the trace kernels of agpt_trace_kernels.h).
+namespace agpt {
+// One trace launch, said in full: where it is enqueued, what it reads and writes, and what picks its kernel instantiation.
+struct TraceLaunch {
+    hipStream_t stream;
+    const uint32_t* queue;       // path ids and their number on the device, or (nullptr, nullptr, n): the rays 0 .. n
+    const uint32_t* count_ptr;
+    uint32_t count_imm;
+    uint32_t* work_head;         // the launch's work-queue frontiers in agpt_ctx::work, zeroed by the caller
+    float4 *ro, *rd;             // (written only by a re-casting launch)
+    DevHit* hits;
+    uint32_t* occ;
+    int count;                   // see use_fast_trace
+    bool small_batch;            // the rays of the batch number fewer than agpt_ctx::small_batch_paths: k_trace_fast<PEEK>
+    bool recast;                 // the wavefront loop's own closest-hit launch (its rays carry d.w): may re-cast a ray in place, see
+                                 // the retire branch of k_trace_fast
+    bool coherent;               // the rays are k_generate's camera rays in sample groups of 64, a pixel per wave: k_trace_fast<COH>
+                                 // (run_wavefront says when; no other caller sets it)
+};
+// count: 0 = off, 1 = reference-order counters (the generic kernel: what the reference's recursion does, equal to the
+// oracle's counters), 2 = the production kernel counting its own work (bench.py's roofline)
+bool use_fast_trace(const agpt_ctx* c, const DevScene& sc, int count);
+// mode 0 closest, 1 any-hit, 2 MIS query (production kernel only; the generic kernel traces MIS rays as closest hits).  Enqueues the
+// launch on t.stream; what fails on the way is left in c->note
+void launch_trace(agpt_ctx* c, int mode, const DevScene& sc, const TraceLaunch& t);
+}  // namespace agpt
 
 struct agpt_scene {
     agpt_ctx* ctx = nullptr;

@@ -1,5 +1,5 @@
 // agpt_shade_kernels.hip -- translation unit of the shading kernels (agpt_shade_kernels.h) and their host-side launchers (the unit's own come with the header; launch_shading picks the unit).
-// build.py compiles it with -mllvm -disable-machine-licm (see the header for why); the trace kernels are in agpt_api.hip,
+// build.py compiles it with -mllvm -disable-machine-licm (see the header for why); the trace kernels are in agpt_trace_kernels.hip,
 // the rest of the library in units of its own (build.py: SOURCES).
 #define AGPT_SHADE_LEVEL 0
 #define AGPT_SHADE_FAST 0

@@ -216,7 +216,7 @@ __device__ __forceinline__ bool sphere_test(const DevPrim& P, const TraceRay& r,
 
 // ---------------------------------------------------------------------------------------------------------
 // Ray admission: the conservative slab test of a fast ray (TraceRay::fast) against a box, by which the short-list prefilter
-// (k_trace_fast: pump_consume) and the top-level walk of long lists (k_candidates), agpt_kernels.h, decide what a ray may touch:
+// (k_trace_fast: pump_consume) and the top-level walk of long lists (k_candidates), agpt_trace_kernels.h, decide what a ray may touch:
 // t ~ fma(b, R, -RN(O*R)) differs from the exact quotient (b-O)/D by at most 2^-23 |t| + 2^-24 |O*R|
 // (R = RN(1/D), one rounding of O*R, one of the fma); rejecting only when tmax*(1+2e-6) + 2E < tmin with
 // E = 2^-22 max|O*R| can therefore only over-accept -- the exact Bounds::Intersect still decides where the
@@ -265,7 +265,7 @@ struct TraceCounters {
 // Decisions, visit order, accepted hits and the work counters are those of the reference's recursion.
 // (This function, the reference-order variant, runs every root-box test.  The short-list instantiations of k_trace_fast do not: a
 // fast ray enters a mesh with an interior root at the root's child pair -- a rejected root box implies two rejected children, an
-// accepted one is followed by exactly that pair at the same t -- and only slow rays and leaf roots keep the re-test; agpt_kernels.h:
+// accepted one is followed by exactly that pair at the same t -- and only slow rays and leaf roots keep the re-test; agpt_trace_kernels.h:
 // pick_next)
 template <bool ANY, bool COUNT>
 __device__ __forceinline__ bool trace_scene(const DevScene& sc, v3 O, v3 D, float tmax_in, DevHit& hit,

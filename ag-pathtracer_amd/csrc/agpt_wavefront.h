@@ -1,6 +1,6 @@
 // agpt_wavefront.h -- what the kernels of the wavefront path tracer share: the per-path state in HBM (PathBuffers), the path-id
-// queues between the kernels, the per-batch constants, the path / pixel order and the counters.  Included by agpt_kernels.h
-// (trace, generate, ...) and by agpt_shade_kernels.h (k_shade and the kernels that finish a batch: k_accumulate, k_export_li,
+// queues between the kernels, the per-batch constants, the path / pixel order and the counters.  Included by agpt_trace_kernels.h
+// (trace), agpt_kernels.h (generate, ...) and by agpt_shade_kernels.h (k_shade and the kernels that finish a batch: k_accumulate, k_export_li,
 // k_resolve_pending), which are separate translation units because they are compiled with different code-generation options (build.py).
 #pragma once
 

@@ -6,7 +6,7 @@ looks at all the frontiers at once, at and above it the wave walks the segments 
 AGPT_SMALL_BATCH_PATHS=0 runs the second form on batches of any size, which is what the GPU file does.
 
 The queue of n rays is cut into AGPT_FRONTIERS = 8 segments of seg_len(n) rays, a multiple of 64, and handed out in chunks of 64 from
-each segment's frontier (agpt_kernels.h, pump_issue).  What can go wrong there depends on n alone: how many segments hold rays at all,
+each segment's frontier (agpt_trace_kernels.h, pump_issue).  What can go wrong there depends on n alone: how many segments hold rays at all,
 and whether the last chunk of the last of them is a full one.  COUNTS has every combination (test_full_batch_cases.py checks that)."""
 import numpy as np
 

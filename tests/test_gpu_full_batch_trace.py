@@ -6,7 +6,7 @@ renders go through the !PEEK forms and must give the oracle's bits and, byte for
 test renders a batch of exactly 48 Mi paths on a default context, where the threshold itself selects them.
 
 Without the peek a wave that finds its segment drained walks on through all eight segments with one failing atomic each, the empty
-trailing ones of a short queue included (agpt_kernels.h, pump_issue); that walk is what the ray counts of the edge test are about.
+trailing ones of a short queue included (agpt_trace_kernels.h, pump_issue); that walk is what the ray counts of the edge test are about.
 Everything is bit-exact; there is no tolerance in this file."""
 import os
 import time
