@@ -110,7 +110,10 @@ def rays_for(desc):
 
 
 def snapshot(g, desc, prims):
-    """everything the two paths must agree on, as bytes: every mesh's BVH, closest- and any-hit records, the render and its ray totals"""
+    """everything the two paths must agree on, as bytes: every mesh's BVH, closest- and any-hit records, the render and its ray totals.
+    It calls bvh() -- agpt_mesh_get_bvh, which runs sync_mirror(s, false) -- and therefore synchronises the mirror's bounds (and the
+    spheres) at every use: after it no mesh has bounds_stale set.  A test that needs a stale flag to survive from one call into the next
+    must not observe through it (test_gpu_update_walks.py observes the device only)."""
     out = {}
     for p in prims:
         nodes, order = g.bvh(p)
